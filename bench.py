@@ -17,9 +17,13 @@ What is timed, and how:
     Infinity Cache), so a step never finds its X in cache from the previous step: the forward pass
     reads X from HBM.  (Inside one step the backward pass re-reads the X its own forward pass streamed
     a few microseconds earlier; what the cache keeps of it is part of the real workload.)
-  * The K-step timed loop (barrier + synchronize on both sides, max over ranks) is repeated until at
-    least --min-ms of device time AND --repeats loops have run; `ms_per_step` / `value` are the MEDIAN
-    loop.  `steps`, `warmup` echo the flags; `repeats` says how many K-step loops were timed.
+  * Exactly --steps steps are timed, as one uninterrupted run after --warmup untimed ones (barrier +
+    synchronize on both sides).  HIP events cut the run into --repeats consecutive pieces; `ms_per_step` /
+    `value` come from the MEDIAN piece (max over ranks).  `steps`, `warmup` echo the flags, `timed_steps`
+    counts the timed steps, `repeats` the pieces and `timed_ms_total` is the wall time of the whole run.
+  * --dump-outputs DIR: after the timed run, what its last step computed (logits, attention map, loss,
+    dX and the weight gradients, as a caller of the step receives them) is written as DIR/<name>.npy in
+    float32, at most 64 MB in all.  The inputs are seeded, so two builds can be compared output for output.
   * `roofline`: the dominant kernel (m1s_bwd_main_kernel: reads X once, writes dX once).  Its
     duration is read live, over the same steps, from a HIP event pair the library attaches to that
     dispatch (hipExtLaunchKernel start / stop events, on the launch stream).  NOTHING is subtracted:
@@ -52,7 +56,7 @@ L3_BYTES = 256 << 20    # Infinity Cache
 def parse_args():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
-    ap.add_argument('--steps', type=int, default=200)
+    ap.add_argument('--steps', type=int, default=200, help='number of timed steps of the headline workload')
     ap.add_argument('--warmup', type=int, default=20)
     ap.add_argument('--batch', type=int, default=32, help='per-GPU batch (cfg 002: 32)')
     ap.add_argument('--hw', type=int, default=14)
@@ -66,8 +70,13 @@ def parse_args():
                     help='number of (X, dX) buffer sets the steps cycle through; 0 = smallest R >= 3 with '
                          'R * (X + dX) >= 1.5 x 256 MiB (Infinity Cache); 1 = the same buffers every step')
     ap.add_argument('--min-ms', type=float, default=50.0,
-                    help='repeat the --steps-long timed loop until this much device time has been measured')
-    ap.add_argument('--repeats', type=int, default=5, help='minimum number of timed loops (median reported)')
+                    help='`extra` workloads: repeat their timed loop until this much device time has been measured')
+    ap.add_argument('--repeats', type=int, default=5,
+                    help='headline: the --steps timed steps are split into this many event-timed pieces; `extra` '
+                         'workloads: minimum number of timed loops (median reported either way)')
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR',
+                    help='after the timed steps, write the outputs of the last one as DIR/<name>.npy (float32, '
+                         '<= 64 MB in all)')
     ap.add_argument('--graph', action='store_true',
                     help='capture the step in a hipGraph (measured: replay overhead makes it slower than '
                          'eager launches for this step, so off by default); implies --rotate 1')
@@ -246,6 +255,15 @@ class HeadWorkload:
         self.cof = cof
         self.hooks = hooks
         self.i = 0
+        self._last = None
+
+    def last_outputs(self):
+        """What a caller of the step received from the last one: forward outputs, loss and every gradient."""
+        r = (self.i - 1) % self.rotate
+        st = self.steppers[r]
+        logits, att, loss = (st.logits, st.att, st.loss) if st is not None else self._last
+        return {'logits': logits, 'att': att, 'loss': loss, 'dX': self.dX[r], 'dWa': self.dWa, 'dba': self.dba,
+                'dWt': self.dWt, 'dbt': self.dbt}
 
     def compute(self, hooks=None):
         r = self.i % self.rotate
@@ -258,7 +276,8 @@ class HeadWorkload:
         logits, att, zsave, abar, _, _ = cof.attn_pool_fwd(X, X, self.Wa, self.ba, self.Wt, self.bt,
                                                            flags=self.flags, keep_prob=self.keep, seed=42,
                                                            offset=self.rng_ctr, workspace=self.ws, hooks=h)
-        _, G, _, _ = cof.softmax_xent_fwd_bwd(logits, self.labels, grad_scale=self.grad_scale)
+        lossbuf, G, _, _ = cof.softmax_xent_fwd_bwd(logits, self.labels, grad_scale=self.grad_scale)
+        self._last = (logits, att, lossbuf)
         cof.attn_pool_bwd(X, X, self.Wa, self.ba, self.Wt, self.bt, att, zsave, abar, G, flags=self.flags,
                           keep_prob=self.keep, seed=42, offset=self.rng_ctr, workspace=self.ws,
                           out=(self.dX[r], None, self.dWa, self.dba, self.dWt, self.dbt), hooks=h)
@@ -347,6 +366,53 @@ def timed_loops(step, barrier, steps, min_ms, repeats, reduce_max):
     return per, enq
 
 
+def timed_steps(step, barrier, steps, pieces, reduce_max):
+    """Exactly `steps` steps as one run between two barriers, cut into `pieces` consecutive pieces by HIP events
+    on the launch stream (no synchronisation inside the run).  Returns the seconds per step of every piece (max
+    over ranks), the wall time of the whole run (max over ranks) and the host's enqueue time per step."""
+    pieces = max(1, min(pieces, steps))
+    sizes = [steps // pieces + (1 if i < steps % pieces else 0) for i in range(pieces)]
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(pieces + 1)]
+    barrier()
+    t0 = time.perf_counter()
+    ev[0].record()
+    for i, n in enumerate(sizes):
+        for _ in range(n):
+            step()
+        ev[i + 1].record()
+    t_enq = time.perf_counter() - t0
+    barrier()
+    wall = reduce_max(time.perf_counter() - t0)
+    per = [reduce_max(ev[i].elapsed_time(ev[i + 1]) * 1e-3) / n for i, n in enumerate(sizes)]
+    return per, wall, t_enq / steps
+
+
+def dump_outputs(arrays, out_dir, budget=64 * 1000 * 1000):
+    """Write every array as out_dir/<name>.npy in float32, at most `budget` bytes in all.  Smallest first, each
+    array is written whole if it fits its even share of the budget still left; otherwise a fixed sample of its
+    flat elements (the first `share` of a randperm drawn from a generator seeded with 0, in index order) is
+    written, the same elements on every run of the same shapes.  Returns {name: shape and count} for the line."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    torch.cuda.synchronize()
+    items = sorted(arrays.items(), key=lambda kv: (kv[1].numel(), kv[0]))
+    left = budget - 128 * len(items)            # .npy headers
+    info = {}
+    for i, (name, t) in enumerate(items):
+        flat = t.detach().reshape(-1)
+        share = left // (len(items) - i)
+        if flat.numel() * 4 <= share:
+            a = t.detach().float().cpu().numpy()
+        else:
+            g = torch.Generator(device=flat.device).manual_seed(0)
+            idx = torch.randperm(flat.numel(), generator=g, device=flat.device)[:share // 4].sort().values
+            a = flat[idx].float().cpu().numpy()
+        np.save(os.path.join(out_dir, name + '.npy'), a)
+        left -= a.nbytes
+        info[name] = {'shape': list(t.shape), 'saved_elements': int(a.size)}
+    return info
+
+
 def kernel_times(cof, work, step_with_hooks, barrier, n, base_hooks=None):
     """Durations of the two streaming kernels over n live steps: dispatch begin -> end timestamps
     attached by hipExtLaunchKernel (see include/apa.h, apa_hooks.prof_*)."""
@@ -371,6 +437,8 @@ def main():
     if world != args.gpus:
         raise SystemExit('bench.py --gpus {} started with WORLD_SIZE={}: the two must agree (one process per '
                          'GPU)'.format(args.gpus, world))
+    if args.steps < 1:
+        raise SystemExit('bench.py: --steps must be at least 1')
     real_stdout = _claim_stdout()
     assert torch.cuda.is_available(), 'bench.py needs an MI355X (no CPU fallback for the product path)'
     if args.comm == 'gloo':                      # ranks may share a GPU in this mode
@@ -561,10 +629,14 @@ def main():
                     st.hooks = None
     for _ in range(args.warmup):
         step()
-    per, enq = timed_loops(step, barrier, args.steps, args.min_ms, args.repeats, reduce_max)
+    per, wall, enq = timed_steps(step, barrier, args.steps, args.repeats, reduce_max)
     sec = _median(per)
-    print('host enqueue {:.1f} us/step, wall {:.1f} us/step (median of {} loops, min {:.1f} max {:.1f})'.format(
-        _median(enq) * 1e6, sec * 1e6, len(per), min(per) * 1e6, max(per) * 1e6), file=sys.stderr)
+    print('host enqueue {:.1f} us/step, {:.1f} us/step (median of {} pieces, min {:.1f} max {:.1f}), {} steps in '
+          '{:.3f} ms'.format(enq * 1e6, sec * 1e6, len(per), min(per) * 1e6, max(per) * 1e6, args.steps, wall * 1e3),
+          file=sys.stderr)
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        dumped = dump_outputs(work.last_outputs(), args.dump_outputs)
 
     # ---- streaming-kernel durations: dispatch timestamps, live over the same steps (eager launches) ----
     kt_steps = max(20, min(args.steps, 200))
@@ -637,8 +709,9 @@ def main():
             'vs_baseline': None,
             'dtype': args.dtype,
             'data': 'synthetic',
+            'timed_steps': args.steps,
             'repeats': len(per),
-            'timed_ms_total': round(sum(per) * args.steps * 1e3, 3),
+            'timed_ms_total': round(wall * 1e3, 3),
             'ms_per_step_min_max': [round(min(per) * 1e3, 5), round(max(per) * 1e3, 5)],
             'config': {
                 'workload': workload,
@@ -682,6 +755,8 @@ def main():
             },
             'step_roofline_frac': round((3.0 * N * P * C * esz) / sec / 1e9 / HBM_PEAK_GBS, 4),
         }
+        if dumped is not None:
+            out['dump_outputs'] = {'dir': args.dump_outputs, 'arrays': dumped}
 
     # ---- the other BASELINE configs, same process, same timing discipline (N = 1 only) ----
     if world == 1 and dist is None and not args.no_extra and out is not None:

@@ -20,6 +20,33 @@ PRE = 'PosePrelogitsBasedAttention/'
 P = 'USE_POSE_PRELOGITS_BASED_ATTENTION'
 
 
+def experiment_yaml(name, dst_dir):
+    """Write the shipped experiment `name` (e.g. '002_MPII_ResNet_withAttention.yaml') as a YAML file in dst_dir and
+    return its path.  Rebuilt from tests/golden/config_reference.json, which holds the reference's own merged table
+    of every shipped experiment next to its defaults: the file sets exactly the keys whose merged value differs
+    from the default (value or type), so loading it over the defaults must give that table back."""
+    import yaml
+    ref = json.load(open(os.path.join(GOLD, 'config_reference.json')))
+    dflt, table = ref['defaults'], ref['experiments'][name]
+    tree = {}
+    for k, v in sorted(table.items()):
+        if k in dflt and dflt[k] == v and type(dflt[k]) is type(v):
+            continue
+        node = tree
+        parts = k.split('.')
+        for p in parts[:-1]:
+            node = node.setdefault(p, {})
+        node[parts[-1]] = v
+    path = os.path.join(str(dst_dir), name)
+    with open(path, 'w') as f:
+        yaml.safe_dump(tree, f, default_flow_style=False)
+    return path
+
+
+def experiment_names():
+    return sorted(json.load(open(os.path.join(GOLD, 'config_reference.json')))['experiments'])
+
+
 def head_fixture_paths():
     return sorted(glob.glob(os.path.join(GOLD, 'ref_head_*.npz')))
 

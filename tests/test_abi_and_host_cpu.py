@@ -208,13 +208,15 @@ def _flat(d, pre=''):
     return out
 
 
-def test_config_table_matches_the_reference_s_own_config_module():
+def test_config_table_matches_the_reference_s_own_config_module(tmp_path):
     """tests/golden/config_reference.json was produced by EXECUTING the reference's src/config.py (defaults, and
     cfg_from_file on each of the seven shipped experiments/*.yaml; tests/golden/make_config_reference.py).
-    Every key of the reference exists here with the same default, and -- where the reference tree is mounted --
-    loading each YAML through this package's loader gives the same merged table."""
+    Every key of the reference exists here with the same default, and loading each experiment through this
+    package's YAML loader (the file rebuilt from the fixture: _ref_fixture.experiment_yaml) gives the same merged
+    table."""
     import json
     from attentionalpoolingaction_amd import config as apa_config
+    from _ref_fixture import experiment_yaml
     ref = json.load(open(os.path.join(GOLD, 'config_reference.json')))
     mine = _flat(apa_config.reset_cfg())
     assert set(ref['defaults']) == set(mine)
@@ -222,9 +224,7 @@ def test_config_table_matches_the_reference_s_own_config_module():
         assert mine[k] == v or (isinstance(v, float) and mine[k] == pytest.approx(v, abs=1e-15)), k
     assert len(ref['experiments']) == 7
     for name, table in ref['experiments'].items():
-        path = os.path.join('/root/reference/experiments', name)
-        if not os.path.exists(path):
-            continue
+        path = experiment_yaml(name, tmp_path)
         apa_config.reset_cfg()
         got = _flat(apa_config.cfg_from_file(path))
         assert set(got) == set(table), name
@@ -303,10 +303,9 @@ def test_config_loads_reference_style_yaml(tmp_path):
     apa_config.reset_cfg()
 
 
-@pytest.mark.skipif(not os.path.isdir('/root/reference/experiments'), reason='reference tree not mounted')
-def test_config_loads_every_shipped_experiment_unchanged():
-    import glob
-    files = sorted(glob.glob('/root/reference/experiments/*.yaml'))
+def test_config_loads_every_shipped_experiment_unchanged(tmp_path):
+    from _ref_fixture import experiment_names, experiment_yaml
+    files = [experiment_yaml(name, tmp_path) for name in experiment_names()]
     assert len(files) >= 7
     for f in files:
         cfg = apa_config.reset_cfg()

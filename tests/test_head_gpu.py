@@ -1227,16 +1227,14 @@ def test_device_label_path_bit_exact_vs_host_functions(gpu):
     assert int(st[0]) == 1
 
 
-def test_cfg001_baseline_head_matches_oracle(gpu):
+def test_cfg001_baseline_head_matches_oracle(gpu, tmp_path):
     """BASELINE configs[0] (001_MPII_ResNet.yaml, no attention, eval batch 1): the shipped YAML loads
     unchanged and network_fn returns global-average-pool + logits (resnet_v1.py:206-217)."""
     from attentionalpoolingaction_amd import config as apa_config, nets_factory
-    ref_yaml = '/root/reference/experiments/001_MPII_ResNet.yaml'
+    from _ref_fixture import experiment_yaml
     cfg = apa_config.reset_cfg()
-    if os.path.exists(ref_yaml):
-        apa_config.cfg_from_file(ref_yaml)
-    else:   # the GPU box has no reference tree: the same keys by hand
-        apa_config.cfg_from_dict({'MODEL_NAME': 'resnet_v1_101', 'TEST': {'BATCH_SIZE': 1}})
+    apa_config.cfg_from_file(experiment_yaml('001_MPII_ResNet.yaml', tmp_path))
+    assert cfg.MODEL_NAME == 'resnet_v1_101' and cfg.TEST.BATCH_SIZE == 1
     assert not cfg.NET.USE_POSE_PRELOGITS_BASED_ATTENTION
     fn = nets_factory.get_network_fn('resnet_v1_101', 393, 16, cfg, is_training=False, device=gpu)
     g = torch.Generator().manual_seed(3)
@@ -1285,21 +1283,17 @@ def test_cfg001_baseline_head_matches_oracle(gpu):
     apa_config.reset_cfg()
 
 
-def test_yaml_driven_training_loop_matches_cpu_reference_loop(gpu):
+def test_yaml_driven_training_loop_matches_cpu_reference_loop(gpu, tmp_path):
     """The pieces together the way src/train.py drives them: cfg 002 YAML -> network_fn -> gen_losses
     -> flat gradient bucket -> ITER_SIZE accumulation (averaged, train.py:547-566) -> fused
     momentum-SGD with L2 on the conv weights and the staircase learning rate.  Three parameter updates
     on a fixed synthetic batch must land where the same loop on the CPU oracle + torch.optim.SGD
     lands (dropout off: cfg.NET.DROPOUT = 0, so both loops are deterministic)."""
     from attentionalpoolingaction_amd import config as apa_config, deploy, loss as apa_loss, nets_factory
-    ref_yaml = '/root/reference/experiments/002_MPII_ResNet_withAttention.yaml'
+    from _ref_fixture import experiment_yaml
     cfg = apa_config.reset_cfg()
-    if os.path.exists(ref_yaml):
-        apa_config.cfg_from_file(ref_yaml)
-    else:
-        apa_config.cfg_from_dict({'MODEL_NAME': 'resnet_v1_101', 'TRAIN': {'ITER_SIZE': 2}, 'NET': {
-            'USE_POSE_PRELOGITS_BASED_ATTENTION': True,
-            'USE_POSE_PRELOGITS_BASED_ATTENTION_SINGLE_LAYER_ATT': True}})
+    apa_config.cfg_from_file(experiment_yaml('002_MPII_ResNet_withAttention.yaml', tmp_path))
+    assert cfg.NET.USE_POSE_PRELOGITS_BASED_ATTENTION and cfg.NET.USE_POSE_PRELOGITS_BASED_ATTENTION_SINGLE_LAYER_ATT
     apa_config.cfg_from_dict({'NET': {'DROPOUT': 0.0}})
     assert cfg.TRAIN.ITER_SIZE == 2 and apa_config.dropout_keep_prob(cfg) == 1.0
     K, N, wd, lr0 = 10, 8, cfg.TRAIN.WEIGHT_DECAY, 5e-3
@@ -1382,6 +1376,52 @@ def test_bench_two_ranks_sharing_one_gpu_over_gloo(gpu, launcher):
     assert cd['allreduce_us'] > 0 and cd['overlap'] in ('on', 'off')
 
 
+def test_bench_dump_outputs_are_the_last_step_and_repeat_run_to_run(gpu, tmp_path):
+    """bench.py --dump-outputs DIR: the last timed step's outputs as float32 .npy files (<= 64 MB in all), from
+    seeded inputs -- two runs with the same arguments write the same arrays, and they belong to one step: the
+    per-example losses, their mean and the top-down bias gradient follow from the dumped logits and attention
+    map and the labels the bench draws."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    dumps = []
+    for run in range(2):
+        d_out = tmp_path / ('run%d' % run)
+        out = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--steps', '7', '--warmup', '2',
+                              '--no-extra', '--no-cpu-baseline', '--dump-outputs', str(d_out)],
+                             capture_output=True, text=True, timeout=600, cwd=root)
+        assert out.returncode == 0, out.stderr[-2000:]
+        line = json.loads([l for l in out.stdout.splitlines() if l.strip()][-1])
+        assert line['timed_steps'] == 7 and line['dump_outputs']['dir'] == str(d_out)
+        files = sorted(glob.glob(str(d_out / '*.npy')))
+        assert {os.path.basename(f)[:-4] for f in files} == {'logits', 'att', 'loss', 'dX', 'dWa', 'dba', 'dWt', 'dbt'}
+        assert sum(os.path.getsize(f) for f in files) <= 64 * 1000 * 1000
+        arrs = {os.path.basename(f)[:-4]: np.load(f) for f in files}
+        assert all(a.dtype == np.float32 for a in arrs.values())
+        assert arrs['logits'].shape == (32, 393) and arrs['dX'].shape == (32, 196, 2048)
+        assert all(np.isfinite(a).all() for a in arrs.values())
+        dumps.append(arrs)
+    a, b = dumps
+    for k in a:
+        np.testing.assert_allclose(a[k], b[k], rtol=1e-5, atol=1e-6 * float(np.abs(a[k]).max() + 1e-30), err_msg=k)
+    # the labels bench.py draws (HeadWorkload: the replicated-weight generator, seed 42, after Wa and Wt)
+    gw = torch.Generator().manual_seed(42)
+    torch.randn(2048, 1, generator=gw)
+    torch.randn(2048, 393, generator=gw)
+    labels = torch.randint(0, 393, (32,), generator=gw).numpy()
+    logits = a['logits'].astype(np.float64)
+    lse = np.log(np.exp(logits - logits.max(1, keepdims=True)).sum(1)) + logits.max(1)
+    xent = lse - logits[np.arange(32), labels]
+    np.testing.assert_allclose(a['loss'][1:], xent, rtol=1e-4, atol=1e-5)
+    assert abs(a['loss'][0] - xent.mean()) < 1e-4 * xent.mean()
+    # logits = mean_p att * (feats Wt + bt)  =>  dbt = sum_n (softmax - onehot)_n * mean_p att_n / N
+    G = np.exp(logits - lse[:, None])
+    G[np.arange(32), labels] -= 1.0
+    dbt = (G * a['att'].astype(np.float64).reshape(32, -1).mean(1)[:, None]).sum(0) / 32
+    np.testing.assert_allclose(a['dbt'], dbt, rtol=0, atol=1e-4 * np.abs(dbt).max())
+
+
 def test_bench_prints_one_json_line_with_the_contract_fields(gpu):
     """bench.py's stdout contract: exactly one JSON line carrying the driver's fields plus the
     `roofline` and `cpu_baseline` objects; also through the N > 1 code path (1-rank RCCL group)."""
@@ -1412,7 +1452,9 @@ def test_bench_prints_one_json_line_with_the_contract_fields(gpu):
         r = d['roofline']
         assert r['bound'] == 'hbm' and r['unit'] == 'GB/s' and abs(r['frac'] - r['achieved'] / r['peak']) < 1e-3
         assert 0.2 < r['frac'] < 1.0 and d['value'] > 2000          # BASELINE target: >= 2000 img/s
-        assert d['repeats'] >= 5 and d['timed_ms_total'] >= 50.0       # >= 50 ms measured, median of >= 5 loops
+        # exactly --steps timed steps, one run cut into >= 5 event-timed pieces (median reported)
+        assert d['timed_steps'] == d['steps'] == 20 and d['repeats'] >= 5
+        assert d['timed_ms_total'] >= 0.9 * 20 * d['ms_per_step'] and min(d['ms_per_step_min_max']) > 0
         assert 'rotated over' in d['config']['workload'] and r['timer'].startswith('hipExtLaunchKernel') and (r['rocprofv3'] is None or 0.3 < r['rocprofv3']['frac'] < 1.0)
         assert d['roofline_fwd']['kernel'] == 'm1s_pool_fwd_kernel' and 0.2 < d['roofline_fwd']['frac'] < 1.0
         if '--no-cpu-baseline' not in extra:
