@@ -107,6 +107,19 @@ _SIGNATURES = {
                                                                     ctypes.c_uint64, c_int, c_void_p]),
     'apa_accumulate_gradients': (c_int, [c_void_p, POINTER(c_void_p), c_int, c_size_t, c_float, c_void_p]),
     'apa_accumulate_gradients_div': (c_int, [c_void_p, POINTER(c_void_p), c_int, c_size_t, c_float, c_void_p]),
+    'apa_pose_att_logits_workspace_bytes': (c_size_t, [c_int] * 5),
+    'apa_pose_att_logits_fwd': (c_int, [c_void_p, c_void_p, POINTER(ctypes.c_int32), c_int, c_int] + [c_void_p] * 5 +
+                                [c_size_t] + [c_int] * 5 + [c_uint, c_float, ctypes.c_uint64, ctypes.c_uint64, c_int,
+                                                            c_void_p]),
+    'apa_pose_att_logits_bwd': (c_int, [c_void_p, c_void_p, POINTER(ctypes.c_int32), c_int, c_int] + [c_void_p] * 4 +
+                                [c_int] + [c_void_p] * 4 + [c_size_t] + [c_int] * 5 +
+                                [c_uint, c_float, ctypes.c_uint64, ctypes.c_uint64, c_int, c_void_p]),
+    'apa_pose_att_logits_fwd_ex': (c_int, [c_void_p, c_void_p, c_void_p, POINTER(ctypes.c_int32), c_int, c_int] +
+                                   [c_void_p] * 5 + [c_size_t] + [c_int] * 5 +
+                                   [c_uint, c_float, ctypes.c_uint64, ctypes.c_uint64, c_int, c_void_p]),
+    'apa_pose_att_logits_bwd_ex': (c_int, [c_void_p, c_void_p, c_void_p, POINTER(ctypes.c_int32), c_int, c_int] +
+                                   [c_void_p] * 4 + [c_int] + [c_void_p] * 4 + [c_size_t] + [c_int] * 5 +
+                                   [c_uint, c_float, ctypes.c_uint64, ctypes.c_uint64, c_int, c_void_p]),
     'apa_prof_event_create': (c_int, [POINTER(c_void_p)]),
     'apa_prof_event_destroy': (c_int, [c_void_p]),
     'apa_prof_event_record': (c_int, [c_void_p, c_void_p]),
@@ -518,6 +531,86 @@ def pose_head_bwd(X, W1, W2, Ppre, dPl, dPpre_ext, *, dX=None, accumulate_dX=Fal
         workspace.data_ptr(), workspace.numel(), N, P, C, Cp, J, dt, _stream_ptr())
     _check(rc, 'apa_pose_head_bwd')
     return dX, dW1, db1, dW2, db2
+
+
+# --------------------------------------------------------------------------------------------
+# pose-heatmap attention head (cfg.NET.USE_POSE_ATTENTION_LOGITS, nets_factory.py:162-189)
+# --------------------------------------------------------------------------------------------
+def pose_att_num_maps(sel, avged) -> int:
+    """M = the selected parts + the averaged map (if any) + the constant map"""
+    return len(sel) + (1 if avged else 0) + 1
+
+
+def _sel_array(sel):
+    arr = (ctypes.c_int32 * max(len(sel), 1))(*[int(j) for j in sel])
+    return arr, len(sel)
+
+
+def pose_att_logits_workspace(N, P, C, M, K, device, workspace=None) -> torch.Tensor:
+    need = int(load_library().apa_pose_att_logits_workspace_bytes(N, P, C, M, K))
+    if workspace is None or workspace.numel() < need:
+        workspace = torch.empty((max(need, 16),), dtype=torch.uint8, device=device)
+    return workspace
+
+
+def pose_att_logits_fwd(X, Pl, sel, avged, W, b, *, flags=0, keep_prob=1.0, seed=0, offset=0, workspace=None,
+                        hooks=None):
+    """F [N, M*C] f32, logits [N,K] f32, workspace = pose_att_logits_fwd(X [N,..,C], Pl [N,..,J] f32, sel (host
+    list of part indices in [0, J)), avged, W [M*C, K], b [K]) -- apa_pose_att_logits_fwd.  `seed` a KeepMask:
+    the replayed mask over F's flat index (APA_FLAG_RNG_EXTERNAL)."""
+    lib = load_library()
+    N, C, J = X.shape[0], X.shape[-1], Pl.shape[-1]
+    P = X.numel() // (N * C)
+    M = pose_att_num_maps(sel, avged)
+    K = W.shape[-1]
+    if W.numel() != M * C * K or Pl.numel() != N * P * J:
+        raise ApaError('pose_att_logits_fwd: W must be [M*C = {}, K] and Pl [N*P = {}, J]'.format(M * C, N * P))
+    workspace = pose_att_logits_workspace(N, P, C, M, K, X.device, workspace)
+    F = torch.empty((N, M * C), dtype=torch.float32, device=X.device)
+    logits = torch.empty((N, K), dtype=torch.float32, device=X.device)
+    s, o, fl = _rng_key(seed, offset, flags)
+    arr, n_sel = _sel_array(sel)
+    args = (_dev_ptr(X, 'X'), _dev_ptr(Pl, 'Pl', torch.float32), arr, n_sel, 1 if avged else 0,
+            _dev_ptr(W, 'W', torch.float32), _dev_ptr(b, 'b', torch.float32), F.data_ptr(), logits.data_ptr(),
+            workspace.data_ptr(), workspace.numel(), N, P, C, J, K, fl, float(keep_prob), s, o, _feat_dtype(X),
+            _stream_ptr())
+    if hooks is not None:
+        rc = lib.apa_pose_att_logits_fwd_ex(_hooks_ptr(hooks), *args)
+    else:
+        rc = lib.apa_pose_att_logits_fwd(*args)
+    _check(rc, 'apa_pose_att_logits_fwd')
+    return F, logits, workspace
+
+
+def pose_att_logits_bwd(X, Pl, sel, avged, W, F, G, dPl, *, dX=None, accumulate_dX=False, flags=0, keep_prob=1.0,
+                        seed=0, offset=0, workspace=None, hooks=None):
+    """dX, dPl, dW, db = pose_att_logits_bwd(...).  dPl [N,..,J] f32 is ACCUMULATED into (pass the pose-loss
+    gradient, or zeros); dX is overwritten, or added to with accumulate_dX (then dX must be given)."""
+    lib = load_library()
+    N, C, J = X.shape[0], X.shape[-1], Pl.shape[-1]
+    P = X.numel() // (N * C)
+    M = pose_att_num_maps(sel, avged)
+    K = W.shape[-1]
+    workspace = pose_att_logits_workspace(N, P, C, M, K, X.device, workspace)
+    if dX is None:
+        if accumulate_dX:
+            raise ApaError('accumulate_dX needs an existing dX buffer')
+        dX = torch.empty_like(X)
+    dW = torch.empty_like(W)
+    db = torch.empty((K,), dtype=torch.float32, device=X.device)
+    s, o, fl = _rng_key(seed, offset, flags)
+    arr, n_sel = _sel_array(sel)
+    args = (_dev_ptr(X, 'X'), _dev_ptr(Pl, 'Pl', torch.float32), arr, n_sel, 1 if avged else 0,
+            _dev_ptr(W, 'W', torch.float32), _dev_ptr(F, 'F', torch.float32), _dev_ptr(G, 'G', torch.float32),
+            _dev_ptr(dX, 'dX', X.dtype), 1 if accumulate_dX else 0, _dev_ptr(dPl, 'dPl', torch.float32),
+            dW.data_ptr(), db.data_ptr(), workspace.data_ptr(), workspace.numel(), N, P, C, J, K, fl,
+            float(keep_prob), s, o, _feat_dtype(X), _stream_ptr())
+    if hooks is not None:
+        rc = lib.apa_pose_att_logits_bwd_ex(_hooks_ptr(hooks), *args)
+    else:
+        rc = lib.apa_pose_att_logits_bwd(*args)
+    _check(rc, 'apa_pose_att_logits_bwd')
+    return dX, dPl, dW, db
 
 
 # --------------------------------------------------------------------------------------------

@@ -739,7 +739,10 @@ class FusedHeadStep:
 
     @staticmethod
     def unsupported_reason(head, cfg, network_fn=None) -> str:
+        from . import nets_factory
         tr = cfg.TRAIN
+        if isinstance(head, nets_factory.PoseAttentionLogitsHead):
+            return 'the pose-heatmap attention head (USE_POSE_ATTENTION_LOGITS) trains through network_fn and autograd'
         if not head.is_training:
             return 'a training-mode head is required'
         if head.rank != 1 or head.with_pose_feat or head.want_topdown:

@@ -8,6 +8,9 @@ map `last_conv` [N,H,W,C] (NHWC, float32 or bfloat16, resident in HBM) directly.
 runs in hand-written HIP (libapa_hip.so) through torch.autograd.Function wrappers -- torch only
 carries device memory, the stream and the autograd graph.
 
+Heads: USE_POSE_ATTENTION_LOGITS (:162-189, PoseAttentionLogitsHead), USE_POSE_PRELOGITS_BASED_ATTENTION (:242-352,
+AttentionalPoolingHead), neither (cfg 001, BaselineHead).  USE_POSE_LOGITS_DIRECTLY[_v2] and
+USE_COMPACT_BILINEAR_POOLING (:193-241) are refused with a ValueError.
 End-point names are the reference's: 'PoseLogits' (:160), 'PosePrelogitsBasedAttention' (:287),
 'TopDownAttention' (:309, on request), 'Logits' (:352), 'logits_beforePool' (:357).
 Parameter names map 1:1 onto the TF variable names.
@@ -16,6 +19,7 @@ from __future__ import annotations
 
 from typing import Callable, Dict, Optional, Tuple
 
+import numpy as np
 import torch
 import torch.nn as nn
 
@@ -666,6 +670,163 @@ class AttentionalPoolingHead(nn.Module):
         return logits, end_points
 
 
+class PoseAttentionLogitsFunction(torch.autograd.Function):
+    """USE_POSE_ATTENTION_LOGITS in one autograd node: PoseLogits head -> M attention-weighted spatial means of
+    last_conv (the selected parts, their mean, a constant map) -> dropout -> 'PoseAttention/Conv'.
+    logits, Pl = f(X, Xpose, W1, b1, W2, b2, W, b); `Xpose is None`: the pose head reads X itself.
+
+    One node, so that the pose-loss gradient and the attention gradient of Pl meet inside the backward pass
+    (apa_pose_att_logits_bwd accumulates into the pose-loss dPl) and the pose head runs its backward once, adding
+    its dX into the pooling op's buffer when the two taps are the same tensor."""
+
+    @staticmethod
+    def forward(ctx, X, Xpose, W1, b1, W2, b2, W, b, sel, avged, flags, keep_prob, seed, offset):
+        Xc = X.contiguous()
+        shared = Xpose is None
+        Xp = Xc if shared else Xpose.contiguous()
+        W1c, W2c, Wc = W1.contiguous(), W2.contiguous(), W.contiguous()
+        Ppre, Pl, pws = cof.pose_head_fwd(Xp, W1c, b1.contiguous(), W2c, b2.contiguous())
+        F, logits, aws = cof.pose_att_logits_fwd(Xc, Pl, sel, avged, Wc, b.contiguous(), flags=flags,
+                                                 keep_prob=keep_prob, seed=seed, offset=offset)
+        ctx.save_for_backward(Xc, Xp, W1c, W2c, Ppre, Pl, Wc, F)
+        ctx.shared = shared
+        ctx.cfg = (sel, avged, flags, keep_prob, seed, offset)
+        ctx.ws = (pws, aws)
+        ctx.shapes = (X.shape, None if shared else Xpose.shape)
+        ctx.set_materialize_grads(False)
+        return logits, Pl
+
+    @staticmethod
+    def backward(ctx, dlogits, dPl):
+        Xc, Xp, W1, W2, Ppre, Pl, W, F = ctx.saved_tensors
+        sel, avged, flags, keep_prob, seed, offset = ctx.cfg
+        pws, aws = ctx.ws
+        if dlogits is None and dPl is None:
+            return (None,) * 14
+        dPl_acc = torch.zeros_like(Pl) if dPl is None else dPl.contiguous().float().clone()
+        dX = dW = db = None
+        if dlogits is not None:
+            dX, dPl_acc, dW, db = cof.pose_att_logits_bwd(
+                Xc, Pl, sel, avged, W, F, dlogits.contiguous().float(), dPl_acc, flags=flags, keep_prob=keep_prob,
+                seed=seed, offset=offset, workspace=aws)
+        xs, xps = ctx.shapes
+        if ctx.shared:
+            dX, dW1, db1, dW2, db2 = cof.pose_head_bwd(Xc, W1, W2, Ppre, dPl_acc, None, dX=dX,
+                                                       accumulate_dX=dX is not None, workspace=pws, ws_from_fwd=True)
+            dXp = None
+        else:
+            dXp, dW1, db1, dW2, db2 = cof.pose_head_bwd(Xp, W1, W2, Ppre, dPl_acc, None, workspace=pws,
+                                                        ws_from_fwd=True)
+            dXp = dXp.view(xps)
+        return (None if dX is None else dX.view(xs), dXp, dW1, db1, dW2, db2, dW, db,
+                None, None, None, None, None, None)
+
+
+def pose_attention_parts(dims, num_parts: int):
+    """The part indices cfg.NET.USE_POSE_ATTENTION_LOGITS_DIMS selects (nets_factory.py:168-172): all parts in order
+    for the default [-1], else `np.array(parts)[DIMS]` -- numpy indexing: negative indices wrap, repeats are allowed,
+    [] selects nothing, an index out of range is an error.  Returned normalised to [0, num_parts)."""
+    dims = list(dims)
+    if dims == [-1]:
+        return list(range(num_parts))
+    idx = np.asarray(dims, dtype=np.int64).reshape(-1)
+    bad = [int(d) for d in idx if not -num_parts <= int(d) < num_parts]
+    if bad:
+        raise ValueError('USE_POSE_ATTENTION_LOGITS_DIMS: index %s out of range for %d pose parts' % (bad, num_parts))
+    return [int(j) for j in np.arange(num_parts)[idx]]
+
+
+class PoseAttentionLogitsHead(nn.Module):
+    """PoseLogits head + the `USE_POSE_ATTENTION_LOGITS` head (nets_factory.py:147-189) as a module: the predicted
+    keypoint heat-maps (raw logits, no activation) used directly as attention maps.
+
+    Parameters (attribute -> TF variable name), reference initialisers in brackets:
+      pose_w1 [C,768], pose_b1          PoseLogits/ExtraConv2d_1x1/{weights,biases}   [N(0,1e-3), 0]
+      pose_w2 [768,J], pose_b2          PoseLogits/Conv2d_1c_1x1/{weights,biases}     [variance scaling, 0]
+      logits_weights [M*C,K], logits_biases   PoseAttention/Conv/{weights,biases}     [N(0,1e-3), 0]
+    M = the selected parts (USE_POSE_ATTENTION_LOGITS_DIMS) + 1 with ..._AVGED_HMAP + 1 (the plain spatial mean).
+    The pose head is always evaluated: the attention maps are its output.
+    """
+
+    TF_NAMES = {
+        'pose_w1': 'PoseLogits/ExtraConv2d_1x1/weights', 'pose_b1': 'PoseLogits/ExtraConv2d_1x1/biases',
+        'pose_w2': 'PoseLogits/Conv2d_1c_1x1/weights', 'pose_b2': 'PoseLogits/Conv2d_1c_1x1/biases',
+        'logits_weights': 'PoseAttention/Conv/weights', 'logits_biases': 'PoseAttention/Conv/biases',
+    }
+
+    def __init__(self, num_classes: int, cfg, in_channels: int = 2048, num_pose_keypoints: int = 16,
+                 is_training: bool = False, seed: int = 42, pose_in_channels: Optional[int] = None,
+                 arg_scope: str = 'resnet', want_topdown: bool = False):
+        super().__init__()
+        net = cfg.NET
+        if not net.USE_POSE_ATTENTION_LOGITS:
+            raise ValueError('PoseAttentionLogitsHead needs cfg.NET.USE_POSE_ATTENTION_LOGITS')
+        if want_topdown:
+            raise ValueError('the pose-attention head has no TopDownAttention end point')
+        self.arg_scope = arg_scope
+        self.num_classes = num_classes
+        self.in_channels = in_channels
+        J = max(num_pose_keypoints, 1)
+        self.parts = pose_attention_parts(net.USE_POSE_ATTENTION_LOGITS_DIMS, J)
+        self.avged = bool(net.USE_POSE_ATTENTION_LOGITS_AVGED_HMAP)
+        self.num_maps = cof.pose_att_num_maps(self.parts, self.avged)
+        self.keep_prob = dropout_keep_prob(cfg)
+        self.is_training = is_training
+        self.seed = seed
+        self._step = 0
+        self._replay_mask = None
+        cp = AttentionalPoolingHead.POSE_PRELOGITS
+        self.pose_w1 = nn.Parameter(torch.randn(pose_in_channels or in_channels, cp) * 0.001)
+        self.pose_b1 = nn.Parameter(torch.zeros(cp))
+        # slim.variance_scaling_initializer(): truncated normal, std = sqrt(1.3 * 2 / fan_in)
+        self.pose_w2 = nn.Parameter(torch.nn.init.trunc_normal_(
+            torch.empty(cp, J), 0.0, 1.0, -2.0, 2.0) * (2.6 / cp) ** 0.5)
+        self.pose_b2 = nn.Parameter(torch.zeros(J))
+        self.logits_weights = nn.Parameter(torch.randn(self.num_maps * in_channels, num_classes) * 0.001)
+        self.logits_biases = nn.Parameter(torch.zeros(num_classes))
+
+    def tf_variable_names(self):
+        return dict(self.TF_NAMES)
+
+    def regularized_weights(self):
+        """conv weights carry slim.l2_regularizer from the backbone's arg-scope; biases do not"""
+        return [self.pose_w1, self.pose_w2, self.logits_weights]
+
+    def replay_dropout_mask(self, keep_mask: Optional[torch.Tensor]) -> None:
+        """Use an externally drawn dropout mask for the NEXT training-mode forward (and its backward): the {0,1}
+        tensor tf.nn.dropout multiplies the concatenated means with, [N,1,1,M*C] (or [N,M*C]).  One-shot; None
+        clears it (APA_FLAG_RNG_EXTERNAL)."""
+        self._replay_mask = keep_mask
+
+    def get_extra_state(self):
+        return {'dropout_step': int(self._step)}
+
+    def set_extra_state(self, state):
+        self._step = int(state.get('dropout_step', 0)) if state else 0
+
+    def forward(self, last_conv: torch.Tensor, last_conv_pose: Optional[torch.Tensor] = None
+                ) -> Tuple[torch.Tensor, Dict[str, torch.Tensor]]:
+        """`last_conv_pose`: the pose head's own tap when cfg.NET.LAST_CONV_MAP_FOR_POSE names another end point
+        (nets_factory.py:148-150); None / the same tensor: the shared tap."""
+        seed = self.seed
+        if self._replay_mask is not None and self.is_training:
+            seed = cof.pack_keep_mask(self._replay_mask, device=self.logits_weights.device)
+        self._replay_mask = None
+        offset = self._step
+        if self.is_training:
+            self._step += 1            # a fresh dropout mask per step
+        pose_in = None if (last_conv_pose is None or last_conv_pose is last_conv) else last_conv_pose
+        flags = cof.attn_flags(is_training=self.is_training)
+        logits, pose_logits = PoseAttentionLogitsFunction.apply(
+            last_conv, pose_in, self.pose_w1, self.pose_b1, self.pose_w2, self.pose_b2, self.logits_weights,
+            self.logits_biases, self.parts, self.avged, flags, self.keep_prob if self.is_training else 1.0, seed,
+            offset)
+        end_points: Dict[str, torch.Tensor] = EndPoints()
+        end_points['PoseLogits'] = pose_logits                                   # :160
+        end_points['Logits'] = logits                                            # :352
+        return logits, end_points
+
+
 class SpatialMeanFunction(torch.autograd.Function):
     """z [N,C] f32 = mean over the spatial positions of X [N,H,W,C] (resnet_v1.py:206-208), in HIP both ways:
     forward = the pooling pass with a constant attention map (one streaming read of X; its `zsave` output),
@@ -841,7 +1002,19 @@ def get_network_fn(name: str, num_classes: int, num_pose_keypoints: int, cfg,
         backbone.module = net
     else:
         fuse_final_relu = False
-    if cfg.NET.USE_POSE_PRELOGITS_BASED_ATTENTION:
+    # the reference's if/elif chain (nets_factory.py:162-242): the first flag set picks the head
+    if cfg.NET.USE_POSE_ATTENTION_LOGITS:
+        head_kwargs.pop('fuse_pose_attention', None)
+        head_kwargs.pop('with_pose_logits', None)
+        head = PoseAttentionLogitsHead(num_classes, cfg, in_channels=channels,
+                                       num_pose_keypoints=num_pose_keypoints, is_training=is_training,
+                                       seed=head_seed, **head_kwargs).to(device)
+    elif cfg.NET.USE_POSE_LOGITS_DIRECTLY or cfg.NET.USE_POSE_LOGITS_DIRECTLY_v2 or \
+            cfg.NET.USE_COMPACT_BILINEAR_POOLING:
+        flag = next(f for f in ('USE_POSE_LOGITS_DIRECTLY', 'USE_POSE_LOGITS_DIRECTLY_v2',
+                                'USE_COMPACT_BILINEAR_POOLING') if cfg.NET[f])
+        raise ValueError('cfg.NET.%s (nets_factory.py:193-241) is not supported by this implementation' % flag)
+    elif cfg.NET.USE_POSE_PRELOGITS_BASED_ATTENTION:
         head = AttentionalPoolingHead(num_classes, cfg, in_channels=channels,
                                       num_pose_keypoints=num_pose_keypoints, is_training=is_training,
                                       seed=head_seed, **head_kwargs).to(device)
@@ -869,7 +1042,7 @@ def get_network_fn(name: str, num_classes: int, num_pose_keypoints: int, cfg,
             eps = last_conv
             last_conv = eps[last_conv_map[name][0]]
             pose_tap = eps.get(getattr(cfg.NET.LAST_CONV_MAP_FOR_POSE, name, None), last_conv)
-            if isinstance(head, AttentionalPoolingHead) and pose_tap is not last_conv:
+            if isinstance(head, (AttentionalPoolingHead, PoseAttentionLogitsHead)) and pose_tap is not last_conv:
                 logits, end_points = head(last_conv, last_conv_pose=pose_tap)
             else:
                 logits, end_points = head(last_conv)

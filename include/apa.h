@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define APA_VERSION 300 /* major*10000 + minor*100 + patch */
+#define APA_VERSION 301 /* major*10000 + minor*100 + patch */
 
 typedef enum apa_status {
   APA_OK = 0,
@@ -179,6 +179,47 @@ int apa_pose_head_bwd_rank1ext(const void* X, const float* W1, const float* W2, 
                                int accumulate_dX, float* dW1, float* db1, float* dW2, float* db2,
                                void* ws, size_t ws_bytes, int N, int P, int C, int Cp, int J, int dtype,
                                void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Pose-heatmap attention head, cfg.NET.USE_POSE_ATTENTION_LOGITS.  Replaces nets_factory.py:162-189 (after the
+ * PoseLogits head of :147-160, apa_pose_head_fwd):
+ *   A[n,p,m] = Pl[n,p,sel[m]]  (m < n_sel)              the selected parts, USE_POSE_ATTENTION_LOGITS_DIMS (:168-172)
+ *            = mean_j Pl[n,p,j] (m == n_sel, avged)     ..._AVGED_HMAP, over all J parts      (:176-179)
+ *            = 1                (m == M - 1)            the plain spatial mean                 (:180-181)
+ *   F[n, m*C + c] = (1/P) sum_p A[n,p,m] X[n,p,c]        tf.concat(part_logits, axis=-1)       (:173-182)
+ *   Fd = F * mask / keep_prob (APA_FLAG_TRAIN) else F    slim.dropout                          (:183)
+ *   logits = Fd . W + b                                  'PoseAttention/Conv'                  (:184-188)
+ * M = n_sel + avged + 1.  X [N,P,C] dtype; Pl [N,P,J] f32 = raw PoseLogits (no activation: negative weights are
+ * fine); W [M*C, K] f32, b [K] f32; F [N, M*C] f32 (out: saved for backward); logits [N,K] f32 (out).
+ * sel: HOST int32 [n_sel], already normalised to [0, J) (numpy indexing of the reference: negative indices wrapped,
+ * repeats allowed; NULL when n_sel == 0); avged: 0 / 1.
+ * flags: APA_FLAG_TRAIN, APA_FLAG_RNG_EXTERNAL (a bit image over the flat index of F).  The hashed mask is the one
+ * apa_dropout_mask(N*M*C, keep_prob, seed, offset) returns: element n*(M*C) + m*C + c of F.
+ * ws: apa_pose_att_logits_workspace_bytes(N, P, C, M, K) bytes; one buffer may serve both calls.
+ * Built for M <= 32, C a multiple of 4, K <= 480 (else APA_ERR_UNSUPPORTED); X 16-byte (f32) / 8-byte (bf16)
+ * aligned.  Every reduction is summed in a fixed order: identical calls give bit-identical results.
+ *
+ * Backward (TF autodiff in the reference).  G = dLoss/dlogits [N,K] f32.
+ *   dW [M*C,K], db [K] f32                       overwritten
+ *   dX [N,P,C] dtype                             overwritten, or (accumulate_dX) added to
+ *   dPl [N,P,J] f32                              ACCUMULATED: dPl[n,p,j] += sum_{m: sel[m]=j} dA[n,p,m]
+ *                                                + avged * dA[n,p,n_sel] / J, dA = (1/P) sum_c X dFd-scaled; the
+ *                                                constant map's share is dropped.  Pass the pose-loss gradient
+ *                                                (or zeros) and hand the sum to apa_pose_head_bwd.
+ * F is the forward call's output; seed / offset / flags as in the forward call.
+ * The _ex forms take apa_hooks: prof_fwd_start / stop bracket the pooling kernel(s) of the call, prof_bwd_start /
+ * stop its classifier kernel(s) (per-kernel HIP-event times for tools/bench_dense.py).
+ */
+size_t apa_pose_att_logits_workspace_bytes(int N, int P, int C, int M, int K);
+int apa_pose_att_logits_fwd(const void* X, const float* Pl, const int32_t* sel, int n_sel, int avged,
+                            const float* W, const float* b, float* F, float* logits, void* ws, size_t ws_bytes,
+                            int N, int P, int C, int J, int K, unsigned flags, float keep_prob, uint64_t seed,
+                            uint64_t offset, int dtype, void* stream);
+int apa_pose_att_logits_bwd(const void* X, const float* Pl, const int32_t* sel, int n_sel, int avged,
+                            const float* W, const float* F, const float* G, void* dX, int accumulate_dX,
+                            float* dPl, float* dW, float* db, void* ws, size_t ws_bytes, int N, int P, int C,
+                            int J, int K, unsigned flags, float keep_prob, uint64_t seed, uint64_t offset,
+                            int dtype, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Action loss: tf.losses.softmax_cross_entropy(one_hot(labels,K), logits, weights=wt)
@@ -438,6 +479,15 @@ int apa_attn_pool_bwd_ex(const apa_hooks* hooks, const void* X, const void* Xatt
                          float* dWa, float* dba, float* dWt, float* dbt, void* ws, size_t ws_bytes,
                          int N, int P, int C, int Ca, int K, int M, unsigned flags, float keep_prob,
                          uint64_t seed, uint64_t offset, int dtype, void* stream);
+int apa_pose_att_logits_fwd_ex(const apa_hooks* hooks, const void* X, const float* Pl, const int32_t* sel,
+                               int n_sel, int avged, const float* W, const float* b, float* F, float* logits,
+                               void* ws, size_t ws_bytes, int N, int P, int C, int J, int K, unsigned flags,
+                               float keep_prob, uint64_t seed, uint64_t offset, int dtype, void* stream);
+int apa_pose_att_logits_bwd_ex(const apa_hooks* hooks, const void* X, const float* Pl, const int32_t* sel,
+                               int n_sel, int avged, const float* W, const float* F, const float* G, void* dX,
+                               int accumulate_dX, float* dPl, float* dW, float* db, void* ws, size_t ws_bytes,
+                               int N, int P, int C, int J, int K, unsigned flags, float keep_prob, uint64_t seed,
+                               uint64_t offset, int dtype, void* stream);
 int apa_attn_head_train_step_ex(const apa_hooks* hooks, const void* X, const void* Xatt,
                                 const float* Wa, const float* ba, const float* Wt, const float* bt,
                                 const int64_t* labels, float loss_wt, float grad_scale, float* logits,

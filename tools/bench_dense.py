@@ -353,6 +353,92 @@ def build_eval002(cof, dev, N=32, H=14, K=393, dtype='f32', rotate=0):
     return _round_robin([ev.run for ev in evs]), info
 
 
+# algorithmic HBM bytes of the four pose-attention kernels (fp32 parameters / F / logits; X and dX in the feature dtype)
+def poseatt_kernel_bytes(N, P, C, J, M, K, xbytes):
+    R = M * C
+    return {
+        'pool_fwd': N * P * C * xbytes + N * P * J * 4 + N * R * 4,                 # X, Pl -> F
+        'cls_fwd': R * K * 4 + N * R * 4 + N * K * 4,                                # W, F -> logits
+        'cls_bwd': 2 * R * K * 4 + N * R * 4 + N * K * 4,                            # W, F, G -> dW, (dF)
+        'pool_bwd': 2 * N * P * C * xbytes + 2 * N * P * J * 4,                      # X, Pl -> dX, dPl
+    }
+
+
+def build_poseatt(cof, dev, N=32, H=14, K=393, dtype='f32', rotate=0):
+    """USE_POSE_ATTENTION_LOGITS, one training step: pose head fwd, pooling fwd, classifier fwd, softmax-xent,
+    pose L2, classifier bwd, pooling bwd, pose head bwd.  X / dX AND W / dW rotate over enough sets that 1.5 x the
+    Infinity Cache lies between two uses (the backbone evicts them between real steps).  Returns the step and a
+    function that times the four new kernels with HIP events (apa_pose_att_logits_*_ex hooks)."""
+    C, P, J, Cp = 2048, H * H, 16, 768
+    parts, avged = list(range(J)), False
+    M = cof.pose_att_num_maps(parts, avged)
+    td = torch.bfloat16 if dtype == 'bf16' else torch.float32
+    g = torch.Generator().manual_seed(42)
+    W1 = (torch.randn(C, Cp, generator=g) * 0.001).to(dev); b1 = torch.zeros(Cp, device=dev)
+    W2 = (torch.randn(Cp, J, generator=g) * (2.6 / Cp) ** 0.5).to(dev); b2 = torch.zeros(J, device=dev)
+    b = torch.zeros(K, device=dev)
+    labels = torch.randint(0, K, (N,), generator=g).to(dev)
+    lbl = torch.rand(N, P, J, generator=g).to(dev)
+    valid = (torch.rand(N, J, generator=g) > 0.3).to(dev)
+    xb = torch.finfo(td).bits // 8
+    per_set = 2 * N * P * C * xb + 2 * M * C * K * 4
+    R = _n_sets(per_set, rotate)
+    sets = []
+    for r in range(R):
+        X = _features(N, P, C, td, dev, seed=42 + r)
+        W = (torch.randn(M * C, K, generator=torch.Generator().manual_seed(7 + r)) * 0.001).to(dev)
+        sets.append((X, W, torch.empty_like(X)))
+    flags = cof.attn_flags(is_training=True)
+    ws = {}
+
+    def step_on(X, W, dX, hooks=None, state={'offset': 0}):
+        off = state['offset']
+        state['offset'] += 1
+        Ppre, Pl, pws = cof.pose_head_fwd(X, W1, b1, W2, b2, workspace=ws.get('pose'))
+        ws['pose'] = pws
+        F, logits, aws = cof.pose_att_logits_fwd(X, Pl, parts, avged, W, b, flags=flags, keep_prob=0.2, seed=42,
+                                                 offset=off, workspace=ws.get('att'), hooks=hooks[0] if hooks else None)
+        ws['att'] = aws
+        _, G, _, _ = cof.softmax_xent_fwd_bwd(logits, labels)
+        _, dPl = cof.pose_l2_loss_fwd_bwd(Pl, lbl, valid)
+        _, dPl, dW, db = cof.pose_att_logits_bwd(X, Pl, parts, avged, W, F, G, dPl, dX=dX, flags=flags,
+                                                 keep_prob=0.2, seed=42, offset=off, workspace=aws,
+                                                 hooks=hooks[1] if hooks else None)
+        cof.pose_head_bwd(X, W1, W2, Ppre, dPl, None, dX=dX, accumulate_dX=True, workspace=pws, ws_from_fwd=True)
+
+    def kernel_times(n=20):
+        evs = [torch.cuda.Event(enable_timing=True) for _ in range(8)]
+        for e in evs:
+            e.record()
+        hf = cof.make_hooks(prof_fwd=(evs[0], evs[1]), prof_bwd=(evs[2], evs[3]))
+        hb = cof.make_hooks(prof_fwd=(evs[4], evs[5]), prof_bwd=(evs[6], evs[7]))
+        acc = {'pool_fwd': [], 'cls_fwd': [], 'cls_bwd': [], 'pool_bwd': []}
+        for i in range(n):
+            X, W, dX = sets[i % R]
+            step_on(X, W, dX, hooks=(hf, hb))
+            torch.cuda.synchronize()
+            acc['pool_fwd'].append(evs[0].elapsed_time(evs[1]))
+            acc['cls_fwd'].append(evs[2].elapsed_time(evs[3]))
+            acc['pool_bwd'].append(evs[4].elapsed_time(evs[5]))
+            acc['cls_bwd'].append(evs[6].elapsed_time(evs[7]))
+        byt = poseatt_kernel_bytes(N, P, C, J, M, K, xb)
+        out = {}
+        for k, v in acc.items():
+            v.sort()
+            us = v[len(v) // 2] * 1e3
+            out[k] = {'us': round(us, 2), 'algorithmic_MB': round(byt[k] / 1e6, 1),
+                      'hbm_frac': round(byt[k] / (us * 1e-6) / (HBM_PEAK_GBS * 1e9), 3)}
+        return out
+
+    runs = [(lambda s=s: step_on(*s)) for s in sets]
+    info = {'workload': 'USE_POSE_ATTENTION_LOGITS training step (pose head 2048->768->16, M={} maps, classifier '
+                        '{}x{} fp32, xent, pose L2, backward); per-GPU batch {} x {}x{}x{} {}'.format(
+                            M, M * C, K, N, H, H, C, dtype) + _rot_note(R, per_set).replace('X/dX', 'X/dX/W'),
+            'bound': 'hbm', 'dtype': dtype, 'N': N, 'rotate': R,
+            'bytes_per_image': sum(poseatt_kernel_bytes(N, P, C, J, M, K, xb).values()) / N}
+    return _round_robin(runs), info, kernel_times
+
+
 def timed(fn, steps, warmup, min_ms=50.0, repeats=5):
     """median over >= `repeats` timed loops of `steps` steps each (>= min_ms of device time in total)."""
     for _ in range(warmup):
@@ -395,7 +481,7 @@ def report(info, sec, repeats):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--workload', default='cfg003', choices=['cfg003', 'perclass', 'eval002', 'rank1', 'posebwd', 'posebwd_acc', 'update003',
-                                                         'update_perclass'])
+                                                         'update_perclass', 'poseatt'])
     ap.add_argument('--batch', type=int, default=32)
     ap.add_argument('--hw', type=int, default=14)
     ap.add_argument('--classes', type=int, default=None)
@@ -417,6 +503,15 @@ def main():
     if args.workload in ('update003', 'update_perclass'):
         print(json.dumps(run_update_pair(cof, dev, 'cfg003' if args.workload == 'update003' else 'perclass',
                                          rotate=args.rotate)))
+        return
+    if args.workload == 'poseatt':
+        step, info, kernel_times = build_poseatt(cof, dev, args.batch, args.hw, args.classes or 393,
+                                                 args.dtype or 'f32', rotate=args.rotate)
+        sec, reps = timed(step, args.steps, args.warmup)
+        out = report(info, sec, reps)
+        out['us_per_step'] = round(sec * 1e6, 2)
+        out['kernels'] = kernel_times()
+        print(json.dumps(out))
         return
     if args.workload == 'cfg003':
         step, info = build_cfg003(cof, dev, args.batch, args.hw, args.classes or 393, args.dtype or 'bf16',
