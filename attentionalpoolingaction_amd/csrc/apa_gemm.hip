@@ -437,26 +437,37 @@ static int gemm_launch_t(const GemmDesc& d, hipStream_t st) {
     splits = (d.K + kps64 - 1) / kps64;
     if (d.twin && !gemm_bf16_twin_ok(d, splits, kps64)) {   // one after the other
       GemmDesc a = d; a.twin = nullptr;
-      const int rc = gemm_launch_t<TA, TB, TC, A_KC, B_KC>(a, st);
-      return rc != APA_OK ? rc : gemm_launch(*d.twin, st);
+      int rc = gemm_launch_t<TA, TB, TC, A_KC, B_KC>(a, st);
+      if (rc == APA_OK) rc = gemm_launch(*d.twin, st);
+      if (d.trace) d.trace->twin = GEMM_TWIN_SERIAL;
+      return rc;
     }
     twin = d.twin != nullptr;
     const int rc = gemm_bf16_launch(d, splits, kps64, st);
     if (rc != APA_OK) return rc;
     pN = d.N;
+    kps = kps64;
   } else {
   if (d.twin) {
     GemmDesc a = d; a.twin = nullptr;
-    const int rc = gemm_launch_t<TA, TB, TC, A_KC, B_KC>(a, st);
-    return rc != APA_OK ? rc : gemm_launch(*d.twin, st);
+    int rc = gemm_launch_t<TA, TB, TC, A_KC, B_KC>(a, st);
+    if (rc == APA_OK) rc = gemm_launch(*d.twin, st);
+    if (d.trace) d.trace->twin = GEMM_TWIN_SERIAL;
+    return rc;
   }
-  if (d.r1_row) {
-    set_error("gemm: the rank-1 epilogue exists in the wide bf16 kernel only (internal)");
+  if (d.r1_row || d.mid_bits) {
+    set_error("gemm: the rank-1 epilogue and the mid-contraction mask exist in the wide bf16 kernel only (internal)");
     return APA_ERR_UNSUPPORTED;
   }
+  if (d.trace) d.trace->kind = GEMM_KIND_GENERIC;
   hipLaunchKernelGGL((gemm128_kernel<TA, TB, TC, A_KC, B_KC, BF16>), dim3(tiles, 1, splits), dim3(256),
                      0, st, p);
   APA_LAUNCH_CHECK("gemm128_kernel");
+  }
+  if (d.trace) {
+    d.trace->splits = splits; d.trace->k_per_split = kps;
+    d.trace->twin = twin ? GEMM_TWIN_FUSED : GEMM_TWIN_NONE;
+    d.trace->reduce = GEMM_REDUCE_NONE;
   }
   if (splits > 1) {
     const long tot = (long)d.M * pN;
@@ -482,6 +493,7 @@ static int gemm_launch_t(const GemmDesc& d, hipStream_t st) {
                          static_cast<TC*>(d.C), d.ldc, d.M, Nst, pN, splits, d.bias, d.beta, d.act, nmain, j);
       APA_LAUNCH_CHECK("gemm_splitk_reduce_tail_kernel");
       d.tail->done = true;
+      if (d.trace) d.trace->reduce = GEMM_REDUCE_TAIL;
       return APA_OK;
     }
     if (vec) {
@@ -494,6 +506,7 @@ static int gemm_launch_t(const GemmDesc& d, hipStream_t st) {
                          d.beta, d.act, tw);
     }
     APA_LAUNCH_CHECK("gemm_splitk_reduce_kernel");
+    if (d.trace) d.trace->reduce = vec ? GEMM_REDUCE_VEC : GEMM_REDUCE_SCALAR;
   }
   return APA_OK;
 }

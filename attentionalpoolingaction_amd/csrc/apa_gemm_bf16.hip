@@ -1634,18 +1634,24 @@ int gemm_bf16_launch(const GemmDesc& d, int splits, int k_per_split, hipStream_t
     p.Nout2 = (t.n_valid > 0 && splits == 1) ? t.n_valid : t.N;
     p.vec_epi2 = vec_epilogue_ok(t, p.Nout2, p.partial2);
   }
+  // (checked for every kind: the generic bf16 kernel has neither epilogue term either)
+  if (d.mid_bits && kind != KIND_WIDE) {
+    set_error("gemm_bf16: mid-contraction mask requested for a product the wide kernel does not serve (internal)");
+    return APA_ERR_UNSUPPORTED;
+  }
+  if (d.r1_row && kind != KIND_WIDE) {
+    set_error("gemm_bf16: rank-1 epilogue requested for a product the wide kernel does not serve (internal)");
+    return APA_ERR_UNSUPPORTED;
+  }
   if (kind != KIND_GENERIC) {   // all-bf16, whole K tiles: DMA staging
     // tile shape: with fewer than ~2.5 tiles of 128 x 128 per CU the ragged last round dominates and
     // the 128 x 64 variant (twice the tiles, three blocks per CU) wins -- measured on the pose head:
     // 294 tiles 38.2 -> 32.6 us, 96 x 3 splits 40.0 -> 35.2 us, but 784 tiles 34.4 -> 37.4 us
     // few tiles, A k-contiguous, no split-K: the ring kernel (one resident round, 3-4 K tiles in flight)
     // wide output, short contraction, both operands k-contiguous, no split-K: one resident round of 256-wide tiles
-    if (d.mid_bits && kind != KIND_WIDE) {
-      set_error("gemm_bf16: mid-contraction mask requested for a product the wide kernel does not serve (internal)");
-      return APA_ERR_UNSUPPORTED;
-    }
     if (kind == KIND_WIDE) {
       const int mt = wide_pick_mt(d.M, d.N, gemm_cu_count());
+      if (d.trace) { d.trace->kind = GEMM_KIND_WIDE; d.trace->mt = mt; }
       if (d.mid_bits) {
         if (!p.vec_epi || d.n_valid > 0 || d.tc != 1 || d.drop_c || d.r1_row || d.mid_k <= 0 || d.mid_k % TK != 0 ||
             d.mid_k >= d.K || (d.N % 8) != 0) {
@@ -1666,10 +1672,6 @@ int gemm_bf16_launch(const GemmDesc& d, int splits, int k_per_split, hipStream_t
       if (d.tc == 1) return launch_wide_mt<bf16_t>(p, mt, st);
       return launch_wide_mt<float>(p, mt, st);
     }
-    if (d.r1_row) {
-      set_error("gemm_bf16: rank-1 epilogue requested for a product the wide kernel does not serve (internal)");
-      return APA_ERR_UNSUPPORTED;
-    }
     if (kind == KIND_RING) {
 #ifdef APA_ABLATION
       static const int m32 = knob("APA_GEMM_M32", 0);      // 6: 192 x 128 tiles, 4: 128 x 128, 8: 256 x 128; 16: MT 6 with 16x16x32
@@ -1681,9 +1683,11 @@ int gemm_bf16_launch(const GemmDesc& d, int splits, int k_per_split, hipStream_t
       if (m32 == 16 && d.tc == 1) return d.b_kc ? launch_ring_mt<bf16_t, false>(p, 6, st) : launch_ring_mt<bf16_t, true>(p, 6, st);
 #endif
       const int mt = ring_pick_mt(d.M, d.N, gemm_cu_count());
+      if (d.trace) { d.trace->kind = GEMM_KIND_RING; d.trace->mt = mt; }
       if (d.tc == 1) return d.b_kc ? launch_ring_mt<bf16_t, false>(p, mt, st) : launch_ring_mt<bf16_t, true>(p, mt, st);
       return d.b_kc ? launch_ring_mt<float, false>(p, mt, st) : launch_ring_mt<float, true>(p, mt, st);
     }
+    if (d.trace) d.trace->kind = kind == KIND_GLDS64 ? GEMM_KIND_GLDS64 : GEMM_KIND_GLDS128;
     if (kind == KIND_GLDS64) {
       if (d.tc == 1) return launch_glds64_layout<bf16_t>(p, !d.a_kc, !d.b_kc, splits, st);
       return launch_glds64_layout<float>(p, !d.a_kc, !d.b_kc, splits, st);
@@ -1691,6 +1695,7 @@ int gemm_bf16_launch(const GemmDesc& d, int splits, int k_per_split, hipStream_t
     if (d.tc == 1) return launch_glds_layout<bf16_t>(p, !d.a_kc, !d.b_kc, splits, st);
     return launch_glds_layout<float>(p, !d.a_kc, !d.b_kc, splits, st);
   }
+  if (d.trace) d.trace->kind = GEMM_KIND_BF16;
   if (d.tb == 1) {
     if (d.tc == 1) return launch_layout<bf16_t, bf16_t>(p, !d.a_kc, !d.b_kc, splits, st);
     return launch_layout<bf16_t, float>(p, !d.a_kc, !d.b_kc, splits, st);

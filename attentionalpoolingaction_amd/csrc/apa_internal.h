@@ -158,6 +158,18 @@ struct ColsumJob {
   const float* aux_src = nullptr; int aux_n = 0; float aux_scale = 0.f; float* aux_dst = nullptr;
   bool done = false;
 };
+// What gemm_launch actually ran (GemmDesc::trace: filled on the host only, read by the kernel-level tests).
+enum GemmKind { GEMM_KIND_NONE = 0, GEMM_KIND_GENERIC, GEMM_KIND_BF16, GEMM_KIND_WIDE, GEMM_KIND_RING,
+                GEMM_KIND_GLDS64, GEMM_KIND_GLDS128 };
+enum GemmReduce { GEMM_REDUCE_NONE = 0, GEMM_REDUCE_VEC, GEMM_REDUCE_SCALAR, GEMM_REDUCE_TAIL };
+enum GemmTwin { GEMM_TWIN_NONE = 0, GEMM_TWIN_FUSED, GEMM_TWIN_SERIAL };
+struct GemmTrace {
+  int kind = GEMM_KIND_NONE;   // GEMM_KIND_GENERIC: gemm128_kernel; GEMM_KIND_BF16: gemm_bf16_kernel
+  int splits = 0, k_per_split = 0;
+  int mt = 0;                  // ring / wide: MFMA row tiles per wave row (block rows = 32 mt)
+  int twin = GEMM_TWIN_NONE;
+  int reduce = GEMM_REDUCE_NONE;
+};
 struct GemmDesc {
   const void* A = nullptr; long lda = 0; int ta = 0; bool a_kc = true;
   const void* B = nullptr; long ldb = 0; int tb = 0; bool b_kc = false;
@@ -190,6 +202,8 @@ struct GemmDesc {
   const uint8_t* mid_bits = nullptr; int mid_k = 0; float mid_inv_keep = 1.f;
   // a column sum to run on the tail blocks of this product's split-K reduce launch (taken only if there is one)
   ColsumJob* tail = nullptr;
+  // optional: where to record the kernel kind / split / reduce that served this product (null at product call sites)
+  GemmTrace* trace = nullptr;
 };
 bool gemm_bf16_wide_serves(int M, int N, int K);   // would this all-bf16, k-contiguous, unsplit product take the wide kernel?
 int gemm_bf16_wide_tile_rows(int M, int N, int K);  // ... and with how many rows per tile (0 = not served)
