@@ -258,6 +258,26 @@ struct M1Plan {
 };
 M1Plan m1_plan(int N, int P, int C, int Ca, int K);
 
+// What the M == 1 path ran (filled on the host only, read by the kernel-level tests through the test-only probe
+// library).  The product never sets the pointer: m1_trace() is null there and nothing is recorded.
+enum M1Pool { M1_POOL_NONE = 0, M1_POOL_STREAM, M1_POOL_VEC, M1_POOL_GENERIC };
+enum M1Logits { M1_LOGITS_NONE = 0, M1_LOGITS_XENT, M1_LOGITS_XENT_PROBS, M1_LOGITS2, M1_LOGITS_PARTIAL,
+                M1_LOGITS_SGEMM };
+enum M1Head { M1_HEAD_NONE = 0, M1_HEAD_TILES, M1_HEAD_ROWS, M1_HEAD_SMALL, M1_HEAD_SGEMM };
+enum M1Gemv { M1_GEMV_NONE = 0, M1_GEMV_BWD2, M1_GEMV_BWD2_RANK1, M1_GEMV_BWD };
+enum M1Reduce { M1_REDUCE_NONE = 0, M1_REDUCE_COLSUM, M1_REDUCE_BWD_REDUCE };
+struct M1Trace {
+  int pool_fwd, fwd_w, fwd_pix;    // M1Pool; stream: VW and PIX, per-pixel vec: VEC (pix 0)
+  int pool_bwd, bwd_w, bwd_pix;
+  int fused, keep_bits, relu_input;   // keep_bits: the backward read the forward call's keep bits
+  int S, ppb, nblk, cw;            // plan; cw: channels per thread column of m1_finalize_fwd_kernel
+  int logits, logits_nv4, logits_nsub;
+  int head, head_ug, head_mv;
+  int gemv, reduce, rng_bump, cat_fwd, cat_bwd;
+};
+extern thread_local M1Trace* g_m1_trace;
+inline M1Trace* m1_trace() { return g_m1_trace; }
+
 int m1_forward(const void* X, const void* Xatt, const float* Wa, const float* ba, const float* Wt,
                const float* bt, float* logits, float* att, float* zsave, float* abar, void* ws,
                int N, int P, int C, int Ca, int K, unsigned flags, float keep_prob, uint64_t seed,
@@ -270,6 +290,7 @@ int m1_backward(const void* X, const void* Xatt, const float* Wa, const float* b
                 float keep_prob, uint64_t seed, uint64_t offset, int dtype, hipStream_t stream,
                 const M1Xent* xf = nullptr, const Hooks& hk = Hooks(), const CatFeat* cat = nullptr);
 bool m1_supported(int C, int Ca, int dtype, bool fused);
+bool m1_vec_supported(int C, int dtype);   // the per-pixel kernels of apa_m1.hip have an instance for C
 bool m1_no_dx_supported(int C, int dtype, bool train);   // can m1_backward honour APA_IFLAG_NO_DX for this shape?
 
 // apa_m1_stream.hip: "pixel tile x channel split" streaming passes for wide maps

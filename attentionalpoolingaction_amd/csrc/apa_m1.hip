@@ -655,6 +655,8 @@ __global__ __launch_bounds__(256) void m1_att_gemv_bwd2_kernel(
 // ============================================================================================
 // host side
 // ============================================================================================
+thread_local M1Trace* g_m1_trace = nullptr;
+
 static bool use_stream_kernels(int C, int dtype);
 // the register-resident per-pixel kernels of this file: C = 64 * EPV * {1, 2, 4, 8}
 static bool vec_kernels_supported(int C, int dtype) {
@@ -665,6 +667,7 @@ static bool vec_kernels_supported(int C, int dtype) {
   if (dtype == APA_DTYPE_BF16 && vec == 8) return false;  // C = 4096 bf16: not instantiated
   return true;
 }
+bool m1_vec_supported(int C, int dtype) { return vec_kernels_supported(C, dtype); }
 // Any channel count that is a whole number of 16-byte vectors is served: the channel-split streaming
 // kernels (apa_m1_stream.hip) for the wide benchmark shapes, the per-pixel kernels of this file for the
 // other powers of two, the run-time-loop kernels of apa_m1_generic.hip for everything else.
@@ -732,6 +735,7 @@ static int launch_pool_fwd(bool fused, bool train, int nblk, hipStream_t st, con
                            const float* Wa, const float* ba, float* att, float* pacc, float* pstat,
                            int P, int S, int act, RngArgs r) {
   const T* x = static_cast<const T*>(X);
+  if (M1Trace* t = m1_trace()) { t->pool_fwd = M1_POOL_VEC; t->fwd_w = VEC; t->fwd_pix = 0; }
 #define APA_GO(F, TR)                                                                          \
   launch_ev(m1_pool_fwd_kernel<T, VEC, F, TR>, dim3(nblk), dim3(256), 0, st, r.ev0, r.ev1, x, Wa, \
                      ba, att, pacc, pstat, P, S, act, r.inv_keep, r.thresh, r.seed, r.offset,  \
@@ -754,6 +758,7 @@ static int launch_bwd_main(bool fused, bool train, int nblk, hipStream_t st, con
   T* dx = static_cast<T*>(dX);
   const float* ex = dA_extra ? dA_extra : att;
   const float exs = dA_extra ? 1.0f : 0.0f;
+  if (M1Trace* t = m1_trace()) { t->pool_bwd = M1_POOL_VEC; t->bwd_w = VEC; t->bwd_pix = 0; }
 #define APA_GO(F, TR)                                                                            \
   launch_ev(m1_bwd_main_kernel<T, VEC, F, TR>, dim3(nblk), dim3(256), 0, st, r.ev0, r.ev1, x, Wa,   \
                      att, dz, zsave, abar, G, bt, sn_pre, dx, dZout, pdwa, pdba, P, S, K, act,   \
@@ -816,6 +821,8 @@ int m1_forward(const void* X, const void* Xatt, const float* Wa, const float* ba
   RngArgs r = rng_args(train, keep_prob, seed, offset, flags);
   r.ev0 = hk.fwd0; r.ev1 = hk.fwd1;
   r.maskbits_out = reinterpret_cast<uint8_t*>(w + pl.off_maskbits);
+  M1Trace* const tr = m1_trace();
+  if (tr) { tr->S = pl.S; tr->ppb = pl.ppb; tr->nblk = pl.nblk; tr->fused = fused; tr->relu_input = r.relu_input; }
 
   if (r.relu_input && !(fused && use_stream_kernels(C, dtype))) {
     set_error("attn_pool M=1: APA_FLAG_RELU_INPUT needs Xatt == X and C in {1024,2048,4096} (f32) / 2048 (bf16)");
@@ -859,9 +866,11 @@ int m1_forward(const void* X, const void* Xatt, const float* Wa, const float* ba
   else if (!ext && vec_kernels_supported(C, dtype))
     rc = APA_DISPATCH_VEC(launch_pool_fwd, dtype, C, fused, train, pl.nblk, st, X, Wa, ba, att,
                           pacc, pstat, P, pl.S, pool_act, r);
-  else
+  else {
+    if (tr) tr->pool_fwd = M1_POOL_GENERIC;
     rc = m1g_launch_pool_fwd(dtype, C, fused, train, pl.nblk, st, X, Wa, ba, att, pacc, pstat, P, pl.S,
                              pool_act, r);
+  }
   if (rc != APA_OK) return rc;
   const int online = (fused && act == ACT_SOFTMAX) ? 1 : 0;
   if (!(dbg_skip() & 2)) {
@@ -869,6 +878,7 @@ int m1_forward(const void* X, const void* Xatt, const float* Wa, const float* ba
     static const int cw_env = knob("APA_M1_FIN_CW", 0);
     int cw = cw_env ? cw_env : 256;
     if (!cw_env) while (cw > 64 && (long)N * ((C + 4 * cw - 1) / (4 * cw)) < 256) cw >>= 1;
+    if (tr) tr->cw = cw;
     hipLaunchKernelGGL(m1_finalize_fwd_kernel, dim3(N, (C + 4 * cw - 1) / (4 * cw)), dim3(256), 0, st, pacc,
                        pstat, zsave, abar, att, P, pl.S, C, online, cw);
     APA_LAUNCH_CHECK("m1_finalize_fwd_kernel");
@@ -885,17 +895,22 @@ int m1_forward(const void* X, const void* Xatt, const float* Wa, const float* ba
       ((reinterpret_cast<uintptr_t>(zsave) | reinterpret_cast<uintptr_t>(Wt) |
         reinterpret_cast<uintptr_t>(xf->G)) & 15) == 0) {
     // training: the same conditions under which m1_backward takes the head kernel, which finishes loss[0]
+    if (tr) tr->logits = xeval ? M1_LOGITS_XENT_PROBS : M1_LOGITS_XENT;
     rc = m1_logits2_xent(zsave, Wt, abar, bt, xf->labels, logits, xf->loss, xf->G, xf->gscale, xf->probs,
                          xf->pred, gemm_ws, N, C, K, st);
     xf->done = rc == APA_OK;
     return rc;
   }
-  if (use_l2 && m1_logits2_supported(C, K) && (reinterpret_cast<uintptr_t>(zsave) & 15) == 0)
+  if (use_l2 && m1_logits2_supported(C, K) && (reinterpret_cast<uintptr_t>(zsave) & 15) == 0) {
+    if (tr) tr->logits = M1_LOGITS2;
     rc = m1_logits2(zsave, Wt, abar, bt, logits, gemm_ws, N, C, K, st);
-  else if (m1_small_supported(C, K) && (reinterpret_cast<uintptr_t>(zsave) & 15) == 0)
+  } else if (m1_small_supported(C, K) && (reinterpret_cast<uintptr_t>(zsave) & 15) == 0) {
+    if (tr) tr->logits = M1_LOGITS_PARTIAL;
     rc = m1_logits(zsave, Wt, abar, bt, logits, gemm_ws, N, C, K, st);
-  else
+  } else {
+    if (tr) tr->logits = M1_LOGITS_SGEMM;
     rc = sgemm_small(zsave, C, 1, Wt, K, 1, logits, K, N, K, C, pl.lsplits, abar, bt, gemm_ws, st);
+  }
   if (rc != APA_OK || !cat) return rc;
   // ..._WITH_POSE_FEAT: logits += zext . Wt[C:C+J]
   return m1_cat_forward(*cat, att, Wt, logits, N, P, C, K, train, r, st);
@@ -923,6 +938,8 @@ int m1_backward(const void* X, const void* Xatt, const float* Wa, const float* b
   float* sn_buf = pdba + pl.nblk;   // [N] floats: the pdba region is sized nblk + N
   RngArgs r = rng_args(train, keep_prob, seed, offset, flags);
   r.ev0 = hk.bwd0; r.ev1 = hk.bwd1;
+  M1Trace* const tr = m1_trace();
+  if (tr) { tr->S = pl.S; tr->ppb = pl.ppb; tr->nblk = pl.nblk; tr->fused = fused; tr->relu_input = r.relu_input; }
   static const int use_bits = knob("APA_M1_KEEP_BITS", 1);
   if ((flags & APA_FLAG_WS_FROM_FWD) && use_bits)   // same workspace, untouched since the forward call
     r.maskbits_in = reinterpret_cast<const uint8_t*>(w + pl.off_maskbits);
@@ -955,8 +972,10 @@ int m1_backward(const void* X, const void* Xatt, const float* Wa, const float* b
       set_error("attn_pool M=1: fused loss path without the head kernel (internal)");
       return APA_ERR_UNSUPPORTED;
     }
-    if (!(use_head && m1_bwd_head_supported(N, C, K)))
+    if (!(use_head && m1_bwd_head_supported(N, C, K))) {
+      if (tr) tr->head = M1_HEAD_SMALL;
       rc = m1_bwd_small(G, Wt, zsave, abar, bt, dz, dWt, dbt, sn_buf, N, C, K, st);
+    }
     if (rc != APA_OK) return rc;
   } else {
     if (xf && xf->done) {
@@ -964,6 +983,7 @@ int m1_backward(const void* X, const void* Xatt, const float* Wa, const float* b
       return APA_ERR_UNSUPPORTED;
     }
     // generic fallback (very large K): dz[n,c] = sum_k G[n,k] Wt[c,k]; dWt[c,k] = sum_n z[n,c] G[n,k]
+    if (tr) tr->head = M1_HEAD_SGEMM;
     rc = sgemm_small(G, K, 1, Wt, 1, K, dz, C, N, C, K, 1, nullptr, nullptr, gemm_ws, st);
     if (rc != APA_OK) return rc;
     rc = sgemm_small(zsave, 1, C, G, K, 1, dWt, K, C, K, N, 1, nullptr, nullptr, gemm_ws, st);
@@ -994,9 +1014,11 @@ int m1_backward(const void* X, const void* Xatt, const float* Wa, const float* b
     rc = APA_DISPATCH_VEC(launch_bwd_main, dtype, C, fused, train, pl.nblk, st, X, Wa, att, dz,
                           zsave, abar, G, bt, small_ok ? sn_buf : nullptr, dX, dZatt, pdwa, pdba,
                           P, pl.S, K, act, r, dA_extra);
-  else
+  else {
+    if (tr) tr->pool_bwd = M1_POOL_GENERIC;
     rc = m1g_launch_bwd_main(dtype, C, fused, train, pl.nblk, st, X, Wa, att, dz, zsave, abar, G, bt,
                              small_ok ? sn_buf : nullptr, dX, dZatt, pdwa, pdba, P, pl.S, K, act, r, dA_extra);
+  }
   if (rc != APA_OK) return rc;
 
   int nred = pl.nblk;
@@ -1021,6 +1043,7 @@ int m1_backward(const void* X, const void* Xatt, const float* Wa, const float* b
     static const int use_v2 = knob("APA_M1_GEMV_BWD2", 1);
     if (use_v2 && Ca % epv == 0 && Ca / epv <= 256) {   // register-resident form
       const int nthr = ((Ca / epv + 63) / 64) * 64;
+      if (tr) tr->gemv = rank1 ? M1_GEMV_BWD2_RANK1 : M1_GEMV_BWD2;
 #define APA_GB2(T, ST)                                                                        \
   hipLaunchKernelGGL((m1_att_gemv_bwd2_kernel<T, ST>), dim3(nb), dim3(nthr), 0, st,               \
                      static_cast<const T*>(Xatt), Wa, dZatt, ST ? static_cast<T*>(dXatt) : nullptr, \
@@ -1031,14 +1054,17 @@ int m1_backward(const void* X, const void* Xatt, const float* Wa, const float* b
     } else if (rank1) {
       set_error("attn_pool M=1: APA_FLAG_DXATT_RANK1: Ca=%d not served by the register-resident GEMV", Ca);
       return APA_ERR_UNSUPPORTED;
-    } else if (dtype == APA_DTYPE_F32)
-      hipLaunchKernelGGL(m1_att_gemv_bwd_kernel<float>, dim3(nb), dim3(256), shm, st,
-                         static_cast<const float*>(Xatt), Wa, dZatt, static_cast<float*>(dXatt),
-                         pdwa, pdba, NP, Ca);
-    else
-      hipLaunchKernelGGL(m1_att_gemv_bwd_kernel<bf16_t>, dim3(nb), dim3(256), shm, st,
-                         static_cast<const bf16_t*>(Xatt), Wa, dZatt, static_cast<bf16_t*>(dXatt),
-                         pdwa, pdba, NP, Ca);
+    } else {
+      if (tr) tr->gemv = M1_GEMV_BWD;
+      if (dtype == APA_DTYPE_F32)
+        hipLaunchKernelGGL(m1_att_gemv_bwd_kernel<float>, dim3(nb), dim3(256), shm, st,
+                           static_cast<const float*>(Xatt), Wa, dZatt, static_cast<float*>(dXatt),
+                           pdwa, pdba, NP, Ca);
+      else
+        hipLaunchKernelGGL(m1_att_gemv_bwd_kernel<bf16_t>, dim3(nb), dim3(256), shm, st,
+                           static_cast<const bf16_t*>(Xatt), Wa, dZatt, static_cast<bf16_t*>(dXatt),
+                           pdwa, pdba, NP, Ca);
+    }
     APA_LAUNCH_CHECK("m1_att_gemv_bwd_kernel");
     nred = nb;
     cred = Ca;
@@ -1047,6 +1073,7 @@ int m1_backward(const void* X, const void* Xatt, const float* Wa, const float* b
                        ? reinterpret_cast<uint64_t*>(static_cast<uintptr_t>(offset))
                        : nullptr;
   if (dbg_skip() & 128) return APA_OK;
+  if (tr) { tr->reduce = small_ok ? M1_REDUCE_COLSUM : M1_REDUCE_BWD_REDUCE; tr->rng_bump = bump != nullptr; }
   if (small_ok) return m1_colsum(pdwa, pdba, dWa, dba, nred, cred, cred, bump, st);
   hipLaunchKernelGGL(m1_bwd_reduce_kernel, dim3((cred + 63) / 64 + 1), dim3(256), 0, st, pdwa, pdba,
                      dWa, dba, abar, G, dbt, nred, cred, N, K, 1, bump);

@@ -131,6 +131,7 @@ bool m1_cat_supported(int J) { return J >= 1 && J <= CAT_MAX_J; }
 int m1_cat_forward(const CatFeat& cat, const float* att, const float* Wt, float* logits, int N, int P,
                    int C, int K, bool train, const M1Rng& r, hipStream_t st) {
   const uint64_t ebase = (uint64_t)N * P * C;
+  if (M1Trace* t = m1_trace()) t->cat_fwd = cat.J;
   hipLaunchKernelGGL(m1_cat_pool_kernel, dim3(N), dim3(256), 0, st, cat.Xext, att, cat.zext, P, cat.J, ebase,
                      train ? 1 : 0, r.inv_keep, r.thresh, r.seed, r.offset, r.offset_dev);
   APA_LAUNCH_CHECK("m1_cat_pool_kernel");
@@ -144,6 +145,7 @@ int m1_cat_backward(const CatFeat& cat, const float* att, const float* G, const 
                     float* e_out, int N, int P, int C, int K, bool softmax, bool train, const M1Rng& r,
                     hipStream_t st) {
   const uint64_t ebase = (uint64_t)N * P * C;
+  if (M1Trace* t = m1_trace()) t->cat_bwd = cat.J;
   hipLaunchKernelGGL(m1_cat_bwd_kernel, dim3(N + 1), dim3(256), 0, st, cat.Xext, att, cat.zext, G,
                      Wt + (size_t)C * K, cat.dXext, dWt + (size_t)C * K, e_out, N, P, cat.J, K, ebase,
                      softmax ? 1 : 0, train ? 1 : 0, r.inv_keep, r.thresh, r.seed, r.offset, r.offset_dev);

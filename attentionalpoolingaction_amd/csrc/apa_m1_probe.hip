@@ -1,0 +1,105 @@
+// apa_m1_probe.hip -- test-only access to the M == 1 dispatch (tests/test_m1_paths_gpu.py).
+//
+// Linked with apa_gemm_probe.hip and the product objects into libapa_gemm_probe.so (never into libapa_hip.so).
+// Each wrapper runs one of the product's own extern "C" entry points with the same arguments while the calling
+// thread's M1Trace pointer (apa_internal.h) is set, so the tests read back which kernel families, template
+// instances, plan and reduce forms served the call.  The trace is zeroed first; the pointer is cleared afterwards.
+#include "apa_internal.h"
+
+namespace {
+constexpr int64_t M1_PROBE_VERSION = 1;   // its own version: the GEMM half (apa_gemm_probe.hip) keeps its ABI
+
+struct TraceScope {
+  explicit TraceScope(apa::M1Trace* t) {
+    if (t) *t = apa::M1Trace{};
+    apa::g_m1_trace = t;
+  }
+  ~TraceScope() { apa::g_m1_trace = nullptr; }
+};
+}  // namespace
+
+extern "C" {
+
+int64_t apa_probe_m1_version(void) { return M1_PROBE_VERSION; }
+int64_t apa_probe_m1_trace_size(void) { return (int64_t)sizeof(apa::M1Trace); }
+
+// out[0..3] = S, ppb, nblk, lsplits of the plan both passes use
+void apa_probe_m1_plan(int N, int P, int C, int Ca, int K, int64_t* out) {
+  const apa::M1Plan pl = apa::m1_plan(N, P, C, Ca, K);
+  out[0] = pl.S; out[1] = pl.ppb; out[2] = pl.nblk; out[3] = pl.lsplits;
+}
+
+// which families have an instance for (C, dtype), and which small-product kernels accept (C, K):
+// bit 0 stream, 1 per-pixel vec, 2 generic, 3 m1_logits2, 4 m1_small (m1_logits / bwd_small / head), 5 bwd_head
+int apa_probe_m1_support(int N, int C, int K, int dtype) {
+  return (apa::m1s_supported(C, dtype) ? 1 : 0) | (apa::m1_vec_supported(C, dtype) ? 2 : 0) |
+         (apa::m1g_supported(C, dtype) ? 4 : 0) | (apa::m1_logits2_supported(C, K) ? 8 : 0) |
+         (apa::m1_small_supported(C, K) ? 16 : 0) | (apa::m1_bwd_head_supported(N, C, K) ? 32 : 0);
+}
+
+int apa_probe_m1_fwd_ex(apa::M1Trace* t, const apa_hooks* hooks, const void* X, const void* Xatt, const float* Wa,
+                        const float* ba, const float* Wt, const float* bt, float* logits, float* att, float* zsave,
+                        float* abar, void* topdown, void* ws, size_t ws_bytes, int N, int P, int C, int Ca, int K,
+                        int M, unsigned flags, float keep_prob, uint64_t seed, uint64_t offset, int dtype,
+                        void* stream) {
+  TraceScope s(t);
+  return apa_attn_pool_fwd_ex(hooks, X, Xatt, Wa, ba, Wt, bt, logits, att, zsave, abar, topdown, ws, ws_bytes, N, P,
+                              C, Ca, K, M, flags, keep_prob, seed, offset, dtype, stream);
+}
+
+int apa_probe_m1_bwd_ex(apa::M1Trace* t, const apa_hooks* hooks, const void* X, const void* Xatt, const float* Wa,
+                        const float* ba, const float* Wt, const float* bt, const float* att, const float* zsave,
+                        const float* abar, const float* G, void* dX, void* dXatt, float* dWa, float* dba,
+                        float* dWt, float* dbt, void* ws, size_t ws_bytes, int N, int P, int C, int Ca, int K,
+                        int M, unsigned flags, float keep_prob, uint64_t seed, uint64_t offset, int dtype,
+                        void* stream) {
+  TraceScope s(t);
+  return apa_attn_pool_bwd_ex(hooks, X, Xatt, Wa, ba, Wt, bt, att, zsave, abar, G, dX, dXatt, dWa, dba, dWt, dbt,
+                              ws, ws_bytes, N, P, C, Ca, K, M, flags, keep_prob, seed, offset, dtype, stream);
+}
+
+int apa_probe_m1_fwd_cat(apa::M1Trace* t, const apa_concat_feat* cat, const apa_hooks* hooks, const void* X,
+                         const void* Xatt, const float* Wa, const float* ba, const float* Wt, const float* bt,
+                         float* logits, float* att, float* zsave, float* abar, void* topdown, void* ws,
+                         size_t ws_bytes, int N, int P, int C, int Ca, int K, int M, unsigned flags, float keep_prob,
+                         uint64_t seed, uint64_t offset, int dtype, void* stream) {
+  TraceScope s(t);
+  return apa_attn_pool_fwd_cat(cat, hooks, X, Xatt, Wa, ba, Wt, bt, logits, att, zsave, abar, topdown, ws, ws_bytes,
+                               N, P, C, Ca, K, M, flags, keep_prob, seed, offset, dtype, stream);
+}
+
+int apa_probe_m1_bwd_cat(apa::M1Trace* t, const apa_concat_feat* cat, const apa_hooks* hooks, const void* X,
+                         const void* Xatt, const float* Wa, const float* ba, const float* Wt, const float* bt,
+                         const float* att, const float* zsave, const float* abar, const float* G, void* dX,
+                         void* dXatt, float* dWa, float* dba, float* dWt, float* dbt, void* ws, size_t ws_bytes,
+                         int N, int P, int C, int Ca, int K, int M, unsigned flags, float keep_prob, uint64_t seed,
+                         uint64_t offset, int dtype, void* stream) {
+  TraceScope s(t);
+  return apa_attn_pool_bwd_cat(cat, hooks, X, Xatt, Wa, ba, Wt, bt, att, zsave, abar, G, dX, dXatt, dWa, dba, dWt,
+                               dbt, ws, ws_bytes, N, P, C, Ca, K, M, flags, keep_prob, seed, offset, dtype, stream);
+}
+
+int apa_probe_m1_train_step_ex(apa::M1Trace* t, const apa_hooks* hooks, const void* X, const void* Xatt,
+                               const float* Wa, const float* ba, const float* Wt, const float* bt,
+                               const int64_t* labels, float loss_wt, float grad_scale, float* logits, float* att,
+                               float* zsave, float* abar, float* loss, float* G, void* dX, void* dXatt, float* dWa,
+                               float* dba, float* dWt, float* dbt, void* ws, size_t ws_bytes, int N, int P, int C,
+                               int Ca, int K, int M, unsigned flags, float keep_prob, uint64_t seed, uint64_t offset,
+                               int dtype, void* stream) {
+  TraceScope s(t);
+  return apa_attn_head_train_step_ex(hooks, X, Xatt, Wa, ba, Wt, bt, labels, loss_wt, grad_scale, logits, att, zsave,
+                                     abar, loss, G, dX, dXatt, dWa, dba, dWt, dbt, ws, ws_bytes, N, P, C, Ca, K, M,
+                                     flags, keep_prob, seed, offset, dtype, stream);
+}
+
+int apa_probe_m1_eval_step(apa::M1Trace* t, const void* X, const void* Xatt, const float* Wa, const float* ba,
+                           const float* Wt, const float* bt, const int64_t* labels, float* logits, float* att,
+                           float* zsave, float* abar, float* loss, float* probs, int64_t* pred, void* ws,
+                           size_t ws_bytes, int N, int P, int C, int Ca, int K, int M, unsigned flags, int dtype,
+                           void* stream) {
+  TraceScope s(t);
+  return apa_attn_head_eval_step(X, Xatt, Wa, ba, Wt, bt, labels, logits, att, zsave, abar, loss, probs, pred, ws,
+                                 ws_bytes, N, P, C, Ca, K, M, flags, dtype, stream);
+}
+
+}  // extern "C"

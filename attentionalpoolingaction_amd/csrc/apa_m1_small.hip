@@ -1004,6 +1004,7 @@ static int launch_logits2(const float* z, const float* Wt, float* part_ws, int N
   constexpr int KG = 7;
   const int ktiles = (K + 15) / 16;
   const int nsub = logits2_nsub(N, C);
+  if (M1Trace* t = m1_trace()) t->logits_nsub = nsub;
   dim3 grid(C / (64 * nsub), (ktiles + KG - 1) / KG, (N + 31) / 32);
   const size_t shm = (size_t)4 * 2 * KG * 256 * sizeof(float);   // 56 KB
   hipLaunchKernelGGL((m1_logits2_kernel<KG>), grid, dim3(256), shm, st, z, Wt, part_ws, N, C, K, nsub);
@@ -1048,8 +1049,10 @@ int m1_logits2_xent(const float* z, const float* Wt, const float* abar, const fl
       hipLaunchKernelGGL((m1_logits_xent_kernel<NV4, false>), dim3(N), dim3(256), 0, st, part_ws,    \
                          abar, bt, labels, logits, loss, G, probs, pred, N, K, nparts, gscale);      \
   } while (0)
-  if (K <= 128) APA_LX(1);
-  else if (K <= 256) APA_LX(2);
+  const int nv4 = K <= 128 ? 1 : (K <= 256 ? 2 : 4);
+  if (M1Trace* t = m1_trace()) t->logits_nv4 = nv4;
+  if (nv4 == 1) APA_LX(1);
+  else if (nv4 == 2) APA_LX(2);
   else APA_LX(4);
 #undef APA_LX
   APA_LAUNCH_CHECK("m1_logits_xent_kernel");
@@ -1066,6 +1069,7 @@ int m1_bwd_small(const float* G, const float* Wt, const float* zsave, const floa
   const size_t shm = shmA > shmB ? shmA : shmB;
   // vectors per thread to stage a 32-row G tile: ceil(32*K/4/256)
   const int maxv = (8 * K + 255) / 256;
+  if (M1Trace* t = m1_trace()) t->head_mv = maxv <= 4 ? 4 : (maxv <= 8 ? 8 : (maxv <= 13 ? 13 : 26));
 #define APA_BS(MV)                                                                               \
   do {                                                                                           \
     if (shm > 64 * 1024) {                                                                       \
@@ -1100,7 +1104,9 @@ int m1_bwd_head(const float* G, const float* Wt, const float* zsave, const float
   const int nb = C / 16;
   const int kpb = (K + nb - 1) / nb;
   const int ug = (((K + 15) / 16) + 3) / 4;
+  M1Trace* const tr = m1_trace();
   if (N > 32 && ug <= 7 && knob("APA_M1_BWD_HEAD_TILES", 1)) {   // several image tiles: the pipelined form
+    if (tr) { tr->head = M1_HEAD_TILES; tr->head_ug = ug <= 1 ? 1 : (ug <= 2 ? 2 : (ug <= 4 ? 4 : 7)); }
 #define APA_BHT(UG)                                                                                      \
   hipLaunchKernelGGL(m1_bwd_head_tiles_kernel<UG>, dim3(2 * nb), dim3(256), 0, st, G, Wt, zsave, abar, \
                      bt, dz, dWt, dbt, sn, N, C, K, loss, lscale)
@@ -1112,6 +1118,7 @@ int m1_bwd_head(const float* G, const float* Wt, const float* zsave, const float
     APA_LAUNCH_CHECK("m1_bwd_head_tiles_kernel");
     return APA_OK;
   }
+  if (tr) { tr->head = M1_HEAD_ROWS; tr->head_ug = ug <= 1 ? 1 : (ug <= 2 ? 2 : (ug <= 4 ? 4 : (ug <= 7 ? 7 : 13))); }
 #define APA_BH(UG)                                                                                \
   hipLaunchKernelGGL(m1_bwd_head_kernel<UG>, dim3(2 * nb), dim3(256), 0, st, G, Wt, zsave, abar, \
                      bt, dz, dWt, dbt, sn, N, C, K, kpb, loss, lscale)

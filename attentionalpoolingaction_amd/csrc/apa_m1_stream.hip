@@ -660,6 +660,7 @@ static int launch_fwd_t(bool fused, bool train, int nblk, hipStream_t st, const 
                         int P, int S, int act, const M1Rng& r) {
   const T* x = static_cast<const T*>(X);
   uint8_t* mbits = r.maskbits_out;
+  if (M1Trace* t = m1_trace()) { t->pool_fwd = M1_POOL_STREAM; t->fwd_w = VW; t->fwd_pix = PIX; }
   if (r.relu_input) {   // instantiated for the default chunk width and the fused map only
     if (!fused || PIX != DefPix<T, VW>::V) {
       set_error("attn_pool M=1 stream kernels: APA_FLAG_RELU_INPUT needs Xatt == X");
@@ -698,6 +699,8 @@ static int launch_bwd_t(bool fused, bool train, int nblk, hipStream_t st, const 
   const float* ex = dA_extra ? dA_extra : att;
   const float exs = dA_extra ? 1.0f : 0.0f;
   const uint8_t* mbits = r.maskbits_in;    // non-null: the forward call's keep-bits (APA_FLAG_WS_FROM_FWD)
+  M1Trace* const tr = m1_trace();
+  if (tr) { tr->pool_bwd = M1_POOL_STREAM; tr->bwd_w = VW; tr->bwd_pix = PIX; }
   if (r.relu_input) {
     if (!fused || PIX != DefPix<T, VW>::V) {
       set_error("attn_pool M=1 stream kernels: APA_FLAG_RELU_INPUT needs Xatt == X");
@@ -730,6 +733,7 @@ static int launch_bwd_t(bool fused, bool train, int nblk, hipStream_t st, const 
       bits_done = true;
     }
   }
+  if (tr) tr->keep_bits = bits_done;
   if (r.no_dx && !bits_done) {
     set_error("m1 stream kernels: APA_IFLAG_NO_DX without the keep-bits backward form (internal)");
     return APA_ERR_UNSUPPORTED;

@@ -316,23 +316,32 @@ def test_m1_batch_and_class_tails(gpu, N, K):
     _grads_close(got, ref, ('dX', 'dWa', 'dba', 'dWt', 'dbt'))
 
 
-@pytest.mark.parametrize('target_blocks', [4, 12, 64])
+# (ids 4 / 12 / 64: the block targets that used to name these three plans)
+@pytest.mark.parametrize('N,S', [(342, 1), (170, 3), (32, 16)], ids=['4', '12', '64'])
 @pytest.mark.parametrize('mode', ['id', 'softmax_dropout', 'sep_att', 'bf16', 'c1024'])
-def test_m1_stream_kernels_pixel_chunking(gpu, monkeypatch, target_blocks, mode):
-    """The channel-split streaming kernels process a block's pixels in chunks of <= 16.  Force
-    S = 1 / 3 / 16 splits per image (13 / 5 / 1 chunks per block at 14x14) and check every variant
-    against the oracle; APA_M1_STREAM=0 must give the same answer from the per-pixel kernels."""
+def test_m1_stream_kernels_pixel_chunking(gpu, N, S, mode):
+    """The channel-split streaming kernels process a block's pixels in chunks (1 pixel for fp32 C <= 2048, 2 for
+    bf16).  The batch size picks S = 1 / 3 / 16 splits per image (m1_plan, asserted through the test-only probe):
+    196 / 65-66 / 12-13 pixels per block at 14x14, so an odd chunk count and, in bf16, a partial last chunk.  Every
+    variant is checked against the float64 oracle, run on the device."""
     from attentionalpoolingaction_amd.custom_ops import custom_ops_factory as cof
-    monkeypatch.setenv('APA_M1_TARGET_BLOCKS', str(target_blocks))
+    from tests import _m1_probe as mp
     C = 1024 if mode == 'c1024' else 2048
-    inp = make_head_inputs(N=4, H=14, W=14, C=C, K=51, Ca=768 if mode == 'sep_att' else None,
+    Ca = 768 if mode == 'sep_att' else C
+    plan_S, ppb, _, _ = mp.plan(N, 196, C, Ca, 51)
+    assert (plan_S, ppb) == (S, -(-196 // S)), (plan_S, ppb)
+    inp = make_head_inputs(N=N, H=14, W=14, C=C, K=51, Ca=768 if mode == 'sep_att' else None,
                            seed=77, dtype=torch.bfloat16 if mode == 'bf16' else torch.float32)
     softmax = mode in ('softmax_dropout', 'c1024')
     train = mode == 'softmax_dropout'
     keep, seed, offset = 0.5, 5, 11
-    mask = cof.dropout_mask(tuple(inp['X'].shape), keep, seed, offset).cpu() if train else None
+    mask = cof.dropout_mask(tuple(inp['X'].shape), keep, seed, offset) if train else None
     flags = orc.AttnFlags(single_layer_att=(mode != 'sep_att'), softmax_att=softmax)
-    ref = _oracle(inp, flags, train=train, keep=keep, mask=mask)
+    dinp = {k: (v.to(gpu) if torch.is_tensor(v) else v) for k, v in inp.items()}
+    if mode != 'sep_att':
+        dinp['Xatt'] = dinp['X']
+    ref = _oracle(dinp, flags, train=train, keep=keep, mask=mask)
+    ref = {k: v.cpu() for k, v in ref.items()}
     got = _run_hip(inp, gpu, softmax=softmax, train=train, keep=keep, seed=seed, offset=offset)
     _close(got['logits'], ref['logits'], TIGHT, 'logits')
     _close(got['att'].reshape(ref['att'].shape), ref['att'], TIGHT, 'attention map')

@@ -66,3 +66,92 @@ def test_gpu_case_table_covers_every_path():
     assert not missing, sorted(missing, key=str)
     names = [c['name'] for c in t.CASES + t.TWIN_CASES]
     assert len(names) == len(set(names))
+
+
+# ------------------------------------------------------------------------------------------ M == 1 dispatch trace
+def test_m1_probe_symbols_and_plan():
+    from tests import _m1_probe as mp
+    lib = mp.load_m1_probe()           # asserts the trace struct size
+    assert lib.apa_probe_m1_trace_size() == ctypes.sizeof(mp.M1Trace) == 4 * len(mp.M1Trace._fields_)
+    for name in mp.M1_SYMBOLS:
+        assert hasattr(lib, name), name
+    prod = cof.load_library()
+    for name in mp.M1_SYMBOLS:
+        assert not hasattr(prod, name), 'libapa_hip.so exports ' + name
+    # hand-checked plans: S = round(512 / N) clamped to [1, min(P / 4, 256)], ppb = ceil(P / S)
+    assert mp.plan(32, 196, 2048, 2048, 393)[:3] == (16, 13, 512)      # cfg 002
+    assert mp.plan(33, 225, 2048, 2048, 393)[:3] == (16, 15, 528)
+    assert mp.plan(170, 196, 2048, 2048, 51)[:2] == (3, 66)
+    assert mp.plan(342, 196, 1024, 1024, 51)[:2] == (1, 196)
+    assert mp.plan(6, 49, 1024, 1024, 51)[:2] == (12, 5)                # clamped to P / 4
+    assert mp.plan(1, 4, 2048, 2048, 51)[:2] == (1, 4)                  # P < 8: one split
+
+
+def test_m1_unreachable_instances_are_recorded():
+    """The instances _m1_probe.UNREACHABLE names are never launched by the product build: every C they would serve is
+    served first by the streaming kernels (vec), and m1_logits2 accepts every C that m1_logits does."""
+    from tests import _m1_probe as mp
+    F32, BF16 = cof.APA_DTYPE_F32, cof.APA_DTYPE_BF16
+    for name, (kind, dt, C) in mp.UNREACHABLE.items():
+        if kind == 'vec':
+            sup = mp.support(8, C, 51, F32 if dt == 'f32' else BF16)
+            assert sup & mp.SUP_VEC and sup & mp.SUP_STREAM, name
+    for C in range(128, 8193, 128):
+        for K in (1, 51, 393, 736):
+            sup = mp.support(8, C, K, F32)
+            assert not (sup & mp.SUP_SMALL) or sup & mp.SUP_LOGITS2, (C, K)
+    # and the reachable vec instances are not streaming C's
+    for dt, Cs in ((F32, (256, 512)), (BF16, (512, 1024))):
+        for C in Cs:
+            sup = mp.support(8, C, 51, dt)
+            assert sup & mp.SUP_VEC and not sup & mp.SUP_STREAM, (dt, C)
+
+
+def test_m1_gpu_case_table_covers_every_reachable_trace_value():
+    from tests import test_m1_paths_gpu as t
+    reached = set()
+    for c in t.CASES:
+        e = dict(c['expect'])
+        pool = e.get('pool_fwd')
+        if pool:
+            reached.add(('pool', pool, c['dt'], e.get('fwd_w'), e.get('fwd_pix')))
+            if c['relu_in']:
+                reached.add(('relu_input', c['dt'], e.get('fwd_w')))
+        for k in ('S', 'cw', 'logits', 'head', 'gemv', 'reduce', 'keep_bits', 'rng_bump', 'cat_fwd'):
+            if k in e:
+                reached.add((k, e[k]))
+        if e.get('logits') in ('xent', 'xent_probs'):
+            reached.add(('nv4', e['logits'], e.get('logits_nv4')))
+        if 'logits_nsub' in e:
+            reached.add(('nsub', e['logits_nsub']))
+        if e.get('head') in ('tiles', 'rows'):
+            reached.add((e['head'], e.get('head_ug')))
+        if e.get('head') == 'small':
+            reached.add(('small', e.get('head_mv')))
+        if e.get('gemv'):
+            reached.add(('gemv_dt', e['gemv'], c['dt']))
+        for m in c['mis']:
+            reached.add(('misaligned', m))
+        if c['rng'] != 'hash':
+            reached.add(('rng', c['rng']))
+        reached.add(('entry', c['entry']))
+    F32, BF16 = cof.APA_DTYPE_F32, cof.APA_DTYPE_BF16
+    need = {('pool', 'stream', F32, 1, 1), ('pool', 'stream', F32, 2, 1), ('pool', 'stream', F32, 4, 2),
+            ('pool', 'stream', BF16, 1, 2),
+            ('pool', 'vec', F32, 1, None), ('pool', 'vec', F32, 2, None), ('pool', 'vec', BF16, 1, None),
+            ('pool', 'vec', BF16, 2, None), ('pool', 'generic', F32, None, None), ('pool', 'generic', BF16, None, None),
+            ('relu_input', F32, 1), ('relu_input', F32, 2), ('relu_input', F32, 4), ('relu_input', BF16, 1)}
+    need |= {('S', 1), ('S', 3), ('S', 16), ('cw', 256), ('cw', 128), ('cw', 64)}
+    need |= {('logits', v) for v in ('xent', 'xent_probs', 'logits2', 'sgemm')}
+    need |= {('nv4', 'xent', v) for v in (1, 2, 4)} | {('nv4', 'xent_probs', v) for v in (1, 2, 4)}
+    need |= {('nsub', 1), ('nsub', 4)}
+    need |= {('tiles', u) for u in (1, 2, 4, 7)} | {('rows', u) for u in (1, 2, 4, 7, 13)}
+    need |= {('small', m) for m in (4, 8, 13, 26)} | {('head', 'sgemm')}
+    need |= {('gemv_dt', g, d) for g in ('bwd2', 'bwd2_rank1', 'bwd') for d in (F32, BF16)}
+    need |= {('reduce', 'colsum'), ('reduce', 'bwd_reduce'), ('keep_bits', 1), ('rng_bump', 1)}
+    need |= {('cat_fwd', 1), ('cat_fwd', 16), ('rng', 'device'), ('rng', 'external')}
+    need |= {('misaligned', m) for m in ('zsave', 'G', 'Wt')} | {('entry', e) for e in ('sep', 'step', 'eval')}
+    missing = need - reached
+    assert not missing, sorted(missing, key=str)
+    names = [c['name'] for c in t.CASES]
+    assert len(names) == len(set(names))
