@@ -21,18 +21,9 @@ int hip_fail(hipError_t e, const char* what) {
   return APA_ERR_HIP;
 }
 
-#ifdef APA_ABLATION
-int g_dbg_skip = knob("APA_DBG_SKIP", 0);
-#endif
-
 }  // namespace apa
 
 using namespace apa;
-
-#ifdef APA_ABLATION
-extern "C" void apa_debug_set_skip(int mask) { apa::g_dbg_skip = mask; }
-
-#endif
 
 extern "C" int apa_prof_event_create(void** event) {
   if (!event) { set_error("apa_prof_event_create: null"); return APA_ERR_INVALID_ARG; }
@@ -491,12 +482,11 @@ extern "C" int apa_pose_attn_train_step(const apa_pose_attn_step_io* io, int N, 
   // The pooling pass's own dX share (A/P . dz . mask/keep) is not written and read back: the streaming backward
   // kernel becomes read-only (APA_IFLAG_NO_DX) and the pose head's dX product adds the term in its epilogue from att,
   // dz and the forward half's keep bits -- one 25.7 MB write and one 25.7 MB read less at the benchmark shape.
-  static const int nodx_knob = knob("APA_POSE_STEP_NODX", 1);
   const int wide_rows = gemm_bf16_wide_tile_rows(N * P, C, Cp);   // (its rank-1 epilogue wants <= 3 images per tile)
   // ... and only if the dX product is certain to take the wide bf16 kernel (the one with the rank-1 epilogue): all-bf16
   // operands with 16-byte addressable rows -- dPpre and the W1 operand are the workspace's (aligned) or the shadow
   // checked above, dX is the caller's
-  const bool nodx = nodx_knob && m1_no_dx_supported(C, dtype, train) && wide_rows > 0 && wide_rows <= 2 * P &&
+  const bool nodx = m1_no_dx_supported(C, dtype, train) && wide_rows > 0 && wide_rows <= 2 * P &&
                     (reinterpret_cast<uintptr_t>(s.dX) & 15) == 0 && C % 8 == 0 && Cp % 8 == 0 &&
                     dtype == APA_DTYPE_BF16;
   rc = attn_pool_bwd_impl(hk, nullptr, xf.done ? &xf : nullptr, s.X, s.Ppre, s.Wa, s.ba, s.Wt, s.bt, s.att, s.zsave,

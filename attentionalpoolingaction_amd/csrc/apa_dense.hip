@@ -579,10 +579,9 @@ __global__ __launch_bounds__(512) void pose_bwd_rows_mfma_kernel(
 
 static bool pose_rows_mfma_ok(const float* dPl, const void* dPpre_ext, const float* ext_row, const float* ext_col,
                               const float* W2, const void* Ppre, int Cp, int J, int dtype) {
-  static const int enabled = knob("APA_POSE_ROWS_MFMA", 1);
   const uintptr_t al = reinterpret_cast<uintptr_t>(dPl) | reinterpret_cast<uintptr_t>(W2) | reinterpret_cast<uintptr_t>(Ppre) |
                        reinterpret_cast<uintptr_t>(ext_col);
-  return enabled && dtype == APA_DTYPE_BF16 && dPl && J == 16 && Cp % 128 == 0 && Cp >= 256 && Cp <= 1024 &&
+  return dtype == APA_DTYPE_BF16 && dPl && J == 16 && Cp % 128 == 0 && Cp >= 256 && Cp <= 1024 &&
          (al & 15) == 0 && (!dPpre_ext || ext_row);
 }
 
@@ -595,19 +594,16 @@ static size_t pose_rows_lds(int rpb, int nthr, int dtype, bool ext) {
 // 4.6 vs 6.9 us, step -3 us in four interleaved pairs) once that still gives half the CUs a block and the tile
 // stays under the 64 KB a launch gets without opting in, else 16
 static int pose_rows_per_block(long R, int nthr, int dtype, bool ext) {
-  static const int forced = knob("APA_POSE_RPB", 0);
   int rpb = (R + 31) / 32 >= 128 ? 32 : 16;
-  if (forced == 16 || forced == 32) rpb = forced;
   if (rpb == 32 && pose_rows_lds(32, nthr, dtype, ext) > 65536) rpb = 16;
   return rpb;
 }
 
 static bool pose_bwd_rows_ok(const float* dPl, const void* Ppre, const void* ext, const float* W2, int Cp,
                              int J, int dtype) {
-  static const int enabled = knob("APA_POSE_BWD_ROWS", 1);
   const uintptr_t al = reinterpret_cast<uintptr_t>(Ppre) | reinterpret_cast<uintptr_t>(ext);
   const int nthr = ((Cp / 2 + 63) / 64) * 64;
-  return enabled && dPl && J <= 16 && Cp % 4 == 0 && Cp <= 1024 && (al & 7) == 0 &&
+  return dPl && J <= 16 && Cp % 4 == 0 && Cp <= 1024 && (al & 7) == 0 &&
          (J != 16 || (reinterpret_cast<uintptr_t>(W2) & 15) == 0) &&
          (dtype == APA_DTYPE_BF16 || dtype == APA_DTYPE_F32) &&
          pose_rows_lds(16, nthr, dtype, ext != nullptr) <= 65536;
@@ -772,8 +768,7 @@ __global__ __launch_bounds__(256) void pose_pl_kernel(const bf16_t* __restrict__
 }
 
 static bool pose_pl_fast(int Cp, int J, int dtype, const void* Ppre) {
-  static const int enabled = knob("APA_POSE_PL_FAST", 1);
-  return enabled && dtype == APA_DTYPE_BF16 && J <= 16 && (Cp == 256 || Cp == 512 || Cp == 768 || Cp == 1024) &&
+  return dtype == APA_DTYPE_BF16 && J <= 16 && (Cp == 256 || Cp == 512 || Cp == 768 || Cp == 1024) &&
          (reinterpret_cast<uintptr_t>(Ppre) & 15) == 0;
 }
 
@@ -915,9 +910,8 @@ extern "C" int apa_pose_head_fwd(const void* X, const float* W1, const float* b1
 // split that fills those 768 slots (C = 2048, Cp = 768: 192 tiles x 4) beats the generic "256 tiles of 128 x 128"
 // rule (x 3): product 33.2 -> 29.0 us, reduce 6.0 -> 6.5 us, cfg 003 step -3 us (three interleaved pairs)
 static int pose_dw1_splits(int C, int Cp, int R, int dtype) {
-  static const int s_env = knob("APA_GEMM_SPLITS", 0);
   int s = gemm_pick_splits(C, Cp, R);
-  if (dtype == APA_DTYPE_BF16 && s > 1 && s_env <= 0) {
+  if (dtype == APA_DTYPE_BF16 && s > 1) {
     const long t64 = (long)((C + 127) / 128) * ((Cp + 63) / 64);
     const long t128 = (long)((C + 127) / 128) * ((Cp + 127) / 128);
     int s2 = (int)((768 + t64 / 2) / t64);
@@ -1033,12 +1027,10 @@ static int pose_head_bwd_impl(const void* X, const float* W1, const float* W2, c
     // here and in the column sum behind (G), small blocks let a CU overlap one block's loads with another's MFMAs
     // and stores (wpb); measured at the benchmark shape (rows kernel + column sum, us): wpb 6 G 1 14.7 + 5.8,
     // 6/2 12.3 + 4.8, 4/2 11.8 + 4.9, 3/2 11.5 + 4.8, 3/4 15.1 + 4.8, 2/4 15.7 + 4.8 (the VALU form: 16.3 + 5.5)
-    static const int wpb_knob = knob("APA_POSE_ROWS_WPB", 0), grp_knob = knob("APA_POSE_ROWS_GRP", 0);
     const int nw = Cp / 64;                           // waves a whole row takes
-    int wpb = nw % 3 == 0 ? 3 : (nw % 4 == 0 ? 4 : 2);
-    if (wpb_knob >= 2 && wpb_knob <= 8 && nw % wpb_knob == 0) wpb = wpb_knob;   // (>= 128 threads: the dPl loaders)
+    const int wpb = nw % 3 == 0 ? 3 : (nw % 4 == 0 ? 4 : 2);
     const int ngrp = nw / wpb;
-    const int G = grp_knob > 0 ? grp_knob : (pl.R >= 2048 ? 2 : 1);
+    const int G = pl.R >= 2048 ? 2 : 1;
     const int nblk = (int)((pl.R + 32L * G - 1) / (32L * G));
     const size_t lds = (size_t)32 * (wpb * 64 + 8) * 2 + 32 * 20 * 4 + 32 * 4;
     const size_t ldp = pose_rows_ld(Cp, J, nthr2);
@@ -1175,9 +1167,8 @@ void* pose_ws_loss_scratch(void* ws, int N, int P, int C, int Cp, int J, int dty
 
 bool pose_step_fast_ok(int N, int P, int C, int Cp, int J, int dtype, const void* Ppre, const float* W2,
                        const float* wa) {
-  static const int enabled = knob("APA_POSE_STEP_FUSED", 1);
   const int nthr = ((Cp / 2 + 63) / 64) * 64;
-  return enabled && dtype == APA_DTYPE_BF16 && J == 16 && pose_pl_fast(Cp, J, dtype, Ppre) &&
+  return dtype == APA_DTYPE_BF16 && J == 16 && pose_pl_fast(Cp, J, dtype, Ppre) &&
          (reinterpret_cast<uintptr_t>(W2) & 15) == 0 && (reinterpret_cast<uintptr_t>(wa) & 15) == 0 &&
          Cp % 4 == 0 && Cp <= 1024 && pose_rows_lds(16, nthr, dtype, false) <= 65536 && N > 0 && P > 0 && C > 0;
 }
@@ -1365,9 +1356,8 @@ constexpr int PC_PG = 16;   // pixel groups per block of the per-class activatio
 constexpr int PC_MAX_PSPLIT = 8;   // pixel splits (grid.z) of the backward activation pass
 // pixel splits of pc_bwd_act_kernel: enough blocks to put one on most CUs; the spatial softmax needs the whole image
 static int pc_bwd_act_psplit(int N, int kgroups, int P, int act) {
-  static const int ps_env = knob("APA_PC_ACT_PSPLIT", 0);
   if (act == 2) return 1;
-  int ps = ps_env > 0 ? ps_env : (256 + N * kgroups - 1) / (N * kgroups);   // HMDB-51 shape, N = 32: 7.9 -> 4.9 us
+  int ps = (256 + N * kgroups - 1) / (N * kgroups);   // HMDB-51 shape, N = 32: 7.9 -> 4.9 us
   if (ps > PC_MAX_PSPLIT) ps = PC_MAX_PSPLIT;
   while (ps > 1 && (P + ps - 1) / ps < PC_PG) --ps;      // at least one pixel per pixel group
   return ps < 1 ? 1 : ps;
@@ -1625,8 +1615,7 @@ static PcDropArgs pc_drop_args(const void* X, void* Xd, long R, int C, float kee
 // is ONE product over the concatenated contraction (the wide kernel's mid-contraction mask) instead of a product plus
 // a read-modify-write product over the 25.7 MB result.  The forward / dW products read the halves with ld = 2 Kp.
 static bool pc_cat(const void* X, int C, int Ca, int dtype) {
-  static const int enabled = knob("APA_PC_CAT", 1);
-  return enabled && dtype == APA_DTYPE_BF16 && Ca == C && C % 8 == 0 && (reinterpret_cast<uintptr_t>(X) & 15) == 0;
+  return dtype == APA_DTYPE_BF16 && Ca == C && C % 8 == 0 && (reinterpret_cast<uintptr_t>(X) & 15) == 0;
 }
 
 size_t pc_workspace_bytes(int N, int P, int C, int Ca, int K, int dtype) {
@@ -1657,7 +1646,7 @@ int pc_weight_images(const float* Wa, const float* ba, const float* Wt, const fl
   char* w = static_cast<char*>(ws);
   const int Kp = pl.Kp;
   const bool wb16 = dtype == APA_DTYPE_BF16;
-  const bool cat = wb16 && Ca == C && C % 8 == 0 && knob("APA_PC_CAT", 1);
+  const bool cat = wb16 && Ca == C && C % 8 == 0;
   const int ldw = cat ? 2 * Kp : Kp;
   void* WtP = w + pl.off_wtp;
   void* WaP = cat ? static_cast<void*>(static_cast<bf16_t*>(WtP) + Kp) : static_cast<void*>(w + pl.off_wap);
@@ -1675,7 +1664,7 @@ int pc_weight_images(const float* Wa, const float* ba, const float* Wt, const fl
       n += pads.describe(roles, K, maps + n);
     }
   }
-  if (wb16 && Ca == C && K <= 64 && C % 256 == 0 && knob("APA_PC_FUSED", 1)) {   // pc_fused_supported, minus X
+  if (wb16 && Ca == C && K <= 64 && C % 256 == 0) {   // pc_fused_supported, minus X
     const PcFusedWs f = pc_fused_carve(w + pl.off_fused, N, P, C);
     const int rc = pc_fused_prep(f, Wa, Wt, ba, bt, C, K, st, nullptr, true);
     if (rc != APA_OK) return rc;
@@ -1727,20 +1716,17 @@ int pc_forward(const void* X, const void* Xatt, const float* Wa, const float* ba
     // Round 5, the one-call train step with caller-kept weight images: NO preparation launch -- the keep bits of this
     // step were written by the previous step's last launch (pc_dw_reduce_kernel's extra blocks) and are believed iff
     // their tag says so; else the forward kernel hashes them itself (first step on a workspace, a jump of the offset)
-    static const int tagged_knob = knob("APA_PC_TAGGED_BITS", 1);
-    const bool tagged = tagged_knob && train && (flags & APA_FLAG_WEIGHT_IMAGES) && xf && xf->labels;
+    const bool tagged = train && (flags & APA_FLAG_WEIGHT_IMAGES) && xf && xf->labels;
     const bool prebits = train && !tagged;
     const PcPrepBits pb = {(size_t)R * C, keep_prob, seed, devctr ? 0 : offset, offd};
     int rc = APA_OK;
     if (!tagged) rc = pc_fused_prep(f, Wa, Wt, ba, bt, C, K, st, prebits ? &pb : nullptr, !(flags & APA_FLAG_WEIGHT_IMAGES));
     if (rc != APA_OK) return rc;
-    static const int fold_xent = knob("APA_PC_XENT_FOLD", 1);
-    static const int fold_act = knob("APA_PC_ACT_FOLD", 1);
-    const bool xent_here = fold_xent && xf && xf->labels && xf->G && xf->loss && !xf->probs && K >= 4 && K <= 64;
+    const bool xent_here = xf && xf->labels && xf->G && xf->loss && !xf->probs && K >= 4 && K <= 64;
     // identity / relu attention: the activation pass rides on the product's epilogue (a block's 32 rows touch at most
     // two images when P >= 32); the softmax needs the whole image's Z first and keeps its own launch
     const int act = act_code(flags);
-    const bool fold = fold_act && act != 2 && !topdown && P >= 32;
+    const bool fold = act != 2 && !topdown && P >= 32;
     const PcFwdFold ff = {att, act, P};
     rc = pc_fused_forward(f, X, Z, Tsave, R, C, K, train, keep_prob, seed, devctr ? 0 : offset, offd, st, prebits,
                           fold ? &ff : nullptr, tagged);
@@ -1821,8 +1807,7 @@ int pc_forward(const void* X, const void* Xatt, const float* Wa, const float* ba
   APA_LAUNCH_CHECK("pc_fwd_act_kernel");
   // one-call train step: the cross-entropy of the logits row is taken by the backward activation pass (one launch
   // less); the batch mean rides on the column-sum launch that ends the backward half
-  static const int fold_xent = knob("APA_PC_XENT_FOLD", 1);
-  if (fold_xent && xf && xf->labels && xf->G && xf->loss && !xf->probs && K >= 4 && K <= 1024) {
+  if (xf && xf->labels && xf->G && xf->loss && !xf->probs && K >= 4 && K <= 1024) {
     xf->done = true;
     xf->deferred = true;
     xf->logits = logits;
@@ -1877,8 +1862,7 @@ int pc_backward(const void* X, const void* Xatt, const float* Wa, const float* W
       if (xf && xf->done) { tail.aux_src = xf->loss + 1; tail.aux_n = -N; tail.aux_scale = xf->lscale; tail.aux_dst = xf->loss; }
       // the same condition as pc_forward's `tagged` (WS_FROM_FWD is set by the library's own train step only): this
       // launch is the step's last -- it also leaves the NEXT step's keep bits behind, tagged (seed, offset + 1)
-      static const int tagged_knob = knob("APA_PC_TAGGED_BITS", 1);
-      if (tagged_knob && train && (flags & APA_FLAG_WEIGHT_IMAGES) && (flags & APA_FLAG_WS_FROM_FWD)) {
+      if (train && (flags & APA_FLAG_WEIGHT_IMAGES) && (flags & APA_FLAG_WS_FROM_FWD)) {
         tail.next_bits = true;
         tail.next_seed = seed;
       }
@@ -1896,15 +1880,13 @@ int pc_backward(const void* X, const void* Xatt, const float* Wa, const float* W
     PcDwTail tail = {pdbt, dbt, dba, N * ps, bump, nullptr, 0, 0.f, nullptr};
     // (aux_n < 0: the batch mean in apa_softmax_xent_fwd_bwd's own summation order -- bit-identical loss[0])
     if (xf && xf->done) { tail.aux_src = xf->loss + 1; tail.aux_n = -N; tail.aux_scale = xf->lscale; tail.aux_dst = xf->loss; }
-    static const int tagged_knob2 = knob("APA_PC_TAGGED_BITS", 1);
-    if (tagged_knob2 && train && (flags & APA_FLAG_WEIGHT_IMAGES) && (flags & APA_FLAG_WS_FROM_FWD)) {
+    if (train && (flags & APA_FLAG_WEIGHT_IMAGES) && (flags & APA_FLAG_WS_FROM_FWD)) {
       tail.next_bits = true;      // (see the identity / relu branch above)
       tail.next_seed = seed;
     }
     // dX = (dT . Wt^T) * mask/keep + dZ . Wa^T: one launch over the concatenated k = 128.  (Round 5: BEFORE the dW
     // launches -- the reduce tail that ends them may overwrite the keep-bit map with the next step's.)
-    static const int exp_mask = knob("APA_PC_EXP", 0);
-    if (train && !(exp_mask & 1)) {
+    if (train) {
       rc = gemm_bf16_mid_dropout(f.dTdZ, 128, f.Wcat2, 128, dX, C, R, C, 128, 1.0f / keep_prob, f.maskbits, st);
     } else {
       GemmDesc g;

@@ -392,8 +392,6 @@ size_t gemm_ws_bytes(int M, int N, int splits) {
 int gemm_pick_splits(int M, int N, int K) {
   const int tiles = ((M + GM - 1) / GM) * ((N + GN - 1) / GN);
   if (tiles >= 128 || K <= 4 * GK) return 1;
-  static const int s_env = knob("APA_GEMM_SPLITS", 0);
-  if (s_env > 0) return s_env;
   int s = (256 + tiles - 1) / tiles;
   const int maxs = K / (4 * GK) > 0 ? K / (4 * GK) : 1;
   if (s > maxs) s = maxs;
@@ -477,8 +475,7 @@ static int gemm_launch_t(const GemmDesc& d, hipStream_t st) {
       tw.N = d.twin->n_valid > 0 ? d.twin->n_valid : d.twin->N;
     }
     const bool vec = pN % 4 == 0 && aligned16(d.ws) && (!twin || aligned16(d.twin->ws));
-    static const int ride = knob("APA_GEMM_REDUCE_TAIL", 1);
-    if (vec && !twin && d.tail && !d.tail->done && ride) {
+    if (vec && !twin && d.tail && !d.tail->done) {
       const ColsumJob& c = *d.tail;
       ColsumJobDev j;
       j.pdwa = c.pdwa; j.dwa = c.dwa; j.nblk = c.nblk; j.C = c.C; j.ld = c.ld; j.rng_bump = c.rng_bump;

@@ -54,32 +54,6 @@ struct Hooks {
   }
 };
 
-// The shipped library has ONE code path and never reads the environment.  The A/B knobs of the development
-// builds (`make ABLATE=1`, -DAPA_ABLATION: tools/fuzz_arms.sh, profiling experiments) go through knob(): in the
-// product build it is a constant expression equal to the default, the name strings are not even linked in
-// (`strings libapa_hip.so | grep '^APA_'` prints nothing).
-#ifdef APA_ABLATION
-inline int knob(const char* name, int dflt) {
-  const char* s = getenv(name);
-  return (s && *s) ? atoi(s) : dflt;
-}
-#else
-constexpr int knob(const char*, int dflt) { return dflt; }
-#endif
-
-// Ablation hook for profiling experiments only (make ABLATE=1): a bit mask of kernels NOT to launch
-// (results are then wrong by construction).  Compiled out of the product build.
-#ifdef APA_ABLATION
-// in-kernel timestamps (s_memtime, shader clock): slot[blk * 8 + i]
-// (define `__device__ unsigned long long apa_dbg_ts[4096];` in the TU under test)
-#define APA_TS(i) do { if ((threadIdx.x & 63) == 0 && (threadIdx.x >> 6) == 0 && blockIdx.x < 512) apa_dbg_ts[blockIdx.x * 8 + (i)] = __builtin_readcyclecounter(); } while (0)
-extern int g_dbg_skip;
-inline int dbg_skip() { return g_dbg_skip; }
-#else
-#define APA_TS(i) do {} while (0)
-constexpr int dbg_skip() { return 0; }
-#endif
-
 // Launch `kernel`; with a start / stop event the launch goes through hipExtLaunchKernel, which brackets
 // exactly this dispatch with the two events.
 template <typename... KArgs, typename... Args>
@@ -261,8 +235,8 @@ M1Plan m1_plan(int N, int P, int C, int Ca, int K);
 // What the M == 1 path ran (filled on the host only, read by the kernel-level tests through the test-only probe
 // library).  The product never sets the pointer: m1_trace() is null there and nothing is recorded.
 enum M1Pool { M1_POOL_NONE = 0, M1_POOL_STREAM, M1_POOL_VEC, M1_POOL_GENERIC };
-enum M1Logits { M1_LOGITS_NONE = 0, M1_LOGITS_XENT, M1_LOGITS_XENT_PROBS, M1_LOGITS2, M1_LOGITS_PARTIAL,
-                M1_LOGITS_SGEMM };
+// (4 was the retired partial-logits form; the values are part of the probe interface and stay put)
+enum M1Logits { M1_LOGITS_NONE = 0, M1_LOGITS_XENT, M1_LOGITS_XENT_PROBS, M1_LOGITS2, M1_LOGITS_SGEMM = 5 };
 enum M1Head { M1_HEAD_NONE = 0, M1_HEAD_TILES, M1_HEAD_ROWS, M1_HEAD_SMALL, M1_HEAD_SGEMM };
 enum M1Gemv { M1_GEMV_NONE = 0, M1_GEMV_BWD2, M1_GEMV_BWD2_RANK1, M1_GEMV_BWD };
 enum M1Reduce { M1_REDUCE_NONE = 0, M1_REDUCE_COLSUM, M1_REDUCE_BWD_REDUCE };
@@ -335,9 +309,6 @@ int m1g_launch_bwd_main(int dtype, int C, bool fused, bool train, int nblk, hipS
 
 // apa_m1_small.hip: LDS-tiled f32-MFMA kernels for the small products of the M == 1 path
 bool m1_small_supported(int C, int K);
-size_t m1_logits_ws_bytes(int N, int C, int K);
-int m1_logits(const float* z, const float* Wt, const float* abar, const float* bt, float* logits,
-              float* part_ws, int N, int C, int K, hipStream_t st);
 int m1_bwd_small(const float* G, const float* Wt, const float* zsave, const float* abar,
                  const float* bt, float* dz, float* dWt, float* dbt, float* sn, int N, int C, int K,
                  hipStream_t st);

@@ -8,13 +8,6 @@
 #include "apa_device.h"
 #include "apa_internal.h"
 
-#ifdef APA_ABLATION
-namespace apa { __device__ unsigned long long apa_dbg_ts[4096]; }
-extern "C" int apa_debug_read_ts2(unsigned long long* host, int n) {
-  return (int)hipMemcpyFromSymbol(host, HIP_SYMBOL(apa::apa_dbg_ts), sizeof(unsigned long long) * n);
-}
-#endif
-
 namespace apa {
 
 // Softmax cross-entropy, fused value + gradient (+ probabilities, + first-index argmax).
@@ -58,10 +51,6 @@ __global__ __launch_bounds__(1024) void softmax_xent_kernel(
   const int wid = (split ? (blockIdx.x == 0 ? 0 : blockIdx.x - 1) : blockIdx.x) * wpb + (threadIdx.x >> 6);
   const int nw = (split ? (blockIdx.x == 0 ? 1 : gridDim.x - 1) : gridDim.x) * wpb;
   float slot_loss = 0.f;
-  APA_TS(0);
-#ifdef APA_ABLATION
-  if (blockIdx.x == 0 && (threadIdx.x & 63) == 0) apa_dbg_ts[64 + (threadIdx.x >> 6)] = __builtin_readcyclecounter();
-#endif
   for (int base = 2 * wid; base < N; base += 2 * nw) {
     const int n = base + half;
     const bool active = n < N;
@@ -76,7 +65,6 @@ __global__ __launch_bounds__(1024) void softmax_xent_kernel(
     }
     const bool lab_ok = lab >= 0 && lab < K;
     const float xl = logits[nc * K + (lab_ok ? lab : 0)];   // the label's logit: one broadcast load
-    APA_TS(1);
     // columns already covered by the previous lane (ragged last vector) leave the reductions
 #pragma unroll
     for (int i = 0; i < NV4; ++i) {
@@ -107,7 +95,6 @@ __global__ __launch_bounds__(1024) void softmax_xent_kernel(
     l = half_sum(l, lane);
     const float inv = 1.0f / l;
     const float lv = lab_ok ? -(xl - mw - logf(l)) : 0.f;
-    APA_TS(2);
     if (active) {
       if (G || probs) {
 #pragma unroll
@@ -137,10 +124,6 @@ __global__ __launch_bounds__(1024) void softmax_xent_kernel(
       }
     }
   }
-  APA_TS(3);
-#ifdef APA_ABLATION
-  if (blockIdx.x == 0 && (threadIdx.x & 63) == 0) apa_dbg_ts[96 + (threadIdx.x >> 6)] = __builtin_readcyclecounter();
-#endif
   if (mode != 0 && loss_role) {
     if (hl == 0) red[(threadIdx.x >> 6) * 2 + half] = slot_loss;
     __syncthreads();
@@ -150,7 +133,6 @@ __global__ __launch_bounds__(1024) void softmax_xent_kernel(
       out_loss[0] = t * lscale;
     }
   }
-  APA_TS(4);
 }
 
 // Generic fallback (K < 4 or K > 1024): one wave per row, three passes over the row.
@@ -280,7 +262,6 @@ extern "C" int apa_softmax_xent_fwd_bwd(const float* logits, const int64_t* labe
   // tf.losses.softmax_cross_entropy with a scalar weight: sum(w * l) / (#non-zero weights) = w*mean
   const float lscale = wt / (float)N;
   const float gscale = wt * grad_scale / (float)N;
-  if (dbg_skip() & 16) return APA_OK;
   if (K < 4 || K > 1024) {
     hipLaunchKernelGGL(softmax_xent_stream_kernel, dim3((N + 3) / 4), dim3(256), 0, st, logits,
                        labels, loss, G, probs, pred, N, K, gscale);

@@ -657,15 +657,11 @@ __global__ __launch_bounds__(256) void m1_att_gemv_bwd2_kernel(
 // ============================================================================================
 thread_local M1Trace* g_m1_trace = nullptr;
 
-static bool use_stream_kernels(int C, int dtype);
-// the register-resident per-pixel kernels of this file: C = 64 * EPV * {1, 2, 4, 8}
+// the register-resident per-pixel kernels of this file: C = 64 * EPV * {1, 2}; the wider powers of two are
+// streaming C's (m1s_supported)
 static bool vec_kernels_supported(int C, int dtype) {
   const int epv = dtype == APA_DTYPE_BF16 ? 8 : 4;
-  if (C % (64 * epv) != 0) return false;
-  const int vec = C / (64 * epv);
-  if (!(vec == 1 || vec == 2 || vec == 4 || vec == 8)) return false;
-  if (dtype == APA_DTYPE_BF16 && vec == 8) return false;  // C = 4096 bf16: not instantiated
-  return true;
+  return C == 64 * epv || C == 128 * epv;
 }
 bool m1_vec_supported(int C, int dtype) { return vec_kernels_supported(C, dtype); }
 // Any channel count that is a whole number of 16-byte vectors is served: the channel-split streaming
@@ -674,17 +670,16 @@ bool m1_vec_supported(int C, int dtype) { return vec_kernels_supported(C, dtype)
 bool m1_supported(int C, int Ca, int dtype, bool fused) {
   const int epv = dtype == APA_DTYPE_BF16 ? 8 : 4;
   if (!fused && (Ca % epv != 0)) return false;
-  return use_stream_kernels(C, dtype) || vec_kernels_supported(C, dtype) || m1g_supported(C, dtype);
+  return m1s_supported(C, dtype) || vec_kernels_supported(C, dtype) || m1g_supported(C, dtype);
 }
 
 // Grid sizing.  The streaming kernels hold 2 blocks (8 waves) per CU at their register budget, so
 // 512 blocks is exactly one resident round of the 256 CUs; small batches get S = 512/N pixel
 // splits per image (>= 4 pixels per block so every wave owns at least one), large batches
-// (N >= 512) one block per image.  APA_M1_TARGET_BLOCKS overrides the target for experiments.
+// (N >= 512) one block per image.
 M1Plan m1_plan(int N, int P, int C, int Ca, int K) {
   M1Plan pl;
-  const int target = knob("APA_M1_TARGET_BLOCKS", 512);
-  int S = (target + N / 2) / N;
+  int S = (512 + N / 2) / N;
   if (S < 1) S = 1;
   int maxS = P >= 8 ? P / 4 : 1;
   if (maxS > 256) maxS = 256;   // m1_finalize_fwd_kernel: one split per thread of a 256-thread block
@@ -715,19 +710,10 @@ M1Plan m1_plan(int N, int P, int C, int Ca, int K) {
 
 typedef M1Rng RngArgs;
 
-// The channel-split streaming kernels (apa_m1_stream.hip) serve wide maps; APA_M1_STREAM=0 forces
-// the per-pixel kernels of this file (A/B experiments).
-static bool use_stream_kernels(int C, int dtype) {
-  static const int enabled = knob("APA_M1_STREAM", 1);
-  return enabled && m1s_supported(C, dtype);
-}
-
 // APA_IFLAG_NO_DX is served by the keep-bits form of the streaming backward kernel: bf16 features in training mode
 // inside a one-call step (the forward half left the bits in the workspace)
 bool m1_no_dx_supported(int C, int dtype, bool train) {
-  static const int use_bits = knob("APA_M1_KEEP_BITS", 1);
-  static const int pix = knob("APA_M1S_PIX", 0);     // 0 = the dtype's default (bf16: 2, apa_m1_stream.hip)
-  return train && dtype == APA_DTYPE_BF16 && use_bits && (pix == 0 || pix == 2) && use_stream_kernels(C, dtype);
+  return train && dtype == APA_DTYPE_BF16 && m1s_supported(C, dtype);
 }
 
 template <typename T, int VEC>
@@ -776,14 +762,11 @@ static int launch_bwd_main(bool fused, bool train, int nblk, hipStream_t st, con
       switch ((C) / 256) {                                                               \
         case 1: return FN<float, 1>(__VA_ARGS__);                                        \
         case 2: return FN<float, 2>(__VA_ARGS__);                                        \
-        case 4: return FN<float, 4>(__VA_ARGS__);                                        \
-        case 8: return FN<float, 8>(__VA_ARGS__);                                        \
       }                                                                                  \
     } else {                                                                             \
       switch ((C) / 512) {                                                               \
         case 1: return FN<bf16_t, 1>(__VA_ARGS__);                                       \
         case 2: return FN<bf16_t, 2>(__VA_ARGS__);                                       \
-        case 4: return FN<bf16_t, 4>(__VA_ARGS__);                                       \
       }                                                                                  \
     }                                                                                    \
     set_error("attn_pool M=1: unsupported C=%d for dtype %d", (C), (dtype));             \
@@ -824,7 +807,7 @@ int m1_forward(const void* X, const void* Xatt, const float* Wa, const float* ba
   M1Trace* const tr = m1_trace();
   if (tr) { tr->S = pl.S; tr->ppb = pl.ppb; tr->nblk = pl.nblk; tr->fused = fused; tr->relu_input = r.relu_input; }
 
-  if (r.relu_input && !(fused && use_stream_kernels(C, dtype))) {
+  if (r.relu_input && !(fused && m1s_supported(C, dtype))) {
     set_error("attn_pool M=1: APA_FLAG_RELU_INPUT needs Xatt == X and C in {1024,2048,4096} (f32) / 2048 (bf16)");
     return APA_ERR_UNSUPPORTED;
   }
@@ -859,8 +842,7 @@ int m1_forward(const void* X, const void* Xatt, const float* Wa, const float* ba
     set_error("attn_pool M=1: APA_FLAG_RNG_EXTERNAL: C=%d is not served by the generic M == 1 kernels", C);
     return APA_ERR_UNSUPPORTED;
   }
-  if (dbg_skip() & 1) {}
-  else if (!ext && use_stream_kernels(C, dtype))
+  if (!ext && m1s_supported(C, dtype))
     rc = m1s_launch_pool_fwd(dtype, C, fused, train, pl.nblk, st, X, Wa, ba, att, pacc, pstat, P,
                              pl.S, pool_act, r);
   else if (!ext && vec_kernels_supported(C, dtype))
@@ -873,24 +855,18 @@ int m1_forward(const void* X, const void* Xatt, const float* Wa, const float* ba
   }
   if (rc != APA_OK) return rc;
   const int online = (fused && act == ACT_SOFTMAX) ? 1 : 0;
-  if (!(dbg_skip() & 2)) {
-    // enough blocks to put every CU to work (the kernel is bound by the bytes each CU loads)
-    static const int cw_env = knob("APA_M1_FIN_CW", 0);
-    int cw = cw_env ? cw_env : 256;
-    if (!cw_env) while (cw > 64 && (long)N * ((C + 4 * cw - 1) / (4 * cw)) < 256) cw >>= 1;
-    if (tr) tr->cw = cw;
-    hipLaunchKernelGGL(m1_finalize_fwd_kernel, dim3(N, (C + 4 * cw - 1) / (4 * cw)), dim3(256), 0, st, pacc,
-                       pstat, zsave, abar, att, P, pl.S, C, online, cw);
-    APA_LAUNCH_CHECK("m1_finalize_fwd_kernel");
-  }
+  // enough blocks to put every CU to work (the kernel is bound by the bytes each CU loads)
+  int cw = 256;
+  while (cw > 64 && (long)N * ((C + 4 * cw - 1) / (4 * cw)) < 256) cw >>= 1;
+  if (tr) tr->cw = cw;
+  hipLaunchKernelGGL(m1_finalize_fwd_kernel, dim3(N, (C + 4 * cw - 1) / (4 * cw)), dim3(256), 0, st, pacc,
+                     pstat, zsave, abar, att, P, pl.S, C, online, cw);
+  APA_LAUNCH_CHECK("m1_finalize_fwd_kernel");
   // logits = z . Wt + abar (x) bt -- the first reader of Wt / bt (apa_hooks.td_weights_ready_event)
   if (hk.td_ready) APA_HIP_CHECK(hipStreamWaitEvent(st, hk.td_ready, 0));
-  static const int use_l2 = knob("APA_M1_LOGITS2", 1);
-  static const int use_lx = knob("APA_M1_LOGITS_XENT", 1);
-  static const int use_bh = knob("APA_M1_BWD_HEAD", 1);
   const bool xeval = xf && xf->probs;
   if (cat) xf = nullptr;   // the extra channels add to the logits after the reduction: no fused loss
-  if (xf && use_l2 && use_lx && (xeval || use_bh) && m1_logits_xent_supported(N, C, K, xeval) &&
+  if (xf && m1_logits_xent_supported(N, C, K, xeval) &&
       (xeval || m1_small_supported(C, K)) &&
       ((reinterpret_cast<uintptr_t>(zsave) | reinterpret_cast<uintptr_t>(Wt) |
         reinterpret_cast<uintptr_t>(xf->G)) & 15) == 0) {
@@ -901,12 +877,9 @@ int m1_forward(const void* X, const void* Xatt, const float* Wa, const float* ba
     xf->done = rc == APA_OK;
     return rc;
   }
-  if (use_l2 && m1_logits2_supported(C, K) && (reinterpret_cast<uintptr_t>(zsave) & 15) == 0) {
+  if (m1_logits2_supported(C, K) && (reinterpret_cast<uintptr_t>(zsave) & 15) == 0) {
     if (tr) tr->logits = M1_LOGITS2;
     rc = m1_logits2(zsave, Wt, abar, bt, logits, gemm_ws, N, C, K, st);
-  } else if (m1_small_supported(C, K) && (reinterpret_cast<uintptr_t>(zsave) & 15) == 0) {
-    if (tr) tr->logits = M1_LOGITS_PARTIAL;
-    rc = m1_logits(zsave, Wt, abar, bt, logits, gemm_ws, N, C, K, st);
   } else {
     if (tr) tr->logits = M1_LOGITS_SGEMM;
     rc = sgemm_small(zsave, C, 1, Wt, K, 1, logits, K, N, K, C, pl.lsplits, abar, bt, gemm_ws, st);
@@ -940,8 +913,7 @@ int m1_backward(const void* X, const void* Xatt, const float* Wa, const float* b
   r.ev0 = hk.bwd0; r.ev1 = hk.bwd1;
   M1Trace* const tr = m1_trace();
   if (tr) { tr->S = pl.S; tr->ppb = pl.ppb; tr->nblk = pl.nblk; tr->fused = fused; tr->relu_input = r.relu_input; }
-  static const int use_bits = knob("APA_M1_KEEP_BITS", 1);
-  if ((flags & APA_FLAG_WS_FROM_FWD) && use_bits)   // same workspace, untouched since the forward call
+  if (flags & APA_FLAG_WS_FROM_FWD)   // same workspace, untouched since the forward call
     r.maskbits_in = reinterpret_cast<const uint8_t*>(w + pl.off_maskbits);
   if (flags & APA_IFLAG_NO_DX) {
     if (fused || !(flags & APA_FLAG_WS_FROM_FWD) || !m1_no_dx_supported(C, dtype, train) || rng_external(flags) || cat) {
@@ -951,7 +923,7 @@ int m1_backward(const void* X, const void* Xatt, const float* Wa, const float* b
     }
     r.no_dx = true;
   }
-  if (r.relu_input && !(fused && use_stream_kernels(C, dtype))) {
+  if (r.relu_input && !(fused && m1s_supported(C, dtype))) {
     set_error("attn_pool M=1: APA_FLAG_RELU_INPUT needs Xatt == X and C in {1024,2048,4096} (f32) / 2048 (bf16)");
     return APA_ERR_UNSUPPORTED;
   }
@@ -961,18 +933,15 @@ int m1_backward(const void* X, const void* Xatt, const float* Wa, const float* b
                         ((reinterpret_cast<uintptr_t>(G) | reinterpret_cast<uintptr_t>(Wt) |
                           reinterpret_cast<uintptr_t>(zsave)) & 15) == 0;
   int rc;
-  if (dbg_skip() & 32) { rc = APA_OK; }
-  else if (small_ok) {
+  if (small_ok) {
     // dz = G . Wt^T, dWt = z^T . G, dbt = abar^T G in one launch
-    static const int use_head = knob("APA_M1_BWD_HEAD", 1);
-    if (use_head && m1_bwd_head_supported(N, C, K))
+    if (m1_bwd_head_supported(N, C, K)) {
       rc = m1_bwd_head(G, Wt, zsave, abar, bt, dz, dWt, dbt, sn_buf, N, C, K, st,
                        xf && xf->done ? xf->loss : nullptr, xf ? xf->lscale : 0.f);
-    else if (xf && xf->done) {
+    } else if (xf && xf->done) {
       set_error("attn_pool M=1: fused loss path without the head kernel (internal)");
       return APA_ERR_UNSUPPORTED;
-    }
-    if (!(use_head && m1_bwd_head_supported(N, C, K))) {
+    } else {
       if (tr) tr->head = M1_HEAD_SMALL;
       rc = m1_bwd_small(G, Wt, zsave, abar, bt, dz, dWt, dbt, sn_buf, N, C, K, st);
     }
@@ -1005,8 +974,7 @@ int m1_backward(const void* X, const void* Xatt, const float* Wa, const float* b
     set_error("attn_pool M=1: APA_FLAG_RNG_EXTERNAL: C=%d is not served by the generic M == 1 kernels", C);
     return APA_ERR_UNSUPPORTED;
   }
-  if (dbg_skip() & 64) {}
-  else if (!ext && use_stream_kernels(C, dtype))
+  if (!ext && m1s_supported(C, dtype))
     rc = m1s_launch_bwd_main(dtype, C, fused, train, pl.nblk, st, X, Wa, att, dz, zsave, abar, G,
                              bt, small_ok ? sn_buf : nullptr, dX, dZatt, pdwa, pdba, P, pl.S, K,
                              act, r, dA_extra);
@@ -1040,8 +1008,7 @@ int m1_backward(const void* X, const void* Xatt, const float* Wa, const float* b
     if (nb > pl.nblk) nb = pl.nblk;  // partial buffer is sized for nblk rows
     const size_t shm = ((size_t)4 * Ca + 8) * sizeof(float);
     const int epv = dtype == APA_DTYPE_F32 ? 4 : 8;
-    static const int use_v2 = knob("APA_M1_GEMV_BWD2", 1);
-    if (use_v2 && Ca % epv == 0 && Ca / epv <= 256) {   // register-resident form
+    if (Ca % epv == 0 && Ca / epv <= 256) {   // register-resident form
       const int nthr = ((Ca / epv + 63) / 64) * 64;
       if (tr) tr->gemv = rank1 ? M1_GEMV_BWD2_RANK1 : M1_GEMV_BWD2;
 #define APA_GB2(T, ST)                                                                        \
@@ -1072,7 +1039,6 @@ int m1_backward(const void* X, const void* Xatt, const float* Wa, const float* b
   uint64_t* bump = (train && (flags & APA_FLAG_RNG_DEVICE))
                        ? reinterpret_cast<uint64_t*>(static_cast<uintptr_t>(offset))
                        : nullptr;
-  if (dbg_skip() & 128) return APA_OK;
   if (tr) { tr->reduce = small_ok ? M1_REDUCE_COLSUM : M1_REDUCE_BWD_REDUCE; tr->rng_bump = bump != nullptr; }
   if (small_ok) return m1_colsum(pdwa, pdba, dWa, dba, nred, cred, cred, bump, st);
   hipLaunchKernelGGL(m1_bwd_reduce_kernel, dim3((cred + 63) / 64 + 1), dim3(256), 0, st, pdwa, pdba,

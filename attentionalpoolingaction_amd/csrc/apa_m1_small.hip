@@ -19,75 +19,10 @@
 #include "apa_device.h"
 #include "apa_internal.h"
 
-#ifdef APA_ABLATION
-namespace apa { __device__ unsigned long long apa_dbg_ts[4096]; }
-extern "C" int apa_debug_read_ts(unsigned long long* host, int n) {
-  return (int)hipMemcpyFromSymbol(host, HIP_SYMBOL(apa::apa_dbg_ts), sizeof(unsigned long long) * n);
-}
-#endif
-
 namespace apa {
 
 __device__ __forceinline__ f32x4 mfma16(float a, float b, f32x4 c) {
   return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
-}
-
-// --------------------------------------------------------------------------------------------
-// L1: partial logits.  grid (ceil(K/32), C/128, ceil(N/32)), 256 threads.
-//   part[cc][n][k] = sum_{c in chunk cc} z[n,c] * Wt[c,k]
-// --------------------------------------------------------------------------------------------
-constexpr int L1_ZS = 130;  // Zs[32][130]: == 2 (mod 32)
-constexpr int L1_WS = 48;   // Ws[128][48]: == 16 (mod 32)
-
-__global__ __launch_bounds__(256) void m1_logits_partial_kernel(const float* __restrict__ z,
-                                                                const float* __restrict__ Wt,
-                                                                float* __restrict__ part, int N,
-                                                                int C, int K) {
-  __shared__ float Zs[32 * L1_ZS];
-  __shared__ float Ws[128 * L1_WS];
-  const int k0 = blockIdx.x * 32, c0 = blockIdx.y * 128, n0 = blockIdx.z * 32;
-  const int tid = threadIdx.x;
-  // Wt tile [128 c][32 k]: one wave-instruction covers 2 rows x 32 consecutive floats
-  {
-    const int col = tid & 31, r0 = tid >> 5;
-    const bool ok = (k0 + col) < K;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) {
-      const int row = r0 + i * 8;
-      Ws[row * L1_WS + col] = ok ? Wt[(size_t)(c0 + row) * K + k0 + col] : 0.f;
-    }
-  }
-  // z tile [32 n][128 c], float4 (rows are 16-byte aligned: C % 4 == 0)
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int v = tid + i * 256;
-    const int row = v >> 5, c4 = (v & 31) * 4;
-    float4 q = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (n0 + row < N) q = *reinterpret_cast<const float4*>(z + (size_t)(n0 + row) * C + c0 + c4);
-    float* d = &Zs[row * L1_ZS + c4];
-    d[0] = q.x; d[1] = q.y; d[2] = q.z; d[3] = q.w;
-  }
-  __syncthreads();
-  const int wave = tid >> 6, lane = tid & 63;
-  const int ni = wave >> 1, kj = wave & 1;
-  const int r = lane & 15, kq = lane >> 4;
-  const float* za = &Zs[(ni * 16 + r) * L1_ZS + kq];
-  const float* wb = &Ws[kq * L1_WS + kj * 16 + r];
-  f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll 8
-  for (int t = 0; t < 32; t += 2) {
-    acc0 = mfma16(za[4 * t], wb[4 * t * L1_WS], acc0);
-    acc1 = mfma16(za[4 * t + 4], wb[(4 * t + 4) * L1_WS], acc1);
-  }
-  const int col = k0 + kj * 16 + r;
-  if (col < K) {
-    float* out = part + ((size_t)blockIdx.y * N) * K;
-#pragma unroll
-    for (int reg = 0; reg < 4; ++reg) {
-      const int row = n0 + ni * 16 + kq * 4 + reg;
-      if (row < N) out[(size_t)row * K + col] = acc0[reg] + acc1[reg];
-    }
-  }
 }
 
 // L2: logits[n,k] = sum_cc part[cc][n][k] + abar[n] * bt[k]   (fixed order over cc)
@@ -559,7 +494,6 @@ __global__ __launch_bounds__(256) void m1_bwd_head_kernel(
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const int r = lane & 15, kq = lane >> 4;
   const int role = blockIdx.x & 1, b = blockIdx.x >> 1, c0 = b * 16;
-  APA_TS(0);
 
   if (role == 0) {
     // ------------------------------ dz + sn ------------------------------
@@ -590,7 +524,6 @@ __global__ __launch_bounds__(256) void m1_bwd_head_kernel(
         const float* grow = G + (size_t)(n0 + b) * K;
         for (int k = lane; k < K; k += 64) sacc = fmaf(grow[k], bt[k], sacc);
       }
-      APA_TS(1);
       f32x4 a0 = {0.f, 0.f, 0.f, 0.f}, a1 = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
       for (int j = 0; j < UG; ++j) {
@@ -600,7 +533,6 @@ __global__ __launch_bounds__(256) void m1_bwd_head_kernel(
           a1 = mfma16(aq1[j][e], bq[j][e], a1);
         }
       }
-      APA_TS(2);
       if (do_sn) {
         sacc = wave_sum(sacc);
         if (lane == 0) sn[n0 + b] = sacc;
@@ -612,7 +544,6 @@ __global__ __launch_bounds__(256) void m1_bwd_head_kernel(
         red[(wave * 2 + 1) * 256 + (kq * 4 + reg) * 16 + r] = a1[reg];
       }
       __syncthreads();
-      APA_TS(3);
 #pragma unroll
       for (int ni = 0; ni < 2; ++ni) {
         const int row = tid >> 4, col = tid & 15;
@@ -622,8 +553,6 @@ __global__ __launch_bounds__(256) void m1_bwd_head_kernel(
         if (n < N) dz[(size_t)n * C + c0 + col] = s;
       }
     }
-    APA_TS(4);
-    APA_TS(5);
     return;
   }
 
@@ -669,15 +598,12 @@ __global__ __launch_bounds__(256) void m1_bwd_head_kernel(
       const float acc = fmaf(wa_, G[(size_t)na * K + kc], wb_ * G[(size_t)nb2 * K + kc]);
       dbt_acc += row_sum16(acc);
     }
-    APA_TS(1);
 #pragma unroll
     for (int t = 0; t < 8; ++t) {
 #pragma unroll
       for (int j = 0; j < UG; ++j) wacc[j] = mfma16(az[t], bg[j][t], wacc[j]);
     }
-    APA_TS(2);
   }
-  APA_TS(3);
 #pragma unroll
   for (int j = 0; j < UG; ++j) {
     const int col = (wave + 4 * j) * 16 + r;
@@ -687,7 +613,6 @@ __global__ __launch_bounds__(256) void m1_bwd_head_kernel(
         dWt[(size_t)(c0 + kq * 4 + reg) * K + col] = wacc[j][reg];
     }
   }
-  APA_TS(4);
   if (do_dbt && r == 0 && kq < kpb && b * kpb + kq < K) dbt[b * kpb + kq] = dbt_acc;
   if (do_loss) {   // block-uniform; `red` is unused by this role
     if (N <= 64) {
@@ -707,7 +632,6 @@ __global__ __launch_bounds__(256) void m1_bwd_head_kernel(
       if (tid == 0) loss[0] = ((red[0] + red[1]) + (red[2] + red[3])) * lscale;
     }
   }
-  APA_TS(5);
 }
 
 // --------------------------------------------------------------------------------------------
@@ -970,26 +894,11 @@ __global__ __launch_bounds__(1024) void m1_colsum_kernel(const float* __restrict
 // ============================================================================================
 // host
 // ============================================================================================
-size_t m1_logits_ws_bytes(int N, int C, int K) { return (size_t)(C / 128) * N * K * sizeof(float); }
-
 bool m1_small_supported(int C, int K) {
   // role A keeps (16 + 32) rows of Kp floats (+ 8 KB) in LDS and stages a 32-row G tile with at
   // most 26 16-byte loads per thread
   return C % 128 == 0 && ((size_t)48 * dz_kp(K) + 2048) * sizeof(float) <= 150 * 1024 &&
          (8 * K + 255) / 256 <= 26;
-}
-
-int m1_logits(const float* z, const float* Wt, const float* abar, const float* bt, float* logits,
-              float* part_ws, int N, int C, int K, hipStream_t st) {
-  dim3 grid((K + 31) / 32, C / 128, (N + 31) / 32);
-  if (!(dbg_skip() & 4))
-  hipLaunchKernelGGL(m1_logits_partial_kernel, grid, dim3(256), 0, st, z, Wt, part_ws, N, C, K);
-  APA_LAUNCH_CHECK("m1_logits_partial_kernel");
-  if (!(dbg_skip() & 8))
-  hipLaunchKernelGGL(m1_logits_reduce_kernel, dim3((N * K + 255) / 256), dim3(256), 0, st, part_ws,
-                     abar, bt, logits, N, K, C / 128);
-  APA_LAUNCH_CHECK("m1_logits_reduce_kernel");
-  return APA_OK;
 }
 
 // L1v2 + L2
@@ -1014,11 +923,8 @@ static int launch_logits2(const float* z, const float* Wt, float* part_ws, int N
 
 int m1_logits2(const float* z, const float* Wt, const float* abar, const float* bt, float* logits,
                float* part_ws, int N, int C, int K, hipStream_t st) {
-  if (!(dbg_skip() & 4)) {
-    const int rc = launch_logits2(z, Wt, part_ws, N, C, K, st);
-    if (rc != APA_OK) return rc;
-  }
-  if (!(dbg_skip() & 8))
+  const int rc = launch_logits2(z, Wt, part_ws, N, C, K, st);
+  if (rc != APA_OK) return rc;
   hipLaunchKernelGGL(m1_logits_reduce_kernel, dim3((N * K + 255) / 256), dim3(256), 0, st, part_ws,
                      abar, bt, logits, N, K, C / (64 * logits2_nsub(N, C)));
   APA_LAUNCH_CHECK("m1_logits_reduce_kernel");
@@ -1105,7 +1011,7 @@ int m1_bwd_head(const float* G, const float* Wt, const float* zsave, const float
   const int kpb = (K + nb - 1) / nb;
   const int ug = (((K + 15) / 16) + 3) / 4;
   M1Trace* const tr = m1_trace();
-  if (N > 32 && ug <= 7 && knob("APA_M1_BWD_HEAD_TILES", 1)) {   // several image tiles: the pipelined form
+  if (N > 32 && ug <= 7) {   // several image tiles: the pipelined form
     if (tr) { tr->head = M1_HEAD_TILES; tr->head_ug = ug <= 1 ? 1 : (ug <= 2 ? 2 : (ug <= 4 ? 4 : 7)); }
 #define APA_BHT(UG)                                                                                      \
   hipLaunchKernelGGL(m1_bwd_head_tiles_kernel<UG>, dim3(2 * nb), dim3(256), 0, st, G, Wt, zsave, abar, \

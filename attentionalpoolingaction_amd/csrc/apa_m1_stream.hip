@@ -36,9 +36,6 @@
 // on one box, physically contiguous X / dX, fp32 (up / down, us): N = 32: 18.55 / 17.65, N = 64: 32.6 / 32.2,
 // N = 256: 164 / 144.5, N = 512: 320 / 298, 512 x 15x15: 384 / 354; bf16 N = 512: 149.5 / 146.5.
 // (docs/DESIGN_HISTORY.md, round 6: how the "two kinds of box" of the N = 512 line turned out to be this.)
-#ifndef APA_M1S_BWD_DOWN
-#define APA_M1S_BWD_DOWN 1
-#endif
 
 namespace apa {
 
@@ -554,7 +551,7 @@ __global__ __launch_bounds__(256, 2) void m1s_bwd_main_kernel(
     for (int i = 0; i < PIX; ++i) kb_r[b][i] = 0u;
   }
   // i-th chunk of the walk (slots past the end re-read the walk's last chunk: L1/L2 hits)
-  auto walk = [&](int i_) { return APA_M1S_BWD_DOWN ? max(nchunk - 1 - i_, 0) : i_; };
+  auto walk = [&](int i_) { return max(nchunk - 1 - i_, 0); };
 #pragma unroll
   for (int b = 0; b < NB - 1; ++b) fetch(b, walk(b));
 
@@ -642,38 +639,28 @@ bool m1s_supported(int C, int dtype) {
 // benchmark batch: the first chunk's arithmetic starts after 8 KB instead of 16 KB per block and less work is left
 // behind the last load (A/B on one box, two runs each: step 51.4 -> 50.1 us, backward kernel 19.45 -> 18.65 us by
 // events; N = 512 unchanged, 276 us; 4 and 8 lose 3 and 6 us).
-// (C = 4096 fp32, VW = 4: 2 and 4 are the instantiated widths; 2 stays the default there)
-#ifndef APA_M1S_BF16_PIX
-#define APA_M1S_BF16_PIX 2
-#endif
-template <typename T, int VW = 1> struct DefPix {
-  static constexpr int V = sizeof(T) == 2 ? APA_M1S_BF16_PIX : (VW == 4 ? 2 : 1);
-};
-static int env_pix(int dtype) {
-  static const int v = knob("APA_M1S_PIX", 0);
-  return v ? v : (dtype == APA_DTYPE_BF16 ? DefPix<bf16_t>::V : DefPix<float>::V);
-}
+// (C = 4096 fp32, VW = 4: 2)
+template <typename T, int VW> constexpr int kPix = sizeof(T) == 2 ? 2 : (VW == 4 ? 2 : 1);
 
-template <typename T, int VW, int PIX>
+template <typename T, int VW>
 static int launch_fwd_t(bool fused, bool train, int nblk, hipStream_t st, const void* X,
                         const float* Wa, const float* ba, float* att, float* pacc, float* pstat,
                         int P, int S, int act, const M1Rng& r) {
+  constexpr int PIX = kPix<T, VW>;
   const T* x = static_cast<const T*>(X);
   uint8_t* mbits = r.maskbits_out;
   if (M1Trace* t = m1_trace()) { t->pool_fwd = M1_POOL_STREAM; t->fwd_w = VW; t->fwd_pix = PIX; }
-  if (r.relu_input) {   // instantiated for the default chunk width and the fused map only
-    if (!fused || PIX != DefPix<T, VW>::V) {
+  if (r.relu_input) {   // instantiated for the fused map only
+    if (!fused) {
       set_error("attn_pool M=1 stream kernels: APA_FLAG_RELU_INPUT needs Xatt == X");
       return APA_ERR_UNSUPPORTED;
     }
-    if constexpr (PIX == DefPix<T, VW>::V) {
-      if (train)
-        launch_ev(m1s_pool_fwd_kernel<T, VW, PIX, true, true, true>, dim3(nblk), dim3(256), 0, st, r.ev0, r.ev1, x, Wa, ba, att, pacc, pstat, P, S, act, r.inv_keep, r.thresh, r.seed,
-                           r.offset, r.offset_dev, mbits);
-      else
-        launch_ev(m1s_pool_fwd_kernel<T, VW, PIX, true, false, true>, dim3(nblk), dim3(256), 0, st, r.ev0, r.ev1, x, Wa, ba, att, pacc, pstat, P, S, act, r.inv_keep, r.thresh, r.seed,
-                           r.offset, r.offset_dev, mbits);
-    }
+    if (train)
+      launch_ev(m1s_pool_fwd_kernel<T, VW, PIX, true, true, true>, dim3(nblk), dim3(256), 0, st, r.ev0, r.ev1, x, Wa, ba, att, pacc, pstat, P, S, act, r.inv_keep, r.thresh, r.seed,
+                         r.offset, r.offset_dev, mbits);
+    else
+      launch_ev(m1s_pool_fwd_kernel<T, VW, PIX, true, false, true>, dim3(nblk), dim3(256), 0, st, r.ev0, r.ev1, x, Wa, ba, att, pacc, pstat, P, S, act, r.inv_keep, r.thresh, r.seed,
+                         r.offset, r.offset_dev, mbits);
     APA_LAUNCH_CHECK("m1s_pool_fwd_kernel");
     return APA_OK;
   }
@@ -688,12 +675,13 @@ static int launch_fwd_t(bool fused, bool train, int nblk, hipStream_t st, const 
   return APA_OK;
 }
 
-template <typename T, int VW, int PIX>
+template <typename T, int VW>
 static int launch_bwd_t(bool fused, bool train, int nblk, hipStream_t st, const void* X,
                         const float* Wa, const float* att, const float* dz, const float* zsave,
                         const float* abar, const float* G, const float* bt, const float* sn_pre,
                         void* dX, float* dZout, float* pdwa, float* pdba, int P, int S, int K,
                         int act, const M1Rng& r, const float* dA_extra) {
+  constexpr int PIX = kPix<T, VW>;
   const T* x = static_cast<const T*>(X);
   T* dx = static_cast<T*>(dX);
   const float* ex = dA_extra ? dA_extra : att;
@@ -702,18 +690,16 @@ static int launch_bwd_t(bool fused, bool train, int nblk, hipStream_t st, const 
   M1Trace* const tr = m1_trace();
   if (tr) { tr->pool_bwd = M1_POOL_STREAM; tr->bwd_w = VW; tr->bwd_pix = PIX; }
   if (r.relu_input) {
-    if (!fused || PIX != DefPix<T, VW>::V) {
+    if (!fused) {
       set_error("attn_pool M=1 stream kernels: APA_FLAG_RELU_INPUT needs Xatt == X");
       return APA_ERR_UNSUPPORTED;
     }
-    if constexpr (PIX == DefPix<T, VW>::V) {
-      if (train)
-        launch_ev(m1s_bwd_main_kernel<T, VW, PIX, true, true, true>, dim3(nblk), dim3(256), 0, st, r.ev0, r.ev1, x, Wa, att, dz, zsave, abar, G, bt, sn_pre, dx, dZout, pdwa, pdba, P, S, K,
-                           act, r.inv_keep, r.thresh, r.seed, r.offset, r.offset_dev, ex, exs, nullptr);
-      else
-        launch_ev(m1s_bwd_main_kernel<T, VW, PIX, true, false, true>, dim3(nblk), dim3(256), 0, st, r.ev0, r.ev1, x, Wa, att, dz, zsave, abar, G, bt, sn_pre, dx, dZout, pdwa, pdba, P, S, K,
-                           act, r.inv_keep, r.thresh, r.seed, r.offset, r.offset_dev, ex, exs, nullptr);
-    }
+    if (train)
+      launch_ev(m1s_bwd_main_kernel<T, VW, PIX, true, true, true>, dim3(nblk), dim3(256), 0, st, r.ev0, r.ev1, x, Wa, att, dz, zsave, abar, G, bt, sn_pre, dx, dZout, pdwa, pdba, P, S, K,
+                         act, r.inv_keep, r.thresh, r.seed, r.offset, r.offset_dev, ex, exs, nullptr);
+    else
+      launch_ev(m1s_bwd_main_kernel<T, VW, PIX, true, false, true>, dim3(nblk), dim3(256), 0, st, r.ev0, r.ev1, x, Wa, att, dz, zsave, abar, G, bt, sn_pre, dx, dZout, pdwa, pdba, P, S, K,
+                         act, r.inv_keep, r.thresh, r.seed, r.offset, r.offset_dev, ex, exs, nullptr);
     APA_LAUNCH_CHECK("m1s_bwd_main_kernel");
     return APA_OK;
   }
@@ -722,7 +708,7 @@ static int launch_bwd_t(bool fused, bool train, int nblk, hipStream_t st, const 
             Wa, att, dz, zsave, abar, G, bt, sn_pre, dx, dZout, pdwa, pdba, P, S, K, act, r.inv_keep,   \
             r.thresh, r.seed, r.offset, r.offset_dev, ex, exs, mbits)
   bool bits_done = false;
-  if constexpr (PIX == DefPix<T, VW>::V && KeepBits<T>::ON) {   // the keep-bits variant: default chunk width, bf16 features
+  if constexpr (KeepBits<T>::ON) {   // the keep-bits variant: bf16 features
     if (train && mbits && !fused && r.no_dx) {   // ... without the dX stores (APA_IFLAG_NO_DX)
       launch_ev(m1s_bwd_main_kernel<T, VW, PIX, false, true, false, true, true>, dim3(nblk), dim3(256), 0, st, r.ev0,
                 r.ev1, x, Wa, att, dz, zsave, abar, G, bt, sn_pre, dx, dZout, pdwa, pdba, P, S, K, act, r.inv_keep,
@@ -747,24 +733,16 @@ static int launch_bwd_t(bool fused, bool train, int nblk, hipStream_t st, const 
   return APA_OK;
 }
 
-#define APA_S_PIX(FN, T, VW, ...)                                           \
-  switch (pix) {                                                            \
-    case 1: return FN<T, VW, 1>(__VA_ARGS__);                               \
-    case 2: return FN<T, VW, 2>(__VA_ARGS__);                               \
-    case 8: return FN<T, VW, 8>(__VA_ARGS__);                               \
-    default: return FN<T, VW, 4>(__VA_ARGS__);                              \
-  }
 #define APA_S_DISPATCH(FN, dtype, C, ...)                                   \
   [&]() -> int {                                                            \
-    const int pix = env_pix(dtype);                                         \
     if ((dtype) == APA_DTYPE_F32) {                                         \
       switch ((C) / 1024) {                                                 \
-        case 1: APA_S_PIX(FN, float, 1, __VA_ARGS__)                        \
-        case 2: APA_S_PIX(FN, float, 2, __VA_ARGS__)                        \
-        case 4: return pix >= 4 ? FN<float, 4, 4>(__VA_ARGS__) : FN<float, 4, 2>(__VA_ARGS__); \
+        case 1: return FN<float, 1>(__VA_ARGS__);                           \
+        case 2: return FN<float, 2>(__VA_ARGS__);                           \
+        case 4: return FN<float, 4>(__VA_ARGS__);                           \
       }                                                                     \
     } else {                                                                \
-      if ((C) == 2048) { APA_S_PIX(FN, bf16_t, 1, __VA_ARGS__) }            \
+      if ((C) == 2048) return FN<bf16_t, 1>(__VA_ARGS__);                   \
     }                                                                       \
     set_error("m1 stream kernels: unsupported C=%d dtype=%d", (C), (dtype)); \
     return APA_ERR_UNSUPPORTED;                                             \

@@ -35,14 +35,6 @@
 
 namespace apa {
 
-// timing-experiment switches of the development build (make ABLATE=1: pieces of a kernel switched off to price them --
-// wrong results by design).  In the product build the tests are the constant 0 and the code they guard is not compiled.
-#ifdef APA_ABLATION
-#define APA_EXPBIT(v, b) ((v) & (b))
-#else
-#define APA_EXPBIT(v, b) 0
-#endif
-
 namespace {
 typedef short bf16x8 __attribute__((ext_vector_type(8)));
 typedef short bf16x4 __attribute__((ext_vector_type(4)));
@@ -512,7 +504,7 @@ __device__ __forceinline__ bf16x8 frag_km_sw(const short* img, int rbase, int ks
 template <bool TRAIN>
 __global__ __launch_bounds__(512) void pc_bwd_dw_kernel(
     const bf16_t* __restrict__ X, const bf16_t* __restrict__ dTdZ, const uint8_t* __restrict__ maskbits,
-    float* __restrict__ partial, int R, int C, int rows_per_split, int exp) {
+    float* __restrict__ partial, int R, int C, int rows_per_split) {
   extern __shared__ __attribute__((aligned(16))) short smem[];
   constexpr int LDI = 128;
   constexpr int IMG = FK * LDI;
@@ -527,7 +519,7 @@ __global__ __launch_bounds__(512) void pc_bwd_dw_kernel(
   const int cx = lg % (int)gridDim.x, sy = lg / (int)gridDim.x;     // (channel tile, row split)
   const int c0 = cx * 128;
   const int rbeg = sy * rows_per_split, rend = min(R, rbeg + rows_per_split);
-  const int nk = APA_EXPBIT(exp, 16) ? 0 : (APA_EXPBIT(exp, 32) ? 1 : (rend - rbeg + FK - 1) / FK);
+  const int nk = (rend - rbeg + FK - 1) / FK;
 
   // Two tiles ahead through registers: a tile's 5 loads per thread are requested two iterations before they are
   // parked in LDS (one iteration of MFMAs does not cover a round trip to HBM with 256 blocks streaming X).  The wait
@@ -542,9 +534,9 @@ __global__ __launch_bounds__(512) void pc_bwd_dw_kernel(
       const int rc = min(r, rend - 1);
       // (plain loads: with the non-temporal hint this kernel is no faster and the NEXT step's forward product loses
       //  1 us -- the map is no longer served from the Infinity Cache)
-      q.av[i] = APA_EXPBIT(exp, 4) ? make_uint4(1u, 2u, 3u, 4u) : ld16(X + (size_t)rc * C + c0 + m);
-      q.bv[i] = APA_EXPBIT(exp, 8) ? make_uint4(1u, 2u, 3u, 4u) : ld16(dTdZ + (size_t)rc * 128 + m);
-      if (TRAIN) q.mb[i] = APA_EXPBIT(exp, 64) ? 0x55u : maskbits[((size_t)rc * C + c0 + m) >> 3];
+      q.av[i] = ld16(X + (size_t)rc * C + c0 + m);
+      q.bv[i] = ld16(dTdZ + (size_t)rc * 128 + m);
+      if (TRAIN) q.mb[i] = maskbits[((size_t)rc * C + c0 + m) >> 3];
     }
   };
   auto settle = [&](Stage& q) {
@@ -581,7 +573,6 @@ __global__ __launch_bounds__(512) void pc_bwd_dw_kernel(
     for (int j = 0; j < 2; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
 
   auto compute = [&](int t) {
-    if (APA_EXPBIT(exp, 2)) return;
     // half 0 (dT columns) contracts against the MASKED features, half 1 (dZ) against the plain ones
     const short* a_img = smem + (t & 1) * STAGE + ((TRAIN && half == 0) ? IMG : 0);
     const short* b_img = smem + (t & 1) * STAGE + (TRAIN ? 2 : 1) * IMG;
@@ -622,7 +613,6 @@ __global__ __launch_bounds__(512) void pc_bwd_dw_kernel(
     if (t + 1 < nk) iteration(t + 1, SA, SB);
   }
   float* out = partial + ((size_t)sy * C + c0) * 128;
-  if (APA_EXPBIT(exp, 1)) return;
 #pragma unroll
   for (int i = 0; i < 4; ++i)
 #pragma unroll
@@ -661,7 +651,7 @@ constexpr size_t DX_LDS_BYTES = (size_t)DX_MAXU * 8192 + DX_LDS_REST;   // the m
 struct PcDxArgs {
   const float* G; const float* att; const float* Tm; const bf16_t* Wcat2; const uint8_t* bits;
   bf16_t* dX; bf16_t* dTdZ; float* pd;
-  int R, C, K, P, act, upb, exp; float inv_keep;
+  int R, C, K, P, act, upb; float inv_keep;
   const float* lpart; float* logits; PcXent xe;      // lpart != nullptr: deferred logits + cross-entropy
 };
 // sum over the 16 lanes of a DPP row (= the 16 rows of a wave's tile): four rotate-and-add steps on the VALU, no LDS
@@ -697,7 +687,7 @@ __global__ __launch_bounds__(512) void pc_bwd_dx_kernel(PcDxArgs a) {
     const uint32_t lbase = (uint32_t)(uintptr_t)smem;
     const int q = wave * 64 + lane, j = q >> 4, m = j & 15, t = j >> 4;
     const bf16_t* src = a.Wcat2 + (size_t)(cbeg + 8 * (m >> 2) + 4 * t + (m & 3)) * 128 + (((q & 15) ^ dx_swz(m)) * 8);
-    for (int u = 0; u < (APA_EXPBIT(a.exp, 8) ? 0 : nu); ++u)
+    for (int u = 0; u < nu; ++u)
       glds16_asm(src + (size_t)u * 32 * 128, (uint32_t)__builtin_amdgcn_readfirstlane((int)(lbase + u * 8192 + wave * 1024)));
   }
   // 2. (one-call step after a folded forward product) the logits of the images these rows touch, from the forward
@@ -705,7 +695,7 @@ __global__ __launch_bounds__(512) void pc_bwd_dx_kernel(PcDxArgs a) {
   const int n_first = m0 / P, n_last = min(m0 + DX_ROWS - 1, R - 1) / P;
   const float invP = 1.0f / (float)P;
   const int n_mine = n_first + wave;
-  const bool has_img = a.lpart && n_mine <= n_last && !APA_EXPBIT(a.exp, 128);
+  const bool has_img = a.lpart && n_mine <= n_last;
   float lg = -INFINITY;
   if (has_img && lane < K) lg = pc_logit_from_partials(a.lpart, n_mine, lane, P);
   // 3. att / T of this lane's row: classes 8 kb + e and 32 + 8 kb + e
@@ -719,10 +709,7 @@ __global__ __launch_bounds__(512) void pc_bwd_dx_kernel(PcDxArgs a) {
 #pragma unroll
       for (int e4 = 0; e4 < 8; e4 += 4) {     // rows are K floats: 4-byte aligned 16-byte loads (dword alignment is enough)
         const int k = 32 * hh + 8 * kb + e4;
-        if (APA_EXPBIT(a.exp, 16)) {
-#pragma unroll
-          for (int e = 0; e < 4; ++e) { av[hh][e4 + e] = 1.f; tv[hh][e4 + e] = 1.f; }
-        } else if (k + 3 < K) {
+        if (k + 3 < K) {
           const f4u x = *reinterpret_cast<const f4u*>(a.att + rbase + k), y = *reinterpret_cast<const f4u*>(a.Tm + rbase + k);
 #pragma unroll
           for (int e = 0; e < 4; ++e) { av[hh][e4 + e] = x[e]; tv[hh][e4 + e] = y[e]; }
@@ -802,7 +789,7 @@ __global__ __launch_bounds__(512) void pc_bwd_dx_kernel(PcDxArgs a) {
         st16(a.dTdZ + (size_t)rowg * 128 + 64 + 32 * hh + 8 * kb, pz);
       }
     }
-    if (sp == 0 && !APA_EXPBIT(a.exp, 64)) {     // dbt | dba: this wave's 16-row column sums (the block's partial row is finished after the loop)
+    if (sp == 0) {     // dbt | dba: this wave's 16-row column sums (the block's partial row is finished after the loop)
 #pragma unroll
       for (int hh = 0; hh < 2; ++hh)
 #pragma unroll
@@ -850,12 +837,12 @@ __global__ __launch_bounds__(512) void pc_bwd_dx_kernel(PcDxArgs a) {
       }
     }
     // (non-temporal: dX is the step's output, nothing in this call reads it back -- 15.0 -> 13.8 us)
-    if (valid && !APA_EXPBIT(a.exp, 1)) st16_nt(a.dX + (size_t)rowg * a.C + cbeg + 32 * u + 8 * kb, Vec<bf16_t>::pack(o));
+    if (valid) st16_nt(a.dX + (size_t)rowg * a.C + cbeg + 32 * u + 8 * kb, Vec<bf16_t>::pack(o));
   };
   bf16x8 afA[2][4], afB[2][4];
   uint32_t mbA, mbB;
   load_u(0, afA, mbA);
-  for (int u = 0; u < (APA_EXPBIT(a.exp, 2) ? 0 : nu); u += 2) {
+  for (int u = 0; u < nu; u += 2) {
     load_u(min(u + 1, nu - 1), afB, mbB);
     unit(u, afA, mbA);
     if (u + 1 < nu) {
@@ -928,9 +915,8 @@ __global__ __launch_bounds__(1024) void pc_dw_reduce_kernel(const float* __restr
 }  // namespace
 
 bool pc_fused_supported(int N, int P, int C, int Ca, int K, int dtype, const void* X, const void* Xatt) {
-  static const int enabled = knob("APA_PC_FUSED", 1);
   (void)N; (void)P;
-  return enabled && dtype == APA_DTYPE_BF16 && Xatt == X && Ca == C && K >= 1 && K <= 64 && C % 256 == 0 &&
+  return dtype == APA_DTYPE_BF16 && Xatt == X && Ca == C && K >= 1 && K <= 64 && C % 256 == 0 &&
          C <= ZB_MAX_C && (reinterpret_cast<uintptr_t>(X) & 15) == 0;
 }
 
@@ -1031,8 +1017,7 @@ int pc_fused_forward(const PcFusedWs& f, const void* X, float* Z, float* T, int 
 
 // dX with the backward activation pass folded in (pc_bwd_dx_kernel); pd: [ceil(R / 128)][2K] partial rows of dbt | dba
 bool pc_fused_dx_supported(int P, int act) {
-  static const int enabled = knob("APA_PC_DX_FUSED", 1);
-  return enabled && act != 2 && P >= 32;
+  return act != 2 && P >= 32;
 }
 int pc_fused_dx_rows(int R) { return (R + DX_ROWS - 1) / DX_ROWS; }
 int pc_fused_dx(const PcFusedWs& f, const float* G, const float* att, const float* Tm, void* dX, float* pd, int R,
@@ -1041,16 +1026,13 @@ int pc_fused_dx(const PcFusedWs& f, const float* G, const float* att, const floa
   a.G = G; a.att = att; a.Tm = Tm; a.Wcat2 = static_cast<const bf16_t*>(f.Wcat2); a.bits = f.maskbits;
   a.dX = static_cast<bf16_t*>(dX); a.dTdZ = static_cast<bf16_t*>(f.dTdZ); a.pd = pd;
   a.R = R; a.C = C; a.K = K; a.P = P; a.act = act; a.inv_keep = train ? 1.0f / keep_prob : 1.0f;
-  static const int dx_exp = knob("APA_PC_DX_EXP", 0);     // timing experiments (development library only)
-  a.exp = dx_exp;
   a.lpart = nullptr; a.logits = nullptr; a.xe = PcXent{nullptr, nullptr, nullptr, 0.f};
   if (defer) {
     a.lpart = f.lpart; a.logits = defer->logits;
     a.xe.labels = defer->labels; a.xe.loss = defer->loss; a.xe.G = defer->G; a.xe.gscale = defer->gscale;
   }
   const int rbs = pc_fused_dx_rows(R), units = C / 32;
-  static const int sp_env = knob("APA_PC_DX_SPLITS", 0);
-  int splits = sp_env > 0 ? sp_env : (256 + rbs / 2) / rbs;      // about one block per CU
+  int splits = (256 + rbs / 2) / rbs;      // about one block per CU
   if (splits < (units + DX_MAXU - 1) / DX_MAXU) splits = (units + DX_MAXU - 1) / DX_MAXU;
   if (splits > units) splits = units;
   a.upb = (units + splits - 1) / splits;
@@ -1074,17 +1056,15 @@ int pc_fused_dx(const PcFusedWs& f, const float* G, const float* att, const floa
 
 int pc_fused_dw(const PcFusedWs& f, const void* X, float* dWt, float* dWa, int R, int C, int K, bool train,
                 float keep_prob, hipStream_t st, const PcDwTail* tail) {
-  static const int s_env = knob("APA_PC_DW_SPLITS", 0);
   // (a 64-channel form -- 32 channel tiles x 8 row splits, half the fp32 partials -- was built and measured in round
   // 4: 51.9 us against 15.5 us: every block then reads 128-byte pieces of X rows 4 KB apart)
   const int ctiles = C / 128;
-  int S = s_env ? s_env : (256 + ctiles - 1) / ctiles;            // one block per CU
+  int S = (256 + ctiles - 1) / ctiles;            // one block per CU
   if (S > PC_DW_MAX_SPLITS) S = PC_DW_MAX_SPLITS;
   int ktiles = (R + FK - 1) / FK;
   if (S > ktiles) S = ktiles;
   const int rows_per_split = ((ktiles + S - 1) / S) * FK;
   S = (R + rows_per_split - 1) / rows_per_split;
-  static const int dw_exp = knob("APA_PC_DW_EXP", 0);   // timing experiments (development library only)
   const bf16_t* x = static_cast<const bf16_t*>(X);
   const bf16_t* g = static_cast<const bf16_t*>(f.dTdZ);
   const size_t shm = (size_t)2 * (train ? 3 : 2) * FK * 128 * sizeof(short);
@@ -1097,7 +1077,7 @@ int pc_fused_dw(const PcFusedWs& f, const void* X, float* dWt, float* dWa, int R
       attr_set = true;                                                                                          \
     }                                                                                                           \
     hipLaunchKernelGGL((pc_bwd_dw_kernel<TR>), dim3(ctiles, S), dim3(512), shm, st, x, g, f.maskbits, f.partial, \
-                       R, C, rows_per_split, dw_exp);                                                           \
+                       R, C, rows_per_split);                                                                   \
   } while (0)
   if (train) APA_DW(true); else APA_DW(false);
 #undef APA_DW

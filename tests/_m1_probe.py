@@ -35,7 +35,7 @@ M1_SYMBOLS = ('apa_probe_m1_version', 'apa_probe_m1_trace_size', 'apa_probe_m1_p
 
 # M1Trace enum values (csrc/apa_internal.h)
 POOLS = {0: 'none', 1: 'stream', 2: 'vec', 3: 'generic'}
-LOGITS = {0: 'none', 1: 'xent', 2: 'xent_probs', 3: 'logits2', 4: 'partial', 5: 'sgemm'}
+LOGITS = {0: 'none', 1: 'xent', 2: 'xent_probs', 3: 'logits2', 5: 'sgemm'}   # (4: the retired partial-logits form)
 HEADS = {0: 'none', 1: 'tiles', 2: 'rows', 3: 'small', 4: 'sgemm'}
 GEMVS = {0: 'none', 1: 'bwd2', 2: 'bwd2_rank1', 3: 'bwd'}
 REDUCES = {0: 'none', 1: 'colsum', 2: 'bwd_reduce'}
@@ -44,17 +44,6 @@ _ENUMS = {'pool_fwd': POOLS, 'pool_bwd': POOLS, 'logits': LOGITS, 'head': HEADS,
 
 # support bits of apa_probe_m1_support
 SUP_STREAM, SUP_VEC, SUP_GENERIC, SUP_LOGITS2, SUP_SMALL, SUP_HEAD = 1, 2, 4, 8, 16, 32
-
-# Template instances the product build can never launch (kept for the development build's A/B knobs): the dispatch
-# asks for the streaming kernels first, and every C these per-pixel instances serve is a streaming C; m1_logits2
-# serves every C % 64 == 0, which includes every C that m1_logits (C % 128 == 0) serves.
-UNREACHABLE = {
-    'm1_pool_fwd_kernel<float, 4> / m1_bwd_main_kernel<float, 4>': ('vec', 'f32', 1024),
-    'm1_pool_fwd_kernel<float, 8> / m1_bwd_main_kernel<float, 8>': ('vec', 'f32', 2048),
-    'm1_pool_fwd_kernel<bf16_t, 4> / m1_bwd_main_kernel<bf16_t, 4>': ('vec', 'bf16', 2048),
-    'm1_logits_partial_kernel (m1_logits)': ('logits_partial', None, None),
-}
-
 
 class M1Trace(ctypes.Structure):
     _fields_ = [(n, ctypes.c_int) for n in (

@@ -381,6 +381,9 @@ TWIN_CASES = [
     # the same at R = 31 x 196 (not a multiple of 8): not bf16-eligible -> generic kernel, two launches
     C('pc_bwd_dwt_dwa_twin_ragged', _kinds('generic', split=4, reduce='scalar', twin='serial'), M=2048, N=400,
       n_valid=393, K=6076, a_kc=False, splits=4, pad=0, twin=dict(n_valid=393)),
+    # bf16-eligible, but R = 4 x 196 is not a whole number of 64-deep k tiles: the generic bf16 kernel, two launches
+    C('pc_bwd_dwt_dwa_twin_k_ragged', _kinds('bf16', split=4, reduce='vec', twin='serial'), M=2048, N=448,
+      n_valid=393, K=784, a_kc=False, splits=4, pad=0, twin=dict(n_valid=393)),
     # fp32-Wt form of Z | T: T is dropout(X) . Wt with unaligned f32 rows -> two launches
     C('pc_fwd_z_t_twin_fp32_wt', _kinds('ring', twin='serial'), M=6272, N=400, K=2048, bias=1, pad=0,
       twin=dict(N=393, tb=0, drop_a=1, keep=0.5, bias=1)),

@@ -87,24 +87,21 @@ def test_m1_probe_symbols_and_plan():
     assert mp.plan(1, 4, 2048, 2048, 51)[:2] == (1, 4)                  # P < 8: one split
 
 
-def test_m1_unreachable_instances_are_recorded():
-    """The instances _m1_probe.UNREACHABLE names are never launched by the product build: every C they would serve is
-    served first by the streaming kernels (vec), and m1_logits2 accepts every C that m1_logits does."""
+def test_m1_support_has_no_unreachable_instances():
+    """The dispatch asks for the streaming kernels first and m1_logits2 before the small-K kernels: the per-pixel
+    (vec) family has instances for no streaming C, and every C the small-K kernels accept is an m1_logits2 C."""
     from tests import _m1_probe as mp
     F32, BF16 = cof.APA_DTYPE_F32, cof.APA_DTYPE_BF16
-    for name, (kind, dt, C) in mp.UNREACHABLE.items():
-        if kind == 'vec':
-            sup = mp.support(8, C, 51, F32 if dt == 'f32' else BF16)
-            assert sup & mp.SUP_VEC and sup & mp.SUP_STREAM, name
-    for C in range(128, 8193, 128):
-        for K in (1, 51, 393, 736):
-            sup = mp.support(8, C, K, F32)
-            assert not (sup & mp.SUP_SMALL) or sup & mp.SUP_LOGITS2, (C, K)
-    # and the reachable vec instances are not streaming C's
+    for dt in (F32, BF16):
+        for C in range(8, 8193, 8):
+            for K in (1, 51, 393, 736):
+                sup = mp.support(8, C, K, dt)
+                assert not (sup & mp.SUP_VEC and sup & mp.SUP_STREAM), (dt, C, K)
+                assert not (sup & mp.SUP_SMALL) or sup & mp.SUP_LOGITS2, (dt, C, K)
+    # and the vec instances that remain serve exactly these C's
     for dt, Cs in ((F32, (256, 512)), (BF16, (512, 1024))):
-        for C in Cs:
-            sup = mp.support(8, C, 51, dt)
-            assert sup & mp.SUP_VEC and not sup & mp.SUP_STREAM, (dt, C)
+        vec = [C for C in range(8, 8193, 8) if mp.support(8, C, 51, dt) & mp.SUP_VEC]
+        assert vec == list(Cs), (dt, vec)
 
 
 def test_m1_gpu_case_table_covers_every_reachable_trace_value():

@@ -6,8 +6,8 @@ Per trial: one (X, dX) pair from the default allocator and one physically contig
 (hipExtMallocWithFlags(hipDeviceMallocContiguous)), every pair freed again, a junk allocation of growing size in
 between so that the driver hands out different physical pages.  Prints the two streaming kernels' durations (HIP event
 pairs of the library, median of 8 steps).  Contiguous pairs reproduce to +-1 %; default pairs show the placement
-lottery (N = 512 fp32: 275 ... 328 us for one binary in one process).  A/B of two builds: run it once per library
-with APA_LIB_PATH=... (the walk direction of the backward pass: build apa_m1_stream.hip with -DAPA_M1S_BWD_DOWN=0).
+lottery (N = 512 fp32: 275 ... 328 us for one binary in one process).  To compare two builds (e.g. of two commits),
+run it once per library with APA_LIB_PATH=...
 """
 import argparse
 import ctypes
