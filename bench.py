@@ -8,7 +8,8 @@ One "step" = one pass of the hot path over one batch that is already resident in
 Workload (cfg 002 semantics): per-GPU batch 32, 14x14x2048 fp32 features, K=393,
 class-agnostic bottom-up map (M=1), training-mode dropout keep=0.2 (nets_factory.py:145).
 
-    python bench.py --gpus 1 --steps 200 --warmup 20
+    python bench.py --gpus 1 --steps 200 --warmup 20            # the headline only
+    python bench.py --gpus 1 --steps 200 --warmup 20 --full     # + roofline, extra, cpu_baseline
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -24,17 +25,19 @@ What is timed, and how:
   * --dump-outputs DIR: after the timed run, what its last step computed (logits, attention map, loss,
     dX and the weight gradients, as a caller of the step receives them) is written as DIR/<name>.npy in
     float32, at most 64 MB in all.  The inputs are seeded, so two builds can be compared output for output.
-  * `roofline`: the dominant kernel (m1s_bwd_main_kernel: reads X once, writes dX once).  Its
-    duration is read live, over the same steps, from a HIP event pair the library attaches to that
+  * A plain run stops there: set-up, warm-up, the timed steps, --dump-outputs and the result line.  Everything
+    else the benchmark measures takes runs of its own and comes with --full, after the headline:
+  * `roofline` (--full): the dominant kernel (m1s_bwd_main_kernel: reads X once, writes dX once).  Its
+    duration is read live, over further steps, from a HIP event pair the library attaches to that
     dispatch (hipExtLaunchKernel start / stop events, on the launch stream).  NOTHING is subtracted:
     the pair reads ~1.2 us above rocprofv3's begin -> end of the same kernel (19.5 vs 18.3 us at
     N = 32, 1-3 % at N = 512: profiles/r02_summary.md, r02_n512_summary.md), so `frac` is the
     conservative figure; `roofline.rocprofv3` quotes the committed profiler average of this exact
     workload next to it, labelled with its source file.
-  * `extra`: the other BASELINE configs on the same driver-timed line (cfg 002 eval step, cfg 003
+  * `extra` (--full): the other BASELINE configs on the same driver-timed line (cfg 002 eval step, cfg 003
     bf16 training step, HMDB-51 per-class bf16 training step, and the headline step at N = 512,
     1.6 GB of features per pass: far outside every cache).
-  * `cpu_baseline`: the literal op-by-op PyTorch-CPU restatement of the reference graph (oracle/, a
+  * `cpu_baseline` (--full): the literal op-by-op PyTorch-CPU restatement of the reference graph (oracle/, a
     *port* -- TF1 cannot run here) timed on this box's host cores.
 """
 import argparse
@@ -69,8 +72,13 @@ def parse_args():
     ap.add_argument('--rotate', type=int, default=0,
                     help='number of (X, dX) buffer sets the steps cycle through; 0 = smallest R >= 3 with '
                          'R * (X + dX) >= 1.5 x 256 MiB (Infinity Cache); 1 = the same buffers every step')
+    ap.add_argument('--full', action='store_true',
+                    help='after the headline, also measure what takes runs of its own: per-kernel durations and '
+                         'roofline figures (`roofline`, `roofline_fwd`), the other BASELINE configs (`extra`) and '
+                         'the CPU baseline (`cpu_baseline`).  Off: the run times the headline steps and nothing else')
     ap.add_argument('--min-ms', type=float, default=50.0,
-                    help='`extra` workloads: repeat their timed loop until this much device time has been measured')
+                    help='`extra` workloads (--full): repeat their timed loop until this much device time has been '
+                         'measured')
     ap.add_argument('--repeats', type=int, default=5,
                     help='headline: the --steps timed steps are split into this many event-timed pieces; `extra` '
                          'workloads: minimum number of timed loops (median reported either way)')
@@ -100,15 +108,16 @@ def parse_args():
                     help='drive the step as three separately marshalled calls instead of one '
                          'apa_attn_head_train_step call: same kernels, more host time per step')
     ap.add_argument('--iter-size', type=int, default=2,
-                    help='extra.cfg002_train_iter_size: TRAIN.ITER_SIZE micro-batches per update (the cfg 002 / 003 '
-                         'YAMLs say 2), run side by side on separate streams (deploy.OverlappedMicroBatches) and, as '
-                         'the yardstick, one after the other; 1 = skip')
-    ap.add_argument('--no-extra', action='store_true', help='skip the `extra` workloads')
-    ap.add_argument('--extra-only', default='', help='comma-separated subset of the extra workloads (experiments)')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--cpu-seconds', type=float, default=10.0)
+                    help='--full, extra.cfg002_train_iter_size: TRAIN.ITER_SIZE micro-batches per update (the cfg '
+                         '002 / 003 YAMLs say 2), run side by side on separate streams (deploy.OverlappedMicroBatches) '
+                         'and, as the yardstick, one after the other; 1 = skip')
+    ap.add_argument('--no-extra', action='store_true', help='--full: skip the `extra` workloads')
+    ap.add_argument('--extra-only', default='',
+                    help='--full: comma-separated subset of the extra workloads (experiments)')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='--full: skip the CPU baseline')
+    ap.add_argument('--cpu-seconds', type=float, default=10.0, help='--full: timed seconds of the CPU baseline')
     ap.add_argument('--traffic-bytes', type=float, default=None,
-                    help='HBM bytes per launch of the dominant kernel from a separate rocprofv3 --pmc run')
+                    help='--full: HBM bytes per launch of the dominant kernel from a separate rocprofv3 --pmc run')
     return ap.parse_args()
 
 
@@ -425,6 +434,86 @@ def kernel_times(cof, work, step_with_hooks, barrier, n, base_hooks=None):
     return f, b
 
 
+def kernel_rooflines(args, cof, work, step, barrier, base_hooks, workload):
+    """--full: `roofline` and `roofline_fwd` of the headline workload.  The two streaming kernels are timed over
+    further live steps (eager launches) by the dispatch timestamps the library attaches; their algorithmic bytes
+    over that time against the HBM peak, next to the committed profiler figures of exactly this workload."""
+    N, P, C, esz = work.N, work.P, work.C, work.esz
+    kt_steps = max(20, min(args.steps, 200))
+    kf, kb = kernel_times(cof, work, step, barrier, kt_steps, base_hooks=base_hooks)
+    kb_avg_ms, kf_avg_ms = sum(kb) / len(kb), sum(kf) / len(kf)
+    alg_bytes = 2.0 * N * P * C * esz           # bwd main kernel: read X once + write dX once
+    achieved = alg_bytes / (kb_avg_ms * 1e-3) / 1e9
+    fwd_bytes = 1.0 * N * P * C * esz
+    fwd_achieved = fwd_bytes / (kf_avg_ms * 1e-3) / 1e9
+
+    # HBM traffic of the dominant kernel comes from separate rocprofv3 --pmc passes (they cannot run
+    # inside this process): the newest committed summary collected on exactly this workload
+    traffic, traffic_source = args.traffic_bytes, ('--traffic-bytes' if args.traffic_bytes is not None else None)
+    if traffic is None and not args.softmax_att:
+        import glob
+        for f in sorted(glob.glob(os.path.join(ROOT, 'profiles', '*_pmc_traffic.json')), reverse=True):
+            try:
+                pmc = json.load(open(f))
+            except (OSError, ValueError):
+                continue
+            hit = [v for k, v in pmc.items() if 'bwd_main' in k and isinstance(v, dict)
+                   and v.get('workload') == workload]
+            if hit:
+                traffic = hit[0]['hbm_bytes_per_launch']
+                traffic_source = 'profiles/' + os.path.basename(f) + ' (rocprofv3 --pmc passes of this command)'
+                break
+
+    def rocprof_reference(kernel_tag, nbytes):
+        """The committed rocprofv3 --kernel-trace --stats average of the same kernel on exactly this
+        workload (profiles/<tag>_kernel_stats.csv + <tag>_bench_under_rocprof.log), for the reader who
+        wants the bench line's event-based duration next to the profiler's: a file, labelled as such."""
+        import csv
+        import glob
+        for f in sorted(glob.glob(os.path.join(ROOT, 'profiles', '*_kernel_stats.csv')), reverse=True):
+            log = f.replace('_kernel_stats.csv', '_bench_under_rocprof.log')
+            try:
+                if json.loads(open(log).read().strip().splitlines()[-1])['config']['workload'] != workload:
+                    continue
+                for r in csv.DictReader(open(f)):
+                    if kernel_tag in r['Name']:
+                        us = float(r['AverageNs']) / 1e3
+                        return {'kernel_avg_us': round(us, 3), 'frac': round(nbytes / (us * 1e-6) / 1e9 / HBM_PEAK_GBS, 4),
+                                'source': 'profiles/' + os.path.basename(f)}
+            except (OSError, ValueError, KeyError, IndexError):
+                continue
+        return None
+
+    stream_kernel = (C % 1024 == 0 and args.dtype == 'f32') or (C == 2048)
+    return {
+        'roofline': {
+            'bound': 'hbm',
+            'kernel': 'm1s_bwd_main_kernel' if stream_kernel else 'm1_bwd_main_kernel',
+            'achieved': round(achieved, 1),
+            'peak': HBM_PEAK_GBS,
+            'unit': 'GB/s',
+            'frac': round(achieved / HBM_PEAK_GBS, 4),
+            'traffic': traffic,
+            'traffic_source': traffic_source,
+            'alg_bytes_per_launch': alg_bytes,
+            'kernel_avg_us': round(kb_avg_ms * 1e3, 3),
+            'kernel_median_us': round(_median(kb) * 1e3, 3),
+            'timer': 'hipExtLaunchKernel start/stop events around the dispatch, {} live steps, nothing '
+                     'subtracted (reads ~1.2 us above rocprofv3\'s begin->end of the same kernel: '
+                     'profiles/r03_summary.md)'.format(len(kb)),
+            'rocprofv3': rocprof_reference('bwd_main', alg_bytes),
+        },
+        'roofline_fwd': {
+            'bound': 'hbm',
+            'kernel': 'm1s_pool_fwd_kernel' if stream_kernel else 'm1_pool_fwd_kernel',
+            'achieved': round(fwd_achieved, 1), 'peak': HBM_PEAK_GBS, 'unit': 'GB/s',
+            'frac': round(fwd_achieved / HBM_PEAK_GBS, 4), 'alg_bytes_per_launch': fwd_bytes,
+            'kernel_avg_us': round(kf_avg_ms * 1e3, 3), 'kernel_median_us': round(_median(kf) * 1e3, 3),
+            'rocprofv3': rocprof_reference('pool_fwd', fwd_bytes),
+        },
+    }
+
+
 def main():
     args = parse_args()
     if 'WORLD_SIZE' not in os.environ and args.gpus > 1:
@@ -638,17 +727,7 @@ def main():
     if args.dump_outputs and rank == 0:
         dumped = dump_outputs(work.last_outputs(), args.dump_outputs)
 
-    # ---- streaming-kernel durations: dispatch timestamps, live over the same steps (eager launches) ----
-    kt_steps = max(20, min(args.steps, 200))
-    kf, kb = kernel_times(cof, work, step, barrier, kt_steps,
-                          base_hooks=overlap.hooks if overlap is not None else None)
     esz = work.esz
-    kb_avg_ms, kf_avg_ms = sum(kb) / len(kb), sum(kf) / len(kf)
-    alg_bytes = 2.0 * N * P * C * esz           # bwd main kernel: read X once + write dX once
-    achieved = alg_bytes / (kb_avg_ms * 1e-3) / 1e9
-    fwd_bytes = 1.0 * N * P * C * esz
-    fwd_achieved = fwd_bytes / (kf_avg_ms * 1e-3) / 1e9
-
     train = not args.eval_mode
     workload = ('cfg002 attentional-pooling head fwd + softmax-xent + bwd, per-GPU batch {} '
                 'x {}x{}x{} {} features, K={}, M=1 (class-agnostic bottom-up map), {}; X/dX rotated over {} '
@@ -656,46 +735,13 @@ def main():
                     N, H, H, C, args.dtype, K,
                     'dropout keep={}'.format(work.keep) if train else 'eval (no dropout)', work.rotate,
                     work.rotate * 2.0 * N * P * C * esz / 1e6))
-    # HBM traffic of the dominant kernel comes from separate rocprofv3 --pmc passes (they cannot run
-    # inside this process): the newest committed summary collected on exactly this workload
-    traffic, traffic_source = args.traffic_bytes, ('--traffic-bytes' if args.traffic_bytes is not None else None)
-    if traffic is None and not args.softmax_att:
-        import glob
-        for f in sorted(glob.glob(os.path.join(ROOT, 'profiles', '*_pmc_traffic.json')), reverse=True):
-            try:
-                pmc = json.load(open(f))
-            except (OSError, ValueError):
-                continue
-            hit = [v for k, v in pmc.items() if 'bwd_main' in k and isinstance(v, dict)
-                   and v.get('workload') == workload]
-            if hit:
-                traffic = hit[0]['hbm_bytes_per_launch']
-                traffic_source = 'profiles/' + os.path.basename(f) + ' (rocprofv3 --pmc passes of this command)'
-                break
-
-    def rocprof_reference(kernel_tag, nbytes):
-        """The committed rocprofv3 --kernel-trace --stats average of the same kernel on exactly this
-        workload (profiles/<tag>_kernel_stats.csv + <tag>_bench_under_rocprof.log), for the reader who
-        wants the bench line's event-based duration next to the profiler's: a file, labelled as such."""
-        import csv
-        import glob
-        for f in sorted(glob.glob(os.path.join(ROOT, 'profiles', '*_kernel_stats.csv')), reverse=True):
-            log = f.replace('_kernel_stats.csv', '_bench_under_rocprof.log')
-            try:
-                if json.loads(open(log).read().strip().splitlines()[-1])['config']['workload'] != workload:
-                    continue
-                for r in csv.DictReader(open(f)):
-                    if kernel_tag in r['Name']:
-                        us = float(r['AverageNs']) / 1e3
-                        return {'kernel_avg_us': round(us, 3), 'frac': round(nbytes / (us * 1e-6) / 1e9 / HBM_PEAK_GBS, 4),
-                                'source': 'profiles/' + os.path.basename(f)}
-            except (OSError, ValueError, KeyError, IndexError):
-                continue
-        return None
+    rooflines = None
+    if args.full:
+        rooflines = kernel_rooflines(args, cof, work, step, barrier, overlap.hooks if overlap is not None else None,
+                                     workload)
 
     out = None
     if rank == 0:
-        stream_kernel = (C % 1024 == 0 and args.dtype == 'f32') or (C == 2048)
         out = {
             'metric': 'images/sec attn-pool fwd+bwd, Nx14x14x2048, 393 classes',
             'value': round(N * world / sec, 1),
@@ -728,38 +774,15 @@ def main():
                               'td-weights-ready hooks; dWa|dba in-stream' if overlap is not None else
                               'two async buckets' if torch_overlap else 'one bucket, in-stream'),
             },
-            'roofline': {
-                'bound': 'hbm',
-                'kernel': 'm1s_bwd_main_kernel' if stream_kernel else 'm1_bwd_main_kernel',
-                'achieved': round(achieved, 1),
-                'peak': HBM_PEAK_GBS,
-                'unit': 'GB/s',
-                'frac': round(achieved / HBM_PEAK_GBS, 4),
-                'traffic': traffic,
-                'traffic_source': traffic_source,
-                'alg_bytes_per_launch': alg_bytes,
-                'kernel_avg_us': round(kb_avg_ms * 1e3, 3),
-                'kernel_median_us': round(_median(kb) * 1e3, 3),
-                'timer': 'hipExtLaunchKernel start/stop events around the dispatch, {} live steps, nothing '
-                         'subtracted (reads ~1.2 us above rocprofv3\'s begin->end of the same kernel: '
-                         'profiles/r03_summary.md)'.format(len(kb)),
-                'rocprofv3': rocprof_reference('bwd_main', alg_bytes),
-            },
-            'roofline_fwd': {
-                'bound': 'hbm',
-                'kernel': 'm1s_pool_fwd_kernel' if stream_kernel else 'm1_pool_fwd_kernel',
-                'achieved': round(fwd_achieved, 1), 'peak': HBM_PEAK_GBS, 'unit': 'GB/s',
-                'frac': round(fwd_achieved / HBM_PEAK_GBS, 4), 'alg_bytes_per_launch': fwd_bytes,
-                'kernel_avg_us': round(kf_avg_ms * 1e3, 3), 'kernel_median_us': round(_median(kf) * 1e3, 3),
-                'rocprofv3': rocprof_reference('pool_fwd', fwd_bytes),
-            },
             'step_roofline_frac': round((3.0 * N * P * C * esz) / sec / 1e9 / HBM_PEAK_GBS, 4),
         }
+        if rooflines is not None:
+            out.update(rooflines)
         if dumped is not None:
             out['dump_outputs'] = {'dir': args.dump_outputs, 'arrays': dumped}
 
-    # ---- the other BASELINE configs, same process, same timing discipline (N = 1 only) ----
-    if world == 1 and dist is None and not args.no_extra and out is not None:
+    # ---- --full: the other BASELINE configs, same process, same timing discipline (N = 1 only) ----
+    if args.full and world == 1 and dist is None and not args.no_extra and out is not None:
         from tools import bench_dense as bd
         extra = {}
         del work
@@ -884,7 +907,7 @@ def main():
         out['extra'] = extra
 
     if rank == 0:
-        if not args.no_cpu_baseline and world == 1:      # reported on rank 0 at N = 1 only
+        if args.full and not args.no_cpu_baseline and world == 1:      # reported on rank 0 at N = 1 only
             out['cpu_baseline'] = cpu_baseline(args, args.cpu_seconds)
         print(json.dumps(out), file=real_stdout, flush=True)
     if dist is not None:

@@ -1423,13 +1423,13 @@ def test_bench_dump_outputs_are_the_last_step_and_repeat_run_to_run(gpu, tmp_pat
 
 
 def test_bench_prints_one_json_line_with_the_contract_fields(gpu):
-    """bench.py's stdout contract: exactly one JSON line carrying the driver's fields plus the
+    """bench.py --full's stdout contract: exactly one JSON line carrying the driver's fields plus the
     `roofline` and `cpu_baseline` objects; also through the N > 1 code path (1-rank RCCL group)."""
     import json
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    for extra in (['--cpu-seconds', '1'], ['--no-cpu-baseline', '--force-dist']):
+    for extra in (['--full', '--cpu-seconds', '1'], ['--full', '--no-cpu-baseline', '--force-dist']):
         out = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--steps', '20', '--warmup', '3'] + extra,
                              capture_output=True, text=True, timeout=600, cwd=root)
         assert out.returncode == 0, out.stderr[-2000:]
@@ -1474,6 +1474,31 @@ def test_bench_prints_one_json_line_with_the_contract_fields(gpu):
             assert it['iter_size'] == 2 and 0.2 < it['overlapped']['step_roofline_frac'] < 1.0
             assert it['overlapped']['us_per_update'] < 1.05 * it['sequential']['us_per_update']
             assert it['one_pass_batch_64']['us_per_update'] < it['sequential']['us_per_update']
+
+
+def test_bench_plain_run_times_the_headline_alone(gpu):
+    """A plain `bench.py --gpus 1 --steps N --warmup W` (no --full): the same one JSON line with the driver's fields
+    and exactly N timed steps, and nothing measured beyond them -- no `roofline`, `roofline_fwd`, `extra` or
+    `cpu_baseline` (those come with --full)."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '1', '--steps', '20', '--warmup',
+                          '3'], capture_output=True, text=True, timeout=600, cwd=root)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [l for l in out.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1, lines
+    d = json.loads(lines[0])
+    for k in ('metric', 'value', 'unit', 'n_gpus', 'steps', 'warmup', 'ms_per_step', 'higher_is_better',
+              'scaling', 'vs_baseline', 'dtype', 'data', 'config'):
+        assert k in d, k
+    assert d['unit'] == 'images/sec' and d['higher_is_better'] is True and d['dtype'] == 'f32'
+    assert d['steps'] == d['timed_steps'] == 20 and d['warmup'] == 3 and d['n_gpus'] == 1 and d['repeats'] >= 5
+    assert abs(d['value'] - 32 / (d['ms_per_step'] * 1e-3)) < 0.01 * d['value'] and d['value'] > 2000
+    assert d['timed_ms_total'] >= 0.9 * 20 * d['ms_per_step'] and 'rotated over' in d['config']['workload']
+    for k in ('roofline', 'roofline_fwd', 'extra', 'cpu_baseline'):
+        assert k not in d, k
 
 
 @pytest.mark.parametrize('lanes,dtype', [(2, torch.float32), (3, torch.bfloat16)])

@@ -7,7 +7,7 @@ mkdir -p "$out"
 for r in 1 2; do
   for arm in A B; do
     lib=$A; [ $arm = B ] && lib=$B
-    APA_LIB_PATH=$lib python3 bench.py --gpus 1 --no-cpu-baseline "$@" > "$out/${arm}_$r.json" 2> "$out/${arm}_$r.err"
+    APA_LIB_PATH=$lib python3 bench.py --gpus 1 --full --no-cpu-baseline "$@" > "$out/${arm}_$r.json" 2> "$out/${arm}_$r.err"
   done
 done
 python3 - "$out" <<'PY'

@@ -61,7 +61,7 @@ def main():
     per_step = [r for r in rows if int(r['Calls']) >= 200 and 'apa::' in r['Name']]
     with open(os.path.join(prof, tag + '_summary.md'), 'w') as f:
         f.write('# {} rocprofv3 summary (MI355X, gfx950)\n\n'.format(tag))
-        cmd = 'python bench.py --steps 200 --warmup 20 --no-cpu-baseline --no-extra ' + bench_args
+        cmd = 'python bench.py --steps 200 --warmup 20 --full --no-cpu-baseline --no-extra ' + bench_args
         if os.path.exists(os.path.join(out_dir, 'cmd.txt')):
             cmd = open(os.path.join(out_dir, 'cmd.txt')).read().strip()
         f.write('Command (inside gpurun): `rocprofv3 --kernel-trace --stats --output-format csv -- {}`\n\n'
