@@ -107,6 +107,11 @@ _SIGNATURES = {
                                                                     ctypes.c_uint64, c_int, c_void_p]),
     'apa_accumulate_gradients': (c_int, [c_void_p, POINTER(c_void_p), c_int, c_size_t, c_float, c_void_p]),
     'apa_accumulate_gradients_div': (c_int, [c_void_p, POINTER(c_void_p), c_int, c_size_t, c_float, c_void_p]),
+    'apa_clip_by_norm_workspace_bytes': (c_size_t, [c_int, POINTER(c_size_t)]),
+    'apa_clip_by_norm_prepare': (c_int, [c_int, POINTER(c_void_p), POINTER(c_size_t), POINTER(c_void_p),
+                                         POINTER(c_float), POINTER(ctypes.c_ubyte), c_void_p, c_size_t,
+                                         POINTER(c_int), c_void_p]),
+    'apa_clip_by_norm_run': (c_int, [c_void_p, c_int, c_int, c_float, c_void_p]),
     'apa_pose_att_logits_workspace_bytes': (c_size_t, [c_int] * 5),
     'apa_pose_att_logits_fwd': (c_int, [c_void_p, c_void_p, POINTER(ctypes.c_int32), c_int, c_int] + [c_void_p] * 5 +
                                 [c_size_t] + [c_int] * 5 + [c_uint, c_float, ctypes.c_uint64, ctypes.c_uint64, c_int,
@@ -1334,6 +1339,101 @@ def rmsprop_step(weights, weight_decay, grad_flat, ms_flat, mom_flat, lr, decay=
                                 _dev_ptr(ms_flat, 'ms_flat', torch.float32),
                                 _dev_ptr(mom_flat, 'mom_flat', torch.float32), lr, decay, momentum, epsilon,
                                 grad_scale, sh, _stream_ptr()), 'apa_rmsprop_step')
+
+
+def _is_dense(t: torch.Tensor) -> bool:
+    """non-overlapping and dense in SOME dimension order (contiguous, channels-last, any permutation): the numel
+    elements fill [data_ptr, data_ptr + 4 * numel) exactly once"""
+    dims = sorted((st, sz) for st, sz in zip(t.stride(), t.shape) if sz != 1)
+    expect = 1
+    for st, sz in dims:
+        if st != expect:
+            return False
+        expect *= sz
+    return True
+
+
+def _elementwise_ptr(t: torch.Tensor, name: str) -> int:
+    """device pointer of an fp32 tensor an ELEMENTWISE op (plus a whole-tensor reduction) may walk as a flat array in
+    memory order: any dense layout -- e.g. the channels-last conv weights of resnet_v1 and their `.grad`."""
+    if not t.is_cuda:
+        raise ApaError('{} must live in GPU memory (got device {}); the HIP path has no CPU '
+                       'fallback'.format(name, t.device))
+    if t.dtype != torch.float32:
+        raise ApaError('{} must be {} (got {})'.format(name, torch.float32, t.dtype))
+    if not _is_dense(t):
+        raise ApaError('{} must be dense (contiguous in some dimension order; strides {})'.format(name, t.stride()))
+    return t.data_ptr()
+
+
+class BoundClipByNorm:
+    """Per-variable clip-by-norm (TRAIN.CLIP_GRADIENTS: slim.learning.clip_gradient_norms -> tf.clip_by_norm on every
+    tensor separately) with the segment table marshalled ONCE into a device workspace: `run(clip)` is two launches on
+    the current stream (or `stream`), no host sync, capturable in a hipGraph.
+
+    `tensors`: fp32 device tensors rewritten in place (views of a flat bucket at any 4-byte offset, `.grad` tensors),
+    each dense in any dimension order (channels-last included: the op is elementwise plus a whole-tensor norm, so it
+    walks memory order); `weights` / `wd`: optional per-tensor weight and coefficient -- t = g + wd * w enters the norm
+    and the output (the regulariser's gradient on clone 0); a weight must have its gradient's shape and strides;
+    `absent`: optional per-tensor flags, True = the gradient is taken as zero and only written (a variable the
+    producer never differentiates).  The constructor marshals the table (one host sync); `run` never does."""
+
+    def __init__(self, tensors, weights=None, wd=None, absent=None, stream: Optional[int] = None):
+        self.lib = load_library()
+        ts = list(tensors)
+        n = len(ts)
+        if n == 0:
+            raise ApaError('clip_by_norm: no tensors')
+        ws_ = list(weights) if weights is not None else [None] * n
+        wds = [float(x) for x in wd] if wd is not None else [0.0] * n
+        ab = [bool(x) for x in absent] if absent is not None else [False] * n
+        if not (len(ws_) == len(wds) == len(ab) == n):
+            raise ApaError('clip_by_norm: weights / wd / absent need one entry per tensor')
+        gp = []
+        for i, t in enumerate(ts):
+            gp.append(_elementwise_ptr(t, 'tensors[%d]' % i))
+        wp = []
+        for i, (w, t, d) in enumerate(zip(ws_, ts, wds)):
+            if d != 0.0:
+                if w is None or w.numel() != t.numel():
+                    raise ApaError('clip_by_norm: tensors[%d] has wd != 0 and needs a weight of its size' % i)
+                if t.numel() > 1 and (tuple(w.shape) != tuple(t.shape) or w.stride() != t.stride()) and not (
+                        w.is_contiguous() and t.is_contiguous()):
+                    raise ApaError('clip_by_norm: weights[%d] (shape %s, strides %s) must lie in memory like its '
+                                   'gradient (shape %s, strides %s)' % (i, tuple(w.shape), w.stride(), tuple(t.shape),
+                                                                       t.stride()))
+                wp.append(_elementwise_ptr(w, 'weights[%d]' % i))
+            else:
+                wp.append(None)
+        self._keep = (ts, ws_)
+        self._n = n
+        self._g = (c_void_p * n)(*gp)
+        self._sizes = (c_size_t * n)(*[t.numel() for t in ts])
+        self._w = (c_void_p * n)(*wp)
+        self._wd = (c_float * n)(*wds)
+        self._ab = (ctypes.c_ubyte * n)(*[1 if x else 0 for x in ab])
+        nbytes = int(self.lib.apa_clip_by_norm_workspace_bytes(n, self._sizes))
+        self.ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=ts[0].device)
+        nch = c_int(0)
+        st = _stream_ptr() if stream is None else stream
+        _check(self.lib.apa_clip_by_norm_prepare(n, self._g, self._sizes, self._w, self._wd, self._ab,
+                                                 self.ws.data_ptr(), self.ws.numel(), ctypes.byref(nch), st),
+               'apa_clip_by_norm_prepare')
+        self.nchunks = nch.value
+
+    def run(self, clip: float, stream: Optional[int] = None) -> None:
+        st = _stream_ptr() if stream is None else stream
+        rc = self.lib.apa_clip_by_norm_run(self.ws.data_ptr(), self._n, self.nchunks, float(clip), st)
+        if rc != 0:
+            _check(rc, 'apa_clip_by_norm_run')
+
+
+def clip_by_norm_(tensors, clip: float, weights=None, wd=None, absent=None) -> None:
+    """tf.clip_by_norm on every tensor of `tensors` separately, in place, on the current stream (see BoundClipByNorm;
+    this one-shot form marshals the table on each call -- a training loop keeps a BoundClipByNorm)."""
+    if float(clip) <= 0.0:
+        return
+    BoundClipByNorm(tensors, weights, wd, absent).run(clip)
 
 
 # --------------------------------------------------------------------------------------------

@@ -15,6 +15,7 @@ world_size 2).
 """
 from __future__ import annotations
 
+import weakref
 from typing import Dict, Iterable, Optional, Sequence, Tuple
 
 import torch
@@ -159,12 +160,21 @@ class OverlappedGradientSum:
     must not be in flight at the same time.  Every rank enqueues them in the same order.  Same sums
     as `sum_clone_gradients` (model_deploy.py:421-451), only the schedule differs."""
 
-    def __init__(self, bucket_att: torch.Tensor, bucket_td: torch.Tensor, comm_att, comm_td, device, runtime=None):
+    def __init__(self, bucket_att: torch.Tensor, bucket_td: torch.Tensor, comm_att, comm_td, device, runtime=None,
+                 clip_td=None, clip_att=None):
         """`runtime` (default: HIP through torch.cuda): where streams, events and the `apa_hooks` struct come from --
         injectable so that the schedule's bookkeeping (which communicator on which stream, the two event
         hand-overs, the order of the collectives) runs on two CPU ranks against stand-ins
-        (tests/test_multi_rank_dryrun_cpu.py); see HipRuntime for the interface."""
+        (tests/test_multi_rank_dryrun_cpu.py); see HipRuntime for the interface.
+        `clip_td` / `clip_att` (TRAIN.CLIP_GRADIENTS > 0): GradientClipper objects over the td part (td_weights,
+        td_biases) and the att part of this rank's bucket.  Clipping is per variable and the two parts hold disjoint
+        variables, so each part is clipped on its own stream right before its all-reduce: the td part on the
+        communication stream after `ready`, the att part on the compute stream."""
         rt = HipRuntime(device) if runtime is None else runtime
+        self.clip_td, self.clip_att = clip_td, clip_att
+        for c in (clip_td, clip_att):              # marshalled here, not lazily inside the first step
+            if c is not None:
+                c.bind()
         self.runtime = rt
         self.bucket_att, self.bucket_td = bucket_att, bucket_td
         self.comm_att, self.comm_td = comm_att, comm_td
@@ -181,11 +191,16 @@ class OverlappedGradientSum:
         `update_att()`: optional optimizer launches for the two parts; `update_td` runs with the
         communication stream current."""
         self.side.wait_event(self.ready)
+        if self.clip_td is not None:
+            with self.runtime.stream(self.side):
+                self.clip_td.apply()
         self.comm_td.all_reduce_(self.bucket_td, self.side)
         if update_td is not None:
             with self.runtime.stream(self.side):
                 update_td()
         self.td_done.record(self.side)
+        if self.clip_att is not None:
+            self.clip_att.apply()
         self.comm_att.all_reduce_(self.bucket_att, self.compute)
         if update_att is not None:
             update_att()
@@ -197,11 +212,130 @@ class OverlappedGradientSum:
 def add_regularization_gradient(bucket: GradientBucket, params: Dict[str, torch.Tensor],
                                 weight_decay: float, regularized: Sequence[str]) -> None:
     """d/dW [ wd * 0.5 * |W|^2 ] = wd * W, added ONCE after the reduce -- equivalent to the
-    reference adding the regularisation loss to clone 0 only (model_deploy.py:294-309)."""
+    reference adding the regularisation loss to clone 0 only (model_deploy.py:294-309).  Not with gradient
+    clipping: the clipper adds wd * w on clone 0 BEFORE the norm (GradientClipper)."""
     if weight_decay == 0.0:
         return
+    if any(c.active and c.covers(bucket.flat) for c in list(_CLIPPERS)):
+        raise ValueError('add_regularization_gradient: TRAIN.CLIP_GRADIENTS > 0 -- the GradientClipper of this bucket '
+                         'already adds wd * w on the chief clone, inside the clip')
     for name in regularized:
         bucket.views[name].add_(params[name].detach().to(bucket.flat.dtype), alpha=weight_decay)
+
+
+class GradientClipper:
+    """TRAIN.CLIP_GRADIENTS (src/train.py:507-513 -> model_deploy.py:297-304): every clone's gradient is clipped per
+    VARIABLE with tf.clip_by_norm (slim.learning.clip_gradient_norms; not a global norm) before the clones are summed
+    and before ITER_SIZE accumulation.  TF 1.x's clip_by_norm, kept in its own order:
+
+        out = (t * c) * min(rsqrt(sum(t * t)), 1 / c)        t = this clone's gradient of the variable
+
+    Clipping is not linear, so the regulariser's gradient wd * w -- part of clone 0's loss in the reference -- has to
+    be inside t on the chief clone: the clipper adds it there (for the names in `regularized`), and the optimiser must
+    not fold it in again (configure_optimizer drops its weight decay when CLIP_GRADIENTS > 0).  The 1/num_clones
+    loss scale must already be in the gradient (pass `grad_scale` to the loss kernels, not to `opt.step`).
+
+    `grads`: a GradientBucket, a dict / list of (name, fp32 tensor), or None = the `.grad` tensors of `params` (the
+    backbone under torch autograd, channels-last conv weights included; a parameter whose `.grad` is None is
+    skipped).  On a GPU the segment table is marshalled by `bind()` -- one host sync; call it once after the first
+    backward, or let the first `apply()` do it -- and `apply()` is then two launches, no sync, capturable.  The table
+    names the `.grad` tensors themselves, so keep them resident: `optimizer.zero_grad(set_to_none=False)`.  If they
+    were replaced (set_to_none=True), `apply()` re-binds (counted in `self.rebinds`) -- and refuses to do so inside a
+    graph capture.  `absent`: names whose gradient the producer never writes (FusedHeadStep's
+    pruned PoseLogits convs on cfg 002): taken as zero -- tf.gradients gives None there, so such a variable gets
+    clip(wd * w) on the chief clone and 0 elsewhere.  `apply()` works in place on the current stream: on a GPU one
+    `cof.BoundClipByNorm` (two launches, no host sync, capturable), on CPU tensors the equivalent torch expressions.
+    Order in a micro-step: backward (including FusedHeadStep's upstream rescale) -> apply() -> GradientAccumulator /
+    all-reduce -> optimiser step.  With CLIP_GRADIENTS <= 0 `apply()` does nothing."""
+
+    def __init__(self, cfg, config: DeploymentConfig, grads, params: Dict[str, torch.Tensor],
+                 regularized: Sequence[str] = (), absent: Sequence[str] = (), clip: Optional[float] = None,
+                 weight_decay: Optional[float] = None):
+        self.clip = float(cfg.TRAIN.CLIP_GRADIENTS) if clip is None else float(clip)
+        wd = float(cfg.TRAIN.WEIGHT_DECAY) if weight_decay is None else float(weight_decay)
+        self.config = config
+        self.params = params
+        reg, ab = set(regularized), set(absent)
+        self._from_params = grads is None
+        if grads is None:
+            named = [(n, None) for n in params]
+        elif isinstance(grads, GradientBucket):
+            named = [(n, grads.views[n]) for n in grads.names]
+        elif isinstance(grads, dict):
+            named = list(grads.items())
+        else:
+            named = list(grads)
+        self.names = [n for n, _ in named]
+        self._grads = [g for _, g in named]
+        self._wd = {n: (wd if (config.is_chief() and n in reg) else 0.0) for n in self.names}
+        self._absent = {n: n in ab for n in self.names}
+        self._bound = None
+        self._key = None
+        self.rebinds = 0
+        _CLIPPERS.add(self)
+
+    @property
+    def active(self) -> bool:
+        return self.clip > 0.0
+
+    def covers(self, t: torch.Tensor) -> bool:
+        """does this clipper work on (part of) the memory of `t`?  (add_regularization_gradient's guard)"""
+        base = t.untyped_storage().data_ptr()
+        return any(g is not None and g.untyped_storage().data_ptr() == base for g in self._grads)
+
+    def bind(self) -> None:
+        """Marshal the segment table of the current gradient tensors now (GPU only; one host sync).  A no-op when
+        clipping is off, on CPU tensors, or while no `.grad` exists yet."""
+        if not self.active:
+            return
+        named = self._current()
+        if not named or not named[0][1].is_cuda:
+            return
+        key = tuple((n, g.data_ptr()) for n, g in named)
+        if self._bound is not None and key == self._key:
+            return
+        if self._bound is not None:
+            self.rebinds += 1
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError('GradientClipper: the gradient tensors changed (or were never bound) inside a graph '
+                               'capture -- bind() before capturing and keep the .grad tensors resident '
+                               '(zero_grad(set_to_none=False))')
+        from .custom_ops import custom_ops_factory as cof
+        self._bound = cof.BoundClipByNorm([g for _, g in named],
+                                          weights=[self.params[n].data for n, _ in named],
+                                          wd=[self._wd[n] for n, _ in named],
+                                          absent=[self._absent[n] for n, _ in named])
+        self._key = key
+
+    def weight_decay_of(self, name: str) -> float:
+        return self._wd[name]
+
+    def _current(self):
+        if not self._from_params:
+            return list(zip(self.names, self._grads))
+        return [(n, self.params[n].grad) for n in self.names if self.params[n].grad is not None]
+
+    def apply(self) -> None:
+        if not self.active:
+            return
+        named = self._current()
+        if not named:
+            return
+        if named[0][1].is_cuda:
+            self.bind()
+            self._bound.run(self.clip)
+            return
+        c = self.clip
+        with torch.no_grad():
+            for n, g in named:
+                t = torch.zeros_like(g) if self._absent[n] else g.clone()
+                if self._wd[n] != 0.0:
+                    t = t + self._wd[n] * self.params[n].data.reshape(g.shape).to(g.dtype)
+                inv = torch.rsqrt((t * t).sum())
+                g.copy_((t * c) * torch.minimum(inv, torch.tensor(1.0 / c, dtype=g.dtype)))
+
+
+_CLIPPERS = weakref.WeakSet()      # every GradientClipper alive (add_regularization_gradient's guard)
 
 
 class GradientAccumulator:
@@ -328,6 +462,8 @@ class MomentumSGD:
     are rebuilt on the spot."""
 
     fused_images = True         # the launch of this optimiser carries image maps (the adaptive ones do not)
+    clipping = False            # TRAIN.CLIP_GRADIENTS > 0 (configure_optimizer): the L2 term is the clipper's, and
+                                # the 1/num_clones scale must be inside the gradient before the clip
 
     def __init__(self, params: Dict[str, torch.Tensor], bucket: GradientBucket, lr: float,
                  momentum: float = 0.9, weight_decay: float = 0.0, regularized: Sequence[str] = (),
@@ -453,8 +589,14 @@ class MomentumSGD:
         for o in self._img_refresh:
             o.refresh_weight_images()
 
+    def _check_grad_scale(self, grad_scale: float) -> None:
+        if self.clipping and grad_scale != 1.0:
+            raise ValueError('grad_scale %r with TRAIN.CLIP_GRADIENTS > 0: the clone loss scale has to be inside the '
+                             'gradient before the clip -- pass it to the loss / head step instead' % grad_scale)
+
     def step(self, lr: Optional[float] = None, grad_scale: float = 1.0) -> None:
         lr = self.lr if lr is None else lr
+        self._check_grad_scale(grad_scale)
         self.check_fresh()
         if self.bucket.flat.is_cuda:
             if self._bound is None:                      # marshalled once per shadow / image set
@@ -528,6 +670,7 @@ class Adam(_AdaptiveOptimizer):
 
     def step(self, lr: Optional[float] = None, grad_scale: float = 1.0) -> None:
         lr = self.lr if lr is None else lr
+        self._check_grad_scale(grad_scale)
         self.check_fresh()
         self.t += 1
         if self.bucket.flat.is_cuda:
@@ -559,6 +702,7 @@ class RMSProp(_AdaptiveOptimizer):
 
     def step(self, lr: Optional[float] = None, grad_scale: float = 1.0) -> None:
         lr = self.lr if lr is None else lr
+        self._check_grad_scale(grad_scale)
         self.check_fresh()
         if self.bucket.flat.is_cuda:
             from .custom_ops import custom_ops_factory as cof
@@ -620,9 +764,17 @@ def configure_optimizer(cfg, params: Dict[str, torch.Tensor], bucket: GradientBu
     (TRAIN.ADAM_BETA1 / ADAM_BETA2 / OPT_EPSILON) and 'rmsprop' (TRAIN.RMSPROP_DECAY / MOMENTUM / OPT_EPSILON).  The
     L2 regulariser's gradient (TRAIN.WEIGHT_DECAY on `regularized`) is folded into the same launch.  As in the
     reference, 'rmsprop' reads cfg.TRAIN.RMSPROP_DECAY, a key src/config.py does not define: without it in the
-    YAML the reference fails with an AttributeError at this point, and so does this function."""
+    YAML the reference fails with an AttributeError at this point, and so does this function.
+    With TRAIN.CLIP_GRADIENTS > 0 the L2 term is NOT folded in: the GradientClipper adds it on the chief clone, inside
+    the clip (model_deploy.py:294-304), and the optimiser refuses a `grad_scale` other than 1 in `step`."""
+    opt = _configure_optimizer(cfg, params, bucket, learning_rate, regularized, bf16_shadows, stale)
+    opt.clipping = float(cfg.TRAIN.CLIP_GRADIENTS) > 0.0
+    return opt
+
+
+def _configure_optimizer(cfg, params, bucket, learning_rate, regularized, bf16_shadows, stale):
     kind = cfg.TRAIN.OPTIMIZER
-    wd = float(cfg.TRAIN.WEIGHT_DECAY)
+    wd = 0.0 if float(cfg.TRAIN.CLIP_GRADIENTS) > 0.0 else float(cfg.TRAIN.WEIGHT_DECAY)
     if kind == 'adam':
         return Adam(params, bucket, lr=learning_rate, beta1=float(cfg.TRAIN.ADAM_BETA1),
                     beta2=float(cfg.TRAIN.ADAM_BETA2), epsilon=float(cfg.TRAIN.OPT_EPSILON), weight_decay=wd,
@@ -640,7 +792,7 @@ def configure_optimizer(cfg, params: Dict[str, torch.Tensor], bucket: GradientBu
     else:
         raise ValueError('Optimizer [%s] was not recognized' % kind)
     return MomentumSGD(params, bucket, lr=learning_rate, momentum=momentum,
-                       weight_decay=float(cfg.TRAIN.WEIGHT_DECAY), regularized=regularized, bf16_shadows=bf16_shadows,
+                       weight_decay=wd, regularized=regularized, bf16_shadows=bf16_shadows,
                        stale=stale)
 
 
@@ -682,7 +834,14 @@ class FusedHeadStep:
         opt = fused.make_optimizer(lr)                                #   needs the per-op module path
         total, end_points = fused(images, labels_action, labels_pose, pose_valid)
         total.backward()              # conv5's gradient enters the backbone's autograd graph; the head's gradients
+        fused.clip()                  # TRAIN.CLIP_GRADIENTS > 0 only (else a no-op): per-variable clip of the bucket
         opt.step()                    # already lie in fused.bucket (the flat all-reduce payload)
+
+    * TRAIN.CLIP_GRADIENTS > 0: `make_optimizer` also builds `fused.clipper` (a GradientClipper over the bucket,
+      with wd * w added on the chief clone and the PoseLogits convs of the cfg 002 forms -- never written by the
+      step -- taken as a zero gradient), and the optimiser folds no L2 term.  Call `fused.clip()` after
+      `total.backward()` (which applies the upstream coefficient to the bucket) and before any ITER_SIZE
+      accumulation or all-reduce of the bucket -- the reference clips each clone's gradient of each micro-step.
 
     * `total` = sum of the clone's tf.losses entries (each scaled by `loss_scale` = 1 / num_clones,
       model_deploy.py:223-225); the L2 regulariser is the optimiser's (`weight_decay * w` folded into its launch).
@@ -734,6 +893,7 @@ class FusedHeadStep:
         self.w1_shadow = None
         self.w2t_image = None
         self._optimizer = None
+        self.clipper = None
         self._anchor = torch.zeros((), requires_grad=True)
         self.probe_events = None
 
@@ -772,10 +932,16 @@ class FusedHeadStep:
         self._steps.clear()
         self._step_obj = self._key = None
 
-    def make_optimizer(self, learning_rate: float):
+    def make_optimizer(self, learning_rate: float, deploy_config: Optional[DeploymentConfig] = None):
         """deploy.configure_optimizer on the head's parameters (the nn.Parameters themselves: their `_version` feeds
         the staleness guard) and this object's bucket, with the bf16 copy of the pose head's W1 as a shadow of the
-        update launch when the cfg 003 step will read one (bf16 features)."""
+        update launch when the cfg 003 step will read one (bf16 features).  With TRAIN.CLIP_GRADIENTS > 0 also
+        `self.clipper` (`deploy_config`: this process's clone, default from torch.distributed)."""
+        if float(self.cfg.TRAIN.CLIP_GRADIENTS) > 0.0:
+            self.clipper = GradientClipper(self.cfg, deploy_config or DeploymentConfig(), self.bucket,
+                                           dict(self.params), regularized=self.regularized,
+                                           absent=[n for n in self.params if n not in self._written])
+            self.clipper.bind()
         shadows = None
         self._drop_steps()                           # re-bind with the shadow / the weight images
         if self.pose_form:
@@ -793,6 +959,12 @@ class FusedHeadStep:
             self._optimizer.add_image('pose_w2', cof.pose_w2t_image_map(img, w2), owner=img,
                                       refresh=lambda: img[:w2.shape[1], :w2.shape[0]].copy_(w2.t()))
         return self._optimizer
+
+    def clip(self) -> None:
+        """TRAIN.CLIP_GRADIENTS: clip this clone's gradients in the bucket (see the class docstring for the order);
+        nothing to do when clipping is off or `make_optimizer` was not called."""
+        if self.clipper is not None:
+            self.clipper.apply()
 
     def refresh_operands(self) -> None:
         """Rebuild the bf16 W1 shadow, the W2^T image and the per-class weight images of the bound step from the

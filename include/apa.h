@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define APA_VERSION 301 /* major*10000 + minor*100 + patch */
+#define APA_VERSION 302 /* major*10000 + minor*100 + patch */
 
 typedef enum apa_status {
   APA_OK = 0,
@@ -619,6 +619,32 @@ int apa_accumulate_gradients(float* out, const float* const* parts, int nparts, 
  * differs by an ulp unless ITER_SIZE is a power of two.  divisor == 0 is rejected. */
 int apa_accumulate_gradients_div(float* out, const float* const* parts, int nparts, size_t n, float divisor,
                                  void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Per-variable gradient clipping by L2 norm (TRAIN.CLIP_GRADIENTS; models/slim/deployment/model_deploy.py:297-304:
+ * slim.learning.clip_gradient_norms -> tf.clip_by_norm on every variable separately), over any number of fp32
+ * segments, in place:
+ *     t   = grads[i] + weight_decay[i] * weights[i]         (the regulariser's gradient, clone 0 only)
+ *     out = (t * clip) * min(rsqrt(sum(t * t)), 1 / clip)   (TF 1.x clip_by_norm, that order)
+ * grad_absent[i] != 0 (optional, may be NULL): the producer never writes segment i (tf.gradients -> None); its
+ * gradient is taken as zero and grads[i] is only written.  grads[i] / weights[i]: device pointers, 4-byte aligned
+ * (views of a flat bucket at any offset); weights / weight_decay may be NULL when no segment is regularised.
+ *   apa_clip_by_norm_workspace_bytes  device workspace (16-byte aligned) for this segment list
+ *   apa_clip_by_norm_prepare          writes the segment / chunk table into `ws` (once per binding; waits for its
+ *                                     own copies on `stream`, so it must not be captured) and returns the chunk
+ *                                     count the run needs
+ *   apa_clip_by_norm_run              two launches on `stream`, no host sync, no allocation: capturable in a
+ *                                     hipGraph; clip <= 0 is "off" (no launch).  Deterministic: the chunking
+ *                                     depends on the sizes only and the partial sums are combined in a fixed order.
+ *                                     `ws` must have been prepared and (nseg, nchunks) must be what prepare took /
+ *                                     returned, else APA_ERR_INVALID_ARG; the kernels also check a header that
+ *                                     prepare writes into `ws` and do nothing if it does not match.
+ */
+size_t apa_clip_by_norm_workspace_bytes(int nseg, const size_t* sizes);
+int apa_clip_by_norm_prepare(int nseg, float* const* grads, const size_t* sizes, const float* const* weights,
+                             const float* weight_decay, const unsigned char* grad_absent, void* ws, size_t ws_bytes,
+                             int* nchunks, void* stream);
+int apa_clip_by_norm_run(void* ws, int nseg, int nchunks, float clip, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Measurement helpers (bench.py): HIP events owned by the library's HIP runtime, for the prof_*

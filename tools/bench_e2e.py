@@ -15,6 +15,9 @@ replaces, these two say what share of a real step that part is and where its inp
             weight-decay term), torch.optim.SGD(momentum) on the backbone (src/train.py:90-94).
             `--module-path`: the same step through network_fn -> gen_losses -> autograd (the per-op calls) with
             torch.optim.SGD on the head -- what round 4 timed.
+            `--clip C` (TRAIN.CLIP_GRADIENTS): after the backward, the head bucket (`fused.clip()`) and the backbone's
+            .grad tensors (deploy.GradientClipper, channels-last weights included) are clipped per variable with the
+            L2 term added inside the clip; the optimisers then fold no weight decay of their own.
 
 `build(...)` returns (step, info, probe): `step()` enqueues one step; `probe(n)` re-runs n steps with HIP events
 around the head (forward: around the module call; backward: from just before `.backward()` to the hook on the
@@ -42,11 +45,14 @@ CFG003 = {'MODEL_NAME': 'resnet_v1_101', 'NET': {'USE_POSE_PRELOGITS_BASED_ATTEN
 
 
 def build(which, dev, N=32, side=448, K=393, J=16, fuse_final_relu=False, backbone='resnet_v1_101',
-          module_path=False):
+          module_path=False, clip=-1.0):
     from attentionalpoolingaction_amd import config as apa_config, loss as apa_loss, nets_factory, deploy
     train = which == 'train003'
     cfg = apa_config.reset_cfg()
     apa_config.cfg_from_dict(dict(CFG003 if train else CFG002, MODEL_NAME=backbone))
+    if train:
+        cfg.TRAIN.CLIP_GRADIENTS = float(clip)
+    clipping = train and float(clip) > 0.0
     wd = float(cfg.TRAIN.WEIGHT_DECAY)
     torch.manual_seed(int(cfg.RNG_SEED))
     fn = nets_factory.get_network_fn(backbone, K, J, cfg, weight_decay=wd, is_training=train, device=dev,
@@ -85,28 +91,42 @@ def build(which, dev, N=32, side=448, K=393, J=16, fuse_final_relu=False, backbo
     else:
         pose_lbl = torch.rand(N, H, H, J, generator=g).to(dev)
         valid = (torch.rand(N, J, generator=g) > 0.3).to(dev)
-        bb_params = [p for p in net.parameters() if p.requires_grad]
+        bb_named = {n: p for n, p in net.named_parameters() if p.requires_grad}
+        bb_params = list(bb_named.values())
         # slim's arg-scope regularises conv weights only (resnet_utils.py:241), never batch-norm beta / gamma
         decay = [p for p in bb_params if p.dim() == 4]
         nodecay = [p for p in bb_params if p.dim() != 4]
         lr, mom = float(cfg.TRAIN.LEARNING_RATE), float(cfg.TRAIN.MOMENTUM)
-        opt_bb = torch.optim.SGD([{'params': decay, 'weight_decay': wd}, {'params': nodecay, 'weight_decay': 0.0}],
-                                 lr=lr, momentum=mom, foreach=True)
+        # --clip (TRAIN.CLIP_GRADIENTS > 0): the L2 term enters each gradient BEFORE the per-variable clip
+        # (model_deploy.py:294-304) -- the clippers add it, so the optimisers' weight_decay is 0; the .grad tensors stay
+        # resident (set_to_none=False) so that the clippers' tables, marshalled once, stay valid
+        wd_opt = 0.0 if clipping else wd
+        opt_bb = torch.optim.SGD([{'params': decay, 'weight_decay': wd_opt},
+                                  {'params': nodecay, 'weight_decay': 0.0}], lr=lr, momentum=mom, foreach=True)
+        dc = deploy.DeploymentConfig(1, 0)
+        clip_bb = deploy.GradientClipper(cfg, dc, None, bb_named,
+                                         regularized=[n for n, p in bb_named.items() if p.dim() == 4])
+        to_none = not clipping
         hp = [p for p in head.parameters() if p.requires_grad]
         reg = {id(w) for w in fn.regularized_weights()}
         if not module_path:
             fused = deploy.FusedHeadStep(fn, cfg, assume_unit_upstream=True)
-            opt_fused = fused.make_optimizer(lr)
+            opt_fused = fused.make_optimizer(lr, deploy_config=dc)
 
             def step():
-                opt_bb.zero_grad(set_to_none=True)
+                opt_bb.zero_grad(set_to_none=to_none)
                 fused.probe_events = ev['head_fwd']
                 total, _ = fused(images, labels, pose_lbl, valid)
                 total.backward()              # conv5's gradient -> backbone; the head's gradients are in the bucket
+                fused.clip()                  # no-ops without --clip
+                clip_bb.apply()
                 opt_fused.step()
                 opt_bb.step()
                 return total
-        opt_head = torch.optim.SGD([{'params': [p for p in hp if id(p) in reg], 'weight_decay': wd},
+        head_named = {n: p for n, p in head.named_parameters() if p.requires_grad}
+        clip_head = deploy.GradientClipper(cfg, dc, None, head_named,
+                                           regularized=[n for n, p in head_named.items() if id(p) in reg])
+        opt_head = torch.optim.SGD([{'params': [p for p in hp if id(p) in reg], 'weight_decay': wd_opt},
                                     {'params': [p for p in hp if id(p) not in reg], 'weight_decay': 0.0}],
                                    lr=lr, momentum=mom, foreach=True)
 
@@ -117,11 +137,13 @@ def build(which, dev, N=32, side=448, K=393, J=16, fuse_final_relu=False, backbo
                                          cfg.TRAIN.LOSS_FN_POSE_WT, ep, cfg)
             # the L2 regulariser enters through the optimisers' weight_decay (same gradient, wd * w)
             total = sum(losses)
-            opt_bb.zero_grad(set_to_none=True)
-            opt_head.zero_grad(set_to_none=True)
+            opt_bb.zero_grad(set_to_none=to_none)
+            opt_head.zero_grad(set_to_none=to_none)
             if ev['head_bwd'] is not None:
                 ev['head_bwd'][0].record()
             total.backward()
+            clip_head.apply()                 # no-ops without --clip
+            clip_bb.apply()
             opt_head.step()
             opt_bb.step()
             return total
@@ -192,6 +214,8 @@ def run(which, dev, steps=6, warmup=3, **kw):
                           else ('HIP events on the compute stream: around the head module call (forward), and from '
                                 'just before .backward() to the autograd hook on the conv5 gradient (backward: '
                                 'loss kernels + head backward)')}}
+    if float(kw.get('clip', -1.0)) > 0.0:
+        out['clip_gradients'] = float(kw['clip'])
     from attentionalpoolingaction_amd import config as apa_config
     apa_config.reset_cfg()
     return out
@@ -208,13 +232,16 @@ def main():
     ap.add_argument('--backbone', default='resnet_v1_101')
     ap.add_argument('--module-path', action='store_true',
                     help='train003: drive the head through network_fn -> gen_losses -> autograd (per-op calls)')
+    ap.add_argument('--clip', type=float, default=-1.0,
+                    help='train003: TRAIN.CLIP_GRADIENTS (per-variable clip-by-norm of the head and backbone '
+                         'gradients, the L2 term inside the clip); <= 0 is off')
     args = ap.parse_args()
     from attentionalpoolingaction_amd.custom_ops import custom_ops_factory as cof
     cof.load_library()
     dev = torch.device('cuda:0')
     print(json.dumps(run(args.workload, dev, args.steps, args.warmup, N=args.batch, side=args.side,
                          fuse_final_relu=args.fuse_final_relu, backbone=args.backbone,
-                         module_path=args.module_path)))
+                         module_path=args.module_path, clip=args.clip)))
 
 
 if __name__ == '__main__':
