@@ -880,7 +880,7 @@ class HeadTrainStep:
                  weight_images=False, share_with=None):
         """`weight_images=True` (per-class maps, M == K): the padded / concatenated operand images of the weights
         are built ONCE in this step's workspace (`self.weight_image_maps` describes them) and every run() passes
-        APA_FLAG_WEIGHT_IMAGES: the caller keeps them current -- `momentum_sgd_step(..., images=...)` /
+        APA_FLAG_WEIGHT_IMAGES: the caller keeps them current -- `BoundMomentumSGD(..., images=...)` /
         `deploy.MomentumSGD.attach_weight_images(step, ...)` in the optimiser's own launch, or
         `refresh_weight_images()` after any other change of the weights.
         `share_with` (another HeadTrainStep of the same shapes): this step is bound to ITS output tensors, workspace
@@ -998,7 +998,7 @@ class PoseAttnTrainStep:
     foreign call, like the reference's one sess.run per step (src/train.py:529-566).
 
     `params = (W1, b1, W2, b2, Wa, ba, Wt, bt)` fp32; `grads = (dX, dW1, db1, dW2, db2, dWa, dba, dWt, dbt)`;
-    `w1_bf16`: optional bf16 copy of W1 the caller keeps current (momentum_sgd_step(..., shadows=...)).
+    `w1_bf16`: optional bf16 copy of W1 the caller keeps current (BoundMomentumSGD(..., shadows=...)).
     Outputs as attributes: Ppre, Pl, att, logits, zsave, abar, loss_action [1+N], loss_pose [1], G, dPl, dZ."""
 
     def __init__(self, X, params, labels, pose_labels, pose_valid, grads, *, flags=0, keep_prob=1.0, seed=0,
@@ -1007,7 +1007,7 @@ class PoseAttnTrainStep:
         """`share_with`: another PoseAttnTrainStep of the same shapes whose activation / loss buffers and workspaces
         this step is bound to as well (see HeadTrainStep).  `w2t_bf16`: optional bf16 [16, Cp + 16] image of W2^T (rows
         J.. and the pad columns zero) the caller keeps current -- `pose_w2t_image(W2)` builds it, `pose_w2t_image_map(image, W2)` describes
-        it for `momentum_sgd_step(..., images=...)`."""
+        it for `BoundMomentumSGD(..., images=...)`."""
         self.lib = load_library()
         W1, b1, W2, b2, Wa, ba, Wt, bt = params
         dX, dW1, db1, dW2, db2, dWa, dba, dWt, dbt = grads
@@ -1158,7 +1158,7 @@ class ApaWeightImage(ctypes.Structure):
 def per_class_weight_images(Wa, ba, Wt, bt, workspace, N, P, dtype):
     """apa_per_class_weight_images: build, inside `workspace`, every padded / concatenated operand image the
     per-class head (M == K) would otherwise rebuild in each call, and return their descriptions
-    [(role 'Wa'|'ba'|'Wt'|'bt', ApaWeightImage), ...] for `momentum_sgd_step(..., images=...)`.  Calls that then
+    [(role 'Wa'|'ba'|'Wt'|'bt', ApaWeightImage), ...] for `BoundMomentumSGD(..., images=...)`.  Calls that then
     pass APA_FLAG_WEIGHT_IMAGES with this workspace skip the per-step weight preparation.  `dtype`: the FEATURE
     dtype the images are for (torch.bfloat16 / torch.float32)."""
     lib = load_library()
@@ -1198,147 +1198,87 @@ def pose_w2t_image_map(image: torch.Tensor, W2: torch.Tensor) -> ApaWeightImage:
     return m
 
 
-def momentum_sgd_step(weights, weight_decay, grad_flat, acc_flat, lr, momentum=0.9, grad_scale=1.0, shadows=None,
-                      images=None):
-    """One fused launch: acc = m*acc + (grad_scale*g + wd_i*w_i); w_i -= lr*acc for every parameter.
-    `weights`: list of fp32 device tensors in bucket order; `weight_decay`: one float per tensor.
-    `shadows`: optional list (one entry per tensor, None = no shadow) of bf16 device tensors that receive the
-    UPDATED weights rounded to bf16 in the same launch (apa_momentum_sgd_step_shadow: the pose head's W1)."""
-    lib = load_library()
-    n = len(weights)
-    ptrs = (c_void_p * n)(*[_dev_ptr(w, 'weights[%d]' % i, torch.float32) for i, w in enumerate(weights)])
-    sizes = (c_size_t * n)(*[w.numel() for w in weights])
-    wds = (c_float * n)(*[float(x) for x in weight_decay])
-    total = sum(w.numel() for w in weights)
-    if grad_flat.numel() != total or acc_flat.numel() != total:
-        raise ValueError('flat buffers hold {} / {} elements, parameters {}'.format(
-            grad_flat.numel(), acc_flat.numel(), total))
-    if images:
-        # `images`: [(segment index, ApaWeightImage), ...] -- the per-class head's operand images, rewritten from the
-        # updated weights by this same launch (apa_momentum_sgd_step_images)
-        sh = None
-        if shadows is not None and any(t is not None for t in shadows):
-            sh = (c_void_p * n)(*[None if t is None else _dev_ptr(t, 'shadow', torch.bfloat16) for t in shadows])
-        ni = len(images)
-        arr = (ApaWeightImage * ni)()
-        seg = (c_int * ni)(*[int(i) for i, _ in images])
-        for q, (_, m) in enumerate(images):
-            ctypes.memmove(ctypes.addressof(arr[q]), ctypes.addressof(m), ctypes.sizeof(ApaWeightImage))
-        _check(lib.apa_momentum_sgd_step_images(
-            n, ptrs, sizes, wds, _dev_ptr(grad_flat, 'grad_flat', torch.float32),
-            _dev_ptr(acc_flat, 'acc_flat', torch.float32), lr, momentum, grad_scale, sh, ctypes.addressof(arr), seg, ni,
-            _stream_ptr()), 'apa_momentum_sgd_step_images')
-        return
-    if shadows is not None and any(t is not None for t in shadows):
-        for w_, t in zip(weights, shadows):
-            if t is not None and (t.dtype != torch.bfloat16 or t.numel() != w_.numel() or not t.is_contiguous()):
-                raise ApaError('momentum_sgd_step: a shadow must be a contiguous bf16 tensor of its weight\'s size')
-        sh = (c_void_p * n)(*[None if t is None else _dev_ptr(t, 'shadow', torch.bfloat16) for t in shadows])
-        _check(lib.apa_momentum_sgd_step_shadow(
-            n, ptrs, sizes, wds, _dev_ptr(grad_flat, 'grad_flat', torch.float32),
-            _dev_ptr(acc_flat, 'acc_flat', torch.float32), lr, momentum, grad_scale, sh, _stream_ptr()),
-            'apa_momentum_sgd_step_shadow')
-        return
-    _check(lib.apa_momentum_sgd_step(n, ptrs, sizes, wds, _dev_ptr(grad_flat, 'grad_flat', torch.float32),
-                                     _dev_ptr(acc_flat, 'acc_flat', torch.float32), lr, momentum,
-                                     grad_scale, _stream_ptr()), 'apa_momentum_sgd_step')
+class _OptimizerArgs:
+    """The argument arrays of every fused optimiser launch (apa_momentum_sgd_step[_shadow|_images], apa_adam_step,
+    apa_rmsprop_step), validated and marshalled in one place.  `weights`: fp32 device tensors in bucket order;
+    `weight_decay`: one float per tensor; `flats`: ((name, fp32 tensor in the bucket layout), ...); `shadows`: None or
+    one entry per tensor (None = no shadow) of contiguous bf16 tensors that receive the UPDATED weights rounded to bf16;
+    `images`: [(segment index, ApaWeightImage), ...] rewritten from the updated weights (momentum only).
+    `head` = (n, pointers, sizes, decays, *flat pointers), `sh` = the shadow table or None, `images` = (image array
+    address, segment array, count) or None.  The object holds every tensor and array it points at."""
 
-
-class BoundMomentumSGD:
-    """`momentum_sgd_step` with the marshalling done ONCE (the optimiser's counterpart of HeadTrainStep): the pointer /
-    size / decay arrays, the shadow table and the image maps are built here, `run(lr, momentum, grad_scale)` is one
-    foreign call.  The per-update python cost of the unbound form (~40 us of ctypes array building for eight
-    parameters) is of the order of a whole HMDB-51 head step; a training loop pays it once per binding."""
-
-    def __init__(self, weights, weight_decay, grad_flat, acc_flat, shadows=None, images=None):
-        self.lib = load_library()
+    def __init__(self, weights, weight_decay, flats, shadows=None, images=None, who='optimiser'):
         n = len(weights)
         total = sum(w.numel() for w in weights)
-        if grad_flat.numel() != total or acc_flat.numel() != total:
-            raise ValueError('flat buffers hold {} / {} elements, parameters {}'.format(
-                grad_flat.numel(), acc_flat.numel(), total))
-        self._keep = (list(weights), grad_flat, acc_flat, list(shadows) if shadows else None,
-                      list(images) if images else None)
-        self._n = n
-        self._ptrs = (c_void_p * n)(*[_dev_ptr(w, 'weights[%d]' % i, torch.float32) for i, w in enumerate(weights)])
-        self._sizes = (c_size_t * n)(*[w.numel() for w in weights])
-        self._wds = (c_float * n)(*[float(x) for x in weight_decay])
-        self._g = _dev_ptr(grad_flat, 'grad_flat', torch.float32)
-        self._a = _dev_ptr(acc_flat, 'acc_flat', torch.float32)
-        self._sh = None
+        for name, f in flats:
+            if f.numel() != total:
+                raise ValueError('%s: %s holds %d elements, the parameters %d' % (who, name, f.numel(), total))
+        self.keep = (list(weights), list(flats), shadows, images)
+        ptrs = [_dev_ptr(w, 'weights[%d]' % i, torch.float32) for i, w in enumerate(weights)]
+        self.head = (n, (c_void_p * n)(*ptrs), (c_size_t * n)(*[w.numel() for w in weights]),
+                     (c_float * n)(*[float(x) for x in weight_decay])) + \
+            tuple(_dev_ptr(f, name, torch.float32) for name, f in flats)
+        self.sh = None
         if shadows is not None and any(t is not None for t in shadows):
             for w_, t in zip(weights, shadows):
                 if t is not None and (t.dtype != torch.bfloat16 or t.numel() != w_.numel() or not t.is_contiguous()):
-                    raise ApaError('momentum_sgd_step: a shadow must be a contiguous bf16 tensor of its weight\'s size')
-            self._sh = (c_void_p * n)(*[None if t is None else _dev_ptr(t, 'shadow', torch.bfloat16) for t in shadows])
-        self._ni = 0
+                    raise ApaError('%s: a shadow must be a contiguous bf16 tensor of its weight\'s size' % who)
+            self.sh = (c_void_p * n)(*[None if t is None else _dev_ptr(t, 'shadow', torch.bfloat16) for t in shadows])
+        self.images = None
         if images:
             ni = len(images)
             self._arr = (ApaWeightImage * ni)()
             self._seg = (c_int * ni)(*[int(i) for i, _ in images])
             for q, (_, m) in enumerate(images):
                 ctypes.memmove(ctypes.addressof(self._arr[q]), ctypes.addressof(m), ctypes.sizeof(ApaWeightImage))
-            self._ni = ni
+            self.images = (ctypes.addressof(self._arr), self._seg, ni)
+
+
+class BoundMomentumSGD:
+    """One fused momentum-SGD launch with its argument arrays marshalled ONCE (the optimiser's counterpart of
+    HeadTrainStep): acc = m*acc + (grad_scale*g + wd_i*w_i); w_i -= lr*acc for every parameter, plus the bf16 shadows
+    (apa_momentum_sgd_step_shadow: the pose head's W1) and the operand images (apa_momentum_sgd_step_images) rewritten
+    from the updated weights in the same launch.  `run(lr, momentum, grad_scale)` is one foreign call.  The per-update
+    python cost of marshalling (~40 us of ctypes array building for eight parameters) is of the order of a whole
+    HMDB-51 head step; a training loop pays it once per binding."""
+
+    def __init__(self, weights, weight_decay, grad_flat, acc_flat, shadows=None, images=None):
+        self.lib = load_library()
+        a = self._args = _OptimizerArgs(weights, weight_decay, (('grad_flat', grad_flat), ('acc_flat', acc_flat)),
+                                        shadows, images, 'BoundMomentumSGD')
+        if a.images:
+            self._who, self._tail = 'apa_momentum_sgd_step_images', (a.sh,) + a.images
+        elif a.sh is not None:
+            self._who, self._tail = 'apa_momentum_sgd_step_shadow', (a.sh,)
+        else:
+            self._who, self._tail = 'apa_momentum_sgd_step', ()
+        self._fn = getattr(self.lib, self._who)
 
     def run(self, lr, momentum=0.9, grad_scale=1.0, stream: Optional[int] = None) -> None:
         st = _stream_ptr() if stream is None else stream
-        if self._ni:
-            rc = self.lib.apa_momentum_sgd_step_images(self._n, self._ptrs, self._sizes, self._wds, self._g, self._a, lr,
-                                                       momentum, grad_scale, self._sh, ctypes.addressof(self._arr),
-                                                       self._seg, self._ni, st)
-            who = 'apa_momentum_sgd_step_images'
-        elif self._sh is not None:
-            rc = self.lib.apa_momentum_sgd_step_shadow(self._n, self._ptrs, self._sizes, self._wds, self._g, self._a, lr,
-                                                       momentum, grad_scale, self._sh, st)
-            who = 'apa_momentum_sgd_step_shadow'
-        else:
-            rc = self.lib.apa_momentum_sgd_step(self._n, self._ptrs, self._sizes, self._wds, self._g, self._a, lr,
-                                                momentum, grad_scale, st)
-            who = 'apa_momentum_sgd_step'
+        rc = self._fn(*self._args.head, lr, momentum, grad_scale, *self._tail, st)
         if rc != 0:
-            _check(rc, who)
-
-
-def _optim_segments(weights, weight_decay, flats, shadows, who):
-    n = len(weights)
-    ptrs = (c_void_p * n)(*[_dev_ptr(w, 'weights[%d]' % i, torch.float32) for i, w in enumerate(weights)])
-    sizes = (c_size_t * n)(*[w.numel() for w in weights])
-    wds = (c_float * n)(*[float(x) for x in weight_decay])
-    total = sum(w.numel() for w in weights)
-    for f in flats:
-        if f.numel() != total:
-            raise ValueError('%s: a flat buffer holds %d elements, the parameters %d' % (who, f.numel(), total))
-    sh = None
-    if shadows is not None and any(t is not None for t in shadows):
-        for w_, t in zip(weights, shadows):
-            if t is not None and (t.dtype != torch.bfloat16 or t.numel() != w_.numel() or not t.is_contiguous()):
-                raise ApaError('%s: a shadow must be a contiguous bf16 tensor of its weight\'s size' % who)
-        sh = (c_void_p * n)(*[None if t is None else _dev_ptr(t, 'shadow', torch.bfloat16) for t in shadows])
-    return n, ptrs, sizes, wds, sh
+            _check(rc, self._who)
 
 
 def adam_step(weights, weight_decay, grad_flat, m_flat, v_flat, lr, t, beta1=0.9, beta2=0.999, epsilon=1e-8,
               grad_scale=1.0, shadows=None):
     """tf.train.AdamOptimizer (src/train.py:84-89) as one fused launch; `t` = number of this update (1, 2, ...):
     lr_t = lr * sqrt(1 - beta2^t) / (1 - beta1^t) is formed here, in double precision, like TF's python side."""
-    lib = load_library()
-    n, ptrs, sizes, wds, sh = _optim_segments(weights, weight_decay, (grad_flat, m_flat, v_flat), shadows, 'adam_step')
+    a = _OptimizerArgs(weights, weight_decay, (('grad_flat', grad_flat), ('m_flat', m_flat), ('v_flat', v_flat)),
+                       shadows, who='adam_step')
     lr_t = float(lr) * (1.0 - float(beta2) ** int(t)) ** 0.5 / (1.0 - float(beta1) ** int(t))
-    _check(lib.apa_adam_step(n, ptrs, sizes, wds, _dev_ptr(grad_flat, 'grad_flat', torch.float32),
-                             _dev_ptr(m_flat, 'm_flat', torch.float32), _dev_ptr(v_flat, 'v_flat', torch.float32),
-                             lr_t, beta1, beta2, epsilon, grad_scale, sh, _stream_ptr()), 'apa_adam_step')
+    _check(load_library().apa_adam_step(*a.head, lr_t, beta1, beta2, epsilon, grad_scale, a.sh, _stream_ptr()),
+           'apa_adam_step')
 
 
 def rmsprop_step(weights, weight_decay, grad_flat, ms_flat, mom_flat, lr, decay=0.9, momentum=0.0, epsilon=1e-10,
                  grad_scale=1.0, shadows=None):
     """tf.train.RMSPropOptimizer (src/train.py:95-100) as one fused launch; `ms_flat` starts at ONE."""
-    lib = load_library()
-    n, ptrs, sizes, wds, sh = _optim_segments(weights, weight_decay, (grad_flat, ms_flat, mom_flat), shadows,
-                                              'rmsprop_step')
-    _check(lib.apa_rmsprop_step(n, ptrs, sizes, wds, _dev_ptr(grad_flat, 'grad_flat', torch.float32),
-                                _dev_ptr(ms_flat, 'ms_flat', torch.float32),
-                                _dev_ptr(mom_flat, 'mom_flat', torch.float32), lr, decay, momentum, epsilon,
-                                grad_scale, sh, _stream_ptr()), 'apa_rmsprop_step')
+    a = _OptimizerArgs(weights, weight_decay, (('grad_flat', grad_flat), ('ms_flat', ms_flat), ('mom_flat', mom_flat)),
+                       shadows, who='rmsprop_step')
+    _check(load_library().apa_rmsprop_step(*a.head, lr, decay, momentum, epsilon, grad_scale, a.sh, _stream_ptr()),
+           'apa_rmsprop_step')
 
 
 def _is_dense(t: torch.Tensor) -> bool:

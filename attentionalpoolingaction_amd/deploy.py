@@ -15,8 +15,10 @@ world_size 2).
 """
 from __future__ import annotations
 
+import collections
+import functools
 import weakref
-from typing import Dict, Iterable, Optional, Sequence, Tuple
+from typing import Callable, Dict, Iterable, NamedTuple, Optional, Sequence, Tuple
 
 import torch
 import torch.distributed as dist
@@ -291,7 +293,7 @@ class GradientClipper:
         named = self._current()
         if not named or not named[0][1].is_cuda:
             return
-        key = tuple((n, g.data_ptr()) for n, g in named)
+        key = tuple((n, g.data_ptr(), self.params[n].data_ptr()) for n, g in named)    # + the weights of wd * w
         if self._bound is not None and key == self._key:
             return
         if self._bound is not None:
@@ -437,144 +439,161 @@ class OverlappedMicroBatches:
 
 class StaleOperandError(RuntimeError):
     """A head parameter was written behind the optimiser's back (load_state_dict, a checkpoint restore, any in-place
-    op on the Parameter) while a bf16 shadow / operand image of it is in use: the next step would run on the OLD
-    weights.  Call `optimizer.refresh_shadows()` (FusedHeadStep: `refresh_operands()`), or build the optimiser with
-    `stale='refresh'`."""
+    op on the Parameter, a new storage: `p.data = t`, `module.to()`) while a bf16 shadow / operand image of it is in
+    use: the next step would run on the OLD weights.  Call `optimizer.refresh_shadows()` (FusedHeadStep:
+    `refresh_operands()`), or build the optimiser with `stale='refresh'`."""
 
 
-class MomentumSGD:
-    """tf.train.MomentumOptimizer(lr, momentum) (src/train.py:90-94): acc = m*acc + g;
-    w -= lr*acc (no Nesterov, no dampening) on the flat bucket layout, with the slim L2
-    regulariser's gradient `wd * w` folded in for the names in `regularized`
-    (resnet_utils.py:241: conv weights only).  On a GPU the whole update is ONE fused HIP launch
-    (`apa_momentum_sgd_step`); CPU tensors (the gloo tests) take the equivalent torch expressions.
+class OperandCopy(NamedTuple):
+    """One entry of an optimiser's registry of operand copies (`operand_copies()`)."""
+    name: str                       # the parameter it copies
+    kind: str                       # SHADOW, LAUNCH_IMAGE or OWNER_IMAGE
+    target: object                  # the bf16 tensor (SHADOW) or the cof.ApaWeightImage map (the images)
+    owner: object                   # what the copy's memory lives in: kept alive until detach_weight_images(owner)
+    refresh: Callable[[], None]     # rebuilds the copy from the current weights
 
-    Operand copies kept current by the update (round 4-5): bf16 shadows of whole parameters, and "images" (affine
-    scatter maps into a step's workspace, `cof.ApaWeightImage`).  Every image entry carries its OWNER -- the object
-    whose memory `map.dst` points into -- so the block cannot return to the allocator while the launch still
-    scatters into it, and `detach_weight_images(owner)` drops it again.
 
-    Staleness guard (round 6): `params` may be the nn.Parameters themselves.  The fused launches write through raw
-    pointers / `.data` and never bump `Parameter._version`; anything else that writes a weight (load_state_dict,
-    `with torch.no_grad(): p.copy_(...)`) does.  The version of every parameter that has a shadow or an image is
-    recorded whenever its copies are (re)written and compared in `check_fresh()` -- called by `step()` and by
-    `FusedHeadStep` before each head step: `stale='raise'` (default) -> StaleOperandError, `'refresh'` -> the copies
-    are rebuilt on the spot."""
+SHADOW = 'shadow'                   # bf16 copy of a whole parameter, rewritten by the update launch (CPU: after it)
+LAUNCH_IMAGE = 'launch'             # operand image whose map rides in the update launch (momentum, <= 3 per parameter)
+OWNER_IMAGE = 'owner'               # operand image rebuilt by its `refresh` after each update
 
-    fused_images = True         # the launch of this optimiser carries image maps (the adaptive ones do not)
+
+class _FusedOptimizer:
+    """What the three fused optimisers share: the parameters and the flat bucket, `wd` (one L2 coefficient per bucket
+    segment, the slim regulariser's gradient `wd * w` folded into the update), `clipping`, the registry of operand
+    copies, the staleness guard and `step()`.  A subclass supplies its hyper-parameters, slot buffers (`_slots`), the
+    GPU launch (`_bind` / `_launch`) and the CPU arithmetic (`_cpu_update`).
+
+    Operand copies: bf16 shadows of whole parameters and "images" (affine scatter maps into a step's workspace,
+    `cof.ApaWeightImage`), one `OperandCopy` each.  Every entry carries its OWNER -- the object whose memory it
+    writes -- so the block cannot return to the allocator while the launch still scatters into it, and
+    `detach_weight_images(owner)` drops it again.
+
+    Freshness: the fused launches write through raw pointers / `.data` and never bump `Parameter._version`; anything
+    else that writes a weight does, and a new storage changes `data_ptr()`.  `(p._version, p.data_ptr())` of every
+    parameter that has a copy is recorded whenever its copies are (re)written and compared in `check_fresh()` (called
+    by `step()` and by `FusedHeadStep` before each head step; a host-side tuple compare): `stale='raise'` (default) ->
+    StaleOperandError, `'refresh'` -> the copies are rebuilt on the spot.  The marshalled launch is rebuilt whenever
+    the copy set, a weight's `data_ptr()`, the bucket, a slot buffer or `tuple(wd)` changes."""
+
+    fused_images = False        # does the launch carry image maps?  (otherwise every image is an OWNER_IMAGE)
     clipping = False            # TRAIN.CLIP_GRADIENTS > 0 (configure_optimizer): the L2 term is the clipper's, and
                                 # the 1/num_clones scale must be inside the gradient before the clip
 
-    def __init__(self, params: Dict[str, torch.Tensor], bucket: GradientBucket, lr: float,
-                 momentum: float = 0.9, weight_decay: float = 0.0, regularized: Sequence[str] = (),
-                 bf16_shadows: Optional[Dict[str, torch.Tensor]] = None, stale: str = 'raise'):
+    def __init__(self, params: Dict[str, torch.Tensor], bucket: GradientBucket, lr: float, weight_decay: float = 0.0,
+                 regularized: Sequence[str] = (), bf16_shadows: Optional[Dict[str, torch.Tensor]] = None,
+                 stale: str = 'raise'):
         """`bf16_shadows` {name: bf16 tensor}: operand copies the bf16 MFMA products read (the pose head's W1 for
         `cof.PoseAttnTrainStep(w1_bf16=...)`), rewritten from the updated weights by the update's own launch."""
         if stale not in ('raise', 'refresh'):
             raise ValueError("stale: 'raise' or 'refresh'")
         self.stale = stale
-        self.shadows = dict(bf16_shadows or {})
         self.params = params
         self.bucket = bucket
-        self._bound = None          # cof.BoundMomentumSGD of the current shadow / image set (marshalled once)
-        self.images = []            # [(segment, ApaWeightImage, owner)]: rewritten by the update's own launch
-        self._img_refresh = []      # owners rebuilt by their own `refresh_weight_images()` after each update
-        self._seen = {}             # name -> Parameter._version when its shadow / images were last written
-        for name, t in self.shadows.items():
-            if name not in params or t.dtype != torch.bfloat16 or t.numel() != params[name].numel():
-                raise ValueError('bf16 shadow %r: a bfloat16 tensor with the element count of that parameter' % name)
-        self.refresh_shadows()          # a shadow is current from the start, not only after the first update
         self.lr = lr
-        self.momentum = momentum
-        self.acc = torch.zeros_like(bucket.flat)
         reg = set(regularized)
         self.wd = [weight_decay if n in reg else 0.0 for n in bucket.names]
+        self.acc = torch.zeros_like(bucket.flat)
+        self._copies = []           # [OperandCopy]
+        self._watched = ()          # the names that have copies
+        self._seen = {}             # watched name -> (p._version, p.data_ptr()) when its copies were last written
+        self._bound = self._bound_key = None        # the marshalled launch and the fingerprint it was built for
+        for name, t in (bf16_shadows or {}).items():
+            if name not in params or t.dtype != torch.bfloat16 or t.numel() != params[name].numel():
+                raise ValueError('bf16 shadow %r: a bfloat16 tensor with the element count of that parameter' % name)
+            self._add([OperandCopy(name, SHADOW, t, t, self._shadow_writer(name, t))])
+        self.refresh_shadows()          # a shadow is current from the start, not only after the first update
 
-    # -- operand images ------------------------------------------------------------------------------------------
+    def _shadow_writer(self, name, t):
+        def write():
+            with torch.no_grad():
+                t.copy_(self.params[name].data.reshape(t.shape))
+        return write
+
+    # -- registry of operand copies ------------------------------------------------------------------------------
+    def operand_copies(self) -> Tuple[OperandCopy, ...]:
+        """every bf16 shadow and operand image this optimiser keeps current (read-only)"""
+        return tuple(self._copies)
+
     def attach_weight_images(self, step, names: Dict[str, str]) -> None:
-        """Keep the per-class head's operand images current in THIS optimiser's launch: `step` is a
-        cof.HeadTrainStep(..., weight_images=True) (or anything with `.weight_image_maps` and
-        `.refresh_weight_images()`), `names` maps the roles 'Wa' / 'ba' / 'Wt' / 'bt' to parameter names of the
-        bucket.  Several steps (micro-batch lanes, rotating buffer sets) may be attached; at most three images per
-        parameter fit the fused launch, further ones are rebuilt by their step's own refresh launch after the
-        update.  The optimiser keeps `step` (hence its workspace) alive until `detach_weight_images(step)`."""
-        watched = [names[role] for role, _ in step.weight_image_maps]
-        count = {}
-        for seg, _, _ in self.images:
-            count[seg] = count.get(seg, 0) + 1
-        fits = self.fused_images
-        new = []
-        for role, m in step.weight_image_maps:
-            seg = self.bucket.names.index(names[role])
-            count[seg] = count.get(seg, 0) + 1
-            fits = fits and count[seg] <= 3
-            new.append((seg, m, step))
-        if fits:
-            self.images += new
-        else:
-            self._img_refresh.append(step)
-        self._bound = None
-        step._image_param_names = watched
-        self._note_written(watched)
-
-    def detach_weight_images(self, owner) -> None:
-        """Forget every image that lives in `owner`'s memory (a step that is dropped or re-bound): the launch stops
-        scattering into it and the reference that kept it alive is released."""
-        self.images = [e for e in self.images if e[2] is not owner]
-        self._img_refresh = [o for o in self._img_refresh if o is not owner]
-        self._bound = None
+        """Keep the per-class head's operand images current: `step` is a cof.HeadTrainStep(..., weight_images=True)
+        (or anything with `.weight_image_maps` and `.refresh_weight_images()`), `names` maps the roles 'Wa' / 'ba' /
+        'Wt' / 'bt' to parameter names of the bucket.  Several steps (micro-batch lanes, rotating buffer sets) may be
+        attached; at most three images per parameter fit the fused launch, further ones (and every image of an
+        optimiser whose launch carries none) are rebuilt by their step's own refresh launch after the update.  The
+        optimiser keeps `step` (hence its workspace) alive until `detach_weight_images(step)`."""
+        maps = [(names[role], m) for role, m in step.weight_image_maps]
+        count = collections.Counter(c.name for c in self._copies if c.kind == LAUNCH_IMAGE)
+        count.update(n for n, _ in maps)
+        kind = LAUNCH_IMAGE if self.fused_images and all(count[n] <= 3 for n, _ in maps) else OWNER_IMAGE
+        refresh = step.refresh_weight_images
+        self._add([OperandCopy(n, kind, m, step, refresh) for n, m in maps])
 
     def add_image(self, name: str, image_map, refresh=None, owner=None) -> None:
         """One more operand image of parameter `name` (a cof.ApaWeightImage, e.g. cof.pose_w2t_image_map: the bf16
-        transposed copy of the pose head's W2) to be rewritten by this optimiser's launch; `refresh()` rebuilds it
-        from the weights where the launch cannot (more than three images on one parameter; the adaptive optimisers,
-        whose launches carry no image maps) and in `refresh_images()`; `owner`: the tensor / object `image_map.dst`
-        points into (kept alive here)."""
-        seg = self.bucket.names.index(name)
-        holder = _ImageRefresh(refresh, owner, [name])
-        if self.fused_images and sum(1 for s_, _, _ in self.images if s_ == seg) < 3:
-            self.images.append((seg, image_map, holder))
-        elif refresh is not None:
-            self._img_refresh.append(holder)
-        else:
-            raise ValueError('add_image(%r): this optimiser cannot rewrite the image in its launch; pass refresh=' % name)
-        self._bound = None
-        self._note_written([name])
+        transposed copy of the pose head's W2), rewritten by this optimiser's launch where it can.  `refresh()`
+        (required) rebuilds it from the weights: after each update where the launch cannot (more than three images
+        on one parameter; the adaptive optimisers) and in `refresh_images()`; `owner`: the tensor / object
+        `image_map.dst` points into (kept alive here)."""
+        if refresh is None:
+            raise ValueError('add_image(%r): refresh= is required -- it rebuilds the image after the weights were '
+                             'written outside the optimiser' % name)
+        fits = self.fused_images and sum(c.kind == LAUNCH_IMAGE and c.name == name for c in self._copies) < 3
+        self._add([OperandCopy(name, LAUNCH_IMAGE if fits else OWNER_IMAGE, image_map, owner, refresh)])
 
-    def _image_owners(self):
-        seen, out = set(), []
-        for o in [e[2] for e in self.images] + list(self._img_refresh):
-            if id(o) not in seen:
-                seen.add(id(o))
-                out.append(o)
-        return out
+    def detach_weight_images(self, owner) -> None:
+        """Forget every copy that lives in `owner`'s memory (a step that is dropped or re-bound): the launch stops
+        scattering into it, the reference that kept it alive is released, and a name left without copies is no
+        longer watched."""
+        self._copies = [c for c in self._copies if c.owner is not owner]
+        self._changed()
+
+    def _add(self, copies) -> None:
+        for c in copies:
+            if c.name not in self.bucket.views:
+                raise ValueError('%r is not a parameter of the bucket' % c.name)
+        self._copies += copies
+        self._changed()
+        self._note_written({c.name for c in copies})
+
+    def _changed(self) -> None:
+        self._bound = None
+        self._watched = tuple(dict.fromkeys(c.name for c in self._copies))
+        self._seen = {n: self._seen[n] for n in self._watched if n in self._seen}
+
+    def _rewrite(self, kinds) -> None:
+        """run the refresh of every copy of `kinds`, each callable once"""
+        for r in {id(c.refresh): c.refresh for c in self._copies if c.kind in kinds}.values():
+            r()
+
+    def _refresh(self, kinds) -> None:
+        self._rewrite(kinds)
+        self._note_written(n for n in self._watched if all(c.kind in kinds for c in self._copies if c.name == n))
 
     def refresh_images(self) -> None:
-        """Rebuild EVERY attached operand image from the current weights (each owner's own refresh launch)."""
-        for o in self._image_owners():
-            o.refresh_weight_images()
-            self._note_written(getattr(o, '_image_param_names', ()))
+        """Rebuild EVERY operand image from the current weights (each owner's own refresh launch)."""
+        self._refresh((LAUNCH_IMAGE, OWNER_IMAGE))
 
     def refresh_shadows(self) -> None:
-        """Rewrite every bf16 operand copy AND every attached operand image from its parameter: at construction, and
-        after the weights were changed behind the optimiser's back (load_state_dict, a checkpoint restore)."""
-        with torch.no_grad():
-            for name, t in self.shadows.items():
-                t.copy_(self.params[name].data.reshape(t.shape))
-        self._note_written(self.shadows)
-        self.refresh_images()
+        """Rewrite every bf16 operand copy AND every operand image from its parameter: at construction, and after
+        the weights were changed behind the optimiser's back (load_state_dict, a checkpoint restore)."""
+        self._refresh((SHADOW, LAUNCH_IMAGE, OWNER_IMAGE))
 
     # -- staleness guard -----------------------------------------------------------------------------------------
+    def _fingerprint(self, name):
+        p = self.params[name]
+        return p._version, p.data_ptr()
+
     def _note_written(self, names) -> None:
         for n in names:
-            self._seen[n] = getattr(self.params[n], '_version', 0)
+            self._seen[n] = self._fingerprint(n)
 
     def stale_names(self):
-        return [n for n, v in self._seen.items() if getattr(self.params[n], '_version', 0) != v]
+        return [n for n in self._watched if self._fingerprint(n) != self._seen.get(n)]
 
     def check_fresh(self) -> None:
-        """Compare `Parameter._version` of every parameter with a shadow / image against the value recorded when
-        the copies were last written (a host-side integer compare, no device work)."""
+        """Compare `(p._version, p.data_ptr())` of every parameter with a shadow / image against the value recorded
+        when the copies were last written (a host-side tuple compare, no device work)."""
         bad = self.stale_names()
         if not bad:
             return
@@ -585,138 +604,141 @@ class MomentumSGD:
             '%s written outside the optimiser since their bf16 shadow / operand images were built: the head would '
             'run on the old weights -- call refresh_shadows() after load_state_dict / a restore' % ', '.join(bad))
 
-    def _after_update(self) -> None:
-        for o in self._img_refresh:
-            o.refresh_weight_images()
+    # -- the update ----------------------------------------------------------------------------------------------
+    def _slots(self):
+        return [self.acc]
 
-    def _check_grad_scale(self, grad_scale: float) -> None:
-        if self.clipping and grad_scale != 1.0:
-            raise ValueError('grad_scale %r with TRAIN.CLIP_GRADIENTS > 0: the clone loss scale has to be inside the '
-                             'gradient before the clip -- pass it to the loss / head step instead' % grad_scale)
-
-    def step(self, lr: Optional[float] = None, grad_scale: float = 1.0) -> None:
-        lr = self.lr if lr is None else lr
-        self._check_grad_scale(grad_scale)
-        self.check_fresh()
-        if self.bucket.flat.is_cuda:
-            if self._bound is None:                      # marshalled once per shadow / image set
-                from .custom_ops import custom_ops_factory as cof
-                ws = [self.params[n].data for n in self.bucket.names]
-                sh = [self.shadows.get(n) for n in self.bucket.names] if self.shadows else None
-                self._bound = cof.BoundMomentumSGD(ws, self.wd, self.bucket.flat, self.acc, shadows=sh,
-                                                   images=[(seg, m) for seg, m, _ in self.images] or None)
-            self._bound.run(lr, self.momentum, grad_scale)
-            self._after_update()
-            return
-        ws = [self.params[n].data for n in self.bucket.names]
-        o = 0
-        for w, wd in zip(ws, self.wd):
-            n = w.numel()
-            g = self.bucket.flat[o:o + n].view_as(w) * grad_scale + wd * w
-            a = self.acc[o:o + n].view_as(w)
-            a.mul_(self.momentum).add_(g)
-            w.add_(a, alpha=-lr)
-            o += n
-        for name, t in self.shadows.items():
-            t.copy_(self.params[name].data.reshape(t.shape))
-
-
-class _ImageRefresh:
-    """owner record of one `add_image` entry: keeps the image's memory alive and knows how to rebuild it"""
-
-    def __init__(self, refresh, owner, names):
-        self._refresh, self.owner, self._image_param_names = refresh, owner, list(names)
-
-    def refresh_weight_images(self) -> None:
-        if self._refresh is not None:
-            self._refresh()
-
-
-class _AdaptiveOptimizer(MomentumSGD):
-    """shared plumbing of Adam / RMSProp below: two slot buffers in the bucket's layout, the L2 term folded in"""
-
-    fused_images = False        # the adaptive launches carry no image maps: an attached owner rebuilds its images
-                                # by its own refresh launch after each update (MomentumSGD._after_update)
-
-    def __init__(self, params, bucket, lr, weight_decay=0.0, regularized=(), bf16_shadows=None, stale='raise'):
-        super().__init__(params, bucket, lr, 0.0, weight_decay, regularized, bf16_shadows, stale)
-        self.slot2 = torch.zeros_like(bucket.flat)          # self.acc is the first slot
-
-    def _cpu_shadows(self) -> None:
-        with torch.no_grad():
-            for name, t in self.shadows.items():
-                t.copy_(self.params[name].data.reshape(t.shape))
+    def _launch_key(self):
+        p = self.params
+        return ([p[n].data_ptr() for n in self.bucket.names], self.bucket.flat.data_ptr(),
+                [s.data_ptr() for s in self._slots()], tuple(self.wd))
 
     def _segments(self, grad_scale):
+        """CPU: (w, g, *slot views) per bucket segment, g with the L2 term folded in"""
         o = 0
+        slots = self._slots()
         for name, wd in zip(self.bucket.names, self.wd):
             w = self.params[name].data
             n = w.numel()
             g = self.bucket.flat[o:o + n].view_as(w) * grad_scale + wd * w
-            yield w, g, self.acc[o:o + n].view_as(w), self.slot2[o:o + n].view_as(w)
+            yield (w, g) + tuple(s[o:o + n].view_as(w) for s in slots)
             o += n
 
+    def step(self, lr: Optional[float] = None, grad_scale: float = 1.0) -> None:
+        lr = self.lr if lr is None else lr
+        if self.clipping and grad_scale != 1.0:
+            raise ValueError('grad_scale %r with TRAIN.CLIP_GRADIENTS > 0: the clone loss scale has to be inside the '
+                             'gradient before the clip -- pass it to the loss / head step instead' % grad_scale)
+        self.check_fresh()
+        if self.bucket.flat.is_cuda:
+            key = self._launch_key()
+            if self._bound is None or key != self._bound_key:
+                ws = [self.params[n].data for n in self.bucket.names]
+                shadows = {c.name: c.target for c in self._copies if c.kind == SHADOW}
+                sh = [shadows.get(n) for n in self.bucket.names] if shadows else None
+                images = [(self.bucket.names.index(c.name), c.target) for c in self._copies if c.kind == LAUNCH_IMAGE]
+                self._bound, self._bound_key = self._bind(ws, list(self.wd), sh, images), key
+            self._launch(lr, grad_scale)
+            self._rewrite((OWNER_IMAGE,))
+        else:
+            self._cpu_update(lr, grad_scale)
+            self._rewrite((SHADOW, OWNER_IMAGE))
 
-class Adam(_AdaptiveOptimizer):
+
+class MomentumSGD(_FusedOptimizer):
+    """tf.train.MomentumOptimizer(lr, momentum) (src/train.py:90-94): acc = m*acc + g;
+    w -= lr*acc (no Nesterov, no dampening) on the flat bucket layout, with the slim L2
+    regulariser's gradient `wd * w` folded in for the names in `regularized`
+    (resnet_utils.py:241: conv weights only).  On a GPU the whole update is ONE fused HIP launch
+    (`cof.BoundMomentumSGD`), which also rewrites the bf16 shadows and up to three operand images per parameter
+    from the updated weights; CPU tensors (the gloo tests) take the equivalent torch expressions.
+
+    The operand copies and their freshness rule are _FusedOptimizer's: a weight written behind the optimiser's back
+    -- a bumped `Parameter._version` or a new `data_ptr()` -- raises StaleOperandError in the next `check_fresh()` /
+    `step()` (or, `stale='refresh'`, rebuilds every copy); the launch is re-marshalled when a weight's storage, the
+    bucket, `acc`, `wd` or the copy set changed."""
+
+    fused_images = True
+
+    def __init__(self, params: Dict[str, torch.Tensor], bucket: GradientBucket, lr: float,
+                 momentum: float = 0.9, weight_decay: float = 0.0, regularized: Sequence[str] = (),
+                 bf16_shadows: Optional[Dict[str, torch.Tensor]] = None, stale: str = 'raise'):
+        super().__init__(params, bucket, lr, weight_decay, regularized, bf16_shadows, stale)
+        self.momentum = momentum
+
+    def _bind(self, ws, wd, sh, images):
+        from .custom_ops import custom_ops_factory as cof
+        return cof.BoundMomentumSGD(ws, wd, self.bucket.flat, self.acc, shadows=sh, images=images or None)
+
+    def _launch(self, lr, grad_scale):
+        self._bound.run(lr, self.momentum, grad_scale)
+
+    def _cpu_update(self, lr, grad_scale):
+        for w, g, a in self._segments(grad_scale):
+            a.mul_(self.momentum).add_(g)
+            w.add_(a, alpha=-lr)
+
+
+class Adam(_FusedOptimizer):
     """tf.train.AdamOptimizer(lr, beta1, beta2, epsilon) (src/train.py:84-89; TF 1.1 training/adam.py):
     lr_t = lr sqrt(1 - b2^t)/(1 - b1^t);  m += (g - m)(1 - b1);  v += (g^2 - v)(1 - b2);  w -= lr_t m/(sqrt(v) + eps).
     Note the reference's epsilon: cfg.TRAIN.OPT_EPSILON defaults to 1.0 (src/config.py:94).  One fused HIP launch
-    (`apa_adam_step`) on a GPU; the torch expressions on CPU tensors."""
+    (`apa_adam_step`, which carries no image maps: an attached owner rebuilds its images after each update) on a GPU;
+    the torch expressions on CPU tensors.  `acc` is m, `slot2` is v."""
 
     def __init__(self, params, bucket, lr, beta1=0.9, beta2=0.999, epsilon=1e-8, weight_decay=0.0, regularized=(),
                  bf16_shadows=None, stale='raise'):
         super().__init__(params, bucket, lr, weight_decay, regularized, bf16_shadows, stale)
+        self.slot2 = torch.zeros_like(bucket.flat)
         self.beta1, self.beta2, self.epsilon, self.t = float(beta1), float(beta2), float(epsilon), 0
 
-    def step(self, lr: Optional[float] = None, grad_scale: float = 1.0) -> None:
-        lr = self.lr if lr is None else lr
-        self._check_grad_scale(grad_scale)
-        self.check_fresh()
+    def _slots(self):
+        return [self.acc, self.slot2]
+
+    def _bind(self, ws, wd, sh, images):
+        from .custom_ops import custom_ops_factory as cof
+        return functools.partial(cof.adam_step, ws, wd, self.bucket.flat, self.acc, self.slot2, shadows=sh)
+
+    def _launch(self, lr, grad_scale):
         self.t += 1
-        if self.bucket.flat.is_cuda:
-            from .custom_ops import custom_ops_factory as cof
-            ws = [self.params[n].data for n in self.bucket.names]
-            sh = [self.shadows.get(n) for n in self.bucket.names] if self.shadows else None
-            cof.adam_step(ws, self.wd, self.bucket.flat, self.acc, self.slot2, lr, self.t, self.beta1, self.beta2,
-                          self.epsilon, grad_scale, shadows=sh)
-            self._after_update()
-            return
+        self._bound(lr, self.t, self.beta1, self.beta2, self.epsilon, grad_scale)
+
+    def _cpu_update(self, lr, grad_scale):
+        self.t += 1
         lr_t = lr * (1.0 - self.beta2 ** self.t) ** 0.5 / (1.0 - self.beta1 ** self.t)
         for w, g, m, v in self._segments(grad_scale):
             m.add_((g - m) * (1.0 - self.beta1))
             v.add_((g * g - v) * (1.0 - self.beta2))
             w.sub_(m * lr_t / (v.sqrt() + self.epsilon))
-        self._cpu_shadows()
 
 
-class RMSProp(_AdaptiveOptimizer):
+class RMSProp(_FusedOptimizer):
     """tf.train.RMSPropOptimizer(lr, decay, momentum, epsilon) (src/train.py:95-100; TF 1.1 training/rmsprop.py, not
     centered):  ms += (g^2 - ms)(1 - decay);  mom = momentum mom + lr g / sqrt(ms + eps);  w -= mom;  `ms` starts at
-    ONE.  One fused HIP launch (`apa_rmsprop_step`) on a GPU."""
+    ONE.  One fused HIP launch (`apa_rmsprop_step`, no image maps) on a GPU.  `acc` is ms, `slot2` is mom."""
 
     def __init__(self, params, bucket, lr, decay=0.9, momentum=0.0, epsilon=1e-10, weight_decay=0.0, regularized=(),
                  bf16_shadows=None, stale='raise'):
         super().__init__(params, bucket, lr, weight_decay, regularized, bf16_shadows, stale)
+        self.slot2 = torch.zeros_like(bucket.flat)
         self.decay, self.momentum, self.epsilon = float(decay), float(momentum), float(epsilon)
         self.acc.fill_(1.0)                                  # rmsprop.py _create_slots: init_rms = ones
 
-    def step(self, lr: Optional[float] = None, grad_scale: float = 1.0) -> None:
-        lr = self.lr if lr is None else lr
-        self._check_grad_scale(grad_scale)
-        self.check_fresh()
-        if self.bucket.flat.is_cuda:
-            from .custom_ops import custom_ops_factory as cof
-            ws = [self.params[n].data for n in self.bucket.names]
-            sh = [self.shadows.get(n) for n in self.bucket.names] if self.shadows else None
-            cof.rmsprop_step(ws, self.wd, self.bucket.flat, self.acc, self.slot2, lr, self.decay, self.momentum,
-                             self.epsilon, grad_scale, shadows=sh)
-            self._after_update()
-            return
+    def _slots(self):
+        return [self.acc, self.slot2]
+
+    def _bind(self, ws, wd, sh, images):
+        from .custom_ops import custom_ops_factory as cof
+        return functools.partial(cof.rmsprop_step, ws, wd, self.bucket.flat, self.acc, self.slot2, shadows=sh)
+
+    def _launch(self, lr, grad_scale):
+        self._bound(lr, self.decay, self.momentum, self.epsilon, grad_scale)
+
+    def _cpu_update(self, lr, grad_scale):
         for w, g, ms, mom in self._segments(grad_scale):
             ms.add_((g * g - ms) * (1.0 - self.decay))
             mom.mul_(self.momentum).add_(g * lr / (ms + self.epsilon).sqrt())
             w.sub_(mom)
-        self._cpu_shadows()
 
 
 def exponential_decay_lr(base_lr: float, global_step: int, decay_steps: int, decay_rate: float,
@@ -858,9 +880,9 @@ class FusedHeadStep:
       most recent: a smaller last batch of an epoch comes back every epoch).  Only the step that is about to run
       has its operand images attached to the optimiser's launch; switching detaches the previous one (the launch
       must not scatter into a workspace nobody vouches for any more) and rebuilds the images of the incoming one.
-    * before every step the optimiser's staleness guard runs (`MomentumSGD.check_fresh`): a weight written behind its
-      back (load_state_dict after make_optimizer) raises StaleOperandError -- or, with `stale='refresh'`, rebuilds
-      the bf16 shadow and every operand image first.  `refresh_operands()` does that by hand."""
+    * before every step the optimiser's staleness guard runs (`check_fresh`): a weight written behind its back
+      (load_state_dict after make_optimizer, a new storage) raises StaleOperandError -- or, with `stale='refresh'`,
+      rebuilds the bf16 shadow and every operand image first.  `refresh_operands()` does that by hand."""
 
     max_bound_steps = 4
 
@@ -955,9 +977,9 @@ class FusedHeadStep:
             # the Pl product reads W2^T as a ready-made bf16 image, rewritten by the optimiser's launch as well
             from .custom_ops import custom_ops_factory as cof
             self.w2t_image = cof.pose_w2t_image(w2)
-            img = self.w2t_image
+            img, p2 = self.w2t_image, self.params['pose_w2']
             self._optimizer.add_image('pose_w2', cof.pose_w2t_image_map(img, w2), owner=img,
-                                      refresh=lambda: img[:w2.shape[1], :w2.shape[0]].copy_(w2.t()))
+                                      refresh=lambda: img[:w2.shape[1], :w2.shape[0]].copy_(p2.data.t()))
         return self._optimizer
 
     def clip(self) -> None:
@@ -1037,7 +1059,8 @@ class FusedHeadStep:
             pose_valid = pose_valid.contiguous()
         if self._optimizer is not None:
             self._optimizer.check_fresh()                # weights written behind the optimiser's back?
-        key = (tuple(X.shape), X.dtype, self._preact)
+        # a bound step reads the weights through the pointers it was bound to: a new storage binds a new step
+        key = (tuple(X.shape), X.dtype, self._preact, tuple(p.data_ptr() for p in self.params.values()))
         st, cached = self._select(key, X, labels_action, labels_pose, pose_valid)
         if cached and self.pose_form:
             st.rebind(X=X, labels=labels_action, pose_labels=labels_pose, pose_valid=pose_valid, offset=head._step)

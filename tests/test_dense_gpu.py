@@ -427,7 +427,8 @@ def test_per_class_weight_images_kept_by_the_optimizer_launch(gpu, K, dtype, tra
     opt = deploy.MomentumSGD(params, bucket, lr=0.05, momentum=0.9, weight_decay=5e-4,
                              regularized=['att_weights', 'td_weights'])
     opt.attach_weight_images(a, {'Wa': 'att_weights', 'ba': 'att_biases', 'Wt': 'td_weights', 'bt': 'td_biases'})
-    assert opt.images and not opt._img_refresh
+    kinds = [c.kind for c in opt.operand_copies()]
+    assert deploy.LAUNCH_IMAGE in kinds and deploy.OWNER_IMAGE not in kinds
 
     def same():
         a.run(); b.run()

@@ -254,6 +254,10 @@ class _FakeImageOwner:
         self.refreshed += 1
 
 
+def _copies(opt, kind):
+    return [c for c in opt.operand_copies() if c.kind == kind]
+
+
 def test_stale_operand_guard_and_image_ownership():
     """VERDICT r05 Weak #1 / ADVICE r05: a weight written behind the optimiser's back (load_state_dict, a no_grad
     copy_) while a bf16 shadow / operand image of it is in use is caught by a host-side `Parameter._version` compare
@@ -286,14 +290,15 @@ def test_stale_operand_guard_and_image_ownership():
     roles = {'Wa': 'att_weights', 'Wt': 'td_weights'}
     opt.attach_weight_images(a, roles)
     opt.attach_weight_images(b, roles)
-    assert len(opt.images) == 4 and all(e[2] in (a, b) for e in opt.images)
+    assert [c.owner for c in _copies(opt, deploy.LAUNCH_IMAGE)] == [a, a, b, b]
     opt.detach_weight_images(a)
-    assert len(opt.images) == 2 and all(e[2] is b for e in opt.images) and not opt._img_refresh
+    assert [c.owner for c in _copies(opt, deploy.LAUNCH_IMAGE)] == [b, b]
+    assert not _copies(opt, deploy.OWNER_IMAGE)
     for _ in range(10):                                  # re-binding does not accumulate entries
         c = _FakeImageOwner()
         opt.attach_weight_images(c, roles)
         opt.detach_weight_images(c)
-    assert len(opt.images) == 2 and not opt._img_refresh
+    assert len(_copies(opt, deploy.LAUNCH_IMAGE)) == 2 and not _copies(opt, deploy.OWNER_IMAGE)
     # a written weight that has an image: refresh_shadows() rebuilds the images too
     with torch.no_grad():
         wt.mul_(2.0)
@@ -306,9 +311,48 @@ def test_stale_operand_guard_and_image_ownership():
     adam.attach_weight_images(a, roles)
     hits = []
     adam.add_image('td_weights', object(), refresh=lambda: hits.append(1))
-    assert len(adam._img_refresh) == 2 and not adam.images
+    assert [c.owner for c in _copies(adam, deploy.OWNER_IMAGE)] == [a, a, None]       # two owners, rebuilt after the
+    assert not _copies(adam, deploy.LAUNCH_IMAGE)                                     # update: none in the launch
     n0 = a.refreshed
     adam.refresh_images()
     assert a.refreshed == n0 + 1 and hits == [1]
     with pytest.raises(ValueError):
         adam.add_image('td_weights', object())           # no launch-side rewrite and no refresh: refused
+    with pytest.raises(ValueError):
+        opt.add_image('td_weights', object())            # refresh= is required on the momentum optimiser as well
+
+
+def test_stale_operand_guard_sees_a_new_storage_and_stops_at_detach():
+    """The staleness guard compares (p._version, p.data_ptr()): `p.data = t` bumps no version but is caught; once the
+    last owner of a name's copies is detached, the name is no longer watched."""
+    w1 = torch.nn.Parameter(torch.randn(6, 4))
+    params = {'pose_w1': w1, 'att_weights': torch.nn.Parameter(torch.randn(6, 3)),
+              'td_weights': torch.nn.Parameter(torch.randn(6, 3))}
+    bucket = deploy.GradientBucket({n: p.shape for n, p in params.items()}, 'cpu')
+    shadow = torch.empty(6, 4, dtype=torch.bfloat16)
+    opt = deploy.MomentumSGD(params, bucket, lr=0.1, bf16_shadows={'pose_w1': shadow})
+    w1.data = torch.randn_like(w1)                       # a new storage (load_state_dict(assign=True), module.to())
+    assert opt.stale_names() == ['pose_w1']
+    with pytest.raises(deploy.StaleOperandError, match='pose_w1'):
+        opt.step()
+    opt.stale = 'refresh'
+    bucket.flat.normal_()
+    opt.step()                                           # rebuilds the shadow first, then updates the new storage
+    assert torch.equal(shadow, w1.data.to(torch.bfloat16)) and not opt.stale_names()
+    # images: watched while an owner holds one, not after the last owner is detached
+    a, b = _FakeImageOwner(), _FakeImageOwner()
+    roles = {'Wa': 'att_weights', 'Wt': 'td_weights'}
+    opt.stale = 'raise'
+    opt.attach_weight_images(a, roles)
+    opt.attach_weight_images(b, roles)
+    opt.detach_weight_images(a)
+    with torch.no_grad():
+        params['td_weights'].mul_(2.0)
+    assert opt.stale_names() == ['td_weights']
+    opt.detach_weight_images(b)
+    assert not opt.stale_names()
+    opt.check_fresh()
+    with torch.no_grad():
+        params['att_weights'].add_(1.0)
+    opt.step()                                           # no copy of it left: nothing to raise about
+    assert [c.name for c in opt.operand_copies()] == ['pose_w1']

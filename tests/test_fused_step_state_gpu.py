@@ -65,10 +65,11 @@ def test_fused_head_step_rebinds_across_batch_shapes_without_dangling_images(gpu
             assert torch.equal(ea['Logits'], eb['Logits']) and torch.equal(ta, tb), i
             assert torch.equal(fused.bucket.flat, twin.bucket.flat), i
             assert torch.equal(fused._dX, twin._dX), i
+            images = [c for c in opt.operand_copies() if c.kind == deploy.LAUNCH_IMAGE]
             if n_images is None:
-                n_images = len(opt.images)
-            assert len(opt.images) == n_images and not opt._img_refresh
-            assert all(e[2] is fused._step_obj for e in opt.images)          # only the current step is attached
+                n_images = len(images)
+            assert len(images) == n_images and not any(c.kind == deploy.OWNER_IMAGE for c in opt.operand_copies())
+            assert all(c.owner is fused._step_obj for c in images)            # only the current step is attached
             opt.step()
             opt_t.step()
             torch.cuda.synchronize()
@@ -151,3 +152,75 @@ def test_fused_head_step_notices_weights_written_behind_the_optimiser(gpu, polic
         assert [float(l) for l in ea['Losses']] == kept
     finally:
         apa_config.reset_cfg()
+
+
+@pytest.mark.parametrize('kind', ['momentum', 'adam'])
+def test_optimiser_follows_new_storage_slots_and_decays(gpu, kind):
+    """The marshalled update launch is rebuilt when what it points at changes without a version bump: a weight's
+    storage (`p.data = t`, also of a shadowed weight under stale='refresh'), the slot buffer (`opt.acc = ...`), a
+    decay (`opt.wd[k] = ...`), and the weight a GradientClipper reads for wd * w.  After each change the next update
+    equals, bit for bit, an optimiser (and clipper) built from scratch on the new state, and the old storage is not
+    written any more."""
+    g = torch.Generator().manual_seed(21)
+    shapes = {'pose_w1': (64, 48), 'att_weights': (48, 1), 'td_weights': (64, 51), 'td_biases': (51,)}
+    reg = ['pose_w1', 'td_weights']
+    one = deploy.DeploymentConfig(num_clones=1, clone_index=0)
+
+    def build(params):
+        bucket = deploy.GradientBucket(shapes, gpu)
+        sh = {'pose_w1': torch.empty(shapes['pose_w1'], dtype=torch.bfloat16, device=gpu)}
+        kw = dict(weight_decay=5e-4, regularized=reg, bf16_shadows=sh, stale='refresh')
+        opt = (deploy.MomentumSGD(params, bucket, lr=0.05, momentum=0.9, **kw) if kind == 'momentum' else
+               deploy.Adam(params, bucket, lr=0.05, epsilon=1e-3, **kw))
+        return opt, sh['pose_w1']
+
+    def fresh(opt):
+        ref, ref_sh = build({n: p.detach().clone() for n, p in opt.params.items()})
+        ref.wd = list(opt.wd)
+        ref.acc.copy_(opt.acc)
+        if kind == 'adam':
+            ref.slot2.copy_(opt.slot2)
+            ref.t = opt.t
+        return ref, ref_sh
+
+    def same_update(opt, sh, ref, ref_sh, clippers=()):
+        grad = torch.randn(opt.bucket.flat.numel(), generator=g).to(gpu)
+        opt.bucket.flat.copy_(grad)
+        ref.bucket.flat.copy_(grad)
+        for c in clippers:
+            c.apply()
+        opt.step()
+        ref.step()
+        torch.cuda.synchronize()
+        for n in shapes:
+            assert torch.equal(opt.params[n].data, ref.params[n].data), n
+        assert torch.equal(opt.acc, ref.acc) and torch.equal(sh, ref_sh)
+        assert torch.equal(sh, opt.params['pose_w1'].data.to(torch.bfloat16))
+
+    params = {n: torch.nn.Parameter((torch.randn(s_, generator=g) / 8).to(gpu)) for n, s_ in shapes.items()}
+    opt, sh = build(params)
+    same_update(opt, sh, *fresh(opt))                                    # bound once
+    # a new storage: of an unwatched weight, and of the shadowed one (stale='refresh' rebuilds the shadow)
+    old = [params[n].data for n in ('td_weights', 'pose_w1')]
+    kept = [t.clone() for t in old]
+    for n in ('td_weights', 'pose_w1'):
+        params[n].data = torch.randn_like(params[n].data) / 8
+    same_update(opt, sh, *fresh(opt))
+    torch.cuda.synchronize()
+    assert all(torch.equal(a, b) for a, b in zip(old, kept))            # the orphaned storage is left alone
+    # a new slot buffer
+    opt.acc = torch.rand_like(opt.acc)
+    same_update(opt, sh, *fresh(opt))
+    # a new decay
+    opt.wd[2] = 1e-2
+    same_update(opt, sh, *fresh(opt))
+    # the clipper: bound once, then the weight of its wd * w term gets a new storage
+    clip = deploy.GradientClipper(None, one, opt.bucket, opt.params, regularized=reg, clip=1.0, weight_decay=5e-4)
+    ref, ref_sh = fresh(opt)
+    ref_clip = deploy.GradientClipper(None, one, ref.bucket, ref.params, regularized=reg, clip=1.0, weight_decay=5e-4)
+    same_update(opt, sh, ref, ref_sh, (clip, ref_clip))
+    params['td_weights'].data = torch.randn_like(params['td_weights'].data) / 8
+    ref, ref_sh = fresh(opt)
+    ref_clip = deploy.GradientClipper(None, one, ref.bucket, ref.params, regularized=reg, clip=1.0, weight_decay=5e-4)
+    same_update(opt, sh, ref, ref_sh, (clip, ref_clip))
+    assert clip.rebinds == 1
