@@ -777,6 +777,10 @@ static int pose_pl_launch(const bf16_t* pp, const float* W2, const float* b2, fl
                           const PosePlExtra* x, hipStream_t st) {
   const bool w2t = x && x->w2t;
   const dim3 grid(w2t ? (R + 31) / 32 : (R + 63) / 64);
+  if (PoseTrace* t = pose_trace()) {
+    t->pl = POSE_PL_FAST; t->pl_fused = x ? 1 : 0; t->pl_w2t = w2t ? 1 : 0;
+    t->pl_ks = Cp / 32 == 8 ? 8 : (Cp / 32 == 16 ? 16 : (Cp / 32 == 24 ? 24 : 32));   // (the switch below)
+  }
   const PosePlExtra none = {nullptr, nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr, 0.f, 1, nullptr};
 #define APA_PL(KSv)                                                                                              \
   do {                                                                                                           \
@@ -829,6 +833,13 @@ static PosePlan pose_plan(int N, int P, int C, int Cp, int J, int dtype) {
   return pl;
 }
 
+thread_local PoseTrace* g_pose_trace = nullptr;
+void pose_plan_offsets(int N, int P, int C, int Cp, int J, int dtype, size_t* out) {
+  const PosePlan pl = pose_plan(N, P, C, Cp, J, dtype);
+  out[0] = (size_t)pl.R; out[1] = (size_t)pl.nchunks; out[2] = pl.off_dppre; out[3] = pl.off_partial;
+  out[4] = pl.off_gemm; out[5] = pl.off_w1b; out[6] = pl.off_lpart; out[7] = pl.total;
+}
+
 __global__ __launch_bounds__(256) void f32_to_bf16_kernel(const float* __restrict__ in,
                                                           bf16_t* __restrict__ out, size_t n8) {
   for (size_t v = (size_t)blockIdx.x * 256 + threadIdx.x; v < n8; v += (size_t)gridDim.x * 256) {
@@ -841,10 +852,12 @@ __global__ __launch_bounds__(256) void f32_to_bf16_kernel(const float* __restric
 
 // W1 as the bf16 operand of the pose-head GEMMs (only when its size allows whole 16-byte vectors)
 static const void* pose_w1_operand(const float* W1, void* ws_w1b, int C, int Cp, int dtype, int* tb,
-                                   hipStream_t st, bool reuse = false) {
+                                   hipStream_t st, bool reuse = false, int* kind = nullptr) {
   *tb = 0;
+  if (kind) *kind = POSE_W1_F32;
   if (dtype != APA_DTYPE_BF16 || ((size_t)C * Cp) % 8 != 0 || (reinterpret_cast<uintptr_t>(W1) & 15))
     return W1;
+  if (kind) *kind = reuse ? POSE_W1_REUSED : POSE_W1_BF16_COPY;
   if (reuse) {   // APA_POSE_WS_FROM_FWD: the forward call's copy is still in the workspace
     *tb = 1;
     return ws_w1b;
@@ -887,7 +900,9 @@ extern "C" int apa_pose_head_fwd(const void* X, const float* W1, const float* b1
   float* gws = reinterpret_cast<float*>(static_cast<char*>(ws) + pl.off_gemm);
   const int R = (int)pl.R;
   int w1_tb = 0;
-  const void* W1op = pose_w1_operand(W1, static_cast<char*>(ws) + pl.off_w1b, C, Cp, dtype, &w1_tb, st);
+  PoseTrace* tr = pose_trace();
+  const void* W1op = pose_w1_operand(W1, static_cast<char*>(ws) + pl.off_w1b, C, Cp, dtype, &w1_tb, st, false,
+                                     tr ? &tr->w1_fwd : nullptr);
   GemmDesc g1;  // Ppre = relu(X.W1 + b1)
   g1.A = X; g1.lda = C; g1.ta = dt_code(dtype); g1.a_kc = true;
   g1.B = W1op; g1.ldb = Cp; g1.tb = w1_tb; g1.b_kc = false;
@@ -897,6 +912,7 @@ extern "C" int apa_pose_head_fwd(const void* X, const float* W1, const float* b1
   if (rc != APA_OK) return rc;
   if (pose_pl_fast(Cp, J, dtype, Ppre))   // Pl = Ppre.W2 + b2: skinny product, one wave per 16 rows
     return pose_pl_launch(static_cast<const bf16_t*>(Ppre), W2, b2, Pl, R, Cp, J, nullptr, st);
+  if (tr) tr->pl = POSE_PL_GEMM;
   GemmDesc g2;  // Pl = Ppre.W2 + b2
   g2.A = Ppre; g2.lda = Cp; g2.ta = dt_code(dtype); g2.a_kc = true;
   g2.B = W2; g2.ldb = J; g2.tb = 0; g2.b_kc = false;
@@ -950,8 +966,15 @@ static int pose_head_bwd_big(const void* X, const float* W1, const void* dPpre, 
     g.M = C; g.N = Cp; g.K = R;
     g.splits = pose_dw1_splits(C, Cp, R, dtype); g.ws = gws;
     g.tail = job;
+    PoseTrace* tr = pose_trace();
+    GemmTrace gt;
+    if (tr) g.trace = &gt;
     rc = gemm_launch(g, st);
     if (rc != APA_OK) return rc;
+    if (tr) {
+      tr->dw1_splits = gt.splits;
+      if (job) tr->colsum = job->done ? POSE_COLSUM_TAIL : POSE_COLSUM_OWN;
+    }
     if (job && !job->done) {     // no split-K reduce launch to ride on: the column sum as a launch of its own
       ColsumMore more;
       more.dwa4 = job->dwa4; more.C3 = job->C3; more.dwa5 = job->dwa5; more.C4 = job->C4;
@@ -967,9 +990,14 @@ static int pose_head_bwd_big(const void* X, const float* W1, const void* dPpre, 
     g.A = dPpre; g.lda = Cp; g.ta = tdt; g.a_kc = true;
     int w1_tb = 0;
     const void* W1op = W1_shadow;
-    if (W1_shadow && dtype == APA_DTYPE_BF16) w1_tb = 1;
-    else W1op = pose_w1_operand(W1, w + pl.off_w1b, C, Cp, dtype, &w1_tb, st,
-                                (accumulate_dX & APA_POSE_WS_FROM_FWD) != 0);
+    PoseTrace* tr = pose_trace();
+    if (W1_shadow && dtype == APA_DTYPE_BF16) {
+      w1_tb = 1;
+      if (tr) tr->w1_bwd = POSE_W1_SHADOW;
+    } else {
+      W1op = pose_w1_operand(W1, w + pl.off_w1b, C, Cp, dtype, &w1_tb, st,
+                             (accumulate_dX & APA_POSE_WS_FROM_FWD) != 0, tr ? &tr->w1_bwd : nullptr);
+    }
     g.B = W1op; g.ldb = Cp; g.tb = w1_tb; g.b_kc = true;   // W1 [C][Cp]: n = c rows, k contiguous
     g.C = dX; g.ldc = C; g.tc = tdt;
     g.M = R; g.N = C; g.K = Cp; g.beta = (accumulate_dX & 1) ? 1.f : 0.f;
@@ -979,6 +1007,7 @@ static int pose_head_bwd_big(const void* X, const float* W1, const void* dPpre, 
       g.r1_row = fuse->pool_att; g.r1_col = fuse->pool_dz; g.r1_bits = fuse->pool_bits; g.r1_P = fuse->pool_P;
       g.r1_invP = 1.0f / (float)fuse->pool_P; g.r1_inv_keep = fuse->pool_inv_keep;
     }
+    if (tr) tr->dx_beta = g.beta != 0.f ? 1 : 0;
     rc = gemm_launch(g, st);
   }
   return rc;
@@ -1042,6 +1071,10 @@ static int pose_head_bwd_impl(const void* X, const float* W1, const float* W2, c
 #define APA_ROWSM(R1v, WAv)                                                                                      \
   hipLaunchKernelGGL((pose_bwd_rows_mfma_kernel<R1v, WAv>), dim3(nblk, ngrp), dim3(64 * wpb), lds, st, dPl, W2, ext_row, \
                      ext_col, static_cast<const bf16_t*>(Ppre), static_cast<bf16_t*>(dPpre), partial, pl.R, Cp, ldp, G)
+    if (PoseTrace* t = pose_trace()) {
+      t->rows = POSE_ROWS_MFMA; t->wpb = wpb; t->ngrp = ngrp; t->G = G; t->wa = want_wa ? 1 : 0;
+      t->form = ext_row ? POSE_FORM_RANK1 : POSE_FORM_PLAIN; t->dw2 = POSE_DW2_ROWS;
+    }
     if (ext_row && want_wa) APA_ROWSM(true, true);
     else if (ext_row) APA_ROWSM(true, false);
     else APA_ROWSM(false, false);
@@ -1083,9 +1116,19 @@ static int pose_head_bwd_impl(const void* X, const float* W1, const float* W2, c
       set_error("apa_pose_head_bwd: the fused dWa / dba outputs need the rank-1 external gradient (internal)");
       return APA_ERR_INVALID_ARG;
     }
+    if (PoseTrace* t = pose_trace()) {
+      t->rows = POSE_ROWS_VALU; t->rpb = rpb; t->wa = want_wa ? 1 : 0; t->dw2 = POSE_DW2_ROWS;
+      t->form = ext_row ? POSE_FORM_RANK1 : (dPpre_ext ? POSE_FORM_EXT : POSE_FORM_PLAIN);
+      t->colsum = POSE_COLSUM_OWN;
+    }
     if (dtype == APA_DTYPE_F32) {
-      if (ext_row && want_wa) APA_ROWS(float, true, false, true);
-      else if (ext_row) APA_ROWS(float, true, false, false);
+      // (no WA arm: the fused outputs need PoseBwdFuse::dWa, which only pose_bwd_fused sets, and
+      // apa_pose_attn_train_step calls that only when pose_step_fast_ok holds -- bf16 features)
+      if (want_wa) {
+        set_error("apa_pose_head_bwd: the fused dWa / dba outputs are built for bf16 features (internal)");
+        return APA_ERR_UNSUPPORTED;
+      }
+      if (ext_row) APA_ROWS(float, true, false, false);
       else if (dPpre_ext) APA_ROWS(float, false, true, false);
       else APA_ROWS(float, false, false, false);
     } else {
@@ -1130,6 +1173,11 @@ static int pose_head_bwd_impl(const void* X, const float* W1, const float* W2, c
                          W2, static_cast<const T*>(dPpre_ext), ext_row, ext_col,                    \
                          static_cast<const T*>(Ppre), static_cast<T*>(dPpre), partial, pl.R, Cp, J); \
   } while (0)
+  if (PoseTrace* t = pose_trace()) {
+    t->rows = POSE_ROWS_DPPRE; t->jm = J <= 16 ? 16 : 32; t->colsum = POSE_COLSUM_OWN;
+    t->form = ext_row ? POSE_FORM_RANK1 : (dPpre_ext ? POSE_FORM_EXT : POSE_FORM_PLAIN);
+    t->dw2 = dPl ? POSE_DW2_GEMM : POSE_DW2_MEMSET;
+  }
   if (dtype == APA_DTYPE_F32) {
     if (J <= 16) APA_DPPRE(float, 16); else APA_DPPRE(float, 32);
   } else {
@@ -1187,8 +1235,13 @@ int pose_fwd_fused(const void* X, const float* W1, const float* b1, const float*
   const int R = (int)pl.R;
   int w1_tb = 0;
   const void* W1op = a.W1_bf16;
-  if (W1op) w1_tb = 1;
-  else W1op = pose_w1_operand(W1, w + pl.off_w1b, C, Cp, dtype, &w1_tb, st);
+  PoseTrace* tr = pose_trace();
+  if (W1op) {
+    w1_tb = 1;
+    if (tr) tr->w1_fwd = POSE_W1_SHADOW;
+  } else {
+    W1op = pose_w1_operand(W1, w + pl.off_w1b, C, Cp, dtype, &w1_tb, st, false, tr ? &tr->w1_fwd : nullptr);
+  }
   GemmDesc g1;  // Ppre = relu(X.W1 + b1)
   g1.A = X; g1.lda = C; g1.ta = dt_code(dtype); g1.a_kc = true;
   g1.B = W1op; g1.ldb = Cp; g1.tb = w1_tb; g1.b_kc = false;

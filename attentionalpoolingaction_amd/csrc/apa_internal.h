@@ -339,6 +339,23 @@ struct PoseStepArgs {
 };
 bool pose_step_fast_ok(int N, int P, int C, int Cp, int J, int dtype, const void* Ppre, const float* W2,
                        const float* wa);
+// What the pose head ran (filled on the host only, as M1Trace: the product never sets the pointer; the test-only
+// probe library does, around one call, and tests/test_pose_paths_gpu.py reads it back).  0 = not decided by this call.
+enum PoseW1 { POSE_W1_NONE = 0, POSE_W1_BF16_COPY, POSE_W1_F32, POSE_W1_REUSED, POSE_W1_SHADOW };
+enum PosePl { POSE_PL_NONE = 0, POSE_PL_FAST, POSE_PL_GEMM };
+enum PoseRows { POSE_ROWS_NONE = 0, POSE_ROWS_MFMA, POSE_ROWS_VALU, POSE_ROWS_DPPRE };
+enum PoseForm { POSE_FORM_NONE = 0, POSE_FORM_PLAIN, POSE_FORM_EXT, POSE_FORM_RANK1 };
+enum PoseDw2 { POSE_DW2_NONE = 0, POSE_DW2_ROWS, POSE_DW2_GEMM, POSE_DW2_MEMSET };
+enum PoseColsum { POSE_COLSUM_NONE = 0, POSE_COLSUM_TAIL, POSE_COLSUM_OWN };
+struct PoseTrace {
+  int w1_fwd, pl, pl_ks, pl_fused, pl_w2t;        // forward: PoseW1 of the Ppre product, PosePl, pose_pl_kernel instance
+  int rows, wpb, ngrp, G, rpb, form, wa, jm;      // backward: PoseRows; mfma: wpb / ngrp / G; valu: rpb; dppre: jm
+  int dw2, colsum, dw1_splits, w1_bwd, dx_beta;   // PoseDw2, PoseColsum, split-K of dW1, PoseW1 of the dX product
+};
+extern thread_local PoseTrace* g_pose_trace;
+inline PoseTrace* pose_trace() { return g_pose_trace; }
+// the workspace carve of the pose head: out[0..7] = R, nchunks, off_dppre, off_partial, off_gemm, off_w1b, off_lpart, total
+void pose_plan_offsets(int N, int P, int C, int Cp, int J, int dtype, size_t* out);
 void* pose_ws_loss_scratch(void* ws, int N, int P, int C, int Cp, int J, int dtype);   // >= apa_pose_l2_workspace_bytes
 int pose_fwd_fused(const void* X, const float* W1, const float* b1, const float* W2, const float* b2, void* Ppre,
                    float* Pl, void* ws, size_t ws_bytes, int N, int P, int C, int Cp, int J, int dtype,
