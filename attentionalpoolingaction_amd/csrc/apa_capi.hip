@@ -375,6 +375,7 @@ extern "C" int apa_attn_head_train_step_ex(const apa_hooks* hooks, const void* X
                               dtype, stream);
   if (rc != APA_OK) return rc;
   if (!xf.done) {
+    if (PcTrace* t = pc_trace()) if (M != 1) t->xent = PC_XENT_OWN;
     rc = apa_softmax_xent_fwd_bwd(logits, labels, loss, G, nullptr, nullptr, N, K, loss_wt, grad_scale,
                                   stream);
     if (rc != APA_OK) return rc;
@@ -550,6 +551,7 @@ extern "C" int apa_attn_head_eval_step(const void* X, const void* Xatt, const fl
   int rc = attn_pool_fwd_impl(Hooks(), nullptr, (M == 1 && !labels) ? &xf : nullptr, X, Xatt, Wa, ba, Wt, bt, logits, att, zsave, abar, nullptr, ws,
                               ws_bytes, N, P, C, Ca, K, M, eval_flags, 1.0f, 0, 0, dtype, stream);
   if (rc != APA_OK || xf.done) return rc;
+  if (PcTrace* t = pc_trace()) if (M != 1) t->xent = PC_XENT_OWN;
   if (labels)
     return apa_softmax_xent_fwd_bwd(logits, labels, loss, nullptr, probs, pred, N, K, 1.0f, 1.0f, stream);
   // no ground truth: the loss slots are scratch at the head of the workspace (label 0 everywhere)

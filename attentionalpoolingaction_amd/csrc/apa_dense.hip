@@ -1391,6 +1391,12 @@ struct PcPadList {
     PcDropArgs dr = {nullptr, nullptr, 0, 1.f, 0, 0, 0, nullptr, 0, nullptr};
     if (drop) dr = *drop;
     const unsigned npad = sg.n ? (unsigned)(((sg.end[sg.n - 1] >> 3) + 255) / 256) : 0u;
+    if (PcTrace* t = pc_trace()) {
+      const bool bwd = t->phase == 2;
+      (bwd ? t->pad_bwd : t->pad_fwd) = (npad + dr.nblocks) ? 1 : 0;
+      (bwd ? t->pad_segs_bwd : t->pad_segs_fwd) = sg.n;
+      (bwd ? t->pad_drop_bwd : t->pad_drop_fwd) = dr.nblocks ? 1 : 0;
+    }
     if (npad + dr.nblocks == 0) return;
     hipLaunchKernelGGL(pc_pad_kernel, dim3(npad + dr.nblocks), dim3(256), 0, st, sg, K, Kp, dr);
   }
@@ -1671,6 +1677,16 @@ static bool pc_cat(const void* X, int C, int Ca, int dtype) {
   return dtype == APA_DTYPE_BF16 && Ca == C && C % 8 == 0 && (reinterpret_cast<uintptr_t>(X) & 15) == 0;
 }
 
+thread_local PcTrace* g_pc_trace = nullptr;
+void pc_plan_offsets(int N, int P, int C, int Ca, int K, int dtype, size_t* out) {
+  const PcPlan pl = pc_plan(N, P, C, Ca, K, dtype);
+  const size_t v[16] = {(size_t)pl.R, (size_t)pl.Kp, pl.off_wap, pl.off_wtp, pl.off_bap, pl.off_z, pl.off_dt, pl.off_dz,
+                        pl.off_pdbt, pl.off_pdba, pl.off_gemm, pl.gemm_half, pl.off_xd, pl.off_bits, pl.off_fused,
+                        pl.total};
+  for (int i = 0; i < 16; ++i) out[i] = v[i];
+}
+int pc_bwd_act_psplit_host(int N, int kgroups, int P, int act) { return pc_bwd_act_psplit(N, kgroups, P, act); }
+
 size_t pc_workspace_bytes(int N, int P, int C, int Ca, int K, int dtype) {
   return pc_plan(N, P, C, Ca, K, dtype).total;
 }
@@ -1705,6 +1721,8 @@ int pc_weight_images(const float* Wa, const float* ba, const float* Wt, const fl
   void* WaP = cat ? static_cast<void*>(static_cast<bf16_t*>(WtP) + Kp) : static_cast<void*>(w + pl.off_wap);
   float* baP = reinterpret_cast<float*>(w + pl.off_bap);
   int n = 0;
+  PcTrace* tr = pc_trace();
+  if (tr) { tr->phase = 3; tr->wimg_cat = cat ? 1 : 0; }
   {
     PcPadList pads;
     pads.add(Wa, WaP, Ca, Kp, wb16, ldw);
@@ -1719,6 +1737,7 @@ int pc_weight_images(const float* Wa, const float* ba, const float* Wt, const fl
   }
   if (wb16 && Ca == C && K <= 64 && C % 256 == 0) {   // pc_fused_supported, minus X
     const PcFusedWs f = pc_fused_carve(w + pl.off_fused, N, P, C);
+    if (tr) tr->wimg_fused = 1;
     const int rc = pc_fused_prep(f, Wa, Wt, ba, bt, C, K, st, nullptr, true);
     if (rc != APA_OK) return rc;
     APA_HIP_CHECK(hipMemsetAsync(f.bits_tag, 0, 64, st));   // whatever the keep-bit map held: nobody may believe it
@@ -1739,6 +1758,7 @@ int pc_weight_images(const float* Wa, const float* ba, const float* Wt, const fl
     }
   }
   if (nmaps) *nmaps = n;
+  if (tr) tr->wimg_maps = n;
   return APA_OK;
 }
 
@@ -1759,7 +1779,10 @@ int pc_forward(const void* X, const void* Xatt, const float* Wa, const float* ba
   const int tdt = dt_code(dtype);
   const bool wb16 = dtype == APA_DTYPE_BF16;   // padded weights stored as bf16
   const bool fast = dtype == APA_DTYPE_BF16 && C % 8 == 0 && (reinterpret_cast<uintptr_t>(X) & 15) == 0;
+  PcTrace* tr = pc_trace();
+  if (tr) { tr->phase = 1; tr->topdown = topdown ? 1 : 0; }
   if (pc_fused_supported(N, P, C, Ca, K, dtype, X, Xatt) && !rng_external(flags)) {
+    if (tr) tr->path_fwd = PC_PATH_FUSED;
     // K <= 64 (HMDB-51): Z | T in ONE pass over X, dropout applied on the way into LDS (apa_pc_fused.hip)
     const PcFusedWs f = pc_fused_carve(w + pl.off_fused, N, P, C);
     const bool devctr = flags & APA_FLAG_RNG_DEVICE;
@@ -1800,11 +1823,16 @@ int pc_forward(const void* X, const void* Xatt, const float* Wa, const float* ba
       xe.labels = xf->labels; xe.loss = xf->loss; xe.G = xf->G; xe.gscale = xf->gscale;
       xf->done = true;
     }
+    if (tr) {
+      tr->fwd_act = PC_ACT_BF16; tr->fwd_act_xe = xent_here ? 1 : 0; tr->logits = PC_LOGITS_FWD_ACT;
+      if (xent_here) tr->xent = PC_XENT_FWD_ACT;
+    }
     hipLaunchKernelGGL(pc_fwd_act_kernel<bf16_t>, grid, dim3(64 * PC_PG), 0, st, Z, Kp, Tsave, att, logits,
                        static_cast<bf16_t*>(topdown), P, K, act_code(flags), xe);
     APA_LAUNCH_CHECK("pc_fwd_act_kernel");
     return APA_OK;
   }
+  if (tr) { tr->path_fwd = PC_PATH_GENERIC; tr->cat = cat ? 1 : 0; tr->fast = fast ? 1 : 0; }
   {
     PcPadList pads;
     if (!(flags & APA_FLAG_WEIGHT_IMAGES)) {     // else: kept current by the caller (pc_weight_images' layout)
@@ -1848,8 +1876,10 @@ int pc_forward(const void* X, const void* Xatt, const float* Wa, const float* ba
   // Z | T: same shape when the attention input has C channels too -- one launch (GemmDesc::twin), else one after
   // the other (the dispatcher decides)
   gz.twin = &gt;
+  if (tr) { gz.trace = &tr->g_z; gt.trace = &tr->g_t; tr->t_drop_a = gt.drop_a; }
   int rc = gemm_launch(gz, st);
   if (rc != APA_OK) return rc;
+  if (tr) { tr->fwd_act = dtype == APA_DTYPE_F32 ? PC_ACT_F32 : PC_ACT_BF16; tr->logits = PC_LOGITS_FWD_ACT; }
   dim3 grid(N, (K + 63) / 64);
   if (dtype == APA_DTYPE_F32)
     hipLaunchKernelGGL(pc_fwd_act_kernel<float>, grid, dim3(64 * PC_PG), 0, st, Z, Kp, Tsave, att, logits,
@@ -1865,7 +1895,7 @@ int pc_forward(const void* X, const void* Xatt, const float* Wa, const float* ba
     xf->deferred = true;
     xf->logits = logits;
   }
-  return APA_OK;
+  return APA_OK;   // (PcTrace::xent of a deferred cross-entropy: recorded where it is taken, in pc_backward)
 }
 
 int pc_backward(const void* X, const void* Xatt, const float* Wa, const float* Wt, const float* att,
@@ -1889,7 +1919,10 @@ int pc_backward(const void* X, const void* Xatt, const float* Wa, const float* W
   const bool fused = (Xatt == X);
   const int tdt = dt_code(dtype);
   const bool wb16 = dtype == APA_DTYPE_BF16;
+  PcTrace* tr = pc_trace();
+  if (tr) tr->phase = 2;
   if (pc_fused_supported(N, P, C, Ca, K, dtype, X, Xatt) && !rng_external(flags)) {
+    if (tr) tr->path_bwd = PC_PATH_FUSED;
     const PcFusedWs f = pc_fused_carve(w + pl.off_fused, N, P, C);
     int rc = APA_OK;
     const bool devctr = flags & APA_FLAG_RNG_DEVICE;
@@ -1928,6 +1961,7 @@ int pc_backward(const void* X, const void* Xatt, const float* Wa, const float* W
     hipLaunchKernelGGL(pc_bwd_act_kernel<bf16_t>, grid, dim3(64 * PC_PG), 0, st, G, att, Tsave, dTc, dTc + 64,
                        pdbt, pdba, P, K, Kp, act_code(flags), 128, df);
     APA_LAUNCH_CHECK("pc_bwd_act_kernel");
+    if (tr) { tr->bwd_act = PC_ACT_BF16; tr->ps = ps; tr->ldg = 128; tr->dx = train ? PC_DX_MID_GEMM : PC_DX_PLAIN_GEMM; }
     // dbt | dba (column sums of the activation pass's block partials), the batch mean of a folded cross-entropy
     // and the dropout counter ride on the tail blocks of the dW reduce launch
     PcDwTail tail = {pdbt, dbt, dba, N * ps, bump, nullptr, 0, 0.f, nullptr};
@@ -1947,6 +1981,7 @@ int pc_backward(const void* X, const void* Xatt, const float* Wa, const float* W
       g.B = f.Wcat2; g.ldb = 128; g.tb = 1; g.b_kc = true;
       g.C = dX; g.ldc = C; g.tc = 1;
       g.M = R; g.N = C; g.K = 128;
+      if (tr) g.trace = &tr->g_dx;
       rc = gemm_launch(g, st);
     }
     if (rc != APA_OK) return rc;
@@ -1957,6 +1992,9 @@ int pc_backward(const void* X, const void* Xatt, const float* Wa, const float* W
   // skipped.  Only the all-bf16 DMA route prepares both operands in the forward pass.
   const bool fast_bf16 = dtype == APA_DTYPE_BF16 && C % 8 == 0 && (reinterpret_cast<uintptr_t>(X) & 15) == 0;
   const bool reuse_fwd = (flags & APA_FLAG_WS_FROM_FWD) && fast_bf16;
+  if (tr) {
+    tr->path_bwd = PC_PATH_GENERIC; tr->cat = cat ? 1 : 0; tr->fast = fast_bf16 ? 1 : 0; tr->reuse_fwd = reuse_fwd ? 1 : 0;
+  }
   if (!reuse_fwd) {
     PcPadList pads;
     if (!(flags & APA_FLAG_WEIGHT_IMAGES)) {
@@ -1988,6 +2026,10 @@ int pc_backward(const void* X, const void* Xatt, const float* Wa, const float* W
                        static_cast<bf16_t*>(dT), static_cast<bf16_t*>(dZ), pdbt, pdba, P, K, Kp,
                        act_code(flags), ldw, df);
   APA_LAUNCH_CHECK("pc_bwd_act_kernel");
+  if (tr) {
+    tr->bwd_act = dtype == APA_DTYPE_F32 ? PC_ACT_F32 : PC_ACT_BF16; tr->ps = ps; tr->ldg = dtype == APA_DTYPE_F32 ? Kp : ldw;
+    if (df.row_logits) tr->xent = PC_XENT_BWD_ACT;
+  }
   int rc = APA_OK;
   {  // dWt[c,k] = sum_r Xt[r,c] dT[r,k]
     GemmDesc g;
@@ -2016,6 +2058,7 @@ int pc_backward(const void* X, const void* Xatt, const float* Wa, const float* W
     h.ws = reinterpret_cast<float*>(reinterpret_cast<char*>(gws) + pl.gemm_half);
     if (dtype == APA_DTYPE_BF16) { h.N = Kp; h.n_valid = K; }   // dZ is [R][Kp] with zero pad columns
     g.twin = &h;
+    if (tr) { g.trace = &tr->g_dwt; h.trace = &tr->g_dwa; tr->dw = PC_DW_TWIN_GEMM; tr->dw_drop_a = g.drop_a; }
     rc = gemm_launch(g, st);
     if (rc != APA_OK) return rc;
   }
@@ -2033,6 +2076,7 @@ int pc_backward(const void* X, const void* Xatt, const float* Wa, const float* W
     if (train) {
       g.mid_bits = reinterpret_cast<const uint8_t*>(w + pl.off_bits); g.mid_k = Kp; g.mid_inv_keep = 1.0f / keep_prob;
     }
+    if (tr) { g.trace = &tr->g_dx; tr->dx = PC_DX_WIDE; tr->mid_bits = g.mid_bits ? 1 : 0; tr->wa_to = PC_WA_NONE; }
     rc = gemm_launch(g, st);
     if (rc != APA_OK) return rc;
     dx_done = true;
@@ -2044,6 +2088,7 @@ int pc_backward(const void* X, const void* Xatt, const float* Wa, const float* W
     g.C = dX; g.ldc = C; g.tc = tdt;
     g.M = R; g.N = C; g.K = Kp;
     if (train) set_dropout(g, false, true, keep_prob, seed, offset, flags);
+    if (tr) { g.trace = &tr->g_dx; tr->dx = PC_DX_TWO; tr->dx_drop_c = g.drop_c; }
     rc = gemm_launch(g, st);
     if (rc != APA_OK) return rc;
   }
@@ -2054,6 +2099,7 @@ int pc_backward(const void* X, const void* Xatt, const float* Wa, const float* W
     g.C = fused ? dX : dXatt; g.ldc = fused ? C : Ca; g.tc = tdt;
     g.M = R; g.N = fused ? C : Ca; g.K = Kp; g.beta = fused ? 1.f : 0.f;
     g.stream_out = true;
+    if (tr) { g.trace = &tr->g_dxa; tr->wa_to = fused ? PC_WA_DX_BETA1 : PC_WA_DXATT; }
     rc = gemm_launch(g, st);
     if (rc != APA_OK) return rc;
   }
@@ -2064,6 +2110,7 @@ int pc_backward(const void* X, const void* Xatt, const float* Wa, const float* W
   ColsumMore more;
   const bool mean = xf && xf->done;     // the batch mean of a cross-entropy taken inside this step (xent's own order)
   if (mean) { more.aux_src = xf->loss + 1; more.aux_n = -N; more.aux_scale = xf->lscale; more.aux_dst = xf->loss; }
+  if (tr) { tr->tail = PC_TAIL_COLSUM; tr->tail_nrows = N * ps; tr->rng_bump = bump ? 1 : 0; tr->aux = mean ? 1 : 0; }
   return m1_colsum(pdbt, nullptr, dbt, nullptr, N * ps, 2 * K, 2 * K, bump, st, dba, K, nullptr, 0, 0, 0,
                    mean ? &more : nullptr);
 }

@@ -393,6 +393,48 @@ struct PcFusedWs {
   float* lpart;       // f32 [ceil(R/32)][2][64]: per-block partial rows of sum_p A * T (folded activation pass)
   uint64_t* bits_tag; // which mask `maskbits` holds: {seed, offset, thresh, n8} + the running step's offset (apa_pc_fused.hip)
 };
+// What the per-class maps ran (filled on the host only, as M1Trace / PoseTrace: the product never sets the pointer; the
+// test-only probe library does, around one call, and tests/test_pc_paths_gpu.py reads it back).  0 = not decided by
+// this call.  `phase` says whose fields the apa_pc_fused.hip host functions fill: 1 pc_forward, 2 pc_backward,
+// 3 pc_weight_images.
+enum PcPath { PC_PATH_NONE = 0, PC_PATH_FUSED, PC_PATH_GENERIC };
+enum PcPrep { PC_PREP_NONE = 0, PC_PREP_WEIGHTS, PC_PREP_BITS, PC_PREP_BOTH };
+enum PcLogitsAt { PC_LOGITS_NONE = 0, PC_LOGITS_FINISH, PC_LOGITS_DX, PC_LOGITS_FWD_ACT };
+enum PcXentAt { PC_XENT_NONE = 0, PC_XENT_FWD_ACT, PC_XENT_DX, PC_XENT_BWD_ACT, PC_XENT_OWN };
+enum PcAct { PC_ACT_NONE = 0, PC_ACT_F32, PC_ACT_BF16, PC_ACT_FOLDED };   // element type of pc_fwd_act / pc_bwd_act, or
+                                                                         // folded into the product / dX kernel
+enum PcDx { PC_DX_NONE = 0, PC_DX_FUSED, PC_DX_MID_GEMM, PC_DX_PLAIN_GEMM, PC_DX_WIDE, PC_DX_TWO };
+enum PcWaTo { PC_WA_NONE = 0, PC_WA_DX_BETA1, PC_WA_DXATT };
+enum PcDw { PC_DW_NONE = 0, PC_DW_FUSED, PC_DW_TWIN_GEMM };
+enum PcTailAt { PC_TAIL_NONE = 0, PC_TAIL_DW, PC_TAIL_COLSUM };
+struct PcTrace {
+  int phase;
+  int path_fwd, path_bwd;                               // PcPath
+  int prep_fwd, prep_bwd, prep_wimg;                    // PcPrep: what pc_prep_kernel was launched for
+  int pad_fwd, pad_segs_fwd, pad_drop_fwd;              // pc_pad_kernel launched; its segments; dropout blocks or not
+                                                        // (pc_weight_images, phase 3, records its pad launch here too)
+  int pad_bwd, pad_segs_bwd, pad_drop_bwd;
+  int cat, fast, reuse_fwd;
+  int zt, zt_train, zt_fold, check_tag;                 // pc_fwd_zt_dma_kernel<TRAIN, FOLD> and its tag argument
+  int fwd_act, fwd_act_xe, topdown;                     // PcAct of the forward activation pass; PcXent given; topdown given
+  int logits, xent;                                     // PcLogitsAt, PcXentAt
+  int t_drop_a;                                         // drop_a of the T product (scalar staging)
+  int bwd_act, ps, ldg;                                 // PcAct; pixel splits; row stride of dT / dZ
+  int dx, upb, dx_splits, rbs, mid_bits, dx_drop_c, wa_to;   // PcDx, fused-dx geometry, PcWaTo
+  int dw, dw_S, dw_rows, dw_ctiles, dw_drop_a;          // PcDw, fused-dw geometry; drop_a of the dWt product
+  int tail, tail_nrows, next_bits, rng_bump, aux;       // PcTailAt; partial rows; next step's bits; counter bump; loss mean
+  int wimg_cat, wimg_fused, wimg_maps;                  // pc_weight_images: [Wt | Wa] concatenated; fused images built; maps
+  GemmTrace g_z, g_t, g_dwt, g_dwa, g_dx, g_dxa;        // the gemm_launch calls (g_dx: the wide or the first dX product)
+};
+extern thread_local PcTrace* g_pc_trace;
+inline PcTrace* pc_trace() { return g_pc_trace; }
+// (test-only probe) the carve of pc_plan: out[0..15] = R, Kp, off_wap, off_wtp, off_bap, off_z, off_dt, off_dz, off_pdbt,
+// off_pdba, off_gemm, gemm_half, off_xd, off_bits, off_fused, total
+void pc_plan_offsets(int N, int P, int C, int Ca, int K, int dtype, size_t* out);
+int pc_bwd_act_psplit_host(int N, int kgroups, int P, int act);
+// fused dx / dw geometry as pc_fused_dx / pc_fused_dw pick it: out[0..5] = upb, splits, rbs, S, rows_per_split, ctiles
+void pc_fused_geometry(int R, int C, int* out);
+
 bool pc_fused_supported(int N, int P, int C, int Ca, int K, int dtype, const void* X, const void* Xatt);
 size_t pc_fused_ws_bytes(int N, int P, int C);
 PcFusedWs pc_fused_carve(void* base, int N, int P, int C);

@@ -964,6 +964,10 @@ int pc_fused_prep(const PcFusedWs& f, const float* Wa, const float* Wt, const fl
     extra = (unsigned)(nb < 1 ? 1 : nb);
   }
   const int nwblk = weights ? C / 16 : 0;
+  if (PcTrace* t = pc_trace()) {
+    const int what = weights ? (bits ? PC_PREP_BOTH : PC_PREP_WEIGHTS) : PC_PREP_BITS;
+    (t->phase == 3 ? t->prep_wimg : t->phase == 2 ? t->prep_bwd : t->prep_fwd) = what;
+  }
   hipLaunchKernelGGL(pc_prep_kernel, dim3((unsigned)nwblk + extra), dim3(256), 0, st, Wa, Wt, ba,
                      bt, static_cast<bf16_t*>(f.WcatT), static_cast<bf16_t*>(f.Wcat2), f.bcat, C, K, mb, nwblk);
   APA_LAUNCH_CHECK("pc_prep_kernel");
@@ -971,6 +975,7 @@ int pc_fused_prep(const PcFusedWs& f, const float* Wa, const float* Wt, const fl
 }
 
 int pc_fused_logits_finish(const PcFusedWs& f, float* logits, int N, int P, int K, hipStream_t st) {
+  if (PcTrace* t = pc_trace()) t->logits = PC_LOGITS_FINISH;
   hipLaunchKernelGGL(pc_logits_finish_kernel, dim3(N), dim3(64), 0, st, f.lpart, logits, P, K);
   APA_LAUNCH_CHECK("pc_logits_finish_kernel");
   return APA_OK;
@@ -979,10 +984,7 @@ int pc_fused_logits_finish(const PcFusedWs& f, float* logits, int N, int P, int 
 int pc_fused_forward(const PcFusedWs& f, const void* X, float* Z, float* T, int R, int C, int K, bool train,
                      float keep_prob, uint64_t seed, uint64_t offset, const uint64_t* offset_dev, hipStream_t st,
                      bool prebits, const PcFwdFold* fold, bool check_tag) {
-  if (C % ZB_KT != 0) {     // pc_fused_supported() admits multiples of 256 only
-    set_error("pc_fused_forward: C=%d is not a multiple of %d", C, ZB_KT);
-    return APA_ERR_UNSUPPORTED;
-  }
+  // (C is a multiple of 256, hence of ZB_KT: the only caller, pc_forward, asks pc_fused_supported() first)
   const float ik = train ? 1.0f / keep_prob : 1.0f;
   const bf16_t* xx = static_cast<const bf16_t*>(X);
   const bf16_t* ww = static_cast<const bf16_t*>(f.WcatT);
@@ -1005,6 +1007,10 @@ int pc_fused_forward(const PcFusedWs& f, const void* X, float* Z, float* T, int 
   uint64_t* tag = (train && check_tag) ? f.bits_tag : nullptr;
   PcFoldArgs fo = {nullptr, nullptr, 0, 1};
   if (fold) { fo.att = fold->att; fo.lpart = f.lpart; fo.act = fold->act; fo.P = fold->P; }
+  if (PcTrace* t = pc_trace()) {
+    t->zt = 1; t->zt_train = train ? 1 : 0; t->zt_fold = fold ? 1 : 0; t->check_tag = tag ? 1 : 0;
+    if (fold) t->fwd_act = PC_ACT_FOLDED;
+  }
 #define APA_ZT(TR, FO)                                                                                         \
   hipLaunchKernelGGL((pc_fwd_zt_dma_kernel<TR, FO>), dim3((R + 31) / 32), dim3(512), zb_lds_bytes(C), st, xx, ww, \
                      f.bcat, Z, T, f.maskbits, R, C, K, ik, keep_thresh(keep_prob), seed, offset, offset_dev, fo, tag)
@@ -1020,6 +1026,32 @@ bool pc_fused_dx_supported(int P, int act) {
   return act != 2 && P >= 32;
 }
 int pc_fused_dx_rows(int R) { return (R + DX_ROWS - 1) / DX_ROWS; }
+// channel units (of 32) per block and channel ranges of pc_bwd_dx_kernel
+static void pc_dx_geometry(int R, int C, int* upb, int* nsplits) {
+  const int rbs = pc_fused_dx_rows(R), units = C / 32;
+  int splits = (256 + rbs / 2) / rbs;      // about one block per CU
+  if (splits < (units + DX_MAXU - 1) / DX_MAXU) splits = (units + DX_MAXU - 1) / DX_MAXU;
+  if (splits > units) splits = units;
+  *upb = (units + splits - 1) / splits;
+  *nsplits = (units + *upb - 1) / *upb;
+}
+// row splits of pc_bwd_dw_kernel
+static void pc_dw_geometry(int R, int C, int* nsplits, int* rows, int* nctiles) {
+  const int ctiles = C / 128;
+  int S = (256 + ctiles - 1) / ctiles;            // one block per CU
+  if (S > PC_DW_MAX_SPLITS) S = PC_DW_MAX_SPLITS;
+  int ktiles = (R + FK - 1) / FK;
+  if (S > ktiles) S = ktiles;
+  const int rows_per_split = ((ktiles + S - 1) / S) * FK;
+  *nsplits = (R + rows_per_split - 1) / rows_per_split;
+  *rows = rows_per_split;
+  *nctiles = ctiles;
+}
+void pc_fused_geometry(int R, int C, int* out) {
+  pc_dx_geometry(R, C, &out[0], &out[1]);
+  out[2] = pc_fused_dx_rows(R);
+  pc_dw_geometry(R, C, &out[3], &out[4], &out[5]);
+}
 int pc_fused_dx(const PcFusedWs& f, const float* G, const float* att, const float* Tm, void* dX, float* pd, int R,
                 int C, int K, int P, int act, bool train, float keep_prob, const M1Xent* defer, hipStream_t st) {
   PcDxArgs a;
@@ -1031,12 +1063,13 @@ int pc_fused_dx(const PcFusedWs& f, const float* G, const float* att, const floa
     a.lpart = f.lpart; a.logits = defer->logits;
     a.xe.labels = defer->labels; a.xe.loss = defer->loss; a.xe.G = defer->G; a.xe.gscale = defer->gscale;
   }
-  const int rbs = pc_fused_dx_rows(R), units = C / 32;
-  int splits = (256 + rbs / 2) / rbs;      // about one block per CU
-  if (splits < (units + DX_MAXU - 1) / DX_MAXU) splits = (units + DX_MAXU - 1) / DX_MAXU;
-  if (splits > units) splits = units;
-  a.upb = (units + splits - 1) / splits;
-  splits = (units + a.upb - 1) / a.upb;
+  const int rbs = pc_fused_dx_rows(R);
+  int splits;
+  pc_dx_geometry(R, C, &a.upb, &splits);
+  if (PcTrace* t = pc_trace()) {
+    t->dx = PC_DX_FUSED; t->bwd_act = PC_ACT_FOLDED; t->upb = a.upb; t->dx_splits = splits; t->rbs = rbs;
+    if (defer) { t->logits = PC_LOGITS_DX; t->xent = PC_XENT_DX; }
+  }
 #define APA_DX(TR)                                                                                              \
   do {                                                                                                          \
     static thread_local PerDevice<bool> attr_dev; bool& attr_set = attr_dev.here();                             \
@@ -1058,13 +1091,8 @@ int pc_fused_dw(const PcFusedWs& f, const void* X, float* dWt, float* dWa, int R
                 float keep_prob, hipStream_t st, const PcDwTail* tail) {
   // (a 64-channel form -- 32 channel tiles x 8 row splits, half the fp32 partials -- was built and measured in round
   // 4: 51.9 us against 15.5 us: every block then reads 128-byte pieces of X rows 4 KB apart)
-  const int ctiles = C / 128;
-  int S = (256 + ctiles - 1) / ctiles;            // one block per CU
-  if (S > PC_DW_MAX_SPLITS) S = PC_DW_MAX_SPLITS;
-  int ktiles = (R + FK - 1) / FK;
-  if (S > ktiles) S = ktiles;
-  const int rows_per_split = ((ktiles + S - 1) / S) * FK;
-  S = (R + rows_per_split - 1) / rows_per_split;
+  int ctiles, S, rows_per_split;
+  pc_dw_geometry(R, C, &S, &rows_per_split, &ctiles);
   const bf16_t* x = static_cast<const bf16_t*>(X);
   const bf16_t* g = static_cast<const bf16_t*>(f.dTdZ);
   const size_t shm = (size_t)2 * (train ? 3 : 2) * FK * 128 * sizeof(short);
@@ -1101,6 +1129,13 @@ int pc_fused_dw(const PcFusedWs& f, const void* X, float* dWt, float* dWa, int R
     }
   }
   tl.ntail = ntail;
+  if (PcTrace* t = pc_trace()) {
+    t->dw = PC_DW_FUSED; t->dw_S = S; t->dw_rows = rows_per_split; t->dw_ctiles = ctiles;
+    if (tail) {
+      t->tail = PC_TAIL_DW; t->tail_nrows = tail->nrows; t->next_bits = nnext > 0 ? 1 : 0;
+      t->rng_bump = tail->rng_bump ? 1 : 0; t->aux = tail->aux_dst ? 1 : 0;
+    }
+  }
   hipLaunchKernelGGL(pc_dw_reduce_kernel, dim3((unsigned)(nmain + ntail + nnext)), dim3(1024), 0, st, f.partial, dWt,
                      dWa, C, K, S, train ? 1.0f / keep_prob : 1.0f, nmain, tl);
   APA_LAUNCH_CHECK("pc_dw_reduce_kernel");

@@ -150,13 +150,18 @@ def softmax_p(z):
     return Bnd(A, A * (2 * ez + C_ACC * (P + 16) * EPS32))
 
 
+def tolerance(b, bf16=False):
+    """the elementwise tolerance `check` asserts: err (+ 2^-8 |ref| for a bf16 output)."""
+    return b.err + (U_BF16 * b.ref.abs() if bf16 else 0.0)
+
+
 def check(got, b, what, *, bf16=False, ambiguous=None, zero_ref=False):
     """|got - ref| <= err (+ 2^-8 |ref| for a bf16 output) elementwise; got finite; the bound below 1 % of
     max |ref| over the elements whose relu gate is certain."""
     got = got.double().reshape(b.ref.shape)
     assert torch.isfinite(got).all(), '{}: non-finite output ({} elements)'.format(
         what, int((~torch.isfinite(got)).sum()))
-    tol = b.err + (U_BF16 * b.ref.abs() if bf16 else 0.0)
+    tol = tolerance(b, bf16)
     bad = (got - b.ref).abs() > tol
     n = int(bad.sum())
     if n:

@@ -278,3 +278,227 @@ def test_pose_head_launches_no_instance_outside_the_case_table():
     assert 'default: APA_PL(32)' in part_a
     assert re.findall(r'APA_DPPRE\((float|bf16_t), (16|32)\)', part_a) == [
         ('float', '16'), ('float', '32'), ('bf16_t', '16'), ('bf16_t', '32')]
+
+
+# ------------------------------------------------------------------------------------------ per-class maps dispatch trace
+def test_pc_probe_symbols_and_plan():
+    from tests import _pc_probe as pc
+    lib = pc.load_pc_probe()           # asserts the trace struct size
+    assert lib.apa_probe_pc_trace_size() == ctypes.sizeof(pc.PcTrace) == 4 * (len(pc._INTS) + 6 * len(pc.GEMMS))
+    for name in pc.PC_SYMBOLS:
+        assert hasattr(lib, name), name
+    prod = cof.load_library()
+    for name in pc.PC_SYMBOLS:
+        assert not hasattr(prod, name), 'libapa_hip.so exports ' + name
+    # the carve of the HMDB-51 shape, by hand: Kp = 64; padded Wa, Wt (fp32-sized slots), ba, Z [R][64] f32, dT, dZ
+    # [R][64] bf16; then the fused part: WcatT, Wcat2 (128 x 2048 bf16 each), bcat (128 f32), [dT | dZ] [R][128] bf16,
+    # 32 dW split partials [2048][128] f32, one keep bit per feature element, two partial rows of 64 per 32-row block,
+    # and the 256-byte tag; the total is what the product reports
+    N, P, C, K = 32, 196, 2048, 51
+    R = N * P
+    pl = pc.plan(N, P, C, C, K, cof.APA_DTYPE_BF16)
+    assert (pl['R'], pl['Kp'], pl['off_wap']) == (R, 64, 0)
+    assert pl['off_wtp'] == C * 64 * 4 and pl['off_bap'] == 2 * C * 64 * 4 and pl['off_z'] == pl['off_bap'] + 256
+    assert pl['off_dt'] - pl['off_z'] == R * 64 * 4 and pl['off_dz'] - pl['off_dt'] == R * 64 * 2
+    assert pl['off_pdbt'] - pl['off_dz'] == R * 64 * 2 and pl['off_pdba'] - pl['off_pdbt'] == K * 4
+    assert pl['off_bits'] - pl['off_xd'] == R * C * 2
+    assert pl['WcatT'] == pl['off_fused'] and pl['Wcat2'] - pl['WcatT'] == 128 * C * 2
+    assert pl['bcat'] - pl['Wcat2'] == C * 128 * 2 and pl['dTdZ'] - pl['bcat'] == 512
+    assert pl['partial'] - pl['dTdZ'] == R * 128 * 2 and pl['maskbits'] - pl['partial'] == 32 * C * 128 * 4
+    assert pl['lpart'] - pl['maskbits'] == R * C // 8 and pl['bits_tag'] - pl['lpart'] == (R // 32) * 2 * 64 * 4
+    assert pl['fused_end'] - pl['bits_tag'] == 256 and pl['fused_end'] == pl['total']
+    assert all(pl[k] % 256 == 0 for k in pc.PLAN_FIELDS[2:] if k not in ('off_pdba',))
+    assert pl['total'] == prod.apa_attn_pool_workspace_bytes(N, P, C, C, K, K, 0)
+    # 64 channel units in 5 ranges of 13, 13, 13, 13, 12; 49 row blocks; 16 channel tiles x 14 row splits of 448 rows
+    assert pc.geometry(R, C) == dict(upb=13, dx_splits=5, rbs=49, dw_S=14, dw_rows=448, dw_ctiles=16)
+    assert pc.support(N, P, C, C, 64, cof.APA_DTYPE_BF16, 0) == (True, True)
+    assert pc.support(N, P, C, C, 65, cof.APA_DTYPE_BF16, 0)[0] is False
+    assert pc.support(N, 25, C, C, K, cof.APA_DTYPE_BF16, 0) == (True, False)
+    assert pc.support(N, P, C, C, K, cof.APA_DTYPE_BF16, 2) == (True, False)
+    assert pc.support(N, P, 8448, 8448, K, cof.APA_DTYPE_BF16, 0)[0] is False
+    assert pc.support(N, P, C, C, K, cof.APA_DTYPE_F32, 0)[0] is False
+
+
+def _pc_reached():
+    from tests import test_pc_paths_gpu as t
+    reached = set()
+    for c in t.CASES + t.MIS_CASES:
+        e = t.expected(c)
+        lit = dict(c['expect'])
+        if 'topdown_t' in lit:
+            lit['topdown'] = lit.pop('topdown_t')
+        for k, v in lit.items():
+            assert e.get(k, v) == v, (c['name'], k, v, e.get(k))
+        e.update(lit)
+        N, P, C, K, R = c['N'], c['P'], c['C'], c['K'], c['N'] * c['P']
+        fused = e['path_fwd'] == 'fused'
+        train = bool(c['train'] and c['entry'] != 'eval')
+        reached.add(('path', e['path_fwd'], c['dt']))
+        reached.add(('entry', e['path_fwd'], c['entry'], train))
+        reached.add(('act', e['path_fwd'], c['dt'], c['act']))
+        reached.add(('rng', e['path_fwd'], c['rng'], train))
+        reached.add(('wimg', e['path_fwd'], c['wimg'], train, c['entry']))
+        reached.add(('keep', c['keep'], train))
+        for k in ('logits', 'xent', 'fwd_act', 'bwd_act', 'dx', 'dw', 'tail', 'wa_to'):
+            if k in e:
+                reached.add((k, e['path_fwd'], e[k]))
+        if c['topdown']:
+            reached.add(('topdown', e['path_fwd'], c['dt']))
+        if c['Ca'] is not None:
+            reached.add(('xatt', c['dt'], 'same_width' if c['Ca'] == C else 'other_width', train))
+        for m, off in c['mis'].items():
+            reached.add(('misaligned', m, off, e['path_fwd'], e.get('dx')))
+        if fused:
+            reached.add(('fused_K', K))
+            reached.add(('fused_C', C))
+            reached.add(('fused_P', P))
+            reached.add(('zt', e['zt_train'], e['zt_fold']))
+            reached.add(('prep_fwd', e['prep_fwd']))
+            if 'prep_bwd' in e:
+                reached.add(('prep_bwd', e['prep_bwd']))
+            reached.add(('tag', c['pre'], c['rng']))
+            if 'next_bits' in e:
+                reached.add(('next_bits', e['next_bits'], e['dx']))
+            if R % 32 and R % 128:
+                reached.add(('fused_ragged',))
+            if R < 32:
+                reached.add(('fused_R_lt_32',))
+            if R < 64:
+                reached.add(('fused_R_lt_64',))
+            for k in ('upb', 'dx_splits', 'dw_S'):
+                if k in lit:
+                    reached.add((k, lit[k]))
+            if e.get('dx') == 'fused':
+                reached.add(('dx_train', train))
+                reached.add(('dx_xent', e['xent'] == 'dx'))
+                if (R + 127) // 128 >= 2 and P == 33:
+                    reached.add(('dx_block_of_5_images',))
+            if 'dw' in e:
+                reached.add(('dw_train', train))
+            if e.get('tail') == 'dw_tail':
+                reached.add(('dw_tail', e['rng_bump'], e['aux'], e['next_bits']))
+        else:
+            reached.add(('generic_K', c['dt'], K))
+            reached.add(('generic', c['dt'], e['cat'], e['fast'], train))
+            reached.add(('pad_fwd', e['pad_segs_fwd'], e['pad_drop_fwd']))
+            reached.add(('t_drop_a', e['t_drop_a']))
+            if 'pad_segs_bwd' in e:
+                reached.add(('pad_bwd', e['pad_segs_bwd'], e['pad_drop_bwd']))
+                reached.add(('reuse_fwd', e['reuse_fwd']))
+                reached.add(('dw_drop_a', e['dw_drop_a']))
+                reached.add(('dx_form', e['dx'], e.get('mid_bits'), e.get('dx_drop_c'), e.get('wa_to')))
+                reached.add(('colsum', e['rng_bump'], e['aux']))
+            if 'ps' in lit:
+                reached.add(('ps', lit['ps']))
+            if c['wide'] is not None:
+                reached.add(('wide', c['wide'], e['dx']))
+            if C % 8:
+                reached.add(('generic_C_mod_8', c['dt']))
+            if (N, P, C) == (32, 196, 2048):
+                reached.add(('shipped', K, c['entry']))
+            if K <= 64 and c['dt'] == cof.APA_DTYPE_BF16:
+                reached.add(('neighbour', 'c8448' if C > 8192 else 'c_mod_256' if C % 256 else 'xatt' if
+                             c['Ca'] == C else 'ca' if c['Ca'] is not None else 'x_misaligned' if c['mis'].get('X')
+                             else 'rng_external' if c['rng'] == 'external' else '?'))
+            if K == 65 and C % 256 == 0 and c['Ca'] is None and not c['mis']:
+                reached.add(('neighbour', 'k65'))
+        if (N, P, C, K) == (32, 196, 2048, 51):
+            reached.add(('shipped', K, c['entry']))
+    return reached, t
+
+
+def test_pc_gpu_case_table_covers_every_reachable_trace_value():
+    F32, BF16 = cof.APA_DTYPE_F32, cof.APA_DTYPE_BF16
+    reached, t = _pc_reached()
+    need = {('path', 'fused', BF16), ('path', 'generic', BF16), ('path', 'generic', F32)}
+    need |= {('entry', p, en, tr) for p in ('fused', 'generic') for en, tr in
+             (('sep', False), ('sep', True), ('step', False), ('step', True), ('eval', False))}
+    need |= {('act', 'fused', BF16, a) for a in ('id', 'relu', 'softmax')}
+    need |= {('act', 'generic', dt, a) for dt in (F32, BF16) for a in ('id', 'relu', 'softmax')}
+    need |= {('rng', 'fused', 'value', True), ('rng', 'fused', 'device', True), ('rng', 'generic', 'device', True),
+             ('rng', 'generic', 'external', True)}
+    need |= {('wimg', 'fused', True, False, 'sep'), ('wimg', 'fused', True, True, 'sep'),
+             ('wimg', 'fused', True, True, 'step'), ('wimg', 'generic', True, True, 'sep'),
+             ('wimg', 'generic', True, False, 'sep')}
+    need |= {('keep', 0.5, True), ('keep', 0.7, True)}
+    # fused path: the shapes and edges
+    need |= {('fused_K', k) for k in (2, 3, 4, 21, 51, 63, 64)}   # (K = 1 has M == 1: the M == 1 path serves it)
+    need |= {('fused_C', ch) for ch in (256, 768, 2048, 4096, 8192)}
+    need |= {('fused_P', p) for p in (25, 32, 33, 36, 49, 196, 225)}
+    need |= {('fused_ragged',), ('fused_R_lt_32',), ('fused_R_lt_64',), ('dx_block_of_5_images',)}
+    need |= {('upb', 1), ('upb', 13), ('upb', 16), ('dx_splits', 5), ('dw_S', 1)}
+    # every launched instance: pc_fwd_zt_dma_kernel<TRAIN, FOLD>, pc_bwd_dx_kernel<TRAIN>, pc_bwd_dw_kernel<TRAIN>
+    need |= {('zt', tr, fo) for tr in (0, 1) for fo in (0, 1)}
+    need |= {('dx_train', tr) for tr in (False, True)} | {('dw_train', tr) for tr in (False, True)}
+    need |= {('dx_xent', x) for x in (False, True)}
+    need |= {('prep_fwd', p) for p in ('none', 'weights', 'bits', 'both')}
+    need |= {('prep_bwd', p) for p in ('none', 'weights', 'bits', 'both')}
+    need |= {('tag', p, 'value') for p in ('fresh', 'believed', 'jump', 'foreign')} | {('tag', 'believed', 'device')}
+    need |= {('next_bits', 1, 'fused'), ('next_bits', 1, 'mid_gemm'), ('next_bits', 0, 'fused')}
+    need |= {('logits', 'fused', v) for v in ('finish', 'dx', 'fwd_act')}
+    need |= {('xent', 'fused', v) for v in ('none', 'fwd_act', 'dx', 'own')}
+    need |= {('fwd_act', 'fused', v) for v in ('folded', 'bf16')} | {('bwd_act', 'fused', v) for v in ('folded', 'bf16')}
+    need |= {('dx', 'fused', v) for v in ('fused', 'mid_gemm', 'plain_gemm')}
+    # the three kinds of tail block of pc_dw_reduce_kernel: column sums (+ counter bump, + loss mean), next step's bits
+    need |= {('dw_tail', 0, 0, 0), ('dw_tail', 1, 0, 0), ('dw_tail', 0, 1, 0), ('dw_tail', 0, 1, 1), ('dw_tail', 1, 1, 1)}
+    need |= {('topdown', 'fused', BF16), ('topdown', 'generic', F32)}
+    # neighbours of the fused path
+    need |= {('neighbour', w) for w in ('k65', 'c8448', 'c_mod_256', 'xatt', 'ca', 'x_misaligned', 'rng_external')}
+    # generic path
+    need |= {('generic_K', BF16, k) for k in (2, 65, 130, 393, 1000, 1024, 1025)}
+    need |= {('generic_K', F32, k) for k in (2, 51, 65, 393, 1025)}
+    need |= {('generic', BF16, 1, 1, tr) for tr in (False, True)} | {('generic', BF16, 0, 1, tr) for tr in (False, True)}
+    need |= {('generic', BF16, 0, 0, True), ('generic', F32, 0, 0, False), ('generic', F32, 0, 0, True)}
+    need |= {('pad_fwd', 3, 1), ('pad_fwd', 3, 0), ('pad_fwd', 2, 0), ('pad_fwd', 0, 1), ('pad_fwd', 0, 0)}
+    need |= {('pad_bwd', 2, 1), ('pad_bwd', 2, 0), ('pad_bwd', 0, 1), ('pad_bwd', 0, 0)}
+    need |= {('reuse_fwd', 0), ('reuse_fwd', 1), ('t_drop_a', 0), ('t_drop_a', 1), ('dw_drop_a', 0), ('dw_drop_a', 2)}
+    need |= {('dx_form', 'wide', 1, None, None), ('dx_form', 'two', None, 0, 'dx_beta1'),
+             ('dx_form', 'two', None, 1, 'dx_beta1'), ('dx_form', 'two', None, 0, 'dxatt'),
+             ('dx_form', 'two', None, 1, 'dxatt')}
+    need |= {('wide', True, 'wide'), ('wide', True, 'two'), ('wide', False, 'two')}
+    need |= {('xent', 'generic', v) for v in ('none', 'bwd_act', 'own')}
+    need |= {('fwd_act', 'generic', v) for v in ('f32', 'bf16')} | {('bwd_act', 'generic', v) for v in ('f32', 'bf16')}
+    need |= {('colsum', 0, 0), ('colsum', 1, 0), ('colsum', 0, 1)}
+    need |= {('ps', 1), ('ps', 2), ('ps', 8)}
+    need |= {('xatt', BF16, 'same_width', True), ('xatt', BF16, 'other_width', False),
+             ('xatt', BF16, 'other_width', True), ('xatt', F32, 'other_width', True)}
+    need |= {('generic_C_mod_8', BF16)}
+    need |= {('misaligned', 'X', 1, 'generic', 'two'), ('misaligned', 'dX', 4, 'generic', 'two')}
+    need |= {('shipped', 51, 'step'), ('shipped', 51, 'eval'), ('shipped', 393, 'step'), ('shipped', 393, 'sep')}
+    missing = need - reached
+    assert not missing, sorted(missing, key=str)
+    names = [c['name'] for c in t.CASES + t.MIS_CASES]
+    assert len(names) == len(set(names))
+
+
+def test_per_class_launches_no_instance_outside_the_case_table():
+    """Part B of apa_dense.hip and apa_pc_fused.hip launch pc_fwd_zt_dma_kernel<TRAIN, FOLD> (four arms),
+    pc_bwd_dx_kernel<TRAIN>, pc_bwd_dw_kernel<TRAIN>, pc_fwd_act_kernel / pc_bwd_act_kernel for float and bf16_t, and the
+    untemplated pc_prep / pc_pad / pc_logits_finish / pc_dw_reduce kernels -- each arm is a `need` entry of the coverage
+    test above.  pc_fused_forward's own `C % ZB_KT` refusal had no caller behind pc_fused_supported (C % 256 == 0) and
+    is gone.  The general (non-"small form") arm of pc_fill_bits / the forward kernel's slow arm stays: its callers are
+    the maps of more than 2^33 elements (a 16 GB bf16 feature map: R > 2^20 rows at C = 8192), which the device
+    holds but no test allocates."""
+    import re
+    here = os.path.join(os.path.dirname(cof.LIB_PATH), '..', 'csrc')
+    fused = open(os.path.join(here, 'apa_pc_fused.hip')).read()
+    dense = open(os.path.join(here, 'apa_dense.hip')).read()
+    part_b = dense[dense.index('// B. Per-class bottom-up maps'):]
+    assert re.findall(r'APA_ZT\((true|false), (true|false)\);', fused) == [
+        ('true', 'true'), ('false', 'true'), ('true', 'false'), ('false', 'false')]
+    assert re.findall(r'APA_DX\((true|false)\);', fused) == ['true', 'false']
+    assert re.findall(r'APA_DW\((true|false)\);', fused) == ['true', 'false']
+    assert 'C % ZB_KT != 0' not in fused
+    assert sorted(re.findall(r'hipLaunchKernelGGL\(\(?(pc_\w+)', fused)) == sorted(
+        ['pc_prep_kernel', 'pc_logits_finish_kernel', 'pc_fwd_zt_dma_kernel', 'pc_bwd_dx_kernel', 'pc_bwd_dw_kernel',
+         'pc_dw_reduce_kernel'])
+    launches = re.findall(r'hipLaunchKernelGGL\(\(?(pc_\w+?)(?:<(\w+)>)?[,)]', part_b)
+    assert sorted(launches) == sorted(
+        [('pc_pad_kernel', ''), ('pc_fwd_act_kernel', 'bf16_t'), ('pc_fwd_act_kernel', 'float'),
+         ('pc_fwd_act_kernel', 'bf16_t'), ('pc_bwd_act_kernel', 'bf16_t'), ('pc_bwd_act_kernel', 'float'),
+         ('pc_bwd_act_kernel', 'bf16_t')]), launches
+    # the table reaches both element types of both activation kernels, on both paths where they exist
+    reached, _ = _pc_reached()
+    for need in (('fwd_act', 'fused', 'bf16'), ('fwd_act', 'generic', 'bf16'), ('fwd_act', 'generic', 'f32'),
+                 ('bwd_act', 'fused', 'bf16'), ('bwd_act', 'generic', 'bf16'), ('bwd_act', 'generic', 'f32')):
+        assert need in reached, need
