@@ -5,6 +5,8 @@
 #include <math.h>
 #include <stdint.h>
 
+#include "apa_colsum.h"
+
 namespace apa {
 
 struct bf16_t { uint16_t v; };
@@ -249,19 +251,14 @@ __device__ __forceinline__ int half_min_first(int v, int lane) {
 // ---------------------------------------------------------------------------------------------
 // Fixed-order column sums of a matrix of per-block partial rows (apa_m1_small.hip: m1_colsum_kernel)
 // ---------------------------------------------------------------------------------------------
-struct ColsumExtra {
-  float* dwa4 = nullptr; int C3 = 0;
-  float* dwa5 = nullptr; int C4 = 0;
-  const float* aux_src = nullptr; int aux_n = 0; float aux_scale = 0.f; float* aux_dst = nullptr;
-};
-// One 1024-thread block of the fixed-order column sum (the body of m1_colsum_kernel; also run by the tail blocks of
-// pc_dw_reduce_kernel, so that both give bit-identical sums): block `bid` of `nbid` owns columns 32 bid .. 32 bid + 31.
-__device__ __forceinline__ void colsum_block(int bid, int nbid, const float* __restrict__ pdwa,
-                                             const float* __restrict__ pdba, float* __restrict__ dwa,
-                                             float* __restrict__ dba, int nblk, int C, int ld,
-                                             uint64_t* __restrict__ rng_bump, float* __restrict__ dwa2, int C1,
-                                             float* __restrict__ dwa3, int C2, int perm_nthr, int perm_cp,
-                                             const ColsumExtra& x) {
+// One 1024-thread block of the fixed-order column sum described by ColsumArgs (apa_colsum.h): the body of
+// m1_colsum_kernel, also run by the tail blocks of gemm_splitk_reduce_tail_kernel and pc_dw_reduce_kernel, so that all
+// three give bit-identical sums.  Block `bid` of `nbid` owns columns 32 bid .. 32 bid + 31.
+__device__ __forceinline__ void colsum_block(int bid, int nbid, const ColsumArgs& x) {
+  const float* __restrict__ pdwa = x.pdwa; const float* __restrict__ pdba = x.pdba;
+  float* __restrict__ dwa = x.dwa; float* __restrict__ dwa2 = x.dwa2; float* __restrict__ dwa3 = x.dwa3;
+  float* __restrict__ dba = x.dba; uint64_t* __restrict__ rng_bump = x.rng_bump;
+  const int nblk = x.nblk, C = x.C, ld = x.ld, C1 = x.C1, C2 = x.C2, perm_nthr = x.perm_nthr, perm_cp = x.perm_cp;
   // perm_nthr > 0: the first section holds the pose head's dW2 partials in the permuted order of
   // pose_bwd_rows_kernel (float4 v of thread t at float4 index v * nthr + t; v = 4 (column & 1) + q / 4)
   __shared__ float red[32][33];

@@ -23,7 +23,7 @@ struct ProbeGemm {
   int64_t stream_out;
 };
 
-struct ProbeColsum {               // every m1_colsum argument GemmDesc::tail carries (perm_* excepted)
+struct ProbeColsum {               // the ColsumArgs fields GemmDesc::tail carries (pdba / dba / perm_* excepted)
   const float* pdwa; float* dwa; int64_t nblk, C, ld;
   float* dwa2; int64_t C1; float* dwa3; int64_t C2; float* dwa4; int64_t C3; float* dwa5; int64_t C4;
   const float* aux_src; int64_t aux_n; double aux_scale; float* aux_dst;
@@ -47,6 +47,16 @@ apa::GemmDesc to_desc(const ProbeGemm& p) {
   d.mid_bits = p.mid_bits; d.mid_k = (int)p.mid_k; d.mid_inv_keep = (float)p.mid_inv_keep;
   d.stream_out = p.stream_out != 0;
   return d;
+}
+
+apa::ColsumArgs to_colsum(const ProbeColsum& c) {
+  apa::ColsumArgs a;
+  a.pdwa = c.pdwa; a.dwa = c.dwa; a.nblk = (int)c.nblk; a.C = (int)c.C; a.ld = (int)c.ld;
+  a.dwa2 = c.dwa2; a.C1 = (int)c.C1; a.dwa3 = c.dwa3; a.C2 = (int)c.C2;
+  a.dwa4 = c.dwa4; a.C3 = (int)c.C3; a.dwa5 = c.dwa5; a.C4 = (int)c.C4;
+  a.aux_src = c.aux_src; a.aux_n = (int)c.aux_n; a.aux_scale = (float)c.aux_scale; a.aux_dst = c.aux_dst;
+  a.rng_bump = c.rng_bump;
+  return a;
 }
 
 void to_trace(const apa::GemmTrace& t, ProbeTrace* o) {
@@ -76,14 +86,7 @@ int apa_probe_gemm_launch(const ProbeGemm* p, const ProbeGemm* twin, const Probe
   apa::GemmDesc d = to_desc(*p), t;
   if (twin) { t = to_desc(*twin); t.trace = &ttr; d.twin = &t; }
   apa::ColsumJob job;
-  if (tail) {
-    job.pdwa = tail->pdwa; job.dwa = tail->dwa; job.nblk = (int)tail->nblk; job.C = (int)tail->C;
-    job.ld = (int)tail->ld; job.dwa2 = tail->dwa2; job.C1 = (int)tail->C1; job.dwa3 = tail->dwa3;
-    job.C2 = (int)tail->C2; job.dwa4 = tail->dwa4; job.C3 = (int)tail->C3; job.dwa5 = tail->dwa5;
-    job.C4 = (int)tail->C4; job.aux_src = tail->aux_src; job.aux_n = (int)tail->aux_n;
-    job.aux_scale = (float)tail->aux_scale; job.aux_dst = tail->aux_dst; job.rng_bump = tail->rng_bump;
-    d.tail = &job;
-  }
+  if (tail) { job.a = to_colsum(*tail); d.tail = &job; }
   d.trace = &tr;
   const int rc = apa::gemm_launch(d, static_cast<hipStream_t>(stream));
   to_trace(tr, trace);
@@ -94,12 +97,7 @@ int apa_probe_gemm_launch(const ProbeGemm* p, const ProbeGemm* twin, const Probe
 
 int apa_probe_m1_colsum(const ProbeColsum* c, void* stream) {
   if (!c) { apa::set_error("apa_probe_m1_colsum: null"); return APA_ERR_INVALID_ARG; }
-  apa::ColsumMore more;   // (the same argument mapping as the product's own fall-back launch, apa_dense.hip)
-  more.dwa4 = c->dwa4; more.C3 = (int)c->C3; more.dwa5 = c->dwa5; more.C4 = (int)c->C4;
-  more.aux_src = c->aux_src; more.aux_n = (int)c->aux_n; more.aux_scale = (float)c->aux_scale;
-  more.aux_dst = c->aux_dst;
-  return apa::m1_colsum(c->pdwa, nullptr, c->dwa, nullptr, (int)c->nblk, (int)c->C, (int)c->ld, c->rng_bump,
-                        static_cast<hipStream_t>(stream), c->dwa2, (int)c->C1, c->dwa3, (int)c->C2, 0, 0, &more);
+  return apa::m1_colsum(to_colsum(*c), static_cast<hipStream_t>(stream));
 }
 
 int apa_probe_sgemm_small(const float* A, int64_t a_si, int64_t a_sk, const float* B, int64_t b_sk, int64_t b_sj,

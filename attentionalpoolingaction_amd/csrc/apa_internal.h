@@ -7,6 +7,7 @@
 #include <stdlib.h>
 
 #include "../../include/apa.h"
+#include "apa_colsum.h"
 
 namespace apa {
 
@@ -66,6 +67,9 @@ inline void launch_ev(void (*kernel)(KArgs...), dim3 grid, dim3 block, size_t sh
 }
 
 inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
+// element type of a feature map as the GEMM descriptors (0 f32, 1 bf16) and the workspace carves (bytes) take it
+inline int dt_code(int dtype) { return dtype == APA_DTYPE_BF16 ? 1 : 0; }
+inline size_t dt_size(int dtype) { return dtype == APA_DTYPE_BF16 ? 2 : 4; }
 
 // splitmix64-derived 2x32-bit dropout key (shared by fwd, bwd and apa_dropout_mask).
 inline void rng_key(uint64_t seed, uint64_t offset, uint32_t* k0, uint32_t* k1) {
@@ -106,7 +110,7 @@ inline RngKeyArgs rng_resolve(unsigned flags, float keep_prob, uint64_t seed, ui
 }
 
 // ------------------------------------------------------------------------------------------
-// Small fp32 GEMM on the f32 MFMA (exact fp32 FMA chain, deterministic):
+// apa_gemm_small.hip: small fp32 GEMM on the f32 MFMA (exact fp32 FMA chain, deterministic):
 //   D[i][j] = sum_k A(i,k) * B(k,j) (+ rank-1 term u[i]*v[j]),  i < m, j < n, k < kdim
 //   A(i,k) = A[i*a_si + k*a_sk],  B(k,j) = B[k*b_sk + j*b_sj],  D[i*ldd + j]
 // splits > 1 runs split-K into `ws` ([splits][m][n] floats) followed by a fixed-order reduce.
@@ -121,15 +125,12 @@ int sgemm_small(const float* A, long a_si, long a_sk, const float* B, long b_sk,
 //   a_kc: A stored [M][K] (k contiguous) else [K][M];  b_kc: B stored [N][K] else [K][N].
 //   ta/tb/tc: 0 = f32, 1 = bf16.  f32 x f32 runs on the exact f32 MFMA, anything else on bf16 MFMA.
 // ------------------------------------------------------------------------------------------
-// A fixed-order column sum (m1_colsum's arguments) that may ride on the tail blocks of a split-K reduce launch
-// (GemmDesc::tail, round 6): the reduce is memory-bound on its partial tiles, the column sum is a handful of blocks
+// The fixed-order column sum (ColsumArgs, apa_colsum.h) as a job that may ride on the tail blocks of a split-K reduce
+// launch (GemmDesc::tail, round 6): the reduce is memory-bound on its partial tiles, the column sum is a handful of blocks
 // that nothing behind the product waits for -- as a launch of its own it cost 4.9 us of the cfg 003 step.  `done` is
-// set by gemm_launch when the job was taken; otherwise the caller launches m1_colsum itself.
+// set by gemm_launch when the job was taken; otherwise the caller launches m1_colsum(a) itself.
 struct ColsumJob {
-  const float* pdwa = nullptr; float* dwa = nullptr; int nblk = 0, C = 0, ld = 0; uint64_t* rng_bump = nullptr;
-  float* dwa2 = nullptr; int C1 = 0; float* dwa3 = nullptr; int C2 = 0; int perm_nthr = 0, perm_cp = 0;
-  float* dwa4 = nullptr; int C3 = 0; float* dwa5 = nullptr; int C4 = 0;
-  const float* aux_src = nullptr; int aux_n = 0; float aux_scale = 0.f; float* aux_dst = nullptr;
+  ColsumArgs a;
   bool done = false;
 };
 // What gemm_launch actually ran (GemmDesc::trace: filled on the host only, read by the kernel-level tests).
@@ -179,8 +180,6 @@ struct GemmDesc {
   // optional: where to record the kernel kind / split / reduce that served this product (null at product call sites)
   GemmTrace* trace = nullptr;
 };
-bool gemm_bf16_wide_serves(int M, int N, int K);   // would this all-bf16, k-contiguous, unsplit product take the wide kernel?
-int gemm_bf16_wide_tile_rows(int M, int N, int K);  // ... and with how many rows per tile (0 = not served)
 size_t gemm_ws_bytes(int M, int N, int splits);
 int gemm_pick_splits(int M, int N, int K);
 int gemm_launch(const GemmDesc& d, hipStream_t st);
@@ -188,6 +187,11 @@ int gemm_launch(const GemmDesc& d, hipStream_t st);
 bool gemm_bf16_eligible(const GemmDesc& d);
 int gemm_bf16_launch(const GemmDesc& d, int splits, int k_per_split, hipStream_t st);
 bool gemm_bf16_twin_ok(const GemmDesc& d, int splits, int k_per_split);   // can d and d.twin share one launch?
+bool gemm_bf16_wide_serves(int M, int N, int K);   // would this all-bf16, k-contiguous, unsplit product take the wide kernel?
+int gemm_bf16_wide_tile_rows(int M, int N, int K);  // ... and with how many rows per tile (0 = not served)
+// apa_gemm_bf16.hip: C = (A[:, :64] . B[:, :64]^T) * mask/keep + A[:, 64:] . B[:, 64:]^T  (all bf16, k contiguous)
+int gemm_bf16_mid_dropout(const void* A, long lda, const void* B, long ldb, void* C, long ldc, int M, int N,
+                          int K, float inv_keep, const uint8_t* maskbits, hipStream_t st);
 
 // ------------------------------------------------------------------------------------------
 // M == 1 factorised path (apa_m1.hip)
@@ -279,13 +283,6 @@ struct M1Rng {
   const uint8_t* maskbits_in = nullptr;      // backward: the forward call's keep-bits, or nullptr (hash again)
   bool no_dx = false;                        // backward, Xatt != X, keep-bits form: skip the dX stores (APA_IFLAG_NO_DX)
 };
-// apa_m1_cat.hip
-bool m1_cat_supported(int J);
-int m1_cat_forward(const CatFeat& cat, const float* att, const float* Wt, float* logits, int N, int P,
-                   int C, int K, bool train, const M1Rng& r, hipStream_t st);
-int m1_cat_backward(const CatFeat& cat, const float* att, const float* G, const float* Wt, float* dWt,
-                    float* e_out, int N, int P, int C, int K, bool softmax, bool train, const M1Rng& r,
-                    hipStream_t st);
 bool m1s_supported(int C, int dtype);
 int m1s_launch_pool_fwd(int dtype, int C, bool fused, bool train, int nblk, hipStream_t st,
                         const void* X, const float* Wa, const float* ba, float* att, float* pacc,
@@ -295,6 +292,14 @@ int m1s_launch_bwd_main(int dtype, int C, bool fused, bool train, int nblk, hipS
                         const float* zsave, const float* abar, const float* G, const float* bt,
                         const float* sn_pre, void* dX, float* dZout, float* pdwa, float* pdba,
                         int P, int S, int K, int act, const M1Rng& r, const float* dA_extra);
+
+// apa_m1_cat.hip: the J extra top-down channels of CatFeat
+bool m1_cat_supported(int J);
+int m1_cat_forward(const CatFeat& cat, const float* att, const float* Wt, float* logits, int N, int P,
+                   int C, int K, bool train, const M1Rng& r, hipStream_t st);
+int m1_cat_backward(const CatFeat& cat, const float* att, const float* G, const float* Wt, float* dWt,
+                    float* e_out, int N, int P, int C, int K, bool softmax, bool train, const M1Rng& r,
+                    hipStream_t st);
 
 // apa_m1_generic.hip: the same two passes for any C (run-time channel loop, LDS accumulators)
 bool m1g_supported(int C, int dtype);
@@ -324,9 +329,10 @@ bool m1_logits_xent_supported(int N, int C, int K, bool eval);
 int m1_logits2_xent(const float* z, const float* Wt, const float* abar, const float* bt,
                     const int64_t* labels, float* logits, float* loss, float* G, float gscale,
                     float* probs, int64_t* pred, float* part_ws, int N, int C, int K, hipStream_t st);
-// dwa2 != nullptr: columns [C1, C2) of the partial matrix are summed into dwa2, dwa3 != nullptr: columns
-// [C2, C) into dwa3 (one launch, up to three outputs)
-// apa_dense.hip: the pose-head halves of the one-call cfg 003 step (apa_pose_attn_train_step)
+// the fixed-order column sum of ColsumArgs (apa_colsum.h) as a launch of its own: ceil(C / 32) blocks of 1024 threads
+int m1_colsum(const ColsumArgs& a, hipStream_t st);
+
+// apa_pose_head.hip: the pose-head halves of the one-call cfg 003 step (apa_pose_attn_train_step)
 struct PoseStepArgs {
   const void* W1_bf16 = nullptr;        // caller-maintained bf16 copy of W1 (nullptr: converted per call)
   const void* W2T_bf16 = nullptr;       // caller-maintained bf16 [16][Cp] transposed copy of W2 (nullptr: staged per block)
@@ -366,37 +372,10 @@ int pose_bwd_fused(const void* X, const float* W1, const float* W2, const void* 
                    void* ws, size_t ws_bytes, int N, int P, int C, int Cp, int J, int dtype,
                    const PoseStepArgs& a, hipStream_t st);
 
-// `more`: a fourth / fifth output section (columns [C3, C4) -> dwa4, [C4, C) -> dwa5) and an optional scalar
-// reduction aux_dst[0] = aux_scale * sum(aux_src[0 .. aux_n)) done by the launch's last block
-struct ColsumMore {
-  float* dwa4 = nullptr; int C3 = 0;
-  float* dwa5 = nullptr; int C4 = 0;
-  const float* aux_src = nullptr; int aux_n = 0; float aux_scale = 0.f; float* aux_dst = nullptr;
-};
-int m1_colsum(const float* pdwa, const float* pdba, float* dwa, float* dba, int nblk, int C, int ld,
-              uint64_t* rng_bump, hipStream_t st, float* dwa2 = nullptr, int C1 = 0, float* dwa3 = nullptr,
-              int C2 = 0, int perm_nthr = 0, int perm_cp = 0, const ColsumMore* more = nullptr);
-
-// apa_gemm_bf16.hip: C = (A[:, :64] . B[:, :64]^T) * mask/keep + A[:, 64:] . B[:, 64:]^T  (all bf16, k contiguous)
-int gemm_bf16_mid_dropout(const void* A, long lda, const void* B, long ldb, void* C, long ldc, int M, int N,
-                          int K, float inv_keep, const uint8_t* maskbits, hipStream_t st);
-
-// apa_pc_fused.hip: per-class maps with K <= 64 (HMDB-51), bf16, Xatt == X: the HBM-bound form
-constexpr int PC_DW_MAX_SPLITS = 32;
-struct PcFusedWs {
-  void* WcatT;      // bf16 [C/64][128][64]: Wa | Wt transposed (zero padded to 64 columns each), k-tile-major
-  void* Wcat2;      // bf16 [C][128]: Wt | Wa
-  float* bcat;      // f32 [128]: ba | bt
-  void* dTdZ;       // bf16 [R][128]: dT | dZ
-  float* partial;   // f32 [splits][C][128]
-  uint8_t* maskbits;  // [R*C/8]: keep decisions of the dropout mask, bit (e & 7) of byte e >> 3
-  float* lpart;       // f32 [ceil(R/32)][2][64]: per-block partial rows of sum_p A * T (folded activation pass)
-  uint64_t* bits_tag; // which mask `maskbits` holds: {seed, offset, thresh, n8} + the running step's offset (apa_pc_fused.hip)
-};
-// What the per-class maps ran (filled on the host only, as M1Trace / PoseTrace: the product never sets the pointer; the
-// test-only probe library does, around one call, and tests/test_pc_paths_gpu.py reads it back).  0 = not decided by
-// this call.  `phase` says whose fields the apa_pc_fused.hip host functions fill: 1 pc_forward, 2 pc_backward,
-// 3 pc_weight_images.
+// Per-class maps (apa_pc_fused.hip, apa_pc.hip).  What they ran (filled on the host only, as M1Trace / PoseTrace: the
+// product never sets the pointer; the test-only probe library does, around one call, and tests/test_pc_paths_gpu.py
+// reads it back).  0 = not decided by this call.  `phase` says whose fields the apa_pc_fused.hip host functions fill:
+// 1 pc_forward, 2 pc_backward, 3 pc_weight_images.
 enum PcPath { PC_PATH_NONE = 0, PC_PATH_FUSED, PC_PATH_GENERIC };
 enum PcPrep { PC_PREP_NONE = 0, PC_PREP_WEIGHTS, PC_PREP_BITS, PC_PREP_BOTH };
 enum PcLogitsAt { PC_LOGITS_NONE = 0, PC_LOGITS_FINISH, PC_LOGITS_DX, PC_LOGITS_FWD_ACT };
@@ -428,10 +407,19 @@ struct PcTrace {
 };
 extern thread_local PcTrace* g_pc_trace;
 inline PcTrace* pc_trace() { return g_pc_trace; }
-// (test-only probe) the carve of pc_plan: out[0..15] = R, Kp, off_wap, off_wtp, off_bap, off_z, off_dt, off_dz, off_pdbt,
-// off_pdba, off_gemm, gemm_half, off_xd, off_bits, off_fused, total
-void pc_plan_offsets(int N, int P, int C, int Ca, int K, int dtype, size_t* out);
-int pc_bwd_act_psplit_host(int N, int kgroups, int P, int act);
+
+// apa_pc_fused.hip: per-class maps with K <= 64 (HMDB-51), bf16, Xatt == X: the HBM-bound form
+constexpr int PC_DW_MAX_SPLITS = 32;
+struct PcFusedWs {
+  void* WcatT;      // bf16 [C/64][128][64]: Wa | Wt transposed (zero padded to 64 columns each), k-tile-major
+  void* Wcat2;      // bf16 [C][128]: Wt | Wa
+  float* bcat;      // f32 [128]: ba | bt
+  void* dTdZ;       // bf16 [R][128]: dT | dZ
+  float* partial;   // f32 [splits][C][128]
+  uint8_t* maskbits;  // [R*C/8]: keep decisions of the dropout mask, bit (e & 7) of byte e >> 3
+  float* lpart;       // f32 [ceil(R/32)][2][64]: per-block partial rows of sum_p A * T (folded activation pass)
+  uint64_t* bits_tag; // which mask `maskbits` holds: {seed, offset, thresh, n8} + the running step's offset (apa_pc_fused.hip)
+};
 // fused dx / dw geometry as pc_fused_dx / pc_fused_dw pick it: out[0..5] = upb, splits, rbs, S, rows_per_split, ctiles
 void pc_fused_geometry(int R, int C, int* out);
 
@@ -442,9 +430,7 @@ struct PcPrepBits {   // the step's keep bits, written by the weight-preparation
   size_t n_elems; float keep_prob; uint64_t seed, offset; const uint64_t* offset_dev;
 };
 struct PcDwTail {     // what the dW reduce launch's tail blocks also do (see pc_dw_reduce_kernel)
-  const float* pdbt; float* dbt; float* dba; int nrows;         // dbt | dba from [nrows][2K] block partials
-  uint64_t* rng_bump;                                            // device-side dropout counter to advance
-  const float* aux_src; int aux_n; float aux_scale; float* aux_dst;   // aux_dst[0] = aux_scale * sum(aux_src)
+  ColsumArgs cs;      // dbt | dba from the [nblk][2K] block partials (+ the counter bump and the batch-mean aux)
   bool next_bits = false; uint64_t next_seed = 0;                     // also prepare the NEXT step's keep bits (tagged)
 };
 // weights == false (APA_FLAG_WEIGHT_IMAGES: the images are the caller's business): the keep bits only
@@ -462,8 +448,12 @@ int pc_fused_logits_finish(const PcFusedWs& f, float* logits, int N, int P, int 
 int pc_fused_dw(const PcFusedWs& f, const void* X, float* dWt, float* dWa, int R, int C, int K, bool train,
                 float keep_prob, hipStream_t st, const PcDwTail* tail = nullptr);
 
-// apa_dense.hip: per-class bottom-up maps (M == K); Tsave = fp32 [N,P,K] top-down map saved for bwd
+// apa_pc.hip: per-class bottom-up maps (M == K); Tsave = fp32 [N,P,K] top-down map saved for bwd
 size_t pc_workspace_bytes(int N, int P, int C, int Ca, int K, int dtype);
+// (test-only probe) the carve of pc_plan: out[0..15] = R, Kp, off_wap, off_wtp, off_bap, off_z, off_dt, off_dz, off_pdbt,
+// off_pdba, off_gemm, gemm_half, off_xd, off_bits, off_fused, total
+void pc_plan_offsets(int N, int P, int C, int Ca, int K, int dtype, size_t* out);
+int pc_bwd_act_psplit_host(int N, int kgroups, int P, int act);
 // every weight image the shape can need, built in `ws`; maps (optional, APA_WIMG_MAX entries) / nmaps describe them
 int pc_weight_images(const float* Wa, const float* ba, const float* Wt, const float* bt, void* ws, int N, int P,
                      int C, int Ca, int K, int dtype, apa_weight_image* maps, int* nmaps, hipStream_t st);

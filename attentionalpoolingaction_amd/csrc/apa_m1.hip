@@ -1040,7 +1040,11 @@ int m1_backward(const void* X, const void* Xatt, const float* Wa, const float* b
                        ? reinterpret_cast<uint64_t*>(static_cast<uintptr_t>(offset))
                        : nullptr;
   if (tr) { tr->reduce = small_ok ? M1_REDUCE_COLSUM : M1_REDUCE_BWD_REDUCE; tr->rng_bump = bump != nullptr; }
-  if (small_ok) return m1_colsum(pdwa, pdba, dWa, dba, nred, cred, cred, bump, st);
+  if (small_ok) {
+    ColsumArgs cs;
+    cs.pdwa = pdwa; cs.pdba = pdba; cs.nblk = nred; cs.C = cred; cs.ld = cred; cs.dwa = dWa; cs.dba = dba; cs.rng_bump = bump;
+    return m1_colsum(cs, st);
+  }
   hipLaunchKernelGGL(m1_bwd_reduce_kernel, dim3((cred + 63) / 64 + 1), dim3(256), 0, st, pdwa, pdba,
                      dWa, dba, abar, G, dbt, nred, cred, N, K, 1, bump);
   APA_LAUNCH_CHECK("m1_bwd_reduce_kernel");

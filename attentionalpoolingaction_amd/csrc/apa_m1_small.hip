@@ -874,22 +874,8 @@ __global__ __launch_bounds__(256) void m1_bwd_head_tiles_kernel(
 // grid = ceil(C/32) blocks of 1024 threads: 32 row groups x 32 columns, 128-byte row segments.
 // The last kernel of the backward call: optionally advances the HBM dropout counter.
 // --------------------------------------------------------------------------------------------
-// Columns [0, C1) go to dwa, columns [C1, C2) to dwa2, columns [C2, C3) to dwa3, [C3, C4) to dwa4 and
-// [C4, C) to dwa5 (up to five outputs from one partial matrix: dW2 | db1 | db2 | dWa | dba of the cfg 003
-// pose head); C1 == ... == C for a single output.
-// aux (optional): aux_dst[0] = aux_scale * sum(aux_src[0 .. aux_n)) in a fixed order, by the LAST block -- a
-// scalar reduction that would otherwise be a launch of its own (the pose loss of the fused cfg 003 step).
-__global__ __launch_bounds__(1024) void m1_colsum_kernel(const float* __restrict__ pdwa,
-                                                         const float* __restrict__ pdba,
-                                                         float* __restrict__ dwa,
-                                                         float* __restrict__ dba, int nblk, int C,
-                                                         int ld, uint64_t* __restrict__ rng_bump,
-                                                         float* __restrict__ dwa2, int C1,
-                                                         float* __restrict__ dwa3, int C2, int perm_nthr,
-                                                         int perm_cp, ColsumExtra x) {
-  colsum_block(blockIdx.x, gridDim.x, pdwa, pdba, dwa, dba, nblk, C, ld, rng_bump, dwa2, C1, dwa3, C2, perm_nthr,
-               perm_cp, x);
-}
+// What is summed and where the sums go: ColsumArgs (apa_colsum.h).
+__global__ __launch_bounds__(1024) void m1_colsum_kernel(ColsumArgs a) { colsum_block(blockIdx.x, gridDim.x, a); }
 
 // ============================================================================================
 // host
@@ -1038,20 +1024,10 @@ int m1_bwd_head(const float* G, const float* Wt, const float* zsave, const float
   return APA_OK;
 }
 
-int m1_colsum(const float* pdwa, const float* pdba, float* dwa, float* dba, int nblk, int C, int ld,
-              uint64_t* rng_bump, hipStream_t st, float* dwa2, int C1, float* dwa3, int C2, int perm_nthr,
-              int perm_cp, const ColsumMore* more) {
-  if (!dwa2) C1 = C;
-  if (!dwa3) C2 = C;
-  ColsumExtra x;
-  x.C3 = C; x.C4 = C;
-  if (more) {
-    if (more->dwa4) { x.dwa4 = more->dwa4; x.C3 = more->C3; }
-    if (more->dwa5) { x.dwa5 = more->dwa5; x.C4 = more->C4; }
-    x.aux_src = more->aux_src; x.aux_n = more->aux_n; x.aux_scale = more->aux_scale; x.aux_dst = more->aux_dst;
-  }
-  hipLaunchKernelGGL(m1_colsum_kernel, dim3((C + 31) / 32), dim3(1024), 0, st, pdwa, pdba, dwa, dba,
-                     nblk, C, ld, rng_bump, dwa2, C1, dwa3, C2, perm_nthr, perm_cp, x);
+int m1_colsum(const ColsumArgs& args, hipStream_t st) {
+  ColsumArgs a = args;
+  const int nb = colsum_prepare(a);
+  hipLaunchKernelGGL(m1_colsum_kernel, dim3(nb), dim3(1024), 0, st, a);
   APA_LAUNCH_CHECK("m1_colsum_kernel");
   return APA_OK;
 }

@@ -5,7 +5,7 @@
 // With K = 51 the two 1x1 convs (Z = X.Wa, T = dropout(X).Wt) are 128 output columns over a 2048-deep
 // contraction: 0.25 GFLOP per image against 3 * P * C * 2 bytes -- the products are HBM-bound, not
 // MFMA-bound, and what matters is how often the 25.7 MB feature map crosses the memory system.  The
-// generic path (apa_dense.hip) materialises dropout(X) (read + write of the map), runs Z and T as two
+// generic path (apa_pc.hip) materialises dropout(X) (read + write of the map), runs Z and T as two
 // split-K GEMMs (two more reads), and in backward materialises it again, runs dWa / dWt as two more
 // GEMMs and dX as two GEMMs with a read-modify-write in between: ten passes over map-sized tensors.
 // Here the map is read ONCE per product group and dX is written once:
@@ -21,7 +21,7 @@
 //                                                    formed in registers from att / T / G, transposed MFMA, 16-byte
 //                                                    stores straight from the accumulators.  Spatial-softmax
 //                                                    attention and P < 32 keep the older form: pc_bwd_act_kernel
-//                                                    (apa_dense.hip) + ONE launch of the DMA-staged GEMM
+//                                                    (apa_pc.hip) + ONE launch of the DMA-staged GEMM
 //                                                    (apa_gemm_bf16.hip) over [dT | dZ] . [Wt | Wa]^T, accumulators
 //                                                    masked in registers between the two 64-deep k tiles.
 // The dropout mask is the library's counter-based one (flat element index r*C + c); the forward pass leaves
@@ -869,8 +869,7 @@ __global__ __launch_bounds__(512) void pc_bwd_dx_kernel(PcDxArgs a) {
 // from the activation pass's block partials, literally m1_colsum_kernel's body (same sums bit for bit) -- and, in the
 // one-call train step, the batch mean of the per-example losses and the dropout counter's increment.
 struct PcTail {
-  const float* pdbt; float* dbt; float* dba; int nrows, K;      // pdbt [nrows][2K]: dbt | dba partials
-  uint64_t* rng_bump; ColsumExtra x;
+  ColsumArgs cs;                                                 // dbt | dba from the [nrows][2K] block partials
   int ntail;                                                     // column-sum blocks (after the nmain reduce blocks)
   PcBitsArgs next;                                               // next.bits != nullptr: the blocks after those write
 };                                                               //   the NEXT step's keep bits (offset tag[4] + 1)
@@ -891,8 +890,7 @@ __global__ __launch_bounds__(1024) void pc_dw_reduce_kernel(const float* __restr
     return;
   }
   if ((int)blockIdx.x >= nmain) {
-    colsum_block((int)blockIdx.x - nmain, tl.ntail, tl.pdbt, nullptr, tl.dbt, nullptr, tl.nrows,
-                 2 * tl.K, 2 * tl.K, tl.rng_bump, tl.dba, tl.K, nullptr, 2 * tl.K, 0, 0, tl.x);
+    colsum_block((int)blockIdx.x - nmain, tl.ntail, tl.cs);
     return;
   }
   const long idx = (long)blockIdx.x * 1024 + threadIdx.x;
@@ -1112,14 +1110,11 @@ int pc_fused_dw(const PcFusedWs& f, const void* X, float* dWt, float* dWa, int R
   APA_LAUNCH_CHECK("pc_bwd_dw_kernel");
   const int nmain = (int)(((long)C * 128 + 1023) / 1024);
   PcTail tl;
-  tl.pdbt = nullptr; tl.dbt = nullptr; tl.dba = nullptr; tl.nrows = 0; tl.K = K; tl.rng_bump = nullptr;
   tl.next = PcBitsArgs{nullptr, 0, 0, 0, 0, nullptr, nullptr};
   int ntail = 0, nnext = 0;
   if (tail) {
-    tl.pdbt = tail->pdbt; tl.dbt = tail->dbt; tl.dba = tail->dba; tl.nrows = tail->nrows; tl.rng_bump = tail->rng_bump;
-    tl.x.aux_src = tail->aux_src; tl.x.aux_n = tail->aux_n; tl.x.aux_scale = tail->aux_scale; tl.x.aux_dst = tail->aux_dst;
-    tl.x.C3 = 2 * K; tl.x.C4 = 2 * K;
-    ntail = (2 * K + 31) / 32;
+    tl.cs = tail->cs;
+    ntail = colsum_prepare(tl.cs);
     if (tail->next_bits && train) {
       tl.next.bits = f.maskbits; tl.next.n8 = (size_t)R * C / 8; tl.next.thresh = keep_thresh(keep_prob);
       tl.next.seed = tail->next_seed; tl.next.tag = f.bits_tag;
@@ -1132,8 +1127,8 @@ int pc_fused_dw(const PcFusedWs& f, const void* X, float* dWt, float* dWa, int R
   if (PcTrace* t = pc_trace()) {
     t->dw = PC_DW_FUSED; t->dw_S = S; t->dw_rows = rows_per_split; t->dw_ctiles = ctiles;
     if (tail) {
-      t->tail = PC_TAIL_DW; t->tail_nrows = tail->nrows; t->next_bits = nnext > 0 ? 1 : 0;
-      t->rng_bump = tail->rng_bump ? 1 : 0; t->aux = tail->aux_dst ? 1 : 0;
+      t->tail = PC_TAIL_DW; t->tail_nrows = tail->cs.nblk; t->next_bits = nnext > 0 ? 1 : 0;
+      t->rng_bump = tail->cs.rng_bump ? 1 : 0; t->aux = tail->cs.aux_dst ? 1 : 0;
     }
   }
   hipLaunchKernelGGL(pc_dw_reduce_kernel, dim3((unsigned)(nmain + ntail + nnext)), dim3(1024), 0, st, f.partial, dWt,

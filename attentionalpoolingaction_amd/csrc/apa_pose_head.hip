@@ -1,12 +1,8 @@
-// apa_dense.hip -- the dense (MFMA-bound) parts of the head, built on apa_gemm.hip:
-//
-//   A. PoseLogits head, /root/reference/models/slim/nets/nets_factory.py:147-160
+// apa_pose_head.hip -- the PoseLogits head, built on apa_gemm.hip (nets_factory.py:147-160 of the reference model):
 //        Ppre = relu(X.W1 + b1)   [N,P,768]      'PoseLogits/ExtraConv2d_1x1'
 //        Pl   = Ppre.W2 + b2      [N,P,J]        'PoseLogits/Conv2d_1c_1x1'
-//      and its backward (the reference relies on TF autodiff).
-//   B. Per-class bottom-up maps (cfg.NET..._PER_CLASS, nets_factory.py:257): M == K.  Z and T are
-//      two real GEMMs here ([N*P, C] x [C, K]); the activation / spatial mean and their gradients
-//      are small fused elementwise-reduction kernels over the [N,P,K] tensors.
+//      and its backward (the reference relies on TF autodiff); pose_fwd_fused / pose_bwd_fused are its halves of the
+//      one-call cfg 003 step.
 #include <type_traits>
 #include <math.h>
 
@@ -15,23 +11,6 @@
 
 namespace apa {
 
-static int dt_code(int dtype) { return dtype == APA_DTYPE_BF16 ? 1 : 0; }
-static size_t dt_size(int dtype) { return dtype == APA_DTYPE_BF16 ? 2 : 4; }
-
-template <typename T> __device__ __forceinline__ float ldf(const T* p, size_t i);
-template <> __device__ __forceinline__ float ldf<float>(const float* p, size_t i) { return p[i]; }
-template <> __device__ __forceinline__ float ldf<bf16_t>(const bf16_t* p, size_t i) {
-  return __uint_as_float((uint32_t)p[i].v << 16);
-}
-template <typename T> __device__ __forceinline__ void stf(T* p, size_t i, float v);
-template <> __device__ __forceinline__ void stf<float>(float* p, size_t i, float v) { p[i] = v; }
-template <> __device__ __forceinline__ void stf<bf16_t>(bf16_t* p, size_t i, float v) {
-  p[i].v = (uint16_t)f32_to_bf16_bits(v);
-}
-
-// =============================================================================================
-// A. PoseLogits head
-// =============================================================================================
 constexpr int POSE_RB = 8;   // rows per block of the dPpre kernel
 
 // dPpre[r,j] = (sum_q dPl[r,q] W2[j,q] + ext[r,j]) * [Ppre[r,j] > 0]
@@ -976,11 +955,7 @@ static int pose_head_bwd_big(const void* X, const float* W1, const void* dPpre, 
       if (job) tr->colsum = job->done ? POSE_COLSUM_TAIL : POSE_COLSUM_OWN;
     }
     if (job && !job->done) {     // no split-K reduce launch to ride on: the column sum as a launch of its own
-      ColsumMore more;
-      more.dwa4 = job->dwa4; more.C3 = job->C3; more.dwa5 = job->dwa5; more.C4 = job->C4;
-      more.aux_src = job->aux_src; more.aux_n = job->aux_n; more.aux_scale = job->aux_scale; more.aux_dst = job->aux_dst;
-      rc = m1_colsum(job->pdwa, nullptr, job->dwa, nullptr, job->nblk, job->C, job->ld, job->rng_bump, st, job->dwa2,
-                     job->C1, job->dwa3, job->C2, job->perm_nthr, job->perm_cp, &more);
+      rc = m1_colsum(job->a, st);
       if (rc != APA_OK) return rc;
       job->done = true;
     }
@@ -1011,6 +986,23 @@ static int pose_head_bwd_big(const void* X, const float* W1, const void* dPpre, 
     rc = gemm_launch(g, st);
   }
   return rc;
+}
+
+// [dW2 | db1 | db2 (| dWa | dba)] from the [nblk][ld] partial rows of either rows kernel: one fixed-order column sum
+// for all of them; in the fused step the same blocks finish the pose loss (its block partials) and advance the dropout
+// counter.  c1: width of the dW2 section; perm_nthr > 0: that section is in pose_bwd_rows_kernel's permuted order.
+static ColsumArgs pose_rows_colsum(const float* partial, int nblk, int ld, int c1, int perm_nthr, int Cp, int J,
+                                   float* dW2, float* db1, float* db2, const PoseBwdFuse* fuse) {
+  ColsumArgs a;
+  a.pdwa = partial; a.nblk = nblk; a.ld = ld;
+  a.dwa = dW2; a.perm_nthr = perm_nthr; a.perm_cp = Cp;
+  a.dwa2 = db1; a.C1 = c1; a.dwa3 = db2; a.C2 = c1 + Cp;
+  a.C = c1 + Cp + J;
+  if (fuse && fuse->dWa) { a.dwa4 = fuse->dWa; a.C3 = a.C; a.dwa5 = fuse->dba; a.C4 = a.C + Cp; a.C += Cp + 1; }
+  if (!fuse) return a;
+  a.rng_bump = fuse->rng_bump;
+  a.aux_src = fuse->aux_src; a.aux_n = fuse->aux_n; a.aux_scale = fuse->aux_scale; a.aux_dst = fuse->aux_dst;
+  return a;
 }
 
 static int pose_head_bwd_impl(const void* X, const float* W1, const float* W2, const void* Ppre,
@@ -1080,20 +1072,10 @@ static int pose_head_bwd_impl(const void* X, const float* W1, const float* W2, c
     else APA_ROWSM(false, false);
 #undef APA_ROWSM
     APA_LAUNCH_CHECK("pose_bwd_rows_mfma_kernel");
-    const int c1 = Cp * J;
-    // [dW2 | db1 | db2 (| dWa | dba)]: one fixed-order column sum for all of them (+ the pose loss and the dropout
-    // counter in the fused step).  Nothing behind it reads its outputs: it rides on the tail blocks of dW1's split-K
-    // reduce launch when there is one (round 6), else it is a launch of its own
+    // Nothing behind the column sum reads its outputs: it rides on the tail blocks of dW1's split-K reduce launch
+    // when there is one (round 6), else it is a launch of its own
     ColsumJob job;
-    job.pdwa = partial; job.dwa = dW2; job.nblk = nblk; job.ld = (int)ldp; job.rng_bump = fuse ? fuse->rng_bump : nullptr;
-    job.dwa2 = db1; job.C1 = c1; job.dwa3 = db2; job.C2 = c1 + Cp; job.perm_nthr = 0; job.perm_cp = Cp;
-    job.C = c1 + Cp + J;
-    if (want_wa) {
-      job.dwa4 = fuse->dWa; job.C3 = c1 + Cp + J;
-      job.dwa5 = fuse->dba; job.C4 = c1 + Cp + J + Cp;
-      job.C = c1 + Cp + J + Cp + 1;
-    }
-    if (fuse) { job.aux_src = fuse->aux_src; job.aux_n = fuse->aux_n; job.aux_scale = fuse->aux_scale; job.aux_dst = fuse->aux_dst; }
+    job.a = pose_rows_colsum(partial, nblk, (int)ldp, Cp * J, 0, Cp, J, dW2, db1, db2, fuse);
     return pose_head_bwd_big(X, W1, dPpre, dX, accumulate_dX, dW1, w, pl, gws, R, C, Cp, dtype, st,
                              fuse ? fuse->W1_bf16 : nullptr, fuse, &job);
   }
@@ -1141,18 +1123,7 @@ static int pose_head_bwd_impl(const void* X, const float* W1, const float* W2, c
 #undef APA_ROWS
     APA_LAUNCH_CHECK("pose_bwd_rows_kernel");
     const int ldp = (int)pose_rows_ld(Cp, J, nthr2), c1 = (int)pose_rows_dw2(Cp, J, nthr2);
-    // [dW2 | db1 | db2 (| dWa | dba)]: one fixed-order column sum for all of them; in the fused step the same
-    // launch finishes the pose loss (its block partials) and advances the dropout counter
-    ColsumMore more;
-    int ncol = c1 + Cp + J;
-    if (want_wa) {
-      more.dwa4 = fuse->dWa; more.C3 = c1 + Cp + J;
-      more.dwa5 = fuse->dba; more.C4 = c1 + Cp + J + Cp;
-      ncol = c1 + Cp + J + Cp + 1;
-    }
-    if (fuse) { more.aux_src = fuse->aux_src; more.aux_n = fuse->aux_n; more.aux_scale = fuse->aux_scale; more.aux_dst = fuse->aux_dst; }
-    int rc = m1_colsum(partial, nullptr, dW2, nullptr, nblk, ncol, ldp, fuse ? fuse->rng_bump : nullptr, st, db1, c1,
-                       db2, c1 + Cp, J == 16 ? nthr2 : 0, Cp, fuse ? &more : nullptr);
+    int rc = m1_colsum(pose_rows_colsum(partial, nblk, ldp, c1, J == 16 ? nthr2 : 0, Cp, J, dW2, db1, db2, fuse), st);
     if (rc != APA_OK) return rc;
     return pose_head_bwd_big(X, W1, dPpre, dX, accumulate_dX, dW1, w, pl, gws, R, C, Cp, dtype, st,
                              fuse ? fuse->W1_bf16 : nullptr, fuse);
@@ -1186,7 +1157,9 @@ static int pose_head_bwd_impl(const void* X, const float* W1, const float* W2, c
 #undef APA_DPPRE
   APA_LAUNCH_CHECK("pose_dppre_kernel");
   // db1 = column sums of dPpre, db2 = column sums of dPl (fixed-order reduce of the block partials)
-  int rc = m1_colsum(partial, nullptr, db1, nullptr, pl.nchunks, Cp + J, Cp + J, nullptr, st, db2, Cp);
+  ColsumArgs cs;
+  cs.pdwa = partial; cs.nblk = pl.nchunks; cs.C = Cp + J; cs.ld = Cp + J; cs.dwa = db1; cs.dwa2 = db2; cs.C1 = Cp;
+  int rc = m1_colsum(cs, st);
   if (rc != APA_OK) return rc;
 
   if (dPl) {  // dW2[j,q] = sum_r Ppre[r,j] dPl[r,q]
@@ -1304,815 +1277,3 @@ extern "C" int apa_pose_head_bwd_rank1ext(const void* X, const float* W1, const 
   return pose_head_bwd_impl(X, W1, W2, Ppre, dPl, nullptr, ext_row, ext_col, dX, accumulate_dX, dW1, db1,
                             dW2, db2, ws, ws_bytes, N, P, C, Cp, J, dtype, stream);
 }
-
-// =============================================================================================
-// B. Per-class bottom-up maps (M == K)
-// =============================================================================================
-namespace apa {
-
-// Zero-padded copies of up to three [rows][K] fp32 parameters as [rows][Kp] in ONE launch; a segment
-// marked bf16 is also converted, so that the bf16 products take the DMA-staged MFMA kernels (both
-// operands bf16, whole 64-wide k tiles).
-struct PcPadSegs {
-  const float* src[3];
-  void* dst[3];
-  long end[3];     // cumulative element counts (rows * Kp)
-  int bf16[3];
-  int ld[3];       // row stride of dst in elements (>= Kp: two parameters can share rows as [Wt | Wa], see pc_cat)
-  int n;
-};
-// Xd = X * mask / keep (bf16), the same counter-based mask as everywhere else (flat index r*C + c); block `bid` of `nb`
-struct PcDropArgs {
-  const bf16_t* X; bf16_t* Xd; size_t n8; float inv_keep; uint32_t thresh; uint64_t seed, offset;
-  const uint64_t* offset_dev; unsigned nblocks;     // nblocks == 0: none
-  uint8_t* bits;                                    // optional: the keep decisions, bit (e & 7) of byte e >> 3
-};
-__device__ __forceinline__ void pc_dropout_block(const PcDropArgs& a, unsigned bid, unsigned nb) {
-  uint32_t k0, k1;
-  rng_key_dev_x(a.seed, a.offset_dev ? *a.offset_dev : a.offset, a.thresh, k0, k1);
-  for (size_t v = (size_t)bid * 256 + threadIdx.x; v < a.n8; v += (size_t)nb * 256) {
-    float x[8];
-    Vec<bf16_t>::unpack(ld16(a.X + v * 8), x);
-    uint32_t byte = 0;
-#pragma unroll
-    for (int e = 0; e < 8; e += 2) {
-      float m0, m1;
-      rng_keep2_x(v * 8 + e, k0, k1, a.thresh, m0, m1);
-      x[e] *= m0 * a.inv_keep;
-      x[e + 1] *= m1 * a.inv_keep;
-      byte |= (m0 != 0.f ? 1u : 0u) << e;
-      byte |= (m1 != 0.f ? 1u : 0u) << (e + 1);
-    }
-    st16(a.Xd + v * 8, Vec<bf16_t>::pack(x));
-    if (a.bits) a.bits[v] = (uint8_t)byte;
-  }
-}
-// One thread per 8 output columns (Kp is a multiple of 8): 16-byte stores and 8x fewer waves -- the
-// one-element-per-thread form was bound by wave dispatch (28 k waves for 1.8 M elements: 8.4 us).
-// Round 4: the forward call's dropout(X) materialisation rides on the same launch (blocks past the padding work):
-// two launches at the floor (6.1 + 8.8 us at K = 393) become one.
-__global__ __launch_bounds__(256) void pc_pad_kernel(PcPadSegs sg, int K, int Kp, PcDropArgs dr) {
-  const unsigned npad = gridDim.x - dr.nblocks;
-  if (blockIdx.x >= npad) { pc_dropout_block(dr, blockIdx.x - npad, dr.nblocks); return; }
-  const unsigned idx = blockIdx.x * 256u + threadIdx.x;       // vector index: 8 elements each
-  if (sg.n == 0 || idx >= (unsigned)(sg.end[sg.n - 1] >> 3)) return;
-  int s = 0;
-  unsigned base = 0;
-  if (sg.n > 1 && idx >= (unsigned)(sg.end[0] >> 3)) { s = 1; base = (unsigned)(sg.end[0] >> 3); }
-  if (sg.n > 2 && idx >= (unsigned)(sg.end[1] >> 3)) { s = 2; base = (unsigned)(sg.end[1] >> 3); }
-  const unsigned j = idx - base;
-  const unsigned kp8 = (unsigned)Kp >> 3;
-  const unsigned r = j / kp8;
-  const int k0 = (int)(j - r * kp8) * 8;
-  const float* __restrict__ src = sg.src[s] + (size_t)r * K;
-  float v[8];
-#pragma unroll
-  for (int e = 0; e < 8; ++e) v[e] = (k0 + e) < K ? src[k0 + e] : 0.f;
-  const size_t doff = (size_t)r * sg.ld[s] + k0;
-  if (sg.bf16[s]) {
-    st16(static_cast<bf16_t*>(sg.dst[s]) + doff, Vec<bf16_t>::pack(v));
-  } else {
-    float4* d = reinterpret_cast<float4*>(static_cast<float*>(sg.dst[s]) + doff);
-    d[0] = make_float4(v[0], v[1], v[2], v[3]);
-    d[1] = make_float4(v[4], v[5], v[6], v[7]);
-  }
-}
-struct PcPadList {
-  PcPadSegs sg;
-  PcPadList() { sg.n = 0; }
-  void add(const float* W, void* Wp, int rows, int Kp, bool to_bf16, int ld = 0) {
-    const int i = sg.n++;
-    sg.src[i] = W; sg.dst[i] = Wp; sg.bf16[i] = to_bf16 ? 1 : 0; sg.ld[i] = ld > 0 ? ld : Kp;
-    sg.end[i] = (i ? sg.end[i - 1] : 0) + (long)rows * Kp;
-  }
-  // (an empty list -- APA_FLAG_WEIGHT_IMAGES: the padded weights are kept by the caller -- launches the dropout
-  // blocks alone, or nothing)
-  void launch(int K, int Kp, hipStream_t st, const PcDropArgs* drop = nullptr) const {
-    PcDropArgs dr = {nullptr, nullptr, 0, 1.f, 0, 0, 0, nullptr, 0, nullptr};
-    if (drop) dr = *drop;
-    const unsigned npad = sg.n ? (unsigned)(((sg.end[sg.n - 1] >> 3) + 255) / 256) : 0u;
-    if (PcTrace* t = pc_trace()) {
-      const bool bwd = t->phase == 2;
-      (bwd ? t->pad_bwd : t->pad_fwd) = (npad + dr.nblocks) ? 1 : 0;
-      (bwd ? t->pad_segs_bwd : t->pad_segs_fwd) = sg.n;
-      (bwd ? t->pad_drop_bwd : t->pad_drop_fwd) = dr.nblocks ? 1 : 0;
-    }
-    if (npad + dr.nblocks == 0) return;
-    hipLaunchKernelGGL(pc_pad_kernel, dim3(npad + dr.nblocks), dim3(256), 0, st, sg, K, Kp, dr);
-  }
-  // the images of this list as apa_weight_image maps: element (c, k) of segment i -> dst[c * ld + k]
-  int describe(const int* roles, int K, apa_weight_image* out) const {
-    for (int i = 0; i < sg.n; ++i) {
-      apa_weight_image& m = out[i];
-      m.dst = sg.dst[i]; m.role = roles[i]; m.is_f32 = sg.bf16[i] ? 0 : 1; m.cols = K; m.c_shift = 0;
-      m.a = sg.ld[i]; m.b = 0; m.d = 1; m.e = 0;
-    }
-    return sg.n;
-  }
-};
-
-constexpr int PC_PG = 16;   // pixel groups per block of the per-class activation passes
-constexpr int PC_MAX_PSPLIT = 8;   // pixel splits (grid.z) of the backward activation pass
-// pixel splits of pc_bwd_act_kernel: enough blocks to put one on most CUs; the spatial softmax needs the whole image
-static int pc_bwd_act_psplit(int N, int kgroups, int P, int act) {
-  if (act == 2) return 1;
-  int ps = (256 + N * kgroups - 1) / (N * kgroups);   // HMDB-51 shape, N = 32: 7.9 -> 4.9 us
-  if (ps > PC_MAX_PSPLIT) ps = PC_MAX_PSPLIT;
-  while (ps > 1 && (P + ps - 1) / ps < PC_PG) --ps;      // at least one pixel per pixel group
-  return ps < 1 ? 1 : ps;
-}
-__device__ __forceinline__ float pc_colsum(const float (&red)[PC_PG][64], int kk) {
-  float s = 0.f;
-#pragma unroll
-  for (int g = 0; g < PC_PG; ++g) s += red[g][kk];   // fixed order
-  return s;
-}
-__device__ __forceinline__ float pc_colmax(const float (&red)[PC_PG][64], int kk) {
-  float m = red[0][kk];
-#pragma unroll
-  for (int g = 1; g < PC_PG; ++g) m = fmaxf(m, red[g][kk]);
-  return m;
-}
-
-// forward activation + spatial mean.  grid (N, ceil(K/64)); 1024 threads = 64 classes x PC_PG pixel
-// groups (16 waves per block: these passes are short dependent-load chains, 4 groups measured 27 us
-// at K = 51 where 32 blocks of 4 waves cannot hide any latency)
-//   A[n,p,k] = f(Z[n,p,k]);  logits[n,k] = (1/P) sum_p A * T;  optional TopDownAttention copy
-// xe (one-call train step, K <= 64 so that one block holds the whole row): the row's softmax cross-entropy on the
-// logits it has just reduced -- G[n,:] = gscale (softmax - onehot), loss[1 + n] = xent_n (src/loss.py:74-80); the batch
-// mean is finished by the tail of the dW reduce launch.  One launch (4.7 us at the latency floor) less per step.
-template <typename T>
-__global__ __launch_bounds__(1024) void pc_fwd_act_kernel(const float* __restrict__ Z, int ldz,
-                                                         const float* __restrict__ Tm,
-                                                         float* __restrict__ att,
-                                                         float* __restrict__ logits,
-                                                         T* __restrict__ topdown, int P, int K,
-                                                         int act, PcXent xe) {
-  __shared__ float red[PC_PG][64];
-  const int n = blockIdx.x;
-  const int kk = threadIdx.x & 63, pg = threadIdx.x >> 6;
-  const int k = blockIdx.y * 64 + kk;
-  const bool ok = k < K;
-  const size_t rbase = (size_t)n * P;
-  float m = -INFINITY, l = 1.f;
-  if (act == 2) {  // spatial softmax over p (tf.nn.softmax: max-subtracted)
-    if (ok)
-      for (int p = pg; p < P; p += PC_PG) m = fmaxf(m, Z[(rbase + p) * ldz + k]);
-    red[pg][kk] = m;
-    __syncthreads();
-    m = pc_colmax(red, kk);
-    __syncthreads();
-    float s = 0.f;
-    if (ok)
-      for (int p = pg; p < P; p += PC_PG) s += expf(Z[(rbase + p) * ldz + k] - m);
-    red[pg][kk] = s;
-    __syncthreads();
-    l = pc_colsum(red, kk);
-    __syncthreads();
-  }
-  const float invl = 1.0f / l;
-  float acc = 0.f;
-  if (ok) {
-    // four pixels per round, their eight loads issued before the first use (a plain loop is one
-    // dependent round trip per pixel)
-    for (int p0 = pg; p0 < P; p0 += 4 * PC_PG) {
-      float z[4], t[4];
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        const size_t pr = rbase + min(p0 + u * PC_PG, P - 1);   // surplus slots re-read the last pixel
-        z[u] = Z[pr * ldz + k];
-        t[u] = Tm[pr * K + k];
-      }
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        const int p = p0 + u * PC_PG;
-        if (p < P) {
-          float a = z[u];
-          if (act == 2) a = expf(z[u] - m) * invl;
-          else if (act == 1) a = fmaxf(z[u], 0.f);
-          att[(rbase + p) * K + k] = a;
-          if (topdown) stf<T>(topdown, (rbase + p) * K + k, t[u]);
-          acc = fmaf(a, t[u], acc);
-        }
-      }
-    }
-  }
-  red[pg][kk] = acc;
-  __syncthreads();
-  __shared__ float lrow[64];
-  if (pg == 0) {                       // wave 0: lane kk owns class k
-    const float lg = ok ? pc_colsum(red, kk) / (float)P : -INFINITY;
-    if (ok) logits[(size_t)n * K + k] = lg;
-    lrow[kk] = lg;
-  }
-  if (xe.labels) {                     // (block-uniform; gridDim.y == 1 and 4 <= K <= 64: lrow holds the whole row)
-    __syncthreads();
-    if (pg == 0) {
-      pc_row_xent(lrow, n, K, xe, true, nullptr);
-    }
-  }
-}
-
-// one-call step, generic K > 64 path: where the gradient row G[n, :] comes from -- memory (row_logits == nullptr) or the
-// logits row the forward activation pass left (4 <= K <= 1024).  (The K <= 64 path takes its cross-entropy in
-// pc_bwd_dx_kernel, apa_pc_fused.hip.)
-struct PcDefer { PcXent xe; const float* row_logits; };
-// backward of the same: dT = G*A/P, dA = G*T/P, dZ = act'(dA); column partials for dbt / dba.
-// dT/dZ are written with leading dimension Kp (pad columns zeroed) in the intermediate dtype.
-template <typename T>
-__global__ __launch_bounds__(1024) void pc_bwd_act_kernel(const float* __restrict__ G,
-                                                         const float* __restrict__ att,
-                                                         const float* __restrict__ Tm,
-                                                         T* __restrict__ dT, T* __restrict__ dZ,
-                                                         float* __restrict__ pdbt,
-                                                         float* __restrict__ pdba, int P, int K,
-                                                         int Kp, int act, int ldg, PcDefer df) {
-  // dT / dZ: [R][ldg] with Kp written columns each (ldg = Kp, or 2*Kp when the two are interleaved as
-  // one [R][dT | dZ] operand for apa_pc_fused.hip)
-  __shared__ float red[PC_PG][64];
-  __shared__ float red2[PC_PG][64];
-  const int n = blockIdx.x;
-  const int kk = threadIdx.x & 63, pg = threadIdx.x >> 6;
-  const int k = blockIdx.y * 64 + kk;
-  const bool ok = k < K;
-  const bool pad = !ok && k < Kp;
-  const size_t rbase = (size_t)n * P;
-  const float invP = 1.0f / (float)P;
-  // grid.z > 1 (identity / relu only: no sum over the image's pixels is needed): block z owns a contiguous
-  // share of the pixels and its own partial row -- N x 1 blocks of 16 waves were 32 CUs' worth of latency chains
-  const int pchunk = (P + gridDim.z - 1) / gridDim.z;
-  const int p_lo = blockIdx.z * pchunk, p_hi = min(P, p_lo + pchunk);
-  // the first two pixels of every thread are requested before the gradient row is known: with the cross-entropy
-  // taken in this launch (df) the two round trips would otherwise be serial (measured 7.4 -> 14.4 us at K = 393)
-  constexpr int NPRE = 2;
-  float pa[NPRE], pt[NPRE];
-#pragma unroll
-  for (int u = 0; u < NPRE; ++u) {
-    const int p = p_lo + pg + u * PC_PG;
-    pa[u] = pt[u] = 0.f;
-    if (ok && p < p_hi) { pa[u] = att[(rbase + p) * K + k]; pt[u] = Tm[(rbase + p) * K + k]; }
-  }
-  float g;
-  if (df.row_logits) {
-    // K > 64 (generic path), one-call step: every block takes its image's cross-entropy itself from the logits row
-    // (softmax_xent_kernel's arithmetic: bit-identical G); block (y, z) = (0, 0) writes G[n, :] and loss[1 + n]
-    __shared__ float growf[1024];
-    if (pg == 0) pc_row_xent_any(df.row_logits + (size_t)n * K, n, K, df.xe, blockIdx.y == 0 && blockIdx.z == 0, growf);
-    __syncthreads();
-    g = ok ? growf[k] * invP : 0.f;
-  } else {
-    g = ok ? G[(size_t)n * K + k] * invP : 0.f;
-  }
-  float corr = 0.f;
-  if (act == 2) {  // sum_p A * dA (host: grid.z == 1)
-    float s = 0.f;
-    if (ok)
-      for (int p = pg; p < P; p += PC_PG) s = fmaf(att[(rbase + p) * K + k], g * Tm[(rbase + p) * K + k], s);
-    red[pg][kk] = s;
-    __syncthreads();
-    corr = pc_colsum(red, kk);
-    __syncthreads();
-  }
-  float sdt = 0.f, sdz = 0.f;
-  auto pixel = [&](int p, float a, float tm) {
-    if (ok) {
-      const float dA = g * tm;
-      const float dt = g * a;
-      float dz = dA;
-      if (act == 2) dz = a * (dA - corr);
-      else if (act == 1) dz = a > 0.f ? dA : 0.f;
-      stf<T>(dT, (rbase + p) * ldg + k, dt);
-      stf<T>(dZ, (rbase + p) * ldg + k, dz);
-      sdt += dt;
-      sdz += dz;
-    } else if (pad) {
-      stf<T>(dT, (rbase + p) * ldg + k, 0.f);
-      stf<T>(dZ, (rbase + p) * ldg + k, 0.f);
-    }
-  };
-#pragma unroll
-  for (int u = 0; u < NPRE; ++u) {
-    const int p = p_lo + pg + u * PC_PG;
-    if (p < p_hi) pixel(p, pa[u], pt[u]);
-  }
-  for (int p = p_lo + pg + NPRE * PC_PG; p < p_hi; p += PC_PG) {   // (batching the loads four pixels deep, as in
-    float a = 0.f, tm = 0.f;                                        //  the forward pass, measured slower here)
-    if (ok) { a = att[(rbase + p) * K + k]; tm = Tm[(rbase + p) * K + k]; }
-    pixel(p, a, tm);
-  }
-  red[pg][kk] = sdt;
-  red2[pg][kk] = sdz;
-  __syncthreads();
-  if (pg == 0 && ok) {
-    const size_t prow = (size_t)n * gridDim.z + blockIdx.z;
-    pdbt[prow * 2 * K + k] = pc_colsum(red, kk);            // one [N * grid.z][2K] partial matrix: dbt | dba
-    pdba[prow * 2 * K + k] = pc_colsum(red2, kk);
-  }
-}
-
-struct PcPlan {
-  long R;
-  int Kp;
-  size_t off_wap, off_wtp, off_bap, off_z, off_dt, off_dz, off_pdbt, off_pdba, off_gemm, gemm_half, off_xd, off_bits, off_fused, total;
-};
-static PcPlan pc_plan(int N, int P, int C, int Ca, int K, int dtype) {
-  PcPlan pl;
-  pl.R = (long)N * P;
-  // bf16: whole 64-wide k tiles for the products that contract over the class axis (dX)
-  pl.Kp = dtype == APA_DTYPE_BF16 ? (K + 63) / 64 * 64 : (K + 7) / 8 * 8;
-  size_t off = 0;
-  pl.off_wap = off;  off += align_up((size_t)Ca * pl.Kp * 4, 256);
-  pl.off_wtp = off;  off += align_up((size_t)C * pl.Kp * 4, 256);
-  pl.off_bap = off;  off += align_up((size_t)pl.Kp * 4, 256);
-  pl.off_z = off;    off += align_up((size_t)pl.R * pl.Kp * 4, 256);
-  pl.off_dt = off;   off += align_up((size_t)pl.R * pl.Kp * dt_size(dtype), 256);
-  pl.off_dz = off;   off += align_up((size_t)pl.R * pl.Kp * dt_size(dtype), 256);
-  // [N * splits][2K]: dbt | dba partials ([ceil(R / 128)][2K] from pc_bwd_dx_kernel)
-  pl.off_pdbt = off; off += align_up(((size_t)N * PC_MAX_PSPLIT + (size_t)pl.R / 128 + 1) * 2 * K * 4, 256);
-  pl.off_pdba = pl.off_pdbt + (size_t)K * 4;
-  const int cm = C > Ca ? C : Ca;
-  {
-    // split-K partials cover the padded width; two buffers: the twin products (Z | T, dWt | dWa) share a launch.
-    // Sized by the splits the launches will pick (the same calls as in pc_forward / pc_backward)
-    int sdw = gemm_pick_splits(C, K, (int)pl.R);
-    const int sdw2 = gemm_pick_splits(Ca, K, (int)pl.R);
-    if (sdw2 > sdw) sdw = sdw2;
-    int sfw = gemm_pick_splits((int)pl.R, pl.Kp, C);
-    const int sfw2 = gemm_pick_splits((int)pl.R, pl.Kp, Ca);
-    if (sfw2 > sfw) sfw = sfw2;
-    if (sfw > 8) sfw = 8;
-    size_t g = gemm_ws_bytes(cm, pl.Kp, sdw);
-    const size_t g2 = gemm_ws_bytes((int)pl.R, pl.Kp, sfw);   // split-K of the skinny forward products
-    if (g2 > g) g = g2;
-    pl.gemm_half = align_up(g, 256);
-    pl.off_gemm = off; off += 2 * pl.gemm_half + 256;
-  }
-  // bf16 training: dropout(X) materialised once per call, so the MFMA GEMMs that consume it can DMA
-  // their operands (the generic kernel applies the mask while staging through registers)
-  pl.off_xd = off;   off += dtype == APA_DTYPE_BF16 ? align_up((size_t)pl.R * C * 2, 256) : 0;
-  // ... and its keep decisions as bits: the one-launch dX product masks its accumulators with them (pc_cat)
-  pl.off_bits = off; off += dtype == APA_DTYPE_BF16 ? align_up((size_t)pl.R * C / 8 + 16, 256) : 0;
-  // K <= 64, bf16: operands of the HBM-bound fused kernels (apa_pc_fused.hip)
-  pl.off_fused = off; off += (dtype == APA_DTYPE_BF16 && K <= 64 && Ca == C) ? pc_fused_ws_bytes(N, P, C) : 0;
-  pl.total = off;
-  return pl;
-}
-
-static PcDropArgs pc_drop_args(const void* X, void* Xd, long R, int C, float keep_prob, uint64_t seed, uint64_t offset,
-                               unsigned flags, uint8_t* bits) {
-  const size_t n8 = (size_t)R * C / 8;
-  size_t nb = (n8 + 255) / 256;
-  if (nb > 4096) nb = 4096;
-  const RngKeyArgs k = rng_resolve(flags, keep_prob, seed, offset);
-  return PcDropArgs{static_cast<const bf16_t*>(X), static_cast<bf16_t*>(Xd), n8, 1.0f / keep_prob, k.thresh, k.seed,
-                    k.offset, k.offset_dev, (unsigned)nb, bits};
-}
-
-// bf16, attention and top-down weights of the same height (Ca == C), 16-byte addressable features: the padded bf16
-// weights lie as ONE [C][Wt (Kp) | Wa (Kp)] image and [dT | dZ] as one [R][2 Kp] image, so that
-//     dX = (dT . Wt^T) * mask/keep + dZ . Wa^T
-// is ONE product over the concatenated contraction (the wide kernel's mid-contraction mask) instead of a product plus
-// a read-modify-write product over the 25.7 MB result.  The forward / dW products read the halves with ld = 2 Kp.
-static bool pc_cat(const void* X, int C, int Ca, int dtype) {
-  return dtype == APA_DTYPE_BF16 && Ca == C && C % 8 == 0 && (reinterpret_cast<uintptr_t>(X) & 15) == 0;
-}
-
-thread_local PcTrace* g_pc_trace = nullptr;
-void pc_plan_offsets(int N, int P, int C, int Ca, int K, int dtype, size_t* out) {
-  const PcPlan pl = pc_plan(N, P, C, Ca, K, dtype);
-  const size_t v[16] = {(size_t)pl.R, (size_t)pl.Kp, pl.off_wap, pl.off_wtp, pl.off_bap, pl.off_z, pl.off_dt, pl.off_dz,
-                        pl.off_pdbt, pl.off_pdba, pl.off_gemm, pl.gemm_half, pl.off_xd, pl.off_bits, pl.off_fused,
-                        pl.total};
-  for (int i = 0; i < 16; ++i) out[i] = v[i];
-}
-int pc_bwd_act_psplit_host(int N, int kgroups, int P, int act) { return pc_bwd_act_psplit(N, kgroups, P, act); }
-
-size_t pc_workspace_bytes(int N, int P, int C, int Ca, int K, int dtype) {
-  return pc_plan(N, P, C, Ca, K, dtype).total;
-}
-
-static int act_code(unsigned flags) {
-  if (flags & APA_FLAG_SOFTMAX_ATT) return 2;
-  if (flags & APA_FLAG_RELU_ATT) return 1;
-  return 0;
-}
-
-static void set_dropout(GemmDesc& g, bool on_a, bool on_c, float keep_prob, uint64_t seed,
-                        uint64_t offset, unsigned flags) {
-  g.drop_a = on_a; g.drop_c = on_c;
-  g.inv_keep = 1.0f / keep_prob;
-  const RngKeyArgs k = rng_resolve(flags, keep_prob, seed, offset);
-  g.thresh = k.thresh; g.seed = k.seed; g.offset = k.offset; g.offset_dev = k.offset_dev;
-}
-
-// APA_FLAG_WEIGHT_IMAGES: every image pc_forward / pc_backward would otherwise prepare per call, built once here
-// (for 16-byte aligned features: the [Wt | Wa] concatenation of pc_cat) and described for the optimiser's launch.
-// K <= 64 (bf16, Ca == C) builds BOTH sets -- the fused kernels' and the padded GEMM operands -- because which path a
-// call takes also depends on its Xatt (== X or not) and on its dropout source.
-int pc_weight_images(const float* Wa, const float* ba, const float* Wt, const float* bt, void* ws, int N, int P,
-                     int C, int Ca, int K, int dtype, apa_weight_image* maps, int* nmaps, hipStream_t st) {
-  const PcPlan pl = pc_plan(N, P, C, Ca, K, dtype);
-  char* w = static_cast<char*>(ws);
-  const int Kp = pl.Kp;
-  const bool wb16 = dtype == APA_DTYPE_BF16;
-  const bool cat = wb16 && Ca == C && C % 8 == 0;
-  const int ldw = cat ? 2 * Kp : Kp;
-  void* WtP = w + pl.off_wtp;
-  void* WaP = cat ? static_cast<void*>(static_cast<bf16_t*>(WtP) + Kp) : static_cast<void*>(w + pl.off_wap);
-  float* baP = reinterpret_cast<float*>(w + pl.off_bap);
-  int n = 0;
-  PcTrace* tr = pc_trace();
-  if (tr) { tr->phase = 3; tr->wimg_cat = cat ? 1 : 0; }
-  {
-    PcPadList pads;
-    pads.add(Wa, WaP, Ca, Kp, wb16, ldw);
-    pads.add(ba, baP, 1, Kp, false);
-    pads.add(Wt, WtP, C, Kp, wb16, ldw);
-    pads.launch(K, Kp, st);
-    APA_LAUNCH_CHECK("pc_pad_kernel");
-    if (maps) {
-      const int roles[3] = {APA_WIMG_ROLE_WA, APA_WIMG_ROLE_BA, APA_WIMG_ROLE_WT};
-      n += pads.describe(roles, K, maps + n);
-    }
-  }
-  if (wb16 && Ca == C && K <= 64 && C % 256 == 0) {   // pc_fused_supported, minus X
-    const PcFusedWs f = pc_fused_carve(w + pl.off_fused, N, P, C);
-    if (tr) tr->wimg_fused = 1;
-    const int rc = pc_fused_prep(f, Wa, Wt, ba, bt, C, K, st, nullptr, true);
-    if (rc != APA_OK) return rc;
-    APA_HIP_CHECK(hipMemsetAsync(f.bits_tag, 0, 64, st));   // whatever the keep-bit map held: nobody may believe it
-    if (maps) {
-      auto put = [&](int role, void* dst, int f32, int sh, int a, int b, int d, int e) {
-        apa_weight_image& m = maps[n++];
-        m.dst = dst; m.role = role; m.is_f32 = f32; m.cols = K; m.c_shift = sh; m.a = a; m.b = b; m.d = d; m.e = e;
-      };
-      // WcatT [C/64][128][64]: tile c >> 6, row = column (Wa: k, Wt: 64 + k), position c & 63
-      put(APA_WIMG_ROLE_WA, f.WcatT, 0, 6, 128 * 64, 1, 64, 0);
-      put(APA_WIMG_ROLE_WT, f.WcatT, 0, 6, 128 * 64, 1, 64, 64 * 64);
-      // Wcat2 [C][128]: Wt | Wa
-      put(APA_WIMG_ROLE_WT, f.Wcat2, 0, 0, 128, 0, 1, 0);
-      put(APA_WIMG_ROLE_WA, f.Wcat2, 0, 0, 128, 0, 1, 64);
-      // bcat f32 [128]: ba | bt
-      put(APA_WIMG_ROLE_BA, f.bcat, 1, 0, 0, 0, 1, 0);
-      put(APA_WIMG_ROLE_BT, f.bcat, 1, 0, 0, 0, 1, 64);
-    }
-  }
-  if (nmaps) *nmaps = n;
-  if (tr) tr->wimg_maps = n;
-  return APA_OK;
-}
-
-int pc_forward(const void* X, const void* Xatt, const float* Wa, const float* ba, const float* Wt,
-               const float* bt, float* logits, float* att, float* Tsave, void* topdown, void* ws,
-               int N, int P, int C, int Ca, int K, unsigned flags, float keep_prob, uint64_t seed,
-               uint64_t offset, int dtype, hipStream_t st, M1Xent* xf) {
-  const PcPlan pl = pc_plan(N, P, C, Ca, K, dtype);
-  char* w = static_cast<char*>(ws);
-  const int Kp = pl.Kp, R = (int)pl.R;
-  const bool cat = pc_cat(X, C, Ca, dtype);
-  const int ldw = cat ? 2 * Kp : Kp;
-  void* WtP = w + pl.off_wtp;                                                   // (bf16 when it is padded at all)
-  void* WaP = cat ? static_cast<void*>(static_cast<bf16_t*>(WtP) + Kp) : static_cast<void*>(w + pl.off_wap);
-  float* baP = reinterpret_cast<float*>(w + pl.off_bap);
-  float* Z = reinterpret_cast<float*>(w + pl.off_z);
-  const bool train = (flags & APA_FLAG_TRAIN) && keep_prob < 1.0f;
-  const int tdt = dt_code(dtype);
-  const bool wb16 = dtype == APA_DTYPE_BF16;   // padded weights stored as bf16
-  const bool fast = dtype == APA_DTYPE_BF16 && C % 8 == 0 && (reinterpret_cast<uintptr_t>(X) & 15) == 0;
-  PcTrace* tr = pc_trace();
-  if (tr) { tr->phase = 1; tr->topdown = topdown ? 1 : 0; }
-  if (pc_fused_supported(N, P, C, Ca, K, dtype, X, Xatt) && !rng_external(flags)) {
-    if (tr) tr->path_fwd = PC_PATH_FUSED;
-    // K <= 64 (HMDB-51): Z | T in ONE pass over X, dropout applied on the way into LDS (apa_pc_fused.hip)
-    const PcFusedWs f = pc_fused_carve(w + pl.off_fused, N, P, C);
-    const bool devctr = flags & APA_FLAG_RNG_DEVICE;
-    const uint64_t* offd = devctr ? reinterpret_cast<const uint64_t*>(static_cast<uintptr_t>(offset)) : nullptr;
-    // training: the weight-preparation launch also writes the step's keep bits (its 128 weight blocks leave half
-    // the chip idle), and the product kernel DMAs them instead of hashing on its critical chain
-    // Round 5, the one-call train step with caller-kept weight images: NO preparation launch -- the keep bits of this
-    // step were written by the previous step's last launch (pc_dw_reduce_kernel's extra blocks) and are believed iff
-    // their tag says so; else the forward kernel hashes them itself (first step on a workspace, a jump of the offset)
-    const bool tagged = train && (flags & APA_FLAG_WEIGHT_IMAGES) && xf && xf->labels;
-    const bool prebits = train && !tagged;
-    const PcPrepBits pb = {(size_t)R * C, keep_prob, seed, devctr ? 0 : offset, offd};
-    int rc = APA_OK;
-    if (!tagged) rc = pc_fused_prep(f, Wa, Wt, ba, bt, C, K, st, prebits ? &pb : nullptr, !(flags & APA_FLAG_WEIGHT_IMAGES));
-    if (rc != APA_OK) return rc;
-    const bool xent_here = xf && xf->labels && xf->G && xf->loss && !xf->probs && K >= 4 && K <= 64;
-    // identity / relu attention: the activation pass rides on the product's epilogue (a block's 32 rows touch at most
-    // two images when P >= 32); the softmax needs the whole image's Z first and keeps its own launch
-    const int act = act_code(flags);
-    const bool fold = act != 2 && !topdown && P >= 32;
-    const PcFwdFold ff = {att, act, P};
-    rc = pc_fused_forward(f, X, Z, Tsave, R, C, K, train, keep_prob, seed, devctr ? 0 : offset, offd, st, prebits,
-                          fold ? &ff : nullptr, tagged);
-    if (rc != APA_OK) return rc;
-    if (fold) {
-      // one-call train step: pc_backward's first launch (pc_bwd_dx_kernel) finishes logits + cross-entropy
-      if (xent_here && pc_fused_dx_supported(P, act)) {
-        xf->done = true;
-        xf->deferred = true;
-        xf->logits = logits;
-        return APA_OK;
-      }
-      return pc_fused_logits_finish(f, logits, N, P, K, st);
-    }
-    dim3 grid(N, (K + 63) / 64);
-    PcXent xe = {nullptr, nullptr, nullptr, 0.f};
-    if (xent_here) {
-      xe.labels = xf->labels; xe.loss = xf->loss; xe.G = xf->G; xe.gscale = xf->gscale;
-      xf->done = true;
-    }
-    if (tr) {
-      tr->fwd_act = PC_ACT_BF16; tr->fwd_act_xe = xent_here ? 1 : 0; tr->logits = PC_LOGITS_FWD_ACT;
-      if (xent_here) tr->xent = PC_XENT_FWD_ACT;
-    }
-    hipLaunchKernelGGL(pc_fwd_act_kernel<bf16_t>, grid, dim3(64 * PC_PG), 0, st, Z, Kp, Tsave, att, logits,
-                       static_cast<bf16_t*>(topdown), P, K, act_code(flags), xe);
-    APA_LAUNCH_CHECK("pc_fwd_act_kernel");
-    return APA_OK;
-  }
-  if (tr) { tr->path_fwd = PC_PATH_GENERIC; tr->cat = cat ? 1 : 0; tr->fast = fast ? 1 : 0; }
-  {
-    PcPadList pads;
-    if (!(flags & APA_FLAG_WEIGHT_IMAGES)) {     // else: kept current by the caller (pc_weight_images' layout)
-      pads.add(Wa, WaP, Ca, Kp, wb16, ldw);
-      pads.add(ba, baP, 1, Kp, false);
-      if (fast) pads.add(Wt, WtP, C, Kp, true, ldw);
-    }
-    if (fast && train) {   // + the materialised dropout(X) of the DMA-staged T product (and its keep bits), same launch
-      const PcDropArgs dr = pc_drop_args(X, w + pl.off_xd, pl.R, C, keep_prob, seed, offset, flags,
-                                         reinterpret_cast<uint8_t*>(w + pl.off_bits));
-      pads.launch(K, Kp, st, &dr);
-    } else {
-      pads.launch(K, Kp, st);
-    }
-    APA_LAUNCH_CHECK("pc_pad_kernel");
-  }
-  GemmDesc gz;  // Z = Xatt . Wa + ba
-  gz.A = Xatt; gz.lda = Ca; gz.ta = tdt; gz.a_kc = true;
-  gz.B = WaP; gz.ldb = ldw; gz.tb = wb16 ? 1 : 0; gz.b_kc = false;
-  gz.C = Z; gz.ldc = Kp; gz.tc = 0;
-  gz.M = R; gz.N = Kp; gz.K = Ca; gz.bias = baP;
-  // N = Kp is one tile column: R/128 blocks cannot fill 256 CUs, so split the contraction
-  float* gws = reinterpret_cast<float*>(w + pl.off_gemm);
-  gz.splits = gemm_pick_splits(R, Kp, Ca); if (gz.splits > 8) gz.splits = 8;
-  gz.ws = gws;
-  GemmDesc gt;  // T = dropout(X) . Wt + bt
-  gt.A = X; gt.lda = C; gt.ta = tdt; gt.a_kc = true;
-  gt.C = Tsave; gt.ldc = K; gt.tc = 0;
-  gt.M = R; gt.K = C; gt.bias = bt;
-  if (fast) {   // zero-padded weights (16-byte rows) + materialised dropout: the DMA-staged MFMA GEMM
-    gt.B = WtP; gt.ldb = ldw; gt.tb = 1; gt.b_kc = false;
-    gt.N = Kp; gt.n_valid = K;
-    if (train) gt.A = w + pl.off_xd;     // (written by the padding launch above)
-  } else {      // Wt rows are K floats: unaligned -> scalar staging, mask applied while staging
-    gt.B = Wt; gt.ldb = K; gt.tb = 0; gt.b_kc = false;
-    gt.N = K;
-    if (train) set_dropout(gt, true, false, keep_prob, seed, offset, flags);
-  }
-  gt.splits = gemm_pick_splits(R, Kp, C); if (gt.splits > 8) gt.splits = 8;
-  gt.ws = reinterpret_cast<float*>(reinterpret_cast<char*>(gws) + pl.gemm_half);
-  // Z | T: same shape when the attention input has C channels too -- one launch (GemmDesc::twin), else one after
-  // the other (the dispatcher decides)
-  gz.twin = &gt;
-  if (tr) { gz.trace = &tr->g_z; gt.trace = &tr->g_t; tr->t_drop_a = gt.drop_a; }
-  int rc = gemm_launch(gz, st);
-  if (rc != APA_OK) return rc;
-  if (tr) { tr->fwd_act = dtype == APA_DTYPE_F32 ? PC_ACT_F32 : PC_ACT_BF16; tr->logits = PC_LOGITS_FWD_ACT; }
-  dim3 grid(N, (K + 63) / 64);
-  if (dtype == APA_DTYPE_F32)
-    hipLaunchKernelGGL(pc_fwd_act_kernel<float>, grid, dim3(64 * PC_PG), 0, st, Z, Kp, Tsave, att, logits,
-                       static_cast<float*>(topdown), P, K, act_code(flags), PcXent{nullptr, nullptr, nullptr, 0.f});
-  else
-    hipLaunchKernelGGL(pc_fwd_act_kernel<bf16_t>, grid, dim3(64 * PC_PG), 0, st, Z, Kp, Tsave, att, logits,
-                       static_cast<bf16_t*>(topdown), P, K, act_code(flags), PcXent{nullptr, nullptr, nullptr, 0.f});
-  APA_LAUNCH_CHECK("pc_fwd_act_kernel");
-  // one-call train step: the cross-entropy of the logits row is taken by the backward activation pass (one launch
-  // less); the batch mean rides on the column-sum launch that ends the backward half
-  if (xf && xf->labels && xf->G && xf->loss && !xf->probs && K >= 4 && K <= 1024) {
-    xf->done = true;
-    xf->deferred = true;
-    xf->logits = logits;
-  }
-  return APA_OK;   // (PcTrace::xent of a deferred cross-entropy: recorded where it is taken, in pc_backward)
-}
-
-int pc_backward(const void* X, const void* Xatt, const float* Wa, const float* Wt, const float* att,
-                const float* Tsave, const float* G, void* dX, void* dXatt, float* dWa, float* dba,
-                float* dWt, float* dbt, void* ws, int N, int P, int C, int Ca, int K,
-                unsigned flags, float keep_prob, uint64_t seed, uint64_t offset, int dtype,
-                hipStream_t st, const M1Xent* xf) {
-  const PcPlan pl = pc_plan(N, P, C, Ca, K, dtype);
-  char* w = static_cast<char*>(ws);
-  const bool cat = pc_cat(X, C, Ca, dtype);
-  const int ldw = cat ? 2 * pl.Kp : pl.Kp;      // row stride of the padded weights and of [dT | dZ]
-  void* WtP = w + pl.off_wtp;
-  void* WaP = cat ? static_cast<void*>(static_cast<bf16_t*>(WtP) + pl.Kp) : static_cast<void*>(w + pl.off_wap);
-  void* dT = w + pl.off_dt;
-  void* dZ = cat ? static_cast<void*>(static_cast<bf16_t*>(dT) + pl.Kp) : static_cast<void*>(w + pl.off_dz);
-  float* pdbt = reinterpret_cast<float*>(w + pl.off_pdbt);
-  float* pdba = reinterpret_cast<float*>(w + pl.off_pdba);
-  float* gws = reinterpret_cast<float*>(w + pl.off_gemm);
-  const int Kp = pl.Kp, R = (int)pl.R;
-  const bool train = (flags & APA_FLAG_TRAIN) && keep_prob < 1.0f;
-  const bool fused = (Xatt == X);
-  const int tdt = dt_code(dtype);
-  const bool wb16 = dtype == APA_DTYPE_BF16;
-  PcTrace* tr = pc_trace();
-  if (tr) tr->phase = 2;
-  if (pc_fused_supported(N, P, C, Ca, K, dtype, X, Xatt) && !rng_external(flags)) {
-    if (tr) tr->path_bwd = PC_PATH_FUSED;
-    const PcFusedWs f = pc_fused_carve(w + pl.off_fused, N, P, C);
-    int rc = APA_OK;
-    const bool devctr = flags & APA_FLAG_RNG_DEVICE;
-    const uint64_t off = devctr ? 0 : offset;
-    const uint64_t* offd = devctr ? reinterpret_cast<const uint64_t*>(static_cast<uintptr_t>(offset)) : nullptr;
-    // APA_FLAG_RNG_DEVICE: this call advances the dropout counter when it is done (include/apa.h) -- in the launch
-    // after the last reader of the counter (the mask bits are regenerated at most here, right below)
-    uint64_t* bump = (train && devctr) ? reinterpret_cast<uint64_t*>(static_cast<uintptr_t>(offset)) : nullptr;
-    if (!(flags & APA_FLAG_WS_FROM_FWD)) {   // else the forward call left the operands and the mask bits in place
-      const PcPrepBits pb = {(size_t)R * C, keep_prob, seed, off, offd};
-      rc = pc_fused_prep(f, Wa, Wt, nullptr, nullptr, C, K, st, train ? &pb : nullptr,
-                         !(flags & APA_FLAG_WEIGHT_IMAGES));
-      if (rc != APA_OK) return rc;
-    }
-    if (pc_fused_dx_supported(P, act_code(flags))) {
-      // identity / relu attention: ONE write-bound kernel forms [dT | dZ] from att / T / G in registers, writes dX,
-      // leaves [dT | dZ] and the dbt | dba block partials behind for the dW launch and its reduce tail
-      const int rbs = pc_fused_dx_rows(R);
-      rc = pc_fused_dx(f, G, att, Tsave, dX, pdbt, R, C, K, P, act_code(flags), train, keep_prob,
-                       (xf && xf->deferred) ? xf : nullptr, st);
-      if (rc != APA_OK) return rc;
-      PcDwTail tail = {pdbt, dbt, dba, rbs, bump, nullptr, 0, 0.f, nullptr};
-      if (xf && xf->done) { tail.aux_src = xf->loss + 1; tail.aux_n = -N; tail.aux_scale = xf->lscale; tail.aux_dst = xf->loss; }
-      // the same condition as pc_forward's `tagged` (WS_FROM_FWD is set by the library's own train step only): this
-      // launch is the step's last -- it also leaves the NEXT step's keep bits behind, tagged (seed, offset + 1)
-      if (train && (flags & APA_FLAG_WEIGHT_IMAGES) && (flags & APA_FLAG_WS_FROM_FWD)) {
-        tail.next_bits = true;
-        tail.next_seed = seed;
-      }
-      return pc_fused_dw(f, X, dWt, dWa, R, C, K, train, keep_prob, st, &tail);
-    }
-    bf16_t* dTc = static_cast<bf16_t*>(f.dTdZ);              // [R][dT (64) | dZ (64)]
-    const int ps = pc_bwd_act_psplit(N, (Kp + 63) / 64, P, act_code(flags));
-    dim3 grid(N, (Kp + 63) / 64, ps);
-    const PcDefer df = {{nullptr, nullptr, nullptr, 0.f}, nullptr};   // (a deferred cross-entropy only goes with the dX kernel above)
-    hipLaunchKernelGGL(pc_bwd_act_kernel<bf16_t>, grid, dim3(64 * PC_PG), 0, st, G, att, Tsave, dTc, dTc + 64,
-                       pdbt, pdba, P, K, Kp, act_code(flags), 128, df);
-    APA_LAUNCH_CHECK("pc_bwd_act_kernel");
-    if (tr) { tr->bwd_act = PC_ACT_BF16; tr->ps = ps; tr->ldg = 128; tr->dx = train ? PC_DX_MID_GEMM : PC_DX_PLAIN_GEMM; }
-    // dbt | dba (column sums of the activation pass's block partials), the batch mean of a folded cross-entropy
-    // and the dropout counter ride on the tail blocks of the dW reduce launch
-    PcDwTail tail = {pdbt, dbt, dba, N * ps, bump, nullptr, 0, 0.f, nullptr};
-    // (aux_n < 0: the batch mean in apa_softmax_xent_fwd_bwd's own summation order -- bit-identical loss[0])
-    if (xf && xf->done) { tail.aux_src = xf->loss + 1; tail.aux_n = -N; tail.aux_scale = xf->lscale; tail.aux_dst = xf->loss; }
-    if (train && (flags & APA_FLAG_WEIGHT_IMAGES) && (flags & APA_FLAG_WS_FROM_FWD)) {
-      tail.next_bits = true;      // (see the identity / relu branch above)
-      tail.next_seed = seed;
-    }
-    // dX = (dT . Wt^T) * mask/keep + dZ . Wa^T: one launch over the concatenated k = 128.  (Round 5: BEFORE the dW
-    // launches -- the reduce tail that ends them may overwrite the keep-bit map with the next step's.)
-    if (train) {
-      rc = gemm_bf16_mid_dropout(f.dTdZ, 128, f.Wcat2, 128, dX, C, R, C, 128, 1.0f / keep_prob, f.maskbits, st);
-    } else {
-      GemmDesc g;
-      g.A = f.dTdZ; g.lda = 128; g.ta = 1; g.a_kc = true;
-      g.B = f.Wcat2; g.ldb = 128; g.tb = 1; g.b_kc = true;
-      g.C = dX; g.ldc = C; g.tc = 1;
-      g.M = R; g.N = C; g.K = 128;
-      if (tr) g.trace = &tr->g_dx;
-      rc = gemm_launch(g, st);
-    }
-    if (rc != APA_OK) return rc;
-    return pc_fused_dw(f, X, dWt, dWa, R, C, K, train, keep_prob, st, &tail);
-  }
-  // APA_FLAG_WS_FROM_FWD (one-call train step): the forward call's padded bf16 weights and its materialised
-  // dropout(X) are still in the workspace -- the second pc_pad / pc_dropout launch (7.9 + 8.4 us at K = 393) is
-  // skipped.  Only the all-bf16 DMA route prepares both operands in the forward pass.
-  const bool fast_bf16 = dtype == APA_DTYPE_BF16 && C % 8 == 0 && (reinterpret_cast<uintptr_t>(X) & 15) == 0;
-  const bool reuse_fwd = (flags & APA_FLAG_WS_FROM_FWD) && fast_bf16;
-  if (tr) {
-    tr->path_bwd = PC_PATH_GENERIC; tr->cat = cat ? 1 : 0; tr->fast = fast_bf16 ? 1 : 0; tr->reuse_fwd = reuse_fwd ? 1 : 0;
-  }
-  if (!reuse_fwd) {
-    PcPadList pads;
-    if (!(flags & APA_FLAG_WEIGHT_IMAGES)) {
-      pads.add(Wa, WaP, Ca, Kp, wb16, ldw);
-      pads.add(Wt, WtP, C, Kp, wb16, ldw);
-    }
-    if (fast_bf16 && train) {   // + dropout(X) for the dWt product (and its keep bits), same launch
-      const PcDropArgs dr = pc_drop_args(X, w + pl.off_xd, pl.R, C, keep_prob, seed, offset, flags,
-                                         reinterpret_cast<uint8_t*>(w + pl.off_bits));
-      pads.launch(K, Kp, st, &dr);
-    } else {
-      pads.launch(K, Kp, st);
-    }
-    APA_LAUNCH_CHECK("pc_pad_kernel");
-  }
-  const int ps = pc_bwd_act_psplit(N, (Kp + 63) / 64, P, act_code(flags));
-  dim3 grid(N, (Kp + 63) / 64, ps);
-  PcDefer df = {{nullptr, nullptr, nullptr, 0.f}, nullptr};
-  if (xf && xf->deferred) {
-    df.row_logits = xf->logits;
-    df.xe.labels = xf->labels; df.xe.loss = xf->loss; df.xe.G = xf->G; df.xe.gscale = xf->gscale;
-  }
-  if (dtype == APA_DTYPE_F32)
-    hipLaunchKernelGGL(pc_bwd_act_kernel<float>, grid, dim3(64 * PC_PG), 0, st, G, att, Tsave,
-                       static_cast<float*>(dT), static_cast<float*>(dZ), pdbt, pdba, P, K, Kp,
-                       act_code(flags), Kp, df);
-  else
-    hipLaunchKernelGGL(pc_bwd_act_kernel<bf16_t>, grid, dim3(64 * PC_PG), 0, st, G, att, Tsave,
-                       static_cast<bf16_t*>(dT), static_cast<bf16_t*>(dZ), pdbt, pdba, P, K, Kp,
-                       act_code(flags), ldw, df);
-  APA_LAUNCH_CHECK("pc_bwd_act_kernel");
-  if (tr) {
-    tr->bwd_act = dtype == APA_DTYPE_F32 ? PC_ACT_F32 : PC_ACT_BF16; tr->ps = ps; tr->ldg = dtype == APA_DTYPE_F32 ? Kp : ldw;
-    if (df.row_logits) tr->xent = PC_XENT_BWD_ACT;
-  }
-  int rc = APA_OK;
-  {  // dWt[c,k] = sum_r Xt[r,c] dT[r,k]
-    GemmDesc g;
-    g.A = X; g.lda = C; g.ta = tdt; g.a_kc = false;
-    g.B = dT; g.ldb = ldw; g.tb = tdt; g.b_kc = false;
-    g.C = dWt; g.ldc = K; g.tc = 0;
-    g.M = C; g.N = K; g.K = R;
-    g.splits = gemm_pick_splits(C, K, R); g.ws = gws;
-    const bool fast = dtype == APA_DTYPE_BF16 && C % 8 == 0 && (reinterpret_cast<uintptr_t>(X) & 15) == 0;
-    if (fast) {
-      g.N = Kp; g.n_valid = K;   // dT is [R][Kp] with zero pad columns
-      if (train) g.A = w + pl.off_xd;   // (from the forward call, or from the padding launch above)
-    } else if (train) {
-      set_dropout(g, true, false, keep_prob, seed, offset, flags);
-      // dropout index of A(m=c, k=r) is r*C + c: the stager computes row*Ktot + k with row = m, so
-      // the transposed operand needs the swapped form -> handled by drop_a == 2
-      g.drop_a = 2;
-    }
-    // dWa[c,k] = sum_r Xatt[r,c] dZ[r,k]: the twin of the same launch when the shapes agree (Ca == C, bf16)
-    GemmDesc h;
-    h.A = Xatt; h.lda = Ca; h.ta = tdt; h.a_kc = false;
-    h.B = dZ; h.ldb = ldw; h.tb = tdt; h.b_kc = false;
-    h.C = dWa; h.ldc = K; h.tc = 0;
-    h.M = Ca; h.N = K; h.K = R;
-    h.splits = gemm_pick_splits(Ca, K, R);
-    h.ws = reinterpret_cast<float*>(reinterpret_cast<char*>(gws) + pl.gemm_half);
-    if (dtype == APA_DTYPE_BF16) { h.N = Kp; h.n_valid = K; }   // dZ is [R][Kp] with zero pad columns
-    g.twin = &h;
-    if (tr) { g.trace = &tr->g_dwt; h.trace = &tr->g_dwa; tr->dw = PC_DW_TWIN_GEMM; tr->dw_drop_a = g.drop_a; }
-    rc = gemm_launch(g, st);
-    if (rc != APA_OK) return rc;
-  }
-  bool dx_done = false;
-  // (the wide kernel's vector epilogue stores 16 bytes at a time: an odd dX address keeps the two-product form)
-  if (cat && fused && gemm_bf16_wide_serves(R, C, 2 * Kp) && (reinterpret_cast<uintptr_t>(dX) & 15) == 0) {
-    // dX = (dT . Wt^T) * mask/keep + dZ . Wa^T as ONE product over [dT | dZ] . [Wt | Wa]^T: the accumulators are
-    // masked with the keep bits after the first Kp of the contraction (gemm_bf16_wide_kernel<.., MID>)
-    GemmDesc g;
-    g.A = dT; g.lda = ldw; g.ta = 1; g.a_kc = true;
-    g.B = WtP; g.ldb = ldw; g.tb = 1; g.b_kc = true;
-    g.C = dX; g.ldc = C; g.tc = 1;
-    g.M = R; g.N = C; g.K = 2 * Kp;
-    g.stream_out = true;
-    if (train) {
-      g.mid_bits = reinterpret_cast<const uint8_t*>(w + pl.off_bits); g.mid_k = Kp; g.mid_inv_keep = 1.0f / keep_prob;
-    }
-    if (tr) { g.trace = &tr->g_dx; tr->dx = PC_DX_WIDE; tr->mid_bits = g.mid_bits ? 1 : 0; tr->wa_to = PC_WA_NONE; }
-    rc = gemm_launch(g, st);
-    if (rc != APA_OK) return rc;
-    dx_done = true;
-  }
-  if (!dx_done) {  // dX = (dT . Wt^T) * mask/keep
-    GemmDesc g;
-    g.A = dT; g.lda = ldw; g.ta = tdt; g.a_kc = true;
-    g.B = WtP; g.ldb = ldw; g.tb = wb16 ? 1 : 0; g.b_kc = true;
-    g.C = dX; g.ldc = C; g.tc = tdt;
-    g.M = R; g.N = C; g.K = Kp;
-    if (train) set_dropout(g, false, true, keep_prob, seed, offset, flags);
-    if (tr) { g.trace = &tr->g_dx; tr->dx = PC_DX_TWO; tr->dx_drop_c = g.drop_c; }
-    rc = gemm_launch(g, st);
-    if (rc != APA_OK) return rc;
-  }
-  if (!dx_done) {  // + dZ . Wa^T  (into dX when the attention input is X itself, else into dXatt)
-    GemmDesc g;
-    g.A = dZ; g.lda = ldw; g.ta = tdt; g.a_kc = true;
-    g.B = WaP; g.ldb = ldw; g.tb = wb16 ? 1 : 0; g.b_kc = true;
-    g.C = fused ? dX : dXatt; g.ldc = fused ? C : Ca; g.tc = tdt;
-    g.M = R; g.N = fused ? C : Ca; g.K = Kp; g.beta = fused ? 1.f : 0.f;
-    g.stream_out = true;
-    if (tr) { g.trace = &tr->g_dxa; tr->wa_to = fused ? PC_WA_DX_BETA1 : PC_WA_DXATT; }
-    rc = gemm_launch(g, st);
-    if (rc != APA_OK) return rc;
-  }
-  // dbt | dba: the LAST launch, so that it can also advance a device-side dropout counter (APA_FLAG_RNG_DEVICE)
-  // after every kernel that keys its mask with it has run
-  uint64_t* bump = (train && (flags & APA_FLAG_RNG_DEVICE))
-                       ? reinterpret_cast<uint64_t*>(static_cast<uintptr_t>(offset)) : nullptr;
-  ColsumMore more;
-  const bool mean = xf && xf->done;     // the batch mean of a cross-entropy taken inside this step (xent's own order)
-  if (mean) { more.aux_src = xf->loss + 1; more.aux_n = -N; more.aux_scale = xf->lscale; more.aux_dst = xf->loss; }
-  if (tr) { tr->tail = PC_TAIL_COLSUM; tr->tail_nrows = N * ps; tr->rng_bump = bump ? 1 : 0; tr->aux = mean ? 1 : 0; }
-  return m1_colsum(pdbt, nullptr, dbt, nullptr, N * ps, 2 * K, 2 * K, bump, st, dba, K, nullptr, 0, 0, 0,
-                   mean ? &more : nullptr);
-}
-
-}  // namespace apa

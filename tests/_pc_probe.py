@@ -136,7 +136,7 @@ PLAN_FIELDS = ('R', 'Kp', 'off_wap', 'off_wtp', 'off_bap', 'off_z', 'off_dt', 'o
 
 
 def plan(N, P, C, Ca, K, dtype):
-    """The workspace carve of csrc/apa_dense.hip pc_plan and, for its fused part, of pc_fused_carve (byte offsets from
+    """The workspace carve of csrc/apa_pc.hip pc_plan and, for its fused part, of pc_fused_carve (byte offsets from
     the workspace base)."""
     out = (ctypes.c_int64 * len(PLAN_FIELDS))()
     load_pc_probe().apa_probe_pc_plan(N, P, C, Ca, K, dtype, out)

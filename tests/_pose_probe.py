@@ -89,7 +89,7 @@ PLAN_FIELDS = ('R', 'nchunks', 'off_dppre', 'off_partial', 'off_gemm', 'off_w1b'
 
 
 def plan(N, P, C, Cp, J, dtype):
-    """The workspace carve of csrc/apa_dense.hip pose_plan (byte offsets)."""
+    """The workspace carve of csrc/apa_pose_head.hip pose_plan (byte offsets)."""
     out = (ctypes.c_int64 * 8)()
     load_pose_probe().apa_probe_pose_plan(N, P, C, Cp, J, dtype, out)
     return dict(zip(PLAN_FIELDS, (int(v) for v in out)))

@@ -132,7 +132,7 @@ class Problem:
         A = self.Aval.float()
         if c.get('drop_a') == 1:
             A = A * (self.mask.view(M, K).float() * self.inv_keep)
-        elif c.get('drop_a') == 2:    # transposed flat index k * M + m (the dWt product of apa_dense.hip)
+        elif c.get('drop_a') == 2:    # transposed flat index k * M + m (the dWt product of apa_pc.hip)
             A = A * (self.mask.view(K, M).t().float() * self.inv_keep)
         B = self.Bval[:Nst].float()
         if bf:
@@ -258,7 +258,7 @@ def _cases():
           C('bf16_drop_c', _kinds('bf16'), M=1000, N=200, K=256, tb=0, tc=1, drop_c=1, bias=1),
           C('bf16_split_scalar_reduce', _kinds('bf16', split=5, reduce='scalar'), M=100, N=18, K=1000, tb=0,
             b_kc=True, splits=5, bias=1),
-          # apa_dense.hip pose fwd g2: Pl = Ppre . W2 + b2 (N = 16) and pose bwd dW2 = Ppre^T dPl
+          # apa_pose_head.hip pose fwd g2: Pl = Ppre . W2 + b2 (N = 16) and pose bwd dW2 = Ppre^T dPl
           C('pose_fwd_g2_shipped', _kinds('bf16', split=6, reduce='vec'), M=6272, N=16, K=768, tb=0, bias=1,
             splits=6, pad=0),
           C('pose_fwd_g2_ragged', _kinds('bf16', split=6, reduce='vec'), M=5983, N=16, K=768, tb=0, bias=1,
@@ -428,7 +428,7 @@ TAIL = [('pose_bwd_dw1_tail_shipped', (2048, 768, 6272), 196, 196),
 
 @pytest.mark.parametrize('case', TAIL, ids=[t[0] for t in TAIL])
 def test_reduce_tail_colsum_is_m1_colsum_bit_for_bit(gpu, case):
-    """Pose bwd dW1 + its tail job as apa_dense.hip builds it: [dW2 | db1 | db2 | dWa | dba] partial rows routed to
+    """Pose bwd dW1 + its tail job as apa_pose_head.hip builds it: [dW2 | db1 | db2 | dWa | dba] partial rows routed to
     five outputs, the aux sum and the RNG counter bump.  The tail blocks of the split-K reduce give the same bits
     as a standalone m1_colsum of the same partials, and the GEMM output equals the plain vector reduce."""
     name, (M, N, K), nblk, aux_n = case

@@ -260,13 +260,12 @@ def test_pose_gpu_case_table_covers_every_reachable_trace_value():
 
 
 def test_pose_head_launches_no_instance_outside_the_case_table():
-    """Part A of apa_dense.hip launches pose_pl_kernel<8|16|24|32, FUSED, W2T>, pose_bwd_rows_mfma_kernel<R1, WA> in
+    """apa_pose_head.hip launches pose_pl_kernel<8|16|24|32, FUSED, W2T>, pose_bwd_rows_mfma_kernel<R1, WA> in
     the three forms (false, false), (true, false), (true, true), pose_bwd_rows_kernel<T, R1, EXT, RPB, WA> and
     pose_dppre_kernel<T, JM, R1> -- each arm is a `need` entry of the coverage test above.  The fp32 WA form of the
     rows kernel had no caller (the fused outputs need bf16 features: pose_step_fast_ok) and is gone."""
     import re
-    src = open(os.path.join(os.path.dirname(cof.LIB_PATH), '..', 'csrc', 'apa_dense.hip')).read()
-    part_a = src[:src.index('// B. Per-class bottom-up maps')]
+    part_a = open(os.path.join(os.path.dirname(cof.LIB_PATH), '..', 'csrc', 'apa_pose_head.hip')).read()
     arms = re.findall(r'APA_ROWS\((float|bf16_t), (true|false), (true|false), (true|false)\);', part_a)
     assert sorted(arms) == sorted([('float', 'true', 'false', 'false'), ('float', 'false', 'true', 'false'),
                                    ('float', 'false', 'false', 'false'), ('bf16_t', 'true', 'false', 'true'),
@@ -472,7 +471,7 @@ def test_pc_gpu_case_table_covers_every_reachable_trace_value():
 
 
 def test_per_class_launches_no_instance_outside_the_case_table():
-    """Part B of apa_dense.hip and apa_pc_fused.hip launch pc_fwd_zt_dma_kernel<TRAIN, FOLD> (four arms),
+    """apa_pc.hip and apa_pc_fused.hip launch pc_fwd_zt_dma_kernel<TRAIN, FOLD> (four arms),
     pc_bwd_dx_kernel<TRAIN>, pc_bwd_dw_kernel<TRAIN>, pc_fwd_act_kernel / pc_bwd_act_kernel for float and bf16_t, and the
     untemplated pc_prep / pc_pad / pc_logits_finish / pc_dw_reduce kernels -- each arm is a `need` entry of the coverage
     test above.  pc_fused_forward's own `C % ZB_KT` refusal had no caller behind pc_fused_supported (C % 256 == 0) and
@@ -482,8 +481,7 @@ def test_per_class_launches_no_instance_outside_the_case_table():
     import re
     here = os.path.join(os.path.dirname(cof.LIB_PATH), '..', 'csrc')
     fused = open(os.path.join(here, 'apa_pc_fused.hip')).read()
-    dense = open(os.path.join(here, 'apa_dense.hip')).read()
-    part_b = dense[dense.index('// B. Per-class bottom-up maps'):]
+    part_b = open(os.path.join(here, 'apa_pc.hip')).read()
     assert re.findall(r'APA_ZT\((true|false), (true|false)\);', fused) == [
         ('true', 'true'), ('false', 'true'), ('true', 'false'), ('false', 'false')]
     assert re.findall(r'APA_DX\((true|false)\);', fused) == ['true', 'false']
@@ -495,8 +493,7 @@ def test_per_class_launches_no_instance_outside_the_case_table():
     launches = re.findall(r'hipLaunchKernelGGL\(\(?(pc_\w+?)(?:<(\w+)>)?[,)]', part_b)
     assert sorted(launches) == sorted(
         [('pc_pad_kernel', ''), ('pc_fwd_act_kernel', 'bf16_t'), ('pc_fwd_act_kernel', 'float'),
-         ('pc_fwd_act_kernel', 'bf16_t'), ('pc_bwd_act_kernel', 'bf16_t'), ('pc_bwd_act_kernel', 'float'),
-         ('pc_bwd_act_kernel', 'bf16_t')]), launches
+         ('pc_bwd_act_kernel', 'bf16_t'), ('pc_bwd_act_kernel', 'float')]), launches   # one site per (kernel, type)
     # the table reaches both element types of both activation kernels, on both paths where they exist
     reached, _ = _pc_reached()
     for need in (('fwd_act', 'fused', 'bf16'), ('fwd_act', 'generic', 'bf16'), ('fwd_act', 'generic', 'f32'),

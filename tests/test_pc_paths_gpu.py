@@ -1,4 +1,4 @@
-"""Every path of the per-class maps (M == K: part B of csrc/apa_dense.hip and csrc/apa_pc_fused.hip) against float64,
+"""Every path of the per-class maps (M == K: csrc/apa_pc.hip and csrc/apa_pc_fused.hip) against float64,
 stage by stage.
 
 Each case runs the product's entry points through the test-only probe library (tests/_pc_probe.py), asserts the traced
@@ -62,7 +62,7 @@ def case(name, N, P, C, K, *, Ca=None, dt=BF16, act='id', train=False, keep=0.5,
 
 
 def expected(c):
-    """The trace of a case, transcribed from the dispatch conditions of pc_forward / pc_backward (apa_dense.hip) and
+    """The trace of a case, transcribed from the dispatch conditions of pc_forward / pc_backward (apa_pc.hip) and
     the pc_fused_* host functions (apa_pc_fused.hip) -- not read back from a run."""
     N, P, C, K, dt, act = c['N'], c['P'], c['C'], c['K'], c['dt'], ACT_CODE[c['act']]
     Ca = C if c['Ca'] is None else c['Ca']

@@ -1,4 +1,4 @@
-"""Every path of the PoseLogits head (csrc/apa_dense.hip, part A) against float64, stage by stage.
+"""Every path of the PoseLogits head (csrc/apa_pose_head.hip) against float64, stage by stage.
 
 Each case runs the product's entry points through the test-only probe library (tests/_pose_probe.py), asserts the
 traced dispatch (W1 operand, Pl kernel and instance, backward rows family with its block shape, gradient form,
@@ -51,7 +51,7 @@ def case(name, N, P, C, Cp, J, *, dt=BF16, form='plain', dpl=True, entry='sep', 
                 mis=dict(mis), images=tuple(images), train=train, expect=expect)
 
 
-# Expected traces are read off the dispatch conditions of apa_dense.hip (pose_pl_fast / pose_pl_launch,
+# Expected traces are read off the dispatch conditions of apa_pose_head.hip (pose_pl_fast / pose_pl_launch,
 # pose_rows_mfma_ok, pose_bwd_rows_ok, pose_rows_lds / pose_rows_per_block, pose_head_bwd_impl, pose_w1_operand,
 # pose_dw1_splits + gemm_launch's tail rule) -- not off a run.
 #   mfma:  bf16, dPl, J = 16, Cp % 128 = 0, 256 <= Cp <= 1024, 16-byte aligned, no dense ext;  nw = Cp / 64,
