@@ -75,6 +75,10 @@ _SIGNATURES = {
     'apa_pose_label_replay_resize': (c_int, [POINTER(c_uint8)] + [c_int] * 11 + [c_float, POINTER(c_float)]),
     'apa_pose_labels_device': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_int,
                                        c_void_p, c_void_p, c_void_p, c_void_p]),
+    'apa_image_aug_size': (c_int, [c_int] * 4 + [POINTER(ctypes.c_int32)]),
+    'apa_preprocess_images_workspace_bytes': (c_size_t, [c_int, c_int, POINTER(ctypes.c_int32), c_int]),
+    'apa_preprocess_images': (c_int, [c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float,
+                                      c_void_p, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
     'apa_frame_pool_fwd': (c_int, [c_void_p] * 5 + [c_int] * 3 + [c_void_p]),
     'apa_frame_pool_bwd': (c_int, [c_void_p] * 8 + [c_int] * 3 + [c_void_p]),
     'apa_attn_head_train_step': (c_int, [c_void_p] * 7 + [c_float, c_float] + [c_void_p] * 13 +
@@ -829,6 +833,76 @@ def pose_labels_device(poses, geoms, out_wd=200, J=16, marker_wd_ratio=0.1, out_
                                       labels.data_ptr(), valid.data_ptr(), status.data_ptr(), _stream_ptr()),
            'apa_pose_labels_device')
     return labels, valid.bool(), status
+
+
+def _geom_rows(geoms):
+    g9 = []
+    for g in geoms:
+        g = [int(v) for v in g]
+        if len(g) != 9:
+            raise ValueError('geom needs 9 integers, got {}'.format(len(g)))
+        g9.append(g)
+    return g9
+
+
+def image_aug_size(src_ht: int, src_wd: int, max_wd: int, resize_side: int) -> Tuple[int, int, int, int]:
+    """(lh, lw, ah, aw): the size after `_resize_if_needed` (src/preprocess_pipeline.py:5-18, limit max_wd =
+    cfg.MAX_INPUT_IMAGE_SIZE) and after the aspect-preserving resize to resize_side (vgg_preprocessing.py:241-294),
+    by the reference's float32 rules.  Host function."""
+    out = (ctypes.c_int32 * 4)()
+    _check(load_library().apa_image_aug_size(int(src_ht), int(src_wd), int(max_wd), int(resize_side), out),
+           'apa_image_aug_size')
+    return tuple(int(v) for v in out)
+
+
+def preprocess_images(frames, geoms, max_wd, out_dtype=torch.float32, device='cuda', mean=128.0, out=None):
+    """The image half of the input pipeline for a batch on the device (include/apa.h: apa_preprocess_images):
+    limit to max_wd, aspect-preserving resize, crop, flip, - mean, straight into the network's NHWC input.
+    frames: list of uint8 arrays [T,h,w,3] (or [h,w,3] when T == 1), any sizes, the same T; geoms: list of
+    (im_ht, im_wd, aug_ht, aug_wd, crop_y, crop_x, crop_h, crop_w, flip), the rows pose_labels_device takes, all
+    with one crop size.  Returns (images [N,T,crop_h,crop_w,3] `out_dtype` device, status int32 [N] device);
+    `out=`: write into this buffer."""
+    lib = load_library()
+    N = len(frames)
+    if N == 0 or len(geoms) != N:
+        raise ValueError('preprocess_images: {} samples, {} geometry rows'.format(N, len(geoms)))
+    arrs = []
+    for f in frames:
+        a = np.asarray(f)
+        if a.dtype != np.uint8 or a.ndim not in (3, 4) or a.shape[-1] != 3:
+            raise ValueError('frames must be uint8 [T,h,w,3] or [h,w,3], got {} {}'.format(a.dtype, a.shape))
+        arrs.append(np.ascontiguousarray(a if a.ndim == 4 else a[None]))
+    T = arrs[0].shape[0]
+    if any(a.shape[0] != T for a in arrs):
+        raise ValueError('every sample of a call needs the same number of frames')
+    g9 = _geom_rows(geoms)
+    crop_h, crop_w = g9[0][6], g9[0][7]
+    if crop_h <= 0 or crop_w <= 0 or any(g[6:8] != [crop_h, crop_w] for g in g9):
+        raise ValueError('every sample of a call needs the same positive crop size')
+    if out_dtype not in (torch.float32, torch.bfloat16):
+        raise ApaError('images are produced as float32 or bfloat16, got {}'.format(out_dtype))
+    # one packed buffer: sample n starts at byte off[n] (no alignment is asked for)
+    off = np.zeros((N,), dtype=np.int64)
+    off[1:] = np.cumsum([a.size for a in arrs[:-1]])
+    packed = np.concatenate([a.reshape(-1) for a in arrs])
+    hw = np.asarray([a.shape[1:3] for a in arrs], dtype=np.int32)
+    dev = torch.device(device)
+    src_d = torch.from_numpy(packed).to(dev)
+    off_d = torch.from_numpy(off).to(dev)
+    hw_d = torch.from_numpy(hw).to(dev)
+    geom_d = torch.tensor(g9, dtype=torch.int32, device=dev)
+    if out is None:
+        out = torch.empty((N, T, crop_h, crop_w, 3), dtype=out_dtype, device=dev)
+    elif out.dtype != out_dtype or out.numel() != N * T * crop_h * crop_w * 3:
+        raise ApaError('preprocess_images: out must be {} with {} elements'.format(out_dtype, N * T * crop_h * crop_w * 3))
+    status = torch.empty((N,), dtype=torch.int32, device=dev)
+    need = int(lib.apa_preprocess_images_workspace_bytes(N, T, hw.ctypes.data_as(POINTER(ctypes.c_int32)), int(max_wd)))
+    ws = torch.empty((max(need, 16),), dtype=torch.uint8, device=dev)
+    _check(lib.apa_preprocess_images(_dev_ptr(src_d, 'frames'), src_d.numel(), off_d.data_ptr(), hw_d.data_ptr(),
+                                     geom_d.data_ptr(), N, T, int(max_wd), float(mean), _dev_ptr(out, 'out'),
+                                     _feat_dtype(out), status.data_ptr(), ws.data_ptr(), ws.numel(), _stream_ptr()),
+           'apa_preprocess_images')
+    return out.view(N, T, crop_h, crop_w, 3), status
 
 
 def frame_pool_fwd(logits, frames_per_video, w=None, b=None):

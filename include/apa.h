@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define APA_VERSION 302 /* major*10000 + minor*100 + patch */
+#define APA_VERSION 303 /* major*10000 + minor*100 + patch */
 
 typedef enum apa_status {
   APA_OK = 0,
@@ -408,6 +408,44 @@ int apa_pose_label_replay_resize(const uint8_t* hm_host, int h, int w, int J, in
 int apa_pose_labels_device(const int64_t* pose, const int32_t* n_vals, const int32_t* geom, int N,
                            int max_vals, int out_wd, int J, float marker_wd_ratio, int out_side,
                            float* labels, uint8_t* valid, int32_t* status, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * The IMAGE half of the input pipeline (src/preprocess_pipeline.py:5-18 `_resize_if_needed` +
+ * models/slim/preprocessing/vgg_preprocessing.py `preprocess_image`, the preprocessing of resnet_v1_*,
+ * vgg_* and inception_v2_tsn), all arithmetic in float32 as the reference's graph:
+ *   1. limit   src wider than max_wd (cfg.MAX_INPUT_IMAGE_SIZE): lw = max_wd, lh = (int64)(f32(sh) *
+ *              (f32(max_wd) / f32(sw))), L = uint8(trunc(legacy bilinear resize of src to [lh, lw])); else L = src
+ *   2. resize  scale = f32(side) / f32(lh > lw ? lw : lh), ah = (int32)(f32(lh) * scale), aw likewise;
+ *              A = legacy bilinear resize of L to [ah, aw], float32 (ah / aw may land one short of side)
+ *   3. crop    [crop_y, crop_y + crop_h) x [crop_x, crop_x + crop_w) of A   4. flip left-right   5. - mean
+ * The legacy bilinear rule is the one of apa_resize_bilinear_tf1.
+ *
+ * HOST function: lh, lw, ah, aw of steps 1-2 -> out[0..3].  APA_ERR_INVALID_ARG for non-positive arguments or
+ * an empty result. */
+int apa_image_aug_size(int src_ht, int src_wd, int max_wd, int resize_side, int32_t out[4]);
+
+/* Workspace of apa_preprocess_images for N samples of T frames whose sizes are src_hw_host int32 [N][2]
+ * (HOST memory): N equal slots, each holding the largest L image of the batch.  0 for invalid arguments. */
+size_t apa_preprocess_images_workspace_bytes(int N, int T, const int32_t* src_hw_host, int max_wd);
+
+/* Steps 1-5 for a whole batch on the device: two launches on `stream`, no synchronisation.
+ *   src      uint8, ONE packed device buffer of src_bytes bytes; the T frames [T, sh, sw, 3] of sample n start
+ *            at byte src_off[n] (int64 [N], any byte offset) and share one geometry (:182-194)
+ *   src_hw   int32 [N][2] = sh, sw (device)
+ *   geom     int32 [N][9], the record apa_pose_labels_device consumes (device): im_ht, im_wd = the ORIGINAL
+ *            size stored with the sample (the keypoint frame; never the limited size; only checked > 0 here),
+ *            aug_ht, aug_wd = ah, aw, then crop_y, crop_x, crop_h, crop_w, flip
+ *   out      [N, T, crop_h, crop_w, 3] f32 or bf16 (out_dtype; bf16 = the f32 result rounded to nearest even).
+ *            Every sample must carry the crop_h x crop_w of sample 0: `out` has N * T * crop_h * crop_w * 3
+ *            elements of THAT size, and nothing outside it is written whatever geom holds.
+ *   status   int32 [N]: 0 = ok; 1 = the reference would have failed or the sample cannot be served, and its
+ *            output is all zero: crop outside A or of another size than sample 0's, non-positive sizes, aug_ht x
+ *            aug_wd not what step 2 gives for any resize side, frames reaching past src_bytes, L larger than a
+ *            workspace slot.  (Sample 0 without a positive crop size: every status is 1, `out` is untouched.)
+ *   ws       apa_preprocess_images_workspace_bytes() bytes (at least 16 * N, else APA_ERR_WORKSPACE) */
+int apa_preprocess_images(const uint8_t* src, size_t src_bytes, const int64_t* src_off, const int32_t* src_hw,
+                          const int32_t* geom, int N, int T, int max_wd, float mean, void* out, int out_dtype,
+                          int32_t* status, void* ws, size_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Video frame pooling of per-frame logits, nets_factory.py:354-374.  logits f32 [B*F, K] (F
