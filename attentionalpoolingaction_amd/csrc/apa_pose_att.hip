@@ -480,9 +480,10 @@ PalPlan pal_plan(int N, int P, int C, int M, int K) {
   return p;
 }
 
-int pal_check(const char* fn, const void* X, const float* Pl, const int32_t* sel, int n_sel, int avged,
-              const float* W, const void* ws, int N, int P, int C, int J, int K, unsigned flags, float keep_prob,
-              uint64_t seed, int dtype, PalMaps* mp) {
+// dX: the backward call's gradient buffer (stored with X's vector width); NULL in the forward call
+int pal_check(const char* fn, const void* X, const void* dX, const float* Pl, const int32_t* sel, int n_sel,
+              int avged, const float* W, const void* ws, int N, int P, int C, int J, int K, unsigned flags,
+              float keep_prob, uint64_t seed, int dtype, PalMaps* mp) {
   if (!X || !Pl || !W || !ws || (n_sel > 0 && !sel)) {
     set_error("%s: null pointer", fn);
     return APA_ERR_INVALID_ARG;
@@ -520,6 +521,14 @@ int pal_check(const char* fn, const void* X, const float* Pl, const int32_t* sel
     set_error("%s: X must be %d-byte aligned", fn, (int)align + 1);
     return APA_ERR_UNSUPPORTED;
   }
+  if (dX && (reinterpret_cast<uintptr_t>(dX) & align)) {
+    set_error("%s: dX must be %d-byte aligned, like X", fn, (int)align + 1);
+    return APA_ERR_UNSUPPORTED;
+  }
+  if (reinterpret_cast<uintptr_t>(ws) & 15) {             // dF is read from it as float4
+    set_error("%s: the workspace must be 16-byte aligned", fn);
+    return APA_ERR_UNSUPPORTED;
+  }
   mp->M = M; mp->nsel = n_sel; mp->avged = avged ? 1 : 0; mp->J = J;
   for (int i = 0; i < PAL_MAXM; ++i) mp->sel[i] = i < n_sel ? sel[i] : 0;
   return APA_OK;
@@ -554,7 +563,8 @@ extern "C" int apa_pose_att_logits_fwd_ex(const apa_hooks* hooks, const void* X,
     return APA_ERR_INVALID_ARG;
   }
   PalMaps mp;
-  int rc = pal_check(fn, X, Pl, sel, n_sel, avged, W, ws, N, P, C, J, K, flags, keep_prob, seed, dtype, &mp);
+  int rc = pal_check(fn, X, nullptr, Pl, sel, n_sel, avged, W, ws, N, P, C, J, K, flags, keep_prob, seed, dtype,
+                     &mp);
   if (rc != APA_OK) return rc;
   const PalPlan plan = pal_plan(N, P, C, mp.M, K);
   if (ws_bytes < plan.total) {
@@ -598,7 +608,7 @@ extern "C" int apa_pose_att_logits_bwd_ex(const apa_hooks* hooks, const void* X,
     return APA_ERR_INVALID_ARG;
   }
   PalMaps mp;
-  int rc = pal_check(fn, X, Pl, sel, n_sel, avged, W, ws, N, P, C, J, K, flags, keep_prob, seed, dtype, &mp);
+  int rc = pal_check(fn, X, dX, Pl, sel, n_sel, avged, W, ws, N, P, C, J, K, flags, keep_prob, seed, dtype, &mp);
   if (rc != APA_OK) return rc;
   const PalPlan plan = pal_plan(N, P, C, mp.M, K);
   if (ws_bytes < plan.total) {

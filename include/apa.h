@@ -196,8 +196,11 @@ int apa_pose_head_bwd_rank1ext(const void* X, const float* W1, const float* W2, 
  * flags: APA_FLAG_TRAIN, APA_FLAG_RNG_EXTERNAL (a bit image over the flat index of F).  The hashed mask is the one
  * apa_dropout_mask(N*M*C, keep_prob, seed, offset) returns: element n*(M*C) + m*C + c of F.
  * ws: apa_pose_att_logits_workspace_bytes(N, P, C, M, K) bytes; one buffer may serve both calls.
- * Built for M <= 32, C a multiple of 4, K <= 480 (else APA_ERR_UNSUPPORTED); X 16-byte (f32) / 8-byte (bf16)
- * aligned.  Every reduction is summed in a fixed order: identical calls give bit-identical results.
+ * Built for M <= 32, C a multiple of 4, K <= 480 (else APA_ERR_UNSUPPORTED).  Alignment, refused with
+ * APA_ERR_UNSUPPORTED before anything is launched: X -- and, in the backward call, dX, which is read and stored with
+ * the same vector width -- 16-byte (f32) / 8-byte (bf16) aligned; ws 16-byte aligned in both calls (dF is read from it
+ * four floats at a time).  Every other operand (Pl, W, b, F, G, logits, dPl, dW, db) needs its element's alignment only.
+ * Every reduction is summed in a fixed order: identical calls give bit-identical results.
  *
  * Backward (TF autodiff in the reference).  G = dLoss/dlogits [N,K] f32.
  *   dW [M*C,K], db [K] f32                       overwritten

@@ -12,7 +12,8 @@
   Separately, the new kernels given the pose head's own Pl are held to 2e-5 relative against the float64
   restatement (_pal_reference), which keeps their arithmetic apart from the pose head's bf16 rounding.
 * A fixed-seed random-shape sweep (odd P, N = 1, K = 1, M = 1 .. 18, C = 4 .. 2048), bit-identical repeats, and the
-  mask the kernels apply against apa_dropout_mask."""
+  mask the kernels apply against apa_dropout_mask.
+Kernel by kernel and stage by stage, workspace stages included: tests/test_pose_att_paths_gpu.py."""
 import numpy as np
 import pytest
 import torch
