@@ -168,8 +168,11 @@ static int attn_pool_fwd_impl(const Hooks& hk, const apa_concat_feat* catp, M1Xe
       set_error("apa_attn_pool_fwd: workspace too small (%zu < %zu)", ws_bytes, need);
       return APA_ERR_WORKSPACE;
     }
-    rc = m1_forward(X, Xatt, Wa, ba, Wt, bt, logits, att, zsave, abar, ws, N, P, C, Ca, K, flags,
-                    keep_prob, seed, offset, dtype, st, xf, hk, catp ? &cat : nullptr);
+    M1Call c;
+    rc = m1_call_fill(c, X, Xatt, nullptr, false, catp ? &cat : nullptr, hk, ws, N, P, C, Ca, K, flags, keep_prob, seed,
+                      offset, dtype, st);
+    if (rc != APA_OK) return rc;
+    rc = m1_forward(c, M1Fwd{X, Xatt, Wa, ba, Wt, bt, logits, att, zsave, abar}, xf);
     if (rc != APA_OK || !topdown) return rc;
     // end_points['TopDownAttention'] = dropout(X).Wt + bt  (nets_factory.py:296-309): the factorised
     // path never needs it; it is materialised only on request (eval.py --ept dumps) by one GEMM.
@@ -277,9 +280,11 @@ static int attn_pool_bwd_impl(const Hooks& hk, const apa_concat_feat* catp, cons
       set_error("apa_attn_pool_bwd: workspace too small (%zu < %zu)", ws_bytes, need);
       return APA_ERR_WORKSPACE;
     }
-    return m1_backward(X, Xatt, Wa, ba, Wt, bt, att, zsave, abar, G, dX, dXatt, dWa, dba, dWt, dbt,
-                       ws, N, P, C, Ca, K, flags, keep_prob, seed, offset, dtype, st, xf, hk,
-                       catp ? &cat : nullptr);
+    const M1Bwd io{X, Xatt, Wa, Wt, bt, att, zsave, abar, G, dX, dXatt, dWa, dba, dWt, dbt};
+    M1Call c;
+    rc = m1_call_fill(c, X, Xatt, &io, xf && xf->done, catp ? &cat : nullptr, hk, ws, N, P, C, Ca, K, flags, keep_prob,
+                      seed, offset, dtype, st);
+    return rc != APA_OK ? rc : m1_backward(c, io, xf);
   }
   if (!zsave) {
     set_error("apa_attn_pool_bwd: M==K needs zsave (the fp32 [N,P,K] top-down map from forward)");
@@ -430,10 +435,8 @@ extern "C" int apa_pose_attn_train_step(const apa_pose_attn_step_io* io, int N, 
   flags &= APA_PUBLIC_FLAGS & ~(APA_FLAG_WS_FROM_FWD | APA_FLAG_DXATT_RANK1);
   hipStream_t st = static_cast<hipStream_t>(stream);
   const bool train = (flags & APA_FLAG_TRAIN) && keep_prob < 1.0f;
-  const bool fast = pose_step_fast_ok(N, P, C, Cp, J, dtype, s.Ppre, s.W2, s.Wa) && m1_small_supported(C, K) &&
-                    m1_supported(C, Cp, dtype, false) &&
-                    ((reinterpret_cast<uintptr_t>(s.G) | reinterpret_cast<uintptr_t>(s.Wt) |
-                      reinterpret_cast<uintptr_t>(s.zsave)) & 15) == 0;
+  const bool fast = pose_step_fast_ok(N, P, C, Cp, J, dtype, s.Ppre, s.W2, s.Wa) && m1_supported(C, Cp, dtype, false) &&
+                    m1_small_route_ok(C, K, s.G, s.Wt, s.zsave);
   if (!fast) {
     // the same step as four calls (what a caller without this entry point runs)
     rc = apa_pose_head_fwd(s.X, s.W1, s.b1, s.W2, s.b2, s.Ppre, s.Pl, s.ws_pose, s.ws_pose_bytes, N, P, C, Cp, J,

@@ -5,6 +5,7 @@
 #include <stddef.h>
 #include <stdint.h>
 #include <stdlib.h>
+#include <type_traits>
 
 #include "../../include/apa.h"
 #include "apa_colsum.h"
@@ -256,64 +257,63 @@ struct M1Trace {
 extern thread_local M1Trace* g_m1_trace;
 inline M1Trace* m1_trace() { return g_m1_trace; }
 
-int m1_forward(const void* X, const void* Xatt, const float* Wa, const float* ba, const float* Wt,
-               const float* bt, float* logits, float* att, float* zsave, float* abar, void* ws,
-               int N, int P, int C, int Ca, int K, unsigned flags, float keep_prob, uint64_t seed,
-               uint64_t offset, int dtype, hipStream_t stream, M1Xent* xf = nullptr,
-               const Hooks& hk = Hooks(), const CatFeat* cat = nullptr);
-int m1_backward(const void* X, const void* Xatt, const float* Wa, const float* ba, const float* Wt,
-                const float* bt, const float* att, const float* zsave, const float* abar,
-                const float* G, void* dX, void* dXatt, float* dWa, float* dba, float* dWt,
-                float* dbt, void* ws, int N, int P, int C, int Ca, int K, unsigned flags,
-                float keep_prob, uint64_t seed, uint64_t offset, int dtype, hipStream_t stream,
-                const M1Xent* xf = nullptr, const Hooks& hk = Hooks(), const CatFeat* cat = nullptr);
-bool m1_supported(int C, int Ca, int dtype, bool fused);
-bool m1_vec_supported(int C, int dtype);   // the per-pixel kernels of apa_m1.hip have an instance for C
-bool m1_no_dx_supported(int C, int dtype, bool train);   // can m1_backward honour APA_IFLAG_NO_DX for this shape?
-
-// apa_m1_stream.hip: "pixel tile x channel split" streaming passes for wide maps
-struct M1Rng {
-  float inv_keep;
-  uint32_t thresh;
-  uint64_t seed, offset;
-  const uint64_t* offset_dev;
-  bool relu_input = false;   // APA_FLAG_RELU_INPUT
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;   // apa_hooks prof_*: dispatch begin / end timestamps
-  uint8_t* maskbits_out = nullptr;           // forward (training): where the keep-bits go
-  const uint8_t* maskbits_in = nullptr;      // backward: the forward call's keep-bits, or nullptr (hash again)
-  bool no_dx = false;                        // backward, Xatt != X, keep-bits form: skip the dX stores (APA_IFLAG_NO_DX)
+enum M1Act { M1_ACT_ID = 0, M1_ACT_RELU = 1, M1_ACT_SOFTMAX = 2 };   // passed to the kernels as int
+// A forward / backward call: the caller's tensors (M1Fwd / M1Bwd) and, in M1Call, everything the call resolves before
+// its first launch, filled by m1_call_fill (which also holds every refusal of the path).  All on the caller's stack.
+struct M1Fwd { const void *X, *Xatt; const float *Wa, *ba, *Wt, *bt; float *logits, *att, *zsave, *abar; };
+struct M1Bwd {
+  const void *X, *Xatt; const float *Wa, *Wt, *bt, *att, *zsave, *abar, *G; void *dX, *dXatt; float *dWa, *dba, *dWt, *dbt;
 };
-bool m1s_supported(int C, int dtype);
-int m1s_launch_pool_fwd(int dtype, int C, bool fused, bool train, int nblk, hipStream_t st,
-                        const void* X, const float* Wa, const float* ba, float* att, float* pacc,
-                        float* pstat, int P, int S, int act, const M1Rng& r);
-int m1s_launch_bwd_main(int dtype, int C, bool fused, bool train, int nblk, hipStream_t st,
-                        const void* X, const float* Wa, const float* att, const float* dz,
-                        const float* zsave, const float* abar, const float* G, const float* bt,
-                        const float* sn_pre, void* dX, float* dZout, float* pdwa, float* pdba,
-                        int P, int S, int K, int act, const M1Rng& r, const float* dA_extra);
-
-// apa_m1_cat.hip: the J extra top-down channels of CatFeat
-bool m1_cat_supported(int J);
-int m1_cat_forward(const CatFeat& cat, const float* att, const float* Wt, float* logits, int N, int P,
-                   int C, int K, bool train, const M1Rng& r, hipStream_t st);
-int m1_cat_backward(const CatFeat& cat, const float* att, const float* G, const float* Wt, float* dWt,
-                    float* e_out, int N, int P, int C, int K, bool softmax, bool train, const M1Rng& r,
-                    hipStream_t st);
-
-// apa_m1_generic.hip: the same two passes for any C (run-time channel loop, LDS accumulators)
-bool m1g_supported(int C, int dtype);
-int m1g_launch_pool_fwd(int dtype, int C, bool fused, bool train, int nblk, hipStream_t st, const void* X,
-                        const float* Wa, const float* ba, float* att, float* pacc, float* pstat, int P, int S,
-                        int act, const M1Rng& r);
-int m1g_launch_bwd_main(int dtype, int C, bool fused, bool train, int nblk, hipStream_t st, const void* X,
-                        const float* Wa, const float* att, const float* dz, const float* zsave,
-                        const float* abar, const float* G, const float* bt, const float* sn_pre, void* dX,
-                        float* dZout, float* pdwa, float* pdba, int P, int S, int K, int act, const M1Rng& r,
-                        const float* dA_extra);
+struct M1Call {
+  int N, P, C, Ca, K, dtype; unsigned flags; hipStream_t st; const CatFeat* cat;
+  int act, pool_act;       // M1Act; pool_act: what the pooling kernel applies (id when att is already final, Xatt != X)
+  // fused: Xatt == X; train: dropout active; rank1 (APA_FLAG_DXATT_RANK1): the caller's dXatt buffer is fp32 [N*P] and
+  // receives dZ itself; ext (APA_FLAG_RNG_EXTERNAL): the caller's keep bits are read by the run-time-loop kernels only;
+  // no_dx (APA_IFLAG_NO_DX): backward, Xatt != X, keep-bits form: skip the dX stores; small: the backward takes the
+  // small-K route (m1_small_route_ok); gemv2: Ca is served by the register-resident attention GEMV backward
+  bool fused, train, rank1, ext, relu_input, no_dx, small, gemv2;
+  M1Pool pool; M1Plan pl;  // the pooling family of both streaming passes; the plan and what is carved from it:
+  float *pacc, *pstat, *pdwa, *pdba, *dz, *dzatt, *gemm_ws, *cat_e;   // (dzatt: the caller's dXatt under rank1)
+  float* sn;               // [N] G . bt behind pdba (the region is sized nblk + N): null off the small-K route
+  uint8_t* maskbits;       // forward (training): where the keep-bits go
+  const uint8_t* maskbits_in;   // backward: the forward call's keep-bits, or nullptr (hash again)
+  RngKeyArgs key; float inv_keep; uint64_t* bump;   // the dropout key; backward: the device step counter to advance, or null
+  const float* ex; float exs;   // backward: per-pixel addend of dA and its scale (the concat channels' share, else att, 0)
+  hipEvent_t ev0, ev1, td_ready, grad_ready;   // ev0 / ev1: apa_hooks prof_*, dispatch begin / end of the streaming pass
+};
+// b: the backward call's tensors (nullptr: a forward call); loss_done: the forward half folded the loss (M1Xent::done)
+int m1_call_fill(M1Call& c, const void* X, const void* Xatt, const M1Bwd* b, bool loss_done, const CatFeat* cat,
+                 const Hooks& hk, void* ws, int N, int P, int C, int Ca, int K, unsigned flags, float keep_prob,
+                 uint64_t seed, uint64_t offset, int dtype, hipStream_t st);
+int m1_forward(const M1Call& c, const M1Fwd& io, M1Xent* xf = nullptr);
+int m1_backward(const M1Call& c, const M1Bwd& io, const M1Xent* xf = nullptr);
+bool m1_supported(int C, int Ca, int dtype, bool fused);
+bool m1_no_dx_supported(int C, int dtype, bool train);   // can m1_backward honour APA_IFLAG_NO_DX for this shape?
+// the FUSED x TRAIN instances of a kernel template: go(std::bool_constant<FUSED>, std::bool_constant<TRAIN>)
+template <typename F> inline int m1_fused_train(bool fused, bool train, F&& go) {
+  if (fused) return train ? go(std::true_type{}, std::true_type{}) : go(std::true_type{}, std::false_type{});
+  return train ? go(std::false_type{}, std::true_type{}) : go(std::false_type{}, std::false_type{});
+}
+bool m1s_supported(int C, int dtype);   // apa_m1_stream.hip: "pixel tile x channel split" for wide maps
+int m1s_launch_pool_fwd(const M1Call& c, const M1Fwd& io);
+int m1s_launch_bwd_main(const M1Call& c, const M1Bwd& io);
+bool m1v_supported(int C, int dtype);   // apa_m1_vec.hip: register-resident per-pixel kernels, narrow powers of two
+int m1v_launch_pool_fwd(const M1Call& c, const M1Fwd& io);
+int m1v_launch_bwd_main(const M1Call& c, const M1Bwd& io);
+bool m1g_supported(int C, int dtype);   // apa_m1_generic.hip: any C (run-time channel loop, LDS accumulators)
+int m1g_launch_pool_fwd(const M1Call& c, const M1Fwd& io);
+int m1g_launch_bwd_main(const M1Call& c, const M1Bwd& io);
+bool m1_cat_supported(int J);   // apa_m1_cat.hip: the J extra top-down channels of CatFeat (c.cat)
+int m1_cat_forward(const M1Call& c, const M1Fwd& io);
+int m1_cat_backward(const M1Call& c, const M1Bwd& io);   // dWt rows C.., dXext, and c.cat_e
 
 // apa_m1_small.hip: LDS-tiled f32-MFMA kernels for the small products of the M == 1 path
 bool m1_small_supported(int C, int K);
+// Are the small-K head kernels usable?  They read G / Wt / z with 16-byte loads.  The forward's fused loss (any_ck:
+// its evaluation form has shape limits of its own), m1_backward and the fused cfg 003 step must agree.
+inline bool m1_small_route_ok(int C, int K, const float* G, const float* Wt, const float* zsave, bool any_ck = false) {
+  return (any_ck || m1_small_supported(C, K)) && (((uintptr_t)G | (uintptr_t)Wt | (uintptr_t)zsave) & 15) == 0;
+}
 int m1_bwd_small(const float* G, const float* Wt, const float* zsave, const float* abar,
                  const float* bt, float* dz, float* dWt, float* dbt, float* sn, int N, int C, int K,
                  hipStream_t st);

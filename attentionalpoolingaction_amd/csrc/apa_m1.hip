@@ -13,186 +13,16 @@
 // Each feature map is streamed from HBM exactly once per pass: X is read once in forward, and
 // read once + dX written once in backward (3*P*C*sizeof(T) algorithmic bytes per image).
 //
-// Kernel shape: one wave owns whole pixels.  A pixel's C channels live in the wave's registers
-// (C/64 per lane, loaded as 16-byte vectors -> 1 KiB per wave-instruction, fully coalesced), so
-// the C-long dot product is a DPP wave reduction and the accumulation into z / dX / dwa needs no
-// second look at memory.  The next pixel's loads are issued before the current one is consumed.
+// This file: the stages every pooling family shares (finalize, the attention GEMV forward / backward for a separate
+// Xatt, softmax rows, the fallback reduce) and the host dispatch.  The two streaming passes themselves come in three
+// families behind one pair of launchers each: apa_m1_stream.hip (wide maps), apa_m1_vec.hip (narrow powers of two),
+// apa_m1_generic.hip (any C).
 #include <math.h>
 
 #include "apa_device.h"
 #include "apa_internal.h"
 
 namespace apa {
-
-enum { ACT_ID = 0, ACT_RELU = 1, ACT_SOFTMAX = 2 };
-
-// --------------------------------------------------------------------------------------------
-// F1: pooling pass.  grid = N*S blocks of 256 threads; block (n,s) owns pixels
-// [s*ppb, min(P,(s+1)*ppb)) of image n, wave w takes every 4th pixel.
-//   FUSED  : Z = x.wa + ba computed in-line (Xatt == X, cfg 002); softmax handled on-line
-//            (running max / sum, flash-style) so X is still read once.
-//   !FUSED : A[n,p] given (already activated / soft-maxed) in att.
-// Outputs: att (FUSED: id/relu -> final A, softmax -> raw Z, normalised in F2),
-//          pacc[blk][C] partial sum_p A*Xt, pstat[blk][4] = {m, l, asum, -}.
-// --------------------------------------------------------------------------------------------
-template <typename T, int VEC, bool FUSED, bool TRAIN>
-__global__ __launch_bounds__(256) void m1_pool_fwd_kernel(
-    const T* __restrict__ X, const float* __restrict__ Wa, const float* __restrict__ ba,
-    float* __restrict__ att, float* __restrict__ pacc, float* __restrict__ pstat, int P, int S,
-    int act, float inv_keep, uint32_t thresh, uint64_t seed, uint64_t offset,
-    const uint64_t* __restrict__ offset_dev) {
-  constexpr int EPV = Vec<T>::EPV;
-  constexpr int EPL = VEC * EPV;
-  constexpr int C = EPL * 64;
-  __shared__ __attribute__((aligned(16))) float sm_acc[4 * C];
-  __shared__ float sm_stat[4 * 4];
-  uint32_t k0 = 0, k1 = 0;
-  if (TRAIN) rng_key_dev(seed, offset_dev ? *offset_dev : offset, k0, k1);
-
-  const int nblk = gridDim.x;
-  const int blk = xcd_remap(blockIdx.x, nblk);
-  const int n = blk / S, s = blk % S;
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int p_begin = (int)(((long)s * P) / S);        // balanced split: sizes differ by <= 1
-  const int p_end = (int)(((long)(s + 1) * P) / S);
-
-  float wa[FUSED ? EPL : 1];
-  float bias = 0.f;
-  if (FUSED) {
-#pragma unroll
-    for (int j = 0; j < VEC; ++j) {
-      const int c0 = j * 64 * EPV + lane * EPV;
-#pragma unroll
-      for (int e = 0; e < EPV; e += 4) {
-        const float4 w = *reinterpret_cast<const float4*>(Wa + c0 + e);
-        wa[j * EPV + e + 0] = w.x; wa[j * EPV + e + 1] = w.y;
-        wa[j * EPV + e + 2] = w.z; wa[j * EPV + e + 3] = w.w;
-      }
-    }
-    bias = ba[0];
-  }
-
-  float acc[EPL];
-#pragma unroll
-  for (int i = 0; i < EPL; ++i) acc[i] = 0.f;
-  float m_run = -INFINITY, l_run = 0.f, a_sum = 0.f;
-
-  const T* xim = X + (size_t)n * P * C;
-  float* att_im = att + (size_t)n * P;
-
-  uint4 cur[VEC], nxt[VEC];
-  int p = p_begin + wave;
-  if (p < p_end) {
-#pragma unroll
-    for (int j = 0; j < VEC; ++j) cur[j] = ld16(xim + (size_t)p * C + j * 64 * EPV + lane * EPV);
-  }
-  for (; p < p_end; p += 4) {
-    const int pn = p + 4;
-    if (pn < p_end) {
-#pragma unroll
-      for (int j = 0; j < VEC; ++j) nxt[j] = ld16(xim + (size_t)pn * C + j * 64 * EPV + lane * EPV);
-    }
-    float x[EPL];
-#pragma unroll
-    for (int j = 0; j < VEC; ++j) Vec<T>::unpack(cur[j], x + j * EPV);
-
-    float a;       // weight applied to this pixel's features
-    float scale = 1.f;
-    if (FUSED) {
-      float d0 = 0.f, d1 = 0.f;
-#pragma unroll
-      for (int i = 0; i < EPL; i += 2) {
-        d0 = fmaf(x[i], wa[i], d0);
-        d1 = fmaf(x[i + 1], wa[i + 1], d1);
-      }
-      const float zl = wave_sum(d0 + d1) + bias;
-      if (act == ACT_SOFTMAX) {
-        const float m_new = fmaxf(m_run, zl);
-        scale = expf(m_run - m_new);  // exp(-inf) = 0 on the first pixel
-        a = expf(zl - m_new);
-        l_run = l_run * scale + a;
-        m_run = m_new;
-        if (lane == 0) att_im[p] = zl;  // raw logit; normalised by the finalize kernel
-      } else {
-        a = (act == ACT_RELU) ? fmaxf(zl, 0.f) : zl;
-        if (lane == 0) att_im[p] = a;
-      }
-    } else {
-      a = att_im[p];
-    }
-    a_sum += a;
-
-    if (TRAIN) {
-      const uint64_t ebase = ((uint64_t)n * P + p) * C;
-      const float ak = a * inv_keep;
-#pragma unroll
-      for (int j = 0; j < VEC; ++j) {
-        const uint64_t e0 = ebase + j * 64 * EPV + lane * EPV;
-#pragma unroll
-        for (int e = 0; e < EPV; e += 2) {
-          float m0, m1;
-          rng_keep2(e0 + e, k0, k1, thresh, m0, m1);
-          const int i = j * EPV + e;
-          acc[i] = fmaf(acc[i], scale, ak * m0 * x[i]);
-          acc[i + 1] = fmaf(acc[i + 1], scale, ak * m1 * x[i + 1]);
-        }
-      }
-    } else {
-#pragma unroll
-      for (int i = 0; i < EPL; ++i) acc[i] = fmaf(acc[i], scale, a * x[i]);
-    }
-#pragma unroll
-    for (int j = 0; j < VEC; ++j) cur[j] = nxt[j];
-  }
-
-  // ---- combine the 4 waves of the block (fixed order -> deterministic) ----
-  if (lane == 0) {
-    sm_stat[wave * 4 + 0] = m_run;
-    sm_stat[wave * 4 + 1] = l_run;
-    sm_stat[wave * 4 + 2] = a_sum;
-  }
-  __syncthreads();
-  float wscale = 1.f, m_blk = 0.f, l_blk = 0.f;
-  if (act == ACT_SOFTMAX && FUSED) {
-    m_blk = fmaxf(fmaxf(sm_stat[0], sm_stat[4]), fmaxf(sm_stat[8], sm_stat[12]));
-    wscale = (m_run == -INFINITY) ? 0.f : expf(m_run - m_blk);
-#pragma unroll
-    for (int w = 0; w < 4; ++w) {
-      const float mw = sm_stat[w * 4];
-      l_blk += (mw == -INFINITY) ? 0.f : sm_stat[w * 4 + 1] * expf(mw - m_blk);
-    }
-  }
-#pragma unroll
-  for (int j = 0; j < VEC; ++j) {
-#pragma unroll
-    for (int e = 0; e < EPV; e += 4) {
-      const int c0 = j * 64 * EPV + lane * EPV + e;
-      const int i = j * EPV + e;
-      *reinterpret_cast<float4*>(&sm_acc[wave * C + c0]) =
-          make_float4(acc[i] * wscale, acc[i + 1] * wscale, acc[i + 2] * wscale, acc[i + 3] * wscale);
-    }
-  }
-  __syncthreads();
-  float* pa = pacc + (size_t)blk * C;
-  for (int v = threadIdx.x; v < C / 4; v += 256) {
-    const float4 a0 = *reinterpret_cast<const float4*>(&sm_acc[0 * C + v * 4]);
-    const float4 a1 = *reinterpret_cast<const float4*>(&sm_acc[1 * C + v * 4]);
-    const float4 a2 = *reinterpret_cast<const float4*>(&sm_acc[2 * C + v * 4]);
-    const float4 a3 = *reinterpret_cast<const float4*>(&sm_acc[3 * C + v * 4]);
-    float4 r;
-    r.x = (a0.x + a1.x) + (a2.x + a3.x);
-    r.y = (a0.y + a1.y) + (a2.y + a3.y);
-    r.z = (a0.z + a1.z) + (a2.z + a3.z);
-    r.w = (a0.w + a1.w) + (a2.w + a3.w);
-    *reinterpret_cast<float4*>(pa + v * 4) = r;
-  }
-  if (threadIdx.x == 0) {
-    pstat[blk * 4 + 0] = m_blk;
-    pstat[blk * 4 + 1] = l_blk;
-    pstat[blk * 4 + 2] = (sm_stat[2] + sm_stat[6]) + (sm_stat[10] + sm_stat[14]);
-    pstat[blk * 4 + 3] = 0.f;
-  }
-}
 
 // --------------------------------------------------------------------------------------------
 // F2: merge the S block partials of each image.  grid (N, C/(4 cw)), block 256, cw channel threads
@@ -322,7 +152,7 @@ __global__ __launch_bounds__(256) void m1_att_gemv_fwd_kernel(const T* __restric
       for (int e = 0; e < EPV; ++e) d = fmaf(x[e], Wa[v * EPV + e], d);
     }
     float zl = wave_sum(d) + bias;
-    if (act == ACT_RELU) zl = fmaxf(zl, 0.f);
+    if (act == M1_ACT_RELU) zl = fmaxf(zl, 0.f);
     if (lane == 0) att[px] = zl;
   }
 }
@@ -339,183 +169,6 @@ __global__ __launch_bounds__(64) void m1_softmax_rows_kernel(float* __restrict__
   l = wave_sum(l);
   const float inv = 1.0f / l;
   for (int p = lane; p < P; p += 64) row[p] = expf(row[p] - m) * inv;
-}
-
-// --------------------------------------------------------------------------------------------
-// B3: backward streaming pass (the dominant kernel: reads X once, writes dX once).
-// grid = N*S blocks of 256 threads, same pixel ownership as F1.
-// --------------------------------------------------------------------------------------------
-template <typename T, int VEC, bool FUSED, bool TRAIN>
-__global__ __launch_bounds__(256) void m1_bwd_main_kernel(
-    const T* __restrict__ X, const float* __restrict__ Wa, const float* __restrict__ att,
-    const float* __restrict__ dz, const float* __restrict__ zsave, const float* __restrict__ abar,
-    const float* __restrict__ G, const float* __restrict__ bt,
-    const float* __restrict__ sn_pre, T* __restrict__ dX,
-    float* __restrict__ dZout, float* __restrict__ pdwa, float* __restrict__ pdba, int P, int S,
-    int K, int act, float inv_keep, uint32_t thresh, uint64_t seed, uint64_t offset,
-    const uint64_t* __restrict__ offset_dev, const float* __restrict__ dA_extra, float extra_scale) {
-  constexpr int EPV = Vec<T>::EPV;
-  constexpr int EPL = VEC * EPV;
-  constexpr int C = EPL * 64;
-  uint32_t k0 = 0, k1 = 0;
-  if (TRAIN) rng_key_dev(seed, offset_dev ? *offset_dev : offset, k0, k1);
-  __shared__ __attribute__((aligned(16))) float sm_acc[FUSED ? 4 * C : 4];
-  __shared__ float sm_dba[4];
-
-  const int nblk = gridDim.x;
-  const int blk = xcd_remap(blockIdx.x, nblk);
-  const int n = blk / S, s = blk % S;
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int p_begin = (int)(((long)s * P) / S);        // balanced split: sizes differ by <= 1
-  const int p_end = (int)(((long)(s + 1) * P) / S);
-  const float invP = 1.0f / (float)P;
-
-  // the first pixel's HBM loads go out before anything else; the per-image constants below
-  // (L2 hits) are fetched in their shadow
-  const T* xim = X + (size_t)n * P * C;
-  T* dxim = dX + (size_t)n * P * C;
-  const float* att_im = att + (size_t)n * P;
-  uint4 cur[VEC], nxt[VEC];
-  int p = p_begin + wave;
-  if (p < p_end) {
-#pragma unroll
-    for (int j = 0; j < VEC; ++j) cur[j] = ld16(xim + (size_t)p * C + j * 64 * EPV + lane * EPV);
-  }
-
-  // per-image constants, every wave computes them redundantly (a few KB from L2)
-  float dzr[EPL];
-  float wa[FUSED ? EPL : 1];
-  float zdz = 0.f;
-#pragma unroll
-  for (int j = 0; j < VEC; ++j) {
-    const int c0 = j * 64 * EPV + lane * EPV;
-#pragma unroll
-    for (int e = 0; e < EPV; e += 4) {
-      const int i = j * EPV + e;
-      const float4 d = *reinterpret_cast<const float4*>(dz + (size_t)n * C + c0 + e);
-      dzr[i] = d.x; dzr[i + 1] = d.y; dzr[i + 2] = d.z; dzr[i + 3] = d.w;
-      if (FUSED) {
-        const float4 w = *reinterpret_cast<const float4*>(Wa + c0 + e);
-        wa[i] = w.x; wa[i + 1] = w.y; wa[i + 2] = w.z; wa[i + 3] = w.w;
-      }
-      if (act == ACT_SOFTMAX) {
-        const float4 zz = *reinterpret_cast<const float4*>(zsave + (size_t)n * C + c0 + e);
-        zdz = fmaf(zz.x, d.x, zdz); zdz = fmaf(zz.y, d.y, zdz);
-        zdz = fmaf(zz.z, d.z, zdz); zdz = fmaf(zz.w, d.w, zdz);
-      }
-    }
-  }
-  float sn;  // G[n,:] . bt: precomputed by the dz kernel (one load), else a K-long dot here
-  if (sn_pre) {
-    sn = sn_pre[n];
-  } else {
-    sn = 0.f;
-    for (int k = lane; k < K; k += 64) sn = fmaf(G[(size_t)n * K + k], bt[k], sn);
-    sn = wave_sum(sn);
-  }
-  float corr = 0.f;
-  if (act == ACT_SOFTMAX) corr = wave_sum(zdz) + sn * abar[n];
-
-  float dwa[FUSED ? EPL : 1];
-  if (FUSED) {
-#pragma unroll
-    for (int i = 0; i < EPL; ++i) dwa[i] = 0.f;
-  }
-  float dba_acc = 0.f;
-
-  for (; p < p_end; p += 4) {
-    const int pn = p + 4;
-    if (pn < p_end) {
-#pragma unroll
-      for (int j = 0; j < VEC; ++j) nxt[j] = ld16(xim + (size_t)pn * C + j * 64 * EPV + lane * EPV);
-    }
-    const float a = att_im[p];
-    float x[EPL];
-#pragma unroll
-    for (int j = 0; j < VEC; ++j) Vec<T>::unpack(cur[j], x + j * EPV);
-
-    float mk[TRAIN ? EPL : 1];  // mask / keep
-    if (TRAIN) {
-      const uint64_t ebase = ((uint64_t)n * P + p) * C;
-#pragma unroll
-      for (int j = 0; j < VEC; ++j) {
-        const uint64_t e0 = ebase + j * 64 * EPV + lane * EPV;
-#pragma unroll
-        for (int e = 0; e < EPV; e += 2) {
-          float m0, m1;
-          rng_keep2(e0 + e, k0, k1, thresh, m0, m1);
-          mk[j * EPV + e] = m0 * inv_keep;
-          mk[j * EPV + e + 1] = m1 * inv_keep;
-        }
-      }
-    }
-    float d0 = 0.f, d1 = 0.f;
-#pragma unroll
-    for (int i = 0; i < EPL; i += 2) {
-      if (TRAIN) {
-        d0 = fmaf(x[i] * mk[i], dzr[i], d0);
-        d1 = fmaf(x[i + 1] * mk[i + 1], dzr[i + 1], d1);
-      } else {
-        d0 = fmaf(x[i], dzr[i], d0);
-        d1 = fmaf(x[i + 1], dzr[i + 1], d1);
-      }
-    }
-    // + the concatenated pose channels' share (apa_m1_cat.hip); callers without them pass att, scale 0
-    const float dA = (wave_sum(d0 + d1) + sn + dA_extra[(size_t)n * P + p] * extra_scale) * invP;
-    float dZ;
-    if (act == ACT_SOFTMAX) dZ = a * (dA - corr);
-    else if (act == ACT_RELU) dZ = a > 0.f ? dA : 0.f;
-    else dZ = dA;
-
-    const float ap = a * invP;
-    float o[EPL];
-#pragma unroll
-    for (int i = 0; i < EPL; ++i) {
-      const float t = TRAIN ? ap * mk[i] : ap;
-      if (FUSED) {
-        o[i] = fmaf(t, dzr[i], dZ * wa[i]);
-        dwa[i] = fmaf(dZ, x[i], dwa[i]);
-      } else {
-        o[i] = t * dzr[i];
-      }
-    }
-#pragma unroll
-    for (int j = 0; j < VEC; ++j)
-      st16(dxim + (size_t)p * C + j * 64 * EPV + lane * EPV, Vec<T>::pack(o + j * EPV));
-    if (FUSED) dba_acc += dZ;
-    else if (lane == 0) dZout[(size_t)n * P + p] = dZ;
-#pragma unroll
-    for (int j = 0; j < VEC; ++j) cur[j] = nxt[j];
-  }
-
-  if (FUSED) {
-#pragma unroll
-    for (int j = 0; j < VEC; ++j) {
-#pragma unroll
-      for (int e = 0; e < EPV; e += 4) {
-        const int c0 = j * 64 * EPV + lane * EPV + e;
-        const int i = j * EPV + e;
-        *reinterpret_cast<float4*>(&sm_acc[wave * C + c0]) =
-            make_float4(dwa[i], dwa[i + 1], dwa[i + 2], dwa[i + 3]);
-      }
-    }
-    if (lane == 0) sm_dba[wave] = dba_acc;
-    __syncthreads();
-    float* pa = pdwa + (size_t)blk * C;
-    for (int v = threadIdx.x; v < C / 4; v += 256) {
-      const float4 a0 = *reinterpret_cast<const float4*>(&sm_acc[0 * C + v * 4]);
-      const float4 a1 = *reinterpret_cast<const float4*>(&sm_acc[1 * C + v * 4]);
-      const float4 a2 = *reinterpret_cast<const float4*>(&sm_acc[2 * C + v * 4]);
-      const float4 a3 = *reinterpret_cast<const float4*>(&sm_acc[3 * C + v * 4]);
-      float4 r;
-      r.x = (a0.x + a1.x) + (a2.x + a3.x);
-      r.y = (a0.y + a1.y) + (a2.y + a3.y);
-      r.z = (a0.z + a1.z) + (a2.z + a3.z);
-      r.w = (a0.w + a1.w) + (a2.w + a3.w);
-      *reinterpret_cast<float4*>(pa + v * 4) = r;
-    }
-    if (threadIdx.x == 0) pdba[blk] = (sm_dba[0] + sm_dba[1]) + (sm_dba[2] + sm_dba[3]);
-  }
 }
 
 // --------------------------------------------------------------------------------------------
@@ -657,20 +310,13 @@ __global__ __launch_bounds__(256) void m1_att_gemv_bwd2_kernel(
 // ============================================================================================
 thread_local M1Trace* g_m1_trace = nullptr;
 
-// the register-resident per-pixel kernels of this file: C = 64 * EPV * {1, 2}; the wider powers of two are
-// streaming C's (m1s_supported)
-static bool vec_kernels_supported(int C, int dtype) {
-  const int epv = dtype == APA_DTYPE_BF16 ? 8 : 4;
-  return C == 64 * epv || C == 128 * epv;
-}
-bool m1_vec_supported(int C, int dtype) { return vec_kernels_supported(C, dtype); }
 // Any channel count that is a whole number of 16-byte vectors is served: the channel-split streaming
-// kernels (apa_m1_stream.hip) for the wide benchmark shapes, the per-pixel kernels of this file for the
+// kernels (apa_m1_stream.hip) for the wide benchmark shapes, the per-pixel kernels (apa_m1_vec.hip) for the
 // other powers of two, the run-time-loop kernels of apa_m1_generic.hip for everything else.
 bool m1_supported(int C, int Ca, int dtype, bool fused) {
   const int epv = dtype == APA_DTYPE_BF16 ? 8 : 4;
   if (!fused && (Ca % epv != 0)) return false;
-  return m1s_supported(C, dtype) || vec_kernels_supported(C, dtype) || m1g_supported(C, dtype);
+  return m1s_supported(C, dtype) || m1v_supported(C, dtype) || m1g_supported(C, dtype);
 }
 
 // Grid sizing.  The streaming kernels hold 2 blocks (8 waves) per CU at their register budget, so
@@ -708,347 +354,240 @@ M1Plan m1_plan(int N, int P, int C, int Ca, int K) {
   return pl;
 }
 
-typedef M1Rng RngArgs;
-
 // APA_IFLAG_NO_DX is served by the keep-bits form of the streaming backward kernel: bf16 features in training mode
 // inside a one-call step (the forward half left the bits in the workspace)
 bool m1_no_dx_supported(int C, int dtype, bool train) {
   return train && dtype == APA_DTYPE_BF16 && m1s_supported(C, dtype);
 }
 
-template <typename T, int VEC>
-static int launch_pool_fwd(bool fused, bool train, int nblk, hipStream_t st, const void* X,
-                           const float* Wa, const float* ba, float* att, float* pacc, float* pstat,
-                           int P, int S, int act, RngArgs r) {
-  const T* x = static_cast<const T*>(X);
-  if (M1Trace* t = m1_trace()) { t->pool_fwd = M1_POOL_VEC; t->fwd_w = VEC; t->fwd_pix = 0; }
-#define APA_GO(F, TR)                                                                          \
-  launch_ev(m1_pool_fwd_kernel<T, VEC, F, TR>, dim3(nblk), dim3(256), 0, st, r.ev0, r.ev1, x, Wa, \
-                     ba, att, pacc, pstat, P, S, act, r.inv_keep, r.thresh, r.seed, r.offset,  \
-                     r.offset_dev)
-  if (fused) { if (train) APA_GO(true, true); else APA_GO(true, false); }
-  else       { if (train) APA_GO(false, true); else APA_GO(false, false); }
-#undef APA_GO
-  APA_LAUNCH_CHECK("m1_pool_fwd_kernel");
-  return APA_OK;
-}
-
-template <typename T, int VEC>
-static int launch_bwd_main(bool fused, bool train, int nblk, hipStream_t st, const void* X,
-                           const float* Wa, const float* att, const float* dz, const float* zsave,
-                           const float* abar, const float* G, const float* bt,
-                           const float* sn_pre, void* dX,
-                           float* dZout, float* pdwa, float* pdba, int P, int S, int K, int act,
-                           RngArgs r, const float* dA_extra) {
-  const T* x = static_cast<const T*>(X);
-  T* dx = static_cast<T*>(dX);
-  const float* ex = dA_extra ? dA_extra : att;
-  const float exs = dA_extra ? 1.0f : 0.0f;
-  if (M1Trace* t = m1_trace()) { t->pool_bwd = M1_POOL_VEC; t->bwd_w = VEC; t->bwd_pix = 0; }
-#define APA_GO(F, TR)                                                                            \
-  launch_ev(m1_bwd_main_kernel<T, VEC, F, TR>, dim3(nblk), dim3(256), 0, st, r.ev0, r.ev1, x, Wa,   \
-                     att, dz, zsave, abar, G, bt, sn_pre, dx, dZout, pdwa, pdba, P, S, K, act,   \
-                     r.inv_keep, r.thresh, r.seed, r.offset, r.offset_dev, ex, exs)
-  if (fused) { if (train) APA_GO(true, true); else APA_GO(true, false); }
-  else       { if (train) APA_GO(false, true); else APA_GO(false, false); }
-#undef APA_GO
-  APA_LAUNCH_CHECK("m1_bwd_main_kernel");
-  return APA_OK;
-}
-
-#define APA_DISPATCH_VEC(FN, dtype, C, ...)                                              \
-  [&]() -> int {                                                                         \
-    if ((dtype) == APA_DTYPE_F32) {                                                      \
-      switch ((C) / 256) {                                                               \
-        case 1: return FN<float, 1>(__VA_ARGS__);                                        \
-        case 2: return FN<float, 2>(__VA_ARGS__);                                        \
-      }                                                                                  \
-    } else {                                                                             \
-      switch ((C) / 512) {                                                               \
-        case 1: return FN<bf16_t, 1>(__VA_ARGS__);                                       \
-        case 2: return FN<bf16_t, 2>(__VA_ARGS__);                                       \
-      }                                                                                  \
-    }                                                                                    \
-    set_error("attn_pool M=1: unsupported C=%d for dtype %d", (C), (dtype));             \
-    return APA_ERR_UNSUPPORTED;                                                          \
-  }()
-
-static int act_of(unsigned flags) {
-  if (flags & APA_FLAG_SOFTMAX_ATT) return ACT_SOFTMAX;  // relu(softmax(.)) == softmax(.)
-  if (flags & APA_FLAG_RELU_ATT) return ACT_RELU;
-  return ACT_ID;
-}
-
-static RngArgs rng_args(bool train, float keep_prob, uint64_t seed, uint64_t offset, unsigned flags) {
-  RngArgs r;
-  r.inv_keep = train ? 1.0f / keep_prob : 1.0f;
-  const RngKeyArgs k = rng_resolve(flags, keep_prob, seed, offset);
-  r.thresh = k.thresh; r.seed = k.seed; r.offset = k.offset; r.offset_dev = k.offset_dev;
-  r.relu_input = (flags & APA_FLAG_RELU_INPUT) != 0;
-  return r;
-}
-
-int m1_forward(const void* X, const void* Xatt, const float* Wa, const float* ba, const float* Wt,
-               const float* bt, float* logits, float* att, float* zsave, float* abar, void* ws,
-               int N, int P, int C, int Ca, int K, unsigned flags, float keep_prob, uint64_t seed,
-               uint64_t offset, int dtype, hipStream_t st, M1Xent* xf, const Hooks& hk,
-               const CatFeat* cat) {
-  const bool fused = (Xatt == X);
-  const bool train = (flags & APA_FLAG_TRAIN) && keep_prob < 1.0f;
-  const int act = act_of(flags);
-  const M1Plan pl = m1_plan(N, P, C, Ca, K);
+int m1_call_fill(M1Call& c, const void* X, const void* Xatt, const M1Bwd* b, bool loss_done, const CatFeat* cat,
+                 const Hooks& hk, void* ws, int N, int P, int C, int Ca, int K, unsigned flags, float keep_prob,
+                 uint64_t seed, uint64_t offset, int dtype, hipStream_t st) {
+  c.N = N; c.P = P; c.C = C; c.Ca = Ca; c.K = K; c.dtype = dtype; c.flags = flags; c.st = st; c.cat = cat;
+  c.fused = (Xatt == X);
+  c.train = (flags & APA_FLAG_TRAIN) && keep_prob < 1.0f;
+  c.act = (flags & APA_FLAG_SOFTMAX_ATT) ? M1_ACT_SOFTMAX   // relu(softmax(.)) == softmax(.)
+          : (flags & APA_FLAG_RELU_ATT) ? M1_ACT_RELU : M1_ACT_ID;
+  c.pool_act = c.fused ? c.act : M1_ACT_ID;
+  c.rank1 = b && (flags & APA_FLAG_DXATT_RANK1) != 0 && !c.fused;
+  c.ext = c.train && rng_external(flags);
+  c.relu_input = (flags & APA_FLAG_RELU_INPUT) != 0;
+  c.no_dx = b && (flags & APA_IFLAG_NO_DX) != 0;
+  c.small = b && m1_small_route_ok(C, K, b->G, b->Wt, b->zsave);
+  const int epv = dtype == APA_DTYPE_F32 ? 4 : 8;
+  c.gemv2 = Ca % epv == 0 && Ca / epv <= 256;
+  c.pool = !c.ext && m1s_supported(C, dtype) ? M1_POOL_STREAM
+           : !c.ext && m1v_supported(C, dtype) ? M1_POOL_VEC : M1_POOL_GENERIC;
+  c.pl = m1_plan(N, P, C, Ca, K);
   char* w = static_cast<char*>(ws);
-  float* pacc = reinterpret_cast<float*>(w + pl.off_pacc);
-  float* pstat = reinterpret_cast<float*>(w + pl.off_pstat);
-  float* gemm_ws = reinterpret_cast<float*>(w + pl.off_gemm);
-  RngArgs r = rng_args(train, keep_prob, seed, offset, flags);
-  r.ev0 = hk.fwd0; r.ev1 = hk.fwd1;
-  r.maskbits_out = reinterpret_cast<uint8_t*>(w + pl.off_maskbits);
-  M1Trace* const tr = m1_trace();
-  if (tr) { tr->S = pl.S; tr->ppb = pl.ppb; tr->nblk = pl.nblk; tr->fused = fused; tr->relu_input = r.relu_input; }
+  c.pacc = reinterpret_cast<float*>(w + c.pl.off_pacc);
+  c.pstat = reinterpret_cast<float*>(w + c.pl.off_pstat);
+  c.pdwa = reinterpret_cast<float*>(w + c.pl.off_pdwa);
+  c.pdba = reinterpret_cast<float*>(w + c.pl.off_pdba);
+  c.sn = c.small ? c.pdba + c.pl.nblk : nullptr;
+  c.dz = reinterpret_cast<float*>(w + c.pl.off_dz);
+  c.dzatt = c.rank1 ? static_cast<float*>(b->dXatt) : reinterpret_cast<float*>(w + c.pl.off_dzatt);
+  c.gemm_ws = reinterpret_cast<float*>(w + c.pl.off_gemm);
+  c.cat_e = reinterpret_cast<float*>(w + c.pl.off_cat_e);
+  c.maskbits = reinterpret_cast<uint8_t*>(w + c.pl.off_maskbits);
+  // APA_FLAG_WS_FROM_FWD: same workspace, untouched since the forward call
+  c.maskbits_in = b && (flags & APA_FLAG_WS_FROM_FWD) ? c.maskbits : nullptr;
+  c.key = rng_resolve(flags, keep_prob, seed, offset);
+  c.inv_keep = c.train ? 1.0f / keep_prob : 1.0f;
+  c.bump = (b && c.train && (flags & APA_FLAG_RNG_DEVICE)) ? reinterpret_cast<uint64_t*>(static_cast<uintptr_t>(offset))
+                                                          : nullptr;
+  // + the concatenated pose channels' share of dA (apa_m1_cat.hip); without them att, scale 0
+  c.ex = b ? (cat ? c.cat_e : b->att) : nullptr;
+  c.exs = cat ? 1.0f : 0.0f;
+  c.ev0 = b ? hk.bwd0 : hk.fwd0; c.ev1 = b ? hk.bwd1 : hk.fwd1;
+  c.td_ready = hk.td_ready; c.grad_ready = hk.grad_ready;
+  if (M1Trace* tr = m1_trace()) {
+    tr->S = c.pl.S; tr->ppb = c.pl.ppb; tr->nblk = c.pl.nblk; tr->fused = c.fused; tr->relu_input = c.relu_input;
+  }
 
-  if (r.relu_input && !(fused && m1s_supported(C, dtype))) {
+  // ---- every refusal of the path: nothing has been launched yet ----
+  if (c.no_dx && (c.fused || !c.maskbits_in || !m1_no_dx_supported(C, dtype, c.train) || rng_external(flags) || cat)) {
+    set_error("attn_pool M=1: NO_DX needs a separate attention input, the forward half's keep bits and the bf16 "
+              "streaming kernels (internal)");
+    return APA_ERR_UNSUPPORTED;
+  }
+  if (c.relu_input && !(c.fused && m1s_supported(C, dtype))) {
     set_error("attn_pool M=1: APA_FLAG_RELU_INPUT needs Xatt == X and C in {1024,2048,4096} (f32) / 2048 (bf16)");
     return APA_ERR_UNSUPPORTED;
   }
-  int pool_act = act;
-  if (!fused && (flags & APA_IFLAG_ATT_READY)) {
-    // the fused cfg 003 step: the pose head's Pl kernel already left Z = Xatt . wa + ba (id / relu applied) in att
-    if (act == ACT_SOFTMAX) {
-      hipLaunchKernelGGL(m1_softmax_rows_kernel, dim3(N), dim3(64), 0, st, att, P);
-      APA_LAUNCH_CHECK("m1_softmax_rows_kernel");
-    }
-    pool_act = ACT_ID;
-  } else if (!fused) {
-    const long NP = (long)N * P;
-    const int nb = (int)((NP + 3) / 4 < 2048 ? (NP + 3) / 4 : 2048);
-    if (dtype == APA_DTYPE_F32)
-      hipLaunchKernelGGL(m1_att_gemv_fwd_kernel<float>, dim3(nb), dim3(256), 0, st,
-                         static_cast<const float*>(Xatt), Wa, ba, att, NP, Ca, act);
-    else
-      hipLaunchKernelGGL(m1_att_gemv_fwd_kernel<bf16_t>, dim3(nb), dim3(256), 0, st,
-                         static_cast<const bf16_t*>(Xatt), Wa, ba, att, NP, Ca, act);
-    APA_LAUNCH_CHECK("m1_att_gemv_fwd_kernel");
-    if (act == ACT_SOFTMAX) {
-      hipLaunchKernelGGL(m1_softmax_rows_kernel, dim3(N), dim3(64), 0, st, att, P);
-      APA_LAUNCH_CHECK("m1_softmax_rows_kernel");
-    }
-    pool_act = ACT_ID;  // att already final
+  if (loss_done && !(c.small && m1_bwd_head_supported(N, C, K))) {
+    set_error("attn_pool M=1: fused loss path without the head kernel (internal)");
+    return APA_ERR_UNSUPPORTED;
   }
-  int rc = APA_OK;
-  // APA_FLAG_RNG_EXTERNAL: the caller's keep bits are read by the run-time-loop kernels only
-  const bool ext = train && rng_external(flags);
-  if (ext && !m1g_supported(C, dtype)) {
+  if (c.ext && !m1g_supported(C, dtype)) {
     set_error("attn_pool M=1: APA_FLAG_RNG_EXTERNAL: C=%d is not served by the generic M == 1 kernels", C);
     return APA_ERR_UNSUPPORTED;
   }
-  if (!ext && m1s_supported(C, dtype))
-    rc = m1s_launch_pool_fwd(dtype, C, fused, train, pl.nblk, st, X, Wa, ba, att, pacc, pstat, P,
-                             pl.S, pool_act, r);
-  else if (!ext && vec_kernels_supported(C, dtype))
-    rc = APA_DISPATCH_VEC(launch_pool_fwd, dtype, C, fused, train, pl.nblk, st, X, Wa, ba, att,
-                          pacc, pstat, P, pl.S, pool_act, r);
-  else {
-    if (tr) tr->pool_fwd = M1_POOL_GENERIC;
-    rc = m1g_launch_pool_fwd(dtype, C, fused, train, pl.nblk, st, X, Wa, ba, att, pacc, pstat, P, pl.S,
-                             pool_act, r);
+  if (b && (flags & APA_IFLAG_NO_ATT_WGRAD)) {
+    if (!c.rank1 || !c.small) {
+      set_error("attn_pool M=1: NO_ATT_WGRAD needs the rank-1 dXatt form and the small-K head kernels (internal)");
+      return APA_ERR_UNSUPPORTED;
+    }
+  } else if (c.rank1 && !c.gemv2) {
+    set_error("attn_pool M=1: APA_FLAG_DXATT_RANK1: Ca=%d not served by the register-resident GEMV", Ca);
+    return APA_ERR_UNSUPPORTED;
+  }
+  return APA_OK;
+}
+
+static int softmax_rows(const M1Call& c, float* att) {
+  hipLaunchKernelGGL(m1_softmax_rows_kernel, dim3(c.N), dim3(64), 0, c.st, att, c.P);
+  APA_LAUNCH_CHECK("m1_softmax_rows_kernel");
+  return APA_OK;
+}
+
+template <typename T>
+static void att_gemv_fwd(const M1Call& c, const M1Fwd& io) {
+  const long NP = (long)c.N * c.P;
+  const int nb = (int)((NP + 3) / 4 < 2048 ? (NP + 3) / 4 : 2048);
+  hipLaunchKernelGGL(m1_att_gemv_fwd_kernel<T>, dim3(nb), dim3(256), 0, c.st, static_cast<const T*>(io.Xatt), io.Wa,
+                     io.ba, io.att, NP, c.Ca, c.act);
+}
+
+int m1_forward(const M1Call& c, const M1Fwd& io, M1Xent* xf) {
+  const int N = c.N, C = c.C, K = c.K;
+  M1Trace* const tr = m1_trace();
+  int rc = APA_OK;
+  if (!c.fused) {
+    // APA_IFLAG_ATT_READY, the fused cfg 003 step: the pose head's Pl kernel already left Z = Xatt . wa + ba (id / relu
+    // applied) in att
+    if (!(c.flags & APA_IFLAG_ATT_READY)) {
+      if (c.dtype == APA_DTYPE_F32) att_gemv_fwd<float>(c, io); else att_gemv_fwd<bf16_t>(c, io);
+      APA_LAUNCH_CHECK("m1_att_gemv_fwd_kernel");
+    }
+    if (c.act == M1_ACT_SOFTMAX && (rc = softmax_rows(c, io.att)) != APA_OK) return rc;
+    // att already final: the pooling kernel applies c.pool_act = id
+  }
+  switch (c.pool) {
+    case M1_POOL_STREAM: rc = m1s_launch_pool_fwd(c, io); break;
+    case M1_POOL_VEC: rc = m1v_launch_pool_fwd(c, io); break;
+    default: rc = m1g_launch_pool_fwd(c, io);
   }
   if (rc != APA_OK) return rc;
-  const int online = (fused && act == ACT_SOFTMAX) ? 1 : 0;
+  const int online = (c.fused && c.act == M1_ACT_SOFTMAX) ? 1 : 0;
   // enough blocks to put every CU to work (the kernel is bound by the bytes each CU loads)
   int cw = 256;
   while (cw > 64 && (long)N * ((C + 4 * cw - 1) / (4 * cw)) < 256) cw >>= 1;
   if (tr) tr->cw = cw;
-  hipLaunchKernelGGL(m1_finalize_fwd_kernel, dim3(N, (C + 4 * cw - 1) / (4 * cw)), dim3(256), 0, st, pacc,
-                     pstat, zsave, abar, att, P, pl.S, C, online, cw);
+  hipLaunchKernelGGL(m1_finalize_fwd_kernel, dim3(N, (C + 4 * cw - 1) / (4 * cw)), dim3(256), 0, c.st, c.pacc,
+                     c.pstat, io.zsave, io.abar, io.att, c.P, c.pl.S, C, online, cw);
   APA_LAUNCH_CHECK("m1_finalize_fwd_kernel");
   // logits = z . Wt + abar (x) bt -- the first reader of Wt / bt (apa_hooks.td_weights_ready_event)
-  if (hk.td_ready) APA_HIP_CHECK(hipStreamWaitEvent(st, hk.td_ready, 0));
+  if (c.td_ready) APA_HIP_CHECK(hipStreamWaitEvent(c.st, c.td_ready, 0));
   const bool xeval = xf && xf->probs;
-  if (cat) xf = nullptr;   // the extra channels add to the logits after the reduction: no fused loss
+  if (c.cat) xf = nullptr;   // the extra channels add to the logits after the reduction: no fused loss
   if (xf && m1_logits_xent_supported(N, C, K, xeval) &&
-      (xeval || m1_small_supported(C, K)) &&
-      ((reinterpret_cast<uintptr_t>(zsave) | reinterpret_cast<uintptr_t>(Wt) |
-        reinterpret_cast<uintptr_t>(xf->G)) & 15) == 0) {
+      m1_small_route_ok(C, K, xf->G, io.Wt, io.zsave, xeval)) {
     // training: the same conditions under which m1_backward takes the head kernel, which finishes loss[0]
     if (tr) tr->logits = xeval ? M1_LOGITS_XENT_PROBS : M1_LOGITS_XENT;
-    rc = m1_logits2_xent(zsave, Wt, abar, bt, xf->labels, logits, xf->loss, xf->G, xf->gscale, xf->probs,
-                         xf->pred, gemm_ws, N, C, K, st);
+    rc = m1_logits2_xent(io.zsave, io.Wt, io.abar, io.bt, xf->labels, io.logits, xf->loss, xf->G, xf->gscale,
+                         xf->probs, xf->pred, c.gemm_ws, N, C, K, c.st);
     xf->done = rc == APA_OK;
     return rc;
   }
-  if (m1_logits2_supported(C, K) && (reinterpret_cast<uintptr_t>(zsave) & 15) == 0) {
+  if (m1_logits2_supported(C, K) && (reinterpret_cast<uintptr_t>(io.zsave) & 15) == 0) {
     if (tr) tr->logits = M1_LOGITS2;
-    rc = m1_logits2(zsave, Wt, abar, bt, logits, gemm_ws, N, C, K, st);
+    rc = m1_logits2(io.zsave, io.Wt, io.abar, io.bt, io.logits, c.gemm_ws, N, C, K, c.st);
   } else {
     if (tr) tr->logits = M1_LOGITS_SGEMM;
-    rc = sgemm_small(zsave, C, 1, Wt, K, 1, logits, K, N, K, C, pl.lsplits, abar, bt, gemm_ws, st);
+    rc = sgemm_small(io.zsave, C, 1, io.Wt, K, 1, io.logits, K, N, K, C, c.pl.lsplits, io.abar, io.bt, c.gemm_ws, c.st);
   }
-  if (rc != APA_OK || !cat) return rc;
+  if (rc != APA_OK || !c.cat) return rc;
   // ..._WITH_POSE_FEAT: logits += zext . Wt[C:C+J]
-  return m1_cat_forward(*cat, att, Wt, logits, N, P, C, K, train, r, st);
+  return m1_cat_forward(c, io);
 }
 
-int m1_backward(const void* X, const void* Xatt, const float* Wa, const float* ba, const float* Wt,
-                const float* bt, const float* att, const float* zsave, const float* abar,
-                const float* G, void* dX, void* dXatt, float* dWa, float* dba, float* dWt,
-                float* dbt, void* ws, int N, int P, int C, int Ca, int K, unsigned flags,
-                float keep_prob, uint64_t seed, uint64_t offset, int dtype, hipStream_t st,
-                const M1Xent* xf, const Hooks& hk, const CatFeat* cat) {
-  (void)ba;
-  const bool fused = (Xatt == X);
-  const bool train = (flags & APA_FLAG_TRAIN) && keep_prob < 1.0f;
-  const int act = act_of(flags);
-  const M1Plan pl = m1_plan(N, P, C, Ca, K);
-  char* w = static_cast<char*>(ws);
-  float* pdwa = reinterpret_cast<float*>(w + pl.off_pdwa);
-  float* pdba = reinterpret_cast<float*>(w + pl.off_pdba);
-  float* dz = reinterpret_cast<float*>(w + pl.off_dz);
-  // APA_FLAG_DXATT_RANK1: the caller's dXatt buffer is fp32 [N*P] and receives dZ itself
-  const bool rank1 = (flags & APA_FLAG_DXATT_RANK1) != 0 && !fused;
-  float* dZatt = rank1 ? static_cast<float*>(dXatt) : reinterpret_cast<float*>(w + pl.off_dzatt);
-  float* gemm_ws = reinterpret_cast<float*>(w + pl.off_gemm);
-  float* sn_buf = pdba + pl.nblk;   // [N] floats: the pdba region is sized nblk + N
-  RngArgs r = rng_args(train, keep_prob, seed, offset, flags);
-  r.ev0 = hk.bwd0; r.ev1 = hk.bwd1;
+// Attention-side backward when Xatt != X, over nb blocks: the register-resident form where it serves Ca
+template <typename T>
+static void att_gemv_bwd(const M1Call& c, const M1Bwd& io, int nb) {
+  const long NP = (long)c.N * c.P;
+  const int Ca = c.Ca;
+  const T* xa = static_cast<const T*>(io.Xatt);
   M1Trace* const tr = m1_trace();
-  if (tr) { tr->S = pl.S; tr->ppb = pl.ppb; tr->nblk = pl.nblk; tr->fused = fused; tr->relu_input = r.relu_input; }
-  if (flags & APA_FLAG_WS_FROM_FWD)   // same workspace, untouched since the forward call
-    r.maskbits_in = reinterpret_cast<const uint8_t*>(w + pl.off_maskbits);
-  if (flags & APA_IFLAG_NO_DX) {
-    if (fused || !(flags & APA_FLAG_WS_FROM_FWD) || !m1_no_dx_supported(C, dtype, train) || rng_external(flags) || cat) {
-      set_error("attn_pool M=1: NO_DX needs a separate attention input, the forward half's keep bits and the bf16 "
-                "streaming kernels (internal)");
-      return APA_ERR_UNSUPPORTED;
-    }
-    r.no_dx = true;
+  if (c.gemv2) {
+    const int nvec = Ca / Vec<T>::EPV, nthr = ((nvec + 63) / 64) * 64;
+    if (tr) tr->gemv = c.rank1 ? M1_GEMV_BWD2_RANK1 : M1_GEMV_BWD2;
+    auto go = [&](auto ST) {
+      hipLaunchKernelGGL((m1_att_gemv_bwd2_kernel<T, decltype(ST)::value>), dim3(nb), dim3(nthr), 0, c.st, xa, io.Wa,
+                         c.dzatt, decltype(ST)::value ? static_cast<T*>(io.dXatt) : nullptr, c.pdwa, c.pdba, NP, Ca);
+    };
+    if (c.rank1) go(std::false_type{}); else go(std::true_type{});
+  } else {
+    if (tr) tr->gemv = M1_GEMV_BWD;
+    const size_t shm = ((size_t)4 * Ca + 8) * sizeof(float);
+    hipLaunchKernelGGL(m1_att_gemv_bwd_kernel<T>, dim3(nb), dim3(256), shm, c.st, xa, io.Wa, c.dzatt,
+                       static_cast<T*>(io.dXatt), c.pdwa, c.pdba, NP, Ca);
   }
-  if (r.relu_input && !(fused && m1s_supported(C, dtype))) {
-    set_error("attn_pool M=1: APA_FLAG_RELU_INPUT needs Xatt == X and C in {1024,2048,4096} (f32) / 2048 (bf16)");
-    return APA_ERR_UNSUPPORTED;
-  }
+}
 
-  // the staged kernels read G / Wt / z with 16-byte loads
-  const bool small_ok = m1_small_supported(C, K) &&
-                        ((reinterpret_cast<uintptr_t>(G) | reinterpret_cast<uintptr_t>(Wt) |
-                          reinterpret_cast<uintptr_t>(zsave)) & 15) == 0;
+int m1_backward(const M1Call& c, const M1Bwd& io, const M1Xent* xf) {
+  const int N = c.N, C = c.C, K = c.K;
+  hipStream_t st = c.st;
+  M1Trace* const tr = m1_trace();
   int rc;
-  if (small_ok) {
+  if (c.small) {
     // dz = G . Wt^T, dWt = z^T . G, dbt = abar^T G in one launch
     if (m1_bwd_head_supported(N, C, K)) {
-      rc = m1_bwd_head(G, Wt, zsave, abar, bt, dz, dWt, dbt, sn_buf, N, C, K, st,
+      rc = m1_bwd_head(io.G, io.Wt, io.zsave, io.abar, io.bt, c.dz, io.dWt, io.dbt, c.sn, N, C, K, st,
                        xf && xf->done ? xf->loss : nullptr, xf ? xf->lscale : 0.f);
-    } else if (xf && xf->done) {
-      set_error("attn_pool M=1: fused loss path without the head kernel (internal)");
-      return APA_ERR_UNSUPPORTED;
     } else {
       if (tr) tr->head = M1_HEAD_SMALL;
-      rc = m1_bwd_small(G, Wt, zsave, abar, bt, dz, dWt, dbt, sn_buf, N, C, K, st);
+      rc = m1_bwd_small(io.G, io.Wt, io.zsave, io.abar, io.bt, c.dz, io.dWt, io.dbt, c.sn, N, C, K, st);
     }
     if (rc != APA_OK) return rc;
   } else {
-    if (xf && xf->done) {
-      set_error("attn_pool M=1: fused loss path without the head kernel (internal)");
-      return APA_ERR_UNSUPPORTED;
-    }
     // generic fallback (very large K): dz[n,c] = sum_k G[n,k] Wt[c,k]; dWt[c,k] = sum_n z[n,c] G[n,k]
     if (tr) tr->head = M1_HEAD_SGEMM;
-    rc = sgemm_small(G, K, 1, Wt, 1, K, dz, C, N, C, K, 1, nullptr, nullptr, gemm_ws, st);
+    rc = sgemm_small(io.G, K, 1, io.Wt, 1, K, c.dz, C, N, C, K, 1, nullptr, nullptr, c.gemm_ws, st);
     if (rc != APA_OK) return rc;
-    rc = sgemm_small(zsave, 1, C, G, K, 1, dWt, K, C, K, N, 1, nullptr, nullptr, gemm_ws, st);
+    rc = sgemm_small(io.zsave, 1, C, io.G, K, 1, io.dWt, K, C, K, N, 1, nullptr, nullptr, c.gemm_ws, st);
     if (rc != APA_OK) return rc;
   }
 
-  const float* dA_extra = nullptr;
-  if (cat) {   // dWt rows C..C+J-1, dXext, and the extra channels' per-pixel share of dA
-    float* e = reinterpret_cast<float*>(w + pl.off_cat_e);
-    rc = m1_cat_backward(*cat, att, G, Wt, dWt, e, N, P, C, K, act == ACT_SOFTMAX, train, r, st);
-    if (rc != APA_OK) return rc;
-    dA_extra = e;
-  }
+  // dWt rows C..C+J-1, dXext, and the extra channels' per-pixel share of dA (c.ex)
+  if (c.cat && (rc = m1_cat_backward(c, io)) != APA_OK) return rc;
   // dWt / dbt are final here (fast path): let a data-parallel caller start their all-reduce now
-  if (small_ok && hk.grad_ready) APA_HIP_CHECK(hipEventRecord(hk.grad_ready, st));
+  if (c.small && c.grad_ready) APA_HIP_CHECK(hipEventRecord(c.grad_ready, st));
 
-  const bool ext = train && rng_external(flags);
-  if (ext && !m1g_supported(C, dtype)) {
-    set_error("attn_pool M=1: APA_FLAG_RNG_EXTERNAL: C=%d is not served by the generic M == 1 kernels", C);
-    return APA_ERR_UNSUPPORTED;
-  }
-  if (!ext && m1s_supported(C, dtype))
-    rc = m1s_launch_bwd_main(dtype, C, fused, train, pl.nblk, st, X, Wa, att, dz, zsave, abar, G,
-                             bt, small_ok ? sn_buf : nullptr, dX, dZatt, pdwa, pdba, P, pl.S, K,
-                             act, r, dA_extra);
-  else if (!ext && vec_kernels_supported(C, dtype))
-    rc = APA_DISPATCH_VEC(launch_bwd_main, dtype, C, fused, train, pl.nblk, st, X, Wa, att, dz,
-                          zsave, abar, G, bt, small_ok ? sn_buf : nullptr, dX, dZatt, pdwa, pdba,
-                          P, pl.S, K, act, r, dA_extra);
-  else {
-    if (tr) tr->pool_bwd = M1_POOL_GENERIC;
-    rc = m1g_launch_bwd_main(dtype, C, fused, train, pl.nblk, st, X, Wa, att, dz, zsave, abar, G, bt,
-                             small_ok ? sn_buf : nullptr, dX, dZatt, pdwa, pdba, P, pl.S, K, act, r, dA_extra);
+  switch (c.pool) {
+    case M1_POOL_STREAM: rc = m1s_launch_bwd_main(c, io); break;
+    case M1_POOL_VEC: rc = m1v_launch_bwd_main(c, io); break;
+    default: rc = m1g_launch_bwd_main(c, io);
   }
   if (rc != APA_OK) return rc;
 
-  int nred = pl.nblk;
+  // APA_IFLAG_NO_ATT_WGRAD, fused cfg 003 step: dWa = Xatt^T dZ and dba = sum dZ ride on the pose head's backward rows
+  // kernel (dZ is a 17th column of dPl there), and its column-sum launch advances the dropout counter
+  if (c.flags & APA_IFLAG_NO_ATT_WGRAD) return APA_OK;
+  int nred = c.pl.nblk;
   int cred = C;
-  if (flags & APA_IFLAG_NO_ATT_WGRAD) {
-    // fused cfg 003 step: dWa = Xatt^T dZ and dba = sum dZ ride on the pose head's backward rows kernel (dZ is a
-    // 17th column of dPl there), and its column-sum launch advances the dropout counter
-    if (!rank1 || !small_ok) {
-      set_error("attn_pool M=1: NO_ATT_WGRAD needs the rank-1 dXatt form and the small-K head kernels (internal)");
-      return APA_ERR_UNSUPPORTED;
-    }
-    return APA_OK;
-  }
-  if (!fused) {
-    const long NP = (long)N * P;
+  if (!c.fused) {
+    const long NP = (long)N * c.P;
     int nb = (int)((NP + 15) / 16);
     if (nb > 1024) nb = 1024;
     if (nb < 1) nb = 1;
-    if (nb > pl.nblk) nb = pl.nblk;  // partial buffer is sized for nblk rows
-    const size_t shm = ((size_t)4 * Ca + 8) * sizeof(float);
-    const int epv = dtype == APA_DTYPE_F32 ? 4 : 8;
-    if (Ca % epv == 0 && Ca / epv <= 256) {   // register-resident form
-      const int nthr = ((Ca / epv + 63) / 64) * 64;
-      if (tr) tr->gemv = rank1 ? M1_GEMV_BWD2_RANK1 : M1_GEMV_BWD2;
-#define APA_GB2(T, ST)                                                                        \
-  hipLaunchKernelGGL((m1_att_gemv_bwd2_kernel<T, ST>), dim3(nb), dim3(nthr), 0, st,               \
-                     static_cast<const T*>(Xatt), Wa, dZatt, ST ? static_cast<T*>(dXatt) : nullptr, \
-                     pdwa, pdba, NP, Ca)
-      if (dtype == APA_DTYPE_F32) { if (rank1) APA_GB2(float, false); else APA_GB2(float, true); }
-      else { if (rank1) APA_GB2(bf16_t, false); else APA_GB2(bf16_t, true); }
-#undef APA_GB2
-    } else if (rank1) {
-      set_error("attn_pool M=1: APA_FLAG_DXATT_RANK1: Ca=%d not served by the register-resident GEMV", Ca);
-      return APA_ERR_UNSUPPORTED;
-    } else {
-      if (tr) tr->gemv = M1_GEMV_BWD;
-      if (dtype == APA_DTYPE_F32)
-        hipLaunchKernelGGL(m1_att_gemv_bwd_kernel<float>, dim3(nb), dim3(256), shm, st,
-                           static_cast<const float*>(Xatt), Wa, dZatt, static_cast<float*>(dXatt),
-                           pdwa, pdba, NP, Ca);
-      else
-        hipLaunchKernelGGL(m1_att_gemv_bwd_kernel<bf16_t>, dim3(nb), dim3(256), shm, st,
-                           static_cast<const bf16_t*>(Xatt), Wa, dZatt, static_cast<bf16_t*>(dXatt),
-                           pdwa, pdba, NP, Ca);
-    }
+    if (nb > c.pl.nblk) nb = c.pl.nblk;  // partial buffer is sized for nblk rows
+    if (c.dtype == APA_DTYPE_F32) att_gemv_bwd<float>(c, io, nb); else att_gemv_bwd<bf16_t>(c, io, nb);
     APA_LAUNCH_CHECK("m1_att_gemv_bwd_kernel");
     nred = nb;
-    cred = Ca;
+    cred = c.Ca;
   }
-  uint64_t* bump = (train && (flags & APA_FLAG_RNG_DEVICE))
-                       ? reinterpret_cast<uint64_t*>(static_cast<uintptr_t>(offset))
-                       : nullptr;
-  if (tr) { tr->reduce = small_ok ? M1_REDUCE_COLSUM : M1_REDUCE_BWD_REDUCE; tr->rng_bump = bump != nullptr; }
-  if (small_ok) {
+  if (tr) { tr->reduce = c.small ? M1_REDUCE_COLSUM : M1_REDUCE_BWD_REDUCE; tr->rng_bump = c.bump != nullptr; }
+  if (c.small) {
     ColsumArgs cs;
-    cs.pdwa = pdwa; cs.pdba = pdba; cs.nblk = nred; cs.C = cred; cs.ld = cred; cs.dwa = dWa; cs.dba = dba; cs.rng_bump = bump;
+    cs.pdwa = c.pdwa; cs.pdba = c.pdba; cs.nblk = nred; cs.C = cred; cs.ld = cred; cs.dwa = io.dWa; cs.dba = io.dba;
+    cs.rng_bump = c.bump;
     return m1_colsum(cs, st);
   }
-  hipLaunchKernelGGL(m1_bwd_reduce_kernel, dim3((cred + 63) / 64 + 1), dim3(256), 0, st, pdwa, pdba,
-                     dWa, dba, abar, G, dbt, nred, cred, N, K, 1, bump);
+  hipLaunchKernelGGL(m1_bwd_reduce_kernel, dim3((cred + 63) / 64 + 1), dim3(256), 0, st, c.pdwa, c.pdba,
+                     io.dWa, io.dba, io.abar, io.G, io.dbt, nred, cred, N, K, 1, c.bump);
   APA_LAUNCH_CHECK("m1_bwd_reduce_kernel");
-  if (hk.grad_ready) APA_HIP_CHECK(hipEventRecord(hk.grad_ready, st));   // dbt comes last here
+  if (c.grad_ready) APA_HIP_CHECK(hipEventRecord(c.grad_ready, st));   // dbt comes last here
   return APA_OK;
 }
 

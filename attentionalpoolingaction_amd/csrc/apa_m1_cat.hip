@@ -128,27 +128,27 @@ __global__ __launch_bounds__(256) void m1_cat_bwd_kernel(
 
 bool m1_cat_supported(int J) { return J >= 1 && J <= CAT_MAX_J; }
 
-int m1_cat_forward(const CatFeat& cat, const float* att, const float* Wt, float* logits, int N, int P,
-                   int C, int K, bool train, const M1Rng& r, hipStream_t st) {
-  const uint64_t ebase = (uint64_t)N * P * C;
+int m1_cat_forward(const M1Call& c, const M1Fwd& io) {
+  const CatFeat& cat = *c.cat;
+  const uint64_t ebase = (uint64_t)c.N * c.P * c.C;
   if (M1Trace* t = m1_trace()) t->cat_fwd = cat.J;
-  hipLaunchKernelGGL(m1_cat_pool_kernel, dim3(N), dim3(256), 0, st, cat.Xext, att, cat.zext, P, cat.J, ebase,
-                     train ? 1 : 0, r.inv_keep, r.thresh, r.seed, r.offset, r.offset_dev);
+  hipLaunchKernelGGL(m1_cat_pool_kernel, dim3(c.N), dim3(256), 0, c.st, cat.Xext, io.att, cat.zext, c.P, cat.J, ebase,
+                     c.train ? 1 : 0, c.inv_keep, c.key.thresh, c.key.seed, c.key.offset, c.key.offset_dev);
   APA_LAUNCH_CHECK("m1_cat_pool_kernel");
-  hipLaunchKernelGGL(m1_cat_logits_add_kernel, dim3((N * K + 255) / 256), dim3(256), 0, st, cat.zext,
-                     Wt + (size_t)C * K, logits, N, cat.J, K);
+  hipLaunchKernelGGL(m1_cat_logits_add_kernel, dim3((c.N * c.K + 255) / 256), dim3(256), 0, c.st, cat.zext,
+                     io.Wt + (size_t)c.C * c.K, io.logits, c.N, cat.J, c.K);
   APA_LAUNCH_CHECK("m1_cat_logits_add_kernel");
   return APA_OK;
 }
 
-int m1_cat_backward(const CatFeat& cat, const float* att, const float* G, const float* Wt, float* dWt,
-                    float* e_out, int N, int P, int C, int K, bool softmax, bool train, const M1Rng& r,
-                    hipStream_t st) {
-  const uint64_t ebase = (uint64_t)N * P * C;
+int m1_cat_backward(const M1Call& c, const M1Bwd& io) {
+  const CatFeat& cat = *c.cat;
+  const uint64_t ebase = (uint64_t)c.N * c.P * c.C;
   if (M1Trace* t = m1_trace()) t->cat_bwd = cat.J;
-  hipLaunchKernelGGL(m1_cat_bwd_kernel, dim3(N + 1), dim3(256), 0, st, cat.Xext, att, cat.zext, G,
-                     Wt + (size_t)C * K, cat.dXext, dWt + (size_t)C * K, e_out, N, P, cat.J, K, ebase,
-                     softmax ? 1 : 0, train ? 1 : 0, r.inv_keep, r.thresh, r.seed, r.offset, r.offset_dev);
+  hipLaunchKernelGGL(m1_cat_bwd_kernel, dim3(c.N + 1), dim3(256), 0, c.st, cat.Xext, io.att, cat.zext, io.G,
+                     io.Wt + (size_t)c.C * c.K, cat.dXext, io.dWt + (size_t)c.C * c.K, c.cat_e, c.N, c.P, cat.J, c.K,
+                     ebase, c.act == M1_ACT_SOFTMAX ? 1 : 0, c.train ? 1 : 0, c.inv_keep, c.key.thresh, c.key.seed,
+                     c.key.offset, c.key.offset_dev);
   APA_LAUNCH_CHECK("m1_cat_bwd_kernel");
   return APA_OK;
 }

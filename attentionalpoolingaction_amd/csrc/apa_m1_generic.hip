@@ -4,7 +4,8 @@
 // The head is backbone-agnostic in the reference (models/slim/nets/nets_factory.py:63-67 taps 512-, 1024-
 // and 2048-channel maps; any slim backbone can be added to last_conv_map), so the op must not return
 // APA_ERR_UNSUPPORTED for a channel count the register-resident kernels were not instantiated for
-// (apa_m1_stream.hip: C in {1024, 2048, 4096}; apa_m1.hip: C in {256 .. 2048 / 4096}).  These two kernels
+// (apa_m1_stream.hip: C in {1024, 2048, 4096} fp32 / 2048 bf16; apa_m1_vec.hip: C in {256, 512} fp32 / {512, 1024}
+// bf16).  These two kernels
 // are the shape-generic arm: same block / pixel ownership, same per-block partial outputs (pacc, pstat,
 // pdwa, pdba) and therefore the same finalize / logits / head / column-sum kernels after them, but the
 // channel loop runs at run time and the per-wave channel accumulators live in LDS instead of registers
@@ -18,8 +19,6 @@
 namespace apa {
 
 namespace {
-enum { G_ACT_ID = 0, G_ACT_RELU = 1, G_ACT_SOFTMAX = 2 };
-
 template <typename T, bool FUSED, bool TRAIN>
 __global__ __launch_bounds__(256) void m1g_pool_fwd_kernel(
     const T* __restrict__ X, const float* __restrict__ Wa, const float* __restrict__ ba,
@@ -53,7 +52,7 @@ __global__ __launch_bounds__(256) void m1g_pool_fwd_kernel(
         for (int e = 0; e < EPV; ++e) d = fmaf(x[e], Wa[v * EPV + e], d);
       }
       const float zl = wave_sum(d) + bias;
-      if (act == G_ACT_SOFTMAX) {
+      if (act == M1_ACT_SOFTMAX) {
         const float m_new = fmaxf(m_run, zl);
         scale = expf(m_run - m_new);   // exp(-inf) = 0 on the first pixel
         a = expf(zl - m_new);
@@ -61,7 +60,7 @@ __global__ __launch_bounds__(256) void m1g_pool_fwd_kernel(
         m_run = m_new;
         if (lane == 0) att_im[p] = zl;   // raw logit; normalised by the finalize kernel
       } else {
-        a = (act == G_ACT_RELU) ? fmaxf(zl, 0.f) : zl;
+        a = (act == M1_ACT_RELU) ? fmaxf(zl, 0.f) : zl;
         if (lane == 0) att_im[p] = a;
       }
     } else {
@@ -92,7 +91,7 @@ __global__ __launch_bounds__(256) void m1g_pool_fwd_kernel(
   __syncthreads();
   float ws[4] = {1.f, 1.f, 1.f, 1.f};
   float m_blk = 0.f, l_blk = 0.f;
-  if (act == G_ACT_SOFTMAX && FUSED) {
+  if (act == M1_ACT_SOFTMAX && FUSED) {
     m_blk = fmaxf(fmaxf(sm_stat[0], sm_stat[4]), fmaxf(sm_stat[8], sm_stat[12]));
 #pragma unroll
     for (int w = 0; w < 4; ++w) {
@@ -143,7 +142,7 @@ __global__ __launch_bounds__(256) void m1g_bwd_main_kernel(
     sn = wave_sum(sn);
   }
   float corr = 0.f;
-  if (act == G_ACT_SOFTMAX) {   // z . dz + (G . bt) * abar
+  if (act == M1_ACT_SOFTMAX) {   // z . dz + (G . bt) * abar
     float zdz = 0.f;
     for (int c = lane; c < C; c += 64) zdz = fmaf(zsave[(size_t)n * C + c], dzr[c], zdz);
     corr = wave_sum(zdz) + sn * abar[n];
@@ -172,8 +171,8 @@ __global__ __launch_bounds__(256) void m1g_bwd_main_kernel(
     const float ex = dA_extra[(size_t)n * P + p] * extra_scale;
     const float dA = (tot + sn + ex) * invP;
     float dZ;
-    if (act == G_ACT_SOFTMAX) dZ = a * (dA - corr);
-    else if (act == G_ACT_RELU) dZ = a > 0.f ? dA : 0.f;
+    if (act == M1_ACT_SOFTMAX) dZ = a * (dA - corr);
+    else if (act == M1_ACT_RELU) dZ = a > 0.f ? dA : 0.f;
     else dZ = dA;
     const float ap = a * invP * (TRAIN ? inv_keep : 1.f);
     for (int v = lane; v < nvec; v += 64) {
@@ -239,56 +238,48 @@ bool m1g_supported(int C, int dtype) {
   return C >= epv && C % epv == 0 && (size_t)4 * C * 4 + 64 <= cap;   // 4 accumulator rows in LDS
 }
 
-int m1g_launch_pool_fwd(int dtype, int C, bool fused, bool train, int nblk, hipStream_t st, const void* X,
-                        const float* Wa, const float* ba, float* att, float* pacc, float* pstat, int P, int S,
-                        int act, const M1Rng& r) {
-  const size_t shm = (size_t)4 * C * 4 + 64;
-#define APA_GG(T, F, TR)                                                                                \
-  do {                                                                                                  \
-    int rc = set_lds(m1g_pool_fwd_kernel<T, F, TR>, shm);                                               \
-    if (rc != APA_OK) return rc;                                                                        \
-    launch_ev(m1g_pool_fwd_kernel<T, F, TR>, dim3(nblk), dim3(256), shm, st, r.ev0, r.ev1,              \
-              static_cast<const T*>(X), Wa, ba, att, pacc, pstat, P, S, C, act, r.inv_keep, r.thresh, r.seed, \
-              r.offset, r.offset_dev);                                                                  \
-  } while (0)
-#define APA_GG2(T)                                                                  \
-  do {                                                                              \
-    if (fused) { if (train) APA_GG(T, true, true); else APA_GG(T, true, false); }   \
-    else       { if (train) APA_GG(T, false, true); else APA_GG(T, false, false); } \
-  } while (0)
-  if (dtype == APA_DTYPE_F32) APA_GG2(float); else APA_GG2(bf16_t);
-#undef APA_GG2
-#undef APA_GG
+template <typename T>
+static int launch_fwd_t(const M1Call& c, const M1Fwd& io) {
+  const size_t shm = (size_t)4 * c.C * 4 + 64;
+  if (M1Trace* t = m1_trace()) t->pool_fwd = M1_POOL_GENERIC;
+  int rc = m1_fused_train(c.fused, c.train, [&](auto F, auto TR) -> int {
+    auto kernel = m1g_pool_fwd_kernel<T, decltype(F)::value, decltype(TR)::value>;
+    int rc = set_lds(kernel, shm);
+    if (rc != APA_OK) return rc;
+    launch_ev(kernel, dim3(c.pl.nblk), dim3(256), shm, c.st, c.ev0, c.ev1, static_cast<const T*>(io.X), io.Wa, io.ba,
+              io.att, c.pacc, c.pstat, c.P, c.pl.S, c.C, c.pool_act, c.inv_keep, c.key.thresh, c.key.seed,
+              c.key.offset, c.key.offset_dev);
+    return APA_OK;
+  });
+  if (rc != APA_OK) return rc;
   APA_LAUNCH_CHECK("m1g_pool_fwd_kernel");
   return APA_OK;
 }
 
-int m1g_launch_bwd_main(int dtype, int C, bool fused, bool train, int nblk, hipStream_t st, const void* X,
-                        const float* Wa, const float* att, const float* dz, const float* zsave,
-                        const float* abar, const float* G, const float* bt, const float* sn_pre, void* dX,
-                        float* dZout, float* pdwa, float* pdba, int P, int S, int K, int act, const M1Rng& r,
-                        const float* dA_extra) {
-  const size_t shm = (fused ? (size_t)4 * C * 4 : 0) + 64;
-  const float* ex = dA_extra ? dA_extra : att;
-  const float exs = dA_extra ? 1.0f : 0.0f;
-#define APA_GG(T, F, TR)                                                                                \
-  do {                                                                                                  \
-    int rc = set_lds(m1g_bwd_main_kernel<T, F, TR>, shm);                                               \
-    if (rc != APA_OK) return rc;                                                                        \
-    launch_ev(m1g_bwd_main_kernel<T, F, TR>, dim3(nblk), dim3(256), shm, st, r.ev0, r.ev1,              \
-              static_cast<const T*>(X), Wa, att, dz, zsave, abar, G, bt, sn_pre, static_cast<T*>(dX), dZout, \
-              pdwa, pdba, P, S, C, K, act, r.inv_keep, r.thresh, r.seed, r.offset, r.offset_dev, ex, exs); \
-  } while (0)
-#define APA_GG2(T)                                                                  \
-  do {                                                                              \
-    if (fused) { if (train) APA_GG(T, true, true); else APA_GG(T, true, false); }   \
-    else       { if (train) APA_GG(T, false, true); else APA_GG(T, false, false); } \
-  } while (0)
-  if (dtype == APA_DTYPE_F32) APA_GG2(float); else APA_GG2(bf16_t);
-#undef APA_GG2
-#undef APA_GG
+template <typename T>
+static int launch_bwd_t(const M1Call& c, const M1Bwd& io) {
+  const size_t shm = (c.fused ? (size_t)4 * c.C * 4 : 0) + 64;
+  if (M1Trace* t = m1_trace()) t->pool_bwd = M1_POOL_GENERIC;
+  int rc = m1_fused_train(c.fused, c.train, [&](auto F, auto TR) -> int {
+    auto kernel = m1g_bwd_main_kernel<T, decltype(F)::value, decltype(TR)::value>;
+    int rc = set_lds(kernel, shm);
+    if (rc != APA_OK) return rc;
+    launch_ev(kernel, dim3(c.pl.nblk), dim3(256), shm, c.st, c.ev0, c.ev1, static_cast<const T*>(io.X), io.Wa, io.att,
+              c.dz, io.zsave, io.abar, io.G, io.bt, c.sn, static_cast<T*>(io.dX), c.dzatt, c.pdwa, c.pdba, c.P,
+              c.pl.S, c.C, c.K, c.act, c.inv_keep, c.key.thresh, c.key.seed, c.key.offset, c.key.offset_dev, c.ex,
+              c.exs);
+    return APA_OK;
+  });
+  if (rc != APA_OK) return rc;
   APA_LAUNCH_CHECK("m1g_bwd_main_kernel");
   return APA_OK;
+}
+
+int m1g_launch_pool_fwd(const M1Call& c, const M1Fwd& io) {
+  return c.dtype == APA_DTYPE_F32 ? launch_fwd_t<float>(c, io) : launch_fwd_t<bf16_t>(c, io);
+}
+int m1g_launch_bwd_main(const M1Call& c, const M1Bwd& io) {
+  return c.dtype == APA_DTYPE_F32 ? launch_bwd_t<float>(c, io) : launch_bwd_t<bf16_t>(c, io);
 }
 
 }  // namespace apa

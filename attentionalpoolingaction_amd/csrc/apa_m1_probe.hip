@@ -32,7 +32,7 @@ void apa_probe_m1_plan(int N, int P, int C, int Ca, int K, int64_t* out) {
 // which families have an instance for (C, dtype), and which small-product kernels accept (C, K):
 // bit 0 stream, 1 per-pixel vec, 2 generic, 3 m1_logits2, 4 m1_small (bwd_small / head), 5 bwd_head
 int apa_probe_m1_support(int N, int C, int K, int dtype) {
-  return (apa::m1s_supported(C, dtype) ? 1 : 0) | (apa::m1_vec_supported(C, dtype) ? 2 : 0) |
+  return (apa::m1s_supported(C, dtype) ? 1 : 0) | (apa::m1v_supported(C, dtype) ? 2 : 0) |
          (apa::m1g_supported(C, dtype) ? 4 : 0) | (apa::m1_logits2_supported(C, K) ? 8 : 0) |
          (apa::m1_small_supported(C, K) ? 16 : 0) | (apa::m1_bwd_head_supported(N, C, K) ? 32 : 0);
 }

@@ -15,7 +15,7 @@
 //     (lane & 15), bit-identical in all four waves (fixed summation order);
 //   * the channel accumulators (z partials, dwa partials) are private to a wave, so they go from
 //     registers straight to the per-block partial row -- no cross-wave LDS reduction.
-// X is read once per pass and dX written once, exactly like the per-pixel kernels in apa_m1.hip
+// X is read once per pass and dX written once, exactly like the per-pixel kernels in apa_m1_vec.hip
 // (which stay as the path for narrow maps).
 #include <math.h>
 
@@ -40,8 +40,6 @@
 namespace apa {
 
 namespace {
-enum { S_ACT_ID = 0, S_ACT_RELU = 1, S_ACT_SOFTMAX = 2 };
-
 // Every wave passes its PIX per-lane partial dot products d[i] (pixel slot i, this wave's channel
 // share).  Returns, in lane l of every wave, the block total of slot (l & 15).
 //   sm: 256 floats, layout [wave][slot][row]; written conflict-free, read back as one float4.
@@ -156,7 +154,7 @@ __device__ __forceinline__ ChunkRange chunk_range(int p_begin, int p_end, int ch
 }
 
 // --------------------------------------------------------------------------------------------
-// Forward pooling pass.  Outputs are those of m1_pool_fwd_kernel (apa_m1.hip):
+// Forward pooling pass.  Outputs are those of m1_pool_fwd_kernel (apa_m1_vec.hip):
 //   att (FUSED: id/relu -> final A, softmax -> raw Z, normalised by the finalize kernel),
 //   pacc[blk][C] = sum_p A*Xt over the block's pixels (softmax: relative to pstat m),
 //   pstat[blk][4] = {m, l, asum, -}.
@@ -218,7 +216,7 @@ __device__ __forceinline__ void fwd_chunk(FwdState<T, VW, PIX, FUSED, TRAIN>& st
       d[i] = d0 + d1;
     }
     const float zt = block_dots<PIX>(d, sm, wave, lane) + st.bias;
-    if (act == S_ACT_SOFTMAX) {
+    if (act == M1_ACT_SOFTMAX) {
       const float m_chunk = row_max16(l16 < np ? zt : -INFINITY);
       const float m_new = fmaxf(st.m_run, m_chunk);
       const float scale = expf(st.m_run - m_new);   // exp(-inf) = 0 on the first chunk
@@ -229,7 +227,7 @@ __device__ __forceinline__ void fwd_chunk(FwdState<T, VW, PIX, FUSED, TRAIN>& st
 #pragma unroll
       for (int i = 0; i < EPL; ++i) st.acc[i] *= scale;
     } else {
-      av = (act == S_ACT_RELU) ? fmaxf(zt, 0.f) : zt;
+      av = (act == M1_ACT_RELU) ? fmaxf(zt, 0.f) : zt;
       if (l16 >= np) av = 0.f;
       if (wave == 0 && lane < np) att_im[q0 + lane] = av;
     }
@@ -367,7 +365,7 @@ __global__ __launch_bounds__(256, 2) void m1s_pool_fwd_kernel(
     }
   }
   if (threadIdx.x == 0) {
-    pstat[blk * 4 + 0] = (FUSED && act == S_ACT_SOFTMAX) ? st.m_run : 0.f;
+    pstat[blk * 4 + 0] = (FUSED && act == M1_ACT_SOFTMAX) ? st.m_run : 0.f;
     pstat[blk * 4 + 1] = st.l_run;
     pstat[blk * 4 + 2] = st.a_sum;
     pstat[blk * 4 + 3] = 0.f;
@@ -376,7 +374,7 @@ __global__ __launch_bounds__(256, 2) void m1s_pool_fwd_kernel(
 
 // --------------------------------------------------------------------------------------------
 // Backward streaming pass (the dominant kernel: reads X once, writes dX once).  Same outputs as
-// m1_bwd_main_kernel (apa_m1.hip): dX, dZout (!FUSED), pdwa[blk][C], pdba[blk] (FUSED).
+// m1_bwd_main_kernel (apa_m1_vec.hip): dX, dZout (!FUSED), pdwa[blk][C], pdba[blk] (FUSED).
 // --------------------------------------------------------------------------------------------
 template <typename T, int VW, int PIX, bool FUSED, bool TRAIN>
 struct BwdState {
@@ -439,8 +437,8 @@ __device__ __forceinline__ void bwd_chunk(BwdState<T, VW, PIX, FUSED, TRAIN>& st
   if (TRAIN) tot *= inv_keep;
   const float dA = (tot + st.sn + e_l) * invP;   // e_l: extra channels' share (apa_m1_cat.hip), else 0
   float dZl;
-  if (act == S_ACT_SOFTMAX) dZl = a_l * (dA - st.corr);
-  else if (act == S_ACT_RELU) dZl = a_l > 0.f ? dA : 0.f;
+  if (act == M1_ACT_SOFTMAX) dZl = a_l * (dA - st.corr);
+  else if (act == M1_ACT_RELU) dZl = a_l > 0.f ? dA : 0.f;
   else dZl = dA;
   if (!FUSED && wave == 0 && lane < np) dZout_im[q0 + lane] = dZl;
   // NODX (separate attention input, fused cfg 003 step): the dX share A/P . dz . mask/keep is formed by the pose
@@ -573,7 +571,7 @@ __global__ __launch_bounds__(256, 2) void m1s_bwd_main_kernel(
           st.wa[i] = w.x; st.wa[i + 1] = w.y; st.wa[i + 2] = w.z; st.wa[i + 3] = w.w;
           st.dwa[i] = 0.f; st.dwa[i + 1] = 0.f; st.dwa[i + 2] = 0.f; st.dwa[i + 3] = 0.f;
         }
-        if (act == S_ACT_SOFTMAX) {
+        if (act == M1_ACT_SOFTMAX) {
           const float4 zz = *reinterpret_cast<const float4*>(zsave + (size_t)n * C + c);
           zdz = fmaf(zz.x, dd.x, zdz); zdz = fmaf(zz.y, dd.y, zdz);
           zdz = fmaf(zz.z, dd.z, zdz); zdz = fmaf(zz.w, dd.w, zdz);
@@ -587,7 +585,7 @@ __global__ __launch_bounds__(256, 2) void m1s_bwd_main_kernel(
       for (int k = lane; k < K; k += 64) sn = fmaf(G[(size_t)n * K + k], bt[k], sn);
       st.sn = wave_sum(sn);
     }
-    if (act == S_ACT_SOFTMAX) {   // corr = z.dz + (G.bt) * abar, z.dz summed over the 4 waves
+    if (act == M1_ACT_SOFTMAX) {   // corr = z.dz + (G.bt) * abar, z.dz summed over the 4 waves
       zdz = wave_sum(zdz);
       if (lane == 0) sm_aux[wave] = zdz;
       __syncthreads();
@@ -643,125 +641,75 @@ bool m1s_supported(int C, int dtype) {
 template <typename T, int VW> constexpr int kPix = sizeof(T) == 2 ? 2 : (VW == 4 ? 2 : 1);
 
 template <typename T, int VW>
-static int launch_fwd_t(bool fused, bool train, int nblk, hipStream_t st, const void* X,
-                        const float* Wa, const float* ba, float* att, float* pacc, float* pstat,
-                        int P, int S, int act, const M1Rng& r) {
+static int launch_fwd_t(const M1Call& c, const M1Fwd& io) {
   constexpr int PIX = kPix<T, VW>;
-  const T* x = static_cast<const T*>(X);
-  uint8_t* mbits = r.maskbits_out;
   if (M1Trace* t = m1_trace()) { t->pool_fwd = M1_POOL_STREAM; t->fwd_w = VW; t->fwd_pix = PIX; }
-  if (r.relu_input) {   // instantiated for the fused map only
-    if (!fused) {
-      set_error("attn_pool M=1 stream kernels: APA_FLAG_RELU_INPUT needs Xatt == X");
-      return APA_ERR_UNSUPPORTED;
-    }
-    if (train)
-      launch_ev(m1s_pool_fwd_kernel<T, VW, PIX, true, true, true>, dim3(nblk), dim3(256), 0, st, r.ev0, r.ev1, x, Wa, ba, att, pacc, pstat, P, S, act, r.inv_keep, r.thresh, r.seed,
-                         r.offset, r.offset_dev, mbits);
-    else
-      launch_ev(m1s_pool_fwd_kernel<T, VW, PIX, true, false, true>, dim3(nblk), dim3(256), 0, st, r.ev0, r.ev1, x, Wa, ba, att, pacc, pstat, P, S, act, r.inv_keep, r.thresh, r.seed,
-                         r.offset, r.offset_dev, mbits);
-    APA_LAUNCH_CHECK("m1s_pool_fwd_kernel");
+  auto go = [&](auto F, auto TR, auto RIN) {
+    launch_ev(m1s_pool_fwd_kernel<T, VW, PIX, decltype(F)::value, decltype(TR)::value, decltype(RIN)::value>,
+              dim3(c.pl.nblk), dim3(256), 0, c.st, c.ev0, c.ev1, static_cast<const T*>(io.X), io.Wa, io.ba, io.att,
+              c.pacc, c.pstat, c.P, c.pl.S, c.pool_act, c.inv_keep, c.key.thresh, c.key.seed, c.key.offset,
+              c.key.offset_dev, c.maskbits);
     return APA_OK;
+  };
+  const std::true_type yes; const std::false_type no;
+  if (c.relu_input) {   // instantiated for the fused map only
+    if (c.train) go(yes, yes, yes); else go(yes, no, yes);
+  } else {
+    m1_fused_train(c.fused, c.train, [&](auto F, auto TR) { return go(F, TR, no); });
   }
-#define APA_GO(F, TR)                                                                            \
-  launch_ev(m1s_pool_fwd_kernel<T, VW, PIX, F, TR>, dim3(nblk), dim3(256), 0, st, r.ev0, r.ev1, x,  \
-                     Wa, ba, att, pacc, pstat, P, S, act, r.inv_keep, r.thresh, r.seed,          \
-                     r.offset, r.offset_dev, mbits)
-  if (fused) { if (train) APA_GO(true, true); else APA_GO(true, false); }
-  else       { if (train) APA_GO(false, true); else APA_GO(false, false); }
-#undef APA_GO
   APA_LAUNCH_CHECK("m1s_pool_fwd_kernel");
   return APA_OK;
 }
 
 template <typename T, int VW>
-static int launch_bwd_t(bool fused, bool train, int nblk, hipStream_t st, const void* X,
-                        const float* Wa, const float* att, const float* dz, const float* zsave,
-                        const float* abar, const float* G, const float* bt, const float* sn_pre,
-                        void* dX, float* dZout, float* pdwa, float* pdba, int P, int S, int K,
-                        int act, const M1Rng& r, const float* dA_extra) {
+static int launch_bwd_t(const M1Call& c, const M1Bwd& io) {
   constexpr int PIX = kPix<T, VW>;
-  const T* x = static_cast<const T*>(X);
-  T* dx = static_cast<T*>(dX);
-  const float* ex = dA_extra ? dA_extra : att;
-  const float exs = dA_extra ? 1.0f : 0.0f;
-  const uint8_t* mbits = r.maskbits_in;    // non-null: the forward call's keep-bits (APA_FLAG_WS_FROM_FWD)
   M1Trace* const tr = m1_trace();
   if (tr) { tr->pool_bwd = M1_POOL_STREAM; tr->bwd_w = VW; tr->bwd_pix = PIX; }
-  if (r.relu_input) {
-    if (!fused) {
-      set_error("attn_pool M=1 stream kernels: APA_FLAG_RELU_INPUT needs Xatt == X");
-      return APA_ERR_UNSUPPORTED;
-    }
-    if (train)
-      launch_ev(m1s_bwd_main_kernel<T, VW, PIX, true, true, true>, dim3(nblk), dim3(256), 0, st, r.ev0, r.ev1, x, Wa, att, dz, zsave, abar, G, bt, sn_pre, dx, dZout, pdwa, pdba, P, S, K,
-                         act, r.inv_keep, r.thresh, r.seed, r.offset, r.offset_dev, ex, exs, nullptr);
-    else
-      launch_ev(m1s_bwd_main_kernel<T, VW, PIX, true, false, true>, dim3(nblk), dim3(256), 0, st, r.ev0, r.ev1, x, Wa, att, dz, zsave, abar, G, bt, sn_pre, dx, dZout, pdwa, pdba, P, S, K,
-                         act, r.inv_keep, r.thresh, r.seed, r.offset, r.offset_dev, ex, exs, nullptr);
-    APA_LAUNCH_CHECK("m1s_bwd_main_kernel");
+  // non-null: the forward call's keep-bits (APA_FLAG_WS_FROM_FWD)
+  const uint8_t* mbits = c.relu_input ? nullptr : c.maskbits_in;
+  auto go = [&](auto F, auto TR, auto RIN, auto BITS, auto NODX) {
+    launch_ev(m1s_bwd_main_kernel<T, VW, PIX, decltype(F)::value, decltype(TR)::value, decltype(RIN)::value,
+                                  decltype(BITS)::value, decltype(NODX)::value>,
+              dim3(c.pl.nblk), dim3(256), 0, c.st, c.ev0, c.ev1, static_cast<const T*>(io.X), io.Wa, io.att, c.dz,
+              io.zsave, io.abar, io.G, io.bt, c.sn, static_cast<T*>(io.dX), c.dzatt, c.pdwa, c.pdba, c.P, c.pl.S,
+              c.K, c.act, c.inv_keep, c.key.thresh, c.key.seed, c.key.offset, c.key.offset_dev, c.ex, c.exs, mbits);
     return APA_OK;
-  }
-#define APA_GO(F, TR, BT)                                                                         \
-  launch_ev(m1s_bwd_main_kernel<T, VW, PIX, F, TR, false, BT>, dim3(nblk), dim3(256), 0, st, r.ev0, r.ev1, x, \
-            Wa, att, dz, zsave, abar, G, bt, sn_pre, dx, dZout, pdwa, pdba, P, S, K, act, r.inv_keep,   \
-            r.thresh, r.seed, r.offset, r.offset_dev, ex, exs, mbits)
-  bool bits_done = false;
-  if constexpr (KeepBits<T>::ON) {   // the keep-bits variant: bf16 features
-    if (train && mbits && !fused && r.no_dx) {   // ... without the dX stores (APA_IFLAG_NO_DX)
-      launch_ev(m1s_bwd_main_kernel<T, VW, PIX, false, true, false, true, true>, dim3(nblk), dim3(256), 0, st, r.ev0,
-                r.ev1, x, Wa, att, dz, zsave, abar, G, bt, sn_pre, dx, dZout, pdwa, pdba, P, S, K, act, r.inv_keep,
-                r.thresh, r.seed, r.offset, r.offset_dev, ex, exs, mbits);
-      bits_done = true;
-    } else if (train && mbits) {
-      if (fused) APA_GO(true, true, true); else APA_GO(false, true, true);
-      bits_done = true;
+  };
+  const std::true_type yes; const std::false_type no;
+  bool bits = false;   // the keep-bits variant: bf16 features
+  if constexpr (KeepBits<T>::ON) bits = c.train && mbits;
+  if (tr && !c.relu_input) tr->keep_bits = bits;
+  if (c.relu_input) {   // instantiated for the fused map only
+    if (c.train) go(yes, yes, yes, no, no); else go(yes, no, yes, no, no);
+  } else if (bits) {
+    if constexpr (KeepBits<T>::ON) {
+      if (c.no_dx) go(no, yes, no, yes, yes);   // ... without the dX stores (APA_IFLAG_NO_DX: Xatt != X)
+      else if (c.fused) go(yes, yes, no, yes, no);
+      else go(no, yes, no, yes, no);
     }
+  } else {
+    m1_fused_train(c.fused, c.train, [&](auto F, auto TR) { return go(F, TR, no, no, no); });
   }
-  if (tr) tr->keep_bits = bits_done;
-  if (r.no_dx && !bits_done) {
-    set_error("m1 stream kernels: APA_IFLAG_NO_DX without the keep-bits backward form (internal)");
-    return APA_ERR_UNSUPPORTED;
-  }
-  if (!bits_done) {
-    if (fused) { if (train) APA_GO(true, true, false); else APA_GO(true, false, false); }
-    else       { if (train) APA_GO(false, true, false); else APA_GO(false, false, false); }
-  }
-#undef APA_GO
   APA_LAUNCH_CHECK("m1s_bwd_main_kernel");
   return APA_OK;
 }
 
-#define APA_S_DISPATCH(FN, dtype, C, ...)                                   \
-  [&]() -> int {                                                            \
-    if ((dtype) == APA_DTYPE_F32) {                                         \
-      switch ((C) / 1024) {                                                 \
-        case 1: return FN<float, 1>(__VA_ARGS__);                           \
-        case 2: return FN<float, 2>(__VA_ARGS__);                           \
-        case 4: return FN<float, 4>(__VA_ARGS__);                           \
-      }                                                                     \
-    } else {                                                                \
-      if ((C) == 2048) return FN<bf16_t, 1>(__VA_ARGS__);                   \
+#define APA_S_DISPATCH(FN)                                                  \
+  if (c.dtype == APA_DTYPE_F32) {                                           \
+    switch (c.C / 1024) {                                                   \
+      case 1: return FN<float, 1>(c, io);                                   \
+      case 2: return FN<float, 2>(c, io);                                   \
+      case 4: return FN<float, 4>(c, io);                                   \
     }                                                                       \
-    set_error("m1 stream kernels: unsupported C=%d dtype=%d", (C), (dtype)); \
-    return APA_ERR_UNSUPPORTED;                                             \
-  }()
+  } else {                                                                  \
+    if (c.C == 2048) return FN<bf16_t, 1>(c, io);                           \
+  }                                                                         \
+  set_error("m1 stream kernels: unsupported C=%d dtype=%d", c.C, c.dtype);  \
+  return APA_ERR_UNSUPPORTED
 
-int m1s_launch_pool_fwd(int dtype, int C, bool fused, bool train, int nblk, hipStream_t st,
-                        const void* X, const float* Wa, const float* ba, float* att, float* pacc,
-                        float* pstat, int P, int S, int act, const M1Rng& r) {
-  return APA_S_DISPATCH(launch_fwd_t, dtype, C, fused, train, nblk, st, X, Wa, ba, att, pacc,
-                        pstat, P, S, act, r);
-}
-
-int m1s_launch_bwd_main(int dtype, int C, bool fused, bool train, int nblk, hipStream_t st,
-                        const void* X, const float* Wa, const float* att, const float* dz,
-                        const float* zsave, const float* abar, const float* G, const float* bt,
-                        const float* sn_pre, void* dX, float* dZout, float* pdwa, float* pdba,
-                        int P, int S, int K, int act, const M1Rng& r, const float* dA_extra) {
-  return APA_S_DISPATCH(launch_bwd_t, dtype, C, fused, train, nblk, st, X, Wa, att, dz, zsave,
-                        abar, G, bt, sn_pre, dX, dZout, pdwa, pdba, P, S, K, act, r, dA_extra);
-}
+int m1s_launch_pool_fwd(const M1Call& c, const M1Fwd& io) { APA_S_DISPATCH(launch_fwd_t); }
+int m1s_launch_bwd_main(const M1Call& c, const M1Bwd& io) { APA_S_DISPATCH(launch_bwd_t); }
+#undef APA_S_DISPATCH
 
 }  // namespace apa

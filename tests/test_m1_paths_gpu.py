@@ -36,8 +36,8 @@ def case(name, N, P, C, K, *, dt=F32, act='id', train=False, Ca=None, rank1=Fals
                 rng=rng, entry=entry, J=J, mis=tuple(mis), keep=keep, expect=expect)
 
 
-# Expected traces are read off the dispatch conditions (apa_m1.hip m1_forward / m1_backward, apa_m1_stream.hip,
-# apa_m1_small.hip); S / ppb / nblk are checked against m1_plan for every case.
+# Expected traces are read off the dispatch conditions (apa_m1.hip m1_call_fill / m1_forward / m1_backward, the
+# launchers of apa_m1_stream.hip / apa_m1_vec.hip / apa_m1_generic.hip, apa_m1_small.hip); S / ppb / nblk are checked against m1_plan for every case.
 CASES = [
     # ---- streaming kernels: fp32 C 1024 / 2048 / 4096 (VW 1 / 2 / 4, PIX 1 / 1 / 2), bf16 C 2048 (VW 1, PIX 2)
     # S = 1: 196 one-pixel chunks per block; logits2 with 4 sub-chunks (N >= 128); head tiles UG 1
@@ -588,3 +588,57 @@ def test_m1_path(gpu, c):
         keys = first if c['entry'] == 'step' else ('logits', 'att', 'zsave', 'abar', 'probs', 'pred')
         for k in keys:
             assert torch.equal(first[k], sep[k]), '{}: one-call step differs from the separate calls'.format(k)
+
+
+# ------------------------------------------------------------------------------------------ refusals
+APA_ERR_UNSUPPORTED = -2    # include/apa.h
+
+# (case, extra flags of the refused calls, which calls are refused, apa_last_error text)
+REFUSALS = [
+    # 257 fp32 vectors per attention row: one more than the register-resident GEMV, the only one with a rank-1 form
+    (case('refused_rank1_ca1028', 2, 16, 256, 3, Ca=1028, rank1=True), 0, ('bwd',),
+     'attn_pool M=1: APA_FLAG_DXATT_RANK1: Ca=1028 not served by the register-resident GEMV'),
+    # a per-pixel (vec) C: the relu-on-load instances exist in the streaming family only
+    (case('refused_relu_input_c512', 2, 16, 512, 3), cof.APA_FLAG_RELU_INPUT, ('fwd', 'bwd'),
+     'attn_pool M=1: APA_FLAG_RELU_INPUT needs Xatt == X and C in {1024,2048,4096} (f32) / 2048 (bf16)'),
+]
+
+
+@pytest.mark.parametrize('c,extra,refused,text', REFUSALS, ids=[r[0]['name'] for r in REFUSALS])
+def test_m1_refused_call_launches_nothing(gpu, c, extra, refused, text):
+    """A call the M == 1 path refuses returns APA_ERR_UNSUPPORTED with its message before anything is queued: after
+    a synchronize no byte of any output, of the workspace or of their guards has changed.  (The backward calls read
+    att / zsave / abar of a served forward call, so a kernel launched in spite of the refusal would write numbers
+    over the NaN sentinels.)"""
+    lib = mp.load_m1_probe()
+    torch.manual_seed(0)
+    inp = _inputs(c, gpu)
+    r = _Run(c, inp, gpu, lib)
+    N, P, C, Ca, K = r.N, r.P, r.C, r.Ca, r.K
+    X = inp['X'].data_ptr()
+    Xatt = X if c['Ca'] is None else inp['Xatt'].data_ptr()
+    args = (None, X, Xatt, inp['Wa'].data_ptr(), inp['ba'].data_ptr(), r.Wt.ptr, inp['bt'].data_ptr())
+    st = gp.stream_ptr()
+
+    def fwd(flags):
+        return lib.apa_attn_pool_fwd_ex(*args, r.p('logits'), r.p('att'), r.p('zsave'), r.p('abar'), None, r.ws.ptr,
+                                        r.ws_bytes, N, P, C, Ca, K, 1, flags, 1.0, 0, 0, c['dt'], st)
+
+    def bwd(flags):
+        return lib.apa_attn_pool_bwd_ex(*args, r.p('att'), r.p('zsave'), r.p('abar'), r.p('G'), r.p('dX'),
+                                        r.p('dXatt'), r.p('dWa'), r.p('dba'), r.p('dWt'), r.p('dbt'), r.ws.ptr,
+                                        r.ws_bytes, N, P, C, Ca, K, 1, flags, 1.0, 0, 0, c['dt'], st)
+
+    assert fwd(r.flags) == 0, lib.apa_last_error()       # the served forward call: real att, zsave, abar
+    torch.cuda.synchronize()
+    bufs = dict(r.out, workspace=r.ws)
+    for b in bufs.values():
+        b.snapshot()
+    for which in refused:
+        rc = (fwd if which == 'fwd' else bwd)(r.flags | extra)
+        assert rc == APA_ERR_UNSUPPORTED, (which, rc)
+        assert lib.apa_last_error().decode() == text, which
+        torch.cuda.synchronize()
+        for k, b in bufs.items():
+            assert torch.equal(b.base.view(gp._INT_VIEW[b.dtype]), b.snap), \
+                '{}: the refused {} call changed {}'.format(c['name'], which, k)
