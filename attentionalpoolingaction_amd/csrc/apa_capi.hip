@@ -532,12 +532,13 @@ extern "C" int apa_per_class_weight_images(const float* Wa, const float* ba, con
   return pc_weight_images(Wa, ba, Wt, bt, ws, N, P, C, Ca, K, dtype, maps, nmaps, static_cast<hipStream_t>(stream));
 }
 
-extern "C" int apa_attn_head_eval_step(const void* X, const void* Xatt, const float* Wa, const float* ba,
-                                       const float* Wt, const float* bt, const int64_t* labels,
-                                       float* logits, float* att, float* zsave, float* abar, float* loss,
-                                       float* probs, int64_t* pred, void* ws, size_t ws_bytes, int N,
-                                       int P, int C, int Ca, int K, int M, unsigned flags, int dtype,
-                                       void* stream) {
+// iflags: library-internal flag bits added to the pooling call (APA_IFLAG_ATT_READY from apa_pose_attn_eval_step)
+static int attn_head_eval_impl(const void* X, const void* Xatt, const float* Wa, const float* ba,
+                               const float* Wt, const float* bt, const int64_t* labels,
+                               float* logits, float* att, float* zsave, float* abar, float* loss,
+                               float* probs, int64_t* pred, void* ws, size_t ws_bytes, int N,
+                               int P, int C, int Ca, int K, int M, unsigned flags, unsigned iflags, int dtype,
+                               void* stream) {
   if (!probs || !pred) {
     apa::set_error("apa_attn_head_eval_step: null probs / pred pointer");
     return APA_ERR_INVALID_ARG;
@@ -546,7 +547,7 @@ extern "C" int apa_attn_head_eval_step(const void* X, const void* Xatt, const fl
     apa::set_error("apa_attn_head_eval_step: labels and loss must be given together");
     return APA_ERR_INVALID_ARG;
   }
-  const unsigned eval_flags = flags & APA_PUBLIC_FLAGS & ~(unsigned)APA_FLAG_TRAIN;   // is_training=False: no dropout
+  const unsigned eval_flags = (flags & APA_PUBLIC_FLAGS & ~(unsigned)APA_FLAG_TRAIN) | iflags;   // is_training=False: no dropout
   // without ground truth the softmax / argmax of a row rides on the logits reduction (M == 1, K <= 512)
   M1Xent xf;
   xf.labels = nullptr; xf.loss = nullptr; xf.G = nullptr; xf.gscale = 0.f; xf.lscale = 0.f; xf.done = false;
@@ -567,4 +568,90 @@ extern "C" int apa_attn_head_eval_step(const void* X, const void* Xatt, const fl
   float* lscratch = reinterpret_cast<float*>(static_cast<char*>(ws) + (size_t)N * 8);
   return apa_softmax_xent_fwd_bwd(logits, static_cast<const int64_t*>(ws), lscratch, nullptr, probs, pred,
                                   N, K, 1.0f, 1.0f, stream);
+}
+
+extern "C" int apa_attn_head_eval_step(const void* X, const void* Xatt, const float* Wa, const float* ba,
+                                       const float* Wt, const float* bt, const int64_t* labels,
+                                       float* logits, float* att, float* zsave, float* abar, float* loss,
+                                       float* probs, int64_t* pred, void* ws, size_t ws_bytes, int N,
+                                       int P, int C, int Ca, int K, int M, unsigned flags, int dtype,
+                                       void* stream) {
+  return attn_head_eval_impl(X, Xatt, Wa, ba, Wt, bt, labels, logits, att, zsave, abar, loss, probs, pred, ws, ws_bytes,
+                             N, P, C, Ca, K, M, flags, 0u, dtype, stream);
+}
+
+// workspace of apa_pose_attn_eval_step: [pose head | pooling (+ the label-free loss scratch) | column-tile partials]
+struct PoseEvalCarve { size_t pose, pool, zpart, total; };
+static PoseEvalCarve pose_eval_carve(int N, int P, int C, int Cp, int J, int K, unsigned flags, int dtype) {
+  PoseEvalCarve c;
+  c.pose = align_up(apa_pose_head_workspace_bytes(N, P, C, Cp, J, dtype), 256);
+  const size_t lf = ((size_t)N * 8 + (size_t)(1 + N) * 4 + 255) / 256 * 256;
+  const size_t pool = apa_attn_pool_workspace_bytes(N, P, C, Cp, K, 1, flags);
+  c.pool = align_up(pool > lf ? pool : lf, 256);
+  c.zpart = pose_eval_zpart_bytes(N, P, Cp);
+  c.total = c.pose + c.pool + c.zpart;
+  return c;
+}
+
+extern "C" size_t apa_pose_attn_eval_workspace_bytes(int N, int P, int C, int Cp, int J, int K, unsigned flags,
+                                                     int dtype, int want_pose_logits) {
+  (void)want_pose_logits;   // both routes fit: the composed route's Ppre lives in the pose head's own dPpre region
+  if (N <= 0 || P <= 0 || C <= 0 || Cp <= 0 || J <= 0 || K <= 0) return 0;
+  return pose_eval_carve(N, P, C, Cp, J, K, flags, dtype).total;
+}
+
+extern "C" int apa_pose_attn_eval_step(const apa_pose_attn_eval_io* io, int N, int P, int C, int Cp, int J, int K,
+                                       unsigned flags, int dtype, void* stream) {
+  if (!io) {
+    set_error("apa_pose_attn_eval_step: null io");
+    return APA_ERR_INVALID_ARG;
+  }
+  const apa_pose_attn_eval_io& s = *io;
+  if (!s.X || !s.W1 || !s.b1 || !s.W2 || !s.b2 || !s.Wa || !s.ba || !s.Wt || !s.bt || !s.att || !s.logits ||
+      !s.zsave || !s.abar || !s.probs || !s.pred) {
+    set_error("apa_pose_attn_eval_step: null pointer in apa_pose_attn_eval_io (only W1_bf16, labels, loss, Pl and route "
+              "may be NULL)");
+    return APA_ERR_INVALID_ARG;
+  }
+  if ((s.labels == nullptr) != (s.loss == nullptr)) {
+    set_error("apa_pose_attn_eval_step: labels and loss must be given together (both null or neither)");
+    return APA_ERR_INVALID_ARG;
+  }
+  int rc = check_common("apa_pose_attn_eval_step", N, P, C, Cp, K, 1, dtype);
+  if (rc != APA_OK) return rc;
+  if (J <= 0) {
+    set_error("apa_pose_attn_eval_step: J=%d", J);
+    return APA_ERR_INVALID_ARG;
+  }
+  if (flags & (APA_FLAG_RELU_INPUT | APA_FLAG_RNG_EXTERNAL)) {
+    set_error("apa_pose_attn_eval_step: APA_FLAG_RELU_INPUT / APA_FLAG_RNG_EXTERNAL have no meaning here (the attention "
+              "input is pose_pre_logits; evaluation draws no mask)");
+    return APA_ERR_UNSUPPORTED;
+  }
+  flags &= APA_FLAG_SOFTMAX_ATT | APA_FLAG_RELU_ATT;   // is_training=False: everything else is a training matter
+  if (!m1_supported(C, Cp, dtype, false)) {
+    set_error("apa_pose_attn_eval_step: C and Cp must be whole 16-byte vectors (multiples of 4 fp32 / 8 bf16 channels, "
+              "C <= 9584); got C=%d Cp=%d dtype=%d", C, Cp, dtype);
+    return APA_ERR_UNSUPPORTED;
+  }
+  const PoseEvalCarve cv = pose_eval_carve(N, P, C, Cp, J, K, flags, dtype);
+  if (!s.ws || s.ws_bytes < cv.total) {
+    set_error("apa_pose_attn_eval_step: workspace too small (%zu < %zu)", s.ws_bytes, cv.total);
+    return APA_ERR_WORKSPACE;
+  }
+  char* w = static_cast<char*>(s.ws);
+  float* zpart = reinterpret_cast<float*>(w + cv.pose + cv.pool);
+  const bool relu_att = (flags & APA_FLAG_RELU_ATT) && !(flags & APA_FLAG_SOFTMAX_ATT);
+  int route = 0;
+  const void* ppre = nullptr;
+  bool att_ready = false;
+  rc = pose_eval_fwd(s.X, s.W1, s.b1, s.W2, s.b2, s.W1_bf16, s.Wa, s.ba, relu_att, s.att, s.Pl, w, cv.pose, zpart, N, P,
+                     C, Cp, J, dtype, static_cast<hipStream_t>(stream), &route, &ppre, &att_ready);
+  if (rc != APA_OK) return rc;
+  if (s.route) *s.route = route;
+  // with att in place the pooling pass never dereferences its attention input (it only must differ from X)
+  const void* xatt = ppre ? ppre : static_cast<const void*>(zpart);
+  return attn_head_eval_impl(s.X, xatt, s.Wa, s.ba, s.Wt, s.bt, s.labels, s.logits, s.att, s.zsave, s.abar, s.loss,
+                             s.probs, s.pred, w + cv.pose, cv.pool, N, P, C, Cp, K, 1, flags,
+                             att_ready ? APA_IFLAG_ATT_READY : 0u, dtype, stream);
 }

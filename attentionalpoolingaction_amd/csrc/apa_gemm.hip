@@ -452,6 +452,10 @@ static int gemm_launch_t(const GemmDesc& d, hipStream_t st) {
     set_error("gemm: the rank-1 epilogue and the mid-contraction mask exist in the wide bf16 kernel only (internal)");
     return APA_ERR_UNSUPPORTED;
   }
+  if (d.zp_out) {
+    set_error("gemm: the contracted epilogue exists in the bf16 ring kernel only (internal)");
+    return APA_ERR_UNSUPPORTED;
+  }
   if (d.trace) d.trace->kind = GEMM_KIND_GENERIC;
   hipLaunchKernelGGL((gemm128_kernel<TA, TB, TC, A_KC, B_KC, BF16>), dim3(tiles, 1, splits), dim3(256),
                      0, st, p);

@@ -123,6 +123,8 @@ struct FastParams {
   // GemmDesc::twin: the second problem of the launch (blockIdx.y == 1); A2 == nullptr: none
   const void* A2; const void* B2; void* C2; long ldc2; const float* bias2; float* partial2; int Nout2, vec_epi2;
   int nt_out;    // GemmDesc::stream_out: non-temporal bf16 vector stores of C
+  // GemmDesc::zp_*: the contracted epilogue of gemm_bf16_ring_kernel<.., ZP> (C is not stored)
+  const float* zp_w; float* zp_out;
 };
 __device__ __forceinline__ void twin_select(FastParams& p) {
   if (blockIdx.y) {
@@ -739,7 +741,7 @@ __device__ __forceinline__ void ring_wait_barrier() {
   asm volatile("s_barrier" ::: "memory");
 }
 
-template <typename TC, bool B_KM, int MT>
+template <typename TC, bool B_KM, int MT, bool ZP = false>
 __global__ __launch_bounds__(512, 1) void gemm_bf16_ring_kernel(FastParams p) {
   typedef RingCfg<MT> R;
   twin_select(p);
@@ -874,6 +876,43 @@ __global__ __launch_bounds__(512, 1) void gemm_bf16_ring_kernel(FastParams p) {
         for (int r = 0; r < 4; ++r)
           stage[((wm * MT + i) * 16 + 4 * kb + r) * LDS_C + wn * 32 + j * 16 + l16] = acc[i][j][r];
     __syncthreads();
+    if constexpr (ZP) {
+      // Contracted form (the host admits it only with bf16 C, N % 128 == 0, bias, no split-K / dropout / beta): the
+      // 16 lanes of a row take the same 16-byte segments as below, apply bias and relu, round to bf16 -- the values a
+      // stored C would hold -- and contract them with the fp32 zp_w[n0 .. n0 + 128): eight FMAs per lane in column
+      // order, then the 16 lanes of the row pairwise (xor 1, 2, 4, 8: one fixed order, no atomics).  One fp32
+      // partial per row and column tile, zp_out[tile_n][row]; C itself is never written.  Every lane runs all MT
+      // rounds (rows past M are computed on whatever the clamped staging left there and not stored).
+      const int c8 = (tid & 15) * 8, gcol = n0 + c8;
+      const float4 w0 = *reinterpret_cast<const float4*>(p.zp_w + gcol);
+      const float4 w1 = *reinterpret_cast<const float4*>(p.zp_w + gcol + 4);
+      const float4 b0 = *reinterpret_cast<const float4*>(p.bias + gcol);
+      const float4 b1 = *reinterpret_cast<const float4*>(p.bias + gcol + 4);
+      float* zrow = p.zp_out + (size_t)(n0 / TN) * p.M;
+#pragma unroll
+      for (int it = 0; it < MT; ++it) {
+        const int row = (tid >> 4) + it * 32, grow = m0 + row;
+        const float4 x0 = *reinterpret_cast<const float4*>(stage + row * LDS_C + c8);
+        const float4 x1 = *reinterpret_cast<const float4*>(stage + row * LDS_C + c8 + 4);
+        float o[8] = {x0.x + b0.x, x0.y + b0.y, x0.z + b0.z, x0.w + b0.w,
+                      x1.x + b1.x, x1.y + b1.y, x1.z + b1.z, x1.w + b1.w};
+        if (p.act == 1) {
+#pragma unroll
+          for (int e = 0; e < 8; ++e) o[e] = fmaxf(o[e], 0.f);
+        }
+        float q[8];
+        Vec<bf16_t>::unpack(Vec<bf16_t>::pack(o), q);
+        float d = q[0] * w0.x;
+        d = fmaf(q[1], w0.y, d); d = fmaf(q[2], w0.z, d); d = fmaf(q[3], w0.w, d);
+        d = fmaf(q[4], w1.x, d); d = fmaf(q[5], w1.y, d); d = fmaf(q[6], w1.z, d); d = fmaf(q[7], w1.w, d);
+        d += __shfl_xor(d, 1);
+        d += __shfl_xor(d, 2);
+        d += __shfl_xor(d, 4);
+        d += __shfl_xor(d, 8);
+        if ((tid & 15) == 0 && grow < p.M) zrow[grow] = d;
+      }
+      return;
+    }
     for (int v = tid; v < R::TMR * 16; v += 512) {
       const int row = v >> 4, c8 = (v & 15) * 8;
       const int grow = m0 + row, gcol = n0 + c8;
@@ -899,17 +938,17 @@ __global__ __launch_bounds__(512, 1) void gemm_bf16_ring_kernel(FastParams p) {
   }
 }
 
-template <typename TC, bool B_KM, int MT>
+template <typename TC, bool B_KM, int MT, bool ZP = false>
 int launch_ring(const FastParams& p, hipStream_t st) {
   typedef RingCfg<MT> R;
   static thread_local PerDevice<bool> attr_dev; bool& attr_set = attr_dev.here();
   if (!attr_set) {
-    APA_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_bf16_ring_kernel<TC, B_KM, MT>),
+    APA_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_bf16_ring_kernel<TC, B_KM, MT, ZP>),
                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)R::LDS_BYTES));
     attr_set = true;
   }
   const int tiles = ((p.M + R::TMR - 1) / R::TMR) * ((p.N + TN - 1) / TN);
-  hipLaunchKernelGGL((gemm_bf16_ring_kernel<TC, B_KM, MT>), dim3(tiles, p.A2 ? 2 : 1), dim3(512), R::LDS_BYTES, st, p);
+  hipLaunchKernelGGL((gemm_bf16_ring_kernel<TC, B_KM, MT, ZP>), dim3(tiles, p.A2 ? 2 : 1), dim3(512), R::LDS_BYTES, st, p);
   APA_LAUNCH_CHECK("gemm_bf16_ring_kernel");
   return APA_OK;
 }
@@ -1258,14 +1297,14 @@ static int ring_pick_mt(int M, int N, int cus) {
   return 0;
 }
 
-template <typename TC, bool B_KM>
+template <typename TC, bool B_KM, bool ZP = false>
 int launch_ring_mt(const FastParams& p, int mt, hipStream_t st) {
   switch (mt) {
-    case 4: return launch_ring<TC, B_KM, 4>(p, st);
-    case 5: return launch_ring<TC, B_KM, 5>(p, st);
-    case 6: return launch_ring<TC, B_KM, 6>(p, st);
-    case 7: return launch_ring<TC, B_KM, 7>(p, st);
-    default: return launch_ring<TC, B_KM, 8>(p, st);
+    case 4: return launch_ring<TC, B_KM, 4, ZP>(p, st);
+    case 5: return launch_ring<TC, B_KM, 5, ZP>(p, st);
+    case 6: return launch_ring<TC, B_KM, 6, ZP>(p, st);
+    case 7: return launch_ring<TC, B_KM, 7, ZP>(p, st);
+    default: return launch_ring<TC, B_KM, 8, ZP>(p, st);
   }
 }
 
@@ -1354,7 +1393,7 @@ int gemm_bf16_mid_dropout(const void* A, long lda, const void* B, long ldb, void
   p.M = M; p.N = N; p.K = K; p.bias = nullptr; p.beta = 0.f; p.act = 0;
   p.k_per_split = K; p.partial = nullptr; p.Nout = N;
   p.A2 = nullptr; p.B2 = nullptr; p.C2 = nullptr; p.ldc2 = 0; p.bias2 = nullptr; p.partial2 = nullptr;
-  p.Nout2 = 0; p.vec_epi2 = 0; p.nt_out = 0;
+  p.Nout2 = 0; p.vec_epi2 = 0; p.nt_out = 0; p.zp_w = nullptr; p.zp_out = nullptr;
   p.drop_c = 0; p.inv_keep = inv_keep; p.thresh = 0; p.seed = 0; p.offset = 0;
   p.offset_dev = nullptr;
   p.vec_epi = N % 8 == 0 && (reinterpret_cast<uintptr_t>(C) & 15) == 0 && (ldc * 2) % 16 == 0;
@@ -1399,10 +1438,23 @@ bool gemm_bf16_eligible(const GemmDesc& d) {
   return true;
 }
 
+// The contracted epilogue (GemmDesc::zp_*) exists in the ring kernel's vector epilogue, k-major bf16 weights only: whole
+// 128-column tiles, whole 64-deep k tiles (any number of them: the ring's prologue and peeled last tile cover nk >= 1,
+// the "at least four k tiles" of the dispatch below is a speed rule), one resident round of tiles, 16-byte addressable
+// operands, bias and contraction vector.
+bool gemm_bf16_zp_serves(const GemmDesc& d) {
+  return gemm_bf16_eligible(d) && d.tb == 1 && d.tc == 1 && d.a_kc && !d.b_kc && d.N % TN == 0 && d.K % TK == 0 &&
+         d.K >= TK && d.splits <= 1 && d.n_valid == 0 && d.bias && d.beta == 0.f && !d.drop_c && !d.twin && !d.r1_row &&
+         !d.mid_bits && d.zp_w && d.zp_out && ((reinterpret_cast<uintptr_t>(d.bias) | reinterpret_cast<uintptr_t>(d.zp_w) |
+                                                reinterpret_cast<uintptr_t>(d.zp_out)) & 15) == 0 &&
+         ring_pick_mt(d.M, d.N, gemm_cu_count()) != 0;
+}
+
 // which kernel gemm_bf16_launch picks for an eligible product
 enum { KIND_GENERIC = 0, KIND_WIDE, KIND_RING, KIND_GLDS64, KIND_GLDS128 };
 static int bf16_kind(const GemmDesc& d, int splits, int k_per_split) {
   if (!(d.tb == 1 && k_per_split % TK == 0 && d.K % TK == 0)) return KIND_GENERIC;
+  if (d.zp_out) return gemm_bf16_zp_serves(d) && splits == 1 ? KIND_RING : KIND_GENERIC;   // (refused below unless RING)
   if (splits == 1 && d.a_kc && d.b_kc && gemm_bf16_wide_serves(d.M, d.N, d.K)) return KIND_WIDE;
   if (d.a_kc && splits == 1 && d.K / TK >= 4 && ring_pick_mt(d.M, d.N, gemm_cu_count())) return KIND_RING;
   const long tiles128 = (long)((d.M + TM - 1) / TM) * ((d.N + TN - 1) / TN) * splits;
@@ -1441,6 +1493,7 @@ int gemm_bf16_launch(const GemmDesc& d, int splits, int k_per_split, hipStream_t
   p.A2 = nullptr; p.B2 = nullptr; p.C2 = nullptr; p.ldc2 = 0; p.bias2 = nullptr; p.partial2 = nullptr;
   p.Nout2 = 0; p.vec_epi2 = 0;
   p.nt_out = d.stream_out ? 1 : 0;
+  p.zp_w = nullptr; p.zp_out = nullptr;
   p.drop_c = d.drop_c; p.inv_keep = d.inv_keep; p.thresh = d.thresh; p.seed = d.seed; p.offset = d.offset;
   p.offset_dev = d.offset_dev;
   p.drop_mid = -1;
@@ -1466,6 +1519,10 @@ int gemm_bf16_launch(const GemmDesc& d, int splits, int k_per_split, hipStream_t
   }
   if (d.r1_row && kind != KIND_WIDE) {
     set_error("gemm_bf16: rank-1 epilogue requested for a product the wide kernel does not serve (internal)");
+    return APA_ERR_UNSUPPORTED;
+  }
+  if (d.zp_out && kind != KIND_RING) {
+    set_error("gemm_bf16: contracted epilogue requested for a product the ring kernel does not serve (internal)");
     return APA_ERR_UNSUPPORTED;
   }
   if (kind != KIND_GENERIC) {   // all-bf16, whole K tiles: DMA staging
@@ -1500,6 +1557,10 @@ int gemm_bf16_launch(const GemmDesc& d, int splits, int k_per_split, hipStream_t
     if (kind == KIND_RING) {
       const int mt = ring_pick_mt(d.M, d.N, gemm_cu_count());
       if (d.trace) { d.trace->kind = GEMM_KIND_RING; d.trace->mt = mt; }
+      if (d.zp_out) {
+        p.zp_w = d.zp_w; p.zp_out = d.zp_out; p.vec_epi = 1; p.C = nullptr;
+        return launch_ring_mt<bf16_t, true, true>(p, mt, st);
+      }
       if (d.tc == 1) return d.b_kc ? launch_ring_mt<bf16_t, false>(p, mt, st) : launch_ring_mt<bf16_t, true>(p, mt, st);
       return d.b_kc ? launch_ring_mt<float, false>(p, mt, st) : launch_ring_mt<float, true>(p, mt, st);
     }

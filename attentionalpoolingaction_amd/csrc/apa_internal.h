@@ -176,6 +176,12 @@ struct GemmDesc {
   // mid-contraction mask (wide kernel only, bf16 C): C = (A[:, :mid_k] . B[:, :mid_k]^T) * keepbit / keep + the rest of
   // the contraction; mid_bits = keep bits of C's elements, natural layout (bit (e & 7) of byte e >> 3, e = m * N + n)
   const uint8_t* mid_bits = nullptr; int mid_k = 0; float mid_inv_keep = 1.f;
+  // contracted epilogue (ring kernel only, opt-in; gemm_bf16_zp_serves says whether a product can have it): C is NOT
+  // stored.  Each 128-column tile applies bias / act, rounds to bf16 as a stored C would be, contracts the rounded
+  // values with the fp32 zp_w[n0 : n0 + 128] and writes one fp32 partial per row, zp_out[(n0 / 128) * M + row] --
+  // N / 128 partials per row, summed in a fixed order by the consumer (the cfg 003 evaluation step: attention logits
+  // out of the pose-head product, pre-logit map never written)
+  const float* zp_w = nullptr; float* zp_out = nullptr;
   // a column sum to run on the tail blocks of this product's split-K reduce launch (taken only if there is one)
   ColsumJob* tail = nullptr;
   // optional: where to record the kernel kind / split / reduce that served this product (null at product call sites)
@@ -188,6 +194,7 @@ int gemm_launch(const GemmDesc& d, hipStream_t st);
 bool gemm_bf16_eligible(const GemmDesc& d);
 int gemm_bf16_launch(const GemmDesc& d, int splits, int k_per_split, hipStream_t st);
 bool gemm_bf16_twin_ok(const GemmDesc& d, int splits, int k_per_split);   // can d and d.twin share one launch?
+bool gemm_bf16_zp_serves(const GemmDesc& d);   // can this product take the contracted epilogue (GemmDesc::zp_*)?
 bool gemm_bf16_wide_serves(int M, int N, int K);   // would this all-bf16, k-contiguous, unsplit product take the wide kernel?
 int gemm_bf16_wide_tile_rows(int M, int N, int K);  // ... and with how many rows per tile (0 = not served)
 // apa_gemm_bf16.hip: C = (A[:, :64] . B[:, :64]^T) * mask/keep + A[:, 64:] . B[:, 64:]^T  (all bf16, k contiguous)
@@ -366,6 +373,12 @@ void* pose_ws_loss_scratch(void* ws, int N, int P, int C, int Cp, int J, int dty
 int pose_fwd_fused(const void* X, const float* W1, const float* b1, const float* W2, const float* b2, void* Ppre,
                    float* Pl, void* ws, size_t ws_bytes, int N, int P, int C, int Cp, int J, int dtype,
                    const PoseStepArgs& a, hipStream_t st);
+// the pose-head half of apa_pose_attn_eval_step (apa_pose_head.hip) and the size of its column-tile partials
+size_t pose_eval_zpart_bytes(int N, int P, int Cp);
+int pose_eval_fwd(const void* X, const float* W1, const float* b1, const float* W2, const float* b2,
+                  const void* W1_bf16, const float* wa, const float* ba, bool relu_att, float* att, float* Pl, void* ws,
+                  size_t ws_bytes, float* zpart, int N, int P, int C, int Cp, int J, int dtype, hipStream_t st,
+                  int* route, const void** ppre, bool* att_ready);
 int pose_bwd_fused(const void* X, const float* W1, const float* W2, const void* Ppre, const float* dPl,
                    const float* dZ, const float* wa, void* dX, int accumulate_dX, float* dW1, float* db1,
                    float* dW2, float* db2, float* dWa, float* dba, float* loss_pose, uint64_t* rng_bump,

@@ -1232,6 +1232,88 @@ int pose_fwd_fused(const void* X, const float* W1, const float* b1, const float*
   return pose_pl_launch(static_cast<const bf16_t*>(Ppre), W2, b2, Pl, R, Cp, J, &x, st);
 }
 
+// att[r] = act(sum_t zp[t][r] + ba): the N / 128 column-tile partials of the contracted epilogue (GemmDesc::zp_*), summed
+// in tile order; id / relu applied, a softmax map stays raw (the pooling call's row softmax takes it from here)
+__global__ __launch_bounds__(256) void pose_zpart_finish_kernel(const float* __restrict__ zp, int nt, long R,
+                                                                const float* __restrict__ ba, int act,
+                                                                float* __restrict__ att) {
+  const long r = (long)blockIdx.x * 256 + threadIdx.x;
+  if (r >= R) return;
+  float z = zp[r];
+  for (int t = 1; t < nt; ++t) z += zp[(size_t)t * R + r];
+  z += ba[0];
+  if (act == 1) z = fmaxf(z, 0.f);
+  att[r] = z;
+}
+
+size_t pose_eval_zpart_bytes(int N, int P, int Cp) {
+  return align_up((size_t)((Cp + 127) / 128) * (size_t)N * P * 4, 256);
+}
+
+// The pose-head half of apa_pose_attn_eval_step.  Fused route (*route = 1; Pl == nullptr, bf16 operands, the product
+// served by the contracted epilogue): Ppre = relu(X.W1 + b1) is formed tile by tile, contracted with wa and never
+// stored; att receives Z = Ppre.wa + ba (id / relu).  Composed route (*route = 0): Ppre goes to the workspace's dPpre
+// region (*ppre), Pl -- when asked for -- comes from the skinny product, whose FUSED form emits att on the same pass
+// where it serves the shape.  *att_ready: att holds Z; else the pooling call's own GEMV forms it from *ppre.
+int pose_eval_fwd(const void* X, const float* W1, const float* b1, const float* W2, const float* b2,
+                  const void* W1_bf16, const float* wa, const float* ba, bool relu_att, float* att, float* Pl, void* ws,
+                  size_t ws_bytes, float* zpart, int N, int P, int C, int Cp, int J, int dtype, hipStream_t st,
+                  int* route, const void** ppre, bool* att_ready) {
+  const PosePlan pl = pose_plan(N, P, C, Cp, J, dtype);
+  if (!ws || ws_bytes < pl.total) {
+    set_error("apa_pose_attn_eval_step: pose workspace too small (%zu < %zu)", ws_bytes, pl.total);
+    return APA_ERR_WORKSPACE;
+  }
+  char* w = static_cast<char*>(ws);
+  const int R = (int)pl.R;
+  int w1_tb = 0;
+  const void* W1op = W1_bf16;
+  PoseTrace* tr = pose_trace();
+  if (W1op && dtype == APA_DTYPE_BF16 && (reinterpret_cast<uintptr_t>(W1op) & 15) == 0) {
+    w1_tb = 1;
+    if (tr) tr->w1_fwd = POSE_W1_SHADOW;
+  } else {
+    W1op = pose_w1_operand(W1, w + pl.off_w1b, C, Cp, dtype, &w1_tb, st, false, tr ? &tr->w1_fwd : nullptr);
+  }
+  GemmDesc g1;  // Ppre = relu(X.W1 + b1)
+  g1.A = X; g1.lda = C; g1.ta = dt_code(dtype); g1.a_kc = true;
+  g1.B = W1op; g1.ldb = Cp; g1.tb = w1_tb; g1.b_kc = false;
+  g1.ldc = Cp; g1.tc = dt_code(dtype);
+  g1.M = R; g1.N = Cp; g1.K = C; g1.bias = b1; g1.act = 1;
+  int rc;
+  if (!Pl && zpart) {
+    g1.zp_w = wa; g1.zp_out = zpart;
+    if (gemm_bf16_zp_serves(g1)) {
+      if ((rc = gemm_launch(g1, st)) != APA_OK) return rc;
+      hipLaunchKernelGGL(pose_zpart_finish_kernel, dim3((unsigned)((R + 255) / 256)), dim3(256), 0, st, zpart, Cp / 128,
+                         (long)R, ba, relu_att ? 1 : 0, att);
+      APA_LAUNCH_CHECK("pose_zpart_finish_kernel");
+      *route = 1; *ppre = nullptr; *att_ready = true;
+      return APA_OK;
+    }
+    g1.zp_w = nullptr; g1.zp_out = nullptr;
+  }
+  void* Ppre = w + pl.off_dppre;
+  g1.C = Ppre;
+  if ((rc = gemm_launch(g1, st)) != APA_OK) return rc;
+  *route = 0; *ppre = Ppre; *att_ready = false;
+  if (!Pl) return APA_OK;
+  if (pose_pl_fast(Cp, J, dtype, Ppre)) {   // the skinny product; with a 16-byte addressable wa the same pass emits att
+    const bool fz = (reinterpret_cast<uintptr_t>(wa) & 15) == 0;
+    PosePlExtra x = {wa, ba, att, relu_att ? 1 : 0, nullptr, nullptr, nullptr, nullptr, 0.f, P, nullptr};
+    *att_ready = fz;
+    return pose_pl_launch(static_cast<const bf16_t*>(Ppre), W2, b2, Pl, R, Cp, J, fz ? &x : nullptr, st);
+  }
+  if (tr) tr->pl = POSE_PL_GEMM;
+  GemmDesc g2;  // Pl = Ppre.W2 + b2
+  g2.A = Ppre; g2.lda = Cp; g2.ta = dt_code(dtype); g2.a_kc = true;
+  g2.B = W2; g2.ldb = J; g2.tb = 0; g2.b_kc = false;
+  g2.C = Pl; g2.ldc = J; g2.tc = 0;
+  g2.M = R; g2.N = J; g2.K = Cp; g2.bias = b2;
+  g2.splits = gemm_pick_splits(R, J, Cp); g2.ws = reinterpret_cast<float*>(w + pl.off_gemm);
+  return gemm_launch(g2, st);
+}
+
 // dPpre (+ the rank-1 attention-branch gradient dZ (x) wa), dW2, db1, db2, dWa, dba in one pass + one column
 // sum that also finishes the pose loss and advances the dropout counter; then dW1 and dX (+)= dPpre.W1^T
 int pose_bwd_fused(const void* X, const float* W1, const float* W2, const void* Ppre, const float* dPl,

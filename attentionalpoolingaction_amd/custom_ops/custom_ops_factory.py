@@ -109,6 +109,9 @@ _SIGNATURES = {
                                  c_void_p, c_float, c_float, c_float, c_float, c_float, POINTER(c_void_p), c_void_p]),
     'apa_pose_attn_train_step': (c_int, [c_void_p] + [c_int] * 6 + [c_uint, c_float, ctypes.c_uint64,
                                                                     ctypes.c_uint64, c_int, c_void_p]),
+    # `const apa_pose_attn_eval_io*` first
+    'apa_pose_attn_eval_workspace_bytes': (c_size_t, [c_int] * 6 + [c_uint, c_int, c_int]),
+    'apa_pose_attn_eval_step': (c_int, [c_void_p] + [c_int] * 6 + [c_uint, c_int, c_void_p]),
     'apa_accumulate_gradients': (c_int, [c_void_p, POINTER(c_void_p), c_int, c_size_t, c_float, c_void_p]),
     'apa_accumulate_gradients_div': (c_int, [c_void_p, POINTER(c_void_p), c_int, c_size_t, c_float, c_void_p]),
     'apa_clip_by_norm_workspace_bytes': (c_size_t, [c_int, POINTER(c_size_t)]),
@@ -1216,10 +1219,102 @@ class HeadEvalStep:
             N, P, C, Ca, K, M, flags, _feat_dtype(X)]
         self._fn = self.lib.apa_attn_head_eval_step
 
+    def rebind(self, X) -> None:
+        """Point the bound step at another feature map of the same shape / dtype (attention from the map itself:
+        the step was built with `Xatt is X`)."""
+        if self._keep[1] is not self._keep[0]:
+            raise ApaError('HeadEvalStep.rebind: a step with a separate attention input is re-built, not re-bound')
+        if X.shape != self._keep[0].shape or X.dtype != self._keep[0].dtype:
+            raise ApaError('HeadEvalStep.rebind: same shape and dtype expected')
+        self._args[0] = self._args[1] = _dev_ptr(X, 'X')
+        self._keep = (X, X) + tuple(self._keep[2:])
+
     def run(self, stream: Optional[int] = None) -> None:
         rc = self._fn(*self._args, _stream_ptr() if stream is None else stream)
         if rc != 0:
             _check(rc, 'apa_attn_head_eval_step')
+
+
+class ApaPoseAttnEvalIO(ctypes.Structure):
+    """`apa_pose_attn_eval_io` of include/apa.h (field order is the ABI)."""
+    _fields_ = ([(n, c_void_p) for n in ('X', 'W1', 'b1', 'W1_bf16', 'W2', 'b2', 'Wa', 'ba', 'Wt', 'bt', 'labels',
+                                          'att', 'logits', 'zsave', 'abar', 'probs', 'pred', 'loss', 'Pl')] +
+                [('ws', c_void_p), ('ws_bytes', c_size_t), ('route', POINTER(c_int))])
+
+
+class PoseAttnEvalStep:
+    """apa_pose_attn_eval_step bound to caller-owned inputs: the cfg 003 head at evaluation time (PoseLogits head ->
+    attention from pose_pre_logits -> pooling -> softmax probabilities + argmax, eval.py:181-197) as ONE foreign call.
+
+    `params = (W1, b1, W2, b2, Wa, ba, Wt, bt)` fp32; `w1_bf16`: optional bf16 copy of W1 the caller keeps current.
+    Outputs as attributes: `att` [N,P,1], `logits`, `zsave`, `abar`, `probs` [N,K], `pred` [N] int64, `loss` [1+N] or
+    None, `Pl` [N,P,J] or None (`want_pose_logits=True`).  `route` (after `run()`): 1 = the pose-head product's
+    epilogue formed the attention logits and pose_pre_logits was never written; 0 = the composed route."""
+
+    def __init__(self, X, params, labels=None, *, flags=0, w1_bf16=None, want_pose_logits=False, workspace=None):
+        self.lib = load_library()
+        W1, b1, W2, b2, Wa, ba, Wt, bt = params
+        N, C = X.shape[0], X.shape[-1]
+        P = X.numel() // (N * C)
+        Cp, J, K = W1.shape[1], W2.shape[1], Wt.shape[1]
+        dev, f32 = X.device, torch.float32
+        if tuple(W1.shape) != (C, Cp) or Wa.numel() != Cp or tuple(Wt.shape) != (C, K) or W2.shape[0] != Cp:
+            raise ApaError('PoseAttnEvalStep: W1 [C,Cp], W2 [Cp,J], Wa [Cp,1], Wt [C,K] expected')
+        if w1_bf16 is not None and w1_bf16.numel() != W1.numel():
+            raise ApaError('PoseAttnEvalStep: w1_bf16 must have W1\'s element count')
+        if labels is not None and labels.numel() != N:
+            raise ApaError('PoseAttnEvalStep: labels [N] expected')
+        flags &= APA_FLAG_SOFTMAX_ATT | APA_FLAG_RELU_ATT
+        dt = _feat_dtype(X)
+        new = lambda *shape, dt=f32: torch.empty(shape, dtype=dt, device=dev)
+        self.att, self.logits, self.zsave, self.abar = new(N, P, 1), new(N, K), new(N, C), new(N)
+        self.probs, self.pred = new(N, K), new(N, dt=torch.int64)
+        self.loss = new(1 + N) if labels is not None else None
+        self.Pl = new(N, P, J) if want_pose_logits else None
+        need = int(self.lib.apa_pose_attn_eval_workspace_bytes(N, P, C, Cp, J, K, flags, dt, int(bool(want_pose_logits))))
+        if workspace is None or workspace.numel() < need:
+            workspace = torch.empty((max(need, 16),), dtype=torch.uint8, device=dev)
+        self.workspace = workspace
+        self._keep = (X, params, labels, w1_bf16)
+        self._route = c_int(-1)
+        io = ApaPoseAttnEvalIO()
+        io.X = _dev_ptr(X, 'X')
+        for name, t in (('W1', W1), ('b1', b1), ('W2', W2), ('b2', b2), ('Wa', Wa), ('ba', ba), ('Wt', Wt), ('bt', bt)):
+            setattr(io, name, _dev_ptr(t, name, f32))
+        io.W1_bf16 = None if w1_bf16 is None else _dev_ptr(w1_bf16, 'w1_bf16', torch.bfloat16)
+        io.labels = _dev_ptr(labels, 'labels', torch.int64)
+        for name in ('att', 'logits', 'zsave', 'abar', 'probs', 'pred', 'loss', 'Pl'):
+            t = getattr(self, name)
+            setattr(io, name, None if t is None else t.data_ptr())
+        io.ws, io.ws_bytes = workspace.data_ptr(), workspace.numel()
+        io.route = ctypes.pointer(self._route)
+        self._io = io
+        self._args = [ctypes.addressof(io), N, P, C, Cp, J, K, flags, dt]
+
+    @property
+    def route(self) -> Optional[int]:
+        """which route the last `run()` took (None before the first one)"""
+        return None if self._route.value < 0 else int(self._route.value)
+
+    def rebind(self, X=None, labels=None) -> None:
+        """Point the bound step at other inputs of the same shapes / dtypes."""
+        keep = list(self._keep)
+        if X is not None:
+            if X.shape != keep[0].shape or X.dtype != keep[0].dtype:
+                raise ApaError('PoseAttnEvalStep.rebind: same shape and dtype expected')
+            self._io.X = _dev_ptr(X, 'X')
+            keep[0] = X
+        if labels is not None:
+            if keep[2] is None or labels.numel() != keep[2].numel():
+                raise ApaError('PoseAttnEvalStep.rebind: the step was bound without labels (or to another batch size)')
+            self._io.labels = _dev_ptr(labels, 'labels', torch.int64)
+            keep[2] = labels
+        self._keep = tuple(keep)
+
+    def run(self, stream: Optional[int] = None) -> None:
+        rc = self.lib.apa_pose_attn_eval_step(*self._args, _stream_ptr() if stream is None else stream)
+        if rc != 0:
+            _check(rc, 'apa_pose_attn_eval_step')
 
 
 class ApaWeightImage(ctypes.Structure):

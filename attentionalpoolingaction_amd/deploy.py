@@ -1100,3 +1100,130 @@ class FusedHeadStep:
         if self.pose_form:
             ep['PoseLogits'] = st.Pl.view(n, h, w, -1)
         return total, ep
+
+
+class FusedHeadEval:
+    """The evaluation counterpart of FusedHeadStep: what eval.py:181-197 computes from `network_fn(images)` -- the
+    logits, `tf.argmax(logits, 1)` and the scores (`tf.nn.softmax(logits, -1)`, or `tf.sigmoid(logits)` when
+    TRAIN.LOSS_FN_ACTION starts with 'multi-label') -- with the head as ONE host call on the conv5 map:
+    `apa_pose_attn_eval_step` for the cfg 003 form (attention from pose_pre_logits, which on the served shapes is
+    never written: the pose-head product's epilogue emits the attention logits), `apa_attn_head_eval_step` for the
+    single-layer forms (cfg 002, per-class maps).
+
+        ev = deploy.FusedHeadEval(network_fn, cfg)          # network_fn built with is_training=False; raises
+        scores, predictions, end_points = ev(images, labels_action)      # ValueError if the module path is needed
+        meter.update(scores, labels_action)                 # eval_utils.Evaluation: accuracy / mAP at the end
+
+    * end_points: 'Logits', 'PosePrelogitsBasedAttention', 'PoseLogits' (cfg 003 form with want_pose_logits=True;
+      eval.py fetches it only under --ept), 'labels' when given, 'TemporalAttention' for video input with
+      NET.USE_TEMPORAL_ATT.  Views of the bound step's buffers: overwritten by the next batch of the same shape.
+    * one bound step (outputs, workspace) per batch shape / dtype, the `max_bound_steps` most recent.
+    * 5-D video input [B,F,H,W,C]: the frames are folded into the batch for the head step, the frame logits go through
+      `cof.frame_pool_fwd` (with the TemporalAttention conv when configured) and the scores and predictions are taken
+      from the POOLED logits (nets_factory.py:354-374, then eval.py:193-197).
+    * the weights are read through the pointers a step was bound to: a parameter with a new storage binds a new step.
+      No bf16 operand copy of W1 is kept here (there is no optimiser launch to keep it current): the conversion runs
+      inside the call."""
+
+    max_bound_steps = 4
+
+    def __init__(self, network_fn, cfg):
+        why = self.unsupported_reason(network_fn.head, cfg, network_fn)
+        if why:
+            raise ValueError('FusedHeadEval: ' + why)
+        self.network_fn, self.head, self.cfg = network_fn, network_fn.head, cfg
+        self.pose_form = not self.head.single_layer
+        self.multi_label = str(cfg.TRAIN.LOSS_FN_ACTION).startswith('multi-label')
+        self._steps = collections.OrderedDict()
+
+    @staticmethod
+    def unsupported_reason(head, cfg, network_fn=None) -> str:
+        from . import nets_factory
+        if isinstance(head, nets_factory.PoseAttentionLogitsHead):
+            return 'the pose-heatmap attention head (USE_POSE_ATTENTION_LOGITS) evaluates through network_fn'
+        if isinstance(head, nets_factory.BaselineHead) or not isinstance(head, nets_factory.AttentionalPoolingHead):
+            return 'the baseline head (cfg 001) has no attention op: it evaluates through network_fn'
+        if head.is_training:
+            return 'a training-mode head: build network_fn with is_training=False (evaluation draws no dropout mask)'
+        if head.rank != 1:
+            return 'rank > 1 runs through the per-op module'
+        if head.with_pose_feat:
+            return '..._WITH_POSE_FEAT (pose logits concatenated to the top-down input) runs through the per-op module'
+        if head.want_topdown:
+            return 'the TopDownAttention dump is materialised by the per-op module only'
+        if not head.single_layer:
+            if head.per_class:
+                return 'per-class maps from pose_pre_logits'
+            if head.pose_w1.shape[0] != head.in_channels:
+                return 'a separate feature tap for the pose head (NET.LAST_CONV_MAP_FOR_POSE)'
+        return ''
+
+    def _bind(self, X, want_pose_logits):
+        from .custom_ops import custom_ops_factory as cof
+        h = self.head
+        flags = cof.attn_flags(h.softmax_att, h.relu_att, False, self._preact)
+        if self.pose_form:
+            return cof.PoseAttnEvalStep(
+                X, (h.pose_w1.data, h.pose_b1.data, h.pose_w2.data, h.pose_b2.data, h.att_weights.data,
+                    h.att_biases.data, h.td_weights.data, h.td_biases.data), flags=flags,
+                want_pose_logits=want_pose_logits)
+        return cof.HeadEvalStep(X, X, h.att_weights.data, h.att_biases.data, h.td_weights.data, h.td_biases.data,
+                                flags=flags)
+
+    def _params(self):
+        h = self.head
+        names = ('att_weights', 'att_biases', 'td_weights', 'td_biases')
+        if self.pose_form:
+            names = ('pose_w1', 'pose_b1', 'pose_w2', 'pose_b2') + names
+        return [getattr(h, n) for n in names]
+
+    def __call__(self, images, labels_action=None, want_pose_logits: bool = False):
+        from . import eval_utils
+        from .custom_ops import custom_ops_factory as cof
+        frames = 1
+        if images.dim() == 5:                                   # nets_factory.py:121-125
+            frames = images.shape[1]
+            images = images.reshape(-1, *images.shape[2:])
+        last_conv, self._preact = self.network_fn.features(images)
+        if last_conv.dim() != 4:
+            raise ValueError('FusedHeadEval: [N,H,W,C] (or [B,F,H,W,C]) feature maps expected')
+        if self._preact and not self.head.can_fuse_input_relu(last_conv.dtype):
+            last_conv, self._preact = torch.relu(last_conv), False
+        n, hh, ww, c = last_conv.shape
+        X = last_conv.detach().contiguous().view(n, -1, c)
+        want_pl = bool(want_pose_logits and self.pose_form)
+        key = (tuple(X.shape), X.dtype, self._preact, want_pl, tuple(p.data_ptr() for p in self._params()))
+        st = self._steps.pop(key, None)
+        if st is None:
+            st = self._bind(X, want_pl)
+        else:
+            st.rebind(X=X) if self.pose_form else st.rebind(X)
+        self._steps[key] = st                                   # most recent last
+        while len(self._steps) > self.max_bound_steps:
+            self._steps.popitem(last=False)
+        st.run()
+        self.step = st
+        ep = {'Logits': st.logits, 'PosePrelogitsBasedAttention': st.att.view(n, hh, ww, -1)}
+        if want_pl:
+            ep['PoseLogits'] = st.Pl.view(n, hh, ww, -1)
+        if labels_action is not None:
+            ep['labels'] = labels_action.squeeze() if labels_action.dim() > 1 else labels_action   # eval.py:198
+        logits, scores, pred = st.logits, st.probs, st.pred
+        if frames > 1:                                          # nets_factory.py:354-374
+            tw = tb = None
+            temporal = self.network_fn.temporal
+            if temporal is not None:
+                if not temporal._bias_initialised:
+                    with torch.no_grad():
+                        temporal['biases'].fill_(1.0 / frames)
+                    temporal._bias_initialised = True
+                tw, tb = temporal['weights'].data.reshape(-1).contiguous(), temporal['biases'].data
+            ep['logits_beforePool'] = st.logits
+            logits, tatt = cof.frame_pool_fwd(st.logits, frames, tw, tb)
+            if tatt is not None:
+                ep['TemporalAttention'] = tatt.view(-1, frames, 1, 1)
+            ep['Logits'] = logits
+            scores, pred = eval_utils.predict(logits, multi_label=self.multi_label)
+        elif self.multi_label:
+            scores, pred = eval_utils.predict(logits, multi_label=True)
+        return scores, pred, ep

@@ -17,15 +17,53 @@ from typing import List, Tuple
 import numpy as np
 
 
-def predict(logits):
-    """(probs [N,K] float32, predictions [N] int64) on the device of `logits`
-    (eval.py:193-197: tf.argmax(logits,1), tf.nn.softmax(logits,-1))."""
+def predict(logits, multi_label=False):
+    """(scores [N,K] float32, predictions [N] int64) on the device of `logits`
+    (eval.py:193-197: tf.argmax(logits,1), tf.nn.softmax(logits,-1)).  `multi_label=True` (TRAIN.LOSS_FN_ACTION
+    starts with 'multi-label', eval.py:194-195): the scores are tf.sigmoid(logits), element-wise -- plain tensor
+    expressions on whatever device holds the logits; the predictions stay the argmax of the logits."""
     import torch
+    if multi_label:
+        logits = logits.float()
+        return torch.sigmoid(logits), logits.argmax(dim=1)
     from .custom_ops import custom_ops_factory as cof
     labels = torch.zeros((logits.shape[0],), dtype=torch.int64, device=logits.device)
     _, _, probs, pred = cof.softmax_xent_fwd_bwd(logits.contiguous(), labels, want_grad=False,
                                                  want_probs=True, want_pred=True)
     return probs, pred
+
+
+class Evaluation:
+    """The accumulation of eval.py:262-306 without a host round trip per batch: `update(scores, labels)` keeps the
+    batch's scores [n,K] and labels [n] where they are (the device of the scores); `result()` concatenates, copies to
+    the host ONCE and returns {'accuracy', 'mAP', 'aps'} through `accuracy` / `compute_map` (eval.py:303-306)."""
+
+    def __init__(self):
+        self._scores, self._labels = [], []
+
+    def update(self, scores, labels) -> None:
+        import torch
+        scores = scores.detach()
+        labels = torch.as_tensor(labels).detach().reshape(-1).to(scores.device)
+        if scores.dim() != 2 or labels.numel() != scores.shape[0]:
+            raise ValueError('Evaluation.update: scores [n,K] and labels [n] expected')
+        self._scores.append(scores.float().clone())      # (a bound step overwrites its buffers on the next batch)
+        self._labels.append(labels.to(torch.int64).clone())
+
+    def __len__(self) -> int:
+        return sum(int(s.shape[0]) for s in self._scores)
+
+    def result(self):
+        import torch
+        if not self._scores:
+            raise ValueError('Evaluation.result: nothing was accumulated')
+        k = self._scores[0].shape[1]
+        # one buffer [n, K + 1] (labels are exact in float64 up to 2^53), one device-to-host copy
+        both = torch.cat([torch.cat(self._scores).double(), torch.cat(self._labels).double().unsqueeze(1)], dim=1).cpu()
+        both = both.numpy()
+        scores, labels = both[:, :k].astype(np.float32), both[:, k].astype(np.int64)
+        m, aps = compute_map(scores, labels)
+        return {'accuracy': accuracy(scores, labels), 'mAP': m, 'aps': aps}
 
 
 def voc_ap(rec: np.ndarray, prec: np.ndarray) -> float:

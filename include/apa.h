@@ -329,6 +329,57 @@ int apa_pose_attn_train_step(const apa_pose_attn_step_io* io, int N, int P, int 
                              unsigned flags, float keep_prob, uint64_t seed, uint64_t offset, int dtype,
                              void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * One host call for the cfg 003 head at EVALUATION time (eval.py:181-197 on the model of
+ * 003_MPII_ResNet_withPoseAttention.yaml): apa_pose_head_fwd followed by apa_attn_head_eval_step(X, Xatt = Ppre, ...).
+ * APA_FLAG_TRAIN is cleared (is_training=False); APA_FLAG_SOFTMAX_ATT / RELU_ATT are honoured.
+ * Two routes, reported in *io->route when that (host) pointer is given:
+ *   1  fused     io->Pl == NULL, dtype bf16, Cp % 128 == 0, C % 64 == 0, X 16-byte aligned, b1 and Wa 16-byte
+ *                aligned, and ceil(N*P / 256) * (Cp / 128) no larger than the number of compute units (the pose-head
+ *                product then runs as one resident round of the DMA-ring GEMM).  The product's epilogue applies bias
+ *                and relu, rounds to bf16 -- the values apa_pose_attn_train_step's attention was trained on --
+ *                contracts each 128-column tile with the fp32 Wa and writes one fp32 partial per row and tile; a
+ *                second launch adds the Cp / 128 partials in tile order (no atomics: two runs agree bit for bit),
+ *                then ba and identity / relu.  pose_pre_logits never exists in memory.
+ *   0  composed  every other case (fp32 features, other Cp, Pl requested, ...): the existing kernels back to back
+ *                inside the call, pose_pre_logits in the workspace.  With Pl requested and Cp in {256,512,768,1024},
+ *                J <= 16, bf16, the Pl product's pass over pose_pre_logits also emits att (as in the training step).
+ * (Both routes also need what apa_attn_pool_fwd needs for M == 1: C and Cp whole 16-byte vectors.)
+ * Outputs as apa_attn_head_eval_step; att holds the attention map (softmax applied under APA_FLAG_SOFTMAX_ATT).
+ * labels / loss ([1+N]) may both be NULL.  Null required pointers: APA_ERR_INVALID_ARG before anything touches the
+ * GPU; ws_bytes below apa_pose_attn_eval_workspace_bytes(): APA_ERR_WORKSPACE.
+ * want_pose_logits: whether io->Pl will be given (the size covers both routes today and does not depend on it).
+ */
+typedef struct apa_pose_attn_eval_io {
+  const void* X;            /* [N,P,C] dtype                                             */
+  const float* W1;          /* [C,Cp]                                                    */
+  const float* b1;          /* [Cp]                                                      */
+  const void* W1_bf16;      /* optional bf16 [C,Cp] copy of W1 (as in the train step)    */
+  const float* W2;          /* [Cp,J]                                                    */
+  const float* b2;          /* [J]                                                       */
+  const float* Wa;          /* [Cp,1]                                                    */
+  const float* ba;          /* [1]                                                       */
+  const float* Wt;          /* [C,K]                                                     */
+  const float* bt;          /* [K]                                                       */
+  const int64_t* labels;    /* [N] or NULL                                               */
+  /* outputs */
+  float* att;               /* [N,P]                                                     */
+  float* logits;            /* [N,K]                                                     */
+  float* zsave;             /* [N,C]                                                     */
+  float* abar;              /* [N]                                                       */
+  float* probs;             /* [N,K]                                                     */
+  int64_t* pred;            /* [N]                                                       */
+  float* loss;              /* [1+N] or NULL (with labels)                               */
+  float* Pl;                /* [N,P,J] or NULL: PoseLogits on request (composed route)   */
+  /* scratch */
+  void* ws;  size_t ws_bytes;
+  int* route;               /* optional, HOST memory: 1 fused, 0 composed                */
+} apa_pose_attn_eval_io;
+size_t apa_pose_attn_eval_workspace_bytes(int N, int P, int C, int Cp, int J, int K, unsigned flags, int dtype,
+                                          int want_pose_logits);
+int apa_pose_attn_eval_step(const apa_pose_attn_eval_io* io, int N, int P, int C, int Cp, int J, int K,
+                            unsigned flags, int dtype, void* stream);
+
 /* Pose loss: src/loss.py:29-70 ('l2', LOSS_FN_POSE_SAMPLED off) fused with its gradient.
  *   loss[0] = wt * sum_j mean_n( valid[n,j] ? 0.5*sum_p (Pl-lbl)^2 / (N*P) : 0 )
  *   dPl = grad_scale * wt * valid[n,j] * (Pl - lbl) / (N*N*P)

@@ -9,6 +9,9 @@ headline stays the cfg 002 training workload); run this file directly for one wo
   perclass  per-class bottom-up maps (M == K), HMDB-51 shape (K = 51, bf16) or K = 393:
             1.893 GFLOP/img at K = 393, 0.246 at K = 51.
   eval002   BASELINE configs[1]: cfg 002 evaluation step (forward + softmax + argmax, one call).
+  eval003   cfg 003 evaluation step, bf16: the one-call apa_pose_attn_eval_step (attention logits out of the
+            pose-head product's epilogue, pose_pre_logits never written) against the sequence cof.pose_head_fwd +
+            cof.HeadEvalStep, alternating in one process; prints both medians and HIP-event times per host call.
 
 Each builder returns (step_fn, info): `step_fn()` enqueues one step on the current stream; `info`
 carries the workload name and the algorithmic work per image.
@@ -353,6 +356,103 @@ def build_eval002(cof, dev, N=32, H=14, K=393, dtype='f32', rotate=0):
     return _round_robin([ev.run for ev in evs]), info
 
 
+def build_eval003(cof, dev, N=32, H=14, K=393, dtype='bf16', rotate=0):
+    """cfg 003 evaluation step: {'fused': the one-call step, 'fused_shadow': the same with a caller-kept bf16 copy of
+    W1, 'sequence': cof.pose_head_fwd + cof.HeadEvalStep on the pose head's Ppre} as round-robin step functions over
+    the same rotating X sets (outputs and workspaces shared per variant), + info + a function that times every HOST
+    CALL of the variants with HIP events."""
+    C, Cp, J, P = 2048, 768, 16, H * H
+    td = torch.bfloat16 if dtype == 'bf16' else torch.float32
+    g = torch.Generator().manual_seed(42)
+    W1 = (torch.randn(C, Cp, generator=g) / C ** 0.5).to(dev); b1 = torch.zeros(Cp, device=dev)
+    W2 = (torch.randn(Cp, J, generator=g) / Cp ** 0.5).to(dev); b2 = torch.zeros(J, device=dev)
+    Wa = (torch.randn(Cp, 1, generator=g) / Cp ** 0.5).to(dev); ba = torch.zeros(1, device=dev)
+    Wt = (torch.randn(C, K, generator=g) / C ** 0.5).to(dev); bt = torch.zeros(K, device=dev)
+    params = (W1, b1, W2, b2, Wa, ba, Wt, bt)
+    per_set = N * P * C * (2 if dtype == 'bf16' else 4)          # forward only: X is all that streams
+    R = _n_sets(per_set, rotate)
+    Xs = [_features(N, P, C, td, dev, seed=42 + r) for r in range(R)]
+    w1_bf16 = W1.to(torch.bfloat16).contiguous() if dtype == 'bf16' else None
+    fused, shadow, seq_eval = [], [], []
+    for Xr in Xs:
+        fused.append(cof.PoseAttnEvalStep(Xr, params, workspace=fused[0].workspace if fused else None))
+        shadow.append(cof.PoseAttnEvalStep(Xr, params, w1_bf16=w1_bf16,
+                                           workspace=shadow[0].workspace if shadow else None))
+    Ppre = torch.empty((N, P, Cp), dtype=td, device=dev)
+    Pl = torch.empty((N, P, J), dtype=torch.float32, device=dev)
+    pws = cof.pose_head_fwd(Xs[0], W1, b1, W2, b2, out=(Ppre, Pl))[2]
+    for Xr in Xs:
+        seq_eval.append(cof.HeadEvalStep(Xr, Ppre, Wa, ba, Wt, bt,
+                                         workspace=seq_eval[0].workspace if seq_eval else None))
+
+    def seq_run(r):
+        cof.pose_head_fwd(Xs[r], W1, b1, W2, b2, workspace=pws, out=(Ppre, Pl))
+        seq_eval[r].run()
+
+    steps = {'fused': _round_robin([st.run for st in fused]),
+             'fused_shadow': _round_robin([st.run for st in shadow]),
+             'sequence': _round_robin([(lambda r=r: seq_run(r)) for r in range(R)])}
+
+    def call_times(n=40):
+        """median HIP-event time of each host call (events recorded on the stream around the call)"""
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
+        acc = {'fused: apa_pose_attn_eval_step': [], 'fused_shadow: apa_pose_attn_eval_step': [],
+               'sequence: apa_pose_head_fwd': [], 'sequence: apa_attn_head_eval_step': []}
+        for i in range(n):
+            r = i % R
+            for name, sts in (('fused', fused), ('fused_shadow', shadow)):
+                ev[0].record(); sts[r].run(); ev[1].record()
+                torch.cuda.synchronize()
+                acc[name + ': apa_pose_attn_eval_step'].append(ev[0].elapsed_time(ev[1]))
+            ev[0].record()
+            cof.pose_head_fwd(Xs[r], W1, b1, W2, b2, workspace=pws, out=(Ppre, Pl))
+            ev[1].record()
+            seq_eval[r].run()
+            ev[2].record()
+            torch.cuda.synchronize()
+            acc['sequence: apa_pose_head_fwd'].append(ev[0].elapsed_time(ev[1]))
+            acc['sequence: apa_attn_head_eval_step'].append(ev[1].elapsed_time(ev[2]))
+        return {k: round(sorted(v)[len(v) // 2] * 1e3, 2) for k, v in acc.items()}
+
+    info = {'workload': 'cfg003 eval step (pose head 2048->768 + attention from pose_pre_logits + M=1 pooling + softmax '
+                        '+ argmax); per-GPU batch {} x {}x{}x{} {}, K={}'.format(N, H, H, C, dtype, K) +
+                        _rot_note(R, per_set).replace('X/dX', 'X'),
+            'bound': 'mfma', 'dtype': dtype, 'N': N, 'rotate': R, 'flops_per_image': 2.0 * P * C * Cp,
+            'routes': lambda: {'fused': fused[0].route, 'fused_shadow': shadow[0].route}}
+    return steps, info, call_times
+
+
+def run_eval003(cof, dev, args):
+    """The variants alternate inside every round (one process, same buffers, same clocks): per variant the median over
+    the rounds of the mean step time of a loop of `steps` steps."""
+    steps, info, call_times = build_eval003(cof, dev, args.batch, args.hw, args.classes or 393, args.dtype or 'bf16',
+                                            rotate=args.rotate)
+    for fn in steps.values():
+        for _ in range(max(args.warmup, info['rotate'])):
+            fn()
+    torch.cuda.synchronize()
+    per = {k: [] for k in steps}
+    rounds = 0
+    t_all = time.perf_counter()
+    while rounds < 9 or time.perf_counter() - t_all < 0.5:
+        for k, fn in steps.items():
+            t0 = time.perf_counter()
+            for _ in range(args.steps):
+                fn()
+            torch.cuda.synchronize()
+            per[k].append((time.perf_counter() - t0) / args.steps)
+        rounds += 1
+        if rounds >= 200:
+            break
+    med = {k: sorted(v)[len(v) // 2] for k, v in per.items()}
+    out = report(info, med['fused'], rounds)
+    out['us_per_step'] = {k: round(v * 1e6, 2) for k, v in med.items()}
+    out['us_per_step_min'] = {k: round(min(v) * 1e6, 2) for k, v in per.items()}
+    out['routes'] = info['routes']()
+    out['us_per_call_hip_events'] = call_times()
+    return out
+
+
 # algorithmic HBM bytes of the four pose-attention kernels (fp32 parameters / F / logits; X and dX in the feature dtype)
 def poseatt_kernel_bytes(N, P, C, J, M, K, xbytes):
     R = M * C
@@ -480,7 +580,7 @@ def report(info, sec, repeats):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument('--workload', default='cfg003', choices=['cfg003', 'perclass', 'eval002', 'rank1', 'posebwd', 'posebwd_acc', 'update003',
+    ap.add_argument('--workload', default='cfg003', choices=['cfg003', 'perclass', 'eval002', 'eval003', 'rank1', 'posebwd', 'posebwd_acc', 'update003',
                                                          'update_perclass', 'poseatt'])
     ap.add_argument('--batch', type=int, default=32)
     ap.add_argument('--hw', type=int, default=14)
@@ -503,6 +603,9 @@ def main():
     if args.workload in ('update003', 'update_perclass'):
         print(json.dumps(run_update_pair(cof, dev, 'cfg003' if args.workload == 'update003' else 'perclass',
                                          rotate=args.rotate)))
+        return
+    if args.workload == 'eval003':
+        print(json.dumps(run_eval003(cof, dev, args)))
         return
     if args.workload == 'poseatt':
         step, info, kernel_times = build_poseatt(cof, dev, args.batch, args.hw, args.classes or 393,
