@@ -514,6 +514,134 @@ extern "C" int apa_pose_attn_train_step(const apa_pose_attn_step_io* io, int N, 
                         s.db2, s.dWa, s.dba, s.loss_pose, bump, s.ws_pose, s.ws_pose_bytes, N, P, C, Cp, J, dtype, a, st);
 }
 
+// ---- the one-call steps on a batch of clips (apa.h: apa_clip_pool) -------------------------------------------------
+// the pooling workspace, then the clip loss's scratch
+static size_t clip_step_pool_bytes(int N, int P, int C, int Ca, int K, int M, unsigned flags) {
+  return align_up(apa_attn_pool_workspace_bytes(N, P, C, Ca, K, M, flags), 256);
+}
+
+extern "C" size_t apa_clip_step_workspace_bytes(int N, int frames, int P, int C, int Ca, int K, int M,
+                                                unsigned flags) {
+  if (N <= 0 || frames <= 0 || N % frames != 0) return 0;
+  const size_t pool = apa_attn_pool_workspace_bytes(N, P, C, Ca, K, M, flags);
+  return pool ? clip_step_pool_bytes(N, P, C, Ca, K, M, flags) + apa_clip_xent_workspace_bytes(N / frames, frames, K)
+              : 0;
+}
+
+// everything apa_clip_xent_fwd_bwd would refuse, BEFORE the forward half is launched; *clip_ws: the loss's scratch
+static int clip_step_check(const char* fn, const apa_clip_pool* clip, const int64_t* labels, const float* loss,
+                           const float* logits, const float* G, void* ws, size_t ws_bytes, int N, int P, int C,
+                           int Ca, int K, int M, unsigned flags, int dtype, size_t* pool_bytes) {
+  if (!clip || !labels || !loss || !logits || !G) {
+    set_error("%s: null clip / labels / loss / logits / G pointer", fn);
+    return APA_ERR_INVALID_ARG;
+  }
+  const int rc = check_common(fn, N, P, C, Ca, K, M, dtype);
+  if (rc != APA_OK) return rc;
+  if (clip->frames <= 0 || N % clip->frames != 0) {
+    set_error("%s: N=%d is not a whole number of clips of %d frames", fn, N, clip->frames);
+    return APA_ERR_INVALID_ARG;
+  }
+  if (!clip->pooled || (clip->w && (!clip->b || !clip->tatt || !clip->dw || !clip->db))) {
+    set_error("%s: apa_clip_pool needs pooled, and with w also b, tatt, dw and db", fn);
+    return APA_ERR_INVALID_ARG;
+  }
+  *pool_bytes = clip_step_pool_bytes(N, P, C, Ca, K, M, flags);
+  const size_t need = *pool_bytes + apa_clip_xent_workspace_bytes(N / clip->frames, clip->frames, K);
+  if (!ws || ws_bytes < need) {
+    set_error("%s: workspace too small (%zu < %zu = apa_clip_step_workspace_bytes)", fn, ws_bytes, need);
+    return APA_ERR_WORKSPACE;
+  }
+  return APA_OK;
+}
+
+static int clip_step_loss(const apa_clip_pool& c, const float* logits, const int64_t* labels, float* loss, float* G,
+                          void* ws, size_t pool_bytes, int N, int K, float wt, float grad_scale, void* stream) {
+  const int B = N / c.frames;
+  return apa_clip_xent_fwd_bwd(logits, labels, c.w, c.b, c.pooled, c.tatt, loss, G, c.dw, c.db,
+                               static_cast<char*>(ws) + pool_bytes, apa_clip_xent_workspace_bytes(B, c.frames, K), B,
+                               c.frames, K, wt, grad_scale, stream);
+}
+
+extern "C" int apa_attn_head_train_step_clips(const apa_clip_pool* clip, const apa_hooks* hooks, const void* X,
+                                              const void* Xatt, const float* Wa, const float* ba, const float* Wt,
+                                              const float* bt, const int64_t* labels, float loss_wt,
+                                              float grad_scale, float* logits, float* att, float* zsave,
+                                              float* abar, float* loss, float* G, void* dX, void* dXatt,
+                                              float* dWa, float* dba, float* dWt, float* dbt, void* ws,
+                                              size_t ws_bytes, int N, int P, int C, int Ca, int K, int M,
+                                              unsigned flags, float keep_prob, uint64_t seed, uint64_t offset,
+                                              int dtype, void* stream) {
+  const Hooks hk(hooks);
+  flags &= APA_PUBLIC_FLAGS;
+  size_t pool_bytes = 0;
+  int rc = clip_step_check("apa_attn_head_train_step_clips", clip, labels, loss, logits, G, ws, ws_bytes, N, P, C, Ca,
+                           K, M, flags, dtype, &pool_bytes);
+  if (rc != APA_OK) return rc;
+  // the per-image cross-entropy the flat step folds into its neighbours (M1Xent) has no place here: the loss is
+  // taken on the pooled rows, so both halves run as the per-op entry points do and G travels through memory
+  rc = attn_pool_fwd_impl(hk, nullptr, nullptr, X, Xatt, Wa, ba, Wt, bt, logits, att, zsave, abar, nullptr, ws,
+                          pool_bytes, N, P, C, Ca, K, M, flags, keep_prob, seed, offset, dtype, stream);
+  if (rc != APA_OK) return rc;
+  rc = clip_step_loss(*clip, logits, labels, loss, G, ws, pool_bytes, N, K, loss_wt, grad_scale, stream);
+  if (rc != APA_OK) return rc;
+  // same workspace, nothing in between (the loss's scratch lies behind it)
+  return attn_pool_bwd_impl(hk, nullptr, nullptr, X, Xatt, Wa, ba, Wt, bt, att, zsave, abar, G, dX, dXatt, dWa, dba,
+                            dWt, dbt, ws, pool_bytes, N, P, C, Ca, K, M, flags | APA_FLAG_WS_FROM_FWD, keep_prob, seed,
+                            offset, dtype, stream);
+}
+
+// apa_pose_attn_train_step's composed route with the clip loss in place of the per-image cross-entropy
+extern "C" int apa_pose_attn_train_step_clips(const apa_clip_pool* clip, const apa_pose_attn_step_io* io, int N, int P,
+                                              int C, int Cp, int J, int K, unsigned flags, float keep_prob,
+                                              uint64_t seed, uint64_t offset, int dtype, void* stream) {
+  if (!io) {
+    set_error("apa_pose_attn_train_step_clips: null io");
+    return APA_ERR_INVALID_ARG;
+  }
+  const apa_pose_attn_step_io& s = *io;
+  if (!s.X || !s.W1 || !s.b1 || !s.W2 || !s.b2 || !s.Wa || !s.ba || !s.Wt || !s.bt || !s.labels ||
+      !s.pose_labels || !s.pose_valid || !s.Ppre || !s.Pl || !s.att || !s.logits || !s.zsave || !s.abar ||
+      !s.loss_action || !s.loss_pose || !s.G || !s.dPl || !s.dZ || !s.dX || !s.dW1 || !s.db1 || !s.dW2 || !s.db2 ||
+      !s.dWa || !s.dba || !s.dWt || !s.dbt || !s.ws_pool || !s.ws_pose) {
+    set_error("apa_pose_attn_train_step_clips: null pointer in apa_pose_attn_step_io (only W1_bf16 / W2T_bf16 may be NULL)");
+    return APA_ERR_INVALID_ARG;
+  }
+  if (J <= 0) {
+    set_error("apa_pose_attn_train_step_clips: J=%d", J);
+    return APA_ERR_INVALID_ARG;
+  }
+  if (flags & (APA_FLAG_RELU_INPUT | APA_FLAG_RNG_EXTERNAL)) {
+    set_error("apa_pose_attn_train_step_clips: APA_FLAG_RELU_INPUT / APA_FLAG_RNG_EXTERNAL are served by the per-op "
+              "entry points");
+    return APA_ERR_UNSUPPORTED;
+  }
+  flags &= APA_PUBLIC_FLAGS & ~(APA_FLAG_WS_FROM_FWD | APA_FLAG_DXATT_RANK1);
+  size_t pool_bytes = 0;
+  int rc = clip_step_check("apa_pose_attn_train_step_clips", clip, s.labels, s.loss_action, s.logits, s.G, s.ws_pool,
+                           s.ws_pool_bytes, N, P, C, Cp, K, 1, flags, dtype, &pool_bytes);
+  if (rc != APA_OK) return rc;
+  // The four calls a caller without this entry point runs, for EVERY shape.  The launches apa_pose_attn_train_step
+  // shares between neighbouring ops on its fast bf16 route (attention logits out of the Pl product's epilogue, dWa / dba
+  // on the pose head's backward rows pass, the pooling pass's dX share in the dX product's epilogue) sum in other
+  // orders than the per-op kernels -- att moves by 2.5e-7, dX by a bf16 ulp -- and this entry point promises the bits
+  // of the separate calls (apa.h); the bf16 operand copies in io (W1_bf16, W2T_bf16) are not read here.
+  rc = apa_pose_head_fwd(s.X, s.W1, s.b1, s.W2, s.b2, s.Ppre, s.Pl, s.ws_pose, s.ws_pose_bytes, N, P, C, Cp, J, dtype,
+                         stream);
+  if (rc != APA_OK) return rc;
+  rc = apa_pose_l2_loss_fwd_bwd(s.Pl, s.pose_labels, s.pose_valid, s.loss_pose, s.dPl,
+                                pose_ws_loss_scratch(s.ws_pose, N, P, C, Cp, J, dtype),
+                                apa_pose_l2_workspace_bytes(N, P, J), N, P, J, s.pose_wt, s.grad_scale, stream);
+  if (rc != APA_OK) return rc;
+  rc = apa_attn_head_train_step_clips(clip, nullptr, s.X, s.Ppre, s.Wa, s.ba, s.Wt, s.bt, s.labels, s.action_wt,
+                                      s.grad_scale, s.logits, s.att, s.zsave, s.abar, s.loss_action, s.G, s.dX, s.dZ,
+                                      s.dWa, s.dba, s.dWt, s.dbt, s.ws_pool, s.ws_pool_bytes, N, P, C, Cp, K, 1,
+                                      flags | APA_FLAG_DXATT_RANK1, keep_prob, seed, offset, dtype, stream);
+  if (rc != APA_OK) return rc;
+  return apa_pose_head_bwd_rank1ext(s.X, s.W1, s.W2, s.Ppre, s.dPl, s.dZ, s.Wa, s.dX, 1 | APA_POSE_WS_FROM_FWD, s.dW1,
+                                    s.db1, s.dW2, s.db2, s.ws_pose, s.ws_pose_bytes, N, P, C, Cp, J, dtype, stream);
+}
+
 extern "C" int apa_per_class_weight_images(const float* Wa, const float* ba, const float* Wt, const float* bt, void* ws,
                                            size_t ws_bytes, int N, int P, int C, int Ca, int K, int dtype,
                                            apa_weight_image* maps, int* nmaps, void* stream) {

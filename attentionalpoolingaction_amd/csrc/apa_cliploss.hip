@@ -1,0 +1,250 @@
+// apa_cliploss.hip -- the action loss of a video clip, value + gradient, in two launches:
+//   frame pooling / temporal attention   models/slim/nets/nets_factory.py:354-374 (reference)
+//   softmax cross-entropy on the POOLED logits                     src/loss.py:74-80
+//   and the whole backward down to the frame logits (tf.gradients in the reference).
+// x = frame logits [B*F, K] (row b*F + f), labels [B]:
+//   a[r]        = x[r,:] . w + b0                       (temporal attention; 1 without)     -> tatt
+//   pooled[b,k] = (1/F) sum_f x[b,f,k] a[b,f]                                                -> pooled
+//   loss[1+b]   = -log softmax(pooled[b])[labels[b]];   loss[0] = wt/B sum_b loss[1+b]
+//   g[b,k]      = wt grad_scale / B (softmax(pooled[b])[k] - [k == labels[b]])
+//   d[r]        = (1/F) sum_k g[b,k] x[r,k]
+//   G[r,k]      = (1/F) g[b,k] a[r] + d[r] w[k]         (the d / w terms vanish without temporal attention)
+//   dw[k]       = sum_r d[r] x[r,k];   db0 = sum_r d[r]                    (fixed order over the rows)
+// It replaces the module path's five launches (fp_att, fp_pool, softmax_xent, fp_bwd, fp_bwd_w) and the four
+// round trips through memory between them.  These tensors are tiny ([B*F, K] with K = 51, F <= 25): the launches
+// are latency chains, so the first one keeps a whole clip in one block -- a[], the pooled row and the gradient row
+// never leave the CU between the stages -- and the second one only does what needs every clip.
+//
+//   launch 1  clip_xent_kernel     one 4-wave block per clip: a (one wave per frame row), pooled (one thread per
+//                                  column), the row's cross-entropy (wave 0), G and d (one wave per frame row)
+//   launch 2  clip_finish_kernel   block 0: the batch mean loss[0] and db0; blocks 1..: 256 columns of dw each
+//                                  (temporal attention only)
+//
+// Which K takes which code:
+//   4 <= K <= 1024   the cross-entropy is pc_row_xent_any (apa_device.h): softmax_xent_kernel<NV4>'s arithmetic on
+//                    the pooled row in LDS -- half-wave trees, exp_fast -- and loss[0] is summed in that kernel's
+//                    order (B <= 64: 32 slots; else sum_scale_kernel's)
+//   K < 4, K > 1024  softmax_xent_stream_kernel's arithmetic (one wave, three passes, expf), loss[0] in
+//                    sum_scale_kernel's order
+//   K <= 4096        the pooled row and the gradient row live in LDS (32 KB at most)
+//   K >  4096        they live in memory: the pooled row in its output, the gradient row in the workspace
+// so that with F == 1 and no temporal attention (pooled = x * 1, G = g * 1) loss and G carry the very bits
+// apa_softmax_xent_fwd_bwd gives.  No atomics; every sum has one order: identical calls give identical bits.
+#include <math.h>
+
+#include "apa_device.h"
+#include "apa_internal.h"
+
+namespace apa {
+
+constexpr int CLIP_LDS_K = 4096;   // pooled + gradient rows in LDS up to this K
+constexpr int CLIP_LDS_F = 64;     // a[b, :] in LDS up to this F (else re-read from tatt)
+
+// dynamic LDS: [row_floats] pooled row | [row_floats] gradient row | [CLIP_LDS_F] a | [4] xent scratch
+template <bool TEMPORAL>
+__global__ __launch_bounds__(256) void clip_xent_kernel(
+    const float* __restrict__ x, const int64_t* __restrict__ labels, const float* __restrict__ w,
+    const float* __restrict__ b0, float* __restrict__ pooled, float* __restrict__ tatt,
+    float* __restrict__ loss, float* __restrict__ G, float* __restrict__ dws, float* __restrict__ gws,
+    int F, int K, int row_floats, float gscale) {
+  extern __shared__ __attribute__((aligned(16))) float clip_sm[];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int b = blockIdx.x;
+  const size_t rb = (size_t)b * F;                 // first frame row of the clip
+  const bool rows_lds = row_floats > 0;
+  float* prow = rows_lds ? clip_sm : pooled + (size_t)b * K;
+  float* grow = rows_lds ? clip_sm + row_floats : gws + (size_t)b * K;
+  float* sa = clip_sm + 2 * row_floats;
+  float* sx = sa + CLIP_LDS_F;
+  const float invF = 1.0f / (float)F;
+  const float* ap = nullptr;
+
+  if (TEMPORAL) {   // a[r] = x[r,:] . w + b0
+    for (int f = wave; f < F; f += 4) {
+      const float* xr = x + (rb + f) * K;
+      float acc = 0.f;
+      for (int k = lane; k < K; k += 64) acc = fmaf(xr[k], w[k], acc);
+      const float a = wave_sum(acc) + b0[0];
+      if (lane == 0) {
+        tatt[rb + f] = a;
+        if (F <= CLIP_LDS_F) sa[f] = a;
+      }
+    }
+    __syncthreads();
+    ap = F <= CLIP_LDS_F ? sa : tatt + rb;
+  }
+
+  // pooled[b,k]: frames in increasing f (F == 1 without attention: x * 1)
+  for (int k = threadIdx.x; k < K; k += 256) {
+    const float* xc = x + rb * K + k;
+    float acc = TEMPORAL ? xc[0] * ap[0] : xc[0];
+    for (int f = 1; f < F; ++f) {
+      const float xv = xc[(size_t)f * K];
+      acc = TEMPORAL ? fmaf(xv, ap[f], acc) : acc + xv;
+    }
+    const float p = acc * invF;
+    prow[k] = p;
+    if (rows_lds) pooled[(size_t)b * K + k] = p;
+  }
+  __syncthreads();
+
+  if (wave == 0) {   // the pooled row's cross-entropy: loss[1+b] and the gradient row
+    if (K >= 4 && K <= 1024) {
+      // a one-row problem for the shared row routine: row 0 of (labels + b, sx, grow)
+      const PcXent xe = {labels + b, sx, grow, gscale};
+      pc_row_xent_any(prow, 0, K, xe, true, grow);
+      if (lane == 0) loss[1 + b] = sx[1];
+    } else {         // softmax_xent_stream_kernel's arithmetic
+      const int lab = (int)labels[b];
+      float m = -INFINITY, xl = 0.f;
+      for (int k = lane; k < K; k += 64) {
+        const float v = prow[k];
+        if (v > m) m = v;
+        if (k == lab) xl = v;
+      }
+      const float mw = wave_max(m);
+      xl = wave_sum(xl);
+      float l = 0.f;
+      for (int k = lane; k < K; k += 64) l += expf(prow[k] - mw);
+      l = wave_sum(l);
+      const float inv = 1.0f / l;
+      // (that kernel also stores p as a probability, so its p - onehot is a subtraction of the ROUNDED product; here p
+      // has one use and the compiler would contract the two into an fma: contraction off for this loop)
+      for (int k = lane; k < K; k += 64) {
+#pragma clang fp contract(off)
+        const float p = expf(prow[k] - mw) * inv;
+        grow[k] = (p - (k == lab ? 1.0f : 0.0f)) * gscale;
+      }
+      if (lane == 0) loss[1 + b] = (lab >= 0 && lab < K) ? -(xl - mw - logf(l)) : 0.f;
+    }
+  }
+  __syncthreads();
+
+  // the gradient at the frame logits, one wave per frame row
+  for (int f = wave; f < F; f += 4) {
+    const size_t r = rb + f;
+    if (!TEMPORAL) {
+      for (int k = lane; k < K; k += 64) G[r * K + k] = grow[k] * invF;
+    } else {
+      const float* xr = x + r * K;
+      float acc = 0.f;
+      for (int k = lane; k < K; k += 64) acc = fmaf(grow[k], xr[k], acc);
+      const float d = wave_sum(acc) * invF;
+      const float a = ap[f];
+      for (int k = lane; k < K; k += 64) G[r * K + k] = fmaf(grow[k] * invF, a, d * w[k]);
+      if (lane == 0) dws[r] = d;
+    }
+  }
+}
+
+// sum of v[0 .. n) by one 256-thread block in sum_scale_kernel's order (apa_loss.hip); the result is valid in thread 0
+__device__ __forceinline__ float clip_block_sum(const float* __restrict__ v, int n, float* red) {
+  float acc = 0.f;
+  for (int i = threadIdx.x; i < n; i += 256) acc += v[i];
+  acc = wave_sum(acc);
+  __syncthreads();   // (red may still be read from a previous sum)
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
+  __syncthreads();
+  return (red[0] + red[1]) + (red[2] + red[3]);
+}
+
+// block 0: loss[0] (in apa_softmax_xent_fwd_bwd's summation order for this (B, K)) and db0; block 1 + j: dw[256 j ..]
+__global__ __launch_bounds__(256) void clip_finish_kernel(const float* __restrict__ x, const float* __restrict__ dws,
+                                                          float* __restrict__ loss, float* __restrict__ dw,
+                                                          float* __restrict__ db, int B, int rows, int K,
+                                                          float lscale) {
+  __shared__ float red[4];
+  if (blockIdx.x == 0) {
+    if (K >= 4 && K <= 1024 && B <= 64) {
+      // softmax_xent_kernel modes 1 / 2: slot n mod 32 adds its rows in increasing n, the slots are added in order
+      if (threadIdx.x == 0) {
+        float t = 0.f;
+        for (int s = 0; s < 32; ++s) {
+          float sl = 0.f;
+          if (s < B) sl += loss[1 + s];
+          if (s + 32 < B) sl += loss[1 + s + 32];
+          t += sl;
+        }
+        loss[0] = t * lscale;
+      }
+    } else {
+      const float t = clip_block_sum(loss + 1, B, red);
+      if (threadIdx.x == 0) loss[0] = t * lscale;
+    }
+    if (dws) {
+      const float s = clip_block_sum(dws, rows, red);
+      if (threadIdx.x == 0) db[0] = s;
+    }
+    return;
+  }
+  const int k = (blockIdx.x - 1) * 256 + threadIdx.x;
+  if (k >= K) return;
+  float acc = 0.f;
+  int r = 0;
+  for (; r + 8 <= rows; r += 8) {   // eight loads in flight, added in row order
+    float xv[8], dv[8];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) { xv[u] = x[(size_t)(r + u) * K + k]; dv[u] = dws[r + u]; }
+#pragma unroll
+    for (int u = 0; u < 8; ++u) acc = fmaf(dv[u], xv[u], acc);
+  }
+  for (; r < rows; ++r) acc = fmaf(dws[r], x[(size_t)r * K + k], acc);
+  dw[k] = acc;
+}
+
+// d [B*F] (temporal attention) | gradient rows [B, K] (K > CLIP_LDS_K), in floats
+static size_t clip_ws_floats(int B, int F, int K, bool temporal, size_t* off_g) {
+  const size_t nd = temporal ? align_up((size_t)B * F, 4) : 0;
+  if (off_g) *off_g = nd;
+  return nd + (K > CLIP_LDS_K ? (size_t)B * K : 0);
+}
+
+}  // namespace apa
+
+using namespace apa;
+
+extern "C" size_t apa_clip_xent_workspace_bytes(int B, int F, int K) {
+  if (B <= 0 || F <= 0 || K <= 0 || (int64_t)B * F > INT32_MAX) return 0;
+  const size_t n = clip_ws_floats(B, F, K, true, nullptr) * sizeof(float);
+  return n < 16 ? 16 : n;
+}
+
+extern "C" int apa_clip_xent_fwd_bwd(const float* logits, const int64_t* labels, const float* w, const float* b,
+                                     float* pooled, float* tatt, float* loss, float* G, float* dw, float* db,
+                                     void* ws, size_t ws_bytes, int B, int F, int K, float wt, float grad_scale,
+                                     void* stream) {
+  if (B <= 0 || F <= 0 || K <= 0 || (int64_t)B * F > INT32_MAX) {
+    set_error("apa_clip_xent_fwd_bwd: non-positive size or B*F past 2^31 (B=%d F=%d K=%d)", B, F, K);
+    return APA_ERR_INVALID_ARG;
+  }
+  if (!logits || !labels || !pooled || !loss || !G || (w && (!b || !tatt || !dw || !db))) {
+    set_error("apa_clip_xent_fwd_bwd: null pointer (temporal attention needs b, tatt, dw and db)");
+    return APA_ERR_INVALID_ARG;
+  }
+  const bool temporal = w != nullptr;
+  size_t off_g = 0;
+  const size_t need = clip_ws_floats(B, F, K, temporal, &off_g) * sizeof(float);
+  if (need && (!ws || ws_bytes < need || (reinterpret_cast<uintptr_t>(ws) & 3))) {
+    set_error("apa_clip_xent_fwd_bwd: workspace too small or misaligned (%zu < %zu)", ws_bytes, need);
+    return APA_ERR_WORKSPACE;
+  }
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  float* dws = temporal ? static_cast<float*>(ws) : nullptr;
+  float* gws = K > CLIP_LDS_K ? static_cast<float*>(ws) + off_g : nullptr;
+  const int row_floats = K > CLIP_LDS_K ? 0 : (K + 3) / 4 * 4;
+  const size_t shm = (size_t)(2 * row_floats + CLIP_LDS_F + 4) * sizeof(float);
+  // the same two factors as apa_softmax_xent_fwd_bwd, over the B clips
+  const float lscale = wt / (float)B;
+  const float gscale = wt * grad_scale / (float)B;
+  if (temporal)
+    hipLaunchKernelGGL(clip_xent_kernel<true>, dim3(B), dim3(256), shm, st, logits, labels, w, b, pooled, tatt, loss,
+                       G, dws, gws, F, K, row_floats, gscale);
+  else
+    hipLaunchKernelGGL(clip_xent_kernel<false>, dim3(B), dim3(256), shm, st, logits, labels, w, b, pooled, tatt,
+                       loss, G, dws, gws, F, K, row_floats, gscale);
+  APA_LAUNCH_CHECK("clip_xent_kernel");
+  const int nb = 1 + (temporal ? (K + 255) / 256 : 0);
+  hipLaunchKernelGGL(clip_finish_kernel, dim3(nb), dim3(256), 0, st, logits, dws, loss, dw, db, B, B * F, K, lscale);
+  APA_LAUNCH_CHECK("clip_finish_kernel");
+  return APA_OK;
+}

@@ -81,6 +81,15 @@ _SIGNATURES = {
                                       c_void_p, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
     'apa_frame_pool_fwd': (c_int, [c_void_p] * 5 + [c_int] * 3 + [c_void_p]),
     'apa_frame_pool_bwd': (c_int, [c_void_p] * 8 + [c_int] * 3 + [c_void_p]),
+    'apa_clip_xent_workspace_bytes': (c_size_t, [c_int] * 3),
+    'apa_clip_xent_fwd_bwd': (c_int, [c_void_p] * 11 + [c_size_t] + [c_int] * 3 + [c_float, c_float, c_void_p]),
+    # the clip forms take a `const apa_clip_pool*` first
+    'apa_clip_step_workspace_bytes': (c_size_t, [c_int] * 7 + [c_uint]),
+    'apa_attn_head_train_step_clips': (c_int, [c_void_p] * 9 + [c_float, c_float] + [c_void_p] * 13 +
+                                       [c_size_t] + [c_int] * 6 + [c_uint, c_float, c_uint64, c_uint64, c_int,
+                                                                   c_void_p]),
+    'apa_pose_attn_train_step_clips': (c_int, [c_void_p, c_void_p] + [c_int] * 6 + [c_uint, c_float, ctypes.c_uint64,
+                                                                                    ctypes.c_uint64, c_int, c_void_p]),
     'apa_attn_head_train_step': (c_int, [c_void_p] * 7 + [c_float, c_float] + [c_void_p] * 13 +
                                  [c_size_t] + [c_int] * 6 + [c_uint, c_float, c_uint64, c_uint64, c_int,
                                                              c_void_p]),
@@ -939,6 +948,80 @@ def frame_pool_bwd(logits, frames_per_video, w, tatt, dpooled):
     return dlogits, dw, db
 
 
+class ApaClipPool(ctypes.Structure):
+    """`apa_clip_pool` of include/apa.h: the frame pooling / temporal attention between the head and the action loss
+    of a clip batch (nets_factory.py:354-374)."""
+    _fields_ = [('frames', c_int), ('w', c_void_p), ('b', c_void_p), ('pooled', c_void_p), ('tatt', c_void_p),
+                ('dw', c_void_p), ('db', c_void_p)]
+
+
+def clip_xent_workspace_bytes(B, F, K) -> int:
+    return int(load_library().apa_clip_xent_workspace_bytes(B, F, K))
+
+
+def clip_xent_fwd_bwd(logits, labels, frames_per_video, w=None, b=None, *, wt=1.0, grad_scale=1.0, workspace=None):
+    """(pooled [B,K], tatt [B*F] or None, loss [1+B], G [B*F,K], dw [K] or None, db [1] or None): frame pooling (with
+    the temporal attention w [K], b [1] when given), softmax cross-entropy on the pooled logits and the gradient at the
+    frame logits, two launches (include/apa.h: apa_clip_xent_fwd_bwd).  logits f32 [B*F,K], labels int64 [B]."""
+    lib = load_library()
+    BF, K = logits.shape
+    F = int(frames_per_video)
+    if F <= 0 or BF % F:
+        raise ApaError('clip_xent_fwd_bwd: {} frame rows are not a whole number of clips of {} frames'.format(BF, F))
+    B = BF // F
+    dev, f32 = logits.device, torch.float32
+    att = w is not None
+    pooled = torch.empty((B, K), dtype=f32, device=dev)
+    tatt = torch.empty((BF,), dtype=f32, device=dev) if att else None
+    loss = torch.empty((1 + B,), dtype=f32, device=dev)
+    G = torch.empty((BF, K), dtype=f32, device=dev)
+    dw = torch.empty((K,), dtype=f32, device=dev) if att else None
+    db = torch.empty((1,), dtype=f32, device=dev) if att else None
+    need = int(lib.apa_clip_xent_workspace_bytes(B, F, K))
+    if workspace is None or workspace.numel() < need:
+        workspace = torch.empty((max(need, 16),), dtype=torch.uint8, device=dev)
+    rc = lib.apa_clip_xent_fwd_bwd(
+        _dev_ptr(logits, 'logits', f32), _dev_ptr(labels, 'labels', torch.int64), _dev_ptr(w, 'w', f32),
+        _dev_ptr(b, 'b', f32), pooled.data_ptr(), _dev_ptr(tatt, 'tatt'), loss.data_ptr(), G.data_ptr(),
+        _dev_ptr(dw, 'dw'), _dev_ptr(db, 'db'), workspace.data_ptr(), workspace.numel(), B, F, K, float(wt),
+        float(grad_scale), _stream_ptr())
+    _check(rc, 'apa_clip_xent_fwd_bwd')
+    return pooled, tatt, loss, G, dw, db
+
+
+def _bind_clip_pool(who, N, K, frames, temporal, temporal_grads, dev, share_with=None):
+    """-> (ApaClipPool, pooled, tatt, keep-alive tuple) for the clip form of a bound step: N = B * frames frame maps,
+    `temporal = (w [K], b [1])` the TemporalAttention conv or None, `temporal_grads = (dw [K], db [1])` where its
+    gradients go (allocated when not given)."""
+    F = int(frames)
+    if F <= 0 or N % F:
+        raise ApaError('{}: N = {} frame maps are not a whole number of clips of {} frames'.format(who, N, F))
+    B, f32 = N // F, torch.float32
+    clip = ApaClipPool()
+    clip.frames = F
+    if share_with is not None:
+        pooled, tatt = share_with.pooled, share_with.tatt
+    else:
+        pooled = torch.empty((B, K), dtype=f32, device=dev)
+        tatt = torch.empty((N,), dtype=f32, device=dev) if temporal is not None else None
+    clip.pooled = pooled.data_ptr()
+    keep = ()
+    if temporal is not None:
+        w, b = temporal
+        if w.numel() != K or b.numel() != 1:
+            raise ApaError('{}: temporal = (w [K], b [1]) expected'.format(who))
+        if temporal_grads is None:
+            temporal_grads = (torch.empty((K,), dtype=f32, device=dev), torch.empty((1,), dtype=f32, device=dev))
+        dw, db = temporal_grads
+        if dw.numel() != K or db.numel() != 1:
+            raise ApaError('{}: temporal_grads = (dw [K], db [1]) expected'.format(who))
+        clip.w, clip.b = _dev_ptr(w, 'temporal w', f32), _dev_ptr(b, 'temporal b', f32)
+        clip.tatt = tatt.data_ptr()
+        clip.dw, clip.db = _dev_ptr(dw, 'temporal dw', f32), _dev_ptr(db, 'temporal db', f32)
+        keep = (temporal, temporal_grads)
+    return clip, pooled, tatt, keep
+
+
 class HeadTrainStep:
     """apa_attn_head_train_step bound to caller-owned buffers: forward, softmax cross-entropy and
     backward of the head as ONE foreign call per step (the reference runs the same sequence inside
@@ -954,8 +1037,13 @@ class HeadTrainStep:
 
     def __init__(self, X, Xatt, Wa, ba, Wt, bt, labels, grads, *, flags=0, keep_prob=1.0, seed=0,
                  offset=0, loss_wt=1.0, grad_scale=1.0, workspace=None, hooks=None, dxatt_rank1=False,
-                 weight_images=False, share_with=None):
-        """`weight_images=True` (per-class maps, M == K): the padded / concatenated operand images of the weights
+                 weight_images=False, share_with=None, frames=1, temporal=None, temporal_grads=None):
+        """`frames` / `temporal` / `temporal_grads`: a batch of CLIPS (apa_attn_head_train_step_clips): X holds the
+        N = B * frames folded frames, `labels` is [B], `temporal = (w [K], b [1])` the TemporalAttention conv (None:
+        plain mean over the frames) and `temporal_grads = (dw [K], db [1])` its gradient buffers.  The step then also
+        exposes `pooled [B,K]` (the clip logits) and `tatt [N]`; `logits` / `G` are the frame logits and their
+        gradient, `loss` is [1+B].  With the defaults nothing changes.
+        `weight_images=True` (per-class maps, M == K): the padded / concatenated operand images of the weights
         are built ONCE in this step's workspace (`self.weight_image_maps` describes them) and every run() passes
         APA_FLAG_WEIGHT_IMAGES: the caller keeps them current -- `BoundMomentumSGD(..., images=...)` /
         `deploy.MomentumSGD.attach_weight_images(step, ...)` in the optimiser's own launch, or
@@ -977,9 +1065,19 @@ class HeadTrainStep:
             flags |= APA_FLAG_DXATT_RANK1
         dX, dXatt, dWa, dba, dWt, dbt = grads
         self.hooks = hooks            # default apa_hooks of run(); kept alive here
+        clips = int(frames) != 1 or temporal is not None
+        n_loss = N
+        self._pre = ()
+        if clips:
+            self._clip, self.pooled, self.tatt, self._clip_keep = _bind_clip_pool(
+                'HeadTrainStep', N, K, frames, temporal, temporal_grads, dev, share_with)
+            self._pre = (ctypes.addressof(self._clip),)
+            n_loss = N // int(frames)
+            if labels.numel() != n_loss:
+                raise ApaError('HeadTrainStep: one label per clip expected ({} clips)'.format(n_loss))
         if share_with is not None:
             o = share_with
-            if tuple(o.logits.shape) != (N, K) or tuple(o.att.shape) != (N, P, M):
+            if tuple(o.logits.shape) != (N, K) or tuple(o.att.shape) != (N, P, M) or o.loss.numel() != 1 + n_loss:
                 raise ApaError('HeadTrainStep: share_with needs a step of the same shapes')
             self.logits, self.att, self.zsave, self.abar, self.loss, self.G = o.logits, o.att, o.zsave, o.abar, o.loss, o.G
             workspace = o.workspace
@@ -988,9 +1086,12 @@ class HeadTrainStep:
             self.att = torch.empty((N, P, M), dtype=torch.float32, device=dev)
             self.zsave = torch.empty((N, C) if M == 1 else (N, P, K), dtype=torch.float32, device=dev)
             self.abar = torch.empty((N,), dtype=torch.float32, device=dev) if M == 1 else None
-            self.loss = torch.empty((1 + N,), dtype=torch.float32, device=dev)
+            self.loss = torch.empty((1 + n_loss,), dtype=torch.float32, device=dev)
             self.G = torch.empty((N, K), dtype=torch.float32, device=dev)
-        need = int(self.lib.apa_attn_pool_workspace_bytes(N, P, C, Ca, K, M, flags))
+        if clips:       # the pooling workspace followed by the clip loss's scratch
+            need = int(self.lib.apa_clip_step_workspace_bytes(N, int(frames), P, C, Ca, K, M, flags))
+        else:
+            need = int(self.lib.apa_attn_pool_workspace_bytes(N, P, C, Ca, K, M, flags))
         if workspace is None or workspace.numel() < need:
             workspace = torch.empty((max(need, 16),), dtype=torch.uint8, device=dev)
         self.workspace = workspace
@@ -1016,7 +1117,7 @@ class HeadTrainStep:
             _dev_ptr(dba, 'dba', torch.float32), _dev_ptr(dWt, 'dWt', torch.float32),
             _dev_ptr(dbt, 'dbt', torch.float32), workspace.data_ptr(), workspace.numel(), N, P, C, Ca, K, M,
             flags, float(keep_prob), int(seed), off, _feat_dtype(X)]
-        self._fn = self.lib.apa_attn_head_train_step_ex
+        self._fn = self.lib.apa_attn_head_train_step_clips if clips else self.lib.apa_attn_head_train_step_ex
 
     def refresh_weight_images(self) -> None:
         """Rebuild the operand images from the current weights (after load_state_dict, or an optimiser that does not
@@ -1052,9 +1153,9 @@ class HeadTrainStep:
         """Enqueue one step on `stream` (a raw hipStream_t) or torch's current stream; `hooks`
         (an ApaHooks) overrides the instance's for this call."""
         h = self.hooks if hooks is None else hooks
-        rc = self._fn(_hooks_ptr(h), *self._args, _stream_ptr() if stream is None else stream)
+        rc = self._fn(*self._pre, _hooks_ptr(h), *self._args, _stream_ptr() if stream is None else stream)
         if rc != 0:
-            _check(rc, 'apa_attn_head_train_step')
+            _check(rc, 'apa_attn_head_train_step_clips' if self._pre else 'apa_attn_head_train_step')
 
 
 class ApaPoseAttnStepIO(ctypes.Structure):
@@ -1080,8 +1181,10 @@ class PoseAttnTrainStep:
 
     def __init__(self, X, params, labels, pose_labels, pose_valid, grads, *, flags=0, keep_prob=1.0, seed=0,
                  offset=0, action_wt=1.0, pose_wt=1.0, grad_scale=1.0, w1_bf16=None, share_with=None,
-                 w2t_bf16=None):
-        """`share_with`: another PoseAttnTrainStep of the same shapes whose activation / loss buffers and workspaces
+                 w2t_bf16=None, frames=1, temporal=None, temporal_grads=None):
+        """`frames` / `temporal` / `temporal_grads`: a batch of clips (apa_pose_attn_train_step_clips), as for
+        HeadTrainStep: `labels` [B], `loss_action` [1+B], `pooled` [B,K], `tatt` [N]; pose labels stay per frame.
+        `share_with`: another PoseAttnTrainStep of the same shapes whose activation / loss buffers and workspaces
         this step is bound to as well (see HeadTrainStep).  `w2t_bf16`: optional bf16 [16, Cp + 16] image of W2^T (rows
         J.. and the pad columns zero) the caller keeps current -- `pose_w2t_image(W2)` builds it, `pose_w2t_image_map(image, W2)` describes
         it for `BoundMomentumSGD(..., images=...)`."""
@@ -1097,17 +1200,25 @@ class PoseAttnTrainStep:
         if pose_valid.dtype == torch.bool:
             pose_valid = pose_valid.to(torch.uint8)
         new = lambda *shape, dt=f32: torch.empty(shape, dtype=dt, device=dev)
+        clips = int(frames) != 1 or temporal is not None
+        n_loss = N
+        self._pre = ()
+        if clips:
+            self._clip, self.pooled, self.tatt, self._clip_keep = _bind_clip_pool(
+                'PoseAttnTrainStep', N, K, frames, temporal, temporal_grads, dev, share_with)
+            self._pre = (ctypes.addressof(self._clip),)
+            n_loss = N // int(frames)
         _shared = ('Ppre', 'Pl', 'att', 'logits', 'zsave', 'abar', 'loss_action', 'loss_pose', 'G', 'dPl', 'dZ')
         if share_with is not None:
             if tuple(share_with.Ppre.shape) != (N, P, Cp) or share_with.Ppre.dtype != X.dtype or \
-                    tuple(share_with.logits.shape) != (N, K):
+                    tuple(share_with.logits.shape) != (N, K) or share_with.loss_action.numel() != 1 + n_loss:
                 raise ApaError('PoseAttnTrainStep: share_with needs a step of the same shapes')
             for name in _shared:
                 setattr(self, name, getattr(share_with, name))
         else:
             self.Ppre, self.Pl, self.att = new(N, P, Cp, dt=X.dtype), new(N, P, J), new(N, P, 1)
             self.logits, self.zsave, self.abar = new(N, K), new(N, C), new(N)
-            self.loss_action, self.loss_pose = new(1 + N), new(1)
+            self.loss_action, self.loss_pose = new(1 + n_loss), new(1)
             self.G, self.dPl, self.dZ = new(N, K), new(N, P, J), new(N * P)
         dt = _feat_dtype(X)
         seed, off, flags = _rng_key(seed, offset, flags)
@@ -1116,8 +1227,11 @@ class PoseAttnTrainStep:
         if share_with is not None:
             self.ws_pool, self.ws_pose = share_with.ws_pool, share_with.ws_pose
         else:
-            self.ws_pool = torch.empty((max(int(self.lib.apa_attn_pool_workspace_bytes(N, P, C, Cp, K, 1, flags)), 16),),
-                                       dtype=torch.uint8, device=dev)
+            if clips:   # the pooling workspace followed by the clip loss's scratch
+                pool_bytes = int(self.lib.apa_clip_step_workspace_bytes(N, int(frames), P, C, Cp, K, 1, flags))
+            else:
+                pool_bytes = int(self.lib.apa_attn_pool_workspace_bytes(N, P, C, Cp, K, 1, flags))
+            self.ws_pool = torch.empty((max(pool_bytes, 16),), dtype=torch.uint8, device=dev)
             self.ws_pose = torch.empty((max(int(self.lib.apa_pose_head_workspace_bytes(N, P, C, Cp, J, dt)), 16),),
                                        dtype=torch.uint8, device=dev)
         self._keep = (X, params, labels, pose_labels, pose_valid, grads, offset, w1_bf16, w2t_bf16)
@@ -1138,8 +1252,9 @@ class PoseAttnTrainStep:
             raise ApaError('PoseAttnTrainStep: w1_bf16 must have W1\'s element count')
         io.labels = _dev_ptr(labels, 'labels', torch.int64)
         io.pose_valid = _dev_ptr(pose_valid, 'pose_valid', torch.uint8)
-        if pose_labels.numel() != N * P * J or pose_valid.numel() != N * J or labels.numel() != N:
-            raise ApaError('PoseAttnTrainStep: labels [N], pose_labels [N,P,J], pose_valid [N,J] expected')
+        if pose_labels.numel() != N * P * J or pose_valid.numel() != N * J or labels.numel() != n_loss:
+            raise ApaError('PoseAttnTrainStep: labels [N] (one per clip for a clip batch), pose_labels [N,P,J], '
+                           'pose_valid [N,J] expected')
         io.action_wt, io.pose_wt, io.grad_scale = float(action_wt), float(pose_wt), float(grad_scale)
         io.dX = _dev_ptr(dX, 'dX', X.dtype)
         for name in ('Ppre', 'Pl', 'att', 'logits', 'zsave', 'abar', 'loss_action', 'loss_pose', 'G', 'dPl', 'dZ'):
@@ -1148,6 +1263,7 @@ class PoseAttnTrainStep:
         io.ws_pose, io.ws_pose_bytes = self.ws_pose.data_ptr(), self.ws_pose.numel()
         self._io = io
         self._args = [ctypes.addressof(io), N, P, C, Cp, J, K, flags, float(keep_prob), int(seed), off, dt]
+        self._fn = self.lib.apa_pose_attn_train_step_clips if clips else self.lib.apa_pose_attn_train_step
 
     def rebind(self, X=None, labels=None, pose_labels=None, pose_valid=None, offset=None) -> None:
         """Point the bound step at other inputs of the same shapes / dtypes and / or another dropout offset (int)
@@ -1180,9 +1296,9 @@ class PoseAttnTrainStep:
         self._keep = tuple(keep)
 
     def run(self, stream: Optional[int] = None) -> None:
-        rc = self.lib.apa_pose_attn_train_step(*self._args, _stream_ptr() if stream is None else stream)
+        rc = self._fn(*self._pre, *self._args, _stream_ptr() if stream is None else stream)
         if rc != 0:
-            _check(rc, 'apa_pose_attn_train_step')
+            _check(rc, 'apa_pose_attn_train_step_clips' if self._pre else 'apa_pose_attn_train_step')
 
 
 class HeadEvalStep:

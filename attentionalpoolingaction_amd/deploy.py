@@ -865,6 +865,16 @@ class FusedHeadStep:
       `total.backward()` (which applies the upstream coefficient to the bucket) and before any ITER_SIZE
       accumulation or all-reduce of the bucket -- the reference clips each clone's gradient of each micro-step.
 
+    * video input `[B,F,H,W,C]` (nets_factory.py:121-125, :354-374): the frames are folded into the batch, the head
+      runs per frame and the action loss is taken on the POOLED logits, all inside the one call
+      (`apa_attn_head_train_step_clips` / `apa_pose_attn_train_step_clips`: frame pooling, the TemporalAttention conv
+      when NET.USE_TEMPORAL_ATT built one, the clip cross-entropy and the gradient at the frame logits in two
+      launches).  `labels_action` is [B]; `labels_pose` / `pose_valid` arrive folded or as [B,F,...]; the temporal
+      bias is initialised to 1/F at the first clip, as `network_fn` does.  The conv's two parameters are in `params`,
+      the bucket and `_written` (the weights regularised, the bias not), so `make_optimizer`, `clip()` and the staleness
+      guard cover them.  End points of a clip step: 'Logits' (pooled [B,K]), 'logits_beforePool' [B*F,K],
+      'TemporalAttention' [B,F,1,1], and the per-frame ones below.  One frame per clip, or 4-D input, takes the flat
+      entry points (no pooling, as in the reference).
     * `total` = sum of the clone's tf.losses entries (each scaled by `loss_scale` = 1 / num_clones,
       model_deploy.py:223-225); the L2 regulariser is the optimiser's (`weight_decay * w` folded into its launch).
       end_points: 'Logits', 'PosePrelogitsBasedAttention', 'PoseLogits' (cfg 003), 'Losses' (the individual values
@@ -902,12 +912,19 @@ class FusedHeadStep:
         self.pose_form = not head.single_layer
         names = ['pose_w1', 'pose_b1', 'pose_w2', 'pose_b2', 'att_weights', 'att_biases', 'td_weights', 'td_biases']
         self.params = {n: getattr(head, n) for n in names}
-        self.bucket = GradientBucket.for_parameters(self.params.items())
         # cfg 002 forms: the PoseLogits convs are pruned from the data path -- no gradient, but their weights are
         # regularised and decay (the optimiser's L2 term on a zero gradient), as in the reference (tf.gradients
         # reaches them through REGULARIZATION_LOSSES only)
         self._written = names if self.pose_form else names[4:]
         reg = {id(w) for w in head.regularized_weights()}
+        self.temporal = getattr(network_fn, 'temporal', None)
+        if self.temporal is not None:       # 'TemporalAttention/Conv/{weights,biases}' (nets_factory.py:362-370)
+            self.params['temporal_weights'] = self.temporal['weights']
+            self.params['temporal_biases'] = self.temporal['biases']
+            names = names + ['temporal_weights', 'temporal_biases']
+            self._written = self._written + ['temporal_weights', 'temporal_biases']
+            reg.add(id(self.temporal['weights']))                # regularised like every conv weight; the bias is not
+        self.bucket = GradientBucket.for_parameters(self.params.items())
         self.regularized = [n for n in names if id(self.params[n]) in reg]
         self._steps = {}                 # key (shape, dtype, preact) -> bound one-call step, most recent last
         self._step_obj = None
@@ -931,8 +948,6 @@ class FusedHeadStep:
             return 'rank > 1, ..._WITH_POSE_FEAT and the TopDownAttention dump run through the per-op module'
         if tr.LOSS_FN_ACTION != 'softmax-xentropy':
             return 'LOSS_FN_ACTION %r (the one-call steps take the softmax cross-entropy)' % tr.LOSS_FN_ACTION
-        if network_fn is not None and network_fn.temporal is not None:
-            return 'temporal attention / frame pooling sit between the head and the loss'
         if head.single_layer:
             if tr.LOSS_FN_POSE and head.with_pose_logits:
                 return 'a pose loss on a head whose attention does not come from the pose head'
@@ -998,12 +1013,18 @@ class FusedHeadStep:
 
     _IMAGE_ROLES = {'Wa': 'att_weights', 'ba': 'att_biases', 'Wt': 'td_weights', 'bt': 'td_biases'}
 
-    def _bind(self, X, labels_action, labels_pose, pose_valid):
+    def _bind(self, X, labels_action, labels_pose, pose_valid, frames=1):
         from .custom_ops import custom_ops_factory as cof
         head, tr, v = self.head, self.cfg.TRAIN, self.bucket.views
         flags = cof.attn_flags(head.softmax_att, head.relu_att, True, self._preact)
         dX = torch.empty_like(X)
         p = {n: t.data for n, t in self.params.items()}
+        clip = {}
+        if frames > 1:      # a clip batch: frame pooling (and the temporal conv) inside the one call
+            clip = dict(frames=frames)
+            if self.temporal is not None:
+                clip.update(temporal=(p['temporal_weights'], p['temporal_biases']),
+                            temporal_grads=(v['temporal_weights'], v['temporal_biases']))
         if self.pose_form:
             shadow = self.w1_shadow if X.dtype == torch.bfloat16 else None
             st = cof.PoseAttnTrainStep(
@@ -1013,24 +1034,24 @@ class FusedHeadStep:
                  v['td_weights'], v['td_biases']), flags=flags, keep_prob=head.keep_prob, seed=head.seed,
                 offset=head._step, action_wt=float(tr.LOSS_FN_ACTION_WT), pose_wt=float(tr.LOSS_FN_POSE_WT),
                 grad_scale=self.loss_scale, w1_bf16=shadow,
-                w2t_bf16=self.w2t_image if X.dtype == torch.bfloat16 else None)
+                w2t_bf16=self.w2t_image if X.dtype == torch.bfloat16 else None, **clip)
         else:
             st = cof.HeadTrainStep(
                 X, X, p['att_weights'], p['att_biases'], p['td_weights'], p['td_biases'], labels_action,
                 (dX, None, v['att_weights'], v['att_biases'], v['td_weights'], v['td_biases']), flags=flags,
                 keep_prob=head.keep_prob, seed=head.seed, offset=head._step, loss_wt=float(tr.LOSS_FN_ACTION_WT),
                 grad_scale=self.loss_scale, hooks=head.hooks,
-                weight_images=bool(head.per_class and self._optimizer is not None))
+                weight_images=bool(head.per_class and self._optimizer is not None), **clip)
         st._dX_buf = dX
         return st
 
-    def _select(self, key, X, labels_action, labels_pose, pose_valid):
+    def _select(self, key, X, labels_action, labels_pose, pose_valid, frames=1):
         """make the bound step of `key` the current one: at most one step has its operand images attached"""
         prev = self._step_obj
         st = self._steps.pop(key, None)
         cached = st is not None
         if st is None:
-            st = self._bind(X, labels_action, labels_pose, pose_valid)
+            st = self._bind(X, labels_action, labels_pose, pose_valid, frames)
         self._steps[key] = st                            # most recent last
         while len(self._steps) > self.max_bound_steps:
             old_key = next(iter(self._steps))
@@ -1057,11 +1078,20 @@ class FusedHeadStep:
             if pose_valid.dtype == torch.bool:
                 pose_valid = pose_valid.to(torch.uint8)
             pose_valid = pose_valid.contiguous()
+        frames = self._frames
+        if self.temporal is not None:
+            if frames > 1 and not self.temporal._bias_initialised:     # 1 / F at the first clip, as network_fn does
+                with torch.no_grad():
+                    self.temporal['biases'].fill_(1.0 / frames)
+                self.temporal._bias_initialised = True
+            if frames == 1:                                  # no pooling (nets_factory.py:354): the conv gets no gradient
+                self.bucket.views['temporal_weights'].zero_()
+                self.bucket.views['temporal_biases'].zero_()
         if self._optimizer is not None:
             self._optimizer.check_fresh()                # weights written behind the optimiser's back?
         # a bound step reads the weights through the pointers it was bound to: a new storage binds a new step
-        key = (tuple(X.shape), X.dtype, self._preact, tuple(p.data_ptr() for p in self.params.values()))
-        st, cached = self._select(key, X, labels_action, labels_pose, pose_valid)
+        key = (tuple(X.shape), frames, X.dtype, self._preact, tuple(p.data_ptr() for p in self.params.values()))
+        st, cached = self._select(key, X, labels_action, labels_pose, pose_valid, frames)
         if cached and self.pose_form:
             st.rebind(X=X, labels=labels_action, pose_labels=labels_pose, pose_valid=pose_valid, offset=head._step)
         elif cached:
@@ -1083,9 +1113,13 @@ class FusedHeadStep:
         return total
 
     def __call__(self, images, labels_action, labels_pose=None, pose_valid=None):
+        self._frames = 1
+        if images.dim() == 5:                                   # nets_factory.py:121-125: frames fold into the batch
+            self._frames = int(images.shape[1])
+            images = images.reshape(-1, *images.shape[2:])
         last_conv, self._preact = self.network_fn.features(images)
         if last_conv.dim() != 4:
-            raise ValueError('FusedHeadStep: [N,H,W,C] feature maps (video input takes the module path)')
+            raise ValueError('FusedHeadStep: [N,H,W,C] (or [B,F,H,W,C]) feature maps expected')
         if self._preact and not self.head.can_fuse_input_relu(last_conv.dtype):
             last_conv, self._preact = torch.relu(last_conv), False
         if self.pose_form and (labels_pose is None or pose_valid is None):
@@ -1099,6 +1133,11 @@ class FusedHeadStep:
               'Losses': [l.detach() for l in self._losses]}
         if self.pose_form:
             ep['PoseLogits'] = st.Pl.view(n, h, w, -1)
+        if self._frames > 1:                                    # nets_factory.py:354-374
+            ep['logits_beforePool'] = st.logits
+            ep['Logits'] = st.pooled
+            if st.tatt is not None:
+                ep['TemporalAttention'] = st.tatt.view(-1, self._frames, 1, 1)
         return total, ep
 
 

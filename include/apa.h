@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define APA_VERSION 303 /* major*10000 + minor*100 + patch */
+#define APA_VERSION 304 /* major*10000 + minor*100 + patch */
 
 typedef enum apa_status {
   APA_OK = 0,
@@ -515,6 +515,27 @@ int apa_frame_pool_bwd(const float* logits, const float* w, const float* tatt, c
                        float* dlogits, float* dw, float* db, float* dlda_ws, int B, int F, int K,
                        void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * The action loss of a video clip: frame pooling / temporal attention (nets_factory.py:354-374), the softmax
+ * cross-entropy on the POOLED logits (src/loss.py:74-80) and the backward of both down to the frame logits (TF
+ * autodiff in the reference), value + gradient in two launches.
+ *   a[r]        = logits[r,:] . w + b[0]   (w == NULL: 1)                       -> tatt [B*F]
+ *   pooled[b,k] = (1/F) sum_f logits[b*F+f, k] a[b*F+f]                         -> pooled [B,K]
+ *   loss[1+b]   = -log softmax(pooled[b])[labels[b]];   loss[0] = wt/B sum_b loss[1+b]
+ *   G[r,k]      = (1/F) g[b,k] a[r] + d[r] w[k],  g = wt grad_scale/B (softmax(pooled) - onehot),
+ *                 d[r] = (1/F) sum_k g[b,k] logits[r,k]                         -> G [B*F,K]
+ *   dw[k]       = sum_r d[r] logits[r,k];  db[0] = sum_r d[r]                   (temporal attention only)
+ * logits f32 [B*F,K] (F consecutive rows per clip); labels int64 [B]; loss f32 [1+B]; w [K], b [1] both NULL for plain
+ * averaging (then tatt, dw, db may be NULL and the d / w terms vanish).  Any B, F, K >= 1 with B*F < 2^31.
+ * ws: apa_clip_xent_workspace_bytes(B, F, K) bytes of scratch, 4-byte aligned (d [B*F]; K > 4096: the gradient rows).
+ * No atomics, every sum in a fixed order: identical calls give bit-identical results; with F == 1 and w == NULL loss and
+ * G are bit-identical to apa_softmax_xent_fwd_bwd(logits, labels, ..., N = B).
+ * Null required pointers, non-positive sizes, B*F overflow: APA_ERR_INVALID_ARG before anything touches the GPU. */
+size_t apa_clip_xent_workspace_bytes(int B, int F, int K);
+int apa_clip_xent_fwd_bwd(const float* logits, const int64_t* labels, const float* w, const float* b, float* pooled,
+                          float* tatt, float* loss, float* G, float* dw, float* db, void* ws, size_t ws_bytes, int B,
+                          int F, int K, float wt, float grad_scale, void* stream);
+
 /* Backward of the global average pool of the attention-free head (cfg 001, resnet_v1.py:206-208
  * `tf.reduce_mean(net, [1, 2])`):  dX[n,p,c] = dz[n,c] / P.   dz f32 [N,C]; dX dtype [N,P,C].
  * (The forward pool is apa_attn_pool_fwd with a constant attention map: its zsave output.) */
@@ -588,6 +609,45 @@ int apa_attn_head_train_step_ex(const apa_hooks* hooks, const void* X, const voi
                                 size_t ws_bytes, int N, int P, int C, int Ca, int K, int M,
                                 unsigned flags, float keep_prob, uint64_t seed, uint64_t offset,
                                 int dtype, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * The one-call training steps on a batch of CLIPS: the N = B * frames feature maps are the folded frames of B clips
+ * (nets_factory.py:121-125), the head runs per frame, and the action loss is taken on the pooled logits.  Inside the
+ * call: the forward half of the step WITHOUT its folded per-image cross-entropy, apa_clip_xent_fwd_bwd, then the
+ * backward half reading G from memory (same workspace: APA_FLAG_WS_FROM_FWD).  Bit-identical to calling
+ * apa_attn_pool_fwd, apa_clip_xent_fwd_bwd, apa_attn_pool_bwd back to back with the same arguments (cfg 003: to
+ * apa_pose_head_fwd, apa_pose_l2_loss_fwd_bwd, apa_attn_head_train_step_clips under APA_FLAG_DXATT_RANK1,
+ * apa_pose_head_bwd_rank1ext -- which is what the cfg 003 form runs for every shape: the launches
+ * apa_pose_attn_train_step shares between neighbouring ops on its fast bf16 route sum in other orders, so they are not
+ * used here, and io->W1_bf16 / io->W2T_bf16 are not read).
+ *   labels int64 [B], loss / io->loss_action f32 [1+B]; logits [N,K] holds the FRAME logits
+ *   (end_points['logits_beforePool']); G [N,K] is the gradient at the frame logits.  Pose labels, the pose loss and
+ *   dropout stay per frame, over the flat N.  N % frames != 0, a null clip / pooled pointer, temporal attention
+ *   without b / tatt / dw / db: APA_ERR_INVALID_ARG before anything touches the GPU.
+ *   ws (io->ws_pool for the cfg 003 form): apa_clip_step_workspace_bytes(N, frames, P, C, Ca, K, M, flags) bytes --
+ *   the pooling workspace followed by the clip loss's scratch; less: APA_ERR_WORKSPACE.
+ */
+typedef struct apa_clip_pool {
+  int frames;       /* F = num_frames of the [B,F,H,W,C] input, nets_factory.py:121-125 (the fold) and :356-358    */
+  const float* w;   /* [K]  TemporalAttention/Conv/weights ([1,1,K,1] squeezed), :362-368; NULL: plain mean (:374) */
+  const float* b;   /* [1]  TemporalAttention/Conv/biases (initialised to 1/F, :366-367); NULL with w               */
+  float* pooled;    /* [B,K]   end_points['Logits'], the reduce_mean over the frames (:371-374)                      */
+  float* tatt;      /* [B*F]   end_points['TemporalAttention'] (:369), [B,F,1,1] flattened; NULL with w              */
+  float* dw;        /* [K]     gradient of the temporal conv's weights (tf.gradients); NULL with w                   */
+  float* db;        /* [1]     gradient of its bias; NULL with w                                                      */
+} apa_clip_pool;
+size_t apa_clip_step_workspace_bytes(int N, int frames, int P, int C, int Ca, int K, int M, unsigned flags);
+int apa_attn_head_train_step_clips(const apa_clip_pool* clip, const apa_hooks* hooks, const void* X, const void* Xatt,
+                                   const float* Wa, const float* ba, const float* Wt, const float* bt,
+                                   const int64_t* labels, float loss_wt, float grad_scale, float* logits,
+                                   float* att, float* zsave, float* abar, float* loss, float* G, void* dX,
+                                   void* dXatt, float* dWa, float* dba, float* dWt, float* dbt, void* ws,
+                                   size_t ws_bytes, int N, int P, int C, int Ca, int K, int M,
+                                   unsigned flags, float keep_prob, uint64_t seed, uint64_t offset,
+                                   int dtype, void* stream);
+int apa_pose_attn_train_step_clips(const apa_clip_pool* clip, const apa_pose_attn_step_io* io, int N, int P, int C,
+                                   int Cp, int J, int K, unsigned flags, float keep_prob, uint64_t seed,
+                                   uint64_t offset, int dtype, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * ..._WITH_POSE_FEAT (nets_factory.py:289-295): `last_conv = tf.concat([last_conv, pose_logits], -1)`

@@ -13,6 +13,13 @@ headline stays the cfg 002 training workload); run this file directly for one wo
             pose-head product's epilogue, pose_pre_logits never written) against the sequence cof.pose_head_fwd +
             cof.HeadEvalStep, alternating in one process; prints both medians and HIP-event times per host call.
 
+  video_perclass / video003
+            a batch of CLIPS, 8 x 4 frames x 14x14x2048 bf16, K = 51, temporal attention on, for the per-class (HMDB-51)
+            head and the cfg 003 head: the one-call clip step (apa_*_train_step_clips: frame pooling, temporal attention
+            and the clip loss inside the call) against the module path (network_fn + gen_losses + backward), alternating
+            in one process, medians of five; also the flat one-call step at N = 32 of the same head, whose per-image
+            cross-entropy is folded into its neighbours, and the clip loss's own two launches.
+
 Each builder returns (step_fn, info): `step_fn()` enqueues one step on the current stream; `info`
 carries the workload name and the algorithmic work per image.
 """
@@ -64,7 +71,22 @@ def _rot_note(R, per_set_bytes):
         '; ONE buffer set (features stay in the Infinity Cache between steps)'
 
 
-def build_cfg003(cof, dev, N=32, H=14, K=393, dtype='bf16', rank1=True, one_call=True, rotate=0):
+def _clip_kwargs(dev, K, frames, temporal):
+    """HeadTrainStep / PoseAttnTrainStep keywords of a clip batch (frames > 1): the TemporalAttention conv at its
+    initial values (N(0, 1e-3) weights, bias 1 / F, nets_factory.py:366-368) and its gradient buffers"""
+    if frames <= 1:
+        return {}
+    kw = dict(frames=frames)
+    if temporal:
+        g = torch.Generator().manual_seed(7)
+        kw['temporal'] = ((torch.randn(K, generator=g) * 1e-3).to(dev), torch.full((1,), 1.0 / frames, device=dev))
+        kw['temporal_grads'] = (torch.empty(K, device=dev), torch.empty(1, device=dev))
+    return kw
+
+
+def build_cfg003(cof, dev, N=32, H=14, K=393, dtype='bf16', rank1=True, one_call=True, rotate=0, frames=1,
+                 temporal=False):
+    """frames > 1 (one-call form only): the N maps are the folded frames of N / frames clips"""
     C, Cp, J, P = 2048, 768, 16, H * H
     td = torch.bfloat16 if dtype == 'bf16' else torch.float32
     g = torch.Generator().manual_seed(42)
@@ -75,7 +97,7 @@ def build_cfg003(cof, dev, N=32, H=14, K=393, dtype='bf16', rank1=True, one_call
     W2 = (torch.randn(Cp, J, generator=g) / Cp ** 0.5).to(dev); b2 = torch.zeros(J, device=dev)
     Wa = (torch.randn(Cp, 1, generator=g) / Cp ** 0.5).to(dev); ba = torch.zeros(1, device=dev)
     Wt = (torch.randn(C, K, generator=g) / C ** 0.5).to(dev); bt = torch.zeros(K, device=dev)
-    labels = torch.randint(0, K, (N,), generator=g).to(dev)
+    labels = torch.randint(0, K, (N // frames,), generator=g).to(dev)
     lbl = torch.rand(N, P, J, generator=g).to(dev)
     valid = (torch.rand(N, J, generator=g) > 0.3).to(dev)
     flags = cof.attn_flags(False, False, True)
@@ -99,6 +121,7 @@ def build_cfg003(cof, dev, N=32, H=14, K=393, dtype='bf16', rank1=True, one_call
         w2t_bf16 = cof.pose_w2t_image(W2)      # ... and so is the bf16 image of W2^T the Pl product reads
         new = lambda t: torch.empty_like(t)
         pgrads = (new(W1), new(b1), new(W2), new(b2), new(Wa), new(ba), new(Wt), new(bt))
+        clip = _clip_kwargs(dev, K, frames, temporal)
         sts = []
         for r in range(R):        # one bound step per (X, dX) set; everything else is shared, as in bench.py's headline:
             #                       weights, parameter gradients, activations, workspaces, dropout counter
@@ -106,7 +129,7 @@ def build_cfg003(cof, dev, N=32, H=14, K=393, dtype='bf16', rank1=True, one_call
             sts.append(cof.PoseAttnTrainStep(Xr, (W1, b1, W2, b2, Wa, ba, Wt, bt), labels, lbl, valid,
                                              (dX if r == 0 else new(Xr),) + pgrads,
                                              flags=flags, keep_prob=0.2, seed=42, offset=ctr, w1_bf16=w1_bf16,
-                                             w2t_bf16=w2t_bf16, share_with=sts[0] if sts else None))
+                                             w2t_bf16=w2t_bf16, share_with=sts[0] if sts else None, **clip))
         info = {'workload': 'cfg003 pose-regularised attention head fwd+bwd (pose head 2048->768->16 + M=1 '
                             'pooling + pose L2 + softmax-xent), one host call; per-GPU batch {} x {}x{}x{} {}, K={}, '
                             'dropout keep=0.2'.format(N, H, H, C, dtype, K) + _rot_note(R, per_set),
@@ -164,7 +187,8 @@ def build_posebwd(cof, dev, N=32, H=14, dtype='bf16', accumulate=False):
     return step, info
 
 
-def build_perclass(cof, dev, N=32, H=14, K=51, dtype='bf16', rotate=0, weight_images=True):
+def build_perclass(cof, dev, N=32, H=14, K=51, dtype='bf16', rotate=0, weight_images=True, frames=1, temporal=False):
+    """frames > 1: the N maps are the folded frames of N / frames clips (apa_attn_head_train_step_clips)"""
     C, P = 2048, H * H
     td = torch.bfloat16 if dtype == 'bf16' else torch.float32
     g = torch.Generator().manual_seed(42)
@@ -173,10 +197,11 @@ def build_perclass(cof, dev, N=32, H=14, K=51, dtype='bf16', rotate=0, weight_im
     X = _features(N, P, C, td, dev)
     Wa = (torch.randn(C, K, generator=g) / C ** 0.5).to(dev); ba = torch.zeros(K, device=dev)
     Wt = (torch.randn(C, K, generator=g) / C ** 0.5).to(dev); bt = torch.zeros(K, device=dev)
-    labels = torch.randint(0, K, (N,), generator=g).to(dev)
+    labels = torch.randint(0, K, (N // frames,), generator=g).to(dev)
     flags = cof.attn_flags(False, False, True)
     ctr = torch.zeros(1, dtype=torch.int64, device=dev)
     pg = (torch.empty_like(Wa), torch.empty_like(ba), torch.empty_like(Wt), torch.empty_like(bt))
+    clip = _clip_kwargs(dev, K, frames, temporal)
     sts = []
     for r in range(R):            # one host call per step, one bound step per (X, dX) set
         Xr = X if r == 0 else _features(N, P, C, td, dev, seed=42 + r)
@@ -185,7 +210,7 @@ def build_perclass(cof, dev, N=32, H=14, K=51, dtype='bf16', rotate=0, weight_im
         # in the optimiser's own launch); here the weights do not change between steps
         sts.append(cof.HeadTrainStep(Xr, Xr, Wa, ba, Wt, bt, labels, (torch.empty_like(Xr), None) + pg, flags=flags,
                                      keep_prob=0.2, seed=42, offset=ctr, weight_images=weight_images,
-                                     share_with=sts[0] if sts else None))
+                                     share_with=sts[0] if sts else None, **clip))
     esz = X.element_size()
     info = {'workload': 'per-class bottom-up maps (M=K, HMDB-51 shape when K=51) attention head fwd+bwd; '
                         'per-GPU batch {} x {}x{}x{} {}, K={}, dropout keep=0.2'.format(N, H, H, C, dtype, K) +
@@ -453,6 +478,104 @@ def run_eval003(cof, dev, args):
     return out
 
 
+def build_video(cof, dev, which, B=8, F=4, H=14, K=51, rotate=0):
+    """A clip batch [B,F,H,H,2048] bf16 with temporal attention, `which` in ('perclass', 'cfg003'):
+      'clip_one_call'  the one-call clip step (build_perclass / build_cfg003 with frames=F)
+      'flat_one_call'  the same head's flat one-call step on N = B * F images (cross-entropy folded)
+      'module_path'    network_fn([B,F,H,H,C]) + gen_losses + backward, the only route for a clip before the clip steps
+    as round-robin step functions over rotating X sets, + info + a function timing the clip loss's own call."""
+    from attentionalpoolingaction_amd import config as apa_config, loss as apa_loss, nets_factory
+    N, C, J, P = B * F, 2048, 16, H * H
+    build = build_perclass if which == 'perclass' else build_cfg003
+    clip_step, info = build(cof, dev, N, H, K, 'bf16', rotate=rotate, frames=F, temporal=True)
+    flat_step, _ = build(cof, dev, N, H, K, 'bf16', rotate=rotate)
+    R = info['rotate']
+    apa_config.reset_cfg()
+    pre = 'USE_POSE_PRELOGITS_BASED_ATTENTION'
+    if which == 'perclass':
+        net, train = {pre: True, pre + '_SINGLE_LAYER_ATT': True, pre + '_PER_CLASS': True}, {'LOSS_FN_POSE': ''}
+    else:
+        net, train = {pre: True}, {'LOSS_FN_POSE': 'l2'}
+    cfg = apa_config.cfg_from_dict({'MODEL_NAME': 'resnet_v1_101', 'NET': dict(net, USE_TEMPORAL_ATT=True),
+                                    'TRAIN': dict(train, LOSS_FN_ACTION='softmax-xentropy')})
+    network_fn = nets_factory.get_network_fn('resnet_v1_101', K, J, cfg, is_training=True, device=dev)
+    params = list(network_fn.head.parameters()) + list(network_fn.temporal.parameters())
+    g = torch.Generator().manual_seed(42)
+    labels = torch.randint(0, K, (B,), generator=g).to(dev)
+    use_pose = which == 'cfg003'
+    lbl = torch.rand(N, H, H, J, generator=g).to(dev) if use_pose else None
+    valid = (torch.rand(N, J, generator=g) > 0.3).to(dev) if use_pose else None
+    clips = [_features(N, P, C, torch.bfloat16, dev, seed=42 + r).view(B, F, H, H, C).requires_grad_(True)
+             for r in range(R)]
+    tc = cfg.TRAIN
+
+    def module_run(r):
+        for t in params:
+            t.grad = None
+        clips[r].grad = None
+        logits, ep = network_fn(clips[r])
+        losses = apa_loss.gen_losses(labels, logits, tc.LOSS_FN_ACTION, K, tc.LOSS_FN_ACTION_WT, lbl,
+                                     ep.get('PoseLogits') if use_pose else None, tc.LOSS_FN_POSE if use_pose else '',
+                                     valid, tc.LOSS_FN_POSE_WT, ep, cfg)
+        sum(losses).backward()
+
+    steps = {'clip_one_call': clip_step, 'module_path': _round_robin([(lambda r=r: module_run(r)) for r in range(R)]),
+             'flat_one_call': flat_step}
+
+    def clip_loss_us(n=200):
+        """median HIP-event time of apa_clip_xent_fwd_bwd alone (its two launches) on [N,K] frame logits"""
+        x = torch.randn(N, K, device=dev)
+        tw, tb = _clip_kwargs(dev, K, F, True)['temporal']
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+        ws = torch.empty((max(cof.clip_xent_workspace_bytes(B, F, K), 16),), dtype=torch.uint8, device=dev)
+        ts = []
+        for _ in range(n):
+            ev[0].record()
+            cof.clip_xent_fwd_bwd(x, labels, F, tw, tb, workspace=ws)
+            ev[1].record()
+            torch.cuda.synchronize()
+            ts.append(ev[0].elapsed_time(ev[1]))
+        return round(sorted(ts)[len(ts) // 2] * 1e3, 2)
+
+    info = dict(info, workload='clip batch {} x {} frames x {}x{}x{} bf16, K={}, temporal attention, {} head: one-call '
+                               'clip step vs module path vs flat one-call step at N={}'.format(
+                                   B, F, H, H, C, K, 'per-class (HMDB-51)' if which == 'perclass' else 'cfg 003', N) +
+                               _rot_note(R, 2 * N * P * C * 2))
+    return steps, info, clip_loss_us
+
+
+def run_video(cof, dev, args, which):
+    """The variants alternate inside every round (one process, same clocks): per variant the median over five (or
+    more) rounds of the mean step time of a loop of `steps` steps."""
+    steps, info, clip_loss_us = build_video(cof, dev, which, args.clips, args.frames, args.hw, args.classes or 51,
+                                            rotate=args.rotate)
+    if args.only:
+        steps = {args.only: steps[args.only]}
+    for fn in steps.values():
+        for _ in range(max(args.warmup, info['rotate'])):
+            fn()
+    torch.cuda.synchronize()
+    per = {k: [] for k in steps}
+    rounds = 0
+    t_all = time.perf_counter()
+    while rounds < 5 or time.perf_counter() - t_all < 0.5:
+        for k, fn in steps.items():
+            t0 = time.perf_counter()
+            for _ in range(args.steps):
+                fn()
+            torch.cuda.synchronize()
+            per[k].append((time.perf_counter() - t0) / args.steps)
+        rounds += 1
+        if rounds >= 200:
+            break
+    med = {k: sorted(v)[len(v) // 2] for k, v in per.items()}
+    out = report(info, med.get('clip_one_call', next(iter(med.values()))), rounds)
+    out['us_per_step'] = {k: round(v * 1e6, 2) for k, v in med.items()}
+    out['us_per_step_min'] = {k: round(min(v) * 1e6, 2) for k, v in per.items()}
+    out['clip_loss_call_us_hip_events'] = clip_loss_us()
+    return out
+
+
 # algorithmic HBM bytes of the four pose-attention kernels (fp32 parameters / F / logits; X and dX in the feature dtype)
 def poseatt_kernel_bytes(N, P, C, J, M, K, xbytes):
     R = M * C
@@ -581,7 +704,11 @@ def report(info, sec, repeats):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--workload', default='cfg003', choices=['cfg003', 'perclass', 'eval002', 'eval003', 'rank1', 'posebwd', 'posebwd_acc', 'update003',
-                                                         'update_perclass', 'poseatt'])
+                                                         'update_perclass', 'poseatt', 'video_perclass', 'video003'])
+    ap.add_argument('--clips', type=int, default=8, help='video_*: clips per batch')
+    ap.add_argument('--frames', type=int, default=4, help='video_*: frames per clip')
+    ap.add_argument('--only', default=None, choices=['clip_one_call', 'module_path', 'flat_one_call'],
+                    help='video_*: run one variant alone (kernel traces)')
     ap.add_argument('--batch', type=int, default=32)
     ap.add_argument('--hw', type=int, default=14)
     ap.add_argument('--classes', type=int, default=None)
@@ -606,6 +733,9 @@ def main():
         return
     if args.workload == 'eval003':
         print(json.dumps(run_eval003(cof, dev, args)))
+        return
+    if args.workload in ('video_perclass', 'video003'):
+        print(json.dumps(run_video(cof, dev, args, 'perclass' if args.workload == 'video_perclass' else 'cfg003')))
         return
     if args.workload == 'poseatt':
         step, info, kernel_times = build_poseatt(cof, dev, args.batch, args.hw, args.classes or 393,
