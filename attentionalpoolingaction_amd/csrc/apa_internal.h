@@ -212,6 +212,8 @@ constexpr unsigned APA_IFLAG_ATT_READY = 1u << 24;      // M == 1, Xatt != X: `a
 constexpr unsigned APA_IFLAG_NO_ATT_WGRAD = 1u << 25;   // M == 1 + DXATT_RANK1: dWa / dba / RNG bump done by the caller
 constexpr unsigned APA_IFLAG_NO_DX = 1u << 26;          // M == 1, Xatt != X: dX is NOT written -- the caller forms the
                                                         // pooling share A/P . dz . mask/keep in its own product's epilogue
+constexpr unsigned APA_IFLAG_FINALIZE_LAUNCH = 1u << 27;   // M == 1 forward: m1_finalize_fwd_kernel stays a launch of its
+                                                           // own where the logits kernel could merge the partials itself
 
 struct M1Xent {
   const int64_t* labels;
@@ -256,13 +258,23 @@ struct M1Trace {
   int pool_fwd, fwd_w, fwd_pix;    // M1Pool; stream: VW and PIX, per-pixel vec: VEC (pix 0)
   int pool_bwd, bwd_w, bwd_pix;
   int fused, keep_bits, relu_input;   // keep_bits: the backward read the forward call's keep bits
-  int S, ppb, nblk, cw;            // plan; cw: channels per thread column of m1_finalize_fwd_kernel
+  int S, ppb, nblk, cw;            // plan; cw: channels per thread column of m1_finalize_fwd_kernel (on the folded
+                                   // route: of the launch it replaces)
   int logits, logits_nv4, logits_nsub;
   int head, head_ug, head_mv;
   int gemv, reduce, rng_bump, cat_fwd, cat_bwd;
 };
 extern thread_local M1Trace* g_m1_trace;
 inline M1Trace* m1_trace() { return g_m1_trace; }
+// Beside the trace, and like it reached through the test-only probe library alone: internal flag bits added to every
+// m1_forward of this thread (the extern "C" entries mask the caller's own), and what the last traced m1_forward did
+// with the finalize step -- M1Trace's layout is part of the probe interface and stays put.
+struct M1FwdRoute {
+  int folded;     // 1: the partial merge ran in the logits kernel's prologue, 0: m1_finalize_fwd_kernel
+  int launches;   // launches behind the pooling pass: finalize (or none), partial logits, reduce
+};
+extern thread_local unsigned g_m1_iflags;
+extern thread_local M1FwdRoute g_m1_fwd_route;
 
 enum M1Act { M1_ACT_ID = 0, M1_ACT_RELU = 1, M1_ACT_SOFTMAX = 2 };   // passed to the kernels as int
 // A forward / backward call: the caller's tensors (M1Fwd / M1Bwd) and, in M1Call, everything the call resolves before
@@ -326,16 +338,22 @@ int m1_bwd_small(const float* G, const float* Wt, const float* zsave, const floa
                  hipStream_t st);
 bool m1_logits2_supported(int C, int K);
 size_t m1_logits2_ws_bytes(int N, int C, int K);
-int m1_logits2(const float* z, const float* Wt, const float* abar, const float* bt, float* logits,
-               float* part_ws, int N, int C, int K, hipStream_t st);
+// The folded forward: the partial logits kernel merges the pooling pass's S per-block partials in its prologue
+// (z, stored too) and the reduce kernel forms abar from the per-block statistics, both with m1_finalize_fwd_kernel's
+// own summation chains -- z and abar are outputs then.  null: z and abar are in memory already.
+struct M1Fold { const float* pacc; const float* pstat; int S, P; };
+bool m1_logits2_fold_supported(int N, int C, int S);
+int m1_logits2(float* z, const float* Wt, float* abar, const float* bt, float* logits,
+               float* part_ws, int N, int C, int K, hipStream_t st, const M1Fold* fold = nullptr);
 bool m1_bwd_head_supported(int N, int C, int K);
 int m1_bwd_head(const float* G, const float* Wt, const float* zsave, const float* abar,
                 const float* bt, float* dz, float* dWt, float* dbt, float* sn, int N, int C, int K,
                 hipStream_t st, float* loss = nullptr, float lscale = 0.f);
 bool m1_logits_xent_supported(int N, int C, int K, bool eval);
-int m1_logits2_xent(const float* z, const float* Wt, const float* abar, const float* bt,
+int m1_logits2_xent(float* z, const float* Wt, float* abar, const float* bt,
                     const int64_t* labels, float* logits, float* loss, float* G, float gscale,
-                    float* probs, int64_t* pred, float* part_ws, int N, int C, int K, hipStream_t st);
+                    float* probs, int64_t* pred, float* part_ws, int N, int C, int K, hipStream_t st,
+                    const M1Fold* fold = nullptr);
 // the fixed-order column sum of ColsumArgs (apa_colsum.h) as a launch of its own: ceil(C / 32) blocks of 1024 threads
 int m1_colsum(const ColsumArgs& a, hipStream_t st);
 

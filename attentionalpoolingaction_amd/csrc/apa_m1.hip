@@ -309,6 +309,8 @@ __global__ __launch_bounds__(256) void m1_att_gemv_bwd2_kernel(
 // host side
 // ============================================================================================
 thread_local M1Trace* g_m1_trace = nullptr;
+thread_local unsigned g_m1_iflags = 0;
+thread_local M1FwdRoute g_m1_fwd_route = {0, 0};
 
 // Any channel count that is a whole number of 16-byte vectors is served: the channel-split streaming
 // kernels (apa_m1_stream.hip) for the wide benchmark shapes, the per-pixel kernels (apa_m1_vec.hip) for the
@@ -470,29 +472,46 @@ int m1_forward(const M1Call& c, const M1Fwd& io, M1Xent* xf) {
   }
   if (rc != APA_OK) return rc;
   const int online = (c.fused && c.act == M1_ACT_SOFTMAX) ? 1 : 0;
+  // which kernels form the logits: the partial-logits kernel with the row's cross-entropy in its reducer (one-call
+  // steps), with the plain reducer, or the split-K product
+  const bool xeval = xf && xf->probs;
+  if (c.cat) xf = nullptr;   // the extra channels add to the logits after the reduction: no fused loss
+  const bool xroute = xf && m1_logits_xent_supported(N, C, K, xeval) &&
+                      m1_small_route_ok(C, K, xf->G, io.Wt, io.zsave, xeval);
+  const bool l2route = m1_logits2_supported(C, K) && (reinterpret_cast<uintptr_t>(io.zsave) & 15) == 0;
+  // The merge of the S block partials: in the partial-logits kernel's prologue where that is exact and within its
+  // budget of 16 loads per lane (identity / relu attention -- the on-line softmax merge and the normalisation of att
+  // stay with the finalize kernel --, S <= 16, N < 128, no concatenated channels, 16-byte rows), else a launch of its own
+  const bool fold = (xroute || l2route) && !((c.flags | g_m1_iflags) & APA_IFLAG_FINALIZE_LAUNCH) &&
+                    c.act != M1_ACT_SOFTMAX && !c.cat && m1_logits2_fold_supported(N, C, c.pl.S) &&
+                    ((reinterpret_cast<uintptr_t>(io.zsave) | reinterpret_cast<uintptr_t>(c.pacc)) & 15) == 0;
+  const M1Fold mf{c.pacc, c.pstat, c.pl.S, c.P};
   // enough blocks to put every CU to work (the kernel is bound by the bytes each CU loads)
   int cw = 256;
   while (cw > 64 && (long)N * ((C + 4 * cw - 1) / (4 * cw)) < 256) cw >>= 1;
-  if (tr) tr->cw = cw;
-  hipLaunchKernelGGL(m1_finalize_fwd_kernel, dim3(N, (C + 4 * cw - 1) / (4 * cw)), dim3(256), 0, c.st, c.pacc,
-                     c.pstat, io.zsave, io.abar, io.att, c.P, c.pl.S, C, online, cw);
-  APA_LAUNCH_CHECK("m1_finalize_fwd_kernel");
+  if (tr) {
+    tr->cw = cw;
+    g_m1_fwd_route.folded = fold;
+    g_m1_fwd_route.launches = (fold ? 0 : 1) + 2;
+  }
+  if (!fold) {
+    hipLaunchKernelGGL(m1_finalize_fwd_kernel, dim3(N, (C + 4 * cw - 1) / (4 * cw)), dim3(256), 0, c.st, c.pacc,
+                       c.pstat, io.zsave, io.abar, io.att, c.P, c.pl.S, C, online, cw);
+    APA_LAUNCH_CHECK("m1_finalize_fwd_kernel");
+  }
   // logits = z . Wt + abar (x) bt -- the first reader of Wt / bt (apa_hooks.td_weights_ready_event)
   if (c.td_ready) APA_HIP_CHECK(hipStreamWaitEvent(c.st, c.td_ready, 0));
-  const bool xeval = xf && xf->probs;
-  if (c.cat) xf = nullptr;   // the extra channels add to the logits after the reduction: no fused loss
-  if (xf && m1_logits_xent_supported(N, C, K, xeval) &&
-      m1_small_route_ok(C, K, xf->G, io.Wt, io.zsave, xeval)) {
+  if (xroute) {
     // training: the same conditions under which m1_backward takes the head kernel, which finishes loss[0]
     if (tr) tr->logits = xeval ? M1_LOGITS_XENT_PROBS : M1_LOGITS_XENT;
     rc = m1_logits2_xent(io.zsave, io.Wt, io.abar, io.bt, xf->labels, io.logits, xf->loss, xf->G, xf->gscale,
-                         xf->probs, xf->pred, c.gemm_ws, N, C, K, c.st);
+                         xf->probs, xf->pred, c.gemm_ws, N, C, K, c.st, fold ? &mf : nullptr);
     xf->done = rc == APA_OK;
     return rc;
   }
-  if (m1_logits2_supported(C, K) && (reinterpret_cast<uintptr_t>(io.zsave) & 15) == 0) {
+  if (l2route) {
     if (tr) tr->logits = M1_LOGITS2;
-    rc = m1_logits2(io.zsave, io.Wt, io.abar, io.bt, io.logits, c.gemm_ws, N, C, K, c.st);
+    rc = m1_logits2(io.zsave, io.Wt, io.abar, io.bt, io.logits, c.gemm_ws, N, C, K, c.st, fold ? &mf : nullptr);
   } else {
     if (tr) tr->logits = M1_LOGITS_SGEMM;
     rc = sgemm_small(io.zsave, C, 1, io.Wt, K, 1, io.logits, K, N, K, C, c.pl.lsplits, io.abar, io.bt, c.gemm_ws, c.st);

@@ -37,6 +37,34 @@ int apa_probe_m1_support(int N, int C, int K, int dtype) {
          (apa::m1_small_supported(C, K) ? 16 : 0) | (apa::m1_bwd_head_supported(N, C, K) ? 32 : 0);
 }
 
+// Internal flag bits (APA_IFLAG_*, apa_internal.h) added to every m1_forward this thread runs through the wrappers
+// below, until set again: APA_IFLAG_FINALIZE_LAUNCH = 1 << 27 puts the two forward sequences side by side
+// (tests/test_m1_fold_gpu.py).  The extern "C" entries mask a caller's own internal bits.
+void apa_probe_m1_set_iflags(unsigned iflags) { apa::g_m1_iflags = iflags; }
+
+// out[0..1] = folded, launches of the last traced m1_forward (M1FwdRoute; M1Trace keeps its layout)
+void apa_probe_m1_fwd_route(int64_t* out) {
+  out[0] = apa::g_m1_fwd_route.folded; out[1] = apa::g_m1_fwd_route.launches;
+}
+
+// m1_call_fill alone, on the host: nothing is launched and no pointer is read.  A forward call (bwd == 0) or a
+// backward call whose tensors all sit at `base` (16-byte aligned); out[0..9] = S, ppb, nblk, lsplits, plan total,
+// pool family, small route, train, fused, offset of the partials in the workspace.  Returns m1_call_fill's status.
+int apa_probe_m1_call_fill(int bwd, int loss_done, int xatt_is_x, int N, int P, int C, int Ca, int K, unsigned flags,
+                           float keep_prob, int dtype, int64_t* out) {
+  alignas(16) static char base[64];
+  apa::M1Call c;
+  apa::M1Bwd b{};
+  b.X = base; b.Xatt = xatt_is_x ? base : base + 16;
+  b.Wt = reinterpret_cast<const float*>(base); b.zsave = b.Wt; b.G = b.Wt; b.att = b.Wt;
+  b.dXatt = base;
+  const int rc = apa::m1_call_fill(c, b.X, b.Xatt, bwd ? &b : nullptr, loss_done != 0, nullptr, apa::Hooks(), base, N,
+                                   P, C, Ca, K, flags, keep_prob, 1, 2, dtype, nullptr);
+  out[0] = c.pl.S; out[1] = c.pl.ppb; out[2] = c.pl.nblk; out[3] = c.pl.lsplits; out[4] = (int64_t)c.pl.total;
+  out[5] = c.pool; out[6] = c.small; out[7] = c.train; out[8] = c.fused; out[9] = (int64_t)c.pl.off_pacc;
+  return rc;
+}
+
 int apa_probe_m1_fwd_ex(apa::M1Trace* t, const apa_hooks* hooks, const void* X, const void* Xatt, const float* Wa,
                         const float* ba, const float* Wt, const float* bt, float* logits, float* att, float* zsave,
                         float* abar, void* topdown, void* ws, size_t ws_bytes, int N, int P, int C, int Ca, int K,

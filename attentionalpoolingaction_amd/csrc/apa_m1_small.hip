@@ -25,15 +25,45 @@ __device__ __forceinline__ f32x4 mfma16(float a, float b, f32x4 c) {
   return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
 }
 
+// abar[n] = (sum_s pstat[n,s,2]) / P on the folded route (S <= 16), bit for bit as m1_finalize_fwd_kernel forms it
+// (apa_m1.hip): one split per thread of a 256-thread block, wave_sum, then (s0 + s1) + (s2 + s3) over the four waves.
+// With S <= 16 the splits sit on the first DPP row of wave 0; every other row and wave sums zeros.
+//   m1_abar_wave:   the same on any one wave (lanes >= S hold 0); the result is wave-uniform
+//   m1_abar_thread: wave_sum's tree over that row written out for one thread (row_sum16: lane ^ 1, lane ^ 2, the
+//                   two quads of a half row, the two half rows; lane 0's value)
+__device__ __forceinline__ float m1_abar_tail(float row0, int P) {
+  const float w0 = (row0 + 0.f) + (0.f + 0.f);       // wave_sum: rows 1..3 of the wave
+  const float asum = (w0 + 0.f) + (0.f + 0.f);       // waves 1..3 of the block
+  return asum * (1.0f / (float)P);
+}
+__device__ __forceinline__ float m1_abar_wave(const float* __restrict__ pstat, int n, int S, int P, int lane) {
+  const float a_s = lane < S ? pstat[((size_t)n * S + lane) * 4 + 2] : 0.f;
+  const float w0 = wave_sum(a_s);
+  return ((w0 + 0.f) + (0.f + 0.f)) * (1.0f / (float)P);
+}
+__device__ __forceinline__ float m1_abar_thread(const float* __restrict__ pstat, int n, int S, int P) {
+  float a[16];
+#pragma unroll
+  for (int u = 0; u < 16; ++u) a[u] = pstat[((size_t)n * S + min(u, S - 1)) * 4 + 2];
+#pragma unroll
+  for (int u = 0; u < 16; ++u) a[u] = u < S ? a[u] : 0.f;
+  const float l0 = (a[0] + a[1]) + (a[2] + a[3]), l7 = (a[7] + a[6]) + (a[5] + a[4]);
+  const float l15 = (a[15] + a[14]) + (a[13] + a[12]), l8 = (a[8] + a[9]) + (a[10] + a[11]);
+  return m1_abar_tail((l0 + l7) + (l15 + l8), P);
+}
+
 // L2: logits[n,k] = sum_cc part[cc][n][k] + abar[n] * bt[k]   (fixed order over cc)
-__global__ __launch_bounds__(256) void m1_logits_reduce_kernel(const float* __restrict__ part,
-                                                               const float* __restrict__ abar,
+// pstat (the folded route): abar is formed here from the pooling pass's statistics and stored for the backward pass
+__global__ __launch_bounds__(256) void m1_logits_reduce_kernel(const float* __restrict__ part, float* abar,
                                                                const float* __restrict__ bt,
                                                                float* __restrict__ logits, int N,
-                                                               int K, int nchunks) {
+                                                               int K, int nchunks,
+                                                               const float* __restrict__ pstat, int S, int P) {
   const int idx = blockIdx.x * 256 + threadIdx.x;
   if (idx >= N * K) return;
   const int n = idx / K, k = idx - n * K;
+  float ab = 0.f;
+  if (pstat) ab = m1_abar_thread(pstat, n, S, P);
   const size_t stride = (size_t)N * K;
   float v[32];
   float acc = 0.f;
@@ -43,7 +73,9 @@ __global__ __launch_bounds__(256) void m1_logits_reduce_kernel(const float* __re
 #pragma unroll
     for (int u = 0; u < 32; ++u) acc += (c + u < nchunks) ? v[u] : 0.f;
   }
-  logits[idx] = fmaf(abar[n], bt[k], acc);
+  if (!pstat) ab = abar[n];
+  else if (k == 0) abar[n] = ab;
+  logits[idx] = fmaf(ab, bt[k], acc);
 }
 
 // L2x: L2 fused with the softmax cross-entropy of the row (apa_attn_head_train_step only).
@@ -56,17 +88,24 @@ __global__ __launch_bounds__(256) void m1_logits_reduce_kernel(const float* __re
 // softmax probabilities and first-index argmax instead (eval.py:193-197).
 template <int NV4, bool EVAL>   // NV4: 16-byte vectors per lane of the half-wave, K <= 512
 __global__ __launch_bounds__(256) void m1_logits_xent_kernel(
-    const float* __restrict__ part, const float* __restrict__ abar, const float* __restrict__ bt,
+    const float* __restrict__ part, float* abar, const float* __restrict__ bt,
     const int64_t* __restrict__ labels, float* __restrict__ logits, float* __restrict__ out_loss,
     float* __restrict__ G, float* __restrict__ probs, int64_t* __restrict__ pred, int N, int K,
-    int nchunks, float gscale) {
+    int nchunks, float gscale, const float* __restrict__ pstat, int S, int P) {
   typedef float f4u __attribute__((ext_vector_type(4), aligned(4)));
   constexpr int EPT = NV4 == 4 ? 2 : 1;
   __shared__ float row[NV4 * 128];
   const int n = blockIdx.x, tid = threadIdx.x;
   const size_t stride = (size_t)N * K;
   const float* prow = part + (size_t)n * K;
-  const float ab = abar[n];
+  // pstat (the folded route): abar[n] is formed here, by every wave alike, and stored for the backward pass
+  float ab;
+  if (pstat) {
+    ab = m1_abar_wave(pstat, n, S, P, tid & 63);
+    if (tid == 0) abar[n] = ab;
+  } else {
+    ab = abar[n];
+  }
   const int lab = EVAL ? 0 : (int)labels[n];
   float btv[EPT], acc[EPT];
 #pragma unroll
@@ -366,12 +405,17 @@ __global__ __launch_bounds__(256) void m1_bwd_small_kernel(
 //   A fragment: lane (r = n, kq) loads the 4 consecutive channels 4kq..4kq+3 of its row as one
 //               16-byte vector and feeds element e to MFMA step e (k-order is free);
 //   B fragment: Wt[c = cw + 4kq + e][k0 + r], 64-byte row segments.
-// (Folding the finalize step in -- forming z in the A registers from the S per-block partials of
-// the pooling pass -- was measured slower than the separate, fully coalesced finalize kernel:
-// 32 strided 16-byte loads per lane, 8.4 us vs 3 + 4 us.)
+// Folding the finalize step in -- forming z in the A registers from the S per-block partials of the pooling pass --
+// was built twice (docs/DESIGN_HISTORY.md has the bytes-per-block table):
+//   * round 2, this kernel's geometry: 128 blocks, each gathering all 32 images x 16 splits of its chunk -- 128 KB
+//     of partials beside 25 KB of Wt, 32 strided 16-byte loads per lane: 8.4 us against 3 + 4 us for the separate,
+//     fully coalesced finalize kernel;
+//   * round 13, m1_logits2_fold_kernel below: 256 blocks of 8 images x 2 k-tile groups, 32 KB of partials + 50 KB
+//     of Wt per block, 16 + 52 loads per lane: 6.65 us against 4.74 + 4.92 us for the two launches (rocprofv3).
 // --------------------------------------------------------------------------------------------
-// (A variant that also did the finalize step in its prologue -- one launch fewer -- measured slower, round 2:
-// training step 51.7 -> 54.1 us; it was removed in round 3.)
+// (The round-2 variant made the training step slower, 51.7 -> 54.1 us, and was removed in round 3.  The 8-image form
+// makes it faster, 50.69 -> 49.95 us over six alternated runs each (profiles/r13_m1_fold_summary.md), and is the
+// M1Fold route of m1_forward, apa_m1.hip.)
 template <int KG>
 __global__ __launch_bounds__(256) void m1_logits2_kernel(const float* __restrict__ z,
                                                          const float* __restrict__ Wt,
@@ -459,6 +503,89 @@ __global__ __launch_bounds__(256) void m1_logits2_kernel(const float* __restrict
       const float sm = (red[t] + red[2 * KG * 256 + t]) + (red[4 * KG * 256 + t] + red[6 * KG * 256 + t]);
       const int n = n0 + ni * 16 + row, kt = gx * KG + j, k = kt * 16 + colr;
       if (n < N && kt < ktiles && k < K) out[(size_t)n * K + k] = sm;
+    }
+  }
+}
+
+// --------------------------------------------------------------------------------------------
+// L1v2f: L1v2 with the partial merge of m1_finalize_fwd_kernel (apa_m1.hip) in its prologue -- no z in memory to
+// wait for, one launch fewer.  Identity / relu attention, S <= 16 splits, N < 128 (m1_forward decides).
+// grid (C/64, ceil(ceil(K/16)/KG), ceil(N/8)); block (cx, gx, rq): 64 channels x KG k-tiles x 8 images, so that a
+// block ingests 8 S 256 B of partials + 64 KG 64 B of Wt (32 + 52 KB at the benchmark shape, over 256 blocks).
+//   A fragment: lane (r, kq) loads channels 4kq..4kq+3 of its wave's 16 of image rq*8 + (r & 7) from EVERY split's
+//               partial row -- 16 16-byte loads (splits >= S repeat the last one), issued in one batch with the B
+//               fragments -- and forms its four z values with the finalize kernel's own chain, r = fmaf(p_u, 1/P, r)
+//               for u = 0 .. S-1: z is bit-identical.  Tile rows 8..15 repeat rows 0..7 (same addresses) and are
+//               dropped at the store; blocks gx == 0 store z for the backward pass.
+//   B fragment, MFMA sequence per output, the (w0 + w1) + (w2 + w3) sum through LDS and part[cx][n][k]: as L1v2, so
+//               the partial logits are bit-identical too.
+// --------------------------------------------------------------------------------------------
+template <int KG>
+__global__ __launch_bounds__(256) void m1_logits2_fold_kernel(const float* __restrict__ pacc,
+                                                              const float* __restrict__ Wt,
+                                                              float* __restrict__ zsave,
+                                                              float* __restrict__ part, int N, int C, int K,
+                                                              int S, int P) {
+  extern __shared__ __attribute__((aligned(16))) float red[];   // [4 waves][KG tiles][8 rows][16]
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const int r = lane & 15, kq = lane >> 4;
+  const int cx = blockIdx.x, gx = blockIdx.y, n0 = blockIdx.z * 8;
+  const int ktiles = (K + 15) >> 4;
+  const int n = min(n0 + (r & 7), N - 1);                              // rows >= N: discarded at the stores
+  const int cw = cx * 64 + wave * 16;
+  const float invP = 1.0f / (float)P;
+  int colj[KG];
+#pragma unroll
+  for (int j = 0; j < KG; ++j)                                          // surplus tiles / columns:
+    colj[j] = min(min(gx * KG + j, ktiles - 1) * 16 + r, K - 1);       // recomputed, discarded
+  // every load of the block in one batch, the partials first: the merge runs while Wt is still arriving
+  constexpr int FB = 16;
+  const float* pa = pacc + (size_t)n * S * C + cw + 4 * kq;
+  float4 first[FB];
+#pragma unroll
+  for (int u = 0; u < FB; ++u) first[u] = *reinterpret_cast<const float4*>(pa + (size_t)min(u, S - 1) * C);
+  __builtin_amdgcn_sched_barrier(0);   // (left to itself the compiler requests Wt first: + 0.7 us on the step)
+  float bw[KG][4];
+#pragma unroll
+  for (int j = 0; j < KG; ++j)
+#pragma unroll
+    for (int e = 0; e < 4; ++e) bw[j][e] = Wt[(size_t)(cw + 4 * kq + e) * K + colj[j]];
+  __builtin_amdgcn_sched_barrier(0);
+  float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+  for (int u = 0; u < FB; ++u) {
+    if (u < S) {
+      z.x = fmaf(first[u].x, invP, z.x); z.y = fmaf(first[u].y, invP, z.y);
+      z.z = fmaf(first[u].z, invP, z.z); z.w = fmaf(first[u].w, invP, z.w);
+    }
+  }
+  if (gx == 0 && r < 8 && n0 + r < N) *reinterpret_cast<float4*>(zsave + (size_t)(n0 + r) * C + cw + 4 * kq) = z;
+  f32x4 acc[KG];
+#pragma unroll
+  for (int j = 0; j < KG; ++j) acc[j] = f32x4{0.f, 0.f, 0.f, 0.f};
+  const float av[4] = {z.x, z.y, z.z, z.w};
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+#pragma unroll
+    for (int j = 0; j < KG; ++j) acc[j] = mfma16(av[e], bw[j][e], acc[j]);
+  }
+  // ---- fixed-order sum of the 4 waves' 16-channel shares (tile rows 0..7: lanes kq < 2), one store per element ----
+  if (kq < 2) {
+#pragma unroll
+    for (int j = 0; j < KG; ++j)
+#pragma unroll
+      for (int reg = 0; reg < 4; ++reg) red[(wave * KG + j) * 128 + (kq * 4 + reg) * 16 + r] = acc[j][reg];
+  }
+  __syncthreads();
+  float* out = part + (size_t)cx * N * K;
+#pragma unroll
+  for (int m = 0; m < (KG + 1) / 2; ++m) {
+    const int i = m * 256 + tid;                 // (tile j, row, column) of the block's KG x 8 x 16 outputs
+    if (i < KG * 128) {
+      const float sm = (red[i] + red[KG * 128 + i]) + (red[2 * KG * 128 + i] + red[3 * KG * 128 + i]);
+      const int j = i >> 7, row = (i >> 4) & 7, colr = i & 15;
+      const int nn = n0 + row, kt = gx * KG + j, k = kt * 16 + colr;
+      if (nn < N && kt < ktiles && k < K) out[(size_t)nn * K + k] = sm;
     }
   }
 }
@@ -907,12 +1034,40 @@ static int launch_logits2(const float* z, const float* Wt, float* part_ws, int N
   return APA_OK;
 }
 
-int m1_logits2(const float* z, const float* Wt, const float* abar, const float* bt, float* logits,
-               float* part_ws, int N, int C, int K, hipStream_t st) {
-  const int rc = launch_logits2(z, Wt, part_ws, N, C, K, st);
+// L1v2f: two k-tile groups per 64-channel chunk and 8-image group while an instance covers half the k-tiles
+// (K <= 416), more groups of 13 beyond
+bool m1_logits2_fold_supported(int N, int C, int S) {
+  return C % 64 == 0 && S >= 1 && S <= 16 && N >= 1 && N < 128;   // N >= 128: the nsub = 4 form keeps its finalize
+}
+
+static int launch_logits2_fold(const M1Fold& f, const float* Wt, float* zsave, float* part_ws, int N, int C, int K,
+                               hipStream_t st) {
+  const int ktiles = (K + 15) / 16, half = (ktiles + 1) / 2;
+  const int kg = half <= 1 ? 1 : (half <= 2 ? 2 : (half <= 4 ? 4 : (half <= 7 ? 7 : 13)));
+  if (M1Trace* t = m1_trace()) t->logits_nsub = 1;
+  dim3 grid(C / 64, (ktiles + kg - 1) / kg, (N + 7) / 8);
+  const size_t shm = (size_t)4 * kg * 128 * sizeof(float);   // 26 KB at KG = 13
+#define APA_LF(KG)                                                                                          \
+  hipLaunchKernelGGL((m1_logits2_fold_kernel<KG>), grid, dim3(256), shm, st, f.pacc, Wt, zsave, part_ws, N, \
+                     C, K, f.S, f.P)
+  if (kg == 1) APA_LF(1);
+  else if (kg == 2) APA_LF(2);
+  else if (kg == 4) APA_LF(4);
+  else if (kg == 7) APA_LF(7);
+  else APA_LF(13);
+#undef APA_LF
+  APA_LAUNCH_CHECK("m1_logits2_fold_kernel");
+  return APA_OK;
+}
+
+int m1_logits2(float* z, const float* Wt, float* abar, const float* bt, float* logits,
+               float* part_ws, int N, int C, int K, hipStream_t st, const M1Fold* fold) {
+  const int rc = fold ? launch_logits2_fold(*fold, Wt, z, part_ws, N, C, K, st)
+                      : launch_logits2(z, Wt, part_ws, N, C, K, st);
   if (rc != APA_OK) return rc;
   hipLaunchKernelGGL(m1_logits_reduce_kernel, dim3((N * K + 255) / 256), dim3(256), 0, st, part_ws,
-                     abar, bt, logits, N, K, C / (64 * logits2_nsub(N, C)));
+                     abar, bt, logits, N, K, C / (64 * logits2_nsub(N, C)), fold ? fold->pstat : nullptr,
+                     fold ? fold->S : 0, fold ? fold->P : 1);
   APA_LAUNCH_CHECK("m1_logits_reduce_kernel");
   return APA_OK;
 }
@@ -924,22 +1079,28 @@ bool m1_logits_xent_supported(int N, int C, int K, bool eval) {
          (eval || m1_bwd_head_supported(N, C, K));   // training: the head kernel finishes loss[0]
 }
 
-int m1_logits2_xent(const float* z, const float* Wt, const float* abar, const float* bt,
+int m1_logits2_xent(float* z, const float* Wt, float* abar, const float* bt,
                     const int64_t* labels, float* logits, float* loss, float* G, float gscale,
-                    float* probs, int64_t* pred, float* part_ws, int N, int C, int K, hipStream_t st) {
+                    float* probs, int64_t* pred, float* part_ws, int N, int C, int K, hipStream_t st,
+                    const M1Fold* fold) {
   {
-    const int rc = launch_logits2(z, Wt, part_ws, N, C, K, st);
+    const int rc = fold ? launch_logits2_fold(*fold, Wt, z, part_ws, N, C, K, st)
+                        : launch_logits2(z, Wt, part_ws, N, C, K, st);
     if (rc != APA_OK) return rc;
   }
   const int nparts = C / (64 * logits2_nsub(N, C));
+  const float* const pstat = fold ? fold->pstat : nullptr;
+  const int fS = fold ? fold->S : 0, fP = fold ? fold->P : 1;
 #define APA_LX(NV4)                                                                                  \
   do {                                                                                               \
     if (probs)                                                                                       \
       hipLaunchKernelGGL((m1_logits_xent_kernel<NV4, true>), dim3(N), dim3(256), 0, st, part_ws,     \
-                         abar, bt, labels, logits, loss, G, probs, pred, N, K, nparts, gscale);      \
+                         abar, bt, labels, logits, loss, G, probs, pred, N, K, nparts, gscale,       \
+                         pstat, fS, fP);                                                             \
     else                                                                                             \
       hipLaunchKernelGGL((m1_logits_xent_kernel<NV4, false>), dim3(N), dim3(256), 0, st, part_ws,    \
-                         abar, bt, labels, logits, loss, G, probs, pred, N, K, nparts, gscale);      \
+                         abar, bt, labels, logits, loss, G, probs, pred, N, K, nparts, gscale,       \
+                         pstat, fS, fP);                                                             \
   } while (0)
   const int nv4 = K <= 128 ? 1 : (K <= 256 ? 2 : 4);
   if (M1Trace* t = m1_trace()) t->logits_nv4 = nv4;
