@@ -352,6 +352,50 @@ extern "C" int apa_attn_pool_bwd_cat(const apa_concat_feat* cat, const apa_hooks
                             flags & APA_PUBLIC_FLAGS & ~APA_FLAG_WS_FROM_FWD, keep_prob, seed, offset, dtype, stream);
 }
 
+// a valid apa_multilabel, or the refusal (nothing has touched the GPU)
+static int check_multilabel(const char* fn, const apa_multilabel* ml) {
+  if (!ml || !ml->labels) {
+    set_error("%s: null apa_multilabel / labels pointer", fn);
+    return APA_ERR_INVALID_ARG;
+  }
+  if (ml->kind != APA_ACTION_LOSS_MULTI_LABEL && ml->kind != APA_ACTION_LOSS_MULTI_LABEL_2) {
+    set_error("%s: unknown loss kind %d", fn, ml->kind);
+    return APA_ERR_INVALID_ARG;
+  }
+  return APA_OK;
+}
+
+// The flat one-call step under a sigmoid action loss: apa_attn_head_train_step_ex with the loss exchanged.  M == 1
+// with the fold's shapes: the logits reducer does the rows' loss (m1_logits_ml_kernel); everything else -- per-class
+// maps (their pc_row_xent folds read integer labels: not entered), K past the fold, the generic route -- runs
+// ml_rows_kernel on the finished logits.  Bit-identical to apa_attn_pool_fwd, apa_multilabel_loss_fwd_bwd,
+// apa_attn_pool_bwd either way.
+static int head_step_multilabel(const apa_multilabel& ml, const Hooks& hk, const void* X, const void* Xatt,
+                                const float* Wa, const float* ba, const float* Wt, const float* bt, float loss_wt,
+                                float grad_scale, float* logits, float* att, float* zsave, float* abar, float* loss,
+                                float* G, void* dX, void* dXatt, float* dWa, float* dba, float* dWt, float* dbt,
+                                void* ws, size_t ws_bytes, int N, int P, int C, int Ca, int K, int M, unsigned flags,
+                                float keep_prob, uint64_t seed, uint64_t offset, int dtype, void* stream) {
+  M1Xent xf;
+  xf.labels = nullptr; xf.loss = loss; xf.G = G;
+  xf.lscale = xf.gscale = 0.f;
+  if (N > 0 && K > 0) ml_scales(ml.kind, loss_wt, grad_scale, N, K, &xf.lscale, &xf.gscale);
+  xf.done = false;
+  xf.kind = ml.kind; xf.mlabels = ml.labels; xf.pos_weight = ml.pos_weight;
+  M1Xent* const xp = M == 1 ? &xf : nullptr;
+  int rc = attn_pool_fwd_impl(hk, nullptr, xp, X, Xatt, Wa, ba, Wt, bt, logits, att, zsave, abar, nullptr, ws,
+                              ws_bytes, N, P, C, Ca, K, M, flags, keep_prob, seed, offset, dtype, stream);
+  if (rc != APA_OK) return rc;
+  if (!xf.done) {
+    rc = ml_loss_rows(ml.kind, ml.labels, ml.pos_weight, logits, loss, G, N, K, loss_wt, grad_scale,
+                      static_cast<hipStream_t>(stream));
+    if (rc != APA_OK) return rc;
+  }
+  return attn_pool_bwd_impl(hk, nullptr, xf.done && !xf.finished ? &xf : nullptr, X, Xatt, Wa, ba, Wt, bt, att, zsave,
+                            abar, G, dX, dXatt, dWa, dba, dWt, dbt, ws, ws_bytes, N, P, C, Ca, K, M,
+                            flags | APA_FLAG_WS_FROM_FWD, keep_prob, seed, offset, dtype, stream);
+}
+
 extern "C" int apa_attn_head_train_step_ex(const apa_hooks* hooks, const void* X, const void* Xatt,
                                            const float* Wa, const float* ba, const float* Wt,
                                            const float* bt, const int64_t* labels, float loss_wt,
@@ -406,15 +450,20 @@ extern "C" int apa_attn_head_train_step(const void* X, const void* Xatt, const f
                                      N, P, C, Ca, K, M, flags, keep_prob, seed, offset, dtype, stream);
 }
 
-extern "C" int apa_pose_attn_train_step(const apa_pose_attn_step_io* io, int N, int P, int C, int Cp, int J,
-                                        int K, unsigned flags, float keep_prob, uint64_t seed, uint64_t offset,
-                                        int dtype, void* stream) {
+// ml: the sigmoid action loss of apa_pose_attn_train_step_multilabel (io->labels unused), null: the softmax
+// cross-entropy on io->labels.  The multi-label form promises the bits of the separate calls (apa.h), so it runs the
+// four-call sequence for every shape, as the clip form does: the launches the fast bf16 route shares between
+// neighbouring ops sum in other orders than the per-op kernels (att moves by 2.5e-7, logits 4.4e-7, dWa 9.4e-7).  The
+// loss still rides in the logits reducer inside apa_attn_head_train_step_multilabel.
+static int pose_attn_step(const apa_multilabel* ml, const apa_pose_attn_step_io* io, int N, int P, int C, int Cp,
+                          int J, int K, unsigned flags, float keep_prob, uint64_t seed, uint64_t offset, int dtype,
+                          void* stream) {
   if (!io) {
     set_error("apa_pose_attn_train_step: null io");
     return APA_ERR_INVALID_ARG;
   }
   const apa_pose_attn_step_io& s = *io;
-  if (!s.X || !s.W1 || !s.b1 || !s.W2 || !s.b2 || !s.Wa || !s.ba || !s.Wt || !s.bt || !s.labels ||
+  if (!s.X || !s.W1 || !s.b1 || !s.W2 || !s.b2 || !s.Wa || !s.ba || !s.Wt || !s.bt || (!ml && !s.labels) ||
       !s.pose_labels || !s.pose_valid || !s.Ppre || !s.Pl || !s.att || !s.logits || !s.zsave || !s.abar ||
       !s.loss_action || !s.loss_pose || !s.G || !s.dPl || !s.dZ || !s.dX || !s.dW1 || !s.db1 || !s.dW2 || !s.db2 ||
       !s.dWa || !s.dba || !s.dWt || !s.dbt || !s.ws_pool || !s.ws_pose) {
@@ -435,7 +484,7 @@ extern "C" int apa_pose_attn_train_step(const apa_pose_attn_step_io* io, int N, 
   flags &= APA_PUBLIC_FLAGS & ~(APA_FLAG_WS_FROM_FWD | APA_FLAG_DXATT_RANK1);
   hipStream_t st = static_cast<hipStream_t>(stream);
   const bool train = (flags & APA_FLAG_TRAIN) && keep_prob < 1.0f;
-  const bool fast = pose_step_fast_ok(N, P, C, Cp, J, dtype, s.Ppre, s.W2, s.Wa) && m1_supported(C, Cp, dtype, false) &&
+  const bool fast = !ml && pose_step_fast_ok(N, P, C, Cp, J, dtype, s.Ppre, s.W2, s.Wa) && m1_supported(C, Cp, dtype, false) &&
                     m1_small_route_ok(C, K, s.G, s.Wt, s.zsave);
   if (!fast) {
     // the same step as four calls (what a caller without this entry point runs)
@@ -446,7 +495,12 @@ extern "C" int apa_pose_attn_train_step(const apa_pose_attn_step_io* io, int N, 
                                   pose_ws_loss_scratch(s.ws_pose, N, P, C, Cp, J, dtype),
                                   apa_pose_l2_workspace_bytes(N, P, J), N, P, J, s.pose_wt, s.grad_scale, stream);
     if (rc != APA_OK) return rc;
-    rc = apa_attn_head_train_step_ex(nullptr, s.X, s.Ppre, s.Wa, s.ba, s.Wt, s.bt, s.labels, s.action_wt,
+    rc = ml ? apa_attn_head_train_step_multilabel(ml, nullptr, nullptr, s.X, s.Ppre, s.Wa, s.ba, s.Wt, s.bt,
+                                                  s.action_wt, s.grad_scale, s.logits, s.att, s.zsave, s.abar,
+                                                  s.loss_action, s.G, s.dX, s.dZ, s.dWa, s.dba, s.dWt, s.dbt,
+                                                  s.ws_pool, s.ws_pool_bytes, N, P, C, Cp, K, 1,
+                                                  flags | APA_FLAG_DXATT_RANK1, keep_prob, seed, offset, dtype, stream)
+            : apa_attn_head_train_step_ex(nullptr, s.X, s.Ppre, s.Wa, s.ba, s.Wt, s.bt, s.labels, s.action_wt,
                                      s.grad_scale, s.logits, s.att, s.zsave, s.abar, s.loss_action, s.G, s.dX,
                                      s.dZ, s.dWa, s.dba, s.dWt, s.dbt, s.ws_pool, s.ws_pool_bytes, N, P, C, Cp, K,
                                      1, flags | APA_FLAG_DXATT_RANK1, keep_prob, seed, offset, dtype, stream);
@@ -514,6 +568,12 @@ extern "C" int apa_pose_attn_train_step(const apa_pose_attn_step_io* io, int N, 
                         s.db2, s.dWa, s.dba, s.loss_pose, bump, s.ws_pose, s.ws_pose_bytes, N, P, C, Cp, J, dtype, a, st);
 }
 
+extern "C" int apa_pose_attn_train_step(const apa_pose_attn_step_io* io, int N, int P, int C, int Cp, int J,
+                                        int K, unsigned flags, float keep_prob, uint64_t seed, uint64_t offset,
+                                        int dtype, void* stream) {
+  return pose_attn_step(nullptr, io, N, P, C, Cp, J, K, flags, keep_prob, seed, offset, dtype, stream);
+}
+
 // ---- the one-call steps on a batch of clips (apa.h: apa_clip_pool) -------------------------------------------------
 // the pooling workspace, then the clip loss's scratch
 static size_t clip_step_pool_bytes(int N, int P, int C, int Ca, int K, int M, unsigned flags) {
@@ -529,7 +589,7 @@ extern "C" size_t apa_clip_step_workspace_bytes(int N, int frames, int P, int C,
 }
 
 // everything apa_clip_xent_fwd_bwd would refuse, BEFORE the forward half is launched; *clip_ws: the loss's scratch
-static int clip_step_check(const char* fn, const apa_clip_pool* clip, const int64_t* labels, const float* loss,
+static int clip_step_check(const char* fn, const apa_clip_pool* clip, const void* labels, const float* loss,
                            const float* logits, const float* G, void* ws, size_t ws_bytes, int N, int P, int C,
                            int Ca, int K, int M, unsigned flags, int dtype, size_t* pool_bytes) {
   if (!clip || !labels || !loss || !logits || !G) {
@@ -555,12 +615,45 @@ static int clip_step_check(const char* fn, const apa_clip_pool* clip, const int6
   return APA_OK;
 }
 
-static int clip_step_loss(const apa_clip_pool& c, const float* logits, const int64_t* labels, float* loss, float* G,
-                          void* ws, size_t pool_bytes, int N, int K, float wt, float grad_scale, void* stream) {
+static int clip_step_loss(const apa_multilabel* ml, const apa_clip_pool& c, const float* logits, const int64_t* labels,
+                          float* loss, float* G, void* ws, size_t pool_bytes, int N, int K, float wt, float grad_scale,
+                          void* stream) {
   const int B = N / c.frames;
+  if (ml)
+    return apa_clip_multilabel_fwd_bwd(ml, logits, c.w, c.b, c.pooled, c.tatt, loss, G, c.dw, c.db,
+                                       static_cast<char*>(ws) + pool_bytes,
+                                       apa_clip_xent_workspace_bytes(B, c.frames, K), B, c.frames, K, wt, grad_scale,
+                                       stream);
   return apa_clip_xent_fwd_bwd(logits, labels, c.w, c.b, c.pooled, c.tatt, loss, G, c.dw, c.db,
                                static_cast<char*>(ws) + pool_bytes, apa_clip_xent_workspace_bytes(B, c.frames, K), B,
                                c.frames, K, wt, grad_scale, stream);
+}
+
+// fn: the entry point's name for the refusals; ml: the sigmoid clip loss (labels unused), null: the cross-entropy
+static int head_step_clips(const char* fn, const apa_multilabel* ml, const apa_clip_pool* clip, const apa_hooks* hooks,
+                           const void* X, const void* Xatt, const float* Wa, const float* ba, const float* Wt,
+                           const float* bt, const int64_t* labels, float loss_wt, float grad_scale, float* logits,
+                           float* att, float* zsave, float* abar, float* loss, float* G, void* dX, void* dXatt,
+                           float* dWa, float* dba, float* dWt, float* dbt, void* ws, size_t ws_bytes, int N, int P,
+                           int C, int Ca, int K, int M, unsigned flags, float keep_prob, uint64_t seed,
+                           uint64_t offset, int dtype, void* stream) {
+  const Hooks hk(hooks);
+  flags &= APA_PUBLIC_FLAGS;
+  size_t pool_bytes = 0;
+  int rc = clip_step_check(fn, clip, ml ? static_cast<const void*>(ml->labels) : labels, loss, logits, G, ws, ws_bytes,
+                           N, P, C, Ca, K, M, flags, dtype, &pool_bytes);
+  if (rc != APA_OK) return rc;
+  // the per-image cross-entropy the flat step folds into its neighbours (M1Xent) has no place here: the loss is
+  // taken on the pooled rows, so both halves run as the per-op entry points do and G travels through memory
+  rc = attn_pool_fwd_impl(hk, nullptr, nullptr, X, Xatt, Wa, ba, Wt, bt, logits, att, zsave, abar, nullptr, ws,
+                          pool_bytes, N, P, C, Ca, K, M, flags, keep_prob, seed, offset, dtype, stream);
+  if (rc != APA_OK) return rc;
+  rc = clip_step_loss(ml, *clip, logits, labels, loss, G, ws, pool_bytes, N, K, loss_wt, grad_scale, stream);
+  if (rc != APA_OK) return rc;
+  // same workspace, nothing in between (the loss's scratch lies behind it)
+  return attn_pool_bwd_impl(hk, nullptr, nullptr, X, Xatt, Wa, ba, Wt, bt, att, zsave, abar, G, dX, dXatt, dWa, dba,
+                            dWt, dbt, ws, pool_bytes, N, P, C, Ca, K, M, flags | APA_FLAG_WS_FROM_FWD, keep_prob, seed,
+                            offset, dtype, stream);
 }
 
 extern "C" int apa_attn_head_train_step_clips(const apa_clip_pool* clip, const apa_hooks* hooks, const void* X,
@@ -572,35 +665,45 @@ extern "C" int apa_attn_head_train_step_clips(const apa_clip_pool* clip, const a
                                               size_t ws_bytes, int N, int P, int C, int Ca, int K, int M,
                                               unsigned flags, float keep_prob, uint64_t seed, uint64_t offset,
                                               int dtype, void* stream) {
-  const Hooks hk(hooks);
-  flags &= APA_PUBLIC_FLAGS;
-  size_t pool_bytes = 0;
-  int rc = clip_step_check("apa_attn_head_train_step_clips", clip, labels, loss, logits, G, ws, ws_bytes, N, P, C, Ca,
-                           K, M, flags, dtype, &pool_bytes);
+  return head_step_clips("apa_attn_head_train_step_clips", nullptr, clip, hooks, X, Xatt, Wa, ba, Wt, bt, labels,
+                         loss_wt, grad_scale, logits, att, zsave, abar, loss, G, dX, dXatt, dWa, dba, dWt, dbt, ws,
+                         ws_bytes, N, P, C, Ca, K, M, flags, keep_prob, seed, offset, dtype, stream);
+}
+
+extern "C" int apa_attn_head_train_step_multilabel(const apa_multilabel* ml, const apa_clip_pool* clip,
+                                                   const apa_hooks* hooks, const void* X, const void* Xatt,
+                                                   const float* Wa, const float* ba, const float* Wt, const float* bt,
+                                                   float loss_wt, float grad_scale, float* logits, float* att,
+                                                   float* zsave, float* abar, float* loss, float* G, void* dX,
+                                                   void* dXatt, float* dWa, float* dba, float* dWt, float* dbt,
+                                                   void* ws, size_t ws_bytes, int N, int P, int C, int Ca, int K,
+                                                   int M, unsigned flags, float keep_prob, uint64_t seed,
+                                                   uint64_t offset, int dtype, void* stream) {
+  const int rc = check_multilabel("apa_attn_head_train_step_multilabel", ml);
   if (rc != APA_OK) return rc;
-  // the per-image cross-entropy the flat step folds into its neighbours (M1Xent) has no place here: the loss is
-  // taken on the pooled rows, so both halves run as the per-op entry points do and G travels through memory
-  rc = attn_pool_fwd_impl(hk, nullptr, nullptr, X, Xatt, Wa, ba, Wt, bt, logits, att, zsave, abar, nullptr, ws,
-                          pool_bytes, N, P, C, Ca, K, M, flags, keep_prob, seed, offset, dtype, stream);
-  if (rc != APA_OK) return rc;
-  rc = clip_step_loss(*clip, logits, labels, loss, G, ws, pool_bytes, N, K, loss_wt, grad_scale, stream);
-  if (rc != APA_OK) return rc;
-  // same workspace, nothing in between (the loss's scratch lies behind it)
-  return attn_pool_bwd_impl(hk, nullptr, nullptr, X, Xatt, Wa, ba, Wt, bt, att, zsave, abar, G, dX, dXatt, dWa, dba,
-                            dWt, dbt, ws, pool_bytes, N, P, C, Ca, K, M, flags | APA_FLAG_WS_FROM_FWD, keep_prob, seed,
-                            offset, dtype, stream);
+  if (clip)
+    return head_step_clips("apa_attn_head_train_step_multilabel", ml, clip, hooks, X, Xatt, Wa, ba, Wt, bt, nullptr,
+                           loss_wt, grad_scale, logits, att, zsave, abar, loss, G, dX, dXatt, dWa, dba, dWt, dbt, ws,
+                           ws_bytes, N, P, C, Ca, K, M, flags, keep_prob, seed, offset, dtype, stream);
+  if (!loss || !G) {
+    set_error("apa_attn_head_train_step_multilabel: null loss / G pointer");
+    return APA_ERR_INVALID_ARG;
+  }
+  return head_step_multilabel(*ml, Hooks(hooks), X, Xatt, Wa, ba, Wt, bt, loss_wt, grad_scale, logits, att, zsave,
+                              abar, loss, G, dX, dXatt, dWa, dba, dWt, dbt, ws, ws_bytes, N, P, C, Ca, K, M,
+                              flags & APA_PUBLIC_FLAGS, keep_prob, seed, offset, dtype, stream);
 }
 
 // apa_pose_attn_train_step's composed route with the clip loss in place of the per-image cross-entropy
-extern "C" int apa_pose_attn_train_step_clips(const apa_clip_pool* clip, const apa_pose_attn_step_io* io, int N, int P,
-                                              int C, int Cp, int J, int K, unsigned flags, float keep_prob,
-                                              uint64_t seed, uint64_t offset, int dtype, void* stream) {
+static int pose_attn_step_clips(const apa_multilabel* ml, const apa_clip_pool* clip, const apa_pose_attn_step_io* io,
+                                int N, int P, int C, int Cp, int J, int K, unsigned flags, float keep_prob,
+                                uint64_t seed, uint64_t offset, int dtype, void* stream) {
   if (!io) {
     set_error("apa_pose_attn_train_step_clips: null io");
     return APA_ERR_INVALID_ARG;
   }
   const apa_pose_attn_step_io& s = *io;
-  if (!s.X || !s.W1 || !s.b1 || !s.W2 || !s.b2 || !s.Wa || !s.ba || !s.Wt || !s.bt || !s.labels ||
+  if (!s.X || !s.W1 || !s.b1 || !s.W2 || !s.b2 || !s.Wa || !s.ba || !s.Wt || !s.bt || (!ml && !s.labels) ||
       !s.pose_labels || !s.pose_valid || !s.Ppre || !s.Pl || !s.att || !s.logits || !s.zsave || !s.abar ||
       !s.loss_action || !s.loss_pose || !s.G || !s.dPl || !s.dZ || !s.dX || !s.dW1 || !s.db1 || !s.dW2 || !s.db2 ||
       !s.dWa || !s.dba || !s.dWt || !s.dbt || !s.ws_pool || !s.ws_pose) {
@@ -618,7 +721,8 @@ extern "C" int apa_pose_attn_train_step_clips(const apa_clip_pool* clip, const a
   }
   flags &= APA_PUBLIC_FLAGS & ~(APA_FLAG_WS_FROM_FWD | APA_FLAG_DXATT_RANK1);
   size_t pool_bytes = 0;
-  int rc = clip_step_check("apa_pose_attn_train_step_clips", clip, s.labels, s.loss_action, s.logits, s.G, s.ws_pool,
+  int rc = clip_step_check("apa_pose_attn_train_step_clips", clip,
+                           ml ? static_cast<const void*>(ml->labels) : s.labels, s.loss_action, s.logits, s.G, s.ws_pool,
                            s.ws_pool_bytes, N, P, C, Cp, K, 1, flags, dtype, &pool_bytes);
   if (rc != APA_OK) return rc;
   // The four calls a caller without this entry point runs, for EVERY shape.  The launches apa_pose_attn_train_step
@@ -633,13 +737,29 @@ extern "C" int apa_pose_attn_train_step_clips(const apa_clip_pool* clip, const a
                                 pose_ws_loss_scratch(s.ws_pose, N, P, C, Cp, J, dtype),
                                 apa_pose_l2_workspace_bytes(N, P, J), N, P, J, s.pose_wt, s.grad_scale, stream);
   if (rc != APA_OK) return rc;
-  rc = apa_attn_head_train_step_clips(clip, nullptr, s.X, s.Ppre, s.Wa, s.ba, s.Wt, s.bt, s.labels, s.action_wt,
-                                      s.grad_scale, s.logits, s.att, s.zsave, s.abar, s.loss_action, s.G, s.dX, s.dZ,
-                                      s.dWa, s.dba, s.dWt, s.dbt, s.ws_pool, s.ws_pool_bytes, N, P, C, Cp, K, 1,
-                                      flags | APA_FLAG_DXATT_RANK1, keep_prob, seed, offset, dtype, stream);
+  rc = head_step_clips("apa_pose_attn_train_step_clips", ml, clip, nullptr, s.X, s.Ppre, s.Wa, s.ba, s.Wt, s.bt,
+                       s.labels, s.action_wt, s.grad_scale, s.logits, s.att, s.zsave, s.abar, s.loss_action, s.G, s.dX,
+                       s.dZ, s.dWa, s.dba, s.dWt, s.dbt, s.ws_pool, s.ws_pool_bytes, N, P, C, Cp, K, 1,
+                       flags | APA_FLAG_DXATT_RANK1, keep_prob, seed, offset, dtype, stream);
   if (rc != APA_OK) return rc;
   return apa_pose_head_bwd_rank1ext(s.X, s.W1, s.W2, s.Ppre, s.dPl, s.dZ, s.Wa, s.dX, 1 | APA_POSE_WS_FROM_FWD, s.dW1,
                                     s.db1, s.dW2, s.db2, s.ws_pose, s.ws_pose_bytes, N, P, C, Cp, J, dtype, stream);
+}
+
+extern "C" int apa_pose_attn_train_step_clips(const apa_clip_pool* clip, const apa_pose_attn_step_io* io, int N, int P,
+                                              int C, int Cp, int J, int K, unsigned flags, float keep_prob,
+                                              uint64_t seed, uint64_t offset, int dtype, void* stream) {
+  return pose_attn_step_clips(nullptr, clip, io, N, P, C, Cp, J, K, flags, keep_prob, seed, offset, dtype, stream);
+}
+
+extern "C" int apa_pose_attn_train_step_multilabel(const apa_multilabel* ml, const apa_clip_pool* clip,
+                                                   const apa_pose_attn_step_io* io, int N, int P, int C, int Cp,
+                                                   int J, int K, unsigned flags, float keep_prob, uint64_t seed,
+                                                   uint64_t offset, int dtype, void* stream) {
+  const int rc = check_multilabel("apa_pose_attn_train_step_multilabel", ml);
+  if (rc != APA_OK) return rc;
+  return clip ? pose_attn_step_clips(ml, clip, io, N, P, C, Cp, J, K, flags, keep_prob, seed, offset, dtype, stream)
+              : pose_attn_step(ml, io, N, P, C, Cp, J, K, flags, keep_prob, seed, offset, dtype, stream);
 }
 
 extern "C" int apa_per_class_weight_images(const float* Wa, const float* ba, const float* Wt, const float* bt, void* ws,

@@ -30,6 +30,11 @@
 //   K >  4096        they live in memory: the pooled row in its output, the gradient row in the workspace
 // so that with F == 1 and no temporal attention (pooled = x * 1, G = g * 1) loss and G carry the very bits
 // apa_softmax_xent_fwd_bwd gives.  No atomics; every sum has one order: identical calls give identical bits.
+//
+// ML (apa_clip_multilabel_fwd_bwd): the sigmoid losses of src/loss.py:88-101 in place of the softmax row -- labels are
+// f32 multi-hot [B,K], loss[1+b] = (1/K) sum_k l(pooled[b,k], t[b,k]), g[b,k] = wt grad_scale/(B K) l' -- by ml_row
+// (apa_device.h) on the whole block, for every K; pooling, tatt, G, d, dw / db, the row placement and launch 2 are the
+// softmax form's.  With F == 1 and no temporal attention: apa_multilabel_loss_fwd_bwd's bits.
 #include <math.h>
 
 #include "apa_device.h"
@@ -41,12 +46,13 @@ constexpr int CLIP_LDS_K = 4096;   // pooled + gradient rows in LDS up to this K
 constexpr int CLIP_LDS_F = 64;     // a[b, :] in LDS up to this F (else re-read from tatt)
 
 // dynamic LDS: [row_floats] pooled row | [row_floats] gradient row | [CLIP_LDS_F] a | [4] xent scratch
-template <bool TEMPORAL>
+template <bool TEMPORAL, bool ML>
 __global__ __launch_bounds__(256) void clip_xent_kernel(
-    const float* __restrict__ x, const int64_t* __restrict__ labels, const float* __restrict__ w,
+    const float* __restrict__ x, const void* __restrict__ labels_any, const float* __restrict__ w,
     const float* __restrict__ b0, float* __restrict__ pooled, float* __restrict__ tatt,
     float* __restrict__ loss, float* __restrict__ G, float* __restrict__ dws, float* __restrict__ gws,
-    int F, int K, int row_floats, float gscale) {
+    int F, int K, int row_floats, float gscale, int kind, float pw) {
+  const int64_t* __restrict__ labels = static_cast<const int64_t*>(labels_any);
   extern __shared__ __attribute__((aligned(16))) float clip_sm[];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int b = blockIdx.x;
@@ -88,7 +94,11 @@ __global__ __launch_bounds__(256) void clip_xent_kernel(
   }
   __syncthreads();
 
-  if (wave == 0) {   // the pooled row's cross-entropy: loss[1+b] and the gradient row
+  if (ML) {   // the pooled row's sigmoid loss, on the whole block: loss[1+b] and the gradient row
+    const float s = ml_row<0>([&](int, int k) { return prow[k]; }, static_cast<const float*>(labels_any) + (size_t)b * K,
+                              grow, K, kind, pw, gscale, sx);
+    if (threadIdx.x == 0) loss[1 + b] = s;
+  } else if (wave == 0) {   // the pooled row's cross-entropy: loss[1+b] and the gradient row
     if (K >= 4 && K <= 1024) {
       // a one-row problem for the shared row routine: row 0 of (labels + b, sx, grow)
       const PcXent xe = {labels + b, sx, grow, gscale};
@@ -199,9 +209,61 @@ static size_t clip_ws_floats(int B, int F, int K, bool temporal, size_t* off_g) 
   return nd + (K > CLIP_LDS_K ? (size_t)B * K : 0);
 }
 
+int clip_loss_finish(const float* x, const float* dws, float* loss, float* dw, float* db, int B, int rows, int K,
+                     float lscale, hipStream_t st) {
+  const int nb = 1 + (dws ? (K + 255) / 256 : 0);
+  hipLaunchKernelGGL(clip_finish_kernel, dim3(nb), dim3(256), 0, st, x, dws, loss, dw, db, B, rows, K, lscale);
+  APA_LAUNCH_CHECK("clip_finish_kernel");
+  return APA_OK;
+}
+
 }  // namespace apa
 
 using namespace apa;
+
+// both launches; ml: the sigmoid form (labels f32 [B,K]), null: the softmax cross-entropy (labels int64 [B])
+static int clip_loss_launch(const char* fn, const apa_multilabel* ml, const float* logits, const void* labels,
+                            const float* w, const float* b, float* pooled, float* tatt, float* loss, float* G,
+                            float* dw, float* db, void* ws, size_t ws_bytes, int B, int F, int K, float wt,
+                            float grad_scale, void* stream) {
+  if (B <= 0 || F <= 0 || K <= 0 || (int64_t)B * F > INT32_MAX) {
+    set_error("%s: non-positive size or B*F past 2^31 (B=%d F=%d K=%d)", fn, B, F, K);
+    return APA_ERR_INVALID_ARG;
+  }
+  if (!logits || !labels || !pooled || !loss || !G || (w && (!b || !tatt || !dw || !db))) {
+    set_error("%s: null pointer (temporal attention needs b, tatt, dw and db)", fn);
+    return APA_ERR_INVALID_ARG;
+  }
+  const bool temporal = w != nullptr;
+  size_t off_g = 0;
+  const size_t need = clip_ws_floats(B, F, K, temporal, &off_g) * sizeof(float);
+  if (need && (!ws || ws_bytes < need || (reinterpret_cast<uintptr_t>(ws) & 3))) {
+    set_error("%s: workspace too small or misaligned (%zu < %zu)", fn, ws_bytes, need);
+    return APA_ERR_WORKSPACE;
+  }
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  float* dws = temporal ? static_cast<float*>(ws) : nullptr;
+  float* gws = K > CLIP_LDS_K ? static_cast<float*>(ws) + off_g : nullptr;
+  const int row_floats = K > CLIP_LDS_K ? 0 : (K + 3) / 4 * 4;
+  const size_t shm = (size_t)(2 * row_floats + CLIP_LDS_F + 4) * sizeof(float);
+  // the same two factors as apa_softmax_xent_fwd_bwd (ml: apa_multilabel_loss_fwd_bwd), over the B clips
+  float lscale = wt / (float)B;
+  float gscale = wt * grad_scale / (float)B;
+  const int kind = ml ? ml->kind : 0;
+  const float pw = ml ? ml->pos_weight : 1.f;
+  if (ml) ml_scales(kind, wt, grad_scale, B, K, &lscale, &gscale);
+#define APA_CX(T, M)                                                                                                 \
+  hipLaunchKernelGGL((clip_xent_kernel<T, M>), dim3(B), dim3(256), shm, st, logits, labels, w, b, pooled, tatt, loss, \
+                     G, dws, gws, F, K, row_floats, gscale, kind, pw)
+  if (ml) {
+    if (temporal) APA_CX(true, true); else APA_CX(false, true);
+  } else {
+    if (temporal) APA_CX(true, false); else APA_CX(false, false);
+  }
+#undef APA_CX
+  APA_LAUNCH_CHECK("clip_xent_kernel");
+  return clip_loss_finish(logits, dws, loss, dw, db, B, B * F, K, lscale, st);
+}
 
 extern "C" size_t apa_clip_xent_workspace_bytes(int B, int F, int K) {
   if (B <= 0 || F <= 0 || K <= 0 || (int64_t)B * F > INT32_MAX) return 0;
@@ -213,38 +275,22 @@ extern "C" int apa_clip_xent_fwd_bwd(const float* logits, const int64_t* labels,
                                      float* pooled, float* tatt, float* loss, float* G, float* dw, float* db,
                                      void* ws, size_t ws_bytes, int B, int F, int K, float wt, float grad_scale,
                                      void* stream) {
-  if (B <= 0 || F <= 0 || K <= 0 || (int64_t)B * F > INT32_MAX) {
-    set_error("apa_clip_xent_fwd_bwd: non-positive size or B*F past 2^31 (B=%d F=%d K=%d)", B, F, K);
+  return clip_loss_launch("apa_clip_xent_fwd_bwd", nullptr, logits, labels, w, b, pooled, tatt, loss, G, dw, db, ws,
+                          ws_bytes, B, F, K, wt, grad_scale, stream);
+}
+
+extern "C" int apa_clip_multilabel_fwd_bwd(const apa_multilabel* ml, const float* logits, const float* w,
+                                           const float* b, float* pooled, float* tatt, float* loss, float* G,
+                                           float* dw, float* db, void* ws, size_t ws_bytes, int B, int F, int K,
+                                           float wt, float grad_scale, void* stream) {
+  if (!ml || !ml->labels) {
+    set_error("apa_clip_multilabel_fwd_bwd: null apa_multilabel / labels pointer");
     return APA_ERR_INVALID_ARG;
   }
-  if (!logits || !labels || !pooled || !loss || !G || (w && (!b || !tatt || !dw || !db))) {
-    set_error("apa_clip_xent_fwd_bwd: null pointer (temporal attention needs b, tatt, dw and db)");
+  if (ml->kind != APA_ACTION_LOSS_MULTI_LABEL && ml->kind != APA_ACTION_LOSS_MULTI_LABEL_2) {
+    set_error("apa_clip_multilabel_fwd_bwd: unknown loss kind %d", ml->kind);
     return APA_ERR_INVALID_ARG;
   }
-  const bool temporal = w != nullptr;
-  size_t off_g = 0;
-  const size_t need = clip_ws_floats(B, F, K, temporal, &off_g) * sizeof(float);
-  if (need && (!ws || ws_bytes < need || (reinterpret_cast<uintptr_t>(ws) & 3))) {
-    set_error("apa_clip_xent_fwd_bwd: workspace too small or misaligned (%zu < %zu)", ws_bytes, need);
-    return APA_ERR_WORKSPACE;
-  }
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  float* dws = temporal ? static_cast<float*>(ws) : nullptr;
-  float* gws = K > CLIP_LDS_K ? static_cast<float*>(ws) + off_g : nullptr;
-  const int row_floats = K > CLIP_LDS_K ? 0 : (K + 3) / 4 * 4;
-  const size_t shm = (size_t)(2 * row_floats + CLIP_LDS_F + 4) * sizeof(float);
-  // the same two factors as apa_softmax_xent_fwd_bwd, over the B clips
-  const float lscale = wt / (float)B;
-  const float gscale = wt * grad_scale / (float)B;
-  if (temporal)
-    hipLaunchKernelGGL(clip_xent_kernel<true>, dim3(B), dim3(256), shm, st, logits, labels, w, b, pooled, tatt, loss,
-                       G, dws, gws, F, K, row_floats, gscale);
-  else
-    hipLaunchKernelGGL(clip_xent_kernel<false>, dim3(B), dim3(256), shm, st, logits, labels, w, b, pooled, tatt,
-                       loss, G, dws, gws, F, K, row_floats, gscale);
-  APA_LAUNCH_CHECK("clip_xent_kernel");
-  const int nb = 1 + (temporal ? (K + 255) / 256 : 0);
-  hipLaunchKernelGGL(clip_finish_kernel, dim3(nb), dim3(256), 0, st, logits, dws, loss, dw, db, B, B * F, K, lscale);
-  APA_LAUNCH_CHECK("clip_finish_kernel");
-  return APA_OK;
+  return clip_loss_launch("apa_clip_multilabel_fwd_bwd", ml, logits, ml->labels, w, b, pooled, tatt, loss, G, dw, db,
+                          ws, ws_bytes, B, F, K, wt, grad_scale, stream);
 }

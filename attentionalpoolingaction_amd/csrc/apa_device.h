@@ -489,4 +489,86 @@ __device__ __forceinline__ void pc_row_xent_any(const float* __restrict__ row, i
   }
 }
 
+// (apa_m1_small.hip's reducers and apa_mlloss.hip's share these)
+// abar[n] = (sum_s pstat[n,s,2]) / P on the folded route (S <= 16), bit for bit as m1_finalize_fwd_kernel forms it
+// (apa_m1.hip): one split per thread of a 256-thread block, wave_sum, then (s0 + s1) + (s2 + s3) over the four waves.
+// With S <= 16 the splits sit on the first DPP row of wave 0; every other row and wave sums zeros.
+//   m1_abar_wave:   the same on any one wave (lanes >= S hold 0); the result is wave-uniform
+//   m1_abar_thread: wave_sum's tree over that row written out for one thread (row_sum16: lane ^ 1, lane ^ 2, the
+//                   two quads of a half row, the two half rows; lane 0's value)
+__device__ __forceinline__ float m1_abar_tail(float row0, int P) {
+  const float w0 = (row0 + 0.f) + (0.f + 0.f);       // wave_sum: rows 1..3 of the wave
+  const float asum = (w0 + 0.f) + (0.f + 0.f);       // waves 1..3 of the block
+  return asum * (1.0f / (float)P);
+}
+__device__ __forceinline__ float m1_abar_wave(const float* __restrict__ pstat, int n, int S, int P, int lane) {
+  const float a_s = lane < S ? pstat[((size_t)n * S + lane) * 4 + 2] : 0.f;
+  const float w0 = wave_sum(a_s);
+  return ((w0 + 0.f) + (0.f + 0.f)) * (1.0f / (float)P);
+}
+__device__ __forceinline__ float m1_abar_thread(const float* __restrict__ pstat, int n, int S, int P) {
+  float a[16];
+#pragma unroll
+  for (int u = 0; u < 16; ++u) a[u] = pstat[((size_t)n * S + min(u, S - 1)) * 4 + 2];
+#pragma unroll
+  for (int u = 0; u < 16; ++u) a[u] = u < S ? a[u] : 0.f;
+  const float l0 = (a[0] + a[1]) + (a[2] + a[3]), l7 = (a[7] + a[6]) + (a[5] + a[4]);
+  const float l15 = (a[15] + a[14]) + (a[13] + a[12]), l8 = (a[8] + a[9]) + (a[10] + a[11]);
+  return m1_abar_tail((l0 + l7) + (l15 + l8), P);
+}
+
+// ---------------------------------------------------------------------------------------------
+// The sigmoid ("multi-label") action losses of one logits row, value + gradient (src/loss.py:88-101), shared by
+// every kernel that computes them (apa_mlloss.hip, apa_cliploss.hip) so that all routes agree bit for bit:
+//   kind APA_ACTION_LOSS_MULTI_LABEL (2), w = 1 + (pw - 1) t:
+//     l = (1 - t) x + w softplus(-x),   l' = (1 - t) - w (1 - sigmoid(x)),   softplus(-x) = log1p(exp(-|x|)) + max(-x, 0)
+//   kind APA_ACTION_LOSS_MULTI_LABEL_2 (3):
+//     l = max(x, 0) - x t + log1p(exp(-|x|)),   l' = sigmoid(x) - t
+// apa_action_loss_fwd_bwd's arithmetic (apa_loss2.hip), every operation rounded on its own (contraction off: the
+// compiler fuses a * b + c differently from one caller to the next, and the callers promise each other's bits).
+__device__ __forceinline__ void ml_term(int kind, float pw, float x, float t, float& l, float& d) {
+#pragma clang fp contract(off)
+  const float lp = log1pf(expf(-fabsf(x)));
+  const float sg = 1.0f / (1.0f + expf(-x));
+  if (kind == 2) {
+    const float w = 1.0f + (pw - 1.0f) * t;
+    const float a = (1.0f - t) * x, sp = lp + fmaxf(-x, 0.f);
+    l = a + w * sp;
+    d = (1.0f - t) - w * (1.0f - sg);
+  } else {
+    l = (fmaxf(x, 0.f) - x * t) + lp;
+    d = sg - t;
+  }
+}
+
+// One row on one 256-thread block: thread tid owns the columns tid + 256 j and takes them in increasing j
+// (xat(j, k): the logit of its j-th column k); gdst[k] = l'_k * gscale, the thread's l_k are added in that order, then
+// wave_sum and (w0 + w1) + (w2 + w3) over the four waves.  Returns (1/K) sum_k l_k in every thread.  MAXJ > 0: the
+// column loop is unrolled MAXJ times (K <= 256 MAXJ, logits in registers); 0: any K.  red: 4 floats of LDS; contains
+// block barriers, so every thread of the block calls it.
+template <int MAXJ, typename XF>
+__device__ __forceinline__ float ml_row(XF&& xat, const float* __restrict__ trow, float* gdst, int K, int kind,
+                                        float pw, float gscale, float* red) {
+  const int tid = threadIdx.x;
+  float acc = 0.f;
+  auto one = [&](int j, int k) {
+    float l, d;
+    ml_term(kind, pw, xat(j, k), trow[k], l, d);
+    gdst[k] = d * gscale;
+    acc += l;
+  };
+  if constexpr (MAXJ > 0) {
+#pragma unroll
+    for (int j = 0; j < MAXJ; ++j)
+      if (tid + 256 * j < K) one(j, tid + 256 * j);
+  } else {
+    for (int j = 0, k = tid; k < K; ++j, k += 256) one(j, k);
+  }
+  acc = wave_sum(acc);
+  __syncthreads();   // (red may still be read from a previous row)
+  if ((tid & 63) == 0) red[tid >> 6] = acc;
+  __syncthreads();
+  return ((red[0] + red[1]) + (red[2] + red[3])) / (float)K;
+}
+
 }  // namespace apa

@@ -226,7 +226,20 @@ struct M1Xent {
   // evaluation form (apa_attn_head_eval_step without ground truth): probabilities + argmax instead
   float* probs = nullptr;     // [N,K]
   int64_t* pred = nullptr;    // [N]
+  // sigmoid ("multi-label") action loss instead (apa_*_train_step_multilabel): kind = APA_ACTION_LOSS_MULTI_LABEL[_2],
+  // 0 = the softmax cross-entropy above; then `labels` is unused, gscale carries the 1/K of the mean over the classes
+  int kind = 0;
+  const float* mlabels = nullptr;   // f32 multi-hot [N,K]
+  float pos_weight = 1.f;
+  bool finished = false;   // (with done) loss[0] is final too: the backward head kernel has nothing to finish
 };
+// The two factors of a sigmoid action loss over n_loss rows of K classes: loss[0] = lscale * sum of the row means,
+// G = gscale * l'.  'multi-label' ignores the action-loss weight (loss.py:93-97 adds the bare mean).
+inline void ml_scales(int kind, float wt, float grad_scale, int n_loss, int K, float* lscale, float* gscale) {
+  const float w = kind == APA_ACTION_LOSS_MULTI_LABEL ? 1.0f : wt;
+  *lscale = w / (float)n_loss;
+  *gscale = w * grad_scale / ((float)n_loss * (float)K);
+}
 
 // ..._WITH_POSE_FEAT (nets_factory.py:289-295): J extra top-down channels (apa_m1_cat.hip)
 struct CatFeat {
@@ -250,7 +263,8 @@ M1Plan m1_plan(int N, int P, int C, int Ca, int K);
 // library).  The product never sets the pointer: m1_trace() is null there and nothing is recorded.
 enum M1Pool { M1_POOL_NONE = 0, M1_POOL_STREAM, M1_POOL_VEC, M1_POOL_GENERIC };
 // (4 was the retired partial-logits form; the values are part of the probe interface and stay put)
-enum M1Logits { M1_LOGITS_NONE = 0, M1_LOGITS_XENT, M1_LOGITS_XENT_PROBS, M1_LOGITS2, M1_LOGITS_SGEMM = 5 };
+enum M1Logits { M1_LOGITS_NONE = 0, M1_LOGITS_XENT, M1_LOGITS_XENT_PROBS, M1_LOGITS2, M1_LOGITS_SGEMM = 5,
+                M1_LOGITS_ML = 6 };
 enum M1Head { M1_HEAD_NONE = 0, M1_HEAD_TILES, M1_HEAD_ROWS, M1_HEAD_SMALL, M1_HEAD_SGEMM };
 enum M1Gemv { M1_GEMV_NONE = 0, M1_GEMV_BWD2, M1_GEMV_BWD2_RANK1, M1_GEMV_BWD };
 enum M1Reduce { M1_REDUCE_NONE = 0, M1_REDUCE_COLSUM, M1_REDUCE_BWD_REDUCE };
@@ -345,6 +359,21 @@ struct M1Fold { const float* pacc; const float* pstat; int S, P; };
 bool m1_logits2_fold_supported(int N, int C, int S);
 int m1_logits2(float* z, const float* Wt, float* abar, const float* bt, float* logits,
                float* part_ws, int N, int C, int K, hipStream_t st, const M1Fold* fold = nullptr);
+int m1_logits2_partials(float* z, const float* Wt, float* part_ws, int N, int C, int K, hipStream_t st,
+                        const M1Fold* fold, int* nparts);
+// apa_mlloss.hip: the sigmoid action losses.  The fold: partial logits, then reduce + the row's loss per image
+// (logits bit-identical to m1_logits2's; loss[0] is left to the backward head kernel, or to clip_loss_finish where
+// that kernel does not serve the shape -- m1_forward)
+bool m1_logits_ml_supported(int N, int C, int K);
+int m1_logits2_ml(float* z, const float* Wt, float* abar, const float* bt, const M1Xent& xf, float* logits,
+                  float* part_ws, int N, int C, int K, hipStream_t st, const M1Fold* fold);
+// the stand-alone form on finished logits: one block per row, then the batch sum (apa_multilabel_loss_fwd_bwd)
+int ml_loss_rows(int kind, const float* labels, float pos_weight, const float* logits, float* loss, float* G, int N,
+                 int K, float wt, float grad_scale, hipStream_t st);
+// apa_cliploss.hip: clip_finish_kernel -- loss[0] = lscale * sum_b loss[1+b] in the softmax step's order for (B, K);
+// with dws also db = sum dws and dw = dws^T x
+int clip_loss_finish(const float* x, const float* dws, float* loss, float* dw, float* db, int B, int rows, int K,
+                     float lscale, hipStream_t st);
 bool m1_bwd_head_supported(int N, int C, int K);
 int m1_bwd_head(const float* G, const float* Wt, const float* zsave, const float* abar,
                 const float* bt, float* dz, float* dWt, float* dbt, float* sn, int N, int C, int K,

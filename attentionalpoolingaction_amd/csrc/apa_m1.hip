@@ -476,7 +476,8 @@ int m1_forward(const M1Call& c, const M1Fwd& io, M1Xent* xf) {
   // steps), with the plain reducer, or the split-K product
   const bool xeval = xf && xf->probs;
   if (c.cat) xf = nullptr;   // the extra channels add to the logits after the reduction: no fused loss
-  const bool xroute = xf && m1_logits_xent_supported(N, C, K, xeval) &&
+  const bool ml = xf && xf->kind != 0;   // a sigmoid loss: its own reducer (apa_mlloss.hip), K <= 1024
+  const bool xroute = xf && (ml ? m1_logits_ml_supported(N, C, K) : m1_logits_xent_supported(N, C, K, xeval)) &&
                       m1_small_route_ok(C, K, xf->G, io.Wt, io.zsave, xeval);
   const bool l2route = m1_logits2_supported(C, K) && (reinterpret_cast<uintptr_t>(io.zsave) & 15) == 0;
   // The merge of the S block partials: in the partial-logits kernel's prologue where that is exact and within its
@@ -503,6 +504,16 @@ int m1_forward(const M1Call& c, const M1Fwd& io, M1Xent* xf) {
   if (c.td_ready) APA_HIP_CHECK(hipStreamWaitEvent(c.st, c.td_ready, 0));
   if (xroute) {
     // training: the same conditions under which m1_backward takes the head kernel, which finishes loss[0]
+    if (ml) {
+      if (tr) tr->logits = M1_LOGITS_ML;
+      rc = m1_logits2_ml(io.zsave, io.Wt, io.abar, io.bt, *xf, io.logits, c.gemm_ws, N, C, K, c.st, fold ? &mf : nullptr);
+      // loss[0]: the backward head kernel's where m1_backward will take it, else one small launch here (same order)
+      xf->finished = !m1_bwd_head_supported(N, C, K);
+      if (rc == APA_OK && xf->finished)
+        rc = clip_loss_finish(nullptr, nullptr, xf->loss, nullptr, nullptr, N, N, K, xf->lscale, c.st);
+      xf->done = rc == APA_OK;
+      return rc;
+    }
     if (tr) tr->logits = xeval ? M1_LOGITS_XENT_PROBS : M1_LOGITS_XENT;
     rc = m1_logits2_xent(io.zsave, io.Wt, io.abar, io.bt, xf->labels, io.logits, xf->loss, xf->G, xf->gscale,
                          xf->probs, xf->pred, c.gemm_ws, N, C, K, c.st, fold ? &mf : nullptr);

@@ -120,6 +120,20 @@ int apa_probe_m1_train_step_ex(apa::M1Trace* t, const apa_hooks* hooks, const vo
                                      flags, keep_prob, seed, offset, dtype, stream);
 }
 
+int apa_probe_m1_train_step_multilabel(apa::M1Trace* t, const apa_multilabel* ml, const apa_clip_pool* clip,
+                                       const apa_hooks* hooks, const void* X, const void* Xatt, const float* Wa,
+                                       const float* ba, const float* Wt, const float* bt, float loss_wt,
+                                       float grad_scale, float* logits, float* att, float* zsave, float* abar,
+                                       float* loss, float* G, void* dX, void* dXatt, float* dWa, float* dba,
+                                       float* dWt, float* dbt, void* ws, size_t ws_bytes, int N, int P, int C, int Ca,
+                                       int K, int M, unsigned flags, float keep_prob, uint64_t seed, uint64_t offset,
+                                       int dtype, void* stream) {
+  TraceScope s(t);
+  return apa_attn_head_train_step_multilabel(ml, clip, hooks, X, Xatt, Wa, ba, Wt, bt, loss_wt, grad_scale, logits,
+                                             att, zsave, abar, loss, G, dX, dXatt, dWa, dba, dWt, dbt, ws, ws_bytes, N,
+                                             P, C, Ca, K, M, flags, keep_prob, seed, offset, dtype, stream);
+}
+
 int apa_probe_m1_eval_step(apa::M1Trace* t, const void* X, const void* Xatt, const float* Wa, const float* ba,
                            const float* Wt, const float* bt, const int64_t* labels, float* logits, float* att,
                            float* zsave, float* abar, float* loss, float* probs, int64_t* pred, void* ws,

@@ -25,33 +25,6 @@ __device__ __forceinline__ f32x4 mfma16(float a, float b, f32x4 c) {
   return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
 }
 
-// abar[n] = (sum_s pstat[n,s,2]) / P on the folded route (S <= 16), bit for bit as m1_finalize_fwd_kernel forms it
-// (apa_m1.hip): one split per thread of a 256-thread block, wave_sum, then (s0 + s1) + (s2 + s3) over the four waves.
-// With S <= 16 the splits sit on the first DPP row of wave 0; every other row and wave sums zeros.
-//   m1_abar_wave:   the same on any one wave (lanes >= S hold 0); the result is wave-uniform
-//   m1_abar_thread: wave_sum's tree over that row written out for one thread (row_sum16: lane ^ 1, lane ^ 2, the
-//                   two quads of a half row, the two half rows; lane 0's value)
-__device__ __forceinline__ float m1_abar_tail(float row0, int P) {
-  const float w0 = (row0 + 0.f) + (0.f + 0.f);       // wave_sum: rows 1..3 of the wave
-  const float asum = (w0 + 0.f) + (0.f + 0.f);       // waves 1..3 of the block
-  return asum * (1.0f / (float)P);
-}
-__device__ __forceinline__ float m1_abar_wave(const float* __restrict__ pstat, int n, int S, int P, int lane) {
-  const float a_s = lane < S ? pstat[((size_t)n * S + lane) * 4 + 2] : 0.f;
-  const float w0 = wave_sum(a_s);
-  return ((w0 + 0.f) + (0.f + 0.f)) * (1.0f / (float)P);
-}
-__device__ __forceinline__ float m1_abar_thread(const float* __restrict__ pstat, int n, int S, int P) {
-  float a[16];
-#pragma unroll
-  for (int u = 0; u < 16; ++u) a[u] = pstat[((size_t)n * S + min(u, S - 1)) * 4 + 2];
-#pragma unroll
-  for (int u = 0; u < 16; ++u) a[u] = u < S ? a[u] : 0.f;
-  const float l0 = (a[0] + a[1]) + (a[2] + a[3]), l7 = (a[7] + a[6]) + (a[5] + a[4]);
-  const float l15 = (a[15] + a[14]) + (a[13] + a[12]), l8 = (a[8] + a[9]) + (a[10] + a[11]);
-  return m1_abar_tail((l0 + l7) + (l15 + l8), P);
-}
-
 // L2: logits[n,k] = sum_cc part[cc][n][k] + abar[n] * bt[k]   (fixed order over cc)
 // pstat (the folded route): abar is formed here from the pooling pass's statistics and stored for the backward pass
 __global__ __launch_bounds__(256) void m1_logits_reduce_kernel(const float* __restrict__ part, float* abar,
@@ -1070,6 +1043,14 @@ int m1_logits2(float* z, const float* Wt, float* abar, const float* bt, float* l
                      fold ? fold->S : 0, fold ? fold->P : 1);
   APA_LAUNCH_CHECK("m1_logits_reduce_kernel");
   return APA_OK;
+}
+
+// the partial-logits launch alone (folded or not), for a reducer that lives in another file (apa_mlloss.hip);
+// *nparts: how many partials per logit it left in part_ws
+int m1_logits2_partials(float* z, const float* Wt, float* part_ws, int N, int C, int K, hipStream_t st,
+                        const M1Fold* fold, int* nparts) {
+  *nparts = C / (64 * logits2_nsub(N, C));
+  return fold ? launch_logits2_fold(*fold, Wt, z, part_ws, N, C, K, st) : launch_logits2(z, Wt, part_ws, N, C, K, st);
 }
 
 bool m1_bwd_head_supported(int N, int C, int K);

@@ -90,6 +90,14 @@ _SIGNATURES = {
                                                                    c_void_p]),
     'apa_pose_attn_train_step_clips': (c_int, [c_void_p, c_void_p] + [c_int] * 6 + [c_uint, c_float, ctypes.c_uint64,
                                                                                     ctypes.c_uint64, c_int, c_void_p]),
+    # the sigmoid action losses take a `const apa_multilabel*` first (the steps: then `const apa_clip_pool*` or NULL)
+    'apa_multilabel_loss_fwd_bwd': (c_int, [c_void_p] * 4 + [c_int, c_int, c_float, c_float, c_void_p]),
+    'apa_clip_multilabel_fwd_bwd': (c_int, [c_void_p] * 11 + [c_size_t] + [c_int] * 3 + [c_float, c_float, c_void_p]),
+    'apa_attn_head_train_step_multilabel': (c_int, [c_void_p] * 9 + [c_float, c_float] + [c_void_p] * 13 +
+                                            [c_size_t] + [c_int] * 6 + [c_uint, c_float, c_uint64, c_uint64, c_int,
+                                                                        c_void_p]),
+    'apa_pose_attn_train_step_multilabel': (c_int, [c_void_p] * 3 + [c_int] * 6 + [c_uint, c_float, ctypes.c_uint64,
+                                                                                   ctypes.c_uint64, c_int, c_void_p]),
     'apa_attn_head_train_step': (c_int, [c_void_p] * 7 + [c_float, c_float] + [c_void_p] * 13 +
                                  [c_size_t] + [c_int] * 6 + [c_uint, c_float, c_uint64, c_uint64, c_int,
                                                              c_void_p]),
@@ -695,6 +703,52 @@ def action_loss_fwd_bwd(kind: str, logits, labels, *, wt=1.0, grad_scale=1.0, po
     return loss, G
 
 
+class ApaMultilabel(ctypes.Structure):
+    """`apa_multilabel` of include/apa.h: a sigmoid action loss (src/loss.py:88-101) and its f32 multi-hot labels."""
+    _fields_ = [('kind', c_int), ('labels', c_void_p), ('pos_weight', c_float)]
+
+
+STEP_ACTION_LOSSES = ('softmax-xentropy', 'multi-label', 'multi-label-2')
+
+
+def _multilabel_labels(who, labels, n_loss, K):
+    """The label tensor of a sigmoid action loss: float32 [n_loss, K] multi-hot (checked before anything else)."""
+    if labels.dtype != torch.float32 or labels.dim() != 2 or tuple(labels.shape) != (n_loss, K):
+        raise ApaError('{}: the multi-label losses take float32 multi-hot labels [{}, {}] (got {} {})'.format(
+            who, n_loss, K, labels.dtype, tuple(labels.shape)))
+    return labels
+
+
+def _bind_multilabel(who, action_loss, labels, n_loss, K, pos_weight):
+    """-> ApaMultilabel for `action_loss` in STEP_ACTION_LOSSES[1:], or None for the softmax cross-entropy."""
+    if action_loss not in STEP_ACTION_LOSSES:
+        raise ApaError('{}: action_loss must be one of {} (got {!r})'.format(who, STEP_ACTION_LOSSES, action_loss))
+    if action_loss == 'softmax-xentropy':
+        return None
+    _multilabel_labels(who, labels, n_loss, K)
+    ml = ApaMultilabel()
+    ml.kind, ml.pos_weight = ACTION_LOSS_KINDS[action_loss], float(pos_weight)
+    ml.labels = _dev_ptr(labels, 'labels', torch.float32)
+    return ml
+
+
+def multilabel_loss_fwd_bwd(kind: str, logits, labels, *, wt=1.0, grad_scale=1.0, pos_weight=10.0):
+    """loss [1+N], G [N,K]: 'multi-label' / 'multi-label-2' (src/loss.py:88-101) on finished logits f32 [N,K], one
+    block per row (include/apa.h: apa_multilabel_loss_fwd_bwd).  labels f32 [N,K] multi-hot; loss[1+n] is the row
+    mean, loss[0] the weighted batch mean."""
+    lib = load_library()
+    N, K = logits.shape
+    ml = _bind_multilabel('multilabel_loss_fwd_bwd', kind if kind != 'softmax-xentropy' else '', labels, N, K,
+                          pos_weight)
+    loss = torch.empty((1 + N,), dtype=torch.float32, device=logits.device)
+    G = torch.empty((N, K), dtype=torch.float32, device=logits.device)
+    rc = lib.apa_multilabel_loss_fwd_bwd(ctypes.addressof(ml), _dev_ptr(logits, 'logits', torch.float32),
+                                         loss.data_ptr(), G.data_ptr(), N, K, float(wt), float(grad_scale),
+                                         _stream_ptr())
+    _check(rc, 'apa_multilabel_loss_fwd_bwd')
+    return loss, G
+
+
 def pose_sampled_loss_fwd_bwd(Pl, lbl, valid, uniform, *, wt=1.0, grad_scale=1.0, want_grad=True):
     """loss [1], dPl, mask = LOSS_FN_POSE_SAMPLED (src/loss.py:36-52); `uniform` = the caller's
     uniform [0,1) draws, same shape as Pl."""
@@ -989,6 +1043,38 @@ def clip_xent_fwd_bwd(logits, labels, frames_per_video, w=None, b=None, *, wt=1.
     return pooled, tatt, loss, G, dw, db
 
 
+def clip_multilabel_fwd_bwd(kind: str, logits, labels, frames_per_video, w=None, b=None, *, wt=1.0, grad_scale=1.0,
+                            pos_weight=10.0, workspace=None):
+    """clip_xent_fwd_bwd with a sigmoid loss on the pooled logits (include/apa.h: apa_clip_multilabel_fwd_bwd):
+    labels f32 [B,K] multi-hot; the same six results."""
+    lib = load_library()
+    BF, K = logits.shape
+    F = int(frames_per_video)
+    if F <= 0 or BF % F:
+        raise ApaError('clip_multilabel_fwd_bwd: {} frame rows are not a whole number of clips of {} frames'.format(BF, F))
+    B = BF // F
+    ml = _bind_multilabel('clip_multilabel_fwd_bwd', kind if kind != 'softmax-xentropy' else '', labels, B, K,
+                          pos_weight)
+    dev, f32 = logits.device, torch.float32
+    att = w is not None
+    pooled = torch.empty((B, K), dtype=f32, device=dev)
+    tatt = torch.empty((BF,), dtype=f32, device=dev) if att else None
+    loss = torch.empty((1 + B,), dtype=f32, device=dev)
+    G = torch.empty((BF, K), dtype=f32, device=dev)
+    dw = torch.empty((K,), dtype=f32, device=dev) if att else None
+    db = torch.empty((1,), dtype=f32, device=dev) if att else None
+    need = int(lib.apa_clip_xent_workspace_bytes(B, F, K))
+    if workspace is None or workspace.numel() < need:
+        workspace = torch.empty((max(need, 16),), dtype=torch.uint8, device=dev)
+    rc = lib.apa_clip_multilabel_fwd_bwd(
+        ctypes.addressof(ml), _dev_ptr(logits, 'logits', f32), _dev_ptr(w, 'w', f32), _dev_ptr(b, 'b', f32),
+        pooled.data_ptr(), _dev_ptr(tatt, 'tatt'), loss.data_ptr(), G.data_ptr(), _dev_ptr(dw, 'dw'),
+        _dev_ptr(db, 'db'), workspace.data_ptr(), workspace.numel(), B, F, K, float(wt), float(grad_scale),
+        _stream_ptr())
+    _check(rc, 'apa_clip_multilabel_fwd_bwd')
+    return pooled, tatt, loss, G, dw, db
+
+
 def _bind_clip_pool(who, N, K, frames, temporal, temporal_grads, dev, share_with=None):
     """-> (ApaClipPool, pooled, tatt, keep-alive tuple) for the clip form of a bound step: N = B * frames frame maps,
     `temporal = (w [K], b [1])` the TemporalAttention conv or None, `temporal_grads = (dw [K], db [1])` where its
@@ -1037,8 +1123,12 @@ class HeadTrainStep:
 
     def __init__(self, X, Xatt, Wa, ba, Wt, bt, labels, grads, *, flags=0, keep_prob=1.0, seed=0,
                  offset=0, loss_wt=1.0, grad_scale=1.0, workspace=None, hooks=None, dxatt_rank1=False,
-                 weight_images=False, share_with=None, frames=1, temporal=None, temporal_grads=None):
-        """`frames` / `temporal` / `temporal_grads`: a batch of CLIPS (apa_attn_head_train_step_clips): X holds the
+                 weight_images=False, share_with=None, frames=1, temporal=None, temporal_grads=None,
+                 action_loss='softmax-xentropy', pos_weight=10.0):
+        """`action_loss='multi-label' | 'multi-label-2'` (src/loss.py:88-101, `pos_weight` for the former): the sigmoid
+        losses through apa_attn_head_train_step_multilabel -- `labels` is then float32 multi-hot [N,K] ([B,K] for
+        clips); with the default nothing changes.
+        `frames` / `temporal` / `temporal_grads`: a batch of CLIPS (apa_attn_head_train_step_clips): X holds the
         N = B * frames folded frames, `labels` is [B], `temporal = (w [K], b [1])` the TemporalAttention conv (None:
         plain mean over the frames) and `temporal_grads = (dw [K], db [1])` its gradient buffers.  The step then also
         exposes `pooled [B,K]` (the clip logits) and `tatt [N]`; `logits` / `G` are the frame logits and their
@@ -1073,8 +1163,10 @@ class HeadTrainStep:
                 'HeadTrainStep', N, K, frames, temporal, temporal_grads, dev, share_with)
             self._pre = (ctypes.addressof(self._clip),)
             n_loss = N // int(frames)
-            if labels.numel() != n_loss:
+            if action_loss == 'softmax-xentropy' and labels.numel() != n_loss:
                 raise ApaError('HeadTrainStep: one label per clip expected ({} clips)'.format(n_loss))
+        self._n_loss, self._K = n_loss, K
+        self._ml = _bind_multilabel('HeadTrainStep', action_loss, labels, n_loss, K, pos_weight)
         if share_with is not None:
             o = share_with
             if tuple(o.logits.shape) != (N, K) or tuple(o.att.shape) != (N, P, M) or o.loss.numel() != 1 + n_loss:
@@ -1109,7 +1201,8 @@ class HeadTrainStep:
             _dev_ptr(X, 'X'), _dev_ptr(X, 'X') if fused else _dev_ptr(Xatt, 'Xatt', X.dtype),
             _dev_ptr(Wa, 'Wa', torch.float32), _dev_ptr(ba, 'ba', torch.float32),
             _dev_ptr(Wt, 'Wt', torch.float32), _dev_ptr(bt, 'bt', torch.float32),
-            _dev_ptr(labels, 'labels', torch.int64), float(loss_wt), float(grad_scale),
+            *(() if self._ml is not None else (_dev_ptr(labels, 'labels', torch.int64),)),
+            float(loss_wt), float(grad_scale),
             self.logits.data_ptr(), self.att.data_ptr(), self.zsave.data_ptr(), _dev_ptr(self.abar, 'abar'),
             self.loss.data_ptr(), self.G.data_ptr(), _dev_ptr(dX, 'dX', X.dtype),
             None if fused else _dev_ptr(dXatt, 'dXatt', torch.float32 if dxatt_rank1 else X.dtype),
@@ -1118,6 +1211,10 @@ class HeadTrainStep:
             _dev_ptr(dbt, 'dbt', torch.float32), workspace.data_ptr(), workspace.numel(), N, P, C, Ca, K, M,
             flags, float(keep_prob), int(seed), off, _feat_dtype(X)]
         self._fn = self.lib.apa_attn_head_train_step_clips if clips else self.lib.apa_attn_head_train_step_ex
+        self._name = 'apa_attn_head_train_step_clips' if clips else 'apa_attn_head_train_step'
+        if self._ml is not None:    # (ml, clip or NULL, hooks, then the same arguments without `labels`)
+            self._pre = (ctypes.addressof(self._ml), ctypes.addressof(self._clip) if clips else None)
+            self._fn, self._name = self.lib.apa_attn_head_train_step_multilabel, 'apa_attn_head_train_step_multilabel'
 
     def refresh_weight_images(self) -> None:
         """Rebuild the operand images from the current weights (after load_state_dict, or an optimiser that does not
@@ -1140,7 +1237,11 @@ class HeadTrainStep:
             self._args[0] = self._args[1] = _dev_ptr(X, 'X')
             keep[0] = keep[1] = X
         if labels is not None:
-            self._args[6] = _dev_ptr(labels, 'labels', torch.int64)
+            if self._ml is not None:
+                _multilabel_labels('HeadTrainStep.rebind', labels, self._n_loss, self._K)
+                self._ml.labels = _dev_ptr(labels, 'labels', torch.float32)
+            else:
+                self._args[6] = _dev_ptr(labels, 'labels', torch.int64)
             keep[6] = labels
         if offset is not None:
             if isinstance(keep[8], torch.Tensor):
@@ -1155,7 +1256,7 @@ class HeadTrainStep:
         h = self.hooks if hooks is None else hooks
         rc = self._fn(*self._pre, _hooks_ptr(h), *self._args, _stream_ptr() if stream is None else stream)
         if rc != 0:
-            _check(rc, 'apa_attn_head_train_step_clips' if self._pre else 'apa_attn_head_train_step')
+            _check(rc, self._name)
 
 
 class ApaPoseAttnStepIO(ctypes.Structure):
@@ -1181,8 +1282,11 @@ class PoseAttnTrainStep:
 
     def __init__(self, X, params, labels, pose_labels, pose_valid, grads, *, flags=0, keep_prob=1.0, seed=0,
                  offset=0, action_wt=1.0, pose_wt=1.0, grad_scale=1.0, w1_bf16=None, share_with=None,
-                 w2t_bf16=None, frames=1, temporal=None, temporal_grads=None):
-        """`frames` / `temporal` / `temporal_grads`: a batch of clips (apa_pose_attn_train_step_clips), as for
+                 w2t_bf16=None, frames=1, temporal=None, temporal_grads=None, action_loss='softmax-xentropy',
+                 pos_weight=10.0):
+        """`action_loss` / `pos_weight`: as for HeadTrainStep (apa_pose_attn_train_step_multilabel; labels float32
+        [n_loss, K]); the pose L2 loss stays.
+        `frames` / `temporal` / `temporal_grads`: a batch of clips (apa_pose_attn_train_step_clips), as for
         HeadTrainStep: `labels` [B], `loss_action` [1+B], `pooled` [B,K], `tatt` [N]; pose labels stay per frame.
         `share_with`: another PoseAttnTrainStep of the same shapes whose activation / loss buffers and workspaces
         this step is bound to as well (see HeadTrainStep).  `w2t_bf16`: optional bf16 [16, Cp + 16] image of W2^T (rows
@@ -1208,6 +1312,8 @@ class PoseAttnTrainStep:
                 'PoseAttnTrainStep', N, K, frames, temporal, temporal_grads, dev, share_with)
             self._pre = (ctypes.addressof(self._clip),)
             n_loss = N // int(frames)
+        self._n_loss, self._K = n_loss, K
+        self._ml = _bind_multilabel('PoseAttnTrainStep', action_loss, labels, n_loss, K, pos_weight)
         _shared = ('Ppre', 'Pl', 'att', 'logits', 'zsave', 'abar', 'loss_action', 'loss_pose', 'G', 'dPl', 'dZ')
         if share_with is not None:
             if tuple(share_with.Ppre.shape) != (N, P, Cp) or share_with.Ppre.dtype != X.dtype or \
@@ -1250,9 +1356,10 @@ class PoseAttnTrainStep:
             io.W2T_bf16 = _dev_ptr(w2t_bf16, 'w2t_bf16', torch.bfloat16)
         if w1_bf16 is not None and w1_bf16.numel() != W1.numel():
             raise ApaError('PoseAttnTrainStep: w1_bf16 must have W1\'s element count')
-        io.labels = _dev_ptr(labels, 'labels', torch.int64)
+        io.labels = None if self._ml is not None else _dev_ptr(labels, 'labels', torch.int64)
         io.pose_valid = _dev_ptr(pose_valid, 'pose_valid', torch.uint8)
-        if pose_labels.numel() != N * P * J or pose_valid.numel() != N * J or labels.numel() != n_loss:
+        if pose_labels.numel() != N * P * J or pose_valid.numel() != N * J or \
+                (self._ml is None and labels.numel() != n_loss):
             raise ApaError('PoseAttnTrainStep: labels [N] (one per clip for a clip batch), pose_labels [N,P,J], '
                            'pose_valid [N,J] expected')
         io.action_wt, io.pose_wt, io.grad_scale = float(action_wt), float(pose_wt), float(grad_scale)
@@ -1264,6 +1371,10 @@ class PoseAttnTrainStep:
         self._io = io
         self._args = [ctypes.addressof(io), N, P, C, Cp, J, K, flags, float(keep_prob), int(seed), off, dt]
         self._fn = self.lib.apa_pose_attn_train_step_clips if clips else self.lib.apa_pose_attn_train_step
+        self._name = 'apa_pose_attn_train_step_clips' if clips else 'apa_pose_attn_train_step'
+        if self._ml is not None:    # (ml, clip or NULL, then the same arguments)
+            self._pre = (ctypes.addressof(self._ml), ctypes.addressof(self._clip) if clips else None)
+            self._fn, self._name = self.lib.apa_pose_attn_train_step_multilabel, 'apa_pose_attn_train_step_multilabel'
 
     def rebind(self, X=None, labels=None, pose_labels=None, pose_valid=None, offset=None) -> None:
         """Point the bound step at other inputs of the same shapes / dtypes and / or another dropout offset (int)
@@ -1276,7 +1387,11 @@ class PoseAttnTrainStep:
             io.X = _dev_ptr(X, 'X')
             keep[0] = X
         if labels is not None:
-            io.labels = _dev_ptr(labels, 'labels', torch.int64)
+            if self._ml is not None:
+                _multilabel_labels('PoseAttnTrainStep.rebind', labels, self._n_loss, self._K)
+                self._ml.labels = _dev_ptr(labels, 'labels', torch.float32)
+            else:
+                io.labels = _dev_ptr(labels, 'labels', torch.int64)
             keep[2] = labels
         if pose_labels is not None:
             if pose_labels.numel() != keep[3].numel():
@@ -1298,7 +1413,7 @@ class PoseAttnTrainStep:
     def run(self, stream: Optional[int] = None) -> None:
         rc = self._fn(*self._pre, *self._args, _stream_ptr() if stream is None else stream)
         if rc != 0:
-            _check(rc, 'apa_pose_attn_train_step_clips' if self._pre else 'apa_pose_attn_train_step')
+            _check(rc, self._name)
 
 
 class HeadEvalStep:

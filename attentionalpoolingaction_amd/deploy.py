@@ -946,7 +946,8 @@ class FusedHeadStep:
             return 'a training-mode head is required'
         if head.rank != 1 or head.with_pose_feat or head.want_topdown:
             return 'rank > 1, ..._WITH_POSE_FEAT and the TopDownAttention dump run through the per-op module'
-        if tr.LOSS_FN_ACTION != 'softmax-xentropy':
+        # 'multi-label' / 'multi-label-2' (HICO, Charades; loss.py:88-101): the *_train_step_multilabel entry points
+        if tr.LOSS_FN_ACTION not in ('softmax-xentropy', 'multi-label', 'multi-label-2'):
             return 'LOSS_FN_ACTION %r (the one-call steps take the softmax cross-entropy)' % tr.LOSS_FN_ACTION
         if head.single_layer:
             if tr.LOSS_FN_POSE and head.with_pose_logits:
@@ -1019,9 +1020,13 @@ class FusedHeadStep:
         flags = cof.attn_flags(head.softmax_att, head.relu_att, True, self._preact)
         dX = torch.empty_like(X)
         p = {n: t.data for n, t in self.params.items()}
+        action_wt = float(tr.LOSS_FN_ACTION_WT)
         clip = {}
+        if tr.LOSS_FN_ACTION != 'softmax-xentropy':     # the sigmoid losses: weight 1, as loss.gen_losses passes it
+            action_wt = 1.0                             # (loss.py:93-101); labels float32 multi-hot [n_loss, K]
+            clip = dict(action_loss=tr.LOSS_FN_ACTION)
         if frames > 1:      # a clip batch: frame pooling (and the temporal conv) inside the one call
-            clip = dict(frames=frames)
+            clip.update(frames=frames)
             if self.temporal is not None:
                 clip.update(temporal=(p['temporal_weights'], p['temporal_biases']),
                             temporal_grads=(v['temporal_weights'], v['temporal_biases']))
@@ -1032,14 +1037,14 @@ class FusedHeadStep:
                     p['td_weights'], p['td_biases']), labels_action, labels_pose, pose_valid,
                 (dX, v['pose_w1'], v['pose_b1'], v['pose_w2'], v['pose_b2'], v['att_weights'], v['att_biases'],
                  v['td_weights'], v['td_biases']), flags=flags, keep_prob=head.keep_prob, seed=head.seed,
-                offset=head._step, action_wt=float(tr.LOSS_FN_ACTION_WT), pose_wt=float(tr.LOSS_FN_POSE_WT),
+                offset=head._step, action_wt=action_wt, pose_wt=float(tr.LOSS_FN_POSE_WT),
                 grad_scale=self.loss_scale, w1_bf16=shadow,
                 w2t_bf16=self.w2t_image if X.dtype == torch.bfloat16 else None, **clip)
         else:
             st = cof.HeadTrainStep(
                 X, X, p['att_weights'], p['att_biases'], p['td_weights'], p['td_biases'], labels_action,
                 (dX, None, v['att_weights'], v['att_biases'], v['td_weights'], v['td_biases']), flags=flags,
-                keep_prob=head.keep_prob, seed=head.seed, offset=head._step, loss_wt=float(tr.LOSS_FN_ACTION_WT),
+                keep_prob=head.keep_prob, seed=head.seed, offset=head._step, loss_wt=action_wt,
                 grad_scale=self.loss_scale, hooks=head.hooks,
                 weight_images=bool(head.per_class and self._optimizer is not None), **clip)
         st._dX_buf = dX
@@ -1124,6 +1129,8 @@ class FusedHeadStep:
             last_conv, self._preact = torch.relu(last_conv), False
         if self.pose_form and (labels_pose is None or pose_valid is None):
             raise ValueError('FusedHeadStep: the cfg 003 form needs labels_pose [N,H,W,J] and pose_valid [N,J]')
+        if self.cfg.TRAIN.LOSS_FN_ACTION != 'softmax-xentropy':     # multi-hot labels of any dtype -> float32, once
+            labels_action = labels_action.to(torch.float32).contiguous()
         # one autograd node either way: with a differentiated backbone it hands conv5's gradient upstream, without
         # one (head-only training) it still scales the bucket by whatever coefficient `total` is given
         total = _FusedHeadFunction.apply(last_conv, self._anchor, self, labels_action, labels_pose, pose_valid)

@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define APA_VERSION 304 /* major*10000 + minor*100 + patch */
+#define APA_VERSION 305 /* major*10000 + minor*100 + patch */
 
 typedef enum apa_status {
   APA_OK = 0,
@@ -648,6 +648,67 @@ int apa_attn_head_train_step_clips(const apa_clip_pool* clip, const apa_hooks* h
 int apa_pose_attn_train_step_clips(const apa_clip_pool* clip, const apa_pose_attn_step_io* io, int N, int P, int C,
                                    int Cp, int J, int K, unsigned flags, float keep_prob, uint64_t seed,
                                    uint64_t offset, int dtype, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * The sigmoid ("multi-label") action losses of HICO and Charades, row-parallel, and the one-call training steps
+ * under them.  TRAIN.LOSS_FN_ACTION 'multi-label' (src/loss.py:88-97: the mean of
+ * tf.nn.weighted_cross_entropy_with_logits(targets, logits, pos_weight=10); the action-loss weight is NOT applied,
+ * :93-97 adds the bare mean) and 'multi-label-2' (src/loss.py:98-101: tf.losses.sigmoid_cross_entropy(labels, logits)
+ * times the weight); labels are the f32 multi-hot rows of read_sparse_label.  With x a logits row and t its label row:
+ *   multi-label:    l_k = (1-t_k) x_k + w_k softplus(-x_k),  l'_k = (1-t_k) - w_k (1 - sigmoid(x_k)),
+ *                   w_k = 1 + (pos_weight-1) t_k,  softplus(-x) = log1p(exp(-|x|)) + max(-x, 0)
+ *   multi-label-2:  l_k = max(x_k, 0) - x_k t_k + log1p(exp(-|x_k|)),  l'_k = sigmoid(x_k) - t_k
+ *   loss[1+n] = (1/K) sum_k l_k;   loss[0] = wt/n_loss sum_n loss[1+n];   G[n,k] = wt grad_scale/(n_loss K) l'_k
+ * (wt = 1 for multi-label) -- apa_action_loss_fwd_bwd's arithmetic, which one block walks serially; here one block
+ * per row, every sum in a fixed order, no atomics: identical calls give identical bits, and every entry point below
+ * runs the same row routine, so they give each other's bits too.  loss[0] sums the rows in the order the softmax
+ * entry points use for the same (n_loss, K).
+ */
+typedef struct apa_multilabel {
+  int kind;            /* APA_ACTION_LOSS_MULTI_LABEL | APA_ACTION_LOSS_MULTI_LABEL_2                         */
+  const float* labels; /* f32 multi-hot [n_loss, K]; n_loss = N (flat) or N / frames (clips)                  */
+  float pos_weight;    /* loss.py:96 passes 10; ignored by multi-label-2                                      */
+} apa_multilabel;
+
+/* src/loss.py:88-101 on finished logits f32 [N,K]: loss f32 [1+N], G f32 [N,K].  Two launches, any N, K >= 1.
+ * ml / ml->labels NULL, an unknown kind, null pointers, non-positive sizes: APA_ERR_INVALID_ARG before anything
+ * touches the GPU. */
+int apa_multilabel_loss_fwd_bwd(const apa_multilabel* ml, const float* logits, float* loss /*[1+N]*/, float* G,
+                                int N, int K, float wt, float grad_scale, void* stream);
+
+/* apa_clip_xent_fwd_bwd with the sigmoid loss on the POOLED logits in place of the softmax cross-entropy
+ * (nets_factory.py:354-374, then src/loss.py:88-101): ml->labels f32 [B,K], loss f32 [1+B]; every other argument,
+ * the workspace (apa_clip_xent_workspace_bytes) and the refusals are apa_clip_xent_fwd_bwd's.  With F == 1 and
+ * w == NULL loss and G are bit-identical to apa_multilabel_loss_fwd_bwd(ml, logits, ..., N = B). */
+int apa_clip_multilabel_fwd_bwd(const apa_multilabel* ml, const float* logits, const float* w, const float* b,
+                                float* pooled, float* tatt, float* loss, float* G, float* dw, float* db, void* ws,
+                                size_t ws_bytes, int B, int F, int K, float wt, float grad_scale, void* stream);
+
+/* apa_attn_head_train_step_ex (clip == NULL) / apa_attn_head_train_step_clips under a sigmoid action loss: the
+ * arguments of those entry points without `labels`.  Bit-identical to apa_attn_pool_fwd, apa_multilabel_loss_fwd_bwd
+ * (clips: apa_clip_multilabel_fwd_bwd), apa_attn_pool_bwd back to back.  Flat, M == 1, 4 <= K <= 832 on the small-K
+ * route: the rows' loss rides in the logits reducer, and the batch sum in the backward head kernel where that serves
+ * the shape (else it is one small launch); else the stand-alone rows kernel runs on the finished logits.  clip: ws holds apa_clip_step_workspace_bytes.
+ * ml / ml->labels NULL, an unknown kind, N % frames != 0: APA_ERR_INVALID_ARG before anything touches the GPU. */
+int apa_attn_head_train_step_multilabel(const apa_multilabel* ml, const apa_clip_pool* clip /* NULL: flat */,
+                                        const apa_hooks* hooks, const void* X, const void* Xatt, const float* Wa,
+                                        const float* ba, const float* Wt, const float* bt, float loss_wt,
+                                        float grad_scale, float* logits, float* att, float* zsave, float* abar,
+                                        float* loss, float* G, void* dX, void* dXatt, float* dWa, float* dba,
+                                        float* dWt, float* dbt, void* ws, size_t ws_bytes, int N, int P, int C, int Ca,
+                                        int K, int M, unsigned flags, float keep_prob, uint64_t seed, uint64_t offset,
+                                        int dtype, void* stream);
+
+/* apa_pose_attn_train_step (clip == NULL) / apa_pose_attn_train_step_clips under a sigmoid action loss; the pose L2
+ * loss stays.  Bit-identical to apa_pose_head_fwd, apa_pose_l2_loss_fwd_bwd, apa_attn_head_train_step_multilabel under
+ * APA_FLAG_DXATT_RANK1, apa_pose_head_bwd_rank1ext back to back -- which is what it runs for every shape, flat and on
+ * clips: the launches apa_pose_attn_train_step shares between neighbouring ops on its fast bf16 route sum in other
+ * orders than the per-op kernels, so they are not used here and io->W1_bf16 / io->W2T_bf16 are not read.  io->labels
+ * is unused and may be NULL; io->loss_action is f32 [1+n_loss].  Refusals as above. */
+int apa_pose_attn_train_step_multilabel(const apa_multilabel* ml, const apa_clip_pool* clip /* NULL: flat */,
+                                        const apa_pose_attn_step_io* io /* io->labels unused, may be NULL */, int N,
+                                        int P, int C, int Cp, int J, int K, unsigned flags, float keep_prob,
+                                        uint64_t seed, uint64_t offset, int dtype, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * ..._WITH_POSE_FEAT (nets_factory.py:289-295): `last_conv = tf.concat([last_conv, pose_logits], -1)`

@@ -20,6 +20,12 @@ headline stays the cfg 002 training workload); run this file directly for one wo
             in one process, medians of five; also the flat one-call step at N = 32 of the same head, whose per-image
             cross-entropy is folded into its neighbours, and the clip loss's own two launches.
 
+  hico002 / charades_clips
+            the multi-label datasets on the class-agnostic head (M = 1), bf16: HICO, 32 x 14x14x2048 images, K = 600,
+            and Charades, 8 clips x 4 frames, K = 157, temporal attention on.  Three variants alternate in one process,
+            medians of five: the one-call multi-label step (apa_attn_head_train_step_multilabel), the module path
+            (network_fn + gen_losses + autograd) and the softmax one-call step of the same shape.
+
 Each builder returns (step_fn, info): `step_fn()` enqueues one step on the current stream; `info`
 carries the workload name and the algorithmic work per image.
 """
@@ -360,6 +366,101 @@ def build_rank1(cof, dev, N=32, H=14, K=51, dtype='bf16', rotate=0):
             'bound': 'hbm', 'dtype': dtype, 'N': N, 'rotate': R, 'flops_per_image': 0.0,
             'bytes_per_image': 3.0 * P * C * X.element_size()}
     return _round_robin([st.run for st in sts]), info
+
+
+def build_multilabel(cof, dev, which, B=32, F=1, H=14, K=600, rotate=0, kind='multi-label'):
+    """`which` in ('hico002', 'charades_clips'): M = 1 head on bf16 features, N = B * F maps (F > 1: clips with the
+    TemporalAttention conv).  -> ({'multilabel_one_call', 'module_path', 'softmax_one_call'}: step functions over the
+    same rotating X sets, info)."""
+    from attentionalpoolingaction_amd import config as apa_config, loss as apa_loss, nets_factory
+    N, C, J, P = B * F, 2048, 16, H * H
+    td = torch.bfloat16
+    g = torch.Generator().manual_seed(42)
+    Wa = (torch.randn(C, 1, generator=g) / C ** 0.5).to(dev); ba = torch.zeros(1, device=dev)
+    Wt = (torch.randn(C, K, generator=g) / C ** 0.5).to(dev); bt = torch.zeros(K, device=dev)
+    multihot = (torch.rand(B, K, generator=g) < 0.1).float().to(dev)
+    labels = torch.randint(0, K, (B,), generator=g).to(dev)
+    flags = cof.attn_flags(False, False, True)
+    ctr = torch.zeros(1, dtype=torch.int64, device=dev)
+    per_set = 2 * N * P * C * 2
+    R = _n_sets(per_set, rotate)
+    pg = (torch.empty_like(Wa), torch.empty_like(ba), torch.empty_like(Wt), torch.empty_like(bt))
+    clip = _clip_kwargs(dev, K, F, True)
+    Xs = [_features(N, P, C, td, dev, seed=42 + r) for r in range(R)]
+    dXs = [torch.empty_like(x) for x in Xs]
+    ml_sts, sm_sts = [], []
+    for r in range(R):            # both one-call forms on the SAME X / dX sets
+        ml_sts.append(cof.HeadTrainStep(Xs[r], Xs[r], Wa, ba, Wt, bt, multihot, (dXs[r], None) + pg, flags=flags,
+                                        keep_prob=0.2, seed=42, offset=ctr, action_loss=kind,
+                                        share_with=ml_sts[0] if ml_sts else None, **clip))
+        sm_sts.append(cof.HeadTrainStep(Xs[r], Xs[r], Wa, ba, Wt, bt, labels, (dXs[r], None) + pg, flags=flags,
+                                        keep_prob=0.2, seed=42, offset=ctr, share_with=sm_sts[0] if sm_sts else None,
+                                        **clip))
+    apa_config.reset_cfg()
+    pre = 'USE_POSE_PRELOGITS_BASED_ATTENTION'
+    cfg = apa_config.cfg_from_dict({'MODEL_NAME': 'resnet_v1_101',
+                                    'NET': {pre: True, pre + '_SINGLE_LAYER_ATT': True, 'USE_TEMPORAL_ATT': F > 1},
+                                    'TRAIN': {'LOSS_FN_POSE': '', 'LOSS_FN_ACTION': kind}})
+    network_fn = nets_factory.get_network_fn('resnet_v1_101', K, J, cfg, is_training=True, device=dev)
+    params = list(network_fn.head.parameters()) + (list(network_fn.temporal.parameters()) if F > 1 else [])
+    shape = (B, F, H, H, C) if F > 1 else (B, H, H, C)
+    ins = [x.view(*shape).requires_grad_(True) for x in Xs]
+    tc = cfg.TRAIN
+
+    def module_run(r):
+        for t in params:
+            t.grad = None
+        ins[r].grad = None
+        logits, ep = network_fn(ins[r])
+        losses = apa_loss.gen_losses(multihot, logits, tc.LOSS_FN_ACTION, K, tc.LOSS_FN_ACTION_WT, None, None, '', None,
+                                     tc.LOSS_FN_POSE_WT, ep, cfg)
+        sum(losses).backward()
+
+    steps = {'multilabel_one_call': _round_robin([st.run for st in ml_sts]),
+             'module_path': _round_robin([(lambda r=r: module_run(r)) for r in range(R)]),
+             'softmax_one_call': _round_robin([st.run for st in sm_sts])}
+    what = 'HICO' if which == 'hico002' else 'Charades'
+    info = {'workload': '{} shape, {} x {} frame(s) x {}x{}x{} bf16, K={}, {!r} on the class-agnostic (M=1) head{}: '
+                        'one-call multi-label step vs module path vs softmax one-call step'.format(
+                            what, B, F, H, H, C, K, kind, ', temporal attention' if F > 1 else '') + _rot_note(R, per_set),
+            'bound': 'hbm', 'dtype': 'bf16', 'N': N, 'rotate': R, 'flops_per_image': 0.0,
+            'bytes_per_image': 3.0 * P * C * 2}
+    return steps, info
+
+
+def run_multilabel(cof, dev, args, which):
+    """The three variants alternate inside every round (one process, same clocks): per variant the median over five (or
+    more) rounds of the mean step time of a loop of `steps` steps, and the spread (max - min) of those rounds."""
+    hico = which == 'hico002'
+    steps, info = build_multilabel(cof, dev, which, B=args.batch if hico else args.clips, F=1 if hico else args.frames,
+                                   H=args.hw, K=args.classes or (600 if hico else 157), rotate=args.rotate)
+    if args.only:
+        steps = {args.only: steps[args.only]}
+    for fn in steps.values():
+        for _ in range(max(args.warmup, info['rotate'])):
+            fn()
+    torch.cuda.synchronize()
+    per = {k: [] for k in steps}
+    rounds = 0
+    t_all = time.perf_counter()
+    while rounds < 5 or time.perf_counter() - t_all < 0.5:
+        for k, fn in steps.items():
+            t0 = time.perf_counter()
+            for _ in range(args.steps):
+                fn()
+            torch.cuda.synchronize()
+            per[k].append((time.perf_counter() - t0) / args.steps)
+        rounds += 1
+        if rounds >= 200:
+            break
+    med = {k: sorted(v)[len(v) // 2] for k, v in per.items()}
+    out = report(info, med.get('multilabel_one_call', next(iter(med.values()))), rounds)
+    out['us_per_step'] = {k: round(v * 1e6, 2) for k, v in med.items()}
+    out['us_per_step_min'] = {k: round(min(v) * 1e6, 2) for k, v in per.items()}
+    out['us_per_step_spread'] = {k: round((max(v) - min(v)) * 1e6, 2) for k, v in per.items()}
+    if 'module_path' in med and 'multilabel_one_call' in med:
+        out['module_path_over_one_call'] = round(med['module_path'] / med['multilabel_one_call'], 2)
+    return out
 
 
 def build_eval002(cof, dev, N=32, H=14, K=393, dtype='f32', rotate=0):
@@ -704,11 +805,13 @@ def report(info, sec, repeats):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--workload', default='cfg003', choices=['cfg003', 'perclass', 'eval002', 'eval003', 'rank1', 'posebwd', 'posebwd_acc', 'update003',
-                                                         'update_perclass', 'poseatt', 'video_perclass', 'video003'])
+                                                         'update_perclass', 'poseatt', 'video_perclass', 'video003',
+                                                         'hico002', 'charades_clips'])
     ap.add_argument('--clips', type=int, default=8, help='video_*: clips per batch')
     ap.add_argument('--frames', type=int, default=4, help='video_*: frames per clip')
-    ap.add_argument('--only', default=None, choices=['clip_one_call', 'module_path', 'flat_one_call'],
-                    help='video_*: run one variant alone (kernel traces)')
+    ap.add_argument('--only', default=None, choices=['clip_one_call', 'module_path', 'flat_one_call',
+                                                     'multilabel_one_call', 'softmax_one_call'],
+                    help='video_* / hico002 / charades_clips: run one variant alone (kernel traces)')
     ap.add_argument('--batch', type=int, default=32)
     ap.add_argument('--hw', type=int, default=14)
     ap.add_argument('--classes', type=int, default=None)
@@ -736,6 +839,9 @@ def main():
         return
     if args.workload in ('video_perclass', 'video003'):
         print(json.dumps(run_video(cof, dev, args, 'perclass' if args.workload == 'video_perclass' else 'cfg003')))
+        return
+    if args.workload in ('hico002', 'charades_clips'):
+        print(json.dumps(run_multilabel(cof, dev, args, args.workload)))
         return
     if args.workload == 'poseatt':
         step, info, kernel_times = build_poseatt(cof, dev, args.batch, args.hw, args.classes or 393,
