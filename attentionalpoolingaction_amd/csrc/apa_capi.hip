@@ -62,24 +62,23 @@ extern "C" const char* apa_status_string(int status) {
   }
 }
 
-static int check_common(const char* fn, int N, int P, int C, int Ca, int K, int M, int dtype) {
-  if (N <= 0 || P <= 0 || C <= 0 || Ca <= 0 || K <= 0) {
-    set_error("%s: non-positive dimension N=%d P=%d C=%d Ca=%d K=%d", fn, N, P, C, Ca, K);
+static int check_common(const char* fn, const PoolDims& d) {
+  if (d.N <= 0 || d.P <= 0 || d.C <= 0 || d.Ca <= 0 || d.K <= 0) {
+    set_error("%s: non-positive dimension N=%d P=%d C=%d Ca=%d K=%d", fn, d.N, d.P, d.C, d.Ca, d.K);
     return APA_ERR_INVALID_ARG;
   }
-  if (M != 1 && M != K) {
-    set_error("%s: M must be 1 (class-agnostic) or K (per-class), got M=%d K=%d", fn, M, K);
+  if (d.M != 1 && d.M != d.K) {
+    set_error("%s: M must be 1 (class-agnostic) or K (per-class), got M=%d K=%d", fn, d.M, d.K);
     return APA_ERR_INVALID_ARG;
   }
-  if (dtype != APA_DTYPE_F32 && dtype != APA_DTYPE_BF16) {
-    set_error("%s: unknown dtype %d", fn, dtype);
+  if (d.dtype != APA_DTYPE_F32 && d.dtype != APA_DTYPE_BF16) {
+    set_error("%s: unknown dtype %d", fn, d.dtype);
     return APA_ERR_INVALID_ARG;
   }
   return APA_OK;
 }
 
-extern "C" size_t apa_attn_pool_workspace_bytes(int N, int P, int C, int Ca, int K, int M,
-                                                unsigned flags) {
+extern "C" size_t apa_attn_pool_workspace_bytes(int N, int P, int C, int Ca, int K, int M, unsigned flags) {
   (void)flags;
   if (N <= 0 || P <= 0 || C <= 0 || Ca <= 0 || K <= 0) return 0;
   if (M == 1) return m1_plan(N, P, C, Ca, K).total;
@@ -89,6 +88,17 @@ extern "C" size_t apa_attn_pool_workspace_bytes(int N, int P, int C, int Ca, int
     return a > b ? a : b;
   }
   return 0;
+}
+
+// The call descriptor of an entry point.  The one place a caller's flags are masked: the library's internal bits, and
+// APA_FLAG_WS_FROM_FWD, which only the one-call steps set, on their own backward half (no forward pass reads it).
+// APA_FLAG_DXATT_RANK1 passes: the cfg 003 steps set it themselves on every backward half, and it too is a backward
+// matter only (m1_call_fill), so a caller's bit on such a step changes nothing.
+static PoolCall pool_call(const PoolDims& dims, unsigned flags, float keep_prob, uint64_t seed, uint64_t offset,
+                          void* ws, size_t ws_bytes, void* stream, const apa_hooks* hooks = nullptr,
+                          const apa_concat_feat* cat = nullptr) {
+  return PoolCall{dims, flags & APA_PUBLIC_FLAGS & ~APA_FLAG_WS_FROM_FWD, keep_prob, seed, offset, ws, ws_bytes,
+                  static_cast<hipStream_t>(stream), Hooks(hooks), cat};
 }
 
 // APA_FLAG_RNG_EXTERNAL: `seed` carries the address of the caller's keep bits
@@ -105,252 +115,208 @@ static int check_rng_flags(const char* fn, unsigned flags, uint64_t seed) {
   return APA_OK;
 }
 
-static int check_cat(const char* fn, const apa_concat_feat* c, int M, unsigned flags, bool topdown,
-                     bool backward, CatFeat* out) {
+static int check_cat(const char* fn, const PoolCall& d, bool topdown, bool backward) {
+  const apa_concat_feat* c = d.cat;
   if (!c->Xext || !c->zext || (backward && !c->dXext)) {
     set_error("%s: apa_concat_feat needs Xext, zext%s", fn, backward ? " and dXext" : "");
     return APA_ERR_INVALID_ARG;
   }
-  if (M != 1 || (flags & APA_FLAG_RELU_INPUT) || topdown || !m1_cat_supported(c->J)) {
+  if (d.M != 1 || (d.flags & APA_FLAG_RELU_INPUT) || topdown || !m1_cat_supported(c->J)) {
     set_error("%s: the concatenated pose channels are built for M == 1, 1 <= J <= 64, without "
-              "APA_FLAG_RELU_INPUT and without the TopDownAttention dump (J=%d M=%d)", fn, c->J, M);
+              "APA_FLAG_RELU_INPUT and without the TopDownAttention dump (J=%d M=%d)", fn, c->J, d.M);
     return APA_ERR_UNSUPPORTED;
   }
-  out->Xext = c->Xext; out->J = c->J; out->zext = c->zext; out->dXext = c->dXext;
   return APA_OK;
 }
 
-static int attn_pool_fwd_impl(const Hooks& hk, const apa_concat_feat* catp, M1Xent* xf, const void* X, const void* Xatt, const float* Wa, const float* ba,
-                                 const float* Wt, const float* bt, float* logits, float* att,
-                                 float* zsave, float* abar, void* topdown, void* ws,
-                                 size_t ws_bytes, int N, int P, int C, int Ca, int K, int M,
-                                 unsigned flags, float keep_prob, uint64_t seed, uint64_t offset,
-                                 int dtype, void* stream) {
-  int rc = check_common("apa_attn_pool_fwd", N, P, C, Ca, K, M, dtype);
+// Every refusal of a pooling call above the paths' own (m1_call_fill), each written once.  f: the forward call's
+// tensors, or b: the backward call's (the other null).
+static int pool_check(const PoolCall& d, const M1Fwd* f, const M1Bwd* b) {
+  const char* fn = b ? "apa_attn_pool_bwd" : "apa_attn_pool_fwd";
+  const void* const X = b ? b->X : f->X;
+  const void* const Xatt = b ? b->Xatt : f->Xatt;
+  const bool topdown = f && f->topdown;
+  int rc = check_common(fn, d);
   if (rc != APA_OK) return rc;
-  if (!X || !Xatt || !Wa || !ba || !Wt || !bt || !logits || !att) {
-    set_error("apa_attn_pool_fwd: null tensor pointer");
+  if (f ? !X || !Xatt || !f->Wa || !f->ba || !f->Wt || !f->bt || !f->logits || !f->att
+        : !X || !Xatt || !b->Wa || !b->Wt || !b->bt || !b->att || !b->G || !b->dX || !b->dWa || !b->dba || !b->dWt ||
+              !b->dbt) {
+    set_error("%s: null tensor pointer", fn);
     return APA_ERR_INVALID_ARG;
   }
-  if ((flags & APA_FLAG_TRAIN) && !(keep_prob > 0.f && keep_prob <= 1.f)) {
-    set_error("apa_attn_pool_fwd: keep_prob=%g outside (0,1]", (double)keep_prob);
+  if (f && Xatt == X && d.Ca != d.C) {
+    set_error("%s: Xatt aliases X but Ca=%d != C=%d", fn, d.Ca, d.C);
     return APA_ERR_INVALID_ARG;
   }
-  if (Xatt == X && Ca != C) {
-    set_error("apa_attn_pool_fwd: Xatt aliases X but Ca=%d != C=%d", Ca, C);
+  if (b && Xatt != X && !b->dXatt) {
+    set_error("%s: Xatt is a separate tensor but dXatt is NULL", fn);
     return APA_ERR_INVALID_ARG;
   }
-  rc = check_rng_flags("apa_attn_pool_fwd", flags, seed);
+  if ((d.flags & APA_FLAG_TRAIN) && !(d.keep_prob > 0.f && d.keep_prob <= 1.f)) {
+    set_error("%s: keep_prob=%g outside (0,1]", fn, (double)d.keep_prob);
+    return APA_ERR_INVALID_ARG;
+  }
+  rc = check_rng_flags(fn, d.flags, d.seed);
   if (rc != APA_OK) return rc;
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  CatFeat cat;
-  if (catp) {
-    rc = check_cat("apa_attn_pool_fwd_cat", catp, M, flags, topdown != nullptr, false, &cat);
-    if (rc != APA_OK) return rc;
-  }
-  if ((flags & APA_FLAG_RELU_INPUT) && (M != 1 || topdown)) {
-    set_error("apa_attn_pool_fwd: APA_FLAG_RELU_INPUT is an M == 1 fast path without the "
-              "TopDownAttention dump");
+  if (d.cat && (rc = check_cat(fn, d, topdown, b != nullptr)) != APA_OK) return rc;
+  if ((d.flags & APA_FLAG_RELU_INPUT) && (d.M != 1 || topdown)) {
+    set_error("%s: APA_FLAG_RELU_INPUT is an M == 1 fast path without the TopDownAttention dump", fn);
     return APA_ERR_UNSUPPORTED;
   }
-  if (M == 1) {
-    if (!zsave || !abar) {
-      set_error("apa_attn_pool_fwd: M==1 needs zsave and abar buffers");
-      return APA_ERR_INVALID_ARG;
-    }
-    if (!m1_supported(C, Ca, dtype, Xatt == X)) {
-      set_error("apa_attn_pool_fwd: M==1 needs C and Ca to be whole 16-byte vectors (multiples of 4 fp32 / "
-                "8 bf16 channels, C <= 9584); got C=%d Ca=%d dtype=%d", C, Ca, dtype);
-      return APA_ERR_UNSUPPORTED;
-    }
-    const size_t need = m1_plan(N, P, C, Ca, K).total;
-    if (!ws || ws_bytes < need) {
-      set_error("apa_attn_pool_fwd: workspace too small (%zu < %zu)", ws_bytes, need);
-      return APA_ERR_WORKSPACE;
-    }
-    M1Call c;
-    rc = m1_call_fill(c, X, Xatt, nullptr, false, catp ? &cat : nullptr, hk, ws, N, P, C, Ca, K, flags, keep_prob, seed,
-                      offset, dtype, st);
-    if (rc != APA_OK) return rc;
-    rc = m1_forward(c, M1Fwd{X, Xatt, Wa, ba, Wt, bt, logits, att, zsave, abar}, xf);
-    if (rc != APA_OK || !topdown) return rc;
-    // end_points['TopDownAttention'] = dropout(X).Wt + bt  (nets_factory.py:296-309): the factorised
-    // path never needs it; it is materialised only on request (eval.py --ept dumps) by one GEMM.
-    GemmDesc g;
-    g.A = X; g.lda = C; g.ta = dtype == APA_DTYPE_BF16 ? 1 : 0; g.a_kc = true;
-    g.B = Wt; g.ldb = K; g.tb = 0; g.b_kc = false;
-    g.C = topdown; g.ldc = K; g.tc = g.ta;
-    g.M = N * P; g.N = K; g.K = C; g.bias = bt;
-    if ((flags & APA_FLAG_TRAIN) && keep_prob < 1.0f) {
-      g.drop_a = 1;
-      g.inv_keep = 1.0f / keep_prob;
-      const RngKeyArgs k = rng_resolve(flags, keep_prob, seed, offset);
-      g.thresh = k.thresh; g.seed = k.seed; g.offset = k.offset; g.offset_dev = k.offset_dev;
-    }
-    return gemm_launch(g, st);
+  if (b && (d.flags & APA_FLAG_DXATT_RANK1) && d.M != 1) {
+    set_error("%s: APA_FLAG_DXATT_RANK1 needs one bottom-up map (M == 1): with per-class maps the gradient w.r.t. "
+              "Xatt has rank K", fn);
+    return APA_ERR_UNSUPPORTED;
   }
-  // M == K: per-class maps, dense MFMA path.  zsave holds the fp32 [N,P,K] top-down map.
-  if (!zsave) {
-    set_error("apa_attn_pool_fwd: M==K needs zsave = fp32 [N,P,K] buffer (top-down map saved for backward)");
+  // what the forward call saves for the backward call: M == 1 zsave and abar; M == K zsave, the fp32 [N,P,K] top-down map
+  const float* const zsave = b ? b->zsave : f->zsave;
+  const float* const abar = b ? b->abar : f->abar;
+  if (!zsave || (d.M == 1 && !abar)) {
+    set_error(d.M == 1 ? "%s: M==1 needs the zsave and abar buffers (backward: from the forward call)"
+                       : "%s: M==K needs zsave = fp32 [N,P,K] buffer (the top-down map, saved by forward for backward)",
+              fn);
     return APA_ERR_INVALID_ARG;
   }
-  const size_t need = pc_workspace_bytes(N, P, C, Ca, K, dtype);
-  if (!ws || ws_bytes < need) {
-    set_error("apa_attn_pool_fwd: workspace too small (%zu < %zu)", ws_bytes, need);
+  if (d.M == 1 && !m1_supported(d.C, d.Ca, d.dtype, Xatt == X)) {
+    set_error("%s: M==1 needs C and Ca to be whole 16-byte vectors (multiples of 4 fp32 / 8 bf16 channels, "
+              "C <= 9584); got C=%d Ca=%d dtype=%d", fn, d.C, d.Ca, d.dtype);
+    return APA_ERR_UNSUPPORTED;
+  }
+  const size_t need = d.M == 1 ? m1_plan(d.N, d.P, d.C, d.Ca, d.K).total
+                               : pc_workspace_bytes(d.N, d.P, d.C, d.Ca, d.K, d.dtype);
+  if (!d.ws || d.ws_bytes < need) {
+    set_error("%s: workspace too small (%zu < %zu)", fn, d.ws_bytes, need);
     return APA_ERR_WORKSPACE;
   }
-  if ((flags & APA_FLAG_WEIGHT_IMAGES) && (reinterpret_cast<uintptr_t>(X) & 15)) {
-    set_error("apa_attn_pool_fwd: APA_FLAG_WEIGHT_IMAGES needs 16-byte aligned features (the images are laid out for them)");
+  if (d.M != 1 && (d.flags & APA_FLAG_WEIGHT_IMAGES) && (reinterpret_cast<uintptr_t>(X) & 15)) {
+    set_error("%s: APA_FLAG_WEIGHT_IMAGES needs 16-byte aligned features (the images are laid out for them)", fn);
     return APA_ERR_INVALID_ARG;
   }
-  if (hk.td_ready) APA_HIP_CHECK(hipStreamWaitEvent(st, hk.td_ready, 0));
-  return pc_forward(X, Xatt, Wa, ba, Wt, bt, logits, att, zsave, topdown, ws, N, P, C, Ca, K, flags,
-                    keep_prob, seed, offset, dtype, st, topdown ? nullptr : xf);
+  return APA_OK;
 }
 
-extern "C" int apa_attn_pool_fwd(const void* X, const void* Xatt, const float* Wa, const float* ba,
-                                 const float* Wt, const float* bt, float* logits, float* att,
-                                 float* zsave, float* abar, void* topdown, void* ws,
-                                 size_t ws_bytes, int N, int P, int C, int Ca, int K, int M,
-                                 unsigned flags, float keep_prob, uint64_t seed, uint64_t offset,
-                                 int dtype, void* stream) {
-  return attn_pool_fwd_impl(Hooks(), nullptr, nullptr, X, Xatt, Wa, ba, Wt, bt, logits, att, zsave, abar, topdown, ws,
-                            ws_bytes, N, P, C, Ca, K, M, flags & APA_PUBLIC_FLAGS, keep_prob, seed, offset, dtype, stream);
+// end_points['TopDownAttention'] = dropout(X).Wt + bt  (nets_factory.py:296-309): the factorised
+// path never needs it; it is materialised only on request (eval.py --ept dumps) by one GEMM.
+static int topdown_product(const PoolCall& d, const M1Fwd& f) {
+  GemmDesc g;
+  g.A = f.X; g.lda = d.C; g.ta = dt_code(d.dtype); g.a_kc = true;
+  g.B = f.Wt; g.ldb = d.K; g.tb = 0; g.b_kc = false;
+  g.C = f.topdown; g.ldc = d.K; g.tc = g.ta;
+  g.M = d.N * d.P; g.N = d.K; g.K = d.C; g.bias = f.bt;
+  if ((d.flags & APA_FLAG_TRAIN) && d.keep_prob < 1.0f) {
+    g.drop_a = 1;
+    g.inv_keep = 1.0f / d.keep_prob;
+    const RngKeyArgs k = rng_resolve(d.flags, d.keep_prob, d.seed, d.offset);
+    g.thresh = k.thresh; g.seed = k.seed; g.offset = k.offset; g.offset_dev = k.offset_dev;
+  }
+  return gemm_launch(g, d.st);
 }
 
-extern "C" int apa_attn_pool_fwd_ex(const apa_hooks* hooks, const void* X, const void* Xatt,
-                                    const float* Wa, const float* ba, const float* Wt, const float* bt,
-                                    float* logits, float* att, float* zsave, float* abar, void* topdown,
-                                    void* ws, size_t ws_bytes, int N, int P, int C, int Ca, int K, int M,
-                                    unsigned flags, float keep_prob, uint64_t seed, uint64_t offset,
-                                    int dtype, void* stream) {
-  return attn_pool_fwd_impl(Hooks(hooks), nullptr, nullptr, X, Xatt, Wa, ba, Wt, bt, logits, att, zsave, abar, topdown,
-                            ws, ws_bytes, N, P, C, Ca, K, M, flags & APA_PUBLIC_FLAGS, keep_prob, seed, offset, dtype, stream);
-}
-
-static int attn_pool_bwd_impl(const Hooks& hk, const apa_concat_feat* catp, const M1Xent* xf, const void* X, const void* Xatt, const float* Wa, const float* ba,
-                                 const float* Wt, const float* bt, const float* att,
-                                 const float* zsave, const float* abar, const float* G, void* dX,
-                                 void* dXatt, float* dWa, float* dba, float* dWt, float* dbt,
-                                 void* ws, size_t ws_bytes, int N, int P, int C, int Ca, int K,
-                                 int M, unsigned flags, float keep_prob, uint64_t seed,
-                                 uint64_t offset, int dtype, void* stream) {
-  int rc = check_common("apa_attn_pool_bwd", N, P, C, Ca, K, M, dtype);
+// xf: the loss (or the evaluation outputs) a one-call step asks the forward pass to fold; `done` says whether it did
+static int attn_pool_fwd(const PoolCall& d, const M1Fwd& f, M1Xent* xf) {
+  int rc = pool_check(d, &f, nullptr);
   if (rc != APA_OK) return rc;
-  if (!X || !Xatt || !Wa || !Wt || !bt || !att || !G || !dX || !dWa || !dba || !dWt || !dbt) {
-    set_error("apa_attn_pool_bwd: null tensor pointer");
-    return APA_ERR_INVALID_ARG;
-  }
-  if (Xatt != X && !dXatt) {
-    set_error("apa_attn_pool_bwd: Xatt is a separate tensor but dXatt is NULL");
-    return APA_ERR_INVALID_ARG;
-  }
-  if ((flags & APA_FLAG_TRAIN) && !(keep_prob > 0.f && keep_prob <= 1.f)) {
-    set_error("apa_attn_pool_bwd: keep_prob=%g outside (0,1]", (double)keep_prob);
-    return APA_ERR_INVALID_ARG;
-  }
-  rc = check_rng_flags("apa_attn_pool_bwd", flags, seed);
-  if (rc != APA_OK) return rc;
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  CatFeat cat;
-  if (catp) {
-    rc = check_cat("apa_attn_pool_bwd_cat", catp, M, flags, false, true, &cat);
-    if (rc != APA_OK) return rc;
-  }
-  if ((flags & APA_FLAG_RELU_INPUT) && M != 1) {
-    set_error("apa_attn_pool_bwd: APA_FLAG_RELU_INPUT is an M == 1 fast path");
-    return APA_ERR_UNSUPPORTED;
-  }
-  if ((flags & APA_FLAG_DXATT_RANK1) && M != 1) {
-    set_error("apa_attn_pool_bwd: APA_FLAG_DXATT_RANK1 needs one bottom-up map (M == 1): with per-class "
-              "maps the gradient w.r.t. Xatt has rank K");
-    return APA_ERR_UNSUPPORTED;
-  }
-  if (M == 1) {
-    if (!zsave || !abar) {
-      set_error("apa_attn_pool_bwd: M==1 needs zsave and abar from the forward call");
-      return APA_ERR_INVALID_ARG;
-    }
-    if (!m1_supported(C, Ca, dtype, Xatt == X)) {
-      set_error("apa_attn_pool_bwd: unsupported C=%d Ca=%d dtype=%d", C, Ca, dtype);
-      return APA_ERR_UNSUPPORTED;
-    }
-    const size_t need = m1_plan(N, P, C, Ca, K).total;
-    if (!ws || ws_bytes < need) {
-      set_error("apa_attn_pool_bwd: workspace too small (%zu < %zu)", ws_bytes, need);
-      return APA_ERR_WORKSPACE;
-    }
-    const M1Bwd io{X, Xatt, Wa, Wt, bt, att, zsave, abar, G, dX, dXatt, dWa, dba, dWt, dbt};
+  if (d.M == 1) {
     M1Call c;
-    rc = m1_call_fill(c, X, Xatt, &io, xf && xf->done, catp ? &cat : nullptr, hk, ws, N, P, C, Ca, K, flags, keep_prob,
-                      seed, offset, dtype, st);
-    return rc != APA_OK ? rc : m1_backward(c, io, xf);
+    rc = m1_call_fill(c, d, &f, nullptr);
+    if (rc != APA_OK) return rc;
+    rc = m1_forward(c, f, xf);
+    return rc != APA_OK || !f.topdown ? rc : topdown_product(d, f);
   }
-  if (!zsave) {
-    set_error("apa_attn_pool_bwd: M==K needs zsave (the fp32 [N,P,K] top-down map from forward)");
-    return APA_ERR_INVALID_ARG;
+  // M == K: per-class maps, dense MFMA path
+  if (d.hk.td_ready) APA_HIP_CHECK(hipStreamWaitEvent(d.st, d.hk.td_ready, 0));
+  return pc_forward(d, f, f.topdown ? nullptr : xf);
+}
+
+// xf: what the forward half of the same step folded and this half has to finish
+static int attn_pool_bwd(const PoolCall& d, const M1Bwd& b, const M1Xent* xf) {
+  int rc = pool_check(d, nullptr, &b);
+  if (rc != APA_OK) return rc;
+  if (d.M == 1) {
+    M1Call c;
+    rc = m1_call_fill(c, d, nullptr, &b, xf);
+    return rc != APA_OK ? rc : m1_backward(c, b, xf);
   }
-  const size_t need = pc_workspace_bytes(N, P, C, Ca, K, dtype);
-  if (!ws || ws_bytes < need) {
-    set_error("apa_attn_pool_bwd: workspace too small (%zu < %zu)", ws_bytes, need);
-    return APA_ERR_WORKSPACE;
-  }
-  if ((flags & APA_FLAG_WEIGHT_IMAGES) && (reinterpret_cast<uintptr_t>(X) & 15)) {
-    set_error("apa_attn_pool_bwd: APA_FLAG_WEIGHT_IMAGES needs 16-byte aligned features (the images are laid out for them)");
-    return APA_ERR_INVALID_ARG;
-  }
-  rc = pc_backward(X, Xatt, Wa, Wt, att, zsave, G, dX, dXatt, dWa, dba, dWt, dbt, ws, N, P, C, Ca, K,
-                   flags, keep_prob, seed, offset, dtype, st, xf);
-  if (rc == APA_OK && hk.grad_ready) APA_HIP_CHECK(hipEventRecord(hk.grad_ready, st));
+  rc = pc_backward(d, b, xf);
+  if (rc == APA_OK && d.hk.grad_ready) APA_HIP_CHECK(hipEventRecord(d.hk.grad_ready, d.st));
   return rc;
-}
-
-extern "C" int apa_attn_pool_bwd(const void* X, const void* Xatt, const float* Wa, const float* ba,
-                                 const float* Wt, const float* bt, const float* att,
-                                 const float* zsave, const float* abar, const float* G, void* dX,
-                                 void* dXatt, float* dWa, float* dba, float* dWt, float* dbt,
-                                 void* ws, size_t ws_bytes, int N, int P, int C, int Ca, int K,
-                                 int M, unsigned flags, float keep_prob, uint64_t seed,
-                                 uint64_t offset, int dtype, void* stream) {
-  return attn_pool_bwd_impl(Hooks(), nullptr, nullptr, X, Xatt, Wa, ba, Wt, bt, att, zsave, abar, G, dX, dXatt, dWa, dba,
-                            dWt, dbt, ws, ws_bytes, N, P, C, Ca, K, M, flags & APA_PUBLIC_FLAGS & ~APA_FLAG_WS_FROM_FWD, keep_prob,
-                            seed, offset, dtype, stream);
-}
-
-extern "C" int apa_attn_pool_bwd_ex(const apa_hooks* hooks, const void* X, const void* Xatt,
-                                    const float* Wa, const float* ba, const float* Wt, const float* bt,
-                                    const float* att, const float* zsave, const float* abar,
-                                    const float* G, void* dX, void* dXatt, float* dWa, float* dba,
-                                    float* dWt, float* dbt, void* ws, size_t ws_bytes, int N, int P,
-                                    int C, int Ca, int K, int M, unsigned flags, float keep_prob,
-                                    uint64_t seed, uint64_t offset, int dtype, void* stream) {
-  return attn_pool_bwd_impl(Hooks(hooks), nullptr, nullptr, X, Xatt, Wa, ba, Wt, bt, att, zsave, abar, G, dX, dXatt,
-                            dWa, dba, dWt, dbt, ws, ws_bytes, N, P, C, Ca, K, M, flags & APA_PUBLIC_FLAGS & ~APA_FLAG_WS_FROM_FWD,
-                            keep_prob, seed, offset, dtype, stream);
 }
 
 extern "C" int apa_attn_pool_fwd_cat(const apa_concat_feat* cat, const apa_hooks* hooks, const void* X,
                                      const void* Xatt, const float* Wa, const float* ba, const float* Wt,
-                                     const float* bt, float* logits, float* att, float* zsave,
-                                     float* abar, void* topdown, void* ws, size_t ws_bytes, int N, int P,
-                                     int C, int Ca, int K, int M, unsigned flags, float keep_prob,
-                                     uint64_t seed, uint64_t offset, int dtype, void* stream) {
-  return attn_pool_fwd_impl(Hooks(hooks), cat, nullptr, X, Xatt, Wa, ba, Wt, bt, logits, att, zsave, abar,
-                            topdown, ws, ws_bytes, N, P, C, Ca, K, M, flags & APA_PUBLIC_FLAGS, keep_prob, seed, offset,
-                            dtype, stream);
+                                     const float* bt, float* logits, float* att, float* zsave, float* abar,
+                                     void* topdown, void* ws, size_t ws_bytes, int N, int P, int C, int Ca, int K,
+                                     int M, unsigned flags, float keep_prob, uint64_t seed, uint64_t offset, int dtype,
+                                     void* stream) {
+  return attn_pool_fwd(pool_call({N, P, C, Ca, K, M, dtype}, flags, keep_prob, seed, offset, ws, ws_bytes, stream,
+                                 hooks, cat),
+                       M1Fwd{X, Xatt, Wa, ba, Wt, bt, logits, att, zsave, abar, topdown}, nullptr);
 }
 
+extern "C" int apa_attn_pool_fwd_ex(const apa_hooks* hooks, const void* X, const void* Xatt, const float* Wa,
+                                    const float* ba, const float* Wt, const float* bt, float* logits, float* att,
+                                    float* zsave, float* abar, void* topdown, void* ws, size_t ws_bytes, int N, int P,
+                                    int C, int Ca, int K, int M, unsigned flags, float keep_prob, uint64_t seed,
+                                    uint64_t offset, int dtype, void* stream) {
+  return apa_attn_pool_fwd_cat(nullptr, hooks, X, Xatt, Wa, ba, Wt, bt, logits, att, zsave, abar, topdown, ws, ws_bytes,
+                               N, P, C, Ca, K, M, flags, keep_prob, seed, offset, dtype, stream);
+}
+
+extern "C" int apa_attn_pool_fwd(const void* X, const void* Xatt, const float* Wa, const float* ba, const float* Wt,
+                                 const float* bt, float* logits, float* att, float* zsave, float* abar, void* topdown,
+                                 void* ws, size_t ws_bytes, int N, int P, int C, int Ca, int K, int M, unsigned flags,
+                                 float keep_prob, uint64_t seed, uint64_t offset, int dtype, void* stream) {
+  return apa_attn_pool_fwd_cat(nullptr, nullptr, X, Xatt, Wa, ba, Wt, bt, logits, att, zsave, abar, topdown, ws,
+                               ws_bytes, N, P, C, Ca, K, M, flags, keep_prob, seed, offset, dtype, stream);
+}
+
+// (a caller cannot vouch for a workspace's history: pool_call clears APA_FLAG_WS_FROM_FWD)
 extern "C" int apa_attn_pool_bwd_cat(const apa_concat_feat* cat, const apa_hooks* hooks, const void* X,
                                      const void* Xatt, const float* Wa, const float* ba, const float* Wt,
-                                     const float* bt, const float* att, const float* zsave,
-                                     const float* abar, const float* G, void* dX, void* dXatt, float* dWa,
-                                     float* dba, float* dWt, float* dbt, void* ws, size_t ws_bytes, int N,
-                                     int P, int C, int Ca, int K, int M, unsigned flags, float keep_prob,
-                                     uint64_t seed, uint64_t offset, int dtype, void* stream) {
-  return attn_pool_bwd_impl(Hooks(hooks), cat, nullptr, X, Xatt, Wa, ba, Wt, bt, att, zsave, abar, G, dX,
-                            dXatt, dWa, dba, dWt, dbt, ws, ws_bytes, N, P, C, Ca, K, M,
-                            flags & APA_PUBLIC_FLAGS & ~APA_FLAG_WS_FROM_FWD, keep_prob, seed, offset, dtype, stream);
+                                     const float* bt, const float* att, const float* zsave, const float* abar,
+                                     const float* G, void* dX, void* dXatt, float* dWa, float* dba, float* dWt,
+                                     float* dbt, void* ws, size_t ws_bytes, int N, int P, int C, int Ca, int K, int M,
+                                     unsigned flags, float keep_prob, uint64_t seed, uint64_t offset, int dtype,
+                                     void* stream) {
+  (void)ba;
+  return attn_pool_bwd(pool_call({N, P, C, Ca, K, M, dtype}, flags, keep_prob, seed, offset, ws, ws_bytes, stream,
+                                 hooks, cat),
+                       M1Bwd{X, Xatt, Wa, Wt, bt, att, zsave, abar, G, dX, dXatt, dWa, dba, dWt, dbt}, nullptr);
 }
+
+extern "C" int apa_attn_pool_bwd_ex(const apa_hooks* hooks, const void* X, const void* Xatt, const float* Wa,
+                                    const float* ba, const float* Wt, const float* bt, const float* att,
+                                    const float* zsave, const float* abar, const float* G, void* dX, void* dXatt,
+                                    float* dWa, float* dba, float* dWt, float* dbt, void* ws, size_t ws_bytes, int N,
+                                    int P, int C, int Ca, int K, int M, unsigned flags, float keep_prob, uint64_t seed,
+                                    uint64_t offset, int dtype, void* stream) {
+  return apa_attn_pool_bwd_cat(nullptr, hooks, X, Xatt, Wa, ba, Wt, bt, att, zsave, abar, G, dX, dXatt, dWa, dba, dWt,
+                               dbt, ws, ws_bytes, N, P, C, Ca, K, M, flags, keep_prob, seed, offset, dtype, stream);
+}
+
+extern "C" int apa_attn_pool_bwd(const void* X, const void* Xatt, const float* Wa, const float* ba, const float* Wt,
+                                 const float* bt, const float* att, const float* zsave, const float* abar,
+                                 const float* G, void* dX, void* dXatt, float* dWa, float* dba, float* dWt, float* dbt,
+                                 void* ws, size_t ws_bytes, int N, int P, int C, int Ca, int K, int M, unsigned flags,
+                                 float keep_prob, uint64_t seed, uint64_t offset, int dtype, void* stream) {
+  return apa_attn_pool_bwd_cat(nullptr, nullptr, X, Xatt, Wa, ba, Wt, bt, att, zsave, abar, G, dX, dXatt, dWa, dba,
+                               dWt, dbt, ws, ws_bytes, N, P, C, Ca, K, M, flags, keep_prob, seed, offset, dtype,
+                               stream);
+}
+
+// ---- the one-call training steps ------------------------------------------------------------------------------------
+// The loss of a step.  ml: a sigmoid action loss on ml->labels (checked by check_multilabel; `labels` unused), null:
+// the softmax cross-entropy on the integer `labels`.  clips: the loss is taken on the rows pooled over each clip's frames
+// (apa.h: apa_clip_pool; `clip` is checked by clip_step_check), loss is [1 + N / frames] then.
+struct StepLoss {
+  const apa_multilabel* ml = nullptr;
+  const int64_t* labels = nullptr;
+  bool clips = false;
+  const apa_clip_pool* clip = nullptr;
+  float wt = 1.f, grad_scale = 1.f;
+  float* loss = nullptr;   // [1 + rows]
+  float* G = nullptr;      // [N,K]: the gradient at the (frame) logits
+};
 
 // a valid apa_multilabel, or the refusal (nothing has touched the GPU)
 static int check_multilabel(const char* fn, const apa_multilabel* ml) {
@@ -365,149 +331,240 @@ static int check_multilabel(const char* fn, const apa_multilabel* ml) {
   return APA_OK;
 }
 
-// The flat one-call step under a sigmoid action loss: apa_attn_head_train_step_ex with the loss exchanged.  M == 1
-// with the fold's shapes: the logits reducer does the rows' loss (m1_logits_ml_kernel); everything else -- per-class
-// maps (their pc_row_xent folds read integer labels: not entered), K past the fold, the generic route -- runs
-// ml_rows_kernel on the finished logits.  Bit-identical to apa_attn_pool_fwd, apa_multilabel_loss_fwd_bwd,
-// apa_attn_pool_bwd either way.
-static int head_step_multilabel(const apa_multilabel& ml, const Hooks& hk, const void* X, const void* Xatt,
-                                const float* Wa, const float* ba, const float* Wt, const float* bt, float loss_wt,
-                                float grad_scale, float* logits, float* att, float* zsave, float* abar, float* loss,
-                                float* G, void* dX, void* dXatt, float* dWa, float* dba, float* dWt, float* dbt,
-                                void* ws, size_t ws_bytes, int N, int P, int C, int Ca, int K, int M, unsigned flags,
-                                float keep_prob, uint64_t seed, uint64_t offset, int dtype, void* stream) {
-  M1Xent xf;
-  xf.labels = nullptr; xf.loss = loss; xf.G = G;
-  xf.lscale = xf.gscale = 0.f;
-  if (N > 0 && K > 0) ml_scales(ml.kind, loss_wt, grad_scale, N, K, &xf.lscale, &xf.gscale);
-  xf.done = false;
-  xf.kind = ml.kind; xf.mlabels = ml.labels; xf.pos_weight = ml.pos_weight;
-  M1Xent* const xp = M == 1 ? &xf : nullptr;
-  int rc = attn_pool_fwd_impl(hk, nullptr, xp, X, Xatt, Wa, ba, Wt, bt, logits, att, zsave, abar, nullptr, ws,
-                              ws_bytes, N, P, C, Ca, K, M, flags, keep_prob, seed, offset, dtype, stream);
-  if (rc != APA_OK) return rc;
-  if (!xf.done) {
-    rc = ml_loss_rows(ml.kind, ml.labels, ml.pos_weight, logits, loss, G, N, K, loss_wt, grad_scale,
-                      static_cast<hipStream_t>(stream));
-    if (rc != APA_OK) return rc;
-  }
-  return attn_pool_bwd_impl(hk, nullptr, xf.done && !xf.finished ? &xf : nullptr, X, Xatt, Wa, ba, Wt, bt, att, zsave,
-                            abar, G, dX, dXatt, dWa, dba, dWt, dbt, ws, ws_bytes, N, P, C, Ca, K, M,
-                            flags | APA_FLAG_WS_FROM_FWD, keep_prob, seed, offset, dtype, stream);
+// the pooling workspace, then the clip loss's scratch
+static size_t clip_step_pool_bytes(int N, int P, int C, int Ca, int K, int M, unsigned flags) {
+  return align_up(apa_attn_pool_workspace_bytes(N, P, C, Ca, K, M, flags), 256);
 }
 
-extern "C" int apa_attn_head_train_step_ex(const apa_hooks* hooks, const void* X, const void* Xatt,
-                                           const float* Wa, const float* ba, const float* Wt,
-                                           const float* bt, const int64_t* labels, float loss_wt,
-                                           float grad_scale, float* logits, float* att, float* zsave,
-                                           float* abar, float* loss, float* G, void* dX, void* dXatt,
-                                           float* dWa, float* dba, float* dWt, float* dbt, void* ws,
-                                           size_t ws_bytes, int N, int P, int C, int Ca, int K, int M,
-                                           unsigned flags, float keep_prob, uint64_t seed,
-                                           uint64_t offset, int dtype, void* stream) {
-  const Hooks hk(hooks);
-  flags &= APA_PUBLIC_FLAGS;
-  if (!labels || !loss || !G) {
-    apa::set_error("apa_attn_head_train_step: null labels / loss / G pointer");
+extern "C" size_t apa_clip_step_workspace_bytes(int N, int frames, int P, int C, int Ca, int K, int M, unsigned flags) {
+  if (N <= 0 || frames <= 0 || N % frames != 0) return 0;
+  const size_t pool = apa_attn_pool_workspace_bytes(N, P, C, Ca, K, M, flags);
+  return pool ? clip_step_pool_bytes(N, P, C, Ca, K, M, flags) + apa_clip_xent_workspace_bytes(N / frames, frames, K)
+              : 0;
+}
+
+// everything the clip loss would refuse, BEFORE the forward half is launched; *pool_bytes: where its scratch begins
+static int clip_step_check(const char* fn, const PoolCall& d, const StepLoss& L, const float* logits,
+                           size_t* pool_bytes) {
+  const apa_clip_pool* clip = L.clip;
+  if (!clip || !(L.ml ? static_cast<const void*>(L.ml->labels) : L.labels) || !L.loss || !logits || !L.G) {
+    set_error("%s: null clip / labels / loss / logits / G pointer", fn);
     return APA_ERR_INVALID_ARG;
   }
-  // Inside one call the loss can be folded into its neighbours (M == 1, K <= 512): the
-  // logits reduction also does the row's softmax cross-entropy, the backward head kernel the batch
-  // mean -- one launch fewer, bit-identical results (same reduction trees).
-  M1Xent xf;
-  xf.labels = labels; xf.loss = loss; xf.G = G;
-  xf.lscale = N > 0 ? loss_wt / (float)N : 0.f;
-  xf.gscale = N > 0 ? loss_wt * grad_scale / (float)N : 0.f;
-  xf.done = false;
-  int rc = attn_pool_fwd_impl(hk, nullptr, &xf, X, Xatt, Wa, ba, Wt, bt, logits, att, zsave, abar,
-                              nullptr, ws, ws_bytes, N, P, C, Ca, K, M, flags, keep_prob, seed, offset,
-                              dtype, stream);
+  const int rc = check_common(fn, d);
   if (rc != APA_OK) return rc;
-  if (!xf.done) {
-    if (PcTrace* t = pc_trace()) if (M != 1) t->xent = PC_XENT_OWN;
-    rc = apa_softmax_xent_fwd_bwd(logits, labels, loss, G, nullptr, nullptr, N, K, loss_wt, grad_scale,
-                                  stream);
-    if (rc != APA_OK) return rc;
+  if (clip->frames <= 0 || d.N % clip->frames != 0) {
+    set_error("%s: N=%d is not a whole number of clips of %d frames", fn, d.N, clip->frames);
+    return APA_ERR_INVALID_ARG;
   }
-  // same workspace, nothing in between: the backward may reuse what the forward prepared in it
-  return attn_pool_bwd_impl(hk, nullptr, xf.done ? &xf : nullptr, X, Xatt, Wa, ba, Wt, bt, att, zsave, abar, G, dX,
-                            dXatt, dWa, dba, dWt, dbt, ws, ws_bytes, N, P, C, Ca, K, M,
-                            flags | APA_FLAG_WS_FROM_FWD, keep_prob,
-                            seed, offset, dtype, stream);
+  if (!clip->pooled || (clip->w && (!clip->b || !clip->tatt || !clip->dw || !clip->db))) {
+    set_error("%s: apa_clip_pool needs pooled, and with w also b, tatt, dw and db", fn);
+    return APA_ERR_INVALID_ARG;
+  }
+  *pool_bytes = clip_step_pool_bytes(d.N, d.P, d.C, d.Ca, d.K, d.M, d.flags);
+  const size_t need = *pool_bytes + apa_clip_xent_workspace_bytes(d.N / clip->frames, clip->frames, d.K);
+  if (!d.ws || d.ws_bytes < need) {
+    set_error("%s: workspace too small (%zu < %zu = apa_clip_step_workspace_bytes)", fn, d.ws_bytes, need);
+    return APA_ERR_WORKSPACE;
+  }
+  return APA_OK;
 }
 
-extern "C" int apa_attn_head_train_step(const void* X, const void* Xatt, const float* Wa,
-                                        const float* ba, const float* Wt, const float* bt,
-                                        const int64_t* labels, float loss_wt, float grad_scale,
-                                        float* logits, float* att, float* zsave, float* abar,
-                                        float* loss, float* G, void* dX, void* dXatt, float* dWa,
-                                        float* dba, float* dWt, float* dbt, void* ws, size_t ws_bytes,
-                                        int N, int P, int C, int Ca, int K, int M, unsigned flags,
-                                        float keep_prob, uint64_t seed, uint64_t offset, int dtype,
-                                        void* stream) {
+// The loss as its neighbours can fold it inside one call (M1Xent; bit-identical results, same reduction trees), or
+// false where no fold applies.  The softmax cross-entropy: the logits reduction also does the row's loss and the
+// backward head kernel the batch mean (M == 1, K <= 512), the per-class maps take it in their activation passes.  A
+// sigmoid loss: M == 1 with the fold's shapes, the logits reducer does the rows' loss (m1_logits_ml_kernel); the
+// per-class pc_row_xent folds read integer labels and are not entered.  On clips the loss is taken on the pooled rows:
+// both halves run as the per-op entry points do and G travels through memory.
+static bool step_xent(const StepLoss& L, const PoolDims& d, M1Xent* xf) {
+  if (L.clips || (L.ml && d.M != 1)) return false;
+  xf->labels = L.ml ? nullptr : L.labels; xf->loss = L.loss; xf->G = L.G;
+  if (L.ml) {
+    xf->kind = L.ml->kind; xf->mlabels = L.ml->labels; xf->pos_weight = L.ml->pos_weight;
+    if (d.N > 0 && d.K > 0) ml_scales(L.ml->kind, L.wt, L.grad_scale, d.N, d.K, &xf->lscale, &xf->gscale);
+  } else if (d.N > 0) {
+    xf->lscale = L.wt / (float)d.N;
+    xf->gscale = L.wt * L.grad_scale / (float)d.N;
+  }
+  return true;
+}
+
+// the stand-alone loss on the finished logits; clips: its scratch lies pool_bytes into the workspace
+static int step_loss_run(const StepLoss& L, const PoolCall& d, const float* logits, size_t pool_bytes) {
+  if (PcTrace* t = pc_trace()) if (d.M != 1) t->xent = PC_XENT_OWN;
+  if (L.clips) {
+    const apa_clip_pool& c = *L.clip;
+    const int B = d.N / c.frames;
+    void* const lws = static_cast<char*>(d.ws) + pool_bytes;
+    const size_t lws_bytes = apa_clip_xent_workspace_bytes(B, c.frames, d.K);
+    return L.ml ? apa_clip_multilabel_fwd_bwd(L.ml, logits, c.w, c.b, c.pooled, c.tatt, L.loss, L.G, c.dw, c.db, lws,
+                                              lws_bytes, B, c.frames, d.K, L.wt, L.grad_scale, d.st)
+                : apa_clip_xent_fwd_bwd(logits, L.labels, c.w, c.b, c.pooled, c.tatt, L.loss, L.G, c.dw, c.db, lws,
+                                        lws_bytes, B, c.frames, d.K, L.wt, L.grad_scale, d.st);
+  }
+  return L.ml ? ml_loss_rows(L.ml->kind, L.ml->labels, L.ml->pos_weight, logits, L.loss, L.G, d.N, d.K, L.wt,
+                             L.grad_scale, d.st)
+              : apa_softmax_xent_fwd_bwd(logits, L.labels, L.loss, L.G, nullptr, nullptr, d.N, d.K, L.wt, L.grad_scale,
+                                         d.st);
+}
+
+// What a step refuses about its loss, before anything is launched.  *pool_bytes: the part of the workspace that is the
+// pooling call's -- all of it, or on clips what lies in front of the clip loss's scratch.
+static int head_step_check(const char* fn, const PoolCall& d, const StepLoss& L, const float* logits,
+                           size_t* pool_bytes) {
+  *pool_bytes = d.ws_bytes;
+  if (L.clips) return clip_step_check(fn, d, L, logits, pool_bytes);
+  if ((!L.ml && !L.labels) || !L.loss || !L.G) {
+    set_error("%s: null labels / loss / G pointer", fn);
+    return APA_ERR_INVALID_ARG;
+  }
+  return APA_OK;
+}
+
+// The step every one-call entry point runs on the attention head, head_step_check passed: forward (with the loss folded
+// where step_xent says so), the stand-alone loss unless the forward half took it, backward on the same workspace with
+// nothing in between -- APA_FLAG_WS_FROM_FWD: it may reuse what the forward half prepared there -- and with the M1Xent
+// exactly when there is something left to finish.  Bit-identical to the three separate calls.
+// fwd_iflags / bwd_iflags: flag bits of one half only (the fast route of apa_pose_attn_train_step).
+static int head_step_run(PoolCall d, const StepLoss& L, const M1Fwd& f, const M1Bwd& b, size_t pool_bytes,
+                         unsigned fwd_iflags = 0, unsigned bwd_iflags = 0) {
+  d.ws_bytes = pool_bytes;
+  const unsigned flags = d.flags;
+  M1Xent xf;
+  const bool fold = step_xent(L, d, &xf);
+  d.flags = flags | fwd_iflags;
+  int rc = attn_pool_fwd(d, f, fold ? &xf : nullptr);
+  if (rc != APA_OK) return rc;
+  if (!xf.done && (rc = step_loss_run(L, d, f.logits, pool_bytes)) != APA_OK) return rc;
+  d.flags = flags | APA_FLAG_WS_FROM_FWD | bwd_iflags;
+  return attn_pool_bwd(d, b, xf.done && !xf.finished ? &xf : nullptr);
+}
+
+// fn: the entry point's name for the refusals
+static int head_step(const char* fn, const PoolCall& d, const StepLoss& L, const M1Fwd& f, const M1Bwd& b) {
+  size_t pool_bytes = 0;
+  const int rc = head_step_check(fn, d, L, f.logits, &pool_bytes);
+  return rc != APA_OK ? rc : head_step_run(d, L, f, b, pool_bytes);
+}
+
+extern "C" int apa_attn_head_train_step_ex(const apa_hooks* hooks, const void* X, const void* Xatt, const float* Wa,
+                                           const float* ba, const float* Wt, const float* bt, const int64_t* labels,
+                                           float loss_wt, float grad_scale, float* logits, float* att, float* zsave,
+                                           float* abar, float* loss, float* G, void* dX, void* dXatt, float* dWa,
+                                           float* dba, float* dWt, float* dbt, void* ws, size_t ws_bytes, int N, int P,
+                                           int C, int Ca, int K, int M, unsigned flags, float keep_prob, uint64_t seed,
+                                           uint64_t offset, int dtype, void* stream) {
+  return head_step("apa_attn_head_train_step",
+                   pool_call({N, P, C, Ca, K, M, dtype}, flags, keep_prob, seed, offset, ws, ws_bytes, stream, hooks),
+                   StepLoss{nullptr, labels, false, nullptr, loss_wt, grad_scale, loss, G},
+                   M1Fwd{X, Xatt, Wa, ba, Wt, bt, logits, att, zsave, abar},
+                   M1Bwd{X, Xatt, Wa, Wt, bt, att, zsave, abar, G, dX, dXatt, dWa, dba, dWt, dbt});
+}
+
+extern "C" int apa_attn_head_train_step(const void* X, const void* Xatt, const float* Wa, const float* ba,
+                                        const float* Wt, const float* bt, const int64_t* labels, float loss_wt,
+                                        float grad_scale, float* logits, float* att, float* zsave, float* abar,
+                                        float* loss, float* G, void* dX, void* dXatt, float* dWa, float* dba,
+                                        float* dWt, float* dbt, void* ws, size_t ws_bytes, int N, int P, int C, int Ca,
+                                        int K, int M, unsigned flags, float keep_prob, uint64_t seed, uint64_t offset,
+                                        int dtype, void* stream) {
   return apa_attn_head_train_step_ex(nullptr, X, Xatt, Wa, ba, Wt, bt, labels, loss_wt, grad_scale, logits,
                                      att, zsave, abar, loss, G, dX, dXatt, dWa, dba, dWt, dbt, ws, ws_bytes,
                                      N, P, C, Ca, K, M, flags, keep_prob, seed, offset, dtype, stream);
 }
 
-// ml: the sigmoid action loss of apa_pose_attn_train_step_multilabel (io->labels unused), null: the softmax
-// cross-entropy on io->labels.  The multi-label form promises the bits of the separate calls (apa.h), so it runs the
-// four-call sequence for every shape, as the clip form does: the launches the fast bf16 route shares between
-// neighbouring ops sum in other orders than the per-op kernels (att moves by 2.5e-7, logits 4.4e-7, dWa 9.4e-7).  The
-// loss still rides in the logits reducer inside apa_attn_head_train_step_multilabel.
-static int pose_attn_step(const apa_multilabel* ml, const apa_pose_attn_step_io* io, int N, int P, int C, int Cp,
-                          int J, int K, unsigned flags, float keep_prob, uint64_t seed, uint64_t offset, int dtype,
-                          void* stream) {
+extern "C" int apa_attn_head_train_step_clips(const apa_clip_pool* clip, const apa_hooks* hooks, const void* X,
+                                              const void* Xatt, const float* Wa, const float* ba, const float* Wt,
+                                              const float* bt, const int64_t* labels, float loss_wt, float grad_scale,
+                                              float* logits, float* att, float* zsave, float* abar, float* loss,
+                                              float* G, void* dX, void* dXatt, float* dWa, float* dba, float* dWt,
+                                              float* dbt, void* ws, size_t ws_bytes, int N, int P, int C, int Ca, int K,
+                                              int M, unsigned flags, float keep_prob, uint64_t seed, uint64_t offset,
+                                              int dtype, void* stream) {
+  return head_step("apa_attn_head_train_step_clips",
+                   pool_call({N, P, C, Ca, K, M, dtype}, flags, keep_prob, seed, offset, ws, ws_bytes, stream, hooks),
+                   StepLoss{nullptr, labels, true, clip, loss_wt, grad_scale, loss, G},
+                   M1Fwd{X, Xatt, Wa, ba, Wt, bt, logits, att, zsave, abar},
+                   M1Bwd{X, Xatt, Wa, Wt, bt, att, zsave, abar, G, dX, dXatt, dWa, dba, dWt, dbt});
+}
+
+// clip == NULL: the flat step, apa_attn_head_train_step_ex with the loss exchanged
+extern "C" int apa_attn_head_train_step_multilabel(const apa_multilabel* ml, const apa_clip_pool* clip,
+                                                   const apa_hooks* hooks, const void* X, const void* Xatt,
+                                                   const float* Wa, const float* ba, const float* Wt, const float* bt,
+                                                   float loss_wt, float grad_scale, float* logits, float* att,
+                                                   float* zsave, float* abar, float* loss, float* G, void* dX,
+                                                   void* dXatt, float* dWa, float* dba, float* dWt, float* dbt,
+                                                   void* ws, size_t ws_bytes, int N, int P, int C, int Ca, int K, int M,
+                                                   unsigned flags, float keep_prob, uint64_t seed, uint64_t offset,
+                                                   int dtype, void* stream) {
+  const int rc = check_multilabel("apa_attn_head_train_step_multilabel", ml);
+  if (rc != APA_OK) return rc;
+  return head_step("apa_attn_head_train_step_multilabel",
+                   pool_call({N, P, C, Ca, K, M, dtype}, flags, keep_prob, seed, offset, ws, ws_bytes, stream, hooks),
+                   StepLoss{ml, nullptr, clip != nullptr, clip, loss_wt, grad_scale, loss, G},
+                   M1Fwd{X, Xatt, Wa, ba, Wt, bt, logits, att, zsave, abar},
+                   M1Bwd{X, Xatt, Wa, Wt, bt, att, zsave, abar, G, dX, dXatt, dWa, dba, dWt, dbt});
+}
+
+// ---- the one-call steps of the pose-regularised head (cfg 003) ------------------------------------------------------
+// d: the pooling call of the step (Ca = Cp, M = 1, io's pooling workspace); L: its action loss.
+//
+// The composed route is the four calls a caller without these entry points runs, and the clip and the sigmoid forms
+// promise the bits of those separate calls (apa.h), so they take it for EVERY shape.  The launches the fast bf16 route
+// shares between neighbouring ops (attention logits out of the Pl product's epilogue, dWa / dba on the pose head's
+// backward rows pass, the pooling pass's dX share in the dX product's epilogue) sum in other orders than the per-op
+// kernels -- att moves by 2.5e-7, logits 4.4e-7, dWa 9.4e-7, dX by a bf16 ulp; the bf16 operand copies in io (W1_bf16,
+// W2T_bf16) are not read there.  A sigmoid loss still rides in the logits reducer inside head_step.
+static int pose_attn_step(const char* fn, const apa_pose_attn_step_io* io, PoolCall d, StepLoss L, int J) {
   if (!io) {
-    set_error("apa_pose_attn_train_step: null io");
+    set_error("%s: null io", fn);
     return APA_ERR_INVALID_ARG;
   }
   const apa_pose_attn_step_io& s = *io;
-  if (!s.X || !s.W1 || !s.b1 || !s.W2 || !s.b2 || !s.Wa || !s.ba || !s.Wt || !s.bt || (!ml && !s.labels) ||
+  if (!s.X || !s.W1 || !s.b1 || !s.W2 || !s.b2 || !s.Wa || !s.ba || !s.Wt || !s.bt || (!L.ml && !s.labels) ||
       !s.pose_labels || !s.pose_valid || !s.Ppre || !s.Pl || !s.att || !s.logits || !s.zsave || !s.abar ||
       !s.loss_action || !s.loss_pose || !s.G || !s.dPl || !s.dZ || !s.dX || !s.dW1 || !s.db1 || !s.dW2 || !s.db2 ||
       !s.dWa || !s.dba || !s.dWt || !s.dbt || !s.ws_pool || !s.ws_pose) {
-    set_error("apa_pose_attn_train_step: null pointer in apa_pose_attn_step_io (only W1_bf16 / W2T_bf16 may be NULL)");
+    set_error("%s: null pointer in apa_pose_attn_step_io (only W1_bf16 / W2T_bf16 may be NULL)", fn);
     return APA_ERR_INVALID_ARG;
   }
-  int rc = check_common("apa_pose_attn_train_step", N, P, C, Cp, K, 1, dtype);
+  // (on clips the shape is checked with the clip itself, in head_step_check below: a null clip is reported first)
+  int rc = L.clips ? APA_OK : check_common(fn, d);
   if (rc != APA_OK) return rc;
   if (J <= 0) {
-    set_error("apa_pose_attn_train_step: J=%d", J);
+    set_error("%s: J=%d", fn, J);
     return APA_ERR_INVALID_ARG;
   }
-  if (flags & (APA_FLAG_RELU_INPUT | APA_FLAG_RNG_EXTERNAL)) {
-    set_error("apa_pose_attn_train_step: APA_FLAG_RELU_INPUT / APA_FLAG_RNG_EXTERNAL are served by the per-op entry "
-              "points (the attention input of cfg 003 is pose_pre_logits; a replayed mask takes the generic kernels)");
+  if (d.flags & (APA_FLAG_RELU_INPUT | APA_FLAG_RNG_EXTERNAL)) {
+    set_error("%s: APA_FLAG_RELU_INPUT / APA_FLAG_RNG_EXTERNAL are served by the per-op entry points (the attention "
+              "input of cfg 003 is pose_pre_logits; a replayed mask takes the generic kernels)", fn);
     return APA_ERR_UNSUPPORTED;
   }
-  flags &= APA_PUBLIC_FLAGS & ~(APA_FLAG_WS_FROM_FWD | APA_FLAG_DXATT_RANK1);
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  const bool train = (flags & APA_FLAG_TRAIN) && keep_prob < 1.0f;
-  const bool fast = !ml && pose_step_fast_ok(N, P, C, Cp, J, dtype, s.Ppre, s.W2, s.Wa) && m1_supported(C, Cp, dtype, false) &&
-                    m1_small_route_ok(C, K, s.G, s.Wt, s.zsave);
+  const int N = d.N, P = d.P, C = d.C, Cp = d.Ca, K = d.K, dtype = d.dtype;
+  d.ws = s.ws_pool; d.ws_bytes = s.ws_pool_bytes;
+  L.labels = s.labels; L.wt = s.action_wt; L.grad_scale = s.grad_scale; L.loss = s.loss_action; L.G = s.G;
+  size_t pool_bytes = 0;   // everything the loss would refuse, the clip's defects among it, before the first launch
+  if ((rc = head_step_check(fn, d, L, s.logits, &pool_bytes)) != APA_OK) return rc;
+  const M1Fwd f{s.X, s.Ppre, s.Wa, s.ba, s.Wt, s.bt, s.logits, s.att, s.zsave, s.abar};
+  const M1Bwd b{s.X, s.Ppre, s.Wa, s.Wt, s.bt, s.att, s.zsave, s.abar, s.G, s.dX, s.dZ, s.dWa, s.dba, s.dWt, s.dbt};
+  const bool train = (d.flags & APA_FLAG_TRAIN) && d.keep_prob < 1.0f;
+  const bool fast = !L.clips && !L.ml && pose_step_fast_ok(N, P, C, Cp, J, dtype, s.Ppre, s.W2, s.Wa) &&
+                    m1_supported(C, Cp, dtype, false) && m1_small_route_ok(C, K, s.G, s.Wt, s.zsave);
   if (!fast) {
-    // the same step as four calls (what a caller without this entry point runs)
     rc = apa_pose_head_fwd(s.X, s.W1, s.b1, s.W2, s.b2, s.Ppre, s.Pl, s.ws_pose, s.ws_pose_bytes, N, P, C, Cp, J,
-                           dtype, stream);
+                           dtype, d.st);
     if (rc != APA_OK) return rc;
     rc = apa_pose_l2_loss_fwd_bwd(s.Pl, s.pose_labels, s.pose_valid, s.loss_pose, s.dPl,
                                   pose_ws_loss_scratch(s.ws_pose, N, P, C, Cp, J, dtype),
-                                  apa_pose_l2_workspace_bytes(N, P, J), N, P, J, s.pose_wt, s.grad_scale, stream);
+                                  apa_pose_l2_workspace_bytes(N, P, J), N, P, J, s.pose_wt, s.grad_scale, d.st);
     if (rc != APA_OK) return rc;
-    rc = ml ? apa_attn_head_train_step_multilabel(ml, nullptr, nullptr, s.X, s.Ppre, s.Wa, s.ba, s.Wt, s.bt,
-                                                  s.action_wt, s.grad_scale, s.logits, s.att, s.zsave, s.abar,
-                                                  s.loss_action, s.G, s.dX, s.dZ, s.dWa, s.dba, s.dWt, s.dbt,
-                                                  s.ws_pool, s.ws_pool_bytes, N, P, C, Cp, K, 1,
-                                                  flags | APA_FLAG_DXATT_RANK1, keep_prob, seed, offset, dtype, stream)
-            : apa_attn_head_train_step_ex(nullptr, s.X, s.Ppre, s.Wa, s.ba, s.Wt, s.bt, s.labels, s.action_wt,
-                                     s.grad_scale, s.logits, s.att, s.zsave, s.abar, s.loss_action, s.G, s.dX,
-                                     s.dZ, s.dWa, s.dba, s.dWt, s.dbt, s.ws_pool, s.ws_pool_bytes, N, P, C, Cp, K,
-                                     1, flags | APA_FLAG_DXATT_RANK1, keep_prob, seed, offset, dtype, stream);
+    d.flags |= APA_FLAG_DXATT_RANK1;   // s.dZ receives dZ itself; apa_pose_head_bwd_rank1ext re-forms dXatt from it
+    rc = head_step_run(d, L, f, b, pool_bytes);
     if (rc != APA_OK) return rc;
     return apa_pose_head_bwd_rank1ext(s.X, s.W1, s.W2, s.Ppre, s.dPl, s.dZ, s.Wa, s.dX, 1 | APA_POSE_WS_FROM_FWD,
                                       s.dW1, s.db1, s.dW2, s.db2, s.ws_pose, s.ws_pose_bytes, N, P, C, Cp, J, dtype,
-                                      stream);
+                                      d.st);
   }
   PoseStepArgs a;
   // a caller-kept bf16 copy of W1 is an OPTIMISATION: apa_momentum_sgd_step_shadow accepts any 4-byte aligned
@@ -516,27 +573,12 @@ static int pose_attn_step(const apa_multilabel* ml, const apa_pose_attn_step_io*
   a.W1_bf16 = (reinterpret_cast<uintptr_t>(s.W1_bf16) & 15) == 0 ? s.W1_bf16 : nullptr;
   a.W2T_bf16 = (reinterpret_cast<uintptr_t>(s.W2T_bf16) & 15) == 0 ? s.W2T_bf16 : nullptr;
   a.wa = s.Wa; a.ba = s.ba; a.att = s.att;
-  a.relu_att = (flags & APA_FLAG_RELU_ATT) && !(flags & APA_FLAG_SOFTMAX_ATT);
+  a.relu_att = (d.flags & APA_FLAG_RELU_ATT) && !(d.flags & APA_FLAG_SOFTMAX_ATT);
   a.pose_labels = s.pose_labels; a.pose_valid = s.pose_valid; a.dPl = s.dPl;
   a.pose_wt = s.pose_wt; a.grad_scale = s.grad_scale;
   rc = pose_fwd_fused(s.X, s.W1, s.b1, s.W2, s.b2, s.Ppre, s.Pl, s.ws_pose, s.ws_pose_bytes, N, P, C, Cp, J, dtype,
-                      a, st);
+                      a, d.st);
   if (rc != APA_OK) return rc;
-  M1Xent xf;
-  xf.labels = s.labels; xf.loss = s.loss_action; xf.G = s.G;
-  xf.lscale = s.action_wt / (float)N;
-  xf.gscale = s.action_wt * s.grad_scale / (float)N;
-  xf.done = false;
-  const Hooks hk;
-  rc = attn_pool_fwd_impl(hk, nullptr, &xf, s.X, s.Ppre, s.Wa, s.ba, s.Wt, s.bt, s.logits, s.att, s.zsave, s.abar,
-                          nullptr, s.ws_pool, s.ws_pool_bytes, N, P, C, Cp, K, 1, flags | APA_IFLAG_ATT_READY,
-                          keep_prob, seed, offset, dtype, stream);
-  if (rc != APA_OK) return rc;
-  if (!xf.done) {
-    rc = apa_softmax_xent_fwd_bwd(s.logits, s.labels, s.loss_action, s.G, nullptr, nullptr, N, K, s.action_wt,
-                                  s.grad_scale, stream);
-    if (rc != APA_OK) return rc;
-  }
   // The pooling pass's own dX share (A/P . dz . mask/keep) is not written and read back: the streaming backward
   // kernel becomes read-only (APA_IFLAG_NO_DX) and the pose head's dX product adds the term in its epilogue from att,
   // dz and the forward half's keep bits -- one 25.7 MB write and one 25.7 MB read less at the benchmark shape.
@@ -547,11 +589,9 @@ static int pose_attn_step(const apa_multilabel* ml, const apa_pose_attn_step_io*
   const bool nodx = m1_no_dx_supported(C, dtype, train) && wide_rows > 0 && wide_rows <= 2 * P &&
                     (reinterpret_cast<uintptr_t>(s.dX) & 15) == 0 && C % 8 == 0 && Cp % 8 == 0 &&
                     dtype == APA_DTYPE_BF16;
-  rc = attn_pool_bwd_impl(hk, nullptr, xf.done ? &xf : nullptr, s.X, s.Ppre, s.Wa, s.ba, s.Wt, s.bt, s.att, s.zsave,
-                          s.abar, s.G, s.dX, s.dZ, s.dWa, s.dba, s.dWt, s.dbt, s.ws_pool, s.ws_pool_bytes, N, P, C,
-                          Cp, K, 1, flags | APA_FLAG_DXATT_RANK1 | APA_FLAG_WS_FROM_FWD | APA_IFLAG_NO_ATT_WGRAD |
-                              (nodx ? APA_IFLAG_NO_DX : 0u),
-                          keep_prob, seed, offset, dtype, stream);
+  // the pose head's Pl kernel left the attention in place; its backward rows pass takes dWa / dba and the RNG bump
+  rc = head_step_run(d, L, f, b, pool_bytes, APA_IFLAG_ATT_READY,
+                     APA_FLAG_DXATT_RANK1 | APA_IFLAG_NO_ATT_WGRAD | (nodx ? APA_IFLAG_NO_DX : 0u));
   if (rc != APA_OK) return rc;
   if (nodx) {
     const M1Plan mp = m1_plan(N, P, C, Cp, K);
@@ -559,207 +599,41 @@ static int pose_attn_step(const apa_multilabel* ml, const apa_pose_attn_step_io*
     a.pool_att = s.att;
     a.pool_dz = reinterpret_cast<const float*>(wp + mp.off_dz);
     a.pool_bits = reinterpret_cast<const uint8_t*>(wp + mp.off_maskbits);
-    a.pool_inv_keep = 1.0f / keep_prob;
+    a.pool_inv_keep = 1.0f / d.keep_prob;
   }
-  uint64_t* bump = (train && (flags & APA_FLAG_RNG_DEVICE))
-                       ? reinterpret_cast<uint64_t*>(static_cast<uintptr_t>(offset)) : nullptr;
+  uint64_t* bump = (train && (d.flags & APA_FLAG_RNG_DEVICE))
+                       ? reinterpret_cast<uint64_t*>(static_cast<uintptr_t>(d.offset)) : nullptr;
   // (same workspace, same call: the bf16 copy of W1 the forward half built there -- when the caller keeps none -- is reused)
   return pose_bwd_fused(s.X, s.W1, s.W2, s.Ppre, s.dPl, s.dZ, s.Wa, s.dX, 1 | APA_POSE_WS_FROM_FWD, s.dW1, s.db1, s.dW2,
-                        s.db2, s.dWa, s.dba, s.loss_pose, bump, s.ws_pose, s.ws_pose_bytes, N, P, C, Cp, J, dtype, a, st);
+                        s.db2, s.dWa, s.dba, s.loss_pose, bump, s.ws_pose, s.ws_pose_bytes, N, P, C, Cp, J, dtype, a,
+                        d.st);
 }
 
-extern "C" int apa_pose_attn_train_step(const apa_pose_attn_step_io* io, int N, int P, int C, int Cp, int J,
-                                        int K, unsigned flags, float keep_prob, uint64_t seed, uint64_t offset,
-                                        int dtype, void* stream) {
-  return pose_attn_step(nullptr, io, N, P, C, Cp, J, K, flags, keep_prob, seed, offset, dtype, stream);
-}
-
-// ---- the one-call steps on a batch of clips (apa.h: apa_clip_pool) -------------------------------------------------
-// the pooling workspace, then the clip loss's scratch
-static size_t clip_step_pool_bytes(int N, int P, int C, int Ca, int K, int M, unsigned flags) {
-  return align_up(apa_attn_pool_workspace_bytes(N, P, C, Ca, K, M, flags), 256);
-}
-
-extern "C" size_t apa_clip_step_workspace_bytes(int N, int frames, int P, int C, int Ca, int K, int M,
-                                                unsigned flags) {
-  if (N <= 0 || frames <= 0 || N % frames != 0) return 0;
-  const size_t pool = apa_attn_pool_workspace_bytes(N, P, C, Ca, K, M, flags);
-  return pool ? clip_step_pool_bytes(N, P, C, Ca, K, M, flags) + apa_clip_xent_workspace_bytes(N / frames, frames, K)
-              : 0;
-}
-
-// everything apa_clip_xent_fwd_bwd would refuse, BEFORE the forward half is launched; *clip_ws: the loss's scratch
-static int clip_step_check(const char* fn, const apa_clip_pool* clip, const void* labels, const float* loss,
-                           const float* logits, const float* G, void* ws, size_t ws_bytes, int N, int P, int C,
-                           int Ca, int K, int M, unsigned flags, int dtype, size_t* pool_bytes) {
-  if (!clip || !labels || !loss || !logits || !G) {
-    set_error("%s: null clip / labels / loss / logits / G pointer", fn);
-    return APA_ERR_INVALID_ARG;
-  }
-  const int rc = check_common(fn, N, P, C, Ca, K, M, dtype);
-  if (rc != APA_OK) return rc;
-  if (clip->frames <= 0 || N % clip->frames != 0) {
-    set_error("%s: N=%d is not a whole number of clips of %d frames", fn, N, clip->frames);
-    return APA_ERR_INVALID_ARG;
-  }
-  if (!clip->pooled || (clip->w && (!clip->b || !clip->tatt || !clip->dw || !clip->db))) {
-    set_error("%s: apa_clip_pool needs pooled, and with w also b, tatt, dw and db", fn);
-    return APA_ERR_INVALID_ARG;
-  }
-  *pool_bytes = clip_step_pool_bytes(N, P, C, Ca, K, M, flags);
-  const size_t need = *pool_bytes + apa_clip_xent_workspace_bytes(N / clip->frames, clip->frames, K);
-  if (!ws || ws_bytes < need) {
-    set_error("%s: workspace too small (%zu < %zu = apa_clip_step_workspace_bytes)", fn, ws_bytes, need);
-    return APA_ERR_WORKSPACE;
-  }
-  return APA_OK;
-}
-
-static int clip_step_loss(const apa_multilabel* ml, const apa_clip_pool& c, const float* logits, const int64_t* labels,
-                          float* loss, float* G, void* ws, size_t pool_bytes, int N, int K, float wt, float grad_scale,
-                          void* stream) {
-  const int B = N / c.frames;
-  if (ml)
-    return apa_clip_multilabel_fwd_bwd(ml, logits, c.w, c.b, c.pooled, c.tatt, loss, G, c.dw, c.db,
-                                       static_cast<char*>(ws) + pool_bytes,
-                                       apa_clip_xent_workspace_bytes(B, c.frames, K), B, c.frames, K, wt, grad_scale,
-                                       stream);
-  return apa_clip_xent_fwd_bwd(logits, labels, c.w, c.b, c.pooled, c.tatt, loss, G, c.dw, c.db,
-                               static_cast<char*>(ws) + pool_bytes, apa_clip_xent_workspace_bytes(B, c.frames, K), B,
-                               c.frames, K, wt, grad_scale, stream);
-}
-
-// fn: the entry point's name for the refusals; ml: the sigmoid clip loss (labels unused), null: the cross-entropy
-static int head_step_clips(const char* fn, const apa_multilabel* ml, const apa_clip_pool* clip, const apa_hooks* hooks,
-                           const void* X, const void* Xatt, const float* Wa, const float* ba, const float* Wt,
-                           const float* bt, const int64_t* labels, float loss_wt, float grad_scale, float* logits,
-                           float* att, float* zsave, float* abar, float* loss, float* G, void* dX, void* dXatt,
-                           float* dWa, float* dba, float* dWt, float* dbt, void* ws, size_t ws_bytes, int N, int P,
-                           int C, int Ca, int K, int M, unsigned flags, float keep_prob, uint64_t seed,
-                           uint64_t offset, int dtype, void* stream) {
-  const Hooks hk(hooks);
-  flags &= APA_PUBLIC_FLAGS;
-  size_t pool_bytes = 0;
-  int rc = clip_step_check(fn, clip, ml ? static_cast<const void*>(ml->labels) : labels, loss, logits, G, ws, ws_bytes,
-                           N, P, C, Ca, K, M, flags, dtype, &pool_bytes);
-  if (rc != APA_OK) return rc;
-  // the per-image cross-entropy the flat step folds into its neighbours (M1Xent) has no place here: the loss is
-  // taken on the pooled rows, so both halves run as the per-op entry points do and G travels through memory
-  rc = attn_pool_fwd_impl(hk, nullptr, nullptr, X, Xatt, Wa, ba, Wt, bt, logits, att, zsave, abar, nullptr, ws,
-                          pool_bytes, N, P, C, Ca, K, M, flags, keep_prob, seed, offset, dtype, stream);
-  if (rc != APA_OK) return rc;
-  rc = clip_step_loss(ml, *clip, logits, labels, loss, G, ws, pool_bytes, N, K, loss_wt, grad_scale, stream);
-  if (rc != APA_OK) return rc;
-  // same workspace, nothing in between (the loss's scratch lies behind it)
-  return attn_pool_bwd_impl(hk, nullptr, nullptr, X, Xatt, Wa, ba, Wt, bt, att, zsave, abar, G, dX, dXatt, dWa, dba,
-                            dWt, dbt, ws, pool_bytes, N, P, C, Ca, K, M, flags | APA_FLAG_WS_FROM_FWD, keep_prob, seed,
-                            offset, dtype, stream);
-}
-
-extern "C" int apa_attn_head_train_step_clips(const apa_clip_pool* clip, const apa_hooks* hooks, const void* X,
-                                              const void* Xatt, const float* Wa, const float* ba, const float* Wt,
-                                              const float* bt, const int64_t* labels, float loss_wt,
-                                              float grad_scale, float* logits, float* att, float* zsave,
-                                              float* abar, float* loss, float* G, void* dX, void* dXatt,
-                                              float* dWa, float* dba, float* dWt, float* dbt, void* ws,
-                                              size_t ws_bytes, int N, int P, int C, int Ca, int K, int M,
-                                              unsigned flags, float keep_prob, uint64_t seed, uint64_t offset,
-                                              int dtype, void* stream) {
-  return head_step_clips("apa_attn_head_train_step_clips", nullptr, clip, hooks, X, Xatt, Wa, ba, Wt, bt, labels,
-                         loss_wt, grad_scale, logits, att, zsave, abar, loss, G, dX, dXatt, dWa, dba, dWt, dbt, ws,
-                         ws_bytes, N, P, C, Ca, K, M, flags, keep_prob, seed, offset, dtype, stream);
-}
-
-extern "C" int apa_attn_head_train_step_multilabel(const apa_multilabel* ml, const apa_clip_pool* clip,
-                                                   const apa_hooks* hooks, const void* X, const void* Xatt,
-                                                   const float* Wa, const float* ba, const float* Wt, const float* bt,
-                                                   float loss_wt, float grad_scale, float* logits, float* att,
-                                                   float* zsave, float* abar, float* loss, float* G, void* dX,
-                                                   void* dXatt, float* dWa, float* dba, float* dWt, float* dbt,
-                                                   void* ws, size_t ws_bytes, int N, int P, int C, int Ca, int K,
-                                                   int M, unsigned flags, float keep_prob, uint64_t seed,
-                                                   uint64_t offset, int dtype, void* stream) {
-  const int rc = check_multilabel("apa_attn_head_train_step_multilabel", ml);
-  if (rc != APA_OK) return rc;
-  if (clip)
-    return head_step_clips("apa_attn_head_train_step_multilabel", ml, clip, hooks, X, Xatt, Wa, ba, Wt, bt, nullptr,
-                           loss_wt, grad_scale, logits, att, zsave, abar, loss, G, dX, dXatt, dWa, dba, dWt, dbt, ws,
-                           ws_bytes, N, P, C, Ca, K, M, flags, keep_prob, seed, offset, dtype, stream);
-  if (!loss || !G) {
-    set_error("apa_attn_head_train_step_multilabel: null loss / G pointer");
-    return APA_ERR_INVALID_ARG;
-  }
-  return head_step_multilabel(*ml, Hooks(hooks), X, Xatt, Wa, ba, Wt, bt, loss_wt, grad_scale, logits, att, zsave,
-                              abar, loss, G, dX, dXatt, dWa, dba, dWt, dbt, ws, ws_bytes, N, P, C, Ca, K, M,
-                              flags & APA_PUBLIC_FLAGS, keep_prob, seed, offset, dtype, stream);
-}
-
-// apa_pose_attn_train_step's composed route with the clip loss in place of the per-image cross-entropy
-static int pose_attn_step_clips(const apa_multilabel* ml, const apa_clip_pool* clip, const apa_pose_attn_step_io* io,
-                                int N, int P, int C, int Cp, int J, int K, unsigned flags, float keep_prob,
-                                uint64_t seed, uint64_t offset, int dtype, void* stream) {
-  if (!io) {
-    set_error("apa_pose_attn_train_step_clips: null io");
-    return APA_ERR_INVALID_ARG;
-  }
-  const apa_pose_attn_step_io& s = *io;
-  if (!s.X || !s.W1 || !s.b1 || !s.W2 || !s.b2 || !s.Wa || !s.ba || !s.Wt || !s.bt || (!ml && !s.labels) ||
-      !s.pose_labels || !s.pose_valid || !s.Ppre || !s.Pl || !s.att || !s.logits || !s.zsave || !s.abar ||
-      !s.loss_action || !s.loss_pose || !s.G || !s.dPl || !s.dZ || !s.dX || !s.dW1 || !s.db1 || !s.dW2 || !s.db2 ||
-      !s.dWa || !s.dba || !s.dWt || !s.dbt || !s.ws_pool || !s.ws_pose) {
-    set_error("apa_pose_attn_train_step_clips: null pointer in apa_pose_attn_step_io (only W1_bf16 / W2T_bf16 may be NULL)");
-    return APA_ERR_INVALID_ARG;
-  }
-  if (J <= 0) {
-    set_error("apa_pose_attn_train_step_clips: J=%d", J);
-    return APA_ERR_INVALID_ARG;
-  }
-  if (flags & (APA_FLAG_RELU_INPUT | APA_FLAG_RNG_EXTERNAL)) {
-    set_error("apa_pose_attn_train_step_clips: APA_FLAG_RELU_INPUT / APA_FLAG_RNG_EXTERNAL are served by the per-op "
-              "entry points");
-    return APA_ERR_UNSUPPORTED;
-  }
-  flags &= APA_PUBLIC_FLAGS & ~(APA_FLAG_WS_FROM_FWD | APA_FLAG_DXATT_RANK1);
-  size_t pool_bytes = 0;
-  int rc = clip_step_check("apa_pose_attn_train_step_clips", clip,
-                           ml ? static_cast<const void*>(ml->labels) : s.labels, s.loss_action, s.logits, s.G, s.ws_pool,
-                           s.ws_pool_bytes, N, P, C, Cp, K, 1, flags, dtype, &pool_bytes);
-  if (rc != APA_OK) return rc;
-  // The four calls a caller without this entry point runs, for EVERY shape.  The launches apa_pose_attn_train_step
-  // shares between neighbouring ops on its fast bf16 route (attention logits out of the Pl product's epilogue, dWa / dba
-  // on the pose head's backward rows pass, the pooling pass's dX share in the dX product's epilogue) sum in other
-  // orders than the per-op kernels -- att moves by 2.5e-7, dX by a bf16 ulp -- and this entry point promises the bits
-  // of the separate calls (apa.h); the bf16 operand copies in io (W1_bf16, W2T_bf16) are not read here.
-  rc = apa_pose_head_fwd(s.X, s.W1, s.b1, s.W2, s.b2, s.Ppre, s.Pl, s.ws_pose, s.ws_pose_bytes, N, P, C, Cp, J, dtype,
-                         stream);
-  if (rc != APA_OK) return rc;
-  rc = apa_pose_l2_loss_fwd_bwd(s.Pl, s.pose_labels, s.pose_valid, s.loss_pose, s.dPl,
-                                pose_ws_loss_scratch(s.ws_pose, N, P, C, Cp, J, dtype),
-                                apa_pose_l2_workspace_bytes(N, P, J), N, P, J, s.pose_wt, s.grad_scale, stream);
-  if (rc != APA_OK) return rc;
-  rc = head_step_clips("apa_pose_attn_train_step_clips", ml, clip, nullptr, s.X, s.Ppre, s.Wa, s.ba, s.Wt, s.bt,
-                       s.labels, s.action_wt, s.grad_scale, s.logits, s.att, s.zsave, s.abar, s.loss_action, s.G, s.dX,
-                       s.dZ, s.dWa, s.dba, s.dWt, s.dbt, s.ws_pool, s.ws_pool_bytes, N, P, C, Cp, K, 1,
-                       flags | APA_FLAG_DXATT_RANK1, keep_prob, seed, offset, dtype, stream);
-  if (rc != APA_OK) return rc;
-  return apa_pose_head_bwd_rank1ext(s.X, s.W1, s.W2, s.Ppre, s.dPl, s.dZ, s.Wa, s.dX, 1 | APA_POSE_WS_FROM_FWD, s.dW1,
-                                    s.db1, s.dW2, s.db2, s.ws_pose, s.ws_pose_bytes, N, P, C, Cp, J, dtype, stream);
+extern "C" int apa_pose_attn_train_step(const apa_pose_attn_step_io* io, int N, int P, int C, int Cp, int J, int K,
+                                        unsigned flags, float keep_prob, uint64_t seed, uint64_t offset, int dtype,
+                                        void* stream) {
+  return pose_attn_step("apa_pose_attn_train_step", io,
+                        pool_call({N, P, C, Cp, K, 1, dtype}, flags, keep_prob, seed, offset, nullptr, 0, stream),
+                        StepLoss{}, J);
 }
 
 extern "C" int apa_pose_attn_train_step_clips(const apa_clip_pool* clip, const apa_pose_attn_step_io* io, int N, int P,
                                               int C, int Cp, int J, int K, unsigned flags, float keep_prob,
                                               uint64_t seed, uint64_t offset, int dtype, void* stream) {
-  return pose_attn_step_clips(nullptr, clip, io, N, P, C, Cp, J, K, flags, keep_prob, seed, offset, dtype, stream);
+  return pose_attn_step("apa_pose_attn_train_step_clips", io,
+                        pool_call({N, P, C, Cp, K, 1, dtype}, flags, keep_prob, seed, offset, nullptr, 0, stream),
+                        StepLoss{nullptr, nullptr, true, clip}, J);
 }
 
 extern "C" int apa_pose_attn_train_step_multilabel(const apa_multilabel* ml, const apa_clip_pool* clip,
-                                                   const apa_pose_attn_step_io* io, int N, int P, int C, int Cp,
-                                                   int J, int K, unsigned flags, float keep_prob, uint64_t seed,
+                                                   const apa_pose_attn_step_io* io, int N, int P, int C, int Cp, int J,
+                                                   int K, unsigned flags, float keep_prob, uint64_t seed,
                                                    uint64_t offset, int dtype, void* stream) {
   const int rc = check_multilabel("apa_pose_attn_train_step_multilabel", ml);
   if (rc != APA_OK) return rc;
-  return clip ? pose_attn_step_clips(ml, clip, io, N, P, C, Cp, J, K, flags, keep_prob, seed, offset, dtype, stream)
-              : pose_attn_step(ml, io, N, P, C, Cp, J, K, flags, keep_prob, seed, offset, dtype, stream);
+  return pose_attn_step("apa_pose_attn_train_step_multilabel", io,
+                        pool_call({N, P, C, Cp, K, 1, dtype}, flags, keep_prob, seed, offset, nullptr, 0, stream),
+                        StepLoss{ml, nullptr, clip != nullptr, clip}, J);
 }
 
 extern "C" int apa_per_class_weight_images(const float* Wa, const float* ba, const float* Wt, const float* bt, void* ws,
@@ -770,62 +644,59 @@ extern "C" int apa_per_class_weight_images(const float* Wa, const float* ba, con
     set_error("apa_per_class_weight_images: null parameter pointer");
     return APA_ERR_INVALID_ARG;
   }
-  int rc = check_common("apa_per_class_weight_images", N, P, C, Ca, K, K, dtype);
+  const PoolCall d = pool_call({N, P, C, Ca, K, K, dtype}, 0u, 1.0f, 0, 0, ws, ws_bytes, stream);
+  const int rc = check_common("apa_per_class_weight_images", d);
   if (rc != APA_OK) return rc;
   const size_t need = pc_workspace_bytes(N, P, C, Ca, K, dtype);
   if (!ws || ws_bytes < need) {
     set_error("apa_per_class_weight_images: workspace too small (%zu < %zu)", ws_bytes, need);
     return APA_ERR_WORKSPACE;
   }
-  return pc_weight_images(Wa, ba, Wt, bt, ws, N, P, C, Ca, K, dtype, maps, nmaps, static_cast<hipStream_t>(stream));
+  return pc_weight_images(d, Wa, ba, Wt, bt, maps, nmaps);
 }
 
-// iflags: library-internal flag bits added to the pooling call (APA_IFLAG_ATT_READY from apa_pose_attn_eval_step)
-static int attn_head_eval_impl(const void* X, const void* Xatt, const float* Wa, const float* ba,
-                               const float* Wt, const float* bt, const int64_t* labels,
-                               float* logits, float* att, float* zsave, float* abar, float* loss,
-                               float* probs, int64_t* pred, void* ws, size_t ws_bytes, int N,
-                               int P, int C, int Ca, int K, int M, unsigned flags, unsigned iflags, int dtype,
-                               void* stream) {
+// the scratch of the label-free evaluation form at the head of the pooling workspace: labels [N] (0 everywhere), then
+// the loss slots [1+N]
+static size_t eval_scratch_bytes(int N) { return align_up((size_t)N * 8 + (size_t)(1 + N) * 4, 256); }
+
+// d.flags: the caller's, plus internal bits (APA_IFLAG_ATT_READY from apa_pose_attn_eval_step)
+static int attn_head_eval(PoolCall d, const M1Fwd& f, const int64_t* labels, float* loss, float* probs,
+                          int64_t* pred) {
   if (!probs || !pred) {
-    apa::set_error("apa_attn_head_eval_step: null probs / pred pointer");
+    set_error("apa_attn_head_eval_step: null probs / pred pointer");
     return APA_ERR_INVALID_ARG;
   }
   if ((labels == nullptr) != (loss == nullptr)) {
-    apa::set_error("apa_attn_head_eval_step: labels and loss must be given together");
+    set_error("apa_attn_head_eval_step: labels and loss must be given together");
     return APA_ERR_INVALID_ARG;
   }
-  const unsigned eval_flags = (flags & APA_PUBLIC_FLAGS & ~(unsigned)APA_FLAG_TRAIN) | iflags;   // is_training=False: no dropout
+  d.flags &= ~(unsigned)APA_FLAG_TRAIN;   // is_training=False: no dropout
   // without ground truth the softmax / argmax of a row rides on the logits reduction (M == 1, K <= 512)
   M1Xent xf;
-  xf.labels = nullptr; xf.loss = nullptr; xf.G = nullptr; xf.gscale = 0.f; xf.lscale = 0.f; xf.done = false;
   xf.probs = probs; xf.pred = pred;
-  int rc = attn_pool_fwd_impl(Hooks(), nullptr, (M == 1 && !labels) ? &xf : nullptr, X, Xatt, Wa, ba, Wt, bt, logits, att, zsave, abar, nullptr, ws,
-                              ws_bytes, N, P, C, Ca, K, M, eval_flags, 1.0f, 0, 0, dtype, stream);
+  int rc = attn_pool_fwd(d, f, (d.M == 1 && !labels) ? &xf : nullptr);
   if (rc != APA_OK || xf.done) return rc;
-  if (PcTrace* t = pc_trace()) if (M != 1) t->xent = PC_XENT_OWN;
+  if (PcTrace* t = pc_trace()) if (d.M != 1) t->xent = PC_XENT_OWN;
   if (labels)
-    return apa_softmax_xent_fwd_bwd(logits, labels, loss, nullptr, probs, pred, N, K, 1.0f, 1.0f, stream);
+    return apa_softmax_xent_fwd_bwd(f.logits, labels, loss, nullptr, probs, pred, d.N, d.K, 1.0f, 1.0f, d.st);
   // no ground truth: the loss slots are scratch at the head of the workspace (label 0 everywhere)
-  const size_t need = ((size_t)N * 8 + (size_t)(1 + N) * 4 + 255) / 256 * 256;
-  if (ws_bytes < need) {
-    apa::set_error("apa_attn_head_eval_step: workspace too small for the label-free form");
+  if (d.ws_bytes < eval_scratch_bytes(d.N)) {
+    set_error("apa_attn_head_eval_step: workspace too small for the label-free form");
     return APA_ERR_WORKSPACE;
   }
-  APA_HIP_CHECK(hipMemsetAsync(ws, 0, (size_t)N * 8, static_cast<hipStream_t>(stream)));
-  float* lscratch = reinterpret_cast<float*>(static_cast<char*>(ws) + (size_t)N * 8);
-  return apa_softmax_xent_fwd_bwd(logits, static_cast<const int64_t*>(ws), lscratch, nullptr, probs, pred,
-                                  N, K, 1.0f, 1.0f, stream);
+  APA_HIP_CHECK(hipMemsetAsync(d.ws, 0, (size_t)d.N * 8, d.st));
+  float* lscratch = reinterpret_cast<float*>(static_cast<char*>(d.ws) + (size_t)d.N * 8);
+  return apa_softmax_xent_fwd_bwd(f.logits, static_cast<const int64_t*>(d.ws), lscratch, nullptr, probs, pred, d.N,
+                                  d.K, 1.0f, 1.0f, d.st);
 }
 
 extern "C" int apa_attn_head_eval_step(const void* X, const void* Xatt, const float* Wa, const float* ba,
-                                       const float* Wt, const float* bt, const int64_t* labels,
-                                       float* logits, float* att, float* zsave, float* abar, float* loss,
-                                       float* probs, int64_t* pred, void* ws, size_t ws_bytes, int N,
-                                       int P, int C, int Ca, int K, int M, unsigned flags, int dtype,
-                                       void* stream) {
-  return attn_head_eval_impl(X, Xatt, Wa, ba, Wt, bt, labels, logits, att, zsave, abar, loss, probs, pred, ws, ws_bytes,
-                             N, P, C, Ca, K, M, flags, 0u, dtype, stream);
+                                       const float* Wt, const float* bt, const int64_t* labels, float* logits,
+                                       float* att, float* zsave, float* abar, float* loss, float* probs, int64_t* pred,
+                                       void* ws, size_t ws_bytes, int N, int P, int C, int Ca, int K, int M,
+                                       unsigned flags, int dtype, void* stream) {
+  return attn_head_eval(pool_call({N, P, C, Ca, K, M, dtype}, flags, 1.0f, 0, 0, ws, ws_bytes, stream),
+                        M1Fwd{X, Xatt, Wa, ba, Wt, bt, logits, att, zsave, abar}, labels, loss, probs, pred);
 }
 
 // workspace of apa_pose_attn_eval_step: [pose head | pooling (+ the label-free loss scratch) | column-tile partials]
@@ -833,7 +704,7 @@ struct PoseEvalCarve { size_t pose, pool, zpart, total; };
 static PoseEvalCarve pose_eval_carve(int N, int P, int C, int Cp, int J, int K, unsigned flags, int dtype) {
   PoseEvalCarve c;
   c.pose = align_up(apa_pose_head_workspace_bytes(N, P, C, Cp, J, dtype), 256);
-  const size_t lf = ((size_t)N * 8 + (size_t)(1 + N) * 4 + 255) / 256 * 256;
+  const size_t lf = eval_scratch_bytes(N);
   const size_t pool = apa_attn_pool_workspace_bytes(N, P, C, Cp, K, 1, flags);
   c.pool = align_up(pool > lf ? pool : lf, 256);
   c.zpart = pose_eval_zpart_bytes(N, P, Cp);
@@ -865,7 +736,7 @@ extern "C" int apa_pose_attn_eval_step(const apa_pose_attn_eval_io* io, int N, i
     set_error("apa_pose_attn_eval_step: labels and loss must be given together (both null or neither)");
     return APA_ERR_INVALID_ARG;
   }
-  int rc = check_common("apa_pose_attn_eval_step", N, P, C, Cp, K, 1, dtype);
+  int rc = check_common("apa_pose_attn_eval_step", {N, P, C, Cp, K, 1, dtype});
   if (rc != APA_OK) return rc;
   if (J <= 0) {
     set_error("apa_pose_attn_eval_step: J=%d", J);
@@ -899,7 +770,8 @@ extern "C" int apa_pose_attn_eval_step(const apa_pose_attn_eval_io* io, int N, i
   if (s.route) *s.route = route;
   // with att in place the pooling pass never dereferences its attention input (it only must differ from X)
   const void* xatt = ppre ? ppre : static_cast<const void*>(zpart);
-  return attn_head_eval_impl(s.X, xatt, s.Wa, s.ba, s.Wt, s.bt, s.labels, s.logits, s.att, s.zsave, s.abar, s.loss,
-                             s.probs, s.pred, w + cv.pose, cv.pool, N, P, C, Cp, K, 1, flags,
-                             att_ready ? APA_IFLAG_ATT_READY : 0u, dtype, stream);
+  PoolCall d = pool_call({N, P, C, Cp, K, 1, dtype}, flags, 1.0f, 0, 0, w + cv.pose, cv.pool, stream);
+  if (att_ready) d.flags |= APA_IFLAG_ATT_READY;
+  return attn_head_eval(d, M1Fwd{s.X, xatt, s.Wa, s.ba, s.Wt, s.bt, s.logits, s.att, s.zsave, s.abar}, s.labels, s.loss,
+                        s.probs, s.pred);
 }

@@ -206,7 +206,7 @@ int gemm_bf16_mid_dropout(const void* A, long lda, const void* B, long ldb, void
 // ------------------------------------------------------------------------------------------
 // Fused train step (apa_attn_head_train_step): softmax cross-entropy folded into the logits
 // reduction (forward sets `done` when it ran), batch-mean loss written by the backward head kernel.
-// Library-internal flag bits (never accepted from a caller: every extern "C" entry masks with APA_PUBLIC_FLAGS)
+// Library-internal flag bits (never accepted from a caller: pool_call, apa_capi.hip, masks with APA_PUBLIC_FLAGS)
 constexpr unsigned APA_PUBLIC_FLAGS = 0x1FFu;
 constexpr unsigned APA_IFLAG_ATT_READY = 1u << 24;      // M == 1, Xatt != X: `att` already holds Z (id / relu applied)
 constexpr unsigned APA_IFLAG_NO_ATT_WGRAD = 1u << 25;   // M == 1 + DXATT_RANK1: dWa / dba / RNG bump done by the caller
@@ -216,11 +216,11 @@ constexpr unsigned APA_IFLAG_FINALIZE_LAUNCH = 1u << 27;   // M == 1 forward: m1
                                                            // own where the logits kernel could merge the partials itself
 
 struct M1Xent {
-  const int64_t* labels;
-  float* loss;   // [1+N]
-  float* G;      // [N,K]
-  float gscale, lscale;
-  bool done;
+  const int64_t* labels = nullptr;
+  float* loss = nullptr;   // [1+N]
+  float* G = nullptr;      // [N,K]
+  float gscale = 0.f, lscale = 0.f;
+  bool done = false;
   bool deferred = false;   // per-class fused path: logits + cross-entropy are finished by the backward activation pass
   float* logits = nullptr; // (deferred: where that pass writes the logits)
   // evaluation form (apa_attn_head_eval_step without ground truth): probabilities + argmax instead
@@ -241,12 +241,18 @@ inline void ml_scales(int kind, float wt, float grad_scale, int n_loss, int K, f
   *gscale = w * grad_scale / ((float)n_loss * (float)K);
 }
 
-// ..._WITH_POSE_FEAT (nets_factory.py:289-295): J extra top-down channels (apa_m1_cat.hip)
-struct CatFeat {
-  const float* Xext = nullptr;   // [N,P,J] f32
-  int J = 0;
-  float* zext = nullptr;         // [N,J] f32: forward output, backward input
-  float* dXext = nullptr;        // [N,P,J] f32 (backward)
+// ..._WITH_POSE_FEAT (nets_factory.py:289-295): J extra top-down channels (apa_m1_cat.hip), as the caller describes
+// them (apa.h): Xext [N,P,J] f32, zext [N,J] f32 (forward output, backward input), dXext [N,P,J] f32 (backward)
+using CatFeat = apa_concat_feat;
+
+// Everything a pooling call carries besides its tensors.  The extern "C" wrappers fill it once (pool_call,
+// apa_capi.hip: the one place a caller's flags are masked); the one-call steps hand the same descriptor to both
+// halves and change only `flags` (and, on clips, `ws_bytes`) in between.
+struct PoolDims { int N, P, C, Ca, K, M, dtype; };
+struct PoolCall : PoolDims {
+  unsigned flags = 0; float keep_prob = 1.f; uint64_t seed = 0, offset = 0;
+  void* ws = nullptr; size_t ws_bytes = 0; hipStream_t st = nullptr; Hooks hk;
+  const apa_concat_feat* cat = nullptr;   // checked by the entry point (check_cat) before either path sees it
 };
 
 struct M1Plan {
@@ -293,7 +299,11 @@ extern thread_local M1FwdRoute g_m1_fwd_route;
 enum M1Act { M1_ACT_ID = 0, M1_ACT_RELU = 1, M1_ACT_SOFTMAX = 2 };   // passed to the kernels as int
 // A forward / backward call: the caller's tensors (M1Fwd / M1Bwd) and, in M1Call, everything the call resolves before
 // its first launch, filled by m1_call_fill (which also holds every refusal of the path).  All on the caller's stack.
-struct M1Fwd { const void *X, *Xatt; const float *Wa, *ba, *Wt, *bt; float *logits, *att, *zsave, *abar; };
+// (the per-class path takes the same two bundles; zsave is its fp32 [N,P,K] top-down map, abar unused.  topdown: the
+// optional TopDownAttention dump of the forward call, feature type)
+struct M1Fwd {
+  const void *X, *Xatt; const float *Wa, *ba, *Wt, *bt; float *logits, *att, *zsave, *abar; void* topdown = nullptr;
+};
 struct M1Bwd {
   const void *X, *Xatt; const float *Wa, *Wt, *bt, *att, *zsave, *abar, *G; void *dX, *dXatt; float *dWa, *dba, *dWt, *dbt;
 };
@@ -314,10 +324,9 @@ struct M1Call {
   const float* ex; float exs;   // backward: per-pixel addend of dA and its scale (the concat channels' share, else att, 0)
   hipEvent_t ev0, ev1, td_ready, grad_ready;   // ev0 / ev1: apa_hooks prof_*, dispatch begin / end of the streaming pass
 };
-// b: the backward call's tensors (nullptr: a forward call); loss_done: the forward half folded the loss (M1Xent::done)
-int m1_call_fill(M1Call& c, const void* X, const void* Xatt, const M1Bwd* b, bool loss_done, const CatFeat* cat,
-                 const Hooks& hk, void* ws, int N, int P, int C, int Ca, int K, unsigned flags, float keep_prob,
-                 uint64_t seed, uint64_t offset, int dtype, hipStream_t st);
+// f: a forward call's tensors, or b: a backward call's (the other null); xf: what the forward half of a one-call step
+// folded (M1Xent::done: the backward half needs the head kernel), or null
+int m1_call_fill(M1Call& c, const PoolCall& d, const M1Fwd* f, const M1Bwd* b, const M1Xent* xf = nullptr);
 int m1_forward(const M1Call& c, const M1Fwd& io, M1Xent* xf = nullptr);
 int m1_backward(const M1Call& c, const M1Bwd& io, const M1Xent* xf = nullptr);
 bool m1_supported(int C, int Ca, int dtype, bool fused);
@@ -515,16 +524,10 @@ size_t pc_workspace_bytes(int N, int P, int C, int Ca, int K, int dtype);
 void pc_plan_offsets(int N, int P, int C, int Ca, int K, int dtype, size_t* out);
 int pc_bwd_act_psplit_host(int N, int kgroups, int P, int act);
 // every weight image the shape can need, built in `ws`; maps (optional, APA_WIMG_MAX entries) / nmaps describe them
-int pc_weight_images(const float* Wa, const float* ba, const float* Wt, const float* bt, void* ws, int N, int P,
-                     int C, int Ca, int K, int dtype, apa_weight_image* maps, int* nmaps, hipStream_t st);
-int pc_forward(const void* X, const void* Xatt, const float* Wa, const float* ba, const float* Wt,
-               const float* bt, float* logits, float* att, float* Tsave, void* topdown, void* ws,
-               int N, int P, int C, int Ca, int K, unsigned flags, float keep_prob, uint64_t seed,
-               uint64_t offset, int dtype, hipStream_t st, M1Xent* xf = nullptr);
-int pc_backward(const void* X, const void* Xatt, const float* Wa, const float* Wt, const float* att,
-                const float* Tsave, const float* G, void* dX, void* dXatt, float* dWa, float* dba,
-                float* dWt, float* dbt, void* ws, int N, int P, int C, int Ca, int K,
-                unsigned flags, float keep_prob, uint64_t seed, uint64_t offset, int dtype,
-                hipStream_t st, const M1Xent* xf = nullptr);
+// (d: shape, dtype, workspace and stream; M = K, no flags)
+int pc_weight_images(const PoolCall& d, const float* Wa, const float* ba, const float* Wt, const float* bt,
+                     apa_weight_image* maps, int* nmaps);
+int pc_forward(const PoolCall& d, const M1Fwd& io, M1Xent* xf = nullptr);
+int pc_backward(const PoolCall& d, const M1Bwd& io, const M1Xent* xf = nullptr);
 
 }  // namespace apa

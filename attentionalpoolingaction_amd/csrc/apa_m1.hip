@@ -362,10 +362,18 @@ bool m1_no_dx_supported(int C, int dtype, bool train) {
   return train && dtype == APA_DTYPE_BF16 && m1s_supported(C, dtype);
 }
 
-int m1_call_fill(M1Call& c, const void* X, const void* Xatt, const M1Bwd* b, bool loss_done, const CatFeat* cat,
-                 const Hooks& hk, void* ws, int N, int P, int C, int Ca, int K, unsigned flags, float keep_prob,
-                 uint64_t seed, uint64_t offset, int dtype, hipStream_t st) {
-  c.N = N; c.P = P; c.C = C; c.Ca = Ca; c.K = K; c.dtype = dtype; c.flags = flags; c.st = st; c.cat = cat;
+int m1_call_fill(M1Call& c, const PoolCall& d, const M1Fwd* f, const M1Bwd* b, const M1Xent* xf) {
+  const void* const X = b ? b->X : f->X;
+  const void* const Xatt = b ? b->Xatt : f->Xatt;
+  const bool loss_done = xf && xf->done;
+  const int N = d.N, P = d.P, C = d.C, Ca = d.Ca, K = d.K, dtype = d.dtype;
+  const unsigned flags = d.flags;
+  const float keep_prob = d.keep_prob;
+  const uint64_t seed = d.seed, offset = d.offset;
+  const CatFeat* const cat = d.cat;
+  const Hooks& hk = d.hk;
+  void* const ws = d.ws;
+  c.N = N; c.P = P; c.C = C; c.Ca = Ca; c.K = K; c.dtype = dtype; c.flags = flags; c.st = d.st; c.cat = cat;
   c.fused = (Xatt == X);
   c.train = (flags & APA_FLAG_TRAIN) && keep_prob < 1.0f;
   c.act = (flags & APA_FLAG_SOFTMAX_ATT) ? M1_ACT_SOFTMAX   // relu(softmax(.)) == softmax(.)

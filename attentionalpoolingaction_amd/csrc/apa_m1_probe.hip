@@ -58,8 +58,12 @@ int apa_probe_m1_call_fill(int bwd, int loss_done, int xatt_is_x, int N, int P, 
   b.X = base; b.Xatt = xatt_is_x ? base : base + 16;
   b.Wt = reinterpret_cast<const float*>(base); b.zsave = b.Wt; b.G = b.Wt; b.att = b.Wt;
   b.dXatt = base;
-  const int rc = apa::m1_call_fill(c, b.X, b.Xatt, bwd ? &b : nullptr, loss_done != 0, nullptr, apa::Hooks(), base, N,
-                                   P, C, Ca, K, flags, keep_prob, 1, 2, dtype, nullptr);
+  apa::PoolCall d{{N, P, C, Ca, K, 1, dtype}};
+  d.flags = flags; d.keep_prob = keep_prob; d.seed = 1; d.offset = 2; d.ws = base;
+  const apa::M1Fwd f{b.X, b.Xatt};
+  apa::M1Xent xf;
+  xf.done = loss_done != 0;
+  const int rc = apa::m1_call_fill(c, d, bwd ? nullptr : &f, bwd ? &b : nullptr, &xf);
   out[0] = c.pl.S; out[1] = c.pl.ppb; out[2] = c.pl.nblk; out[3] = c.pl.lsplits; out[4] = (int64_t)c.pl.total;
   out[5] = c.pool; out[6] = c.small; out[7] = c.train; out[8] = c.fused; out[9] = (int64_t)c.pl.off_pacc;
   return rc;

@@ -398,8 +398,12 @@ struct PcCall {
   uint64_t* bump;                       // APA_FLAG_RNG_DEVICE: the counter the backward call's LAST launch advances
 };
 // X == nullptr (pc_weight_images: which features will come is not known): the layout of 16-byte addressable ones
-static PcCall pc_call(void* ws, const void* X, int N, int P, int C, int Ca, int K, int dtype, unsigned flags = 0,
-                      float keep_prob = 1.f, uint64_t seed = 0, uint64_t offset = 0) {
+static PcCall pc_call(const PoolCall& d, const void* X) {
+  const int N = d.N, P = d.P, C = d.C, Ca = d.Ca, K = d.K, dtype = d.dtype;
+  const unsigned flags = d.flags;
+  const float keep_prob = d.keep_prob;
+  const uint64_t seed = d.seed, offset = d.offset;
+  void* const ws = d.ws;
   PcCall c;
   c.N = N; c.P = P; c.C = C; c.Ca = Ca; c.K = K; c.dtype = dtype; c.flags = flags; c.keep_prob = keep_prob;
   c.pl = pc_plan(N, P, C, Ca, K, dtype); c.w = static_cast<char*>(ws);
@@ -470,9 +474,11 @@ static int pc_bwd_act(const PcCall& c, const float* G, const float* att, const f
 // (for 16-byte aligned features: the [Wt | Wa] concatenation of PcCall::cat) and described for the optimiser's launch.
 // K <= 64 (bf16, Ca == C) builds BOTH sets -- the fused kernels' and the padded GEMM operands -- because which path a
 // call takes also depends on its Xatt (== X or not) and on its dropout source.
-int pc_weight_images(const float* Wa, const float* ba, const float* Wt, const float* bt, void* ws, int N, int P,
-                     int C, int Ca, int K, int dtype, apa_weight_image* maps, int* nmaps, hipStream_t st) {
-  const PcCall c = pc_call(ws, nullptr, N, P, C, Ca, K, dtype);
+int pc_weight_images(const PoolCall& d, const float* Wa, const float* ba, const float* Wt, const float* bt,
+                     apa_weight_image* maps, int* nmaps) {
+  const int N = d.N, P = d.P, C = d.C, Ca = d.Ca, K = d.K;
+  hipStream_t const st = d.st;
+  const PcCall c = pc_call(d, nullptr);
   const int Kp = c.Kp;
   int n = 0;
   PcTrace* tr = pc_trace();
@@ -517,10 +523,12 @@ int pc_weight_images(const float* Wa, const float* ba, const float* Wt, const fl
 }
 
 // K <= 64 (HMDB-51): Z | T in ONE pass over X, dropout applied on the way into LDS (apa_pc_fused.hip)
-static int pc_forward_fused(const PcCall& c, const void* X, const float* Wa, const float* ba, const float* Wt,
-                            const float* bt, float* logits, float* att, float* Tsave, void* topdown, hipStream_t st,
-                            M1Xent* xf) {
+static int pc_forward_fused(const PcCall& c, const M1Fwd& io, hipStream_t st, M1Xent* xf) {
   const int N = c.N, P = c.P, C = c.C, K = c.K, R = c.R;
+  const void* const X = io.X;
+  const float *const Wa = io.Wa, *const ba = io.ba, *const Wt = io.Wt, *const bt = io.bt;
+  float *const logits = io.logits, *const att = io.att, *const Tsave = io.zsave;
+  void* const topdown = io.topdown;
   PcTrace* tr = pc_trace();
   if (tr) tr->path_fwd = PC_PATH_FUSED;
   const PcFusedWs f = pc_fused_carve(c.w + c.pl.off_fused, N, P, C);
@@ -566,10 +574,12 @@ static int pc_forward_fused(const PcCall& c, const void* X, const float* Wa, con
   return pc_fwd_act(c, Tsave, att, logits, topdown, xe, st);
 }
 
-static int pc_forward_generic(const PcCall& c, const void* X, const void* Xatt, const float* Wa, const float* ba,
-                              const float* Wt, const float* bt, float* logits, float* att, float* Tsave,
-                              void* topdown, hipStream_t st, M1Xent* xf) {
+static int pc_forward_generic(const PcCall& c, const M1Fwd& io, hipStream_t st, M1Xent* xf) {
   const int C = c.C, Ca = c.Ca, K = c.K, Kp = c.Kp, R = c.R;
+  const void *const X = io.X, *const Xatt = io.Xatt;
+  const float *const Wa = io.Wa, *const ba = io.ba, *const Wt = io.Wt, *const bt = io.bt;
+  float *const logits = io.logits, *const att = io.att, *const Tsave = io.zsave;
+  void* const topdown = io.topdown;
   PcTrace* tr = pc_trace();
   if (tr) { tr->path_fwd = PC_PATH_GENERIC; tr->cat = c.cat ? 1 : 0; tr->fast = c.dma ? 1 : 0; }
   {
@@ -625,15 +635,12 @@ static int pc_forward_generic(const PcCall& c, const void* X, const void* Xatt, 
   return APA_OK;   // (PcTrace::xent of a deferred cross-entropy: recorded where it is taken, in pc_backward)
 }
 
-int pc_forward(const void* X, const void* Xatt, const float* Wa, const float* ba, const float* Wt,
-               const float* bt, float* logits, float* att, float* Tsave, void* topdown, void* ws,
-               int N, int P, int C, int Ca, int K, unsigned flags, float keep_prob, uint64_t seed,
-               uint64_t offset, int dtype, hipStream_t st, M1Xent* xf) {
-  const PcCall c = pc_call(ws, X, N, P, C, Ca, K, dtype, flags, keep_prob, seed, offset);
-  if (PcTrace* tr = pc_trace()) { tr->phase = 1; tr->topdown = topdown ? 1 : 0; }
-  if (pc_fused_supported(N, P, C, Ca, K, dtype, X, Xatt) && !rng_external(flags))
-    return pc_forward_fused(c, X, Wa, ba, Wt, bt, logits, att, Tsave, topdown, st, xf);
-  return pc_forward_generic(c, X, Xatt, Wa, ba, Wt, bt, logits, att, Tsave, topdown, st, xf);
+int pc_forward(const PoolCall& d, const M1Fwd& io, M1Xent* xf) {
+  const PcCall c = pc_call(d, io.X);
+  if (PcTrace* tr = pc_trace()) { tr->phase = 1; tr->topdown = io.topdown ? 1 : 0; }
+  if (pc_fused_supported(d.N, d.P, d.C, d.Ca, d.K, d.dtype, io.X, io.Xatt) && !rng_external(d.flags))
+    return pc_forward_fused(c, io, d.st, xf);
+  return pc_forward_generic(c, io, d.st, xf);
 }
 
 // dbt | dba: the fixed-order column sums of the [nrows][2K] block partials.  The call's LAST launch (its own, or
@@ -649,10 +656,12 @@ static ColsumArgs pc_tail_colsum(const PcCall& c, int nrows, float* dbt, float* 
   return a;
 }
 
-static int pc_backward_fused(const PcCall& c, const void* X, const float* Wa, const float* Wt, const float* att,
-                             const float* Tsave, const float* G, void* dX, float* dWa, float* dba, float* dWt,
-                             float* dbt, hipStream_t st, const M1Xent* xf) {
+static int pc_backward_fused(const PcCall& c, const M1Bwd& io, hipStream_t st, const M1Xent* xf) {
   const int N = c.N, P = c.P, C = c.C, K = c.K, R = c.R;
+  const void* const X = io.X;
+  const float *const Wa = io.Wa, *const Wt = io.Wt, *const att = io.att, *const Tsave = io.zsave, *const G = io.G;
+  void* const dX = io.dX;
+  float *const dWa = io.dWa, *const dba = io.dba, *const dWt = io.dWt, *const dbt = io.dbt;
   PcTrace* tr = pc_trace();
   if (tr) tr->path_bwd = PC_PATH_FUSED;
   const PcFusedWs f = pc_fused_carve(c.w + c.pl.off_fused, N, P, C);
@@ -708,9 +717,11 @@ static int pc_backward_fused(const PcCall& c, const void* X, const float* Wa, co
   return pc_fused_dw(f, X, dWt, dWa, R, C, K, c.train, c.keep_prob, st, &tail);
 }
 
-static int pc_backward_generic(const PcCall& c, const void* X, const void* Xatt, const float* Wa, const float* Wt,
-                               const float* att, const float* Tsave, const float* G, void* dX, void* dXatt,
-                               float* dWa, float* dba, float* dWt, float* dbt, hipStream_t st, const M1Xent* xf) {
+static int pc_backward_generic(const PcCall& c, const M1Bwd& io, hipStream_t st, const M1Xent* xf) {
+  const void *const X = io.X, *const Xatt = io.Xatt;
+  const float *const Wa = io.Wa, *const Wt = io.Wt, *const att = io.att, *const Tsave = io.zsave, *const G = io.G;
+  void *const dX = io.dX, *const dXatt = io.dXatt;
+  float *const dWa = io.dWa, *const dba = io.dba, *const dWt = io.dWt, *const dbt = io.dbt;
   const int N = c.N, C = c.C, Ca = c.Ca, K = c.K, Kp = c.Kp, R = c.R, ldw = c.ldw, tdt = c.tdt;
   void* dT = c.w + c.pl.off_dt;
   void* dZ = c.cat ? static_cast<void*>(static_cast<bf16_t*>(dT) + Kp) : static_cast<void*>(c.w + c.pl.off_dz);
@@ -825,16 +836,12 @@ static int pc_backward_generic(const PcCall& c, const void* X, const void* Xatt,
   return m1_colsum(tail, st);
 }
 
-int pc_backward(const void* X, const void* Xatt, const float* Wa, const float* Wt, const float* att,
-                const float* Tsave, const float* G, void* dX, void* dXatt, float* dWa, float* dba,
-                float* dWt, float* dbt, void* ws, int N, int P, int C, int Ca, int K,
-                unsigned flags, float keep_prob, uint64_t seed, uint64_t offset, int dtype,
-                hipStream_t st, const M1Xent* xf) {
-  const PcCall c = pc_call(ws, X, N, P, C, Ca, K, dtype, flags, keep_prob, seed, offset);
+int pc_backward(const PoolCall& d, const M1Bwd& io, const M1Xent* xf) {
+  const PcCall c = pc_call(d, io.X);
   if (PcTrace* tr = pc_trace()) tr->phase = 2;
-  if (pc_fused_supported(N, P, C, Ca, K, dtype, X, Xatt) && !rng_external(flags))
-    return pc_backward_fused(c, X, Wa, Wt, att, Tsave, G, dX, dWa, dba, dWt, dbt, st, xf);
-  return pc_backward_generic(c, X, Xatt, Wa, Wt, att, Tsave, G, dX, dXatt, dWa, dba, dWt, dbt, st, xf);
+  if (pc_fused_supported(d.N, d.P, d.C, d.Ca, d.K, d.dtype, io.X, io.Xatt) && !rng_external(d.flags))
+    return pc_backward_fused(c, io, d.st, xf);
+  return pc_backward_generic(c, io, d.st, xf);
 }
 
 }  // namespace apa
