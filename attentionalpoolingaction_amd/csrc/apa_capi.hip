@@ -549,14 +549,19 @@ static int pose_attn_step(const char* fn, const apa_pose_attn_step_io* io, PoolC
   const M1Fwd f{s.X, s.Ppre, s.Wa, s.ba, s.Wt, s.bt, s.logits, s.att, s.zsave, s.abar};
   const M1Bwd b{s.X, s.Ppre, s.Wa, s.Wt, s.bt, s.att, s.zsave, s.abar, s.G, s.dX, s.dZ, s.dWa, s.dba, s.dWt, s.dbt};
   const bool train = (d.flags & APA_FLAG_TRAIN) && d.keep_prob < 1.0f;
-  const bool fast = !L.clips && !L.ml && pose_step_fast_ok(N, P, C, Cp, J, dtype, s.Ppre, s.W2, s.Wa) &&
-                    m1_supported(C, Cp, dtype, false) && m1_small_route_ok(C, K, s.G, s.Wt, s.zsave);
+  // the pose head's call on its own workspace, and its two halves: the external gradient of the backward half is
+  // rank-1, dZ (x) Wa, added to the dX the pooling pass wrote, on the workspace the forward half prepared
+  PoseCall pc = pose_call(fn, N, P, C, Cp, J, dtype, s.ws_pose, s.ws_pose_bytes, d.st);
+  pc.ws_name = "pose workspace";
+  const PoseFwd pf = {s.X, s.W1, s.b1, s.W2, s.b2, s.Ppre, s.Pl};
+  const PoseBwd pb = {s.X, s.W1, s.W2, s.Ppre, s.dPl, nullptr, s.dZ, s.Wa, s.dX, s.dW1, s.db1, s.dW2, s.db2, true, true};
+  const bool fast = !L.clips && !L.ml && pose_step_fast_ok(pc, pf, pb) && m1_supported(C, Cp, dtype, false) &&
+                    m1_small_route_ok(C, K, s.G, s.Wt, s.zsave);
   if (!fast) {
     rc = apa_pose_head_fwd(s.X, s.W1, s.b1, s.W2, s.b2, s.Ppre, s.Pl, s.ws_pose, s.ws_pose_bytes, N, P, C, Cp, J,
                            dtype, d.st);
     if (rc != APA_OK) return rc;
-    rc = apa_pose_l2_loss_fwd_bwd(s.Pl, s.pose_labels, s.pose_valid, s.loss_pose, s.dPl,
-                                  pose_ws_loss_scratch(s.ws_pose, N, P, C, Cp, J, dtype),
+    rc = apa_pose_l2_loss_fwd_bwd(s.Pl, s.pose_labels, s.pose_valid, s.loss_pose, s.dPl, pose_ws_loss_scratch(pc),
                                   apa_pose_l2_workspace_bytes(N, P, J), N, P, J, s.pose_wt, s.grad_scale, d.st);
     if (rc != APA_OK) return rc;
     d.flags |= APA_FLAG_DXATT_RANK1;   // s.dZ receives dZ itself; apa_pose_head_bwd_rank1ext re-forms dXatt from it
@@ -576,8 +581,7 @@ static int pose_attn_step(const char* fn, const apa_pose_attn_step_io* io, PoolC
   a.relu_att = (d.flags & APA_FLAG_RELU_ATT) && !(d.flags & APA_FLAG_SOFTMAX_ATT);
   a.pose_labels = s.pose_labels; a.pose_valid = s.pose_valid; a.dPl = s.dPl;
   a.pose_wt = s.pose_wt; a.grad_scale = s.grad_scale;
-  rc = pose_fwd_fused(s.X, s.W1, s.b1, s.W2, s.b2, s.Ppre, s.Pl, s.ws_pose, s.ws_pose_bytes, N, P, C, Cp, J, dtype,
-                      a, d.st);
+  rc = pose_fwd_fused(pc, pf, a);
   if (rc != APA_OK) return rc;
   // The pooling pass's own dX share (A/P . dz . mask/keep) is not written and read back: the streaming backward
   // kernel becomes read-only (APA_IFLAG_NO_DX) and the pose head's dX product adds the term in its epilogue from att,
@@ -601,12 +605,11 @@ static int pose_attn_step(const char* fn, const apa_pose_attn_step_io* io, PoolC
     a.pool_bits = reinterpret_cast<const uint8_t*>(wp + mp.off_maskbits);
     a.pool_inv_keep = 1.0f / d.keep_prob;
   }
-  uint64_t* bump = (train && (d.flags & APA_FLAG_RNG_DEVICE))
-                       ? reinterpret_cast<uint64_t*>(static_cast<uintptr_t>(d.offset)) : nullptr;
+  a.dWa = s.dWa; a.dba = s.dba; a.loss_pose = s.loss_pose;
+  a.rng_bump = (train && (d.flags & APA_FLAG_RNG_DEVICE))
+                   ? reinterpret_cast<uint64_t*>(static_cast<uintptr_t>(d.offset)) : nullptr;
   // (same workspace, same call: the bf16 copy of W1 the forward half built there -- when the caller keeps none -- is reused)
-  return pose_bwd_fused(s.X, s.W1, s.W2, s.Ppre, s.dPl, s.dZ, s.Wa, s.dX, 1 | APA_POSE_WS_FROM_FWD, s.dW1, s.db1, s.dW2,
-                        s.db2, s.dWa, s.dba, s.loss_pose, bump, s.ws_pose, s.ws_pose_bytes, N, P, C, Cp, J, dtype, a,
-                        d.st);
+  return pose_bwd_fused(pc, pb, a);
 }
 
 extern "C" int apa_pose_attn_train_step(const apa_pose_attn_step_io* io, int N, int P, int C, int Cp, int J, int K,
@@ -761,17 +764,18 @@ extern "C" int apa_pose_attn_eval_step(const apa_pose_attn_eval_io* io, int N, i
   char* w = static_cast<char*>(s.ws);
   float* zpart = reinterpret_cast<float*>(w + cv.pose + cv.pool);
   const bool relu_att = (flags & APA_FLAG_RELU_ATT) && !(flags & APA_FLAG_SOFTMAX_ATT);
-  int route = 0;
-  const void* ppre = nullptr;
-  bool att_ready = false;
-  rc = pose_eval_fwd(s.X, s.W1, s.b1, s.W2, s.b2, s.W1_bf16, s.Wa, s.ba, relu_att, s.att, s.Pl, w, cv.pose, zpart, N, P,
-                     C, Cp, J, dtype, static_cast<hipStream_t>(stream), &route, &ppre, &att_ready);
+  PoseCall pc = pose_call("apa_pose_attn_eval_step", N, P, C, Cp, J, dtype, w, cv.pose, stream);
+  pc.ws_name = "pose workspace";
+  PoseStepArgs a;
+  a.W1_bf16 = s.W1_bf16; a.wa = s.Wa; a.ba = s.ba; a.att = s.att; a.relu_att = relu_att;
+  PoseEvalOut o = {0, nullptr, false};
+  rc = pose_eval_fwd(pc, PoseFwd{s.X, s.W1, s.b1, s.W2, s.b2, nullptr, s.Pl}, a, zpart, &o);
   if (rc != APA_OK) return rc;
-  if (s.route) *s.route = route;
+  if (s.route) *s.route = o.route;
   // with att in place the pooling pass never dereferences its attention input (it only must differ from X)
-  const void* xatt = ppre ? ppre : static_cast<const void*>(zpart);
+  const void* xatt = o.ppre ? o.ppre : static_cast<const void*>(zpart);
   PoolCall d = pool_call({N, P, C, Cp, K, 1, dtype}, flags, 1.0f, 0, 0, w + cv.pose, cv.pool, stream);
-  if (att_ready) d.flags |= APA_IFLAG_ATT_READY;
+  if (o.att_ready) d.flags |= APA_IFLAG_ATT_READY;
   return attn_head_eval(d, M1Fwd{s.X, xatt, s.Wa, s.ba, s.Wt, s.bt, s.logits, s.att, s.zsave, s.abar}, s.labels, s.loss,
                         s.probs, s.pred);
 }

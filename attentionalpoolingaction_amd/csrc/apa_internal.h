@@ -395,19 +395,50 @@ int m1_logits2_xent(float* z, const float* Wt, float* abar, const float* bt,
 // the fixed-order column sum of ColsumArgs (apa_colsum.h) as a launch of its own: ceil(C / 32) blocks of 1024 threads
 int m1_colsum(const ColsumArgs& a, hipStream_t st);
 
-// apa_pose_head.hip: the pose-head halves of the one-call cfg 003 step (apa_pose_attn_train_step)
+// apa_pose_head.hip.  A pose-head call, described once: its shape, its stream, its workspace and the carve of it
+// (pose_call fills it; pose_check holds every refusal, in the order the entry points promise).  fn / ws_name: what the
+// refusals call the entry point and its workspace -- a one-call step has two of them and says "pose workspace".
+struct PosePlan {
+  long R;
+  int nchunks;
+  size_t off_dppre, off_partial, off_gemm, off_w1b, off_lpart, total;
+};
+struct PoseCall {
+  const char* fn; const char* ws_name;
+  int N, P, C, Cp, J, dtype; hipStream_t st;
+  void* ws; size_t ws_bytes; PosePlan pl;   // pl: all zero while a dimension is non-positive (pose_check refuses those)
+  char* at(size_t off) const { return static_cast<char*>(ws) + off; }
+};
+PoseCall pose_call(const char* fn, int N, int P, int C, int Cp, int J, int dtype, void* ws, size_t ws_bytes,
+                   void* stream);
+// The caller's tensors of a forward / backward call (as M1Fwd / M1Bwd).  The external gradient of dPpre is a map
+// (dPpre_ext), rank-1 (ext_row (x) ext_col) or absent; accumulate: dX += dPpre . W1^T; ws_from_fwd: the workspace still
+// holds what the forward call on it left there (APA_POSE_WS_FROM_FWD).
+struct PoseFwd {
+  const void* X; const float *W1, *b1, *W2, *b2; void* Ppre; float* Pl;
+};
+struct PoseBwd {
+  const void* X; const float *W1, *W2; const void* Ppre; const float* dPl; const void* dPpre_ext;
+  const float *ext_row, *ext_col; void* dX; float *dW1, *db1, *dW2, *db2; bool accumulate, ws_from_fwd;
+};
+// What the one-call cfg 003 steps add to the two bundles (apa_pose_attn_train_step; the evaluation step reads W1_bf16
+// and the attention conv only)
 struct PoseStepArgs {
   const void* W1_bf16 = nullptr;        // caller-maintained bf16 copy of W1 (nullptr: converted per call)
   const void* W2T_bf16 = nullptr;       // caller-maintained bf16 [16][Cp] transposed copy of W2 (nullptr: staged per block)
   const float* wa = nullptr; const float* ba = nullptr; float* att = nullptr; bool relu_att = false;
   const float* pose_labels = nullptr; const uint8_t* pose_valid = nullptr; float* dPl = nullptr;
   float pose_wt = 1.f, grad_scale = 1.f;
-  // backward half: the pooling's dX share formed in the pose head's dX product (nullptr: dX already holds it)
+  // backward half: the attention conv's gradients (they leave with the rows pass, whose external gradient is
+  // dZ (x) wa), the pose loss its column sum finishes and the device-side dropout counter it advances
+  float* dWa = nullptr; float* dba = nullptr; float* loss_pose = nullptr; uint64_t* rng_bump = nullptr;
+  // ... and the attentional pooling's own dX share, formed in the dX product's epilogue (APA_IFLAG_NO_DX on the pooling
+  // side): dX = dPpre . W1^T + att/P . dz . mask/keep -- att [R], dz [N, C], keep bits [R * C / 8] (nullptr: all kept).
+  // pool_att == nullptr: dX already holds the share
   const float* pool_att = nullptr; const float* pool_dz = nullptr; const uint8_t* pool_bits = nullptr;
   float pool_inv_keep = 1.f;
 };
-bool pose_step_fast_ok(int N, int P, int C, int Cp, int J, int dtype, const void* Ppre, const float* W2,
-                       const float* wa);
+bool pose_step_fast_ok(const PoseCall& c, const PoseFwd& f, const PoseBwd& b);
 // What the pose head ran (filled on the host only, as M1Trace: the product never sets the pointer; the test-only
 // probe library does, around one call, and tests/test_pose_paths_gpu.py reads it back).  0 = not decided by this call.
 enum PoseW1 { POSE_W1_NONE = 0, POSE_W1_BF16_COPY, POSE_W1_F32, POSE_W1_REUSED, POSE_W1_SHADOW };
@@ -425,21 +456,14 @@ extern thread_local PoseTrace* g_pose_trace;
 inline PoseTrace* pose_trace() { return g_pose_trace; }
 // the workspace carve of the pose head: out[0..7] = R, nchunks, off_dppre, off_partial, off_gemm, off_w1b, off_lpart, total
 void pose_plan_offsets(int N, int P, int C, int Cp, int J, int dtype, size_t* out);
-void* pose_ws_loss_scratch(void* ws, int N, int P, int C, int Cp, int J, int dtype);   // >= apa_pose_l2_workspace_bytes
-int pose_fwd_fused(const void* X, const float* W1, const float* b1, const float* W2, const float* b2, void* Ppre,
-                   float* Pl, void* ws, size_t ws_bytes, int N, int P, int C, int Cp, int J, int dtype,
-                   const PoseStepArgs& a, hipStream_t st);
-// the pose-head half of apa_pose_attn_eval_step (apa_pose_head.hip) and the size of its column-tile partials
+void* pose_ws_loss_scratch(const PoseCall& c);   // >= apa_pose_l2_workspace_bytes
+int pose_fwd_fused(const PoseCall& c, const PoseFwd& f, const PoseStepArgs& a);
+int pose_bwd_fused(const PoseCall& c, const PoseBwd& b, const PoseStepArgs& a);
+// the pose-head half of apa_pose_attn_eval_step (apa_pose_head.hip) and the size of its column-tile partials.
+// f.Ppre is not read (the map stays in the workspace, or is never stored); f.Pl may be null
+struct PoseEvalOut { int route; const void* ppre; bool att_ready; };
 size_t pose_eval_zpart_bytes(int N, int P, int Cp);
-int pose_eval_fwd(const void* X, const float* W1, const float* b1, const float* W2, const float* b2,
-                  const void* W1_bf16, const float* wa, const float* ba, bool relu_att, float* att, float* Pl, void* ws,
-                  size_t ws_bytes, float* zpart, int N, int P, int C, int Cp, int J, int dtype, hipStream_t st,
-                  int* route, const void** ppre, bool* att_ready);
-int pose_bwd_fused(const void* X, const float* W1, const float* W2, const void* Ppre, const float* dPl,
-                   const float* dZ, const float* wa, void* dX, int accumulate_dX, float* dW1, float* db1,
-                   float* dW2, float* db2, float* dWa, float* dba, float* loss_pose, uint64_t* rng_bump,
-                   void* ws, size_t ws_bytes, int N, int P, int C, int Cp, int J, int dtype,
-                   const PoseStepArgs& a, hipStream_t st);
+int pose_eval_fwd(const PoseCall& c, const PoseFwd& f, const PoseStepArgs& a, float* zpart, PoseEvalOut* out);
 
 // Per-class maps (apa_pc_fused.hip, apa_pc.hip).  What they ran (filled on the host only, as M1Trace / PoseTrace: the
 // product never sets the pointer; the test-only probe library does, around one call, and tests/test_pc_paths_gpu.py

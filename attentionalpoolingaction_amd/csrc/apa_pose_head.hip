@@ -2,7 +2,11 @@
 //        Ppre = relu(X.W1 + b1)   [N,P,768]      'PoseLogits/ExtraConv2d_1x1'
 //        Pl   = Ppre.W2 + b2      [N,P,J]        'PoseLogits/Conv2d_1c_1x1'
 //      and its backward (the reference relies on TF autodiff); pose_fwd_fused / pose_bwd_fused are its halves of the
-//      one-call cfg 003 step.
+//      one-call cfg 003 step, pose_eval_fwd its half of the evaluation step.
+//      Host layer: a call is described once (PoseCall: shape, stream, workspace and its carve; PoseFwd / PoseBwd: the
+//      caller's tensors; PoseStepArgs: what a one-call step adds), refused in one place (pose_check), and every
+//      product has one builder: pose_w1_operand, pose_ppre_product, pose_pl_product forward; pose_rows_route picks
+//      one of pose_rows_mfma / pose_rows_valu / pose_rows_dppre backward, pose_head_bwd_big is the tail of all three.
 #include <type_traits>
 #include <math.h>
 
@@ -556,12 +560,18 @@ __global__ __launch_bounds__(512) void pose_bwd_rows_mfma_kernel(
   }
 }
 
-static bool pose_rows_mfma_ok(const float* dPl, const void* dPpre_ext, const float* ext_row, const float* ext_col,
-                              const float* W2, const void* Ppre, int Cp, int J, int dtype) {
-  const uintptr_t al = reinterpret_cast<uintptr_t>(dPl) | reinterpret_cast<uintptr_t>(W2) | reinterpret_cast<uintptr_t>(Ppre) |
-                       reinterpret_cast<uintptr_t>(ext_col);
-  return dtype == APA_DTYPE_BF16 && dPl && J == 16 && Cp % 128 == 0 && Cp >= 256 && Cp <= 1024 &&
-         (al & 15) == 0 && (!dPpre_ext || ext_row);
+// ---------------------------------------------------------------------------------------------
+// Which rows pass serves a backward call.  The three facts every form turns on -- the block's thread count, the LDS
+// bound and the operand alignments -- are stated here and nowhere else.
+// ---------------------------------------------------------------------------------------------
+// threads of a rows-kernel block: one per 2 columns, whole waves (the MFMA form's Cp % 128 == 0 makes it Cp / 2)
+static int pose_rows_nthr(int Cp) { return ((Cp / 2 + 63) / 64) * 64; }
+
+static bool pose_rows_mfma_ok(const PoseCall& c, const PoseBwd& b) {
+  const uintptr_t al = reinterpret_cast<uintptr_t>(b.dPl) | reinterpret_cast<uintptr_t>(b.W2) |
+                       reinterpret_cast<uintptr_t>(b.Ppre) | reinterpret_cast<uintptr_t>(b.ext_col);
+  return c.dtype == APA_DTYPE_BF16 && b.dPl && c.J == 16 && c.Cp % 128 == 0 && c.Cp >= 256 && c.Cp <= 1024 &&
+         (al & 15) == 0 && (!b.dPpre_ext || b.ext_row);
 }
 
 // LDS bytes of one block: dPl rows + ext_row + the [rpb][nthr] tile(s)
@@ -578,14 +588,18 @@ static int pose_rows_per_block(long R, int nthr, int dtype, bool ext) {
   return rpb;
 }
 
-static bool pose_bwd_rows_ok(const float* dPl, const void* Ppre, const void* ext, const float* W2, int Cp,
-                             int J, int dtype) {
-  const uintptr_t al = reinterpret_cast<uintptr_t>(Ppre) | reinterpret_cast<uintptr_t>(ext);
-  const int nthr = ((Cp / 2 + 63) / 64) * 64;
-  return dPl && J <= 16 && Cp % 4 == 0 && Cp <= 1024 && (al & 7) == 0 &&
-         (J != 16 || (reinterpret_cast<uintptr_t>(W2) & 15) == 0) &&
-         (dtype == APA_DTYPE_BF16 || dtype == APA_DTYPE_F32) &&
-         pose_rows_lds(16, nthr, dtype, ext != nullptr) <= 65536;
+static bool pose_bwd_rows_ok(const PoseCall& c, const PoseBwd& b) {
+  const uintptr_t al = reinterpret_cast<uintptr_t>(b.Ppre) | reinterpret_cast<uintptr_t>(b.dPpre_ext);
+  return b.dPl && c.J <= 16 && c.Cp % 4 == 0 && c.Cp <= 1024 && (al & 7) == 0 &&
+         (c.J != 16 || (reinterpret_cast<uintptr_t>(b.W2) & 15) == 0) &&
+         (c.dtype == APA_DTYPE_BF16 || c.dtype == APA_DTYPE_F32) &&
+         pose_rows_lds(16, pose_rows_nthr(c.Cp), c.dtype, b.dPpre_ext != nullptr) <= 65536;
+}
+
+// one pass over Ppre on the matrix pipe, the same pass on the VALU, or the chunk kernel plus a dW2 product of its own
+static PoseRows pose_rows_route(const PoseCall& c, const PoseBwd& b) {
+  if (!pose_bwd_rows_ok(c, b)) return POSE_ROWS_DPPRE;
+  return pose_rows_mfma_ok(c, b) ? POSE_ROWS_MFMA : POSE_ROWS_VALU;
 }
 
 // Pl = Ppre . W2 + b2 for bf16 features: [R, Cp] x [Cp, J <= 16] -- 16 output columns, so a 128-wide GEMM
@@ -752,13 +766,18 @@ static bool pose_pl_fast(int Cp, int J, int dtype, const void* Ppre) {
 }
 
 // the skinny product's launch; `x` != nullptr: the fused form (attention logits column and / or pose L2 loss)
-static int pose_pl_launch(const bf16_t* pp, const float* W2, const float* b2, float* Pl, int R, int Cp, int J,
-                          const PosePlExtra* x, hipStream_t st) {
+static int pose_pl_launch(const PoseCall& c, const PoseFwd& f, const PosePlExtra* x) {
+  const bf16_t* pp = static_cast<const bf16_t*>(f.Ppre);
+  const float *W2 = f.W2, *b2 = f.b2;
+  float* Pl = f.Pl;
+  const int R = (int)c.pl.R, J = c.J;
+  hipStream_t st = c.st;
   const bool w2t = x && x->w2t;
   const dim3 grid(w2t ? (R + 31) / 32 : (R + 63) / 64);
+  int ks = c.Cp / 32;                                  // k steps of 32: the kernel's instance
+  if (ks != 8 && ks != 16 && ks != 24) ks = 32;        // (pose_pl_fast: Cp = 256 / 512 / 768 / 1024)
   if (PoseTrace* t = pose_trace()) {
-    t->pl = POSE_PL_FAST; t->pl_fused = x ? 1 : 0; t->pl_w2t = w2t ? 1 : 0;
-    t->pl_ks = Cp / 32 == 8 ? 8 : (Cp / 32 == 16 ? 16 : (Cp / 32 == 24 ? 24 : 32));   // (the switch below)
+    t->pl = POSE_PL_FAST; t->pl_fused = x ? 1 : 0; t->pl_w2t = w2t ? 1 : 0; t->pl_ks = ks;
   }
   const PosePlExtra none = {nullptr, nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr, 0.f, 1, nullptr};
 #define APA_PL(KSv)                                                                                              \
@@ -768,7 +787,7 @@ static int pose_pl_launch(const bf16_t* pp, const float* W2, const float* b2, fl
     else if (x) hipLaunchKernelGGL((pose_pl_kernel<KSv, true>), grid, dim3(256), 0, st, pp, W2, b2, Pl, R, J, *x); \
     else hipLaunchKernelGGL((pose_pl_kernel<KSv, false>), grid, dim3(256), 0, st, pp, W2, b2, Pl, R, J, none);    \
   } while (0)
-  switch (Cp / 32) {
+  switch (ks) {
     case 8: APA_PL(8); break;
     case 16: APA_PL(16); break;
     case 24: APA_PL(24); break;
@@ -779,11 +798,8 @@ static int pose_pl_launch(const bf16_t* pp, const float* W2, const float* b2, fl
   return APA_OK;
 }
 
-struct PosePlan {
-  long R;
-  int nchunks;
-  size_t off_dppre, off_partial, off_gemm, off_w1b, off_lpart, total;
-};
+static bool pose_dims_ok(int N, int P, int C, int Cp, int J) { return N > 0 && P > 0 && C > 0 && Cp > 0 && J > 0; }
+
 static PosePlan pose_plan(int N, int P, int C, int Cp, int J, int dtype) {
   PosePlan pl;
   pl.R = (long)N * P;
@@ -791,7 +807,7 @@ static PosePlan pose_plan(int N, int P, int C, int Cp, int J, int dtype) {
   size_t off = 0;
   pl.off_dppre = off;   off += align_up((size_t)pl.R * Cp * dt_size(dtype), 256);
   const size_t rows_part = (size_t)((pl.R + POSE_RPB_MIN - 1) / POSE_RPB_MIN) *
-                           pose_rows_ld(Cp, J, ((Cp / 2 + 63) / 64) * 64) * 4;
+                           pose_rows_ld(Cp, J, pose_rows_nthr(Cp)) * 4;
   const size_t chunk_part = (size_t)pl.nchunks * (Cp + J) * 4;
   pl.off_partial = off; off += align_up(rows_part > chunk_part ? rows_part : chunk_part, 256);
   size_t g = gemm_ws_bytes((int)pl.R, J, 32);
@@ -819,6 +835,44 @@ void pose_plan_offsets(int N, int P, int C, int Cp, int J, int dtype, size_t* ou
   out[4] = pl.off_gemm; out[5] = pl.off_w1b; out[6] = pl.off_lpart; out[7] = pl.total;
 }
 
+PoseCall pose_call(const char* fn, int N, int P, int C, int Cp, int J, int dtype, void* ws, size_t ws_bytes,
+                   void* stream) {
+  PoseCall c = {fn, "workspace", N, P, C, Cp, J, dtype, static_cast<hipStream_t>(stream), ws, ws_bytes, PosePlan{}};
+  if (pose_dims_ok(N, P, C, Cp, J)) c.pl = pose_plan(N, P, C, Cp, J, dtype);
+  return c;
+}
+
+// Every refusal of a pose-head call that an entry point can earn, in the order the entry points have always fired
+// them.  operands: the entry point's own null-pointer list came out clean (it shares one text with the dimensions).
+// b: a backward call, which adds its own -- and has never refused an unknown dtype, so it still does not.
+static int pose_check(const PoseCall& c, bool operands, const PoseBwd* b = nullptr) {
+  if (!operands || !pose_dims_ok(c.N, c.P, c.C, c.Cp, c.J)) {
+    set_error("%s: null pointer or non-positive dimension", c.fn);
+    return APA_ERR_INVALID_ARG;
+  }
+  if (!b && c.dtype != APA_DTYPE_F32 && c.dtype != APA_DTYPE_BF16) {
+    set_error("%s: unknown dtype %d", c.fn, c.dtype);
+    return APA_ERR_INVALID_ARG;
+  }
+  if (b && !b->dPl && !b->dPpre_ext && !b->ext_row) {
+    set_error("%s: neither dPl nor dPpre_ext given (no gradient to propagate)", c.fn);
+    return APA_ERR_INVALID_ARG;
+  }
+  if (b && (c.J > 32 || c.Cp > 2048)) {
+    set_error("%s: J=%d > 32 or Cp=%d > 2048 not built", c.fn, c.J, c.Cp);
+    return APA_ERR_UNSUPPORTED;
+  }
+  if (!c.ws || c.ws_bytes < c.pl.total) {
+    set_error("%s: %s too small (%zu < %zu)", c.fn, c.ws_name, c.ws_bytes, c.pl.total);
+    return APA_ERR_WORKSPACE;
+  }
+  if (b && c.Cp % 4 != 0) {
+    set_error("%s: Cp=%d must be a multiple of 4", c.fn, c.Cp);
+    return APA_ERR_UNSUPPORTED;
+  }
+  return APA_OK;
+}
+
 __global__ __launch_bounds__(256) void f32_to_bf16_kernel(const float* __restrict__ in,
                                                           bf16_t* __restrict__ out, size_t n8) {
   for (size_t v = (size_t)blockIdx.x * 256 + threadIdx.x; v < n8; v += (size_t)gridDim.x * 256) {
@@ -829,25 +883,58 @@ __global__ __launch_bounds__(256) void f32_to_bf16_kernel(const float* __restric
   }
 }
 
-// W1 as the bf16 operand of the pose-head GEMMs (only when its size allows whole 16-byte vectors)
-static const void* pose_w1_operand(const float* W1, void* ws_w1b, int C, int Cp, int dtype, int* tb,
-                                   hipStream_t st, bool reuse = false, int* kind = nullptr) {
-  *tb = 0;
-  if (kind) *kind = POSE_W1_F32;
-  if (dtype != APA_DTYPE_BF16 || ((size_t)C * Cp) % 8 != 0 || (reinterpret_cast<uintptr_t>(W1) & 15))
-    return W1;
-  if (kind) *kind = reuse ? POSE_W1_REUSED : POSE_W1_BF16_COPY;
-  if (reuse) {   // APA_POSE_WS_FROM_FWD: the forward call's copy is still in the workspace
-    *tb = 1;
-    return ws_w1b;
+// W1 as the B operand of the Ppre product (slot = w1_fwd) and of the dX product (w1_bwd), decided here and nowhere
+// else.  With bf16 features, so that the MFMA GEMMs can DMA both operands straight into LDS:
+//   * the caller's bf16 shadow, if it gave one the products can read (16-byte addressable rows);
+//   * else a bf16 copy in the workspace -- the one the forward call on the same workspace left there (reuse), or a fresh
+//     conversion -- when W1's size and address allow whole 16-byte vectors;
+//   * else, and with fp32 features, W1 itself.
+struct PoseW1Op { const void* B; int tb; };
+static PoseW1Op pose_w1_operand(const PoseCall& c, const float* W1, const void* shadow, bool reuse,
+                                int PoseTrace::*slot) {
+  PoseW1Op op = {W1, 0};
+  int kind = POSE_W1_F32;
+  if (shadow && c.dtype == APA_DTYPE_BF16 && (reinterpret_cast<uintptr_t>(shadow) & 15) == 0) {
+    op = {shadow, 1};
+    kind = POSE_W1_SHADOW;
+  } else if (c.dtype == APA_DTYPE_BF16 && ((size_t)c.C * c.Cp) % 8 == 0 && (reinterpret_cast<uintptr_t>(W1) & 15) == 0) {
+    bf16_t* w1b = reinterpret_cast<bf16_t*>(c.at(c.pl.off_w1b));
+    op = {w1b, 1};
+    kind = reuse ? POSE_W1_REUSED : POSE_W1_BF16_COPY;
+    if (!reuse) {
+      const size_t n8 = (size_t)c.C * c.Cp / 8;
+      size_t nb = (n8 + 255) / 256;
+      if (nb > 2048) nb = 2048;
+      hipLaunchKernelGGL(f32_to_bf16_kernel, dim3((unsigned)nb), dim3(256), 0, c.st, W1, w1b, n8);
+    }
   }
-  const size_t n8 = (size_t)C * Cp / 8;
-  size_t nb = (n8 + 255) / 256;
-  if (nb > 2048) nb = 2048;
-  hipLaunchKernelGGL(f32_to_bf16_kernel, dim3((unsigned)nb), dim3(256), 0, st, W1,
-                     static_cast<bf16_t*>(ws_w1b), n8);
-  *tb = 1;
-  return ws_w1b;
+  if (PoseTrace* t = pose_trace()) t->*slot = kind;
+  return op;
+}
+
+// Ppre = relu(X.W1 + b1), C = f.Ppre
+static GemmDesc pose_ppre_product(const PoseCall& c, const PoseFwd& f, const PoseW1Op& w1) {
+  GemmDesc g;
+  g.A = f.X; g.lda = c.C; g.ta = dt_code(c.dtype); g.a_kc = true;
+  g.B = w1.B; g.ldb = c.Cp; g.tb = w1.tb; g.b_kc = false;
+  g.C = f.Ppre; g.ldc = c.Cp; g.tc = dt_code(c.dtype);
+  g.M = (int)c.pl.R; g.N = c.Cp; g.K = c.C; g.bias = f.b1; g.act = 1;
+  return g;
+}
+
+// Pl = Ppre.W2 + b2: the skinny product, one wave per 16 rows (x: what its fused form adds, or null), where it serves
+// the shape; else a split-K GEMM, which takes no extras
+static int pose_pl_product(const PoseCall& c, const PoseFwd& f, const PosePlExtra* x) {
+  if (pose_pl_fast(c.Cp, c.J, c.dtype, f.Ppre)) return pose_pl_launch(c, f, x);
+  if (PoseTrace* t = pose_trace()) t->pl = POSE_PL_GEMM;
+  const int R = (int)c.pl.R;
+  GemmDesc g;
+  g.A = f.Ppre; g.lda = c.Cp; g.ta = dt_code(c.dtype); g.a_kc = true;
+  g.B = f.W2; g.ldb = c.J; g.tb = 0; g.b_kc = false;
+  g.C = f.Pl; g.ldc = c.J; g.tc = 0;
+  g.M = R; g.N = c.J; g.K = c.Cp; g.bias = f.b2;
+  g.splits = gemm_pick_splits(R, c.J, c.Cp); g.ws = reinterpret_cast<float*>(c.at(c.pl.off_gemm));
+  return gemm_launch(g, c.st);
 }
 
 }  // namespace apa
@@ -855,50 +942,20 @@ static const void* pose_w1_operand(const float* W1, void* ws_w1b, int C, int Cp,
 using namespace apa;
 
 extern "C" size_t apa_pose_head_workspace_bytes(int N, int P, int C, int Cp, int J, int dtype) {
-  if (N <= 0 || P <= 0 || C <= 0 || Cp <= 0 || J <= 0) return 0;
+  if (!pose_dims_ok(N, P, C, Cp, J)) return 0;
   return pose_plan(N, P, C, Cp, J, dtype).total;
 }
 
 extern "C" int apa_pose_head_fwd(const void* X, const float* W1, const float* b1, const float* W2,
                                  const float* b2, void* Ppre, float* Pl, void* ws, size_t ws_bytes,
                                  int N, int P, int C, int Cp, int J, int dtype, void* stream) {
-  if (!X || !W1 || !b1 || !W2 || !b2 || !Ppre || !Pl || N <= 0 || P <= 0 || C <= 0 || Cp <= 0 || J <= 0) {
-    set_error("apa_pose_head_fwd: null pointer or non-positive dimension");
-    return APA_ERR_INVALID_ARG;
-  }
-  if (dtype != APA_DTYPE_F32 && dtype != APA_DTYPE_BF16) {
-    set_error("apa_pose_head_fwd: unknown dtype %d", dtype);
-    return APA_ERR_INVALID_ARG;
-  }
-  const PosePlan pl = pose_plan(N, P, C, Cp, J, dtype);
-  if (!ws || ws_bytes < pl.total) {
-    set_error("apa_pose_head_fwd: workspace too small (%zu < %zu)", ws_bytes, pl.total);
-    return APA_ERR_WORKSPACE;
-  }
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  float* gws = reinterpret_cast<float*>(static_cast<char*>(ws) + pl.off_gemm);
-  const int R = (int)pl.R;
-  int w1_tb = 0;
-  PoseTrace* tr = pose_trace();
-  const void* W1op = pose_w1_operand(W1, static_cast<char*>(ws) + pl.off_w1b, C, Cp, dtype, &w1_tb, st, false,
-                                     tr ? &tr->w1_fwd : nullptr);
-  GemmDesc g1;  // Ppre = relu(X.W1 + b1)
-  g1.A = X; g1.lda = C; g1.ta = dt_code(dtype); g1.a_kc = true;
-  g1.B = W1op; g1.ldb = Cp; g1.tb = w1_tb; g1.b_kc = false;
-  g1.C = Ppre; g1.ldc = Cp; g1.tc = dt_code(dtype);
-  g1.M = R; g1.N = Cp; g1.K = C; g1.bias = b1; g1.act = 1;
-  int rc = gemm_launch(g1, st);
+  const PoseCall c = pose_call("apa_pose_head_fwd", N, P, C, Cp, J, dtype, ws, ws_bytes, stream);
+  const PoseFwd f = {X, W1, b1, W2, b2, Ppre, Pl};
+  int rc = pose_check(c, X && W1 && b1 && W2 && b2 && Ppre && Pl);
   if (rc != APA_OK) return rc;
-  if (pose_pl_fast(Cp, J, dtype, Ppre))   // Pl = Ppre.W2 + b2: skinny product, one wave per 16 rows
-    return pose_pl_launch(static_cast<const bf16_t*>(Ppre), W2, b2, Pl, R, Cp, J, nullptr, st);
-  if (tr) tr->pl = POSE_PL_GEMM;
-  GemmDesc g2;  // Pl = Ppre.W2 + b2
-  g2.A = Ppre; g2.lda = Cp; g2.ta = dt_code(dtype); g2.a_kc = true;
-  g2.B = W2; g2.ldb = J; g2.tb = 0; g2.b_kc = false;
-  g2.C = Pl; g2.ldc = J; g2.tc = 0;
-  g2.M = R; g2.N = J; g2.K = Cp; g2.bias = b2;
-  g2.splits = gemm_pick_splits(R, J, Cp); g2.ws = gws;
-  return gemm_launch(g2, st);
+  rc = gemm_launch(pose_ppre_product(c, f, pose_w1_operand(c, W1, nullptr, false, &PoseTrace::w1_fwd)), c.st);
+  if (rc != APA_OK) return rc;
+  return pose_pl_product(c, f, nullptr);
 }
 
 // split-K factor of dW1 = X^T . dPpre.  bf16 features take the 128 x 64 tile kernel, three blocks per CU: the
@@ -918,173 +975,133 @@ static int pose_dw1_splits(int C, int Cp, int R, int dtype) {
   return s;
 }
 
-// the two dense products of the backward pass: dW1 = X^T . dPpre and dX (+)= dPpre . W1^T
-// fused-step extras of the backward pass (apa_pose_attn_train_step)
-struct PoseBwdFuse {
-  float* dWa = nullptr; float* dba = nullptr;                 // attention conv gradients (rank-1 ext only)
-  const float* aux_src = nullptr; int aux_n = 0; float aux_scale = 0.f; float* aux_dst = nullptr;   // pose loss
-  uint64_t* rng_bump = nullptr;                               // device-side dropout counter to advance
-  const void* W1_bf16 = nullptr;                              // caller-maintained bf16 copy of W1
-  // the attentional pooling's own dX share, formed in the dX product's epilogue (APA_IFLAG_NO_DX on the pooling side):
-  // dX = dPpre . W1^T + att/P . dz . mask/keep  -- att [R], dz [N, C], keep bits [R * C / 8] (nullptr: all kept)
-  const float* pool_att = nullptr; const float* pool_dz = nullptr; const uint8_t* pool_bits = nullptr;
-  int pool_P = 0; float pool_inv_keep = 1.f;
-};
-
-static int pose_head_bwd_big(const void* X, const float* W1, const void* dPpre, void* dX, int accumulate_dX,
-                             float* dW1, char* w, const PosePlan& pl, float* gws, int R, int C, int Cp,
-                             int dtype, hipStream_t st, const void* W1_shadow = nullptr,
-                             const PoseBwdFuse* fuse = nullptr, ColsumJob* job = nullptr) {
-  const int tdt = dt_code(dtype);
+// The tail of every backward route, the two dense products: dW1 = X^T . dPpre and dX (+)= dPpre . W1^T.
+// job: a column sum nothing behind it reads (the MFMA rows pass's) -- it rides on the tail blocks of dW1's split-K
+// reduce launch when there is one (round 6), else it is a launch of its own here; null: already launched.
+// x: the fused step's extras (the W1 shadow, the pooling's dX share), or null
+static int pose_head_bwd_big(const PoseCall& c, const PoseBwd& b, const PoseStepArgs* x, ColsumJob* job) {
+  const int tdt = dt_code(c.dtype), R = (int)c.pl.R, C = c.C, Cp = c.Cp;
+  const void* dPpre = c.at(c.pl.off_dppre);
+  PoseTrace* tr = pose_trace();
   int rc;
   {  // dW1[c,j] = sum_r X[r,c] dPpre[r,j]
     GemmDesc g;
-    g.A = X; g.lda = C; g.ta = tdt; g.a_kc = false;
+    g.A = b.X; g.lda = C; g.ta = tdt; g.a_kc = false;
     g.B = dPpre; g.ldb = Cp; g.tb = tdt; g.b_kc = false;
-    g.C = dW1; g.ldc = Cp; g.tc = 0;
+    g.C = b.dW1; g.ldc = Cp; g.tc = 0;
     g.M = C; g.N = Cp; g.K = R;
-    g.splits = pose_dw1_splits(C, Cp, R, dtype); g.ws = gws;
+    g.splits = pose_dw1_splits(C, Cp, R, c.dtype); g.ws = reinterpret_cast<float*>(c.at(c.pl.off_gemm));
     g.tail = job;
-    PoseTrace* tr = pose_trace();
     GemmTrace gt;
     if (tr) g.trace = &gt;
-    rc = gemm_launch(g, st);
+    rc = gemm_launch(g, c.st);
     if (rc != APA_OK) return rc;
     if (tr) {
       tr->dw1_splits = gt.splits;
       if (job) tr->colsum = job->done ? POSE_COLSUM_TAIL : POSE_COLSUM_OWN;
     }
     if (job && !job->done) {     // no split-K reduce launch to ride on: the column sum as a launch of its own
-      rc = m1_colsum(job->a, st);
+      rc = m1_colsum(job->a, c.st);
       if (rc != APA_OK) return rc;
       job->done = true;
     }
   }
   {  // dX (+)= dPpre . W1^T
+    const PoseW1Op w1 = pose_w1_operand(c, b.W1, x ? x->W1_bf16 : nullptr, b.ws_from_fwd, &PoseTrace::w1_bwd);
     GemmDesc g;
     g.A = dPpre; g.lda = Cp; g.ta = tdt; g.a_kc = true;
-    int w1_tb = 0;
-    const void* W1op = W1_shadow;
-    PoseTrace* tr = pose_trace();
-    if (W1_shadow && dtype == APA_DTYPE_BF16) {
-      w1_tb = 1;
-      if (tr) tr->w1_bwd = POSE_W1_SHADOW;
-    } else {
-      W1op = pose_w1_operand(W1, w + pl.off_w1b, C, Cp, dtype, &w1_tb, st,
-                             (accumulate_dX & APA_POSE_WS_FROM_FWD) != 0, tr ? &tr->w1_bwd : nullptr);
-    }
-    g.B = W1op; g.ldb = Cp; g.tb = w1_tb; g.b_kc = true;   // W1 [C][Cp]: n = c rows, k contiguous
-    g.C = dX; g.ldc = C; g.tc = tdt;
-    g.M = R; g.N = C; g.K = Cp; g.beta = (accumulate_dX & 1) ? 1.f : 0.f;
+    g.B = w1.B; g.ldb = Cp; g.tb = w1.tb; g.b_kc = true;   // W1 [C][Cp]: n = c rows, k contiguous
+    g.C = b.dX; g.ldc = C; g.tc = tdt;
+    g.M = R; g.N = C; g.K = Cp; g.beta = b.accumulate ? 1.f : 0.f;
     g.stream_out = true;      // dX is the step's output: nothing in this call reads it back
-    if (fuse && fuse->pool_att) {   // nothing was written to dX: its pooling share is formed in this epilogue
+    if (x && x->pool_att) {   // nothing was written to dX: its pooling share is formed in this epilogue
       g.beta = 0.f;
-      g.r1_row = fuse->pool_att; g.r1_col = fuse->pool_dz; g.r1_bits = fuse->pool_bits; g.r1_P = fuse->pool_P;
-      g.r1_invP = 1.0f / (float)fuse->pool_P; g.r1_inv_keep = fuse->pool_inv_keep;
+      g.r1_row = x->pool_att; g.r1_col = x->pool_dz; g.r1_bits = x->pool_bits; g.r1_P = c.P;
+      g.r1_invP = 1.0f / (float)c.P; g.r1_inv_keep = x->pool_inv_keep;
     }
     if (tr) tr->dx_beta = g.beta != 0.f ? 1 : 0;
-    rc = gemm_launch(g, st);
+    rc = gemm_launch(g, c.st);
   }
   return rc;
 }
 
 // [dW2 | db1 | db2 (| dWa | dba)] from the [nblk][ld] partial rows of either rows kernel: one fixed-order column sum
-// for all of them; in the fused step the same blocks finish the pose loss (its block partials) and advance the dropout
-// counter.  c1: width of the dW2 section; perm_nthr > 0: that section is in pose_bwd_rows_kernel's permuted order.
-static ColsumArgs pose_rows_colsum(const float* partial, int nblk, int ld, int c1, int perm_nthr, int Cp, int J,
-                                   float* dW2, float* db1, float* db2, const PoseBwdFuse* fuse) {
+// for all of them; in the fused step (x) the same blocks finish the pose loss -- the block partials pose_fwd_fused's Pl
+// launch left in the workspace, one per block of it -- and advance the dropout counter.
+// c1: width of the dW2 section; perm_nthr > 0: that section is in pose_bwd_rows_kernel's permuted order.
+static ColsumArgs pose_rows_colsum(const PoseCall& c, const PoseBwd& b, const PoseStepArgs* x, int nblk, int ld,
+                                   int c1, int perm_nthr) {
   ColsumArgs a;
-  a.pdwa = partial; a.nblk = nblk; a.ld = ld;
-  a.dwa = dW2; a.perm_nthr = perm_nthr; a.perm_cp = Cp;
-  a.dwa2 = db1; a.C1 = c1; a.dwa3 = db2; a.C2 = c1 + Cp;
-  a.C = c1 + Cp + J;
-  if (fuse && fuse->dWa) { a.dwa4 = fuse->dWa; a.C3 = a.C; a.dwa5 = fuse->dba; a.C4 = a.C + Cp; a.C += Cp + 1; }
-  if (!fuse) return a;
-  a.rng_bump = fuse->rng_bump;
-  a.aux_src = fuse->aux_src; a.aux_n = fuse->aux_n; a.aux_scale = fuse->aux_scale; a.aux_dst = fuse->aux_dst;
+  a.pdwa = reinterpret_cast<const float*>(c.at(c.pl.off_partial)); a.nblk = nblk; a.ld = ld;
+  a.dwa = b.dW2; a.perm_nthr = perm_nthr; a.perm_cp = c.Cp;
+  a.dwa2 = b.db1; a.C1 = c1; a.dwa3 = b.db2; a.C2 = c1 + c.Cp;
+  a.C = c1 + c.Cp + c.J;
+  if (!x) return a;
+  if (x->dWa) { a.dwa4 = x->dWa; a.C3 = a.C; a.dwa5 = x->dba; a.C4 = a.C + c.Cp; a.C += c.Cp + 1; }
+  a.rng_bump = x->rng_bump;
+  a.aux_src = reinterpret_cast<const float*>(c.at(c.pl.off_lpart));
+  a.aux_n = (int)(x->W2T_bf16 ? (c.pl.R + 31) / 32 : (c.pl.R + 63) / 64);
+  a.aux_scale = 0.5f * x->pose_wt / ((float)c.N * (float)c.N * (float)c.P);
+  a.aux_dst = x->loss_pose;
   return a;
 }
 
-static int pose_head_bwd_impl(const void* X, const float* W1, const float* W2, const void* Ppre,
-                              const float* dPl, const void* dPpre_ext, const float* ext_row,
-                              const float* ext_col, void* dX, int accumulate_dX, float* dW1, float* db1,
-                              float* dW2, float* db2, void* ws, size_t ws_bytes, int N, int P, int C,
-                              int Cp, int J, int dtype, void* stream, const PoseBwdFuse* fuse = nullptr) {
-  if (!X || !W1 || !W2 || !Ppre || !dX || !dW1 || !db1 || !dW2 || !db2 || N <= 0 || P <= 0 ||
-      C <= 0 || Cp <= 0 || J <= 0) {
-    set_error("apa_pose_head_bwd: null pointer or non-positive dimension");
-    return APA_ERR_INVALID_ARG;
-  }
-  if (!dPl && !dPpre_ext && !ext_row) {
-    set_error("apa_pose_head_bwd: neither dPl nor dPpre_ext given (no gradient to propagate)");
-    return APA_ERR_INVALID_ARG;
-  }
-  if (J > 32 || Cp > 2048) {
-    set_error("apa_pose_head_bwd: J=%d > 32 or Cp=%d > 2048 not built", J, Cp);
-    return APA_ERR_UNSUPPORTED;
-  }
-  const PosePlan pl = pose_plan(N, P, C, Cp, J, dtype);
-  if (!ws || ws_bytes < pl.total) {
-    set_error("apa_pose_head_bwd: workspace too small (%zu < %zu)", ws_bytes, pl.total);
-    return APA_ERR_WORKSPACE;
-  }
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  char* w = static_cast<char*>(ws);
-  void* dPpre = w + pl.off_dppre;
-  float* partial = reinterpret_cast<float*>(w + pl.off_partial);
-  float* gws = reinterpret_cast<float*>(w + pl.off_gemm);
-  const int R = (int)pl.R;
-  const int tdt = dt_code(dtype);
+// The three arms of the backward pass.  Each writes dPpre to the workspace with its kernel, records what it ran and
+// sees to the column sums (and to dW2, where its kernel does not form it); pose_head_bwd_big follows.
 
-  if (Cp % 4 != 0) {
-    set_error("apa_pose_head_bwd: Cp=%d must be a multiple of 4", Cp);
-    return APA_ERR_UNSUPPORTED;
-  }
-  if (pose_bwd_rows_ok(dPl, Ppre, dPpre_ext, W2, Cp, J, dtype) &&
-      pose_rows_mfma_ok(dPl, dPpre_ext, ext_row, ext_col, W2, Ppre, Cp, J, dtype)) {
-    // round 6: the same pass on the matrix pipe (bf16 features); partial rows in NATURAL [dW2 | db1 | db2 (| dWa | dba)] order
-    const int nthr2 = Cp / 2;
-    // waves per block (a wave owns 64 channels) and 32-row groups per block.  Fewer partial rows mean less traffic
-    // here and in the column sum behind (G), small blocks let a CU overlap one block's loads with another's MFMAs
-    // and stores (wpb); measured at the benchmark shape (rows kernel + column sum, us): wpb 6 G 1 14.7 + 5.8,
-    // 6/2 12.3 + 4.8, 4/2 11.8 + 4.9, 3/2 11.5 + 4.8, 3/4 15.1 + 4.8, 2/4 15.7 + 4.8 (the VALU form: 16.3 + 5.5)
-    const int nw = Cp / 64;                           // waves a whole row takes
-    const int wpb = nw % 3 == 0 ? 3 : (nw % 4 == 0 ? 4 : 2);
-    const int ngrp = nw / wpb;
-    const int G = pl.R >= 2048 ? 2 : 1;
-    const int nblk = (int)((pl.R + 32L * G - 1) / (32L * G));
-    const size_t lds = (size_t)32 * (wpb * 64 + 8) * 2 + 32 * 20 * 4 + 32 * 4;
-    const size_t ldp = pose_rows_ld(Cp, J, nthr2);
-    const bool want_wa = fuse && fuse->dWa;
-    if (want_wa && !ext_row) {
-      set_error("apa_pose_head_bwd: the fused dWa / dba outputs need the rank-1 external gradient (internal)");
-      return APA_ERR_INVALID_ARG;
-    }
+// Round 6: the one-pass rows kernel on the matrix pipe (bf16 features); partial rows in NATURAL
+// [dW2 | db1 | db2 (| dWa | dba)] order.  Its column sum is handed on as `job`
+static int pose_rows_mfma(const PoseCall& c, const PoseBwd& b, const PoseStepArgs* x, ColsumJob* job) {
+  const PosePlan& pl = c.pl;
+  const float *dPl = b.dPl, *W2 = b.W2, *ext_row = b.ext_row, *ext_col = b.ext_col;
+  const void* Ppre = b.Ppre;
+  void* dPpre = c.at(pl.off_dppre);
+  float* partial = reinterpret_cast<float*>(c.at(pl.off_partial));
+  const int Cp = c.Cp, J = c.J;
+  hipStream_t st = c.st;
+  // waves per block (a wave owns 64 channels) and 32-row groups per block.  Fewer partial rows mean less traffic
+  // here and in the column sum behind (G), small blocks let a CU overlap one block's loads with another's MFMAs
+  // and stores (wpb); measured at the benchmark shape (rows kernel + column sum, us): wpb 6 G 1 14.7 + 5.8,
+  // 6/2 12.3 + 4.8, 4/2 11.8 + 4.9, 3/2 11.5 + 4.8, 3/4 15.1 + 4.8, 2/4 15.7 + 4.8 (the VALU form: 16.3 + 5.5)
+  const int nw = Cp / 64;                           // waves a whole row takes
+  const int wpb = nw % 3 == 0 ? 3 : (nw % 4 == 0 ? 4 : 2);
+  const int ngrp = nw / wpb;
+  const int G = pl.R >= 2048 ? 2 : 1;
+  const int nblk = (int)((pl.R + 32L * G - 1) / (32L * G));
+  const size_t lds = (size_t)32 * (wpb * 64 + 8) * 2 + 32 * 20 * 4 + 32 * 4;
+  const size_t ldp = pose_rows_ld(Cp, J, pose_rows_nthr(Cp));
+  const bool want_wa = x && x->dWa;
 #define APA_ROWSM(R1v, WAv)                                                                                      \
   hipLaunchKernelGGL((pose_bwd_rows_mfma_kernel<R1v, WAv>), dim3(nblk, ngrp), dim3(64 * wpb), lds, st, dPl, W2, ext_row, \
                      ext_col, static_cast<const bf16_t*>(Ppre), static_cast<bf16_t*>(dPpre), partial, pl.R, Cp, ldp, G)
-    if (PoseTrace* t = pose_trace()) {
-      t->rows = POSE_ROWS_MFMA; t->wpb = wpb; t->ngrp = ngrp; t->G = G; t->wa = want_wa ? 1 : 0;
-      t->form = ext_row ? POSE_FORM_RANK1 : POSE_FORM_PLAIN; t->dw2 = POSE_DW2_ROWS;
-    }
-    if (ext_row && want_wa) APA_ROWSM(true, true);
-    else if (ext_row) APA_ROWSM(true, false);
-    else APA_ROWSM(false, false);
-#undef APA_ROWSM
-    APA_LAUNCH_CHECK("pose_bwd_rows_mfma_kernel");
-    // Nothing behind the column sum reads its outputs: it rides on the tail blocks of dW1's split-K reduce launch
-    // when there is one (round 6), else it is a launch of its own
-    ColsumJob job;
-    job.a = pose_rows_colsum(partial, nblk, (int)ldp, Cp * J, 0, Cp, J, dW2, db1, db2, fuse);
-    return pose_head_bwd_big(X, W1, dPpre, dX, accumulate_dX, dW1, w, pl, gws, R, C, Cp, dtype, st,
-                             fuse ? fuse->W1_bf16 : nullptr, fuse, &job);
+  if (PoseTrace* t = pose_trace()) {
+    t->rows = POSE_ROWS_MFMA; t->wpb = wpb; t->ngrp = ngrp; t->G = G; t->wa = want_wa ? 1 : 0;
+    t->form = ext_row ? POSE_FORM_RANK1 : POSE_FORM_PLAIN; t->dw2 = POSE_DW2_ROWS;
   }
-  if (pose_bwd_rows_ok(dPl, Ppre, dPpre_ext, W2, Cp, J, dtype)) {
-    // one pass: dPpre + partial rows [dW2 | db1 | db2], one fixed-order column sum for all three
-    const int nthr2 = ((Cp / 2 + 63) / 64) * 64;
-    const int rpb = pose_rows_per_block(pl.R, nthr2, dtype, dPpre_ext != nullptr && !ext_row);
-    const int nblk = (int)((pl.R + rpb - 1) / rpb);
-    const size_t lds = pose_rows_lds(rpb, nthr2, dtype, dPpre_ext != nullptr && !ext_row);
+  if (ext_row && want_wa) APA_ROWSM(true, true);
+  else if (ext_row) APA_ROWSM(true, false);
+  else APA_ROWSM(false, false);
+#undef APA_ROWSM
+  APA_LAUNCH_CHECK("pose_bwd_rows_mfma_kernel");
+  job->a = pose_rows_colsum(c, b, x, nblk, (int)ldp, Cp * J, 0);
+  return APA_OK;
+}
+
+// The same pass on the VALU: dPpre + partial rows [dW2 | db1 | db2], one fixed-order column sum for all three
+static int pose_rows_valu(const PoseCall& c, const PoseBwd& b, const PoseStepArgs* x) {
+  const PosePlan& pl = c.pl;
+  const float *dPl = b.dPl, *W2 = b.W2, *ext_row = b.ext_row, *ext_col = b.ext_col;
+  const void *Ppre = b.Ppre, *dPpre_ext = b.dPpre_ext;
+  void* dPpre = c.at(pl.off_dppre);
+  float* partial = reinterpret_cast<float*>(c.at(pl.off_partial));
+  const int Cp = c.Cp, J = c.J;
+  hipStream_t st = c.st;
+  const int nthr2 = pose_rows_nthr(Cp);
+  const bool ext = dPpre_ext != nullptr && !ext_row;
+  const int rpb = pose_rows_per_block(pl.R, nthr2, c.dtype, ext);
+  const int nblk = (int)((pl.R + rpb - 1) / rpb);
+  const size_t lds = pose_rows_lds(rpb, nthr2, c.dtype, ext);
+  const bool want_wa = x && x->dWa;
 #define APA_ROWS2(T, R1v, EXTv, RPBv, WAv)                                                                      \
   hipLaunchKernelGGL((pose_bwd_rows_kernel<T, R1v, EXTv, RPBv, WAv>), dim3(nblk), dim3(nthr2), lds, st, dPl, W2, \
                      static_cast<const T*>(dPpre_ext), ext_row, ext_col, static_cast<const T*>(Ppre),       \
@@ -1093,45 +1110,38 @@ static int pose_head_bwd_impl(const void* X, const float* W1, const float* W2, c
   do {                                                                               \
     if (rpb == 32) APA_ROWS2(T, R1v, EXTv, 32, WAv); else APA_ROWS2(T, R1v, EXTv, 16, WAv); \
   } while (0)
-    const bool want_wa = fuse && fuse->dWa;
-    if (want_wa && !ext_row) {
-      set_error("apa_pose_head_bwd: the fused dWa / dba outputs need the rank-1 external gradient (internal)");
-      return APA_ERR_INVALID_ARG;
-    }
-    if (PoseTrace* t = pose_trace()) {
-      t->rows = POSE_ROWS_VALU; t->rpb = rpb; t->wa = want_wa ? 1 : 0; t->dw2 = POSE_DW2_ROWS;
-      t->form = ext_row ? POSE_FORM_RANK1 : (dPpre_ext ? POSE_FORM_EXT : POSE_FORM_PLAIN);
-      t->colsum = POSE_COLSUM_OWN;
-    }
-    if (dtype == APA_DTYPE_F32) {
-      // (no WA arm: the fused outputs need PoseBwdFuse::dWa, which only pose_bwd_fused sets, and
-      // apa_pose_attn_train_step calls that only when pose_step_fast_ok holds -- bf16 features)
-      if (want_wa) {
-        set_error("apa_pose_head_bwd: the fused dWa / dba outputs are built for bf16 features (internal)");
-        return APA_ERR_UNSUPPORTED;
-      }
-      if (ext_row) APA_ROWS(float, true, false, false);
-      else if (dPpre_ext) APA_ROWS(float, false, true, false);
-      else APA_ROWS(float, false, false, false);
-    } else {
-      if (ext_row && want_wa) APA_ROWS(bf16_t, true, false, true);
-      else if (ext_row) APA_ROWS(bf16_t, true, false, false);
-      else if (dPpre_ext) APA_ROWS(bf16_t, false, true, false);
-      else APA_ROWS(bf16_t, false, false, false);
-    }
+  if (PoseTrace* t = pose_trace()) {
+    t->rows = POSE_ROWS_VALU; t->rpb = rpb; t->wa = want_wa ? 1 : 0; t->dw2 = POSE_DW2_ROWS;
+    t->form = ext_row ? POSE_FORM_RANK1 : (dPpre_ext ? POSE_FORM_EXT : POSE_FORM_PLAIN);
+    t->colsum = POSE_COLSUM_OWN;
+  }
+  if (c.dtype == APA_DTYPE_F32) {   // (no WA arm: pose_head_bwd_impl refuses the fused outputs with fp32 features)
+    if (ext_row) APA_ROWS(float, true, false, false);
+    else if (dPpre_ext) APA_ROWS(float, false, true, false);
+    else APA_ROWS(float, false, false, false);
+  } else {
+    if (ext_row && want_wa) APA_ROWS(bf16_t, true, false, true);
+    else if (ext_row) APA_ROWS(bf16_t, true, false, false);
+    else if (dPpre_ext) APA_ROWS(bf16_t, false, true, false);
+    else APA_ROWS(bf16_t, false, false, false);
+  }
 #undef APA_ROWS2
 #undef APA_ROWS
-    APA_LAUNCH_CHECK("pose_bwd_rows_kernel");
-    const int ldp = (int)pose_rows_ld(Cp, J, nthr2), c1 = (int)pose_rows_dw2(Cp, J, nthr2);
-    int rc = m1_colsum(pose_rows_colsum(partial, nblk, ldp, c1, J == 16 ? nthr2 : 0, Cp, J, dW2, db1, db2, fuse), st);
-    if (rc != APA_OK) return rc;
-    return pose_head_bwd_big(X, W1, dPpre, dX, accumulate_dX, dW1, w, pl, gws, R, C, Cp, dtype, st,
-                             fuse ? fuse->W1_bf16 : nullptr, fuse);
-  }
-  if (fuse) {
-    set_error("apa_pose_head_bwd: the fused step needs the one-pass rows kernel (J <= 16, Cp <= 1024; internal)");
-    return APA_ERR_UNSUPPORTED;
-  }
+  APA_LAUNCH_CHECK("pose_bwd_rows_kernel");
+  const int ldp = (int)pose_rows_ld(Cp, J, nthr2), c1 = (int)pose_rows_dw2(Cp, J, nthr2);
+  return m1_colsum(pose_rows_colsum(c, b, x, nblk, ldp, c1, J == 16 ? nthr2 : 0), st);
+}
+
+// Every other shape (J <= 32, Cp <= 2048): dPpre by chunks of 8 rows, db1 / db2 from its block partials, dW2 as a
+// product of its own (all zero without a pose-loss gradient)
+static int pose_rows_dppre(const PoseCall& c, const PoseBwd& b) {
+  const PosePlan& pl = c.pl;
+  const float *dPl = b.dPl, *W2 = b.W2, *ext_row = b.ext_row, *ext_col = b.ext_col;
+  const void *Ppre = b.Ppre, *dPpre_ext = b.dPpre_ext;
+  void* dPpre = c.at(pl.off_dppre);
+  float* partial = reinterpret_cast<float*>(c.at(pl.off_partial));
+  const int Cp = c.Cp, J = c.J, R = (int)pl.R;
+  hipStream_t st = c.st;
   const int nthr = ((Cp / 4 + 63) / 64) * 64;   // one thread per 4 columns (<= 512: Cp <= 2048)
 #define APA_DPPRE(T, JM)                                                                            \
   do {                                                                                              \
@@ -1149,7 +1159,7 @@ static int pose_head_bwd_impl(const void* X, const float* W1, const float* W2, c
     t->form = ext_row ? POSE_FORM_RANK1 : (dPpre_ext ? POSE_FORM_EXT : POSE_FORM_PLAIN);
     t->dw2 = dPl ? POSE_DW2_GEMM : POSE_DW2_MEMSET;
   }
-  if (dtype == APA_DTYPE_F32) {
+  if (c.dtype == APA_DTYPE_F32) {
     if (J <= 16) APA_DPPRE(float, 16); else APA_DPPRE(float, 32);
   } else {
     if (J <= 16) APA_DPPRE(bf16_t, 16); else APA_DPPRE(bf16_t, 32);
@@ -1158,78 +1168,81 @@ static int pose_head_bwd_impl(const void* X, const float* W1, const float* W2, c
   APA_LAUNCH_CHECK("pose_dppre_kernel");
   // db1 = column sums of dPpre, db2 = column sums of dPl (fixed-order reduce of the block partials)
   ColsumArgs cs;
-  cs.pdwa = partial; cs.nblk = pl.nchunks; cs.C = Cp + J; cs.ld = Cp + J; cs.dwa = db1; cs.dwa2 = db2; cs.C1 = Cp;
-  int rc = m1_colsum(cs, st);
+  cs.pdwa = partial; cs.nblk = pl.nchunks; cs.C = Cp + J; cs.ld = Cp + J; cs.dwa = b.db1; cs.dwa2 = b.db2; cs.C1 = Cp;
+  const int rc = m1_colsum(cs, st);
   if (rc != APA_OK) return rc;
-
-  if (dPl) {  // dW2[j,q] = sum_r Ppre[r,j] dPl[r,q]
-    GemmDesc g;
-    g.A = Ppre; g.lda = Cp; g.ta = tdt; g.a_kc = false;
-    g.B = dPl; g.ldb = J; g.tb = 0; g.b_kc = false;
-    g.C = dW2; g.ldc = J; g.tc = 0;
-    g.M = Cp; g.N = J; g.K = R;
-    g.splits = gemm_pick_splits(Cp, J, R); g.ws = gws;
-    rc = gemm_launch(g, st);
-    if (rc != APA_OK) return rc;
-  } else {
-    APA_HIP_CHECK(hipMemsetAsync(dW2, 0, (size_t)Cp * J * sizeof(float), st));
+  if (!dPl) {
+    APA_HIP_CHECK(hipMemsetAsync(b.dW2, 0, (size_t)Cp * J * sizeof(float), st));
+    return APA_OK;
   }
-  return pose_head_bwd_big(X, W1, dPpre, dX, accumulate_dX, dW1, w, pl, gws, R, C, Cp, dtype, st);
+  GemmDesc g;  // dW2[j,q] = sum_r Ppre[r,j] dPl[r,q]
+  g.A = Ppre; g.lda = Cp; g.ta = dt_code(c.dtype); g.a_kc = false;
+  g.B = dPl; g.ldb = J; g.tb = 0; g.b_kc = false;
+  g.C = b.dW2; g.ldc = J; g.tc = 0;
+  g.M = Cp; g.N = J; g.K = R;
+  g.splits = gemm_pick_splits(Cp, J, R); g.ws = reinterpret_cast<float*>(c.at(pl.off_gemm));
+  return gemm_launch(g, st);
+}
+
+// The backward pass: checks, route, arm, tail.  x: the fused step's extras, or null.  The three refusals under `x`
+// can fire from internal callers only (apa_pose_attn_train_step takes this route when pose_step_fast_ok holds)
+static int pose_head_bwd_impl(const PoseCall& c, const PoseBwd& b, const PoseStepArgs* x = nullptr) {
+  int rc = pose_check(c, b.X && b.W1 && b.W2 && b.Ppre && b.dX && b.dW1 && b.db1 && b.dW2 && b.db2, &b);
+  if (rc != APA_OK) return rc;
+  const PoseRows rows = pose_rows_route(c, b);
+  if (x && rows == POSE_ROWS_DPPRE) {
+    set_error("%s: the fused step needs the one-pass rows kernel (J <= 16, Cp <= 1024; internal)", c.fn);
+    return APA_ERR_UNSUPPORTED;
+  }
+  if (x && x->dWa && !b.ext_row) {
+    set_error("%s: the fused dWa / dba outputs need the rank-1 external gradient (internal)", c.fn);
+    return APA_ERR_INVALID_ARG;
+  }
+  if (x && x->dWa && c.dtype == APA_DTYPE_F32) {
+    set_error("%s: the fused dWa / dba outputs are built for bf16 features (internal)", c.fn);
+    return APA_ERR_UNSUPPORTED;
+  }
+  ColsumJob job;
+  switch (rows) {
+    case POSE_ROWS_MFMA: rc = pose_rows_mfma(c, b, x, &job); break;
+    case POSE_ROWS_VALU: rc = pose_rows_valu(c, b, x); break;
+    default: rc = pose_rows_dppre(c, b); break;
+  }
+  if (rc != APA_OK) return rc;
+  return pose_head_bwd_big(c, b, x, rows == POSE_ROWS_MFMA ? &job : nullptr);
 }
 
 // ---------------------------------------------------------------------------------------------
-// The pose-head halves of the one-call cfg 003 step (apa_pose_attn_train_step, apa_capi.hip)
+// The pose-head halves of the one-call cfg 003 steps (apa_capi.hip)
 // ---------------------------------------------------------------------------------------------
 namespace apa {
 
-void* pose_ws_loss_scratch(void* ws, int N, int P, int C, int Cp, int J, int dtype) {
-  return static_cast<char*>(ws) + pose_plan(N, P, C, Cp, J, dtype).off_lpart;
-}
+void* pose_ws_loss_scratch(const PoseCall& c) { return c.at(c.pl.off_lpart); }
 
-bool pose_step_fast_ok(int N, int P, int C, int Cp, int J, int dtype, const void* Ppre, const float* W2,
-                       const float* wa) {
-  const int nthr = ((Cp / 2 + 63) / 64) * 64;
-  return dtype == APA_DTYPE_BF16 && J == 16 && pose_pl_fast(Cp, J, dtype, Ppre) &&
-         (reinterpret_cast<uintptr_t>(W2) & 15) == 0 && (reinterpret_cast<uintptr_t>(wa) & 15) == 0 &&
-         Cp % 4 == 0 && Cp <= 1024 && pose_rows_lds(16, nthr, dtype, false) <= 65536 && N > 0 && P > 0 && C > 0;
+// The fused halves below serve a step whose forward half can take the skinny Pl product with both extras and whose
+// backward half (dPl and the rank-1 gradient dZ (x) wa given) takes a one-pass rows kernel with the WA outputs
+bool pose_step_fast_ok(const PoseCall& c, const PoseFwd& f, const PoseBwd& b) {
+  return c.dtype == APA_DTYPE_BF16 && c.J == 16 && pose_pl_fast(c.Cp, c.J, c.dtype, f.Ppre) &&
+         (reinterpret_cast<uintptr_t>(b.ext_col) & 15) == 0 && pose_rows_route(c, b) != POSE_ROWS_DPPRE &&
+         pose_dims_ok(c.N, c.P, c.C, c.Cp, c.J);
 }
 
 // Ppre = relu(X.W1 + b1); then ONE launch for Pl = Ppre.W2 + b2, the attention logits Z = Ppre.wa + ba and the
-// pose L2 loss (dPl + block partials kept in the workspace until pose_bwd_fused's last launch sums them)
-int pose_fwd_fused(const void* X, const float* W1, const float* b1, const float* W2, const float* b2, void* Ppre,
-                   float* Pl, void* ws, size_t ws_bytes, int N, int P, int C, int Cp, int J, int dtype,
-                   const PoseStepArgs& a, hipStream_t st) {
-  const PosePlan pl = pose_plan(N, P, C, Cp, J, dtype);
-  if (!ws || ws_bytes < pl.total) {
-    set_error("apa_pose_attn_train_step: pose workspace too small (%zu < %zu)", ws_bytes, pl.total);
-    return APA_ERR_WORKSPACE;
-  }
-  char* w = static_cast<char*>(ws);
-  const int R = (int)pl.R;
-  int w1_tb = 0;
-  const void* W1op = a.W1_bf16;
-  PoseTrace* tr = pose_trace();
-  if (W1op) {
-    w1_tb = 1;
-    if (tr) tr->w1_fwd = POSE_W1_SHADOW;
-  } else {
-    W1op = pose_w1_operand(W1, w + pl.off_w1b, C, Cp, dtype, &w1_tb, st, false, tr ? &tr->w1_fwd : nullptr);
-  }
-  GemmDesc g1;  // Ppre = relu(X.W1 + b1)
-  g1.A = X; g1.lda = C; g1.ta = dt_code(dtype); g1.a_kc = true;
-  g1.B = W1op; g1.ldb = Cp; g1.tb = w1_tb; g1.b_kc = false;
-  g1.C = Ppre; g1.ldc = Cp; g1.tc = dt_code(dtype);
-  g1.M = R; g1.N = Cp; g1.K = C; g1.bias = b1; g1.act = 1;
-  int rc = gemm_launch(g1, st);
+// pose L2 loss (dPl + block partials kept in the workspace until pose_bwd_fused's last launch sums them).
+// pose_step_fast_ok held: the skinny product serves the shape
+int pose_fwd_fused(const PoseCall& c, const PoseFwd& f, const PoseStepArgs& a) {
+  int rc = pose_check(c, true);
   if (rc != APA_OK) return rc;
-  const float denom = (float)N * (float)N * (float)P;          // loss.py:54-62 (apa_pose_l2_loss_fwd_bwd)
+  rc = gemm_launch(pose_ppre_product(c, f, pose_w1_operand(c, f.W1, a.W1_bf16, false, &PoseTrace::w1_fwd)), c.st);
+  if (rc != APA_OK) return rc;
+  const float denom = (float)c.N * (float)c.N * (float)c.P;          // loss.py:54-62 (apa_pose_l2_loss_fwd_bwd)
   PosePlExtra x;
   x.wa = a.wa; x.ba = a.ba; x.att = a.att; x.act = a.relu_att ? 1 : 0;
   x.lbl = a.pose_labels; x.valid = a.pose_valid; x.dPl = a.dPl;
-  x.lpart = reinterpret_cast<float*>(w + pl.off_lpart);
-  x.gcoef = a.grad_scale * a.pose_wt / denom; x.P = P;
+  x.lpart = reinterpret_cast<float*>(c.at(c.pl.off_lpart));
+  x.gcoef = a.grad_scale * a.pose_wt / denom; x.P = c.P;
   x.w2t = static_cast<const bf16_t*>(a.W2T_bf16);
-  return pose_pl_launch(static_cast<const bf16_t*>(Ppre), W2, b2, Pl, R, Cp, J, &x, st);
+  return pose_pl_launch(c, f, &x);
 }
 
 // att[r] = act(sum_t zp[t][r] + ba): the N / 128 column-tile partials of the contracted epilogue (GemmDesc::zp_*), summed
@@ -1250,103 +1263,61 @@ size_t pose_eval_zpart_bytes(int N, int P, int Cp) {
   return align_up((size_t)((Cp + 127) / 128) * (size_t)N * P * 4, 256);
 }
 
-// The pose-head half of apa_pose_attn_eval_step.  Fused route (*route = 1; Pl == nullptr, bf16 operands, the product
-// served by the contracted epilogue): Ppre = relu(X.W1 + b1) is formed tile by tile, contracted with wa and never
-// stored; att receives Z = Ppre.wa + ba (id / relu).  Composed route (*route = 0): Ppre goes to the workspace's dPpre
-// region (*ppre), Pl -- when asked for -- comes from the skinny product, whose FUSED form emits att on the same pass
-// where it serves the shape.  *att_ready: att holds Z; else the pooling call's own GEMV forms it from *ppre.
-int pose_eval_fwd(const void* X, const float* W1, const float* b1, const float* W2, const float* b2,
-                  const void* W1_bf16, const float* wa, const float* ba, bool relu_att, float* att, float* Pl, void* ws,
-                  size_t ws_bytes, float* zpart, int N, int P, int C, int Cp, int J, int dtype, hipStream_t st,
-                  int* route, const void** ppre, bool* att_ready) {
-  const PosePlan pl = pose_plan(N, P, C, Cp, J, dtype);
-  if (!ws || ws_bytes < pl.total) {
-    set_error("apa_pose_attn_eval_step: pose workspace too small (%zu < %zu)", ws_bytes, pl.total);
-    return APA_ERR_WORKSPACE;
-  }
-  char* w = static_cast<char*>(ws);
-  const int R = (int)pl.R;
-  int w1_tb = 0;
-  const void* W1op = W1_bf16;
-  PoseTrace* tr = pose_trace();
-  if (W1op && dtype == APA_DTYPE_BF16 && (reinterpret_cast<uintptr_t>(W1op) & 15) == 0) {
-    w1_tb = 1;
-    if (tr) tr->w1_fwd = POSE_W1_SHADOW;
-  } else {
-    W1op = pose_w1_operand(W1, w + pl.off_w1b, C, Cp, dtype, &w1_tb, st, false, tr ? &tr->w1_fwd : nullptr);
-  }
-  GemmDesc g1;  // Ppre = relu(X.W1 + b1)
-  g1.A = X; g1.lda = C; g1.ta = dt_code(dtype); g1.a_kc = true;
-  g1.B = W1op; g1.ldb = Cp; g1.tb = w1_tb; g1.b_kc = false;
-  g1.ldc = Cp; g1.tc = dt_code(dtype);
-  g1.M = R; g1.N = Cp; g1.K = C; g1.bias = b1; g1.act = 1;
-  int rc;
-  if (!Pl && zpart) {
-    g1.zp_w = wa; g1.zp_out = zpart;
+// The pose-head half of apa_pose_attn_eval_step; a: the W1 shadow and the attention conv (wa, ba, att, relu_att).
+// Fused route (out->route = 1; no Pl asked for, bf16 operands, the product served by the contracted epilogue):
+// Ppre = relu(X.W1 + b1) is formed tile by tile, contracted with wa and never stored; att receives Z = Ppre.wa + ba
+// (id / relu).  Composed route (route = 0): Ppre goes to the workspace's dPpre region (out->ppre), Pl -- when asked
+// for -- comes from pose_pl_product, whose skinny FUSED form emits att on the same pass where it serves the shape.
+// out->att_ready: att holds Z; else the pooling call's own GEMV forms it from out->ppre.
+int pose_eval_fwd(const PoseCall& c, const PoseFwd& f, const PoseStepArgs& a, float* zpart, PoseEvalOut* out) {
+  int rc = pose_check(c, true);
+  if (rc != APA_OK) return rc;
+  const int R = (int)c.pl.R;
+  PoseFwd fw = f;
+  fw.Ppre = nullptr;
+  GemmDesc g1 = pose_ppre_product(c, fw, pose_w1_operand(c, f.W1, a.W1_bf16, false, &PoseTrace::w1_fwd));
+  if (!f.Pl && zpart) {
+    g1.zp_w = a.wa; g1.zp_out = zpart;
     if (gemm_bf16_zp_serves(g1)) {
-      if ((rc = gemm_launch(g1, st)) != APA_OK) return rc;
-      hipLaunchKernelGGL(pose_zpart_finish_kernel, dim3((unsigned)((R + 255) / 256)), dim3(256), 0, st, zpart, Cp / 128,
-                         (long)R, ba, relu_att ? 1 : 0, att);
+      if ((rc = gemm_launch(g1, c.st)) != APA_OK) return rc;
+      hipLaunchKernelGGL(pose_zpart_finish_kernel, dim3((unsigned)((R + 255) / 256)), dim3(256), 0, c.st, zpart,
+                         c.Cp / 128, (long)R, a.ba, a.relu_att ? 1 : 0, a.att);
       APA_LAUNCH_CHECK("pose_zpart_finish_kernel");
-      *route = 1; *ppre = nullptr; *att_ready = true;
+      *out = {1, nullptr, true};
       return APA_OK;
     }
     g1.zp_w = nullptr; g1.zp_out = nullptr;
   }
-  void* Ppre = w + pl.off_dppre;
-  g1.C = Ppre;
-  if ((rc = gemm_launch(g1, st)) != APA_OK) return rc;
-  *route = 0; *ppre = Ppre; *att_ready = false;
-  if (!Pl) return APA_OK;
-  if (pose_pl_fast(Cp, J, dtype, Ppre)) {   // the skinny product; with a 16-byte addressable wa the same pass emits att
-    const bool fz = (reinterpret_cast<uintptr_t>(wa) & 15) == 0;
-    PosePlExtra x = {wa, ba, att, relu_att ? 1 : 0, nullptr, nullptr, nullptr, nullptr, 0.f, P, nullptr};
-    *att_ready = fz;
-    return pose_pl_launch(static_cast<const bf16_t*>(Ppre), W2, b2, Pl, R, Cp, J, fz ? &x : nullptr, st);
-  }
-  if (tr) tr->pl = POSE_PL_GEMM;
-  GemmDesc g2;  // Pl = Ppre.W2 + b2
-  g2.A = Ppre; g2.lda = Cp; g2.ta = dt_code(dtype); g2.a_kc = true;
-  g2.B = W2; g2.ldb = J; g2.tb = 0; g2.b_kc = false;
-  g2.C = Pl; g2.ldc = J; g2.tc = 0;
-  g2.M = R; g2.N = J; g2.K = Cp; g2.bias = b2;
-  g2.splits = gemm_pick_splits(R, J, Cp); g2.ws = reinterpret_cast<float*>(w + pl.off_gemm);
-  return gemm_launch(g2, st);
+  fw.Ppre = c.at(c.pl.off_dppre);
+  g1.C = fw.Ppre;
+  if ((rc = gemm_launch(g1, c.st)) != APA_OK) return rc;
+  *out = {0, fw.Ppre, false};
+  if (!f.Pl) return APA_OK;
+  // with the skinny product and a 16-byte addressable wa the same pass emits att
+  const bool fz = pose_pl_fast(c.Cp, c.J, c.dtype, fw.Ppre) && (reinterpret_cast<uintptr_t>(a.wa) & 15) == 0;
+  const PosePlExtra x = {a.wa, a.ba, a.att, a.relu_att ? 1 : 0, nullptr, nullptr, nullptr, nullptr, 0.f, c.P, nullptr};
+  out->att_ready = fz;
+  return pose_pl_product(c, fw, fz ? &x : nullptr);
 }
 
 // dPpre (+ the rank-1 attention-branch gradient dZ (x) wa), dW2, db1, db2, dWa, dba in one pass + one column
 // sum that also finishes the pose loss and advances the dropout counter; then dW1 and dX (+)= dPpre.W1^T
-int pose_bwd_fused(const void* X, const float* W1, const float* W2, const void* Ppre, const float* dPl,
-                   const float* dZ, const float* wa, void* dX, int accumulate_dX, float* dW1, float* db1,
-                   float* dW2, float* db2, float* dWa, float* dba, float* loss_pose, uint64_t* rng_bump,
-                   void* ws, size_t ws_bytes, int N, int P, int C, int Cp, int J, int dtype,
-                   const PoseStepArgs& a, hipStream_t st) {
-  const PosePlan pl = pose_plan(N, P, C, Cp, J, dtype);
-  PoseBwdFuse f;
-  f.dWa = dWa; f.dba = dba;
-  f.aux_src = reinterpret_cast<const float*>(static_cast<char*>(ws) + pl.off_lpart);
-  f.aux_n = (int)(a.W2T_bf16 ? (pl.R + 31) / 32 : (pl.R + 63) / 64);     // loss partials: one per block of the Pl launch
-  f.aux_scale = 0.5f * a.pose_wt / ((float)N * (float)N * (float)P);
-  f.aux_dst = loss_pose;
-  f.rng_bump = rng_bump;
-  f.W1_bf16 = a.W1_bf16;
-  f.pool_att = a.pool_att; f.pool_dz = a.pool_dz; f.pool_bits = a.pool_bits; f.pool_P = P;
-  f.pool_inv_keep = a.pool_inv_keep;
-  return pose_head_bwd_impl(X, W1, W2, Ppre, dPl, nullptr, dZ, wa, dX, accumulate_dX, dW1, db1, dW2, db2, ws,
-                            ws_bytes, N, P, C, Cp, J, dtype, st, &f);
-}
+int pose_bwd_fused(const PoseCall& c, const PoseBwd& b, const PoseStepArgs& a) { return pose_head_bwd_impl(c, b, &a); }
 
 }  // namespace apa
 
+// (the two bits of the public accumulate_dX are taken apart here and nowhere else)
 extern "C" int apa_pose_head_bwd(const void* X, const float* W1, const float* W2, const void* Ppre,
                                  const float* dPl, const void* dPpre_ext, void* dX, int accumulate_dX,
                                  float* dW1, float* db1, float* dW2, float* db2, void* ws,
                                  size_t ws_bytes, int N, int P, int C, int Cp, int J, int dtype,
                                  void* stream) {
-  return pose_head_bwd_impl(X, W1, W2, Ppre, dPl, dPpre_ext, nullptr, nullptr, dX, accumulate_dX, dW1, db1,
-                            dW2, db2, ws, ws_bytes, N, P, C, Cp, J, dtype, stream);
+  return pose_head_bwd_impl(pose_call("apa_pose_head_bwd", N, P, C, Cp, J, dtype, ws, ws_bytes, stream),
+                            PoseBwd{X, W1, W2, Ppre, dPl, dPpre_ext, nullptr, nullptr, dX, dW1, db1, dW2, db2,
+                                    (accumulate_dX & 1) != 0, (accumulate_dX & APA_POSE_WS_FROM_FWD) != 0});
 }
 
+// (everything behind its own check reports as apa_pose_head_bwd, whose second form it is)
 extern "C" int apa_pose_head_bwd_rank1ext(const void* X, const float* W1, const float* W2,
                                           const void* Ppre, const float* dPl, const float* ext_row,
                                           const float* ext_col, void* dX, int accumulate_dX, float* dW1,
@@ -1356,6 +1327,7 @@ extern "C" int apa_pose_head_bwd_rank1ext(const void* X, const float* W1, const 
     set_error("apa_pose_head_bwd_rank1ext: null ext_row / ext_col");
     return APA_ERR_INVALID_ARG;
   }
-  return pose_head_bwd_impl(X, W1, W2, Ppre, dPl, nullptr, ext_row, ext_col, dX, accumulate_dX, dW1, db1,
-                            dW2, db2, ws, ws_bytes, N, P, C, Cp, J, dtype, stream);
+  return pose_head_bwd_impl(pose_call("apa_pose_head_bwd", N, P, C, Cp, J, dtype, ws, ws_bytes, stream),
+                            PoseBwd{X, W1, W2, Ppre, dPl, nullptr, ext_row, ext_col, dX, dW1, db1, dW2, db2,
+                                    (accumulate_dX & 1) != 0, (accumulate_dX & APA_POSE_WS_FROM_FWD) != 0});
 }

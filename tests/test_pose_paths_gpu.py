@@ -51,9 +51,10 @@ def case(name, N, P, C, Cp, J, *, dt=BF16, form='plain', dpl=True, entry='sep', 
                 mis=dict(mis), images=tuple(images), train=train, expect=expect)
 
 
-# Expected traces are read off the dispatch conditions of apa_pose_head.hip (pose_pl_fast / pose_pl_launch,
-# pose_rows_mfma_ok, pose_bwd_rows_ok, pose_rows_lds / pose_rows_per_block, pose_head_bwd_impl, pose_w1_operand,
-# pose_dw1_splits + gemm_launch's tail rule) -- not off a run.
+# Expected traces are read off the dispatch conditions of apa_pose_head.hip (pose_pl_fast / pose_pl_product /
+# pose_pl_launch, pose_rows_route = pose_rows_mfma_ok + pose_bwd_rows_ok, pose_rows_lds / pose_rows_per_block, the arms
+# pose_rows_mfma / pose_rows_valu / pose_rows_dppre, pose_w1_operand, pose_dw1_splits + gemm_launch's tail rule in
+# pose_head_bwd_big) -- not off a run.
 #   mfma:  bf16, dPl, J = 16, Cp % 128 = 0, 256 <= Cp <= 1024, 16-byte aligned, no dense ext;  nw = Cp / 64,
 #          wpb = 3 if nw % 3 == 0 else 4 if nw % 4 == 0 else 2, ngrp = nw / wpb, G = 2 iff R >= 2048
 #   valu:  dPl, J <= 16, Cp <= 1024, 8-byte aligned Ppre / ext, 16 rows fit 64 KB;  rpb = 32 iff R >= 4065 and 32 rows fit
