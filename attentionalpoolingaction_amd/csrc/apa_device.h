@@ -225,6 +225,17 @@ __device__ __forceinline__ int xcd_remap(int b, int nblk) {
   return base + idx;
 }
 
+// Pixels [p_begin, p_end) of split s of the S balanced splits of an image's P pixels (sizes differ by <= 1), in
+// 32-bit arithmetic: (S + 1) * P has to fit 31 bits -- m1_pix_range_ok, which m1_call_fill (apa_m1.hip) checks before
+// the first launch.  (As 64-bit quotients the two divisions were ~130 scalar instructions each in front of the
+// streaming kernels' first load.)
+__host__ __device__ inline bool m1_pix_range_ok(int P, int S) { return ((long long)S + 1) * P < (1ll << 31); }
+__host__ __device__ __forceinline__ void m1_pix_range(int s, int P, int S, int& p_begin, int& p_end) {
+  const unsigned lo = (unsigned)s * (unsigned)P;
+  p_begin = (int)(lo / (unsigned)S);
+  p_end = (int)((lo + (unsigned)P) / (unsigned)S);
+}
+
 // reductions over HALF a wave (lanes 0-31 / 32-63 reduce independently): softmax rows
 __device__ __forceinline__ float half_sum(float v, int lane) {
   v = row_sum16(v);
@@ -501,10 +512,16 @@ __device__ __forceinline__ float m1_abar_tail(float row0, int P) {
   const float asum = (w0 + 0.f) + (0.f + 0.f);       // waves 1..3 of the block
   return asum * (1.0f / (float)P);
 }
-__device__ __forceinline__ float m1_abar_wave(const float* __restrict__ pstat, int n, int S, int P, int lane) {
-  const float a_s = lane < S ? pstat[((size_t)n * S + lane) * 4 + 2] : 0.f;
+// (in two halves, for a caller that has other loads to request between this lane's load and its use)
+__device__ __forceinline__ float m1_abar_wave_load(const float* __restrict__ pstat, int n, int S, int lane) {
+  return lane < S ? pstat[((size_t)n * S + lane) * 4 + 2] : 0.f;
+}
+__device__ __forceinline__ float m1_abar_wave_sum(float a_s, int P) {
   const float w0 = wave_sum(a_s);
   return ((w0 + 0.f) + (0.f + 0.f)) * (1.0f / (float)P);
+}
+__device__ __forceinline__ float m1_abar_wave(const float* __restrict__ pstat, int n, int S, int P, int lane) {
+  return m1_abar_wave_sum(m1_abar_wave_load(pstat, n, S, lane), P);
 }
 __device__ __forceinline__ float m1_abar_thread(const float* __restrict__ pstat, int n, int S, int P) {
   float a[16];

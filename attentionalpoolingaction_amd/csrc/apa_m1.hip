@@ -31,8 +31,8 @@ namespace apa {
 //   abar[n] = (1/P) sum_p A[n,p];  softmax: att[n,p] <- exp(Z - M)/L
 // --------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void m1_finalize_fwd_kernel(
-    const float* __restrict__ pacc, const float* __restrict__ pstat, float* __restrict__ z,
-    float* __restrict__ abar, float* __restrict__ att, int P, int S, int C, int online_softmax, int cw) {
+    const float* __restrict__ pacc, const float* __restrict__ pstat, int P, int S, int C, int online_softmax, int cw,
+    float* __restrict__ z, float* __restrict__ abar, float* __restrict__ att) {   // inputs and sizes first: preload
   // cw = threads of the block that carry channels (one float4 each): the grid is (N, ceil(C / 4cw)).  A CU
   // sustains only ~25-30 GB/s of vector loads, so the 4 MB of partials want to be spread over all 256
   // CUs (cw = 64 at N = 32: 256 blocks x 16 KB) rather than 64 blocks x 64 KB (cw = 256).
@@ -416,6 +416,11 @@ int m1_call_fill(M1Call& c, const PoolCall& d, const M1Fwd* f, const M1Bwd* b, c
   }
 
   // ---- every refusal of the path: nothing has been launched yet ----
+  // the streaming kernels split an image's pixels in 32-bit arithmetic (m1_pix_range); the other families keep 64 bits
+  if (c.pool == M1_POOL_STREAM && !m1_pix_range_ok(P, c.pl.S)) {
+    set_error("attn_pool M=1: P=%d pixels per image in S=%d splits: (S + 1) * P does not fit 31 bits", P, c.pl.S);
+    return APA_ERR_UNSUPPORTED;
+  }
   if (c.no_dx && (c.fused || !c.maskbits_in || !m1_no_dx_supported(C, dtype, c.train) || rng_external(flags) || cat)) {
     set_error("attn_pool M=1: NO_DX needs a separate attention input, the forward half's keep bits and the bf16 "
               "streaming kernels (internal)");
@@ -505,7 +510,7 @@ int m1_forward(const M1Call& c, const M1Fwd& io, M1Xent* xf) {
   }
   if (!fold) {
     hipLaunchKernelGGL(m1_finalize_fwd_kernel, dim3(N, (C + 4 * cw - 1) / (4 * cw)), dim3(256), 0, c.st, c.pacc,
-                       c.pstat, io.zsave, io.abar, io.att, c.P, c.pl.S, C, online, cw);
+                       c.pstat, c.P, c.pl.S, C, online, cw, io.zsave, io.abar, io.att);
     APA_LAUNCH_CHECK("m1_finalize_fwd_kernel");
   }
   // logits = z . Wt + abar (x) bt -- the first reader of Wt / bt (apa_hooks.td_weights_ready_event)

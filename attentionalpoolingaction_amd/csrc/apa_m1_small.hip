@@ -27,11 +27,11 @@ __device__ __forceinline__ f32x4 mfma16(float a, float b, f32x4 c) {
 
 // L2: logits[n,k] = sum_cc part[cc][n][k] + abar[n] * bt[k]   (fixed order over cc)
 // pstat (the folded route): abar is formed here from the pooling pass's statistics and stored for the backward pass
-__global__ __launch_bounds__(256) void m1_logits_reduce_kernel(const float* __restrict__ part, float* abar,
-                                                               const float* __restrict__ bt,
-                                                               float* __restrict__ logits, int N,
-                                                               int K, int nchunks,
-                                                               const float* __restrict__ pstat, int S, int P) {
+__global__ __launch_bounds__(256) void m1_logits_reduce_kernel(const float* __restrict__ part,
+                                                               const float* __restrict__ pstat,
+                                                               const float* __restrict__ bt, int N, int K,
+                                                               int nchunks, int S, int P, float* abar,
+                                                               float* __restrict__ logits) {
   const int idx = blockIdx.x * 256 + threadIdx.x;
   if (idx >= N * K) return;
   const int n = idx / K, k = idx - n * K;
@@ -59,26 +59,27 @@ __global__ __launch_bounds__(256) void m1_logits_reduce_kernel(const float* __re
 // is left to the backward head kernel, which follows in the same host call.
 // EVAL (apa_attn_head_eval_step without ground truth): no labels, no loss, no gradient -- the row's
 // softmax probabilities and first-index argmax instead (eval.py:193-197).
+// Parameter order (all kernels of this file): the pointers and sizes of a block's first batch of global loads lie in
+// the first 14 argument dwords, which kernarg preload (Makefile) hands the wave in SGPRs -- no scalar-memory wait in
+// front of that batch; the outputs' pointers follow and are fetched under it.
 template <int NV4, bool EVAL>   // NV4: 16-byte vectors per lane of the half-wave, K <= 512
 __global__ __launch_bounds__(256) void m1_logits_xent_kernel(
-    const float* __restrict__ part, float* abar, const float* __restrict__ bt,
-    const int64_t* __restrict__ labels, float* __restrict__ logits, float* __restrict__ out_loss,
-    float* __restrict__ G, float* __restrict__ probs, int64_t* __restrict__ pred, int N, int K,
-    int nchunks, float gscale, const float* __restrict__ pstat, int S, int P) {
+    const float* __restrict__ part, const float* __restrict__ pstat, const int64_t* __restrict__ labels,
+    const float* __restrict__ bt, int N, int K, int nchunks, int S, int P, float gscale,
+    // ---- beyond the preload window ----
+    float* abar, float* __restrict__ logits, float* __restrict__ out_loss, float* __restrict__ G,
+    float* __restrict__ probs, int64_t* __restrict__ pred) {
   typedef float f4u __attribute__((ext_vector_type(4), aligned(4)));
   constexpr int EPT = NV4 == 4 ? 2 : 1;
   __shared__ float row[NV4 * 128];
   const int n = blockIdx.x, tid = threadIdx.x;
   const size_t stride = (size_t)N * K;
   const float* prow = part + (size_t)n * K;
-  // pstat (the folded route): abar[n] is formed here, by every wave alike, and stored for the backward pass
-  float ab;
-  if (pstat) {
-    ab = m1_abar_wave(pstat, n, S, P, tid & 63);
-    if (tid == 0) abar[n] = ab;
-  } else {
-    ab = abar[n];
-  }
+  // pstat (the folded route): abar[n] is formed here, by every wave alike, and stored for the backward pass.  Its
+  // load goes out with bt and the partials, one batch; the sum and the store wait behind them.
+  float a_s = 0.f;
+  if (pstat) a_s = m1_abar_wave_load(pstat, n, S, tid & 63);
+  else a_s = abar[n];                        // (the finalize kernel's abar: in the same batch)
   const int lab = EVAL ? 0 : (int)labels[n];
   float btv[EPT], acc[EPT];
 #pragma unroll
@@ -97,6 +98,11 @@ __global__ __launch_bounds__(256) void m1_logits_xent_kernel(
     for (int e = 0; e < EPT; ++e)
 #pragma unroll
       for (int u = 0; u < 32; ++u) acc[e] += (c + u < nchunks) ? v[e][u] : 0.f;
+  }
+  float ab = a_s;
+  if (pstat) {
+    ab = m1_abar_wave_sum(a_s, P);
+    if (tid == 0) abar[n] = ab;
   }
 #pragma unroll
   for (int e = 0; e < EPT; ++e) {
@@ -587,9 +593,10 @@ typedef float f4u __attribute__((ext_vector_type(4), aligned(4)));
 template <int UG>   // 16-wide k groups (role 0) / k tiles (role 1) per wave: ceil(ceil(K/16)/4)
 __global__ __launch_bounds__(256) void m1_bwd_head_kernel(
     const float* __restrict__ G, const float* __restrict__ Wt, const float* __restrict__ zsave,
-    const float* __restrict__ abar, const float* __restrict__ bt, float* __restrict__ dz,
-    float* __restrict__ dWt, float* __restrict__ dbt, float* __restrict__ sn, int N, int C, int K,
-    int kpb, float* __restrict__ loss, float lscale) {
+    const float* __restrict__ abar, float* __restrict__ loss, int N, int C, int K, int kpb,
+    // ---- beyond the preload window (bt: read by the 32 sn waves only, behind their tile's loads) ----
+    const float* __restrict__ bt, float* __restrict__ dz, float* __restrict__ dWt, float* __restrict__ dbt,
+    float* __restrict__ sn, float lscale) {
   __shared__ float red[4 * 2 * 256];
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const int r = lane & 15, kq = lane >> 4;
@@ -757,8 +764,8 @@ __device__ __forceinline__ void raw_barrier_lds() {
 template <int UG>
 __global__ __launch_bounds__(256) void m1_bwd_head_tiles_kernel(
     const float* __restrict__ G, const float* __restrict__ Wt, const float* __restrict__ zsave,
-    const float* __restrict__ abar, const float* __restrict__ bt, float* __restrict__ dz,
-    float* __restrict__ dWt, float* __restrict__ dbt, float* __restrict__ sn, int N, int C, int K,
+    const float* __restrict__ abar, const float* __restrict__ bt, int N, int C, int K,
+    float* __restrict__ dz, float* __restrict__ dWt, float* __restrict__ dbt, float* __restrict__ sn,
     float* __restrict__ loss, float lscale) {
   __shared__ float red[4 * 2 * 256];
   __shared__ float sred[4][32];
@@ -974,8 +981,14 @@ __global__ __launch_bounds__(256) void m1_bwd_head_tiles_kernel(
 // grid = ceil(C/32) blocks of 1024 threads: 32 row groups x 32 columns, 128-byte row segments.
 // The last kernel of the backward call: optionally advances the HBM dropout counter.
 // --------------------------------------------------------------------------------------------
-// What is summed and where the sums go: ColsumArgs (apa_colsum.h).
-__global__ __launch_bounds__(1024) void m1_colsum_kernel(ColsumArgs a) { colsum_block(blockIdx.x, gridDim.x, a); }
+// What is summed and where the sums go: ColsumArgs (apa_colsum.h).  A struct passed by value is not preloaded, so the
+// fields the first batch of loads is addressed with travel in front of it as scalars (and the grid size, a hidden
+// argument otherwise); the descriptor's own copies of them are not read.
+__global__ __launch_bounds__(1024) void m1_colsum_kernel(const float* __restrict__ pdwa, int nblk, int C, int ld, int C1,
+                                                         int nbid, ColsumArgs a) {
+  a.pdwa = pdwa; a.nblk = nblk; a.C = C; a.ld = ld; a.C1 = C1;
+  colsum_block(blockIdx.x, nbid, a);
+}
 
 // ============================================================================================
 // host
@@ -1039,8 +1052,8 @@ int m1_logits2(float* z, const float* Wt, float* abar, const float* bt, float* l
                       : launch_logits2(z, Wt, part_ws, N, C, K, st);
   if (rc != APA_OK) return rc;
   hipLaunchKernelGGL(m1_logits_reduce_kernel, dim3((N * K + 255) / 256), dim3(256), 0, st, part_ws,
-                     abar, bt, logits, N, K, C / (64 * logits2_nsub(N, C)), fold ? fold->pstat : nullptr,
-                     fold ? fold->S : 0, fold ? fold->P : 1);
+                     fold ? fold->pstat : nullptr, bt, N, K, C / (64 * logits2_nsub(N, C)), fold ? fold->S : 0,
+                     fold ? fold->P : 1, abar, logits);
   APA_LAUNCH_CHECK("m1_logits_reduce_kernel");
   return APA_OK;
 }
@@ -1076,12 +1089,12 @@ int m1_logits2_xent(float* z, const float* Wt, float* abar, const float* bt,
   do {                                                                                               \
     if (probs)                                                                                       \
       hipLaunchKernelGGL((m1_logits_xent_kernel<NV4, true>), dim3(N), dim3(256), 0, st, part_ws,     \
-                         abar, bt, labels, logits, loss, G, probs, pred, N, K, nparts, gscale,       \
-                         pstat, fS, fP);                                                             \
+                         pstat, labels, bt, N, K, nparts, fS, fP, gscale, abar, logits, loss, G,     \
+                         probs, pred);                                                               \
     else                                                                                             \
       hipLaunchKernelGGL((m1_logits_xent_kernel<NV4, false>), dim3(N), dim3(256), 0, st, part_ws,    \
-                         abar, bt, labels, logits, loss, G, probs, pred, N, K, nparts, gscale,       \
-                         pstat, fS, fP);                                                             \
+                         pstat, labels, bt, N, K, nparts, fS, fP, gscale, abar, logits, loss, G,     \
+                         probs, pred);                                                               \
   } while (0)
   const int nv4 = K <= 128 ? 1 : (K <= 256 ? 2 : 4);
   if (M1Trace* t = m1_trace()) t->logits_nv4 = nv4;
@@ -1143,7 +1156,7 @@ int m1_bwd_head(const float* G, const float* Wt, const float* zsave, const float
     if (tr) { tr->head = M1_HEAD_TILES; tr->head_ug = ug <= 1 ? 1 : (ug <= 2 ? 2 : (ug <= 4 ? 4 : 7)); }
 #define APA_BHT(UG)                                                                                      \
   hipLaunchKernelGGL(m1_bwd_head_tiles_kernel<UG>, dim3(2 * nb), dim3(256), 0, st, G, Wt, zsave, abar, \
-                     bt, dz, dWt, dbt, sn, N, C, K, loss, lscale)
+                     bt, N, C, K, dz, dWt, dbt, sn, loss, lscale)
     if (ug <= 1) APA_BHT(1);
     else if (ug <= 2) APA_BHT(2);
     else if (ug <= 4) APA_BHT(4);
@@ -1155,7 +1168,7 @@ int m1_bwd_head(const float* G, const float* Wt, const float* zsave, const float
   if (tr) { tr->head = M1_HEAD_ROWS; tr->head_ug = ug <= 1 ? 1 : (ug <= 2 ? 2 : (ug <= 4 ? 4 : (ug <= 7 ? 7 : 13))); }
 #define APA_BH(UG)                                                                                \
   hipLaunchKernelGGL(m1_bwd_head_kernel<UG>, dim3(2 * nb), dim3(256), 0, st, G, Wt, zsave, abar, \
-                     bt, dz, dWt, dbt, sn, N, C, K, kpb, loss, lscale)
+                     loss, N, C, K, kpb, bt, dz, dWt, dbt, sn, lscale)
   if (ug <= 1) APA_BH(1);
   else if (ug <= 2) APA_BH(2);
   else if (ug <= 4) APA_BH(4);
@@ -1169,7 +1182,7 @@ int m1_bwd_head(const float* G, const float* Wt, const float* zsave, const float
 int m1_colsum(const ColsumArgs& args, hipStream_t st) {
   ColsumArgs a = args;
   const int nb = colsum_prepare(a);
-  hipLaunchKernelGGL(m1_colsum_kernel, dim3(nb), dim3(1024), 0, st, a);
+  hipLaunchKernelGGL(m1_colsum_kernel, dim3(nb), dim3(1024), 0, st, a.pdwa, a.nblk, a.C, a.ld, a.C1, nb, a);
   APA_LAUNCH_CHECK("m1_colsum_kernel");
   return APA_OK;
 }

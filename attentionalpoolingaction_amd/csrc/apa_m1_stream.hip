@@ -282,25 +282,31 @@ __device__ __forceinline__ void fwd_chunk(FwdState<T, VW, PIX, FUSED, TRAIN>& st
   }
 }
 
+// Parameter order (both kernels of this file): the objects of this file are built with kernarg preload, which hands a
+// wave the first 14 argument dwords in SGPRs at launch.  Everything the address of the first chunk's loads is made of
+// -- X, P, S and the grid size (xcd_remap: gridDim.x is a hidden argument at the far end of the block) -- and the
+// pointers of the loads that follow it lie in that window, so no scalar-memory wait stands in front of the first
+// global_load; the rest is fetched with s_load under the first chunk.  The dropout key (a dependent read of the
+// device counter) is formed behind the issue of the ring's first NB - 1 chunks: chunk 0's arithmetic is its first
+// use, behind an HBM wait that is longer.
 template <typename T, int VW, int PIX, bool FUSED, bool TRAIN, bool RIN = false>
 __global__ __launch_bounds__(256, 2) void m1s_pool_fwd_kernel(
-    const T* __restrict__ X, const float* __restrict__ Wa, const float* __restrict__ ba,
-    float* __restrict__ att, float* __restrict__ pacc, float* __restrict__ pstat, int P, int S,
-    int act, float inv_keep, uint32_t thresh, uint64_t seed, uint64_t offset,
+    const T* __restrict__ X, int P, int S, int nblk, int act, const float* __restrict__ Wa,
+    const float* __restrict__ ba, float* __restrict__ att, float* __restrict__ pacc,
+    // ---- beyond the preload window ----
+    float* __restrict__ pstat, float inv_keep, uint32_t thresh, uint64_t seed, uint64_t offset,
     const uint64_t* __restrict__ offset_dev, uint8_t* __restrict__ maskbits) {
   constexpr int EPV = Vec<T>::EPV;
   constexpr int EPL = VW * EPV;   // channels per lane
   constexpr int CW = EPL * 64;    // channels per wave
   constexpr int C = CW * 4;
   __shared__ __attribute__((aligned(16))) float sm_x[APA_M1S_NB][256];   // one exchange buffer per ring slot
-  uint32_t k0 = 0, k1 = 0;
-  if (TRAIN) rng_key_dev(seed, offset_dev ? *offset_dev : offset, k0, k1);
 
-  const int blk = xcd_remap(blockIdx.x, gridDim.x);
-  const int n = blk / S, s = blk % S;
+  const unsigned blk = (unsigned)xcd_remap(blockIdx.x, nblk);
+  const int n = (int)(blk / (unsigned)S), s = (int)(blk % (unsigned)S);
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int p_begin = (int)(((long)s * P) / S);
-  const int p_end = (int)(((long)(s + 1) * P) / S);
+  int p_begin, p_end;
+  m1_pix_range(s, P, S, p_begin, p_end);
   const int npt = p_end - p_begin;
   const int nchunk = (npt + PIX - 1) / PIX;
   const int cbase = wave * CW + lane * EPV;   // + j * 64 * EPV
@@ -338,6 +344,9 @@ __global__ __launch_bounds__(256, 2) void m1s_pool_fwd_kernel(
     }
     st.bias = ba[0];
   }
+  __builtin_amdgcn_sched_barrier(0);   // every load through the window's pointers is out: now the first scalar wait
+  uint32_t k0 = 0, k1 = 0;
+  if (TRAIN) rng_key_dev(seed, offset_dev ? *offset_dev : offset, k0, k1);
 
   // chunk k + NB - 1 is always fetched (clamped to the block's last pixel past the end: L1/L2 hits)
   for (int ch = 0; ch < nchunk; ch += NB) {
@@ -491,13 +500,14 @@ template <int BPL> __device__ __forceinline__ uint32_t ld_keep_bits(const uint8_
 
 template <typename T, int VW, int PIX, bool FUSED, bool TRAIN, bool RIN = false, bool BITS = false, bool NODX = false>
 __global__ __launch_bounds__(256, 2) void m1s_bwd_main_kernel(
-    const T* __restrict__ X, const float* __restrict__ Wa, const float* __restrict__ att,
-    const float* __restrict__ dz, const float* __restrict__ zsave, const float* __restrict__ abar,
+    const T* __restrict__ X, int P, int S, int nblk, int K, const float* __restrict__ att,
+    const float* __restrict__ dA_extra, const uint8_t* __restrict__ maskbits, const float* __restrict__ dz,
+    // ---- beyond the preload window ----
+    const float* __restrict__ Wa, const float* __restrict__ zsave, const float* __restrict__ abar,
     const float* __restrict__ G, const float* __restrict__ bt, const float* __restrict__ sn_pre,
     T* __restrict__ dX, float* __restrict__ dZout, float* __restrict__ pdwa,
-    float* __restrict__ pdba, int P, int S, int K, int act, float inv_keep, uint32_t thresh,
-    uint64_t seed, uint64_t offset, const uint64_t* __restrict__ offset_dev,
-    const float* __restrict__ dA_extra, float extra_scale, const uint8_t* __restrict__ maskbits) {
+    float* __restrict__ pdba, int act, float inv_keep, uint32_t thresh,
+    uint64_t seed, uint64_t offset, const uint64_t* __restrict__ offset_dev, float extra_scale) {
   // dA_extra [N,P]: per-pixel additive term of dA * P from the concatenated pose channels; callers
   // without them pass `att` and extra_scale = 0, so the load is unconditional (straight-line code)
   constexpr int EPV = Vec<T>::EPV;
@@ -506,14 +516,12 @@ __global__ __launch_bounds__(256, 2) void m1s_bwd_main_kernel(
   constexpr int C = CW * 4;
   __shared__ __attribute__((aligned(16))) float sm_x[APA_M1S_NB][256];
   __shared__ float sm_aux[4];
-  uint32_t k0 = 0, k1 = 0;
-  if (TRAIN) rng_key_dev(seed, offset_dev ? *offset_dev : offset, k0, k1);
 
-  const int blk = xcd_remap(blockIdx.x, gridDim.x);
-  const int n = blk / S, s = blk % S;
+  const unsigned blk = (unsigned)xcd_remap(blockIdx.x, nblk);
+  const int n = (int)(blk / (unsigned)S), s = (int)(blk % (unsigned)S);
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, l16 = lane & 15;
-  const int p_begin = (int)(((long)s * P) / S);
-  const int p_end = (int)(((long)(s + 1) * P) / S);
+  int p_begin, p_end;
+  m1_pix_range(s, P, S, p_begin, p_end);
   const int npt = p_end - p_begin;
   const int nchunk = (npt + PIX - 1) / PIX;
   const int cbase = wave * CW + lane * EPV;
@@ -552,6 +560,8 @@ __global__ __launch_bounds__(256, 2) void m1s_bwd_main_kernel(
   auto walk = [&](int i_) { return max(nchunk - 1 - i_, 0); };
 #pragma unroll
   for (int b = 0; b < NB - 1; ++b) fetch(b, walk(b));
+  uint32_t k0 = 0, k1 = 0;
+  if (TRAIN) rng_key_dev(seed, offset_dev ? *offset_dev : offset, k0, k1);
 
   // per-image constants: L2 hits issued behind the first chunk's HBM loads
   BwdState<T, VW, PIX, FUSED, TRAIN> st;
@@ -646,8 +656,8 @@ static int launch_fwd_t(const M1Call& c, const M1Fwd& io) {
   if (M1Trace* t = m1_trace()) { t->pool_fwd = M1_POOL_STREAM; t->fwd_w = VW; t->fwd_pix = PIX; }
   auto go = [&](auto F, auto TR, auto RIN) {
     launch_ev(m1s_pool_fwd_kernel<T, VW, PIX, decltype(F)::value, decltype(TR)::value, decltype(RIN)::value>,
-              dim3(c.pl.nblk), dim3(256), 0, c.st, c.ev0, c.ev1, static_cast<const T*>(io.X), io.Wa, io.ba, io.att,
-              c.pacc, c.pstat, c.P, c.pl.S, c.pool_act, c.inv_keep, c.key.thresh, c.key.seed, c.key.offset,
+              dim3(c.pl.nblk), dim3(256), 0, c.st, c.ev0, c.ev1, static_cast<const T*>(io.X), c.P, c.pl.S, c.pl.nblk,
+              c.pool_act, io.Wa, io.ba, io.att, c.pacc, c.pstat, c.inv_keep, c.key.thresh, c.key.seed, c.key.offset,
               c.key.offset_dev, c.maskbits);
     return APA_OK;
   };
@@ -671,9 +681,9 @@ static int launch_bwd_t(const M1Call& c, const M1Bwd& io) {
   auto go = [&](auto F, auto TR, auto RIN, auto BITS, auto NODX) {
     launch_ev(m1s_bwd_main_kernel<T, VW, PIX, decltype(F)::value, decltype(TR)::value, decltype(RIN)::value,
                                   decltype(BITS)::value, decltype(NODX)::value>,
-              dim3(c.pl.nblk), dim3(256), 0, c.st, c.ev0, c.ev1, static_cast<const T*>(io.X), io.Wa, io.att, c.dz,
-              io.zsave, io.abar, io.G, io.bt, c.sn, static_cast<T*>(io.dX), c.dzatt, c.pdwa, c.pdba, c.P, c.pl.S,
-              c.K, c.act, c.inv_keep, c.key.thresh, c.key.seed, c.key.offset, c.key.offset_dev, c.ex, c.exs, mbits);
+              dim3(c.pl.nblk), dim3(256), 0, c.st, c.ev0, c.ev1, static_cast<const T*>(io.X), c.P, c.pl.S, c.pl.nblk, c.K,
+              io.att, c.ex, mbits, c.dz, io.Wa, io.zsave, io.abar, io.G, io.bt, c.sn, static_cast<T*>(io.dX), c.dzatt,
+              c.pdwa, c.pdba, c.act, c.inv_keep, c.key.thresh, c.key.seed, c.key.offset, c.key.offset_dev, c.exs);
     return APA_OK;
   };
   const std::true_type yes; const std::false_type no;
