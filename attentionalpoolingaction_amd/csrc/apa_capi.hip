@@ -129,6 +129,16 @@ static int check_cat(const char* fn, const PoolCall& d, bool topdown, bool backw
   return APA_OK;
 }
 
+// APA_FLAG_FROZEN_INPUT on per-class maps: only the fused K <= 64 route has an arm without the dX product.  Asked by
+// the backward call and by the one-call steps BEFORE their forward half: nothing has been queued when it refuses.
+static int frozen_input_check(const char* fn, const PoolDims& d, unsigned flags, const void* X, const void* Xatt) {
+  if (!(flags & APA_FLAG_FROZEN_INPUT) || d.M == 1) return APA_OK;
+  if (pc_fused_supported(d.N, d.P, d.C, d.Ca, d.K, d.dtype, X, Xatt) && !rng_external(flags)) return APA_OK;
+  set_error("%s: APA_FLAG_FROZEN_INPUT is not served by the dense per-class route (K > 64, fp32 features, a separate "
+            "attention input or a replayed mask; K=%d dtype=%d): run without the flag", fn, d.K, d.dtype);
+  return APA_ERR_UNSUPPORTED;
+}
+
 // Every refusal of a pooling call above the paths' own (m1_call_fill), each written once.  f: the forward call's
 // tensors, or b: the backward call's (the other null).
 static int pool_check(const PoolCall& d, const M1Fwd* f, const M1Bwd* b) {
@@ -139,8 +149,8 @@ static int pool_check(const PoolCall& d, const M1Fwd* f, const M1Bwd* b) {
   int rc = check_common(fn, d);
   if (rc != APA_OK) return rc;
   if (f ? !X || !Xatt || !f->Wa || !f->ba || !f->Wt || !f->bt || !f->logits || !f->att
-        : !X || !Xatt || !b->Wa || !b->Wt || !b->bt || !b->att || !b->G || !b->dX || !b->dWa || !b->dba || !b->dWt ||
-              !b->dbt) {
+        : !X || !Xatt || !b->Wa || !b->Wt || !b->bt || !b->att || !b->G ||
+              (!b->dX && !(d.flags & APA_FLAG_FROZEN_INPUT)) || !b->dWa || !b->dba || !b->dWt || !b->dbt) {
     set_error("%s: null tensor pointer", fn);
     return APA_ERR_INVALID_ARG;
   }
@@ -163,6 +173,17 @@ static int pool_check(const PoolCall& d, const M1Fwd* f, const M1Bwd* b) {
     set_error("%s: APA_FLAG_RELU_INPUT is an M == 1 fast path without the TopDownAttention dump", fn);
     return APA_ERR_UNSUPPORTED;
   }
+  if ((d.flags & APA_FLAG_FROZEN_INPUT) && topdown) {
+    set_error("%s: APA_FLAG_FROZEN_INPUT together with the TopDownAttention dump is not served: run without the flag",
+              fn);
+    return APA_ERR_UNSUPPORTED;
+  }
+  if (b && (d.flags & APA_FLAG_FROZEN_INPUT) && d.cat) {
+    set_error("%s: APA_FLAG_FROZEN_INPUT is not served by the *_cat entry points (concatenated pose channels): run "
+              "without the flag", fn);
+    return APA_ERR_UNSUPPORTED;
+  }
+  if (b && (rc = frozen_input_check(fn, d, d.flags, X, Xatt)) != APA_OK) return rc;
   if (b && (d.flags & APA_FLAG_DXATT_RANK1) && d.M != 1) {
     set_error("%s: APA_FLAG_DXATT_RANK1 needs one bottom-up map (M == 1): with per-class maps the gradient w.r.t. "
               "Xatt has rank K", fn);
@@ -430,10 +451,15 @@ static int head_step_run(PoolCall d, const StepLoss& L, const M1Fwd& f, const M1
                          unsigned fwd_iflags = 0, unsigned bwd_iflags = 0) {
   d.ws_bytes = pool_bytes;
   const unsigned flags = d.flags;
+  int rc = APA_OK;
+  if ((flags & APA_FLAG_FROZEN_INPUT) && f.X && f.Xatt) {   // the backward half's refusal of the flag, before the forward half
+    if ((rc = check_common("apa_attn_head_train_step", d)) != APA_OK) return rc;
+    if ((rc = frozen_input_check("apa_attn_head_train_step", d, flags, f.X, f.Xatt)) != APA_OK) return rc;
+  }
   M1Xent xf;
   const bool fold = step_xent(L, d, &xf);
   d.flags = flags | fwd_iflags;
-  int rc = attn_pool_fwd(d, f, fold ? &xf : nullptr);
+  rc = attn_pool_fwd(d, f, fold ? &xf : nullptr);
   if (rc != APA_OK) return rc;
   if (!xf.done && (rc = step_loss_run(L, d, f.logits, pool_bytes)) != APA_OK) return rc;
   d.flags = flags | APA_FLAG_WS_FROM_FWD | bwd_iflags;
@@ -524,9 +550,10 @@ static int pose_attn_step(const char* fn, const apa_pose_attn_step_io* io, PoolC
   const apa_pose_attn_step_io& s = *io;
   if (!s.X || !s.W1 || !s.b1 || !s.W2 || !s.b2 || !s.Wa || !s.ba || !s.Wt || !s.bt || (!L.ml && !s.labels) ||
       !s.pose_labels || !s.pose_valid || !s.Ppre || !s.Pl || !s.att || !s.logits || !s.zsave || !s.abar ||
-      !s.loss_action || !s.loss_pose || !s.G || !s.dPl || !s.dZ || !s.dX || !s.dW1 || !s.db1 || !s.dW2 || !s.db2 ||
+      !s.loss_action || !s.loss_pose || !s.G || !s.dPl || !s.dZ || (!s.dX && !(d.flags & APA_FLAG_FROZEN_INPUT)) || !s.dW1 || !s.db1 || !s.dW2 || !s.db2 ||
       !s.dWa || !s.dba || !s.dWt || !s.dbt || !s.ws_pool || !s.ws_pose) {
-    set_error("%s: null pointer in apa_pose_attn_step_io (only W1_bf16 / W2T_bf16 may be NULL)", fn);
+    set_error("%s: null pointer in apa_pose_attn_step_io (only W1_bf16 / W2T_bf16 -- and dX under "
+              "APA_FLAG_FROZEN_INPUT -- may be NULL)", fn);
     return APA_ERR_INVALID_ARG;
   }
   // (on clips the shape is checked with the clip itself, in head_step_check below: a null clip is reported first)
@@ -549,12 +576,16 @@ static int pose_attn_step(const char* fn, const apa_pose_attn_step_io* io, PoolC
   const M1Fwd f{s.X, s.Ppre, s.Wa, s.ba, s.Wt, s.bt, s.logits, s.att, s.zsave, s.abar};
   const M1Bwd b{s.X, s.Ppre, s.Wa, s.Wt, s.bt, s.att, s.zsave, s.abar, s.G, s.dX, s.dZ, s.dWa, s.dba, s.dWt, s.dbt};
   const bool train = (d.flags & APA_FLAG_TRAIN) && d.keep_prob < 1.0f;
+  // APA_FLAG_FROZEN_INPUT: the pooling pass takes its arm without the dX stores (the flag rides in d.flags) and the
+  // pose head's dX product is not launched -- the pooling share its epilogue carries on the fast route goes with it
+  const bool frozen = (d.flags & APA_FLAG_FROZEN_INPUT) != 0;
   // the pose head's call on its own workspace, and its two halves: the external gradient of the backward half is
   // rank-1, dZ (x) Wa, added to the dX the pooling pass wrote, on the workspace the forward half prepared
   PoseCall pc = pose_call(fn, N, P, C, Cp, J, dtype, s.ws_pose, s.ws_pose_bytes, d.st);
   pc.ws_name = "pose workspace";
   const PoseFwd pf = {s.X, s.W1, s.b1, s.W2, s.b2, s.Ppre, s.Pl};
-  const PoseBwd pb = {s.X, s.W1, s.W2, s.Ppre, s.dPl, nullptr, s.dZ, s.Wa, s.dX, s.dW1, s.db1, s.dW2, s.db2, true, true};
+  const PoseBwd pb = {s.X, s.W1, s.W2, s.Ppre, s.dPl, nullptr, s.dZ, s.Wa, s.dX, s.dW1, s.db1, s.dW2, s.db2, true, true,
+                      frozen};
   const bool fast = !L.clips && !L.ml && pose_step_fast_ok(pc, pf, pb) && m1_supported(C, Cp, dtype, false) &&
                     m1_small_route_ok(C, K, s.G, s.Wt, s.zsave);
   if (!fast) {
@@ -567,7 +598,8 @@ static int pose_attn_step(const char* fn, const apa_pose_attn_step_io* io, PoolC
     d.flags |= APA_FLAG_DXATT_RANK1;   // s.dZ receives dZ itself; apa_pose_head_bwd_rank1ext re-forms dXatt from it
     rc = head_step_run(d, L, f, b, pool_bytes);
     if (rc != APA_OK) return rc;
-    return apa_pose_head_bwd_rank1ext(s.X, s.W1, s.W2, s.Ppre, s.dPl, s.dZ, s.Wa, s.dX, 1 | APA_POSE_WS_FROM_FWD,
+    return apa_pose_head_bwd_rank1ext(s.X, s.W1, s.W2, s.Ppre, s.dPl, s.dZ, s.Wa, s.dX,
+                                      1 | APA_POSE_WS_FROM_FWD | (frozen ? APA_POSE_NO_DX : 0),
                                       s.dW1, s.db1, s.dW2, s.db2, s.ws_pose, s.ws_pose_bytes, N, P, C, Cp, J, dtype,
                                       d.st);
   }
@@ -590,7 +622,7 @@ static int pose_attn_step(const char* fn, const apa_pose_attn_step_io* io, PoolC
   // ... and only if the dX product is certain to take the wide bf16 kernel (the one with the rank-1 epilogue): all-bf16
   // operands with 16-byte addressable rows -- dPpre and the W1 operand are the workspace's (aligned) or the shadow
   // checked above, dX is the caller's
-  const bool nodx = m1_no_dx_supported(C, dtype, train) && wide_rows > 0 && wide_rows <= 2 * P &&
+  const bool nodx = !frozen && m1_no_dx_supported(C, dtype, train) && wide_rows > 0 && wide_rows <= 2 * P &&
                     (reinterpret_cast<uintptr_t>(s.dX) & 15) == 0 && C % 8 == 0 && Cp % 8 == 0 &&
                     dtype == APA_DTYPE_BF16;
   // the pose head's Pl kernel left the attention in place; its backward rows pass takes dWa / dba and the RNG bump

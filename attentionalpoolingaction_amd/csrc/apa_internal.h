@@ -207,7 +207,7 @@ int gemm_bf16_mid_dropout(const void* A, long lda, const void* B, long ldb, void
 // Fused train step (apa_attn_head_train_step): softmax cross-entropy folded into the logits
 // reduction (forward sets `done` when it ran), batch-mean loss written by the backward head kernel.
 // Library-internal flag bits (never accepted from a caller: pool_call, apa_capi.hip, masks with APA_PUBLIC_FLAGS)
-constexpr unsigned APA_PUBLIC_FLAGS = 0x1FFu;
+constexpr unsigned APA_PUBLIC_FLAGS = 0x3FFu;
 constexpr unsigned APA_IFLAG_ATT_READY = 1u << 24;      // M == 1, Xatt != X: `att` already holds Z (id / relu applied)
 constexpr unsigned APA_IFLAG_NO_ATT_WGRAD = 1u << 25;   // M == 1 + DXATT_RANK1: dWa / dba / RNG bump done by the caller
 constexpr unsigned APA_IFLAG_NO_DX = 1u << 26;          // M == 1, Xatt != X: dX is NOT written -- the caller forms the
@@ -312,7 +312,7 @@ struct M1Call {
   int act, pool_act;       // M1Act; pool_act: what the pooling kernel applies (id when att is already final, Xatt != X)
   // fused: Xatt == X; train: dropout active; rank1 (APA_FLAG_DXATT_RANK1): the caller's dXatt buffer is fp32 [N*P] and
   // receives dZ itself; ext (APA_FLAG_RNG_EXTERNAL): the caller's keep bits are read by the run-time-loop kernels only;
-  // no_dx (APA_IFLAG_NO_DX): backward, Xatt != X, keep-bits form: skip the dX stores; small: the backward takes the
+  // no_dx (APA_FLAG_FROZEN_INPUT / APA_IFLAG_NO_DX): backward: no kernel stores through dX; small: the backward takes the
   // small-K route (m1_small_route_ok); gemv2: Ca is served by the register-resident attention GEMV backward
   bool fused, train, rank1, ext, relu_input, no_dx, small, gemv2;
   M1Pool pool; M1Plan pl;  // the pooling family of both streaming passes; the plan and what is carved from it:
@@ -330,7 +330,7 @@ int m1_call_fill(M1Call& c, const PoolCall& d, const M1Fwd* f, const M1Bwd* b, c
 int m1_forward(const M1Call& c, const M1Fwd& io, M1Xent* xf = nullptr);
 int m1_backward(const M1Call& c, const M1Bwd& io, const M1Xent* xf = nullptr);
 bool m1_supported(int C, int Ca, int dtype, bool fused);
-bool m1_no_dx_supported(int C, int dtype, bool train);   // can m1_backward honour APA_IFLAG_NO_DX for this shape?
+bool m1_no_dx_supported(int C, int dtype, bool train);   // APA_IFLAG_NO_DX: can the caller form the dX share from the keep bits?
 // the FUSED x TRAIN instances of a kernel template: go(std::bool_constant<FUSED>, std::bool_constant<TRAIN>)
 template <typename F> inline int m1_fused_train(bool fused, bool train, F&& go) {
   if (fused) return train ? go(std::true_type{}, std::true_type{}) : go(std::true_type{}, std::false_type{});
@@ -413,13 +413,15 @@ PoseCall pose_call(const char* fn, int N, int P, int C, int Cp, int J, int dtype
                    void* stream);
 // The caller's tensors of a forward / backward call (as M1Fwd / M1Bwd).  The external gradient of dPpre is a map
 // (dPpre_ext), rank-1 (ext_row (x) ext_col) or absent; accumulate: dX += dPpre . W1^T; ws_from_fwd: the workspace still
-// holds what the forward call on it left there (APA_POSE_WS_FROM_FWD).
+// holds what the forward call on it left there (APA_POSE_WS_FROM_FWD); no_dx (APA_POSE_NO_DX / APA_FLAG_FROZEN_INPUT): the
+// dX product is not launched and dX may be null.
 struct PoseFwd {
   const void* X; const float *W1, *b1, *W2, *b2; void* Ppre; float* Pl;
 };
 struct PoseBwd {
   const void* X; const float *W1, *W2; const void* Ppre; const float* dPl; const void* dPpre_ext;
   const float *ext_row, *ext_col; void* dX; float *dW1, *db1, *dW2, *db2; bool accumulate, ws_from_fwd;
+  bool no_dx = false;
 };
 // What the one-call cfg 003 steps add to the two bundles (apa_pose_attn_train_step; the evaluation step reads W1_bf16
 // and the attention conv only)

@@ -356,8 +356,9 @@ M1Plan m1_plan(int N, int P, int C, int Ca, int K) {
   return pl;
 }
 
-// APA_IFLAG_NO_DX is served by the keep-bits form of the streaming backward kernel: bf16 features in training mode
-// inside a one-call step (the forward half left the bits in the workspace)
+// Every backward kernel family has an arm without the dX stores (APA_FLAG_FROZEN_INPUT).  APA_IFLAG_NO_DX -- the
+// caller re-forms the pooling share of dX itself, from the keep bits -- additionally needs the keep-bits form of the
+// streaming kernel: bf16 features in training mode inside a one-call step (the forward half left the bits in the workspace)
 bool m1_no_dx_supported(int C, int dtype, bool train) {
   return train && dtype == APA_DTYPE_BF16 && m1s_supported(C, dtype);
 }
@@ -382,7 +383,7 @@ int m1_call_fill(M1Call& c, const PoolCall& d, const M1Fwd* f, const M1Bwd* b, c
   c.rank1 = b && (flags & APA_FLAG_DXATT_RANK1) != 0 && !c.fused;
   c.ext = c.train && rng_external(flags);
   c.relu_input = (flags & APA_FLAG_RELU_INPUT) != 0;
-  c.no_dx = b && (flags & APA_IFLAG_NO_DX) != 0;
+  c.no_dx = b && (flags & (APA_IFLAG_NO_DX | APA_FLAG_FROZEN_INPUT)) != 0;
   c.small = b && m1_small_route_ok(C, K, b->G, b->Wt, b->zsave);
   const int epv = dtype == APA_DTYPE_F32 ? 4 : 8;
   c.gemv2 = Ca % epv == 0 && Ca / epv <= 256;
@@ -421,7 +422,13 @@ int m1_call_fill(M1Call& c, const PoolCall& d, const M1Fwd* f, const M1Bwd* b, c
     set_error("attn_pool M=1: P=%d pixels per image in S=%d splits: (S + 1) * P does not fit 31 bits", P, c.pl.S);
     return APA_ERR_UNSUPPORTED;
   }
-  if (c.no_dx && (c.fused || !c.maskbits_in || !m1_no_dx_supported(C, dtype, c.train) || rng_external(flags) || cat)) {
+  if (c.no_dx && cat) {   // m1_cat_backward's share of dA is served, its kernels' dX side has no arm
+    set_error("attn_pool M=1: APA_FLAG_FROZEN_INPUT is not served by the *_cat entry points (concatenated pose "
+              "channels): run without the flag");
+    return APA_ERR_UNSUPPORTED;
+  }
+  if (b && (flags & APA_IFLAG_NO_DX) &&
+      (c.fused || !c.maskbits_in || !m1_no_dx_supported(C, dtype, c.train) || rng_external(flags))) {
     set_error("attn_pool M=1: NO_DX needs a separate attention input, the forward half's keep bits and the bf16 "
               "streaming kernels (internal)");
     return APA_ERR_UNSUPPORTED;

@@ -111,7 +111,7 @@ __global__ __launch_bounds__(256) void m1g_pool_fwd_kernel(
   }
 }
 
-template <typename T, bool FUSED, bool TRAIN>
+template <typename T, bool FUSED, bool TRAIN, bool NODX>
 __global__ __launch_bounds__(256) void m1g_bwd_main_kernel(
     const T* __restrict__ X, const float* __restrict__ Wa, const float* __restrict__ att,
     const float* __restrict__ dz, const float* __restrict__ zsave, const float* __restrict__ abar,
@@ -148,7 +148,7 @@ __global__ __launch_bounds__(256) void m1g_bwd_main_kernel(
     corr = wave_sum(zdz) + sn * abar[n];
   }
   const T* xim = X + (size_t)n * P * C;
-  T* dxim = dX + (size_t)n * P * C;
+  T* dxim = NODX ? nullptr : dX + (size_t)n * P * C;
   float dba_acc = 0.f;
   for (int p = p_begin + wave; p < p_end; p += 4) {
     const T* xr = xim + (size_t)p * C;
@@ -175,9 +175,16 @@ __global__ __launch_bounds__(256) void m1g_bwd_main_kernel(
     else if (act == M1_ACT_RELU) dZ = a > 0.f ? dA : 0.f;
     else dZ = dA;
     const float ap = a * invP * (TRAIN ? inv_keep : 1.f);
-    for (int v = lane; v < nvec; v += 64) {
+    // NODX (APA_FLAG_FROZEN_INPUT): no second pass over the row but for the dwa accumulators of the fused form
+    for (int v = lane; v < (NODX && !FUSED ? 0 : nvec); v += 64) {
       float x[EPV], o[EPV];
       Vec<T>::unpack(ld16(xr + v * EPV), x);
+      if constexpr (NODX) {
+#pragma unroll
+        for (int e = 0; e < EPV; ++e)
+          if (FUSED) my[v * EPV + e] = fmaf(dZ, x[e], my[v * EPV + e]);
+        continue;
+      }
 #pragma unroll
       for (int e = 0; e < EPV; e += 2) {
         float m0 = 1.f, m1 = 1.f;
@@ -260,8 +267,8 @@ template <typename T>
 static int launch_bwd_t(const M1Call& c, const M1Bwd& io) {
   const size_t shm = (c.fused ? (size_t)4 * c.C * 4 : 0) + 64;
   if (M1Trace* t = m1_trace()) t->pool_bwd = M1_POOL_GENERIC;
-  int rc = m1_fused_train(c.fused, c.train, [&](auto F, auto TR) -> int {
-    auto kernel = m1g_bwd_main_kernel<T, decltype(F)::value, decltype(TR)::value>;
+  auto go = [&](auto F, auto TR, auto NODX) -> int {
+    auto kernel = m1g_bwd_main_kernel<T, decltype(F)::value, decltype(TR)::value, decltype(NODX)::value>;
     int rc = set_lds(kernel, shm);
     if (rc != APA_OK) return rc;
     launch_ev(kernel, dim3(c.pl.nblk), dim3(256), shm, c.st, c.ev0, c.ev1, static_cast<const T*>(io.X), io.Wa, io.att,
@@ -269,6 +276,9 @@ static int launch_bwd_t(const M1Call& c, const M1Bwd& io) {
               c.pl.S, c.C, c.K, c.act, c.inv_keep, c.key.thresh, c.key.seed, c.key.offset, c.key.offset_dev, c.ex,
               c.exs);
     return APA_OK;
+  };
+  int rc = m1_fused_train(c.fused, c.train, [&](auto F, auto TR) -> int {   // c.no_dx: the arm without the dX stores
+    return c.no_dx ? go(F, TR, std::true_type{}) : go(F, TR, std::false_type{});
   });
   if (rc != APA_OK) return rc;
   APA_LAUNCH_CHECK("m1g_bwd_main_kernel");

@@ -430,8 +430,10 @@ __device__ __forceinline__ void bwd_chunk(BwdState<T, VW, PIX, FUSED, TRAIN>& st
         if (TRAIN) {
           const uint32_t b = BITS ? ((kbits[i] >> c) & 3u)
                                   : rng_keep2_bits(ebase + j * 64 * EPV + e, k0, k1, thresh);
-          const int bit = i * EPL + c;
-          mb[bit >> 5] |= b << (bit & 31);
+          if constexpr (!NODX) {   // kept for the dX loop below only
+            const int bit = i * EPL + c;
+            mb[bit >> 5] |= b << (bit & 31);
+          }
           d0 = fmaf((b & 1u) ? x[e] : 0.f, st.dzr[c], d0);
           d1 = fmaf((b & 2u) ? x[e + 1] : 0.f, st.dzr[c + 1], d1);
         } else {
@@ -450,9 +452,11 @@ __device__ __forceinline__ void bwd_chunk(BwdState<T, VW, PIX, FUSED, TRAIN>& st
   else if (act == M1_ACT_RELU) dZl = a_l > 0.f ? dA : 0.f;
   else dZl = dA;
   if (!FUSED && wave == 0 && lane < np) dZout_im[q0 + lane] = dZl;
-  // NODX (separate attention input, fused cfg 003 step): the dX share A/P . dz . mask/keep is formed by the pose
-  // head's dX product in its epilogue; with Xatt != X the loop below does nothing else, so the pass is read-only
-  if constexpr (NODX) return;
+  // NODX: nothing is stored through dX (APA_FLAG_FROZEN_INPUT: nobody reads it; APA_IFLAG_NO_DX, fused cfg 003 step:
+  // the dX share A/P . dz . mask/keep is formed by the pose head's dX product in its epilogue).  With Xatt != X the
+  // loop below does nothing else; with Xatt == X it still accumulates dwa / dba from the chunk in registers, in the
+  // same order as the writing arm -- only o[], the packed mask words and the stores go away
+  if constexpr (NODX && !FUSED) return;
 
 #pragma unroll
   for (int i = 0; i < PIX; ++i) {
@@ -471,6 +475,10 @@ __device__ __forceinline__ void bwd_chunk(BwdState<T, VW, PIX, FUSED, TRAIN>& st
 #pragma unroll
       for (int e = 0; e < EPV; ++e) {
         const int c = j * EPV + e;
+        if constexpr (NODX) {   // (FUSED) the weight-gradient half of the arm below, nothing else
+          if constexpr (FUSED) st.dwa[c] = fmaf(dZa, RIN ? fmaxf(x[e], 0.f) : x[e], st.dwa[c]);
+          continue;
+        }
         float t = apk;
         if (TRAIN) {
           const int bit = i * EPL + c;
@@ -488,7 +496,7 @@ __device__ __forceinline__ void bwd_chunk(BwdState<T, VW, PIX, FUSED, TRAIN>& st
           o[e] = t * st.dzr[c];
         }
       }
-      st16_nt(dxim + (size_t)(q0 + src) * C + cbase + j * 64 * EPV, Vec<T>::pack(o));
+      if constexpr (!NODX) st16_nt(dxim + (size_t)(q0 + src) * C + cbase + j * 64 * EPV, Vec<T>::pack(o));
     }
   }
 }
@@ -528,7 +536,7 @@ __global__ __launch_bounds__(256, 2) void m1s_bwd_main_kernel(
   const float invP = 1.0f / (float)P;
 
   const T* xim = opaque_global(X + (size_t)n * P * C);
-  T* dxim = dX + (size_t)n * P * C;
+  T* dxim = NODX ? nullptr : dX + (size_t)n * P * C;   // NODX: dX may be NULL and is never dereferenced
   const float* att_im = opaque_global(att + (size_t)n * P);     // (prefetched with the chunk: keep the loads chained)
   float* dZout_im = FUSED ? nullptr : dZout + (size_t)n * P;
 
@@ -687,19 +695,20 @@ static int launch_bwd_t(const M1Call& c, const M1Bwd& io) {
     return APA_OK;
   };
   const std::true_type yes; const std::false_type no;
+  // every form has its arm without the dX stores (APA_FLAG_FROZEN_INPUT / APA_IFLAG_NO_DX): c.no_dx never reaches an
+  // instance that stores through dX
+  auto arm = [&](auto F, auto TR, auto RIN, auto BITS) { return c.no_dx ? go(F, TR, RIN, BITS, yes) : go(F, TR, RIN, BITS, no); };
   bool bits = false;   // the keep-bits variant: bf16 features
   if constexpr (KeepBits<T>::ON) bits = c.train && mbits;
   if (tr && !c.relu_input) tr->keep_bits = bits;
   if (c.relu_input) {   // instantiated for the fused map only
-    if (c.train) go(yes, yes, yes, no, no); else go(yes, no, yes, no, no);
+    if (c.train) arm(yes, yes, yes, no); else arm(yes, no, yes, no);
   } else if (bits) {
     if constexpr (KeepBits<T>::ON) {
-      if (c.no_dx) go(no, yes, no, yes, yes);   // ... without the dX stores (APA_IFLAG_NO_DX: Xatt != X)
-      else if (c.fused) go(yes, yes, no, yes, no);
-      else go(no, yes, no, yes, no);
+      if (c.fused) arm(yes, yes, no, yes); else arm(no, yes, no, yes);
     }
   } else {
-    m1_fused_train(c.fused, c.train, [&](auto F, auto TR) { return go(F, TR, no, no, no); });
+    m1_fused_train(c.fused, c.train, [&](auto F, auto TR) { return arm(F, TR, no, no); });
   }
   APA_LAUNCH_CHECK("m1s_bwd_main_kernel");
   return APA_OK;

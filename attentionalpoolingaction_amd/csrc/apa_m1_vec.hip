@@ -185,8 +185,10 @@ __global__ __launch_bounds__(256) void m1_pool_fwd_kernel(
 // --------------------------------------------------------------------------------------------
 // B3: backward streaming pass (the dominant kernel: reads X once, writes dX once).
 // grid = N*S blocks of 256 threads, same pixel ownership as F1.
+// NODX (APA_FLAG_FROZEN_INPUT): nothing is stored through dX (it may be NULL); dZout / pdwa / pdba are formed by the
+// same operations in the same order as in the writing arm.
 // --------------------------------------------------------------------------------------------
-template <typename T, int VEC, bool FUSED, bool TRAIN>
+template <typename T, int VEC, bool FUSED, bool TRAIN, bool NODX>
 __global__ __launch_bounds__(256) void m1_bwd_main_kernel(
     const T* __restrict__ X, const float* __restrict__ Wa, const float* __restrict__ att,
     const float* __restrict__ dz, const float* __restrict__ zsave, const float* __restrict__ abar,
@@ -214,7 +216,7 @@ __global__ __launch_bounds__(256) void m1_bwd_main_kernel(
   // the first pixel's HBM loads go out before anything else; the per-image constants below
   // (L2 hits) are fetched in their shadow
   const T* xim = X + (size_t)n * P * C;
-  T* dxim = dX + (size_t)n * P * C;
+  T* dxim = NODX ? nullptr : dX + (size_t)n * P * C;
   const float* att_im = att + (size_t)n * P;
   uint4 cur[VEC], nxt[VEC];
   int p = p_begin + wave;
@@ -308,21 +310,28 @@ __global__ __launch_bounds__(256) void m1_bwd_main_kernel(
     else if (act == M1_ACT_RELU) dZ = a > 0.f ? dA : 0.f;
     else dZ = dA;
 
-    const float ap = a * invP;
-    float o[EPL];
-#pragma unroll
-    for (int i = 0; i < EPL; ++i) {
-      const float t = TRAIN ? ap * mk[i] : ap;
+    if constexpr (NODX) {
       if (FUSED) {
-        o[i] = fmaf(t, dzr[i], dZ * wa[i]);
-        dwa[i] = fmaf(dZ, x[i], dwa[i]);
-      } else {
-        o[i] = t * dzr[i];
-      }
-    }
 #pragma unroll
-    for (int j = 0; j < VEC; ++j)
-      st16(dxim + (size_t)p * C + j * 64 * EPV + lane * EPV, Vec<T>::pack(o + j * EPV));
+        for (int i = 0; i < EPL; ++i) dwa[i] = fmaf(dZ, x[i], dwa[i]);
+      }
+    } else {
+      const float ap = a * invP;
+      float o[EPL];
+#pragma unroll
+      for (int i = 0; i < EPL; ++i) {
+        const float t = TRAIN ? ap * mk[i] : ap;
+        if (FUSED) {
+          o[i] = fmaf(t, dzr[i], dZ * wa[i]);
+          dwa[i] = fmaf(dZ, x[i], dwa[i]);
+        } else {
+          o[i] = t * dzr[i];
+        }
+      }
+#pragma unroll
+      for (int j = 0; j < VEC; ++j)
+        st16(dxim + (size_t)p * C + j * 64 * EPV + lane * EPV, Vec<T>::pack(o + j * EPV));
+    }
     if (FUSED) dba_acc += dZ;
     else if (lane == 0) dZout[(size_t)n * P + p] = dZ;
 #pragma unroll
@@ -385,12 +394,16 @@ static int launch_fwd_t(const M1Call& c, const M1Fwd& io) {
 template <typename T, int VEC>
 static int launch_bwd_t(const M1Call& c, const M1Bwd& io) {
   if (M1Trace* t = m1_trace()) { t->pool_bwd = M1_POOL_VEC; t->bwd_w = VEC; t->bwd_pix = 0; }
-  m1_fused_train(c.fused, c.train, [&](auto F, auto TR) {
-    launch_ev(m1_bwd_main_kernel<T, VEC, decltype(F)::value, decltype(TR)::value>, dim3(c.pl.nblk), dim3(256), 0,
+  auto go = [&](auto F, auto TR, auto NODX) {
+    launch_ev(m1_bwd_main_kernel<T, VEC, decltype(F)::value, decltype(TR)::value, decltype(NODX)::value>,
+              dim3(c.pl.nblk), dim3(256), 0,
               c.st, c.ev0, c.ev1, static_cast<const T*>(io.X), io.Wa, io.att, c.dz, io.zsave, io.abar, io.G, io.bt,
               c.sn, static_cast<T*>(io.dX), c.dzatt, c.pdwa, c.pdba, c.P, c.pl.S, c.K, c.act, c.inv_keep,
               c.key.thresh, c.key.seed, c.key.offset, c.key.offset_dev, c.ex, c.exs);
     return APA_OK;
+  };
+  m1_fused_train(c.fused, c.train, [&](auto F, auto TR) {   // c.no_dx: the arm without the dX stores
+    return c.no_dx ? go(F, TR, std::true_type{}) : go(F, TR, std::false_type{});
   });
   APA_LAUNCH_CHECK("m1_bwd_main_kernel");
   return APA_OK;

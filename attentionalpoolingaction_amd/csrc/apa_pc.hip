@@ -660,7 +660,9 @@ static int pc_backward_fused(const PcCall& c, const M1Bwd& io, hipStream_t st, c
   const int N = c.N, P = c.P, C = c.C, K = c.K, R = c.R;
   const void* const X = io.X;
   const float *const Wa = io.Wa, *const Wt = io.Wt, *const att = io.att, *const Tsave = io.zsave, *const G = io.G;
-  void* const dX = io.dX;
+  // APA_FLAG_FROZEN_INPUT: no launch below is handed the caller's dX
+  const bool frozen = (c.flags & APA_FLAG_FROZEN_INPUT) != 0;
+  void* const dX = frozen ? nullptr : io.dX;
   float *const dWa = io.dWa, *const dba = io.dba, *const dWt = io.dWt, *const dbt = io.dbt;
   PcTrace* tr = pc_trace();
   if (tr) tr->path_bwd = PC_PATH_FUSED;
@@ -691,7 +693,9 @@ static int pc_backward_fused(const PcCall& c, const M1Bwd& io, hipStream_t st, c
     if (tr) { tr->bwd_act = PC_ACT_BF16; tr->ps = ps; tr->ldg = 128; tr->dx = c.train ? PC_DX_MID_GEMM : PC_DX_PLAIN_GEMM; }
     // dX = (dT . Wt^T) * mask/keep + dZ . Wa^T: one launch over the concatenated k = 128.  (Round 5: BEFORE the dW
     // launches -- the reduce tail that ends them may overwrite the keep-bit map with the next step's.)
-    if (c.train) {
+    if (frozen) {   // the product's only output is dX: not launched
+      if (tr) tr->dx = PC_DX_NONE;
+    } else if (c.train) {
       rc = gemm_bf16_mid_dropout(f.dTdZ, 128, f.Wcat2, 128, dX, C, R, C, 128, 1.0f / c.keep_prob, f.maskbits, st);
     } else {
       GemmDesc g;
@@ -841,6 +845,10 @@ int pc_backward(const PoolCall& d, const M1Bwd& io, const M1Xent* xf) {
   if (PcTrace* tr = pc_trace()) tr->phase = 2;
   if (pc_fused_supported(d.N, d.P, d.C, d.Ca, d.K, d.dtype, io.X, io.Xatt) && !rng_external(d.flags))
     return pc_backward_fused(c, io, d.st, xf);
+  if (d.flags & APA_FLAG_FROZEN_INPUT) {   // (the entry points refuse this before their forward half: frozen_input_check)
+    set_error("per-class maps: APA_FLAG_FROZEN_INPUT is not served by the dense per-class route");
+    return APA_ERR_UNSUPPORTED;
+  }
   return pc_backward_generic(c, io, d.st, xf);
 }
 

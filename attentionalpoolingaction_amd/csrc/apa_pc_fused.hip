@@ -669,7 +669,10 @@ __device__ __forceinline__ float row16_sum(float v) {
 // low three bits spread the eight rows of each set and bit 3 tells the two sets apart.  (With (m & 7) alone both
 // sets land on the same eight slots: SQ_LDS_BANK_CONFLICT / SQ_LDS_IDX_ACTIVE = 0.47 on the first build.)
 __device__ __forceinline__ int dx_swz(int m) { return (m & 7) | ((((m + 4) >> 3) & 1) << 3); }
-template <bool TRAIN>
+// NODX (APA_FLAG_FROZEN_INPUT): everything but the product -- the kernel's other outputs have consumers ([dT | dZ]: the
+// dW kernel; the dbt | dba partial rows: its reduce tail; the deferred logits and cross-entropy) and are formed by the
+// same operations on channel range 0, the only one launched (upb = 0: no weight slab, no keep bits, no channel unit).
+template <bool TRAIN, bool NODX>
 __global__ __launch_bounds__(512) void pc_bwd_dx_kernel(PcDxArgs a) {
   extern __shared__ __attribute__((aligned(16))) short smem[];
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, l16 = lane & 15, kb = lane >> 4;
@@ -683,7 +686,7 @@ __global__ __launch_bounds__(512) void pc_bwd_dx_kernel(PcDxArgs a) {
 
   // 1. the weight slab: unit u = 32 channels x 128 k, image row j = 16 t + m <- channel c0 + 8 (m >> 2) + 4 t + (m & 3);
   //    one 1 KB DMA instruction per wave and unit
-  {
+  if constexpr (!NODX) {
     const uint32_t lbase = (uint32_t)(uintptr_t)smem;
     const int q = wave * 64 + lane, j = q >> 4, m = j & 15, t = j >> 4;
     const bf16_t* src = a.Wcat2 + (size_t)(cbeg + 8 * (m >> 2) + 4 * t + (m & 3)) * 128 + (((q & 15) ^ dx_swz(m)) * 8);
@@ -724,7 +727,7 @@ __global__ __launch_bounds__(512) void pc_bwd_dx_kernel(PcDxArgs a) {
   }
   // 4. keep bits of the block: [row][unit] dwords
   uint32_t mreg[4];
-  if (TRAIN) {
+  if (TRAIN && !NODX) {
 #pragma unroll
     for (int it = 0; it < 4; ++it) {
       const int i = tid + it * 512, row = i >> 4, d = i & 15;
@@ -755,7 +758,7 @@ __global__ __launch_bounds__(512) void pc_bwd_dx_kernel(PcDxArgs a) {
       grow[i] = k < K ? a.G[(size_t)(n_first + (i >> 6)) * K + k] * invP : 0.f;
     }
   }
-  if (TRAIN) {
+  if (TRAIN && !NODX) {
 #pragma unroll
     for (int it = 0; it < 4; ++it) {
       const int i = tid + it * 512;
@@ -839,15 +842,17 @@ __global__ __launch_bounds__(512) void pc_bwd_dx_kernel(PcDxArgs a) {
     // (non-temporal: dX is the step's output, nothing in this call reads it back -- 15.0 -> 13.8 us)
     if (valid) st16_nt(a.dX + (size_t)rowg * a.C + cbeg + 32 * u + 8 * kb, Vec<bf16_t>::pack(o));
   };
-  bf16x8 afA[2][4], afB[2][4];
-  uint32_t mbA, mbB;
-  load_u(0, afA, mbA);
-  for (int u = 0; u < nu; u += 2) {
-    load_u(min(u + 1, nu - 1), afB, mbB);
-    unit(u, afA, mbA);
-    if (u + 1 < nu) {
-      load_u(min(u + 2, nu - 1), afA, mbA);
-      unit(u + 1, afB, mbB);
+  if constexpr (!NODX) {
+    bf16x8 afA[2][4], afB[2][4];
+    uint32_t mbA, mbB;
+    load_u(0, afA, mbA);
+    for (int u = 0; u < nu; u += 2) {
+      load_u(min(u + 1, nu - 1), afB, mbB);
+      unit(u, afA, mbA);
+      if (u + 1 < nu) {
+        load_u(min(u + 2, nu - 1), afA, mbA);
+        unit(u + 1, afB, mbB);
+      }
     }
   }
   if (sp == 0) {     // the block's dbt | dba partial row: waves in fixed order
@@ -1064,23 +1069,28 @@ int pc_fused_dx(const PcFusedWs& f, const float* G, const float* att, const floa
   const int rbs = pc_fused_dx_rows(R);
   int splits;
   pc_dx_geometry(R, C, &a.upb, &splits);
+  const bool nodx = dX == nullptr;   // APA_FLAG_FROZEN_INPUT (pc_backward_fused): channel range 0 alone, without a slab
+  if (nodx) { a.upb = 0; splits = 1; }
   if (PcTrace* t = pc_trace()) {
-    t->dx = PC_DX_FUSED; t->bwd_act = PC_ACT_FOLDED; t->upb = a.upb; t->dx_splits = splits; t->rbs = rbs;
+    t->dx = nodx ? PC_DX_NONE : PC_DX_FUSED; t->bwd_act = PC_ACT_FOLDED; t->upb = a.upb; t->dx_splits = splits; t->rbs = rbs;
     if (defer) { t->logits = PC_LOGITS_DX; t->xent = PC_XENT_DX; }
   }
-#define APA_DX(TR)                                                                                              \
+#define APA_DX_ARM(TR, ND)                                                                                      \
   do {                                                                                                          \
     static thread_local PerDevice<bool> attr_dev; bool& attr_set = attr_dev.here();                             \
     if (!attr_set) {                                                                                            \
-      APA_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(pc_bwd_dx_kernel<TR>),                    \
+      APA_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(pc_bwd_dx_kernel<TR, ND>),                \
                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)DX_LDS_BYTES));        \
       attr_set = true;                                                                                          \
     }                                                                                                           \
-    hipLaunchKernelGGL((pc_bwd_dx_kernel<TR>), dim3(rbs, splits), dim3(512), (size_t)a.upb * 8192 + DX_LDS_REST, \
-                       st, a);                                                                                  \
+    hipLaunchKernelGGL((pc_bwd_dx_kernel<TR, ND>), dim3(rbs, splits), dim3(512),                                \
+                       (size_t)a.upb * 8192 + DX_LDS_REST, st, a);                                              \
   } while (0)
+  // (nodx: the arm of the same instance without the product and the dX stores)
+#define APA_DX(TR) do { if (nodx) APA_DX_ARM(TR, true); else APA_DX_ARM(TR, false); } while (0)
   if (train) APA_DX(true); else APA_DX(false);
 #undef APA_DX
+#undef APA_DX_ARM
   APA_LAUNCH_CHECK("pc_bwd_dx_kernel");
   return APA_OK;
 }

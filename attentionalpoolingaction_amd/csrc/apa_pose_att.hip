@@ -516,6 +516,10 @@ int pal_check(const char* fn, const void* X, const void* dX, const float* Pl, co
               "APA_FLAG_RELU_INPUT (M=%d C=%d K=%d flags=%u)", fn, PAL_MAXM, PAL_MAXK, M, C, K, flags);
     return APA_ERR_UNSUPPORTED;
   }
+  if (flags & APA_FLAG_FROZEN_INPUT) {   // the pose-heatmap attention head has no arm without the dX stores
+    set_error("%s: APA_FLAG_FROZEN_INPUT is not served by the pose-heatmap attention head: run without the flag", fn);
+    return APA_ERR_UNSUPPORTED;
+  }
   const uintptr_t align = dtype == APA_DTYPE_F32 ? 15 : 7;
   if (reinterpret_cast<uintptr_t>(X) & align) {
     set_error("%s: X must be %d-byte aligned", fn, (int)align + 1);

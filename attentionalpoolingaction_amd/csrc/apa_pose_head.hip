@@ -975,7 +975,8 @@ static int pose_dw1_splits(int C, int Cp, int R, int dtype) {
   return s;
 }
 
-// The tail of every backward route, the two dense products: dW1 = X^T . dPpre and dX (+)= dPpre . W1^T.
+// The tail of every backward route, the two dense products: dW1 = X^T . dPpre and dX (+)= dPpre . W1^T (b.no_dx: the
+// first alone -- the second's only output is dX, and the pooling share its epilogue may carry goes with it).
 // job: a column sum nothing behind it reads (the MFMA rows pass's) -- it rides on the tail blocks of dW1's split-K
 // reduce launch when there is one (round 6), else it is a launch of its own here; null: already launched.
 // x: the fused step's extras (the W1 shadow, the pooling's dX share), or null
@@ -1005,6 +1006,10 @@ static int pose_head_bwd_big(const PoseCall& c, const PoseBwd& b, const PoseStep
       if (rc != APA_OK) return rc;
       job->done = true;
     }
+  }
+  if (b.no_dx) {
+    if (tr) tr->dx_beta = 0;
+    return rc;
   }
   {  // dX (+)= dPpre . W1^T
     const PoseW1Op w1 = pose_w1_operand(c, b.W1, x ? x->W1_bf16 : nullptr, b.ws_from_fwd, &PoseTrace::w1_bwd);
@@ -1187,7 +1192,7 @@ static int pose_rows_dppre(const PoseCall& c, const PoseBwd& b) {
 // The backward pass: checks, route, arm, tail.  x: the fused step's extras, or null.  The three refusals under `x`
 // can fire from internal callers only (apa_pose_attn_train_step takes this route when pose_step_fast_ok holds)
 static int pose_head_bwd_impl(const PoseCall& c, const PoseBwd& b, const PoseStepArgs* x = nullptr) {
-  int rc = pose_check(c, b.X && b.W1 && b.W2 && b.Ppre && b.dX && b.dW1 && b.db1 && b.dW2 && b.db2, &b);
+  int rc = pose_check(c, b.X && b.W1 && b.W2 && b.Ppre && (b.dX || b.no_dx) && b.dW1 && b.db1 && b.dW2 && b.db2, &b);
   if (rc != APA_OK) return rc;
   const PoseRows rows = pose_rows_route(c, b);
   if (x && rows == POSE_ROWS_DPPRE) {
@@ -1306,7 +1311,7 @@ int pose_bwd_fused(const PoseCall& c, const PoseBwd& b, const PoseStepArgs& a) {
 
 }  // namespace apa
 
-// (the two bits of the public accumulate_dX are taken apart here and nowhere else)
+// (the three bits of the public accumulate_dX are taken apart here and nowhere else)
 extern "C" int apa_pose_head_bwd(const void* X, const float* W1, const float* W2, const void* Ppre,
                                  const float* dPl, const void* dPpre_ext, void* dX, int accumulate_dX,
                                  float* dW1, float* db1, float* dW2, float* db2, void* ws,
@@ -1314,7 +1319,8 @@ extern "C" int apa_pose_head_bwd(const void* X, const float* W1, const float* W2
                                  void* stream) {
   return pose_head_bwd_impl(pose_call("apa_pose_head_bwd", N, P, C, Cp, J, dtype, ws, ws_bytes, stream),
                             PoseBwd{X, W1, W2, Ppre, dPl, dPpre_ext, nullptr, nullptr, dX, dW1, db1, dW2, db2,
-                                    (accumulate_dX & 1) != 0, (accumulate_dX & APA_POSE_WS_FROM_FWD) != 0});
+                                    (accumulate_dX & 1) != 0, (accumulate_dX & APA_POSE_WS_FROM_FWD) != 0,
+                                    (accumulate_dX & APA_POSE_NO_DX) != 0});
 }
 
 // (everything behind its own check reports as apa_pose_head_bwd, whose second form it is)
@@ -1329,5 +1335,6 @@ extern "C" int apa_pose_head_bwd_rank1ext(const void* X, const float* W1, const 
   }
   return pose_head_bwd_impl(pose_call("apa_pose_head_bwd", N, P, C, Cp, J, dtype, ws, ws_bytes, stream),
                             PoseBwd{X, W1, W2, Ppre, dPl, nullptr, ext_row, ext_col, dX, dW1, db1, dW2, db2,
-                                    (accumulate_dX & 1) != 0, (accumulate_dX & APA_POSE_WS_FROM_FWD) != 0});
+                                    (accumulate_dX & 1) != 0, (accumulate_dX & APA_POSE_WS_FROM_FWD) != 0,
+                                    (accumulate_dX & APA_POSE_NO_DX) != 0});
 }

@@ -35,6 +35,10 @@ APA_FLAG_RELU_INPUT = 16  # X in memory is the pre-activation map: relu fused in
 APA_FLAG_DXATT_RANK1 = 32  # attn_pool_bwd returns dZ [N*P] instead of dXatt = dZ (x) Wa
 APA_FLAG_RNG_EXTERNAL = 128  # `seed` is the address of a caller-supplied, bit-packed dropout keep mask
 APA_FLAG_WEIGHT_IMAGES = 256  # per-class maps: the operand images in the workspace are kept current by the caller
+APA_FLAG_FROZEN_INPUT = 512  # the features are frozen: the backward half writes no dX (the pointer may be NULL)
+APA_POSE_WS_FROM_FWD = 2    # bits of apa_pose_head_bwd's accumulate_dX
+APA_POSE_NO_DX = 4
+APA_ERR_UNSUPPORTED = -2
 APA_WIMG_MAX = 12
 APA_WIMG_ROLES = {0: 'Wa', 1: 'ba', 2: 'Wt', 3: 'bt'}
 
@@ -350,11 +354,15 @@ def attn_pool_fwd(X, Xatt, Wa, ba, Wt, bt, *, flags=0, keep_prob=1.0, seed=0, of
 
 
 def attn_pool_bwd(X, Xatt, Wa, ba, Wt, bt, att, zsave, abar, G, *, flags=0, keep_prob=1.0, seed=0,
-                  offset=0, workspace=None, out=None, dxatt_rank1=False, hooks=None):
+                  offset=0, workspace=None, out=None, dxatt_rank1=False, hooks=None, want_dx=True):
     """dX, dXatt, dWa, dba, dWt, dbt = attn_pool_bwd(...).  `out` may supply preallocated
     (dX, dXatt, dWa, dba, dWt, dbt) buffers (e.g. views into a flat DP gradient bucket).
     `dxatt_rank1=True` (separate attention input, one bottom-up map): the second result is dZ, f32
-    [N*P], with dXatt = dZ (x) Wa left to the consumer (APA_FLAG_DXATT_RANK1)."""
+    [N*P], with dXatt = dZ (x) Wa left to the consumer (APA_FLAG_DXATT_RANK1).
+    `want_dx=False` (frozen features, APA_FLAG_FROZEN_INPUT): no gradient for X is computed or stored, the first
+    result is None and `out[0]` may be None; everything else is bit-identical.  Where the library refuses the flag
+    (APA_ERR_UNSUPPORTED: the dense per-class route) the call is repeated without it on a scratch dX -- the full
+    cost, the same results, still None for dX."""
     lib = load_library()
     N = X.shape[0]
     C = X.shape[-1]
@@ -367,8 +375,10 @@ def attn_pool_bwd(X, Xatt, Wa, ba, Wt, bt, att, zsave, abar, G, *, flags=0, keep
     fused = Xatt is X
     if dxatt_rank1 and not fused:
         flags |= APA_FLAG_DXATT_RANK1
+    if not want_dx:
+        flags |= APA_FLAG_FROZEN_INPUT
     if out is None:
-        dX = torch.empty_like(X)
+        dX = torch.empty_like(X) if want_dx else None
         if fused:
             dXatt = None
         elif dxatt_rank1:
@@ -386,16 +396,21 @@ def attn_pool_bwd(X, Xatt, Wa, ba, Wt, bt, att, zsave, abar, G, *, flags=0, keep
         workspace = torch.empty((max(need, 16),), dtype=torch.uint8, device=dev)
     xatt_ptr = _dev_ptr(X, 'X') if fused else _dev_ptr(Xatt, 'Xatt', X.dtype)
     seed, offset, flags = _rng_key(seed, offset, flags)
-    rc = lib.apa_attn_pool_bwd_ex(
-        _hooks_ptr(hooks), _dev_ptr(X, 'X'), xatt_ptr, _dev_ptr(Wa, 'Wa', torch.float32),
-        _dev_ptr(ba, 'ba', torch.float32), _dev_ptr(Wt, 'Wt', torch.float32),
-        _dev_ptr(bt, 'bt', torch.float32), _dev_ptr(att, 'att', torch.float32),
-        _dev_ptr(zsave, 'zsave'), _dev_ptr(abar, 'abar'), _dev_ptr(G, 'G', torch.float32),
-        _dev_ptr(dX, 'dX'), _dev_ptr(dXatt, 'dXatt'), _dev_ptr(dWa, 'dWa'), _dev_ptr(dba, 'dba'),
-        _dev_ptr(dWt, 'dWt'), _dev_ptr(dbt, 'dbt'), workspace.data_ptr(), workspace.numel(), N, P,
-        C, Ca, K, M, flags, float(keep_prob), int(seed), offset, dt, _stream_ptr())
+
+    def call(dx, fl):
+        return lib.apa_attn_pool_bwd_ex(
+            _hooks_ptr(hooks), _dev_ptr(X, 'X'), xatt_ptr, _dev_ptr(Wa, 'Wa', torch.float32),
+            _dev_ptr(ba, 'ba', torch.float32), _dev_ptr(Wt, 'Wt', torch.float32),
+            _dev_ptr(bt, 'bt', torch.float32), _dev_ptr(att, 'att', torch.float32),
+            _dev_ptr(zsave, 'zsave'), _dev_ptr(abar, 'abar'), _dev_ptr(G, 'G', torch.float32),
+            _dev_ptr(dx, 'dX'), _dev_ptr(dXatt, 'dXatt'), _dev_ptr(dWa, 'dWa'), _dev_ptr(dba, 'dba'),
+            _dev_ptr(dWt, 'dWt'), _dev_ptr(dbt, 'dbt'), workspace.data_ptr(), workspace.numel(), N, P,
+            C, Ca, K, M, fl, float(keep_prob), int(seed), offset, dt, _stream_ptr())
+    rc = call(dX, flags)
+    if rc == APA_ERR_UNSUPPORTED and not want_dx:      # a route without the arm: the full call, dX to scratch
+        rc = call(torch.empty_like(X), flags & ~APA_FLAG_FROZEN_INPUT)
     _check(rc, 'apa_attn_pool_bwd')
-    return dX, dXatt, dWa, dba, dWt, dbt
+    return (dX if want_dx else None), dXatt, dWa, dba, dWt, dbt
 
 
 class ApaConcatFeat(ctypes.Structure):
@@ -512,14 +527,15 @@ def pose_head_fwd(X, W1, b1, W2, b2, workspace=None, out=None):
 
 
 def pose_head_bwd(X, W1, W2, Ppre, dPl, dPpre_ext, *, dX=None, accumulate_dX=False, workspace=None, ws_from_fwd=False,
-                  ext_rank1=None):
+                  ext_rank1=None, want_dx=True):
     """dX, dW1, db1, dW2, db2 = pose_head_bwd(...).  dPl: pose-loss gradient [..,J] f32 or None;
     dPpre_ext: gradient from the attention branch [..,Cp] (dtype of X) or None.  With
     accumulate_dX the product dPpre.W1^T is ADDED to the given dX buffer.  `ext_rank1=(row, col)`:
     the attention-branch gradient in rank-1 form row [N*P] (x) col [Cp], both f32
     (apa_pose_head_bwd_rank1ext; dPpre_ext must then be None).  `ws_from_fwd=True`: `workspace` is
     the one pose_head_fwd returned and nothing has written to it since (APA_POSE_WS_FROM_FWD: the bf16
-    copy of W1 in it is reused)."""
+    copy of W1 in it is reused).  `want_dx=False` (frozen features, APA_POSE_NO_DX): the dX product is not launched,
+    `dX` is not touched and the first result is None."""
     lib = load_library()
     N, C = X.shape[0], X.shape[-1]
     P = X.numel() // (N * C)
@@ -530,8 +546,10 @@ def pose_head_bwd(X, W1, W2, Ppre, dPl, dPpre_ext, *, dX=None, accumulate_dX=Fal
         if ws_from_fwd:
             raise ApaError('ws_from_fwd needs the workspace of the forward call')
         workspace = torch.empty((max(need, 16),), dtype=torch.uint8, device=X.device)
-    acc_flag = (1 if accumulate_dX else 0) | (2 if ws_from_fwd else 0)
-    if dX is None:
+    acc_flag = (1 if accumulate_dX else 0) | (APA_POSE_WS_FROM_FWD if ws_from_fwd else 0)
+    if not want_dx:
+        acc_flag, dX = (acc_flag & ~1) | APA_POSE_NO_DX, None
+    elif dX is None:
         if accumulate_dX:
             raise ApaError('accumulate_dX needs an existing dX buffer')
         dX = torch.empty_like(X)
@@ -1133,6 +1151,10 @@ class HeadTrainStep:
         plain mean over the frames) and `temporal_grads = (dw [K], db [1])` its gradient buffers.  The step then also
         exposes `pooled [B,K]` (the clip logits) and `tatt [N]`; `logits` / `G` are the frame logits and their
         gradient, `loss` is [1+B].  With the defaults nothing changes.
+        `grads[0] = None` (frozen features): the step runs with APA_FLAG_FROZEN_INPUT and writes no dX; every other
+        output is bit-identical.  If the library refuses the flag for the route (APA_ERR_UNSUPPORTED: the dense
+        per-class route, K > 64 -- refused before anything is queued), the first run() allocates a scratch dX
+        (`self.dX_scratch`) and from then on runs the full step: the same results at the full cost, never a wrong one.
         `weight_images=True` (per-class maps, M == K): the padded / concatenated operand images of the weights
         are built ONCE in this step's workspace (`self.weight_image_maps` describes them) and every run() passes
         APA_FLAG_WEIGHT_IMAGES: the caller keeps them current -- `BoundMomentumSGD(..., images=...)` /
@@ -1154,6 +1176,10 @@ class HeadTrainStep:
                 raise ApaError('HeadTrainStep: dxatt_rank1 wants grads[1] = dZ, float32 [N*P]')
             flags |= APA_FLAG_DXATT_RANK1
         dX, dXatt, dWa, dba, dWt, dbt = grads
+        self.frozen_input = dX is None
+        self.dX_scratch = None
+        if self.frozen_input:
+            flags |= APA_FLAG_FROZEN_INPUT
         self.hooks = hooks            # default apa_hooks of run(); kept alive here
         clips = int(frames) != 1 or temporal is not None
         n_loss = N
@@ -1212,6 +1238,7 @@ class HeadTrainStep:
             flags, float(keep_prob), int(seed), off, _feat_dtype(X)]
         self._fn = self.lib.apa_attn_head_train_step_clips if clips else self.lib.apa_attn_head_train_step_ex
         self._name = 'apa_attn_head_train_step_clips' if clips else 'apa_attn_head_train_step'
+        self._dx_idx = 14 if self._ml is not None else 15
         if self._ml is not None:    # (ml, clip or NULL, hooks, then the same arguments without `labels`)
             self._pre = (ctypes.addressof(self._ml), ctypes.addressof(self._clip) if clips else None)
             self._fn, self._name = self.lib.apa_attn_head_train_step_multilabel, 'apa_attn_head_train_step_multilabel'
@@ -1255,6 +1282,12 @@ class HeadTrainStep:
         (an ApaHooks) overrides the instance's for this call."""
         h = self.hooks if hooks is None else hooks
         rc = self._fn(*self._pre, _hooks_ptr(h), *self._args, _stream_ptr() if stream is None else stream)
+        if rc == APA_ERR_UNSUPPORTED and self.frozen_input:     # no arm on this route: the full step, dX to scratch
+            self.frozen_input = False
+            self.dX_scratch = torch.empty_like(self._keep[0])
+            self._args[self._dx_idx] = self.dX_scratch.data_ptr()
+            self._args[-5] &= ~APA_FLAG_FROZEN_INPUT
+            rc = self._fn(*self._pre, _hooks_ptr(h), *self._args, _stream_ptr() if stream is None else stream)
         if rc != 0:
             _check(rc, self._name)
 
@@ -1291,10 +1324,17 @@ class PoseAttnTrainStep:
         `share_with`: another PoseAttnTrainStep of the same shapes whose activation / loss buffers and workspaces
         this step is bound to as well (see HeadTrainStep).  `w2t_bf16`: optional bf16 [16, Cp + 16] image of W2^T (rows
         J.. and the pad columns zero) the caller keeps current -- `pose_w2t_image(W2)` builds it, `pose_w2t_image_map(image, W2)` describes
-        it for `BoundMomentumSGD(..., images=...)`."""
+        it for `BoundMomentumSGD(..., images=...)`.
+        `grads[0] = None` (frozen features): APA_FLAG_FROZEN_INPUT -- the pooling pass stores no dX and the pose
+        head's dX product is not launched; every other output is bit-identical.  Should the library refuse the flag
+        (APA_ERR_UNSUPPORTED), run() allocates a scratch dX and runs the full step, as HeadTrainStep does."""
         self.lib = load_library()
         W1, b1, W2, b2, Wa, ba, Wt, bt = params
         dX, dW1, db1, dW2, db2, dWa, dba, dWt, dbt = grads
+        self.frozen_input = dX is None
+        self.dX_scratch = None
+        if self.frozen_input:
+            flags |= APA_FLAG_FROZEN_INPUT
         N, C = X.shape[0], X.shape[-1]
         P = X.numel() // (N * C)
         Cp, J, K = W1.shape[1], W2.shape[1], Wt.shape[1]
@@ -1412,6 +1452,12 @@ class PoseAttnTrainStep:
 
     def run(self, stream: Optional[int] = None) -> None:
         rc = self._fn(*self._pre, *self._args, _stream_ptr() if stream is None else stream)
+        if rc == APA_ERR_UNSUPPORTED and self.frozen_input:     # the full step, dX to scratch
+            self.frozen_input = False
+            self.dX_scratch = torch.empty_like(self._keep[0])
+            self._io.dX = self.dX_scratch.data_ptr()
+            self._args[7] &= ~APA_FLAG_FROZEN_INPUT
+            rc = self._fn(*self._pre, *self._args, _stream_ptr() if stream is None else stream)
         if rc != 0:
             _check(rc, self._name)
 

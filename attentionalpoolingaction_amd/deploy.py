@@ -47,6 +47,64 @@ class DeploymentConfig:
         return self.clone_index == 0
 
 
+def trainable_scopes(cfg) -> list:
+    """TRAIN.TRAINABLE_SCOPES as `_get_variables_to_train` reads it (src/train.py:172-175): '' -> [] (every trainable
+    variable), otherwise the comma-separated scopes, each stripped."""
+    s = cfg.TRAIN.TRAINABLE_SCOPES
+    return [scope.strip() for scope in s.split(',')] if s != '' else []
+
+
+def in_trainable_scopes(tf_name: str, scopes: Sequence[str]) -> bool:
+    """`tf.get_collection(TRAINABLE_VARIABLES, scope)` (src/train.py:178-180) is a PREFIX match on the variable name:
+    'PosePrelogitsBasedAttention/Conv' also takes 'PosePrelogitsBasedAttention/Conv2d_PrePose_Attn/weights'.  No
+    scopes: every variable."""
+    return not scopes or any(tf_name.startswith(s) for s in scopes)
+
+
+def _tf_trainable_variables(network_fn):
+    """[(TF name, Parameter)] of every trainable variable in creation order: the backbone's (its batch-norm moving
+    statistics are not trainable variables), the head's, 'TemporalAttention/Conv/*'."""
+    out = []
+    backbone = getattr(network_fn, 'backbone', None)
+    if backbone is not None and hasattr(backbone, 'tf_variable_map'):
+        for tfn, (mod, attr) in backbone.tf_variable_map().items():
+            p = getattr(mod, attr)
+            if isinstance(p, torch.nn.Parameter):
+                out.append((tfn, p))
+    head = network_fn.head
+    named = dict(head.named_parameters())
+    out += [(tfn, named[attr]) for attr, tfn in head.tf_variable_names().items() if attr in named]
+    temporal = getattr(network_fn, 'temporal', None)
+    if temporal is not None:
+        out += [('TemporalAttention/Conv/weights', temporal['weights']),
+                ('TemporalAttention/Conv/biases', temporal['biases'])]
+    return out
+
+
+def variables_to_train(network_fn, cfg) -> list:
+    """_get_variables_to_train (src/train.py:166-181): the ordered TF names of the variables the optimiser trains --
+    every trainable variable when TRAIN.TRAINABLE_SCOPES is empty, else scope by scope (in the order listed) the
+    variables whose name starts with the scope, in creation order; a variable two scopes reach is listed once."""
+    names = [tfn for tfn, _ in _tf_trainable_variables(network_fn)]
+    scopes = trainable_scopes(cfg)
+    if not scopes:
+        return names
+    return list(dict.fromkeys(n for s in scopes for n in names if n.startswith(s)))
+
+
+def apply_trainable_scopes(network_fn, cfg) -> list:
+    """`requires_grad_(False)` on every parameter outside `variables_to_train` (backbone included) -> that list.  The
+    reference hands the list to `optimize_clones(var_list=...)` (src/train.py:504-513): a variable outside it has no
+    gradient, no L2 step and no optimiser slot.  With a scope list that reaches no backbone variable the conv5 map
+    then needs no gradient either."""
+    trained = variables_to_train(network_fn, cfg)
+    keep = set(trained)
+    for tfn, p in _tf_trainable_variables(network_fn):
+        if tfn not in keep:
+            p.requires_grad_(False)
+    return trained
+
+
 class GradientBucket:
     """One flat fp32 buffer holding every head gradient; `views[name]` are the per-parameter
     windows the HIP kernels (or autograd) write into."""
@@ -482,9 +540,13 @@ class _FusedOptimizer:
 
     def __init__(self, params: Dict[str, torch.Tensor], bucket: GradientBucket, lr: float, weight_decay: float = 0.0,
                  regularized: Sequence[str] = (), bf16_shadows: Optional[Dict[str, torch.Tensor]] = None,
-                 stale: str = 'raise'):
+                 stale: str = 'raise', trainable: Optional[Sequence[str]] = None):
         """`bf16_shadows` {name: bf16 tensor}: operand copies the bf16 MFMA products read (the pose head's W1 for
-        `cof.PoseAttnTrainStep(w1_bf16=...)`), rewritten from the updated weights by the update's own launch."""
+        `cof.PoseAttnTrainStep(w1_bf16=...)`), rewritten from the updated weights by the update's own launch.
+        `trainable` (TRAIN.TRAINABLE_SCOPES, configure_optimizer): the bucket names the optimiser trains, default
+        all.  A segment outside it is FROZEN: never written, never decayed, no slot (`slot_names()`), whatever its
+        gradient window holds.  CPU buckets only -- on a GPU build the bucket over the trained variables
+        (FusedHeadStep does), so the fused launch walks nothing it must not touch."""
         if stale not in ('raise', 'refresh'):
             raise ValueError("stale: 'raise' or 'refresh'")
         self.stale = stale
@@ -492,7 +554,11 @@ class _FusedOptimizer:
         self.bucket = bucket
         self.lr = lr
         reg = set(regularized)
-        self.wd = [weight_decay if n in reg else 0.0 for n in bucket.names]
+        self.frozen = frozenset(bucket.names) - frozenset(bucket.names if trainable is None else trainable)
+        if self.frozen and bucket.flat.is_cuda:
+            raise ValueError('frozen variables %s in a GPU bucket: build the bucket over the trained variables '
+                             '(deploy.variables_to_train)' % ', '.join(sorted(self.frozen)))
+        self.wd = [weight_decay if (n in reg and n not in self.frozen) else 0.0 for n in bucket.names]
         self.acc = torch.zeros_like(bucket.flat)
         self._copies = []           # [OperandCopy]
         self._watched = ()          # the names that have copies
@@ -520,9 +586,10 @@ class _FusedOptimizer:
         (or anything with `.weight_image_maps` and `.refresh_weight_images()`), `names` maps the roles 'Wa' / 'ba' /
         'Wt' / 'bt' to parameter names of the bucket.  Several steps (micro-batch lanes, rotating buffer sets) may be
         attached; at most three images per parameter fit the fused launch, further ones (and every image of an
-        optimiser whose launch carries none) are rebuilt by their step's own refresh launch after the update.  The
+        optimiser whose launch carries none) are rebuilt by their step's own refresh launch after the update.  A role
+        missing from `names` (a variable frozen by TRAIN.TRAINABLE_SCOPES) keeps the image its step built.  The
         optimiser keeps `step` (hence its workspace) alive until `detach_weight_images(step)`."""
-        maps = [(names[role], m) for role, m in step.weight_image_maps]
+        maps = [(names[role], m) for role, m in step.weight_image_maps if role in names]
         count = collections.Counter(c.name for c in self._copies if c.kind == LAUNCH_IMAGE)
         count.update(n for n, _ in maps)
         kind = LAUNCH_IMAGE if self.fused_images and all(count[n] <= 3 for n, _ in maps) else OWNER_IMAGE
@@ -613,13 +680,20 @@ class _FusedOptimizer:
         return ([p[n].data_ptr() for n in self.bucket.names], self.bucket.flat.data_ptr(),
                 [s.data_ptr() for s in self._slots()], tuple(self.wd))
 
+    def slot_names(self):
+        """the bucket names that have optimiser slots: every one but the frozen"""
+        return [n for n in self.bucket.names if n not in self.frozen]
+
     def _segments(self, grad_scale):
-        """CPU: (w, g, *slot views) per bucket segment, g with the L2 term folded in"""
+        """CPU: (w, g, *slot views) per TRAINED bucket segment, g with the L2 term folded in"""
         o = 0
         slots = self._slots()
         for name, wd in zip(self.bucket.names, self.wd):
             w = self.params[name].data
             n = w.numel()
+            if name in self.frozen:
+                o += n
+                continue
             g = self.bucket.flat[o:o + n].view_as(w) * grad_scale + wd * w
             yield (w, g) + tuple(s[o:o + n].view_as(w) for s in slots)
             o += n
@@ -662,8 +736,9 @@ class MomentumSGD(_FusedOptimizer):
 
     def __init__(self, params: Dict[str, torch.Tensor], bucket: GradientBucket, lr: float,
                  momentum: float = 0.9, weight_decay: float = 0.0, regularized: Sequence[str] = (),
-                 bf16_shadows: Optional[Dict[str, torch.Tensor]] = None, stale: str = 'raise'):
-        super().__init__(params, bucket, lr, weight_decay, regularized, bf16_shadows, stale)
+                 bf16_shadows: Optional[Dict[str, torch.Tensor]] = None, stale: str = 'raise',
+                 trainable: Optional[Sequence[str]] = None):
+        super().__init__(params, bucket, lr, weight_decay, regularized, bf16_shadows, stale, trainable)
         self.momentum = momentum
 
     def _bind(self, ws, wd, sh, images):
@@ -687,8 +762,8 @@ class Adam(_FusedOptimizer):
     the torch expressions on CPU tensors.  `acc` is m, `slot2` is v."""
 
     def __init__(self, params, bucket, lr, beta1=0.9, beta2=0.999, epsilon=1e-8, weight_decay=0.0, regularized=(),
-                 bf16_shadows=None, stale='raise'):
-        super().__init__(params, bucket, lr, weight_decay, regularized, bf16_shadows, stale)
+                 bf16_shadows=None, stale='raise', trainable=None):
+        super().__init__(params, bucket, lr, weight_decay, regularized, bf16_shadows, stale, trainable)
         self.slot2 = torch.zeros_like(bucket.flat)
         self.beta1, self.beta2, self.epsilon, self.t = float(beta1), float(beta2), float(epsilon), 0
 
@@ -718,8 +793,8 @@ class RMSProp(_FusedOptimizer):
     ONE.  One fused HIP launch (`apa_rmsprop_step`, no image maps) on a GPU.  `acc` is ms, `slot2` is mom."""
 
     def __init__(self, params, bucket, lr, decay=0.9, momentum=0.0, epsilon=1e-10, weight_decay=0.0, regularized=(),
-                 bf16_shadows=None, stale='raise'):
-        super().__init__(params, bucket, lr, weight_decay, regularized, bf16_shadows, stale)
+                 bf16_shadows=None, stale='raise', trainable=None):
+        super().__init__(params, bucket, lr, weight_decay, regularized, bf16_shadows, stale, trainable)
         self.slot2 = torch.zeros_like(bucket.flat)
         self.decay, self.momentum, self.epsilon = float(decay), float(momentum), float(epsilon)
         self.acc.fill_(1.0)                                  # rmsprop.py _create_slots: init_rms = ones
@@ -780,7 +855,7 @@ def configure_learning_rate(cfg, num_samples_per_epoch: int, num_clones: int, gl
 
 def configure_optimizer(cfg, params: Dict[str, torch.Tensor], bucket: GradientBucket, learning_rate: float,
                         regularized: Sequence[str] = (), bf16_shadows: Optional[Dict[str, torch.Tensor]] = None,
-                        stale: str = 'raise'):
+                        stale: str = 'raise', tf_names: Optional[Dict[str, str]] = None):
     """_configure_optimizer (src/train.py:72-105): every optimiser the reference can select, each as ONE fused
     launch -- 'momentum' (cfgs 001-003: MomentumOptimizer(lr, TRAIN.MOMENTUM)), 'sgd' (momentum 0), 'adam'
     (TRAIN.ADAM_BETA1 / ADAM_BETA2 / OPT_EPSILON) and 'rmsprop' (TRAIN.RMSPROP_DECAY / MOMENTUM / OPT_EPSILON).  The
@@ -788,25 +863,31 @@ def configure_optimizer(cfg, params: Dict[str, torch.Tensor], bucket: GradientBu
     reference, 'rmsprop' reads cfg.TRAIN.RMSPROP_DECAY, a key src/config.py does not define: without it in the
     YAML the reference fails with an AttributeError at this point, and so does this function.
     With TRAIN.CLIP_GRADIENTS > 0 the L2 term is NOT folded in: the GradientClipper adds it on the chief clone, inside
-    the clip (model_deploy.py:294-304), and the optimiser refuses a `grad_scale` other than 1 in `step`."""
-    opt = _configure_optimizer(cfg, params, bucket, learning_rate, regularized, bf16_shadows, stale)
+    the clip (model_deploy.py:294-304), and the optimiser refuses a `grad_scale` other than 1 in `step`.
+    TRAIN.TRAINABLE_SCOPES (src/train.py:166-181, handed to optimize_clones(var_list=...)): a bucket segment whose TF
+    variable name -- `tf_names[name]`, default the bucket name itself -- starts with none of the scopes is frozen:
+    no update, no L2 step, no slot (_FusedOptimizer: `trainable`)."""
+    scopes = trainable_scopes(cfg)
+    tfn = tf_names or {}
+    trainable = [n for n in bucket.names if in_trainable_scopes(tfn.get(n, n), scopes)] if scopes else None
+    opt = _configure_optimizer(cfg, params, bucket, learning_rate, regularized, bf16_shadows, stale, trainable)
     opt.clipping = float(cfg.TRAIN.CLIP_GRADIENTS) > 0.0
     return opt
 
 
-def _configure_optimizer(cfg, params, bucket, learning_rate, regularized, bf16_shadows, stale):
+def _configure_optimizer(cfg, params, bucket, learning_rate, regularized, bf16_shadows, stale, trainable=None):
     kind = cfg.TRAIN.OPTIMIZER
     wd = 0.0 if float(cfg.TRAIN.CLIP_GRADIENTS) > 0.0 else float(cfg.TRAIN.WEIGHT_DECAY)
     if kind == 'adam':
         return Adam(params, bucket, lr=learning_rate, beta1=float(cfg.TRAIN.ADAM_BETA1),
                     beta2=float(cfg.TRAIN.ADAM_BETA2), epsilon=float(cfg.TRAIN.OPT_EPSILON), weight_decay=wd,
-                    regularized=regularized, bf16_shadows=bf16_shadows, stale=stale)
+                    regularized=regularized, bf16_shadows=bf16_shadows, stale=stale, trainable=trainable)
     if kind == 'rmsprop':
         if 'RMSPROP_DECAY' not in cfg.TRAIN:
             raise AttributeError('RMSPROP_DECAY')            # src/train.py:98 on the reference's own config table
         return RMSProp(params, bucket, lr=learning_rate, decay=float(cfg.TRAIN.RMSPROP_DECAY),
                        momentum=float(cfg.TRAIN.MOMENTUM), epsilon=float(cfg.TRAIN.OPT_EPSILON), weight_decay=wd,
-                       regularized=regularized, bf16_shadows=bf16_shadows, stale=stale)
+                       regularized=regularized, bf16_shadows=bf16_shadows, stale=stale, trainable=trainable)
     if kind == 'momentum':
         momentum = float(cfg.TRAIN.MOMENTUM)
     elif kind == 'sgd':
@@ -815,7 +896,7 @@ def _configure_optimizer(cfg, params, bucket, learning_rate, regularized, bf16_s
         raise ValueError('Optimizer [%s] was not recognized' % kind)
     return MomentumSGD(params, bucket, lr=learning_rate, momentum=momentum,
                        weight_decay=wd, regularized=regularized, bf16_shadows=bf16_shadows,
-                       stale=stale)
+                       stale=stale, trainable=trainable)
 
 
 class _FusedHeadFunction(torch.autograd.Function):
@@ -886,6 +967,18 @@ class FusedHeadStep:
     * `assume_unit_upstream=True`: the caller promises `total` enters the differentiated scalar with coefficient 1
       (`(total + other).backward()`), which saves one pass over the [N,H,W,C] gradient; the default multiplies by
       whatever arrives -- conv5's gradient and the bucket alike, with or without a differentiated backbone.
+    * TRAIN.TRAINABLE_SCOPES (src/train.py:166-181): `trained` / `frozen` split the head's variables by the prefix
+      rule of `variables_to_train`.  The bucket, the optimiser's parameter set and slots, the L2 term and the clipper
+      cover the trained ones only; a frozen variable's gradient -- still computed, its products share launches with
+      the others -- goes to private scratch, the variable is never written or decayed, and the bf16 W1 shadow, the
+      W2^T image and the per-class images of a frozen variable are built once (`make_optimizer`) and only rebuilt by
+      the staleness guard / `refresh_operands()`.  `deploy.apply_trainable_scopes(network_fn, cfg)` freezes the
+      parameters themselves, backbone included.
+    * frozen features (`frozen_features=True`; the default when TRAIN.TRAINABLE_SCOPES is set): a step whose conv5 map
+      does not require grad (precomputed features, or no backbone variable in the scopes) is bound without a
+      conv5-gradient buffer and runs with APA_FLAG_FROZEN_INPUT: no dX is computed or stored; losses, end points
+      and the bucket are bit-identical to the full step.  Without scopes and without the argument every step fills
+      its conv5-gradient buffer (`_dX`), whether or not autograd asks for it.
     * one bound step (outputs, workspace, conv5-gradient buffer) is kept per batch shape / dtype (`max_bound_steps`
       most recent: a smaller last batch of an epoch comes back every epoch).  Only the step that is about to run
       has its operand images attached to the optimiser's launch; switching detaches the previous one (the launch
@@ -897,7 +990,7 @@ class FusedHeadStep:
     max_bound_steps = 4
 
     def __init__(self, network_fn, cfg, loss_scale: float = 1.0, assume_unit_upstream: bool = False,
-                 stale: str = 'raise'):
+                 stale: str = 'raise', frozen_features: Optional[bool] = None):
         from . import nets_factory
         head = network_fn.head
         if not isinstance(head, nets_factory.AttentionalPoolingHead):
@@ -909,23 +1002,46 @@ class FusedHeadStep:
         self.loss_scale = float(loss_scale)
         self.assume_unit_upstream = bool(assume_unit_upstream)
         self.stale = stale
+        # may a step whose conv5 map needs no gradient skip dX?  Default: when the configuration declares frozen
+        # training (TRAIN.TRAINABLE_SCOPES is set); without it a head-only step keeps filling `_dX`, as it always has
+        self.frozen_features = bool(trainable_scopes(cfg)) if frozen_features is None else bool(frozen_features)
         self.pose_form = not head.single_layer
         names = ['pose_w1', 'pose_b1', 'pose_w2', 'pose_b2', 'att_weights', 'att_biases', 'td_weights', 'td_biases']
         self.params = {n: getattr(head, n) for n in names}
         # cfg 002 forms: the PoseLogits convs are pruned from the data path -- no gradient, but their weights are
         # regularised and decay (the optimiser's L2 term on a zero gradient), as in the reference (tf.gradients
         # reaches them through REGULARIZATION_LOSSES only)
-        self._written = names if self.pose_form else names[4:]
+        written = names if self.pose_form else names[4:]
         reg = {id(w) for w in head.regularized_weights()}
+        self.tf_names = {n: head.tf_variable_names()[n] for n in names}
         self.temporal = getattr(network_fn, 'temporal', None)
         if self.temporal is not None:       # 'TemporalAttention/Conv/{weights,biases}' (nets_factory.py:362-370)
             self.params['temporal_weights'] = self.temporal['weights']
             self.params['temporal_biases'] = self.temporal['biases']
             names = names + ['temporal_weights', 'temporal_biases']
-            self._written = self._written + ['temporal_weights', 'temporal_biases']
+            written = written + ['temporal_weights', 'temporal_biases']
             reg.add(id(self.temporal['weights']))                # regularised like every conv weight; the bias is not
-        self.bucket = GradientBucket.for_parameters(self.params.items())
-        self.regularized = [n for n in names if id(self.params[n]) in reg]
+            self.tf_names.update(temporal_weights='TemporalAttention/Conv/weights',
+                                 temporal_biases='TemporalAttention/Conv/biases')
+        # TRAIN.TRAINABLE_SCOPES (src/train.py:166-181): the bucket -- hence the all-reduce, the optimiser's parameter
+        # set, its slots, the L2 term and the clipper -- covers the trained variables only.  The step still computes
+        # a frozen variable's gradient (its products are part of the shared launches) into a private scratch tensor
+        scopes = trainable_scopes(cfg)
+        self.trained = [n for n in names if in_trainable_scopes(self.tf_names[n], scopes)]
+        self.frozen = [n for n in names if n not in self.trained]
+        if not self.trained:
+            raise ValueError('FusedHeadStep: TRAIN.TRAINABLE_SCOPES %r reaches no head variable'
+                             % cfg.TRAIN.TRAINABLE_SCOPES)
+        self.bucket = GradientBucket.for_parameters((n, self.params[n]) for n in self.trained)
+        self._grad_out = dict(self.bucket.views)
+        for n in self.frozen:
+            if n in written:
+                self._grad_out[n] = torch.empty_like(self.params[n].data, dtype=self.bucket.flat.dtype)
+        self._written = [n for n in written if n in self.trained]
+        self._absent = [n for n in self.trained if n not in written]
+        self.regularized = [n for n in self.trained if id(self.params[n]) in reg]
+        self._frozen_copies = []         # [(name, refresh)]: operand copies of frozen variables, built once
+        self._frozen_seen = {}
         self._steps = {}                 # key (shape, dtype, preact) -> bound one-call step, most recent last
         self._step_obj = None
         self._key = None
@@ -934,6 +1050,7 @@ class FusedHeadStep:
         self._optimizer = None
         self.clipper = None
         self._anchor = torch.zeros((), requires_grad=True)
+        self._want_dx = True
         self.probe_events = None
 
     @staticmethod
@@ -975,28 +1092,64 @@ class FusedHeadStep:
         the staleness guard) and this object's bucket, with the bf16 copy of the pose head's W1 as a shadow of the
         update launch when the cfg 003 step will read one (bf16 features).  With TRAIN.CLIP_GRADIENTS > 0 also
         `self.clipper` (`deploy_config`: this process's clone, default from torch.distributed)."""
+        trained = {n: self.params[n] for n in self.trained}
         if float(self.cfg.TRAIN.CLIP_GRADIENTS) > 0.0:
             self.clipper = GradientClipper(self.cfg, deploy_config or DeploymentConfig(), self.bucket,
-                                           dict(self.params), regularized=self.regularized,
-                                           absent=[n for n in self.params if n not in self._written])
+                                           trained, regularized=self.regularized, absent=self._absent)
             self.clipper.bind()
         shadows = None
         self._drop_steps()                           # re-bind with the shadow / the weight images
+        self._frozen_copies = []
         if self.pose_form:
             w1 = self.params['pose_w1']
-            self.w1_shadow = torch.empty(w1.shape, dtype=torch.bfloat16, device=w1.device)
-            shadows = {'pose_w1': self.w1_shadow}
-        self._optimizer = configure_optimizer(self.cfg, dict(self.params), self.bucket, learning_rate,
-                                              regularized=self.regularized, bf16_shadows=shadows, stale=self.stale)
+            shadow = self.w1_shadow = torch.empty(w1.shape, dtype=torch.bfloat16, device=w1.device)
+            if 'pose_w1' in trained:
+                shadows = {'pose_w1': shadow}
+            else:                                    # a frozen W1: the shadow is built once and never rewritten
+                self._frozen_copies.append(('pose_w1', lambda: shadow.copy_(w1.data)))
+        self._optimizer = configure_optimizer(self.cfg, trained, self.bucket, learning_rate,
+                                              regularized=self.regularized, bf16_shadows=shadows, stale=self.stale,
+                                              tf_names=self.tf_names)
         w2 = self.params['pose_w2'].data
         if self.pose_form and w2.is_cuda and w2.shape[1] <= 16:
             # the Pl product reads W2^T as a ready-made bf16 image, rewritten by the optimiser's launch as well
             from .custom_ops import custom_ops_factory as cof
             self.w2t_image = cof.pose_w2t_image(w2)
             img, p2 = self.w2t_image, self.params['pose_w2']
-            self._optimizer.add_image('pose_w2', cof.pose_w2t_image_map(img, w2), owner=img,
-                                      refresh=lambda: img[:w2.shape[1], :w2.shape[0]].copy_(p2.data.t()))
+            refresh = lambda: img[:w2.shape[1], :w2.shape[0]].copy_(p2.data.t())   # noqa: E731
+            if 'pose_w2' in trained:
+                self._optimizer.add_image('pose_w2', cof.pose_w2t_image_map(img, w2), owner=img, refresh=refresh)
+            else:
+                self._frozen_copies.append(('pose_w2', refresh))
+        if self.head.per_class:                      # the per-class operand images of the bound step (_select)
+            self._frozen_copies += [(n, self._refresh_step_images) for n in self._IMAGE_ROLES.values()
+                                    if n in self.frozen]
+        self._refresh_frozen_copies()
         return self._optimizer
+
+    # -- operand copies of FROZEN variables: no optimiser launch rewrites them, the staleness guard still sees them
+    def _refresh_step_images(self) -> None:
+        if self._step_obj is not None and getattr(self._step_obj, 'weight_image_maps', None):
+            self._step_obj.refresh_weight_images()
+
+    def _refresh_frozen_copies(self) -> None:
+        with torch.no_grad():
+            for r in {id(r): r for _, r in self._frozen_copies}.values():
+                r()
+        self._frozen_seen = {n: (self.params[n]._version, self.params[n].data_ptr()) for n, _ in self._frozen_copies}
+
+    def _check_frozen_fresh(self) -> None:
+        bad = [n for n, seen in self._frozen_seen.items()
+               if (self.params[n]._version, self.params[n].data_ptr()) != seen]
+        if not bad:
+            return
+        if self.stale == 'refresh':
+            self._refresh_frozen_copies()
+            return
+        raise StaleOperandError(
+            '%s (frozen by TRAIN.TRAINABLE_SCOPES) written since their bf16 shadow / operand images were built: the '
+            'head would run on the old weights -- call refresh_operands() after load_state_dict / a restore'
+            % ', '.join(bad))
 
     def clip(self) -> None:
         """TRAIN.CLIP_GRADIENTS: clip this clone's gradients in the bucket (see the class docstring for the order);
@@ -1009,6 +1162,7 @@ class FusedHeadStep:
         current weights (after load_state_dict / a checkpoint restore that happened after `make_optimizer`)."""
         if self._optimizer is not None:
             self._optimizer.refresh_shadows()
+            self._refresh_frozen_copies()
         elif self._step_obj is not None and getattr(self._step_obj, 'weight_image_maps', None):
             self._step_obj.refresh_weight_images()
 
@@ -1016,9 +1170,11 @@ class FusedHeadStep:
 
     def _bind(self, X, labels_action, labels_pose, pose_valid, frames=1):
         from .custom_ops import custom_ops_factory as cof
-        head, tr, v = self.head, self.cfg.TRAIN, self.bucket.views
+        head, tr, v = self.head, self.cfg.TRAIN, self._grad_out
         flags = cof.attn_flags(head.softmax_att, head.relu_att, True, self._preact)
-        dX = torch.empty_like(X)
+        # frozen features (conv5 needs no gradient): no [N,P,C] gradient buffer, the step runs with
+        # APA_FLAG_FROZEN_INPUT (a route the library has no arm for falls back to the full step on a scratch buffer)
+        dX = torch.empty_like(X) if self._want_dx else None
         p = {n: t.data for n, t in self.params.items()}
         action_wt = float(tr.LOSS_FN_ACTION_WT)
         clip = {}
@@ -1069,7 +1225,7 @@ class FusedHeadStep:
             if getattr(st, 'weight_image_maps', None):   # per-class maps: rewritten by the optimiser's launch
                 if cached:
                     st.refresh_weight_images()           # they went stale while another shape was current
-                self._optimizer.attach_weight_images(st, self._IMAGE_ROLES)
+                self._optimizer.attach_weight_images(st, {r: n for r, n in self._IMAGE_ROLES.items() if n in self.trained})
         self._step_obj, self._key = st, key
         return st, cached
 
@@ -1090,12 +1246,14 @@ class FusedHeadStep:
                     self.temporal['biases'].fill_(1.0 / frames)
                 self.temporal._bias_initialised = True
             if frames == 1:                                  # no pooling (nets_factory.py:354): the conv gets no gradient
-                self.bucket.views['temporal_weights'].zero_()
-                self.bucket.views['temporal_biases'].zero_()
+                self._grad_out['temporal_weights'].zero_()
+                self._grad_out['temporal_biases'].zero_()
         if self._optimizer is not None:
             self._optimizer.check_fresh()                # weights written behind the optimiser's back?
+            self._check_frozen_fresh()
         # a bound step reads the weights through the pointers it was bound to: a new storage binds a new step
-        key = (tuple(X.shape), frames, X.dtype, self._preact, tuple(p.data_ptr() for p in self.params.values()))
+        key = (tuple(X.shape), frames, X.dtype, self._preact, self._want_dx,
+               tuple(p.data_ptr() for p in self.params.values()))
         st, cached = self._select(key, X, labels_action, labels_pose, pose_valid, frames)
         if cached and self.pose_form:
             st.rebind(X=X, labels=labels_action, pose_labels=labels_pose, pose_valid=pose_valid, offset=head._step)
@@ -1131,6 +1289,8 @@ class FusedHeadStep:
             raise ValueError('FusedHeadStep: the cfg 003 form needs labels_pose [N,H,W,J] and pose_valid [N,J]')
         if self.cfg.TRAIN.LOSS_FN_ACTION != 'softmax-xentropy':     # multi-hot labels of any dtype -> float32, once
             labels_action = labels_action.to(torch.float32).contiguous()
+        # decided per step: a conv5 map that needs no gradient (frozen / precomputed features) gets none
+        self._want_dx = bool(last_conv.requires_grad) or not self.frozen_features
         # one autograd node either way: with a differentiated backbone it hands conv5's gradient upstream, without
         # one (head-only training) it still scales the bucket by whatever coefficient `total` is given
         total = _FusedHeadFunction.apply(last_conv, self._anchor, self, labels_action, labels_pose, pose_valid)

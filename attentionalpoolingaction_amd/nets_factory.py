@@ -143,8 +143,9 @@ class AttentionalPoolingFunction(torch.autograd.Function):
         dX, dXatt, dWa, dba, dWt, dbt = cof.attn_pool_bwd(
             Xc, Xa, Wa.contiguous(), ba.contiguous(), Wt.contiguous(), bt.contiguous(), att, zsave,
             abar, dlogits.contiguous().float(), flags=flags, keep_prob=keep_prob, seed=seed,
-            offset=offset, workspace=ctx.ws, hooks=ctx.hooks)
-        dX = dX.view(ctx.xshape)
+            offset=offset, workspace=ctx.ws, hooks=ctx.hooks, want_dx=ctx.needs_input_grad[0])
+        if dX is not None:                    # frozen features (X needs no gradient): never computed
+            dX = dX.view(ctx.xshape)
         if dXatt is not None:
             dXatt = dXatt.view(ctx.xatt_shape)
         return dX, dXatt, dWa, dba, dWt, dbt, None, None, None, None, None, None
@@ -209,7 +210,8 @@ class PoseHeadFunction(torch.autograd.Function):
         dPl_c = None if dPl is None else dPl.contiguous().float()
         dPpre_c = None if dPpre is None else dPpre.contiguous().to(Xc.dtype)
         dX, dW1, db1, dW2, db2 = cof.pose_head_bwd(Xc, W1.contiguous(), W2.contiguous(), Ppre, dPl_c,
-                                                   dPpre_c, workspace=ctx.ws, ws_from_fwd=True)
+                                                   dPpre_c, workspace=ctx.ws, ws_from_fwd=True,
+                                                   want_dx=ctx.needs_input_grad[0])
         return dX, dW1, db1, dW2, db2
 
 

@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define APA_VERSION 305 /* major*10000 + minor*100 + patch */
+#define APA_VERSION 306 /* major*10000 + minor*100 + patch */
 
 typedef enum apa_status {
   APA_OK = 0,
@@ -95,6 +95,17 @@ typedef enum apa_status {
                                 /* APA_ERR_INVALID_ARG); ignored for M == 1.  A stale image is the caller's bug,   */
                                 /* like a stale apa_pose_attn_step_io.W1_bf16.                                    */
 
+#define APA_FLAG_FROZEN_INPUT 512u /* the features are FROZEN (conv5 precomputed, or nothing upstream of it trains --  */
+                                /* TRAIN.TRAINABLE_SCOPES without a backbone scope): the backward half writes NO     */
+                                /* gradient for X.  The `dX` argument is ignored and may be NULL; every other output */
+                                /* is, bit for bit, what the same call produces without the flag.  Accepted by       */
+                                /* apa_attn_pool_bwd[_ex] and every apa_*_train_step* entry point (apa_pose_head_bwd  */
+                                /* has no flags word: APA_POSE_NO_DX).  Served for M == 1 by every kernel family and  */
+                                /* for per-class maps on the fused K <= 64 route; the dense per-class route, the      */
+                                /* *_cat entry points and a forward call that also asks for the TopDownAttention dump */
+                                /* refuse it with APA_ERR_UNSUPPORTED before anything is queued (run without it).     */
+                                /* A forward call otherwise ignores it.                                               */
+
 int apa_version(void);
 /* Thread-local, never NULL; describes the last failure on the calling thread. */
 const char* apa_last_error(void);
@@ -136,6 +147,9 @@ int apa_attn_pool_fwd(const void* X, const void* Xatt, const float* Wa, const fl
  *   dX [N,P,C] dtype; dXatt [N,P,Ca] dtype or NULL when Xatt == X (its term is folded into dX);
  *   dWa [Ca,M], dba [M], dWt [C,K], dbt [K]  f32.
  * att/zsave/abar are the tensors the forward call produced.
+ * APA_FLAG_FROZEN_INPUT: dX is not written (NULL allowed); M == 1: the streaming pass becomes read-only like the
+ * forward one (cfg 002 fp32, 32 x 14x14x2048: 51.4 MB of the call's 102.8 MB go, 17.5 -> 12.0 us); per-class maps
+ * K <= 64: the dX kernel keeps its row work ([dT | dZ], the dbt | dba partials) and loses the product and the stores.
  */
 int apa_attn_pool_bwd(const void* X, const void* Xatt, const float* Wa, const float* ba,
                       const float* Wt, const float* bt, const float* att, const float* zsave,
@@ -161,8 +175,12 @@ int apa_dropout_mask(uint8_t* mask, size_t n_elems, float keep_prob, uint64_t se
  * dX [N,P,C] dtype, overwritten or (accumulate_dX & 1) added to what the buffer already holds.
  * accumulate_dX & APA_POSE_WS_FROM_FWD: `ws` is the workspace of the matching apa_pose_head_fwd call and has
  * not been written since -- the bf16 copy of W1 the forward call left there is reused, not rebuilt.
+ * accumulate_dX & APA_POSE_NO_DX: the features are frozen (as APA_FLAG_FROZEN_INPUT for the entry points that have a
+ * flags word): the dX product dPpre . W1^T is not launched, `dX` is ignored and may be NULL; dW1, db1, dW2, db2 are
+ * what the call produces without the bit, bit for bit.
  */
 #define APA_POSE_WS_FROM_FWD 2
+#define APA_POSE_NO_DX 4
 size_t apa_pose_head_workspace_bytes(int N, int P, int C, int Cp, int J, int dtype);
 int apa_pose_head_fwd(const void* X, const float* W1, const float* b1, const float* W2,
                       const float* b2, void* Ppre, float* Pl, void* ws, size_t ws_bytes, int N, int P,
@@ -250,6 +268,9 @@ int apa_softmax_xent_fwd_bwd(const float* logits, const int64_t* labels, float* 
  * call launches are shared between the three ops (for the per-class maps with K <= 64 the cross-entropy is taken
  * by the first backward kernel, which is what writes logits / loss / G), so an error return from the second half
  * (e.g. APA_ERR_WORKSPACE) leaves them undefined.
+ * APA_FLAG_FROZEN_INPUT (also the _ex, _clips and _multilabel forms): the backward half writes no dX (NULL allowed);
+ * a route without that arm is refused before the forward half is queued.  Measured against the same step with dX,
+ * alternating in one process, 32 x 14x14x2048: cfg 002 fp32 45.6 -> 40.1 us, HMDB-51 per-class bf16 50.6 -> 42.7 us.
  */
 int apa_attn_head_train_step(const void* X, const void* Xatt, const float* Wa, const float* ba,
                              const float* Wt, const float* bt, const int64_t* labels, float loss_wt,
@@ -289,6 +310,9 @@ int apa_attn_head_eval_step(const void* X, const void* Xatt, const float* Wa, co
  * NULL = as before.  Same values.
  * All pointers device memory; X/Ppre/dX of `dtype`, everything else f32 (labels int64, pose_valid uint8).
  * flags: APA_FLAG_SOFTMAX_ATT / RELU_ATT / TRAIN / RNG_DEVICE as for apa_attn_pool_fwd.
+ * APA_FLAG_FROZEN_INPUT (also the _clips and _multilabel forms): io->dX is ignored and may be NULL -- the pooling pass
+ * stores nothing and the pose head's dX product dPpre . W1^T (with the pooling share in its epilogue) is not launched;
+ * every other output is unchanged bit for bit.  32 x 14x14x2048 bf16, K = 393: 139.1 -> 113.5 us.
  */
 typedef struct apa_pose_attn_step_io {
   const void* X;            /* [N,P,C]                                                   */

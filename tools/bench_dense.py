@@ -26,6 +26,12 @@ headline stays the cfg 002 training workload); run this file directly for one wo
             medians of five: the one-call multi-label step (apa_attn_head_train_step_multilabel), the module path
             (network_fn + gen_losses + autograd) and the softmax one-call step of the same shape.
 
+  frozen002 / frozen003 / frozen_perclass
+            the one-call training steps on FROZEN features (APA_FLAG_FROZEN_INPUT: no dX is computed or stored) against
+            the same step as it runs today, at the BASELINE shapes (32 x 14x14x2048; cfg 002 fp32 K = 393, cfg 003 bf16
+            K = 393, HMDB-51 per-class bf16 K = 51), alternating in one process, medians of five; frozen002 also
+            prints the HIP-event times of the two M == 1 streaming kernels for both forms.
+
 Each builder returns (step_fn, info): `step_fn()` enqueues one step on the current stream; `info`
 carries the workload name and the algorithmic work per image.
 """
@@ -763,6 +769,90 @@ def build_poseatt(cof, dev, N=32, H=14, K=393, dtype='f32', rotate=0):
     return _round_robin(runs), info, kernel_times
 
 
+def build_frozen(cof, dev, which, frozen, N=32, H=14, rotate=0):
+    """One-call training steps on FROZEN features (APA_FLAG_FROZEN_INPUT: None in the dX slot) or, frozen=False, the
+    same step as it runs today -- the BASELINE shapes: 32 x 14x14x2048; frozen002: cfg 002, fp32, K = 393;
+    frozen003: cfg 003, bf16, K = 393; frozen_perclass: HMDB-51 per-class maps, bf16, K = 51.  The feature maps rotate
+    over the same number of sets in both forms (sized for the full step's X + dX).  -> (step, steps_list, info)"""
+    C, P = 2048, H * H
+    dtype = 'f32' if which == 'frozen002' else 'bf16'
+    td = torch.float32 if dtype == 'f32' else torch.bfloat16
+    K = 51 if which == 'frozen_perclass' else 393
+    g = torch.Generator().manual_seed(42)
+    per_set = 2 * N * P * C * (4 if dtype == 'f32' else 2)
+    R = _n_sets(per_set, rotate)
+    Xs = [_features(N, P, C, td, dev, seed=42 + r) for r in range(R)]
+    dx = (lambda X: None) if frozen else (lambda X: torch.empty_like(X))
+    flags = cof.attn_flags(False, False, True)
+    ctr = torch.zeros(1, dtype=torch.int64, device=dev)
+    labels = torch.randint(0, K, (N,), generator=g).to(dev)
+    new = lambda t: torch.empty_like(t)
+    sts = []
+    if which == 'frozen003':
+        Cp, J = 768, 16
+        W1 = (torch.randn(C, Cp, generator=g) / C ** 0.5).to(dev); b1 = torch.zeros(Cp, device=dev)
+        W2 = (torch.randn(Cp, J, generator=g) / Cp ** 0.5).to(dev); b2 = torch.zeros(J, device=dev)
+        Wa = (torch.randn(Cp, 1, generator=g) / Cp ** 0.5).to(dev); ba = torch.zeros(1, device=dev)
+        Wt = (torch.randn(C, K, generator=g) / C ** 0.5).to(dev); bt = torch.zeros(K, device=dev)
+        lbl = torch.rand(N, P, J, generator=g).to(dev)
+        valid = (torch.rand(N, J, generator=g) > 0.3).to(dev)
+        params = (W1, b1, W2, b2, Wa, ba, Wt, bt)
+        pgrads = tuple(new(t) for t in params)
+        w1_bf16, w2t_bf16 = W1.to(torch.bfloat16).contiguous(), cof.pose_w2t_image(W2)
+        for X in Xs:
+            sts.append(cof.PoseAttnTrainStep(X, params, labels, lbl, valid, (dx(X),) + pgrads, flags=flags,
+                                             keep_prob=0.2, seed=42, offset=ctr, w1_bf16=w1_bf16, w2t_bf16=w2t_bf16,
+                                             share_with=sts[0] if sts else None))
+    else:
+        M = K if which == 'frozen_perclass' else 1
+        Wa = (torch.randn(C, M, generator=g) / C ** 0.5).to(dev); ba = torch.zeros(M, device=dev)
+        Wt = (torch.randn(C, K, generator=g) / C ** 0.5).to(dev); bt = torch.zeros(K, device=dev)
+        pg = (new(Wa), new(ba), new(Wt), new(bt))
+        for X in Xs:
+            sts.append(cof.HeadTrainStep(X, X, Wa, ba, Wt, bt, labels, (dx(X), None) + pg, flags=flags, keep_prob=0.2,
+                                         seed=42, offset=ctr, weight_images=M > 1, share_with=sts[0] if sts else None))
+    info = {'dtype': dtype, 'N': N, 'K': K, 'rotate': R,
+            'shape': '{} x {}x{}x{} {}, K={}, dropout keep=0.2'.format(N, H, H, C, dtype, K)}
+    return _round_robin([st.run for st in sts]), sts, info
+
+
+def run_frozen(cof, dev, args, which):
+    """The frozen step and today's step ALTERNATING in one process: five timed loops of each, interleaved; medians.
+    The yardstick is the full step of the same process.  frozen002 also reports the two streaming kernels of the
+    M == 1 head by HIP events (apa_hooks prof_*, cof.KernelTimer) for both forms."""
+    full, full_sts, info = build_frozen(cof, dev, which, False, args.batch, args.hw, args.rotate)
+    froz, froz_sts, _ = build_frozen(cof, dev, which, True, args.batch, args.hw, args.rotate)
+    for _ in range(args.warmup):
+        full(); froz()
+    torch.cuda.synchronize()
+    assert all(st.frozen_input for st in froz_sts), 'the library refused the flag: the frozen form ran the full step'
+    runs = {'full': [], 'frozen': []}
+    for _ in range(5):
+        for name, fn in (('full', full), ('frozen', froz)):
+            sec, _ = timed(fn, args.steps, 0, min_ms=0.0, repeats=1)
+            runs[name].append(sec * 1e6)
+    med = {k: sorted(v)[len(v) // 2] for k, v in runs.items()}
+    out = {'workload': '{}: one-call training step on frozen features (APA_FLAG_FROZEN_INPUT) against the same step '
+                       'writing dX, alternating in one process; {}'.format(which, info['shape']) +
+                       _rot_note(info['rotate'], 2 * info['N'] * args.hw * args.hw * 2048 * (4 if info['dtype'] == 'f32' else 2)),
+           'us_per_step': {k: round(v, 2) for k, v in med.items()},
+           'us_per_step_runs': {k: [round(x, 2) for x in v] for k, v in runs.items()},
+           'frozen_over_full': round(med['frozen'] / med['full'], 4), 'dtype': info['dtype'], 'rotate': info['rotate']}
+    if which == 'frozen002':        # per-kernel HIP-event times of the two streaming passes, one step each form in turn
+        n = 20
+        kt = {'full': cof.KernelTimer(n), 'frozen': cof.KernelTimer(n)}
+        for i in range(n):
+            for name, sts in (('full', full_sts), ('frozen', froz_sts)):
+                sts[i % len(sts)].run(hooks=kt[name].hooks(i))
+        torch.cuda.synchronize()
+        med_us = lambda v: round(sorted(v)[len(v) // 2] * 1e3, 2)
+        out['kernels_us'] = {name: {'m1s_pool_fwd_kernel': med_us(t.fwd_elapsed_ms()),
+                                    'm1s_bwd_main_kernel': med_us(t.bwd_elapsed_ms())} for name, t in kt.items()}
+        for t in kt.values():
+            t.close()
+    return out
+
+
 def timed(fn, steps, warmup, min_ms=50.0, repeats=5):
     """median over >= `repeats` timed loops of `steps` steps each (>= min_ms of device time in total)."""
     for _ in range(warmup):
@@ -806,7 +896,8 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--workload', default='cfg003', choices=['cfg003', 'perclass', 'eval002', 'eval003', 'rank1', 'posebwd', 'posebwd_acc', 'update003',
                                                          'update_perclass', 'poseatt', 'video_perclass', 'video003',
-                                                         'hico002', 'charades_clips'])
+                                                         'hico002', 'charades_clips', 'frozen002', 'frozen003',
+                                                         'frozen_perclass'])
     ap.add_argument('--clips', type=int, default=8, help='video_*: clips per batch')
     ap.add_argument('--frames', type=int, default=4, help='video_*: frames per clip')
     ap.add_argument('--only', default=None, choices=['clip_one_call', 'module_path', 'flat_one_call',
@@ -842,6 +933,9 @@ def main():
         return
     if args.workload in ('hico002', 'charades_clips'):
         print(json.dumps(run_multilabel(cof, dev, args, args.workload)))
+        return
+    if args.workload.startswith('frozen'):
+        print(json.dumps(run_frozen(cof, dev, args, args.workload)))
         return
     if args.workload == 'poseatt':
         step, info, kernel_times = build_poseatt(cof, dev, args.batch, args.hw, args.classes or 393,
