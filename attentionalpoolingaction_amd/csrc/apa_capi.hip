@@ -725,6 +725,70 @@ static int attn_head_eval(PoolCall d, const M1Fwd& f, const int64_t* labels, flo
                                   d.K, 1.0f, 1.0f, d.st);
 }
 
+// What the *_eval_step_clips entry points refuse about their clip and their scores, before anything is launched.
+static int eval_scores_check(const char* fn, const apa_clip_pool* clip, int kind, int N, int K, const float* logits,
+                             const int64_t* labels, const float* loss, const float* probs, const int64_t* pred) {
+  if (kind != APA_SCORES_SOFTMAX && kind != APA_SCORES_SIGMOID) {
+    set_error("%s: unknown scores kind %d", fn, kind);
+    return APA_ERR_INVALID_ARG;
+  }
+  if (!logits || !probs || !pred) {
+    set_error("%s: null logits / probs / pred pointer", fn);
+    return APA_ERR_INVALID_ARG;
+  }
+  if ((labels == nullptr) != (loss == nullptr)) {
+    set_error("%s: labels and loss must be given together", fn);
+    return APA_ERR_INVALID_ARG;
+  }
+  if (kind == APA_SCORES_SIGMOID && labels) {
+    set_error("%s: the sigmoid scores take no labels / loss (eval.py computes none)", fn);
+    return APA_ERR_INVALID_ARG;
+  }
+  if (N <= 0 || K <= 0) {
+    set_error("%s: non-positive size N=%d K=%d", fn, N, K);
+    return APA_ERR_INVALID_ARG;
+  }
+  if (!clip) return APA_OK;
+  if (clip->frames <= 0 || N % clip->frames != 0) {
+    set_error("%s: N=%d is not a whole number of clips of %d frames", fn, N, clip->frames);
+    return APA_ERR_INVALID_ARG;
+  }
+  if (!clip->pooled || (clip->w && (!clip->b || !clip->tatt))) {
+    set_error("%s: apa_clip_pool needs pooled, and with w also b and tatt", fn);
+    return APA_ERR_INVALID_ARG;
+  }
+  return APA_OK;
+}
+
+// The tail of both *_eval_step_clips entry points, eval_scores_check passed: the flat softmax form is attn_head_eval
+// itself; every other form runs the forward half without a folded or trailing softmax, then the one scores launch.
+static int attn_head_eval_clips(const char* fn, const apa_clip_pool* clip, int kind, PoolCall d, const M1Fwd& f,
+                                const int64_t* labels, float* loss, float* probs, int64_t* pred) {
+  if (!clip && kind == APA_SCORES_SOFTMAX) return attn_head_eval(d, f, labels, loss, probs, pred);
+  d.flags &= ~(unsigned)APA_FLAG_TRAIN;   // is_training=False: no dropout
+  const int rc = attn_pool_fwd(d, f, nullptr);
+  if (rc != APA_OK) return rc;
+  if (PcTrace* t = pc_trace()) if (d.M != 1) t->xent = PC_XENT_OWN;
+  const int F = clip ? clip->frames : 1;
+  return clip_scores_launch(fn, kind, f.logits, clip ? clip->w : nullptr, clip ? clip->b : nullptr, labels,
+                            clip ? clip->pooled : nullptr, clip ? clip->tatt : nullptr, probs, pred, loss, d.N / F, F,
+                            d.K, d.st);
+}
+
+extern "C" int apa_attn_head_eval_step_clips(const apa_clip_pool* clip, int scores_kind, const void* X,
+                                             const void* Xatt, const float* Wa, const float* ba, const float* Wt,
+                                             const float* bt, const int64_t* labels, float* logits, float* att,
+                                             float* zsave, float* abar, float* loss, float* probs, int64_t* pred,
+                                             void* ws, size_t ws_bytes, int N, int P, int C, int Ca, int K, int M,
+                                             unsigned flags, int dtype, void* stream) {
+  const char* fn = "apa_attn_head_eval_step_clips";
+  const int rc = eval_scores_check(fn, clip, scores_kind, N, K, logits, labels, loss, probs, pred);
+  if (rc != APA_OK) return rc;
+  return attn_head_eval_clips(fn, clip, scores_kind,
+                              pool_call({N, P, C, Ca, K, M, dtype}, flags, 1.0f, 0, 0, ws, ws_bytes, stream),
+                              M1Fwd{X, Xatt, Wa, ba, Wt, bt, logits, att, zsave, abar}, labels, loss, probs, pred);
+}
+
 extern "C" int apa_attn_head_eval_step(const void* X, const void* Xatt, const float* Wa, const float* ba,
                                        const float* Wt, const float* bt, const int64_t* labels, float* logits,
                                        float* att, float* zsave, float* abar, float* loss, float* probs, int64_t* pred,
@@ -754,49 +818,53 @@ extern "C" size_t apa_pose_attn_eval_workspace_bytes(int N, int P, int C, int Cp
   return pose_eval_carve(N, P, C, Cp, J, K, flags, dtype).total;
 }
 
-extern "C" int apa_pose_attn_eval_step(const apa_pose_attn_eval_io* io, int N, int P, int C, int Cp, int J, int K,
-                                       unsigned flags, int dtype, void* stream) {
+// clips_fn == nullptr: apa_pose_attn_eval_step; else the _clips entry point of that name with its clip and scores kind
+static int pose_attn_eval(const char* clips_fn, const apa_clip_pool* clip, int kind, const apa_pose_attn_eval_io* io,
+                          int N, int P, int C, int Cp, int J, int K, unsigned flags, int dtype, void* stream) {
+  const char* fn = clips_fn ? clips_fn : "apa_pose_attn_eval_step";
   if (!io) {
-    set_error("apa_pose_attn_eval_step: null io");
+    set_error("%s: null io", fn);
     return APA_ERR_INVALID_ARG;
   }
   const apa_pose_attn_eval_io& s = *io;
   if (!s.X || !s.W1 || !s.b1 || !s.W2 || !s.b2 || !s.Wa || !s.ba || !s.Wt || !s.bt || !s.att || !s.logits ||
       !s.zsave || !s.abar || !s.probs || !s.pred) {
-    set_error("apa_pose_attn_eval_step: null pointer in apa_pose_attn_eval_io (only W1_bf16, labels, loss, Pl and route "
-              "may be NULL)");
+    set_error("%s: null pointer in apa_pose_attn_eval_io (only W1_bf16, labels, loss, Pl and route may be NULL)",
+              fn);
     return APA_ERR_INVALID_ARG;
   }
   if ((s.labels == nullptr) != (s.loss == nullptr)) {
-    set_error("apa_pose_attn_eval_step: labels and loss must be given together (both null or neither)");
+    set_error("%s: labels and loss must be given together (both null or neither)", fn);
     return APA_ERR_INVALID_ARG;
   }
-  int rc = check_common("apa_pose_attn_eval_step", {N, P, C, Cp, K, 1, dtype});
+  int rc = check_common(fn, {N, P, C, Cp, K, 1, dtype});
   if (rc != APA_OK) return rc;
+  if (clips_fn && (rc = eval_scores_check(fn, clip, kind, N, K, s.logits, s.labels, s.loss, s.probs, s.pred)) != APA_OK)
+    return rc;
   if (J <= 0) {
-    set_error("apa_pose_attn_eval_step: J=%d", J);
+    set_error("%s: J=%d", fn, J);
     return APA_ERR_INVALID_ARG;
   }
   if (flags & (APA_FLAG_RELU_INPUT | APA_FLAG_RNG_EXTERNAL)) {
-    set_error("apa_pose_attn_eval_step: APA_FLAG_RELU_INPUT / APA_FLAG_RNG_EXTERNAL have no meaning here (the attention "
-              "input is pose_pre_logits; evaluation draws no mask)");
+    set_error("%s: APA_FLAG_RELU_INPUT / APA_FLAG_RNG_EXTERNAL have no meaning here (the attention input is "
+              "pose_pre_logits; evaluation draws no mask)", fn);
     return APA_ERR_UNSUPPORTED;
   }
   flags &= APA_FLAG_SOFTMAX_ATT | APA_FLAG_RELU_ATT;   // is_training=False: everything else is a training matter
   if (!m1_supported(C, Cp, dtype, false)) {
-    set_error("apa_pose_attn_eval_step: C and Cp must be whole 16-byte vectors (multiples of 4 fp32 / 8 bf16 channels, "
-              "C <= 9584); got C=%d Cp=%d dtype=%d", C, Cp, dtype);
+    set_error("%s: C and Cp must be whole 16-byte vectors (multiples of 4 fp32 / 8 bf16 channels, C <= 9584); got "
+              "C=%d Cp=%d dtype=%d", fn, C, Cp, dtype);
     return APA_ERR_UNSUPPORTED;
   }
   const PoseEvalCarve cv = pose_eval_carve(N, P, C, Cp, J, K, flags, dtype);
   if (!s.ws || s.ws_bytes < cv.total) {
-    set_error("apa_pose_attn_eval_step: workspace too small (%zu < %zu)", s.ws_bytes, cv.total);
+    set_error("%s: workspace too small (%zu < %zu)", fn, s.ws_bytes, cv.total);
     return APA_ERR_WORKSPACE;
   }
   char* w = static_cast<char*>(s.ws);
   float* zpart = reinterpret_cast<float*>(w + cv.pose + cv.pool);
   const bool relu_att = (flags & APA_FLAG_RELU_ATT) && !(flags & APA_FLAG_SOFTMAX_ATT);
-  PoseCall pc = pose_call("apa_pose_attn_eval_step", N, P, C, Cp, J, dtype, w, cv.pose, stream);
+  PoseCall pc = pose_call(fn, N, P, C, Cp, J, dtype, w, cv.pose, stream);
   pc.ws_name = "pose workspace";
   PoseStepArgs a;
   a.W1_bf16 = s.W1_bf16; a.wa = s.Wa; a.ba = s.ba; a.att = s.att; a.relu_att = relu_att;
@@ -808,6 +876,19 @@ extern "C" int apa_pose_attn_eval_step(const apa_pose_attn_eval_io* io, int N, i
   const void* xatt = o.ppre ? o.ppre : static_cast<const void*>(zpart);
   PoolCall d = pool_call({N, P, C, Cp, K, 1, dtype}, flags, 1.0f, 0, 0, w + cv.pose, cv.pool, stream);
   if (o.att_ready) d.flags |= APA_IFLAG_ATT_READY;
-  return attn_head_eval(d, M1Fwd{s.X, xatt, s.Wa, s.ba, s.Wt, s.bt, s.logits, s.att, s.zsave, s.abar}, s.labels, s.loss,
-                        s.probs, s.pred);
+  const M1Fwd f{s.X, xatt, s.Wa, s.ba, s.Wt, s.bt, s.logits, s.att, s.zsave, s.abar};
+  return clips_fn ? attn_head_eval_clips(fn, clip, kind, d, f, s.labels, s.loss, s.probs, s.pred)
+                  : attn_head_eval(d, f, s.labels, s.loss, s.probs, s.pred);
+}
+
+extern "C" int apa_pose_attn_eval_step(const apa_pose_attn_eval_io* io, int N, int P, int C, int Cp, int J, int K,
+                                       unsigned flags, int dtype, void* stream) {
+  return pose_attn_eval(nullptr, nullptr, APA_SCORES_SOFTMAX, io, N, P, C, Cp, J, K, flags, dtype, stream);
+}
+
+extern "C" int apa_pose_attn_eval_step_clips(const apa_clip_pool* clip, int scores_kind,
+                                             const apa_pose_attn_eval_io* io, int N, int P, int C, int Cp, int J, int K,
+                                             unsigned flags, int dtype, void* stream) {
+  return pose_attn_eval("apa_pose_attn_eval_step_clips", clip, scores_kind, io, N, P, C, Cp, J, K, flags, dtype,
+                        stream);
 }

@@ -37,13 +37,11 @@
 // softmax form's.  With F == 1 and no temporal attention: apa_multilabel_loss_fwd_bwd's bits.
 #include <math.h>
 
+#include "apa_clip_stages.h"
 #include "apa_device.h"
 #include "apa_internal.h"
 
 namespace apa {
-
-constexpr int CLIP_LDS_K = 4096;   // pooled + gradient rows in LDS up to this K
-constexpr int CLIP_LDS_F = 64;     // a[b, :] in LDS up to this F (else re-read from tatt)
 
 // dynamic LDS: [row_floats] pooled row | [row_floats] gradient row | [CLIP_LDS_F] a | [4] xent scratch
 template <bool TEMPORAL, bool ML>
@@ -65,33 +63,9 @@ __global__ __launch_bounds__(256) void clip_xent_kernel(
   const float invF = 1.0f / (float)F;
   const float* ap = nullptr;
 
-  if (TEMPORAL) {   // a[r] = x[r,:] . w + b0
-    for (int f = wave; f < F; f += 4) {
-      const float* xr = x + (rb + f) * K;
-      float acc = 0.f;
-      for (int k = lane; k < K; k += 64) acc = fmaf(xr[k], w[k], acc);
-      const float a = wave_sum(acc) + b0[0];
-      if (lane == 0) {
-        tatt[rb + f] = a;
-        if (F <= CLIP_LDS_F) sa[f] = a;
-      }
-    }
-    __syncthreads();
-    ap = F <= CLIP_LDS_F ? sa : tatt + rb;
-  }
-
-  // pooled[b,k]: frames in increasing f (F == 1 without attention: x * 1)
-  for (int k = threadIdx.x; k < K; k += 256) {
-    const float* xc = x + rb * K + k;
-    float acc = TEMPORAL ? xc[0] * ap[0] : xc[0];
-    for (int f = 1; f < F; ++f) {
-      const float xv = xc[(size_t)f * K];
-      acc = TEMPORAL ? fmaf(xv, ap[f], acc) : acc + xv;
-    }
-    const float p = acc * invF;
-    prow[k] = p;
-    if (rows_lds) pooled[(size_t)b * K + k] = p;
-  }
+  // a[r] = x[r,:] . w + b0, then pooled[b,k]: the stages clip_scores_kernel shares (apa_clip_stages.h)
+  if (TEMPORAL) ap = clip_tatt_stage(x, w, b0, tatt, sa, F <= CLIP_LDS_F, rb, F, K);
+  clip_pool_stage<TEMPORAL>(x, ap, prow, rows_lds ? pooled + (size_t)b * K : nullptr, rb, F, K);
   __syncthreads();
 
   if (ML) {   // the pooled row's sigmoid loss, on the whole block: loss[1+b] and the gradient row

@@ -500,6 +500,63 @@ __device__ __forceinline__ void pc_row_xent_any(const float* __restrict__ row, i
   }
 }
 
+// The forward-only sibling (apa_clipscores.hip): the same kernel's probabilities, first maximal index and row loss for
+// one row of 4 <= K <= 1024, in the same three passes and the same operation order per lane, so the bits are
+// apa_softmax_xent_fwd_bwd's.  ONE whole wave calls it; lab < 0 (no ground truth): *lv = 0.  probs: K floats of the
+// row's output, or nullptr.  *lv and *cand are valid in every lane.
+__device__ __forceinline__ void pc_row_softmax_any(const float* __restrict__ row, int K, int lab,
+                                                   float* __restrict__ probs, float* lv, int* cand) {
+  typedef float f4u __attribute__((ext_vector_type(4), aligned(4)));
+  const int nv4 = K <= 128 ? 1 : (K <= 256 ? 2 : (K <= 512 ? 4 : 8));
+  const int lane = threadIdx.x & 63, hl = lane & 31;
+  const bool lab_ok = lab >= 0 && lab < K;
+  const float xl = row[lab_ok ? lab : 0];
+  auto vec = [&](int i, int& colc) {       // this lane's i-th vector, columns the previous lane covers masked out
+    const int col0 = 4 * (hl + 32 * i);
+    colc = min(col0, K - 4);
+    f4u v = *reinterpret_cast<const f4u*>(row + colc);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) v[e] = colc + e >= col0 ? v[e] : -INFINITY;
+    return v;
+  };
+  float m = -INFINITY;
+  int arg = 0x7fffffff;
+#pragma unroll 1
+  for (int i = 0; i < nv4; ++i) {
+    int colc;
+    const f4u v = vec(i, colc);
+#pragma unroll
+    for (int e = 0; e < 4; ++e)
+      if (v[e] > m) { m = v[e]; arg = colc + e; }   // first maximal index of this lane
+  }
+  const float mw = half_max(m, lane);
+  *cand = half_min_first((m == mw) ? arg : 0x7fffffff, lane);
+  float l = 0.f;
+#pragma unroll 1
+  for (int i = 0; i < nv4; ++i) {
+    int colc;
+    const f4u v = vec(i, colc);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) l += exp_fast(v[e] - mw);
+  }
+  l = half_sum(l, lane);
+  const float inv = 1.0f / l;
+  *lv = lab_ok ? -(xl - mw - logf(l)) : 0.f;
+  if (probs && lane < 32) {
+#pragma unroll 1
+    for (int i = 0; i < nv4; ++i) {
+      int colc;
+      const f4u v = vec(i, colc);
+      const int col0 = 4 * (hl + 32 * i);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const int c = colc + e;
+        if (c >= col0 && c < K) probs[c] = exp_fast(v[e] - mw) * inv;
+      }
+    }
+  }
+}
+
 // (apa_m1_small.hip's reducers and apa_mlloss.hip's share these)
 // abar[n] = (sum_s pstat[n,s,2]) / P on the folded route (S <= 16), bit for bit as m1_finalize_fwd_kernel forms it
 // (apa_m1.hip): one split per thread of a 256-thread block, wave_sum, then (s0 + s1) + (s2 + s3) over the four waves.

@@ -383,6 +383,13 @@ int ml_loss_rows(int kind, const float* labels, float pos_weight, const float* l
 // with dws also db = sum dws and dw = dws^T x
 int clip_loss_finish(const float* x, const float* dws, float* loss, float* dw, float* db, int B, int rows, int K,
                      float lscale, hipStream_t st);
+// apa_clipscores.hip: clip_scores_kernel, the one launch behind the logits of an evaluation step -- frame pooling,
+// then the scores (kind: APA_SCORES_*), the prediction and, with labels, the loss of the pooled rows.  pooled ==
+// nullptr (F == 1, no temporal attention only): the logits rows are the pooled rows.  Arguments checked by the caller
+// but for what the launch itself cannot serve.
+int clip_scores_launch(const char* fn, int kind, const float* logits, const float* w, const float* b,
+                       const int64_t* labels, float* pooled, float* tatt, float* scores, int64_t* pred, float* loss,
+                       int B, int F, int K, hipStream_t st);
 bool m1_bwd_head_supported(int N, int C, int K);
 int m1_bwd_head(const float* G, const float* Wt, const float* zsave, const float* abar,
                 const float* bt, float* dz, float* dWt, float* dbt, float* sn, int N, int C, int K,

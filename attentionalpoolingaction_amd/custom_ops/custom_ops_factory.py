@@ -39,6 +39,8 @@ APA_FLAG_FROZEN_INPUT = 512  # the features are frozen: the backward half writes
 APA_POSE_WS_FROM_FWD = 2    # bits of apa_pose_head_bwd's accumulate_dX
 APA_POSE_NO_DX = 4
 APA_ERR_UNSUPPORTED = -2
+APA_SCORES_SOFTMAX = 0   # eval.py:197
+APA_SCORES_SIGMOID = 1   # eval.py:194-195 (TRAIN.LOSS_FN_ACTION starts with 'multi-label')
 APA_WIMG_MAX = 12
 APA_WIMG_ROLES = {0: 'Wa', 1: 'ba', 2: 'Wt', 3: 'bt'}
 
@@ -114,6 +116,11 @@ _SIGNATURES = {
                                     [c_size_t] + [c_int] * 6 + [c_uint, c_float, c_uint64, c_uint64, c_int,
                                                                 c_void_p]),
     'apa_attn_head_eval_step': (c_int, [c_void_p] * 15 + [c_size_t] + [c_int] * 6 + [c_uint, c_int, c_void_p]),
+    # evaluation of clips / sigmoid scores: `const apa_clip_pool*` (or NULL) and the scores kind first
+    'apa_clip_scores': (c_int, [c_int] + [c_void_p] * 9 + [c_int] * 3 + [c_void_p]),
+    'apa_attn_head_eval_step_clips': (c_int, [c_void_p, c_int] + [c_void_p] * 15 + [c_size_t] + [c_int] * 6 +
+                                      [c_uint, c_int, c_void_p]),
+    'apa_pose_attn_eval_step_clips': (c_int, [c_void_p, c_int, c_void_p] + [c_int] * 6 + [c_uint, c_int, c_void_p]),
     'apa_momentum_sgd_step': (c_int, [c_int, POINTER(c_void_p), POINTER(c_size_t), POINTER(c_float),
                                       c_void_p, c_void_p, c_float, c_float, c_float, c_void_p]),
     'apa_momentum_sgd_step_shadow': (c_int, [c_int, POINTER(c_void_p), POINTER(c_size_t), POINTER(c_float),
@@ -1031,6 +1038,69 @@ def clip_xent_workspace_bytes(B, F, K) -> int:
     return int(load_library().apa_clip_xent_workspace_bytes(B, F, K))
 
 
+def _scores_kind(who: str, kind: str) -> int:
+    if kind not in ('softmax', 'sigmoid'):
+        raise ApaError("{}: scores must be 'softmax' or 'sigmoid', got {!r}".format(who, kind))
+    return APA_SCORES_SIGMOID if kind == 'sigmoid' else APA_SCORES_SOFTMAX
+
+
+def clip_scores(logits, frames_per_video, w=None, b=None, *, kind='softmax', labels=None):
+    """(pooled [B,K], tatt [B*F] or None, scores [B,K], pred int64 [B], loss [1+B] or None): frame pooling (with the
+    temporal attention w [K], b [1] when given), then the softmax / sigmoid scores and the first-index argmax of the
+    pooled rows -- with int64 `labels` [B] (softmax only) also their cross-entropy -- in one launch (include/apa.h:
+    apa_clip_scores).  logits f32 [B*F,K]."""
+    lib = load_library()
+    BF, K = logits.shape
+    F = int(frames_per_video)
+    if F <= 0 or BF % F:
+        raise ApaError('clip_scores: {} frame rows are not a whole number of clips of {} frames'.format(BF, F))
+    B = BF // F
+    code = _scores_kind('clip_scores', kind)
+    dev, f32 = logits.device, torch.float32
+    pooled = torch.empty((B, K), dtype=f32, device=dev)
+    tatt = torch.empty((BF,), dtype=f32, device=dev) if w is not None else None
+    scores = torch.empty((B, K), dtype=f32, device=dev)
+    pred = torch.empty((B,), dtype=torch.int64, device=dev)
+    loss = torch.empty((1 + B,), dtype=f32, device=dev) if labels is not None else None
+    if labels is not None and labels.numel() != B:
+        raise ApaError('clip_scores: labels int64 [B] expected, one per clip')
+    rc = lib.apa_clip_scores(code, _dev_ptr(logits, 'logits', f32), _dev_ptr(w, 'w', f32), _dev_ptr(b, 'b', f32),
+                             _dev_ptr(labels, 'labels', torch.int64), pooled.data_ptr(), _dev_ptr(tatt, 'tatt'),
+                             scores.data_ptr(), pred.data_ptr(), _dev_ptr(loss, 'loss'), B, F, K, _stream_ptr())
+    _check(rc, 'apa_clip_scores')
+    return pooled, tatt, scores, pred, loss
+
+
+def _bind_eval_clip(who: str, N: int, K: int, frames, temporal, scores: str, labels, dev):
+    """What HeadEvalStep / PoseAttnEvalStep add for clips and / or sigmoid scores: (B, kind code, the ApaClipPool or
+    None, pooled, tatt, the tensors to keep alive).  frames == 1 without temporal attention: no clip (the logits rows
+    are the pooled rows)."""
+    code = _scores_kind(who, scores)
+    F = int(frames)
+    if F <= 0 or N % F:
+        raise ApaError('{}: {} feature maps are not a whole number of clips of {} frames'.format(who, N, F))
+    B = N // F
+    if code == APA_SCORES_SIGMOID and labels is not None:
+        raise ApaError('{}: the sigmoid scores take no labels (eval.py computes no loss)'.format(who))
+    if labels is not None and labels.numel() != B:
+        raise ApaError('{}: labels int64 [{}] expected, one per clip'.format(who, B))
+    if F == 1 and temporal is None:
+        return B, code, None, None, None, ()
+    clip = ApaClipPool()
+    clip.frames = F
+    pooled = torch.empty((B, K), dtype=torch.float32, device=dev)
+    tatt = None
+    clip.pooled = pooled.data_ptr()
+    if temporal is not None:
+        w, b = temporal
+        if w.numel() != K or b.numel() != 1:
+            raise ApaError('{}: temporal = (w [K], b [1]) expected'.format(who))
+        tatt = torch.empty((N,), dtype=torch.float32, device=dev)
+        clip.w, clip.b = _dev_ptr(w, 'temporal w', torch.float32), _dev_ptr(b, 'temporal b', torch.float32)
+        clip.tatt = tatt.data_ptr()
+    return B, code, clip, pooled, tatt, (temporal,)
+
+
 def clip_xent_fwd_bwd(logits, labels, frames_per_video, w=None, b=None, *, wt=1.0, grad_scale=1.0, workspace=None):
     """(pooled [B,K], tatt [B*F] or None, loss [1+B], G [B*F,K], dw [K] or None, db [1] or None): frame pooling (with
     the temporal attention w [K], b [1] when given), softmax cross-entropy on the pooled logits and the gradient at the
@@ -1465,22 +1535,31 @@ class PoseAttnTrainStep:
 class HeadEvalStep:
     """apa_attn_head_eval_step bound to caller-owned inputs: forward + softmax probabilities + argmax
     (+ per-example loss when `labels` is given) as ONE foreign call (eval.py:181-197).  Outputs:
-    `logits`, `att`, `probs` [N,K], `pred` [N] int64, `loss` [1+N] or None."""
+    `logits`, `att`, `probs` [N,K], `pred` [N] int64, `loss` [1+N] or None.
 
-    def __init__(self, X, Xatt, Wa, ba, Wt, bt, labels=None, *, flags=0, workspace=None):
+    `frames` > 1 (the N maps are the folded frames of B = N / frames clips), `temporal = (w [K], b [1])` (the
+    TemporalAttention conv) and / or `scores='sigmoid'` (the multi-label datasets, no labels): the step is
+    apa_attn_head_eval_step_clips -- `logits` stays the [N,K] frame logits, `pooled` [B,K] and `tatt` [N] (None without
+    them) are further outputs, and `probs`, `pred`, `labels`, `loss` are per clip (B in place of N).  With the defaults
+    nothing changes."""
+
+    def __init__(self, X, Xatt, Wa, ba, Wt, bt, labels=None, *, flags=0, workspace=None, frames=1, temporal=None,
+                 scores='softmax'):
         self.lib = load_library()
         N, C = X.shape[0], X.shape[-1]
         P = X.numel() // (N * C)
         Ca, M, K = Xatt.shape[-1], Wa.shape[1], Wt.shape[1]
         dev = X.device
         flags &= ~APA_FLAG_TRAIN
+        B, code, self._clip, self.pooled, self.tatt, keep = _bind_eval_clip('HeadEvalStep', N, K, frames, temporal,
+                                                                          scores, labels, dev)
         self.logits = torch.empty((N, K), dtype=torch.float32, device=dev)
         self.att = torch.empty((N, P, M), dtype=torch.float32, device=dev)
         self.zsave = torch.empty((N, C) if M == 1 else (N, P, K), dtype=torch.float32, device=dev)
         self.abar = torch.empty((N,), dtype=torch.float32, device=dev) if M == 1 else None
-        self.probs = torch.empty((N, K), dtype=torch.float32, device=dev)
-        self.pred = torch.empty((N,), dtype=torch.int64, device=dev)
-        self.loss = torch.empty((1 + N,), dtype=torch.float32, device=dev) if labels is not None else None
+        self.probs = torch.empty((B, K), dtype=torch.float32, device=dev)
+        self.pred = torch.empty((B,), dtype=torch.int64, device=dev)
+        self.loss = torch.empty((1 + B,), dtype=torch.float32, device=dev) if labels is not None else None
         need = int(self.lib.apa_attn_pool_workspace_bytes(N, P, C, Ca, K, M, flags))
         if workspace is None or workspace.numel() < need:
             workspace = torch.empty((max(need, 16),), dtype=torch.uint8, device=dev)
@@ -1494,7 +1573,11 @@ class HeadEvalStep:
             self.zsave.data_ptr(), _dev_ptr(self.abar, 'abar'), _dev_ptr(self.loss, 'loss'),
             self.probs.data_ptr(), self.pred.data_ptr(), workspace.data_ptr(), workspace.numel(),
             N, P, C, Ca, K, M, flags, _feat_dtype(X)]
-        self._fn = self.lib.apa_attn_head_eval_step
+        self._fn, self._name, self._pre = self.lib.apa_attn_head_eval_step, 'apa_attn_head_eval_step', ()
+        if self._clip is not None or code != APA_SCORES_SOFTMAX:    # (clip or NULL, the kind, then the same arguments)
+            self._keep += keep
+            self._fn, self._name = self.lib.apa_attn_head_eval_step_clips, 'apa_attn_head_eval_step_clips'
+            self._pre = (None if self._clip is None else ctypes.addressof(self._clip), code)
 
     def rebind(self, X) -> None:
         """Point the bound step at another feature map of the same shape / dtype (attention from the map itself:
@@ -1507,9 +1590,9 @@ class HeadEvalStep:
         self._keep = (X, X) + tuple(self._keep[2:])
 
     def run(self, stream: Optional[int] = None) -> None:
-        rc = self._fn(*self._args, _stream_ptr() if stream is None else stream)
+        rc = self._fn(*self._pre, *self._args, _stream_ptr() if stream is None else stream)
         if rc != 0:
-            _check(rc, 'apa_attn_head_eval_step')
+            _check(rc, self._name)
 
 
 class ApaPoseAttnEvalIO(ctypes.Structure):
@@ -1526,27 +1609,29 @@ class PoseAttnEvalStep:
     `params = (W1, b1, W2, b2, Wa, ba, Wt, bt)` fp32; `w1_bf16`: optional bf16 copy of W1 the caller keeps current.
     Outputs as attributes: `att` [N,P,1], `logits`, `zsave`, `abar`, `probs` [N,K], `pred` [N] int64, `loss` [1+N] or
     None, `Pl` [N,P,J] or None (`want_pose_logits=True`).  `route` (after `run()`): 1 = the pose-head product's
-    epilogue formed the attention logits and pose_pre_logits was never written; 0 = the composed route."""
+    epilogue formed the attention logits and pose_pre_logits was never written; 0 = the composed route.
+    `frames`, `temporal`, `scores`: as for HeadEvalStep (apa_pose_attn_eval_step_clips; both routes are kept)."""
 
-    def __init__(self, X, params, labels=None, *, flags=0, w1_bf16=None, want_pose_logits=False, workspace=None):
+    def __init__(self, X, params, labels=None, *, flags=0, w1_bf16=None, want_pose_logits=False, workspace=None,
+                 frames=1, temporal=None, scores='softmax'):
         self.lib = load_library()
         W1, b1, W2, b2, Wa, ba, Wt, bt = params
         N, C = X.shape[0], X.shape[-1]
         P = X.numel() // (N * C)
         Cp, J, K = W1.shape[1], W2.shape[1], Wt.shape[1]
         dev, f32 = X.device, torch.float32
+        B, code, self._clip, self.pooled, self.tatt, keep = _bind_eval_clip('PoseAttnEvalStep', N, K, frames, temporal,
+                                                                          scores, labels, dev)
         if tuple(W1.shape) != (C, Cp) or Wa.numel() != Cp or tuple(Wt.shape) != (C, K) or W2.shape[0] != Cp:
             raise ApaError('PoseAttnEvalStep: W1 [C,Cp], W2 [Cp,J], Wa [Cp,1], Wt [C,K] expected')
         if w1_bf16 is not None and w1_bf16.numel() != W1.numel():
             raise ApaError('PoseAttnEvalStep: w1_bf16 must have W1\'s element count')
-        if labels is not None and labels.numel() != N:
-            raise ApaError('PoseAttnEvalStep: labels [N] expected')
         flags &= APA_FLAG_SOFTMAX_ATT | APA_FLAG_RELU_ATT
         dt = _feat_dtype(X)
         new = lambda *shape, dt=f32: torch.empty(shape, dtype=dt, device=dev)
         self.att, self.logits, self.zsave, self.abar = new(N, P, 1), new(N, K), new(N, C), new(N)
-        self.probs, self.pred = new(N, K), new(N, dt=torch.int64)
-        self.loss = new(1 + N) if labels is not None else None
+        self.probs, self.pred = new(B, K), new(B, dt=torch.int64)
+        self.loss = new(1 + B) if labels is not None else None
         self.Pl = new(N, P, J) if want_pose_logits else None
         need = int(self.lib.apa_pose_attn_eval_workspace_bytes(N, P, C, Cp, J, K, flags, dt, int(bool(want_pose_logits))))
         if workspace is None or workspace.numel() < need:
@@ -1567,6 +1652,11 @@ class PoseAttnEvalStep:
         io.route = ctypes.pointer(self._route)
         self._io = io
         self._args = [ctypes.addressof(io), N, P, C, Cp, J, K, flags, dt]
+        self._fn, self._name = self.lib.apa_pose_attn_eval_step, 'apa_pose_attn_eval_step'
+        if self._clip is not None or code != APA_SCORES_SOFTMAX:    # (clip or NULL, the kind, then the same arguments)
+            self._keep += keep
+            self._fn, self._name = self.lib.apa_pose_attn_eval_step_clips, 'apa_pose_attn_eval_step_clips'
+            self._args = [None if self._clip is None else ctypes.addressof(self._clip), code] + self._args
 
     @property
     def route(self) -> Optional[int]:
@@ -1589,9 +1679,9 @@ class PoseAttnEvalStep:
         self._keep = tuple(keep)
 
     def run(self, stream: Optional[int] = None) -> None:
-        rc = self.lib.apa_pose_attn_eval_step(*self._args, _stream_ptr() if stream is None else stream)
+        rc = self._fn(*self._args, _stream_ptr() if stream is None else stream)
         if rc != 0:
-            _check(rc, 'apa_pose_attn_eval_step')
+            _check(rc, self._name)
 
 
 class ApaWeightImage(ctypes.Structure):

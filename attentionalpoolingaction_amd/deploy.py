@@ -1324,9 +1324,11 @@ class FusedHeadEval:
       eval.py fetches it only under --ept), 'labels' when given, 'TemporalAttention' for video input with
       NET.USE_TEMPORAL_ATT.  Views of the bound step's buffers: overwritten by the next batch of the same shape.
     * one bound step (outputs, workspace) per batch shape / dtype, the `max_bound_steps` most recent.
-    * 5-D video input [B,F,H,W,C]: the frames are folded into the batch for the head step, the frame logits go through
-      `cof.frame_pool_fwd` (with the TemporalAttention conv when configured) and the scores and predictions are taken
-      from the POOLED logits (nets_factory.py:354-374, then eval.py:193-197).
+    * 5-D video input [B,F,H,W,C]: the frames are folded into the batch for the head step; frame pooling (with the
+      TemporalAttention conv when configured) and the scores and predictions of the POOLED logits (nets_factory.py:
+      354-374, then eval.py:193-197) run inside the same call (`apa_attn_head_eval_step_clips` /
+      `apa_pose_attn_eval_step_clips`), as do the sigmoid scores of a multi-label configuration, flat or on clips.
+      Nothing runs behind the call: every returned tensor is a view of `ev.step`'s buffers.
     * the weights are read through the pointers a step was bound to: a parameter with a new storage binds a new step.
       No bf16 operand copy of W1 is kept here (there is no optimiser launch to keep it current): the conversion runs
       inside the call."""
@@ -1364,17 +1366,20 @@ class FusedHeadEval:
                 return 'a separate feature tap for the pose head (NET.LAST_CONV_MAP_FOR_POSE)'
         return ''
 
-    def _bind(self, X, want_pose_logits):
+    def _bind(self, X, want_pose_logits, frames=1, temporal=None):
         from .custom_ops import custom_ops_factory as cof
         h = self.head
         flags = cof.attn_flags(h.softmax_att, h.relu_att, False, self._preact)
+        # flat softmax batches: the defaults, i.e. the steps as they always were; clips and / or sigmoid scores: the
+        # *_eval_step_clips entry points (frame pooling, scores and predictions inside the call)
+        clips = dict(frames=frames, temporal=temporal, scores='sigmoid' if self.multi_label else 'softmax')
         if self.pose_form:
             return cof.PoseAttnEvalStep(
                 X, (h.pose_w1.data, h.pose_b1.data, h.pose_w2.data, h.pose_b2.data, h.att_weights.data,
                     h.att_biases.data, h.td_weights.data, h.td_biases.data), flags=flags,
-                want_pose_logits=want_pose_logits)
+                want_pose_logits=want_pose_logits, **clips)
         return cof.HeadEvalStep(X, X, h.att_weights.data, h.att_biases.data, h.td_weights.data, h.td_biases.data,
-                                flags=flags)
+                                flags=flags, **clips)
 
     def _params(self):
         h = self.head
@@ -1384,8 +1389,6 @@ class FusedHeadEval:
         return [getattr(h, n) for n in names]
 
     def __call__(self, images, labels_action=None, want_pose_logits: bool = False):
-        from . import eval_utils
-        from .custom_ops import custom_ops_factory as cof
         frames = 1
         if images.dim() == 5:                                   # nets_factory.py:121-125
             frames = images.shape[1]
@@ -1398,38 +1401,34 @@ class FusedHeadEval:
         n, hh, ww, c = last_conv.shape
         X = last_conv.detach().contiguous().view(n, -1, c)
         want_pl = bool(want_pose_logits and self.pose_form)
-        key = (tuple(X.shape), X.dtype, self._preact, want_pl, tuple(p.data_ptr() for p in self._params()))
+        tw = tb = None
+        temporal = self.network_fn.temporal if frames > 1 else None     # nets_factory.py:354-374
+        if temporal is not None:
+            if not temporal._bias_initialised:
+                with torch.no_grad():
+                    temporal['biases'].fill_(1.0 / frames)
+                temporal._bias_initialised = True
+            tw, tb = temporal['weights'].data.reshape(-1).contiguous(), temporal['biases'].data
+        key = (tuple(X.shape), X.dtype, self._preact, want_pl, tuple(p.data_ptr() for p in self._params()), frames,
+               None if tw is None else tw.data_ptr(), None if tb is None else tb.data_ptr())
         st = self._steps.pop(key, None)
         if st is None:
-            st = self._bind(X, want_pl)
+            st = self._bind(X, want_pl, frames, None if tw is None else (tw, tb))
         else:
             st.rebind(X=X) if self.pose_form else st.rebind(X)
         self._steps[key] = st                                   # most recent last
         while len(self._steps) > self.max_bound_steps:
             self._steps.popitem(last=False)
-        st.run()
+        st.run()                                                # everything returned below is a view of st's buffers
         self.step = st
         ep = {'Logits': st.logits, 'PosePrelogitsBasedAttention': st.att.view(n, hh, ww, -1)}
         if want_pl:
             ep['PoseLogits'] = st.Pl.view(n, hh, ww, -1)
         if labels_action is not None:
             ep['labels'] = labels_action.squeeze() if labels_action.dim() > 1 else labels_action   # eval.py:198
-        logits, scores, pred = st.logits, st.probs, st.pred
-        if frames > 1:                                          # nets_factory.py:354-374
-            tw = tb = None
-            temporal = self.network_fn.temporal
-            if temporal is not None:
-                if not temporal._bias_initialised:
-                    with torch.no_grad():
-                        temporal['biases'].fill_(1.0 / frames)
-                    temporal._bias_initialised = True
-                tw, tb = temporal['weights'].data.reshape(-1).contiguous(), temporal['biases'].data
+        if frames > 1:
             ep['logits_beforePool'] = st.logits
-            logits, tatt = cof.frame_pool_fwd(st.logits, frames, tw, tb)
-            if tatt is not None:
-                ep['TemporalAttention'] = tatt.view(-1, frames, 1, 1)
-            ep['Logits'] = logits
-            scores, pred = eval_utils.predict(logits, multi_label=self.multi_label)
-        elif self.multi_label:
-            scores, pred = eval_utils.predict(logits, multi_label=True)
-        return scores, pred, ep
+            ep['Logits'] = st.pooled
+            if st.tatt is not None:
+                ep['TemporalAttention'] = st.tatt.view(-1, frames, 1, 1)
+        return st.probs, st.pred, ep

@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define APA_VERSION 306 /* major*10000 + minor*100 + patch */
+#define APA_VERSION 307 /* major*10000 + minor*100 + patch */
 
 typedef enum apa_status {
   APA_OK = 0,
@@ -733,6 +733,55 @@ int apa_pose_attn_train_step_multilabel(const apa_multilabel* ml, const apa_clip
                                         const apa_pose_attn_step_io* io /* io->labels unused, may be NULL */, int N,
                                         int P, int C, int Cp, int J, int K, unsigned flags, float keep_prob,
                                         uint64_t seed, uint64_t offset, int dtype, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Evaluation of clips and of the sigmoid ("multi-label") datasets: what src/eval.py does behind the frame logits --
+ * frame pooling / temporal attention (nets_factory.py:354-374), then the scores and the prediction (eval.py:193-197)
+ * -- in ONE launch, one block per clip, and the one-call evaluation steps that end in it.
+ *   a[r]        = logits[r,:] . w + b[0]   (w == NULL: 1)                       -> tatt [B*F]
+ *   pooled[b,k] = (1/F) sum_f logits[b*F+f, k] a[b*F+f]                         -> pooled [B,K]
+ *   APA_SCORES_SOFTMAX  scores[b,:] = softmax(pooled[b,:]), pred[b] = its first maximal index; with labels int64 [B]
+ *                       loss[1+b] = -log softmax(pooled[b])[labels[b]], loss[0] = (1/B) sum_b loss[1+b]
+ *   APA_SCORES_SIGMOID  scores[b,k] = 1 / (1 + exp(-pooled[b,k])), pred[b] = first maximal index of pooled[b,:] (the
+ *                       argmax of the LOGITS, eval.py:193); labels and loss must be NULL (eval.py takes no loss)
+ * pooled and tatt carry apa_frame_pool_fwd's and apa_clip_xent_fwd_bwd's bits; the softmax scores, pred and loss carry
+ * apa_softmax_xent_fwd_bwd's on the same pooled rows (loss[0] in its summation order for (B, K)).  labels == NULL is
+ * served by the kernel: no scratch, no memset.  No workspace, no atomics, every sum in a fixed order: identical calls
+ * give identical bits.  With labels one extra block recomputes the B rows' losses for loss[0] (B clips of latency on
+ * one compute unit; clips of more than 8192 frames: APA_ERR_UNSUPPORTED with labels).
+ * Null required pointers (logits, pooled, scores, pred; b and tatt with w), non-positive sizes, B*F past 2^31, an
+ * unknown kind, labels without loss or loss without labels, either of them under APA_SCORES_SIGMOID:
+ * APA_ERR_INVALID_ARG before anything touches the GPU. */
+#define APA_SCORES_SOFTMAX 0   /* eval.py:197 */
+#define APA_SCORES_SIGMOID 1   /* eval.py:194-195, TRAIN.LOSS_FN_ACTION starts with 'multi-label' */
+
+/* frame logits f32 [B*F,K] -> pooled [B,K], tatt [B*F] (w != NULL), scores [B,K], pred int64 [B], loss [1+B] */
+int apa_clip_scores(int kind, const float* logits, const float* w, const float* b, const int64_t* labels,
+                    float* pooled, float* tatt, float* scores, int64_t* pred, float* loss, int B, int F, int K,
+                    void* stream);
+
+/* apa_attn_head_eval_step / apa_pose_attn_eval_step on a batch of CLIPS and / or with the sigmoid scores: N = B *
+ * clip->frames folded frames, logits [N,K] holds the FRAME logits (end_points['logits_beforePool']), probs [B,K]
+ * (io->probs), pred [B], labels [B], loss [1+B].  clip->pooled is required, clip->tatt exactly when clip->w is given
+ * (and clip->b with it); clip->dw / clip->db are not read.  clip == NULL: F = 1 without temporal attention -- the
+ * logits rows are the pooled rows and no `pooled` is written; with APA_SCORES_SOFTMAX that call IS
+ * apa_attn_head_eval_step (apa_pose_attn_eval_step), same launches, same bits.
+ * Otherwise the forward half runs WITHOUT the softmax that rides in (or trails) its logits reduction, and the launch
+ * of apa_clip_scores is the only one behind the logits: bit-identical to apa_attn_pool_fwd without APA_FLAG_TRAIN
+ * (the pose form: preceded by apa_pose_head_fwd, or apa_pose_attn_eval_step up to its logits -- both of its routes
+ * are kept) followed by apa_clip_scores.  Workspace: apa_attn_pool_workspace_bytes /
+ * apa_pose_attn_eval_workspace_bytes for the flat N; the scores launch needs none.  No allocation, no
+ * synchronisation, no memset: capturable like every other entry point.
+ * Refused with APA_ERR_INVALID_ARG before anything touches the GPU: what apa_clip_scores refuses, N % frames != 0,
+ * and what the flat evaluation steps refuse. */
+int apa_attn_head_eval_step_clips(const apa_clip_pool* clip /* NULL: flat */, int scores_kind, const void* X,
+                                  const void* Xatt, const float* Wa, const float* ba, const float* Wt,
+                                  const float* bt, const int64_t* labels, float* logits, float* att, float* zsave,
+                                  float* abar, float* loss, float* probs, int64_t* pred, void* ws, size_t ws_bytes,
+                                  int N, int P, int C, int Ca, int K, int M, unsigned flags, int dtype, void* stream);
+int apa_pose_attn_eval_step_clips(const apa_clip_pool* clip /* NULL: flat */, int scores_kind,
+                                  const apa_pose_attn_eval_io* io, int N, int P, int C, int Cp, int J, int K,
+                                  unsigned flags, int dtype, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * ..._WITH_POSE_FEAT (nets_factory.py:289-295): `last_conv = tf.concat([last_conv, pose_logits], -1)`

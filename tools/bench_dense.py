@@ -32,6 +32,15 @@ headline stays the cfg 002 training workload); run this file directly for one wo
             K = 393, HMDB-51 per-class bf16 K = 51), alternating in one process, medians of five; frozen002 also
             prints the HIP-event times of the two M == 1 streaming kernels for both forms.
 
+  eval_video_perclass / eval_video002 / eval_hico002 / eval_charades_clips
+            the evaluation step of the clip and multi-label datasets: HMDB-51's test protocol (4 clips x 25 frames x
+            14x14x2048 bf16, K = 51, per-class maps), 8 x 4 frames fp32 K = 51 M = 1 with temporal attention, HICO (32
+            images bf16, K = 600, sigmoid scores) and Charades (8 x 4 frames bf16, K = 157, temporal attention, sigmoid
+            scores).  Two variants alternate in one process, medians of five: `one_call`
+            (apa_attn_head_eval_step_clips: frame pooling, scores and predictions inside the call) and `sequence`, the
+            calls deploy.FusedHeadEval made before that entry point existed (HeadEvalStep.run, cof.frame_pool_fwd,
+            eval_utils.predict).
+
 Each builder returns (step_fn, info): `step_fn()` enqueues one step on the current stream; `info`
 carries the workload name and the algorithmic work per image.
 """
@@ -585,6 +594,91 @@ def run_eval003(cof, dev, args):
     return out
 
 
+EVAL_CLIPS = {   # clips, frames, dtype, K, per-class maps, temporal attention, multi-label (sigmoid) scores
+    'eval_video_perclass': dict(B=4, F=25, dtype='bf16', K=51, per_class=True, temporal=False, multi_label=False),
+    'eval_video002': dict(B=8, F=4, dtype='f32', K=51, per_class=False, temporal=True, multi_label=False),
+    'eval_hico002': dict(B=32, F=1, dtype='bf16', K=600, per_class=False, temporal=False, multi_label=True),
+    'eval_charades_clips': dict(B=8, F=4, dtype='bf16', K=157, per_class=False, temporal=True, multi_label=True),
+}
+
+
+def build_eval_clips(cof, dev, which, H=14, rotate=0):
+    """The evaluation step of a clip / multi-label dataset, {'one_call', 'sequence'} as round-robin step functions over
+    the same rotating X sets:
+      'one_call'  cof.HeadEvalStep(frames=, temporal=, scores=): apa_attn_head_eval_step_clips
+      'sequence'  what deploy.FusedHeadEval ran before that entry point: the flat HeadEvalStep (its softmax / argmax over
+                  the frame logits are not read), cof.frame_pool_fwd on clips, then eval_utils.predict on the (pooled)
+                  logits -- for clips and for the sigmoid scores; its tensors are allocated per call, as they were."""
+    from attentionalpoolingaction_amd import eval_utils
+    w = EVAL_CLIPS[which]
+    B, F, K, C, P = w['B'], w['F'], w['K'], 2048, H * H
+    N, M = B * F, (w['K'] if w['per_class'] else 1)
+    td = torch.bfloat16 if w['dtype'] == 'bf16' else torch.float32
+    g = torch.Generator().manual_seed(42)
+    Wa = (torch.randn(C, M, generator=g) / C ** 0.5).to(dev); ba = torch.zeros(M, device=dev)
+    Wt = (torch.randn(C, K, generator=g) / C ** 0.5).to(dev); bt = torch.zeros(K, device=dev)
+    temporal = _clip_kwargs(dev, K, F, True)['temporal'] if w['temporal'] else None
+    tw, tb = temporal if temporal else (None, None)
+    per_set = N * P * C * (2 if w['dtype'] == 'bf16' else 4)          # forward only: X is all that streams
+    R = _n_sets(per_set, rotate)
+    Xs = [_features(N, P, C, td, dev, seed=42 + r) for r in range(R)]
+    one, seq = [], []
+    for Xr in Xs:
+        one.append(cof.HeadEvalStep(Xr, Xr, Wa, ba, Wt, bt, frames=F, temporal=temporal,
+                                    scores='sigmoid' if w['multi_label'] else 'softmax',
+                                    workspace=one[0].workspace if one else None))
+        seq.append(cof.HeadEvalStep(Xr, Xr, Wa, ba, Wt, bt, workspace=seq[0].workspace if seq else None))
+
+    def seq_run(r):
+        st = seq[r]
+        st.run()
+        logits = st.logits
+        if F > 1:
+            logits, _ = cof.frame_pool_fwd(st.logits, F, tw, tb)
+        return eval_utils.predict(logits, multi_label=w['multi_label'])
+
+    steps = {'one_call': _round_robin([st.run for st in one]),
+             'sequence': _round_robin([(lambda r=r: seq_run(r)) for r in range(R)])}
+    info = {'workload': '{}: evaluation step, {} x {} frames x {}x{}x{} {}, K={}, {}, {}, {} scores; one call '
+                        '(apa_attn_head_eval_step_clips) against HeadEvalStep.run + frame_pool_fwd + eval_utils.predict'
+                        .format(which, B, F, H, H, C, w['dtype'], K, 'per-class maps' if w['per_class'] else 'M = 1',
+                                'temporal attention' if w['temporal'] else 'plain mean over the frames',
+                                'sigmoid' if w['multi_label'] else 'softmax') +
+                        _rot_note(R, per_set).replace('X/dX', 'X'),
+            'dtype': w['dtype'], 'N': N, 'rotate': R, 'entry': one[0]._name}
+    return steps, info
+
+
+def run_eval_clips(cof, dev, args, which):
+    """The two variants ALTERNATING in one process: five timed loops of each, interleaved; medians, and per variant the
+    spread (max - min) of its five loops.  --only: one variant alone (kernel traces); `steps_run` is then the number of
+    steps behind the trace's call counts."""
+    steps, info = build_eval_clips(cof, dev, which, args.hw, args.rotate)
+    if args.only:
+        steps = {args.only: steps[args.only]}
+    warm = max(args.warmup, info['rotate'])
+    for fn in steps.values():
+        for _ in range(warm):
+            fn()
+    torch.cuda.synchronize()
+    runs = {k: [] for k in steps}
+    for _ in range(5):
+        for name, fn in steps.items():
+            sec, _ = timed(fn, args.steps, 0, min_ms=0.0, repeats=1)
+            runs[name].append(sec * 1e6)
+    med = {k: sorted(v)[len(v) // 2] for k, v in runs.items()}
+    out = {'workload': info['workload'], 'entry': info['entry'], 'dtype': info['dtype'], 'rotate': info['rotate'],
+           'us_per_step': {k: round(v, 2) for k, v in med.items()},
+           'us_per_step_runs': {k: [round(x, 2) for x in v] for k, v in runs.items()},
+           'us_per_step_spread': {k: round(max(v) - min(v), 2) for k, v in runs.items()},
+           'steps_run': warm + 5 * args.steps}
+    if 'one_call' in med and 'sequence' in med:
+        out['one_call_minus_sequence_us'] = round(med['one_call'] - med['sequence'], 2)
+        out['one_call_within_sequence_spread'] = bool(
+            med['one_call'] - med['sequence'] <= max(runs['sequence']) - min(runs['sequence']))
+    return out
+
+
 def build_video(cof, dev, which, B=8, F=4, H=14, K=51, rotate=0):
     """A clip batch [B,F,H,H,2048] bf16 with temporal attention, `which` in ('perclass', 'cfg003'):
       'clip_one_call'  the one-call clip step (build_perclass / build_cfg003 with frames=F)
@@ -897,12 +991,13 @@ def main():
     ap.add_argument('--workload', default='cfg003', choices=['cfg003', 'perclass', 'eval002', 'eval003', 'rank1', 'posebwd', 'posebwd_acc', 'update003',
                                                          'update_perclass', 'poseatt', 'video_perclass', 'video003',
                                                          'hico002', 'charades_clips', 'frozen002', 'frozen003',
-                                                         'frozen_perclass'])
+                                                         'frozen_perclass'] + sorted(EVAL_CLIPS))
     ap.add_argument('--clips', type=int, default=8, help='video_*: clips per batch')
     ap.add_argument('--frames', type=int, default=4, help='video_*: frames per clip')
     ap.add_argument('--only', default=None, choices=['clip_one_call', 'module_path', 'flat_one_call',
-                                                     'multilabel_one_call', 'softmax_one_call'],
-                    help='video_* / hico002 / charades_clips: run one variant alone (kernel traces)')
+                                                     'multilabel_one_call', 'softmax_one_call', 'one_call',
+                                                     'sequence'],
+                    help='video_* / hico002 / charades_clips / eval_*: run one variant alone (kernel traces)')
     ap.add_argument('--batch', type=int, default=32)
     ap.add_argument('--hw', type=int, default=14)
     ap.add_argument('--classes', type=int, default=None)
@@ -933,6 +1028,9 @@ def main():
         return
     if args.workload in ('hico002', 'charades_clips'):
         print(json.dumps(run_multilabel(cof, dev, args, args.workload)))
+        return
+    if args.workload in EVAL_CLIPS:
+        print(json.dumps(run_eval_clips(cof, dev, args, args.workload)))
         return
     if args.workload.startswith('frozen'):
         print(json.dumps(run_frozen(cof, dev, args, args.workload)))
