@@ -339,8 +339,8 @@ struct StepLoss {
   float* G = nullptr;      // [N,K]: the gradient at the (frame) logits
 };
 
-// a valid apa_multilabel, or the refusal (nothing has touched the GPU)
-static int check_multilabel(const char* fn, const apa_multilabel* ml) {
+// a valid apa_multilabel, or the refusal (nothing has touched the GPU); apa_internal.h: the stand-alone losses call it too
+int apa::check_multilabel(const char* fn, const apa_multilabel* ml) {
   if (!ml || !ml->labels) {
     set_error("%s: null apa_multilabel / labels pointer", fn);
     return APA_ERR_INVALID_ARG;

@@ -21,11 +21,10 @@
 //                                  (temporal attention only)
 //
 // Which K takes which code:
-//   4 <= K <= 1024   the cross-entropy is pc_row_xent_any (apa_device.h): softmax_xent_kernel<NV4>'s arithmetic on
-//                    the pooled row in LDS -- half-wave trees, exp_fast -- and loss[0] is summed in that kernel's
-//                    order (B <= 64: 32 slots; else sum_scale_kernel's)
-//   K < 4, K > 1024  softmax_xent_stream_kernel's arithmetic (one wave, three passes, expf), loss[0] in
-//                    sum_scale_kernel's order
+//   4 <= K <= 1024   the cross-entropy is pc_row_xent_any (apa_xent_row.h): softmax_xent_kernel<NV4>'s row routine in
+//                    its three-pass form, on the pooled row in LDS
+//   K < 4, K > 1024  xent_row_stream, softmax_xent_stream_kernel's row routine (one wave, three passes, expf)
+//   loss[0]          the order xent_mean_slots32(B, K) picks, as there
 //   K <= 4096        the pooled row and the gradient row live in LDS (32 KB at most)
 //   K >  4096        they live in memory: the pooled row in its output, the gradient row in the workspace
 // so that with F == 1 and no temporal attention (pooled = x * 1, G = g * 1) loss and G carry the very bits
@@ -73,107 +72,52 @@ __global__ __launch_bounds__(256) void clip_xent_kernel(
                               grow, K, kind, pw, gscale, sx);
     if (threadIdx.x == 0) loss[1 + b] = s;
   } else if (wave == 0) {   // the pooled row's cross-entropy: loss[1+b] and the gradient row
-    if (K >= 4 && K <= 1024) {
+    if (xent_row_half_wave(K)) {
       // a one-row problem for the shared row routine: row 0 of (labels + b, sx, grow)
       const PcXent xe = {labels + b, sx, grow, gscale};
       pc_row_xent_any(prow, 0, K, xe, true, grow);
       if (lane == 0) loss[1 + b] = sx[1];
-    } else {         // softmax_xent_stream_kernel's arithmetic
-      const int lab = (int)labels[b];
-      float m = -INFINITY, xl = 0.f;
-      for (int k = lane; k < K; k += 64) {
-        const float v = prow[k];
-        if (v > m) m = v;
-        if (k == lab) xl = v;
-      }
-      const float mw = wave_max(m);
-      xl = wave_sum(xl);
-      float l = 0.f;
-      for (int k = lane; k < K; k += 64) l += expf(prow[k] - mw);
-      l = wave_sum(l);
-      const float inv = 1.0f / l;
-      // (that kernel also stores p as a probability, so its p - onehot is a subtraction of the ROUNDED product; here p
-      // has one use and the compiler would contract the two into an fma: contraction off for this loop)
-      for (int k = lane; k < K; k += 64) {
-#pragma clang fp contract(off)
-        const float p = expf(prow[k] - mw) * inv;
-        grow[k] = (p - (k == lab ? 1.0f : 0.0f)) * gscale;
-      }
-      if (lane == 0) loss[1 + b] = (lab >= 0 && lab < K) ? -(xl - mw - logf(l)) : 0.f;
+    } else {
+      const float lv =
+          xent_row_stream([&](int k) { return prow[k]; }, K, (int)labels[b], false, nullptr, true, grow, gscale, nullptr);
+      if (lane == 0) loss[1 + b] = lv;
     }
   }
   __syncthreads();
 
   // the gradient at the frame logits, one wave per frame row
-  for (int f = wave; f < F; f += 4) {
-    const size_t r = rb + f;
-    if (!TEMPORAL) {
-      for (int k = lane; k < K; k += 64) G[r * K + k] = grow[k] * invF;
-    } else {
-      const float* xr = x + r * K;
-      float acc = 0.f;
-      for (int k = lane; k < K; k += 64) acc = fmaf(grow[k], xr[k], acc);
-      const float d = wave_sum(acc) * invF;
-      const float a = ap[f];
-      for (int k = lane; k < K; k += 64) G[r * K + k] = fmaf(grow[k] * invF, a, d * w[k]);
-      if (lane == 0) dws[r] = d;
-    }
-  }
+  for (int f = wave; f < F; f += 4)
+    clip_grad_row<TEMPORAL>(x, w, grow, TEMPORAL ? ap + f : nullptr, G, dws, rb + f, K, invF, lane);
 }
 
-// sum of v[0 .. n) by one 256-thread block in sum_scale_kernel's order (apa_loss.hip); the result is valid in thread 0
-__device__ __forceinline__ float clip_block_sum(const float* __restrict__ v, int n, float* red) {
-  float acc = 0.f;
-  for (int i = threadIdx.x; i < n; i += 256) acc += v[i];
-  acc = wave_sum(acc);
-  __syncthreads();   // (red may still be read from a previous sum)
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
-  __syncthreads();
-  return (red[0] + red[1]) + (red[2] + red[3]);
-}
-
-// block 0: loss[0] (in apa_softmax_xent_fwd_bwd's summation order for this (B, K)) and db0; block 1 + j: dw[256 j ..]
+// block 0: loss[0] (in apa_softmax_xent_fwd_bwd's summation order for this (B, K), apa_xent_row.h) and db0; block 1 + j:
+// dw[256 j ..]
 __global__ __launch_bounds__(256) void clip_finish_kernel(const float* __restrict__ x, const float* __restrict__ dws,
                                                           float* __restrict__ loss, float* __restrict__ dw,
                                                           float* __restrict__ db, int B, int rows, int K,
                                                           float lscale) {
-  __shared__ float red[4];
+  __shared__ float red[32];
   if (blockIdx.x == 0) {
-    if (K >= 4 && K <= 1024 && B <= 64) {
-      // softmax_xent_kernel modes 1 / 2: slot n mod 32 adds its rows in increasing n, the slots are added in order
-      if (threadIdx.x == 0) {
-        float t = 0.f;
-        for (int s = 0; s < 32; ++s) {
-          float sl = 0.f;
-          if (s < B) sl += loss[1 + s];
-          if (s + 32 < B) sl += loss[1 + s + 32];
-          t += sl;
-        }
-        loss[0] = t * lscale;
+    if (xent_mean_slots32(B, K)) {
+      if (threadIdx.x < 64) {
+        const int lane = threadIdx.x;
+        const float t = xent_mean32_finish(xent_mean32_load(loss + 1, B, lane), red, lane);
+        if (lane == 0) loss[0] = t * lscale;
       }
     } else {
-      const float t = clip_block_sum(loss + 1, B, red);
+      const float t = block_sum256(xent_mean256_load(loss + 1, B), red);
       if (threadIdx.x == 0) loss[0] = t * lscale;
     }
-    if (dws) {
-      const float s = clip_block_sum(dws, rows, red);
+    if (dws) {   // db0 in the 256-thread order
+      __syncthreads();   // (red is still read by the loss sum)
+      const float s = block_sum256(xent_mean256_load(dws, rows), red);
       if (threadIdx.x == 0) db[0] = s;
     }
     return;
   }
   const int k = (blockIdx.x - 1) * 256 + threadIdx.x;
   if (k >= K) return;
-  float acc = 0.f;
-  int r = 0;
-  for (; r + 8 <= rows; r += 8) {   // eight loads in flight, added in row order
-    float xv[8], dv[8];
-#pragma unroll
-    for (int u = 0; u < 8; ++u) { xv[u] = x[(size_t)(r + u) * K + k]; dv[u] = dws[r + u]; }
-#pragma unroll
-    for (int u = 0; u < 8; ++u) acc = fmaf(dv[u], xv[u], acc);
-  }
-  for (; r < rows; ++r) acc = fmaf(dws[r], x[(size_t)r * K + k], acc);
-  dw[k] = acc;
+  dw[k] = clip_dw_col(x, dws, rows, K, k);
 }
 
 // d [B*F] (temporal attention) | gradient rows [B, K] (K > CLIP_LDS_K), in floats
@@ -257,14 +201,8 @@ extern "C" int apa_clip_multilabel_fwd_bwd(const apa_multilabel* ml, const float
                                            const float* b, float* pooled, float* tatt, float* loss, float* G,
                                            float* dw, float* db, void* ws, size_t ws_bytes, int B, int F, int K,
                                            float wt, float grad_scale, void* stream) {
-  if (!ml || !ml->labels) {
-    set_error("apa_clip_multilabel_fwd_bwd: null apa_multilabel / labels pointer");
-    return APA_ERR_INVALID_ARG;
-  }
-  if (ml->kind != APA_ACTION_LOSS_MULTI_LABEL && ml->kind != APA_ACTION_LOSS_MULTI_LABEL_2) {
-    set_error("apa_clip_multilabel_fwd_bwd: unknown loss kind %d", ml->kind);
-    return APA_ERR_INVALID_ARG;
-  }
+  const int rc = check_multilabel("apa_clip_multilabel_fwd_bwd", ml);
+  if (rc != APA_OK) return rc;
   return clip_loss_launch("apa_clip_multilabel_fwd_bwd", ml, logits, ml->labels, w, b, pooled, tatt, loss, G, dw, db,
                           ws, ws_bytes, B, F, K, wt, grad_scale, stream);
 }

@@ -12,8 +12,9 @@
 // or, for the sigmoid scores, the tensor expressions of eval_utils.predict.  One 4-wave block per clip: a[] and the
 // pooled row stay on the CU.  a[] and pooled come from the stages clip_xent_kernel runs (apa_clip_stages.h), so they
 // carry apa_clip_xent_fwd_bwd's and apa_frame_pool_fwd's bits; the softmax row carries apa_softmax_xent_fwd_bwd's:
-//   4 <= K <= 1024   pc_row_softmax_any (apa_device.h): softmax_xent_kernel<NV4>'s arithmetic on the row in LDS
-//   K < 4, K > 1024  softmax_xent_stream_kernel's arithmetic (one wave, three passes, expf)
+//   4 <= K <= 1024   pc_row_softmax_any (apa_xent_row.h): softmax_xent_kernel<NV4>'s row routine in its three-pass
+//                    form, on the row in LDS
+//   K < 4, K > 1024  xent_row_stream, softmax_xent_stream_kernel's row routine (one wave, three passes, expf)
 //   K <= 4096        the pooled row lives in LDS; beyond that in its output
 //   F <= 64          a[b, :] lives in LDS; beyond that it is re-read from tatt
 // loss[0] needs every clip and a launch has no order between its blocks, so with labels ONE MORE block walks all B
@@ -34,31 +35,6 @@ namespace apa {
 
 constexpr int CLIP_SCORES_MAX_F_LABELS = 8192;   // the loss block keeps a[b, :] in LDS (32 KB)
 
-// softmax_xent_stream_kernel's arithmetic (apa_loss.hip) on one row by ONE wave; P(k): the row's k-th value.  probs ==
-// nullptr: only *lv.  *lv and *cand are wave-uniform.
-template <typename PF>
-__device__ __forceinline__ void clip_row_softmax_stream(PF&& P, int K, int lab, float* __restrict__ probs, float* lv,
-                                                        int* cand) {
-  const int lane = threadIdx.x & 63;
-  float m = -INFINITY, xl = 0.f;
-  int arg = 0x7fffffff;
-  for (int k = lane; k < K; k += 64) {
-    const float v = P(k);
-    if (v > m) { m = v; arg = k; }
-    if (k == lab) xl = v;
-  }
-  const float mw = wave_max(m);
-  *cand = wave_min_i((m == mw) ? arg : 0x7fffffff);
-  xl = wave_sum(xl);
-  float l = 0.f;
-  for (int k = lane; k < K; k += 64) l += expf(P(k) - mw);
-  l = wave_sum(l);
-  const float inv = 1.0f / l;
-  if (probs)
-    for (int k = lane; k < K; k += 64) probs[k] = expf(P(k) - mw) * inv;
-  *lv = (lab >= 0 && lab < K) ? -(xl - mw - logf(l)) : 0.f;
-}
-
 // dynamic LDS: [row_floats] pooled row | [4] scratch | [32] loss slots | [CLIP_LDS_F, or F with labels] a
 // grid: B blocks, one per clip (+ 1 with labels: the loss block).  pooled == nullptr: F == 1 without attention, the
 // logits rows are the pooled rows.
@@ -75,8 +51,8 @@ __global__ __launch_bounds__(256) void clip_scores_kernel(
   float* slot = sx + 4;
   float* sa = slot + 32;
   const bool loss_block = (int)blockIdx.x == B;
-  const bool row_routine = K >= 4 && K <= 1024;
-  const bool slots32 = row_routine && B <= 64;
+  const bool row_routine = xent_row_half_wave(K);
+  const bool slots32 = xent_mean_slots32(B, K);
   float own = 0.f;   // loss block: this thread's share of loss[0]
   const int b_lo = loss_block ? 0 : blockIdx.x, b_hi = loss_block ? B : blockIdx.x + 1;
 
@@ -133,10 +109,10 @@ __global__ __launch_bounds__(256) void clip_scores_kernel(
         if (row_routine) {   // (K <= 1024 < CLIP_LDS_K: the row is in LDS)
           pc_row_softmax_any(prow, K, lab, prb, &lv, &cand);
         } else if (prow) {
-          clip_row_softmax_stream([&](int k) { return prow[k]; }, K, lab, prb, &lv, &cand);
+          lv = xent_row_stream([&](int k) { return prow[k]; }, K, lab, !loss_block, prb, false, nullptr, 0.f, &cand);
         } else {
-          clip_row_softmax_stream([&](int k) { return clip_pool_col<TEMPORAL>(x + rb * K + k, ap, F, K); }, K, lab,
-                                  prb, &lv, &cand);
+          lv = xent_row_stream([&](int k) { return clip_pool_col<TEMPORAL>(x + rb * K + k, ap, F, K); }, K, lab,
+                               !loss_block, prb, false, nullptr, 0.f, &cand);
         }
         if (lane == 0) {
           if (loss_block) {
@@ -154,20 +130,17 @@ __global__ __launch_bounds__(256) void clip_scores_kernel(
     }
   }
 
+  // loss[0]: the thread's share is its slot's sum (32-slot order) or its strided sum (256-thread order); the finish is
+  // apa_xent_row.h's
   if (!SIGMOID && loss_block) {
     if (slots32) {
-      if (threadIdx.x < 32) slot[threadIdx.x] = own;
-      __syncthreads();
-      if (threadIdx.x == 0) {
-        float t = 0.f;
-        for (int s = 0; s < 32; ++s) t += slot[s];
-        loss[0] = t * lscale;
+      if (wave == 0) {
+        const float t = xent_mean32_slots(own, slot, lane);
+        if (lane == 0) loss[0] = t * lscale;
       }
     } else {
-      const float ws = wave_sum(own);
-      if (lane == 0) slot[wave] = ws;
-      __syncthreads();
-      if (threadIdx.x == 0) loss[0] = ((slot[0] + slot[1]) + (slot[2] + slot[3])) * lscale;
+      const float t = block_sum256(own, slot);
+      if (threadIdx.x == 0) loss[0] = t * lscale;
     }
   }
 }

@@ -259,6 +259,14 @@ __device__ __forceinline__ int half_min_first(int v, int lane) {
   return lane < 32 ? s0 : s1;
 }
 
+}  // namespace apa
+
+// the softmax cross-entropy row routines and the batch mean, on the helpers above (colsum_block below finishes a
+// folded loss with them)
+#include "apa_xent_row.h"
+
+namespace apa {
+
 // ---------------------------------------------------------------------------------------------
 // Fixed-order column sums of a matrix of per-block partial rows (apa_m1_small.hip: m1_colsum_kernel)
 // ---------------------------------------------------------------------------------------------
@@ -330,30 +338,19 @@ __device__ __forceinline__ void colsum_block(int bid, int nbid, const ColsumArgs
   if (x.aux_src && bid == nbid - 1) {
     __syncthreads();
     if (x.aux_n < 0) {
-      // the batch mean of per-example losses in apa_softmax_xent_fwd_bwd's own summation order, so that a
-      // cross-entropy folded into another kernel leaves a bit-identical loss[0]:
-      //   N <= 64 (softmax_xent_kernel modes 1 / 2): slot w = n mod 32 adds its rows in increasing n, the slots
-      //   are added in order;  N > 64 (sum_scale_kernel): 256 strided threads, wave sums, (r0 + r1) + (r2 + r3)
+      // the batch mean of per-example losses in apa_softmax_xent_fwd_bwd's own summation order (apa_xent_row.h), so
+      // that a cross-entropy folded into another kernel leaves a bit-identical loss[0].  (The folds that end here
+      // serve 4 <= K <= 1024 only: N alone picks the order.)
       const int N = -x.aux_n;
-      if (N <= 64) {
-        if (threadIdx.x == 0) {
-          float t = 0.f;
-          for (int w = 0; w < 32; ++w) {
-            float sl = 0.f;
-            if (w < N) sl += x.aux_src[w];
-            if (w + 32 < N) sl += x.aux_src[w + 32];
-            t += sl;
-          }
-          x.aux_dst[0] = t * x.aux_scale;
+      if (xent_mean_slots32(N, XENT_ROW_MIN_K)) {
+        if (threadIdx.x < 64) {
+          const int lane = threadIdx.x;
+          const float t = xent_mean32_finish(xent_mean32_load(x.aux_src, N, lane), red[1], lane);
+          if (lane == 0) x.aux_dst[0] = t * x.aux_scale;
         }
       } else {
-        float a = 0.f;
-        if (threadIdx.x < 256)
-          for (int i = threadIdx.x; i < N; i += 256) a += x.aux_src[i];
-        a = wave_sum(a);
-        if ((threadIdx.x & 63) == 0 && threadIdx.x < 256) red[1][threadIdx.x >> 6] = a;
-        __syncthreads();
-        if (threadIdx.x == 0) x.aux_dst[0] = ((red[1][0] + red[1][1]) + (red[1][2] + red[1][3])) * x.aux_scale;
+        const float t = block_sum256(xent_mean256_load(x.aux_src, N), red[1]);
+        if (threadIdx.x == 0) x.aux_dst[0] = t * x.aux_scale;
       }
     } else {
       float a = 0.f;
@@ -390,171 +387,6 @@ __device__ __forceinline__ float pc_logit_from_partials(const float* __restrict_
     for (int j = 0; j < 8; ++j) s += v[j];
   }
   return s / (float)P;
-}
-
-// softmax_xent_kernel<1>'s arithmetic to the letter (apa_loss.hip), so that a folded loss and its gradient are
-// BIT-identical to the separate launch: half a wave owns the row (both halves run the same row here), lane hl holds
-// the 4 columns colc .. colc + 3, the ragged last vector is shifted back and its already-covered columns masked out;
-// half-wave max / sum trees, exp_fast, fmaf(p, gscale, -gscale).  Called by ONE whole wave; lrow = the logits row in
-// LDS (4 <= K <= 64).  write: G[n, :] and loss[1 + n] go to memory; grow (optional, LDS): the gradient row for the
-// caller's own use.
-struct PcXent { const int64_t* labels; float* loss; float* G; float gscale; };
-__device__ __forceinline__ void pc_row_xent(const float* lrow, int n, int K, const PcXent& xe, bool write, float* grow) {
-  const int lane = threadIdx.x & 63, hl = lane & 31;
-  const int lab = (int)xe.labels[n];
-  const bool lab_ok = lab >= 0 && lab < K;
-  const int col0 = 4 * hl, colc = min(col0, K - 4);
-  float v[4];
-#pragma unroll
-  for (int e = 0; e < 4; ++e) v[e] = colc + e >= col0 ? lrow[colc + e] : -INFINITY;
-  const float xl = lrow[lab_ok ? lab : 0];
-  float m = -INFINITY;
-#pragma unroll
-  for (int e = 0; e < 4; ++e)
-    if (v[e] > m) m = v[e];
-  const float mw = half_max(m, lane);
-  float l = 0.f;
-#pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    v[e] = exp_fast(v[e] - mw);
-    l += v[e];
-  }
-  l = half_sum(l, lane);
-  const float inv = 1.0f / l;
-  const float lv = lab_ok ? -(xl - mw - logf(l)) : 0.f;
-  if (lane < 32) {
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const int c = colc + e;
-      if (c >= col0 && c < K) {
-        const float gv = fmaf(v[e] * inv, xe.gscale, c == lab ? -xe.gscale : 0.f);
-        if (write) xe.G[(size_t)n * K + c] = gv;
-        if (grow) grow[c] = gv;
-      }
-    }
-    if (hl == 0 && write) xe.loss[1 + n] = lv;
-  }
-}
-
-// The same for any 4 <= K <= 1024: softmax_xent_kernel<NV4>'s arithmetic (apa_loss.hip) on one row that lies in global
-// memory -- NV4 = 16-byte vectors per lane of the half wave; ONE whole wave calls it, both halves run the same row.
-// Three passes that re-read the row (cache hits) instead of holding 4 * NV4 values per lane: the caller is a 16-wave
-// block whose occupancy 100+ registers would halve (pc_bwd_act_kernel went 7.4 -> 14.4 us with the register form).
-// The operation order per lane -- vectors in increasing i, elements in increasing e, then the half-wave trees -- is
-// the kernel's, so the results are bit-identical.
-// grow (LDS, >= K floats) receives the gradient row; write: G[n, :] and loss[1 + n] also go to memory.
-__device__ __forceinline__ void pc_row_xent_any(const float* __restrict__ row, int n, int K, const PcXent& xe, bool write,
-                                                float* grow) {
-  typedef float f4u __attribute__((ext_vector_type(4), aligned(4)));
-  const int nv4 = K <= 128 ? 1 : (K <= 256 ? 2 : (K <= 512 ? 4 : 8));
-  const int lane = threadIdx.x & 63, hl = lane & 31;
-  const int lab = (int)xe.labels[n];
-  const bool lab_ok = lab >= 0 && lab < K;
-  const float xl = row[lab_ok ? lab : 0];
-  auto vec = [&](int i, int& colc) {       // this lane's i-th vector, columns the previous lane covers masked out
-    const int col0 = 4 * (hl + 32 * i);
-    colc = min(col0, K - 4);
-    f4u v = *reinterpret_cast<const f4u*>(row + colc);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) v[e] = colc + e >= col0 ? v[e] : -INFINITY;
-    return v;
-  };
-  float m = -INFINITY;
-#pragma unroll 1
-  for (int i = 0; i < nv4; ++i) {
-    int colc;
-    const f4u v = vec(i, colc);
-#pragma unroll
-    for (int e = 0; e < 4; ++e)
-      if (v[e] > m) m = v[e];
-  }
-  const float mw = half_max(m, lane);
-  float l = 0.f;
-#pragma unroll 1
-  for (int i = 0; i < nv4; ++i) {
-    int colc;
-    const f4u v = vec(i, colc);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) l += exp_fast(v[e] - mw);
-  }
-  l = half_sum(l, lane);
-  const float inv = 1.0f / l;
-  const float lv = lab_ok ? -(xl - mw - logf(l)) : 0.f;
-  if (lane < 32) {
-#pragma unroll 1
-    for (int i = 0; i < nv4; ++i) {
-      int colc;
-      const f4u v = vec(i, colc);
-      const int col0 = 4 * (hl + 32 * i);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const int c = colc + e;
-        if (c >= col0 && c < K) {
-          const float gv = fmaf(exp_fast(v[e] - mw) * inv, xe.gscale, c == lab ? -xe.gscale : 0.f);
-          if (write) xe.G[(size_t)n * K + c] = gv;
-          grow[c] = gv;
-        }
-      }
-    }
-    if (hl == 0 && write) xe.loss[1 + n] = lv;
-  }
-}
-
-// The forward-only sibling (apa_clipscores.hip): the same kernel's probabilities, first maximal index and row loss for
-// one row of 4 <= K <= 1024, in the same three passes and the same operation order per lane, so the bits are
-// apa_softmax_xent_fwd_bwd's.  ONE whole wave calls it; lab < 0 (no ground truth): *lv = 0.  probs: K floats of the
-// row's output, or nullptr.  *lv and *cand are valid in every lane.
-__device__ __forceinline__ void pc_row_softmax_any(const float* __restrict__ row, int K, int lab,
-                                                   float* __restrict__ probs, float* lv, int* cand) {
-  typedef float f4u __attribute__((ext_vector_type(4), aligned(4)));
-  const int nv4 = K <= 128 ? 1 : (K <= 256 ? 2 : (K <= 512 ? 4 : 8));
-  const int lane = threadIdx.x & 63, hl = lane & 31;
-  const bool lab_ok = lab >= 0 && lab < K;
-  const float xl = row[lab_ok ? lab : 0];
-  auto vec = [&](int i, int& colc) {       // this lane's i-th vector, columns the previous lane covers masked out
-    const int col0 = 4 * (hl + 32 * i);
-    colc = min(col0, K - 4);
-    f4u v = *reinterpret_cast<const f4u*>(row + colc);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) v[e] = colc + e >= col0 ? v[e] : -INFINITY;
-    return v;
-  };
-  float m = -INFINITY;
-  int arg = 0x7fffffff;
-#pragma unroll 1
-  for (int i = 0; i < nv4; ++i) {
-    int colc;
-    const f4u v = vec(i, colc);
-#pragma unroll
-    for (int e = 0; e < 4; ++e)
-      if (v[e] > m) { m = v[e]; arg = colc + e; }   // first maximal index of this lane
-  }
-  const float mw = half_max(m, lane);
-  *cand = half_min_first((m == mw) ? arg : 0x7fffffff, lane);
-  float l = 0.f;
-#pragma unroll 1
-  for (int i = 0; i < nv4; ++i) {
-    int colc;
-    const f4u v = vec(i, colc);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) l += exp_fast(v[e] - mw);
-  }
-  l = half_sum(l, lane);
-  const float inv = 1.0f / l;
-  *lv = lab_ok ? -(xl - mw - logf(l)) : 0.f;
-  if (probs && lane < 32) {
-#pragma unroll 1
-    for (int i = 0; i < nv4; ++i) {
-      int colc;
-      const f4u v = vec(i, colc);
-      const int col0 = 4 * (hl + 32 * i);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const int c = colc + e;
-        if (c >= col0 && c < K) probs[c] = exp_fast(v[e] - mw) * inv;
-      }
-    }
-  }
 }
 
 // (apa_m1_small.hip's reducers and apa_mlloss.hip's share these)

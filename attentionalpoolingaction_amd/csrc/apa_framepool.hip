@@ -5,12 +5,13 @@
 //   temporal   : a[b,f] = x[b,f,:] . w + b0   (1x1 conv K->1, bias init 1/F)   (:362-372)
 //                pooled = mean_f ( x * a )
 // and its backward.  Tiny tensors ([B*F, K] with F <= 25): one wave per frame row.
+#include "apa_clip_stages.h"
 #include "apa_device.h"
 #include "apa_internal.h"
 
 namespace apa {
 
-// tatt[row] = x[row,:] . w + b0     (one wave per row)
+// tatt[row] = x[row,:] . w + b0     (one wave per row: clip_tatt_row)
 __global__ __launch_bounds__(256) void fp_att_kernel(const float* __restrict__ x,
                                                      const float* __restrict__ w,
                                                      const float* __restrict__ b0,
@@ -18,13 +19,11 @@ __global__ __launch_bounds__(256) void fp_att_kernel(const float* __restrict__ x
   const int lane = threadIdx.x & 63;
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= rows) return;
-  float acc = 0.f;
-  for (int k = lane; k < K; k += 64) acc = fmaf(x[(size_t)row * K + k], w[k], acc);
-  acc = wave_sum(acc);
-  if (lane == 0) tatt[row] = acc + b0[0];
+  const float a = clip_tatt_row(x + (size_t)row * K, w, b0, K, lane);
+  if (lane == 0) tatt[row] = a;
 }
 
-// pooled[b,k] = (1/F) sum_f x[b,f,k] * (tatt ? tatt[b,f] : 1)
+// pooled[b,k] = (1/F) sum_f x[b,f,k] * (tatt ? tatt[b,f] : 1)   (its own loop: see apa_clip_stages.h)
 __global__ __launch_bounds__(256) void fp_pool_kernel(const float* __restrict__ x,
                                                       const float* __restrict__ tatt,
                                                       float* __restrict__ pooled, int F, int K) {
@@ -40,7 +39,7 @@ __global__ __launch_bounds__(256) void fp_pool_kernel(const float* __restrict__ 
   }
 }
 
-// backward, one wave per frame row:
+// backward, one wave per frame row (clip_grad_row):
 //   dLda[row] = (1/F) sum_k g[b,k] x[row,k]
 //   dx[row,k] = (1/F) g[b,k] * a[row] + dLda[row] * w[k]          (temporal)
 //   dx[row,k] = (1/F) g[b,k]                                       (plain)
@@ -54,32 +53,20 @@ __global__ __launch_bounds__(256) void fp_bwd_kernel(const float* __restrict__ x
   const int lane = threadIdx.x & 63;
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= rows) return;
-  const int b = row / F;
   const float invF = 1.0f / (float)F;
-  const float* gr = g + (size_t)b * K;
-  if (!w) {
-    for (int k = lane; k < K; k += 64) dx[(size_t)row * K + k] = gr[k] * invF;
-    return;
-  }
-  float acc = 0.f;
-  for (int k = lane; k < K; k += 64) acc = fmaf(gr[k], x[(size_t)row * K + k], acc);
-  const float d = wave_sum(acc) * invF;
-  const float a = tatt[row];
-  for (int k = lane; k < K; k += 64) dx[(size_t)row * K + k] = fmaf(gr[k] * invF, a, d * w[k]);
-  if (lane == 0) dlda[row] = d;
+  const float* gr = g + (size_t)(row / F) * K;
+  if (!w) clip_grad_row<false>(x, w, gr, nullptr, dx, dlda, row, K, invF, lane);
+  else clip_grad_row<true>(x, w, gr, tatt + row, dx, dlda, row, K, invF, lane);
 }
 
-// dw[k] = sum_rows dLda[row] * x[row,k];  db = sum_rows dLda[row]   (fixed order over rows)
+// dw[k] = sum_rows dLda[row] * x[row,k] (clip_dw_col);  db = sum_rows dLda[row], serially by one thread (the clip loss
+// sums its db in the 256-thread order: each path keeps its own)
 __global__ __launch_bounds__(256) void fp_bwd_w_kernel(const float* __restrict__ x,
                                                        const float* __restrict__ dlda,
                                                        float* __restrict__ dw,
                                                        float* __restrict__ db, int rows, int K) {
   const int k = blockIdx.x * 256 + threadIdx.x;
-  if (k < K) {
-    float acc = 0.f;
-    for (int r = 0; r < rows; ++r) acc = fmaf(dlda[r], x[(size_t)r * K + k], acc);
-    dw[k] = acc;
-  }
+  if (k < K) dw[k] = clip_dw_col(x, dlda, rows, K, k);
   if (blockIdx.x == 0 && threadIdx.x == 0) {
     float s = 0.f;
     for (int r = 0; r < rows; ++r) s += dlda[r];

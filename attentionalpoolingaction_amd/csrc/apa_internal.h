@@ -240,6 +240,8 @@ inline void ml_scales(int kind, float wt, float grad_scale, int n_loss, int K, f
   *lscale = w / (float)n_loss;
   *gscale = w * grad_scale / ((float)n_loss * (float)K);
 }
+// apa_capi.hip: a valid apa_multilabel (non-null, labels given, a sigmoid loss kind), or the refusal in fn's name
+int check_multilabel(const char* fn, const apa_multilabel* ml);
 
 // ..._WITH_POSE_FEAT (nets_factory.py:289-295): J extra top-down channels (apa_m1_cat.hip), as the caller describes
 // them (apa.h): Xext [N,P,J] f32, zext [N,J] f32 (forward output, backward input), dXext [N,P,J] f32 (backward)

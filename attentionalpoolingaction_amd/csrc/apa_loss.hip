@@ -10,38 +10,19 @@
 
 namespace apa {
 
-// Softmax cross-entropy, fused value + gradient (+ probabilities, + first-index argmax).
-// These launches are pure latency chains, and two things dominate them (in-kernel timestamps,
-// tools/kbench.cpp): global round trips and COLD INSTRUCTION FETCH -- a small kernel starts with
-// an empty instruction cache and straight-line code streams in at well under 2 bytes per cycle,
-// so code size is time.  Hence:
-//   * HALF a wave (32 lanes) owns a row, so one copy of the code reduces two rows at once and a
-//     16-wave block covers 32 rows in a single pass (no per-row unrolled copies);
-//   * a row is NV4 (<= 8) 16-byte vectors per lane, not predicated dwords: rows of K = 393 floats
-//     are only 4-byte aligned, gfx950 services unaligned dwordx4 accesses; the ragged last vector
-//     is shifted back to end at K-1 and its already-covered columns are masked out;
-//   * every load is issued before anything is consumed, every store after the last reduction.
+// Softmax cross-entropy, fused value + gradient (+ probabilities, + first-index argmax).  The row is xent_row_regs
+// (apa_xent_row.h: why half a wave per row, why unaligned 16-byte vectors, why code size is time): a 16-wave block
+// covers 32 rows in a single pass (no per-row unrolled copies).
 // out_loss[1+n] = xent_n (unweighted); out_loss[0] = lscale * sum_n xent_n.
 //   mode 1: one block does everything (N <= 64, only the loss is wanted);
 //   mode 2: block 0 computes the losses / predictions of ALL rows (the batch mean needs every row
 //           anyway), blocks 1.. write G / probs: one CU moving 2 x 50 KB alone is 3 us of queueing;
 //   mode 0: N > 64, out_loss[0] is summed by sum_scale_kernel.
-__device__ __forceinline__ int half_min_i(int v, int lane) {
-  v = min(v, __builtin_amdgcn_update_dpp(0x7fffffff, v, 0xB1, 0xf, 0xf, false));
-  v = min(v, __builtin_amdgcn_update_dpp(0x7fffffff, v, 0x4E, 0xf, 0xf, false));
-  v = min(v, __builtin_amdgcn_update_dpp(0x7fffffff, v, 0x141, 0xf, 0xf, false));
-  v = min(v, __builtin_amdgcn_update_dpp(0x7fffffff, v, 0x140, 0xf, 0xf, false));
-  const int s0 = min(__builtin_amdgcn_readlane(v, 0), __builtin_amdgcn_readlane(v, 16));
-  const int s1 = min(__builtin_amdgcn_readlane(v, 32), __builtin_amdgcn_readlane(v, 48));
-  return lane < 32 ? s0 : s1;
-}
-
-template <int NV4>   // 16-byte vectors per lane: ceil(ceil(K/4)/32)
+template <int NV4>   // 16-byte vectors per lane: xent_row_nv4(K)
 __global__ __launch_bounds__(1024) void softmax_xent_kernel(
     const float* __restrict__ logits, const int64_t* __restrict__ labels,
     float* __restrict__ out_loss, float* __restrict__ G, float* __restrict__ probs,
     int64_t* __restrict__ pred, int N, int K, float gscale, float lscale, int mode) {
-  typedef float f4u __attribute__((ext_vector_type(4), aligned(4)));
   __shared__ float red[32];
   const int lane = threadIdx.x & 63, half = lane >> 5, hl = lane & 31;
   const int wpb = blockDim.x >> 6;
@@ -55,68 +36,16 @@ __global__ __launch_bounds__(1024) void softmax_xent_kernel(
     const int n = base + half;
     const bool active = n < N;
     const size_t nc = (size_t)min(n, N - 1);   // the idle half of a ragged last pair re-reads row N-1
-    const int lab = (int)labels[nc];
-    f4u v[NV4];
-    int colc[NV4];
-#pragma unroll
-    for (int i = 0; i < NV4; ++i) {
-      colc[i] = min(4 * (hl + 32 * i), K - 4);
-      v[i] = *reinterpret_cast<const f4u*>(logits + nc * K + colc[i]);
-    }
-    const bool lab_ok = lab >= 0 && lab < K;
-    const float xl = logits[nc * K + (lab_ok ? lab : 0)];   // the label's logit: one broadcast load
-    // columns already covered by the previous lane (ragged last vector) leave the reductions
-#pragma unroll
-    for (int i = 0; i < NV4; ++i) {
-      const int col0 = 4 * (hl + 32 * i);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) v[i][e] = colc[i] + e >= col0 ? v[i][e] : -INFINITY;
-    }
-    float m = -INFINITY;
-    int arg = 0x7fffffff;
-#pragma unroll
-    for (int i = 0; i < NV4; ++i) {
-#pragma unroll
-      for (int e = 0; e < 4; ++e)
-        if (v[i][e] > m) { m = v[i][e]; arg = colc[i] + e; }   // first maximal index of this lane
-    }
-    const float mw = half_max(m, lane);
-    // argmax: smallest index among the lanes holding the max (np / tf argmax tie rule: first)
-    const int cand = half_min_i((m == mw) ? arg : 0x7fffffff, lane);
-    float l = 0.f;
-#pragma unroll
-    for (int i = 0; i < NV4; ++i) {
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        v[i][e] = exp_fast(v[i][e] - mw);   // 0 for the excluded columns
-        l += v[i][e];
-      }
-    }
-    l = half_sum(l, lane);
-    const float inv = 1.0f / l;
-    const float lv = lab_ok ? -(xl - mw - logf(l)) : 0.f;
+    const float* row = logits + nc * K;
+    int cand;
+    const float lv = xent_row_regs<NV4>(
+        [&](int colc) { return *reinterpret_cast<const f4u*>(row + colc); }, [&](int c) { return row[c]; }, K,
+        (int)labels[nc], gscale, lane, active && (G || probs),
+        [&](int colc, int col0, const f4u& p, const f4u& g) {
+          xent_store_vec(probs != nullptr, probs + nc * K, G != nullptr, G + nc * K, colc, col0, K, p, g);
+        },
+        &cand);
     if (active) {
-      if (G || probs) {
-#pragma unroll
-        for (int i = 0; i < NV4; ++i) {
-          const int col0 = 4 * (hl + 32 * i);
-          f4u p, g;
-#pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            p[e] = v[i][e] * inv;
-            g[e] = fmaf(p[e], gscale, colc[i] + e == lab ? -gscale : 0.f);
-          }
-          if (colc[i] == col0) {
-            if (probs) *reinterpret_cast<f4u*>(probs + nc * K + colc[i]) = p;
-            if (G) *reinterpret_cast<f4u*>(G + nc * K + colc[i]) = g;
-          } else if (col0 < K) {   // the one ragged lane of the row: its own columns only
-            for (int e = col0 - colc[i]; e < 4; ++e) {
-              if (probs) probs[nc * K + colc[i] + e] = p[e];
-              if (G) G[nc * K + colc[i] + e] = g[e];
-            }
-          }
-        }
-      }
       slot_loss += lv;   // a half-wave's rows are summed in increasing n
       if (hl == 0 && loss_role) {
         out_loss[1 + n] = lv;
@@ -124,6 +53,8 @@ __global__ __launch_bounds__(1024) void softmax_xent_kernel(
       }
     }
   }
+  // The 32-slot order of the batch mean, by definition: the slots are this block's half waves.  A kernel that folds
+  // the loss in reproduces it with xent_mean32_* (apa_xent_row.h).
   if (mode != 0 && loss_role) {
     if (hl == 0) red[(threadIdx.x >> 6) * 2 + half] = slot_loss;
     __syncthreads();
@@ -135,52 +66,30 @@ __global__ __launch_bounds__(1024) void softmax_xent_kernel(
   }
 }
 
-// Generic fallback (K < 4 or K > 1024): one wave per row, three passes over the row.
+// Generic fallback (K < 4 or K > 1024): one wave per row, xent_row_stream.
 __global__ __launch_bounds__(256) void softmax_xent_stream_kernel(
     const float* __restrict__ logits, const int64_t* __restrict__ labels,
     float* __restrict__ out_loss, float* __restrict__ G, float* __restrict__ probs,
     int64_t* __restrict__ pred, int N, int K, float gscale) {
-  const int lane = threadIdx.x & 63;
   const int n = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (n >= N) return;
   const float* row = logits + (size_t)n * K;
-  const int lab = (int)labels[n];
-  float m = -INFINITY, xl = 0.f;
-  int arg = 0x7fffffff;
-  for (int k = lane; k < K; k += 64) {
-    const float x = row[k];
-    if (x > m) { m = x; arg = k; }
-    if (k == lab) xl = x;
-  }
-  const float mw = wave_max(m);
-  const int cand = wave_min_i((m == mw) ? arg : 0x7fffffff);
-  xl = wave_sum(xl);
-  float l = 0.f;
-  for (int k = lane; k < K; k += 64) l += expf(row[k] - mw);
-  l = wave_sum(l);
-  const float inv = 1.0f / l;
-  for (int k = lane; k < K; k += 64) {
-    const float p = expf(row[k] - mw) * inv;
-    if (probs) probs[(size_t)n * K + k] = p;
-    if (G) G[(size_t)n * K + k] = (p - (k == lab ? 1.0f : 0.0f)) * gscale;
-  }
-  if (lane == 0) {
-    out_loss[1 + n] = (lab >= 0 && lab < K) ? -(xl - mw - logf(l)) : 0.f;
+  int cand;
+  const float lv = xent_row_stream([&](int k) { return row[k]; }, K, (int)labels[n], probs != nullptr,
+                                   probs + (size_t)n * K, G != nullptr, G + (size_t)n * K, gscale, &cand);
+  if ((threadIdx.x & 63) == 0) {
+    out_loss[1 + n] = lv;
     if (pred) pred[n] = cand;
   }
 }
 
-// out[0] = scale * sum_{i<count} in[i], fixed order (one block).
+// out[0] = scale * sum_{i<count} in[i], fixed order (one block): the 256-thread order of the batch mean, by definition
 __global__ __launch_bounds__(256) void sum_scale_kernel(const float* __restrict__ in,
                                                         float* __restrict__ out, int count,
                                                         float scale) {
   __shared__ float red[4];
-  float acc = 0.f;
-  for (int i = threadIdx.x; i < count; i += 256) acc += in[i];
-  acc = wave_sum(acc);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
-  __syncthreads();
-  if (threadIdx.x == 0) out[0] = ((red[0] + red[1]) + (red[2] + red[3])) * scale;
+  const float t = block_sum256(xent_mean256_load(in, count), red);
+  if (threadIdx.x == 0) out[0] = t * scale;
 }
 
 // Pose L2: block (n, s) handles share s of image n's P*J elements (grid.y shares: N blocks alone were 32 CUs'
@@ -205,10 +114,8 @@ __global__ __launch_bounds__(256) void pose_l2_kernel(const float* __restrict__ 
     acc = fmaf(vm * d, d, acc);
     if (dPl) dPl[base + idx] = gcoef * vm * d;
   }
-  acc = wave_sum(acc);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
-  __syncthreads();
-  if (threadIdx.x == 0) ws[(size_t)n * gridDim.y + blockIdx.y] = (red[0] + red[1]) + (red[2] + red[3]);
+  acc = block_sum256(acc, red);
+  if (threadIdx.x == 0) ws[(size_t)n * gridDim.y + blockIdx.y] = acc;
 }
 
 __global__ __launch_bounds__(256) void zero_out_channels_kernel(const float* __restrict__ in,
@@ -262,7 +169,7 @@ extern "C" int apa_softmax_xent_fwd_bwd(const float* logits, const int64_t* labe
   // tf.losses.softmax_cross_entropy with a scalar weight: sum(w * l) / (#non-zero weights) = w*mean
   const float lscale = wt / (float)N;
   const float gscale = wt * grad_scale / (float)N;
-  if (K < 4 || K > 1024) {
+  if (!xent_row_half_wave(K)) {
     hipLaunchKernelGGL(softmax_xent_stream_kernel, dim3((N + 3) / 4), dim3(256), 0, st, logits,
                        labels, loss, G, probs, pred, N, K, gscale);
     APA_LAUNCH_CHECK("softmax_xent_stream_kernel");
@@ -273,16 +180,18 @@ extern "C" int apa_softmax_xent_fwd_bwd(const float* logits, const int64_t* labe
   // N <= 64: one launch; block 0 = losses + batch mean, blocks 1.. = gradients (when any are
   // wanted).  A 16-wave block covers 32 rows per pass (half a wave per row).
   const bool wide = G || probs;
-  const int mode = N <= 64 ? (wide ? 2 : 1) : 0;
+  const int mode = xent_mean_slots32(N, K) ? (wide ? 2 : 1) : 0;
   int nb = mode == 1 ? 1 : (N + 31) / 32 + (mode == 2 ? 1 : 0);
   if (nb > 1024) nb = 1024;
 #define APA_XENT(NV4)                                                                           \
   hipLaunchKernelGGL(softmax_xent_kernel<NV4>, dim3(nb), dim3(1024), 0, st, logits, labels, loss, \
                      G, probs, pred, N, K, gscale, lscale, mode)
-  if (K <= 128) APA_XENT(1);
-  else if (K <= 256) APA_XENT(2);
-  else if (K <= 512) APA_XENT(4);
-  else APA_XENT(8);
+  switch (xent_row_nv4(K)) {
+    case 1: APA_XENT(1); break;
+    case 2: APA_XENT(2); break;
+    case 4: APA_XENT(4); break;
+    default: APA_XENT(8);
+  }
 #undef APA_XENT
   APA_LAUNCH_CHECK("softmax_xent_kernel");
   if (mode == 0) {

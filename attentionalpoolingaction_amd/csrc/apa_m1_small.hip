@@ -53,9 +53,9 @@ __global__ __launch_bounds__(256) void m1_logits_reduce_kernel(const float* __re
 
 // L2x: L2 fused with the softmax cross-entropy of the row (apa_attn_head_train_step only).
 // One block per image: 256 threads sum the row's partials (same fixed order as L2), publish the
-// logits row to memory and to LDS; then half a wave runs the row code of softmax_xent_kernel
-// (apa_loss.hip) on the LDS copy -- same lane layout, same reduction trees, so logits, per-example
-// loss and G are bit-identical to the two separate launches.  The batch-mean loss (needs every row)
+// logits row to memory and to LDS; then half a wave runs softmax_xent_kernel's row routine (xent_row_regs,
+// apa_xent_row.h) on the LDS copy, so logits, per-example loss and G are bit-identical to the two
+// separate launches.  The batch-mean loss (needs every row)
 // is left to the backward head kernel, which follows in the same host call.
 // EVAL (apa_attn_head_eval_step without ground truth): no labels, no loss, no gradient -- the row's
 // softmax probabilities and first-index argmax instead (eval.py:193-197).
@@ -69,7 +69,6 @@ __global__ __launch_bounds__(256) void m1_logits_xent_kernel(
     // ---- beyond the preload window ----
     float* abar, float* __restrict__ logits, float* __restrict__ out_loss, float* __restrict__ G,
     float* __restrict__ probs, int64_t* __restrict__ pred) {
-  typedef float f4u __attribute__((ext_vector_type(4), aligned(4)));
   constexpr int EPT = NV4 == 4 ? 2 : 1;
   __shared__ float row[NV4 * 128];
   const int n = blockIdx.x, tid = threadIdx.x;
@@ -115,67 +114,20 @@ __global__ __launch_bounds__(256) void m1_logits_xent_kernel(
   }
   __syncthreads();
   if (tid >= 64) return;
-  // ---- the row, on wave 0: both halves hold the same row, half 0 stores ----
-  const int lane = tid, hl = lane & 31;
-  f4u v[NV4];
-  int colc[NV4];
-#pragma unroll
-  for (int i = 0; i < NV4; ++i) {
-    colc[i] = min(4 * (hl + 32 * i), K - 4);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) v[i][e] = row[colc[i] + e];
-  }
-  const bool lab_ok = lab >= 0 && lab < K;
-  const float xl = row[lab_ok ? lab : 0];
-#pragma unroll
-  for (int i = 0; i < NV4; ++i) {
-    const int col0 = 4 * (hl + 32 * i);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) v[i][e] = colc[i] + e >= col0 ? v[i][e] : -INFINITY;
-  }
-  float m = -INFINITY;
-  int arg = 0x7fffffff;
-#pragma unroll
-  for (int i = 0; i < NV4; ++i)
-#pragma unroll
-    for (int e = 0; e < 4; ++e)
-      if (v[i][e] > m) { m = v[i][e]; arg = colc[i] + e; }   // first maximal index of this lane
-  const float mw = half_max(m, lane);
+  // ---- the row, on wave 0 (xent_row_regs): both halves hold the same row, half 0 stores ----
+  const int lane = tid;
+  float* __restrict__ dst = (EVAL ? probs : G) + (size_t)n * K;
   int cand = 0;
-  if (EVAL) cand = half_min_first((m == mw) ? arg : 0x7fffffff, lane);
-  float l = 0.f;
-#pragma unroll
-  for (int i = 0; i < NV4; ++i) {
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      v[i][e] = exp_fast(v[i][e] - mw);   // 0 for the excluded columns
-      l += v[i][e];
-    }
-  }
-  l = half_sum(l, lane);
-  const float inv = 1.0f / l;
-  const float lv = lab_ok ? -(xl - mw - logf(l)) : 0.f;
-  if (lane < 32) {
-    float* __restrict__ dst = EVAL ? probs : G;
-#pragma unroll
-    for (int i = 0; i < NV4; ++i) {
-      const int col0 = 4 * (hl + 32 * i);
-      f4u g;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const float pe = v[i][e] * inv;
-        g[e] = EVAL ? pe : fmaf(pe, gscale, colc[i] + e == lab ? -gscale : 0.f);
-      }
-      if (colc[i] == col0) {
-        *reinterpret_cast<f4u*>(dst + (size_t)n * K + colc[i]) = g;
-      } else if (col0 < K) {   // the one ragged lane of the row: its own columns only
-        for (int e = col0 - colc[i]; e < 4; ++e) dst[(size_t)n * K + colc[i] + e] = g[e];
-      }
-    }
-    if (lane == 0) {
-      if (EVAL) pred[n] = cand;
-      else out_loss[1 + n] = lv;
-    }
+  const float lv = xent_row_regs<NV4>(
+      [&](int colc) { return f4u{row[colc], row[colc + 1], row[colc + 2], row[colc + 3]}; },
+      [&](int c) { return row[c]; }, K, lab, gscale, lane, lane < 32,
+      [&](int colc, int col0, const f4u& p, const f4u& g) {
+        xent_store_vec(EVAL, dst, !EVAL, dst, colc, col0, K, p, g);
+      },
+      EVAL ? &cand : nullptr);
+  if (lane == 0) {
+    if (EVAL) pred[n] = cand;
+    else out_loss[1 + n] = lv;
   }
 }
 
@@ -676,17 +628,15 @@ __global__ __launch_bounds__(256) void m1_bwd_head_kernel(
   // dbt[k] = sum_n abar[n] G[n,k]: k slice [b*kpb, (b+1)*kpb) of this block, on wave 3:
   // 16 lanes per k (two rows each), 4 k per round
   const bool do_dbt = wave == 3;
-  // fused step: loss[0] = lscale * sum_n loss[1+n] (the rows were written by m1_logits_xent_kernel),
-  // in the slot order of softmax_xent_kernel's loss block: slot s = rows s, s + 32; slots 0..31
-  // (N > 64: the order of sum_scale_kernel, apa_loss.hip -- strided per-thread sums, wave_sum, 4 waves)
+  // fused step: loss[0] = lscale * sum_n loss[1+n] (the rows were written by m1_logits_xent_kernel), in
+  // apa_softmax_xent_fwd_bwd's summation order for (N, K) (apa_xent_row.h): the rows are requested here, in front of
+  // the tile loop, and reduced behind it
   const bool do_loss = loss != nullptr && b == 0;
-  float lrow = 0.f;
+  const bool slots32 = xent_mean_slots32(N, K);
+  float lpart = 0.f;   // this thread's loaded share of the sum, in either order
   if (do_loss) {
-    if (N <= 64) {
-      if (wave == 2 && lane < N) lrow = loss[1 + lane];
-    } else {
-      for (int i = tid; i < N; i += 256) lrow += loss[1 + i];
-    }
+    if (!slots32) lpart = xent_mean256_load(loss + 1, N);
+    else if (wave == 2) lpart = xent_mean32_load(loss + 1, N, lane);
   }
   for (int n0 = 0; n0 < N; n0 += 32) {
     float az[8], bg[UG][8];
@@ -722,21 +672,14 @@ __global__ __launch_bounds__(256) void m1_bwd_head_kernel(
   }
   if (do_dbt && r == 0 && kq < kpb && b * kpb + kq < K) dbt[b * kpb + kq] = dbt_acc;
   if (do_loss) {   // block-uniform; `red` is unused by this role
-    if (N <= 64) {
+    if (slots32) {
       if (wave == 2) {
-        red[lane] = lrow;
-        __builtin_amdgcn_wave_barrier();
-        if (lane == 0) {
-          float t = 0.f;
-          for (int w = 0; w < 32; ++w) t += (0.f + red[w]) + red[w + 32];
-          loss[0] = t * lscale;
-        }
+        const float t = xent_mean32_finish(lpart, red, lane);
+        if (lane == 0) loss[0] = t * lscale;
       }
     } else {
-      lrow = wave_sum(lrow);
-      if (lane == 0) red[wave] = lrow;
-      __syncthreads();
-      if (tid == 0) loss[0] = ((red[0] + red[1]) + (red[2] + red[3])) * lscale;
+      const float t = block_sum256(lpart, red);
+      if (tid == 0) loss[0] = t * lscale;
     }
   }
 }
@@ -883,13 +826,11 @@ __global__ __launch_bounds__(256) void m1_bwd_head_tiles_kernel(
   for (int j = 0; j < UG; ++j) { wacc[j] = f32x4{0.f, 0.f, 0.f, 0.f}; dacc[j] = 0.f; }
   const bool dbt_owner = b == 0;          // block 0's four waves hold every column of G
   const bool do_loss = loss != nullptr && b == 0;
-  float lrow = 0.f;
-  if (do_loss) {   // the slot orders of the one-tile kernel (bit-identical loss for every N)
-    if (N <= 64) {
-      if (wave == 2 && lane < N) lrow = loss[1 + lane];
-    } else {
-      for (int i = tid; i < N; i += 256) lrow += loss[1 + i];
-    }
+  const bool slots32 = xent_mean_slots32(N, K);
+  float lpart = 0.f;   // this thread's loaded share of the sum, in either order
+  if (do_loss) {   // loss[0], as in the one-tile kernel (bit-identical loss for every N)
+    if (!slots32) lpart = xent_mean256_load(loss + 1, N);
+    else if (wave == 2) lpart = xent_mean32_load(loss + 1, N, lane);
   }
   // Loads only -- nothing that consumes a loaded value (a multiply by the row's live flag would make the compiler
   // wait for the load on the spot); rows >= N are zeroed when the tile is multiplied.  The 9 + UG scalar loads of
@@ -957,21 +898,14 @@ __global__ __launch_bounds__(256) void m1_bwd_head_tiles_kernel(
     }
   }
   if (do_loss) {   // block-uniform; `red` is unused by this role
-    if (N <= 64) {
+    if (slots32) {
       if (wave == 2) {
-        red[lane] = lrow;
-        __builtin_amdgcn_wave_barrier();
-        if (lane == 0) {
-          float t = 0.f;
-          for (int w = 0; w < 32; ++w) t += (0.f + red[w]) + red[w + 32];
-          loss[0] = t * lscale;
-        }
+        const float t = xent_mean32_finish(lpart, red, lane);
+        if (lane == 0) loss[0] = t * lscale;
       }
     } else {
-      lrow = wave_sum(lrow);
-      if (lane == 0) red[wave] = lrow;
-      __syncthreads();
-      if (tid == 0) loss[0] = ((red[0] + red[1]) + (red[2] + red[3])) * lscale;
+      const float t = block_sum256(lpart, red);
+      if (tid == 0) loss[0] = t * lscale;
     }
   }
 }

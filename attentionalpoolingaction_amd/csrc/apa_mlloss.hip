@@ -120,14 +120,8 @@ using namespace apa;
 
 extern "C" int apa_multilabel_loss_fwd_bwd(const apa_multilabel* ml, const float* logits, float* loss, float* G, int N,
                                            int K, float wt, float grad_scale, void* stream) {
-  if (!ml || !ml->labels) {
-    set_error("apa_multilabel_loss_fwd_bwd: null apa_multilabel / labels pointer");
-    return APA_ERR_INVALID_ARG;
-  }
-  if (ml->kind != APA_ACTION_LOSS_MULTI_LABEL && ml->kind != APA_ACTION_LOSS_MULTI_LABEL_2) {
-    set_error("apa_multilabel_loss_fwd_bwd: unknown loss kind %d", ml->kind);
-    return APA_ERR_INVALID_ARG;
-  }
+  const int rc = check_multilabel("apa_multilabel_loss_fwd_bwd", ml);
+  if (rc != APA_OK) return rc;
   if (!logits || !loss || !G || N <= 0 || K <= 0) {
     set_error("apa_multilabel_loss_fwd_bwd: null pointer or non-positive N=%d K=%d", N, K);
     return APA_ERR_INVALID_ARG;
