@@ -325,6 +325,135 @@ extern "C" int apa_attn_pool_bwd(const void* X, const void* Xatt, const float* W
                                stream);
 }
 
+// ---- rank > 1 with one bottom-up map (apa.h: apa_rank_maps; apa_m1_rank.hip) ----------------------------------------
+// Every refusal of a rank call, nothing launched: the rank's own first (in the order apa.h lists them), then what
+// the rank-1 call refuses about the same arguments.  rk: rank 0 from the flat list, then the descriptor's entries.
+static int rank_check(const char* fn, const apa_rank_maps* rank, const PoolCall& d, const M1Fwd* f, const M1Bwd* b,
+                      RankCall* rk) {
+  if (!rank) {
+    set_error("%s: null apa_rank_maps", fn);
+    return APA_ERR_INVALID_ARG;
+  }
+  if (rank->extra < 1 || rank->extra > APA_RANK_MAX - 1) {
+    set_error("%s: apa_rank_maps.extra=%d outside 1..%d (rank 2..%d)", fn, rank->extra, APA_RANK_MAX - 1, APA_RANK_MAX);
+    return APA_ERR_INVALID_ARG;
+  }
+  int rc = check_common(fn, d);
+  if (rc != APA_OK) return rc;
+  if (d.M != 1) {
+    set_error("%s: rank > 1 is built for one bottom-up map (M == 1), got M=%d", fn, d.M);
+    return APA_ERR_UNSUPPORTED;
+  }
+  if (d.flags & (APA_FLAG_SOFTMAX_ATT | APA_FLAG_RELU_INPUT | APA_FLAG_FROZEN_INPUT)) {
+    set_error("%s: rank > 1 does not take %s", fn,
+              (d.flags & APA_FLAG_SOFTMAX_ATT) ? "APA_FLAG_SOFTMAX_ATT (softmax attention with rank > 1 is not a valid "
+                                                 "reference configuration)"
+              : (d.flags & APA_FLAG_RELU_INPUT) ? "APA_FLAG_RELU_INPUT" : "APA_FLAG_FROZEN_INPUT");
+    return APA_ERR_UNSUPPORTED;
+  }
+  rk->R = rank->extra + 1;
+  rk->Wt[0] = f ? f->Wt : b->Wt; rk->bt[0] = f ? f->bt : b->bt;
+  rk->dWt[0] = b ? b->dWt : nullptr; rk->dbt[0] = b ? b->dbt : nullptr;
+  rk->z0 = rank->z0; rk->ws = d.ws;
+  for (int r = 0; r < rank->extra; ++r) {
+    if (!rank->chain_w[r] || !rank->chain_b[r] || !rank->Wt[r] || !rank->bt[r] ||
+        (b && (!rank->dchain_w[r] || !rank->dchain_b[r] || !rank->dWt[r] || !rank->dbt[r]))) {
+      set_error("%s: null pointer in entry %d of apa_rank_maps (extra=%d)", fn, r, rank->extra);
+      return APA_ERR_INVALID_ARG;
+    }
+    rk->cw[r] = rank->chain_w[r]; rk->cb[r] = rank->chain_b[r];
+    rk->Wt[r + 1] = rank->Wt[r]; rk->bt[r + 1] = rank->bt[r];
+    rk->dcw[r] = b ? rank->dchain_w[r] : nullptr; rk->dcb[r] = b ? rank->dchain_b[r] : nullptr;
+    rk->dWt[r + 1] = b ? rank->dWt[r] : nullptr; rk->dbt[r + 1] = b ? rank->dbt[r] : nullptr;
+  }
+  if (!rank->z0) {
+    set_error("%s: apa_rank_maps.z0 is NULL (the [N,P] map the forward call saves for the backward call)", fn);
+    return APA_ERR_INVALID_ARG;
+  }
+  if ((rc = pool_check(d, f, b)) != APA_OK) return rc;
+  const void* const X = b ? b->X : f->X;
+  const void* const Xatt = b ? b->Xatt : f->Xatt;
+  if (!m1r_supported(d.C, d.Ca, d.dtype, Xatt == X)) {
+    set_error("%s: rank > 1 needs C a whole number of 16-byte vectors up to 2048 channels; got C=%d Ca=%d dtype=%d", fn,
+              d.C, d.Ca, d.dtype);
+    return APA_ERR_UNSUPPORTED;
+  }
+  const size_t need = m1r_workspace_bytes(d.N, d.P, d.C, d.Ca, d.K, rk->R);
+  if (d.ws_bytes < need) {
+    set_error("%s: workspace too small (%zu < %zu = apa_attn_pool_rank_workspace_bytes)", fn, d.ws_bytes, need);
+    return APA_ERR_WORKSPACE;
+  }
+  return APA_OK;
+}
+
+extern "C" size_t apa_attn_pool_rank_workspace_bytes(int N, int P, int C, int Ca, int K, int extra) {
+  if (N <= 0 || P <= 0 || C <= 0 || Ca <= 0 || K <= 0 || extra < 1 || extra > APA_RANK_MAX - 1) return 0;
+  return m1r_workspace_bytes(N, P, C, Ca, K, extra + 1);
+}
+
+static int rank_fwd_run(const PoolCall& d, const RankCall& rk, const M1Fwd& f) {
+  M1Call c;
+  const int rc = m1_call_fill(c, d, &f, nullptr);
+  return rc != APA_OK ? rc : m1r_forward(c, rk, f);
+}
+static int rank_bwd_run(const PoolCall& d, const RankCall& rk, const M1Bwd& b) {
+  M1Call c;
+  const int rc = m1_call_fill(c, d, nullptr, &b);
+  return rc != APA_OK ? rc : m1r_backward(c, rk, b);
+}
+
+extern "C" int apa_attn_pool_rank_fwd(const apa_rank_maps* rank, const void* X, const void* Xatt, const float* Wa,
+                                      const float* ba, const float* Wt, const float* bt, float* logits, float* att,
+                                      float* zsave, float* abar, void* ws, size_t ws_bytes, int N, int P, int C, int Ca,
+                                      int K, int M, unsigned flags, float keep_prob, uint64_t seed, uint64_t offset,
+                                      int dtype, void* stream) {
+  const PoolCall d = pool_call({N, P, C, Ca, K, M, dtype}, flags, keep_prob, seed, offset, ws, ws_bytes, stream);
+  const M1Fwd f{X, Xatt, Wa, ba, Wt, bt, logits, att, zsave, abar};
+  RankCall rk = {};
+  const int rc = rank_check("apa_attn_pool_rank_fwd", rank, d, &f, nullptr, &rk);
+  return rc != APA_OK ? rc : rank_fwd_run(d, rk, f);
+}
+
+extern "C" int apa_attn_pool_rank_bwd(const apa_rank_maps* rank, const void* X, const void* Xatt, const float* Wa,
+                                      const float* ba, const float* Wt, const float* bt, const float* att,
+                                      const float* zsave, const float* abar, const float* G, void* dX, void* dXatt,
+                                      float* dWa, float* dba, float* dWt, float* dbt, void* ws, size_t ws_bytes, int N,
+                                      int P, int C, int Ca, int K, int M, unsigned flags, float keep_prob,
+                                      uint64_t seed, uint64_t offset, int dtype, void* stream) {
+  (void)ba;
+  const PoolCall d = pool_call({N, P, C, Ca, K, M, dtype}, flags, keep_prob, seed, offset, ws, ws_bytes, stream);
+  const M1Bwd b{X, Xatt, Wa, Wt, bt, att, zsave, abar, G, dX, dXatt, dWa, dba, dWt, dbt};
+  RankCall rk = {};
+  const int rc = rank_check("apa_attn_pool_rank_bwd", rank, d, nullptr, &b, &rk);
+  return rc != APA_OK ? rc : rank_bwd_run(d, rk, b);
+}
+
+// forward, softmax cross-entropy, backward: the three entry points' own launches in one host call, so bit-identical
+// to them; both halves are checked before the first launch
+extern "C" int apa_attn_head_train_step_rank(const apa_rank_maps* rank, const void* X, const void* Xatt,
+                                             const float* Wa, const float* ba, const float* Wt, const float* bt,
+                                             const int64_t* labels, float loss_wt, float grad_scale, float* logits,
+                                             float* att, float* zsave, float* abar, float* loss, float* G, void* dX,
+                                             void* dXatt, float* dWa, float* dba, float* dWt, float* dbt, void* ws,
+                                             size_t ws_bytes, int N, int P, int C, int Ca, int K, int M, unsigned flags,
+                                             float keep_prob, uint64_t seed, uint64_t offset, int dtype, void* stream) {
+  const char* fn = "apa_attn_head_train_step_rank";
+  const PoolCall d = pool_call({N, P, C, Ca, K, M, dtype}, flags, keep_prob, seed, offset, ws, ws_bytes, stream);
+  const M1Fwd f{X, Xatt, Wa, ba, Wt, bt, logits, att, zsave, abar};
+  const M1Bwd b{X, Xatt, Wa, Wt, bt, att, zsave, abar, G, dX, dXatt, dWa, dba, dWt, dbt};
+  RankCall rkf = {}, rkb = {};
+  int rc = rank_check(fn, rank, d, &f, nullptr, &rkf);
+  if (rc != APA_OK) return rc;
+  if (!labels || !loss || !G) {
+    set_error("%s: null labels / loss / G pointer", fn);
+    return APA_ERR_INVALID_ARG;
+  }
+  if ((rc = rank_check(fn, rank, d, nullptr, &b, &rkb)) != APA_OK) return rc;
+  if ((rc = rank_fwd_run(d, rkf, f)) != APA_OK) return rc;
+  rc = apa_softmax_xent_fwd_bwd(logits, labels, loss, G, nullptr, nullptr, N, K, loss_wt, grad_scale, stream);
+  return rc != APA_OK ? rc : rank_bwd_run(d, rkb, b);
+}
+
 // ---- the one-call training steps ------------------------------------------------------------------------------------
 // The loss of a step.  ml: a sigmoid action loss on ml->labels (checked by check_multilabel; `labels` unused), null:
 // the softmax cross-entropy on the integer `labels`.  clips: the loss is taken on the rows pooled over each clip's frames

@@ -347,6 +347,26 @@ int m1v_launch_bwd_main(const M1Call& c, const M1Bwd& io);
 bool m1g_supported(int C, int dtype);   // apa_m1_generic.hip: any C (run-time channel loop, LDS accumulators)
 int m1g_launch_pool_fwd(const M1Call& c, const M1Fwd& io);
 int m1g_launch_bwd_main(const M1Call& c, const M1Bwd& io);
+// the attention GEMV of a separate attention input as launches of their own (apa_m1.hip; m1_forward / m1_backward run
+// the same): Z = Xatt . Wa + ba with c.act into io.att; dXatt / the dWa, dba partials from c.dzatt over *nred blocks
+int m1_att_gemv_forward(const M1Call& c, const M1Fwd& io);
+int m1_att_gemv_backward(const M1Call& c, const M1Bwd& io, int* nred);
+// apa_m1_rank.hip: R = 2 .. APA_RANK_MAX attention maps chained from one bottom-up map (apa.h: apa_rank_maps), one
+// streaming pass per direction.  RankCall: rank 0 first, then the descriptor's entries; ws: the call's workspace
+// (m1_plan's carve in front, the rank region behind it).  M1Fwd / M1Bwd carry rank 0's Wt / bt / dWt / dbt too;
+// att is [N,P,R], zsave [N,R,C], abar [N,R].
+struct RankCall {
+  int R;
+  const float* cw[APA_RANK_MAX - 1]; const float* cb[APA_RANK_MAX - 1];
+  const float* Wt[APA_RANK_MAX]; const float* bt[APA_RANK_MAX];
+  float* dcw[APA_RANK_MAX - 1]; float* dcb[APA_RANK_MAX - 1];
+  float* dWt[APA_RANK_MAX]; float* dbt[APA_RANK_MAX];
+  float* z0; void* ws;
+};
+bool m1r_supported(int C, int Ca, int dtype, bool fused);
+size_t m1r_workspace_bytes(int N, int P, int C, int Ca, int K, int R);
+int m1r_forward(const M1Call& c, const RankCall& rk, const M1Fwd& io);
+int m1r_backward(const M1Call& c, const RankCall& rk, const M1Bwd& io);
 bool m1_cat_supported(int J);   // apa_m1_cat.hip: the J extra top-down channels of CatFeat (c.cat)
 int m1_cat_forward(const M1Call& c, const M1Fwd& io);
 int m1_cat_backward(const M1Call& c, const M1Bwd& io);   // dWt rows C.., dXext, and c.cat_e

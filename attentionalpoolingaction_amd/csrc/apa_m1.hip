@@ -575,6 +575,24 @@ static void att_gemv_bwd(const M1Call& c, const M1Bwd& io, int nb) {
   }
 }
 
+int m1_att_gemv_forward(const M1Call& c, const M1Fwd& io) {
+  if (c.dtype == APA_DTYPE_F32) att_gemv_fwd<float>(c, io); else att_gemv_fwd<bf16_t>(c, io);
+  APA_LAUNCH_CHECK("m1_att_gemv_fwd_kernel");
+  return APA_OK;
+}
+
+int m1_att_gemv_backward(const M1Call& c, const M1Bwd& io, int* nred) {
+  const long NP = (long)c.N * c.P;
+  int nb = (int)((NP + 15) / 16);
+  if (nb > 1024) nb = 1024;
+  if (nb < 1) nb = 1;
+  if (nb > c.pl.nblk) nb = c.pl.nblk;  // partial buffer is sized for nblk rows
+  if (c.dtype == APA_DTYPE_F32) att_gemv_bwd<float>(c, io, nb); else att_gemv_bwd<bf16_t>(c, io, nb);
+  APA_LAUNCH_CHECK("m1_att_gemv_bwd_kernel");
+  *nred = nb;
+  return APA_OK;
+}
+
 int m1_backward(const M1Call& c, const M1Bwd& io, const M1Xent* xf) {
   const int N = c.N, C = c.C, K = c.K;
   hipStream_t st = c.st;
@@ -617,14 +635,7 @@ int m1_backward(const M1Call& c, const M1Bwd& io, const M1Xent* xf) {
   int nred = c.pl.nblk;
   int cred = C;
   if (!c.fused) {
-    const long NP = (long)N * c.P;
-    int nb = (int)((NP + 15) / 16);
-    if (nb > 1024) nb = 1024;
-    if (nb < 1) nb = 1;
-    if (nb > c.pl.nblk) nb = c.pl.nblk;  // partial buffer is sized for nblk rows
-    if (c.dtype == APA_DTYPE_F32) att_gemv_bwd<float>(c, io, nb); else att_gemv_bwd<bf16_t>(c, io, nb);
-    APA_LAUNCH_CHECK("m1_att_gemv_bwd_kernel");
-    nred = nb;
+    if ((rc = m1_att_gemv_backward(c, io, &nred)) != APA_OK) return rc;
     cred = c.Ca;
   }
   if (tr) { tr->reduce = c.small ? M1_REDUCE_COLSUM : M1_REDUCE_BWD_REDUCE; tr->rng_bump = c.bump != nullptr; }

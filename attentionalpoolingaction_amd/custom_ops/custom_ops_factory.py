@@ -42,6 +42,7 @@ APA_ERR_UNSUPPORTED = -2
 APA_SCORES_SOFTMAX = 0   # eval.py:197
 APA_SCORES_SIGMOID = 1   # eval.py:194-195 (TRAIN.LOSS_FN_ACTION starts with 'multi-label')
 APA_WIMG_MAX = 12
+APA_RANK_MAX = 4         # attention maps chained from one bottom-up map (apa_rank_maps)
 APA_WIMG_ROLES = {0: 'Wa', 1: 'ba', 2: 'Wt', 3: 'bt'}
 
 # every symbol include/apa.h declares: name -> (restype, argtypes)
@@ -112,6 +113,15 @@ _SIGNATURES = {
                               [c_uint, c_float, c_uint64, c_uint64, c_int, c_void_p]),
     'apa_attn_pool_bwd_cat': (c_int, [c_void_p] * 19 + [c_size_t] + [c_int] * 6 +
                               [c_uint, c_float, c_uint64, c_uint64, c_int, c_void_p]),
+    # rank > 1 with one bottom-up map: `const apa_rank_maps*` first, then the plain arguments (no topdown, no hooks)
+    'apa_attn_pool_rank_workspace_bytes': (c_size_t, [c_int] * 6),
+    'apa_attn_pool_rank_fwd': (c_int, [c_void_p] * 12 + [c_size_t] + [c_int] * 6 +
+                               [c_uint, c_float, c_uint64, c_uint64, c_int, c_void_p]),
+    'apa_attn_pool_rank_bwd': (c_int, [c_void_p] * 18 + [c_size_t] + [c_int] * 6 +
+                               [c_uint, c_float, c_uint64, c_uint64, c_int, c_void_p]),
+    'apa_attn_head_train_step_rank': (c_int, [c_void_p] * 8 + [c_float, c_float] + [c_void_p] * 13 +
+                                      [c_size_t] + [c_int] * 6 + [c_uint, c_float, c_uint64, c_uint64, c_int,
+                                                                  c_void_p]),
     'apa_attn_head_train_step_ex': (c_int, [c_void_p] * 8 + [c_float, c_float] + [c_void_p] * 13 +
                                     [c_size_t] + [c_int] * 6 + [c_uint, c_float, c_uint64, c_uint64, c_int,
                                                                 c_void_p]),
@@ -488,6 +498,112 @@ def attn_pool_bwd_cat(X, Xatt, Xext, zext, Wa, ba, Wt, bt, att, zsave, abar, G, 
         _stream_ptr())
     _check(rc, 'apa_attn_pool_bwd_cat')
     return dX, dXatt, dXext, dWa, dba, dWt, dbt
+
+
+class ApaRankMaps(ctypes.Structure):
+    """`apa_rank_maps` of include/apa.h: ranks 1 .. R-1 of NET.USE_POSE_PRELOGITS_BASED_ATTENTION_RANK = R (entry
+    r-1 for rank r; rank 0 travels in the flat argument list)."""
+    _fields_ = [('extra', c_int),
+                ('chain_w', c_void_p * (APA_RANK_MAX - 1)), ('chain_b', c_void_p * (APA_RANK_MAX - 1)),
+                ('Wt', c_void_p * (APA_RANK_MAX - 1)), ('bt', c_void_p * (APA_RANK_MAX - 1)),
+                ('dchain_w', c_void_p * (APA_RANK_MAX - 1)), ('dchain_b', c_void_p * (APA_RANK_MAX - 1)),
+                ('dWt', c_void_p * (APA_RANK_MAX - 1)), ('dbt', c_void_p * (APA_RANK_MAX - 1)),
+                ('z0', c_void_p)]
+
+
+def _bind_rank_maps(who, Wts, bts, chain_w, chain_b, z0, grads=None) -> ApaRankMaps:
+    """Wts / bts: R tensors [C,K] / [K] (rank 0 first); chain_w / chain_b: R - 1 one-element tensors (the weights and
+    biases of 'Conv2d_PrePose_Attn<r>'); grads = (dWts, dbts, dchain_w, dchain_b) of the same shapes, backward only.
+    The rank is checked here: the library would refuse it too (APA_ERR_INVALID_ARG)."""
+    R = len(Wts)
+    if not (2 <= R <= APA_RANK_MAX):
+        raise ApaError('{}: rank {} outside 2..{}'.format(who, R, APA_RANK_MAX))
+    if len(bts) != R or len(chain_w) != R - 1 or len(chain_b) != R - 1:
+        raise ApaError('{}: rank {} needs {} Wt / bt and {} chain weights / biases'.format(who, R, R, R - 1))
+    rk = ApaRankMaps()
+    rk.extra = R - 1
+    for r in range(R - 1):
+        if chain_w[r].numel() != 1 or chain_b[r].numel() != 1:
+            raise ApaError('{}: the chain convs map one channel to one channel (one float each)'.format(who))
+        rk.chain_w[r] = _dev_ptr(chain_w[r], 'chain_w', torch.float32)
+        rk.chain_b[r] = _dev_ptr(chain_b[r], 'chain_b', torch.float32)
+        rk.Wt[r] = _dev_ptr(Wts[r + 1], 'Wt', torch.float32)
+        rk.bt[r] = _dev_ptr(bts[r + 1], 'bt', torch.float32)
+        if grads is not None:
+            dWts, dbts, dcw, dcb = grads
+            rk.dWt[r] = _dev_ptr(dWts[r + 1], 'dWt', torch.float32)
+            rk.dbt[r] = _dev_ptr(dbts[r + 1], 'dbt', torch.float32)
+            rk.dchain_w[r] = _dev_ptr(dcw[r], 'dchain_w', torch.float32)
+            rk.dchain_b[r] = _dev_ptr(dcb[r], 'dchain_b', torch.float32)
+    rk.z0 = _dev_ptr(z0, 'z0', torch.float32)
+    return rk
+
+
+def _rank_dims(X, Xatt, Wa, Wts):
+    N, C = X.shape[0], X.shape[-1]
+    return N, X.numel() // (N * C), C, Xatt.shape[-1], Wts[0].shape[1], Wa.shape[1]
+
+
+def _rank_workspace(who, lib, workspace, N, P, C, Ca, K, R, dev):
+    need = int(lib.apa_attn_pool_rank_workspace_bytes(N, P, C, Ca, K, R - 1))
+    if workspace is None or workspace.numel() < max(need, 16):
+        workspace = torch.empty((max(need, 16),), dtype=torch.uint8, device=dev)
+    return workspace
+
+
+def attn_pool_rank_fwd(X, Xatt, Wa, ba, Wts, bts, chain_w, chain_b, *, flags=0, keep_prob=1.0, seed=0, offset=0,
+                       workspace=None):
+    """logits, att, zsave, abar, z0, workspace = attn_pool_rank_fwd(...): R = len(Wts) attention maps chained from
+    ONE bottom-up map, pooled in one pass over X (include/apa.h: apa_attn_pool_rank_fwd).  att [N,P,R], zsave
+    [N,R,C], abar [N,R], z0 [N,P] (saved for the backward call)."""
+    lib = load_library()
+    N, P, C, Ca, K, M = _rank_dims(X, Xatt, Wa, Wts)
+    R, dev = len(Wts), X.device
+    logits = torch.empty((N, K), dtype=torch.float32, device=dev)
+    att = torch.empty((N, P, R), dtype=torch.float32, device=dev)
+    zsave = torch.empty((N, R, C), dtype=torch.float32, device=dev)
+    abar = torch.empty((N, R), dtype=torch.float32, device=dev)
+    z0 = torch.empty((N, P), dtype=torch.float32, device=dev)
+    rk = _bind_rank_maps('attn_pool_rank_fwd', Wts, bts, chain_w, chain_b, z0)
+    workspace = _rank_workspace('attn_pool_rank_fwd', lib, workspace, N, P, C, Ca, K, R, dev)
+    xatt_ptr = _dev_ptr(X, 'X') if Xatt is X else _dev_ptr(Xatt, 'Xatt', X.dtype)
+    seed, offset, flags = _rng_key(seed, offset, flags)
+    rc = lib.apa_attn_pool_rank_fwd(
+        ctypes.addressof(rk), _dev_ptr(X, 'X'), xatt_ptr, _dev_ptr(Wa, 'Wa', torch.float32),
+        _dev_ptr(ba, 'ba', torch.float32), _dev_ptr(Wts[0], 'Wt', torch.float32), _dev_ptr(bts[0], 'bt', torch.float32),
+        logits.data_ptr(), att.data_ptr(), zsave.data_ptr(), abar.data_ptr(), workspace.data_ptr(), workspace.numel(),
+        N, P, C, Ca, K, M, flags, float(keep_prob), int(seed), offset, _feat_dtype(X), _stream_ptr())
+    _check(rc, 'apa_attn_pool_rank_fwd')
+    return logits, att, zsave, abar, z0, workspace
+
+
+def attn_pool_rank_bwd(X, Xatt, Wa, ba, Wts, bts, chain_w, chain_b, att, zsave, abar, z0, G, *, flags=0,
+                       keep_prob=1.0, seed=0, offset=0, workspace=None, out=None):
+    """dX, dXatt, dWa, dba, dWts, dbts, dchain_w, dchain_b = attn_pool_rank_bwd(...); the last four are lists (R, R,
+    R - 1, R - 1 tensors).  `out` may supply the eight preallocated (e.g. views into a flat gradient bucket)."""
+    lib = load_library()
+    N, P, C, Ca, K, M = _rank_dims(X, Xatt, Wa, Wts)
+    R, dev, fused = len(Wts), X.device, Xatt is X
+    if out is None:
+        out = (torch.empty_like(X), None if fused else torch.empty_like(Xatt), torch.empty_like(Wa),
+               torch.empty_like(ba), [torch.empty_like(w) for w in Wts], [torch.empty_like(b) for b in bts],
+               [torch.empty_like(w) for w in chain_w], [torch.empty_like(b) for b in chain_b])
+    dX, dXatt, dWa, dba, dWts, dbts, dcw, dcb = out
+    rk = _bind_rank_maps('attn_pool_rank_bwd', Wts, bts, chain_w, chain_b, z0, (dWts, dbts, dcw, dcb))
+    workspace = _rank_workspace('attn_pool_rank_bwd', lib, workspace, N, P, C, Ca, K, R, dev)
+    xatt_ptr = _dev_ptr(X, 'X') if fused else _dev_ptr(Xatt, 'Xatt', X.dtype)
+    seed, offset, flags = _rng_key(seed, offset, flags)
+    rc = lib.apa_attn_pool_rank_bwd(
+        ctypes.addressof(rk), _dev_ptr(X, 'X'), xatt_ptr, _dev_ptr(Wa, 'Wa', torch.float32),
+        _dev_ptr(ba, 'ba', torch.float32), _dev_ptr(Wts[0], 'Wt', torch.float32), _dev_ptr(bts[0], 'bt', torch.float32),
+        _dev_ptr(att, 'att', torch.float32), _dev_ptr(zsave, 'zsave', torch.float32),
+        _dev_ptr(abar, 'abar', torch.float32), _dev_ptr(G, 'G', torch.float32), _dev_ptr(dX, 'dX', X.dtype),
+        None if fused else _dev_ptr(dXatt, 'dXatt', X.dtype), _dev_ptr(dWa, 'dWa', torch.float32),
+        _dev_ptr(dba, 'dba', torch.float32), _dev_ptr(dWts[0], 'dWt', torch.float32),
+        _dev_ptr(dbts[0], 'dbt', torch.float32), workspace.data_ptr(), workspace.numel(), N, P, C, Ca, K, M, flags,
+        float(keep_prob), int(seed), offset, _feat_dtype(X), _stream_ptr())
+    _check(rc, 'apa_attn_pool_rank_bwd')
+    return dX, dXatt, dWa, dba, dWts, dbts, dcw, dcb
 
 
 def dropout_mask(shape, keep_prob, seed, offset, device='cuda') -> torch.Tensor:
@@ -1360,6 +1476,73 @@ class HeadTrainStep:
             rc = self._fn(*self._pre, _hooks_ptr(h), *self._args, _stream_ptr() if stream is None else stream)
         if rc != 0:
             _check(rc, self._name)
+
+
+class RankHeadTrainStep:
+    """apa_attn_head_train_step_rank bound to caller-owned buffers, in the style of HeadTrainStep: forward, softmax
+    cross-entropy and backward of a rank-R head (one bottom-up map, R = len(Wts) in 2..APA_RANK_MAX) as ONE foreign
+    call per step, bit-identical to attn_pool_rank_fwd, softmax_xent_fwd_bwd and attn_pool_rank_bwd in turn.
+
+    Outputs: `logits [N,K]`, `att [N,P,R]`, `zsave [N,R,C]`, `abar [N,R]`, `z0 [N,P]`, `loss [1+N]`, `G [N,K]`, and
+    the gradient buffers `grads = (dX, dXatt, dWa, dba, dWts, dbts, dchain_w, dchain_b)` (lists for the last four;
+    e.g. views into a flat data-parallel bucket).  `offset`: int, or a 1-element int64 CUDA tensor (device-side
+    dropout counter, advanced by the backward half)."""
+
+    def __init__(self, X, Xatt, Wa, ba, Wts, bts, chain_w, chain_b, labels, grads, *, flags=0, keep_prob=1.0, seed=0,
+                 offset=0, loss_wt=1.0, grad_scale=1.0, workspace=None):
+        self.lib = load_library()
+        N, P, C, Ca, K, M = _rank_dims(X, Xatt, Wa, Wts)
+        R, dev, fused = len(Wts), X.device, Xatt is X
+        dX, dXatt, dWa, dba, dWts, dbts, dcw, dcb = grads
+        self.logits = torch.empty((N, K), dtype=torch.float32, device=dev)
+        self.att = torch.empty((N, P, R), dtype=torch.float32, device=dev)
+        self.zsave = torch.empty((N, R, C), dtype=torch.float32, device=dev)
+        self.abar = torch.empty((N, R), dtype=torch.float32, device=dev)
+        self.z0 = torch.empty((N, P), dtype=torch.float32, device=dev)
+        self.loss = torch.empty((1 + N,), dtype=torch.float32, device=dev)
+        self.G = torch.empty((N, K), dtype=torch.float32, device=dev)
+        self._rank = _bind_rank_maps('RankHeadTrainStep', Wts, bts, chain_w, chain_b, self.z0, (dWts, dbts, dcw, dcb))
+        self.workspace = _rank_workspace('RankHeadTrainStep', self.lib, workspace, N, P, C, Ca, K, R, dev)
+        self._keep = (X, Xatt, Wa, ba, Wts, bts, chain_w, chain_b, labels, grads, offset, seed)
+        seed, off, flags = _rng_key(seed, offset, flags)     # the pointers below stay valid
+        self._args = [
+            ctypes.addressof(self._rank), _dev_ptr(X, 'X'),
+            _dev_ptr(X, 'X') if fused else _dev_ptr(Xatt, 'Xatt', X.dtype),
+            _dev_ptr(Wa, 'Wa', torch.float32), _dev_ptr(ba, 'ba', torch.float32),
+            _dev_ptr(Wts[0], 'Wt', torch.float32), _dev_ptr(bts[0], 'bt', torch.float32),
+            _dev_ptr(labels, 'labels', torch.int64), float(loss_wt), float(grad_scale),
+            self.logits.data_ptr(), self.att.data_ptr(), self.zsave.data_ptr(), self.abar.data_ptr(),
+            self.loss.data_ptr(), self.G.data_ptr(), _dev_ptr(dX, 'dX', X.dtype),
+            None if fused else _dev_ptr(dXatt, 'dXatt', X.dtype), _dev_ptr(dWa, 'dWa', torch.float32),
+            _dev_ptr(dba, 'dba', torch.float32), _dev_ptr(dWts[0], 'dWt', torch.float32),
+            _dev_ptr(dbts[0], 'dbt', torch.float32), self.workspace.data_ptr(), self.workspace.numel(), N, P, C, Ca,
+            K, M, flags, float(keep_prob), int(seed), off, _feat_dtype(X)]
+
+    def rebind(self, X=None, labels=None, offset=None) -> None:
+        """Another feature map / label tensor of the SAME shape and dtype, and / or another dropout offset (int).
+        Fused attention input only (Xatt is X)."""
+        keep = list(self._keep)
+        if X is not None:
+            if self._args[1] != self._args[2]:
+                raise ApaError('RankHeadTrainStep.rebind: a separate attention input is bound')
+            if X.shape != keep[0].shape or X.dtype != keep[0].dtype:
+                raise ApaError('RankHeadTrainStep.rebind: same shape and dtype expected')
+            self._args[1] = self._args[2] = _dev_ptr(X, 'X')
+            keep[0] = keep[1] = X
+        if labels is not None:
+            self._args[7] = _dev_ptr(labels, 'labels', torch.int64)
+            keep[8] = labels
+        if offset is not None:
+            if isinstance(keep[10], torch.Tensor):
+                raise ApaError('RankHeadTrainStep.rebind: the step was bound to a device-side dropout counter')
+            self._args[-2] = int(offset)
+            keep[10] = int(offset)
+        self._keep = tuple(keep)
+
+    def run(self, stream: Optional[int] = None) -> None:
+        rc = self.lib.apa_attn_head_train_step_rank(*self._args, _stream_ptr() if stream is None else stream)
+        if rc != 0:
+            _check(rc, 'apa_attn_head_train_step_rank')
 
 
 class ApaPoseAttnStepIO(ctypes.Structure):

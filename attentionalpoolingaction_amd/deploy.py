@@ -930,7 +930,9 @@ class FusedHeadStep:
     src/train.py:393-422) plus `optimizer.compute_gradients` on the clone loss (model_deploy.py:263) -- as ONE host
     call on the conv5 map: `apa_pose_attn_train_step` for the cfg 003 form (attention from pose_pre_logits, pose L2 +
     softmax cross-entropy), `apa_attn_head_train_step` for the cfg 002 / per-class (HMDB-51) forms (attention from
-    the map itself, softmax cross-entropy).  The YAML-driven surface stays the reference's: `get_network_fn(...)`
+    the map itself, softmax cross-entropy), `apa_attn_head_train_step_rank` for rank 2..4 on one bottom-up map from
+    conv5 (NET.USE_POSE_PRELOGITS_BASED_ATTENTION_RANK; flat batches, softmax cross-entropy: its per-rank variables
+    join `params`, `tf_names`, the bucket, `regularized`, the staleness guard and the TRAINABLE_SCOPES split).  The YAML-driven surface stays the reference's: `get_network_fn(...)`
     builds backbone + head, this object drives them.
 
         fused = deploy.FusedHeadStep(network_fn, cfg)                 # raises ValueError if the configuration
@@ -1012,6 +1014,15 @@ class FusedHeadStep:
         # regularised and decay (the optimiser's L2 term on a zero gradient), as in the reference (tf.gradients
         # reaches them through REGULARIZATION_LOSSES only)
         written = names if self.pose_form else names[4:]
+        # rank > 1 (apa_attn_head_train_step_rank): the chain convs 'Conv2d_PrePose_Attn<r>' and the top-down convs
+        # 'Conv_<r>' of ranks 1 .. R-1, under the attribute names head.tf_variable_names() lists them by
+        self.rank_names = ['%s.%d' % (a, r) for r in range(head.rank - 1)
+                           for a in ('att_weights_r', 'att_biases_r', 'td_weights_r', 'td_biases_r')]
+        for n in self.rank_names:
+            attr, r = n.split('.')
+            self.params[n] = getattr(head, attr)[int(r)]
+        names = names + self.rank_names
+        written = written + self.rank_names
         reg = {id(w) for w in head.regularized_weights()}
         self.tf_names = {n: head.tf_variable_names()[n] for n in names}
         self.temporal = getattr(network_fn, 'temporal', None)
@@ -1061,8 +1072,19 @@ class FusedHeadStep:
             return 'the pose-heatmap attention head (USE_POSE_ATTENTION_LOGITS) trains through network_fn and autograd'
         if not head.is_training:
             return 'a training-mode head is required'
-        if head.rank != 1 or head.with_pose_feat or head.want_topdown:
-            return 'rank > 1, ..._WITH_POSE_FEAT and the TopDownAttention dump run through the per-op module'
+        if head.with_pose_feat or head.want_topdown:
+            return '..._WITH_POSE_FEAT and the TopDownAttention dump run through the per-op module'
+        if head.rank != 1:
+            # rank 2..APA_RANK_MAX on one bottom-up map computed from conv5: apa_attn_head_train_step_rank
+            from .custom_ops import custom_ops_factory as cof
+            if head.rank > cof.APA_RANK_MAX:
+                return 'rank %d > %d runs through the per-op module' % (head.rank, cof.APA_RANK_MAX)
+            if not head.single_layer:
+                return 'rank > 1 with attention from pose_pre_logits runs through the per-op module'
+            if head.per_class:
+                return 'rank > 1 with per-class maps runs through the per-op module'
+            if tr.LOSS_FN_ACTION != 'softmax-xentropy':
+                return 'rank > 1 with LOSS_FN_ACTION %r (the rank step takes the softmax cross-entropy)' % tr.LOSS_FN_ACTION
         # 'multi-label' / 'multi-label-2' (HICO, Charades; loss.py:88-101): the *_train_step_multilabel entry points
         if tr.LOSS_FN_ACTION not in ('softmax-xentropy', 'multi-label', 'multi-label-2'):
             return 'LOSS_FN_ACTION %r (the one-call steps take the softmax cross-entropy)' % tr.LOSS_FN_ACTION
@@ -1186,7 +1208,24 @@ class FusedHeadStep:
             if self.temporal is not None:
                 clip.update(temporal=(p['temporal_weights'], p['temporal_biases']),
                             temporal_grads=(v['temporal_weights'], v['temporal_biases']))
-        if self.pose_form:
+        if head.rank > 1:
+            # all R maps in one pass over conv5 per direction.  The rank step has no arm without the dX stores: with
+            # frozen features conv5's gradient goes to a scratch buffer nobody reads
+            R = head.rank
+            dX_rank = dX if dX is not None else torch.empty_like(X)
+            st = cof.RankHeadTrainStep(
+                X, X, p['att_weights'], p['att_biases'],
+                [p['td_weights']] + [p['td_weights_r.%d' % r] for r in range(R - 1)],
+                [p['td_biases']] + [p['td_biases_r.%d' % r] for r in range(R - 1)],
+                [p['att_weights_r.%d' % r] for r in range(R - 1)], [p['att_biases_r.%d' % r] for r in range(R - 1)],
+                labels_action,
+                (dX_rank, None, v['att_weights'], v['att_biases'],
+                 [v['td_weights']] + [v['td_weights_r.%d' % r] for r in range(R - 1)],
+                 [v['td_biases']] + [v['td_biases_r.%d' % r] for r in range(R - 1)],
+                 [v['att_weights_r.%d' % r] for r in range(R - 1)], [v['att_biases_r.%d' % r] for r in range(R - 1)]),
+                flags=flags, keep_prob=head.keep_prob, seed=head.seed, offset=head._step, loss_wt=action_wt,
+                grad_scale=self.loss_scale)
+        elif self.pose_form:
             shadow = self.w1_shadow if X.dtype == torch.bfloat16 else None
             st = cof.PoseAttnTrainStep(
                 X, (p['pose_w1'], p['pose_b1'], p['pose_w2'], p['pose_b2'], p['att_weights'], p['att_biases'],
@@ -1283,6 +1322,9 @@ class FusedHeadStep:
         last_conv, self._preact = self.network_fn.features(images)
         if last_conv.dim() != 4:
             raise ValueError('FusedHeadStep: [N,H,W,C] (or [B,F,H,W,C]) feature maps expected')
+        if self._frames > 1 and self.head.rank > 1:
+            raise ValueError('FusedHeadStep: a clip batch [B,F,H,W,C] with rank > 1 is not served by the one-call rank '
+                             'step (frame pooling at rank > 1 runs through the per-op module)')
         if self._preact and not self.head.can_fuse_input_relu(last_conv.dtype):
             last_conv, self._preact = torch.relu(last_conv), False
         if self.pose_form and (labels_pose is None or pose_valid is None):
@@ -1296,7 +1338,9 @@ class FusedHeadStep:
         total = _FusedHeadFunction.apply(last_conv, self._anchor, self, labels_action, labels_pose, pose_valid)
         st = self._step_obj
         n, h, w = last_conv.shape[:3]
-        ep = {'Logits': st.logits, 'PosePrelogitsBasedAttention': st.att.view(n, h, w, -1),
+        # rank > 1: the stacked maps [N,H,W,1,R] (nets_factory.py:271-274)
+        att = st.att.view(n, h, w, 1, -1) if self.head.rank > 1 else st.att.view(n, h, w, -1)
+        ep = {'Logits': st.logits, 'PosePrelogitsBasedAttention': att,
               'Losses': [l.detach() for l in self._losses]}
         if self.pose_form:
             ep['PoseLogits'] = st.Pl.view(n, h, w, -1)

@@ -151,6 +151,48 @@ class AttentionalPoolingFunction(torch.autograd.Function):
         return dX, dXatt, dWa, dba, dWt, dbt, None, None, None, None, None, None
 
 
+class AttentionalPoolingRankFunction(torch.autograd.Function):
+    """logits, att = f(X, Xatt, Wa, ba, R, Wt_0..Wt_{R-1}, bt_0.., w_1..w_{R-1}, b_1..): rank R > 1 with ONE
+    bottom-up map (nets_factory.py:258-274, :298-309, :322-328) as one autograd node over apa_attn_pool_rank_fwd /
+    _bwd -- one streaming pass over X per direction for all R maps, where the per-op path makes two or R.
+    w_r / b_r: the [1,1] weights and [1] biases of 'Conv2d_PrePose_Attn<r>'.  att is [N,P,R]; `Xatt is None`:
+    attention from X itself."""
+
+    @staticmethod
+    def forward(ctx, X, Xatt, Wa, ba, flags, keep_prob, seed, offset, R, *params):
+        Xc = X.contiguous()
+        fused = Xatt is None
+        Xa = Xc if fused else Xatt.contiguous()
+        p = [t.contiguous() for t in params]
+        Wts, bts, cws, cbs = p[:R], p[R:2 * R], p[2 * R:3 * R - 1], p[3 * R - 1:]
+        logits, att, zsave, abar, z0, ws = cof.attn_pool_rank_fwd(
+            Xc, Xa, Wa.contiguous(), ba.contiguous(), Wts, bts, cws, cbs, flags=flags, keep_prob=keep_prob, seed=seed,
+            offset=offset)
+        ctx.save_for_backward(Xc, Xa, Wa, ba, att, zsave, abar, z0, *p)
+        ctx.fused, ctx.R = fused, R
+        ctx.cfg = (flags, keep_prob, seed, offset)
+        ctx.ws = ws
+        ctx.shapes = (X.shape, None if fused else Xatt.shape, [t.shape for t in params])
+        ctx.mark_non_differentiable(att)
+        return logits, att
+
+    @staticmethod
+    def backward(ctx, dlogits, _datt):
+        Xc, Xa, Wa, ba, att, zsave, abar, z0 = ctx.saved_tensors[:8]
+        p, R = list(ctx.saved_tensors[8:]), ctx.R
+        flags, keep_prob, seed, offset = ctx.cfg
+        if ctx.fused:
+            Xa = Xc
+        dX, dXatt, dWa, dba, dWts, dbts, dcw, dcb = cof.attn_pool_rank_bwd(
+            Xc, Xa, Wa.contiguous(), ba.contiguous(), p[:R], p[R:2 * R], p[2 * R:3 * R - 1], p[3 * R - 1:], att, zsave,
+            abar, z0, dlogits.contiguous().float(), flags=flags, keep_prob=keep_prob, seed=seed, offset=offset,
+            workspace=ctx.ws)
+        xs, xas, ps = ctx.shapes
+        grads = [g.view(sh) for g, sh in zip(list(dWts) + list(dbts) + list(dcw) + list(dcb), ps)]
+        return (dX.view(xs), None if dXatt is None else dXatt.view(xas), dWa, dba, None, None, None, None, None,
+                *grads)
+
+
 class AttentionalPoolingCatFunction(torch.autograd.Function):
     """logits, att = f(X, Xatt, Xext, Wa, ba, Wt, bt): ..._WITH_POSE_FEAT (nets_factory.py:289-296) --
     attentional pooling over concat(X, Xext) with Wt [C+J, K], the concatenation never formed
@@ -319,8 +361,11 @@ class AttentionalPoolingHead(nn.Module):
     def __init__(self, num_classes: int, cfg, in_channels: int = 2048, num_pose_keypoints: int = 16,
                  is_training: bool = False, seed: int = 42, with_pose_logits: Optional[bool] = None,
                  want_topdown: bool = False, fuse_pose_attention: bool = True,
-                 pose_in_channels: Optional[int] = None, arg_scope: str = 'resnet'):
+                 pose_in_channels: Optional[int] = None, arg_scope: str = 'resnet', fuse_ranks: bool = False):
         super().__init__()
+        # rank 2..APA_RANK_MAX on one bottom-up map as ONE op (AttentionalPoolingRankFunction: one pass over conv5 per
+        # direction) instead of the two / R passes of the rank-1 op below; off by default
+        self.fuse_ranks = bool(fuse_ranks)
         if arg_scope not in self.ARG_SCOPES:
             raise ValueError('arg_scope must be one of %s' % sorted(self.ARG_SCOPES))
         self.arg_scope = arg_scope
@@ -477,6 +522,12 @@ class AttentionalPoolingHead(nn.Module):
             ws.append(self.pose_feat_weights)
         return ws
 
+    def ranks_fused(self) -> bool:
+        """True when forward() routes rank > 1 through the one rank op (`fuse_ranks`): rank 2..APA_RANK_MAX, one
+        bottom-up map, no ..._WITH_POSE_FEAT, no TopDownAttention dump.  Everything else runs the per-op path."""
+        return (self.fuse_ranks and 2 <= self.rank <= cof.APA_RANK_MAX and not self.per_class
+                and not self.with_pose_feat and not self.want_topdown)
+
     def can_fuse_input_relu(self, dtype=torch.float32) -> bool:
         """True when the conv5 map has no consumer but the rank-1, single-layer attention op of the
         streaming kernels -- then the backbone may hand over its PRE-activation map and the op applies
@@ -606,6 +657,15 @@ class AttentionalPoolingHead(nn.Module):
             end_points['PosePrelogitsBasedAttention'] = att.view(n, h, w, -1)    # :287
             if topdown is not None:
                 end_points['TopDownAttention'] = topdown.view(n, h, w, -1)       # :309
+        elif self.ranks_fused():
+            # rank R > 1 on one bottom-up map, fuse_ranks: all R maps in one streaming pass per direction
+            flags = cof.attn_flags(False, self.relu_att, self.is_training)
+            wts = [self.td_weights] + list(self.td_weights_r)
+            bts = [self.td_biases] + list(self.td_biases_r)
+            logits, att = AttentionalPoolingRankFunction.apply(
+                last_conv, xatt, self.att_weights, self.att_biases, flags, self.keep_prob if self.is_training else 1.0,
+                seed, offset, self.rank, *wts, *bts, *self.att_weights_r, *self.att_biases_r)
+            end_points['PosePrelogitsBasedAttention'] = att.view(n, h, w, 1, self.rank)   # [N,H,W,1,R] (:271-274)
         elif not self.rank_collapsed:
             # rank R > 1 in general (:258-274, :298-309, :322-328): conv r consumes the output of conv r-1,
             # so map r is an affine function of the attention input with the effective weights
@@ -1007,6 +1067,7 @@ def get_network_fn(name: str, num_classes: int, num_pose_keypoints: int, cfg,
     # the reference's if/elif chain (nets_factory.py:162-242): the first flag set picks the head
     if cfg.NET.USE_POSE_ATTENTION_LOGITS:
         head_kwargs.pop('fuse_pose_attention', None)
+        head_kwargs.pop('fuse_ranks', None)
         head_kwargs.pop('with_pose_logits', None)
         head = PoseAttentionLogitsHead(num_classes, cfg, in_channels=channels,
                                        num_pose_keypoints=num_pose_keypoints, is_training=is_training,
@@ -1022,6 +1083,7 @@ def get_network_fn(name: str, num_classes: int, num_pose_keypoints: int, cfg,
                                       seed=head_seed, **head_kwargs).to(device)
     else:   # cfg 001: the backbone's own average-pool + logits head
         head_kwargs.pop('arg_scope', None)
+        head_kwargs.pop('fuse_ranks', None)
         head = BaselineHead(num_classes, cfg, in_channels=channels, is_training=is_training,
                             seed=head_seed, num_pose_keypoints=num_pose_keypoints).to(device)
     temporal = None

@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define APA_VERSION 307 /* major*10000 + minor*100 + patch */
+#define APA_VERSION 308 /* major*10000 + minor*100 + patch */
 
 typedef enum apa_status {
   APA_OK = 0,
@@ -815,6 +815,68 @@ int apa_attn_pool_bwd_cat(const apa_concat_feat* cat, const apa_hooks* hooks, co
                           float* dbt, void* ws, size_t ws_bytes, int N, int P, int C, int Ca, int K,
                           int M, unsigned flags, float keep_prob, uint64_t seed, uint64_t offset,
                           int dtype, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * NET.USE_POSE_PRELOGITS_BASED_ATTENTION_RANK = R > 1 (nets_factory.py:247-328) with ONE bottom-up map: R attention
+ * maps, each with top-down weights of its own, pooled in one streaming pass over X per direction.  Every further
+ * attention conv ('Conv2d_PrePose_Attn<r>', a 1x1 conv on a one-channel map) is a scalar affine map of the map
+ * before it:
+ *     Z_0 = Xatt . Wa + ba        Z_r = chain_w[r-1] * Z_{r-1} + chain_b[r-1]  (r = 1 .. R-1)       A_r = f(Z_r)
+ *     z_r[n,:] = (1/P) sum_p A_r[n,p] Xt[n,p,:]       abar_r[n] = (1/P) sum_p A_r[n,p]       Xt = X * mask / keep
+ *     logits   = sum_r ( z_r . Wt_r + abar_r (x) bt_r )
+ * f is the identity or, with APA_FLAG_RELU_ATT, relu; ONE dropout mask serves all ranks (the reference drops
+ * last_conv once).  The flat argument list carries rank 0 (Wt, bt, dWt, dbt); the descriptor in front of it carries
+ * ranks 1 .. R-1, entry r-1 for rank r.  Buffers of the rank calls:
+ *     att [N,P,R] (end point 'PosePrelogitsBasedAttention'), zsave [N,R,C], abar [N,R], logits [N,K],
+ *     rank.z0 [N,P]: Z_0, written by the forward call, read by the backward call (the relu gates of every rank
+ *     follow from it).
+ * The backward call adds dchain_w / dchain_b (one float each) and dWt / dbt of ranks 1 .. R-1; dX, dXatt, dWa, dba as
+ * apa_attn_pool_bwd.  Results repeat bit for bit (no atomics).  apa_attn_head_train_step_rank is forward, softmax
+ * cross-entropy (apa_softmax_xent_fwd_bwd: loss [1+N], G [N,K]) and backward in one host call, bit-identical to
+ * the three calls made separately.
+ *
+ * Served: M == 1; fp32 / bf16 features with C a whole number of 16-byte vectors up to 2048 channels (a separate
+ * attention input: any such Ca); all three sources of the dropout mask.  Refused before anything is launched:
+ *   APA_ERR_INVALID_ARG   rank == NULL, rank->extra outside 1 .. APA_RANK_MAX-1, M not 1 or K, a null pointer among
+ *                         the first `extra` entries (or z0), any refusal of apa_attn_pool_fwd / _bwd's arguments
+ *   APA_ERR_UNSUPPORTED   M != 1, APA_FLAG_SOFTMAX_ATT (not a valid reference configuration with rank > 1),
+ *                         APA_FLAG_RELU_INPUT, APA_FLAG_FROZEN_INPUT, C > 2048
+ *   APA_ERR_WORKSPACE     ws_bytes < apa_attn_pool_rank_workspace_bytes(...)
+ */
+#define APA_RANK_MAX 4
+typedef struct apa_rank_maps {
+  int extra;                              /* R - 1, 1 .. APA_RANK_MAX-1 */
+  const float* chain_w[APA_RANK_MAX - 1]; /* device, one float each */
+  const float* chain_b[APA_RANK_MAX - 1];
+  const float* Wt[APA_RANK_MAX - 1];      /* [C,K] each */
+  const float* bt[APA_RANK_MAX - 1];      /* [K] each */
+  float* dchain_w[APA_RANK_MAX - 1];      /* backward only */
+  float* dchain_b[APA_RANK_MAX - 1];
+  float* dWt[APA_RANK_MAX - 1];
+  float* dbt[APA_RANK_MAX - 1];
+  float* z0;                              /* [N,P] saved by forward, read by backward */
+} apa_rank_maps;
+
+/* 0 for a shape or rank (R = extra + 1) that is not served */
+size_t apa_attn_pool_rank_workspace_bytes(int N, int P, int C, int Ca, int K, int extra);
+int apa_attn_pool_rank_fwd(const apa_rank_maps* rank, const void* X, const void* Xatt, const float* Wa,
+                           const float* ba, const float* Wt, const float* bt, float* logits, float* att,
+                           float* zsave, float* abar, void* ws, size_t ws_bytes, int N, int P, int C, int Ca,
+                           int K, int M, unsigned flags, float keep_prob, uint64_t seed, uint64_t offset,
+                           int dtype, void* stream);
+int apa_attn_pool_rank_bwd(const apa_rank_maps* rank, const void* X, const void* Xatt, const float* Wa,
+                           const float* ba, const float* Wt, const float* bt, const float* att,
+                           const float* zsave, const float* abar, const float* G, void* dX, void* dXatt,
+                           float* dWa, float* dba, float* dWt, float* dbt, void* ws, size_t ws_bytes, int N,
+                           int P, int C, int Ca, int K, int M, unsigned flags, float keep_prob, uint64_t seed,
+                           uint64_t offset, int dtype, void* stream);
+int apa_attn_head_train_step_rank(const apa_rank_maps* rank, const void* X, const void* Xatt, const float* Wa,
+                                  const float* ba, const float* Wt, const float* bt, const int64_t* labels,
+                                  float loss_wt, float grad_scale, float* logits, float* att, float* zsave,
+                                  float* abar, float* loss, float* G, void* dX, void* dXatt, float* dWa,
+                                  float* dba, float* dWt, float* dbt, void* ws, size_t ws_bytes, int N, int P,
+                                  int C, int Ca, int K, int M, unsigned flags, float keep_prob, uint64_t seed,
+                                  uint64_t offset, int dtype, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Fused optimizer step (src/train.py:90-94 tf.train.MomentumOptimizer + the slim L2 regulariser of

@@ -1,0 +1,321 @@
+"""Rank > 1 on one bottom-up map as one op (include/apa.h: apa_rank_maps), the parts that need no GPU: the float64
+reference of tests/_rank_reference.py against the oracle and the two reference-executed rank fixtures, the new entry
+points declared / exported / bound and refusing bad arguments before anything touches a device, the surface of
+deploy.FusedHeadStep and get_network_fn(..., fuse_ranks=True), and the gate condition of the GPU case table."""
+import ctypes
+import os
+import re
+
+import numpy as np
+import pytest
+import torch
+
+import _ref_fixture as rf
+from attentionalpoolingaction_amd import config as apa_config
+from attentionalpoolingaction_amd.custom_ops import custom_ops_factory as cof
+from oracle import attn_pool_oracle as orc
+from tests import _rank_reference as rr
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+NEW = ['apa_attn_pool_rank_workspace_bytes', 'apa_attn_pool_rank_fwd', 'apa_attn_pool_rank_bwd',
+       'apa_attn_head_train_step_rank']
+INVALID, UNSUPPORTED = -1, -2
+FIXTURES = ['rank2_train', 'rank3_relu_train']
+PRE = rf.PRE
+
+
+# ------------------------------------------------------------------------------------------ the float64 reference
+@pytest.mark.parametrize('R,relu,sep,train', [(2, False, False, False), (3, True, False, True), (4, True, True, True),
+                                              (3, False, True, True), (2, True, False, True)])
+def test_reference_matches_the_oracle_and_autograd(R, relu, sep, train):
+    """tests/_rank_reference.forward / backward == oracle.attentional_pooling (which restates rank 2-3 as the
+    reference's loop) and torch autograd through it, to 1e-12, on random small shapes."""
+    g = torch.Generator().manual_seed(100 * R + 10 * relu + sep)
+    N, H, W, C, Ca, K = 3, 2, 3, 12, 7, 5
+    P = H * W
+    rnd = lambda *s: torch.randn(s, generator=g, dtype=torch.float64)
+    X = rnd(N, H, W, C).clamp_min(0).requires_grad_(True)
+    Xatt = rnd(N, H, W, Ca).requires_grad_(True) if sep else X
+    Wa = (rnd(Ca if sep else C, 1) * 0.3).requires_grad_(True)
+    ba = rnd(1).requires_grad_(True)
+    cw = [rnd(1, 1).requires_grad_(True) for _ in range(R - 1)]
+    cb = [rnd(1).requires_grad_(True) for _ in range(R - 1)]
+    Wts = [(rnd(C, K) * 0.3).requires_grad_(True) for _ in range(R)]
+    bts = [rnd(K).requires_grad_(True) for _ in range(R)]
+    G = rnd(N, K)
+    keep = 0.5
+    mask = (torch.rand((N, H, W, C), generator=g) < keep).double() if train else None
+    flags = orc.AttnFlags(single_layer_att=not sep, relu_att=relu, rank=R)
+    logits, ep = orc.attentional_pooling(X, Xatt if sep else None, None, [Wa] + cw, [ba] + cb, Wts, bts, flags,
+                                         is_training=train, keep_prob=keep, dropout_mask=mask)
+    (logits * G).sum().backward()
+
+    d = lambda t: t.detach()
+    f3 = lambda t: d(t).reshape(N, P, -1)
+    fwd = rr.forward(f3(X), f3(Xatt), d(Wa)[:, 0], d(ba), [float(d(w)) for w in cw], [float(d(b)) for b in cb],
+                     [d(w) for w in Wts], [d(b) for b in bts], relu, None if mask is None else mask.reshape(N, P, C),
+                     keep)
+    close = lambda a, b, what: _close(a, b, 1e-12, what)
+    close(fwd['logits'], d(logits), 'logits')
+    close(fwd['A'], d(ep['PosePrelogitsBasedAttention']).reshape(N, P, R), 'attention maps')
+    bw = rr.backward(f3(X), f3(Xatt), d(Wa)[:, 0], [float(d(w)) for w in cw], [d(w) for w in Wts], [d(b) for b in bts],
+                     relu, fwd, G, None if mask is None else mask.reshape(N, P, C), keep, fused=not sep)
+    close(bw['dX'], X.grad.reshape(N, P, C), 'dX')
+    if sep:
+        close(bw['dXatt'], Xatt.grad.reshape(N, P, Ca), 'dXatt')
+    close(bw['dWa'], Wa.grad[:, 0], 'dWa')
+    close(bw['dba'], ba.grad[0], 'dba')
+    for r in range(R):
+        close(bw['dWts'][r], Wts[r].grad, 'dWt %d' % r)
+        close(bw['dbts'][r], bts[r].grad, 'dbt %d' % r)
+    for r in range(R - 1):
+        close(bw['dcw'][r], cw[r].grad.reshape(()), 'dw %d' % (r + 1))
+        close(bw['dcb'][r], cb[r].grad.reshape(()), 'db %d' % (r + 1))
+
+
+def _close(got, exp, tol, what):
+    got = np.asarray(got, dtype=np.float64).reshape(np.asarray(exp).shape)
+    exp = np.asarray(exp, dtype=np.float64)
+    scale = max(float(np.abs(exp).max()) if exp.size else 0.0, 1e-3)
+    e = float(np.abs(got - exp).max()) if exp.size else 0.0
+    assert e <= tol * scale, '%s: max abs err %.3e > %.1e * %.3e' % (what, e, tol, scale)
+
+
+@pytest.mark.parametrize('name', FIXTURES)
+def test_reference_matches_the_rank_fixtures(name):
+    """The same formulas against what the reference's own code computed (ref_head_rank2_train: identity, rank 2;
+    ref_head_rank3_relu_train): logits, the stacked attention maps, the loss and every gradient of the head's
+    variables and of the feature map, to 1e-12 (float32-stored tensors at storage rounding).  The fixture's gradients
+    are those of the total loss: the L2 regulariser adds weight_decay * w to every conv weight."""
+    fx = rf.HeadFixture(os.path.join(rf.GOLD, 'ref_head_%s.npz' % name))
+    q = rr.fixture_problem(fx)
+    R, N = q['R'], q['X'].shape[0]
+    fwd = rr.forward(q['X'], q['X'], q['Wa'], q['ba'], q['cw'], q['cb'], q['Wts'], q['bts'], q['relu'], q['mask'],
+                     q['keep'])
+    _close(fwd['logits'], fx.expected('out/logits'), fx.tol('out/logits'), 'logits')
+    _close(fwd['A'], fx.expected('out/ep/PosePrelogitsBasedAttention'), fx.tol('out/ep/PosePrelogitsBasedAttention'),
+           'attention maps')
+    p = torch.softmax(fwd['logits'], dim=1)
+    onehot = torch.nn.functional.one_hot(q['labels'], p.shape[1]).double()
+    loss = -(torch.log_softmax(fwd['logits'], dim=1) * onehot).sum(dim=1).mean()
+    _close(loss, fx.expected('out/losses')[0], fx.tol('out/losses'), 'loss')
+    bw = rr.backward(q['X'], q['X'], q['Wa'], q['cw'], q['Wts'], q['bts'], q['relu'], fwd, (p - onehot) / N,
+                     q['mask'], q['keep'])
+    wd = fx.meta['weight_decay']
+    grad = lambda vn: fx.expected('grad/var/' + vn).reshape(-1)
+    _close(bw['dX'].reshape(-1), fx.expected('grad/images').reshape(-1), fx.tol('grad/images'), 'dX')
+    a0 = q['att_names'][0]
+    _close(bw['dWa'] + wd * q['Wa'], grad(a0 + '/weights'), fx.tol('grad/var/' + a0 + '/weights'), 'dWa')
+    _close(bw['dba'].reshape(1), grad(a0 + '/biases'), fx.tol('grad/var/' + a0 + '/biases'), 'dba')
+    for r in range(R):
+        n = q['td_names'][r]
+        _close((bw['dWts'][r] + wd * q['Wts'][r]).reshape(-1), grad(n + '/weights'), fx.tol('grad/var/' + n + '/weights'),
+               n)
+        _close(bw['dbts'][r], grad(n + '/biases'), fx.tol('grad/var/' + n + '/biases'), n)
+    for r in range(R - 1):
+        n = q['att_names'][r + 1]
+        _close((bw['dcw'][r] + wd * q['cw'][r]).reshape(1), grad(n + '/weights'), fx.tol('grad/var/' + n + '/weights'), n)
+        _close(bw['dcb'][r].reshape(1), grad(n + '/biases'), fx.tol('grad/var/' + n + '/biases'), n)
+
+
+# ------------------------------------------------------------------------------------------ the C ABI
+def test_new_entry_points_are_declared_exported_and_bound():
+    header = open(os.path.join(ROOT, 'include', 'apa.h')).read()
+    header = re.sub(r'/\*.*?\*/', '', header, flags=re.S)
+    lib = cof.load_library()
+    for name in NEW:
+        m = re.search(r'\b%s\s*\(([^)]*)\)' % name, header)
+        assert m, '%s is not declared in include/apa.h' % name
+        nargs = len([a for a in m.group(1).split(',') if a.strip()])
+        assert hasattr(lib, name), name
+        assert len(cof._SIGNATURES[name][1]) == nargs, (name, nargs)
+    # the ctypes structure follows the header's field order
+    m = re.search(r'typedef\s+struct\s+apa_rank_maps\s*\{(.*?)\}\s*apa_rank_maps;', header, flags=re.S)
+    assert m, 'apa_rank_maps is not declared'
+    fields = []
+    for decl in m.group(1).split(';'):
+        decl = decl.strip()
+        if decl:
+            fields.append(re.search(r'(\w+)\s*(\[[^\]]*\])?\s*$', decl).group(1))
+    assert fields == [n for n, _ in cof.ApaRankMaps._fields_]
+    assert re.search(r'#define\s+APA_RANK_MAX\s+4\b', header) and cof.APA_RANK_MAX == 4
+    assert ctypes.sizeof(cof.ApaRankMaps) == 8 + 8 * 8 * (cof.APA_RANK_MAX - 1) + 8
+    assert lib.apa_version() >= 308
+
+
+def _maps(extra=1, hole=None):
+    """an apa_rank_maps whose first `extra` entries hold non-null pointers that are never dereferenced"""
+    p = 0x1000
+    rk = cof.ApaRankMaps()
+    rk.extra = extra
+    for r in range(max(0, min(extra, cof.APA_RANK_MAX - 1))):
+        for name in ('chain_w', 'chain_b', 'Wt', 'bt', 'dchain_w', 'dchain_b', 'dWt', 'dbt'):
+            getattr(rk, name)[r] = None if hole == (name, r) else p
+    rk.z0 = None if hole == ('z0', 0) else p
+    return rk
+
+
+def test_rank_entry_points_refuse_before_touching_a_device():
+    """R = 1 and R = 5 (`extra` out of range), M != 1, the softmax / relu-input / frozen-input flags, a null pointer
+    among the first `extra` entries: each returns its status with nothing launched (no GPU on this machine)."""
+    lib = cof.load_library()
+    p = 0x1000
+    err = lambda: lib.apa_last_error()
+
+    def fwd(rk, M=1, K=5, flags=0, C=256):
+        return lib.apa_attn_pool_rank_fwd(None if rk is None else ctypes.addressof(rk), p, p, p, p, p, p, p, p, p, p,
+                                          p, 1 << 30, 2, 4, C, C, K, M, flags, 0.5, 0, 0, 0, None)
+
+    def bwd(rk, M=1, K=5, flags=0):
+        return lib.apa_attn_pool_rank_bwd(None if rk is None else ctypes.addressof(rk), p, p, p, p, p, p, p, p, p, p,
+                                          p, None, p, p, p, p, p, 1 << 30, 2, 4, 256, 256, K, M, flags, 0.5, 0, 0, 0,
+                                          None)
+
+    def step(rk, M=1, K=5, flags=0, labels=p):
+        return lib.apa_attn_head_train_step_rank(None if rk is None else ctypes.addressof(rk), p, p, p, p, p, p, labels,
+                                                 1.0, 1.0, p, p, p, p, p, p, p, None, p, p, p, p, p, 1 << 30, 2, 4, 256,
+                                                 256, K, M, flags, 0.5, 0, 0, 0, None)
+    for call in (fwd, bwd, step):
+        assert call(None) == INVALID and b'null' in err()
+        for extra in (0, 4, -1, 7):                                   # R = 1, R = 5, ...
+            assert call(_maps(extra)) == INVALID and b'extra' in err(), extra
+        assert call(_maps(1), M=5, K=5) == UNSUPPORTED and b'M == 1' in err()          # per-class maps
+        assert call(_maps(1), M=3, K=5) == INVALID and b'M must be 1' in err()
+        assert call(_maps(1), flags=cof.APA_FLAG_SOFTMAX_ATT) == UNSUPPORTED and b'SOFTMAX_ATT' in err()
+        assert call(_maps(1), flags=cof.APA_FLAG_RELU_INPUT) == UNSUPPORTED and b'RELU_INPUT' in err()
+        assert call(_maps(1), flags=cof.APA_FLAG_FROZEN_INPUT) == UNSUPPORTED and b'FROZEN_INPUT' in err()
+        for name in ('chain_w', 'chain_b', 'Wt', 'bt'):
+            assert call(_maps(2, hole=(name, 1))) == INVALID and b'entry 1' in err(), name
+        assert call(_maps(3, hole=('z0', 0))) == INVALID and b'z0' in err()
+    for name in ('dchain_w', 'dchain_b', 'dWt', 'dbt'):                # the backward half's pointers
+        assert bwd(_maps(3, hole=(name, 2))) == INVALID and b'entry 2' in err(), name
+        assert step(_maps(3, hole=(name, 2))) == INVALID and b'entry 2' in err(), name
+        assert fwd(_maps(3, hole=(name, 2))) != INVALID or b'entry' not in err()     # the forward call does not ask
+    assert step(_maps(1), labels=None) == INVALID and b'null' in err()
+    assert fwd(_maps(1), C=4096) == UNSUPPORTED and b'2048' in err()              # beyond the widest instance
+    assert fwd(_maps(1), C=250) == UNSUPPORTED                                     # not whole 16-byte vectors
+    ws = lib.apa_attn_pool_rank_workspace_bytes
+    assert ws(2, 4, 256, 256, 5, 0) == 0 and ws(2, 4, 256, 256, 5, 4) == 0 and ws(0, 4, 256, 256, 5, 1) == 0
+    assert ws(2, 4, 256, 256, 5, 1) > lib.apa_attn_pool_workspace_bytes(2, 4, 256, 256, 5, 1, 0)
+    assert ws(2, 4, 256, 256, 5, 3) > ws(2, 4, 256, 256, 5, 1)
+
+
+def test_python_wrappers_check_the_rank_first():
+    N, P, C, K = 2, 4, 8, 3
+    X = torch.zeros(N, P, C)
+    Wa, ba = torch.zeros(C, 1), torch.zeros(1)
+    one = lambda: torch.zeros(1, 1)
+    for R in (1, 5):
+        with pytest.raises(cof.ApaError, match='rank %d outside 2..4' % R):
+            cof.attn_pool_rank_fwd(X, X, Wa, ba, [torch.zeros(C, K)] * R, [torch.zeros(K)] * R, [one()] * (R - 1),
+                                   [torch.zeros(1)] * (R - 1))
+    with pytest.raises(cof.ApaError, match='chain weights'):
+        cof.attn_pool_rank_fwd(X, X, Wa, ba, [torch.zeros(C, K)] * 3, [torch.zeros(K)] * 3, [one()], [torch.zeros(1)])
+
+
+# ------------------------------------------------------------------------------------------ deploy / nets_factory
+@pytest.mark.parametrize('case,R', [('rank2_train', 2), ('rank3_relu_train', 3)])
+def test_fused_head_step_takes_rank_2_and_3(case, R):
+    from attentionalpoolingaction_amd import deploy
+    try:
+        network_fn, cfg = rr.network(case)
+        head = network_fn.head
+        assert head.rank == R and head.single_layer
+        assert deploy.FusedHeadStep.unsupported_reason(head, cfg, network_fn) == ''
+        fused = deploy.FusedHeadStep(network_fn, cfg)
+        tfn = head.tf_variable_names()
+        per_rank = ['%s.%d' % (a, r) for r in range(R - 1)
+                    for a in ('att_weights_r', 'att_biases_r', 'td_weights_r', 'td_biases_r')]
+        for n in per_rank:
+            assert n in fused.params and n in fused.bucket.views and fused.tf_names[n] == tfn[n], n
+            attr, r = n.split('.')
+            assert fused.params[n] is getattr(head, attr)[int(r)]
+            assert fused.bucket.views[n].shape == fused.params[n].shape
+            assert n in fused._written
+        C, K = head.in_channels, head.num_classes
+        assert fused.bucket.views['td_weights_r.0'].numel() == C * K and fused.bucket.views['att_weights_r.0'].numel() == 1
+        sizes = sum(p.numel() for p in fused.params.values())
+        assert fused.bucket.flat.numel() == sizes
+        assert set(fused.regularized) == {'pose_w1', 'pose_w2', 'att_weights', 'td_weights'} | \
+            {n for n in per_rank if 'weights' in n}
+        # TRAIN.TRAINABLE_SCOPES splits the per-rank variables by their tf names like the others
+        cfg.TRAIN.TRAINABLE_SCOPES = PRE + 'Conv_1,' + PRE + 'Conv2d_PrePose_Attn1'
+        scoped = deploy.FusedHeadStep(network_fn, cfg)
+        assert set(scoped.trained) == {'att_weights_r.0', 'att_biases_r.0', 'td_weights_r.0', 'td_biases_r.0'}
+        assert set(scoped.bucket.views) == set(scoped.trained)
+    finally:
+        apa_config.reset_cfg()
+
+
+P_ = rf.P
+
+
+@pytest.mark.parametrize('net,train_cfg,kw,word', [
+    ({P_ + '_PER_CLASS': True}, {}, {}, 'per-class'),
+    ({P_ + '_WITH_POSE_FEAT': True}, {}, {}, '_WITH_POSE_FEAT'),
+    ({}, {}, {'want_topdown': True}, 'TopDownAttention'),
+    ({}, {'LOSS_FN_ACTION': 'multi-label'}, {}, 'multi-label'),
+    ({}, {'LOSS_FN_ACTION': 'multi-label-2'}, {}, 'multi-label-2'),
+    ({P_ + '_SINGLE_LAYER_ATT': False}, {'LOSS_FN_POSE': 'l2'}, {}, 'pose_pre_logits'),
+    ({P_ + '_RANK': 5}, {}, {}, 'rank 5'),
+])
+def test_fused_head_step_still_refuses_the_other_rank_forms(net, train_cfg, kw, word):
+    from attentionalpoolingaction_amd import deploy
+    try:
+        network_fn, cfg = rr.network('rank2_train', net, train_cfg, **kw)
+        why = deploy.FusedHeadStep.unsupported_reason(network_fn.head, cfg, network_fn)
+        assert why and word in why, why
+        with pytest.raises(ValueError):
+            deploy.FusedHeadStep(network_fn, cfg)
+    finally:
+        apa_config.reset_cfg()
+
+
+def test_fused_head_step_refuses_clips_at_rank_2():
+    from attentionalpoolingaction_amd import deploy
+    try:
+        network_fn, cfg = rr.network('rank2_train')
+        fused = deploy.FusedHeadStep(network_fn, cfg)
+        with pytest.raises(ValueError, match='clip batch'):
+            fused(torch.zeros(2, 3, 4, 4, 32), torch.zeros(2, dtype=torch.int64))
+    finally:
+        apa_config.reset_cfg()
+
+
+@pytest.mark.parametrize('case', FIXTURES)
+def test_fuse_ranks_changes_no_parameter(case):
+    """get_network_fn(..., fuse_ranks=True): the same parameter names, shapes and tf names; the routing flag is on
+    exactly for the forms the one op serves; the default is off."""
+    try:
+        a, _ = rr.network(case)
+        b, _ = rr.network(case, fuse_ranks=True)
+        pa, pb = dict(a.head.named_parameters()), dict(b.head.named_parameters())
+        assert list(pa) == list(pb) and all(pa[n].shape == pb[n].shape for n in pa)
+        assert a.head.tf_variable_names() == b.head.tf_variable_names()
+        assert not a.head.fuse_ranks and not a.head.ranks_fused() and b.head.ranks_fused()
+        for net, kw in (({P_ + '_PER_CLASS': True}, {}), ({P_ + '_WITH_POSE_FEAT': True}, {}),
+                        ({}, {'want_topdown': True}), ({P_ + '_RANK': 1}, {}), ({P_ + '_RANK': 5}, {})):
+            c, _ = rr.network(case, net, fuse_ranks=True, **kw)
+            assert c.head.fuse_ranks and not c.head.ranks_fused(), (net, kw)
+        d, _ = rr.network(case, {P_ + '_SINGLE_LAYER_ATT': False}, fuse_ranks=True)      # attention from pose_pre_logits
+        assert d.head.ranks_fused()
+    finally:
+        apa_config.reset_cfg()
+
+
+# ------------------------------------------------------------------------------------------ the GPU case table
+@pytest.mark.parametrize('c', rr.CASES, ids=[c['name'] for c in rr.CASES])
+def test_gpu_case_inputs_meet_the_gate_condition(c):
+    """In the float64 reference alone (no kernel involved): at most 3 % of a case's N P R relu gates lie within their
+    bound of zero, and every rank has between 10 % and 90 % of its gates open (closed_rank: exempt, its rank 2 is
+    closed everywhere).  Identity cases: the same spread of signs, so a negative map is exercised."""
+    inp = rr.inputs(c)
+    assert inp['X'].dtype == (torch.bfloat16 if c['bf16'] else torch.float32)
+    assert float(inp['X'].float().min()) == 0.0 and [float(w) for w in inp['cw']] == \
+        [float(torch.tensor(w)) for w in rr.CHAIN_W[:c['R'] - 1]]
+    _, amb, opened = rr.forward_bnd(c, inp, None)
+    if amb is None:
+        amb = torch.zeros_like(opened)
+    excl, opn = rr.check_gate_condition(c, amb, opened)
+    if c['b2'] is not None:
+        assert opn[2] == 0.0 and 0.10 <= opn[0] <= 0.90 and 0.10 <= opn[1] <= 0.90

@@ -41,6 +41,13 @@ headline stays the cfg 002 training workload); run this file directly for one wo
             calls deploy.FusedHeadEval made before that entry point existed (HeadEvalStep.run, cof.frame_pool_fwd,
             eval_utils.predict).
 
+  rank2_002 / rank3_002
+            NET.USE_POSE_PRELOGITS_BASED_ATTENTION_RANK = 2 (identity attention) / 3 (relu) on the cfg 002 shape (32 x
+            14x14x2048 fp32, K = 393, training).  Three variants alternate in one process, medians of five: `rank_one_call`
+            (apa_attn_head_train_step_rank: all R maps in one pass over conv5 per direction), `module_path` (network_fn
+            with fuse_ranks=False + gen_losses + autograd: two or R passes of the rank-1 op) and `rank1_one_call`, the
+            rank-1 one-call step of the same shape, for scale.
+
 Each builder returns (step_fn, info): `step_fn()` enqueues one step on the current stream; `info`
 carries the workload name and the algorithmic work per image.
 """
@@ -381,6 +388,125 @@ def build_rank1(cof, dev, N=32, H=14, K=51, dtype='bf16', rotate=0):
             'bound': 'hbm', 'dtype': dtype, 'N': N, 'rotate': R, 'flops_per_image': 0.0,
             'bytes_per_image': 3.0 * P * C * X.element_size()}
     return _round_robin([st.run for st in sts]), info
+
+
+RANK_WORKLOADS = {'rank2_002': (2, False), 'rank3_002': (3, True)}      # (rank, relu attention)
+
+
+def build_rank(cof, dev, which, N=32, H=14, K=393, rotate=0):
+    """NET.USE_POSE_PRELOGITS_BASED_ATTENTION_RANK = 2 (identity attention) / 3 (relu) on the cfg 002 shape
+    (N x 14x14x2048 fp32, K = 393, training, keep 0.2), as round-robin step functions over rotating X sets:
+      'rank_one_call'   apa_attn_head_train_step_rank: all R maps in one pass over conv5 per direction
+      'module_path'     network_fn (fuse_ranks=False) + gen_losses + backward: two (identity) or R (relu) passes of
+                        the rank-1 op per direction, dX summed by autograd
+      'rank1_one_call'  the rank-1 one-call step of the same shape and activation, for scale (what the R small
+                        products and the wider streaming passes add)"""
+    from attentionalpoolingaction_amd import config as apa_config, loss as apa_loss, nets_factory
+    R, relu = RANK_WORKLOADS[which]
+    C, J, P = 2048, 16, H * H
+    g = torch.Generator().manual_seed(42)
+    per_set = 2 * N * P * C * 4
+    nsets = _n_sets(per_set, rotate)
+    Xs = [_features(N, P, C, torch.float32, dev, seed=42 + r) for r in range(nsets)]
+    labels = torch.randint(0, K, (N,), generator=g).to(dev)
+    apa_config.reset_cfg()
+    pre = 'USE_POSE_PRELOGITS_BASED_ATTENTION'
+    cfg = apa_config.cfg_from_dict({'MODEL_NAME': 'resnet_v1_101',
+                                    'NET': {pre: True, pre + '_SINGLE_LAYER_ATT': True, pre + '_RANK': R,
+                                            pre + '_RELU_ATT': relu},
+                                    'TRAIN': {'LOSS_FN_POSE': '', 'LOSS_FN_ACTION': 'softmax-xentropy'}})
+    network_fn = nets_factory.get_network_fn('resnet_v1_101', K, J, cfg, is_training=True, device=dev)
+    head = network_fn.head
+    with torch.no_grad():       # trained-looking values: maps of both signs, every rank's gates partly open
+        head.att_weights.copy_((torch.randn(C, 1, generator=g) / C ** 0.5).to(dev))
+        head.att_biases.fill_(0.1)
+        for r, (w, b) in enumerate(((-0.7, 0.2), (1.3, -0.15), (0.6, 0.1))[:R - 1]):
+            head.att_weights_r[r].fill_(w)
+            head.att_biases_r[r].fill_(b)
+        for t in [head.td_weights] + list(head.td_weights_r):
+            t.copy_((torch.randn(C, K, generator=g) / C ** 0.5).to(dev))
+    params = list(head.parameters())
+    p = {n: t.data for n, t in head.named_parameters()}
+    Wts = [p['td_weights']] + [p['td_weights_r.%d' % r] for r in range(R - 1)]
+    bts = [p['td_biases']] + [p['td_biases_r.%d' % r] for r in range(R - 1)]
+    cws = [p['att_weights_r.%d' % r] for r in range(R - 1)]
+    cbs = [p['att_biases_r.%d' % r] for r in range(R - 1)]
+    flags = cof.attn_flags(False, relu, True)
+    like = lambda ts: [torch.empty_like(t) for t in ts]
+    pg = (torch.empty_like(p['att_weights']), torch.empty_like(p['att_biases']), like(Wts), like(bts), like(cws),
+          like(cbs))
+    dXs = [torch.empty_like(x) for x in Xs]
+    rank_steps, one_steps = [], []
+    for r in range(nsets):
+        rank_steps.append(cof.RankHeadTrainStep(
+            Xs[r], Xs[r], p['att_weights'], p['att_biases'], Wts, bts, cws, cbs, labels, (dXs[r], None) + pg,
+            flags=flags, keep_prob=head.keep_prob, seed=42, offset=r,
+            workspace=rank_steps[0].workspace if rank_steps else None))
+        one_steps.append(cof.HeadTrainStep(
+            Xs[r], Xs[r], p['att_weights'], p['att_biases'], Wts[0], bts[0], labels,
+            (dXs[r], None, pg[0], pg[1], pg[2][0], pg[3][0]), flags=flags, keep_prob=head.keep_prob, seed=42, offset=r,
+            share_with=one_steps[0] if one_steps else None))
+    feats = [x.view(N, H, H, C).requires_grad_(True) for x in Xs]
+    tc = cfg.TRAIN
+
+    def module_run(r):
+        for t in params:
+            t.grad = None
+        feats[r].grad = None
+        logits, ep = network_fn(feats[r])
+        losses = apa_loss.gen_losses(labels, logits, tc.LOSS_FN_ACTION, K, tc.LOSS_FN_ACTION_WT, None, None, '', None,
+                                     tc.LOSS_FN_POSE_WT, ep, cfg)
+        sum(losses).backward()
+
+    steps = {'rank_one_call': _round_robin([st.run for st in rank_steps]),
+             'module_path': _round_robin([(lambda r=r: module_run(r)) for r in range(nsets)]),
+             'rank1_one_call': _round_robin([st.run for st in one_steps])}
+    info = {'workload': 'rank {} ({} attention) on one bottom-up map, cfg 002 shape: per-GPU batch {} x {}x{}x{} fp32, '
+                        'K={}, training, keep={}: one-call rank step vs module path (fuse_ranks=False) vs the rank-1 '
+                        'one-call step'.format(R, 'relu' if relu else 'identity', N, H, H, C, K, head.keep_prob) +
+                        _rot_note(nsets, per_set),
+            'bound': 'hbm', 'dtype': 'f32', 'N': N, 'rotate': nsets, 'flops_per_image': 0.0,
+            'bytes_per_image': 3.0 * P * C * 4, 'rank': R}
+    return steps, info
+
+
+def run_rank(cof, dev, args, which):
+    """The three variants alternate inside every round (one process, same clocks): per variant the median over five
+    (or more) rounds of the mean step time of a loop of `steps` steps, and the spread (max - min) of its rounds."""
+    steps, info = build_rank(cof, dev, which, args.batch, args.hw, args.classes or 393, rotate=args.rotate)
+    if args.only:
+        steps = {args.only: steps[args.only]}
+    for fn in steps.values():
+        for _ in range(max(args.warmup, info['rotate'])):
+            fn()
+    torch.cuda.synchronize()
+    per = {k: [] for k in steps}
+    rounds = 0
+    t_all = time.perf_counter()
+    while rounds < 5 or time.perf_counter() - t_all < 0.5:
+        for k, fn in steps.items():
+            t0 = time.perf_counter()
+            for _ in range(args.steps):
+                fn()
+            torch.cuda.synchronize()
+            per[k].append((time.perf_counter() - t0) / args.steps)
+        rounds += 1
+        if rounds >= 200:
+            break
+    med = {k: sorted(v)[len(v) // 2] for k, v in per.items()}
+    out = report(info, med.get('rank_one_call', next(iter(med.values()))), rounds)
+    out['rank'] = info['rank']
+    out['us_per_step'] = {k: round(v * 1e6, 2) for k, v in med.items()}
+    out['us_per_step_min'] = {k: round(min(v) * 1e6, 2) for k, v in per.items()}
+    out['us_spread'] = {k: round((max(v) - min(v)) * 1e6, 2) for k, v in per.items()}
+    if 'rank_one_call' in med and 'module_path' in med:
+        gain = (med['module_path'] - med['rank_one_call']) * 1e6
+        out['module_over_one_call'] = round(med['module_path'] / med['rank_one_call'], 3)
+        out['faster_by_more_than_the_spreads'] = bool(gain > max(out['us_spread']['rank_one_call'],
+                                                                 out['us_spread']['module_path']))
+    if 'rank_one_call' in med and 'rank1_one_call' in med:
+        out['one_call_over_rank1'] = round(med['rank_one_call'] / med['rank1_one_call'], 3)
+    return out
 
 
 def build_multilabel(cof, dev, which, B=32, F=1, H=14, K=600, rotate=0, kind='multi-label'):
@@ -991,13 +1117,13 @@ def main():
     ap.add_argument('--workload', default='cfg003', choices=['cfg003', 'perclass', 'eval002', 'eval003', 'rank1', 'posebwd', 'posebwd_acc', 'update003',
                                                          'update_perclass', 'poseatt', 'video_perclass', 'video003',
                                                          'hico002', 'charades_clips', 'frozen002', 'frozen003',
-                                                         'frozen_perclass'] + sorted(EVAL_CLIPS))
+                                                         'frozen_perclass'] + sorted(EVAL_CLIPS) + sorted(RANK_WORKLOADS))
     ap.add_argument('--clips', type=int, default=8, help='video_*: clips per batch')
     ap.add_argument('--frames', type=int, default=4, help='video_*: frames per clip')
     ap.add_argument('--only', default=None, choices=['clip_one_call', 'module_path', 'flat_one_call',
                                                      'multilabel_one_call', 'softmax_one_call', 'one_call',
-                                                     'sequence'],
-                    help='video_* / hico002 / charades_clips / eval_*: run one variant alone (kernel traces)')
+                                                     'sequence', 'rank_one_call', 'rank1_one_call'],
+                    help='video_* / hico002 / charades_clips / eval_* / rank*: run one variant alone (kernel traces)')
     ap.add_argument('--batch', type=int, default=32)
     ap.add_argument('--hw', type=int, default=14)
     ap.add_argument('--classes', type=int, default=None)
@@ -1031,6 +1157,9 @@ def main():
         return
     if args.workload in EVAL_CLIPS:
         print(json.dumps(run_eval_clips(cof, dev, args, args.workload)))
+        return
+    if args.workload in RANK_WORKLOADS:
+        print(json.dumps(run_rank(cof, dev, args, args.workload)))
         return
     if args.workload.startswith('frozen'):
         print(json.dumps(run_frozen(cof, dev, args, args.workload)))
