@@ -62,7 +62,8 @@ extern "C" const char* apa_status_string(int status) {
   }
 }
 
-static int check_common(const char* fn, const PoolDims& d) {
+// fp8_ok: the entry point serves an FP8 feature cache (PoolCall::fp8_ok); every other one answers "unknown dtype"
+static int check_common(const char* fn, const PoolDims& d, bool fp8_ok = false) {
   if (d.N <= 0 || d.P <= 0 || d.C <= 0 || d.Ca <= 0 || d.K <= 0) {
     set_error("%s: non-positive dimension N=%d P=%d C=%d Ca=%d K=%d", fn, d.N, d.P, d.C, d.Ca, d.K);
     return APA_ERR_INVALID_ARG;
@@ -71,8 +72,37 @@ static int check_common(const char* fn, const PoolDims& d) {
     set_error("%s: M must be 1 (class-agnostic) or K (per-class), got M=%d K=%d", fn, d.M, d.K);
     return APA_ERR_INVALID_ARG;
   }
-  if (d.dtype != APA_DTYPE_F32 && d.dtype != APA_DTYPE_BF16) {
+  if (d.dtype != APA_DTYPE_F32 && d.dtype != APA_DTYPE_BF16 && !(fp8_ok && d.dtype == APA_DTYPE_FP8_E4M3)) {
     set_error("%s: unknown dtype %d", fn, d.dtype);
+    return APA_ERR_INVALID_ARG;
+  }
+  return APA_OK;
+}
+
+// What a call on an FP8 feature cache (APA_DTYPE_FP8_E4M3, apa.h) refuses, each reason by name and before anything is
+// launched.  backward: a backward call or the backward half of a one-call step -- a cache has no gradient.
+static int fp8_check(const char* fn, const PoolCall& d, const void* X, const void* Xatt, bool topdown, bool backward,
+                     const void* dX) {
+  if (d.dtype != APA_DTYPE_FP8_E4M3) return APA_OK;
+  const char* why = d.M != 1 ? "per-class maps (M != 1)"
+                    : Xatt != X ? "a separate attention input (Xatt != X)"
+                    : d.C % 16 != 0 ? "a channel count that is not a multiple of 16"
+                    : d.C > M1F_MAX_C ? "more than 8192 channels"
+                    : (d.flags & APA_FLAG_SOFTMAX_ATT) ? "APA_FLAG_SOFTMAX_ATT"
+                    : (d.flags & APA_FLAG_RELU_INPUT) ? "APA_FLAG_RELU_INPUT"
+                    : (d.flags & APA_FLAG_RNG_EXTERNAL) ? "APA_FLAG_RNG_EXTERNAL"
+                    : topdown ? "the TopDownAttention dump" : nullptr;
+  if (why) {
+    set_error("%s: APA_DTYPE_FP8_E4M3 does not serve %s (M=%d C=%d): the FP8 cache feeds the fused class-agnostic head "
+              "with identity or relu attention", fn, why, d.M, d.C);
+    return APA_ERR_UNSUPPORTED;
+  }
+  if (backward && (!(d.flags & APA_FLAG_FROZEN_INPUT) || dX)) {
+    set_error("%s: APA_DTYPE_FP8_E4M3 needs APA_FLAG_FROZEN_INPUT and a NULL dX: a feature cache has no gradient", fn);
+    return APA_ERR_INVALID_ARG;
+  }
+  if (reinterpret_cast<uintptr_t>(X) & 15) {
+    set_error("%s: APA_DTYPE_FP8_E4M3 features must be 16-byte aligned", fn);
     return APA_ERR_INVALID_ARG;
   }
   return APA_OK;
@@ -99,6 +129,11 @@ static PoolCall pool_call(const PoolDims& dims, unsigned flags, float keep_prob,
                           const apa_concat_feat* cat = nullptr) {
   return PoolCall{dims, flags & APA_PUBLIC_FLAGS & ~APA_FLAG_WS_FROM_FWD, keep_prob, seed, offset, ws, ws_bytes,
                   static_cast<hipStream_t>(stream), Hooks(hooks), cat};
+}
+// ... of an entry point that serves an FP8 feature cache: the plain pooling calls and the attention head's one-call steps
+static PoolCall fp8_served(PoolCall d) {
+  d.fp8_ok = d.cat == nullptr;
+  return d;
 }
 
 // APA_FLAG_RNG_EXTERNAL: `seed` carries the address of the caller's keep bits
@@ -146,7 +181,7 @@ static int pool_check(const PoolCall& d, const M1Fwd* f, const M1Bwd* b) {
   const void* const X = b ? b->X : f->X;
   const void* const Xatt = b ? b->Xatt : f->Xatt;
   const bool topdown = f && f->topdown;
-  int rc = check_common(fn, d);
+  int rc = check_common(fn, d, d.fp8_ok);
   if (rc != APA_OK) return rc;
   if (f ? !X || !Xatt || !f->Wa || !f->ba || !f->Wt || !f->bt || !f->logits || !f->att
         : !X || !Xatt || !b->Wa || !b->Wt || !b->bt || !b->att || !b->G ||
@@ -154,6 +189,7 @@ static int pool_check(const PoolCall& d, const M1Fwd* f, const M1Bwd* b) {
     set_error("%s: null tensor pointer", fn);
     return APA_ERR_INVALID_ARG;
   }
+  if ((rc = fp8_check(fn, d, X, Xatt, topdown, b != nullptr, b ? b->dX : nullptr)) != APA_OK) return rc;
   if (f && Xatt == X && d.Ca != d.C) {
     set_error("%s: Xatt aliases X but Ca=%d != C=%d", fn, d.Ca, d.C);
     return APA_ERR_INVALID_ARG;
@@ -269,8 +305,8 @@ extern "C" int apa_attn_pool_fwd_cat(const apa_concat_feat* cat, const apa_hooks
                                      void* topdown, void* ws, size_t ws_bytes, int N, int P, int C, int Ca, int K,
                                      int M, unsigned flags, float keep_prob, uint64_t seed, uint64_t offset, int dtype,
                                      void* stream) {
-  return attn_pool_fwd(pool_call({N, P, C, Ca, K, M, dtype}, flags, keep_prob, seed, offset, ws, ws_bytes, stream,
-                                 hooks, cat),
+  return attn_pool_fwd(fp8_served(pool_call({N, P, C, Ca, K, M, dtype}, flags, keep_prob, seed, offset, ws, ws_bytes,
+                                            stream, hooks, cat)),
                        M1Fwd{X, Xatt, Wa, ba, Wt, bt, logits, att, zsave, abar, topdown}, nullptr);
 }
 
@@ -300,8 +336,8 @@ extern "C" int apa_attn_pool_bwd_cat(const apa_concat_feat* cat, const apa_hooks
                                      unsigned flags, float keep_prob, uint64_t seed, uint64_t offset, int dtype,
                                      void* stream) {
   (void)ba;
-  return attn_pool_bwd(pool_call({N, P, C, Ca, K, M, dtype}, flags, keep_prob, seed, offset, ws, ws_bytes, stream,
-                                 hooks, cat),
+  return attn_pool_bwd(fp8_served(pool_call({N, P, C, Ca, K, M, dtype}, flags, keep_prob, seed, offset, ws, ws_bytes,
+                                            stream, hooks, cat)),
                        M1Bwd{X, Xatt, Wa, Wt, bt, att, zsave, abar, G, dX, dXatt, dWa, dba, dWt, dbt}, nullptr);
 }
 
@@ -501,7 +537,7 @@ static int clip_step_check(const char* fn, const PoolCall& d, const StepLoss& L,
     set_error("%s: null clip / labels / loss / logits / G pointer", fn);
     return APA_ERR_INVALID_ARG;
   }
-  const int rc = check_common(fn, d);
+  const int rc = check_common(fn, d, d.fp8_ok);
   if (rc != APA_OK) return rc;
   if (clip->frames <= 0 || d.N % clip->frames != 0) {
     set_error("%s: N=%d is not a whole number of clips of %d frames", fn, d.N, clip->frames);
@@ -581,8 +617,13 @@ static int head_step_run(PoolCall d, const StepLoss& L, const M1Fwd& f, const M1
   d.ws_bytes = pool_bytes;
   const unsigned flags = d.flags;
   int rc = APA_OK;
+  // what the backward half refuses about an FP8 cache (a training step on one is a frozen step), before the forward half
+  if (d.fp8_ok && d.dtype == APA_DTYPE_FP8_E4M3 && f.X && f.Xatt) {
+    if ((rc = check_common("apa_attn_head_train_step", d, true)) != APA_OK) return rc;
+    if ((rc = fp8_check("apa_attn_head_train_step", d, f.X, f.Xatt, false, true, b.dX)) != APA_OK) return rc;
+  }
   if ((flags & APA_FLAG_FROZEN_INPUT) && f.X && f.Xatt) {   // the backward half's refusal of the flag, before the forward half
-    if ((rc = check_common("apa_attn_head_train_step", d)) != APA_OK) return rc;
+    if ((rc = check_common("apa_attn_head_train_step", d, d.fp8_ok)) != APA_OK) return rc;
     if ((rc = frozen_input_check("apa_attn_head_train_step", d, flags, f.X, f.Xatt)) != APA_OK) return rc;
   }
   M1Xent xf;
@@ -610,7 +651,8 @@ extern "C" int apa_attn_head_train_step_ex(const apa_hooks* hooks, const void* X
                                            int C, int Ca, int K, int M, unsigned flags, float keep_prob, uint64_t seed,
                                            uint64_t offset, int dtype, void* stream) {
   return head_step("apa_attn_head_train_step",
-                   pool_call({N, P, C, Ca, K, M, dtype}, flags, keep_prob, seed, offset, ws, ws_bytes, stream, hooks),
+                   fp8_served(pool_call({N, P, C, Ca, K, M, dtype}, flags, keep_prob, seed, offset, ws, ws_bytes, stream,
+                                        hooks)),
                    StepLoss{nullptr, labels, false, nullptr, loss_wt, grad_scale, loss, G},
                    M1Fwd{X, Xatt, Wa, ba, Wt, bt, logits, att, zsave, abar},
                    M1Bwd{X, Xatt, Wa, Wt, bt, att, zsave, abar, G, dX, dXatt, dWa, dba, dWt, dbt});
@@ -637,7 +679,8 @@ extern "C" int apa_attn_head_train_step_clips(const apa_clip_pool* clip, const a
                                               int M, unsigned flags, float keep_prob, uint64_t seed, uint64_t offset,
                                               int dtype, void* stream) {
   return head_step("apa_attn_head_train_step_clips",
-                   pool_call({N, P, C, Ca, K, M, dtype}, flags, keep_prob, seed, offset, ws, ws_bytes, stream, hooks),
+                   fp8_served(pool_call({N, P, C, Ca, K, M, dtype}, flags, keep_prob, seed, offset, ws, ws_bytes, stream,
+                                        hooks)),
                    StepLoss{nullptr, labels, true, clip, loss_wt, grad_scale, loss, G},
                    M1Fwd{X, Xatt, Wa, ba, Wt, bt, logits, att, zsave, abar},
                    M1Bwd{X, Xatt, Wa, Wt, bt, att, zsave, abar, G, dX, dXatt, dWa, dba, dWt, dbt});
@@ -656,7 +699,8 @@ extern "C" int apa_attn_head_train_step_multilabel(const apa_multilabel* ml, con
   const int rc = check_multilabel("apa_attn_head_train_step_multilabel", ml);
   if (rc != APA_OK) return rc;
   return head_step("apa_attn_head_train_step_multilabel",
-                   pool_call({N, P, C, Ca, K, M, dtype}, flags, keep_prob, seed, offset, ws, ws_bytes, stream, hooks),
+                   fp8_served(pool_call({N, P, C, Ca, K, M, dtype}, flags, keep_prob, seed, offset, ws, ws_bytes, stream,
+                                        hooks)),
                    StepLoss{ml, nullptr, clip != nullptr, clip, loss_wt, grad_scale, loss, G},
                    M1Fwd{X, Xatt, Wa, ba, Wt, bt, logits, att, zsave, abar},
                    M1Bwd{X, Xatt, Wa, Wt, bt, att, zsave, abar, G, dX, dXatt, dWa, dba, dWt, dbt});
@@ -914,7 +958,7 @@ extern "C" int apa_attn_head_eval_step_clips(const apa_clip_pool* clip, int scor
   const int rc = eval_scores_check(fn, clip, scores_kind, N, K, logits, labels, loss, probs, pred);
   if (rc != APA_OK) return rc;
   return attn_head_eval_clips(fn, clip, scores_kind,
-                              pool_call({N, P, C, Ca, K, M, dtype}, flags, 1.0f, 0, 0, ws, ws_bytes, stream),
+                              fp8_served(pool_call({N, P, C, Ca, K, M, dtype}, flags, 1.0f, 0, 0, ws, ws_bytes, stream)),
                               M1Fwd{X, Xatt, Wa, ba, Wt, bt, logits, att, zsave, abar}, labels, loss, probs, pred);
 }
 
@@ -923,7 +967,7 @@ extern "C" int apa_attn_head_eval_step(const void* X, const void* Xatt, const fl
                                        float* att, float* zsave, float* abar, float* loss, float* probs, int64_t* pred,
                                        void* ws, size_t ws_bytes, int N, int P, int C, int Ca, int K, int M,
                                        unsigned flags, int dtype, void* stream) {
-  return attn_head_eval(pool_call({N, P, C, Ca, K, M, dtype}, flags, 1.0f, 0, 0, ws, ws_bytes, stream),
+  return attn_head_eval(fp8_served(pool_call({N, P, C, Ca, K, M, dtype}, flags, 1.0f, 0, 0, ws, ws_bytes, stream)),
                         M1Fwd{X, Xatt, Wa, ba, Wt, bt, logits, att, zsave, abar}, labels, loss, probs, pred);
 }
 

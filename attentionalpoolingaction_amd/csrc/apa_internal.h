@@ -255,6 +255,7 @@ struct PoolCall : PoolDims {
   unsigned flags = 0; float keep_prob = 1.f; uint64_t seed = 0, offset = 0;
   void* ws = nullptr; size_t ws_bytes = 0; hipStream_t st = nullptr; Hooks hk;
   const apa_concat_feat* cat = nullptr;   // checked by the entry point (check_cat) before either path sees it
+  bool fp8_ok = false;   // the entry point serves APA_DTYPE_FP8_E4M3 (apa_capi.hip: fp8_served); else "unknown dtype"
 };
 
 struct M1Plan {
@@ -269,7 +270,7 @@ M1Plan m1_plan(int N, int P, int C, int Ca, int K);
 
 // What the M == 1 path ran (filled on the host only, read by the kernel-level tests through the test-only probe
 // library).  The product never sets the pointer: m1_trace() is null there and nothing is recorded.
-enum M1Pool { M1_POOL_NONE = 0, M1_POOL_STREAM, M1_POOL_VEC, M1_POOL_GENERIC };
+enum M1Pool { M1_POOL_NONE = 0, M1_POOL_STREAM, M1_POOL_VEC, M1_POOL_GENERIC, M1_POOL_FP8 };
 // (4 was the retired partial-logits form; the values are part of the probe interface and stay put)
 enum M1Logits { M1_LOGITS_NONE = 0, M1_LOGITS_XENT, M1_LOGITS_XENT_PROBS, M1_LOGITS2, M1_LOGITS_SGEMM = 5,
                 M1_LOGITS_ML = 6 };
@@ -347,6 +348,12 @@ int m1v_launch_bwd_main(const M1Call& c, const M1Bwd& io);
 bool m1g_supported(int C, int dtype);   // apa_m1_generic.hip: any C (run-time channel loop, LDS accumulators)
 int m1g_launch_pool_fwd(const M1Call& c, const M1Fwd& io);
 int m1g_launch_bwd_main(const M1Call& c, const M1Bwd& io);
+// apa_m1_fp8.hip: an FP8 feature cache (APA_DTYPE_FP8_E4M3; io.X: codes, then the per-image scales): fused attention,
+// identity / relu, no dX -- pool_check (apa_capi.hip) refuses everything else before a call gets here
+constexpr int M1F_MAX_C = 8192;
+bool m1f_supported(int C);
+int m1f_launch_pool_fwd(const M1Call& c, const M1Fwd& io);
+int m1f_launch_bwd_main(const M1Call& c, const M1Bwd& io);
 // the attention GEMV of a separate attention input as launches of their own (apa_m1.hip; m1_forward / m1_backward run
 // the same): Z = Xatt . Wa + ba with c.act into io.att; dXatt / the dWa, dba partials from c.dzatt over *nred blocks
 int m1_att_gemv_forward(const M1Call& c, const M1Fwd& io);

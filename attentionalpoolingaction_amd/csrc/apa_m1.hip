@@ -16,7 +16,7 @@
 // This file: the stages every pooling family shares (finalize, the attention GEMV forward / backward for a separate
 // Xatt, softmax rows, the fallback reduce) and the host dispatch.  The two streaming passes themselves come in three
 // families behind one pair of launchers each: apa_m1_stream.hip (wide maps), apa_m1_vec.hip (narrow powers of two),
-// apa_m1_generic.hip (any C).
+// apa_m1_generic.hip (any C); a fourth, apa_m1_fp8.hip, reads an FP8 feature cache.
 #include <math.h>
 
 #include "apa_device.h"
@@ -316,6 +316,7 @@ thread_local M1FwdRoute g_m1_fwd_route = {0, 0};
 // kernels (apa_m1_stream.hip) for the wide benchmark shapes, the per-pixel kernels (apa_m1_vec.hip) for the
 // other powers of two, the run-time-loop kernels of apa_m1_generic.hip for everything else.
 bool m1_supported(int C, int Ca, int dtype, bool fused) {
+  if (dtype == APA_DTYPE_FP8_E4M3) return fused && m1f_supported(C);
   const int epv = dtype == APA_DTYPE_BF16 ? 8 : 4;
   if (!fused && (Ca % epv != 0)) return false;
   return m1s_supported(C, dtype) || m1v_supported(C, dtype) || m1g_supported(C, dtype);
@@ -387,7 +388,8 @@ int m1_call_fill(M1Call& c, const PoolCall& d, const M1Fwd* f, const M1Bwd* b, c
   c.small = b && m1_small_route_ok(C, K, b->G, b->Wt, b->zsave);
   const int epv = dtype == APA_DTYPE_F32 ? 4 : 8;
   c.gemv2 = Ca % epv == 0 && Ca / epv <= 256;
-  c.pool = !c.ext && m1s_supported(C, dtype) ? M1_POOL_STREAM
+  c.pool = dtype == APA_DTYPE_FP8_E4M3 ? M1_POOL_FP8
+           : !c.ext && m1s_supported(C, dtype) ? M1_POOL_STREAM
            : !c.ext && m1v_supported(C, dtype) ? M1_POOL_VEC : M1_POOL_GENERIC;
   c.pl = m1_plan(N, P, C, Ca, K);
   char* w = static_cast<char*>(ws);
@@ -417,6 +419,13 @@ int m1_call_fill(M1Call& c, const PoolCall& d, const M1Fwd* f, const M1Bwd* b, c
   }
 
   // ---- every refusal of the path: nothing has been launched yet ----
+  // an FP8 cache: the entry points (pool_check, apa_capi.hip) name each reason; a call built inside the library that
+  // reaches here with one of them is refused all the same
+  if (c.pool == M1_POOL_FP8 && (!c.fused || c.act == M1_ACT_SOFTMAX || c.relu_input || c.ext || cat || (b && !c.no_dx) ||
+                                (flags & APA_IFLAG_NO_DX) || !m1f_supported(C))) {
+    set_error("attn_pool M=1: APA_DTYPE_FP8_E4M3 serves the fused identity / relu head on frozen features only");
+    return APA_ERR_UNSUPPORTED;
+  }
   // the streaming kernels split an image's pixels in 32-bit arithmetic (m1_pix_range); the other families keep 64 bits
   if (c.pool == M1_POOL_STREAM && !m1_pix_range_ok(P, c.pl.S)) {
     set_error("attn_pool M=1: P=%d pixels per image in S=%d splits: (S + 1) * P does not fit 31 bits", P, c.pl.S);
@@ -488,6 +497,7 @@ int m1_forward(const M1Call& c, const M1Fwd& io, M1Xent* xf) {
   switch (c.pool) {
     case M1_POOL_STREAM: rc = m1s_launch_pool_fwd(c, io); break;
     case M1_POOL_VEC: rc = m1v_launch_pool_fwd(c, io); break;
+    case M1_POOL_FP8: rc = m1f_launch_pool_fwd(c, io); break;
     default: rc = m1g_launch_pool_fwd(c, io);
   }
   if (rc != APA_OK) return rc;
@@ -625,6 +635,7 @@ int m1_backward(const M1Call& c, const M1Bwd& io, const M1Xent* xf) {
   switch (c.pool) {
     case M1_POOL_STREAM: rc = m1s_launch_bwd_main(c, io); break;
     case M1_POOL_VEC: rc = m1v_launch_bwd_main(c, io); break;
+    case M1_POOL_FP8: rc = m1f_launch_bwd_main(c, io); break;
     default: rc = m1g_launch_bwd_main(c, io);
   }
   if (rc != APA_OK) return rc;

@@ -27,6 +27,7 @@ LIB_PATH = os.path.join(ROOT_PATH, LIB_NAME)
 
 APA_DTYPE_F32 = 0
 APA_DTYPE_BF16 = 1
+APA_DTYPE_FP8_E4M3 = 2   # a cached feature map: OCP E4M3 codes + one fp32 scale per image (Fp8Features)
 APA_FLAG_SOFTMAX_ATT = 1
 APA_FLAG_RELU_ATT = 2
 APA_FLAG_TRAIN = 4
@@ -61,6 +62,9 @@ _SIGNATURES = {
     'apa_attn_pool_bwd_ex': (c_int, [c_void_p] * 18 + [c_size_t] + [c_int] * 6 +
                              [c_uint, c_float, c_uint64, c_uint64, c_int, c_void_p]),
     'apa_dropout_mask': (c_int, [c_void_p, c_size_t, c_float, c_uint64, c_uint64, c_void_p]),
+    'apa_fp8_features_bytes': (c_size_t, [c_int, c_int, c_int]),
+    'apa_quantize_features_fp8': (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
+    'apa_dequantize_features_fp8': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     'apa_pose_head_workspace_bytes': (c_size_t, [c_int] * 6),
     'apa_pose_head_fwd': (c_int, [c_void_p] * 8 + [c_size_t] + [c_int] * 6 + [c_void_p]),
     'apa_pose_head_bwd': (c_int, [c_void_p] * 7 + [c_int] + [c_void_p] * 5 + [c_size_t] + [c_int] * 6 +
@@ -233,12 +237,151 @@ def _stream_ptr() -> int:
     return torch.cuda.current_stream().cuda_stream
 
 
-def _feat_dtype(t: torch.Tensor) -> int:
+def _feat_dtype(t) -> int:
+    if isinstance(t, Fp8Features):
+        return APA_DTYPE_FP8_E4M3
     if t.dtype == torch.float32:
         return APA_DTYPE_F32
     if t.dtype == torch.bfloat16:
         return APA_DTYPE_BF16
     raise ApaError('feature maps must be float32 or bfloat16, got {}'.format(t.dtype))
+
+
+# --------------------------------------------------------------------------------------------
+# FP8 feature cache (include/apa.h: APA_DTYPE_FP8_E4M3)
+# --------------------------------------------------------------------------------------------
+FP8_E4M3_MAX = 448.0
+
+
+def fp8_scale_offset(N: int, P: int, C: int) -> int:
+    """byte offset of the N fp32 scales: the first 256-byte boundary behind the N*P*C codes"""
+    return (N * P * C + 255) // 256 * 256
+
+
+def fp8_features_bytes(N: int, P: int, C: int) -> int:
+    """apa_fp8_features_bytes, restated (a cache can be laid out without the library)"""
+    return fp8_scale_offset(N, P, C) + 4 * N
+
+
+class Fp8Features(object):
+    """A cached conv5 map in OCP FP8 E4M3 with one fp32 scale per image, as ONE uint8 buffer in the layout the
+    library reads (include/apa.h): N*P*C codes in [N,P,C] order, then -- at the next 256-byte boundary -- N scales;
+    element value = scale[n] * decode(code).  `codes` (torch.float8_e4m3fn, `shape`) and `scale` (float32 [N]) are
+    views of that buffer.  Pass one as `X` (and the same object as `Xatt`) to attn_pool_fwd / attn_pool_bwd(want_dx=
+    False) / HeadTrainStep(grads[0] = None) / HeadEvalStep: the class-agnostic head on frozen features.  Build one
+    with quantize_features(), or with from_parts() from a cache that keeps codes and scales in separate arrays."""
+
+    dtype = torch.float8_e4m3fn
+
+    def __init__(self, buffer: torch.Tensor, shape):
+        shape = tuple(int(d) for d in shape)
+        if len(shape) < 2:
+            raise ApaError('Fp8Features: [N, ..., C] expected')
+        N, C = shape[0], shape[-1]
+        n = int(np.prod(shape))
+        P = n // (N * C)
+        if C % 16:
+            raise ApaError('Fp8Features: C = {} is not a multiple of 16'.format(C))
+        if buffer.dtype != torch.uint8 or buffer.dim() != 1 or not buffer.is_contiguous() or \
+                buffer.numel() < fp8_features_bytes(N, P, C):
+            raise ApaError('Fp8Features: a contiguous 1-D uint8 buffer of fp8_features_bytes(N, P, C) bytes expected')
+        if buffer.data_ptr() % 16:
+            raise ApaError('Fp8Features: the buffer must be 16-byte aligned')
+        self.buffer, self.shape = buffer, shape
+        off = fp8_scale_offset(N, P, C)
+        self.codes = buffer[:n].view(torch.float8_e4m3fn).view(shape)
+        self.scale = buffer[off:off + 4 * N].view(torch.float32)
+
+    # what the wrappers ask of a feature tensor
+    device = property(lambda self: self.buffer.device)
+    is_cuda = property(lambda self: self.buffer.is_cuda)
+
+    def dim(self) -> int:
+        return len(self.shape)
+
+    def numel(self) -> int:
+        return int(np.prod(self.shape))
+
+    def is_contiguous(self) -> bool:
+        return True
+
+    def data_ptr(self) -> int:
+        return self.buffer.data_ptr()
+
+    def flat(self) -> 'Fp8Features':
+        """the same buffer seen as [N, P, C]"""
+        N, C = self.shape[0], self.shape[-1]
+        return Fp8Features(self.buffer, (N, self.numel() // (N * C), C))
+
+    @classmethod
+    def empty(cls, shape, device) -> 'Fp8Features':
+        shape = tuple(int(d) for d in shape)
+        N, C = shape[0], shape[-1]
+        P = int(np.prod(shape)) // (N * C)
+        return cls(torch.zeros((fp8_features_bytes(N, P, C),), dtype=torch.uint8, device=device), shape)
+
+    @classmethod
+    def from_parts(cls, codes: torch.Tensor, scale: torch.Tensor) -> 'Fp8Features':
+        """Pack a batch gathered from a cache that keeps `codes` ([N, ..., C], float8_e4m3fn or uint8) and `scale`
+        ([N] float32) apart -- a training loop's random minibatch: `Fp8Features.from_parts(all_codes[idx],
+        all_scales[idx])`.  One allocation and two copies on the codes' device."""
+        if codes.dtype not in (torch.float8_e4m3fn, torch.uint8):
+            raise ApaError('Fp8Features.from_parts: codes must be float8_e4m3fn (or their uint8 bits)')
+        if scale.numel() != codes.shape[0]:
+            raise ApaError('Fp8Features.from_parts: one scale per image expected')
+        out = cls.empty(codes.shape, codes.device)
+        out.codes.view(torch.uint8).copy_(codes.contiguous().view(torch.uint8))
+        out.scale.copy_(scale.reshape(-1).to(torch.float32))
+        return out
+
+    def dequantize(self, dtype=torch.float32) -> torch.Tensor:
+        """scale[n] * decode(code) as a float32 / bfloat16 tensor of `shape`: the device's own decode for a CUDA
+        cache (apa_dequantize_features_fp8), torch's for a CPU one."""
+        if dtype not in (torch.float32, torch.bfloat16):
+            raise ApaError('Fp8Features.dequantize: float32 or bfloat16')
+        N, C = self.shape[0], self.shape[-1]
+        if not self.is_cuda:
+            s = self.scale.view((N,) + (1,) * (len(self.shape) - 1))
+            return (self.codes.to(torch.float32) * s).to(dtype)
+        out = torch.empty(self.shape, dtype=dtype, device=self.device)
+        rc = load_library().apa_dequantize_features_fp8(
+            self.data_ptr(), out.data_ptr(), APA_DTYPE_F32 if dtype == torch.float32 else APA_DTYPE_BF16, N,
+            self.numel() // (N * C), C, _stream_ptr())
+        _check(rc, 'apa_dequantize_features_fp8')
+        return out
+
+
+def quantize_features(X: torch.Tensor):
+    """(Fp8Features, status) = quantize_features(X): X [N, ..., C] float32 / bfloat16, C a multiple of 16.  Per image, in
+    fp32 with IEEE division (include/apa.h): amax = max |x|, scale = amax / 448, inv = 448 / amax (both 0 when amax
+    is 0), code = rne_e4m3(x * inv).  status int32 [N]: 1 = the image holds a non-finite value (codes and scale are
+    zero then).  A CUDA tensor makes the device call (apa_quantize_features_fp8); a CPU tensor runs the same rule in
+    torch, bit for bit -- a cache can be built and inspected without a GPU."""
+    if X.dtype not in (torch.float32, torch.bfloat16):
+        raise ApaError('quantize_features: float32 or bfloat16 features expected, got {}'.format(X.dtype))
+    N, C = X.shape[0], X.shape[-1]
+    P = X.numel() // (N * C)
+    out = Fp8Features.empty(X.shape, X.device)
+    status = torch.zeros((N,), dtype=torch.int32, device=X.device)
+    if X.is_cuda:
+        rc = load_library().apa_quantize_features_fp8(_dev_ptr(X, 'X'), APA_DTYPE_F32 if X.dtype == torch.float32
+                                                      else APA_DTYPE_BF16, out.data_ptr(), status.data_ptr(), N, P, C,
+                                                      _stream_ptr())
+        _check(rc, 'apa_quantize_features_fp8')
+        return out, status
+    x = X.to(torch.float32).reshape(N, -1)
+    bad = ~torch.isfinite(x).all(dim=1)
+    amax = torch.where(bad, torch.zeros(()), x.abs().amax(dim=1))
+    live = amax > 0
+    m = torch.full((), FP8_E4M3_MAX, dtype=torch.float32)
+    one = torch.ones((), dtype=torch.float32)
+    scale = torch.where(live, amax / m, torch.zeros(()))
+    inv = torch.where(live, m / torch.where(live, amax, one), torch.zeros(()))
+    y = torch.where(live[:, None], x * inv[:, None], torch.zeros(()))
+    out.codes.copy_(y.to(torch.float8_e4m3fn).view(X.shape))
+    out.scale.copy_(scale)
+    status.copy_(bad.to(torch.int32))
+    return out, status
 
 
 class KeepMask(object):
@@ -390,6 +533,9 @@ def attn_pool_bwd(X, Xatt, Wa, ba, Wt, bt, att, zsave, abar, G, *, flags=0, keep
     dt = _feat_dtype(X)
     dev = X.device
     fused = Xatt is X
+    fp8 = isinstance(X, Fp8Features)
+    if fp8 and (want_dx or (out is not None and out[0] is not None)):
+        raise ApaError('attn_pool_bwd: an Fp8Features cache has no gradient: pass want_dx=False (and out[0] = None)')
     if dxatt_rank1 and not fused:
         flags |= APA_FLAG_DXATT_RANK1
     if not want_dx:
@@ -424,7 +570,7 @@ def attn_pool_bwd(X, Xatt, Wa, ba, Wt, bt, att, zsave, abar, G, *, flags=0, keep
             _dev_ptr(dWt, 'dWt'), _dev_ptr(dbt, 'dbt'), workspace.data_ptr(), workspace.numel(), N, P,
             C, Ca, K, M, fl, float(keep_prob), int(seed), offset, dt, _stream_ptr())
     rc = call(dX, flags)
-    if rc == APA_ERR_UNSUPPORTED and not want_dx:      # a route without the arm: the full call, dX to scratch
+    if rc == APA_ERR_UNSUPPORTED and not want_dx and not fp8:      # a route without the arm: the full call, dX to scratch
         rc = call(torch.empty_like(X), flags & ~APA_FLAG_FROZEN_INPUT)
     _check(rc, 'apa_attn_pool_bwd')
     return (dX if want_dx else None), dXatt, dWa, dba, dWt, dbt
@@ -1362,6 +1508,10 @@ class HeadTrainStep:
                 raise ApaError('HeadTrainStep: dxatt_rank1 wants grads[1] = dZ, float32 [N*P]')
             flags |= APA_FLAG_DXATT_RANK1
         dX, dXatt, dWa, dba, dWt, dbt = grads
+        self._fp8 = isinstance(X, Fp8Features)
+        if self._fp8 and (dX is not None or not fused):
+            raise ApaError('HeadTrainStep: an Fp8Features cache is frozen (grads[0] must be None) and supplies its own '
+                           'attention input (Xatt must be the same object)')
         self.frozen_input = dX is None
         self.dX_scratch = None
         if self.frozen_input:
@@ -1468,7 +1618,8 @@ class HeadTrainStep:
         (an ApaHooks) overrides the instance's for this call."""
         h = self.hooks if hooks is None else hooks
         rc = self._fn(*self._pre, _hooks_ptr(h), *self._args, _stream_ptr() if stream is None else stream)
-        if rc == APA_ERR_UNSUPPORTED and self.frozen_input:     # no arm on this route: the full step, dX to scratch
+        if rc == APA_ERR_UNSUPPORTED and self.frozen_input and not self._fp8:     # no arm on this route: the full step, dX to scratch
+            # (an FP8 cache has no full step to fall back to: the refusal is raised below)
             self.frozen_input = False
             self.dX_scratch = torch.empty_like(self._keep[0])
             self._args[self._dx_idx] = self.dX_scratch.data_ptr()

@@ -1062,6 +1062,7 @@ class FusedHeadStep:
         self.clipper = None
         self._anchor = torch.zeros((), requires_grad=True)
         self._want_dx = True
+        self._fp8 = False
         self.probe_events = None
 
     @staticmethod
@@ -1096,6 +1097,25 @@ class FusedHeadStep:
                 return 'per-class maps from pose_pre_logits'
             if tr.LOSS_FN_POSE != 'l2' or tr.LOSS_FN_POSE_SAMPLED:
                 return 'LOSS_FN_POSE %r / sampled (the cfg 003 step takes the plain pose L2 loss)' % tr.LOSS_FN_POSE
+        return ''
+
+    @staticmethod
+    def fp8_unsupported_reason(head, network_fn=None, training=True) -> str:
+        """why an Fp8Features batch (custom_ops_factory: a cached conv5 map in FP8 E4M3) cannot feed this head; '' when
+        it can.  The FP8 arm is the single-layer class-agnostic form on frozen features -- about the batch, not the
+        head: `unsupported_reason` does not change."""
+        if network_fn is not None and getattr(network_fn, 'backbone', None) is not None:
+            return 'a network_fn with a backbone (an FP8 batch IS the cached conv5 map: build it with backbone=None)'
+        if not head.single_layer:
+            return 'attention from pose_pre_logits (the cfg 003 form)'
+        if head.per_class:
+            return 'per-class attention maps'
+        if head.rank != 1:
+            return 'rank %d attention' % head.rank
+        if head.with_pose_feat:
+            return '..._WITH_POSE_FEAT'
+        if head.softmax_att:
+            return 'spatial-softmax attention'
         return ''
 
     @property
@@ -1271,7 +1291,7 @@ class FusedHeadStep:
     def _run(self, last_conv, labels_action, labels_pose, pose_valid):
         head = self.head
         n, c = last_conv.shape[0], last_conv.shape[-1]
-        X = last_conv.detach().contiguous().view(n, -1, c)
+        X = last_conv.flat() if self._fp8 else last_conv.detach().contiguous().view(n, -1, c)
         if self.pose_form:
             J = self.params['pose_w2'].shape[1]
             labels_pose = labels_pose.contiguous().float().view(n, -1, J)
@@ -1315,13 +1335,22 @@ class FusedHeadStep:
         return total
 
     def __call__(self, images, labels_action, labels_pose=None, pose_valid=None):
+        from .custom_ops.custom_ops_factory import Fp8Features
         self._frames = 1
-        if images.dim() == 5:                                   # nets_factory.py:121-125: frames fold into the batch
+        self._fp8 = isinstance(images, Fp8Features)
+        if self._fp8:       # a cached conv5 map in FP8: frozen by construction, no backbone in front of it
+            why = self.fp8_unsupported_reason(self.head, self.network_fn)
+            if not why and not self.frozen_features:
+                why = 'frozen_features=False (a cache has no gradient: build the step with frozen_features=True)'
+            if why:
+                raise ValueError('FusedHeadStep: an Fp8Features batch is not served with ' + why)
+        elif images.dim() == 5:                                 # nets_factory.py:121-125: frames fold into the batch
             self._frames = int(images.shape[1])
             images = images.reshape(-1, *images.shape[2:])
-        last_conv, self._preact = self.network_fn.features(images)
+        last_conv, self._preact = (images, False) if self._fp8 else self.network_fn.features(images)
         if last_conv.dim() != 4:
-            raise ValueError('FusedHeadStep: [N,H,W,C] (or [B,F,H,W,C]) feature maps expected')
+            raise ValueError('FusedHeadStep: [N,H,W,C] (or [B,F,H,W,C]; an Fp8Features batch: [N,H,W,C]) feature maps '
+                             'expected')
         if self._frames > 1 and self.head.rank > 1:
             raise ValueError('FusedHeadStep: a clip batch [B,F,H,W,C] with rank > 1 is not served by the one-call rank '
                              'step (frame pooling at rank > 1 runs through the per-op module)')
@@ -1332,7 +1361,7 @@ class FusedHeadStep:
         if self.cfg.TRAIN.LOSS_FN_ACTION != 'softmax-xentropy':     # multi-hot labels of any dtype -> float32, once
             labels_action = labels_action.to(torch.float32).contiguous()
         # decided per step: a conv5 map that needs no gradient (frozen / precomputed features) gets none
-        self._want_dx = bool(last_conv.requires_grad) or not self.frozen_features
+        self._want_dx = not self._fp8 and (bool(last_conv.requires_grad) or not self.frozen_features)
         # one autograd node either way: with a differentiated backbone it hands conv5's gradient upstream, without
         # one (head-only training) it still scales the bucket by whatever coefficient `total` is given
         total = _FusedHeadFunction.apply(last_conv, self._anchor, self, labels_action, labels_pose, pose_valid)
@@ -1433,17 +1462,24 @@ class FusedHeadEval:
         return [getattr(h, n) for n in names]
 
     def __call__(self, images, labels_action=None, want_pose_logits: bool = False):
+        from .custom_ops.custom_ops_factory import Fp8Features
         frames = 1
-        if images.dim() == 5:                                   # nets_factory.py:121-125
+        fp8 = isinstance(images, Fp8Features)
+        if fp8:             # a cached conv5 map in FP8 (see FusedHeadStep.fp8_unsupported_reason)
+            why = FusedHeadStep.fp8_unsupported_reason(self.head, self.network_fn)
+            if why:
+                raise ValueError('FusedHeadEval: an Fp8Features batch is not served with ' + why)
+        elif images.dim() == 5:                                 # nets_factory.py:121-125
             frames = images.shape[1]
             images = images.reshape(-1, *images.shape[2:])
-        last_conv, self._preact = self.network_fn.features(images)
+        last_conv, self._preact = (images, False) if fp8 else self.network_fn.features(images)
         if last_conv.dim() != 4:
-            raise ValueError('FusedHeadEval: [N,H,W,C] (or [B,F,H,W,C]) feature maps expected')
+            raise ValueError('FusedHeadEval: [N,H,W,C] (or [B,F,H,W,C]; an Fp8Features batch: [N,H,W,C]) feature maps '
+                             'expected')
         if self._preact and not self.head.can_fuse_input_relu(last_conv.dtype):
             last_conv, self._preact = torch.relu(last_conv), False
         n, hh, ww, c = last_conv.shape
-        X = last_conv.detach().contiguous().view(n, -1, c)
+        X = last_conv.flat() if fp8 else last_conv.detach().contiguous().view(n, -1, c)
         want_pl = bool(want_pose_logits and self.pose_form)
         tw = tb = None
         temporal = self.network_fn.temporal if frames > 1 else None     # nets_factory.py:354-374

@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define APA_VERSION 308 /* major*10000 + minor*100 + patch */
+#define APA_VERSION 309 /* major*10000 + minor*100 + patch */
 
 typedef enum apa_status {
   APA_OK = 0,
@@ -48,6 +48,10 @@ typedef enum apa_status {
 /* dtype of the feature-map tensors (X, Xatt, dX, dXatt, TopDown); parameters are always f32 */
 #define APA_DTYPE_F32 0
 #define APA_DTYPE_BF16 1
+/* A CACHED feature map in OCP FP8 E4M3 with one fp32 scale per image (see "FP8 feature cache" below).  Served by the
+ * class-agnostic head on frozen features only: apa_attn_pool_fwd[_ex], apa_attn_pool_bwd[_ex], apa_attn_head_train_step*
+ * and apa_attn_head_eval_step*; every other entry point answers "unknown dtype". */
+#define APA_DTYPE_FP8_E4M3 2
 
 /* flags (mirror cfg.NET.USE_POSE_PRELOGITS_BASED_ATTENTION_*, src/config.py:194-203)      */
 #define APA_FLAG_SOFTMAX_ATT 1u /* _SOFTMAX_ATT: spatial softmax of the bottom-up map       */
@@ -162,6 +166,28 @@ int apa_attn_pool_bwd(const void* X, const void* Xatt, const float* Wa, const fl
  * parity tests to hand the oracle the exact mask (TF's own RNG stream is not reproducible). */
 int apa_dropout_mask(uint8_t* mask, size_t n_elems, float keep_prob, uint64_t seed, uint64_t offset,
                      void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * FP8 feature cache (APA_DTYPE_FP8_E4M3).  A conv5 map that is computed once and read for a whole training run is
+ * kept as OCP E4M3 codes (torch.float8_e4m3fn: code 56 = 1.0, 126 = 448, 0x7F / 0xFF = NaN) with one scale per image.
+ * The feature pointer X of such a call addresses ONE allocation of apa_fp8_features_bytes(N, P, C) bytes:
+ *   N*P*C bytes of codes in [N,P,C] order, 16-byte aligned, then -- at the next 256-byte boundary -- N fp32 scales;
+ *   element value = scale[n] * decode(code).
+ * Quantisation (fp32 arithmetic, IEEE division, so a CPU restatement is bit-exact):
+ *   amax_n = max |x| over image n;  scale_n = amax_n / 448;  inv_n = 448 / amax_n  (both 0 when amax_n == 0);
+ *   code = rne_e4m3(x * inv_n).
+ * status int32 [N]: 0 = ok, 1 = image n holds a non-finite value (its codes and scale are then zero).
+ * src_dtype / dst_dtype: APA_DTYPE_F32 or APA_DTYPE_BF16; src / dst 16-byte aligned, C a multiple of 16.
+ * The pooling calls take such an X with Xatt == X, M == 1, C a multiple of 16 up to 8192, identity or ReLU attention;
+ * APA_FLAG_SOFTMAX_ATT, APA_FLAG_RELU_INPUT, APA_FLAG_RNG_EXTERNAL, a separate attention input, per-class maps and the
+ * TopDownAttention dump are refused with APA_ERR_UNSUPPORTED.  A cache has no gradient: a backward call or a training
+ * step without APA_FLAG_FROZEN_INPUT, or with a non-NULL dX, is refused with APA_ERR_INVALID_ARG.  The workspace is
+ * apa_attn_pool_workspace_bytes; the dropout mask is apa_dropout_mask's over the flat [N,P,C] index.
+ */
+size_t apa_fp8_features_bytes(int N, int P, int C);
+int apa_quantize_features_fp8(const void* src, int src_dtype, void* dst, int32_t* status, int N, int P, int C,
+                              void* stream);
+int apa_dequantize_features_fp8(const void* src, void* dst, int dst_dtype, int N, int P, int C, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * PoseLogits head.  Replaces nets_factory.py:147-160:

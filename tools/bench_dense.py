@@ -26,6 +26,11 @@ headline stays the cfg 002 training workload); run this file directly for one wo
             medians of five: the one-call multi-label step (apa_attn_head_train_step_multilabel), the module path
             (network_fn + gen_losses + autograd) and the softmax one-call step of the same shape.
 
+  frozen002_fp8 / eval002_fp8
+            cfg 002 on an FP8 E4M3 feature cache (Fp8Features) against the same step on the bf16 maps: the frozen
+            one-call training step / the one-call evaluation step, alternating in one process, medians of five and
+            their spread, the streaming kernels by HIP events with their bytes per second; --batch 512 for the
+            bandwidth-bound size
   frozen002 / frozen003 / frozen_perclass
             the one-call training steps on FROZEN features (APA_FLAG_FROZEN_INPUT: no dX is computed or stored) against
             the same step as it runs today, at the BASELINE shapes (32 x 14x14x2048; cfg 002 fp32 K = 393, cfg 003 bf16
@@ -1073,6 +1078,95 @@ def run_frozen(cof, dev, args, which):
     return out
 
 
+def build_fp8(cof, dev, train, fp8, N=32, H=14, rotate=0):
+    """cfg 002 on cached conv5 features, 14x14x2048, K = 393: the frozen one-call training step (train=True, dropout
+    keep 0.2, None in the dX slot) or the one-call evaluation step, on an FP8 E4M3 cache (fp8=True: Fp8Features, the
+    bf16 maps quantised) or on the bf16 maps themselves.  Each form rotates over enough sets of ITS OWN size that 1.5 x
+    the Infinity Cache lies between two uses of a set.  -> (step, steps_list, info)"""
+    C, P, K = 2048, H * H, 393
+    g = torch.Generator().manual_seed(42)
+    per_set = N * P * C * (1 if fp8 else 2)
+    R = _n_sets(per_set, rotate)
+    Xs = []
+    for r in range(R):
+        X = _features(N, P, C, torch.bfloat16, dev, seed=42 + r)
+        if fp8:
+            X, status = cof.quantize_features(X)
+            assert int(status.sum()) == 0
+        Xs.append(X)
+    Wa = (torch.randn(C, 1, generator=g) / C ** 0.5).to(dev); ba = torch.zeros(1, device=dev)
+    Wt = (torch.randn(C, K, generator=g) / C ** 0.5).to(dev); bt = torch.zeros(K, device=dev)
+    labels = torch.randint(0, K, (N,), generator=g).to(dev)
+    sts = []
+    if train:
+        ctr = torch.zeros(1, dtype=torch.int64, device=dev)
+        pg = tuple(torch.empty_like(t) for t in (Wa, ba, Wt, bt))
+        for X in Xs:
+            sts.append(cof.HeadTrainStep(X, X, Wa, ba, Wt, bt, labels, (None, None) + pg,
+                                         flags=cof.attn_flags(False, False, True), keep_prob=0.2, seed=42, offset=ctr,
+                                         share_with=sts[0] if sts else None))
+    else:
+        for X in Xs:
+            sts.append(cof.HeadEvalStep(X, X, Wa, ba, Wt, bt, workspace=sts[0].workspace if sts else None))
+    info = {'N': N, 'rotate': R, 'bytes_per_step': per_set, 'params': (Wa, ba, Wt, bt), 'features': Xs,
+            'shape': '{} x {}x{}x{}, K={}'.format(N, H, H, C, K) + (', dropout keep=0.2' if train else '')}
+    return _round_robin([st.run for st in sts]), sts, info
+
+
+def run_fp8(cof, dev, args, which):
+    """frozen002_fp8 / eval002_fp8: the FP8 and the bf16 form ALTERNATING in one process, five timed loops of each,
+    interleaved; medians and the loops' spread.  Then the streaming kernels of both forms by HIP events (apa_hooks
+    prof_*: the pooling pass of the forward half, the main pass of the backward half) with their algorithmic bytes per
+    second -- the feature bytes each pass reads once -- against the HBM peak."""
+    train = which == 'frozen002_fp8'
+    forms = {}
+    for name, fp8 in (('bf16', False), ('fp8', True)):
+        forms[name] = build_fp8(cof, dev, train, fp8, args.batch, args.hw, args.rotate)
+    for _ in range(args.warmup):
+        for step, _, _ in forms.values():
+            step()
+    torch.cuda.synchronize()
+    if train:
+        assert all(st.frozen_input for _, sts, _ in forms.values() for st in sts)
+    runs = {k: [] for k in forms}
+    for _ in range(5):
+        for name, (step, _, _) in forms.items():
+            sec, _ = timed(step, args.steps, 0, min_ms=0.0, repeats=1)
+            runs[name].append(sec * 1e6)
+    med = {k: sorted(v)[len(v) // 2] for k, v in runs.items()}
+    info = forms['fp8'][2]
+    out = {'workload': '{}: cfg 002 one-call {} step on an FP8 E4M3 feature cache against the same step on the bf16 '
+                       'maps, alternating in one process; {}; each form rotates over its own sets ({} bf16 / {} fp8)'.format(
+                           which, 'frozen training' if train else 'evaluation', info['shape'],
+                           forms['bf16'][2]['rotate'], info['rotate']),
+           'us_per_step': {k: round(v, 2) for k, v in med.items()},
+           'us_per_step_runs': {k: [round(x, 2) for x in v] for k, v in runs.items()},
+           'us_per_step_spread': {k: round(max(v) - min(v), 2) for k, v in runs.items()},
+           'fp8_over_bf16': round(med['fp8'] / med['bf16'], 4)}
+    n = 20
+    med_us = lambda v: sorted(v)[len(v) // 2] * 1e3
+    out['kernels_us'], out['kernels_gbs'], out['kernels_frac_of_hbm_peak'] = {}, {}, {}
+    for name, (_, sts, inf) in forms.items():
+        kt = cof.KernelTimer(n)
+        Wa, ba, Wt, bt = inf['params']
+        for i in range(n):
+            if train:
+                sts[i % len(sts)].run(hooks=kt.hooks(i))
+            else:       # the evaluation step takes no hooks: its pooling pass through the forward entry point
+                X = inf['features'][i % len(sts)]
+                cof.attn_pool_fwd(X, X, Wa, ba, Wt, bt, workspace=sts[0].workspace, hooks=kt.hooks(i))
+        torch.cuda.synchronize()
+        t = {'pool_fwd': med_us(kt.fwd_elapsed_ms())}
+        if train:
+            t['bwd_main'] = med_us(kt.bwd_elapsed_ms())
+        kt.close()
+        out['kernels_us'][name] = {k: round(v, 2) for k, v in t.items()}
+        out['kernels_gbs'][name] = {k: round(inf['bytes_per_step'] / v / 1e3, 1) for k, v in t.items()}
+        out['kernels_frac_of_hbm_peak'][name] = {k: round(inf['bytes_per_step'] / v / 1e3 / HBM_PEAK_GBS, 4)
+                                                 for k, v in t.items()}
+    return out
+
+
 def timed(fn, steps, warmup, min_ms=50.0, repeats=5):
     """median over >= `repeats` timed loops of `steps` steps each (>= min_ms of device time in total)."""
     for _ in range(warmup):
@@ -1117,7 +1211,8 @@ def main():
     ap.add_argument('--workload', default='cfg003', choices=['cfg003', 'perclass', 'eval002', 'eval003', 'rank1', 'posebwd', 'posebwd_acc', 'update003',
                                                          'update_perclass', 'poseatt', 'video_perclass', 'video003',
                                                          'hico002', 'charades_clips', 'frozen002', 'frozen003',
-                                                         'frozen_perclass'] + sorted(EVAL_CLIPS) + sorted(RANK_WORKLOADS))
+                                                         'frozen_perclass', 'frozen002_fp8', 'eval002_fp8'] +
+                    sorted(EVAL_CLIPS) + sorted(RANK_WORKLOADS))
     ap.add_argument('--clips', type=int, default=8, help='video_*: clips per batch')
     ap.add_argument('--frames', type=int, default=4, help='video_*: frames per clip')
     ap.add_argument('--only', default=None, choices=['clip_one_call', 'module_path', 'flat_one_call',
@@ -1160,6 +1255,9 @@ def main():
         return
     if args.workload in RANK_WORKLOADS:
         print(json.dumps(run_rank(cof, dev, args, args.workload)))
+        return
+    if args.workload in ('frozen002_fp8', 'eval002_fp8'):
+        print(json.dumps(run_fp8(cof, dev, args, args.workload)))
         return
     if args.workload.startswith('frozen'):
         print(json.dumps(run_frozen(cof, dev, args, args.workload)))
