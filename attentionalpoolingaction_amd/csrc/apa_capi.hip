@@ -971,6 +971,128 @@ extern "C" int apa_attn_head_eval_step(const void* X, const void* Xatt, const fl
                         M1Fwd{X, Xatt, Wa, ba, Wt, bt, logits, att, zsave, abar}, labels, loss, probs, pred);
 }
 
+// ---- a resident feature cache read by image index (apa.h: apa_feature_cache) -----------------------------------------
+// What a *_cached call refuses about its descriptor and about the forms a cache cannot have, each reason by name and
+// before anything is queued; what remains (pointers, workspace, the FP8 arm's own limits) is pool_check's as ever.
+// backward: a backward call or a training step.
+static int cache_check(const char* fn, const apa_feature_cache* fc, const PoolCall& d, const void* X, const void* Xatt,
+                       bool topdown, bool backward, const void* dX) {
+  if (!fc || !fc->index) {
+    set_error("%s: null apa_feature_cache / index pointer", fn);
+    return APA_ERR_INVALID_ARG;
+  }
+  if (reinterpret_cast<uintptr_t>(fc->index) & 3) {
+    set_error("%s: apa_feature_cache.index must be 4-byte aligned", fn);
+    return APA_ERR_INVALID_ARG;
+  }
+  if (fc->cache_images < 1) {
+    set_error("%s: apa_feature_cache.cache_images=%d: a cache holds at least one image", fn, fc->cache_images);
+    return APA_ERR_INVALID_ARG;
+  }
+  const int rc = check_common(fn, d, true);
+  if (rc != APA_OK) return rc;
+  if (dX) {
+    set_error("%s: a feature cache has no gradient: dX must be NULL", fn);
+    return APA_ERR_INVALID_ARG;
+  }
+  if (backward && !(d.flags & APA_FLAG_FROZEN_INPUT)) {
+    set_error("%s: a feature cache is frozen: a backward call or a training step needs APA_FLAG_FROZEN_INPUT", fn);
+    return APA_ERR_INVALID_ARG;
+  }
+  const char* why = d.M != 1 ? "per-class maps (M != 1)"
+                    : (X && Xatt != X) ? "a separate attention input (Xatt != X)"
+                    : (d.flags & APA_FLAG_SOFTMAX_ATT) ? "APA_FLAG_SOFTMAX_ATT"
+                    : (d.flags & APA_FLAG_RELU_INPUT) ? "APA_FLAG_RELU_INPUT"
+                    : (d.flags & APA_FLAG_RNG_EXTERNAL) ? "APA_FLAG_RNG_EXTERNAL"
+                    : topdown ? "the TopDownAttention dump"
+                    : d.cat ? "the concatenated pose channels (_cat)" : nullptr;
+  if (why) {
+    set_error("%s: a feature cache does not serve %s: the gathered kernels feed the fused class-agnostic head with "
+              "identity or relu attention", fn, why);
+    return APA_ERR_UNSUPPORTED;
+  }
+  return APA_OK;
+}
+
+// labels_cached: `labels` is [T]; the loss reads the [N] copy the forward pooling pass leaves in the workspace
+static const int64_t* cached_labels(PoolCall* d, const apa_feature_cache* fc, const int64_t* labels) {
+  if (!fc->labels_cached || !labels || !d->ws) return labels;
+  d->fc_labels = labels;
+  return m1_gathered_labels(d->ws, m1_plan(d->N, d->P, d->C, d->Ca, d->K));
+}
+
+extern "C" int apa_attn_pool_fwd_cached(const apa_feature_cache* cache, const apa_hooks* hooks, const void* X,
+                                        const void* Xatt, const float* Wa, const float* ba, const float* Wt,
+                                        const float* bt, float* logits, float* att, float* zsave, float* abar,
+                                        void* topdown, void* ws, size_t ws_bytes, int N, int P, int C, int Ca, int K,
+                                        int M, unsigned flags, float keep_prob, uint64_t seed, uint64_t offset,
+                                        int dtype, void* stream) {
+  PoolCall d = fp8_served(pool_call({N, P, C, Ca, K, M, dtype}, flags, keep_prob, seed, offset, ws, ws_bytes, stream,
+                                    hooks));
+  const int rc = cache_check("apa_attn_pool_fwd_cached", cache, d, X, Xatt, topdown != nullptr, false, nullptr);
+  if (rc != APA_OK) return rc;
+  d.fc = cache;
+  return attn_pool_fwd(d, M1Fwd{X, Xatt, Wa, ba, Wt, bt, logits, att, zsave, abar, topdown}, nullptr);
+}
+
+extern "C" int apa_attn_pool_bwd_cached(const apa_feature_cache* cache, const apa_hooks* hooks, const void* X,
+                                        const void* Xatt, const float* Wa, const float* ba, const float* Wt,
+                                        const float* bt, const float* att, const float* zsave, const float* abar,
+                                        const float* G, void* dX, void* dXatt, float* dWa, float* dba, float* dWt,
+                                        float* dbt, void* ws, size_t ws_bytes, int N, int P, int C, int Ca, int K, int M,
+                                        unsigned flags, float keep_prob, uint64_t seed, uint64_t offset, int dtype,
+                                        void* stream) {
+  (void)ba;
+  PoolCall d = fp8_served(pool_call({N, P, C, Ca, K, M, dtype}, flags, keep_prob, seed, offset, ws, ws_bytes, stream,
+                                    hooks));
+  const int rc = cache_check("apa_attn_pool_bwd_cached", cache, d, X, Xatt, false, true, dX);
+  if (rc != APA_OK) return rc;
+  d.fc = cache;
+  return attn_pool_bwd(d, M1Bwd{X, Xatt, Wa, Wt, bt, att, zsave, abar, G, dX, dXatt, dWa, dba, dWt, dbt}, nullptr);
+}
+
+extern "C" int apa_attn_head_train_step_cached(const apa_feature_cache* cache, const apa_hooks* hooks, const void* X,
+                                               const void* Xatt, const float* Wa, const float* ba, const float* Wt,
+                                               const float* bt, const int64_t* labels, float loss_wt, float grad_scale,
+                                               float* logits, float* att, float* zsave, float* abar, float* loss,
+                                               float* G, void* dX, void* dXatt, float* dWa, float* dba, float* dWt,
+                                               float* dbt, void* ws, size_t ws_bytes, int N, int P, int C, int Ca, int K,
+                                               int M, unsigned flags, float keep_prob, uint64_t seed, uint64_t offset,
+                                               int dtype, void* stream) {
+  const char* fn = "apa_attn_head_train_step_cached";
+  PoolCall d = fp8_served(pool_call({N, P, C, Ca, K, M, dtype}, flags, keep_prob, seed, offset, ws, ws_bytes, stream,
+                                    hooks));
+  const int rc = cache_check(fn, cache, d, X, Xatt, false, true, dX);
+  if (rc != APA_OK) return rc;
+  d.fc = cache;
+  const int64_t* lab = cached_labels(&d, cache, labels);
+  return head_step(fn, d, StepLoss{nullptr, lab, false, nullptr, loss_wt, grad_scale, loss, G},
+                   M1Fwd{X, Xatt, Wa, ba, Wt, bt, logits, att, zsave, abar},
+                   M1Bwd{X, Xatt, Wa, Wt, bt, att, zsave, abar, G, dX, dXatt, dWa, dba, dWt, dbt});
+}
+
+// flat batches, softmax or sigmoid scores: everything behind the pooling pass never sees X
+extern "C" int apa_attn_head_eval_step_cached(const apa_feature_cache* cache, const apa_clip_pool* clip,
+                                              int scores_kind, const void* X, const void* Xatt, const float* Wa,
+                                              const float* ba, const float* Wt, const float* bt, const int64_t* labels,
+                                              float* logits, float* att, float* zsave, float* abar, float* loss,
+                                              float* probs, int64_t* pred, void* ws, size_t ws_bytes, int N, int P,
+                                              int C, int Ca, int K, int M, unsigned flags, int dtype, void* stream) {
+  const char* fn = "apa_attn_head_eval_step_cached";
+  PoolCall d = fp8_served(pool_call({N, P, C, Ca, K, M, dtype}, flags, 1.0f, 0, 0, ws, ws_bytes, stream));
+  int rc = cache_check(fn, cache, d, X, Xatt, false, false, nullptr);
+  if (rc != APA_OK) return rc;
+  if (clip) {
+    set_error("%s: a feature cache does not serve clips: flat batches only (clip must be NULL)", fn);
+    return APA_ERR_UNSUPPORTED;
+  }
+  if ((rc = eval_scores_check(fn, nullptr, scores_kind, N, K, logits, labels, loss, probs, pred)) != APA_OK) return rc;
+  d.fc = cache;
+  const int64_t* lab = cached_labels(&d, cache, labels);
+  return attn_head_eval_clips(fn, nullptr, scores_kind, d, M1Fwd{X, Xatt, Wa, ba, Wt, bt, logits, att, zsave, abar}, lab,
+                              loss, probs, pred);
+}
+
 // workspace of apa_pose_attn_eval_step: [pose head | pooling (+ the label-free loss scratch) | column-tile partials]
 struct PoseEvalCarve { size_t pose, pool, zpart, total; };
 static PoseEvalCarve pose_eval_carve(int N, int P, int C, int Cp, int J, int K, unsigned flags, int dtype) {

@@ -6,6 +6,7 @@
 #include <stdint.h>
 
 #include "apa_colsum.h"
+#include "apa_gather.h"
 
 namespace apa {
 
@@ -234,6 +235,23 @@ __host__ __device__ __forceinline__ void m1_pix_range(int s, int P, int S, int& 
   const unsigned lo = (unsigned)s * (unsigned)P;
   p_begin = (int)(lo / (unsigned)S);
   p_end = (int)((lo + (unsigned)P) / (unsigned)S);
+}
+
+// The gathered arm of the M == 1 streaming passes (apa.h: apa_feature_cache): batch image n is image index[n] of a
+// T-image cache behind X.  A kernel's gathered instances (template parameter GATHER) take one M1Gather (apa_gather.h)
+// as their last argument, the plain instances an empty M1NoGather in its place, and fetch the feature rows -- on the
+// FP8 arm also the scale -- of image m1_src_image(n, g); every other address, and the dropout hash's element index,
+// keep the batch position n.  The price is one dependent scalar read in front of the first feature load, paid by the
+// gathered instances alone.
+__device__ __forceinline__ int m1_src_image(int n, const M1NoGather&) { return n; }
+__device__ __forceinline__ int m1_src_image(int n, const M1Gather& g) { return min(max(g.index[n], 0), g.T - 1); }
+// forward pass, `one`: true in exactly one thread per image
+__device__ __forceinline__ void m1_gather_note(int, bool, const M1NoGather&) {}
+__device__ __forceinline__ void m1_gather_note(int n, bool one, const M1Gather& g) {
+  if (!one) return;
+  const int raw = g.index[n], src = min(max(raw, 0), g.T - 1);
+  if (g.status && raw != src) atomicAdd(g.status, 1);
+  if (g.labels_out) g.labels_out[n] = g.labels[src];
 }
 
 // reductions over HALF a wave (lanes 0-31 / 32-63 reduce independently): softmax rows

@@ -124,17 +124,21 @@ extern "C" size_t apa_fp8_features_bytes(int N, int P, int C) {
   return fp8_scale_offset(N, P, C) + (size_t)N * 4;
 }
 
-extern "C" int apa_quantize_features_fp8(const void* src, int src_dtype, void* dst, int32_t* status, int N, int P,
-                                         int C, void* stream) {
-  const char* fn = "apa_quantize_features_fp8";
+// n images of src into slots [first, first + n) of the T-image cache at dst
+static int quantize_at(const char* fn, const void* src, int src_dtype, void* dst, int T, int first, int32_t* status,
+                       int N, int P, int C, void* stream) {
   const int rc = fp8_shape_check(fn, src, dst, src_dtype, N, P, C);
   if (rc != APA_OK) return rc;
   if (!status) {
     set_error("%s: null status pointer", fn);
     return APA_ERR_INVALID_ARG;
   }
-  uint8_t* codes = static_cast<uint8_t*>(dst);
-  float* scale = reinterpret_cast<float*>(codes + fp8_scale_offset(N, P, C));
+  if (first < 0 || T < 1 || (long)first + N > (long)T) {
+    set_error("%s: slots [%d, %d + %d) do not lie inside a cache of %d images", fn, first, first, N, T);
+    return APA_ERR_INVALID_ARG;
+  }
+  uint8_t* codes = static_cast<uint8_t*>(dst) + (size_t)first * P * C;
+  float* scale = reinterpret_cast<float*>(static_cast<uint8_t*>(dst) + fp8_scale_offset(T, P, C)) + first;
   const long nvec = (long)P * C / 16;
   hipStream_t st = static_cast<hipStream_t>(stream);
   if (src_dtype == APA_DTYPE_F32)
@@ -145,6 +149,17 @@ extern "C" int apa_quantize_features_fp8(const void* src, int src_dtype, void* d
                        scale, status, nvec);
   APA_LAUNCH_CHECK("fp8_quantize_kernel");
   return APA_OK;
+}
+
+extern "C" int apa_quantize_features_fp8(const void* src, int src_dtype, void* dst, int32_t* status, int N, int P,
+                                         int C, void* stream) {
+  return quantize_at("apa_quantize_features_fp8", src, src_dtype, dst, N, 0, status, N, P, C, stream);
+}
+
+extern "C" int apa_quantize_features_fp8_at(const void* src, int src_dtype, void* cache, int cache_images, int first,
+                                            int32_t* status, int n, int P, int C, void* stream) {
+  return quantize_at("apa_quantize_features_fp8_at", src, src_dtype, cache, cache_images, first, status, n, P, C,
+                     stream);
 }
 
 extern "C" int apa_dequantize_features_fp8(const void* src, void* dst, int dst_dtype, int N, int P, int C,

@@ -1,0 +1,21 @@
+// apa_gather.h -- the argument the gathered instances of the M == 1 streaming kernels take (apa_device.h: m1_src_image),
+// shared by the device code and the host launchers (apa_internal.h: M1Call).
+#pragma once
+#include <stdint.h>
+
+#include <type_traits>
+
+namespace apa {
+
+struct M1Gather {
+  const int32_t* index;      // [N]
+  int T;                     // images behind X; an id outside [0, T) is clamped
+  int32_t* status;           // nullable: += 1 per clamped id (forward pass only)
+  const int64_t* labels;     // nullable: [T] labels, read through index ...
+  int64_t* labels_out;       // ... into [N] (workspace), where the loss reducers behind the pass read them
+};
+// the trailing argument of a streaming kernel: M1Gather on the gathered instances, nothing on the plain ones
+struct M1NoGather {};
+template <bool GATHER> using M1GatherArg = std::conditional_t<GATHER, M1Gather, M1NoGather>;
+
+}  // namespace apa

@@ -9,6 +9,7 @@
 
 #include "../../include/apa.h"
 #include "apa_colsum.h"
+#include "apa_gather.h"
 
 namespace apa {
 
@@ -256,6 +257,11 @@ struct PoolCall : PoolDims {
   void* ws = nullptr; size_t ws_bytes = 0; hipStream_t st = nullptr; Hooks hk;
   const apa_concat_feat* cat = nullptr;   // checked by the entry point (check_cat) before either path sees it
   bool fp8_ok = false;   // the entry point serves APA_DTYPE_FP8_E4M3 (apa_capi.hip: fp8_served); else "unknown dtype"
+  // the *_cached entry points (apa.h: apa_feature_cache), checked by cache_check (apa_capi.hip) before either path sees
+  // it: X is a T-image cache, batch image n is its image index[n].  fc_labels: the [T] labels to read through the
+  // index (labels_cached), which the forward pooling pass drops into the workspace (m1_gathered_labels)
+  const apa_feature_cache* fc = nullptr;
+  const int64_t* fc_labels = nullptr;
 };
 
 struct M1Plan {
@@ -326,7 +332,14 @@ struct M1Call {
   RngKeyArgs key; float inv_keep; uint64_t* bump;   // the dropout key; backward: the device step counter to advance, or null
   const float* ex; float exs;   // backward: per-pixel addend of dA and its scale (the concat channels' share, else att, 0)
   hipEvent_t ev0, ev1, td_ready, grad_ready;   // ev0 / ev1: apa_hooks prof_*, dispatch begin / end of the streaming pass
+  // a gathered call (PoolCall::fc): both streaming passes run their gathered instances on `ga`; T: the images behind X
+  bool gather; int T; M1Gather ga;
 };
+// where a gathered forward pass leaves labels[index[n]] for the loss reducers behind it: the head of the pdwa region,
+// which nothing writes before the backward pass (nblk * C * 4 >= N * 8 bytes for every served C)
+inline int64_t* m1_gathered_labels(void* ws, const M1Plan& pl) {
+  return reinterpret_cast<int64_t*>(static_cast<char*>(ws) + pl.off_pdwa);
+}
 // f: a forward call's tensors, or b: a backward call's (the other null); xf: what the forward half of a one-call step
 // folded (M1Xent::done: the backward half needs the head kernel), or null
 int m1_call_fill(M1Call& c, const PoolCall& d, const M1Fwd* f, const M1Bwd* b, const M1Xent* xf = nullptr);

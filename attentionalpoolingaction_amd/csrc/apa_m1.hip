@@ -413,6 +413,16 @@ int m1_call_fill(M1Call& c, const PoolCall& d, const M1Fwd* f, const M1Bwd* b, c
   c.ex = b ? (cat ? c.cat_e : b->att) : nullptr;
   c.exs = cat ? 1.0f : 0.0f;
   c.ev0 = b ? hk.bwd0 : hk.fwd0; c.ev1 = b ? hk.bwd1 : hk.fwd1;
+  c.gather = d.fc != nullptr;
+  c.T = c.gather ? d.fc->cache_images : N;
+  c.ga = M1Gather{nullptr, 0, nullptr, nullptr, nullptr};
+  if (c.gather) {   // the backward pass reports and copies nothing: the forward pass did
+    c.ga.index = d.fc->index; c.ga.T = c.T;
+    if (f) {
+      c.ga.status = d.fc->status;
+      if (d.fc_labels) { c.ga.labels = d.fc_labels; c.ga.labels_out = m1_gathered_labels(ws, c.pl); }
+    }
+  }
   c.td_ready = hk.td_ready; c.grad_ready = hk.grad_ready;
   if (M1Trace* tr = m1_trace()) {
     tr->S = c.pl.S; tr->ppb = c.pl.ppb; tr->nblk = c.pl.nblk; tr->fused = c.fused; tr->relu_input = c.relu_input;
@@ -424,6 +434,13 @@ int m1_call_fill(M1Call& c, const PoolCall& d, const M1Fwd* f, const M1Bwd* b, c
   if (c.pool == M1_POOL_FP8 && (!c.fused || c.act == M1_ACT_SOFTMAX || c.relu_input || c.ext || cat || (b && !c.no_dx) ||
                                 (flags & APA_IFLAG_NO_DX) || !m1f_supported(C))) {
     set_error("attn_pool M=1: APA_DTYPE_FP8_E4M3 serves the fused identity / relu head on frozen features only");
+    return APA_ERR_UNSUPPORTED;
+  }
+  // a gathered call: the entry points (cache_check, apa_capi.hip) name each reason; only the forms a cache can have
+  // have gathered instances
+  if (c.gather && (!c.fused || c.act == M1_ACT_SOFTMAX || c.relu_input || c.ext || cat || (b && !c.no_dx) ||
+                   (flags & APA_IFLAG_NO_DX))) {
+    set_error("attn_pool M=1: a feature cache serves the fused identity / relu head on frozen features only");
     return APA_ERR_UNSUPPORTED;
   }
   // the streaming kernels split an image's pixels in 32-bit arithmetic (m1_pix_range); the other families keep 64 bits

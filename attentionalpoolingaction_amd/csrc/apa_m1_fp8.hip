@@ -77,15 +77,18 @@ __device__ __forceinline__ void merge_waves(float (&acc)[NV * 16], float s, floa
   }
 }
 
-template <int NV, bool TRAIN>
+// GATHER: the gathered instances (apa_device.h: M1Gather; the plain ones take an empty M1NoGather) read the codes and
+// the scale of cache image index[n]
+template <int NV, bool TRAIN, bool GATHER = false>
 __global__ __launch_bounds__(256, blocks_per_cu(NV)) void m1f_pool_fwd_kernel(
     const uint8_t* __restrict__ X, const float* __restrict__ scale, const float* __restrict__ Wa,
     const float* __restrict__ ba, float* __restrict__ att, float* __restrict__ pacc, float* __restrict__ pstat, int P,
     int S, int C, int act, float inv_keep, uint32_t thresh, uint64_t seed, uint64_t offset,
-    const uint64_t* __restrict__ offset_dev) {
+    const uint64_t* __restrict__ offset_dev, M1GatherArg<GATHER> g) {
   constexpr int PIX = pix_per_chunk(NV);
   extern __shared__ __attribute__((aligned(16))) float sm[];   // [C] merge row, then 4 per-wave sums
   const int blk = blockIdx.x, n = blk / S, s = blk % S;
+  const int src = GATHER ? m1_src_image(n, g) : n;
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int p_begin = (int)(((long)s * P) / S), p_end = (int)(((long)(s + 1) * P) / S);
   const int p_last = p_end - 1;
@@ -101,7 +104,7 @@ __global__ __launch_bounds__(256, blocks_per_cu(NV)) void m1f_pool_fwd_kernel(
   const int nchunk = (npw + PIX - 1) / PIX;
   const int pw0 = p_begin + wave;
 
-  const uint8_t* xim = opaque_codes(X + (size_t)n * P * C);
+  const uint8_t* xim = opaque_codes(X + (size_t)src * P * C);
   uint4 xr[2][PIX][NV];
   load_chunk<NV, PIX>(xr[0], xim, pw0, p_last, C, voff);
   // L2 hits, issued in the shadow of the first chunk's loads
@@ -117,7 +120,7 @@ __global__ __launch_bounds__(256, blocks_per_cu(NV)) void m1f_pool_fwd_kernel(
   }
 #pragma unroll
   for (int i = 0; i < NV * 16; ++i) acc[i] = 0.f;
-  const float bias = ba[0], sn = scale[n];
+  const float bias = ba[0], sn = scale[src];
   uint32_t k0 = 0, k1 = 0;
   if (TRAIN) rng_key_dev(seed, offset_dev ? *offset_dev : offset, k0, k1);
   float a_sum = 0.f;
@@ -167,6 +170,7 @@ __global__ __launch_bounds__(256, blocks_per_cu(NV)) void m1f_pool_fwd_kernel(
   float* sm_stat = sm + C;
   if (lane == 0) sm_stat[wave] = a_sum;
   merge_waves<NV>(acc, sn, sm, pacc + (size_t)blk * C, voff, active, wave);   // (its barriers publish sm_stat)
+  m1_gather_note(n, s == 0 && threadIdx.x == 0, g);
   if (threadIdx.x == 192) {
     pstat[blk * 4 + 0] = 0.f;
     pstat[blk * 4 + 1] = 0.f;
@@ -175,16 +179,17 @@ __global__ __launch_bounds__(256, blocks_per_cu(NV)) void m1f_pool_fwd_kernel(
   }
 }
 
-template <int NV, bool TRAIN>
+template <int NV, bool TRAIN, bool GATHER = false>
 __global__ __launch_bounds__(256, blocks_per_cu(NV)) void m1f_bwd_main_kernel(
     const uint8_t* __restrict__ X, const float* __restrict__ scale, const float* __restrict__ att,
     const float* __restrict__ dz, const float* __restrict__ G, const float* __restrict__ bt,
     const float* __restrict__ sn_pre, float* __restrict__ pdwa, float* __restrict__ pdba, int P, int S, int C, int K,
     int act, float inv_keep, uint32_t thresh, uint64_t seed, uint64_t offset,
-    const uint64_t* __restrict__ offset_dev) {
+    const uint64_t* __restrict__ offset_dev, M1GatherArg<GATHER> g) {
   constexpr int PIX = pix_per_chunk(NV);
   extern __shared__ __attribute__((aligned(16))) float sm[];   // [C] merge row, then 4 per-wave sums
   const int blk = blockIdx.x, n = blk / S, s = blk % S;
+  const int src = GATHER ? m1_src_image(n, g) : n;
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int p_begin = (int)(((long)s * P) / S), p_end = (int)(((long)(s + 1) * P) / S);
   const int p_last = p_end - 1;
@@ -200,7 +205,7 @@ __global__ __launch_bounds__(256, blocks_per_cu(NV)) void m1f_bwd_main_kernel(
   const int nchunk = (npw + PIX - 1) / PIX;
   const int pw0 = p_begin + wave;
 
-  const uint8_t* xim = opaque_codes(X + (size_t)n * P * C);
+  const uint8_t* xim = opaque_codes(X + (size_t)src * P * C);
   uint4 xr[2][PIX][NV];
   load_chunk<NV, PIX>(xr[0], xim, pw0, p_last, C, voff);
   float dzr[NV * 16], dwa[NV * 16];
@@ -216,7 +221,7 @@ __global__ __launch_bounds__(256, blocks_per_cu(NV)) void m1f_bwd_main_kernel(
   }
 #pragma unroll
   for (int i = 0; i < NV * 16; ++i) dwa[i] = 0.f;
-  const float sc = scale[n];
+  const float sc = scale[src];
   float gb;   // G[n,:] . bt
   if (sn_pre) {
     gb = sn_pre[n];
@@ -287,15 +292,25 @@ bool m1f_supported(int C) { return C >= 16 && C % 16 == 0 && C <= M1F_MAX_C; }
 int m1f_launch_pool_fwd(const M1Call& c, const M1Fwd& io) {
   if (M1Trace* t = m1_trace()) t->pool_fwd = M1_POOL_FP8;
   const uint8_t* X = static_cast<const uint8_t*>(io.X);
-  const float* scale = reinterpret_cast<const float*>(X + fp8_scale_offset(c.N, c.P, c.C));
+  // (a gathered call: the scales lie behind the codes of all c.T images of the cache)
+  const float* scale = reinterpret_cast<const float*>(X + fp8_scale_offset(c.T, c.P, c.C));
   const size_t shm = (size_t)c.C * 4 + 16;
   by_nv(c.C, [&](auto NV) -> int {
     auto go = [&](auto TR) {
       launch_ev(m1f_pool_fwd_kernel<decltype(NV)::value, decltype(TR)::value>, dim3(c.pl.nblk), dim3(256), shm, c.st,
                 c.ev0, c.ev1, X, scale, io.Wa, io.ba, io.att, c.pacc, c.pstat, c.P, c.pl.S, c.C, c.pool_act, c.inv_keep,
-                c.key.thresh, c.key.seed, c.key.offset, c.key.offset_dev);
+                c.key.thresh, c.key.seed, c.key.offset, c.key.offset_dev, M1NoGather{});
     };
-    if (c.train) go(std::true_type{}); else go(std::false_type{});
+    auto gathered = [&](auto TR) {
+      launch_ev(m1f_pool_fwd_kernel<decltype(NV)::value, decltype(TR)::value, true>, dim3(c.pl.nblk), dim3(256), shm,
+                c.st, c.ev0, c.ev1, X, scale, io.Wa, io.ba, io.att, c.pacc, c.pstat, c.P, c.pl.S, c.C, c.pool_act,
+                c.inv_keep, c.key.thresh, c.key.seed, c.key.offset, c.key.offset_dev, c.ga);
+    };
+    if (c.gather) {
+      if (c.train) gathered(std::true_type{}); else gathered(std::false_type{});
+    } else {
+      if (c.train) go(std::true_type{}); else go(std::false_type{});
+    }
     return APA_OK;
   });
   APA_LAUNCH_CHECK("m1f_pool_fwd_kernel");
@@ -305,15 +320,24 @@ int m1f_launch_pool_fwd(const M1Call& c, const M1Fwd& io) {
 int m1f_launch_bwd_main(const M1Call& c, const M1Bwd& io) {
   if (M1Trace* t = m1_trace()) t->pool_bwd = M1_POOL_FP8;
   const uint8_t* X = static_cast<const uint8_t*>(io.X);
-  const float* scale = reinterpret_cast<const float*>(X + fp8_scale_offset(c.N, c.P, c.C));
+  const float* scale = reinterpret_cast<const float*>(X + fp8_scale_offset(c.T, c.P, c.C));
   const size_t shm = (size_t)c.C * 4 + 16;
   by_nv(c.C, [&](auto NV) -> int {
     auto go = [&](auto TR) {
       launch_ev(m1f_bwd_main_kernel<decltype(NV)::value, decltype(TR)::value>, dim3(c.pl.nblk), dim3(256), shm, c.st,
                 c.ev0, c.ev1, X, scale, io.att, c.dz, io.G, io.bt, c.sn, c.pdwa, c.pdba, c.P, c.pl.S, c.C, c.K, c.act,
-                c.inv_keep, c.key.thresh, c.key.seed, c.key.offset, c.key.offset_dev);
+                c.inv_keep, c.key.thresh, c.key.seed, c.key.offset, c.key.offset_dev, M1NoGather{});
     };
-    if (c.train) go(std::true_type{}); else go(std::false_type{});
+    auto gathered = [&](auto TR) {
+      launch_ev(m1f_bwd_main_kernel<decltype(NV)::value, decltype(TR)::value, true>, dim3(c.pl.nblk), dim3(256), shm,
+                c.st, c.ev0, c.ev1, X, scale, io.att, c.dz, io.G, io.bt, c.sn, c.pdwa, c.pdba, c.P, c.pl.S, c.C, c.K,
+                c.act, c.inv_keep, c.key.thresh, c.key.seed, c.key.offset, c.key.offset_dev, c.ga);
+    };
+    if (c.gather) {
+      if (c.train) gathered(std::true_type{}); else gathered(std::false_type{});
+    } else {
+      if (c.train) go(std::true_type{}); else go(std::false_type{});
+    }
     return APA_OK;
   });
   APA_LAUNCH_CHECK("m1f_bwd_main_kernel");

@@ -19,12 +19,13 @@
 namespace apa {
 
 namespace {
-template <typename T, bool FUSED, bool TRAIN>
+// GATHER: the gathered instances (apa_device.h: M1Gather; the plain ones take an empty M1NoGather)
+template <typename T, bool FUSED, bool TRAIN, bool GATHER = false>
 __global__ __launch_bounds__(256) void m1g_pool_fwd_kernel(
     const T* __restrict__ X, const float* __restrict__ Wa, const float* __restrict__ ba,
     float* __restrict__ att, float* __restrict__ pacc, float* __restrict__ pstat, int P, int S, int C,
     int act, float inv_keep, uint32_t thresh, uint64_t seed, uint64_t offset,
-    const uint64_t* __restrict__ offset_dev) {
+    const uint64_t* __restrict__ offset_dev, M1GatherArg<GATHER> g) {
   constexpr int EPV = Vec<T>::EPV;
   extern __shared__ __attribute__((aligned(16))) float sm[];   // [4][C] accumulators, then 16 stats
   float* sm_stat = sm + 4 * (size_t)C;
@@ -38,7 +39,7 @@ __global__ __launch_bounds__(256) void m1g_pool_fwd_kernel(
   for (int c = lane; c < C; c += 64) my[c] = 0.f;
   const float bias = FUSED ? ba[0] : 0.f;
   float m_run = -INFINITY, l_run = 0.f, a_sum = 0.f;
-  const T* xim = X + (size_t)n * P * C;
+  const T* xim = X + (size_t)(GATHER ? m1_src_image(n, g) : n) * P * C;
   float* att_im = att + (size_t)n * P;
   for (int p = p_begin + wave; p < p_end; p += 4) {
     const T* xr = xim + (size_t)p * C;
@@ -103,6 +104,7 @@ __global__ __launch_bounds__(256) void m1g_pool_fwd_kernel(
   float* pa = pacc + (size_t)blk * C;
   for (int c = threadIdx.x; c < C; c += 256)
     pa[c] = (sm[c] * ws[0] + sm[C + c] * ws[1]) + (sm[2 * (size_t)C + c] * ws[2] + sm[3 * (size_t)C + c] * ws[3]);
+  m1_gather_note(n, s == 0 && threadIdx.x == 0, g);
   if (threadIdx.x == 0) {
     pstat[blk * 4 + 0] = m_blk;
     pstat[blk * 4 + 1] = l_blk;
@@ -111,14 +113,15 @@ __global__ __launch_bounds__(256) void m1g_pool_fwd_kernel(
   }
 }
 
-template <typename T, bool FUSED, bool TRAIN, bool NODX>
+template <typename T, bool FUSED, bool TRAIN, bool NODX, bool GATHER = false>
 __global__ __launch_bounds__(256) void m1g_bwd_main_kernel(
     const T* __restrict__ X, const float* __restrict__ Wa, const float* __restrict__ att,
     const float* __restrict__ dz, const float* __restrict__ zsave, const float* __restrict__ abar,
     const float* __restrict__ G, const float* __restrict__ bt, const float* __restrict__ sn_pre,
     T* __restrict__ dX, float* __restrict__ dZout, float* __restrict__ pdwa, float* __restrict__ pdba,
     int P, int S, int C, int K, int act, float inv_keep, uint32_t thresh, uint64_t seed, uint64_t offset,
-    const uint64_t* __restrict__ offset_dev, const float* __restrict__ dA_extra, float extra_scale) {
+    const uint64_t* __restrict__ offset_dev, const float* __restrict__ dA_extra, float extra_scale,
+    M1GatherArg<GATHER> g) {
   constexpr int EPV = Vec<T>::EPV;
   extern __shared__ __attribute__((aligned(16))) float sm[];   // FUSED: [4][C] dwa accumulators; then 8 floats
   float* sm_aux = sm + (FUSED ? 4 * (size_t)C : 0);
@@ -147,7 +150,7 @@ __global__ __launch_bounds__(256) void m1g_bwd_main_kernel(
     for (int c = lane; c < C; c += 64) zdz = fmaf(zsave[(size_t)n * C + c], dzr[c], zdz);
     corr = wave_sum(zdz) + sn * abar[n];
   }
-  const T* xim = X + (size_t)n * P * C;
+  const T* xim = X + (size_t)(GATHER ? m1_src_image(n, g) : n) * P * C;
   T* dxim = NODX ? nullptr : dX + (size_t)n * P * C;
   float dba_acc = 0.f;
   for (int p = p_begin + wave; p < p_end; p += 4) {
@@ -249,13 +252,28 @@ template <typename T>
 static int launch_fwd_t(const M1Call& c, const M1Fwd& io) {
   const size_t shm = (size_t)4 * c.C * 4 + 64;
   if (M1Trace* t = m1_trace()) t->pool_fwd = M1_POOL_GENERIC;
+  if (c.gather) {   // (m1_call_fill: fused)
+    auto go = [&](auto TR) -> int {
+      auto kernel = m1g_pool_fwd_kernel<T, true, decltype(TR)::value, true>;
+      int rc = set_lds(kernel, shm);
+      if (rc != APA_OK) return rc;
+      launch_ev(kernel, dim3(c.pl.nblk), dim3(256), shm, c.st, c.ev0, c.ev1, static_cast<const T*>(io.X), io.Wa, io.ba,
+                io.att, c.pacc, c.pstat, c.P, c.pl.S, c.C, c.pool_act, c.inv_keep, c.key.thresh, c.key.seed,
+                c.key.offset, c.key.offset_dev, c.ga);
+      return APA_OK;
+    };
+    const int rc = c.train ? go(std::true_type{}) : go(std::false_type{});
+    if (rc != APA_OK) return rc;
+    APA_LAUNCH_CHECK("m1g_pool_fwd_kernel");
+    return APA_OK;
+  }
   int rc = m1_fused_train(c.fused, c.train, [&](auto F, auto TR) -> int {
     auto kernel = m1g_pool_fwd_kernel<T, decltype(F)::value, decltype(TR)::value>;
     int rc = set_lds(kernel, shm);
     if (rc != APA_OK) return rc;
     launch_ev(kernel, dim3(c.pl.nblk), dim3(256), shm, c.st, c.ev0, c.ev1, static_cast<const T*>(io.X), io.Wa, io.ba,
               io.att, c.pacc, c.pstat, c.P, c.pl.S, c.C, c.pool_act, c.inv_keep, c.key.thresh, c.key.seed,
-              c.key.offset, c.key.offset_dev);
+              c.key.offset, c.key.offset_dev, M1NoGather{});
     return APA_OK;
   });
   if (rc != APA_OK) return rc;
@@ -267,6 +285,22 @@ template <typename T>
 static int launch_bwd_t(const M1Call& c, const M1Bwd& io) {
   const size_t shm = (c.fused ? (size_t)4 * c.C * 4 : 0) + 64;
   if (M1Trace* t = m1_trace()) t->pool_bwd = M1_POOL_GENERIC;
+  if (c.gather) {   // (m1_call_fill: fused, no dX)
+    auto go = [&](auto TR) -> int {
+      auto kernel = m1g_bwd_main_kernel<T, true, decltype(TR)::value, true, true>;
+      int rc = set_lds(kernel, shm);
+      if (rc != APA_OK) return rc;
+      launch_ev(kernel, dim3(c.pl.nblk), dim3(256), shm, c.st, c.ev0, c.ev1, static_cast<const T*>(io.X), io.Wa, io.att,
+                c.dz, io.zsave, io.abar, io.G, io.bt, c.sn, static_cast<T*>(nullptr), c.dzatt, c.pdwa, c.pdba, c.P,
+                c.pl.S, c.C, c.K, c.act, c.inv_keep, c.key.thresh, c.key.seed, c.key.offset, c.key.offset_dev, c.ex,
+                c.exs, c.ga);
+      return APA_OK;
+    };
+    const int rc = c.train ? go(std::true_type{}) : go(std::false_type{});
+    if (rc != APA_OK) return rc;
+    APA_LAUNCH_CHECK("m1g_bwd_main_kernel");
+    return APA_OK;
+  }
   auto go = [&](auto F, auto TR, auto NODX) -> int {
     auto kernel = m1g_bwd_main_kernel<T, decltype(F)::value, decltype(TR)::value, decltype(NODX)::value>;
     int rc = set_lds(kernel, shm);
@@ -274,7 +308,7 @@ static int launch_bwd_t(const M1Call& c, const M1Bwd& io) {
     launch_ev(kernel, dim3(c.pl.nblk), dim3(256), shm, c.st, c.ev0, c.ev1, static_cast<const T*>(io.X), io.Wa, io.att,
               c.dz, io.zsave, io.abar, io.G, io.bt, c.sn, static_cast<T*>(io.dX), c.dzatt, c.pdwa, c.pdba, c.P,
               c.pl.S, c.C, c.K, c.act, c.inv_keep, c.key.thresh, c.key.seed, c.key.offset, c.key.offset_dev, c.ex,
-              c.exs);
+              c.exs, M1NoGather{});
     return APA_OK;
   };
   int rc = m1_fused_train(c.fused, c.train, [&](auto F, auto TR) -> int {   // c.no_dx: the arm without the dX stores

@@ -148,4 +148,26 @@ int apa_probe_m1_eval_step(apa::M1Trace* t, const void* X, const void* Xatt, con
                                  ws_bytes, N, P, C, Ca, K, M, flags, dtype, stream);
 }
 
+// the *_cached entry points (apa.h: apa_feature_cache; tests/test_feature_cache_gpu.py)
+int apa_probe_m1_fwd_cached(apa::M1Trace* t, const apa_feature_cache* cache, const apa_hooks* hooks, const void* X,
+                            const void* Xatt, const float* Wa, const float* ba, const float* Wt, const float* bt,
+                            float* logits, float* att, float* zsave, float* abar, void* topdown, void* ws,
+                            size_t ws_bytes, int N, int P, int C, int Ca, int K, int M, unsigned flags, float keep_prob,
+                            uint64_t seed, uint64_t offset, int dtype, void* stream) {
+  TraceScope s(t);
+  return apa_attn_pool_fwd_cached(cache, hooks, X, Xatt, Wa, ba, Wt, bt, logits, att, zsave, abar, topdown, ws,
+                                  ws_bytes, N, P, C, Ca, K, M, flags, keep_prob, seed, offset, dtype, stream);
+}
+
+int apa_probe_m1_bwd_cached(apa::M1Trace* t, const apa_feature_cache* cache, const apa_hooks* hooks, const void* X,
+                            const void* Xatt, const float* Wa, const float* ba, const float* Wt, const float* bt,
+                            const float* att, const float* zsave, const float* abar, const float* G, void* dX,
+                            void* dXatt, float* dWa, float* dba, float* dWt, float* dbt, void* ws, size_t ws_bytes,
+                            int N, int P, int C, int Ca, int K, int M, unsigned flags, float keep_prob, uint64_t seed,
+                            uint64_t offset, int dtype, void* stream) {
+  TraceScope s(t);
+  return apa_attn_pool_bwd_cached(cache, hooks, X, Xatt, Wa, ba, Wt, bt, att, zsave, abar, G, dX, dXatt, dWa, dba, dWt,
+                                  dbt, ws, ws_bytes, N, P, C, Ca, K, M, flags, keep_prob, seed, offset, dtype, stream);
+}
+
 }  // extern "C"

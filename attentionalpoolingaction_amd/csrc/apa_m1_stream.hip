@@ -289,13 +289,16 @@ __device__ __forceinline__ void fwd_chunk(FwdState<T, VW, PIX, FUSED, TRAIN>& st
 // global_load; the rest is fetched with s_load under the first chunk.  The dropout key (a dependent read of the
 // device counter) is formed behind the issue of the ring's first NB - 1 chunks: chunk 0's arithmetic is its first
 // use, behind an HBM wait that is longer.
-template <typename T, int VW, int PIX, bool FUSED, bool TRAIN, bool RIN = false>
+// GATHER: the gathered instances (apa_device.h: M1Gather; the plain ones take an empty M1NoGather).  The window is full,
+// so the descriptor lies behind it: the index read is one scalar load in front of the first chunk's address, which the
+// plain instances do not have.
+template <typename T, int VW, int PIX, bool FUSED, bool TRAIN, bool RIN = false, bool GATHER = false>
 __global__ __launch_bounds__(256, 2) void m1s_pool_fwd_kernel(
     const T* __restrict__ X, int P, int S, int nblk, int act, const float* __restrict__ Wa,
     const float* __restrict__ ba, float* __restrict__ att, float* __restrict__ pacc,
     // ---- beyond the preload window ----
     float* __restrict__ pstat, float inv_keep, uint32_t thresh, uint64_t seed, uint64_t offset,
-    const uint64_t* __restrict__ offset_dev, uint8_t* __restrict__ maskbits) {
+    const uint64_t* __restrict__ offset_dev, uint8_t* __restrict__ maskbits, M1GatherArg<GATHER> g) {
   constexpr int EPV = Vec<T>::EPV;
   constexpr int EPL = VW * EPV;   // channels per lane
   constexpr int CW = EPL * 64;    // channels per wave
@@ -311,7 +314,7 @@ __global__ __launch_bounds__(256, 2) void m1s_pool_fwd_kernel(
   const int nchunk = (npt + PIX - 1) / PIX;
   const int cbase = wave * CW + lane * EPV;   // + j * 64 * EPV
 
-  const T* xim = opaque_global(X + (size_t)n * P * C);
+  const T* xim = opaque_global(X + (size_t)(GATHER ? m1_src_image(n, g) : n) * P * C);
   float* att_im = att + (size_t)n * P;
   uint8_t* bits_im = TRAIN ? maskbits + (size_t)n * P * MaskBytes<EPL>::BPP : nullptr;
 
@@ -373,6 +376,7 @@ __global__ __launch_bounds__(256, 2) void m1s_pool_fwd_kernel(
           make_float4(st.acc[i], st.acc[i + 1], st.acc[i + 2], st.acc[i + 3]);
     }
   }
+  m1_gather_note(n, s == 0 && threadIdx.x == 0, g);
   if (threadIdx.x == 0) {
     pstat[blk * 4 + 0] = (FUSED && act == M1_ACT_SOFTMAX) ? st.m_run : 0.f;
     pstat[blk * 4 + 1] = st.l_run;
@@ -506,7 +510,8 @@ template <int BPL> __device__ __forceinline__ uint32_t ld_keep_bits(const uint8_
   return *reinterpret_cast<const uint16_t*>(p);
 }
 
-template <typename T, int VW, int PIX, bool FUSED, bool TRAIN, bool RIN = false, bool BITS = false, bool NODX = false>
+template <typename T, int VW, int PIX, bool FUSED, bool TRAIN, bool RIN = false, bool BITS = false, bool NODX = false,
+          bool GATHER = false>
 __global__ __launch_bounds__(256, 2) void m1s_bwd_main_kernel(
     const T* __restrict__ X, int P, int S, int nblk, int K, const float* __restrict__ att,
     const float* __restrict__ dA_extra, const uint8_t* __restrict__ maskbits, const float* __restrict__ dz,
@@ -515,7 +520,7 @@ __global__ __launch_bounds__(256, 2) void m1s_bwd_main_kernel(
     const float* __restrict__ G, const float* __restrict__ bt, const float* __restrict__ sn_pre,
     T* __restrict__ dX, float* __restrict__ dZout, float* __restrict__ pdwa,
     float* __restrict__ pdba, int act, float inv_keep, uint32_t thresh,
-    uint64_t seed, uint64_t offset, const uint64_t* __restrict__ offset_dev, float extra_scale) {
+    uint64_t seed, uint64_t offset, const uint64_t* __restrict__ offset_dev, float extra_scale, M1GatherArg<GATHER> g) {
   // dA_extra [N,P]: per-pixel additive term of dA * P from the concatenated pose channels; callers
   // without them pass `att` and extra_scale = 0, so the load is unconditional (straight-line code)
   constexpr int EPV = Vec<T>::EPV;
@@ -535,7 +540,7 @@ __global__ __launch_bounds__(256, 2) void m1s_bwd_main_kernel(
   const int cbase = wave * CW + lane * EPV;
   const float invP = 1.0f / (float)P;
 
-  const T* xim = opaque_global(X + (size_t)n * P * C);
+  const T* xim = opaque_global(X + (size_t)(GATHER ? m1_src_image(n, g) : n) * P * C);
   T* dxim = NODX ? nullptr : dX + (size_t)n * P * C;   // NODX: dX may be NULL and is never dereferenced
   const float* att_im = opaque_global(att + (size_t)n * P);     // (prefetched with the chunk: keep the loads chained)
   float* dZout_im = FUSED ? nullptr : dZout + (size_t)n * P;
@@ -666,11 +671,19 @@ static int launch_fwd_t(const M1Call& c, const M1Fwd& io) {
     launch_ev(m1s_pool_fwd_kernel<T, VW, PIX, decltype(F)::value, decltype(TR)::value, decltype(RIN)::value>,
               dim3(c.pl.nblk), dim3(256), 0, c.st, c.ev0, c.ev1, static_cast<const T*>(io.X), c.P, c.pl.S, c.pl.nblk,
               c.pool_act, io.Wa, io.ba, io.att, c.pacc, c.pstat, c.inv_keep, c.key.thresh, c.key.seed, c.key.offset,
-              c.key.offset_dev, c.maskbits);
+              c.key.offset_dev, c.maskbits, M1NoGather{});
     return APA_OK;
   };
+  // the gathered instances (m1_call_fill: fused, no relu on the input)
+  auto gathered = [&](auto TR) {
+    launch_ev(m1s_pool_fwd_kernel<T, VW, PIX, true, decltype(TR)::value, false, true>, dim3(c.pl.nblk), dim3(256), 0,
+              c.st, c.ev0, c.ev1, static_cast<const T*>(io.X), c.P, c.pl.S, c.pl.nblk, c.pool_act, io.Wa, io.ba, io.att,
+              c.pacc, c.pstat, c.inv_keep, c.key.thresh, c.key.seed, c.key.offset, c.key.offset_dev, c.maskbits, c.ga);
+  };
   const std::true_type yes; const std::false_type no;
-  if (c.relu_input) {   // instantiated for the fused map only
+  if (c.gather) {
+    if (c.train) gathered(yes); else gathered(no);
+  } else if (c.relu_input) {   // instantiated for the fused map only
     if (c.train) go(yes, yes, yes); else go(yes, no, yes);
   } else {
     m1_fused_train(c.fused, c.train, [&](auto F, auto TR) { return go(F, TR, no); });
@@ -691,17 +704,33 @@ static int launch_bwd_t(const M1Call& c, const M1Bwd& io) {
                                   decltype(BITS)::value, decltype(NODX)::value>,
               dim3(c.pl.nblk), dim3(256), 0, c.st, c.ev0, c.ev1, static_cast<const T*>(io.X), c.P, c.pl.S, c.pl.nblk, c.K,
               io.att, c.ex, mbits, c.dz, io.Wa, io.zsave, io.abar, io.G, io.bt, c.sn, static_cast<T*>(io.dX), c.dzatt,
-              c.pdwa, c.pdba, c.act, c.inv_keep, c.key.thresh, c.key.seed, c.key.offset, c.key.offset_dev, c.exs);
+              c.pdwa, c.pdba, c.act, c.inv_keep, c.key.thresh, c.key.seed, c.key.offset, c.key.offset_dev, c.exs,
+              M1NoGather{});
     return APA_OK;
   };
   const std::true_type yes; const std::false_type no;
   // every form has its arm without the dX stores (APA_FLAG_FROZEN_INPUT / APA_IFLAG_NO_DX): c.no_dx never reaches an
   // instance that stores through dX
   auto arm = [&](auto F, auto TR, auto RIN, auto BITS) { return c.no_dx ? go(F, TR, RIN, BITS, yes) : go(F, TR, RIN, BITS, no); };
+  // the gathered instances (m1_call_fill: fused, no relu on the input, no dX)
+  auto gathered = [&](auto TR, auto BITS) {
+    launch_ev(m1s_bwd_main_kernel<T, VW, PIX, true, decltype(TR)::value, false, decltype(BITS)::value, true, true>,
+              dim3(c.pl.nblk), dim3(256), 0, c.st, c.ev0, c.ev1, static_cast<const T*>(io.X), c.P, c.pl.S, c.pl.nblk, c.K,
+              io.att, c.ex, mbits, c.dz, io.Wa, io.zsave, io.abar, io.G, io.bt, c.sn, static_cast<T*>(nullptr), c.dzatt,
+              c.pdwa, c.pdba, c.act, c.inv_keep, c.key.thresh, c.key.seed, c.key.offset, c.key.offset_dev, c.exs, c.ga);
+  };
   bool bits = false;   // the keep-bits variant: bf16 features
   if constexpr (KeepBits<T>::ON) bits = c.train && mbits;
   if (tr && !c.relu_input) tr->keep_bits = bits;
-  if (c.relu_input) {   // instantiated for the fused map only
+  if (c.gather) {
+    if (bits) {
+      if constexpr (KeepBits<T>::ON) gathered(yes, yes);
+    } else if (c.train) {
+      gathered(yes, no);
+    } else {
+      gathered(no, no);
+    }
+  } else if (c.relu_input) {   // instantiated for the fused map only
     if (c.train) arm(yes, yes, yes, no); else arm(yes, no, yes, no);
   } else if (bits) {
     if constexpr (KeepBits<T>::ON) {

@@ -23,12 +23,13 @@ namespace apa {
 // Outputs: att (FUSED: id/relu -> final A, softmax -> raw Z, normalised in F2),
 //          pacc[blk][C] partial sum_p A*Xt, pstat[blk][4] = {m, l, asum, -}.
 // --------------------------------------------------------------------------------------------
-template <typename T, int VEC, bool FUSED, bool TRAIN>
+// GATHER: the gathered instances (apa_device.h: M1Gather; the plain ones take an empty M1NoGather)
+template <typename T, int VEC, bool FUSED, bool TRAIN, bool GATHER = false>
 __global__ __launch_bounds__(256) void m1_pool_fwd_kernel(
     const T* __restrict__ X, const float* __restrict__ Wa, const float* __restrict__ ba,
     float* __restrict__ att, float* __restrict__ pacc, float* __restrict__ pstat, int P, int S,
     int act, float inv_keep, uint32_t thresh, uint64_t seed, uint64_t offset,
-    const uint64_t* __restrict__ offset_dev) {
+    const uint64_t* __restrict__ offset_dev, M1GatherArg<GATHER> g) {
   constexpr int EPV = Vec<T>::EPV;
   constexpr int EPL = VEC * EPV;
   constexpr int C = EPL * 64;
@@ -65,7 +66,7 @@ __global__ __launch_bounds__(256) void m1_pool_fwd_kernel(
   for (int i = 0; i < EPL; ++i) acc[i] = 0.f;
   float m_run = -INFINITY, l_run = 0.f, a_sum = 0.f;
 
-  const T* xim = X + (size_t)n * P * C;
+  const T* xim = X + (size_t)(GATHER ? m1_src_image(n, g) : n) * P * C;
   float* att_im = att + (size_t)n * P;
 
   uint4 cur[VEC], nxt[VEC];
@@ -174,6 +175,7 @@ __global__ __launch_bounds__(256) void m1_pool_fwd_kernel(
     r.w = (a0.w + a1.w) + (a2.w + a3.w);
     *reinterpret_cast<float4*>(pa + v * 4) = r;
   }
+  m1_gather_note(n, s == 0 && threadIdx.x == 0, g);
   if (threadIdx.x == 0) {
     pstat[blk * 4 + 0] = m_blk;
     pstat[blk * 4 + 1] = l_blk;
@@ -188,7 +190,7 @@ __global__ __launch_bounds__(256) void m1_pool_fwd_kernel(
 // NODX (APA_FLAG_FROZEN_INPUT): nothing is stored through dX (it may be NULL); dZout / pdwa / pdba are formed by the
 // same operations in the same order as in the writing arm.
 // --------------------------------------------------------------------------------------------
-template <typename T, int VEC, bool FUSED, bool TRAIN, bool NODX>
+template <typename T, int VEC, bool FUSED, bool TRAIN, bool NODX, bool GATHER = false>
 __global__ __launch_bounds__(256) void m1_bwd_main_kernel(
     const T* __restrict__ X, const float* __restrict__ Wa, const float* __restrict__ att,
     const float* __restrict__ dz, const float* __restrict__ zsave, const float* __restrict__ abar,
@@ -196,7 +198,8 @@ __global__ __launch_bounds__(256) void m1_bwd_main_kernel(
     const float* __restrict__ sn_pre, T* __restrict__ dX,
     float* __restrict__ dZout, float* __restrict__ pdwa, float* __restrict__ pdba, int P, int S,
     int K, int act, float inv_keep, uint32_t thresh, uint64_t seed, uint64_t offset,
-    const uint64_t* __restrict__ offset_dev, const float* __restrict__ dA_extra, float extra_scale) {
+    const uint64_t* __restrict__ offset_dev, const float* __restrict__ dA_extra, float extra_scale,
+    M1GatherArg<GATHER> g) {
   constexpr int EPV = Vec<T>::EPV;
   constexpr int EPL = VEC * EPV;
   constexpr int C = EPL * 64;
@@ -215,7 +218,7 @@ __global__ __launch_bounds__(256) void m1_bwd_main_kernel(
 
   // the first pixel's HBM loads go out before anything else; the per-image constants below
   // (L2 hits) are fetched in their shadow
-  const T* xim = X + (size_t)n * P * C;
+  const T* xim = X + (size_t)(GATHER ? m1_src_image(n, g) : n) * P * C;
   T* dxim = NODX ? nullptr : dX + (size_t)n * P * C;
   const float* att_im = att + (size_t)n * P;
   uint4 cur[VEC], nxt[VEC];
@@ -381,10 +384,20 @@ bool m1v_supported(int C, int dtype) {
 template <typename T, int VEC>
 static int launch_fwd_t(const M1Call& c, const M1Fwd& io) {
   if (M1Trace* t = m1_trace()) { t->pool_fwd = M1_POOL_VEC; t->fwd_w = VEC; t->fwd_pix = 0; }
+  if (c.gather) {   // (m1_call_fill: fused)
+    auto go = [&](auto TR) {
+      launch_ev(m1_pool_fwd_kernel<T, VEC, true, decltype(TR)::value, true>, dim3(c.pl.nblk), dim3(256), 0, c.st,
+                c.ev0, c.ev1, static_cast<const T*>(io.X), io.Wa, io.ba, io.att, c.pacc, c.pstat, c.P, c.pl.S,
+                c.pool_act, c.inv_keep, c.key.thresh, c.key.seed, c.key.offset, c.key.offset_dev, c.ga);
+    };
+    if (c.train) go(std::true_type{}); else go(std::false_type{});
+    APA_LAUNCH_CHECK("m1_pool_fwd_kernel");
+    return APA_OK;
+  }
   m1_fused_train(c.fused, c.train, [&](auto F, auto TR) {
     launch_ev(m1_pool_fwd_kernel<T, VEC, decltype(F)::value, decltype(TR)::value>, dim3(c.pl.nblk), dim3(256), 0,
               c.st, c.ev0, c.ev1, static_cast<const T*>(io.X), io.Wa, io.ba, io.att, c.pacc, c.pstat, c.P, c.pl.S,
-              c.pool_act, c.inv_keep, c.key.thresh, c.key.seed, c.key.offset, c.key.offset_dev);
+              c.pool_act, c.inv_keep, c.key.thresh, c.key.seed, c.key.offset, c.key.offset_dev, M1NoGather{});
     return APA_OK;
   });
   APA_LAUNCH_CHECK("m1_pool_fwd_kernel");
@@ -394,12 +407,23 @@ static int launch_fwd_t(const M1Call& c, const M1Fwd& io) {
 template <typename T, int VEC>
 static int launch_bwd_t(const M1Call& c, const M1Bwd& io) {
   if (M1Trace* t = m1_trace()) { t->pool_bwd = M1_POOL_VEC; t->bwd_w = VEC; t->bwd_pix = 0; }
+  if (c.gather) {   // (m1_call_fill: fused, no dX)
+    auto go = [&](auto TR) {
+      launch_ev(m1_bwd_main_kernel<T, VEC, true, decltype(TR)::value, true, true>, dim3(c.pl.nblk), dim3(256), 0,
+                c.st, c.ev0, c.ev1, static_cast<const T*>(io.X), io.Wa, io.att, c.dz, io.zsave, io.abar, io.G, io.bt,
+                c.sn, static_cast<T*>(nullptr), c.dzatt, c.pdwa, c.pdba, c.P, c.pl.S, c.K, c.act, c.inv_keep,
+                c.key.thresh, c.key.seed, c.key.offset, c.key.offset_dev, c.ex, c.exs, c.ga);
+    };
+    if (c.train) go(std::true_type{}); else go(std::false_type{});
+    APA_LAUNCH_CHECK("m1_bwd_main_kernel");
+    return APA_OK;
+  }
   auto go = [&](auto F, auto TR, auto NODX) {
     launch_ev(m1_bwd_main_kernel<T, VEC, decltype(F)::value, decltype(TR)::value, decltype(NODX)::value>,
               dim3(c.pl.nblk), dim3(256), 0,
               c.st, c.ev0, c.ev1, static_cast<const T*>(io.X), io.Wa, io.att, c.dz, io.zsave, io.abar, io.G, io.bt,
               c.sn, static_cast<T*>(io.dX), c.dzatt, c.pdwa, c.pdba, c.P, c.pl.S, c.K, c.act, c.inv_keep,
-              c.key.thresh, c.key.seed, c.key.offset, c.key.offset_dev, c.ex, c.exs);
+              c.key.thresh, c.key.seed, c.key.offset, c.key.offset_dev, c.ex, c.exs, M1NoGather{});
     return APA_OK;
   };
   m1_fused_train(c.fused, c.train, [&](auto F, auto TR) {   // c.no_dx: the arm without the dX stores

@@ -65,6 +65,19 @@ _SIGNATURES = {
     'apa_fp8_features_bytes': (c_size_t, [c_int, c_int, c_int]),
     'apa_quantize_features_fp8': (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     'apa_dequantize_features_fp8': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
+    # a resident feature cache read by image index: `const apa_feature_cache*` first, then the *_ex arguments (the
+    # evaluation step: then those of apa_attn_head_eval_step_clips)
+    'apa_attn_pool_fwd_cached': (c_int, [c_void_p] * 14 + [c_size_t] + [c_int] * 6 +
+                                 [c_uint, c_float, c_uint64, c_uint64, c_int, c_void_p]),
+    'apa_attn_pool_bwd_cached': (c_int, [c_void_p] * 19 + [c_size_t] + [c_int] * 6 +
+                                 [c_uint, c_float, c_uint64, c_uint64, c_int, c_void_p]),
+    'apa_attn_head_train_step_cached': (c_int, [c_void_p] * 9 + [c_float, c_float] + [c_void_p] * 13 +
+                                        [c_size_t] + [c_int] * 6 + [c_uint, c_float, c_uint64, c_uint64, c_int,
+                                                                    c_void_p]),
+    'apa_attn_head_eval_step_cached': (c_int, [c_void_p, c_void_p, c_int] + [c_void_p] * 15 + [c_size_t] + [c_int] * 6 +
+                                       [c_uint, c_int, c_void_p]),
+    'apa_quantize_features_fp8_at': (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int,
+                                             c_void_p]),
     'apa_pose_head_workspace_bytes': (c_size_t, [c_int] * 6),
     'apa_pose_head_fwd': (c_int, [c_void_p] * 8 + [c_size_t] + [c_int] * 6 + [c_void_p]),
     'apa_pose_head_bwd': (c_int, [c_void_p] * 7 + [c_int] + [c_void_p] * 5 + [c_size_t] + [c_int] * 6 +
@@ -238,6 +251,8 @@ def _stream_ptr() -> int:
 
 
 def _feat_dtype(t) -> int:
+    if isinstance(t, CachedBatch):
+        t = t.cache.features
     if isinstance(t, Fp8Features):
         return APA_DTYPE_FP8_E4M3
     if t.dtype == torch.float32:
@@ -369,6 +384,16 @@ def quantize_features(X: torch.Tensor):
                                                       _stream_ptr())
         _check(rc, 'apa_quantize_features_fp8')
         return out, status
+    codes, scale, bad = _quantize_rule_cpu(X)
+    out.codes.copy_(codes)
+    out.scale.copy_(scale)
+    status.copy_(bad)
+    return out, status
+
+
+def _quantize_rule_cpu(X: torch.Tensor):
+    """(codes float8_e4m3fn like X, scale float32 [N], status int32 [N]): the quantisation rule in torch on the CPU"""
+    N = X.shape[0]
     x = X.to(torch.float32).reshape(N, -1)
     bad = ~torch.isfinite(x).all(dim=1)
     amax = torch.where(bad, torch.zeros(()), x.abs().amax(dim=1))
@@ -378,10 +403,166 @@ def quantize_features(X: torch.Tensor):
     scale = torch.where(live, amax / m, torch.zeros(()))
     inv = torch.where(live, m / torch.where(live, amax, one), torch.zeros(()))
     y = torch.where(live[:, None], x * inv[:, None], torch.zeros(()))
-    out.codes.copy_(y.to(torch.float8_e4m3fn).view(X.shape))
-    out.scale.copy_(scale)
-    status.copy_(bad.to(torch.int32))
-    return out, status
+    return y.to(torch.float8_e4m3fn).view(X.shape), scale, bad.to(torch.int32)
+
+
+# --------------------------------------------------------------------------------------------
+# a resident feature cache read by image index (include/apa.h: apa_feature_cache)
+# --------------------------------------------------------------------------------------------
+class ApaFeatureCache(ctypes.Structure):
+    """`apa_feature_cache` of include/apa.h (field order is the ABI)."""
+    _fields_ = [('index', c_void_p), ('cache_images', c_int), ('labels_cached', c_int), ('status', c_void_p)]
+
+
+def _index_tensor(who: str, index, device, n_images: Optional[int] = None) -> torch.Tensor:
+    """`index` (tensor or sequence of image ids) as a contiguous int32 tensor on `device`; an int32 tensor that already
+    is one passes through uncopied (an epoch's views)."""
+    t = index if isinstance(index, torch.Tensor) else torch.as_tensor(list(index), dtype=torch.int64)
+    if t.dim() != 1 or t.numel() < 1 or t.dtype.is_floating_point or t.dtype == torch.bool:
+        raise ApaError('{}: a non-empty 1-D integer index expected'.format(who))
+    if t.dtype != torch.int32 or t.device != torch.device(device) or not t.is_contiguous():
+        t = t.to(device=device, dtype=torch.int32).contiguous()
+    if n_images is not None and t.numel() != n_images:
+        raise ApaError('{}: an index of {} images expected (got {})'.format(who, n_images, t.numel()))
+    return t
+
+
+class FeatureCache(object):
+    """T cached conv5 maps [T,H,W,C] (float32 / bfloat16 tensor, or one Fp8Features of N = T) that stay where they are:
+    a batch is the cache plus a vector of image ids (`select`), which the gathered kernels read through -- no gathered
+    copy per step.  `labels`: optional int64 [T], read through the same index when a step is given `labels=None`.
+    `status` (int32 [1] on the cache's device): how many ids outside [0, T) the forward passes met and clamped since it
+    was last zeroed.  `gather` makes the copy a loop without the gathered kernels makes; it is the comparison route."""
+
+    def __init__(self, features, labels: Optional[torch.Tensor] = None):
+        fp8 = isinstance(features, Fp8Features)
+        if not fp8 and features.dtype not in (torch.float32, torch.bfloat16):
+            raise ApaError('FeatureCache: float32 / bfloat16 features or an Fp8Features expected')
+        if features.dim() < 3 or not features.is_contiguous():
+            raise ApaError('FeatureCache: contiguous [T, ..., C] features expected')
+        self.features, self.shape = features, tuple(int(d) for d in features.shape)
+        self.T = self.shape[0]
+        self.device = features.device
+        if labels is not None and (labels.dtype != torch.int64 or labels.numel() != self.T or
+                                   labels.device != self.device or not labels.is_contiguous()):
+            raise ApaError('FeatureCache: labels int64 [{}] on the cache\'s device expected'.format(self.T))
+        self.labels = labels
+        self.status = torch.zeros((1,), dtype=torch.int32, device=self.device)
+
+    fp8 = property(lambda self: isinstance(self.features, Fp8Features))
+    dtype = property(lambda self: self.features.dtype)
+
+    @classmethod
+    def empty(cls, shape, dtype, device, labels: Optional[torch.Tensor] = None) -> 'FeatureCache':
+        """a zeroed cache of `shape` = [T,H,W,C]; dtype torch.float32 / bfloat16 / float8_e4m3fn"""
+        if dtype == torch.float8_e4m3fn:
+            return cls(Fp8Features.empty(shape, device), labels)
+        return cls(torch.zeros(tuple(shape), dtype=dtype, device=device), labels)
+
+    def write(self, first: int, features: torch.Tensor) -> torch.Tensor:
+        """Images [first, first + n) <- `features` [n,H,W,C] float32 / bfloat16 on the cache's device: cast (fp32 / bf16
+        cache) or quantised into place (FP8: apa_quantize_features_fp8_at; a CPU cache applies the same rule in torch,
+        bit for bit).  Returns the int32 [n] status of quantize_features (zeros for a cast)."""
+        n, first = int(features.shape[0]), int(first)
+        if tuple(features.shape[1:]) != self.shape[1:] or first < 0 or first + n > self.T:
+            raise ApaError('FeatureCache.write: [n,{}] features for slots inside [0, {}) expected'.format(
+                ','.join(str(d) for d in self.shape[1:]), self.T))
+        if features.dtype not in (torch.float32, torch.bfloat16) or features.device != self.device:
+            raise ApaError('FeatureCache.write: float32 / bfloat16 features on the cache\'s device expected')
+        status = torch.zeros((n,), dtype=torch.int32, device=self.device)
+        if not self.fp8:
+            self.features[first:first + n].copy_(features)
+            return status
+        f = self.features
+        if not f.is_cuda:
+            codes, scale, bad = _quantize_rule_cpu(features)
+            f.codes[first:first + n].copy_(codes)
+            f.scale[first:first + n].copy_(scale)
+            status.copy_(bad)
+            return status
+        C = self.shape[-1]
+        src = features.contiguous()
+        rc = load_library().apa_quantize_features_fp8_at(
+            _dev_ptr(src, 'features'), APA_DTYPE_F32 if src.dtype == torch.float32 else APA_DTYPE_BF16, f.data_ptr(),
+            self.T, first, status.data_ptr(), n, src.numel() // (n * C), C, _stream_ptr())
+        _check(rc, 'apa_quantize_features_fp8_at')
+        return status
+
+    def gather(self, index):
+        """the batch as a copy: features[index] (an Fp8Features for an FP8 cache: from_parts(codes[index],
+        scale[index])) -- what a loop without the gathered kernels does every step"""
+        idx = _index_tensor('FeatureCache.gather', index, self.device).long()
+        if self.fp8:
+            return Fp8Features.from_parts(self.features.codes[idx], self.features.scale[idx])
+        return self.features[idx]
+
+    def select(self, index) -> 'CachedBatch':
+        """the batch without a copy: this cache and `index` (int32 on the cache's device, or converted once)"""
+        return CachedBatch(self, index)
+
+    def epoch(self, batch_size: int, seed: int, shuffle: bool = True, drop_last: bool = True):
+        """One permutation of the T image ids per call, drawn on the cache's device from `seed` (arange without
+        `shuffle`), yielded as its `batch_size`-long int32 views; the short last batch is dropped or yielded."""
+        if batch_size < 1:
+            raise ApaError('FeatureCache.epoch: batch_size >= 1 expected')
+        if shuffle:
+            g = torch.Generator(device=self.device)
+            g.manual_seed(int(seed))
+            perm = torch.randperm(self.T, generator=g, device=self.device).to(torch.int32)
+        else:
+            perm = torch.arange(self.T, dtype=torch.int32, device=self.device)
+        end = self.T - self.T % batch_size if drop_last else self.T
+        for a in range(0, end, batch_size):
+            yield perm[a:min(a + batch_size, end)]
+
+
+class CachedBatch(object):
+    """N images of a FeatureCache named by an int32 index: pass one as `X` (and the same object as `Xatt`) to
+    attn_pool_fwd / attn_pool_bwd(want_dx=False) / HeadTrainStep(grads[0] = None) / HeadEvalStep.  Nothing is copied;
+    the kernels fetch image index[n] where they fetch image n of a plain batch, and the results are those of the same
+    call on `cache.gather(index)`, bit for bit."""
+
+    def __init__(self, cache: FeatureCache, index):
+        self.cache = cache
+        self.index = _index_tensor('CachedBatch', index, cache.device)
+        self.shape = (int(self.index.numel()),) + cache.shape[1:]
+
+    # what the wrappers ask of a feature tensor
+    device = property(lambda self: self.cache.device)
+    is_cuda = property(lambda self: self.cache.features.is_cuda)
+    dtype = property(lambda self: self.cache.features.dtype)
+
+    def dim(self) -> int:
+        return len(self.shape)
+
+    def numel(self) -> int:
+        return int(np.prod(self.shape))
+
+    def is_contiguous(self) -> bool:
+        return True
+
+    def data_ptr(self) -> int:
+        return self.cache.features.data_ptr()
+
+    def flat(self) -> 'CachedBatch':
+        return self
+
+    def descriptor(self, labels_cached: bool = False) -> ApaFeatureCache:
+        """the apa_feature_cache of this batch (keep it, and this object, alive while calls that use it are in flight)"""
+        if not self.index.is_cuda:
+            raise ApaError('CachedBatch: the index must live in GPU memory; the HIP path has no CPU fallback')
+        return ApaFeatureCache(self.index.data_ptr(), self.cache.T, 1 if labels_cached else 0,
+                               self.cache.status.data_ptr())
+
+
+def _cached(who: str, X, Xatt, frozen: bool = True) -> Optional['CachedBatch']:
+    """X as a CachedBatch, or None for a plain feature tensor; a cache supplies its own attention input and is frozen"""
+    if not isinstance(X, CachedBatch):
+        return None
+    if Xatt is not X or not frozen:
+        raise ApaError('{}: a CachedBatch is frozen (no gradient for X: want_dx=False / grads[0] = None) and supplies '
+                       'its own attention input (Xatt must be the same object)'.format(who))
+    return X
 
 
 class KeepMask(object):
@@ -491,19 +672,26 @@ def attn_pool_fwd(X, Xatt, Wa, ba, Wt, bt, *, flags=0, keep_prob=1.0, seed=0, of
     K = Wt.shape[1]
     dt = _feat_dtype(X)
     dev = X.device
+    cb = _cached('attn_pool_fwd', X, Xatt)
     logits = torch.empty((N, K), dtype=torch.float32, device=dev)
     att = torch.empty((N, P, M), dtype=torch.float32, device=dev)
     # saved for backward: M == 1 -> z [N,C] + abar [N]; per-class -> the fp32 top-down map [N,P,K]
     zsave = torch.empty((N, C) if M == 1 else (N, P, K), dtype=torch.float32, device=dev)
     abar = torch.empty((N,), dtype=torch.float32, device=dev) if M == 1 else None
+    if want_topdown and isinstance(X, (Fp8Features, CachedBatch)):
+        raise ApaError('attn_pool_fwd: the TopDownAttention dump is not served on a feature cache')
     topdown = torch.empty((N, P, K), dtype=X.dtype, device=dev) if want_topdown else None
     need = int(lib.apa_attn_pool_workspace_bytes(N, P, C, Ca, K, M, flags))
     if workspace is None or workspace.numel() < need:
         workspace = torch.empty((max(need, 16),), dtype=torch.uint8, device=dev)
     xatt_ptr = _dev_ptr(X, 'X') if Xatt is X else _dev_ptr(Xatt, 'Xatt', X.dtype)
     seed, offset, flags = _rng_key(seed, offset, flags)
-    rc = lib.apa_attn_pool_fwd_ex(
-        _hooks_ptr(hooks), _dev_ptr(X, 'X'), xatt_ptr, _dev_ptr(Wa, 'Wa', torch.float32),
+    fn, pre = lib.apa_attn_pool_fwd_ex, ()
+    if cb is not None:      # a FeatureCache read by index: the descriptor in front of the same arguments
+        desc = cb.descriptor()
+        fn, pre = lib.apa_attn_pool_fwd_cached, (ctypes.addressof(desc),)
+    rc = fn(
+        *pre, _hooks_ptr(hooks), _dev_ptr(X, 'X'), xatt_ptr, _dev_ptr(Wa, 'Wa', torch.float32),
         _dev_ptr(ba, 'ba', torch.float32), _dev_ptr(Wt, 'Wt', torch.float32),
         _dev_ptr(bt, 'bt', torch.float32), logits.data_ptr(), att.data_ptr(),
         _dev_ptr(zsave, 'zsave'), _dev_ptr(abar, 'abar'), _dev_ptr(topdown, 'topdown'),
@@ -536,6 +724,11 @@ def attn_pool_bwd(X, Xatt, Wa, ba, Wt, bt, att, zsave, abar, G, *, flags=0, keep
     fp8 = isinstance(X, Fp8Features)
     if fp8 and (want_dx or (out is not None and out[0] is not None)):
         raise ApaError('attn_pool_bwd: an Fp8Features cache has no gradient: pass want_dx=False (and out[0] = None)')
+    cb = _cached('attn_pool_bwd', X, Xatt, frozen=not want_dx and (out is None or out[0] is None))
+    fn, pre = lib.apa_attn_pool_bwd_ex, ()
+    if cb is not None:      # a FeatureCache read by index: the descriptor in front of the same arguments
+        desc = cb.descriptor()
+        fn, pre = lib.apa_attn_pool_bwd_cached, (ctypes.addressof(desc),)
     if dxatt_rank1 and not fused:
         flags |= APA_FLAG_DXATT_RANK1
     if not want_dx:
@@ -561,8 +754,8 @@ def attn_pool_bwd(X, Xatt, Wa, ba, Wt, bt, att, zsave, abar, G, *, flags=0, keep
     seed, offset, flags = _rng_key(seed, offset, flags)
 
     def call(dx, fl):
-        return lib.apa_attn_pool_bwd_ex(
-            _hooks_ptr(hooks), _dev_ptr(X, 'X'), xatt_ptr, _dev_ptr(Wa, 'Wa', torch.float32),
+        return fn(
+            *pre, _hooks_ptr(hooks), _dev_ptr(X, 'X'), xatt_ptr, _dev_ptr(Wa, 'Wa', torch.float32),
             _dev_ptr(ba, 'ba', torch.float32), _dev_ptr(Wt, 'Wt', torch.float32),
             _dev_ptr(bt, 'bt', torch.float32), _dev_ptr(att, 'att', torch.float32),
             _dev_ptr(zsave, 'zsave'), _dev_ptr(abar, 'abar'), _dev_ptr(G, 'G', torch.float32),
@@ -570,7 +763,7 @@ def attn_pool_bwd(X, Xatt, Wa, ba, Wt, bt, att, zsave, abar, G, *, flags=0, keep
             _dev_ptr(dWt, 'dWt'), _dev_ptr(dbt, 'dbt'), workspace.data_ptr(), workspace.numel(), N, P,
             C, Ca, K, M, fl, float(keep_prob), int(seed), offset, dt, _stream_ptr())
     rc = call(dX, flags)
-    if rc == APA_ERR_UNSUPPORTED and not want_dx and not fp8:      # a route without the arm: the full call, dX to scratch
+    if rc == APA_ERR_UNSUPPORTED and not want_dx and not fp8 and cb is None:      # a route without the arm: the full call, dX to scratch
         rc = call(torch.empty_like(X), flags & ~APA_FLAG_FROZEN_INPUT)
     _check(rc, 'apa_attn_pool_bwd')
     return (dX if want_dx else None), dXatt, dWa, dba, dWt, dbt
@@ -1492,6 +1685,10 @@ class HeadTrainStep:
         APA_FLAG_WEIGHT_IMAGES: the caller keeps them current -- `BoundMomentumSGD(..., images=...)` /
         `deploy.MomentumSGD.attach_weight_images(step, ...)` in the optimiser's own launch, or
         `refresh_weight_images()` after any other change of the weights.
+        `X` a CachedBatch (`FeatureCache.select(index)`, passed as `Xatt` too; `grads[0] = None`): the step reads the
+        N images `index` names straight from the resident cache (apa_attn_head_train_step_cached), bit-identical to the
+        step on `cache.gather(index)`; `labels=None` reads the cache's own labels through the same index;
+        `rebind(index=...)` moves the step to another batch of the cache.  Flat softmax cross-entropy, M == 1 only.
         `share_with` (another HeadTrainStep of the same shapes): this step is bound to ITS output tensors, workspace
         and weight images -- a training loop has one set of them; only X / dX differ between the bound steps
         (bench.py's rotating feature-map sets)."""
@@ -1508,7 +1705,22 @@ class HeadTrainStep:
                 raise ApaError('HeadTrainStep: dxatt_rank1 wants grads[1] = dZ, float32 [N*P]')
             flags |= APA_FLAG_DXATT_RANK1
         dX, dXatt, dWa, dba, dWt, dbt = grads
-        self._fp8 = isinstance(X, Fp8Features)
+        # a FeatureCache read by index (apa_attn_head_train_step_cached): `X` is a CachedBatch; `labels=None` reads the
+        # cache's own labels through the same index (labels_cached), else `labels` is [N] as ever
+        cb = self._cached = _cached('HeadTrainStep', X, Xatt, frozen=dX is None)
+        if cb is not None:
+            if dxatt_rank1 or weight_images or int(frames) != 1 or temporal is not None or M != 1 or \
+                    action_loss != 'softmax-xentropy':
+                raise ApaError('HeadTrainStep: a CachedBatch feeds the flat class-agnostic step with the softmax '
+                               'cross-entropy (no clips, sigmoid losses, per-class maps or weight images)')
+            if share_with is not None and share_with._cached is None:
+                raise ApaError('HeadTrainStep: share_with needs another step on a CachedBatch')
+            if labels is None and cb.cache.labels is None:
+                raise ApaError('HeadTrainStep: labels=None needs a FeatureCache with labels')
+            self._fc = cb.descriptor(labels_cached=labels is None)
+            if labels is None:
+                labels = cb.cache.labels
+        self._fp8 = isinstance(cb.cache.features if cb is not None else X, Fp8Features)
         if self._fp8 and (dX is not None or not fused):
             raise ApaError('HeadTrainStep: an Fp8Features cache is frozen (grads[0] must be None) and supplies its own '
                            'attention input (Xatt must be the same object)')
@@ -1578,6 +1790,9 @@ class HeadTrainStep:
         if self._ml is not None:    # (ml, clip or NULL, hooks, then the same arguments without `labels`)
             self._pre = (ctypes.addressof(self._ml), ctypes.addressof(self._clip) if clips else None)
             self._fn, self._name = self.lib.apa_attn_head_train_step_multilabel, 'apa_attn_head_train_step_multilabel'
+        if cb is not None:          # (the descriptor, hooks, then the same arguments)
+            self._pre = (ctypes.addressof(self._fc),)
+            self._fn, self._name = self.lib.apa_attn_head_train_step_cached, 'apa_attn_head_train_step_cached'
 
     def refresh_weight_images(self) -> None:
         """Rebuild the operand images from the current weights (after load_state_dict, or an optimiser that does not
@@ -1587,12 +1802,21 @@ class HeadTrainStep:
             N, C = X.shape[0], X.shape[-1]
             per_class_weight_images(Wa, ba, Wt, bt, self.workspace, N, X.numel() // (N * C), X.dtype)
 
-    def rebind(self, X=None, labels=None, offset=None) -> None:
+    def rebind(self, X=None, labels=None, offset=None, index=None) -> None:
         """Point the bound step at another feature map / label tensor of the SAME shape and dtype (a training loop
         whose backbone hands over a fresh conv5 tensor every step) and / or at another dropout offset (int), without
-        re-allocating outputs or workspace.  Fused attention input only (Xatt is X)."""
+        re-allocating outputs or workspace.  Fused attention input only (Xatt is X).
+        `index` (a step on a CachedBatch): another batch of the same cache -- an int32 tensor of the same length on
+        the cache's device (an epoch's views pass uncopied); one marshalled pointer changes."""
         keep = list(self._keep)
+        if index is not None:
+            if self._cached is None:
+                raise ApaError('HeadTrainStep.rebind: index= needs a step bound to a CachedBatch')
+            self._index = _index_tensor('HeadTrainStep.rebind', index, self._cached.cache.device, self._cached.shape[0])
+            self._fc.index = self._index.data_ptr()
         if X is not None:
+            if self._cached is not None:
+                raise ApaError('HeadTrainStep.rebind: a step on a CachedBatch is re-bound with index=')
             if self._args[0] != self._args[1]:
                 raise ApaError('HeadTrainStep.rebind: a separate attention input is bound')
             if X.shape != keep[0].shape or X.dtype != keep[0].dtype:
@@ -1604,6 +1828,8 @@ class HeadTrainStep:
                 _multilabel_labels('HeadTrainStep.rebind', labels, self._n_loss, self._K)
                 self._ml.labels = _dev_ptr(labels, 'labels', torch.float32)
             else:
+                if self._cached is not None and self._fc.labels_cached:
+                    raise ApaError('HeadTrainStep.rebind: the step reads the cache\'s labels through the index')
                 self._args[6] = _dev_ptr(labels, 'labels', torch.int64)
             keep[6] = labels
         if offset is not None:
@@ -1618,7 +1844,7 @@ class HeadTrainStep:
         (an ApaHooks) overrides the instance's for this call."""
         h = self.hooks if hooks is None else hooks
         rc = self._fn(*self._pre, _hooks_ptr(h), *self._args, _stream_ptr() if stream is None else stream)
-        if rc == APA_ERR_UNSUPPORTED and self.frozen_input and not self._fp8:     # no arm on this route: the full step, dX to scratch
+        if rc == APA_ERR_UNSUPPORTED and self.frozen_input and not self._fp8 and self._cached is None:     # no arm on this route: the full step, dX to scratch
             # (an FP8 cache has no full step to fall back to: the refusal is raised below)
             self.frozen_input = False
             self.dX_scratch = torch.empty_like(self._keep[0])
@@ -1875,7 +2101,11 @@ class HeadEvalStep:
     TemporalAttention conv) and / or `scores='sigmoid'` (the multi-label datasets, no labels): the step is
     apa_attn_head_eval_step_clips -- `logits` stays the [N,K] frame logits, `pooled` [B,K] and `tatt` [N] (None without
     them) are further outputs, and `probs`, `pred`, `labels`, `loss` are per clip (B in place of N).  With the defaults
-    nothing changes."""
+    nothing changes.
+
+    `X` a CachedBatch (`FeatureCache.select(index)`, passed as `Xatt` too): apa_attn_head_eval_step_cached on the images
+    `index` names (flat batches, softmax or sigmoid scores); `labels=None` with softmax scores reads the cache's own
+    labels, if it has any, through the index; `rebind(index=...)` moves the step to another batch of the cache."""
 
     def __init__(self, X, Xatt, Wa, ba, Wt, bt, labels=None, *, flags=0, workspace=None, frames=1, temporal=None,
                  scores='softmax'):
@@ -1885,8 +2115,18 @@ class HeadEvalStep:
         Ca, M, K = Xatt.shape[-1], Wa.shape[1], Wt.shape[1]
         dev = X.device
         flags &= ~APA_FLAG_TRAIN
+        # a FeatureCache read by index (apa_attn_head_eval_step_cached): `X` is a CachedBatch; `labels=None` with
+        # softmax scores reads the cache's own labels, if it has any, through the same index (labels_cached)
+        cb = self._cached = _cached('HeadEvalStep', X, Xatt)
+        if cb is not None:
+            if int(frames) != 1 or temporal is not None or M != 1:
+                raise ApaError('HeadEvalStep: a CachedBatch feeds the flat class-agnostic step (no clips, no per-class maps)')
+            use_cached = labels is None and cb.cache.labels is not None and scores == 'softmax'
+            self._fc = cb.descriptor(labels_cached=use_cached)
         B, code, self._clip, self.pooled, self.tatt, keep = _bind_eval_clip('HeadEvalStep', N, K, frames, temporal,
                                                                           scores, labels, dev)
+        if cb is not None and use_cached:
+            labels = cb.cache.labels
         self.logits = torch.empty((N, K), dtype=torch.float32, device=dev)
         self.att = torch.empty((N, P, M), dtype=torch.float32, device=dev)
         self.zsave = torch.empty((N, C) if M == 1 else (N, P, K), dtype=torch.float32, device=dev)
@@ -1912,10 +2152,23 @@ class HeadEvalStep:
             self._keep += keep
             self._fn, self._name = self.lib.apa_attn_head_eval_step_clips, 'apa_attn_head_eval_step_clips'
             self._pre = (None if self._clip is None else ctypes.addressof(self._clip), code)
+        if cb is not None:      # (the descriptor, clip = NULL, the kind, then the same arguments)
+            self._fn, self._name = self.lib.apa_attn_head_eval_step_cached, 'apa_attn_head_eval_step_cached'
+            self._pre = (ctypes.addressof(self._fc), None, code)
 
-    def rebind(self, X) -> None:
+    def rebind(self, X=None, index=None) -> None:
         """Point the bound step at another feature map of the same shape / dtype (attention from the map itself:
-        the step was built with `Xatt is X`)."""
+        the step was built with `Xatt is X`).  `index` (a step on a CachedBatch): another batch of the same cache, an
+        int32 tensor of the same length on the cache's device."""
+        if index is not None:
+            if self._cached is None:
+                raise ApaError('HeadEvalStep.rebind: index= needs a step bound to a CachedBatch')
+            self._index = _index_tensor('HeadEvalStep.rebind', index, self._cached.cache.device, self._cached.shape[0])
+            self._fc.index = self._index.data_ptr()
+        if X is None:
+            return
+        if self._cached is not None:
+            raise ApaError('HeadEvalStep.rebind: a step on a CachedBatch is re-bound with index=')
         if self._keep[1] is not self._keep[0]:
             raise ApaError('HeadEvalStep.rebind: a step with a separate attention input is re-built, not re-bound')
         if X.shape != self._keep[0].shape or X.dtype != self._keep[0].dtype:

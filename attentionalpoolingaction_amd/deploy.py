@@ -1063,6 +1063,7 @@ class FusedHeadStep:
         self._anchor = torch.zeros((), requires_grad=True)
         self._want_dx = True
         self._fp8 = False
+        self._cb = False
         self.probe_events = None
 
     @staticmethod
@@ -1291,7 +1292,7 @@ class FusedHeadStep:
     def _run(self, last_conv, labels_action, labels_pose, pose_valid):
         head = self.head
         n, c = last_conv.shape[0], last_conv.shape[-1]
-        X = last_conv.flat() if self._fp8 else last_conv.detach().contiguous().view(n, -1, c)
+        X = last_conv.flat() if (self._fp8 or self._cb) else last_conv.detach().contiguous().view(n, -1, c)
         if self.pose_form:
             J = self.params['pose_w2'].shape[1]
             labels_pose = labels_pose.contiguous().float().view(n, -1, J)
@@ -1311,10 +1312,14 @@ class FusedHeadStep:
             self._optimizer.check_fresh()                # weights written behind the optimiser's back?
             self._check_frozen_fresh()
         # a bound step reads the weights through the pointers it was bound to: a new storage binds a new step
+        # (a CachedBatch: one bound step per cache and label source; only the index, and per-batch labels, are re-bound)
         key = (tuple(X.shape), frames, X.dtype, self._preact, self._want_dx,
-               tuple(p.data_ptr() for p in self.params.values()))
+               tuple(p.data_ptr() for p in self.params.values())) + \
+              ((id(X.cache), labels_action is None) if self._cb else ())
         st, cached = self._select(key, X, labels_action, labels_pose, pose_valid, frames)
-        if cached and self.pose_form:
+        if cached and self._cb:
+            st.rebind(index=X.index, labels=labels_action, offset=head._step)
+        elif cached and self.pose_form:
             st.rebind(X=X, labels=labels_action, pose_labels=labels_pose, pose_valid=pose_valid, offset=head._step)
         elif cached:
             st.rebind(X=X, labels=labels_action, offset=head._step)
@@ -1335,19 +1340,27 @@ class FusedHeadStep:
         return total
 
     def __call__(self, images, labels_action, labels_pose=None, pose_valid=None):
-        from .custom_ops.custom_ops_factory import Fp8Features
+        """`images`: the input batch; an Fp8Features batch (a cached conv5 map in FP8); or a CachedBatch (N images of a
+        resident FeatureCache named by index, any of its dtypes: `labels_action=None` reads the cache's own labels
+        through the index).  The two cached forms are frozen by construction (frozen_features=True) and are served
+        under the head conditions of fp8_unsupported_reason."""
+        from .custom_ops.custom_ops_factory import CachedBatch, Fp8Features
         self._frames = 1
+        self._cb = isinstance(images, CachedBatch)
         self._fp8 = isinstance(images, Fp8Features)
-        if self._fp8:       # a cached conv5 map in FP8: frozen by construction, no backbone in front of it
+        if self._fp8 or self._cb:   # a cached conv5 map: frozen by construction, no backbone in front of it
+            what = 'an Fp8Features batch' if self._fp8 else 'a CachedBatch'
             why = self.fp8_unsupported_reason(self.head, self.network_fn)
             if not why and not self.frozen_features:
                 why = 'frozen_features=False (a cache has no gradient: build the step with frozen_features=True)'
+            if not why and self._cb and self.cfg.TRAIN.LOSS_FN_ACTION != 'softmax-xentropy':
+                why = 'LOSS_FN_ACTION %r (the cached step takes the softmax cross-entropy)' % self.cfg.TRAIN.LOSS_FN_ACTION
             if why:
-                raise ValueError('FusedHeadStep: an Fp8Features batch is not served with ' + why)
+                raise ValueError('FusedHeadStep: %s is not served with %s' % (what, why))
         elif images.dim() == 5:                                 # nets_factory.py:121-125: frames fold into the batch
             self._frames = int(images.shape[1])
             images = images.reshape(-1, *images.shape[2:])
-        last_conv, self._preact = (images, False) if self._fp8 else self.network_fn.features(images)
+        last_conv, self._preact = (images, False) if (self._fp8 or self._cb) else self.network_fn.features(images)
         if last_conv.dim() != 4:
             raise ValueError('FusedHeadStep: [N,H,W,C] (or [B,F,H,W,C]; an Fp8Features batch: [N,H,W,C]) feature maps '
                              'expected')
@@ -1361,7 +1374,7 @@ class FusedHeadStep:
         if self.cfg.TRAIN.LOSS_FN_ACTION != 'softmax-xentropy':     # multi-hot labels of any dtype -> float32, once
             labels_action = labels_action.to(torch.float32).contiguous()
         # decided per step: a conv5 map that needs no gradient (frozen / precomputed features) gets none
-        self._want_dx = not self._fp8 and (bool(last_conv.requires_grad) or not self.frozen_features)
+        self._want_dx = not (self._fp8 or self._cb) and (bool(last_conv.requires_grad) or not self.frozen_features)
         # one autograd node either way: with a differentiated backbone it hands conv5's gradient upstream, without
         # one (head-only training) it still scales the bucket by whatever coefficient `total` is given
         total = _FusedHeadFunction.apply(last_conv, self._anchor, self, labels_action, labels_pose, pose_valid)
@@ -1462,13 +1475,15 @@ class FusedHeadEval:
         return [getattr(h, n) for n in names]
 
     def __call__(self, images, labels_action=None, want_pose_logits: bool = False):
-        from .custom_ops.custom_ops_factory import Fp8Features
+        from .custom_ops.custom_ops_factory import CachedBatch, Fp8Features
         frames = 1
-        fp8 = isinstance(images, Fp8Features)
-        if fp8:             # a cached conv5 map in FP8 (see FusedHeadStep.fp8_unsupported_reason)
+        cb = isinstance(images, CachedBatch)
+        fp8 = isinstance(images, Fp8Features) or cb
+        if fp8:             # a cached conv5 map: FP8, or a FeatureCache read by index (see FusedHeadStep.fp8_unsupported_reason)
             why = FusedHeadStep.fp8_unsupported_reason(self.head, self.network_fn)
             if why:
-                raise ValueError('FusedHeadEval: an Fp8Features batch is not served with ' + why)
+                raise ValueError('FusedHeadEval: %s is not served with %s' % (
+                    'a CachedBatch' if cb else 'an Fp8Features batch', why))
         elif images.dim() == 5:                                 # nets_factory.py:121-125
             frames = images.shape[1]
             images = images.reshape(-1, *images.shape[2:])
@@ -1490,10 +1505,13 @@ class FusedHeadEval:
                 temporal._bias_initialised = True
             tw, tb = temporal['weights'].data.reshape(-1).contiguous(), temporal['biases'].data
         key = (tuple(X.shape), X.dtype, self._preact, want_pl, tuple(p.data_ptr() for p in self._params()), frames,
-               None if tw is None else tw.data_ptr(), None if tb is None else tb.data_ptr())
+               None if tw is None else tw.data_ptr(), None if tb is None else tb.data_ptr(),
+               id(X.cache) if cb else None)
         st = self._steps.pop(key, None)
         if st is None:
             st = self._bind(X, want_pl, frames, None if tw is None else (tw, tb))
+        elif cb:                                                # the same cache: only the index is re-bound
+            st.rebind(index=X.index)
         else:
             st.rebind(X=X) if self.pose_form else st.rebind(X)
         self._steps[key] = st                                   # most recent last

@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define APA_VERSION 309 /* major*10000 + minor*100 + patch */
+#define APA_VERSION 310 /* major*10000 + minor*100 + patch */
 
 typedef enum apa_status {
   APA_OK = 0,
@@ -841,6 +841,65 @@ int apa_attn_pool_bwd_cat(const apa_concat_feat* cat, const apa_hooks* hooks, co
                           float* dbt, void* ws, size_t ws_bytes, int N, int P, int C, int Ca, int K,
                           int M, unsigned flags, float keep_prob, uint64_t seed, uint64_t offset,
                           int dtype, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * A resident feature cache read by image index.  A frozen-features run reads one tensor epoch after epoch, the cached
+ * conv5 map; with the *_cached entry points X addresses the WHOLE cache -- T = cache_images maps [T,P,C] in fp32, bf16
+ * or FP8 (APA_DTYPE_FP8_E4M3: the one allocation of apa_fp8_features_bytes(T, P, C) bytes, scales behind all T
+ * images' codes) -- and image n of the batch is cache image index[n]: a shuffled mini-batch, or a slice of the cache,
+ * without a gathered copy.  Only the feature rows (FP8: and the scale) are fetched through the index; every output,
+ * the workspace and the dropout mask (apa_dropout_mask over the flat [N,P,C] index of the BATCH) keep the batch
+ * position, so a cached call is bit-identical to the plain call on a gathered copy of the same images, with the same
+ * launches.  An index entry outside [0, T) is clamped into the cache -- nothing outside it is ever addressed -- and,
+ * with `status` given, counted there by the forward pass (the caller zeroes the word; a training step counts once).
+ * labels_cached (the steps): `labels` is [T] and image n's label is labels[index[n]], read by the forward pooling
+ * pass; else `labels` is [N] as in the plain steps.
+ * Served: the class-agnostic head (M == 1) with attention from the map itself (Xatt == X), identity or ReLU attention,
+ * evaluation or training on frozen features.  Refused before anything is queued --
+ *   APA_ERR_INVALID_ARG: a NULL descriptor or index, cache_images < 1, a non-NULL dX, a backward call or a training
+ *                        step without APA_FLAG_FROZEN_INPUT;
+ *   APA_ERR_UNSUPPORTED: M != 1, a separate attention input, APA_FLAG_SOFTMAX_ATT, APA_FLAG_RELU_INPUT,
+ *                        APA_FLAG_RNG_EXTERNAL, the TopDownAttention dump, clips (eval: clip must be NULL);
+ * then whatever the plain entry point refuses (for FP8: what the FP8 arm refuses).  Not built: clips, the sigmoid
+ * training losses, rank > 1, per-class maps, the concatenated pose channels, the pose head and the cfg 003 steps.
+ * Workspace: apa_attn_pool_workspace_bytes of the BATCH shape.  The signatures are those of apa_attn_pool_fwd_ex /
+ * apa_attn_pool_bwd_ex / apa_attn_head_train_step_ex / apa_attn_head_eval_step_clips with the descriptor in front.
+ */
+typedef struct apa_feature_cache {
+  const int32_t* index;   /* device, [N], 4-byte aligned: batch image n is cache image index[n] */
+  int cache_images;       /* T: images behind X (FP8: the scales sit at the offset of a T-image buffer) */
+  int labels_cached;      /* 1: labels is [T], read through index; 0: labels is [N] as ever */
+  int32_t* status;        /* device, nullable: number of index entries outside [0, T), which were clamped */
+} apa_feature_cache;
+
+int apa_attn_pool_fwd_cached(const apa_feature_cache* cache, const apa_hooks* hooks, const void* X, const void* Xatt,
+                             const float* Wa, const float* ba, const float* Wt, const float* bt, float* logits,
+                             float* att, float* zsave, float* abar, void* topdown, void* ws, size_t ws_bytes, int N,
+                             int P, int C, int Ca, int K, int M, unsigned flags, float keep_prob, uint64_t seed,
+                             uint64_t offset, int dtype, void* stream);
+int apa_attn_pool_bwd_cached(const apa_feature_cache* cache, const apa_hooks* hooks, const void* X, const void* Xatt,
+                             const float* Wa, const float* ba, const float* Wt, const float* bt, const float* att,
+                             const float* zsave, const float* abar, const float* G, void* dX, void* dXatt, float* dWa,
+                             float* dba, float* dWt, float* dbt, void* ws, size_t ws_bytes, int N, int P, int C, int Ca,
+                             int K, int M, unsigned flags, float keep_prob, uint64_t seed, uint64_t offset, int dtype,
+                             void* stream);
+int apa_attn_head_train_step_cached(const apa_feature_cache* cache, const apa_hooks* hooks, const void* X,
+                                    const void* Xatt, const float* Wa, const float* ba, const float* Wt,
+                                    const float* bt, const int64_t* labels, float loss_wt, float grad_scale,
+                                    float* logits, float* att, float* zsave, float* abar, float* loss, float* G,
+                                    void* dX, void* dXatt, float* dWa, float* dba, float* dWt, float* dbt, void* ws,
+                                    size_t ws_bytes, int N, int P, int C, int Ca, int K, int M, unsigned flags,
+                                    float keep_prob, uint64_t seed, uint64_t offset, int dtype, void* stream);
+int apa_attn_head_eval_step_cached(const apa_feature_cache* cache, const apa_clip_pool* clip /* NULL */,
+                                   int scores_kind, const void* X, const void* Xatt, const float* Wa, const float* ba,
+                                   const float* Wt, const float* bt, const int64_t* labels, float* logits, float* att,
+                                   float* zsave, float* abar, float* loss, float* probs, int64_t* pred, void* ws,
+                                   size_t ws_bytes, int N, int P, int C, int Ca, int K, int M, unsigned flags,
+                                   int dtype, void* stream);
+/* apa_quantize_features_fp8 into place: the n images of src become images [first, first + n) of the T-image FP8 cache
+ * at `cache` (same rule, same kernel; status int32 [n]).  Slots outside the cache: APA_ERR_INVALID_ARG. */
+int apa_quantize_features_fp8_at(const void* src, int src_dtype, void* cache, int cache_images, int first,
+                                 int32_t* status, int n, int P, int C, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * NET.USE_POSE_PRELOGITS_BASED_ATTENTION_RANK = R > 1 (nets_factory.py:247-328) with ONE bottom-up map: R attention

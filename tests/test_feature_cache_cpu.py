@@ -1,0 +1,301 @@
+"""The resident feature cache read by image index, without a GPU: the header, the ctypes table and the library agree on
+the new names; every refusal of the *_cached entry points is made, by name, before any HIP call; FeatureCache /
+CachedBatch on the CPU (layout, write, gather, epoch); the deploy layer's refusals answer what they answered."""
+import ctypes
+import os
+import re
+
+import pytest
+import torch
+
+from attentionalpoolingaction_amd.custom_ops import custom_ops_factory as cof
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+INVALID, UNSUPPORTED, WORKSPACE = -1, -2, -3
+F8 = torch.float8_e4m3fn
+NEW = ('apa_attn_pool_fwd_cached', 'apa_attn_pool_bwd_cached', 'apa_attn_head_train_step_cached',
+       'apa_attn_head_eval_step_cached', 'apa_quantize_features_fp8_at')
+
+
+# ------------------------------------------------------------------------------------------ ABI
+def test_header_table_and_library_agree_on_the_new_names():
+    header = open(os.path.join(ROOT, 'include', 'apa.h')).read()
+    bare = re.sub(r'/\*.*?\*/', '', header, flags=re.S)
+    declared = set(re.findall(r'\b(apa_[a-z0-9_]+)\s*\(', bare))
+    lib = cof.load_library()
+    for name in NEW:
+        assert name in declared and name in cof.exported_symbols() and hasattr(lib, name), name
+    assert lib.apa_version() >= 310
+    # the descriptor: field order and types are the ABI
+    m = re.search(r'typedef struct apa_feature_cache \{(.*?)\} apa_feature_cache;', bare, flags=re.S)
+    fields = [f.strip() for f in m.group(1).split(';') if f.strip()]
+    assert fields == ['const int32_t* index', 'int cache_images', 'int labels_cached', 'int32_t* status']
+    assert [n for n, _ in cof.ApaFeatureCache._fields_] == ['index', 'cache_images', 'labels_cached', 'status']
+    assert ctypes.sizeof(cof.ApaFeatureCache) == 24 and cof.ApaFeatureCache.status.offset == 16
+    # the cached signatures are the plain ones with the descriptor in front
+    sig = cof._SIGNATURES
+    for cached, plain in (('apa_attn_pool_fwd_cached', 'apa_attn_pool_fwd_ex'),
+                          ('apa_attn_pool_bwd_cached', 'apa_attn_pool_bwd_ex'),
+                          ('apa_attn_head_train_step_cached', 'apa_attn_head_train_step_ex'),
+                          ('apa_attn_head_eval_step_cached', 'apa_attn_head_eval_step_clips')):
+        assert sig[cached] == (sig[plain][0], [ctypes.c_void_p] + list(sig[plain][1])), cached
+
+
+# ------------------------------------------------------------------------------------------ refusals
+FAKE = 0x10000                       # a 16-byte aligned non-null address: nothing is dereferenced
+FROZEN = cof.APA_FLAG_FROZEN_INPUT
+
+
+def _desc(index=FAKE, T=7, labels_cached=0, status=None):
+    return cof.ApaFeatureCache(index, T, labels_cached, status)
+
+
+def _calls(lib):
+    """the four entry points on dummy pointers; `cache`: an ApaFeatureCache, or None for a NULL descriptor"""
+    def ptr(cache):
+        return None if cache is None else ctypes.addressof(cache)
+
+    def fwd(cache, dtype=0, N=2, P=9, C=32, K=8, M=1, flags=0, xatt=FAKE, topdown=None, ws_bytes=0, dX=None):
+        rc = lib.apa_attn_pool_fwd_cached(ptr(cache), None, FAKE, xatt, FAKE, FAKE, FAKE, FAKE, FAKE, FAKE, FAKE, FAKE,
+                                          topdown, FAKE, ws_bytes, N, P, C, C, K, M, flags, 1.0, 0, 0, dtype, None)
+        return rc, lib.apa_last_error()
+
+    def bwd(cache, dtype=0, N=2, P=9, C=32, K=8, M=1, flags=FROZEN, xatt=FAKE, dX=None, ws_bytes=0, topdown=None):
+        rc = lib.apa_attn_pool_bwd_cached(ptr(cache), None, FAKE, xatt, FAKE, FAKE, FAKE, FAKE, FAKE, FAKE, FAKE, FAKE,
+                                          dX, None if xatt == FAKE else FAKE, FAKE, FAKE, FAKE, FAKE, FAKE, ws_bytes,
+                                          N, P, C, C, K, M, flags, 1.0, 0, 0, dtype, None)
+        return rc, lib.apa_last_error()
+
+    def step(cache, dtype=0, N=2, P=9, C=32, K=8, M=1, flags=FROZEN, xatt=FAKE, dX=None, ws_bytes=0, topdown=None):
+        rc = lib.apa_attn_head_train_step_cached(ptr(cache), None, FAKE, xatt, FAKE, FAKE, FAKE, FAKE, FAKE, 1.0, 1.0,
+                                                 FAKE, FAKE, FAKE, FAKE, FAKE, FAKE, dX,
+                                                 None if xatt == FAKE else FAKE, FAKE, FAKE, FAKE, FAKE, FAKE, ws_bytes,
+                                                 N, P, C, C, K, M, flags, 1.0, 0, 0, dtype, None)
+        return rc, lib.apa_last_error()
+
+    def ev(cache, dtype=0, N=2, P=9, C=32, K=8, M=1, flags=0, xatt=FAKE, ws_bytes=0, clip=None, kind=0, dX=None,
+           topdown=None):
+        rc = lib.apa_attn_head_eval_step_cached(ptr(cache), clip, kind, FAKE, xatt, FAKE, FAKE, FAKE, FAKE, None, FAKE,
+                                                FAKE, FAKE, FAKE, None, FAKE, FAKE, FAKE, ws_bytes, N, P, C, C, K, M,
+                                                flags, dtype, None)
+        return rc, lib.apa_last_error()
+    return fwd, bwd, step, ev
+
+
+@pytest.mark.parametrize('dtype', [0, 1, 2], ids=['f32', 'bf16', 'fp8'])
+def test_cached_refusals_name_their_reason_before_any_hip_call(dtype):
+    """(dummy pointers: a call that got past its checks would fault -- an accepted call stops at the workspace check,
+    still in front of the first launch)"""
+    lib = cof.load_library()
+    fwd, bwd, step, ev = _calls(lib)
+    ok = _desc()
+    other = FAKE + 0x1000
+    for call in (fwd, bwd, step, ev):
+        name = call.__name__
+        # everything in order: the next refusal is the workspace's, nothing was launched
+        rc, err = call(ok, dtype)
+        assert rc == WORKSPACE and b'workspace' in err, (name, err)
+        # APA_ERR_INVALID_ARG: the descriptor
+        for cache, word in ((None, b'null apa_feature_cache'), (_desc(index=None), b'null apa_feature_cache'),
+                            (_desc(T=0), b'cache_images=0'), (_desc(T=-3), b'cache_images=-3'),
+                            (_desc(index=FAKE + 2), b'4-byte aligned')):
+            rc, err = call(cache, dtype)
+            assert rc == INVALID and word in err and b'_cached' in err, (name, word, rc, err)
+        # APA_ERR_UNSUPPORTED: forms a cache cannot have
+        for kw, word in ((dict(M=8), b'per-class maps'), (dict(xatt=other), b'separate attention input'),
+                         (dict(flags=cof.APA_FLAG_SOFTMAX_ATT), b'APA_FLAG_SOFTMAX_ATT'),
+                         (dict(flags=cof.APA_FLAG_RELU_INPUT), b'APA_FLAG_RELU_INPUT'),
+                         (dict(flags=cof.APA_FLAG_RNG_EXTERNAL | cof.APA_FLAG_TRAIN), b'APA_FLAG_RNG_EXTERNAL')):
+            if 'flags' in kw and call in (bwd, step):
+                kw = dict(flags=kw['flags'] | FROZEN)
+            rc, err = call(ok, dtype, **kw)
+            assert rc == UNSUPPORTED and word in err and b'feature cache' in err, (name, kw, rc, err)
+    # a cache has no gradient: a dX, or a backward call / a training step without the flag
+    for call in (bwd, step):
+        rc, err = call(ok, dtype, dX=FAKE)
+        assert rc == INVALID and b'dX must be NULL' in err, err
+        rc, err = call(ok, dtype, flags=0)
+        assert rc == INVALID and b'APA_FLAG_FROZEN_INPUT' in err, err
+    rc, err = fwd(ok, dtype, topdown=FAKE)
+    assert rc == UNSUPPORTED and b'TopDownAttention' in err
+    # clips are not built: the evaluation step takes a NULL clip only; the scores kind is checked as ever
+    clip = cof.ApaClipPool()
+    clip.frames = 1
+    rc, err = ev(ok, dtype, clip=ctypes.addressof(clip))
+    assert rc == UNSUPPORTED and b'clips' in err
+    rc, err = ev(ok, dtype, kind=5)
+    assert rc == INVALID and b'scores kind' in err
+    rc, err = ev(ok, dtype, kind=cof.APA_SCORES_SIGMOID)            # sigmoid scores are served: on to the workspace
+    assert rc == WORKSPACE, err
+    # the dimensions are checked before anything is derived from them
+    rc, err = step(ok, dtype, N=0)
+    assert rc == INVALID and b'non-positive' in err
+    # labels through the index: accepted, and still in front of the first launch
+    rc, err = step(_desc(labels_cached=1, status=FAKE), dtype)
+    assert rc == WORKSPACE, err
+
+
+def test_fp8_cache_keeps_the_fp8_arms_own_limits():
+    lib = cof.load_library()
+    fwd, bwd, step, ev = _calls(lib)
+    for call in (fwd, bwd, step, ev):
+        rc, err = call(_desc(), 2, C=24)
+        assert rc == UNSUPPORTED and b'multiple of 16' in err and b'APA_DTYPE_FP8_E4M3' in err, err
+    # unknown dtype
+    rc, err = fwd(_desc(), 3)
+    assert rc == INVALID and b'unknown dtype 3' in err
+
+
+def test_quantize_at_refusals():
+    q = cof.load_library().apa_quantize_features_fp8_at
+    err = cof.load_library().apa_last_error
+    assert q(FAKE, 0, FAKE, 7, 5, FAKE, 3, 9, 32, None) == INVALID and b'do not lie inside a cache of 7' in err()
+    assert q(FAKE, 0, FAKE, 7, -1, FAKE, 3, 9, 32, None) == INVALID and b'inside a cache' in err()
+    assert q(FAKE, 0, FAKE, 0, 0, FAKE, 1, 9, 32, None) == INVALID
+    assert q(FAKE, 2, FAKE, 7, 0, FAKE, 3, 9, 32, None) == INVALID and b'unknown dtype 2' in err()
+    assert q(FAKE, 0, FAKE, 7, 0, FAKE, 3, 9, 24, None) == UNSUPPORTED and b'multiple of 16' in err()
+    assert q(None, 0, FAKE, 7, 0, FAKE, 3, 9, 32, None) == INVALID
+    assert q(FAKE, 0, FAKE, 7, 0, None, 3, 9, 32, None) == INVALID and b'status' in err()
+    assert q(FAKE, 0, FAKE, 7, 0, FAKE, 0, 9, 32, None) == INVALID
+
+
+# ------------------------------------------------------------------------------------------ FeatureCache on the CPU
+def _images(T=7, H=2, W=3, C=32, seed=3):
+    g = torch.Generator().manual_seed(seed)
+    X = torch.relu(torch.randn(T, H, W, C, generator=g)) * torch.tensor([1.0, 37.0, 1e-3] * T)[:T].view(T, 1, 1, 1)
+    X[2] = 0.0                                  # an all-zero image
+    X[5, 1, 2, 7] = float('inf')                # non-finite: reported, not encoded
+    return X
+
+
+def test_fp8_cache_layout_is_fp8features_of_all_images():
+    T, H, W, C = 7, 2, 3, 32
+    cache = cof.FeatureCache.empty((T, H, W, C), F8, 'cpu')
+    f = cache.features
+    assert isinstance(f, cof.Fp8Features) and cache.fp8 and cache.T == T and cache.shape == (T, H, W, C)
+    assert f.buffer.numel() == cof.fp8_features_bytes(T, H * W, C) == cof.fp8_scale_offset(T, H * W, C) + 4 * T
+    assert f.scale.data_ptr() == f.data_ptr() + cof.fp8_scale_offset(T, H * W, C)
+    assert cache.status.dtype == torch.int32 and cache.status.numel() == 1
+    for dt in (torch.float32, torch.bfloat16):
+        c = cof.FeatureCache.empty((T, H, W, C), dt, 'cpu')
+        assert not c.fp8 and c.features.dtype == dt and tuple(c.features.shape) == (T, H, W, C)
+    with pytest.raises(cof.ApaError):
+        cof.FeatureCache(torch.zeros(T, H, W, C, dtype=torch.float64))
+    with pytest.raises(cof.ApaError):
+        cof.FeatureCache(torch.zeros(T, H, W, C), labels=torch.zeros(T - 1, dtype=torch.int64))
+
+
+@pytest.mark.parametrize('src', [torch.float32, torch.bfloat16], ids=['f32', 'bf16'])
+def test_write_in_two_chunks_is_quantize_features_of_the_whole(src):
+    X = _images().to(src)
+    whole, status = cof.quantize_features(X)
+    cache = cof.FeatureCache.empty(X.shape, F8, 'cpu')
+    s1 = cache.write(3, X[3:])                  # out of order: the second chunk first
+    s0 = cache.write(0, X[:3])
+    assert torch.equal(cache.features.buffer, whole.buffer)
+    assert torch.equal(torch.cat([s0, s1]), status) and status.tolist() == [0, 0, 0, 0, 0, 1, 0]
+    # a cast cache
+    for dt in (torch.float32, torch.bfloat16):
+        c = cof.FeatureCache.empty(X.shape, dt, 'cpu')
+        assert c.write(0, X[:4]).tolist() == [0] * 4 and c.write(4, X[4:]).tolist() == [0] * 3
+        assert torch.equal(c.features[:5], X[:5].to(dt)) and torch.equal(c.features[6], X[6].to(dt))
+    with pytest.raises(cof.ApaError):
+        cache.write(5, X[:3])                   # past the end
+    with pytest.raises(cof.ApaError):
+        cache.write(0, X[:3, :, :, :16])        # another image shape
+
+
+def test_gather_and_select():
+    X = _images()
+    X[5] = X[4] * 0.5
+    whole, _ = cof.quantize_features(X)
+    labels = torch.arange(7, dtype=torch.int64) * 3
+    cache = cof.FeatureCache(whole, labels)
+    idx = [6, 0, 6, 3, 1]
+    g = cache.gather(idx)
+    want = cof.Fp8Features.from_parts(whole.codes[idx], whole.scale[idx])
+    assert isinstance(g, cof.Fp8Features) and g.shape == (5, 2, 3, 32) and torch.equal(g.buffer, want.buffer)
+    plain = cof.FeatureCache(X.clone())
+    assert torch.equal(plain.gather(torch.tensor(idx)), X[idx])
+    b = cache.select(idx)
+    assert isinstance(b, cof.CachedBatch) and b.cache is cache and b.shape == (5, 2, 3, 32) and b.dim() == 4
+    assert b.index.dtype == torch.int32 and b.index.tolist() == idx and b.numel() == 5 * 2 * 3 * 32
+    assert b.data_ptr() == whole.data_ptr() and cof._feat_dtype(b) == cof.APA_DTYPE_FP8_E4M3
+    assert cof._feat_dtype(plain.select(idx)) == cof.APA_DTYPE_F32
+    i32 = torch.tensor(idx, dtype=torch.int32)
+    assert cache.select(i32).index.data_ptr() == i32.data_ptr()         # an int32 index is used as it is
+    with pytest.raises(cof.ApaError):
+        cache.select([])
+    with pytest.raises(cof.ApaError):
+        cache.select(torch.tensor([0.5, 1.0]))
+    # no CPU fallback, and a cache is frozen and supplies its own attention input
+    w = torch.zeros(32, 1)
+    with pytest.raises(cof.ApaError, match='GPU memory'):
+        cof.attn_pool_fwd(b, b, w, torch.zeros(1), torch.zeros(32, 3), torch.zeros(3))
+    with pytest.raises(cof.ApaError, match='frozen'):
+        cof.attn_pool_bwd(b, b, w, w, w, w, w, w, w, w)                 # want_dx defaults to True
+    with pytest.raises(cof.ApaError, match='same object'):
+        cof.attn_pool_fwd(b, cache.select(idx), w, torch.zeros(1), torch.zeros(32, 3), torch.zeros(3))
+
+
+@pytest.mark.parametrize('T,bs', [(7, 3), (8, 4), (5, 5), (3, 7)])
+def test_epoch(T, bs):
+    cache = cof.FeatureCache(torch.zeros(T, 1, 1, 16))
+    for drop_last in (True, False):
+        batches = list(cache.epoch(bs, seed=11, drop_last=drop_last))
+        again = list(cache.epoch(bs, seed=11, drop_last=drop_last))
+        assert all(b.dtype == torch.int32 and b.dim() == 1 for b in batches)
+        assert len(batches) == len(again) and all(torch.equal(a, b) for a, b in zip(batches, again))   # by seed
+        sizes = [b.numel() for b in batches]
+        if drop_last:
+            assert sizes == [bs] * (T // bs)
+        else:
+            assert sizes == [bs] * (T // bs) + ([T % bs] if T % bs else [])
+        ids = torch.cat(batches).tolist() if batches else []
+        assert len(set(ids)) == len(ids) and set(ids) <= set(range(T))                  # no id twice
+        if not drop_last:
+            assert sorted(ids) == list(range(T))                                        # every id exactly once
+        # the batches are views of one permutation
+        if len(batches) > 1:
+            assert batches[1].data_ptr() == batches[0].data_ptr() + 4 * bs
+    if T >= 7:
+        a = torch.cat(list(cache.epoch(bs, seed=11, drop_last=False)))
+        b = torch.cat(list(cache.epoch(bs, seed=12, drop_last=False)))
+        assert not torch.equal(a, b)                                                    # another seed, another order
+    plain = torch.cat(list(cache.epoch(bs, seed=11, shuffle=False, drop_last=False)))
+    assert plain.tolist() == list(range(T))
+    with pytest.raises(cof.ApaError):
+        list(cache.epoch(0, seed=1))
+
+
+# ------------------------------------------------------------------------------------------ deploy
+def test_deploy_refusals_answer_what_they_answered():
+    """FusedHeadStep.unsupported_reason / fp8_unsupported_reason are about the head, not the batch: a CachedBatch is
+    served under the conditions an Fp8Features batch is, and neither function changed its answers."""
+    from attentionalpoolingaction_amd import config as apa_config, deploy
+    from tests import _ref_fixture as rf
+    P = 'USE_POSE_PRELOGITS_BASED_ATTENTION'
+    try:
+        fx = rf.HeadFixture(os.path.join(rf.GOLD, 'ref_head_cfg002_train_c2048_libmask.npz'))
+        network_fn, cfg = rf.build_head(fx, device='cpu')
+        head = network_fn.head
+        assert deploy.FusedHeadStep.unsupported_reason(head, cfg, network_fn) == ''
+        assert deploy.FusedHeadStep.fp8_unsupported_reason(head, network_fn) == ''
+        fx3 = rf.HeadFixture(os.path.join(rf.GOLD, 'ref_head_cfg003_train.npz'))
+        net3, cfg3 = rf.build_head(fx3, device='cpu', in_channels=2048)
+        assert deploy.FusedHeadStep.unsupported_reason(net3.head, cfg3, net3) == ''
+        assert 'cfg 003' in deploy.FusedHeadStep.fp8_unsupported_reason(net3.head, net3)
+        # a CachedBatch on a CPU cache reaches the head conditions first (nothing touches a GPU)
+        cache = cof.FeatureCache(torch.zeros(4, 3, 3, 2048), torch.zeros(4, dtype=torch.int64))
+        batch = cache.select([1, 0])
+        with pytest.raises(ValueError, match='a CachedBatch is not served with attention from pose_pre_logits'):
+            deploy.FusedHeadStep(net3, cfg3, frozen_features=True)(batch, None, None, None)
+        with pytest.raises(ValueError, match='frozen_features=False'):
+            deploy.FusedHeadStep(network_fn, cfg, frozen_features=False)(batch, None)
+        fxe = rf.HeadFixture(os.path.join(rf.GOLD, 'ref_head_cfg003_eval.npz'))
+        net3e, cfg3e = rf.build_head(fxe, device='cpu', in_channels=2048)
+        assert deploy.FusedHeadEval.unsupported_reason(net3e.head, cfg3e, net3e) == ''
+        with pytest.raises(ValueError, match='a CachedBatch is not served with attention from pose_pre_logits'):
+            deploy.FusedHeadEval(net3e, cfg3e)(batch)
+    finally:
+        apa_config.reset_cfg()

@@ -31,6 +31,12 @@ headline stays the cfg 002 training workload); run this file directly for one wo
             one-call training step / the one-call evaluation step, alternating in one process, medians of five and
             their spread, the streaming kernels by HIP events with their bytes per second; --batch 512 for the
             bandwidth-bound size
+  cached002_fp8 / cached002_bf16
+            cfg 002 frozen one-call training step from a RESIDENT feature cache (--cache-images, at least 2048 maps
+            14x14x2048, FP8 E4M3 or bf16; --batch 512 for the bandwidth-bound size), three variants alternating in one
+            process, medians of five and their spread: (a) the gathered step (apa_attn_head_train_step_cached) with a
+            fresh shuffled index per step, (b) gather + rebind + the plain step -- the loop without the gathered
+            kernels --, (c) the plain step on one fixed contiguous batch.
   frozen002 / frozen003 / frozen_perclass
             the one-call training steps on FROZEN features (APA_FLAG_FROZEN_INPUT: no dX is computed or stored) against
             the same step as it runs today, at the BASELINE shapes (32 x 14x14x2048; cfg 002 fp32 K = 393, cfg 003 bf16
@@ -1167,6 +1173,83 @@ def run_fp8(cof, dev, args, which):
     return out
 
 
+def build_cached(cof, dev, fp8, N=512, H=14, T=2048):
+    """cfg 002 frozen one-call training step (dropout keep 0.2, K = 393) from a RESIDENT cache of T 14x14x2048 maps (FP8
+    E4M3 or bf16) with its labels, three ways: (a) the gathered step on cache.select(index), a fresh shuffled index
+    per step (epoch() views, re-bound); (b) today's loop: cache.gather(index) + labels[index] + rebind + the plain
+    step; (c) the plain step on one fixed contiguous batch of the cache.  -> ({name: step}, info)"""
+    C, P, K = 2048, H * H, 393
+    T = max(int(T), 4 * N)
+    g = torch.Generator().manual_seed(42)
+    labels = torch.randint(0, K, (T,), generator=g).to(dev)
+    cache = cof.FeatureCache.empty((T, H, H, C), torch.float8_e4m3fn if fp8 else torch.bfloat16, dev, labels=labels)
+    for first in range(0, T, 256):
+        n = min(256, T - first)
+        status = cache.write(first, _features(n, P, C, torch.bfloat16, dev, seed=42 + first).view(n, H, H, C))
+        assert int(status.sum()) == 0
+    Wa = (torch.randn(C, 1, generator=g) / C ** 0.5).to(dev); ba = torch.zeros(1, device=dev)
+    Wt = (torch.randn(C, K, generator=g) / C ** 0.5).to(dev); bt = torch.zeros(K, device=dev)
+    pg = tuple(torch.empty_like(t) for t in (Wa, ba, Wt, bt))
+    ctr = torch.zeros(1, dtype=torch.int64, device=dev)
+    kw = dict(flags=cof.attn_flags(False, False, True), keep_prob=0.2, seed=42, offset=ctr)
+    batches = [b for e in range(4) for b in cache.epoch(N, seed=e)]        # four epochs' shuffled batches, int32 views
+    batch0 = cache.select(batches[0])
+    st_a = cof.HeadTrainStep(batch0, batch0, Wa, ba, Wt, bt, None, (None, None) + pg, **kw)
+    X0 = cache.gather(batches[0])
+    st_b = cof.HeadTrainStep(X0, X0, Wa, ba, Wt, bt, labels[:N].clone(), (None, None) + pg, **kw)
+    f = cache.features
+    Xc = cof.Fp8Features.from_parts(f.codes[:N], f.scale[:N]) if fp8 else f[:N]
+    st_c = cof.HeadTrainStep(Xc, Xc, Wa, ba, Wt, bt, labels[:N].contiguous(), (None, None) + pg, **kw)
+    state = {'a': 0, 'b': 0}
+
+    def step_a():
+        st_a.rebind(index=batches[state['a'] % len(batches)])
+        state['a'] += 1
+        st_a.run()
+
+    def step_b():
+        idx = batches[state['b'] % len(batches)]
+        state['b'] += 1
+        st_b.rebind(X=cache.gather(idx), labels=labels[idx.long()])
+        st_b.run()
+
+    bytes_img = P * C * (1 if fp8 else 2)
+    info = {'N': N, 'T': T, 'shape': '{} of {} x {}x{}x{}, K={}, dropout keep=0.2'.format(N, T, H, H, C, K),
+            'feature_bytes_per_step': 2 * N * bytes_img, 'gather_bytes_per_step': 2 * N * bytes_img,
+            'cache_bytes': T * bytes_img, 'steps': (st_a, st_b, st_c)}
+    return {'a_gathered': step_a, 'b_gather_rebind_plain': step_b, 'c_plain_fixed': st_c.run}, info
+
+
+def run_cached(cof, dev, args, which):
+    """cached002_fp8 / cached002_bf16: the three variants ALTERNATING in one process, five timed loops of each,
+    interleaved; medians and the loops' spread.  a - c: what the gathered step costs over the plain step on a fixed
+    batch (the dependent index read, and a fresh batch from HBM where (c)'s one batch may stay in the Infinity Cache);
+    a / b: against the only route a shuffled epoch had."""
+    fp8 = which == 'cached002_fp8'
+    forms, info = build_cached(cof, dev, fp8, args.batch, args.hw, args.cache_images)
+    for _ in range(args.warmup):
+        for step in forms.values():
+            step()
+    torch.cuda.synchronize()
+    assert all(st.frozen_input for st in info['steps'])
+    runs = {k: [] for k in forms}
+    for _ in range(5):
+        for name, step in forms.items():
+            sec, _ = timed(step, args.steps, 0, min_ms=0.0, repeats=1)
+            runs[name].append(sec * 1e6)
+    med = {k: sorted(v)[len(v) // 2] for k, v in runs.items()}
+    return {'workload': '{}: cfg 002 frozen one-call training step from a resident {} feature cache, three variants '
+                        'alternating in one process; {}'.format(which, 'FP8 E4M3' if fp8 else 'bf16', info['shape']),
+            'us_per_step': {k: round(v, 2) for k, v in med.items()},
+            'us_per_step_runs': {k: [round(x, 2) for x in v] for k, v in runs.items()},
+            'us_per_step_spread': {k: round(max(v) - min(v), 2) for k, v in runs.items()},
+            'a_minus_c_us': round(med['a_gathered'] - med['c_plain_fixed'], 2),
+            'a_over_b': round(med['a_gathered'] / med['b_gather_rebind_plain'], 4),
+            'feature_bytes_per_step': info['feature_bytes_per_step'],
+            'gather_bytes_per_step': info['gather_bytes_per_step'], 'cache_bytes': info['cache_bytes'],
+            'clamped_ids': int(info['steps'][0]._cached.cache.status)}
+
+
 def timed(fn, steps, warmup, min_ms=50.0, repeats=5):
     """median over >= `repeats` timed loops of `steps` steps each (>= min_ms of device time in total)."""
     for _ in range(warmup):
@@ -1211,7 +1294,8 @@ def main():
     ap.add_argument('--workload', default='cfg003', choices=['cfg003', 'perclass', 'eval002', 'eval003', 'rank1', 'posebwd', 'posebwd_acc', 'update003',
                                                          'update_perclass', 'poseatt', 'video_perclass', 'video003',
                                                          'hico002', 'charades_clips', 'frozen002', 'frozen003',
-                                                         'frozen_perclass', 'frozen002_fp8', 'eval002_fp8'] +
+                                                         'frozen_perclass', 'frozen002_fp8', 'eval002_fp8',
+                                                         'cached002_fp8', 'cached002_bf16'] +
                     sorted(EVAL_CLIPS) + sorted(RANK_WORKLOADS))
     ap.add_argument('--clips', type=int, default=8, help='video_*: clips per batch')
     ap.add_argument('--frames', type=int, default=4, help='video_*: frames per clip')
@@ -1220,6 +1304,7 @@ def main():
                                                      'sequence', 'rank_one_call', 'rank1_one_call'],
                     help='video_* / hico002 / charades_clips / eval_* / rank*: run one variant alone (kernel traces)')
     ap.add_argument('--batch', type=int, default=32)
+    ap.add_argument('--cache-images', type=int, default=2048, help='cached002_*: images in the resident cache')
     ap.add_argument('--hw', type=int, default=14)
     ap.add_argument('--classes', type=int, default=None)
     ap.add_argument('--dtype', default=None, choices=['bf16', 'f32'])
@@ -1258,6 +1343,9 @@ def main():
         return
     if args.workload in ('frozen002_fp8', 'eval002_fp8'):
         print(json.dumps(run_fp8(cof, dev, args, args.workload)))
+        return
+    if args.workload in ('cached002_fp8', 'cached002_bf16'):
+        print(json.dumps(run_cached(cof, dev, args, args.workload)))
         return
     if args.workload.startswith('frozen'):
         print(json.dumps(run_frozen(cof, dev, args, args.workload)))
