@@ -44,6 +44,7 @@ APA_SCORES_SOFTMAX = 0   # eval.py:197
 APA_SCORES_SIGMOID = 1   # eval.py:194-195 (TRAIN.LOSS_FN_ACTION starts with 'multi-label')
 APA_WIMG_MAX = 12
 APA_RANK_MAX = 4         # attention maps chained from one bottom-up map (apa_rank_maps)
+APA_EXPLAIN_MAX_CLASSES = 8   # classes per image of one apa_attn_explain call
 APA_WIMG_ROLES = {0: 'Wa', 1: 'ba', 2: 'Wt', 3: 'bt'}
 
 # every symbol include/apa.h declares: name -> (restype, argtypes)
@@ -103,6 +104,11 @@ _SIGNATURES = {
     'apa_preprocess_images_workspace_bytes': (c_size_t, [c_int, c_int, POINTER(ctypes.c_int32), c_int]),
     'apa_preprocess_images': (c_int, [c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float,
                                       c_void_p, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
+    # class attention maps and overlays (apa_explain.hip)
+    'apa_attn_explain_workspace_bytes': (c_size_t, [c_int] * 6),
+    'apa_attn_explain': (c_int, [c_void_p] * 11 + [c_size_t] + [c_int] * 6 + [c_uint, c_int, c_void_p]),
+    'apa_attention_overlay_workspace_bytes': (c_size_t, [c_int, c_int]),
+    'apa_attention_overlay': (c_int, [c_void_p] * 5 + [c_size_t] + [c_int] * 6 + [c_void_p]),
     'apa_frame_pool_fwd': (c_int, [c_void_p] * 5 + [c_int] * 3 + [c_void_p]),
     'apa_frame_pool_bwd': (c_int, [c_void_p] * 8 + [c_int] * 3 + [c_void_p]),
     'apa_clip_xent_workspace_bytes': (c_size_t, [c_int] * 3),
@@ -1256,6 +1262,68 @@ def resize_bilinear_tf1(img, out_h: int, out_w: int):
     _check(lib.apa_resize_bilinear_tf1(_dev_ptr(img, 'img', torch.float32), out.data_ptr(), N, h, w, C,
                                        int(out_h), int(out_w), _stream_ptr()), 'apa_resize_bilinear_tf1')
     return out
+
+
+def attn_explain(X, att, Wt, bt, classes, *, flags=0, workspace=None, hooks=None):
+    """Top-down and combined attention maps of T chosen classes per image in one pass over X (include/apa.h:
+    apa_attn_explain).  X [N,P,C] (or [N,H,W,C]) f32 / bf16, the map the top-down conv reads; att [N,P,M] f32, M == 1 or
+    K, the `att` of an evaluation step; Wt [C,K], bt [K] f32; classes [N] or [N,T] integers on the device (any integer
+    type: converted to int32 on the device, no host synchronisation).  flags: APA_FLAG_RELU_INPUT or 0.
+    Returns (topdown [N,T,P], combined [N,T,P], class_logit [N,T], status): status is an int32 device scalar, the number
+    of class ids outside [0,K), which were clamped.  hooks (make_hooks(prof_fwd=...)): an event pair around the pass
+    over X."""
+    lib = load_library()
+    if X.dim() < 3:
+        raise ApaError('attn_explain: X must be [N,P,C] or [N,H,W,C]')
+    N, C = X.shape[0], X.shape[-1]
+    P = X.numel() // max(N * C, 1)
+    if tuple(Wt.shape[:1]) != (C,) or Wt.dim() != 2 or bt.numel() != Wt.shape[1]:
+        raise ApaError('attn_explain: Wt [C,K] and bt [K] expected')
+    K = Wt.shape[1]
+    if att.dim() != 3 or tuple(att.shape[:2]) != (N, P):
+        raise ApaError('attn_explain: att must be [N,P,M] (got {})'.format(tuple(att.shape)))
+    M = att.shape[2]
+    if classes.dim() == 1:
+        classes = classes.view(-1, 1)
+    if classes.dim() != 2 or classes.shape[0] != N or classes.dtype.is_floating_point:
+        raise ApaError('attn_explain: classes must be integers [N] or [N,T]')
+    T = classes.shape[1]
+    cls = classes.to(torch.int32).contiguous()
+    dev = X.device
+    dt = _feat_dtype(X)
+    topdown = torch.empty((N, T, P), dtype=torch.float32, device=dev)
+    combined = torch.empty((N, T, P), dtype=torch.float32, device=dev)
+    class_logit = torch.empty((N, T), dtype=torch.float32, device=dev)
+    status = torch.zeros((), dtype=torch.int32, device=dev)
+    need = int(lib.apa_attn_explain_workspace_bytes(N, P, C, K, T, dt))
+    if workspace is None or workspace.numel() < need:
+        workspace = torch.empty((max(need, 16),), dtype=torch.uint8, device=dev)
+    _check(lib.apa_attn_explain(_hooks_ptr(hooks), _dev_ptr(X, 'X'), _dev_ptr(att, 'att', torch.float32), _dev_ptr(Wt, 'Wt', torch.float32),
+                                _dev_ptr(bt, 'bt', torch.float32), _dev_ptr(cls, 'classes'), topdown.data_ptr(),
+                                combined.data_ptr(), class_logit.data_ptr(), status.data_ptr(),
+                                _dev_ptr(workspace, 'workspace'), workspace.numel(), N, P, C, K, M, T, int(flags), dt,
+                                _stream_ptr()), 'apa_attn_explain')
+    return topdown, combined, class_logit, status
+
+
+def attention_overlay(maps, images, *, want_f32=False):
+    """The reference's overlaid heat-map (src/train.py:184-195) at image size (include/apa.h: apa_attention_overlay):
+    maps [N,T,h,w] f32, images [N,H,W,3] f32 (the network's input).  Returns the uint8 overlay [N,T,H,W,3]
+    (tf.summary.image's scaling per (n,t) image), and with want_f32 the pair (uint8, float32 overlay)."""
+    lib = load_library()
+    if maps.dim() != 4 or images.dim() != 4 or images.shape[-1] != 3 or images.shape[0] != maps.shape[0]:
+        raise ApaError('attention_overlay: maps [N,T,h,w] and images [N,H,W,3] expected (got {} and {})'.format(
+            tuple(maps.shape), tuple(images.shape)))
+    N, T, h, w = maps.shape
+    H, W = images.shape[1:3]
+    dev = maps.device
+    u8 = torch.empty((N, T, H, W, 3), dtype=torch.uint8, device=dev)
+    f32 = torch.empty((N, T, H, W, 3), dtype=torch.float32, device=dev) if want_f32 else None
+    ws = torch.empty((max(int(lib.apa_attention_overlay_workspace_bytes(N, T)), 16),), dtype=torch.uint8, device=dev)
+    _check(lib.apa_attention_overlay(_dev_ptr(maps, 'maps', torch.float32), _dev_ptr(images, 'images', torch.float32),
+                                     None if f32 is None else f32.data_ptr(), _dev_ptr(u8, 'overlay'), ws.data_ptr(),
+                                     ws.numel(), N, T, h, w, H, W, _stream_ptr()), 'apa_attention_overlay')
+    return (u8, f32) if want_f32 else u8
 
 
 # --------------------------------------------------------------------------------------------

@@ -1530,3 +1530,80 @@ class FusedHeadEval:
             if st.tatt is not None:
                 ep['TemporalAttention'] = st.tatt.view(-1, frames, 1, 1)
         return st.probs, st.pred, ep
+
+    def explain(self, images, classes=None, topk: int = 1, overlay: bool = True, input_images=None):
+        """Why the batch was given its classes: the bottom-up map, the top-down map of T chosen classes per image and
+        their product (the paper's figures; the end points the reference dumps with `eval.py --ept` and summarises in
+        train.py:451-460), from ONE extra pass over the conv5 map (`cof.attn_explain`) behind the bound evaluation
+        step, which runs exactly as in `__call__`.  The K-map 'TopDownAttention' dump is never built.
+
+        * classes=None: the step's own predictions -- topk == 1 takes `pred` (no host synchronisation), topk > 1
+          `torch.topk` of the scores.  Explicit `classes`: integers [N] or [N,T] (clips: [B] or [B,T]), T <= 8.
+        * returns a dict: 'bottom_up' [N,H,W], 'top_down' [N,T,H,W], 'combined' [N,T,H,W], 'class_logit' [N,T]
+          (== the step's logits[n, class]), 'classes' [N,T] int64, 'scores' (what `__call__` returns), 'status' (int32
+          device scalar: class ids outside [0,K), which were clamped); with overlay=True also 'overlay_bottom_up'
+          [N,1,Hi,Wi,3] and 'overlay_combined' [N,T,Hi,Wi,3], uint8 (`cof.attention_overlay`: train.py:184-195, then
+          tf.summary.image's scaling).  With per-class bottom-up maps 'bottom_up' is [N,T,H,W], the chosen classes'.
+        * the overlay is laid over `images` when a backbone is in front, over `input_images` [N,Hi,Wi,3] otherwise.
+        * clip batches [B,F,...]: the frames are folded as in `__call__`; a clip's classes are repeated for its F
+          frames and every map is per FRAME.  The temporal attention weight of a frame is NOT applied to its maps.
+        * dense feature maps only: an Fp8Features or CachedBatch batch raises ValueError."""
+        from .custom_ops import custom_ops_factory as cof
+        for kind, what in ((cof.CachedBatch, 'a CachedBatch'), (cof.Fp8Features, 'an Fp8Features batch')):
+            if isinstance(images, kind):
+                raise ValueError('FusedHeadEval.explain: %s is not served: the explain kernel reads dense feature maps'
+                                 % what)
+        if self.head.is_training:
+            raise ValueError('FusedHeadEval.explain: a training-mode head (evaluation semantics only: no dropout)')
+        topk = int(topk)
+        if classes is None and not 1 <= topk <= cof.APA_EXPLAIN_MAX_CLASSES:
+            raise ValueError('FusedHeadEval.explain: topk must be 1..%d' % cof.APA_EXPLAIN_MAX_CLASSES)
+        has_backbone = self.network_fn.backbone is not None
+        src = None
+        if overlay:
+            src = images if has_backbone else input_images
+            if src is None:
+                raise ValueError('FusedHeadEval.explain: overlay=True needs an image source: there is no backbone in '
+                                 'front (`images` is the conv5 map) and no input_images were given')
+        scores, pred, ep = self(images)
+        st = self.step
+        frames = images.shape[1] if images.dim() == 5 else 1
+        X = st._keep[0]                                         # the dense [N,P,C] map the step was bound to
+        n, hh, ww = ep['PosePrelogitsBasedAttention'].shape[:3]
+        if classes is None:
+            cls = pred.view(-1, 1) if topk == 1 else torch.topk(scores, topk, dim=1).indices
+        else:
+            cls = classes if classes.dim() > 1 else classes.view(-1, 1)
+            if cls.dim() != 2 or cls.dtype.is_floating_point:
+                raise ValueError('FusedHeadEval.explain: classes must be integers [N] or [N,T]')
+            cls = cls.to(X.device)
+        if cls.shape[0] * frames != n:
+            raise ValueError('FusedHeadEval.explain: %d rows of classes for %d %s' % (
+                cls.shape[0], n // frames, 'clips' if frames > 1 else 'images'))
+        if frames > 1:                                          # a clip's classes, for each of its frames
+            cls = cls.repeat_interleave(frames, dim=0)
+        cls = cls.to(torch.int64)
+        t = cls.shape[1]
+        flags = cof.APA_FLAG_RELU_INPUT if self._preact else 0
+        h = self.head
+        td, comb, cl, status = cof.attn_explain(X, st.att, h.td_weights.data, h.td_biases.data, cls, flags=flags)
+        if st.att.shape[2] == 1:
+            bottom = st.att.view(n, hh, ww)
+            bottom_maps = st.att.view(n, 1, hh, ww)
+        else:                                                   # per-class maps: the chosen classes' own
+            k = st.att.shape[2]
+            idx = cls.clamp(0, k - 1).view(n, 1, t).expand(n, st.att.shape[1], t)
+            bottom_maps = torch.gather(st.att, 2, idx).permute(0, 2, 1).contiguous().view(n, t, hh, ww)
+            bottom = bottom_maps
+        out = {'bottom_up': bottom, 'top_down': td.view(n, t, hh, ww), 'combined': comb.view(n, t, hh, ww),
+               'class_logit': cl, 'classes': cls, 'scores': scores, 'status': status}
+        if overlay:
+            if src.dim() == 5:
+                src = src.reshape(-1, *src.shape[2:])
+            if src.dim() != 4 or src.shape[0] != n or src.shape[-1] != 3:
+                raise ValueError('FusedHeadEval.explain: the overlay needs images [N,Hi,Wi,3] for the %d maps (got %s)'
+                                 % (n, tuple(src.shape)))
+            src = src.detach().to(device=X.device, dtype=torch.float32).contiguous()
+            out['overlay_bottom_up'] = cof.attention_overlay(bottom_maps.contiguous(), src)
+            out['overlay_combined'] = cof.attention_overlay(out['combined'], src)
+        return out

@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define APA_VERSION 310 /* major*10000 + minor*100 + patch */
+#define APA_VERSION 311 /* major*10000 + minor*100 + patch */
 
 typedef enum apa_status {
   APA_OK = 0,
@@ -900,6 +900,48 @@ int apa_attn_head_eval_step_cached(const apa_feature_cache* cache, const apa_cli
  * at `cache` (same rule, same kernel; status int32 [n]).  Slots outside the cache: APA_ERR_INVALID_ARG. */
 int apa_quantize_features_fp8_at(const void* src, int src_dtype, void* cache, int cache_images, int first,
                                  int32_t* status, int n, int P, int C, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Class attention maps (nets_factory.py:247-328: end points 'TopDownAttention' / 'PosePrelogitsBasedAttention') of T
+ * chosen classes per image, in one pass over the map the top-down conv reads -- the K-map [N,P,K] dump is never built:
+ *     topdown[n,t,p]   = sum_c x[n,p,c] * Wt[c,k] + bt[k]            k = classes[n,t],  x = X (APA_FLAG_RELU_INPUT: max(X,0))
+ *     combined[n,t,p]  = att[n,p, M == 1 ? 0 : k] * topdown[n,t,p]
+ *     class_logit[n,t] = (1/P) * sum_p combined[n,t,p]               (the evaluation step's logits[n,k])
+ * X [N,P,C] f32 / bf16; att [N,P,M] f32, M == 1 or K: the `att` output of an evaluation step (softmax / relu already
+ * applied); Wt [C,K], bt [K] f32; classes [N,T] int32 on the device; the three outputs f32, [N,T,P] / [N,T,P] / [N,T].
+ * A class id outside [0,K) is clamped and, with `status` given, counted there (the caller zeroes the word; the
+ * convention of apa_feature_cache.index).  Evaluation semantics only: no dropout.  fp32 accumulation in a fixed order,
+ * no floating-point atomics: two calls give the same bits.  At most three launches.  hooks (may be NULL): only
+ * prof_fwd_start / prof_fwd_stop are read; they bracket the dispatch of the pass over X.
+ * Refused before anything touches the GPU, in this order --
+ *   APA_ERR_INVALID_ARG   a null pointer (status may be NULL), a non-positive N / P / C / K / M, M not 1 or K, a flag
+ *                         bit other than APA_FLAG_RELU_INPUT, an unknown dtype
+ *   APA_ERR_UNSUPPORTED   APA_DTYPE_FP8_E4M3, T outside 1 .. APA_EXPLAIN_MAX_CLASSES, C % 4 != 0, T * C > 16384 (the
+ *                         weights of an image's classes are staged in 64 KiB of LDS)
+ *   APA_ERR_WORKSPACE     ws_bytes < apa_attn_explain_workspace_bytes(...) (which is 0 for arguments refused above)
+ *   APA_ERR_INVALID_ARG   X not aligned to its load width (16 bytes; 8 for bf16 with C % 8 == 4), ws not to 16 bytes
+ */
+#define APA_EXPLAIN_MAX_CLASSES 8
+size_t apa_attn_explain_workspace_bytes(int N, int P, int C, int K, int T, int dtype);
+int apa_attn_explain(const apa_hooks* hooks /* NULL */, const void* X, const float* att, const float* Wt, const float* bt, const int32_t* classes,
+                     float* topdown, float* combined, float* class_logit, int32_t* status, void* ws, size_t ws_bytes,
+                     int N, int P, int C, int K, int M, int T, unsigned flags, int dtype, void* stream);
+
+/* The reference's overlaid heat-map (src/train.py:184-195, _gen_overlayed_img) at image size:
+ *     m    = tf.image.resize_images(map, [H,W])          TF 1.1 legacy bilinear, the rule of apa_resize_bilinear_tf1
+ *     gray = 0.2989 r + 0.5870 g + 0.1140 b               float32, summed in that order
+ *     out  = 0.5 * [gray, gray, gray] + 0.5 * [255 m, 0, 0]
+ * maps [N,T,h,w] f32 (any of att / topdown / combined); images [N,H,W,3] f32, the network's input (mean-subtracted);
+ * overlay_f32 [N,T,H,W,3] f32 and overlay_u8 [N,T,H,W,3] uint8, either may be NULL but not both.  The uint8 form is
+ * the rule tf.summary.image documents, per (n,t) image with lo / hi the min / max of its H*W*3 float values:
+ *     lo <  0: s = 127 / max(|lo|,|hi|), o = 128;     lo >= 0: s = 255 / hi, o = 0;     max(|lo|,|hi|) == 0: s = 0
+ *     u8 = (uint8) min(255, max(0, trunc(v * s + o)))
+ * The resized map is never materialised.  One launch, two with overlay_u8 (which needs a workspace of
+ * apa_attention_overlay_workspace_bytes(N, T) bytes, else APA_ERR_WORKSPACE; 0 for non-positive arguments).
+ * Null maps / images, no output, non-positive sizes: APA_ERR_INVALID_ARG before anything touches the GPU. */
+size_t apa_attention_overlay_workspace_bytes(int N, int T);
+int apa_attention_overlay(const float* maps, const float* images, float* overlay_f32, uint8_t* overlay_u8, void* ws,
+                          size_t ws_bytes, int N, int T, int h, int w, int H, int W, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * NET.USE_POSE_PRELOGITS_BASED_ATTENTION_RANK = R > 1 (nets_factory.py:247-328) with ONE bottom-up map: R attention

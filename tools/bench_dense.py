@@ -37,6 +37,11 @@ headline stays the cfg 002 training workload); run this file directly for one wo
             process, medians of five and their spread: (a) the gathered step (apa_attn_head_train_step_cached) with a
             fresh shuffled index per step, (b) gather + rebind + the plain step -- the loop without the gathered
             kernels --, (c) the plain step on one fixed contiguous batch.
+  explain002
+            class attention maps of T = 1 and T = 5 chosen classes at the cfg 002 shape (32 x 14x14x2048 fp32, K = 393):
+            the one-call evaluation step + cof.attn_explain against the per-op forward with want_topdown=True + torch.gather,
+            alternating in one process, medians of five; the explain pass over X and m1s_pool_fwd_kernel by HIP events
+            against the 8 TB/s peak.
   frozen002 / frozen003 / frozen_perclass
             the one-call training steps on FROZEN features (APA_FLAG_FROZEN_INPUT: no dX is computed or stored) against
             the same step as it runs today, at the BASELINE shapes (32 x 14x14x2048; cfg 002 fp32 K = 393, cfg 003 bf16
@@ -1250,6 +1255,83 @@ def run_cached(cof, dev, args, which):
             'clamped_ids': int(info['steps'][0]._cached.cache.status)}
 
 
+def run_explain002(cof, dev, args):
+    """Class attention maps of T chosen classes at the cfg 002 benchmark shape (32 x 14x14x2048 fp32, K = 393), T = 1 and
+    T = 5: the one-call evaluation step + cof.attn_explain against the only other route, the per-op forward with
+    want_topdown=True (all K maps, [N,P,K]) + torch.gather of the chosen classes, both producing scores, prediction,
+    the top-down and the combined maps of the same fixed classes.  The two alternate in one process, medians of five
+    loops; X rotates over enough sets that no step finds its map cached.  Also: the explain pass over X and the
+    evaluation step's m1s_pool_fwd_kernel (the same bytes) by HIP events, against the 8 TB/s peak."""
+    N, H, C, K = args.batch, args.hw, 2048, args.classes or 393
+    P = H * H
+    g = torch.Generator().manual_seed(42)
+    Wa = (torch.randn(C, 1, generator=g) / C ** 0.5).to(dev); ba = torch.zeros(1, device=dev)
+    Wt = (torch.randn(C, K, generator=g) / C ** 0.5).to(dev); bt = torch.zeros(K, device=dev)
+    per_set = N * P * C * 4
+    R = _n_sets(per_set, args.rotate)
+    Xs = [_features(N, P, C, torch.float32, dev, seed=42 + r) for r in range(R)]
+    evs = []
+    for X in Xs:
+        evs.append(cof.HeadEvalStep(X, X, Wa, ba, Wt, bt, workspace=evs[0].workspace if evs else None))
+    out = {'workload': 'explain002: evaluation step + attn_explain against the per-op forward with want_topdown=True + '
+                       'torch.gather, alternating in one process; {} x {}x{}x{} f32, K={}'.format(N, H, H, C, K) +
+                       _rot_note(R, per_set).replace('X/dX', 'X'),
+           'dtype': 'f32', 'rotate': R, 'x_bytes': per_set}
+    for T in (1, 5):
+        cls = torch.stack([(torch.arange(N) * 7 + 13 * t) % K for t in range(T)], dim=1).to(dev)
+        cls32 = cls.to(torch.int32)
+        idx = cls.view(N, 1, T).expand(N, P, T)
+        ws = torch.empty((int(evs[0].lib.apa_attn_explain_workspace_bytes(N, P, C, K, T, 0)),), dtype=torch.uint8, device=dev)
+        state = {'a': 0, 'b': 0, 'mod_ws': None}
+
+        def explain_route():
+            ev = evs[state['a'] % R]
+            state['a'] += 1
+            ev.run()
+            return cof.attn_explain(ev._keep[0], ev.att, Wt, bt, cls32, workspace=ws)
+
+        def module_route():
+            X = Xs[state['b'] % R]
+            state['b'] += 1
+            logits, att, _, _, topdown, state['mod_ws'] = cof.attn_pool_fwd(X, X, Wa, ba, Wt, bt, want_topdown=True,
+                                                                            workspace=state['mod_ws'])
+            probs = torch.softmax(logits, -1)
+            pred = torch.argmax(logits, 1)
+            td = torch.gather(topdown, 2, idx)
+            return td, att * td, probs, pred
+
+        for _ in range(args.warmup):
+            explain_route(); module_route()
+        torch.cuda.synchronize()
+        runs = {'explain': [], 'module': []}
+        for _ in range(5):
+            for name, fn in (('explain', explain_route), ('module', module_route)):
+                sec, _ = timed(fn, args.steps, 0, min_ms=0.0, repeats=1)
+                runs[name].append(sec * 1e6)
+        med = {k: sorted(v)[len(v) // 2] for k, v in runs.items()}
+        # the pass over X alone, and the evaluation step's pooling pass over the same bytes, by HIP events
+        n = 20
+        kt_e, kt_p = cof.KernelTimer(n), cof.KernelTimer(n)
+        for i in range(n):
+            X = Xs[i % R]
+            _, att, _, _, _, state['mod_ws'] = cof.attn_pool_fwd(X, X, Wa, ba, Wt, bt, workspace=state['mod_ws'],
+                                                                 hooks=kt_p.hooks(i))
+            cof.attn_explain(X, att, Wt, bt, cls32, workspace=ws, hooks=kt_e.hooks(i))
+        torch.cuda.synchronize()
+        med_us = lambda v: sorted(v)[len(v) // 2] * 1e3
+        k_e, k_p = med_us(kt_e.fwd_elapsed_ms()), med_us(kt_p.fwd_elapsed_ms())
+        kt_e.close(); kt_p.close()
+        out['T=%d' % T] = {
+            'us_per_step': {k: round(v, 2) for k, v in med.items()},
+            'us_per_step_runs': {k: [round(x, 2) for x in v] for k, v in runs.items()},
+            'explain_over_module': round(med['explain'] / med['module'], 4),
+            'kernels_us': {'explain_main_kernel': round(k_e, 2), 'm1s_pool_fwd_kernel': round(k_p, 2)},
+            'explain_main_kernel_frac_of_hbm_peak': round(per_set / (k_e * 1e-6) / 1e9 / HBM_PEAK_GBS, 4),
+            'm1s_pool_fwd_kernel_frac_of_hbm_peak': round(per_set / (k_p * 1e-6) / 1e9 / HBM_PEAK_GBS, 4),
+            'module_route_topdown_bytes': N * P * K * 4, 'explain_route_map_bytes': 2 * N * T * P * 4}
+    return out
+
+
 def timed(fn, steps, warmup, min_ms=50.0, repeats=5):
     """median over >= `repeats` timed loops of `steps` steps each (>= min_ms of device time in total)."""
     for _ in range(warmup):
@@ -1295,7 +1377,7 @@ def main():
                                                          'update_perclass', 'poseatt', 'video_perclass', 'video003',
                                                          'hico002', 'charades_clips', 'frozen002', 'frozen003',
                                                          'frozen_perclass', 'frozen002_fp8', 'eval002_fp8',
-                                                         'cached002_fp8', 'cached002_bf16'] +
+                                                         'cached002_fp8', 'cached002_bf16', 'explain002'] +
                     sorted(EVAL_CLIPS) + sorted(RANK_WORKLOADS))
     ap.add_argument('--clips', type=int, default=8, help='video_*: clips per batch')
     ap.add_argument('--frames', type=int, default=4, help='video_*: frames per clip')
@@ -1349,6 +1431,9 @@ def main():
         return
     if args.workload.startswith('frozen'):
         print(json.dumps(run_frozen(cof, dev, args, args.workload)))
+        return
+    if args.workload == 'explain002':
+        print(json.dumps(run_explain002(cof, dev, args)))
         return
     if args.workload == 'poseatt':
         step, info, kernel_times = build_poseatt(cof, dev, args.batch, args.hw, args.classes or 393,
