@@ -185,7 +185,11 @@ template <int EPL> struct MaskBytes {
   static constexpr int BPP = 256 * BPL;       // bytes per pixel (4 waves x 64 lanes)
 };
 
-template <typename T, int VW, int PIX, bool FUSED, bool TRAIN, bool RIN>
+// SM: softmax attention.  A template argument of both passes: as a test of the run-time `act` all three arms stayed in
+// the chunk loop (forward: seven conditional branches per chunk, the expf sequence and the accumulators copied around
+// the rescale on the identity path; backward: four per chunk, whose merge made the loop's tail a block of its own).
+// Identity against relu stays a select on `act`.
+template <typename T, int VW, int PIX, bool FUSED, bool TRAIN, bool SM, bool RIN>
 __device__ __forceinline__ void fwd_chunk(FwdState<T, VW, PIX, FUSED, TRAIN>& st,
                                           const uint4 (&xr)[PIX][VW], ChunkRange cr, float* sm,
                                           float* __restrict__ att_im, int n, int P, int C, int cbase,
@@ -216,7 +220,7 @@ __device__ __forceinline__ void fwd_chunk(FwdState<T, VW, PIX, FUSED, TRAIN>& st
       d[i] = d0 + d1;
     }
     const float zt = block_dots<PIX>(d, sm, wave, lane) + st.bias;
-    if (act == M1_ACT_SOFTMAX) {
+    if constexpr (SM) {
       const float m_chunk = row_max16(l16 < np ? zt : -INFINITY);
       const float m_new = fmaxf(st.m_run, m_chunk);
       const float scale = expf(st.m_run - m_new);   // exp(-inf) = 0 on the first chunk
@@ -293,7 +297,8 @@ __device__ __forceinline__ void fwd_chunk(FwdState<T, VW, PIX, FUSED, TRAIN>& st
 // so the descriptor lies behind it: the index read is one scalar load in front of the first chunk's address, which the
 // plain instances do not have.  FUSED only, without RIN and (backward) NODX only: the launchers below name every
 // instance from m1_pool_form's tags.
-template <typename T, int VW, int PIX, bool FUSED, bool TRAIN, bool RIN = false, bool GATHER = false>
+// SM: the softmax instances (fwd_chunk); forward: of the fused forms only, a map that is already final is pooled as it is.
+template <typename T, int VW, int PIX, bool FUSED, bool TRAIN, bool SM, bool RIN = false, bool GATHER = false>
 __global__ __launch_bounds__(256, 2) void m1s_pool_fwd_kernel(
     const T* __restrict__ X, int P, int S, int nblk, int act, const float* __restrict__ Wa,
     const float* __restrict__ ba, float* __restrict__ att, float* __restrict__ pacc,
@@ -361,9 +366,9 @@ __global__ __launch_bounds__(256, 2) void m1s_pool_fwd_kernel(
       const int slot = (u + NBm1) % NB;
       if (!FUSED) av_r[slot] = att_rd[min(p_begin + (ch + u + NBm1) * PIX + l16, p_last)];
       load_chunk<T, VW, PIX>(xr[slot], xim, p_begin + (ch + u + NBm1) * PIX, p_last, C, cbase);
-      fwd_chunk<T, VW, PIX, FUSED, TRAIN, RIN>(st, xr[u], chunk_range<PIX>(p_begin, p_end, ch + u), sm_x[u],
-                                               att_im, n, P, C, cbase, wave, lane, act, inv_keep, thresh,
-                                               k0, k1, bits_im, av_r[u]);
+      fwd_chunk<T, VW, PIX, FUSED, TRAIN, SM, RIN>(st, xr[u], chunk_range<PIX>(p_begin, p_end, ch + u), sm_x[u], att_im,
+                                                   n, P, C, cbase, wave, lane, act, inv_keep, thresh, k0, k1, bits_im,
+                                                   av_r[u]);
     }
   }
 
@@ -379,7 +384,7 @@ __global__ __launch_bounds__(256, 2) void m1s_pool_fwd_kernel(
   }
   m1_gather_note(n, s == 0 && threadIdx.x == 0, g);
   if (threadIdx.x == 0) {
-    pstat[blk * 4 + 0] = (FUSED && act == M1_ACT_SOFTMAX) ? st.m_run : 0.f;
+    pstat[blk * 4 + 0] = (FUSED && SM) ? st.m_run : 0.f;
     pstat[blk * 4 + 1] = st.l_run;
     pstat[blk * 4 + 2] = st.a_sum;
     pstat[blk * 4 + 3] = 0.f;
@@ -400,7 +405,7 @@ struct BwdState {
   float dba_acc, sn, corr;
 };
 
-template <typename T, int VW, int PIX, bool FUSED, bool TRAIN, bool RIN, bool BITS, bool NODX = false>
+template <typename T, int VW, int PIX, bool FUSED, bool TRAIN, bool SM, bool RIN, bool BITS, bool NODX = false>
 __device__ __forceinline__ void bwd_chunk(BwdState<T, VW, PIX, FUSED, TRAIN>& st,
                                           const uint4 (&xr)[PIX][VW], float a_l, float e_l,
                                           const uint32_t (&kbits)[PIX],
@@ -453,9 +458,8 @@ __device__ __forceinline__ void bwd_chunk(BwdState<T, VW, PIX, FUSED, TRAIN>& st
   if (TRAIN) tot *= inv_keep;
   const float dA = (tot + st.sn + e_l) * invP;   // e_l: extra channels' share (apa_m1_cat.hip), else 0
   float dZl;
-  if (act == M1_ACT_SOFTMAX) dZl = a_l * (dA - st.corr);
-  else if (act == M1_ACT_RELU) dZl = a_l > 0.f ? dA : 0.f;
-  else dZl = dA;
+  if constexpr (SM) dZl = a_l * (dA - st.corr);
+  else dZl = (act == M1_ACT_RELU && !(a_l > 0.f)) ? 0.f : dA;   // relu gates on att > 0, identity passes dA
   if (!FUSED && wave == 0 && lane < np) dZout_im[q0 + lane] = dZl;
   // NODX: nothing is stored through dX (APA_FLAG_FROZEN_INPUT: nobody reads it; APA_IFLAG_NO_DX, fused cfg 003 step:
   // the dX share A/P . dz . mask/keep is formed by the pose head's dX product in its epilogue).  With Xatt != X the
@@ -511,8 +515,8 @@ template <int BPL> __device__ __forceinline__ uint32_t ld_keep_bits(const uint8_
   return *reinterpret_cast<const uint16_t*>(p);
 }
 
-template <typename T, int VW, int PIX, bool FUSED, bool TRAIN, bool RIN = false, bool BITS = false, bool NODX = false,
-          bool GATHER = false>
+template <typename T, int VW, int PIX, bool FUSED, bool TRAIN, bool SM, bool RIN = false, bool BITS = false,
+          bool NODX = false, bool GATHER = false>
 __global__ __launch_bounds__(256, 2) void m1s_bwd_main_kernel(
     const T* __restrict__ X, int P, int S, int nblk, int K, const float* __restrict__ att,
     const float* __restrict__ dA_extra, const uint8_t* __restrict__ maskbits, const float* __restrict__ dz,
@@ -595,7 +599,7 @@ __global__ __launch_bounds__(256, 2) void m1s_bwd_main_kernel(
           st.wa[i] = w.x; st.wa[i + 1] = w.y; st.wa[i + 2] = w.z; st.wa[i + 3] = w.w;
           st.dwa[i] = 0.f; st.dwa[i + 1] = 0.f; st.dwa[i + 2] = 0.f; st.dwa[i + 3] = 0.f;
         }
-        if (act == M1_ACT_SOFTMAX) {
+        if constexpr (SM) {
           const float4 zz = *reinterpret_cast<const float4*>(zsave + (size_t)n * C + c);
           zdz = fmaf(zz.x, dd.x, zdz); zdz = fmaf(zz.y, dd.y, zdz);
           zdz = fmaf(zz.z, dd.z, zdz); zdz = fmaf(zz.w, dd.w, zdz);
@@ -609,7 +613,7 @@ __global__ __launch_bounds__(256, 2) void m1s_bwd_main_kernel(
       for (int k = lane; k < K; k += 64) sn = fmaf(G[(size_t)n * K + k], bt[k], sn);
       st.sn = wave_sum(sn);
     }
-    if (act == M1_ACT_SOFTMAX) {   // corr = z.dz + (G.bt) * abar, z.dz summed over the 4 waves
+    if constexpr (SM) {   // corr = z.dz + (G.bt) * abar, z.dz summed over the 4 waves
       zdz = wave_sum(zdz);
       if (lane == 0) sm_aux[wave] = zdz;
       __syncthreads();
@@ -623,9 +627,9 @@ __global__ __launch_bounds__(256, 2) void m1s_bwd_main_kernel(
       if (u > 0 && ch + u >= nchunk) break;
       constexpr int NBm1 = NB - 1;
       fetch((u + NBm1) % NB, walk(ch + u + NBm1));
-      bwd_chunk<T, VW, PIX, FUSED, TRAIN, RIN, BITS, NODX>(st, xr[u], a_r[u], e_r[u], kb_r[u], chunk_range<PIX>(p_begin, p_end, walk(ch + u)),
-                                                           sm_x[u], dxim, dZout_im, n, P, C, cbase, wave, lane, act, invP,
-                                                           inv_keep, thresh, k0, k1);
+      bwd_chunk<T, VW, PIX, FUSED, TRAIN, SM, RIN, BITS, NODX>(
+          st, xr[u], a_r[u], e_r[u], kb_r[u], chunk_range<PIX>(p_begin, p_end, walk(ch + u)), sm_x[u], dxim, dZout_im, n,
+          P, C, cbase, wave, lane, act, invP, inv_keep, thresh, k0, k1);
     }
   }
 
@@ -670,10 +674,20 @@ static int launch_fwd_t(const M1Call& c, const M1Fwd& io) {
   if (M1Trace* t = m1_trace()) { t->pool_fwd = M1_POOL_STREAM; t->fwd_w = VW; t->fwd_pix = PIX; }
   m1_pool_form(c, [&](auto F, auto TR, auto G) {
     constexpr bool f = decltype(F)::value, t = decltype(TR)::value, g = decltype(G)::value;
-    auto kernel = m1s_pool_fwd_kernel<T, VW, PIX, f, t, false, g>;
-    // relu on the input: instantiated for the plain fused map only (m1_call_fill: relu_input is fused, never gathered)
+    auto arm = [&](auto SM) {
+      constexpr bool sm = decltype(SM)::value;
+      auto k = m1s_pool_fwd_kernel<T, VW, PIX, f, t, sm, false, g>;
+      // relu on the input: instantiated for the plain fused map only (m1_call_fill: relu_input is fused, never gathered)
+      if constexpr (f && !g) {
+        if (c.relu_input) k = m1s_pool_fwd_kernel<T, VW, PIX, true, t, sm, true>;
+      }
+      return k;
+    };
+    auto kernel = arm(std::false_type{});
+    // softmax: plain fused maps only (m1_call_fill: pool_act is the identity on a map that is already final, and the
+    // cache form a gathered call has to be excludes softmax)
     if constexpr (f && !g) {
-      if (c.relu_input) kernel = m1s_pool_fwd_kernel<T, VW, PIX, true, t, true>;
+      if (c.pool_act == M1_ACT_SOFTMAX) kernel = arm(std::true_type{});
     }
     launch_ev(kernel, dim3(c.pl.nblk), dim3(256), 0, c.st, c.ev0, c.ev1, static_cast<const T*>(io.X), c.P, c.pl.S,
               c.pl.nblk, c.pool_act, io.Wa, io.ba, io.att, c.pacc, c.pstat, c.inv_keep, c.key.thresh, c.key.seed,
@@ -700,11 +714,20 @@ static int launch_bwd_t(const M1Call& c, const M1Bwd& io) {
     // instance that stores through dX, and a gathered call (m1_call_fill: no dX) has no instance that does
     auto arm = [&](auto RIN, auto BITS) {
       constexpr bool r = decltype(RIN)::value, b = decltype(BITS)::value;
-      auto k = m1s_bwd_main_kernel<T, VW, PIX, f, t, r, b, true, g>;
+      auto act_arm = [&](auto SM) {
+        constexpr bool sm = decltype(SM)::value;
+        auto k = m1s_bwd_main_kernel<T, VW, PIX, f, t, sm, r, b, true, g>;
+        if constexpr (!g) {
+          if (!c.no_dx) k = m1s_bwd_main_kernel<T, VW, PIX, f, t, sm, r, b, false>;
+        }
+        return k;
+      };
+      // softmax: every plain form has its instance (dZ is formed in this pass, fused or not); a gathered call has none
+      // (m1_call_fill: the cache form excludes softmax)
       if constexpr (!g) {
-        if (!c.no_dx) k = m1s_bwd_main_kernel<T, VW, PIX, f, t, r, b, false>;
+        if (c.act == M1_ACT_SOFTMAX) return act_arm(std::true_type{});
       }
-      return k;
+      return act_arm(std::false_type{});
     };
     const std::true_type yes; const std::false_type no;
     auto kernel = arm(no, no);
