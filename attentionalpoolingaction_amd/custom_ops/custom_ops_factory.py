@@ -45,6 +45,7 @@ APA_SCORES_SIGMOID = 1   # eval.py:194-195 (TRAIN.LOSS_FN_ACTION starts with 'mu
 APA_WIMG_MAX = 12
 APA_RANK_MAX = 4         # attention maps chained from one bottom-up map (apa_rank_maps)
 APA_EXPLAIN_MAX_CLASSES = 8   # classes per image of one apa_attn_explain call
+APA_AP_MAX_SAMPLES = 16384    # rows of one apa_average_precision call (a class's keys are sorted in one block's LDS)
 APA_WIMG_ROLES = {0: 'Wa', 1: 'ba', 2: 'Wt', 3: 'bt'}
 
 # every symbol include/apa.h declares: name -> (restype, argtypes)
@@ -109,6 +110,9 @@ _SIGNATURES = {
     'apa_attn_explain': (c_int, [c_void_p] * 11 + [c_size_t] + [c_int] * 6 + [c_uint, c_int, c_void_p]),
     'apa_attention_overlay_workspace_bytes': (c_size_t, [c_int, c_int]),
     'apa_attention_overlay': (c_int, [c_void_p] * 5 + [c_size_t] + [c_int] * 6 + [c_void_p]),
+    # average precision, mAP and accuracy of accumulated scores (apa_metrics.hip)
+    'apa_average_precision_workspace_bytes': (c_size_t, [c_int, c_int]),
+    'apa_average_precision': (c_int, [c_void_p] * 3 + [c_int, c_int] + [c_void_p] * 5 + [c_size_t, c_void_p]),
     'apa_frame_pool_fwd': (c_int, [c_void_p] * 5 + [c_int] * 3 + [c_void_p]),
     'apa_frame_pool_bwd': (c_int, [c_void_p] * 8 + [c_int] * 3 + [c_void_p]),
     'apa_clip_xent_workspace_bytes': (c_size_t, [c_int] * 3),
@@ -1324,6 +1328,58 @@ def attention_overlay(maps, images, *, want_f32=False):
                                      None if f32 is None else f32.data_ptr(), _dev_ptr(u8, 'overlay'), ws.data_ptr(),
                                      ws.numel(), N, T, h, w, H, W, _stream_ptr()), 'apa_attention_overlay')
     return (u8, f32) if want_f32 else u8
+
+
+# --------------------------------------------------------------------------------------------
+# average precision, mAP and accuracy (include/apa.h: apa_average_precision)
+# --------------------------------------------------------------------------------------------
+def average_precision_workspace_bytes(T: int, K: int) -> int:
+    """apa_average_precision_workspace_bytes: 0 for a shape the call refuses (T outside 1..APA_AP_MAX_SAMPLES, K < 1)"""
+    return int(load_library().apa_average_precision_workspace_bytes(int(T), int(K)))
+
+
+def average_precision_result_bytes(K: int) -> int:
+    """bytes of the one buffer the four results of average_precision are views of"""
+    return 8 * K + 24 + 4 * K + 8
+
+
+def average_precision(scores, labels=None, targets=None, *, workspace=None, out=None):
+    """Per-class average precision, mAP and accuracy of accumulated scores on the device (include/apa.h:
+    apa_average_precision, which states the ranking rule): scores [T,K] f32; labels [T] int64 (class k's positives are
+    labels == k) or targets [T,K] f32 multi-hot (targets[:,k] > 0), exactly one of the two.  Returns
+    (ap [K] float64, npos [K] int32, summary [3] float64 = (mAP, accuracy, classes with positives), status [2] int32 =
+    (NaN scores, labels outside [0,K))), all on the device, no synchronisation.  The four are views of ONE uint8 buffer
+    (`out`, average_precision_result_bytes(K) bytes: ap, summary, npos, status in that order), so a caller can bring
+    them to the host with a single copy of their common storage."""
+    lib = load_library()
+    if scores.dim() != 2:
+        raise ApaError('average_precision: scores [T,K] expected (got {})'.format(tuple(scores.shape)))
+    if (labels is None) == (targets is None):
+        raise ApaError('average_precision: exactly one of labels [T] / targets [T,K] is given')
+    T, K = (int(d) for d in scores.shape)
+    if labels is not None and tuple(labels.shape) != (T,):
+        raise ApaError('average_precision: labels [T] = [{}] expected (got {})'.format(T, tuple(labels.shape)))
+    if targets is not None and tuple(targets.shape) != (T, K):
+        raise ApaError('average_precision: targets [T,K] = [{},{}] expected (got {})'.format(T, K, tuple(targets.shape)))
+    dev = scores.device
+    nbytes = average_precision_result_bytes(K)
+    if out is None:
+        out = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+    elif out.dtype != torch.uint8 or out.dim() != 1 or out.numel() < nbytes or not out.is_contiguous():
+        raise ApaError('average_precision: out must be a contiguous uint8 buffer of average_precision_result_bytes(K) bytes')
+    ap = out[:8 * K].view(torch.float64)
+    summary = out[8 * K:8 * K + 24].view(torch.float64)
+    npos = out[8 * K + 24:12 * K + 24].view(torch.int32)
+    status = out[12 * K + 24:12 * K + 32].view(torch.int32)
+    need = int(lib.apa_average_precision_workspace_bytes(T, K))
+    if workspace is None or workspace.numel() < need:
+        workspace = torch.empty((max(need, 16),), dtype=torch.uint8, device=dev)
+    _check(lib.apa_average_precision(_dev_ptr(scores, 'scores', torch.float32), _dev_ptr(labels, 'labels', torch.int64),
+                                     _dev_ptr(targets, 'targets', torch.float32), T, K, _dev_ptr(ap, 'ap'),
+                                     npos.data_ptr(), summary.data_ptr(), status.data_ptr(),
+                                     _dev_ptr(workspace, 'workspace'), workspace.numel(), _stream_ptr()),
+           'apa_average_precision')
+    return ap, npos, summary, status
 
 
 # --------------------------------------------------------------------------------------------

@@ -1531,6 +1531,15 @@ class FusedHeadEval:
                 ep['TemporalAttention'] = st.tatt.view(-1, frames, 1, 1)
         return st.probs, st.pred, ep
 
+    def new_evaluation(self, capacity: int):
+        """An `eval_utils.DeviceEvaluation` for this head's scores: its K, its device, and multi-hot targets when
+        TRAIN.LOSS_FN_ACTION starts with 'multi-label' (the configurations whose scores are sigmoids).  Feed it what
+        `__call__` returns -- `meter.update(scores, labels_action)` -- and read accuracy / mAP from `meter.result()`:
+        nothing touches the host until then."""
+        from . import eval_utils
+        w = self.head.td_weights
+        return eval_utils.DeviceEvaluation(capacity, int(w.shape[1]), w.device, multi_label=self.multi_label)
+
     def explain(self, images, classes=None, topk: int = 1, overlay: bool = True, input_images=None):
         """Why the batch was given its classes: the bottom-up map, the top-down map of T chosen classes per image and
         their product (the paper's figures; the end points the reference dumps with `eval.py --ept` and summarises in

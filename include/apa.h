@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define APA_VERSION 311 /* major*10000 + minor*100 + patch */
+#define APA_VERSION 312 /* major*10000 + minor*100 + patch */
 
 typedef enum apa_status {
   APA_OK = 0,
@@ -942,6 +942,49 @@ int apa_attn_explain(const apa_hooks* hooks /* NULL */, const void* X, const flo
 size_t apa_attention_overlay_workspace_bytes(int N, int T);
 int apa_attention_overlay(const float* maps, const float* images, float* overlay_f32, uint8_t* overlay_u8, void* ws,
                           size_t ws_bytes, int N, int T, int h, int w, int H, int W, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * The metric an evaluation reports (src/eval.py:303-306): per-class average precision, their mean and the accuracy of
+ * T accumulated score rows, on the device -- src/eval/utils.py:4-16 (compute_map) over
+ * src/eval/cap_eval_utils.py:55-109 (calc_pr_ovr_noref + voc_ap), in float64.
+ *     scores  [T,K] f32 row-major, contiguous
+ *     labels  [T] int64, or NULL        class k's positives are labels == k (compute_map)
+ *     targets [T,K] f32 multi-hot, or NULL        class k's positives are targets[:,k] > 0 (calc_pr_ovr_noref's counts > 0)
+ *     ap      [K] f64     npos [K] int32: the positives of each class
+ *     summary [3] f64     mAP, accuracy, the number of classes with positives
+ *     status  [2] int32   NaN scores seen, labels outside [0,K)         (written, not accumulated)
+ * Exactly one of labels / targets is given.  The accuracy -- the share of rows whose FIRST maximum (np.argmax) is the
+ * label -- exists with labels only; with targets summary[1] is NaN.
+ *
+ * THE RANKING RULE.  A class's scores are ranked in descending order; equal scores are ordered by DESCENDING sample
+ * index (what np.argsort(out, kind='stable')[::-1] gives).  -0.0 and +0.0 are equal; +-inf are ordinary values; a NaN
+ * is counted in status[0] and ranked behind every number; a label outside [0,K) is counted in status[1] and is no
+ * class's positive.  (The reference ranks with np.argsort(out)[::-1], whose order under ties is that of an unstable
+ * introsort and cannot be stated; on tie-free scores the two rankings are the same.)
+ *
+ * THE VALUE.  With ctp_i the positives among ranks 0 .. i:  P_i = ctp_i / (i + 1),  R_i = ctp_i / npos, both correctly
+ * rounded float64 quotients;  E_i = max(P_i, P_{i+1}, ...);  ap = sum over the positives i of (R_i - R_{i-1}) * E_i,
+ * the difference taken between the two rounded quotients.  The counts are integers and the maximum is exact; the sum
+ * runs in rank order, as voc_ap's loop adds its terms, so on tie-free scores ap has the host routine's rounding (a class
+ * whose samples are all positives gets exactly 1.0), and two calls on the same input give the same bits.  mAP adds the
+ * classes' values in one fixed order of its own (np.mean's pairwise order is not restated: the values lie in [0,1], the
+ * two means differ by at most K * 2^-52).  A class without positives has npos = 0, ap = 0 and is left out of the mean;
+ * mAP is the mean of the others' ap, NaN if there are none.
+ *
+ * Three launches on `stream`, no floating-point atomics, no synchronisation.  A class's keys are sorted in ONE block's
+ * LDS, which bounds T: APA_AP_MAX_SAMPLES (128 KiB of keys).  Larger evaluations are not served (no multi-pass sort).
+ * Refused before anything touches the GPU, in this order --
+ *   APA_ERR_INVALID_ARG   a null scores / ap / npos / summary / status; both or neither of labels / targets;
+ *                         T < 1 or K < 1
+ *   APA_ERR_UNSUPPORTED   T > APA_AP_MAX_SAMPLES
+ *   APA_ERR_WORKSPACE     ws NULL or ws_bytes < apa_average_precision_workspace_bytes(T, K) (0 for arguments refused
+ *                         above)
+ *   APA_ERR_INVALID_ARG   ws not 16-byte aligned
+ */
+#define APA_AP_MAX_SAMPLES 16384
+size_t apa_average_precision_workspace_bytes(int T, int K);
+int apa_average_precision(const float* scores, const int64_t* labels, const float* targets, int T, int K, double* ap,
+                          int32_t* npos, double* summary, int32_t* status, void* ws, size_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * NET.USE_POSE_PRELOGITS_BASED_ATTENTION_RANK = R > 1 (nets_factory.py:247-328) with ONE bottom-up map: R attention

@@ -57,6 +57,10 @@ headline stays the cfg 002 training workload); run this file directly for one wo
             calls deploy.FusedHeadEval made before that entry point existed (HeadEvalStep.run, cof.frame_pool_fwd,
             eval_utils.predict).
 
+  map393    The metric of a validation pass, T = 7000 accumulated score rows of K = 393 classes (--samples / --classes;
+            --multi-hot for sigmoid scores against multi-hot targets, e.g. the HICO-like 9600 x 600): the host route
+            (eval_utils.Evaluation.result(): one copy, K argsorts, voc_ap loops) against the device route
+            (eval_utils.DeviceEvaluation.result(): three launches, one small copy), alternating in one process.
   rank2_002 / rank3_002
             NET.USE_POSE_PRELOGITS_BASED_ATTENTION_RANK = 2 (identity attention) / 3 (relu) on the cfg 002 shape (32 x
             14x14x2048 fp32, K = 393, training).  Three variants alternate in one process, medians of five: `rank_one_call`
@@ -73,6 +77,7 @@ import os
 import sys
 import time
 
+import numpy as np
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -1332,6 +1337,83 @@ def run_explain002(cof, dev, args):
     return out
 
 
+def run_map393(cof, dev, args):
+    """The metric of a validation pass: eval_utils.Evaluation.result() (one copy to the host, then K argsorts and
+    voc_ap loops in numpy) against eval_utils.DeviceEvaluation.result() (cof.average_precision: three launches, one
+    small copy) on the same accumulated scores -- softmax of random logits, T = --samples (7000), K = --classes (393).
+    --multi-hot: sigmoid scores and multi-hot targets (the HICO-like case, e.g. --samples 9600 --classes 600); the
+    host route is then what Evaluation.result() does with single labels -- one copy, calc_pr_ovr_noref per class --
+    since Evaluation itself takes single labels only.  The two routes alternate in one process: five runs each, a host
+    run one call, a device run --steps calls.  Also: the three launches alone by device events around
+    cof.average_precision with a preallocated workspace."""
+    from attentionalpoolingaction_amd import eval_utils
+    T, K, multi = args.samples or 7000, args.classes or 393, args.multi_hot
+    g = torch.Generator().manual_seed(42)
+    logits = torch.randn(T, K, generator=g) * 3.0
+    if multi:
+        scores = torch.sigmoid(logits).to(dev)
+        truth = (torch.rand(T, K, generator=g) < 0.02).float().to(dev)
+    else:
+        scores = torch.softmax(logits, -1).to(dev)
+        truth = torch.randint(0, K, (T,), generator=g).to(dev)
+    batch = 512
+    meter = eval_utils.DeviceEvaluation(T, K, dev, multi_label=multi)
+    old = eval_utils.Evaluation()
+    for at in range(0, T, batch):
+        meter.update(scores[at:at + batch], truth[at:at + batch])
+        if not multi:
+            old.update(scores[at:at + batch], truth[at:at + batch])
+
+    def host_route():
+        if not multi:
+            return old.result()
+        both = torch.cat([scores.double(), truth.double()], dim=1).cpu().numpy()      # one copy, as Evaluation.result()
+        s, t = both[:, :K].astype(np.float32), both[:, K:]
+        aps = [eval_utils.calc_pr_ovr_noref(t[:, k], s[:, k])[3] for k in range(K) if (t[:, k] > 0).any()]
+        return {'mAP': float(np.mean(aps)), 'aps': aps}
+
+    ref, got = host_route(), meter.result()
+    for _ in range(args.warmup):
+        meter.result()
+    torch.cuda.synchronize()
+    runs = {'host': [], 'device': []}
+    for _ in range(5):
+        t0 = time.perf_counter()
+        host_route()
+        torch.cuda.synchronize()
+        runs['host'].append((time.perf_counter() - t0) * 1e6)
+        t0 = time.perf_counter()
+        for _ in range(args.steps):
+            meter.result()
+        torch.cuda.synchronize()
+        runs['device'].append((time.perf_counter() - t0) * 1e6 / args.steps)
+    med = {k: sorted(v)[len(v) // 2] for k, v in runs.items()}
+    # the launches alone
+    ws = torch.empty((cof.average_precision_workspace_bytes(T, K),), dtype=torch.uint8, device=dev)
+    out_buf = torch.empty((cof.average_precision_result_bytes(K),), dtype=torch.uint8, device=dev)
+    kw = dict(targets=truth) if multi else dict(labels=truth)
+    ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(20)]
+    for e0, e1 in ev:
+        e0.record()
+        cof.average_precision(scores, workspace=ws, out=out_buf, **kw)
+        e1.record()
+    torch.cuda.synchronize()
+    launches = sorted(e0.elapsed_time(e1) * 1e3 for e0, e1 in ev)
+    return {'workload': 'map393: Evaluation.result() (host numpy) against DeviceEvaluation.result() (three launches), '
+                        'alternating in one process; T={} K={} {}'.format(T, K, 'multi-hot sigmoid' if multi else
+                                                                          'single-label softmax'),
+            'T': T, 'K': K, 'multi_hot': bool(multi),
+            'us_per_result': {k: round(v, 1) for k, v in med.items()},
+            'us_per_result_runs': {k: [round(x, 1) for x in v] for k, v in runs.items()},
+            'spread': {k: round((max(v) - min(v)) / med[k], 4) for k, v in runs.items()},
+            'host_over_device': round(med['host'] / med['device'], 2),
+            'three_launches_us_by_events': {'median': round(launches[len(launches) // 2], 1),
+                                            'min': round(launches[0], 1), 'max': round(launches[-1], 1)},
+            'key_bytes': int(ws.numel()), 'copy_back_bytes': int(out_buf.numel()),
+            'mAP': {'host': ref['mAP'], 'device': got['mAP'], 'abs_diff': abs(ref['mAP'] - got['mAP'])},
+            'classes_with_positives': len(got['aps'])}
+
+
 def timed(fn, steps, warmup, min_ms=50.0, repeats=5):
     """median over >= `repeats` timed loops of `steps` steps each (>= min_ms of device time in total)."""
     for _ in range(warmup):
@@ -1377,7 +1459,7 @@ def main():
                                                          'update_perclass', 'poseatt', 'video_perclass', 'video003',
                                                          'hico002', 'charades_clips', 'frozen002', 'frozen003',
                                                          'frozen_perclass', 'frozen002_fp8', 'eval002_fp8',
-                                                         'cached002_fp8', 'cached002_bf16', 'explain002'] +
+                                                         'cached002_fp8', 'cached002_bf16', 'explain002', 'map393'] +
                     sorted(EVAL_CLIPS) + sorted(RANK_WORKLOADS))
     ap.add_argument('--clips', type=int, default=8, help='video_*: clips per batch')
     ap.add_argument('--frames', type=int, default=4, help='video_*: frames per clip')
@@ -1389,6 +1471,8 @@ def main():
     ap.add_argument('--cache-images', type=int, default=2048, help='cached002_*: images in the resident cache')
     ap.add_argument('--hw', type=int, default=14)
     ap.add_argument('--classes', type=int, default=None)
+    ap.add_argument('--samples', type=int, default=None, help='map393: accumulated score rows (default 7000)')
+    ap.add_argument('--multi-hot', action='store_true', help='map393: sigmoid scores against multi-hot targets')
     ap.add_argument('--dtype', default=None, choices=['bf16', 'f32'])
     ap.add_argument('--per-op', action='store_true',
                     help='cfg003: drive the step as separate calls (pose head fwd, pose loss, attention train step, '
@@ -1434,6 +1518,9 @@ def main():
         return
     if args.workload == 'explain002':
         print(json.dumps(run_explain002(cof, dev, args)))
+        return
+    if args.workload == 'map393':
+        print(json.dumps(run_map393(cof, dev, args)))
         return
     if args.workload == 'poseatt':
         step, info, kernel_times = build_poseatt(cof, dev, args.batch, args.hw, args.classes or 393,
