@@ -383,6 +383,7 @@ int m1g_launch_bwd_main(const M1Call& c, const M1Bwd& io);
 // identity / relu, no dX -- pool_check (apa_capi.hip) refuses everything else before a call gets here
 constexpr int M1F_MAX_C = 8192;
 bool m1f_supported(int C);
+int m1f_vectors_per_lane(int C);   // NV of the instance both launchers pick for a supported C: 1 / 2 / 4 / 8
 int m1f_launch_pool_fwd(const M1Call& c, const M1Fwd& io);
 int m1f_launch_bwd_main(const M1Call& c, const M1Bwd& io);
 // the attention GEMV of a separate attention input as launches of their own (apa_m1.hip; m1_forward / m1_backward run
@@ -402,6 +403,7 @@ struct RankCall {
   float* z0; void* ws;
 };
 bool m1r_supported(int C, int Ca, int dtype, bool fused);
+int m1r_vectors_per_lane(int C, int dtype);   // NVL of the instance both passes pick: f32 2 / 8, bf16 1 / 4; 0: none serves C
 size_t m1r_workspace_bytes(int N, int P, int C, int Ca, int K, int R);
 int m1r_forward(const M1Call& c, const RankCall& rk, const M1Fwd& io);
 int m1r_backward(const M1Call& c, const RankCall& rk, const M1Bwd& io);

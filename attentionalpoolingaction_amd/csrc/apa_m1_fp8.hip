@@ -278,13 +278,20 @@ __global__ __launch_bounds__(256, blocks_per_cu(NV)) void m1f_bwd_main_kernel(
 }
 
 template <typename F> int by_nv(int C, F&& go) {
-  const int nv = (C / 16 + 63) / 64;
-  if (nv <= 1) return go(std::integral_constant<int, 1>{});
-  if (nv <= 2) return go(std::integral_constant<int, 2>{});
-  if (nv <= 4) return go(std::integral_constant<int, 4>{});
-  return go(std::integral_constant<int, 8>{});
+  switch (m1f_vectors_per_lane(C)) {
+    case 1: return go(std::integral_constant<int, 1>{});
+    case 2: return go(std::integral_constant<int, 2>{});
+    case 4: return go(std::integral_constant<int, 4>{});
+    default: return go(std::integral_constant<int, 8>{});
+  }
 }
 }  // namespace
+
+// NV of the instance that serves C: the 16-code vectors of a row over the 64 lanes, rounded up to 1 / 2 / 4 / 8
+int m1f_vectors_per_lane(int C) {
+  const int nv = (C / 16 + 63) / 64;
+  return nv <= 1 ? 1 : (nv <= 2 ? 2 : (nv <= 4 ? 4 : 8));
+}
 
 // C a whole number of 16-code vectors, at most eight per lane of the wave that owns a pixel row
 bool m1f_supported(int C) { return C >= 16 && C % 16 == 0 && C <= M1F_MAX_C; }

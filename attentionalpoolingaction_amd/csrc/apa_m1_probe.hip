@@ -37,6 +37,12 @@ int apa_probe_m1_support(int N, int C, int K, int dtype) {
          (apa::m1_small_supported(C, K) ? 16 : 0) | (apa::m1_bwd_head_supported(N, C, K) ? 32 : 0);
 }
 
+// The template instance the FP8 launchers / the rank-R launchers pick, by the functions they call themselves: NV of
+// m1f_pool_fwd_kernel / m1f_bwd_main_kernel (0: m1f_supported refuses C), NVL of m1r_pool_fwd_kernel /
+// m1r_bwd_main_kernel (0: no instance serves C).  Host only, nothing is launched.
+int apa_probe_m1f_instance(int C) { return apa::m1f_supported(C) ? apa::m1f_vectors_per_lane(C) : 0; }
+int apa_probe_m1r_instance(int C, int dtype) { return apa::m1r_vectors_per_lane(C, dtype); }
+
 // Internal flag bits (APA_IFLAG_*, apa_internal.h) added to every m1_forward this thread runs through the wrappers
 // below, until set again: APA_IFLAG_FINALIZE_LAUNCH = 1 << 27 puts the two forward sequences side by side
 // (tests/test_m1_fold_gpu.py).  The extern "C" entries mask a caller's own internal bits.

@@ -515,13 +515,6 @@ RankPlan rank_plan(int N, int P, int C, int Ca, int K, int R) {
   return rp;
 }
 
-// elements per lane of the instance that serves C (0: none)
-int rank_el(int C, int dtype) {
-  const int epv = dtype == APA_DTYPE_BF16 ? 8 : 4;
-  if (C < epv || C % epv != 0) return 0;
-  return C <= 512 ? 8 : (C <= 2048 ? 32 : 0);
-}
-
 template <typename T, int NVL>
 int launch_fwd(const M1Call& c, const RankCall& rk, const RankPlan& rp, const M1Fwd& io, const ChainPtrs& ch) {
   char* w = static_cast<char*>(rk.ws);
@@ -561,10 +554,18 @@ ChainPtrs chain_ptrs(const RankCall& rk) {
 }
 }  // namespace
 
+// NVL of the instance that serves C (0: none): 8 elements per lane up to C = 512, 32 up to C = 2048, in 16-byte
+// vectors of 4 (f32) or 8 (bf16) elements
+int m1r_vectors_per_lane(int C, int dtype) {
+  const int epv = dtype == APA_DTYPE_BF16 ? 8 : 4;
+  if (C < epv || C % epv != 0) return 0;
+  return C <= 512 ? 8 / epv : (C <= 2048 ? 32 / epv : 0);
+}
+
 bool m1r_supported(int C, int Ca, int dtype, bool fused) {
   const int epv = dtype == APA_DTYPE_BF16 ? 8 : 4;
   if (!fused && (Ca < epv || Ca % epv != 0)) return false;
-  return rank_el(C, dtype) != 0;
+  return m1r_vectors_per_lane(C, dtype) != 0;
 }
 
 size_t m1r_workspace_bytes(int N, int P, int C, int Ca, int K, int R) { return rank_plan(N, P, C, Ca, K, R).total; }
@@ -585,11 +586,11 @@ int m1r_forward(const M1Call& c, const RankCall& rk, const M1Fwd& io) {
     f0.att = rk.z0;
     if ((rc = m1_att_gemv_forward(c0, f0)) != APA_OK) return rc;
   }
-  const int el = rank_el(C, c.dtype);
+  const int nvl = m1r_vectors_per_lane(C, c.dtype);
   if (c.dtype == APA_DTYPE_F32)
-    rc = el == 8 ? launch_fwd<float, 2>(c, rk, rp, io, ch) : launch_fwd<float, 8>(c, rk, rp, io, ch);
+    rc = nvl == 2 ? launch_fwd<float, 2>(c, rk, rp, io, ch) : launch_fwd<float, 8>(c, rk, rp, io, ch);
   else
-    rc = el == 8 ? launch_fwd<bf16_t, 1>(c, rk, rp, io, ch) : launch_fwd<bf16_t, 4>(c, rk, rp, io, ch);
+    rc = nvl == 1 ? launch_fwd<bf16_t, 1>(c, rk, rp, io, ch) : launch_fwd<bf16_t, 4>(c, rk, rp, io, ch);
   if (rc != APA_OK) return rc;
   APA_LAUNCH_CHECK("m1r_pool_fwd_kernel");
   hipLaunchKernelGGL(m1r_finalize_fwd_kernel, dim3(N, (R * C / 4 + 255) / 256), dim3(256), 0, c.st,
@@ -651,12 +652,12 @@ int m1r_backward(const M1Call& c, const RankCall& rk, const M1Bwd& io) {
       if (rc != APA_OK) return rc;
     }
   }
-  const int el = rank_el(C, c.dtype);
+  const int nvl = m1r_vectors_per_lane(C, c.dtype);
   const float* snp = small ? sn : nullptr;
   if (c.dtype == APA_DTYPE_F32)
-    rc = el == 8 ? launch_bwd<float, 2>(c, rk, rp, io, ch, snp) : launch_bwd<float, 8>(c, rk, rp, io, ch, snp);
+    rc = nvl == 2 ? launch_bwd<float, 2>(c, rk, rp, io, ch, snp) : launch_bwd<float, 8>(c, rk, rp, io, ch, snp);
   else
-    rc = el == 8 ? launch_bwd<bf16_t, 1>(c, rk, rp, io, ch, snp) : launch_bwd<bf16_t, 4>(c, rk, rp, io, ch, snp);
+    rc = nvl == 1 ? launch_bwd<bf16_t, 1>(c, rk, rp, io, ch, snp) : launch_bwd<bf16_t, 4>(c, rk, rp, io, ch, snp);
   if (rc != APA_OK) return rc;
   APA_LAUNCH_CHECK("m1r_bwd_main_kernel");
   FinishArgs fa;

@@ -1,6 +1,7 @@
 """ctypes glue for the M == 1 half of the test-only probe library (csrc/apa_m1_probe.hip, linked into
 libapa_gemm_probe.so): the product's attentional-pooling entry points run with a host-side dispatch trace
-(apa_internal.h M1Trace), the plan and support helpers, and the float64 error model that
+(apa_internal.h M1Trace), the plan and support helpers, the template instance the FP8 and the rank-R launchers pick for a
+width (fp8_instance / rank_instance: the functions those launchers call), and the float64 error model that
 tests/test_m1_paths_gpu.py compares the kernels with.
 
 Error model (elementwise; `Bnd` carries a float64 reference and an absolute bound side by side):
@@ -29,12 +30,13 @@ EPS32 = 2.0 ** -24
 U_BF16 = 2.0 ** -8
 
 M1_PROBE_VERSION = 1
-M1_SYMBOLS = ('apa_probe_m1_version', 'apa_probe_m1_trace_size', 'apa_probe_m1_plan', 'apa_probe_m1_support', 'apa_probe_m1_fwd_ex',
+M1_SYMBOLS = ('apa_probe_m1_version', 'apa_probe_m1_trace_size', 'apa_probe_m1_plan', 'apa_probe_m1_support',
+              'apa_probe_m1f_instance', 'apa_probe_m1r_instance', 'apa_probe_m1_fwd_ex',
               'apa_probe_m1_bwd_ex', 'apa_probe_m1_fwd_cat', 'apa_probe_m1_bwd_cat', 'apa_probe_m1_train_step_ex',
               'apa_probe_m1_eval_step')
 
 # M1Trace enum values (csrc/apa_internal.h)
-POOLS = {0: 'none', 1: 'stream', 2: 'vec', 3: 'generic'}
+POOLS = {0: 'none', 1: 'stream', 2: 'vec', 3: 'generic', 4: 'fp8'}
 LOGITS = {0: 'none', 1: 'xent', 2: 'xent_probs', 3: 'logits2', 5: 'sgemm'}   # (4: the retired partial-logits form)
 HEADS = {0: 'none', 1: 'tiles', 2: 'rows', 3: 'small', 4: 'sgemm'}
 GEMVS = {0: 'none', 1: 'bwd2', 2: 'bwd2_rank1', 3: 'bwd'}
@@ -85,6 +87,8 @@ def load_m1_probe():
         lib.apa_probe_m1_plan.argtypes = [ctypes.c_int] * 5 + [ctypes.c_void_p]
         lib.apa_probe_m1_plan.restype = None
         lib.apa_probe_m1_support.argtypes = [ctypes.c_int] * 4
+        lib.apa_probe_m1f_instance.argtypes = [ctypes.c_int]
+        lib.apa_probe_m1r_instance.argtypes = [ctypes.c_int] * 2
         for probe, prod in (('apa_probe_m1_fwd_ex', 'apa_attn_pool_fwd_ex'),
                             ('apa_probe_m1_bwd_ex', 'apa_attn_pool_bwd_ex'),
                             ('apa_probe_m1_fwd_cat', 'apa_attn_pool_fwd_cat'),
@@ -108,6 +112,16 @@ def plan(N, P, C, Ca, K):
 
 def support(N, C, K, dtype):
     return int(load_m1_probe().apa_probe_m1_support(N, C, K, dtype))
+
+
+def fp8_instance(C):
+    """NV of the FP8 streaming kernels' instance for C, from the function their launchers call (0: C is refused)."""
+    return int(load_m1_probe().apa_probe_m1f_instance(C))
+
+
+def rank_instance(C, dtype):
+    """NVL of the rank-R kernels' instance for (C, dtype), from the function their launchers call (0: none)."""
+    return int(load_m1_probe().apa_probe_m1r_instance(C, dtype))
 
 
 # ------------------------------------------------------------------------------------------ error model

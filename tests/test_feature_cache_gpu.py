@@ -7,7 +7,9 @@ trace), fp32 / bf16 / FP8, identity and ReLU, evaluation and training, both head
 kernels: one gathered training step per dtype against the float64 error model of tests/test_m1_paths_gpu.py, and
 deploy.FusedHeadStep / FusedHeadEval on a CachedBatch against the float64 oracle on the cfg 002 reference fixtures.
 
-Cache: T = 7 images; batches index = [6, 0, 6, 3, 1] (a repeated id, unordered, the cache's last image) and N = 1."""
+Cache: T = 7 images; batches index = [6, 0, 6, 3, 1] (a repeated id, unordered, the cache's last image) and N = 1, whose
+blocks hold 4 - 5 pixels; and indices of length 342 and 171 (S = 1 and S = 3: 16 - 33 pixels per block), so that the
+long-block loops of the stream / vec / generic kernels run through the index as well."""
 import ctypes
 import os
 
@@ -221,6 +223,47 @@ def test_gathered_calls_equal_the_calls_on_a_gathered_copy(gpu, combo, P):
     torch.cuda.synchronize()
     assert torch.equal(cache.features.buffer if cache.fp8 else cache.features, before)
     assert int(cache.status) == 0
+
+
+# ------------------------------------------------------------------------------------------ long blocks through the index
+LONG = [(342, 33), (171, 49)]       # (N, P): m1_plan's S = 1 (33 pixels per block) and S = 3 (blocks of 16 / 16 / 17)
+
+
+def _long_index(N):
+    """N ids into the T-image cache: INDEX first (a repeated id, unordered, the cache's last image), then seeded draws"""
+    g = torch.Generator().manual_seed(31 + N)
+    idx = torch.randint(0, T, (N,), generator=g)
+    idx[:len(INDEX)] = torch.tensor(INDEX)
+    assert set(idx.tolist()) == set(range(T))
+    return idx.tolist()
+
+
+@pytest.mark.parametrize('N,P', LONG, ids=['n342_p33_S1', 'n171_p49_S3'])
+@pytest.mark.parametrize('combo', [c for c in COMBOS if c[0] != POOL_FP8], ids=_combo_id)
+def test_gathered_long_blocks_equal_the_calls_on_a_gathered_copy(gpu, combo, N, P):
+    """The batches above give blocks of 4 - 5 pixels, a wave one or two of them; here a block holds 16 - 33, so the
+    pixel loops of the stream / vec / generic kernels run their steady state with the image behind the index (the FP8
+    family: tests/test_fp8_instances_gpu.py).  Bit comparison only -- the plain kernels have their float64 tests at
+    long blocks in tests/test_m1_paths_gpu.py."""
+    family, dtype, C = combo
+    K = 20
+    S, ppb = mp.plan(N, P, C, C, K)[:2]
+    assert (S, ppb) == {33: (1, 33), 49: (3, 17)}[P]
+    cache = _cache(dtype, P, C, gpu)
+    before = cache.features.clone()
+    index = _long_index(N)
+    batch, copy = cache.select(index), cache.gather(index)
+    G = ((torch.rand(N, K, generator=torch.Generator().manual_seed(N + K)) * 1.25 - 0.25) / N).to(gpu)
+    for act in ('id', 'relu'):
+        p = _params(C, K, act, cache, gpu)
+        for train in (False, True):
+            flags = _flags(act, train)
+            what = '%s N=%d P=%d %s %s' % (_combo_id(combo), N, P, act, 'train' if train else 'eval')
+            ref = _separate(copy, p, G, flags)
+            _same(_separate(batch, p, G, flags), ref, what)
+            assert _traced_families(batch, p, G, flags, ref) == (family, family), what
+    torch.cuda.synchronize()
+    assert torch.equal(cache.features, before) and int(cache.status) == 0
 
 
 def test_device_counter_advances_once_per_step_in_both(gpu):

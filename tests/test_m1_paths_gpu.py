@@ -314,14 +314,19 @@ class _Run:
 
 # ------------------------------------------------------------------------------------------ references
 def _forward_ref(c, inp, keepmask):
-    """Bnd att, zsave, abar, logits (+ zext), and the relu-ambiguous pixels, from the inputs alone."""
+    """Bnd att, zsave, abar, logits (+ zext), and the relu-ambiguous pixels, from the inputs alone.  The contractions
+    over the channels and over the pixels are taken as Ca and P additions long; a case may state the kernel's own
+    longest chains instead (c['chains']: 'dot' for a pixel's channel contraction, 'pool' for the pooled sums over the
+    pixels, 'logits' for the logits' channel contraction -- tests/_fp8_cases.py derives them), never longer ones."""
     N, P, C, K, J = c['N'], c['P'], c['C'], c['K'], c['J']
     X = inp['X'].double()
     if c['relu_in']:
         X = X.clamp_min(0)
     Xa = X if c['Ca'] is None else inp['Xatt'].double()
     Ca = Xa.shape[-1]
-    zl = contract('npc,c->np', Bnd(Xa), Bnd(inp['Wa'].double()), Ca) + Bnd(inp['ba'].double().expand(N, P))
+    chains = c.get('chains') or {}
+    Ldot, Lpool, Llog = min(chains.get('dot', Ca), Ca), min(chains.get('pool', P), P), min(chains.get('logits', C), C)
+    zl =contract('npc,c->np', Bnd(Xa), Bnd(inp['Wa'].double()), Ldot) + Bnd(inp['ba'].double().expand(N, P))
     amb = None
     if c['act'] == 'softmax':
         A = mp.softmax_p(zl)
@@ -331,11 +336,11 @@ def _forward_ref(c, inp, keepmask):
     else:
         A = zl
     Xt, Xe = _dropped(c, inp, X, keepmask)
-    zs = contract('np,npc->nc', A, Xt, P).scale(1.0 / P)
+    zs = contract('np,npc->nc', A, Xt, Lpool).scale(1.0 / P)
     ones = Bnd(torch.ones(P, dtype=torch.float64, device=X.device))
-    ab = contract('np,p->n', A, ones, P).scale(1.0 / P)
+    ab = contract('np,p->n', A, ones, Lpool).scale(1.0 / P)
     Wt = inp['Wt'].double()
-    lg = contract('nc,ck->nk', zs, Bnd(Wt[:C]), C) + Bnd(ab.ref[:, None], ab.err[:, None]).mul(
+    lg = contract('nc,ck->nk', zs, Bnd(Wt[:C]), Llog) + Bnd(ab.ref[:, None], ab.err[:, None]).mul(
         Bnd(inp['bt'].double()[None, :]))
     ze = None
     if J:
@@ -359,7 +364,7 @@ def _dropped(c, inp, X, keepmask):
 
 def _backward_ref(c, inp, got, keepmask):
     """Bnd dX, dXatt, dWa, dba, dWt, dbt (+ dXext) from the kernel's own att, zsave, abar, zext and G (every
-    backward kernel reads `att`, so a relu gate is att > 0 exactly)."""
+    backward kernel reads `att`, so a relu gate is att > 0 exactly).  c['chains']['dot']: as in _forward_ref."""
     N, P, C, K, J = c['N'], c['P'], c['C'], c['K'], c['J']
     X = inp['X'].double()
     Xr = X.clamp_min(0) if c['relu_in'] else X
@@ -377,7 +382,8 @@ def _backward_ref(c, inp, got, keepmask):
     out['dWt'] = contract('nc,nk->ck', zs, G, N)
     out['dbt'] = contract('n,nk->k', ab, G, N)
     sn = contract('nk,k->n', G, Bnd(inp['bt'].double()), K)
-    dA = contract('npc,nc->np', Xt, dz, C) + Bnd(sn.ref[:, None].expand(N, P), sn.err[:, None].expand(N, P))
+    dA = contract('npc,nc->np', Xt, dz, min((c.get('chains') or {}).get('dot', C), C)) + \
+        Bnd(sn.ref[:, None].expand(N, P), sn.err[:, None].expand(N, P))
     if J:
         ze = Bnd(got['zext'].double().reshape(N, J))
         out['dWt_ext'] = contract('nj,nk->jk', ze, G, N)

@@ -1,7 +1,10 @@
 """Rank > 1 on one bottom-up map as one op (include/apa.h: apa_rank_maps), the parts that need no GPU: the float64
 reference of tests/_rank_reference.py against the oracle and the two reference-executed rank fixtures, the new entry
 points declared / exported / bound and refusing bad arguments before anything touches a device, the surface of
-deploy.FusedHeadStep and get_network_fn(..., fuse_ranks=True), and the gate condition of the GPU case table."""
+deploy.FusedHeadStep and get_network_fn(..., fuse_ranks=True), and of the GPU case table (tests/_rank_reference.CASES)
+its gate condition and its reach table: every instance of the two rank kernels, the ragged wide instances, the separate
+attention input, every backward and forward product and every kind of split has a case, by the dispatch's own
+functions (apa_probe_m1r_instance, apa_probe_m1_plan, apa_probe_m1_support)."""
 import ctypes
 import os
 import re
@@ -319,3 +322,30 @@ def test_gpu_case_inputs_meet_the_gate_condition(c):
     excl, opn = rr.check_gate_condition(c, amb, opened)
     if c['b2'] is not None:
         assert opn[2] == 0.0 and 0.10 <= opn[0] <= 0.90 and 0.10 <= opn[1] <= 0.90
+
+
+def test_gpu_case_table_reaches_every_key():
+    """tests/_rank_reference.REQUIRED: the 16 instances per pass (element type, NVL) x FUSED x TRAIN, C = 516 / 520 with
+    a single vector in the last lane row of the wide instances, a separate attention input on a wide instance, on
+    bf16, narrower and wider than a lane row, R = 4 on a wide instance, the three backward and two forward products, a
+    wave without a pixel, P % S != 0, and S = 1 with more than 8 pixels per wave."""
+    from tests import _m1_probe as mp
+    F32, BF16 = cof.APA_DTYPE_F32, cof.APA_DTYPE_BF16
+    # the probe names the launchers' choice: m1r_vectors_per_lane
+    for C, want in ((4, 2), (512, 2), (516, 8), (2048, 8), (2052, 0), (6, 0), (0, 0)):
+        assert mp.rank_instance(C, F32) == want, C
+    for C, want in ((8, 1), (512, 1), (520, 4), (2048, 4), (2056, 0), (516, 0), (4, 0)):
+        assert mp.rank_instance(C, BF16) == want, C
+    table = rr.reach_table()
+    missing = rr.REQUIRED - set(table)
+    assert not missing, sorted(missing, key=str)
+    assert len({k for k in table if k[0] == 'instance'}) == 16
+    names = [c['name'] for c in rr.CASES]
+    assert len(names) == len(set(names))
+    by = {c['name']: c for c in rr.CASES}
+    assert {by[n]['C'] for n in table[('lanes', 'f32', 'ragged')]} >= {516}
+    assert {by[n]['C'] for n in table[('lanes', 'bf16', 'ragged')]} == {520}
+    # a key held by one case alone is lost with it
+    for key in (('instance', 'bf16', 4, False, False), ('split', 'P < 4'), ('backward', 'sgemm, C >= 1024')):
+        (only,) = table[key]
+        assert key not in rr.reach_table([c for c in rr.CASES if c['name'] != only])

@@ -1,6 +1,7 @@
 """Rank > 1 on one bottom-up map in one streaming pass (csrc/apa_m1_rank.hip; include/apa.h: apa_rank_maps) on the GPU.
 
-Every case of tests/_rank_reference.CASES runs the forward and the backward entry point twice -- the two runs must
+Every case of tests/_rank_reference.CASES (its reach table -- every instance, product and split of the two kernels --
+is asserted by tests/test_rank_maps_cpu.py) runs the forward and the backward entry point twice -- the two runs must
 repeat bit for bit -- with every output and the workspace inside NaN-guarded allocations, and is compared with the
 float64 formulas in the error model of tests/_m1_probe.py: the forward outputs from the inputs, the logits and the
 backward from the kernel's own forward outputs.  Then: the one-call step against the three separate calls (bits) and
@@ -133,6 +134,30 @@ def _same_bits(a, b, what):
         assert torch.equal(a[k], b[k]), '{}: {} differs'.format(what, k)
 
 
+def _ratio(got, b, bf16=False):
+    """largest |got - ref| / tolerance over the elements with a tolerance above zero"""
+    err = (got.double().reshape(b.ref.shape) - b.ref).abs()
+    tol = mp.tolerance(b, bf16)
+    ok = tol > 0
+    return float((err[ok] / tol[ok]).max()) if bool(ok.any()) else 0.0
+
+
+def _print_ratios(c, got, fref, lg, bref):
+    """the figures of profiles/fp8_rank_instances_summary.md, printed before anything is asserted"""
+    bf, R = c['bf16'], c['R']
+    out = {k: _ratio(got[k], fref[k]) for k in ('z0', 'att', 'zsave', 'abar')}
+    out['logits'] = _ratio(got['logits'], lg)
+    out['dX'] = _ratio(got['dX'], bref['dX'], bf)
+    if c['Ca'] is not None:
+        out['dXatt'] = _ratio(got['dXatt'], bref['dXatt'], bf)
+    out['dWa'], out['dba'] = _ratio(got['dWa'], bref['dWa']), _ratio(got['dba'], bref['dba'])
+    out['dWt'] = max(_ratio(got['dWt%d' % r], bref['dWts'][r]) for r in range(R))
+    out['dbt'] = max(_ratio(got['dbt%d' % r], bref['dbts'][r]) for r in range(R))
+    out['dcw'] = max(_ratio(got['dcw%d' % r], bref['dcw'][r]) for r in range(R - 1))
+    out['dcb'] = max(_ratio(got['dcb%d' % r], bref['dcb'][r]) for r in range(R - 1))
+    print('RANKRATIO {} {}'.format(c['name'], ' '.join('{}={:.4f}'.format(k, v) for k, v in out.items())))
+
+
 def _check_backward(c, got, ref):
     bf = c['bf16']
     R = c['R']
@@ -174,6 +199,8 @@ def test_rank_case(gpu, c):
         fref, amb, opened = rr.forward_bnd(c, inp, r.mask)
         if amb is not None:
             rr.check_gate_condition(c, amb, opened)
+        _print_ratios(c, got, fref, rr.logits_bnd(c, inp, rr.parts_of(c, inp, got)),
+                      rr.backward_bnd(c, inp, rr.parts_of(c, inp, got), got['G'], r.mask, _plan(c)))
         mp.check(got['z0'], fref['z0'], 'z0')
         mp.check(got['att'], fref['att'], 'att', ambiguous=amb)
         closed = c['b2'] is not None
