@@ -1093,6 +1093,67 @@ extern "C" int apa_attn_head_eval_step_cached(const apa_feature_cache* cache, co
                               loss, probs, pred);
 }
 
+// ---- clips and the sigmoid losses from a frame cache (apa.h: the *_cached_clips steps) --------------------------------
+// labels_cached reads a per-FRAME table through the index; a clip's or a sigmoid row's labels are per clip / per row
+static int cached_clip_labels_check(const char* fn, const apa_feature_cache* fc, bool ml, bool clip) {
+  if (!fc->labels_cached || (!ml && !clip)) return APA_OK;
+  set_error("%s: apa_feature_cache.labels_cached = 1 is not served together with %s: such labels are per clip or per "
+            "row and come from the sampler (apa_sample_clip_frames), not through the frame index", fn,
+            ml ? "an apa_multilabel" : "an apa_clip_pool");
+  return APA_ERR_INVALID_ARG;
+}
+
+// ml == NULL && clip == NULL: apa_attn_head_train_step_cached itself
+extern "C" int apa_attn_head_train_step_cached_clips(const apa_feature_cache* cache, const apa_multilabel* ml,
+                                                     const apa_clip_pool* clip, const apa_hooks* hooks, const void* X,
+                                                     const void* Xatt, const float* Wa, const float* ba,
+                                                     const float* Wt, const float* bt, const int64_t* labels,
+                                                     float loss_wt, float grad_scale, float* logits, float* att,
+                                                     float* zsave, float* abar, float* loss, float* G, void* dX,
+                                                     void* dXatt, float* dWa, float* dba, float* dWt, float* dbt,
+                                                     void* ws, size_t ws_bytes, int N, int P, int C, int Ca, int K,
+                                                     int M, unsigned flags, float keep_prob, uint64_t seed,
+                                                     uint64_t offset, int dtype, void* stream) {
+  if (!ml && !clip)
+    return apa_attn_head_train_step_cached(cache, hooks, X, Xatt, Wa, ba, Wt, bt, labels, loss_wt, grad_scale, logits,
+                                           att, zsave, abar, loss, G, dX, dXatt, dWa, dba, dWt, dbt, ws, ws_bytes, N, P,
+                                           C, Ca, K, M, flags, keep_prob, seed, offset, dtype, stream);
+  const char* fn = "apa_attn_head_train_step_cached_clips";
+  PoolCall d = fp8_served(pool_call({N, P, C, Ca, K, M, dtype}, flags, keep_prob, seed, offset, ws, ws_bytes, stream,
+                                    hooks));
+  int rc = cache_check(fn, cache, d, X, Xatt, false, true, dX);
+  if (rc != APA_OK) return rc;
+  if (ml && (rc = check_multilabel(fn, ml)) != APA_OK) return rc;
+  if ((rc = cached_clip_labels_check(fn, cache, ml != nullptr, clip != nullptr)) != APA_OK) return rc;
+  d.fc = cache;
+  return head_step(fn, d, StepLoss{ml, ml ? nullptr : labels, clip != nullptr, clip, loss_wt, grad_scale, loss, G},
+                   M1Fwd{X, Xatt, Wa, ba, Wt, bt, logits, att, zsave, abar},
+                   M1Bwd{X, Xatt, Wa, Wt, bt, att, zsave, abar, G, dX, dXatt, dWa, dba, dWt, dbt});
+}
+
+// clip == NULL: apa_attn_head_eval_step_cached itself
+extern "C" int apa_attn_head_eval_step_cached_clips(const apa_feature_cache* cache, const apa_clip_pool* clip,
+                                                    int scores_kind, const void* X, const void* Xatt, const float* Wa,
+                                                    const float* ba, const float* Wt, const float* bt,
+                                                    const int64_t* labels, float* logits, float* att, float* zsave,
+                                                    float* abar, float* loss, float* probs, int64_t* pred, void* ws,
+                                                    size_t ws_bytes, int N, int P, int C, int Ca, int K, int M,
+                                                    unsigned flags, int dtype, void* stream) {
+  if (!clip)
+    return apa_attn_head_eval_step_cached(cache, nullptr, scores_kind, X, Xatt, Wa, ba, Wt, bt, labels, logits, att,
+                                          zsave, abar, loss, probs, pred, ws, ws_bytes, N, P, C, Ca, K, M, flags, dtype,
+                                          stream);
+  const char* fn = "apa_attn_head_eval_step_cached_clips";
+  PoolCall d = fp8_served(pool_call({N, P, C, Ca, K, M, dtype}, flags, 1.0f, 0, 0, ws, ws_bytes, stream));
+  int rc = cache_check(fn, cache, d, X, Xatt, false, false, nullptr);
+  if (rc != APA_OK) return rc;
+  if ((rc = cached_clip_labels_check(fn, cache, false, true)) != APA_OK) return rc;
+  if ((rc = eval_scores_check(fn, clip, scores_kind, N, K, logits, labels, loss, probs, pred)) != APA_OK) return rc;
+  d.fc = cache;
+  return attn_head_eval_clips(fn, clip, scores_kind, d, M1Fwd{X, Xatt, Wa, ba, Wt, bt, logits, att, zsave, abar},
+                              labels, loss, probs, pred);
+}
+
 // workspace of apa_pose_attn_eval_step: [pose head | pooling (+ the label-free loss scratch) | column-tile partials]
 struct PoseEvalCarve { size_t pose, pool, zpart, total; };
 static PoseEvalCarve pose_eval_carve(int N, int P, int C, int Cp, int J, int K, unsigned flags, int dtype) {

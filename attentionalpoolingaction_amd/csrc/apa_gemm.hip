@@ -66,6 +66,13 @@ __device__ __forceinline__ float keep1(uint64_t e, uint32_t k0, uint32_t k1, uin
   return (e & 1) ? m1 : m0;
 }
 
+// keep1 for an element index that may lie past the mask (a tile's zero fill): with an external keep-bit image of
+// `nbits` bits the index is held inside it; the counter hash takes any index
+__device__ __forceinline__ float keep1_in(uint64_t e, uint64_t nbits, uint32_t k0, uint32_t k1, uint32_t thresh) {
+  if (thresh == RNG_THRESH_EXTERNAL) e = e < nbits ? e : nbits - 1;
+  return keep1(e, k0, k1, thresh);
+}
+
 // Stage one 128 x 32 operand tile into registers (as fp32 values).  rows: r0.., k: k0..
 // KC: element (r,k) at base[r*ld + k]; else at base[k*ld + r].
 template <typename T, bool KC>
@@ -105,7 +112,11 @@ struct Stager {
   // dropout on the staged elements of the [N*P, C] feature map.  Flat element index:
   //   trans == false : operand(row, k) = X[row, k]  -> row * ld_idx + k   (ld_idx = K = C)
   //   trans == true  : operand(row, k) = X[k, row]  -> k * ld_idx + row   (ld_idx = M = C)
-  __device__ __forceinline__ void dropout(int r0, int k0, int ld_idx, bool trans, float inv_keep,
+  // A tile reaches past the matrix (rows beyond M, k beyond K): those elements are load()'s zero fill and their
+  // keep value is immaterial.  The counter hash may be asked for them; an external keep-bit image holds `nbits` =
+  // M * K bits and none for them -- a 128-row tile of an 18-row map would read 16 * C bytes past it -- so there
+  // (keep1_in) the element index is held inside the image.
+  __device__ __forceinline__ void dropout(int r0, int k0, int ld_idx, bool trans, uint64_t nbits, float inv_keep,
                                           uint32_t thresh, uint32_t h0, uint32_t h1, int tid) {
 #pragma unroll
     for (int i = 0; i < NV; ++i) {
@@ -117,7 +128,7 @@ struct Stager {
       for (int j = 0; j < VL; ++j) {
         const int rr = r0 + (KC ? r : r + j), kk = k0 + (KC ? k + j : k);
         const uint64_t e = trans ? (uint64_t)kk * ld_idx + rr : (uint64_t)rr * ld_idx + kk;
-        v[i * VL + j] *= keep1(e, h0, h1, thresh) * inv_keep;
+        v[i * VL + j] *= keep1_in(e, nbits, h0, h1, thresh) * inv_keep;
       }
     }
   }
@@ -197,7 +208,7 @@ __global__ __launch_bounds__(256) void gemm128_kernel(GemmParams p) {
     sa.load(A, p.lda, m0, p.M, kbeg, kend, p.a_vec, tid);
     sb.load(B, p.ldb, n0, p.N, kbeg, kend, p.b_vec, tid);
     if (p.drop_a)
-      sa.dropout(m0, kbeg, p.drop_a == 2 ? p.M : p.K, p.drop_a == 2, p.inv_keep, p.thresh, h0, h1, tid);
+      sa.dropout(m0, kbeg, p.drop_a == 2 ? p.M : p.K, p.drop_a == 2, (uint64_t)p.M * p.K, p.inv_keep, p.thresh, h0, h1, tid);
     sa.template store<BF16>(As(0), tid);
     sb.template store<BF16>(Bs(0), tid);
   }
@@ -247,8 +258,8 @@ __global__ __launch_bounds__(256) void gemm128_kernel(GemmParams p) {
     }
     if (more) {
       if (p.drop_a)
-        sa.dropout(m0, kbeg + (t + 1) * GK, p.drop_a == 2 ? p.M : p.K, p.drop_a == 2, p.inv_keep,
-                   p.thresh, h0, h1, tid);
+        sa.dropout(m0, kbeg + (t + 1) * GK, p.drop_a == 2 ? p.M : p.K, p.drop_a == 2, (uint64_t)p.M * p.K,
+                   p.inv_keep, p.thresh, h0, h1, tid);
       if (NBUF == 1) __syncthreads();  // everyone is done reading the only buffer
       sa.template store<BF16>(As(cur ^ 1), tid);
       sb.template store<BF16>(Bs(cur ^ 1), tid);

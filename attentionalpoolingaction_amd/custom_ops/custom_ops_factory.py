@@ -42,6 +42,9 @@ APA_POSE_NO_DX = 4
 APA_ERR_UNSUPPORTED = -2
 APA_SCORES_SOFTMAX = 0   # eval.py:197
 APA_SCORES_SIGMOID = 1   # eval.py:194-195 (TRAIN.LOSS_FN_ACTION starts with 'multi-label')
+APA_CLIP_FRAMES_UNIFORM = 0          # apa_sample_clip_frames: frame i = min(step * i, n - 1)
+APA_CLIP_FRAMES_RANDOM_SEGMENT = 1   # one draw inside each of the F segments
+CLIP_FRAME_MODES = {'uniform': APA_CLIP_FRAMES_UNIFORM, 'random-segment': APA_CLIP_FRAMES_RANDOM_SEGMENT}
 APA_WIMG_MAX = 12
 APA_RANK_MAX = 4         # attention maps chained from one bottom-up map (apa_rank_maps)
 APA_EXPLAIN_MAX_CLASSES = 8   # classes per image of one apa_attn_explain call
@@ -80,6 +83,14 @@ _SIGNATURES = {
                                        [c_uint, c_int, c_void_p]),
     'apa_quantize_features_fp8_at': (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int,
                                              c_void_p]),
+    # clips / sigmoid losses from a frame cache: (cache, ml or NULL, clip or NULL, hooks), then the arguments of
+    # apa_attn_head_train_step_cached from X on; (cache, clip or NULL, kind), then those of the evaluation step
+    'apa_attn_head_train_step_cached_clips': (c_int, [c_void_p] * 11 + [c_float, c_float] + [c_void_p] * 13 +
+                                              [c_size_t] + [c_int] * 6 + [c_uint, c_float, c_uint64, c_uint64, c_int,
+                                                                          c_void_p]),
+    'apa_attn_head_eval_step_cached_clips': (c_int, [c_void_p, c_void_p, c_int] + [c_void_p] * 15 + [c_size_t] +
+                                             [c_int] * 6 + [c_uint, c_int, c_void_p]),
+    'apa_sample_clip_frames': (c_int, [c_void_p] * 10 + [c_int] * 5 + [c_void_p]),
     'apa_pose_head_workspace_bytes': (c_size_t, [c_int] * 6),
     'apa_pose_head_fwd': (c_int, [c_void_p] * 8 + [c_size_t] + [c_int] * 6 + [c_void_p]),
     'apa_pose_head_bwd': (c_int, [c_void_p] * 7 + [c_int] + [c_void_p] * 5 + [c_size_t] + [c_int] * 6 +
@@ -458,6 +469,8 @@ class FeatureCache(object):
             raise ApaError('FeatureCache: labels int64 [{}] on the cache\'s device expected'.format(self.T))
         self.labels = labels
         self.status = torch.zeros((1,), dtype=torch.int32, device=self.device)
+        self.V, self.video_first, self.video_frames = 0, None, None     # set_videos
+        self.video_labels, self.video_targets = None, None
 
     fp8 = property(lambda self: isinstance(self.features, Fp8Features))
     dtype = property(lambda self: self.features.dtype)
@@ -525,6 +538,95 @@ class FeatureCache(object):
         for a in range(0, end, batch_size):
             yield perm[a:min(a + batch_size, end)]
 
+    # ---- a cache of video FRAMES: clips sampled on the device (include/apa.h: apa_sample_clip_frames) ----
+    def set_videos(self, first, count, labels: Optional[torch.Tensor] = None,
+                   targets: Optional[torch.Tensor] = None) -> None:
+        """The cache holds the frames of V videos: video v owns the slots [first[v], first[v] + count[v]).  `labels`
+        int64 [V] and / or `targets` float32 multi-hot [V,K] (on the cache's device) are what `sample_clips` hands out
+        per clip.  Validated once, here, on the host: count >= 1, first >= 0, first + count <= T, shapes, devices."""
+        who = 'FeatureCache.set_videos'
+        f = first.detach().cpu() if isinstance(first, torch.Tensor) else torch.as_tensor(list(first))
+        c = count.detach().cpu() if isinstance(count, torch.Tensor) else torch.as_tensor(list(count))
+        if f.dim() != 1 or c.dim() != 1 or f.numel() < 1 or f.numel() != c.numel() or \
+                f.dtype.is_floating_point or c.dtype.is_floating_point or f.dtype == torch.bool or c.dtype == torch.bool:
+            raise ApaError('{}: first and count are integer vectors of one length V >= 1'.format(who))
+        f, c = f.long(), c.long()
+        if int(c.min()) < 1:
+            raise ApaError('{}: every video has at least one frame (count >= 1)'.format(who))
+        if int(f.min()) < 0 or int((f + c).max()) > self.T:
+            raise ApaError('{}: every video lies inside the cache: 0 <= first, first + count <= {}'.format(who, self.T))
+        V = int(f.numel())
+        if labels is not None and (labels.dtype != torch.int64 or tuple(labels.shape) != (V,) or
+                                   labels.device != self.device or not labels.is_contiguous()):
+            raise ApaError('{}: labels int64 [{}] on the cache\'s device expected'.format(who, V))
+        if targets is not None and (targets.dtype != torch.float32 or targets.dim() != 2 or targets.shape[0] != V or
+                                    targets.shape[1] < 1 or targets.device != self.device or
+                                    not targets.is_contiguous()):
+            raise ApaError('{}: targets float32 [{}, K] on the cache\'s device expected'.format(who, V))
+        self.V = V
+        self.video_first = f.to(device=self.device, dtype=torch.int32).contiguous()
+        self.video_frames = c.to(device=self.device, dtype=torch.int32).contiguous()
+        self.video_labels, self.video_targets = labels, targets
+
+    def sample_clips(self, videos, frames: int, mode: str = 'uniform', u: Optional[torch.Tensor] = None,
+                     generator: Optional[torch.Generator] = None, out: Optional['CachedClips'] = None) -> 'CachedClips':
+        """B clips of `frames` frames each, one per entry of `videos` (ids into set_videos' tables; int32 on the cache's
+        device passes uncopied), as a CachedClips: the batch's frame index and the clips' labels / targets, written by
+        ONE launch (apa_sample_clip_frames; no host synchronisation).  mode 'uniform': the reference's evenly spaced
+        frames; 'random-segment': one frame inside each of the F segments, from the uniform draws `u` float32 [B*frames]
+        in [0,1) -- given, or drawn here from `generator` (torch.rand on the cache's device).  `out`: a previous
+        CachedClips of the same B and `frames` whose buffers are rewritten in place -- a step bound to it needs no
+        rebind.  A video id outside [0,V) is clamped and counted in the cache's `status`."""
+        who = 'FeatureCache.sample_clips'
+        if self.video_first is None:
+            raise ApaError('{}: set_videos first'.format(who))
+        if mode not in CLIP_FRAME_MODES:
+            raise ApaError('{}: mode must be one of {} (got {!r})'.format(who, tuple(CLIP_FRAME_MODES), mode))
+        F = int(frames)
+        if F < 1:
+            raise ApaError('{}: frames >= 1 expected'.format(who))
+        vid = _index_tensor(who, videos, self.device)
+        B = int(vid.numel())
+        if B * F > 2 ** 31 - 1:
+            raise ApaError('{}: B * frames past 2^31 - 1'.format(who))
+        if u is not None and (u.dtype != torch.float32 or u.numel() != B * F or u.device != self.device or
+                              not u.is_contiguous()):
+            raise ApaError('{}: u float32 [{}] on the cache\'s device expected'.format(who, B * F))
+        if out is not None and (not isinstance(out, CachedClips) or out.cache is not self or out.frames != F or
+                                out.index.numel() != B * F):
+            raise ApaError('{}: out must be a CachedClips of this cache with the same B and frames'.format(who))
+        if not self.features.is_cuda:
+            raise ApaError('{}: the cache must live in GPU memory; the HIP path has no CPU fallback'.format(who))
+        if mode == 'random-segment' and u is None:
+            u = torch.rand((B * F,), dtype=torch.float32, device=self.device, generator=generator)
+        clips = out if out is not None else CachedClips(self, B, F)
+        K = 0 if self.video_targets is None else int(self.video_targets.shape[1])
+        rc = load_library().apa_sample_clip_frames(
+            self.video_first.data_ptr(), self.video_frames.data_ptr(), _dev_ptr(self.video_labels, 'labels'),
+            _dev_ptr(self.video_targets, 'targets'), vid.data_ptr(), _dev_ptr(u, 'u'), clips.index.data_ptr(),
+            _dev_ptr(clips.labels, 'labels'), _dev_ptr(clips.targets, 'targets'), self.status.data_ptr(), self.V, B, F,
+            K, CLIP_FRAME_MODES[mode], _stream_ptr())
+        _check(rc, 'apa_sample_clip_frames')
+        clips.videos = vid
+        return clips
+
+    def video_epoch(self, batch_videos: int, seed: int, shuffle: bool = True, drop_last: bool = True):
+        """`epoch` over the V videos of set_videos: one permutation of the video ids per call, drawn on the cache's
+        device from `seed`, yielded as its `batch_videos`-long int32 views (what `sample_clips` takes as `videos`)."""
+        if self.video_first is None:
+            raise ApaError('FeatureCache.video_epoch: set_videos first')
+        if batch_videos < 1:
+            raise ApaError('FeatureCache.video_epoch: batch_videos >= 1 expected')
+        if shuffle:
+            g = torch.Generator(device=self.device)
+            g.manual_seed(int(seed))
+            perm = torch.randperm(self.V, generator=g, device=self.device).to(torch.int32)
+        else:
+            perm = torch.arange(self.V, dtype=torch.int32, device=self.device)
+        end = self.V - self.V % batch_videos if drop_last else self.V
+        for a in range(0, end, batch_videos):
+            yield perm[a:min(a + batch_videos, end)]
+
 
 class CachedBatch(object):
     """N images of a FeatureCache named by an int32 index: pass one as `X` (and the same object as `Xatt`) to
@@ -563,6 +665,21 @@ class CachedBatch(object):
             raise ApaError('CachedBatch: the index must live in GPU memory; the HIP path has no CPU fallback')
         return ApaFeatureCache(self.index.data_ptr(), self.cache.T, 1 if labels_cached else 0,
                                self.cache.status.data_ptr())
+
+
+class CachedClips(CachedBatch):
+    """B clips of `frames` frames of a FeatureCache of video frames (`FeatureCache.sample_clips`): a CachedBatch of
+    N = B * frames images whose `index` the sampler writes on the device, with the clips' `labels` int64 [B] and / or
+    `targets` float32 [B,K] beside it (None where set_videos had none).  The buffers are this object's own:
+    `sample_clips(..., out=clips)` rewrites them in place, so a step bound to them follows without a rebind."""
+
+    def __init__(self, cache: FeatureCache, B: int, frames: int):
+        dev = cache.device
+        CachedBatch.__init__(self, cache, torch.zeros((int(B) * int(frames),), dtype=torch.int32, device=dev))
+        self.frames, self.videos = int(frames), None
+        self.labels = None if cache.video_labels is None else torch.zeros((int(B),), dtype=torch.int64, device=dev)
+        self.targets = None if cache.video_targets is None else torch.zeros(
+            (int(B), int(cache.video_targets.shape[1])), dtype=torch.float32, device=dev)
 
 
 def _cached(who: str, X, Xatt, frozen: bool = True) -> Optional['CachedBatch']:
@@ -1812,7 +1929,10 @@ class HeadTrainStep:
         `X` a CachedBatch (`FeatureCache.select(index)`, passed as `Xatt` too; `grads[0] = None`): the step reads the
         N images `index` names straight from the resident cache (apa_attn_head_train_step_cached), bit-identical to the
         step on `cache.gather(index)`; `labels=None` reads the cache's own labels through the same index;
-        `rebind(index=...)` moves the step to another batch of the cache.  Flat softmax cross-entropy, M == 1 only.
+        `rebind(index=...)` moves the step to another batch of the cache.  M == 1 only.  With `frames` / `temporal` /
+        a sigmoid `action_loss` the index names the B * frames frames of B clips (a CachedClips of
+        `FeatureCache.sample_clips`; apa_attn_head_train_step_cached_clips), `labels` is per clip / per row and must
+        be given (the CachedClips' `labels` / `targets`): bit-identical to the same step on the gathered frames.
         `share_with` (another HeadTrainStep of the same shapes): this step is bound to ITS output tensors, workspace
         and weight images -- a training loop has one set of them; only X / dX differ between the bound steps
         (bench.py's rotating feature-map sets)."""
@@ -1832,13 +1952,19 @@ class HeadTrainStep:
         # a FeatureCache read by index (apa_attn_head_train_step_cached): `X` is a CachedBatch; `labels=None` reads the
         # cache's own labels through the same index (labels_cached), else `labels` is [N] as ever
         cb = self._cached = _cached('HeadTrainStep', X, Xatt, frozen=dX is None)
+        cached_clips = False        # a CachedBatch with clips and / or a sigmoid loss: the *_cached_clips entry point
         if cb is not None:
-            if dxatt_rank1 or weight_images or int(frames) != 1 or temporal is not None or M != 1 or \
-                    action_loss != 'softmax-xentropy':
-                raise ApaError('HeadTrainStep: a CachedBatch feeds the flat class-agnostic step with the softmax '
-                               'cross-entropy (no clips, sigmoid losses, per-class maps or weight images)')
+            if dxatt_rank1 or weight_images or M != 1:
+                raise ApaError('HeadTrainStep: a CachedBatch feeds the class-agnostic step, flat or on clips (no '
+                               'per-class maps, weight images or dxatt_rank1)')
             if share_with is not None and share_with._cached is None:
                 raise ApaError('HeadTrainStep: share_with needs another step on a CachedBatch')
+            # clips and / or a sigmoid loss: apa_attn_head_train_step_cached_clips; their labels are per clip / per row
+            # (FeatureCache.sample_clips hands them out), never read through the frame index
+            cached_clips = int(frames) != 1 or temporal is not None or action_loss != 'softmax-xentropy'
+            if cached_clips and labels is None:
+                raise ApaError('HeadTrainStep: clips and the multi-label losses on a CachedBatch need labels (per clip '
+                               '/ per row: CachedClips.labels / .targets); labels=None reads per-image labels only')
             if labels is None and cb.cache.labels is None:
                 raise ApaError('HeadTrainStep: labels=None needs a FeatureCache with labels')
             self._fc = cb.descriptor(labels_cached=labels is None)
@@ -1895,11 +2021,15 @@ class HeadTrainStep:
             if self.weight_image_maps:
                 flags |= APA_FLAG_WEIGHT_IMAGES
         seed, off, flags = _rng_key(seed, offset, flags)     # the pointers below stay valid
+        # the int64 `labels` argument: every entry point but apa_attn_head_train_step_multilabel has it (the cached clip
+        # step keeps it under a sigmoid loss too, NULL then); dX sits 9 arguments behind it
+        has_labels_slot = self._ml is None or cached_clips
+        self._dx_idx = 15 if has_labels_slot else 14
         self._args = [
             _dev_ptr(X, 'X'), _dev_ptr(X, 'X') if fused else _dev_ptr(Xatt, 'Xatt', X.dtype),
             _dev_ptr(Wa, 'Wa', torch.float32), _dev_ptr(ba, 'ba', torch.float32),
             _dev_ptr(Wt, 'Wt', torch.float32), _dev_ptr(bt, 'bt', torch.float32),
-            *(() if self._ml is not None else (_dev_ptr(labels, 'labels', torch.int64),)),
+            *((None if self._ml is not None else _dev_ptr(labels, 'labels', torch.int64),) if has_labels_slot else ()),
             float(loss_wt), float(grad_scale),
             self.logits.data_ptr(), self.att.data_ptr(), self.zsave.data_ptr(), _dev_ptr(self.abar, 'abar'),
             self.loss.data_ptr(), self.G.data_ptr(), _dev_ptr(dX, 'dX', X.dtype),
@@ -1910,13 +2040,18 @@ class HeadTrainStep:
             flags, float(keep_prob), int(seed), off, _feat_dtype(X)]
         self._fn = self.lib.apa_attn_head_train_step_clips if clips else self.lib.apa_attn_head_train_step_ex
         self._name = 'apa_attn_head_train_step_clips' if clips else 'apa_attn_head_train_step'
-        self._dx_idx = 14 if self._ml is not None else 15
         if self._ml is not None:    # (ml, clip or NULL, hooks, then the same arguments without `labels`)
             self._pre = (ctypes.addressof(self._ml), ctypes.addressof(self._clip) if clips else None)
             self._fn, self._name = self.lib.apa_attn_head_train_step_multilabel, 'apa_attn_head_train_step_multilabel'
         if cb is not None:          # (the descriptor, hooks, then the same arguments)
             self._pre = (ctypes.addressof(self._fc),)
             self._fn, self._name = self.lib.apa_attn_head_train_step_cached, 'apa_attn_head_train_step_cached'
+        if cached_clips:            # (the descriptor, ml or NULL, clip or NULL, hooks, then the cached
+            # step's arguments: the `labels` slot stays, NULL under a sigmoid loss)
+            self._pre = (ctypes.addressof(self._fc), None if self._ml is None else ctypes.addressof(self._ml),
+                         ctypes.addressof(self._clip) if clips else None)
+            self._fn = self.lib.apa_attn_head_train_step_cached_clips
+            self._name = 'apa_attn_head_train_step_cached_clips'
 
     def refresh_weight_images(self) -> None:
         """Rebuild the operand images from the current weights (after load_state_dict, or an optimiser that does not
@@ -2228,8 +2363,11 @@ class HeadEvalStep:
     nothing changes.
 
     `X` a CachedBatch (`FeatureCache.select(index)`, passed as `Xatt` too): apa_attn_head_eval_step_cached on the images
-    `index` names (flat batches, softmax or sigmoid scores); `labels=None` with softmax scores reads the cache's own
-    labels, if it has any, through the index; `rebind(index=...)` moves the step to another batch of the cache."""
+    `index` names (softmax or sigmoid scores); `labels=None` with softmax scores on a flat batch reads the cache's own
+    labels, if it has any, through the index; `rebind(index=...)` moves the step to another batch of the cache.  With
+    `frames` > 1 or `temporal` the index names the frames of B clips (a CachedClips of `FeatureCache.sample_clips`;
+    apa_attn_head_eval_step_cached_clips) and `labels`, if given, is per clip; `labels=None` computes no loss there --
+    the cache's per-image labels are not read for a clip, `temporal` on single frames (`frames=1`) included."""
 
     def __init__(self, X, Xatt, Wa, ba, Wt, bt, labels=None, *, flags=0, workspace=None, frames=1, temporal=None,
                  scores='softmax'):
@@ -2243,9 +2381,12 @@ class HeadEvalStep:
         # softmax scores reads the cache's own labels, if it has any, through the same index (labels_cached)
         cb = self._cached = _cached('HeadEvalStep', X, Xatt)
         if cb is not None:
-            if int(frames) != 1 or temporal is not None or M != 1:
-                raise ApaError('HeadEvalStep: a CachedBatch feeds the flat class-agnostic step (no clips, no per-class maps)')
-            use_cached = labels is None and cb.cache.labels is not None and scores == 'softmax'
+            if M != 1:
+                raise ApaError('HeadEvalStep: a CachedBatch feeds the class-agnostic step (no per-class maps)')
+            # exactly when _bind_eval_clip below builds a clip (temporal attention on single frames is one too): its
+            # labels are per clip, never read through the frame index -- labels=None then means no loss
+            cached_clips = int(frames) != 1 or temporal is not None
+            use_cached = labels is None and cb.cache.labels is not None and scores == 'softmax' and not cached_clips
             self._fc = cb.descriptor(labels_cached=use_cached)
         B, code, self._clip, self.pooled, self.tatt, keep = _bind_eval_clip('HeadEvalStep', N, K, frames, temporal,
                                                                           scores, labels, dev)
@@ -2279,11 +2420,23 @@ class HeadEvalStep:
         if cb is not None:      # (the descriptor, clip = NULL, the kind, then the same arguments)
             self._fn, self._name = self.lib.apa_attn_head_eval_step_cached, 'apa_attn_head_eval_step_cached'
             self._pre = (ctypes.addressof(self._fc), None, code)
+            if self._clip is not None:      # (the descriptor, the clip, the kind, then the same arguments)
+                self._fn = self.lib.apa_attn_head_eval_step_cached_clips
+                self._name = 'apa_attn_head_eval_step_cached_clips'
+                self._pre = (ctypes.addressof(self._fc), ctypes.addressof(self._clip), code)
 
-    def rebind(self, X=None, index=None) -> None:
+    def rebind(self, X=None, index=None, labels=None) -> None:
         """Point the bound step at another feature map of the same shape / dtype (attention from the map itself:
         the step was built with `Xatt is X`).  `index` (a step on a CachedBatch): another batch of the same cache, an
-        int32 tensor of the same length on the cache's device."""
+        int32 tensor of the same length on the cache's device.  `labels`: another int64 label tensor of the same
+        length, for a step that was built with labels of its own."""
+        if labels is not None:
+            if self._keep[6] is None or (self._cached is not None and self._fc.labels_cached):
+                raise ApaError('HeadEvalStep.rebind: the step was built without labels of its own')
+            if labels.numel() != self._keep[6].numel():
+                raise ApaError('HeadEvalStep.rebind: labels int64 [{}] expected'.format(self._keep[6].numel()))
+            self._args[6] = _dev_ptr(labels, 'labels', torch.int64)
+            self._keep = self._keep[:6] + (labels,) + tuple(self._keep[7:])
         if index is not None:
             if self._cached is None:
                 raise ApaError('HeadEvalStep.rebind: index= needs a step bound to a CachedBatch')

@@ -1342,9 +1342,12 @@ class FusedHeadStep:
     def __call__(self, images, labels_action, labels_pose=None, pose_valid=None):
         """`images`: the input batch; an Fp8Features batch (a cached conv5 map in FP8); or a CachedBatch (N images of a
         resident FeatureCache named by index, any of its dtypes: `labels_action=None` reads the cache's own labels
-        through the index).  The two cached forms are frozen by construction (frozen_features=True) and are served
-        under the head conditions of fp8_unsupported_reason."""
-        from .custom_ops.custom_ops_factory import CachedBatch, Fp8Features
+        through the index; under LOSS_FN_ACTION 'multi-label*' `labels_action` is [N,K]); or a CachedClips
+        (`FeatureCache.sample_clips`: B clips of a frame cache -- `frames` comes from the batch, `labels_action=None`
+        means the batch's own labels / targets, and the end points are those of a 5-D clip batch).  The cached forms
+        are frozen by construction (frozen_features=True) and are served under the head conditions of
+        fp8_unsupported_reason; one bound step per (cache, B, F, loss kind)."""
+        from .custom_ops.custom_ops_factory import CachedBatch, CachedClips, Fp8Features
         self._frames = 1
         self._cb = isinstance(images, CachedBatch)
         self._fp8 = isinstance(images, Fp8Features)
@@ -1353,10 +1356,19 @@ class FusedHeadStep:
             why = self.fp8_unsupported_reason(self.head, self.network_fn)
             if not why and not self.frozen_features:
                 why = 'frozen_features=False (a cache has no gradient: build the step with frozen_features=True)'
-            if not why and self._cb and self.cfg.TRAIN.LOSS_FN_ACTION != 'softmax-xentropy':
-                why = 'LOSS_FN_ACTION %r (the cached step takes the softmax cross-entropy)' % self.cfg.TRAIN.LOSS_FN_ACTION
             if why:
                 raise ValueError('FusedHeadStep: %s is not served with %s' % (what, why))
+            multi_label = self.cfg.TRAIN.LOSS_FN_ACTION != 'softmax-xentropy'
+            if isinstance(images, CachedClips):     # clips sampled from a frame cache: F and the labels ride along
+                self._frames = int(images.frames)
+                if labels_action is None:
+                    labels_action = images.targets if multi_label else images.labels
+                    if labels_action is None:
+                        raise ValueError('FusedHeadStep: labels_action=None needs a CachedClips with %s '
+                                         '(FeatureCache.set_videos)' % ('targets' if multi_label else 'labels'))
+            elif self._cb and multi_label and labels_action is None:
+                raise ValueError('FusedHeadStep: a CachedBatch under LOSS_FN_ACTION %r needs labels_action [N,K] (the '
+                                 'cache\'s own labels are class ids)' % self.cfg.TRAIN.LOSS_FN_ACTION)
         elif images.dim() == 5:                                 # nets_factory.py:121-125: frames fold into the batch
             self._frames = int(images.shape[1])
             images = images.reshape(-1, *images.shape[2:])
@@ -1475,7 +1487,7 @@ class FusedHeadEval:
         return [getattr(h, n) for n in names]
 
     def __call__(self, images, labels_action=None, want_pose_logits: bool = False):
-        from .custom_ops.custom_ops_factory import CachedBatch, Fp8Features
+        from .custom_ops.custom_ops_factory import CachedBatch, CachedClips, Fp8Features
         frames = 1
         cb = isinstance(images, CachedBatch)
         fp8 = isinstance(images, Fp8Features) or cb
@@ -1484,6 +1496,10 @@ class FusedHeadEval:
             if why:
                 raise ValueError('FusedHeadEval: %s is not served with %s' % (
                     'a CachedBatch' if cb else 'an Fp8Features batch', why))
+            if isinstance(images, CachedClips):     # clips sampled from a frame cache: F and the labels ride along
+                frames = int(images.frames)
+                if labels_action is None:
+                    labels_action = images.targets if self.multi_label else images.labels
         elif images.dim() == 5:                                 # nets_factory.py:121-125
             frames = images.shape[1]
             images = images.reshape(-1, *images.shape[2:])

@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define APA_VERSION 312 /* major*10000 + minor*100 + patch */
+#define APA_VERSION 313 /* major*10000 + minor*100 + patch */
 
 typedef enum apa_status {
   APA_OK = 0,
@@ -860,8 +860,9 @@ int apa_attn_pool_bwd_cat(const apa_concat_feat* cat, const apa_hooks* hooks, co
  *                        step without APA_FLAG_FROZEN_INPUT;
  *   APA_ERR_UNSUPPORTED: M != 1, a separate attention input, APA_FLAG_SOFTMAX_ATT, APA_FLAG_RELU_INPUT,
  *                        APA_FLAG_RNG_EXTERNAL, the TopDownAttention dump, clips (eval: clip must be NULL);
- * then whatever the plain entry point refuses (for FP8: what the FP8 arm refuses).  Not built: clips, the sigmoid
- * training losses, rank > 1, per-class maps, the concatenated pose channels, the pose head and the cfg 003 steps.
+ * then whatever the plain entry point refuses (for FP8: what the FP8 arm refuses).  Clips and the sigmoid training
+ * losses: the *_cached_clips steps below.  Not built: rank > 1, per-class maps, the concatenated pose channels, the
+ * pose head and the cfg 003 steps, clips or sigmoid losses with labels_cached.
  * Workspace: apa_attn_pool_workspace_bytes of the BATCH shape.  The signatures are those of apa_attn_pool_fwd_ex /
  * apa_attn_pool_bwd_ex / apa_attn_head_train_step_ex / apa_attn_head_eval_step_clips with the descriptor in front.
  */
@@ -896,6 +897,80 @@ int apa_attn_head_eval_step_cached(const apa_feature_cache* cache, const apa_cli
                                    float* zsave, float* abar, float* loss, float* probs, int64_t* pred, void* ws,
                                    size_t ws_bytes, int N, int P, int C, int Ca, int K, int M, unsigned flags,
                                    int dtype, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Clips and the sigmoid ("multi-label") losses from a resident FRAME cache: the one-call steps of
+ * apa_attn_head_train_step_clips / apa_attn_head_train_step_multilabel / apa_attn_head_eval_step_clips with the cache
+ * descriptor in front.  The N = B * clip->frames batch images are the frames index[] names (apa_sample_clip_frames
+ * writes such an index, and the clips' labels, on the device); the clip loss, the sigmoid reducers and the scores
+ * launch never see X, so nothing but the pooling passes' gathered instances differs from the plain steps.
+ * Contract: bit-identical to the same clip / multi-label step on a gathered copy of the B * frames frames, with the
+ * same launches -- for fp32, bf16 and FP8 caches, FP8 keeping its own limits.
+ *   apa_attn_head_train_step_cached_clips(cache, ml, clip, hooks, <the arguments of apa_attn_head_train_step_cached
+ *   from X on>): ml == NULL: the softmax cross-entropy on `labels` (int64 [N], or [B] with a clip); ml given: the
+ *   sigmoid loss on ml->labels ([N,K], or [B,K] with a clip) and `labels` is not read (it may be NULL).  clip == NULL:
+ *   flat.  loss is [1 + N] flat, [1 + B] on clips.  ml == NULL && clip == NULL: the call IS
+ *   apa_attn_head_train_step_cached, same launches, same bits (labels_cached included).
+ *   apa_attn_head_eval_step_cached_clips(cache, clip, scores_kind, <the arguments of apa_attn_head_eval_step_clips from
+ *   X on>): clip == NULL is apa_attn_head_eval_step_cached with a NULL clip.
+ * Workspace: apa_clip_step_workspace_bytes of the batch shape for a training step with a clip,
+ * apa_attn_pool_workspace_bytes otherwise (every evaluation step: the scores launch needs none).
+ * Refused before anything is queued, in this order --
+ *   1. what apa_attn_head_train_step_cached / apa_attn_head_eval_step_cached refuse about the descriptor, the
+ *      dimensions, dX, APA_FLAG_FROZEN_INPUT and the forms a cache cannot have, with the same text;
+ *   2. training: an invalid ml (apa_attn_head_train_step_multilabel's refusals);
+ *   3. APA_ERR_INVALID_ARG: labels_cached = 1 together with a clip or an ml ("labels_cached"): such labels are per clip
+ *      or per row and come from the sampler, not from a per-frame table behind the index;
+ *   4. what the plain clip / multi-label / evaluation entry points refuse (N % frames != 0, the clip's pointers, the
+ *      scores kind, labels and loss; then the pooling call's own checks and the workspace), with their text.
+ * apa_attn_head_eval_step_cached keeps refusing any clip as it always did.
+ */
+int apa_attn_head_train_step_cached_clips(const apa_feature_cache* cache, const apa_multilabel* ml /* NULL: softmax */,
+                                          const apa_clip_pool* clip /* NULL: flat */, const apa_hooks* hooks,
+                                          const void* X, const void* Xatt, const float* Wa, const float* ba,
+                                          const float* Wt, const float* bt, const int64_t* labels, float loss_wt,
+                                          float grad_scale, float* logits, float* att, float* zsave, float* abar,
+                                          float* loss, float* G, void* dX, void* dXatt, float* dWa, float* dba,
+                                          float* dWt, float* dbt, void* ws, size_t ws_bytes, int N, int P, int C,
+                                          int Ca, int K, int M, unsigned flags, float keep_prob, uint64_t seed,
+                                          uint64_t offset, int dtype, void* stream);
+int apa_attn_head_eval_step_cached_clips(const apa_feature_cache* cache, const apa_clip_pool* clip /* NULL: flat */,
+                                         int scores_kind, const void* X, const void* Xatt, const float* Wa,
+                                         const float* ba, const float* Wt, const float* bt, const int64_t* labels,
+                                         float* logits, float* att, float* zsave, float* abar, float* loss,
+                                         float* probs, int64_t* pred, void* ws, size_t ws_bytes, int N, int P, int C,
+                                         int Ca, int K, int M, unsigned flags, int dtype, void* stream);
+
+/* "These B videos, F frames each" -> the index a *_cached call reads, and the clips' labels, in ONE launch on the
+ * device: no workspace, no host synchronisation, capturable; identical calls give identical bits.
+ *   video_first  int32 [V]   cache slot of each video's frame 0
+ *   video_frames int32 [V]   its frame count n >= 1 (a smaller value is read as 1)
+ *   videos       int32 [B]   the batch's video ids; an id outside [0,V) is clamped and, with `status` given, counted
+ *                            there (the caller zeroes the word; the convention of apa_feature_cache.status)
+ *   u            f32 [B*F]   the caller's uniform draws in [0,1) (as apa_pose_sampled_loss_fwd_bwd's `uniform`;
+ *                            TensorFlow's random stream is not reproduced); read by RANDOM_SEGMENT only -- under
+ *                            UNIFORM it is ignored, NULL or not
+ *   index        int32 [B*F] = video_first[v] + frame_i, clip b's frames at [b*F, (b+1)*F)
+ *   video_labels int64 [V] (nullable) -> labels int64 [B];  video_targets f32 [V,K] (nullable) -> targets f32 [B,K]
+ * The frame rule is _get_frame_sublist (src/datasets/image_read_utils.py:12-44) as video_data_utils.py:79-81 calls it
+ * (num_consec_frames = 1, start_frame = 0), with its int32 `/` read as floor division (TF 1.1 under Python 2: our
+ * reading, TensorFlow is absent):
+ *   step = max((n - 1) / F, 1)
+ *   APA_CLIP_FRAMES_UNIFORM         frame_i = min(step * i, n - 1)
+ *   APA_CLIP_FRAMES_RANDOM_SEGMENT  lo = min(step * i, n - 2), hi = min(step * (i + 1), n - 1),
+ *                                   frame_i = lo + min((int)(u[b*F+i] * (float)(hi - lo)), hi - lo - 1) in fp32,
+ *                                   clamped to [0, n - 1]; hi <= lo (n = 1): lo clamped
+ * Refused with APA_ERR_INVALID_ARG before anything is queued: a null video_first / video_frames / videos / index,
+ * video_labels without labels or video_targets without targets, non-positive V / B / frames (K with video_targets),
+ * an unknown mode, RANDOM_SEGMENT without u, B * frames past 2^31 - 1. */
+#define APA_CLIP_FRAMES_UNIFORM 0
+#define APA_CLIP_FRAMES_RANDOM_SEGMENT 1
+int apa_sample_clip_frames(const int32_t* video_first, const int32_t* video_frames,
+                           const int64_t* video_labels /* NULL */, const float* video_targets /* NULL */,
+                           const int32_t* videos, const float* u /* NULL */, int32_t* index, int64_t* labels,
+                           float* targets, int32_t* status /* NULL */, int V, int B, int frames, int K, int mode,
+                           void* stream);
+
 /* apa_quantize_features_fp8 into place: the n images of src become images [first, first + n) of the T-image FP8 cache
  * at `cache` (same rule, same kernel; status int32 [n]).  Slots outside the cache: APA_ERR_INVALID_ARG. */
 int apa_quantize_features_fp8_at(const void* src, int src_dtype, void* cache, int cache_images, int first,

@@ -37,6 +37,14 @@ headline stays the cfg 002 training workload); run this file directly for one wo
             process, medians of five and their spread: (a) the gathered step (apa_attn_head_train_step_cached) with a
             fresh shuffled index per step, (b) gather + rebind + the plain step -- the loop without the gathered
             kernels --, (c) the plain step on one fixed contiguous batch.
+  cached_hmdb_clips_fp8 / cached_hmdb_clips_bf16 / cached_charades_fp8 / cached_charades_bf16
+            one-call CLIP training step from a resident FRAME cache (--cache-images maps in videos of 25 frames, FP8 E4M3
+            or bf16): --clips 8 x --frames 4, temporal attention, M = 1; K = 51 with the softmax cross-entropy (HMDB-51)
+            or K = 157 with 'multi-label' (Charades).  Three variants alternating in one process, medians of five and
+            their spread: (a) the device sampler with fresh draws per step + the cached clip step
+            (apa_sample_clip_frames, apa_attn_head_train_step_cached_clips), (b) the sampler + gather + rebind + the
+            plain clip step, (c) the plain clip step on one fixed batch; and the evaluation step at 4 clips x 25 frames,
+            (a) against (b).
   explain002
             class attention maps of T = 1 and T = 5 chosen classes at the cfg 002 shape (32 x 14x14x2048 fp32, K = 393):
             the one-call evaluation step + cof.attn_explain against the per-op forward with want_topdown=True + torch.gather,
@@ -1260,6 +1268,125 @@ def run_cached(cof, dev, args, which):
             'clamped_ids': int(info['steps'][0]._cached.cache.status)}
 
 
+CACHED_CLIPS = {'cached_hmdb_clips_fp8': (51, 'softmax-xentropy', True), 'cached_hmdb_clips_bf16': (51, 'softmax-xentropy', False),
+                'cached_charades_fp8': (157, 'multi-label', True), 'cached_charades_bf16': (157, 'multi-label', False)}
+
+
+def build_cached_clips(cof, dev, which, B=8, F=4, H=14, T=2048, eval_B=4, eval_F=25):
+    """One-call clip training step (temporal attention, dropout keep 0.2, M = 1; K = 51 softmax cross-entropy or K = 157
+    'multi-label') from a RESIDENT frame cache of videos of 25 frames (14x14x2048 maps, FP8 E4M3 or bf16), three ways:
+    (a) the device sampler (random-segment, fresh draws per step, out= the bound CachedClips) + the cached clip step;
+    (b) the sampler + cache.gather(index) + rebind + the plain clip step; (c) the plain clip step on one fixed batch.
+    And an evaluation step at eval_B x eval_F frames (uniform sampling): (a) cached, (b) gather + rebind.
+    -> ({name: step}, {name: eval step}, info)"""
+    K, loss, fp8 = CACHED_CLIPS[which]
+    C, P, NF = 2048, H * H, 25
+    V = max(int(T) // NF, 4 * max(B, eval_B))
+    T = V * NF
+    g = torch.Generator().manual_seed(42)
+    cache = cof.FeatureCache.empty((T, H, H, C), torch.float8_e4m3fn if fp8 else torch.bfloat16, dev)
+    for first in range(0, T, 256):
+        n = min(256, T - first)
+        status = cache.write(first, _features(n, P, C, torch.bfloat16, dev, seed=42 + first).view(n, H, H, C))
+        assert int(status.sum()) == 0
+    ml = loss != 'softmax-xentropy'
+    vlab = None if ml else torch.randint(0, K, (V,), generator=g).to(dev)
+    vtar = (torch.rand(V, K, generator=g) < 0.05).float().to(dev) if ml else None
+    cache.set_videos(torch.arange(V) * NF, torch.full((V,), NF), labels=vlab, targets=vtar)
+    Wa = (torch.randn(C, 1, generator=g) / C ** 0.5).to(dev); ba = torch.zeros(1, device=dev)
+    Wt = (torch.randn(C, K, generator=g) / C ** 0.5).to(dev); bt = torch.zeros(K, device=dev)
+    tw = (torch.randn(K, generator=g) * 0.01).to(dev); tb = torch.full((1,), 1.0 / F, device=dev)
+    pg = tuple(torch.empty_like(t) for t in (Wa, ba, Wt, bt))
+    tg = (torch.empty_like(tw), torch.empty_like(tb))
+    ctr = torch.zeros(1, dtype=torch.int64, device=dev)
+    kw = dict(flags=cof.attn_flags(False, False, True), keep_prob=0.2, seed=42, offset=ctr, frames=F, temporal=(tw, tb),
+              temporal_grads=tg, action_loss=loss)
+    lab = lambda c: c.targets if ml else c.labels
+    batches = [b for e in range(4) for b in cache.video_epoch(B, seed=e)]      # four epochs' shuffled video batches
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(7)
+    clips_a = cache.sample_clips(batches[0], F, mode='random-segment', generator=gen)
+    clips_b = cache.sample_clips(batches[0], F, mode='random-segment', generator=gen)
+    st_a = cof.HeadTrainStep(clips_a, clips_a, Wa, ba, Wt, bt, lab(clips_a), (None, None) + pg, **kw)
+    X0 = cache.gather(clips_b.index)
+    st_b = cof.HeadTrainStep(X0, X0, Wa, ba, Wt, bt, lab(clips_b), (None, None) + pg, **kw)
+    f = cache.features
+    Xc = cof.Fp8Features.from_parts(f.codes[:B * F], f.scale[:B * F]) if fp8 else f[:B * F]
+    st_c = cof.HeadTrainStep(Xc, Xc, Wa, ba, Wt, bt, lab(clips_a).clone(), (None, None) + pg, **kw)
+    state = {'a': 0, 'b': 0, 'ea': 0, 'eb': 0}
+
+    def step_a():
+        cache.sample_clips(batches[state['a'] % len(batches)], F, mode='random-segment', generator=gen, out=clips_a)
+        state['a'] += 1
+        st_a.run()
+
+    def step_b():
+        cache.sample_clips(batches[state['b'] % len(batches)], F, mode='random-segment', generator=gen, out=clips_b)
+        state['b'] += 1
+        st_b.rebind(X=cache.gather(clips_b.index), labels=lab(clips_b))
+        st_b.run()
+
+    # evaluation: eval_B clips of all 25 frames, uniform sampling, sigmoid scores for the multi-label head
+    etb = torch.full((1,), 1.0 / eval_F, device=dev)
+    ebatches = [b for b in cache.video_epoch(eval_B, seed=9, shuffle=False)]
+    ekw = dict(frames=eval_F, temporal=(tw, etb), scores='sigmoid' if ml else 'softmax')
+    eclips_a, eclips_b = cache.sample_clips(ebatches[0], eval_F), cache.sample_clips(ebatches[0], eval_F)
+    ev_a = cof.HeadEvalStep(eclips_a, eclips_a, Wa, ba, Wt, bt, **ekw)
+    E0 = cache.gather(eclips_b.index)
+    ev_b = cof.HeadEvalStep(E0, E0, Wa, ba, Wt, bt, **ekw)
+
+    def eval_a():
+        cache.sample_clips(ebatches[state['ea'] % len(ebatches)], eval_F, out=eclips_a)
+        state['ea'] += 1
+        ev_a.run()
+
+    def eval_b():
+        cache.sample_clips(ebatches[state['eb'] % len(ebatches)], eval_F, out=eclips_b)
+        state['eb'] += 1
+        ev_b.rebind(X=cache.gather(eclips_b.index))
+        ev_b.run()
+
+    bytes_img = P * C * (1 if fp8 else 2)
+    info = {'shape': '{} clips x {} frames of {} videos x {} frames ({} maps {}x{}x{}), K={}, {}, temporal attention, '
+                     'dropout keep=0.2'.format(B, F, V, NF, T, H, H, C, K, loss),
+            'eval_shape': '{} clips x {} frames'.format(eval_B, eval_F),
+            'feature_bytes_per_step': 2 * B * F * bytes_img, 'gather_bytes_per_step': 2 * B * F * bytes_img,
+            'cache_bytes': T * bytes_img, 'steps': (st_a, st_b, st_c), 'cache': cache}
+    return ({'a_sampler_cached_clips': step_a, 'b_sampler_gather_rebind_plain': step_b, 'c_plain_fixed': st_c.run},
+            {'a_sampler_cached_clips': eval_a, 'b_sampler_gather_rebind_plain': eval_b}, info)
+
+
+def run_cached_clips(cof, dev, args, which):
+    """cached_hmdb_clips_* / cached_charades_*: the variants ALTERNATING in one process, five timed loops of each,
+    interleaved; medians and the loops' spread -- run_cached's protocol, for the training step and for evaluation."""
+    forms, evals, info = build_cached_clips(cof, dev, which, args.clips, args.frames, args.hw, args.cache_images)
+    out = {'workload': '{}: frozen one-call clip training step from a resident {} frame cache, three variants '
+                       'alternating in one process; {}'.format(which, 'FP8 E4M3' if CACHED_CLIPS[which][2] else 'bf16',
+                                                               info['shape'])}
+    for tag, group in (('', forms), ('eval_', evals)):
+        for _ in range(args.warmup):
+            for step in group.values():
+                step()
+        torch.cuda.synchronize()
+        runs = {k: [] for k in group}
+        for _ in range(5):
+            for name, step in group.items():
+                sec, _ = timed(step, args.steps, 0, min_ms=0.0, repeats=1)
+                runs[name].append(sec * 1e6)
+        med = {k: sorted(v)[len(v) // 2] for k, v in runs.items()}
+        out[tag + 'us_per_step'] = {k: round(v, 2) for k, v in med.items()}
+        out[tag + 'us_per_step_runs'] = {k: [round(x, 2) for x in v] for k, v in runs.items()}
+        out[tag + 'us_per_step_spread'] = {k: round(max(v) - min(v), 2) for k, v in runs.items()}
+        out[tag + 'a_over_b'] = round(med['a_sampler_cached_clips'] / med['b_sampler_gather_rebind_plain'], 4)
+        if not tag:
+            out['a_minus_c_us'] = round(med['a_sampler_cached_clips'] - med['c_plain_fixed'], 2)
+    assert all(st.frozen_input for st in info['steps'])
+    out.update(eval_shape=info['eval_shape'], feature_bytes_per_step=info['feature_bytes_per_step'],
+               gather_bytes_per_step=info['gather_bytes_per_step'], cache_bytes=info['cache_bytes'],
+               clamped_ids=int(info['cache'].status))
+    return out
+
+
 def run_explain002(cof, dev, args):
     """Class attention maps of T chosen classes at the cfg 002 benchmark shape (32 x 14x14x2048 fp32, K = 393), T = 1 and
     T = 5: the one-call evaluation step + cof.attn_explain against the only other route, the per-op forward with
@@ -1460,7 +1587,7 @@ def main():
                                                          'hico002', 'charades_clips', 'frozen002', 'frozen003',
                                                          'frozen_perclass', 'frozen002_fp8', 'eval002_fp8',
                                                          'cached002_fp8', 'cached002_bf16', 'explain002', 'map393'] +
-                    sorted(EVAL_CLIPS) + sorted(RANK_WORKLOADS))
+                    sorted(EVAL_CLIPS) + sorted(RANK_WORKLOADS) + sorted(CACHED_CLIPS))
     ap.add_argument('--clips', type=int, default=8, help='video_*: clips per batch')
     ap.add_argument('--frames', type=int, default=4, help='video_*: frames per clip')
     ap.add_argument('--only', default=None, choices=['clip_one_call', 'module_path', 'flat_one_call',
@@ -1512,6 +1639,9 @@ def main():
         return
     if args.workload in ('cached002_fp8', 'cached002_bf16'):
         print(json.dumps(run_cached(cof, dev, args, args.workload)))
+        return
+    if args.workload in CACHED_CLIPS:
+        print(json.dumps(run_cached_clips(cof, dev, args, args.workload)))
         return
     if args.workload.startswith('frozen'):
         print(json.dumps(run_frozen(cof, dev, args, args.workload)))
