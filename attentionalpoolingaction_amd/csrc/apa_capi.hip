@@ -1154,6 +1154,154 @@ extern "C" int apa_attn_head_eval_step_cached_clips(const apa_feature_cache* cac
                               labels, loss, probs, pred);
 }
 
+// ---- a whole epoch over the cache behind one host call (apa.h: apa_epoch) --------------------------------------------
+// Both calls ARE the loop over the *_cached step they name (and, training, apa_momentum_sgd_step behind each step):
+// the same entry points with the same arguments, so the same launches and the same bits.  What is added is the order of
+// things: every refusal -- the epoch's, the optimiser's, the descriptor's, the step's for the shape (both halves, and
+// the evaluation pass's shorter last batch) -- is made here, before the first launch.
+
+// the epoch's own refusals; *steps: the number of steps it runs
+static int epoch_check(const char* fn, const apa_epoch* ep, const apa_feature_cache* cache, int N, bool train,
+                       int* steps) {
+  if (!ep || !ep->order) {
+    set_error("%s: null apa_epoch / order pointer", fn);
+    return APA_ERR_INVALID_ARG;
+  }
+  if (!cache) {
+    set_error("%s: null apa_feature_cache", fn);
+    return APA_ERR_INVALID_ARG;
+  }
+  if (N <= 0) {
+    set_error("%s: non-positive batch size N=%d", fn, N);
+    return APA_ERR_INVALID_ARG;
+  }
+  if (train ? (ep->count < N || ep->count % N != 0) : ep->count < 1) {
+    set_error(train ? "%s: apa_epoch.count=%d is not a whole, positive number of batches of N=%d images"
+                    : "%s: apa_epoch.count=%d: an evaluation pass visits at least one image (N=%d)", fn, ep->count, N);
+    return APA_ERR_INVALID_ARG;
+  }
+  const long long s = ((long long)ep->count + N - 1) / N;
+  if (s * N > 0x7fffffffLL) {
+    set_error("%s: steps * N = %lld is past 2^31 - 1 (count=%d, N=%d)", fn, s * N, ep->count, N);
+    return APA_ERR_INVALID_ARG;
+  }
+  *steps = (int)s;
+  return APA_OK;
+}
+
+// what sgd_launch (apa_optim.hip) refuses about apa_momentum_sgd_step's arguments, before the first step
+static int epoch_sgd_check(const char* fn, const apa_epoch_sgd* o) {
+  if (o->nseg <= 0 || o->nseg > APA_SGD_MAX_SEGMENTS || !o->weights || !o->sizes || !o->weight_decay ||
+      !o->grad_flat || !o->acc_flat) {
+    set_error("%s: apa_epoch_sgd: bad arguments (nseg=%d, max %d; weights, sizes, weight_decay, grad_flat and acc_flat "
+              "must be given)", fn, o->nseg, APA_SGD_MAX_SEGMENTS);
+    return APA_ERR_INVALID_ARG;
+  }
+  for (int i = 0; i < o->nseg; ++i)
+    if (!o->weights[i]) {
+      set_error("%s: apa_epoch_sgd.weights[%d] is NULL", fn, i);
+      return APA_ERR_INVALID_ARG;
+    }
+  return APA_OK;
+}
+
+// the pooling call's refusals and the M == 1 paths' own (m1_call_fill) for one half; nothing is launched
+static int epoch_half_check(const PoolCall& d, const M1Fwd* f, const M1Bwd* b) {
+  const int rc = pool_check(d, f, b);
+  if (rc != APA_OK) return rc;
+  M1Call c;
+  return m1_call_fill(c, d, f, b);
+}
+
+extern "C" int apa_attn_head_train_epoch_cached(const apa_epoch* ep, const apa_epoch_sgd* opt,
+                                                const apa_feature_cache* cache, const apa_hooks* hooks, const void* X,
+                                                const void* Xatt, const float* Wa, const float* ba, const float* Wt,
+                                                const float* bt, const int64_t* labels, float loss_wt, float grad_scale,
+                                                float* logits, float* att, float* zsave, float* abar, float* loss,
+                                                float* G, void* dX, void* dXatt, float* dWa, float* dba, float* dWt,
+                                                float* dbt, void* ws, size_t ws_bytes, int N, int P, int C, int Ca, int K,
+                                                int M, unsigned flags, float keep_prob, uint64_t seed, uint64_t offset,
+                                                int dtype, void* stream) {
+  const char* fn = "apa_attn_head_train_epoch_cached";
+  if (!opt || !opt->lr) {
+    set_error("%s: null apa_epoch_sgd / lr pointer", fn);
+    return APA_ERR_INVALID_ARG;
+  }
+  int steps = 0;
+  int rc = epoch_check(fn, ep, cache, N, true, &steps);
+  if (rc != APA_OK) return rc;
+  if ((rc = epoch_sgd_check(fn, opt)) != APA_OK) return rc;
+  apa_feature_cache fc = *cache;
+  fc.index = ep->order;
+  {  // the step's checks, once for the shape
+    PoolCall d = fp8_served(pool_call({N, P, C, Ca, K, M, dtype}, flags, keep_prob, seed, offset, ws, ws_bytes, stream,
+                                      hooks));
+    if ((rc = cache_check(fn, &fc, d, X, Xatt, false, true, dX)) != APA_OK) return rc;
+    d.fc = &fc;
+    const StepLoss L{nullptr, labels, false, nullptr, loss_wt, grad_scale, loss, G};
+    const M1Fwd f{X, Xatt, Wa, ba, Wt, bt, logits, att, zsave, abar};
+    const M1Bwd b{X, Xatt, Wa, Wt, bt, att, zsave, abar, G, dX, dXatt, dWa, dba, dWt, dbt};
+    size_t pool_bytes = 0;
+    if ((rc = head_step_check(fn, d, L, logits, &pool_bytes)) != APA_OK) return rc;
+    d.ws_bytes = pool_bytes;
+    if ((rc = epoch_half_check(d, &f, nullptr)) != APA_OK) return rc;
+    d.flags |= APA_FLAG_WS_FROM_FWD;
+    if ((rc = epoch_half_check(d, nullptr, &b)) != APA_OK) return rc;
+  }
+  const bool rng_dev = (flags & APA_FLAG_RNG_DEVICE) != 0;   // the counter in HBM advances by itself
+  for (int s = 0; s < steps; ++s) {
+    fc.index = ep->order + (size_t)s * N;
+    rc = apa_attn_head_train_step_cached(&fc, hooks, X, Xatt, Wa, ba, Wt, bt,
+                                         (fc.labels_cached || !labels) ? labels : labels + (size_t)s * N, loss_wt,
+                                         grad_scale, logits, att, zsave, abar, loss + (size_t)s * (1 + N), G, dX, dXatt,
+                                         dWa, dba, dWt, dbt, ws, ws_bytes, N, P, C, Ca, K, M, flags, keep_prob, seed,
+                                         rng_dev ? offset : offset + (uint64_t)s, dtype, stream);
+    if (rc != APA_OK) return rc;
+    rc = apa_momentum_sgd_step(opt->nseg, opt->weights, opt->sizes, opt->weight_decay, opt->grad_flat, opt->acc_flat,
+                               opt->lr[s], opt->momentum, opt->grad_scale, stream);
+    if (rc != APA_OK) return rc;
+  }
+  return APA_OK;
+}
+
+extern "C" int apa_attn_head_eval_epoch_cached(const apa_epoch* ep, const apa_feature_cache* cache, int scores_kind,
+                                               const void* X, const void* Xatt, const float* Wa, const float* ba,
+                                               const float* Wt, const float* bt, const int64_t* labels, float* logits,
+                                               float* att, float* zsave, float* abar, float* loss, float* probs,
+                                               int64_t* pred, void* ws, size_t ws_bytes, int N, int P, int C, int Ca,
+                                               int K, int M, unsigned flags, int dtype, void* stream) {
+  const char* fn = "apa_attn_head_eval_epoch_cached";
+  int steps = 0;
+  int rc = epoch_check(fn, ep, cache, N, false, &steps);
+  if (rc != APA_OK) return rc;
+  apa_feature_cache fc = *cache;
+  fc.index = ep->order;
+  const int last = ep->count - (steps - 1) * N;   // rows of the last step, 1..N
+  {  // the step's checks, once for the full batch and once for the last step's shape
+    const M1Fwd f{X, Xatt, Wa, ba, Wt, bt, logits, att, zsave, abar};
+    for (int n : {N, last}) {
+      PoolCall d = fp8_served(pool_call({n, P, C, Ca, K, M, dtype}, flags, 1.0f, 0, 0, ws, ws_bytes, stream));
+      if ((rc = cache_check(fn, &fc, d, X, Xatt, false, false, nullptr)) != APA_OK) return rc;
+      if ((rc = eval_scores_check(fn, nullptr, scores_kind, n, K, logits, labels, loss, probs, pred)) != APA_OK)
+        return rc;
+      d.fc = &fc;
+      d.flags &= ~(unsigned)APA_FLAG_TRAIN;
+      if ((rc = epoch_half_check(d, &f, nullptr)) != APA_OK) return rc;
+    }
+  }
+  for (int s = 0; s < steps; ++s) {
+    const size_t row = (size_t)s * N;
+    fc.index = ep->order + row;
+    rc = apa_attn_head_eval_step_cached(&fc, nullptr, scores_kind, X, Xatt, Wa, ba, Wt, bt,
+                                        (fc.labels_cached || !labels) ? labels : labels + row, logits + row * K, att,
+                                        zsave, abar, loss ? loss + (size_t)s * (1 + N) : nullptr, probs + row * K,
+                                        pred + row, ws, ws_bytes, s == steps - 1 ? last : N, P, C, Ca, K, M, flags,
+                                        dtype, stream);
+    if (rc != APA_OK) return rc;
+  }
+  return APA_OK;
+}
+
 // workspace of apa_pose_attn_eval_step: [pose head | pooling (+ the label-free loss scratch) | column-tile partials]
 struct PoseEvalCarve { size_t pose, pool, zpart, total; };
 static PoseEvalCarve pose_eval_carve(int N, int P, int C, int Cp, int J, int K, unsigned flags, int dtype) {

@@ -91,6 +91,15 @@ _SIGNATURES = {
     'apa_attn_head_eval_step_cached_clips': (c_int, [c_void_p, c_void_p, c_int] + [c_void_p] * 15 + [c_size_t] +
                                              [c_int] * 6 + [c_uint, c_int, c_void_p]),
     'apa_sample_clip_frames': (c_int, [c_void_p] * 10 + [c_int] * 5 + [c_void_p]),
+    # a whole epoch over the cache: (order, T, seed, epoch, stream); (`const apa_epoch*`, `const apa_epoch_sgd*`), then
+    # every argument of apa_attn_head_train_step_cached; (`const apa_epoch*`, the descriptor, the kind), then the
+    # arguments of apa_attn_head_eval_step_cached from X on
+    'apa_epoch_order': (c_int, [c_void_p, c_int, c_uint64, c_uint64, c_void_p]),
+    'apa_attn_head_train_epoch_cached': (c_int, [c_void_p] * 11 + [c_float, c_float] + [c_void_p] * 13 +
+                                         [c_size_t] + [c_int] * 6 + [c_uint, c_float, c_uint64, c_uint64, c_int,
+                                                                     c_void_p]),
+    'apa_attn_head_eval_epoch_cached': (c_int, [c_void_p, c_void_p, c_int] + [c_void_p] * 15 + [c_size_t] +
+                                        [c_int] * 6 + [c_uint, c_int, c_void_p]),
     'apa_pose_head_workspace_bytes': (c_size_t, [c_int] * 6),
     'apa_pose_head_fwd': (c_int, [c_void_p] * 8 + [c_size_t] + [c_int] * 6 + [c_void_p]),
     'apa_pose_head_bwd': (c_int, [c_void_p] * 7 + [c_int] + [c_void_p] * 5 + [c_size_t] + [c_int] * 6 +
@@ -538,6 +547,13 @@ class FeatureCache(object):
         for a in range(0, end, batch_size):
             yield perm[a:min(a + batch_size, end)]
 
+    def order(self, seed: int, epoch: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The visiting order of epoch `epoch` of the run keyed by `seed`: all T image ids, int32 on the cache's device,
+        by the counter-based rule of include/apa.h (`epoch_order`: one launch on a GPU cache, the host restatement on
+        a CPU one -- the same bits).  `out`: an int32 [T] tensor rewritten in place, so that an epoch call bound to it
+        follows without a rebind.  `epoch` / `video_epoch` (torch.randperm) are other orders."""
+        return epoch_order(self.T, seed, epoch, self.device, out=out)
+
     # ---- a cache of video FRAMES: clips sampled on the device (include/apa.h: apa_sample_clip_frames) ----
     def set_videos(self, first, count, labels: Optional[torch.Tensor] = None,
                    targets: Optional[torch.Tensor] = None) -> None:
@@ -680,6 +696,97 @@ class CachedClips(CachedBatch):
         self.labels = None if cache.video_labels is None else torch.zeros((int(B),), dtype=torch.int64, device=dev)
         self.targets = None if cache.video_targets is None else torch.zeros(
             (int(B), int(cache.video_targets.shape[1])), dtype=torch.float32, device=dev)
+
+
+# --------------------------------------------------------------------------------------------
+# a whole epoch over the cache (include/apa.h: apa_epoch_order, apa_epoch, apa_epoch_sgd)
+# --------------------------------------------------------------------------------------------
+class ApaEpoch(ctypes.Structure):
+    """`apa_epoch` of include/apa.h (field order is the ABI)."""
+    _fields_ = [('order', c_void_p), ('count', c_int)]
+
+
+class ApaEpochSgd(ctypes.Structure):
+    """`apa_epoch_sgd` of include/apa.h (field order is the ABI)."""
+    _fields_ = [('nseg', c_int), ('weights', c_void_p), ('sizes', c_void_p), ('weight_decay', c_void_p),
+                ('grad_flat', c_void_p), ('acc_flat', c_void_p), ('lr', c_void_p), ('momentum', c_float),
+                ('grad_scale', c_float)]
+
+
+_EPOCH_ROUNDS = 6
+_M64 = (1 << 64) - 1
+
+
+def _mix64(s: int, o: int) -> int:
+    """the dropout key's splitmix64 step (include/apa.h: apa_epoch_order), python integers mod 2^64"""
+    z = (s + 0x9E3779B97F4A7C15 * (o + 1)) & _M64
+    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & _M64
+    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & _M64
+    return z ^ (z >> 31)
+
+
+def _epoch_hash(x: np.ndarray, k0: int, k1: int) -> np.ndarray:
+    """the dropout mask's two-round 24-bit multiply-xorshift mix on uint64 lanes that hold 32-bit values"""
+    u, m32, m24 = np.uint64, np.uint64(0xFFFFFFFF), np.uint64(0xFFFFFF)
+    x = x ^ u(k0)
+    x = x ^ (x >> u(16))
+    x = ((x & m24) * u(0xB5297B)) & m32
+    x = x ^ (x >> u(13))
+    x = x ^ u(k1)
+    x = x ^ (x >> u(17))
+    x = ((x & m24) * u(0x68E31D)) & m32
+    return x ^ (x >> u(15))
+
+
+def _epoch_order_rule_cpu(T: int, seed: int, epoch: int) -> torch.Tensor:
+    """apa_epoch_order's rule restated in numpy (include/apa.h), bit for bit: int32 [T] on the CPU.  A keyed six-round
+    alternating Feistel network on the smallest power-of-two domain >= max(T, 4), walked until the image is < T."""
+    T = int(T)
+    if not 1 <= T < 2 ** 31:
+        raise ApaError('epoch_order: 1 <= T < 2^31 expected (got {})'.format(T))
+    b = max(2, (T - 1).bit_length())
+    lb = b // 2
+    rb = np.uint64(b - lb)
+    mL, mR = np.uint64((1 << lb) - 1), np.uint64((1 << (b - lb)) - 1)
+    h = _mix64(int(seed) & _M64, int(epoch) & _M64)
+    keys = [_mix64(h, r) for r in range(_EPOCH_ROUNDS)]
+
+    def perm(x):
+        L, R = x >> rb, x & mR
+        for r, z in enumerate(keys):
+            if r % 2 == 0:
+                L = L ^ (_epoch_hash(R, z & 0xFFFFFFFF, z >> 32) & mL)
+            else:
+                R = R ^ (_epoch_hash(L, z & 0xFFFFFFFF, z >> 32) & mR)
+        return (L << rb) | R
+
+    x = perm(np.arange(T, dtype=np.uint64))
+    while True:
+        walk = np.nonzero(x >= np.uint64(T))[0]
+        if walk.size == 0:
+            return torch.from_numpy(x.astype(np.int32))
+        x[walk] = perm(x[walk])
+
+
+def epoch_order(T: int, seed: int, epoch: int, device, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """order int32 [T]: order[i] = the image visited at position i of epoch `epoch` of the run keyed by `seed`, a
+    permutation of [0, T) that is a pure function of (T, seed, epoch) (include/apa.h: apa_epoch_order).  On a GPU
+    `device` it is ONE launch -- no sort, no workspace, no host synchronisation, capturable; on the CPU the host
+    restatement of the same rule gives the same bits.  `out`: an int32 [T] tensor on `device`, rewritten in place."""
+    T, device = int(T), torch.device(device)
+    if not 1 <= T < 2 ** 31:
+        raise ApaError('epoch_order: 1 <= T < 2^31 expected (got {})'.format(T))
+    if out is not None and (out.dtype != torch.int32 or out.dim() != 1 or out.numel() != T or
+                            out.device.type != device.type or not out.is_contiguous()):
+        raise ApaError('epoch_order: out must be a contiguous int32 [{}] tensor on {}'.format(T, device))
+    if out is None:
+        out = torch.empty((T,), dtype=torch.int32, device=device)
+    if device.type != 'cuda':
+        out.copy_(_epoch_order_rule_cpu(T, seed, epoch))
+        return out
+    rc = load_library().apa_epoch_order(out.data_ptr(), T, int(seed) & _M64, int(epoch) & _M64, _stream_ptr())
+    _check(rc, 'apa_epoch_order')
+    return out
 
 
 def _cached(who: str, X, Xatt, frozen: bool = True) -> Optional['CachedBatch']:
@@ -2659,6 +2766,212 @@ class BoundMomentumSGD:
         rc = self._fn(*self._args.head, lr, momentum, grad_scale, *self._tail, st)
         if rc != 0:
             _check(rc, self._who)
+
+
+def _epoch_order_arg(who: str, order: torch.Tensor, cache: FeatureCache) -> torch.Tensor:
+    if not isinstance(order, torch.Tensor) or order.dtype != torch.int32 or order.dim() != 1 or \
+            not order.is_contiguous() or order.device != cache.device:
+        raise ApaError('{}: order must be a contiguous int32 vector on the cache\'s device (FeatureCache.order)'
+                       .format(who))
+    return order
+
+
+def _epoch_outputs(who: str, obj, outputs, shapes, dev) -> None:
+    """set obj.<name> for every (name, shape, dtype) of `shapes`: the caller's tensor from `outputs` (same element
+    count and dtype, contiguous, on `dev`) or a fresh one"""
+    outputs = dict(outputs or {})
+    for name, shape, dtype in shapes:
+        t = outputs.pop(name, None)
+        if t is None:
+            t = torch.empty(shape, dtype=dtype, device=dev)
+        elif t.dtype != dtype or t.numel() != int(np.prod(shape)) or not t.is_contiguous() or t.device != dev:
+            raise ApaError('{}: outputs[{!r}] must be a contiguous {} tensor of {} elements on {}'.format(
+                who, name, dtype, int(np.prod(shape)), dev))
+        setattr(obj, name, t)
+    if outputs:
+        raise ApaError('{}: unknown outputs {}'.format(who, sorted(outputs)))
+
+
+def _epoch_cache(who: str, cache: FeatureCache):
+    """(N-independent) shape of a cache an epoch call can read: (P, C, dtype code)"""
+    if not isinstance(cache, FeatureCache):
+        raise ApaError('{}: a FeatureCache expected'.format(who))
+    if not cache.features.is_cuda:
+        raise ApaError('{}: the cache must live in GPU memory; the HIP path has no CPU fallback'.format(who))
+    C = cache.shape[-1]
+    return int(np.prod(cache.shape[1:])) // C, C, _feat_dtype(cache.features)
+
+
+class HeadTrainEpoch:
+    """apa_attn_head_train_epoch_cached bound to caller-owned buffers, everything marshalled ONCE: a whole epoch of
+    frozen-feature training on a resident FeatureCache -- `steps` times (the gathered one-call step on the next `N` ids
+    of `order`, then the fused momentum-SGD update with that step's learning rate) -- as ONE foreign call, bit-identical
+    in every output, weight and accumulator to the loop of `HeadTrainStep.rebind(index=, offset=) + run()` and
+    `BoundMomentumSGD.run(lr[s], ...)`.
+
+    `grads = (dWa, dba, dWt, dbt)`: where the step writes its gradients -- views of `grad_flat`, the flat bucket the
+    update reads; `weights` / `weight_decay` / `grad_flat` / `acc_flat`: BoundMomentumSGD's arguments (segments the
+    step does not write decay on whatever their window of `grad_flat` holds).  `labels=None`: the cache's own labels,
+    read through the order; else pass `labels` int64 [count], in visiting order, to `run`.  `offset`: the dropout
+    offset of the first step (step s uses offset + s), or a 1-element int64 CUDA tensor (the device counter, which
+    advances by itself).  `steps`: the most steps one `run` may take (the loss log's rows).
+    Outputs: `loss` [steps, 1+N] (the epoch's log: row s = step s's mean and per-example losses), and the LAST step's
+    `logits`, `att`, `zsave`, `abar`, `G`; `outputs={name: tensor}` binds caller-owned buffers in their place."""
+
+    def __init__(self, cache, N, Wa, ba, Wt, bt, grads, weights, weight_decay, grad_flat, acc_flat, *, steps,
+                 momentum=0.9, update_grad_scale=1.0, labels_cached=True, flags=0, keep_prob=1.0, seed=0, offset=0,
+                 loss_wt=1.0, grad_scale=1.0, workspace=None, hooks=None, outputs=None):
+        who = 'HeadTrainEpoch'
+        self.lib = load_library()
+        P, C, dt = _epoch_cache(who, cache)
+        N, steps = int(N), int(steps)
+        if N < 1 or steps < 1:
+            raise ApaError('{}: N >= 1 and steps >= 1 expected'.format(who))
+        if Wa.shape[1] != 1:
+            raise ApaError('{}: a feature cache feeds the class-agnostic head (M == 1)'.format(who))
+        if labels_cached and cache.labels is None:
+            raise ApaError('{}: labels_cached needs a FeatureCache with labels'.format(who))
+        K, dev = Wt.shape[1], cache.device
+        self.cache, self.N, self.steps, self.hooks = cache, N, steps, hooks
+        f32 = torch.float32
+        _epoch_outputs(who, self, outputs, (('logits', (N, K), f32), ('att', (N, P, 1), f32), ('zsave', (N, C), f32),
+                                            ('abar', (N,), f32), ('loss', (steps, 1 + N), f32), ('G', (N, K), f32)), dev)
+        flags |= APA_FLAG_FROZEN_INPUT
+        need = int(self.lib.apa_attn_pool_workspace_bytes(N, P, C, C, K, 1, flags))
+        if workspace is None or workspace.numel() < need:
+            workspace = torch.empty((max(need, 16),), dtype=torch.uint8, device=dev)
+        self.workspace = workspace
+        dWa, dba, dWt, dbt = grads
+        a = self._opt_args = _OptimizerArgs(weights, weight_decay, (('grad_flat', grad_flat), ('acc_flat', acc_flat)),
+                                            who=who)
+        self._lr = (c_float * steps)()
+        nseg, wptr, sizes, wd, gptr, aptr = a.head
+        self._sgd = ApaEpochSgd(nseg, ctypes.addressof(wptr), ctypes.addressof(sizes), ctypes.addressof(wd), gptr, aptr,
+                                ctypes.addressof(self._lr), float(momentum), float(update_grad_scale))
+        self._ep = ApaEpoch(None, 0)
+        self._fc = ApaFeatureCache(None, cache.T, 1 if labels_cached else 0, cache.status.data_ptr())
+        self._labels_cached = bool(labels_cached)
+        self._keep = (Wa, ba, Wt, bt, grads, offset, seed, None, None)
+        seed, off, flags = _rng_key(seed, offset, flags)     # the pointers below stay valid
+        self._off_dev = isinstance(offset, torch.Tensor)
+        X = cache.features.data_ptr()
+        self._args = [
+            X, X, _dev_ptr(Wa, 'Wa', torch.float32), _dev_ptr(ba, 'ba', torch.float32),
+            _dev_ptr(Wt, 'Wt', torch.float32), _dev_ptr(bt, 'bt', torch.float32),
+            _dev_ptr(cache.labels, 'labels', torch.int64) if labels_cached else None,
+            float(loss_wt), float(grad_scale),
+            self.logits.data_ptr(), self.att.data_ptr(), self.zsave.data_ptr(), self.abar.data_ptr(),
+            self.loss.data_ptr(), self.G.data_ptr(), None, None, _dev_ptr(dWa, 'dWa', torch.float32),
+            _dev_ptr(dba, 'dba', torch.float32), _dev_ptr(dWt, 'dWt', torch.float32),
+            _dev_ptr(dbt, 'dbt', torch.float32), workspace.data_ptr(), workspace.numel(), N, P, C, C, K, 1,
+            flags, float(keep_prob), int(seed), off, dt]
+        self._pre = (ctypes.addressof(self._ep), ctypes.addressof(self._sgd), ctypes.addressof(self._fc))
+
+    def run(self, order, lr, offset=None, labels=None, stream: Optional[int] = None, hooks=None) -> int:
+        """Enqueue the epoch over `order` (int32 on the cache's device, a whole number of batches: FeatureCache.order,
+        or its first steps * N entries) with `lr[s]` the learning rate of update s (a sequence of order.numel() / N
+        floats, or one float for all).  `offset` (int): another dropout offset for the first step.  `labels`: int64
+        [count] in visiting order, for an epoch built with labels_cached=False.  Returns the number of steps."""
+        who = 'HeadTrainEpoch.run'
+        order = _epoch_order_arg(who, order, self.cache)
+        count = int(order.numel())
+        steps = count // self.N
+        if steps < 1 or count % self.N or steps > self.steps:
+            raise ApaError('{}: {} ids are not 1..{} whole batches of {}'.format(who, count, self.steps, self.N))
+        lrs = [float(lr)] * steps if isinstance(lr, (int, float)) else [float(v) for v in lr]
+        if len(lrs) != steps:
+            raise ApaError('{}: one learning rate per step expected ({} for {} steps)'.format(who, len(lrs), steps))
+        self._lr[:steps] = lrs
+        if self._labels_cached:
+            if labels is not None:
+                raise ApaError('{}: the epoch reads the cache\'s labels through the order'.format(who))
+        else:
+            if labels is None or labels.numel() != count:
+                raise ApaError('{}: labels int64 [{}] in visiting order expected'.format(who, count))
+            self._args[6] = _dev_ptr(labels, 'labels', torch.int64)
+        if offset is not None:
+            if self._off_dev:
+                raise ApaError('{}: the epoch was bound to a device-side dropout counter'.format(who))
+            self._args[-2] = int(offset)
+        self._keep = self._keep[:7] + (order, labels)
+        self._ep.order, self._ep.count = order.data_ptr(), count
+        h = self.hooks if hooks is None else hooks
+        rc = self.lib.apa_attn_head_train_epoch_cached(*self._pre, _hooks_ptr(h), *self._args,
+                                                       _stream_ptr() if stream is None else stream)
+        if rc != 0:
+            _check(rc, 'apa_attn_head_train_epoch_cached')
+        return steps
+
+
+class HeadEvalEpoch:
+    """apa_attn_head_eval_epoch_cached bound once: a validation pass over `count` images of a resident FeatureCache in
+    batches of `N` (the last one shorter) as ONE foreign call, bit-identical to the loop of HeadEvalStep on
+    `cache.select(order[s*N:(s+1)*N])`.  `scores`: 'softmax' | 'sigmoid'.  `capacity`: the most rows one `run` may
+    visit.  `want_loss` (softmax scores, a cache with labels): the per-step losses, read through the order.
+    Outputs: `logits`, `probs` [capacity,K] and `pred` [capacity] (rows [0, count) are written, nothing behind them),
+    `loss` [ceil(capacity / N), 1+N] or None, and the LAST step's `att`, `zsave`, `abar`.  `run(..., probs=t)` writes
+    the scores into the caller's float32 [count,K] tensor instead (eval_utils.DeviceEvaluation.reserve)."""
+
+    def __init__(self, cache, N, Wa, ba, Wt, bt, *, capacity, flags=0, scores='softmax', want_loss=False,
+                 workspace=None, outputs=None):
+        who = 'HeadEvalEpoch'
+        self.lib = load_library()
+        P, C, dt = _epoch_cache(who, cache)
+        N, capacity = int(N), int(capacity)
+        if N < 1 or capacity < 1:
+            raise ApaError('{}: N >= 1 and capacity >= 1 expected'.format(who))
+        if Wa.shape[1] != 1:
+            raise ApaError('{}: a feature cache feeds the class-agnostic head (M == 1)'.format(who))
+        if scores not in ('softmax', 'sigmoid'):
+            raise ApaError('{}: scores must be \'softmax\' or \'sigmoid\' (got {!r})'.format(who, scores))
+        if want_loss and (scores != 'softmax' or cache.labels is None):
+            raise ApaError('{}: want_loss needs softmax scores and a FeatureCache with labels'.format(who))
+        K, dev = Wt.shape[1], cache.device
+        self.cache, self.N, self.capacity, self.K = cache, N, capacity, K
+        flags &= ~APA_FLAG_TRAIN
+        f32 = torch.float32
+        self.loss = None
+        _epoch_outputs(who, self, outputs,
+                       (('logits', (capacity, K), f32), ('probs', (capacity, K), f32), ('pred', (capacity,), torch.int64),
+                        ('att', (N, P, 1), f32), ('zsave', (N, C), f32), ('abar', (N,), f32)) +
+                       ((('loss', ((capacity + N - 1) // N, 1 + N), f32),) if want_loss else ()), dev)
+        need = int(self.lib.apa_attn_pool_workspace_bytes(N, P, C, C, K, 1, flags))
+        if workspace is None or workspace.numel() < need:
+            workspace = torch.empty((max(need, 16),), dtype=torch.uint8, device=dev)
+        self.workspace = workspace
+        self._ep = ApaEpoch(None, 0)
+        self._fc = ApaFeatureCache(None, cache.T, 1 if want_loss else 0, cache.status.data_ptr())
+        self._keep = (Wa, ba, Wt, bt, None, None)
+        X = cache.features.data_ptr()
+        self._args = [
+            X, X, _dev_ptr(Wa, 'Wa', torch.float32), _dev_ptr(ba, 'ba', torch.float32),
+            _dev_ptr(Wt, 'Wt', torch.float32), _dev_ptr(bt, 'bt', torch.float32),
+            _dev_ptr(cache.labels, 'labels', torch.int64) if want_loss else None, self.logits.data_ptr(),
+            self.att.data_ptr(), self.zsave.data_ptr(), self.abar.data_ptr(), _dev_ptr(self.loss, 'loss'),
+            self.probs.data_ptr(), self.pred.data_ptr(), workspace.data_ptr(), workspace.numel(),
+            N, P, C, C, K, 1, flags, dt]
+        self._pre = (ctypes.addressof(self._ep), ctypes.addressof(self._fc),
+                     APA_SCORES_SOFTMAX if scores == 'softmax' else APA_SCORES_SIGMOID)
+
+    def run(self, order, count: Optional[int] = None, probs: Optional[torch.Tensor] = None,
+            stream: Optional[int] = None) -> int:
+        """Enqueue the pass over the first `count` ids of `order` (default: all of it).  Returns the number of steps."""
+        who = 'HeadEvalEpoch.run'
+        order = _epoch_order_arg(who, order, self.cache)
+        count = int(order.numel()) if count is None else int(count)
+        if not 1 <= count <= min(int(order.numel()), self.capacity):
+            raise ApaError('{}: count = {} outside 1..{} (the order\'s length and the capacity)'.format(
+                who, count, min(int(order.numel()), self.capacity)))
+        if probs is not None and (tuple(probs.shape) != (count, self.K) or probs.device != self.cache.device):
+            raise ApaError('{}: probs float32 [{}, {}] on the cache\'s device expected'.format(who, count, self.K))
+        self._args[12] = self.probs.data_ptr() if probs is None else _dev_ptr(probs, 'probs', torch.float32)
+        self._keep = self._keep[:4] + (order, probs)
+        self._ep.order, self._ep.count = order.data_ptr(), count
+        rc = self.lib.apa_attn_head_eval_epoch_cached(*self._pre, *self._args,
+                                                      _stream_ptr() if stream is None else stream)
+        if rc != 0:
+            _check(rc, 'apa_attn_head_eval_epoch_cached')
+        return (count + self.N - 1) // self.N
 
 
 def adam_step(weights, weight_decay, grad_flat, m_flat, v_flat, lr, t, beta1=0.9, beta2=0.999, epsilon=1e-8,

@@ -1064,6 +1064,7 @@ class FusedHeadStep:
         self._want_dx = True
         self._fp8 = False
         self._cb = False
+        self._epoch = self._epoch_key = None     # the bound epoch call of train_epoch
         self.probe_events = None
 
     @staticmethod
@@ -1129,6 +1130,7 @@ class FusedHeadStep:
                 self._optimizer.detach_weight_images(st)
         self._steps.clear()
         self._step_obj = self._key = None
+        self._epoch = self._epoch_key = None
 
     def make_optimizer(self, learning_rate: float, deploy_config: Optional[DeploymentConfig] = None):
         """deploy.configure_optimizer on the head's parameters (the nn.Parameters themselves: their `_version` feeds
@@ -1405,6 +1407,82 @@ class FusedHeadStep:
                 ep['TemporalAttention'] = st.tatt.view(-1, self._frames, 1, 1)
         return total, ep
 
+    def epoch_unsupported_reason(self, cache=None) -> str:
+        """why `train_epoch` cannot run this configuration (on this cache); '' when it can.  The epoch call is the flat
+        CachedBatch step under the softmax cross-entropy with the fused momentum-SGD update behind every step."""
+        tr = self.cfg.TRAIN
+        why = self.fp8_unsupported_reason(self.head, self.network_fn)
+        if why:
+            return why
+        if not self.frozen_features:
+            return 'frozen_features=False (a cache has no gradient: build the step with frozen_features=True)'
+        if tr.LOSS_FN_ACTION != 'softmax-xentropy':
+            return 'LOSS_FN_ACTION %r (the epoch call takes the softmax cross-entropy)' % tr.LOSS_FN_ACTION
+        if tr.OPTIMIZER not in ('momentum', 'sgd'):
+            return 'TRAIN.OPTIMIZER %r (the epoch call runs the momentum / sgd update)' % tr.OPTIMIZER
+        if int(tr.ITER_SIZE) != 1:
+            return 'TRAIN.ITER_SIZE %d (gradient accumulation over micro-steps)' % int(tr.ITER_SIZE)
+        if self.clipper is not None and self.clipper.active:
+            return 'TRAIN.CLIP_GRADIENTS > 0 (an active gradient clipper between the step and the update)'
+        if self.loss_scale != 1.0:
+            return ('more than one clone (loss_scale %r: the gradients of an epoch call are not all-reduced)'
+                    % self.loss_scale)
+        if self.temporal is not None:
+            return 'a TemporalAttention conv (clips are not served by the epoch call)'
+        if cache is not None and cache.labels is None:
+            return 'a FeatureCache without labels (the epoch reads them through the order)'
+        return ''
+
+    def train_epoch(self, cache, batch_size: int, order, lr=None):
+        """A whole epoch of frozen-feature training on a resident `FeatureCache` as ONE host call
+        (`cof.HeadTrainEpoch`: apa_attn_head_train_epoch_cached): steps = order.numel() / batch_size times the step
+        `__call__` runs on `cache.select(order[s*N:(s+1)*N])` (the cache's own labels, a fresh dropout mask per step)
+        followed by the update `opt.step()` runs, on this object's bucket and the optimiser's accumulators -- the same
+        launches, the same bits.  `order`: int32 on the cache's device (`cache.order(seed, epoch)`, or its first
+        steps * batch_size ids).  `lr`: one learning rate per step (e.g. `configure_learning_rate` per global step), or
+        None for the optimiser's own.  Needs `make_optimizer()` first.  The staleness guards run once, in front; the
+        head's step counter advances by `steps`.  Returns the loss log [steps, 1 + batch_size] (row s: the mean and
+        the per-example losses of step s) as a device tensor -- nothing synchronises.  Served: what a flat CachedBatch
+        is served with, under the softmax cross-entropy, TRAIN.OPTIMIZER momentum / sgd, ITER_SIZE 1, no active
+        clipper, one clone; anything else is a ValueError that names the reason."""
+        from .custom_ops import custom_ops_factory as cof
+        if self._optimizer is None:
+            raise ValueError('FusedHeadStep.train_epoch: make_optimizer() first (the epoch call runs its update)')
+        why = self.epoch_unsupported_reason(cache)
+        if why:
+            raise ValueError('FusedHeadStep.train_epoch: an epoch call is not served with %s' % why)
+        opt, head = self._optimizer, self.head
+        opt.check_fresh()                                # weights written behind the optimiser's back?
+        self._check_frozen_fresh()
+        if opt.operand_copies():
+            raise ValueError('FusedHeadStep.train_epoch: an epoch call is not served with operand copies attached to '
+                             'the optimiser (%s): its update rewrites none' % ', '.join(opt._watched))
+        N = int(batch_size)
+        count = int(order.numel())
+        if N < 1 or count < N or count % N:
+            raise ValueError('FusedHeadStep.train_epoch: order holds %d ids, not a whole number of batches of %d'
+                             % (count, N))
+        steps = count // N
+        lrs = [float(opt.lr)] * steps if lr is None else [float(v) for v in lr]
+        if len(lrs) != steps:
+            raise ValueError('FusedHeadStep.train_epoch: one learning rate per step expected (%d for %d steps)'
+                             % (len(lrs), steps))
+        p, v = {n: t.data for n, t in self.params.items()}, self._grad_out
+        key = (id(cache), N, tuple(t.data_ptr() for t in p.values()), self.bucket.flat.data_ptr(), opt.acc.data_ptr(),
+               tuple(opt.wd), float(opt.momentum))
+        if self._epoch is None or self._epoch_key != key or self._epoch.steps < steps:
+            self._epoch = cof.HeadTrainEpoch(
+                cache, N, p['att_weights'], p['att_biases'], p['td_weights'], p['td_biases'],
+                (v['att_weights'], v['att_biases'], v['td_weights'], v['td_biases']),
+                [p[n] for n in self.bucket.names], list(opt.wd), self.bucket.flat, opt.acc, steps=steps,
+                momentum=opt.momentum, flags=cof.attn_flags(head.softmax_att, head.relu_att, True, False),
+                keep_prob=head.keep_prob, seed=head.seed, offset=head._step,
+                loss_wt=float(self.cfg.TRAIN.LOSS_FN_ACTION_WT), grad_scale=self.loss_scale, hooks=head.hooks)
+            self._epoch_key = key
+        self._epoch.run(order, lrs, offset=head._step)
+        head._step += steps                              # a fresh dropout mask per step, as __call__ leaves it
+        return self._epoch.loss[:steps]
+
 
 class FusedHeadEval:
     """The evaluation counterpart of FusedHeadStep: what eval.py:181-197 computes from `network_fn(images)` -- the
@@ -1555,6 +1633,46 @@ class FusedHeadEval:
         from . import eval_utils
         w = self.head.td_weights
         return eval_utils.DeviceEvaluation(capacity, int(w.shape[1]), w.device, multi_label=self.multi_label)
+
+    def evaluate_cache(self, cache, batch_size: int, meter=None, order=None):
+        """A whole validation pass over a resident `FeatureCache` as ONE host call (`cof.HeadEvalEpoch`:
+        apa_attn_head_eval_epoch_cached): the images `order` names (int32 on the cache's device; default all T, in
+        cache order) in batches of `batch_size`, the last one shorter, with the scores written straight into
+        `meter.reserve(count)` -- no copy, no synchronisation -- and the truth taken from `cache.labels[order]`.
+        `meter`: an `eval_utils.DeviceEvaluation` (default: `new_evaluation(count)`); it is returned, and
+        `meter.result()` equals that of a meter fed by `__call__` batch by batch.  Served: what a flat CachedBatch is
+        served with, softmax scores, a cache with labels; anything else is a ValueError that names the reason.
+        `self.epoch` is the bound pass (`logits`, `pred`, the last batch's `att`)."""
+        import torch
+        from .custom_ops import custom_ops_factory as cof
+        why = FusedHeadStep.fp8_unsupported_reason(self.head, self.network_fn)
+        if not why and self.multi_label:
+            why = ('LOSS_FN_ACTION %r (multi-hot targets: the cache\'s labels are class ids)'
+                   % self.cfg.TRAIN.LOSS_FN_ACTION)
+        if not why and cache.labels is None:
+            why = 'a FeatureCache without labels (the truth is cache.labels[order])'
+        if why:
+            raise ValueError('FusedHeadEval.evaluate_cache: a cache pass is not served with %s' % why)
+        N = int(batch_size)
+        if N < 1:
+            raise ValueError('FusedHeadEval.evaluate_cache: batch_size >= 1 expected')
+        if order is None:
+            order = torch.arange(cache.T, dtype=torch.int32, device=cache.device)
+        count = int(cof._epoch_order_arg('FusedHeadEval.evaluate_cache', order, cache).numel())
+        if meter is None:
+            meter = self.new_evaluation(count)
+        h = self.head
+        key = (id(cache), N, tuple(p.data_ptr() for p in self._params()))
+        ep = getattr(self, 'epoch', None)
+        if ep is None or self._epoch_key != key or ep.capacity < count:
+            ep = self.epoch = cof.HeadEvalEpoch(
+                cache, N, h.att_weights.data, h.att_biases.data, h.td_weights.data, h.td_biases.data, capacity=count,
+                flags=cof.attn_flags(h.softmax_att, h.relu_att, False, False), scores='softmax')
+            self._epoch_key = key
+        scores, truth = meter.reserve(count)
+        truth.copy_(cache.labels[order.long().clamp_(0, cache.T - 1)])       # (an id outside the cache is clamped, as
+        ep.run(order, count, probs=scores)                                   # the kernels clamp it)
+        return meter
 
     def explain(self, images, classes=None, topk: int = 1, overlay: bool = True, input_images=None):
         """Why the batch was given its classes: the bottom-up map, the top-down map of T chosen classes per image and

@@ -142,6 +142,21 @@ class DeviceEvaluation:
         self._truth[self._n:self._n + n].copy_(labels, non_blocking=True)
         self._n += n
 
+    def reserve(self, n: int):
+        """The next `n` rows as views `(scores [n,K], truth [n] or [n,K])` of the meter's own buffers, the cursor
+        moved behind them: a producer writes its scores (and the truth) in place instead of handing copies to
+        `update` (deploy.FusedHeadEval.evaluate_cache: the evaluation pass's `probs` ARE these rows).  The rows count
+        as accumulated at once: write both views before `result()`."""
+        n = int(n)
+        if n < 1:
+            raise ValueError('DeviceEvaluation.reserve: n >= 1 expected (got %d)' % n)
+        if self._n + n > self.capacity:
+            raise ValueError('DeviceEvaluation.reserve: %d rows behind %d overflow the capacity of %d'
+                             % (n, self._n, self.capacity))
+        a = self._n
+        self._n += n
+        return self._scores[a:a + n], self._truth[a:a + n]
+
     def result(self):
         import torch
         from .custom_ops import custom_ops_factory as cof

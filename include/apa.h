@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define APA_VERSION 313 /* major*10000 + minor*100 + patch */
+#define APA_VERSION 314 /* major*10000 + minor*100 + patch */
 
 typedef enum apa_status {
   APA_OK = 0,
@@ -1144,6 +1144,73 @@ int apa_momentum_sgd_step_shadow(int nseg, float* const* weights, const size_t* 
                                  const float* weight_decay, const float* grad_flat, float* acc_flat,
                                  float lr, float momentum, float grad_scale, void* const* bf16_shadow,
                                  void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * A whole epoch over a resident feature cache behind ONE host call: the visiting order drawn on the device, the step
+ * and update loop in C, a validation pass that writes every row's scores where the caller wants them.
+ *
+ * apa_epoch_order: order[i] (int32 [T], device, 4-byte aligned) = the image visited at position i of epoch `epoch`
+ * of the run keyed by `seed`; a permutation of [0, T) for every 1 <= T < 2^31.  Counter-based -- every element is
+ * computed on its own from (seed, epoch, i, T) -- in one launch: no atomics, no workspace, no sort, no allocation,
+ * capturable; identical calls give identical bits.  The rule, for a host restatement (all arithmetic unsigned):
+ *   mix64(s, o):   z = s + 0x9E3779B97F4A7C15 * (o + 1);  z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9;
+ *                  z = (z ^ z >> 27) * 0x94D049BB133111EB;  return z ^ z >> 31          (mod 2^64: the dropout key's)
+ *   hash(x, k0, k1), 32 bits: x ^= k0;  x ^= x >> 16;  x = (x & 0xFFFFFF) * 0xB5297B;  x ^= x >> 13;  x ^= k1;
+ *                  x ^= x >> 17;  x = (x & 0xFFFFFF) * 0x68E31D;  x ^= x >> 15          (mod 2^32: the dropout mask's)
+ *   b = max(2, bits of T - 1), lb = b / 2, rb = b - lb;  h = mix64(seed, epoch);  key_r = mix64(h, r), r = 0..5,
+ *   k0 = its low and k1 = its high 32 bits
+ *   perm(x): L = x >> rb, R = x & (2^rb - 1);  for r = 0..5: r even: L ^= hash(R, k0_r, k1_r) & (2^lb - 1),
+ *            r odd: R ^= hash(L, k0_r, k1_r) & (2^rb - 1);  return L << rb | R          (a bijection of [0, 2^b))
+ *   order[i] = perm applied to i, and again while the image is >= T (cycle walking; two applications on average)
+ * Refused with APA_ERR_INVALID_ARG: a NULL or misaligned order, T < 1.
+ *
+ * apa_attn_head_train_epoch_cached(ep, opt, cache, hooks, <apa_attn_head_train_step_cached's arguments from X on>) IS,
+ * bit for bit in every output, weight and accumulator, this loop of steps = ep->count / N passes:
+ *   for s in 0 .. steps-1:
+ *     apa_attn_head_train_step_cached with cache.index = ep->order + s*N, dropout offset + s, loss + s*(1+N)
+ *     apa_momentum_sgd_step(opt->nseg .. opt->acc_flat, opt->lr[s], opt->momentum, opt->grad_scale, stream)
+ * Under APA_FLAG_RNG_DEVICE the counter in HBM advances by itself and `offset` is passed unchanged.  loss is the
+ * epoch's log [steps][1+N]; logits, att, zsave, abar and G hold the last step's values; dWa..dbt are opt->grad_flat's
+ * segments where the update is to see them.  cache->index is ignored; cache_images, labels_cached and status mean what
+ * they mean in the step: with labels_cached = 0 `labels` is [count] in visiting order, status counts a clamped id once
+ * per visit.  opt->lr is a HOST array read during the call.  No allocation, no synchronisation; workspace: the step's.
+ * Refused before the first launch, in this order: a NULL opt / lr; a NULL ep / order; a NULL cache; N < 1; count < N or
+ * count % N != 0; steps * N past 2^31 - 1; what apa_momentum_sgd_step refuses (nseg, NULL arrays, a NULL weight); then
+ * everything apa_attn_head_train_step_cached refuses, both halves' checks run once for the shape.
+ *
+ * apa_attn_head_eval_epoch_cached(ep, cache, scores_kind, <apa_attn_head_eval_step_cached's arguments from X on>) IS
+ * the loop of steps = ceil(ep->count / N) evaluation steps on order + s*N: the per-row outputs advance by s*N rows
+ * (logits, probs [count,K], pred [count]; labels [count] unless labels_cached), loss, where asked for, is logged
+ * [steps][1+N]; att, zsave and abar are the last step's.  The last step runs the remaining count - (steps-1)*N rows
+ * as a smaller batch in the same workspace, its shape checked before the first launch too; nothing is written past
+ * row count.  Refusals as above (count < 1 in place of the batch rule), then the evaluation step's.
+ */
+typedef struct apa_epoch {          /* what is visited */
+  const int32_t* order;             /* device, [count], 4-byte aligned: image ids in visiting order            */
+  int count;                        /* train: steps = count / N, count % N == 0; eval: steps = ceil(count / N) */
+} apa_epoch;
+
+typedef struct apa_epoch_sgd {      /* the update behind every step: apa_momentum_sgd_step's arguments         */
+  int nseg; float* const* weights; const size_t* sizes; const float* weight_decay;
+  const float* grad_flat; float* acc_flat;
+  const float* lr;                  /* HOST, [steps]: the learning rate of update s                            */
+  float momentum, grad_scale;
+} apa_epoch_sgd;
+
+int apa_epoch_order(int32_t* order, int T, uint64_t seed, uint64_t epoch, void* stream);
+int apa_attn_head_train_epoch_cached(const apa_epoch* ep, const apa_epoch_sgd* opt, const apa_feature_cache* cache,
+                                     const apa_hooks* hooks, const void* X, const void* Xatt, const float* Wa,
+                                     const float* ba, const float* Wt, const float* bt, const int64_t* labels,
+                                     float loss_wt, float grad_scale, float* logits, float* att, float* zsave,
+                                     float* abar, float* loss, float* G, void* dX, void* dXatt, float* dWa, float* dba,
+                                     float* dWt, float* dbt, void* ws, size_t ws_bytes, int N, int P, int C, int Ca,
+                                     int K, int M, unsigned flags, float keep_prob, uint64_t seed, uint64_t offset,
+                                     int dtype, void* stream);
+int apa_attn_head_eval_epoch_cached(const apa_epoch* ep, const apa_feature_cache* cache, int scores_kind,
+                                    const void* X, const void* Xatt, const float* Wa, const float* ba, const float* Wt,
+                                    const float* bt, const int64_t* labels, float* logits, float* att, float* zsave,
+                                    float* abar, float* loss, float* probs, int64_t* pred, void* ws, size_t ws_bytes,
+                                    int N, int P, int C, int Ca, int K, int M, unsigned flags, int dtype, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Weight images of the per-class head (M == K) kept current at WEIGHT-UPDATE time instead of being rebuilt by

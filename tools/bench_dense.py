@@ -37,6 +37,14 @@ headline stays the cfg 002 training workload); run this file directly for one wo
             process, medians of five and their spread: (a) the gathered step (apa_attn_head_train_step_cached) with a
             fresh shuffled index per step, (b) gather + rebind + the plain step -- the loop without the gathered
             kernels --, (c) the plain step on one fixed contiguous batch.
+  epoch002_fp8 / epoch002_bf16
+            a whole frozen-feature EPOCH of cfg 002 from the resident cache of cached002_* (--cache-images 2048, --batch
+            32: 64 steps, momentum SGD behind every step, a fresh order per epoch), three routes alternating in one
+            process, medians of five epochs, wall clock (one synchronise per epoch) and device events: (a) the epoch
+            call (apa_epoch_order + apa_attn_head_train_epoch_cached: one foreign call per epoch), (b) the lean loop
+            (HeadTrainStep.rebind + run + BoundMomentumSGD.run per step), (c) the deploy loop (FusedHeadStep on a
+            CachedBatch + opt.step() per step); and the validation pass, FusedHeadEval.evaluate_cache against the loop
+            of FusedHeadEval.__call__ + meter.update.
   cached_hmdb_clips_fp8 / cached_hmdb_clips_bf16 / cached_charades_fp8 / cached_charades_bf16
             one-call CLIP training step from a resident FRAME cache (--cache-images maps in videos of 25 frames, FP8 E4M3
             or bf16): --clips 8 x --frames 4, temporal attention, M = 1; K = 51 with the softmax cross-entropy (HMDB-51)
@@ -1268,6 +1276,147 @@ def run_cached(cof, dev, args, which):
             'clamped_ids': int(info['steps'][0]._cached.cache.status)}
 
 
+def _epoch_cfg002(dev, K, training):
+    from attentionalpoolingaction_amd import config as apa_config, nets_factory
+    apa_config.reset_cfg()
+    pre = 'USE_POSE_PRELOGITS_BASED_ATTENTION'
+    cfg = apa_config.cfg_from_dict({'MODEL_NAME': 'resnet_v1_101', 'NET': {pre: True, pre + '_SINGLE_LAYER_ATT': True},
+                                    'TRAIN': {'LOSS_FN_POSE': '', 'LOSS_FN_ACTION': 'softmax-xentropy'}})
+    return nets_factory.get_network_fn('resnet_v1_101', K, 16, cfg, is_training=training, device=dev), cfg
+
+
+def run_epoch(cof, dev, args, which):
+    """epoch002_fp8 / epoch002_bf16: a whole frozen-feature epoch of cfg 002 (K = 393, dropout keep 0.2, momentum SGD
+    behind every step) from the resident cache of cached002_*: --cache-images / --batch steps per epoch (2048 / 32 =
+    64), a fresh order per epoch.  Three routes ALTERNATE in one process, medians of five epochs each, every epoch
+    timed by wall clock around it with ONE synchronise at its end, and by a pair of device events around it:
+      a_epoch_call   cache.order(out=) + HeadTrainEpoch.run: one foreign call per epoch
+      b_lean_loop    cache.epoch() views; HeadTrainStep.rebind(index=) + run() + BoundMomentumSGD.run() per step
+      c_deploy_loop  deploy.FusedHeadStep(cache.select(index), None) + opt.step() per step
+    and the validation pass over the same cache: deploy.FusedHeadEval.evaluate_cache (one call, scores into the meter's
+    rows) against the loop of FusedHeadEval.__call__ + meter.update."""
+    from attentionalpoolingaction_amd import deploy
+    fp8 = which == 'epoch002_fp8'
+    N, H, T = args.batch, args.hw, args.cache_images - args.cache_images % args.batch
+    C, P, K = 2048, H * H, 393
+    steps = T // N
+    g = torch.Generator().manual_seed(42)
+    labels = torch.randint(0, K, (T,), generator=g).to(dev)
+    cache = cof.FeatureCache.empty((T, H, H, C), torch.float8_e4m3fn if fp8 else torch.bfloat16, dev, labels=labels)
+    for first in range(0, T, 256):
+        n = min(256, T - first)
+        status = cache.write(first, _features(n, P, C, torch.bfloat16, dev, seed=42 + first).view(n, H, H, C))
+        assert int(status.sum()) == 0
+    Wa0, Wt0 = torch.randn(C, 1, generator=g) / C ** 0.5, torch.randn(C, K, generator=g) / C ** 0.5
+    lr, momentum, wd = 1e-3, 0.9, [1e-4, 0.0, 1e-4, 0.0]
+    kw = dict(flags=cof.attn_flags(False, False, True), keep_prob=0.2, seed=42)
+
+    def lean_state():
+        w = [Wa0.clone().to(dev), torch.zeros(1, device=dev), Wt0.clone().to(dev), torch.zeros(K, device=dev)]
+        grad = torch.zeros((sum(t.numel() for t in w),), device=dev)
+        o, views = 0, []
+        for t in w:
+            views.append(grad[o:o + t.numel()].view(t.shape))
+            o += t.numel()
+        return w, grad, torch.zeros_like(grad), tuple(views), torch.zeros(1, dtype=torch.int64, device=dev)
+
+    # (a) one call per epoch
+    wa, ga, acca, va, ctra = lean_state()
+    ep = cof.HeadTrainEpoch(cache, N, *wa, va, wa, wd, ga, acca, steps=steps, momentum=momentum, offset=ctra, **kw)
+    order_a = torch.empty((T,), dtype=torch.int32, device=dev)
+    lrs = [lr] * steps
+    state = {'a': 0, 'b': 0, 'c': 0}
+
+    def epoch_a():
+        cache.order(7, state['a'], out=order_a)
+        state['a'] += 1
+        ep.run(order_a, lrs)
+
+    # (b) the lean loop
+    wb, gb, accb, vb, ctrb = lean_state()
+    b0 = cache.select(torch.arange(N, dtype=torch.int32, device=dev))
+    st_b = cof.HeadTrainStep(b0, b0, *wb, None, (None, None) + vb, offset=ctrb, **kw)
+    sgd_b = cof.BoundMomentumSGD(wb, wd, gb, accb)
+
+    def epoch_b():
+        state['b'] += 1
+        for idx in cache.epoch(N, seed=state['b']):
+            st_b.rebind(index=idx)
+            st_b.run()
+            sgd_b.run(lr, momentum, 1.0)
+
+    # (c) the deploy loop
+    network_fn, cfg = _epoch_cfg002(dev, K, True)
+    with torch.no_grad():
+        network_fn.head.att_weights.copy_(Wa0.to(dev).view_as(network_fn.head.att_weights))
+        network_fn.head.td_weights.copy_(Wt0.to(dev).view_as(network_fn.head.td_weights))
+    fused = deploy.FusedHeadStep(network_fn, cfg, frozen_features=True)
+    opt = fused.make_optimizer(lr)
+
+    def epoch_c():
+        state['c'] += 1
+        for idx in cache.epoch(N, seed=state['c']):
+            fused(cache.select(idx), None)
+            opt.step()
+
+    # (d) the deploy layer's own epoch call, for what it adds to (a)
+    net_d, cfg_d = _epoch_cfg002(dev, K, True)
+    fused_d = deploy.FusedHeadStep(net_d, cfg_d, frozen_features=True)
+    fused_d.make_optimizer(lr)
+
+    def epoch_d():
+        fused_d.train_epoch(cache, N, cache.order(9, fused_d.head._step, out=order_a))
+
+    # the validation pass
+    net_e, cfg_e = _epoch_cfg002(dev, K, False)
+    ev = deploy.FusedHeadEval(net_e, cfg_e)
+    meter_a, meter_b = ev.new_evaluation(T), ev.new_evaluation(T)
+    all_ids = torch.arange(T, dtype=torch.int32, device=dev)
+
+    def eval_a():
+        meter_a.reset()
+        ev.evaluate_cache(cache, N, meter=meter_a, order=all_ids)
+
+    def eval_b():
+        meter_b.reset()
+        for a in range(0, T, N):
+            idx = all_ids[a:a + N]
+            scores, _, _ = ev(cache.select(idx))
+            meter_b.update(scores, labels[a:a + N])
+
+    def measure(forms):
+        for fn in forms.values():
+            fn()
+        torch.cuda.synchronize()
+        wall, device = {k: [] for k in forms}, {k: [] for k in forms}
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        for _ in range(5):
+            for name, fn in forms.items():
+                t0 = time.perf_counter()
+                e0.record()
+                fn()
+                e1.record()
+                torch.cuda.synchronize()
+                wall[name].append((time.perf_counter() - t0) * 1e6 / steps)
+                device[name].append(e0.elapsed_time(e1) * 1e3 / steps)
+        med = lambda v: sorted(v)[len(v) // 2]
+        return {k: {'wall_us_per_step': round(med(wall[k]), 2), 'device_us_per_step': round(med(device[k]), 2),
+                    'wall_over_device': round(med(wall[k]) / med(device[k]), 3),
+                    'wall_runs': [round(x, 2) for x in wall[k]], 'device_runs': [round(x, 2) for x in device[k]]}
+                for k in forms}
+
+    train = measure({'a_epoch_call': epoch_a, 'b_lean_loop': epoch_b, 'c_deploy_loop': epoch_c,
+                     'd_deploy_train_epoch': epoch_d})
+    evals = measure({'a_evaluate_cache': eval_a, 'b_call_loop': eval_b})
+    fastest = min(('a_epoch_call', 'b_lean_loop', 'c_deploy_loop'), key=lambda k: train[k]['wall_us_per_step'])
+    return {'workload': '{}: cfg 002 frozen epoch from a resident {} cache, {} steps of N={} over {} x {}x{}x{}, K={}, '
+                        'three routes alternating in one process, medians of five epochs'.format(
+                            which, 'FP8 E4M3' if fp8 else 'bf16', steps, N, T, H, H, C, K),
+            'steps_per_epoch': steps, 'train': train, 'fastest_train_route_by_wall': fastest, 'eval': evals,
+            'fastest_eval_route_by_wall': min(evals, key=lambda k: evals[k]['wall_us_per_step']),
+            'clamped_ids': int(cache.status)}
+
+
 CACHED_CLIPS = {'cached_hmdb_clips_fp8': (51, 'softmax-xentropy', True), 'cached_hmdb_clips_bf16': (51, 'softmax-xentropy', False),
                 'cached_charades_fp8': (157, 'multi-label', True), 'cached_charades_bf16': (157, 'multi-label', False)}
 
@@ -1586,7 +1735,8 @@ def main():
                                                          'update_perclass', 'poseatt', 'video_perclass', 'video003',
                                                          'hico002', 'charades_clips', 'frozen002', 'frozen003',
                                                          'frozen_perclass', 'frozen002_fp8', 'eval002_fp8',
-                                                         'cached002_fp8', 'cached002_bf16', 'explain002', 'map393'] +
+                                                         'cached002_fp8', 'cached002_bf16', 'epoch002_fp8',
+                                                         'epoch002_bf16', 'explain002', 'map393'] +
                     sorted(EVAL_CLIPS) + sorted(RANK_WORKLOADS) + sorted(CACHED_CLIPS))
     ap.add_argument('--clips', type=int, default=8, help='video_*: clips per batch')
     ap.add_argument('--frames', type=int, default=4, help='video_*: frames per clip')
@@ -1639,6 +1789,9 @@ def main():
         return
     if args.workload in ('cached002_fp8', 'cached002_bf16'):
         print(json.dumps(run_cached(cof, dev, args, args.workload)))
+        return
+    if args.workload in ('epoch002_fp8', 'epoch002_bf16'):
+        print(json.dumps(run_epoch(cof, dev, args, args.workload)))
         return
     if args.workload in CACHED_CLIPS:
         print(json.dumps(run_cached_clips(cof, dev, args, args.workload)))
