@@ -82,12 +82,20 @@ static int check_common(const char* fn, const PoolDims& d, bool fp8_ok = false) 
 // A form a frozen cache (an FP8 one, apa.h: APA_DTYPE_FP8_E4M3; one read by image index, apa_feature_cache) cannot
 // have, by name, or null: the one chain behind fp8_check and cache_check, whose order decides what a call with several
 // defects is told.  fp8: the FP8 kernels' channel limits apply.  (An FP8 call never gets to the _cat row: fp8_served.)
-static const char* cache_form_why(const PoolCall& d, const void* X, const void* Xatt, bool topdown, bool fp8) {
-  return d.M != 1 ? "per-class maps (M != 1)"
+// per_class (the *_cached pooling calls and steps, not the epoch calls, never FP8): per-class maps of a shape on the fused
+// K <= 64 route are a form a cache has -- the two kernels of that route that read X have gathered instances
+// (apa_pc_fused.hip) -- and spatial-softmax attention goes with them: it is served by the same two X readers.
+static bool cache_per_class(const PoolCall& d) {
+  return d.M != 1 && pc_fused_shape_supported(d.C, d.Ca, d.K, d.dtype);
+}
+static const char* cache_form_why(const PoolCall& d, const void* X, const void* Xatt, bool topdown, bool fp8,
+                                  bool per_class = false) {
+  const bool pc = per_class && !fp8 && cache_per_class(d);
+  return (d.M != 1 && !pc) ? "per-class maps (M != 1)"
          : (X && Xatt != X) ? "a separate attention input (Xatt != X)"
          : (fp8 && d.C % 16 != 0) ? "a channel count that is not a multiple of 16"
          : (fp8 && d.C > M1F_MAX_C) ? "more than 8192 channels"
-         : (d.flags & APA_FLAG_SOFTMAX_ATT) ? "APA_FLAG_SOFTMAX_ATT"
+         : ((d.flags & APA_FLAG_SOFTMAX_ATT) && !pc) ? "APA_FLAG_SOFTMAX_ATT"
          : (d.flags & APA_FLAG_RELU_INPUT) ? "APA_FLAG_RELU_INPUT"
          : (d.flags & APA_FLAG_RNG_EXTERNAL) ? "APA_FLAG_RNG_EXTERNAL"
          : topdown ? "the TopDownAttention dump"
@@ -981,9 +989,10 @@ extern "C" int apa_attn_head_eval_step(const void* X, const void* Xatt, const fl
 // ---- a resident feature cache read by image index (apa.h: apa_feature_cache) -----------------------------------------
 // What a *_cached call refuses about its descriptor and about the forms a cache cannot have, each reason by name and
 // before anything is queued; what remains (pointers, workspace, the FP8 arm's own limits) is pool_check's as ever.
-// backward: a backward call or a training step.
+// backward: a backward call or a training step.  per_class: false for the epoch calls, which keep refusing M != 1 (their
+// update rewrites no weight images, which the per-class deploy path relies on) while the step they loop over serves it.
 static int cache_check(const char* fn, const apa_feature_cache* fc, const PoolCall& d, const void* X, const void* Xatt,
-                       bool topdown, bool backward, const void* dX) {
+                       bool topdown, bool backward, const void* dX, bool per_class = true) {
   if (!fc || !fc->index) {
     set_error("%s: null apa_feature_cache / index pointer", fn);
     return APA_ERR_INVALID_ARG;
@@ -1006,10 +1015,19 @@ static int cache_check(const char* fn, const apa_feature_cache* fc, const PoolCa
     set_error("%s: a feature cache is frozen: a backward call or a training step needs APA_FLAG_FROZEN_INPUT", fn);
     return APA_ERR_INVALID_ARG;
   }
-  if (const char* why = cache_form_why(d, X, Xatt, topdown, false)) {   // (FP8's own limits: pool_check)
-    set_error("%s: a feature cache does not serve %s: the gathered kernels feed the fused class-agnostic head with "
-              "identity or relu attention", fn, why);
+  if (const char* why = cache_form_why(d, X, Xatt, topdown, false, per_class)) {   // (FP8's own limits: pool_check)
+    if (per_class && cache_per_class(d))
+      set_error("%s: a feature cache does not serve %s: with per-class maps the gathered kernels feed the fused bf16 "
+                "route (K <= 64) with attention from the map itself", fn, why);
+    else
+      set_error("%s: a feature cache does not serve %s: the gathered kernels feed the fused class-agnostic head with "
+                "identity or relu attention", fn, why);
     return APA_ERR_UNSUPPORTED;
+  }
+  if (d.M != 1 && (reinterpret_cast<uintptr_t>(X) & 15)) {
+    set_error("%s: a feature cache of per-class maps must be 16-byte aligned (the fused route fetches its rows by "
+              "LDS-DMA)", fn);
+    return APA_ERR_INVALID_ARG;
   }
   return APA_OK;
 }
@@ -1018,6 +1036,7 @@ static int cache_check(const char* fn, const apa_feature_cache* fc, const PoolCa
 static const int64_t* cached_labels(PoolCall* d, const apa_feature_cache* fc, const int64_t* labels) {
   if (!fc->labels_cached || !labels || !d->ws) return labels;
   d->fc_labels = labels;
+  if (d->M != 1) return pc_gathered_labels(d->ws, d->N, d->P, d->C, d->Ca, d->K, d->dtype);
   return m1_gathered_labels(d->ws, m1_plan(d->N, d->P, d->C, d->Ca, d->K));
 }
 
@@ -1236,7 +1255,8 @@ extern "C" int apa_attn_head_train_epoch_cached(const apa_epoch* ep, const apa_e
   {  // the step's checks, once for the shape
     PoolCall d = fp8_served(pool_call({N, P, C, Ca, K, M, dtype}, flags, keep_prob, seed, offset, ws, ws_bytes, stream,
                                       hooks));
-    if ((rc = cache_check(fn, &fc, d, X, Xatt, false, true, dX)) != APA_OK) return rc;
+    // (per-class maps: refused here although the step serves them -- this call's update rewrites no weight images)
+    if ((rc = cache_check(fn, &fc, d, X, Xatt, false, true, dX, false)) != APA_OK) return rc;
     d.fc = &fc;
     const StepLoss L{nullptr, labels, false, nullptr, loss_wt, grad_scale, loss, G};
     const M1Fwd f{X, Xatt, Wa, ba, Wt, bt, logits, att, zsave, abar};
@@ -1281,7 +1301,8 @@ extern "C" int apa_attn_head_eval_epoch_cached(const apa_epoch* ep, const apa_fe
     const M1Fwd f{X, Xatt, Wa, ba, Wt, bt, logits, att, zsave, abar};
     for (int n : {N, last}) {
       PoolCall d = fp8_served(pool_call({n, P, C, Ca, K, M, dtype}, flags, 1.0f, 0, 0, ws, ws_bytes, stream));
-      if ((rc = cache_check(fn, &fc, d, X, Xatt, false, false, nullptr)) != APA_OK) return rc;
+      // (per-class maps: refused with the training epoch's, so that the pair stays one interface)
+      if ((rc = cache_check(fn, &fc, d, X, Xatt, false, false, nullptr, false)) != APA_OK) return rc;
       if ((rc = eval_scores_check(fn, nullptr, scores_kind, n, K, logits, labels, loss, probs, pred)) != APA_OK)
         return rc;
       d.fc = &fc;

@@ -19,4 +19,13 @@ struct M1Gather {
 struct M1NoGather {};
 template <bool GATHER> using M1GatherArg = std::conditional_t<GATHER, M1Gather, M1NoGather>;
 
+// ... and of the two per-class kernels that read X (apa_pc_fused.hip).  Their blocks own ROWS of the flat [N * P] batch,
+// not images, so the pixels per image travel along: batch row r is pixel r - n P of batch image n = r / P and its
+// feature row is m1_src_image(n, g) * P + that pixel.
+struct PcGather {
+  M1Gather g;
+  int P;
+};
+template <bool GATHER> using PcGatherArg = std::conditional_t<GATHER, PcGather, M1NoGather>;
+
 }  // namespace apa

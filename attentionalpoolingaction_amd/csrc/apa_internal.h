@@ -588,6 +588,8 @@ struct PcFusedWs {
 void pc_fused_geometry(int R, int C, int* out);
 
 bool pc_fused_supported(int N, int P, int C, int Ca, int K, int dtype, const void* X, const void* Xatt);
+// ... its shape half: what a per-class call on a feature cache is admitted by (apa_capi.hip: cache_form_why)
+bool pc_fused_shape_supported(int C, int Ca, int K, int dtype);
 size_t pc_fused_ws_bytes(int N, int P, int C);
 PcFusedWs pc_fused_carve(void* base, int N, int P, int C);
 struct PcPrepBits {   // the step's keep bits, written by the weight-preparation launch's extra blocks
@@ -601,19 +603,25 @@ struct PcDwTail {     // what the dW reduce launch's tail blocks also do (see pc
 int pc_fused_prep(const PcFusedWs& f, const float* Wa, const float* Wt, const float* ba, const float* bt, int C,
                   int K, hipStream_t st, const PcPrepBits* bits = nullptr, bool weights = true);
 struct PcFwdFold { float* att; int act; int P; };   // identity (0) / relu (1) attention folded into the product's epilogue
+// ga (here and in pc_fused_dw, the two kernels that read X): a gathered call -- X is the cache -- or null
 int pc_fused_forward(const PcFusedWs& f, const void* X, float* Z, float* T, int R, int C, int K, bool train,
                      float keep_prob, uint64_t seed, uint64_t offset, const uint64_t* offset_dev, hipStream_t st,
-                     bool prebits = false, const PcFwdFold* fold = nullptr, bool check_tag = false);
+                     bool prebits = false, const PcFwdFold* fold = nullptr, bool check_tag = false,
+                     const PcGather* ga = nullptr);
 bool pc_fused_dx_supported(int P, int act);
 int pc_fused_dx_rows(int R);
 int pc_fused_dx(const PcFusedWs& f, const float* G, const float* att, const float* Tm, void* dX, float* pd, int R,
                 int C, int K, int P, int act, bool train, float keep_prob, const M1Xent* defer, hipStream_t st);
 int pc_fused_logits_finish(const PcFusedWs& f, float* logits, int N, int P, int K, hipStream_t st);
 int pc_fused_dw(const PcFusedWs& f, const void* X, float* dWt, float* dWa, int R, int C, int K, bool train,
-                float keep_prob, hipStream_t st, const PcDwTail* tail = nullptr);
+                float keep_prob, hipStream_t st, const PcDwTail* tail = nullptr, const PcGather* ga = nullptr);
 
 // apa_pc.hip: per-class bottom-up maps (M == K); Tsave = fp32 [N,P,K] top-down map saved for bwd
 size_t pc_workspace_bytes(int N, int P, int C, int Ca, int K, int dtype);
+// where a gathered forward product leaves labels[index[n]] (labels_cached) for the loss behind it: the head of the
+// materialised dropout(X) region, which only the generic route writes -- and a gathered call never takes that route
+// (bf16: the region holds N P C 2 >= 8 N bytes)
+int64_t* pc_gathered_labels(void* ws, int N, int P, int C, int Ca, int K, int dtype);
 // (test-only probe) the carve of pc_plan: out[0..15] = R, Kp, off_wap, off_wtp, off_bap, off_z, off_dt, off_dz, off_pdbt,
 // off_pdba, off_gemm, gemm_half, off_xd, off_bits, off_fused, total
 void pc_plan_offsets(int N, int P, int C, int Ca, int K, int dtype, size_t* out);

@@ -396,7 +396,15 @@ struct PcCall {
   bool train; int act;                  // act: 0 identity, 1 relu, 2 spatial softmax attention
   RngKeyArgs key;                       // the dropout key as the kernels take it (rng_resolve)
   uint64_t* bump;                       // APA_FLAG_RNG_DEVICE: the counter the backward call's LAST launch advances
+  // a gathered call (PoolCall::fc): X is the cache, and the two kernels that read it (pc_fwd_zt_dma_kernel,
+  // pc_bwd_dw_kernel) run their gathered instances on `ga`.  status / labels: filled by pc_forward alone -- the backward
+  // pass reports and copies nothing.  Fused route only: the generic one materialises dropout(X) from a dense X
+  bool gather; PcGather ga;
+  const PcGather* gather_arg() const { return gather ? &ga : nullptr; }
 };
+int64_t* pc_gathered_labels(void* ws, int N, int P, int C, int Ca, int K, int dtype) {
+  return reinterpret_cast<int64_t*>(static_cast<char*>(ws) + pc_plan(N, P, C, Ca, K, dtype).off_xd);
+}
 // X == nullptr (pc_weight_images: which features will come is not known): the layout of 16-byte addressable ones
 static PcCall pc_call(const PoolCall& d, const void* X) {
   const int N = d.N, P = d.P, C = d.C, Ca = d.Ca, K = d.K, dtype = d.dtype;
@@ -419,7 +427,17 @@ static PcCall pc_call(const PoolCall& d, const void* X) {
   c.key = rng_resolve(flags, keep_prob, seed, offset);
   c.bump = (c.train && (flags & APA_FLAG_RNG_DEVICE)) ? reinterpret_cast<uint64_t*>(static_cast<uintptr_t>(offset))
                                                        : nullptr;
+  c.gather = d.fc != nullptr;
+  c.ga = PcGather{M1Gather{nullptr, 0, nullptr, nullptr, nullptr}, P};
+  if (c.gather) { c.ga.g.index = d.fc->index; c.ga.g.T = d.fc->cache_images; }
   return c;
+}
+// A gathered call is the fused route's or nobody's: cache_check (apa_capi.hip) admits exactly what pc_fused_supported
+// serves, and a call built inside the library that gets here without it is refused before anything is queued.
+static int pc_gather_refuse(const char* who) {
+  set_error("%s: a feature cache feeds the fused per-class route only (bf16, Xatt == X, K <= 64, C %% 256 == 0, "
+            "C <= 8192, 16-byte aligned, no replayed mask)", who);
+  return APA_ERR_UNSUPPORTED;
 }
 
 // the padding launch; training on the DMA route: + the materialised dropout(X) and its keep bits, as extra blocks
@@ -550,7 +568,7 @@ static int pc_forward_fused(const PcCall& c, const M1Fwd& io, hipStream_t st, M1
   const bool fold = c.act != 2 && !topdown && P >= 32;
   const PcFwdFold ff = {att, c.act, P};
   rc = pc_fused_forward(f, X, c.Z, Tsave, R, C, K, c.train, c.keep_prob, c.key.seed, c.key.offset, c.key.offset_dev, st,
-                        prebits, fold ? &ff : nullptr, tagged);
+                        prebits, fold ? &ff : nullptr, tagged, c.gather_arg());
   if (rc != APA_OK) return rc;
   if (fold) {
     // one-call train step: pc_backward's first launch (pc_bwd_dx_kernel) finishes logits + cross-entropy
@@ -636,10 +654,18 @@ static int pc_forward_generic(const PcCall& c, const M1Fwd& io, hipStream_t st, 
 }
 
 int pc_forward(const PoolCall& d, const M1Fwd& io, M1Xent* xf) {
-  const PcCall c = pc_call(d, io.X);
+  PcCall c = pc_call(d, io.X);
+  if (c.gather) {   // the forward product counts the clamped ids and leaves the labels read through the index
+    c.ga.g.status = d.fc->status;
+    if (d.fc_labels) {
+      c.ga.g.labels = d.fc_labels;
+      c.ga.g.labels_out = pc_gathered_labels(d.ws, d.N, d.P, d.C, d.Ca, d.K, d.dtype);
+    }
+  }
   if (PcTrace* tr = pc_trace()) { tr->phase = 1; tr->topdown = io.topdown ? 1 : 0; }
   if (pc_fused_supported(d.N, d.P, d.C, d.Ca, d.K, d.dtype, io.X, io.Xatt) && !rng_external(d.flags))
     return pc_forward_fused(c, io, d.st, xf);
+  if (c.gather) return pc_gather_refuse("attn_pool_fwd M=K");
   return pc_forward_generic(c, io, d.st, xf);
 }
 
@@ -718,7 +744,7 @@ static int pc_backward_fused(const PcCall& c, const M1Bwd& io, hipStream_t st, c
     tail.next_bits = true;
     tail.next_seed = c.key.seed;
   }
-  return pc_fused_dw(f, X, dWt, dWa, R, C, K, c.train, c.keep_prob, st, &tail);
+  return pc_fused_dw(f, X, dWt, dWa, R, C, K, c.train, c.keep_prob, st, &tail, c.gather_arg());
 }
 
 static int pc_backward_generic(const PcCall& c, const M1Bwd& io, hipStream_t st, const M1Xent* xf) {
@@ -845,6 +871,7 @@ int pc_backward(const PoolCall& d, const M1Bwd& io, const M1Xent* xf) {
   if (PcTrace* tr = pc_trace()) tr->phase = 2;
   if (pc_fused_supported(d.N, d.P, d.C, d.Ca, d.K, d.dtype, io.X, io.Xatt) && !rng_external(d.flags))
     return pc_backward_fused(c, io, d.st, xf);
+  if (c.gather) return pc_gather_refuse("attn_pool_bwd M=K");
   if (d.flags & APA_FLAG_FROZEN_INPUT) {   // (the entry points refuse this before their forward half: frozen_input_check)
     set_error("per-class maps: APA_FLAG_FROZEN_INPUT is not served by the dense per-class route");
     return APA_ERR_UNSUPPORTED;

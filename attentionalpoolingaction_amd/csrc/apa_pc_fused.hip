@@ -260,12 +260,17 @@ __global__ __launch_bounds__(64) void pc_logits_finish_kernel(const float* __res
   if (k < K) logits[(size_t)n * K + k] = pc_logit_from_partials(lpart, n, k, P);
 }
 
-template <bool TRAIN, bool FOLD = false>
+// GATHER (apa.h: apa_feature_cache): X is a T-image cache and batch row r = n P + p is fetched from row
+// m1_src_image(n, g) P + p of it.  A block's 32 rows straddle images wherever they like, so the lookup is the lane's own,
+// for the one row whose DMA source it holds: one dependent index read in front of the first A piece, under which the keep
+// bits and tile 0's slab pieces are already in flight.  Nothing else knows -- Z, T, att, the partials, the keep bits and
+// the dropout element index keep the batch row.  The plain instances take an empty M1NoGather and are the code they were.
+template <bool TRAIN, bool FOLD = false, bool GATHER = false>
 __global__ __launch_bounds__(512) void pc_fwd_zt_dma_kernel(
     const bf16_t* __restrict__ X, const bf16_t* __restrict__ WcatT, const float* __restrict__ bcat,
     float* __restrict__ Z, float* __restrict__ T, uint8_t* __restrict__ maskbits, int R, int C, int K,
     float inv_keep, uint32_t thresh, uint64_t seed, uint64_t offset, const uint64_t* __restrict__ offset_dev,
-    PcFoldArgs fo, uint64_t* __restrict__ tag) {
+    PcFoldArgs fo, uint64_t* __restrict__ tag, PcGatherArg<GATHER> g) {
   extern __shared__ __attribute__((aligned(16))) short smem[];
   typedef __attribute__((address_space(3))) void* lptr;
   uint8_t* const s_bits = reinterpret_cast<uint8_t*>(smem + ZB_NST * ZB_STAGE_EL);   // [32 rows][C / 8], chunks swizzled
@@ -285,10 +290,18 @@ __global__ __launch_bounds__(512) void pc_fwd_zt_dma_kernel(
   // rows 8 (wave & 3) ..), slab blocks 4 wave .. 4 wave + 3 (tile (4 wave + j) >> 4, rows 8 ((4 wave + j) & 15) ..)
   const bf16_t* asrc;
   const bf16_t* bsrc[4];
+  [[maybe_unused]] int g_n = 0, g_p = 0, g_raw = 0;     // GATHER: this lane's batch (image, pixel) and its index entry
   {
     const int row = 8 * (wave & 3) + (lane >> 3);
     const int chunk = (lane & 7) ^ ((row >> 1) & 7);
-    asrc = X + (size_t)min(m0 + row, R - 1) * C + (wave >> 2) * 64 + chunk * 8;
+    if constexpr (GATHER) {
+      const int rc = min(m0 + row, R - 1);
+      g_n = rc / g.P; g_p = rc - g_n * g.P;
+      g_raw = g.g.index[g_n];          // requested here, used below once tile 0's other pieces have been asked for
+      asrc = X + (wave >> 2) * 64 + chunk * 8;
+    } else {
+      asrc = X + (size_t)min(m0 + row, R - 1) * C + (wave >> 2) * 64 + chunk * 8;
+    }
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       const int blk = 4 * wave + j, n = 8 * (blk & 15) + (lane >> 3);
@@ -297,13 +310,17 @@ __global__ __launch_bounds__(512) void pc_fwd_zt_dma_kernel(
   }
   const uint32_t lds0 = (uint32_t)(size_t)(lptr)smem;
   const uint32_t lds_bits = lds0 + (uint32_t)(ZB_NST * ZB_STAGE_EL * 2);
-  auto issue = [&](int t) {
+  auto issue_a = [&](int t) {
     const uint32_t st = lds0 + (uint32_t)((t % ZB_NST) * ZB_STAGE_EL * 2);
     glds16_asm(asrc + (size_t)t * ZB_KT, st + (uint32_t)wave * 1024u);
+  };
+  auto issue_b = [&](int t) {
+    const uint32_t st = lds0 + (uint32_t)((t % ZB_NST) * ZB_STAGE_EL * 2);
 #pragma unroll
     for (int j = 0; j < 4; ++j)
       glds16_asm(bsrc[j] + (size_t)t * (2 * 128 * 64), st + (uint32_t)(ZB_A_EL * 2) + (uint32_t)(4 * wave + j) * 1024u);
   };
+  auto issue = [&](int t) { issue_a(t); issue_b(t); };
   // Main loop roles (round 5, final): wave = (column half hq: Z | T) x (k-step kq of every stage).  A wave multiplies ALL
   // 32 rows by its half's 64 columns for one 32-channel k-step per stage: 2 A + 4 B fragment reads for 8 MFMAs, where the
   // (half x column group x row tile) split of rounds 3-4 read 4 + 8 for the same 8 -- the loop turned out to be bound by
@@ -326,7 +343,15 @@ __global__ __launch_bounds__(512) void pc_fwd_zt_dma_kernel(
                  lds_bits + (uint32_t)u0 * 16u);
     }
   }
-  issue(0);
+  if constexpr (GATHER) {
+    // tile 0's five pieces, the slab's first (a tile's pieces only have to be neighbours in issue order for the counted
+    // waits below); the A piece follows the index entry -- the clamped id, so nothing outside the cache is addressed
+    issue_b(0);
+    asrc += ((size_t)min(max(g_raw, 0), g.g.T - 1) * g.P + g_p) * C;
+    issue_a(0);
+  } else {
+    issue(0);
+  }
   if (nkt > 1) issue(1);
   bool have_bits = true;
   if (TRAIN && tag) {
@@ -385,6 +410,9 @@ __global__ __launch_bounds__(512) void pc_fwd_zt_dma_kernel(
       pacc[1][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[1], bf, pacc[1][j], 0, 0, 0);
     }
   }
+  // GATHER: the lane that holds the DMA source of an image's first row (first k half, first chunk) reports for it --
+  // every row below R is such a lane's in exactly one block, whatever P; the queue is empty by now
+  if constexpr (GATHER) m1_gather_note(g_n, wave < 4 && (lane & 7) == 0 && g_p == 0 && m0 + 8 * wave + (lane >> 3) < R, g.g);
   // the k-step partials -> the epilogue's layout: wave (half, wn, mt) owns rows 16 mt .., columns 64 half + 32 wn + 16 j
   f32x4 acc[2];
   {
@@ -501,10 +529,15 @@ __device__ __forceinline__ bf16x8 frag_km_sw(const short* img, int rbase, int ks
   return bf16x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
 }
 
-template <bool TRAIN>
+// GATHER (see pc_fwd_zt_dma_kernel): the X rows alone come through the index; [dT | dZ] and the keep bits keep the batch
+// row.  A thread walks two rows per tile, FK further each tile, across image boundaries wherever the row split put them:
+// it carries (image, pixel) of both along -- a carry loop, FK may exceed P, no division behind the prologue -- and reads
+// the index entries two tiles ahead of the load that needs them, so that no feature load waits for one: the entries of
+// tiles 0 and 1 in the prologue (the one dependent read), those of tile t + 2 behind the loads of tile t.
+template <bool TRAIN, bool GATHER = false>
 __global__ __launch_bounds__(512) void pc_bwd_dw_kernel(
     const bf16_t* __restrict__ X, const bf16_t* __restrict__ dTdZ, const uint8_t* __restrict__ maskbits,
-    float* __restrict__ partial, int R, int C, int rows_per_split) {
+    float* __restrict__ partial, int R, int C, int rows_per_split, PcGatherArg<GATHER> g) {
   extern __shared__ __attribute__((aligned(16))) short smem[];
   constexpr int LDI = 128;
   constexpr int IMG = FK * LDI;
@@ -526,6 +559,35 @@ __global__ __launch_bounds__(512) void pc_bwd_dw_kernel(
   // for tile t + 1 sits in an opaque use BEFORE tile t + 2 is requested, and the hand-over barrier waits for LDS
   // only -- `__syncthreads` is a fence and would wait for the prefetch as well.
   struct Stage { uint4 av[2], bv[2]; uint32_t mb[TRAIN ? 2 : 1]; };
+  // GATHER: (image, pixel) of this thread's two rows in the tile whose index entries are read next, g_tile; the entries
+  // (as read: clamped at use, m1_src_image's clamp) and pixels of the next load's tile in slot 0, of the one after in
+  // slot 1.  Rows past the split -- zero operands, see store -- take the split's last row, as the plain loads do.
+  [[maybe_unused]] int g_n[2] = {0, 0}, g_p[2] = {0, 0}, g_raw[2][2] = {{0, 0}, {0, 0}}, g_pix[2][2] = {{0, 0}, {0, 0}};
+  [[maybe_unused]] int g_nend = 0, g_pend = 0, g_tile = 0;
+  [[maybe_unused]] auto lookup = [&]() {       // slot 1 -> slot 0; tile g_tile's entries into slot 1; on to the next tile
+    if constexpr (GATHER) {
+#pragma unroll
+      for (int i = 0; i < 2; ++i) {
+        g_raw[0][i] = g_raw[1][i]; g_pix[0][i] = g_pix[1][i];
+        const bool past = rbeg + g_tile * FK + (tid >> 4) + 32 * i > rend - 1;
+        g_raw[1][i] = g.g.index[past ? g_nend : g_n[i]];
+        g_pix[1][i] = past ? g_pend : g_p[i];
+        g_p[i] += FK;
+        while (g_p[i] >= g.P) { g_p[i] -= g.P; ++g_n[i]; }
+      }
+      ++g_tile;
+    }
+  };
+  if constexpr (GATHER) {
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      const int r0 = rbeg + (tid >> 4) + 32 * i;
+      g_n[i] = r0 / g.P; g_p[i] = r0 - g_n[i] * g.P;
+    }
+    g_nend = (rend - 1) / g.P; g_pend = rend - 1 - g_nend * g.P;
+    lookup();
+    lookup();
+  }
   auto load = [&](int t, Stage& q) {
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
@@ -534,10 +596,14 @@ __global__ __launch_bounds__(512) void pc_bwd_dw_kernel(
       const int rc = min(r, rend - 1);
       // (plain loads: with the non-temporal hint this kernel is no faster and the NEXT step's forward product loses
       //  1 us -- the map is no longer served from the Infinity Cache)
-      q.av[i] = ld16(X + (size_t)rc * C + c0 + m);
+      if constexpr (GATHER)
+        q.av[i] = ld16(X + ((size_t)min(max(g_raw[0][i], 0), g.g.T - 1) * g.P + g_pix[0][i]) * C + c0 + m);
+      else
+        q.av[i] = ld16(X + (size_t)rc * C + c0 + m);
       q.bv[i] = ld16(dTdZ + (size_t)rc * 128 + m);
       if (TRAIN) q.mb[i] = maskbits[((size_t)rc * C + c0 + m) >> 3];
     }
+    lookup();
   };
   auto settle = [&](Stage& q) {
 #pragma unroll
@@ -917,10 +983,12 @@ __global__ __launch_bounds__(1024) void pc_dw_reduce_kernel(const float* __restr
 }
 }  // namespace
 
+bool pc_fused_shape_supported(int C, int Ca, int K, int dtype) {
+  return dtype == APA_DTYPE_BF16 && Ca == C && K >= 1 && K <= 64 && C % 256 == 0 && C <= ZB_MAX_C;
+}
 bool pc_fused_supported(int N, int P, int C, int Ca, int K, int dtype, const void* X, const void* Xatt) {
   (void)N; (void)P;
-  return dtype == APA_DTYPE_BF16 && Xatt == X && Ca == C && K >= 1 && K <= 64 && C % 256 == 0 &&
-         C <= ZB_MAX_C && (reinterpret_cast<uintptr_t>(X) & 15) == 0;
+  return pc_fused_shape_supported(C, Ca, K, dtype) && Xatt == X && (reinterpret_cast<uintptr_t>(X) & 15) == 0;
 }
 
 size_t pc_fused_ws_bytes(int N, int P, int C) {
@@ -986,7 +1054,7 @@ int pc_fused_logits_finish(const PcFusedWs& f, float* logits, int N, int P, int 
 
 int pc_fused_forward(const PcFusedWs& f, const void* X, float* Z, float* T, int R, int C, int K, bool train,
                      float keep_prob, uint64_t seed, uint64_t offset, const uint64_t* offset_dev, hipStream_t st,
-                     bool prebits, const PcFwdFold* fold, bool check_tag) {
+                     bool prebits, const PcFwdFold* fold, bool check_tag, const PcGather* ga) {
   // (C is a multiple of 256, hence of ZB_KT: the only caller, pc_forward, asks pc_fused_supported() first)
   const float ik = train ? 1.0f / keep_prob : 1.0f;
   const bf16_t* xx = static_cast<const bf16_t*>(X);
@@ -1001,6 +1069,15 @@ int pc_fused_forward(const PcFusedWs& f, const void* X, float* Z, float* T, int 
                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)ZB_LDS_MAX));
     APA_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(pc_fwd_zt_dma_kernel<false, true>),
                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)ZB_LDS_MAX));
+    // ... and their gathered siblings
+    APA_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(pc_fwd_zt_dma_kernel<true, false, true>),
+                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)ZB_LDS_MAX));
+    APA_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(pc_fwd_zt_dma_kernel<false, false, true>),
+                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)ZB_LDS_MAX));
+    APA_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(pc_fwd_zt_dma_kernel<true, true, true>),
+                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)ZB_LDS_MAX));
+    APA_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(pc_fwd_zt_dma_kernel<false, true, true>),
+                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)ZB_LDS_MAX));
     attr_set = true;
   }
   if (train && !prebits && !check_tag) {
@@ -1014,12 +1091,15 @@ int pc_fused_forward(const PcFusedWs& f, const void* X, float* Z, float* T, int 
     t->zt = 1; t->zt_train = train ? 1 : 0; t->zt_fold = fold ? 1 : 0; t->check_tag = tag ? 1 : 0;
     if (fold) t->fwd_act = PC_ACT_FOLDED;
   }
-#define APA_ZT(TR, FO)                                                                                         \
-  hipLaunchKernelGGL((pc_fwd_zt_dma_kernel<TR, FO>), dim3((R + 31) / 32), dim3(512), zb_lds_bytes(C), st, xx, ww, \
-                     f.bcat, Z, T, f.maskbits, R, C, K, ik, keep_thresh(keep_prob), seed, offset, offset_dev, fo, tag)
+#define APA_ZT_G(TR, FO, GA, garg)                                                                             \
+  hipLaunchKernelGGL((pc_fwd_zt_dma_kernel<TR, FO, GA>), dim3((R + 31) / 32), dim3(512), zb_lds_bytes(C), st, xx, \
+                     ww, f.bcat, Z, T, f.maskbits, R, C, K, ik, keep_thresh(keep_prob), seed, offset, offset_dev, fo, \
+                     tag, garg)
+#define APA_ZT(TR, FO) do { if (ga) APA_ZT_G(TR, FO, true, *ga); else APA_ZT_G(TR, FO, false, M1NoGather{}); } while (0)
   if (fold) { if (train) APA_ZT(true, true); else APA_ZT(false, true); }
   else      { if (train) APA_ZT(true, false); else APA_ZT(false, false); }
 #undef APA_ZT
+#undef APA_ZT_G
   APA_LAUNCH_CHECK("pc_fwd_zt_dma_kernel");
   return APA_OK;
 }
@@ -1096,7 +1176,7 @@ int pc_fused_dx(const PcFusedWs& f, const float* G, const float* att, const floa
 }
 
 int pc_fused_dw(const PcFusedWs& f, const void* X, float* dWt, float* dWa, int R, int C, int K, bool train,
-                float keep_prob, hipStream_t st, const PcDwTail* tail) {
+                float keep_prob, hipStream_t st, const PcDwTail* tail, const PcGather* ga) {
   // (a 64-channel form -- 32 channel tiles x 8 row splits, half the fp32 partials -- was built and measured in round
   // 4: 51.9 us against 15.5 us: every block then reads 128-byte pieces of X rows 4 KB apart)
   int ctiles, S, rows_per_split;
@@ -1104,19 +1184,22 @@ int pc_fused_dw(const PcFusedWs& f, const void* X, float* dWt, float* dWa, int R
   const bf16_t* x = static_cast<const bf16_t*>(X);
   const bf16_t* g = static_cast<const bf16_t*>(f.dTdZ);
   const size_t shm = (size_t)2 * (train ? 3 : 2) * FK * 128 * sizeof(short);
-#define APA_DW(TR)                                                                                              \
+#define APA_DW_G(TR, GA, garg)                                                                                  \
   do {                                                                                                          \
     static thread_local PerDevice<bool> attr_dev; bool& attr_set = attr_dev.here();                             \
     if (!attr_set) {                                                                                            \
-      APA_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(pc_bwd_dw_kernel<TR>),                    \
+      APA_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(pc_bwd_dw_kernel<TR, GA>),                \
                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));                 \
       attr_set = true;                                                                                          \
     }                                                                                                           \
-    hipLaunchKernelGGL((pc_bwd_dw_kernel<TR>), dim3(ctiles, S), dim3(512), shm, st, x, g, f.maskbits, f.partial, \
-                       R, C, rows_per_split);                                                                   \
+    hipLaunchKernelGGL((pc_bwd_dw_kernel<TR, GA>), dim3(ctiles, S), dim3(512), shm, st, x, g, f.maskbits,       \
+                       f.partial, R, C, rows_per_split, garg);                                                  \
   } while (0)
+  // (the gathered instances: the same treatment, each its own memo)
+#define APA_DW(TR) do { if (ga) APA_DW_G(TR, true, *ga); else APA_DW_G(TR, false, M1NoGather{}); } while (0)
   if (train) APA_DW(true); else APA_DW(false);
 #undef APA_DW
+#undef APA_DW_G
   APA_LAUNCH_CHECK("pc_bwd_dw_kernel");
   const int nmain = (int)(((long)C * 128 + 1023) / 1024);
   PcTail tl;

@@ -90,6 +90,15 @@ int apa_probe_pc_eval_step(apa::PcTrace* t, const void* X, const void* Xatt, con
                                  ws_bytes, N, P, C, Ca, K, M, flags, dtype, stream);
 }
 
+// The trace without a wrapper: every entry point of THIS library the calling thread runs between the two calls records
+// into *t (zeroed here).  tests/test_cached_perclass_gpu.py brackets the *_cached calls and steps, clips and sigmoid
+// losses included, and the plain calls on a gathered copy they must match launch for launch.
+void apa_probe_pc_trace_begin(apa::PcTrace* t) {
+  if (t) *t = apa::PcTrace{};
+  apa::g_pc_trace = t;
+}
+void apa_probe_pc_trace_end(void) { apa::g_pc_trace = nullptr; }
+
 int apa_probe_pc_weight_images(apa::PcTrace* t, const float* Wa, const float* ba, const float* Wt, const float* bt,
                                void* ws, size_t ws_bytes, int N, int P, int C, int Ca, int K, int dtype,
                                apa_weight_image* maps, int* nmaps, void* stream) {

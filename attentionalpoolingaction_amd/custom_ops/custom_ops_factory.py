@@ -799,6 +799,13 @@ def _cached(who: str, X, Xatt, frozen: bool = True) -> Optional['CachedBatch']:
     return X
 
 
+def cached_per_class_served(cb, K: int) -> bool:
+    """Does the library serve per-class maps (M == K) on this CachedBatch?  The C rule (apa_capi.hip: cache_form_why,
+    the shape half of pc_fused_supported): a bf16 cache on the fused K <= 64 route."""
+    C = int(cb.shape[-1])
+    return (not cb.cache.fp8 and cb.dtype == torch.bfloat16 and 1 <= int(K) <= 64 and C % 256 == 0 and C <= 8192)
+
+
 class KeepMask(object):
     """A dropout keep mask drawn OUTSIDE the library (the reference's tf.nn.dropout: floor(keep_prob + U),
     nets_factory.py:143-146,296), bit-packed for APA_FLAG_RNG_EXTERNAL: pass it as `seed=` to any of the
@@ -2036,7 +2043,9 @@ class HeadTrainStep:
         `X` a CachedBatch (`FeatureCache.select(index)`, passed as `Xatt` too; `grads[0] = None`): the step reads the
         N images `index` names straight from the resident cache (apa_attn_head_train_step_cached), bit-identical to the
         step on `cache.gather(index)`; `labels=None` reads the cache's own labels through the same index;
-        `rebind(index=...)` moves the step to another batch of the cache.  M == 1 only.  With `frames` / `temporal` /
+        `rebind(index=...)` moves the step to another batch of the cache.  M == 1, or per-class maps (M == K,
+        `weight_images` included) on a bf16 cache with K <= 64, C % 256 == 0, C <= 8192 (cached_per_class_served: the
+        fused per-class route, whose two kernels that read X have gathered instances).  With `frames` / `temporal` /
         a sigmoid `action_loss` the index names the B * frames frames of B clips (a CachedClips of
         `FeatureCache.sample_clips`; apa_attn_head_train_step_cached_clips), `labels` is per clip / per row and must
         be given (the CachedClips' `labels` / `targets`): bit-identical to the same step on the gathered frames.
@@ -2061,7 +2070,9 @@ class HeadTrainStep:
         cb = self._cached = _cached('HeadTrainStep', X, Xatt, frozen=dX is None)
         cached_clips = False        # a CachedBatch with clips and / or a sigmoid loss: the *_cached_clips entry point
         if cb is not None:
-            if dxatt_rank1 or weight_images or M != 1:
+            # per-class maps (M == K, weight images included): a bf16 cache on the fused K <= 64 route
+            per_class = M != 1 and M == K and cached_per_class_served(cb, K)
+            if dxatt_rank1 or ((weight_images or M != 1) and not per_class):
                 raise ApaError('HeadTrainStep: a CachedBatch feeds the class-agnostic step, flat or on clips (no '
                                'per-class maps, weight images or dxatt_rank1)')
             if share_with is not None and share_with._cached is None:
@@ -2471,7 +2482,8 @@ class HeadEvalStep:
 
     `X` a CachedBatch (`FeatureCache.select(index)`, passed as `Xatt` too): apa_attn_head_eval_step_cached on the images
     `index` names (softmax or sigmoid scores); `labels=None` with softmax scores on a flat batch reads the cache's own
-    labels, if it has any, through the index; `rebind(index=...)` moves the step to another batch of the cache.  With
+    labels, if it has any, through the index; `rebind(index=...)` moves the step to another batch of the cache
+    (M == 1, or per-class maps where cached_per_class_served says so).  With
     `frames` > 1 or `temporal` the index names the frames of B clips (a CachedClips of `FeatureCache.sample_clips`;
     apa_attn_head_eval_step_cached_clips) and `labels`, if given, is per clip; `labels=None` computes no loss there --
     the cache's per-image labels are not read for a clip, `temporal` on single frames (`frames=1`) included."""
@@ -2488,7 +2500,7 @@ class HeadEvalStep:
         # softmax scores reads the cache's own labels, if it has any, through the same index (labels_cached)
         cb = self._cached = _cached('HeadEvalStep', X, Xatt)
         if cb is not None:
-            if M != 1:
+            if M != 1 and not (M == K and cached_per_class_served(cb, K)):    # (those: a bf16 cache, the fused route)
                 raise ApaError('HeadEvalStep: a CachedBatch feeds the class-agnostic step (no per-class maps)')
             # exactly when _bind_eval_clip below builds a clip (temporal attention on single frames is one too): its
             # labels are per clip, never read through the frame index -- labels=None then means no loss

@@ -1120,6 +1120,31 @@ class FusedHeadStep:
             return 'spatial-softmax attention'
         return ''
 
+    @staticmethod
+    def cache_unsupported_reason(head, network_fn, batch) -> str:
+        """why `batch` -- an Fp8Features batch, a CachedBatch or a CachedClips -- cannot feed this head; '' when it can.
+        An Fp8Features batch, and every head but the single-layer per-class one: `fp8_unsupported_reason`.  The per-class
+        head (with identity, ReLU or spatial-softmax attention) is served from a bf16 cache on the fused per-class
+        route (K <= 64, C % 256 == 0, C <= 8192: cof.cached_per_class_served), flat or on clips."""
+        from .custom_ops import custom_ops_factory as cof
+        why = FusedHeadStep.fp8_unsupported_reason(head, network_fn)
+        if why != 'per-class attention maps' or not isinstance(batch, cof.CachedBatch):
+            return why
+        if head.rank != 1:
+            return 'rank %d attention' % head.rank
+        if head.with_pose_feat:
+            return '..._WITH_POSE_FEAT'
+        K, C = int(head.num_classes), int(batch.shape[-1])
+        if batch.cache.fp8:
+            return 'per-class attention maps from an FP8 cache (the gathered per-class kernels read bf16)'
+        if batch.dtype != torch.bfloat16:
+            return 'per-class attention maps from a %s cache (the gathered per-class kernels read bf16)' % (
+                str(batch.dtype).replace('torch.', ''))
+        if not cof.cached_per_class_served(batch, K):
+            return ('per-class attention maps with K = %d classes on %d channels (a cache feeds the fused per-class '
+                    'route: K <= 64, C %% 256 == 0, C <= 8192)' % (K, C))
+        return ''
+
     @property
     def _dX(self):
         return None if self._step_obj is None else self._step_obj._dX_buf
@@ -1347,15 +1372,16 @@ class FusedHeadStep:
         through the index; under LOSS_FN_ACTION 'multi-label*' `labels_action` is [N,K]); or a CachedClips
         (`FeatureCache.sample_clips`: B clips of a frame cache -- `frames` comes from the batch, `labels_action=None`
         means the batch's own labels / targets, and the end points are those of a 5-D clip batch).  The cached forms
-        are frozen by construction (frozen_features=True) and are served under the head conditions of
-        fp8_unsupported_reason; one bound step per (cache, B, F, loss kind)."""
+        are frozen by construction (frozen_features=True) and are served under the conditions of
+        cache_unsupported_reason (an FP8 batch: fp8_unsupported_reason; a bf16 cache also feeds the per-class head);
+        one bound step per (cache, B, F, loss kind)."""
         from .custom_ops.custom_ops_factory import CachedBatch, CachedClips, Fp8Features
         self._frames = 1
         self._cb = isinstance(images, CachedBatch)
         self._fp8 = isinstance(images, Fp8Features)
         if self._fp8 or self._cb:   # a cached conv5 map: frozen by construction, no backbone in front of it
             what = 'an Fp8Features batch' if self._fp8 else 'a CachedBatch'
-            why = self.fp8_unsupported_reason(self.head, self.network_fn)
+            why = self.cache_unsupported_reason(self.head, self.network_fn, images)
             if not why and not self.frozen_features:
                 why = 'frozen_features=False (a cache has no gradient: build the step with frozen_features=True)'
             if why:
@@ -1569,8 +1595,8 @@ class FusedHeadEval:
         frames = 1
         cb = isinstance(images, CachedBatch)
         fp8 = isinstance(images, Fp8Features) or cb
-        if fp8:             # a cached conv5 map: FP8, or a FeatureCache read by index (see FusedHeadStep.fp8_unsupported_reason)
-            why = FusedHeadStep.fp8_unsupported_reason(self.head, self.network_fn)
+        if fp8:             # a cached conv5 map: FP8, or a FeatureCache read by index (see FusedHeadStep.cache_unsupported_reason)
+            why = FusedHeadStep.cache_unsupported_reason(self.head, self.network_fn, images)
             if why:
                 raise ValueError('FusedHeadEval: %s is not served with %s' % (
                     'a CachedBatch' if cb else 'an Fp8Features batch', why))

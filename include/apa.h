@@ -855,14 +855,23 @@ int apa_attn_pool_bwd_cat(const apa_concat_feat* cat, const apa_hooks* hooks, co
  * labels_cached (the steps): `labels` is [T] and image n's label is labels[index[n]], read by the forward pooling
  * pass; else `labels` is [N] as in the plain steps.
  * Served: the class-agnostic head (M == 1) with attention from the map itself (Xatt == X), identity or ReLU attention,
- * evaluation or training on frozen features.  Refused before anything is queued --
+ * evaluation or training on frozen features; and per-class maps (M == K) from a bf16 cache where the plain entry point
+ * takes the fused per-class route -- Ca == C, K <= 64, C % 256 == 0, C <= 8192, Xatt == X, a 16-byte aligned cache --
+ * with identity, ReLU or spatial-softmax attention, APA_FLAG_WEIGHT_IMAGES and the tagged keep-bit hand-off of the
+ * one-call train step included (the bits are keyed by batch position).  Of that route only the two kernels that read X
+ * (the Z | T product and the dW product) have gathered instances; labels_cached leaves its [N] copy in the workspace's
+ * materialised-dropout region, which that route never writes.
+ * Refused before anything is queued --
  *   APA_ERR_INVALID_ARG: a NULL descriptor or index, cache_images < 1, a non-NULL dX, a backward call or a training
- *                        step without APA_FLAG_FROZEN_INPUT;
- *   APA_ERR_UNSUPPORTED: M != 1, a separate attention input, APA_FLAG_SOFTMAX_ATT, APA_FLAG_RELU_INPUT,
- *                        APA_FLAG_RNG_EXTERNAL, the TopDownAttention dump, clips (eval: clip must be NULL);
+ *                        step without APA_FLAG_FROZEN_INPUT, per-class maps on a cache that is not 16-byte aligned;
+ *   APA_ERR_UNSUPPORTED: M != 1 outside the shapes above (fp32 or FP8 caches, K > 64, other C), a separate attention
+ *                        input, APA_FLAG_SOFTMAX_ATT with M == 1, APA_FLAG_RELU_INPUT, APA_FLAG_RNG_EXTERNAL, the
+ *                        TopDownAttention dump, clips (eval: clip must be NULL);
  * then whatever the plain entry point refuses (for FP8: what the FP8 arm refuses).  Clips and the sigmoid training
- * losses: the *_cached_clips steps below.  Not built: rank > 1, per-class maps, the concatenated pose channels, the
- * pose head and the cfg 003 steps, clips or sigmoid losses with labels_cached.
+ * losses: the *_cached_clips steps below.  Not built: rank > 1, per-class maps from fp32 or FP8 caches, with K > 64 or
+ * on the generic route, M == 1 spatial-softmax attention, the concatenated pose channels, the pose head and the
+ * cfg 003 steps, clips or sigmoid losses with labels_cached; the epoch calls (apa_attn_head_train_epoch_cached /
+ * apa_attn_head_eval_epoch_cached) keep refusing M != 1.
  * Workspace: apa_attn_pool_workspace_bytes of the BATCH shape.  The signatures are those of apa_attn_pool_fwd_ex /
  * apa_attn_pool_bwd_ex / apa_attn_head_train_step_ex / apa_attn_head_eval_step_clips with the descriptor in front.
  */

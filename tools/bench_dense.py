@@ -37,6 +37,12 @@ headline stays the cfg 002 training workload); run this file directly for one wo
             process, medians of five and their spread: (a) the gathered step (apa_attn_head_train_step_cached) with a
             fresh shuffled index per step, (b) gather + rebind + the plain step -- the loop without the gathered
             kernels --, (c) the plain step on one fixed contiguous batch.
+  cached_perclass_bf16
+            the same three variants for the HMDB-51 per-class head (M = K = 51, bf16, weight images kept by the caller)
+            from a resident bf16 cache of --cache-images (2048) maps 14x14x2048, --batch 32.
+  cached_hmdb_perclass_clips_bf16
+            cached_hmdb_clips_bf16 with the per-class head (M = K = 51): 81 videos x 25 frames, 8 clips x 4 frames,
+            temporal attention; evaluation at 4 x 25.
   epoch002_fp8 / epoch002_bf16
             a whole frozen-feature EPOCH of cfg 002 from the resident cache of cached002_* (--cache-images 2048, --batch
             32: 64 steps, momentum SGD behind every step, a fresh order per epoch), three routes alternating in one
@@ -1199,12 +1205,14 @@ def run_fp8(cof, dev, args, which):
     return out
 
 
-def build_cached(cof, dev, fp8, N=512, H=14, T=2048):
+def build_cached(cof, dev, fp8, N=512, H=14, T=2048, per_class=False):
     """cfg 002 frozen one-call training step (dropout keep 0.2, K = 393) from a RESIDENT cache of T 14x14x2048 maps (FP8
     E4M3 or bf16) with its labels, three ways: (a) the gathered step on cache.select(index), a fresh shuffled index
     per step (epoch() views, re-bound); (b) today's loop: cache.gather(index) + labels[index] + rebind + the plain
-    step; (c) the plain step on one fixed contiguous batch of the cache.  -> ({name: step}, info)"""
-    C, P, K = 2048, H * H, 393
+    step; (c) the plain step on one fixed contiguous batch of the cache.  per_class: the HMDB-51 per-class head instead
+    (M = K = 51, weight images kept by the caller, as frozen_perclass runs it).  -> ({name: step}, info)"""
+    C, P, K = 2048, H * H, 51 if per_class else 393
+    M = K if per_class else 1
     T = max(int(T), 4 * N)
     g = torch.Generator().manual_seed(42)
     labels = torch.randint(0, K, (T,), generator=g).to(dev)
@@ -1213,11 +1221,11 @@ def build_cached(cof, dev, fp8, N=512, H=14, T=2048):
         n = min(256, T - first)
         status = cache.write(first, _features(n, P, C, torch.bfloat16, dev, seed=42 + first).view(n, H, H, C))
         assert int(status.sum()) == 0
-    Wa = (torch.randn(C, 1, generator=g) / C ** 0.5).to(dev); ba = torch.zeros(1, device=dev)
+    Wa = (torch.randn(C, M, generator=g) / C ** 0.5).to(dev); ba = torch.zeros(M, device=dev)
     Wt = (torch.randn(C, K, generator=g) / C ** 0.5).to(dev); bt = torch.zeros(K, device=dev)
     pg = tuple(torch.empty_like(t) for t in (Wa, ba, Wt, bt))
     ctr = torch.zeros(1, dtype=torch.int64, device=dev)
-    kw = dict(flags=cof.attn_flags(False, False, True), keep_prob=0.2, seed=42, offset=ctr)
+    kw = dict(flags=cof.attn_flags(False, False, True), keep_prob=0.2, seed=42, offset=ctr, weight_images=per_class)
     batches = [b for e in range(4) for b in cache.epoch(N, seed=e)]        # four epochs' shuffled batches, int32 views
     batch0 = cache.select(batches[0])
     st_a = cof.HeadTrainStep(batch0, batch0, Wa, ba, Wt, bt, None, (None, None) + pg, **kw)
@@ -1252,7 +1260,8 @@ def run_cached(cof, dev, args, which):
     batch (the dependent index read, and a fresh batch from HBM where (c)'s one batch may stay in the Infinity Cache);
     a / b: against the only route a shuffled epoch had."""
     fp8 = which == 'cached002_fp8'
-    forms, info = build_cached(cof, dev, fp8, args.batch, args.hw, args.cache_images)
+    per_class = which == 'cached_perclass_bf16'
+    forms, info = build_cached(cof, dev, fp8, args.batch, args.hw, args.cache_images, per_class=per_class)
     for _ in range(args.warmup):
         for step in forms.values():
             step()
@@ -1264,8 +1273,9 @@ def run_cached(cof, dev, args, which):
             sec, _ = timed(step, args.steps, 0, min_ms=0.0, repeats=1)
             runs[name].append(sec * 1e6)
     med = {k: sorted(v)[len(v) // 2] for k, v in runs.items()}
-    return {'workload': '{}: cfg 002 frozen one-call training step from a resident {} feature cache, three variants '
-                        'alternating in one process; {}'.format(which, 'FP8 E4M3' if fp8 else 'bf16', info['shape']),
+    return {'workload': '{}: {} frozen one-call training step from a resident {} feature cache, three variants '
+                        'alternating in one process; {}'.format(which, 'HMDB-51 per-class' if per_class else 'cfg 002',
+                                                                'FP8 E4M3' if fp8 else 'bf16', info['shape']),
             'us_per_step': {k: round(v, 2) for k, v in med.items()},
             'us_per_step_runs': {k: [round(x, 2) for x in v] for k, v in runs.items()},
             'us_per_step_spread': {k: round(max(v) - min(v), 2) for k, v in runs.items()},
@@ -1418,7 +1428,9 @@ def run_epoch(cof, dev, args, which):
 
 
 CACHED_CLIPS = {'cached_hmdb_clips_fp8': (51, 'softmax-xentropy', True), 'cached_hmdb_clips_bf16': (51, 'softmax-xentropy', False),
-                'cached_charades_fp8': (157, 'multi-label', True), 'cached_charades_bf16': (157, 'multi-label', False)}
+                'cached_charades_fp8': (157, 'multi-label', True), 'cached_charades_bf16': (157, 'multi-label', False),
+                'cached_hmdb_perclass_clips_bf16': (51, 'softmax-xentropy', False)}
+PER_CLASS_CLIPS = ('cached_hmdb_perclass_clips_bf16',)      # M = K (the HMDB-51 configuration) instead of M = 1
 
 
 def build_cached_clips(cof, dev, which, B=8, F=4, H=14, T=2048, eval_B=4, eval_F=25):
@@ -1442,14 +1454,15 @@ def build_cached_clips(cof, dev, which, B=8, F=4, H=14, T=2048, eval_B=4, eval_F
     vlab = None if ml else torch.randint(0, K, (V,), generator=g).to(dev)
     vtar = (torch.rand(V, K, generator=g) < 0.05).float().to(dev) if ml else None
     cache.set_videos(torch.arange(V) * NF, torch.full((V,), NF), labels=vlab, targets=vtar)
-    Wa = (torch.randn(C, 1, generator=g) / C ** 0.5).to(dev); ba = torch.zeros(1, device=dev)
+    M = K if which in PER_CLASS_CLIPS else 1
+    Wa = (torch.randn(C, M, generator=g) / C ** 0.5).to(dev); ba = torch.zeros(M, device=dev)
     Wt = (torch.randn(C, K, generator=g) / C ** 0.5).to(dev); bt = torch.zeros(K, device=dev)
     tw = (torch.randn(K, generator=g) * 0.01).to(dev); tb = torch.full((1,), 1.0 / F, device=dev)
     pg = tuple(torch.empty_like(t) for t in (Wa, ba, Wt, bt))
     tg = (torch.empty_like(tw), torch.empty_like(tb))
     ctr = torch.zeros(1, dtype=torch.int64, device=dev)
     kw = dict(flags=cof.attn_flags(False, False, True), keep_prob=0.2, seed=42, offset=ctr, frames=F, temporal=(tw, tb),
-              temporal_grads=tg, action_loss=loss)
+              temporal_grads=tg, action_loss=loss, weight_images=M > 1)
     lab = lambda c: c.targets if ml else c.labels
     batches = [b for e in range(4) for b in cache.video_epoch(B, seed=e)]      # four epochs' shuffled video batches
     gen = torch.Generator(device=dev)
@@ -1497,7 +1510,7 @@ def build_cached_clips(cof, dev, which, B=8, F=4, H=14, T=2048, eval_B=4, eval_F
 
     bytes_img = P * C * (1 if fp8 else 2)
     info = {'shape': '{} clips x {} frames of {} videos x {} frames ({} maps {}x{}x{}), K={}, {}, temporal attention, '
-                     'dropout keep=0.2'.format(B, F, V, NF, T, H, H, C, K, loss),
+                     'dropout keep=0.2'.format(B, F, V, NF, T, H, H, C, K, loss) + (', per-class maps (M = K)' if M > 1 else ''),
             'eval_shape': '{} clips x {} frames'.format(eval_B, eval_F),
             'feature_bytes_per_step': 2 * B * F * bytes_img, 'gather_bytes_per_step': 2 * B * F * bytes_img,
             'cache_bytes': T * bytes_img, 'steps': (st_a, st_b, st_c), 'cache': cache}
@@ -1735,7 +1748,8 @@ def main():
                                                          'update_perclass', 'poseatt', 'video_perclass', 'video003',
                                                          'hico002', 'charades_clips', 'frozen002', 'frozen003',
                                                          'frozen_perclass', 'frozen002_fp8', 'eval002_fp8',
-                                                         'cached002_fp8', 'cached002_bf16', 'epoch002_fp8',
+                                                         'cached002_fp8', 'cached002_bf16', 'cached_perclass_bf16',
+                                                         'epoch002_fp8',
                                                          'epoch002_bf16', 'explain002', 'map393'] +
                     sorted(EVAL_CLIPS) + sorted(RANK_WORKLOADS) + sorted(CACHED_CLIPS))
     ap.add_argument('--clips', type=int, default=8, help='video_*: clips per batch')
@@ -1787,7 +1801,7 @@ def main():
     if args.workload in ('frozen002_fp8', 'eval002_fp8'):
         print(json.dumps(run_fp8(cof, dev, args, args.workload)))
         return
-    if args.workload in ('cached002_fp8', 'cached002_bf16'):
+    if args.workload in ('cached002_fp8', 'cached002_bf16', 'cached_perclass_bf16'):
         print(json.dumps(run_cached(cof, dev, args, args.workload)))
         return
     if args.workload in ('epoch002_fp8', 'epoch002_bf16'):
