@@ -21,6 +21,25 @@ int hip_fail(hipError_t e, const char* what) {
   return APA_ERR_HIP;
 }
 
+__global__ void zero_words_kernel(uint32_t* __restrict__ p, size_t n) {
+  const size_t stride = (size_t)gridDim.x * blockDim.x;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) p[i] = 0u;
+}
+
+int zero_fill(void* p, size_t bytes, hipStream_t st) {
+  if (!p || (bytes & 3) || (reinterpret_cast<uintptr_t>(p) & 3)) {
+    set_error("zero_fill: %zu bytes at %p are not whole 4-byte words (internal)", bytes, p);
+    return APA_ERR_INVALID_ARG;
+  }
+  const size_t n = bytes / 4;
+  if (n == 0) return APA_OK;
+  const size_t nb = (n + 255) / 256;
+  hipLaunchKernelGGL(zero_words_kernel, dim3((unsigned)(nb < 1024 ? nb : 1024)), dim3(256), 0, st,
+                     static_cast<uint32_t*>(p), n);
+  APA_LAUNCH_CHECK("zero_words_kernel");
+  return APA_OK;
+}
+
 }  // namespace apa
 
 using namespace apa;
@@ -907,7 +926,8 @@ static int attn_head_eval(PoolCall d, const M1Fwd& f, const int64_t* labels, flo
     set_error("apa_attn_head_eval_step: workspace too small for the label-free form");
     return APA_ERR_WORKSPACE;
   }
-  APA_HIP_CHECK(hipMemsetAsync(d.ws, 0, (size_t)d.N * 8, d.st));
+  rc = zero_fill(d.ws, (size_t)d.N * 8, d.st);
+  if (rc != APA_OK) return rc;
   float* lscratch = reinterpret_cast<float*>(static_cast<char*>(d.ws) + (size_t)d.N * 8);
   return apa_softmax_xent_fwd_bwd(f.logits, static_cast<const int64_t*>(d.ws), lscratch, nullptr, probs, pred, d.N,
                                   d.K, 1.0f, 1.0f, d.st);

@@ -16,6 +16,10 @@ namespace apa {
 // Thread-local error text behind apa_last_error().
 void set_error(const char* fmt, ...);
 int hip_fail(hipError_t e, const char* what);
+// Zero `bytes` (whole 4-byte words) at `p` with a kernel launch on `st`.  Not hipMemsetAsync: a memset node of a captured
+// graph is not a launch, and the replays of such graphs did not reproduce the eager calls (tests/test_graph_replay_gpu.py);
+// with this, every node a capture of the library records is a kernel.
+int zero_fill(void* p, size_t bytes, hipStream_t st);
 
 // Per-device memo slots.  A host thread may hipSetDevice between two calls, so whatever a launcher remembers
 // about "the device" (CU count, LDS limit, "hipFuncSetAttribute already done for this kernel") is keyed by the

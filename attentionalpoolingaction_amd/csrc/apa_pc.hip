@@ -518,7 +518,8 @@ int pc_weight_images(const PoolCall& d, const float* Wa, const float* ba, const 
     if (tr) tr->wimg_fused = 1;
     const int rc = pc_fused_prep(f, Wa, Wt, ba, bt, C, K, st, nullptr, true);
     if (rc != APA_OK) return rc;
-    APA_HIP_CHECK(hipMemsetAsync(f.bits_tag, 0, 64, st));   // whatever the keep-bit map held: nobody may believe it
+    const int rcz = zero_fill(f.bits_tag, 64, st);          // whatever the keep-bit map held: nobody may believe it
+    if (rcz != APA_OK) return rcz;
     if (maps) {
       auto put = [&](int role, void* dst, int f32, int sh, int a, int b, int d, int e) {
         apa_weight_image& m = maps[n++];

@@ -1177,8 +1177,7 @@ static int pose_rows_dppre(const PoseCall& c, const PoseBwd& b) {
   const int rc = m1_colsum(cs, st);
   if (rc != APA_OK) return rc;
   if (!dPl) {
-    APA_HIP_CHECK(hipMemsetAsync(b.dW2, 0, (size_t)Cp * J * sizeof(float), st));
-    return APA_OK;
+    return zero_fill(b.dW2, (size_t)Cp * J * sizeof(float), st);
   }
   GemmDesc g;  // dW2[j,q] = sum_r Ppre[r,j] dPl[r,q]
   g.A = Ppre; g.lda = Cp; g.ta = dt_code(c.dtype); g.a_kc = false;

@@ -2184,7 +2184,11 @@ class HeadTrainStep:
         whose backbone hands over a fresh conv5 tensor every step) and / or at another dropout offset (int), without
         re-allocating outputs or workspace.  Fused attention input only (Xatt is X).
         `index` (a step on a CachedBatch): another batch of the same cache -- an int32 tensor of the same length on
-        the cache's device (an epoch's views pass uncopied); one marshalled pointer changes."""
+        the cache's device (an epoch's views pass uncopied); one marshalled pointer changes.
+        Under a captured hipGraph: everything rebind changes travels by value (pointers, the int offset), so a graph
+        captured BEFORE the rebind keeps replaying the step as captured -- write new indices / labels / features into
+        the bound tensors in place instead, and bind the dropout offset to a device counter (`offset=` a 1-element
+        int64 CUDA tensor), which the replays read and advance."""
         keep = list(self._keep)
         if index is not None:
             if self._cached is None:
@@ -2883,7 +2887,11 @@ class HeadTrainEpoch:
         """Enqueue the epoch over `order` (int32 on the cache's device, a whole number of batches: FeatureCache.order,
         or its first steps * N entries) with `lr[s]` the learning rate of update s (a sequence of order.numel() / N
         floats, or one float for all).  `offset` (int): another dropout offset for the first step.  `labels`: int64
-        [count] in visiting order, for an epoch built with labels_cached=False.  Returns the number of steps."""
+        [count] in visiting order, for an epoch built with labels_cached=False.  Returns the number of steps.
+        Under a captured hipGraph: `lr[s]`, an int `offset` and the addresses of `order` / `labels` are read HERE, when
+        the call is enqueued, and are frozen in the graph -- every replay trains with the captured rates (another
+        `lr` needs a re-capture); the contents of `order` / `labels`, the device dropout counter (advanced by the
+        number of steps per replay), weights and accumulators are re-read from HBM."""
         who = 'HeadTrainEpoch.run'
         order = _epoch_order_arg(who, order, self.cache)
         count = int(order.numel())

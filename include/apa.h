@@ -17,7 +17,12 @@
  *     re-entrant (the reference ops run concurrently on TF inter-op threads,
  *     src/custom_ops/pose_utils.hpp:7-14).
  *   - every launch goes to the hipStream_t passed as `void* stream`; no implicit
- *     synchronisation, no allocation -> all entry points are hipGraph-capturable.
+ *     synchronisation, no allocation -> all entry points are hipGraph-capturable
+ *     (tests/test_graph_replay_gpu.py replays each of them), with two exceptions that are meant for bind time
+ *     and for measurement: apa_clip_by_norm_prepare (marshals a host table and waits for its own copies) and
+ *     apa_prof_event_record (records a HIP event).  A capture freezes what travels by value: a dropout offset
+ *     without APA_FLAG_RNG_DEVICE, the lr array of apa_epoch_sgd, the (seed, epoch) of apa_epoch_order and the
+ *     members of the descriptor structs; what a replay re-reads is what lies in HBM behind the pointers.
  *   - layouts are the reference's: feature maps NHWC flattened to [N, P=H*W, C]; 1x1-conv
  *     weights [Cin, Cout] (TF HWIO [1,1,Cin,Cout] squeezed); float32 unless stated.
  *
