@@ -4,6 +4,7 @@
 #include <stdio.h>
 
 #include "apa_internal.h"
+#include "../../include/apa_clip_epoch.h"
 
 namespace apa {
 
@@ -1338,6 +1339,197 @@ extern "C" int apa_attn_head_eval_epoch_cached(const apa_epoch* ep, const apa_fe
                                         zsave, abar, loss ? loss + (size_t)s * (1 + N) : nullptr, probs + row * K,
                                         pred + row, ws, ws_bytes, s == steps - 1 ? last : N, P, C, Ca, K, M, flags,
                                         dtype, stream);
+    if (rc != APA_OK) return rc;
+  }
+  return APA_OK;
+}
+
+// ---- a whole epoch of CLIPS / sigmoid losses behind one host call (apa_clip_epoch.h) --------------------------------
+// The same construction as the flat epoch calls above, with the keyed sampler in front of every step: the loop over
+// apa_sample_clip_frames_keyed, the *_cached_clips step and (training) apa_momentum_sgd_step, every refusal made first.
+
+// the epoch's own refusals; F: frames per video (1 without a clip); *B, *steps: videos per step, steps
+static int clip_epoch_check(const char* fn, const apa_epoch* ep, const apa_clip_epoch* ce,
+                            const apa_feature_cache* cache, const apa_clip_pool* clip, int N, bool train, int* B,
+                            int* steps) {
+  if (!ep || !ep->order) {
+    set_error("%s: null apa_epoch / order pointer", fn);
+    return APA_ERR_INVALID_ARG;
+  }
+  if (!cache) {
+    set_error("%s: null apa_feature_cache", fn);
+    return APA_ERR_INVALID_ARG;
+  }
+  if (!ce) {
+    set_error("%s: null apa_clip_epoch", fn);
+    return APA_ERR_INVALID_ARG;
+  }
+  const int F = clip ? clip->frames : 1;
+  if (N <= 0 || F <= 0 || N % F != 0) {
+    set_error("%s: N=%d is not a whole, positive number of clips of %d frames", fn, N, F);
+    return APA_ERR_INVALID_ARG;
+  }
+  const int b = N / F;
+  if (train ? (ep->count < b || ep->count % b != 0) : ep->count < 1) {
+    set_error(train ? "%s: apa_epoch.count=%d is not a whole, positive number of batches of B=%d videos"
+                    : "%s: apa_epoch.count=%d: an evaluation pass visits at least one video (B=%d)", fn, ep->count, b);
+    return APA_ERR_INVALID_ARG;
+  }
+  const long long s = ((long long)ep->count + b - 1) / b;
+  if (s * b > 0x7fffffffLL) {
+    set_error("%s: steps * B = %lld is past 2^31 - 1 (count=%d, B=%d)", fn, s * b, ep->count, b);
+    return APA_ERR_INVALID_ARG;
+  }
+  *B = b;
+  *steps = (int)s;
+  return APA_OK;
+}
+
+// the sampler's call of one step: labels / targets are sampled where both the table and the destination are given
+static int clip_epoch_sample(const apa_clip_epoch* ce, const int32_t* videos, int64_t* labels, float* targets,
+                             int32_t* status, int B, int F, int K, int mode, int step, void* stream) {
+  const bool lab = ce->video_labels && labels, tgt = ce->video_targets && targets;
+  return apa_sample_clip_frames_keyed(ce->video_first, ce->video_frames, lab ? ce->video_labels : nullptr,
+                                      tgt ? ce->video_targets : nullptr, videos, ce->index, lab ? labels : nullptr,
+                                      tgt ? targets : nullptr, status, ce->V, B, F, K, mode, ce->seed, ce->epoch,
+                                      (uint64_t)step, stream);
+}
+
+// what the step will read from the sampler must be sampled; then the sampler's own refusals for the shape
+static int clip_epoch_sampler_check(const char* fn, const apa_clip_epoch* ce, const int32_t* videos, bool need_labels,
+                                    bool need_targets, int B, int F, int K, int mode) {
+  if (!ce->index || (reinterpret_cast<uintptr_t>(ce->index) & 3)) {
+    set_error("%s: apa_clip_epoch.index must be a 4-byte aligned device pointer (int32 [B*frames] scratch)", fn);
+    return APA_ERR_INVALID_ARG;
+  }
+  if (need_targets && (!ce->video_targets || !ce->targets)) {
+    set_error("%s: a sigmoid loss reads the sampled targets: apa_clip_epoch.video_targets and .targets are required", fn);
+    return APA_ERR_INVALID_ARG;
+  }
+  if (need_labels && (!ce->video_labels || !ce->labels)) {
+    set_error("%s: the softmax cross-entropy reads the sampled labels: apa_clip_epoch.video_labels and .labels are "
+              "required", fn);
+    return APA_ERR_INVALID_ARG;
+  }
+  const bool lab = ce->video_labels && ce->labels, tgt = ce->video_targets && ce->targets;
+  return sample_clip_check(fn, ce->video_first, ce->video_frames, lab ? ce->video_labels : nullptr,
+                           tgt ? ce->video_targets : nullptr, videos, ce->index, ce->labels, ce->targets, ce->V, B, F, K,
+                           mode, false);
+}
+
+extern "C" int apa_attn_head_train_epoch_cached_clips(
+    const apa_epoch* ep, const apa_epoch_sgd* opt, const apa_clip_epoch* ce, const apa_feature_cache* cache,
+    const apa_multilabel* ml, const apa_clip_pool* clip, const apa_hooks* hooks, const void* X, const void* Xatt,
+    const float* Wa, const float* ba, const float* Wt, const float* bt, const int64_t* labels, float loss_wt,
+    float grad_scale, float* logits, float* att, float* zsave, float* abar, float* loss, float* G, void* dX, void* dXatt,
+    float* dWa, float* dba, float* dWt, float* dbt, void* ws, size_t ws_bytes, int N, int P, int C, int Ca, int K, int M,
+    unsigned flags, float keep_prob, uint64_t seed, uint64_t offset, int dtype, void* stream) {
+  const char* fn = "apa_attn_head_train_epoch_cached_clips";
+  (void)labels;   // the sampler's take their place
+  if (!opt || !opt->lr) {
+    set_error("%s: null apa_epoch_sgd / lr pointer", fn);
+    return APA_ERR_INVALID_ARG;
+  }
+  int B = 0, steps = 0;
+  int rc = clip_epoch_check(fn, ep, ce, cache, clip, N, true, &B, &steps);
+  if (rc != APA_OK) return rc;
+  if ((rc = epoch_sgd_check(fn, opt)) != APA_OK) return rc;
+  const int F = N / B;
+  if ((rc = clip_epoch_sampler_check(fn, ce, ep->order, ml == nullptr, ml != nullptr, B, F, K, ce->mode)) != APA_OK)
+    return rc;
+  apa_multilabel mls{};
+  if (ml) {
+    mls = *ml;
+    mls.labels = ce->targets;
+    if ((rc = check_multilabel(fn, &mls)) != APA_OK) return rc;
+  }
+  const apa_multilabel* const m = ml ? &mls : nullptr;
+  apa_feature_cache fc = *cache;
+  fc.index = ce->index;
+  fc.labels_cached = 0;
+  {  // the step's checks, once for the shape
+    PoolCall d = fp8_served(pool_call({N, P, C, Ca, K, M, dtype}, flags, keep_prob, seed, offset, ws, ws_bytes, stream,
+                                      hooks));
+    // (per-class maps: refused here although the step serves them -- this call's update rewrites no weight images)
+    if ((rc = cache_check(fn, &fc, d, X, Xatt, false, true, dX, false)) != APA_OK) return rc;
+    d.fc = &fc;
+    const StepLoss L{m, m ? nullptr : ce->labels, clip != nullptr, clip, loss_wt, grad_scale, loss, G};
+    const M1Fwd f{X, Xatt, Wa, ba, Wt, bt, logits, att, zsave, abar};
+    const M1Bwd b{X, Xatt, Wa, Wt, bt, att, zsave, abar, G, dX, dXatt, dWa, dba, dWt, dbt};
+    size_t pool_bytes = 0;
+    if ((rc = head_step_check(fn, d, L, logits, &pool_bytes)) != APA_OK) return rc;
+    d.ws_bytes = pool_bytes;
+    if ((rc = epoch_half_check(d, &f, nullptr)) != APA_OK) return rc;
+    d.flags |= APA_FLAG_WS_FROM_FWD;
+    if ((rc = epoch_half_check(d, nullptr, &b)) != APA_OK) return rc;
+  }
+  const bool rng_dev = (flags & APA_FLAG_RNG_DEVICE) != 0;   // the counter in HBM advances by itself
+  for (int s = 0; s < steps; ++s) {
+    rc = clip_epoch_sample(ce, ep->order + (size_t)s * B, ce->labels, ce->targets, fc.status, B, F, K, ce->mode, s,
+                           stream);
+    if (rc != APA_OK) return rc;
+    rc = apa_attn_head_train_step_cached_clips(&fc, m, clip, hooks, X, Xatt, Wa, ba, Wt, bt, ce->labels, loss_wt,
+                                               grad_scale, logits, att, zsave, abar, loss + (size_t)s * (1 + B), G, dX,
+                                               dXatt, dWa, dba, dWt, dbt, ws, ws_bytes, N, P, C, Ca, K, M, flags,
+                                               keep_prob, seed, rng_dev ? offset : offset + (uint64_t)s, dtype, stream);
+    if (rc != APA_OK) return rc;
+    rc = apa_momentum_sgd_step(opt->nseg, opt->weights, opt->sizes, opt->weight_decay, opt->grad_flat, opt->acc_flat,
+                               opt->lr[s], opt->momentum, opt->grad_scale, stream);
+    if (rc != APA_OK) return rc;
+  }
+  return APA_OK;
+}
+
+extern "C" int apa_attn_head_eval_epoch_cached_clips(
+    const apa_epoch* ep, const apa_clip_epoch* ce, const apa_feature_cache* cache, const apa_clip_pool* clip,
+    int scores_kind, const void* X, const void* Xatt, const float* Wa, const float* ba, const float* Wt, const float* bt,
+    const int64_t* labels, float* logits, float* att, float* zsave, float* abar, float* loss, float* probs, int64_t* pred,
+    void* ws, size_t ws_bytes, int N, int P, int C, int Ca, int K, int M, unsigned flags, int dtype, void* stream) {
+  const char* fn = "apa_attn_head_eval_epoch_cached_clips";
+  (void)labels;   // the sampler's take their place
+  int B = 0, steps = 0;
+  int rc = clip_epoch_check(fn, ep, ce, cache, clip, N, false, &B, &steps);
+  if (rc != APA_OK) return rc;
+  const int F = N / B;
+  const int last = ep->count - (steps - 1) * B;   // videos of the last step, 1..B
+  if ((rc = clip_epoch_sampler_check(fn, ce, ep->order, loss != nullptr, false, B, F, K, APA_CLIP_FRAMES_UNIFORM)) !=
+      APA_OK)
+    return rc;
+  apa_feature_cache fc = *cache;
+  fc.index = ce->index;
+  fc.labels_cached = 0;
+  {  // the step's checks, once for the full batch and once for the last step's shape
+    const M1Fwd f{X, Xatt, Wa, ba, Wt, bt, logits, att, zsave, abar};
+    for (int b : {B, last}) {
+      const int n = b * F;
+      PoolCall d = fp8_served(pool_call({n, P, C, Ca, K, M, dtype}, flags, 1.0f, 0, 0, ws, ws_bytes, stream));
+      // (per-class maps: refused with the training epoch's, so that the pair stays one interface)
+      if ((rc = cache_check(fn, &fc, d, X, Xatt, false, false, nullptr, false)) != APA_OK) return rc;
+      if ((rc = eval_scores_check(fn, clip, scores_kind, n, K, logits, loss ? ce->labels : nullptr, loss, probs, pred)) !=
+          APA_OK)
+        return rc;
+      d.fc = &fc;
+      d.flags &= ~(unsigned)APA_FLAG_TRAIN;
+      if ((rc = epoch_half_check(d, &f, nullptr)) != APA_OK) return rc;
+    }
+  }
+  for (int s = 0; s < steps; ++s) {
+    const size_t row = (size_t)s * B;
+    const int b = s == steps - 1 ? last : B;
+    rc = clip_epoch_sample(ce, ep->order + row, ce->labels ? ce->labels + row : nullptr,
+                           ce->targets ? ce->targets + row * K : nullptr, fc.status, b, F, K, APA_CLIP_FRAMES_UNIFORM, s,
+                           stream);
+    if (rc != APA_OK) return rc;
+    apa_clip_pool cp{};
+    if (clip) {
+      cp = *clip;
+      cp.pooled = clip->pooled + row * K;
+    }
+    // (clip == NULL: one-frame videos -- the logits rows are the per-video rows and advance with the others)
+    rc = apa_attn_head_eval_step_cached_clips(&fc, clip ? &cp : nullptr, scores_kind, X, Xatt, Wa, ba, Wt, bt,
+                                              loss ? ce->labels + row : nullptr, clip ? logits : logits + row * K, att,
+                                              zsave, abar, loss ? loss + (size_t)s * (1 + B) : nullptr, probs + row * K,
+                                              pred + row, ws, ws_bytes, b * F, P, C, Ca, K, M, flags, dtype, stream);
     if (rc != APA_OK) return rc;
   }
   return APA_OK;

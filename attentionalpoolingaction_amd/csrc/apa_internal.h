@@ -247,6 +247,10 @@ inline void ml_scales(int kind, float wt, float grad_scale, int n_loss, int K, f
 }
 // apa_capi.hip: a valid apa_multilabel (non-null, labels given, a sigmoid loss kind), or the refusal in fn's name
 int check_multilabel(const char* fn, const apa_multilabel* ml);
+// what apa_sample_clip_frames and apa_sample_clip_frames_keyed refuse (apa_clipcache.hip); nothing has touched the GPU
+int sample_clip_check(const char* fn, const void* video_first, const void* video_frames, const void* video_labels,
+                      const void* video_targets, const void* videos, const void* index, const void* labels,
+                      const void* targets, int V, int B, int frames, int K, int mode, bool u_missing);
 
 // ..._WITH_POSE_FEAT (nets_factory.py:289-295): J extra top-down channels (apa_m1_cat.hip), as the caller describes
 // them (apa.h): Xext [N,P,J] f32, zext [N,J] f32 (forward output, backward input), dXext [N,P,J] f32 (backward)

@@ -1065,6 +1065,7 @@ class FusedHeadStep:
         self._fp8 = False
         self._cb = False
         self._epoch = self._epoch_key = None     # the bound epoch call of train_epoch
+        self._video_epoch = self._video_epoch_key = None     # ... and of train_video_epoch
         self.probe_events = None
 
     @staticmethod
@@ -1156,6 +1157,7 @@ class FusedHeadStep:
         self._steps.clear()
         self._step_obj = self._key = None
         self._epoch = self._epoch_key = None
+        self._video_epoch = self._video_epoch_key = None
 
     def make_optimizer(self, learning_rate: float, deploy_config: Optional[DeploymentConfig] = None):
         """deploy.configure_optimizer on the head's parameters (the nn.Parameters themselves: their `_version` feeds
@@ -1509,6 +1511,101 @@ class FusedHeadStep:
         head._step += steps                              # a fresh dropout mask per step, as __call__ leaves it
         return self._epoch.loss[:steps]
 
+    def video_epoch_unsupported_reason(self, cache=None) -> str:
+        """why `train_video_epoch` cannot run this configuration (on this cache); '' when it can.  The clip epoch call is
+        the CachedClips step -- softmax cross-entropy or a sigmoid loss, with or without the TemporalAttention conv --
+        with the fused momentum-SGD update behind every step."""
+        tr = self.cfg.TRAIN
+        why = self.fp8_unsupported_reason(self.head, self.network_fn)
+        if why:
+            return why
+        if not self.frozen_features:
+            return 'frozen_features=False (a cache has no gradient: build the step with frozen_features=True)'
+        if tr.OPTIMIZER not in ('momentum', 'sgd'):
+            return 'TRAIN.OPTIMIZER %r (the epoch call runs the momentum / sgd update)' % tr.OPTIMIZER
+        if int(tr.ITER_SIZE) != 1:
+            return 'TRAIN.ITER_SIZE %d (gradient accumulation over micro-steps)' % int(tr.ITER_SIZE)
+        if self.clipper is not None and self.clipper.active:
+            return 'TRAIN.CLIP_GRADIENTS > 0 (an active gradient clipper between the step and the update)'
+        if self.loss_scale != 1.0:
+            return ('more than one clone (loss_scale %r: the gradients of an epoch call are not all-reduced)'
+                    % self.loss_scale)
+        if cache is not None:
+            multi_label = tr.LOSS_FN_ACTION != 'softmax-xentropy'
+            if cache.video_first is None:
+                return 'a FeatureCache without videos (FeatureCache.set_videos names them)'
+            if multi_label and cache.video_targets is None:
+                return 'a FeatureCache without video targets (LOSS_FN_ACTION %r reads them)' % tr.LOSS_FN_ACTION
+            if not multi_label and cache.video_labels is None:
+                return 'a FeatureCache without video labels (the softmax cross-entropy reads them)'
+        return ''
+
+    def train_video_epoch(self, cache, batch_videos: int, frames: int, order, lr=None, mode: str = 'random-segment',
+                          seed: int = 0, epoch: int = 0):
+        """A whole epoch of frozen-feature training on the VIDEOS of a resident frame cache (`FeatureCache.set_videos`)
+        as ONE host call (`clip_epoch.ClipTrainEpoch`: apa_attn_head_train_epoch_cached_clips): steps = order.numel() /
+        batch_videos times the step `__call__` runs on `clip_epoch.sample_clips_keyed(cache, order[s*B:(s+1)*B], frames,
+        mode, seed, epoch, step=s)` (the clips' own labels / targets, a fresh dropout mask per step) followed by the
+        update `opt.step()` runs -- the same launches, the same bits.  Served under the softmax cross-entropy and both
+        multi-label losses, with and without NET.USE_TEMPORAL_ATT; `frames=1`: one-frame videos, the flat multi-label
+        datasets.  `order`: int32 VIDEO ids on the cache's device (`cof.epoch_order(cache.V, seed, epoch, device)`, or
+        its first steps * batch_videos ids).  `lr`: one learning rate per step, or None for the optimiser's own.  Needs
+        `make_optimizer()` first.  The staleness guards run once, in front; the head's step counter advances by
+        `steps`.  Returns the loss log [steps, 1 + batch_videos] as a device tensor -- nothing synchronises.  Anything
+        that is not served (more than one clone, frozen_features=False, per-class maps, the cfg 003 form, another
+        optimiser, ITER_SIZE > 1, an active clipper) is a ValueError that names the reason."""
+        from .custom_ops import clip_epoch, custom_ops_factory as cof
+        who = 'FusedHeadStep.train_video_epoch'
+        if self._optimizer is None:
+            raise ValueError('%s: make_optimizer() first (the epoch call runs its update)' % who)
+        why = self.video_epoch_unsupported_reason(cache)
+        if why:
+            raise ValueError('%s: a clip epoch call is not served with %s' % (who, why))
+        opt, head, tr = self._optimizer, self.head, self.cfg.TRAIN
+        opt.check_fresh()                                # weights written behind the optimiser's back?
+        self._check_frozen_fresh()
+        if opt.operand_copies():
+            raise ValueError('%s: an epoch call is not served with operand copies attached to the optimiser (%s): its '
+                             'update rewrites none' % (who, ', '.join(opt._watched)))
+        B, F = int(batch_videos), int(frames)
+        count = int(order.numel())
+        if B < 1 or F < 1 or count < B or count % B:
+            raise ValueError('%s: order holds %d video ids, not a whole number of batches of %d' % (who, count, B))
+        steps = count // B
+        lrs = [float(opt.lr)] * steps if lr is None else [float(v) for v in lr]
+        if len(lrs) != steps:
+            raise ValueError('%s: one learning rate per step expected (%d for %d steps)' % (who, len(lrs), steps))
+        p, v = {n: t.data for n, t in self.params.items()}, self._grad_out
+        temporal = {}
+        if self.temporal is not None:                    # exactly what _run does in front of a step
+            if F > 1 and not self.temporal._bias_initialised:
+                with torch.no_grad():
+                    self.temporal['biases'].fill_(1.0 / F)
+                self.temporal._bias_initialised = True
+            if F == 1:                                   # no pooling: the conv gets no gradient, its weights still decay
+                v['temporal_weights'].zero_()
+                v['temporal_biases'].zero_()
+            else:
+                temporal = dict(temporal=(p['temporal_weights'], p['temporal_biases']),
+                                temporal_grads=(v['temporal_weights'], v['temporal_biases']))
+        multi_label = tr.LOSS_FN_ACTION != 'softmax-xentropy'
+        key = (id(cache), B, F, mode, tuple(t.data_ptr() for t in p.values()), self.bucket.flat.data_ptr(),
+               opt.acc.data_ptr(), tuple(opt.wd), float(opt.momentum))
+        if self._video_epoch is None or self._video_epoch_key != key or self._video_epoch.steps < steps:
+            self._video_epoch = clip_epoch.ClipTrainEpoch(
+                cache, B, F, p['att_weights'], p['att_biases'], p['td_weights'], p['td_biases'],
+                (v['att_weights'], v['att_biases'], v['td_weights'], v['td_biases']),
+                [p[n] for n in self.bucket.names], list(opt.wd), self.bucket.flat, opt.acc, steps=steps,
+                action_loss=tr.LOSS_FN_ACTION, mode=mode, momentum=opt.momentum,
+                flags=cof.attn_flags(head.softmax_att, head.relu_att, True, False), keep_prob=head.keep_prob,
+                seed=head.seed, offset=head._step,
+                loss_wt=1.0 if multi_label else float(tr.LOSS_FN_ACTION_WT),   # (loss.py:93-101 passes no weight)
+                grad_scale=self.loss_scale, hooks=head.hooks, **temporal)
+            self._video_epoch_key = key
+        log = self._video_epoch.run(order, lrs, seed=seed, epoch=epoch, offset=head._step)
+        head._step += steps                              # a fresh dropout mask per step, as __call__ leaves it
+        return log
+
 
 class FusedHeadEval:
     """The evaluation counterpart of FusedHeadStep: what eval.py:181-197 computes from `network_fn(images)` -- the
@@ -1698,6 +1795,65 @@ class FusedHeadEval:
         scores, truth = meter.reserve(count)
         truth.copy_(cache.labels[order.long().clamp_(0, cache.T - 1)])       # (an id outside the cache is clamped, as
         ep.run(order, count, probs=scores)                                   # the kernels clamp it)
+        return meter
+
+    def evaluate_videos(self, cache, batch_videos: int, frames: int, meter=None, order=None):
+        """A whole validation pass over the VIDEOS of a resident frame cache (`FeatureCache.set_videos`) as ONE host
+        call (`clip_epoch.ClipEvalEpoch`: apa_attn_head_eval_epoch_cached_clips): the videos `order` names (int32 on the
+        cache's device; default all V, in table order) in batches of `batch_videos`, the last one shorter, each as
+        `frames` uniformly spaced frames (the reference's test protocol), with the scores AND the truth -- the videos'
+        labels, or their multi-hot targets when TRAIN.LOSS_FN_ACTION starts with 'multi-label' -- written straight into
+        `meter.reserve(count)`: no copy, no host step.  `meter`: an `eval_utils.DeviceEvaluation` (default:
+        `new_evaluation(count)`); it is returned, and equals one fed by `__call__` on
+        `cache.sample_clips(order[a:a+B], frames)` batch by batch, bit for bit.  With and without NET.USE_TEMPORAL_ATT
+        (which takes part at frames > 1, as in `__call__`).  Anything that is not served (per-class maps, the cfg 003
+        form, a cache without videos or without the truth the scores need) is a ValueError that names the reason.
+        `self.video_epoch` is the bound pass (`pred`, `pooled`, the last batch's frame logits and `att`)."""
+        import torch
+        from .custom_ops import clip_epoch, custom_ops_factory as cof
+        who = 'FusedHeadEval.evaluate_videos'
+        why = FusedHeadStep.fp8_unsupported_reason(self.head, self.network_fn)
+        if not why and getattr(cache, 'video_first', None) is None:
+            why = 'a FeatureCache without videos (FeatureCache.set_videos names them)'
+        if not why and self.multi_label and cache.video_targets is None:
+            why = ('a FeatureCache without video targets (LOSS_FN_ACTION %r: the truth is multi-hot)'
+                   % self.cfg.TRAIN.LOSS_FN_ACTION)
+        if not why and not self.multi_label and cache.video_labels is None:
+            why = 'a FeatureCache without video labels (the truth of the softmax scores)'
+        if why:
+            raise ValueError('%s: a video pass is not served with %s' % (who, why))
+        B, F = int(batch_videos), int(frames)
+        if B < 1 or F < 1:
+            raise ValueError('%s: batch_videos >= 1 and frames >= 1 expected' % who)
+        if order is None:
+            order = torch.arange(cache.V, dtype=torch.int32, device=cache.device)
+        count = int(cof._epoch_order_arg(who, order, cache).numel())
+        if meter is None:
+            meter = self.new_evaluation(count)
+        h = self.head
+        tw = tb = None
+        temporal = self.network_fn.temporal if F > 1 else None          # nets_factory.py:354-374, as __call__
+        if temporal is not None:
+            if not temporal._bias_initialised:
+                with torch.no_grad():
+                    temporal['biases'].fill_(1.0 / F)
+                temporal._bias_initialised = True
+            tw, tb = temporal['weights'].data.reshape(-1).contiguous(), temporal['biases'].data
+        key = (id(cache), B, F, tuple(p.data_ptr() for p in self._params()),
+               None if tw is None else tw.data_ptr(), None if tb is None else tb.data_ptr())
+        ep = getattr(self, 'video_epoch', None)
+        if ep is None or self._video_epoch_key != key or ep.capacity < count:
+            ep = self.video_epoch = clip_epoch.ClipEvalEpoch(
+                cache, B, F, h.att_weights.data, h.att_biases.data, h.td_weights.data, h.td_biases.data,
+                capacity=count, temporal=None if tw is None else (tw, tb),
+                flags=cof.attn_flags(h.softmax_att, h.relu_att, False, False),
+                scores='sigmoid' if self.multi_label else 'softmax')
+            self._video_epoch_key = key
+        scores, truth = meter.reserve(count)
+        if self.multi_label:
+            ep.run(order, count, probs=scores, targets=truth)
+        else:
+            ep.run(order, count, probs=scores, labels=truth)
         return meter
 
     def explain(self, images, classes=None, topk: int = 1, overlay: bool = True, input_images=None):

@@ -51,6 +51,14 @@ headline stays the cfg 002 training workload); run this file directly for one wo
             (HeadTrainStep.rebind + run + BoundMomentumSGD.run per step), (c) the deploy loop (FusedHeadStep on a
             CachedBatch + opt.step() per step); and the validation pass, FusedHeadEval.evaluate_cache against the loop
             of FusedHeadEval.__call__ + meter.update.
+  epoch_hmdb_clips_fp8 / epoch_hmdb_clips_bf16 / epoch_charades_fp8 / epoch_charades_bf16
+            a whole frozen-feature EPOCH of clips at the shapes of cached_hmdb_clips_* / cached_charades_* (81 videos x
+            25 frames, --clips 8 x --frames 4 per step: 10 steps, temporal attention, momentum SGD behind every step),
+            three routes alternating in one process, medians of five epochs, wall clock and device events as
+            epoch002_*: (a) the epoch call (apa_epoch_order + apa_attn_head_train_epoch_cached_clips, draws keyed on the
+            device), (b) the lean loop (torch.rand + sample_clips(out=) + HeadTrainStep.run + BoundMomentumSGD.run per
+            step), (c) the deploy loop (sample_clips + FusedHeadStep on the CachedClips + opt.step() per step); and the
+            validation pass at 4 x 25 uniform frames, FusedHeadEval.evaluate_videos against the per-batch loop.
   cached_hmdb_clips_fp8 / cached_hmdb_clips_bf16 / cached_charades_fp8 / cached_charades_bf16
             one-call CLIP training step from a resident FRAME cache (--cache-images maps in videos of 25 frames, FP8 E4M3
             or bf16): --clips 8 x --frames 4, temporal attention, M = 1; K = 51 with the softmax cross-entropy (HMDB-51)
@@ -1286,6 +1294,32 @@ def run_cached(cof, dev, args, which):
             'clamped_ids': int(info['steps'][0]._cached.cache.status)}
 
 
+def _measure_routes(forms, steps):
+    """{name: callable that enqueues one pass of `steps` steps} ALTERNATING, five timed passes each after one untimed:
+    per pass the wall clock around it with ONE synchronise at its end and a pair of device events around it; medians per
+    step, the five figures, the wall / device ratio and the spread (max - min) of the five wall figures"""
+    for fn in forms.values():
+        fn()
+    torch.cuda.synchronize()
+    wall, device = {k: [] for k in forms}, {k: [] for k in forms}
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    for _ in range(5):
+        for name, fn in forms.items():
+            t0 = time.perf_counter()
+            e0.record()
+            fn()
+            e1.record()
+            torch.cuda.synchronize()
+            wall[name].append((time.perf_counter() - t0) * 1e6 / steps)
+            device[name].append(e0.elapsed_time(e1) * 1e3 / steps)
+    med = lambda v: sorted(v)[len(v) // 2]
+    return {k: {'wall_us_per_step': round(med(wall[k]), 2), 'device_us_per_step': round(med(device[k]), 2),
+                'wall_over_device': round(med(wall[k]) / med(device[k]), 3),
+                'wall_spread_us': round(max(wall[k]) - min(wall[k]), 2),
+                'wall_runs': [round(x, 2) for x in wall[k]], 'device_runs': [round(x, 2) for x in device[k]]}
+            for k in forms}
+
+
 def _epoch_cfg002(dev, K, training):
     from attentionalpoolingaction_amd import config as apa_config, nets_factory
     apa_config.reset_cfg()
@@ -1394,26 +1428,7 @@ def run_epoch(cof, dev, args, which):
             scores, _, _ = ev(cache.select(idx))
             meter_b.update(scores, labels[a:a + N])
 
-    def measure(forms):
-        for fn in forms.values():
-            fn()
-        torch.cuda.synchronize()
-        wall, device = {k: [] for k in forms}, {k: [] for k in forms}
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        for _ in range(5):
-            for name, fn in forms.items():
-                t0 = time.perf_counter()
-                e0.record()
-                fn()
-                e1.record()
-                torch.cuda.synchronize()
-                wall[name].append((time.perf_counter() - t0) * 1e6 / steps)
-                device[name].append(e0.elapsed_time(e1) * 1e3 / steps)
-        med = lambda v: sorted(v)[len(v) // 2]
-        return {k: {'wall_us_per_step': round(med(wall[k]), 2), 'device_us_per_step': round(med(device[k]), 2),
-                    'wall_over_device': round(med(wall[k]) / med(device[k]), 3),
-                    'wall_runs': [round(x, 2) for x in wall[k]], 'device_runs': [round(x, 2) for x in device[k]]}
-                for k in forms}
+    measure = lambda forms: _measure_routes(forms, steps)
 
     train = measure({'a_epoch_call': epoch_a, 'b_lean_loop': epoch_b, 'c_deploy_loop': epoch_c,
                      'd_deploy_train_epoch': epoch_d})
@@ -1423,6 +1438,163 @@ def run_epoch(cof, dev, args, which):
                         'three routes alternating in one process, medians of five epochs'.format(
                             which, 'FP8 E4M3' if fp8 else 'bf16', steps, N, T, H, H, C, K),
             'steps_per_epoch': steps, 'train': train, 'fastest_train_route_by_wall': fastest, 'eval': evals,
+            'fastest_eval_route_by_wall': min(evals, key=lambda k: evals[k]['wall_us_per_step']),
+            'clamped_ids': int(cache.status)}
+
+
+CLIP_EPOCHS = {'epoch_hmdb_clips_fp8': (51, 'softmax-xentropy', True), 'epoch_hmdb_clips_bf16': (51, 'softmax-xentropy', False),
+               'epoch_charades_fp8': (157, 'multi-label', True), 'epoch_charades_bf16': (157, 'multi-label', False)}
+
+
+def _clip_epoch_net(dev, K, loss, training):
+    from attentionalpoolingaction_amd import config as apa_config, nets_factory
+    apa_config.reset_cfg()
+    pre = 'USE_POSE_PRELOGITS_BASED_ATTENTION'
+    cfg = apa_config.cfg_from_dict({'MODEL_NAME': 'resnet_v1_101',
+                                    'NET': {pre: True, pre + '_SINGLE_LAYER_ATT': True, 'USE_TEMPORAL_ATT': True},
+                                    'TRAIN': {'LOSS_FN_POSE': '', 'LOSS_FN_ACTION': loss}})
+    return nets_factory.get_network_fn('resnet_v1_101', K, 16, cfg, is_training=training, device=dev), cfg
+
+
+def run_clip_epoch(cof, dev, args, which):
+    """epoch_hmdb_clips_* / epoch_charades_*: a whole frozen-feature epoch of CLIPS (the shapes of cached_hmdb_clips_* /
+    cached_charades_*: --clips x --frames frames per step from videos of 25 frames, temporal attention, dropout keep
+    0.2, M = 1; K = 51 softmax cross-entropy or K = 157 'multi-label'; momentum SGD behind every step), one epoch = the
+    81 videos' worth of steps.  Three routes ALTERNATE in one process, medians of five epochs each, by wall clock (ONE
+    synchronise at the end of an epoch) and by a pair of device events:
+      a_epoch_call   cof.epoch_order(V, out=) + ClipTrainEpoch.run: one foreign call per epoch, keyed draws
+      b_lean_loop    per step: torch.rand + sample_clips(u=, out=) + HeadTrainStep.run + BoundMomentumSGD.run
+      c_deploy_loop  per step: sample_clips(out=) + deploy.FusedHeadStep(clips, None) + opt.step()
+    plus d, the deploy layer's own call (train_video_epoch), and the validation pass at 4 x 25 uniform frames:
+    deploy.FusedHeadEval.evaluate_videos (one call) against the loop of sample_clips + FusedHeadEval.__call__ +
+    meter.update."""
+    from attentionalpoolingaction_amd import deploy
+    from attentionalpoolingaction_amd.custom_ops import clip_epoch
+    K, loss, fp8 = CLIP_EPOCHS[which]
+    B, F, H, NF, eval_B, eval_F = args.clips, args.frames, args.hw, 25, 4, 25
+    C, P = 2048, H * H
+    V = max(int(args.cache_images) // NF, 4 * max(B, eval_B))
+    T = V * NF
+    steps = V // B
+    g = torch.Generator().manual_seed(42)
+    cache = cof.FeatureCache.empty((T, H, H, C), torch.float8_e4m3fn if fp8 else torch.bfloat16, dev)
+    for first in range(0, T, 256):
+        n = min(256, T - first)
+        status = cache.write(first, _features(n, P, C, torch.bfloat16, dev, seed=42 + first).view(n, H, H, C))
+        assert int(status.sum()) == 0
+    ml = loss != 'softmax-xentropy'
+    vlab = None if ml else torch.randint(0, K, (V,), generator=g).to(dev)
+    vtar = (torch.rand(V, K, generator=g) < 0.05).float().to(dev) if ml else None
+    cache.set_videos(torch.arange(V) * NF, torch.full((V,), NF), labels=vlab, targets=vtar)
+    Wa0, Wt0 = torch.randn(C, 1, generator=g) / C ** 0.5, torch.randn(C, K, generator=g) / C ** 0.5
+    tw0 = torch.randn(K, generator=g) * 0.01
+    lr, momentum, wd = 1e-3, 0.9, [1e-4, 0.0, 1e-4, 0.0, 1e-4, 0.0]
+    kw = dict(flags=cof.attn_flags(False, False, True), keep_prob=0.2, seed=42, action_loss=loss)
+    lab = lambda c: c.targets if ml else c.labels
+
+    def lean_state():
+        w = [Wa0.clone().to(dev), torch.zeros(1, device=dev), Wt0.clone().to(dev), torch.zeros(K, device=dev),
+             tw0.clone().to(dev), torch.full((1,), 1.0 / F, device=dev)]
+        grad = torch.zeros((sum(t.numel() for t in w),), device=dev)
+        o, views = 0, []
+        for t in w:
+            views.append(grad[o:o + t.numel()].view(t.shape))
+            o += t.numel()
+        return w, grad, torch.zeros_like(grad), tuple(views), torch.zeros(1, dtype=torch.int64, device=dev)
+
+    state = {'a': 0, 'b': 0, 'c': 0, 'd': 0}
+    lrs = [lr] * steps
+    # (a) one call per epoch
+    wa, ga, acca, va, ctra = lean_state()
+    ep = clip_epoch.ClipTrainEpoch(cache, B, F, *wa[:4], va[:4], wa, wd, ga, acca, steps=steps, temporal=(wa[4], wa[5]),
+                                   temporal_grads=(va[4], va[5]), momentum=momentum, offset=ctra, **kw)
+    order_a = torch.empty((V,), dtype=torch.int32, device=dev)
+
+    def epoch_a():
+        cof.epoch_order(V, 7, state['a'], dev, out=order_a)
+        ep.run(order_a[:steps * B], lrs, seed=7, epoch=state['a'])
+        state['a'] += 1
+
+    # (b) the lean loop
+    wb, gb, accb, vb, ctrb = lean_state()
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(7)
+    clips_b = cache.sample_clips(torch.arange(B, dtype=torch.int32, device=dev), F, mode='random-segment', generator=gen)
+    st_b = cof.HeadTrainStep(clips_b, clips_b, *wb[:4], lab(clips_b), (None, None) + vb[:4], offset=ctrb, frames=F,
+                             temporal=(wb[4], wb[5]), temporal_grads=(vb[4], vb[5]), **kw)
+    sgd_b = cof.BoundMomentumSGD(wb, wd, gb, accb)
+
+    def epoch_b():
+        state['b'] += 1
+        for vids in cache.video_epoch(B, seed=state['b']):
+            u = torch.rand((B * F,), dtype=torch.float32, device=dev, generator=gen)
+            cache.sample_clips(vids, F, mode='random-segment', u=u, out=clips_b)
+            st_b.run()
+            sgd_b.run(lr, momentum, 1.0)
+
+    # (c) the deploy loop, (d) the deploy layer's own epoch call
+    def deploy_net(training):
+        net, cfg = _clip_epoch_net(dev, K, loss, training)
+        with torch.no_grad():
+            net.head.att_weights.copy_(Wa0.to(dev).view_as(net.head.att_weights))
+            net.head.td_weights.copy_(Wt0.to(dev).view_as(net.head.td_weights))
+            net.temporal['weights'].copy_(tw0.to(dev).view_as(net.temporal['weights']))
+        return net, cfg
+    net_c, cfg_c = deploy_net(True)
+    fused = deploy.FusedHeadStep(net_c, cfg_c, frozen_features=True)
+    opt = fused.make_optimizer(lr)
+    clips_c = cache.sample_clips(torch.arange(B, dtype=torch.int32, device=dev), F, mode='random-segment', generator=gen)
+
+    def epoch_c():
+        state['c'] += 1
+        for vids in cache.video_epoch(B, seed=state['c']):
+            cache.sample_clips(vids, F, mode='random-segment', generator=gen, out=clips_c)
+            fused(clips_c, None)
+            opt.step()
+
+    net_d, cfg_d = deploy_net(True)
+    fused_d = deploy.FusedHeadStep(net_d, cfg_d, frozen_features=True)
+    fused_d.make_optimizer(lr)
+
+    def epoch_d():
+        cof.epoch_order(V, 9, state['d'], dev, out=order_a)
+        fused_d.train_video_epoch(cache, B, F, order_a[:steps * B], seed=9, epoch=state['d'])
+        state['d'] += 1
+
+    train = _measure_routes({'a_epoch_call': epoch_a, 'b_lean_loop': epoch_b, 'c_deploy_loop': epoch_c,
+                             'd_deploy_train_video_epoch': epoch_d}, steps)
+
+    # the validation pass: eval_B videos x 25 uniform frames per step, all V videos
+    net_e, cfg_e = deploy_net(False)
+    ev = deploy.FusedHeadEval(net_e, cfg_e)
+    meter_a, meter_b = ev.new_evaluation(V), ev.new_evaluation(V)
+    all_ids = torch.arange(V, dtype=torch.int32, device=dev)
+    esteps = (V + eval_B - 1) // eval_B
+
+    def eval_a():
+        meter_a.reset()
+        ev.evaluate_videos(cache, eval_B, eval_F, meter=meter_a, order=all_ids)
+
+    def eval_b():
+        meter_b.reset()
+        for a in range(0, V, eval_B):
+            clips = cache.sample_clips(all_ids[a:a + eval_B], eval_F)
+            scores, _, _ = ev(clips)
+            meter_b.update(scores, lab(clips))
+
+    evals = _measure_routes({'a_evaluate_videos': eval_a, 'b_call_loop': eval_b}, esteps)
+    assert torch.equal(meter_a._scores[:V], meter_b._scores[:V])
+    fastest = min(('a_epoch_call', 'b_lean_loop', 'c_deploy_loop'), key=lambda k: train[k]['wall_us_per_step'])
+    a, b = train['a_epoch_call'], train['b_lean_loop']
+    return {'workload': '{}: frozen clip epoch from a resident {} frame cache, {} steps of {} clips x {} frames over {} '
+                        'videos x {} frames ({}x{}x{}), K={}, {}, temporal attention, three routes alternating in one '
+                        'process, medians of five epochs'.format(which, 'FP8 E4M3' if fp8 else 'bf16', steps, B, F, V,
+                                                                  NF, H, H, C, K, loss),
+            'steps_per_epoch': steps, 'train': train, 'fastest_train_route_by_wall': fastest,
+            'epoch_call_minus_lean_loop_us': round(a['wall_us_per_step'] - b['wall_us_per_step'], 2),
+            'epoch_call_beats_lean_loop_by_more_than_its_spread':
+                bool(b['wall_us_per_step'] - a['wall_us_per_step'] > b['wall_spread_us']),
+            'eval_shape': '{} videos x {} frames per step, {} steps'.format(eval_B, eval_F, esteps), 'eval': evals,
             'fastest_eval_route_by_wall': min(evals, key=lambda k: evals[k]['wall_us_per_step']),
             'clamped_ids': int(cache.status)}
 
@@ -1751,7 +1923,7 @@ def main():
                                                          'cached002_fp8', 'cached002_bf16', 'cached_perclass_bf16',
                                                          'epoch002_fp8',
                                                          'epoch002_bf16', 'explain002', 'map393'] +
-                    sorted(EVAL_CLIPS) + sorted(RANK_WORKLOADS) + sorted(CACHED_CLIPS))
+                    sorted(EVAL_CLIPS) + sorted(RANK_WORKLOADS) + sorted(CACHED_CLIPS) + sorted(CLIP_EPOCHS))
     ap.add_argument('--clips', type=int, default=8, help='video_*: clips per batch')
     ap.add_argument('--frames', type=int, default=4, help='video_*: frames per clip')
     ap.add_argument('--only', default=None, choices=['clip_one_call', 'module_path', 'flat_one_call',
@@ -1809,6 +1981,9 @@ def main():
         return
     if args.workload in CACHED_CLIPS:
         print(json.dumps(run_cached_clips(cof, dev, args, args.workload)))
+        return
+    if args.workload in CLIP_EPOCHS:
+        print(json.dumps(run_clip_epoch(cof, dev, args, args.workload)))
         return
     if args.workload.startswith('frozen'):
         print(json.dumps(run_frozen(cof, dev, args, args.workload)))
