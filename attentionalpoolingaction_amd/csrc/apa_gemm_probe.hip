@@ -100,6 +100,14 @@ int apa_probe_m1_colsum(const ProbeColsum* c, void* stream) {
   return apa::m1_colsum(to_colsum(*c), static_cast<hipStream_t>(stream));
 }
 
+// ... with the scalar sum of block 0 as well: dba[0] = sum of pdba[0 .. nblk) (ProbeColsum keeps its layout)
+int apa_probe_m1_colsum_dba(const ProbeColsum* c, const float* pdba, float* dba, void* stream) {
+  if (!c) { apa::set_error("apa_probe_m1_colsum_dba: null"); return APA_ERR_INVALID_ARG; }
+  apa::ColsumArgs a = to_colsum(*c);
+  a.pdba = pdba; a.dba = dba;
+  return apa::m1_colsum(a, static_cast<hipStream_t>(stream));
+}
+
 int apa_probe_sgemm_small(const float* A, int64_t a_si, int64_t a_sk, const float* B, int64_t b_sk, int64_t b_sj,
                           float* D, int64_t ldd, int m, int n, int kdim, int splits, const float* u, const float* v,
                           float* ws, void* stream) {

@@ -219,6 +219,8 @@ constexpr unsigned APA_IFLAG_NO_DX = 1u << 26;          // M == 1, Xatt != X: dX
                                                         // pooling share A/P . dz . mask/keep in its own product's epilogue
 constexpr unsigned APA_IFLAG_FINALIZE_LAUNCH = 1u << 27;   // M == 1 forward: m1_finalize_fwd_kernel stays a launch of its
                                                            // own where the logits kernel could merge the partials itself
+constexpr unsigned APA_IFLAG_FOLD_TILE16 = 1u << 28;   // M == 1 folded forward: the 16-image geometry at any shape (read from
+                                                       // g_m1_iflags only: the probe library's tests)
 
 struct M1Xent {
   const int64_t* labels = nullptr;

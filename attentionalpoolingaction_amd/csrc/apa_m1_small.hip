@@ -72,14 +72,21 @@ __global__ __launch_bounds__(256) void m1_logits_xent_kernel(
   constexpr int EPT = NV4 == 4 ? 2 : 1;
   __shared__ float row[NV4 * 128];
   const int n = blockIdx.x, tid = threadIdx.x;
-  const size_t stride = (size_t)N * K;
-  const float* prow = part + (size_t)n * K;
+  // A partial is addressed as the one scalar base `part` plus a 32-bit byte offset per lane, u N K 4 + (n K + j) 4
+  // (nchunks N K 4 < 2^32: m1_logits_xent_supported): as 64-bit scalar address pairs per copy the 64 addresses spilled
+  // SGPRs and put a scalar wait between the bt loads and the partials' loads.
+  const uint32_t strideb = (uint32_t)N * (uint32_t)K * 4u;
+  uint32_t offb[EPT];
+#pragma unroll
+  for (int e = 0; e < EPT; ++e) offb[e] = ((uint32_t)n * (uint32_t)K + (uint32_t)min(tid + 256 * e, K - 1)) * 4u;
   // pstat (the folded route): abar[n] is formed here, by every wave alike, and stored for the backward pass.  Its
   // load goes out with bt and the partials, one batch; the sum and the store wait behind them.
   float a_s = 0.f;
   if (pstat) a_s = m1_abar_wave_load(pstat, n, S, tid & 63);
   else a_s = abar[n];                        // (the finalize kernel's abar: in the same batch)
-  const int lab = EVAL ? 0 : (int)labels[n];
+  // (int)labels[n] as its low dword alone: the unused high half of a 64-bit scalar load is a register the compiler
+  // reuses at once, behind a wait for the load
+  const int lab = EVAL ? 0 : reinterpret_cast<const int*>(labels)[2 * (size_t)n];
   float btv[EPT], acc[EPT];
 #pragma unroll
   for (int e = 0; e < EPT; ++e) {
@@ -88,11 +95,18 @@ __global__ __launch_bounds__(256) void m1_logits_xent_kernel(
   }
   for (int c = 0; c < nchunks; c += 32) {   // one round trip for up to 32 partials
     float v[EPT][32];
+    uint32_t o[EPT][32];
+#pragma unroll
+    for (int e = 0; e < EPT; ++e)
+#pragma unroll
+      for (int u = 0; u < 32; ++u) o[e][u] = (uint32_t)min(c + u, nchunks - 1) * strideb + offb[e];
+    __builtin_amdgcn_sched_barrier(0);   // (left to itself the compiler waits for the first 16 before it requests the rest)
 #pragma unroll
     for (int e = 0; e < EPT; ++e)
 #pragma unroll
       for (int u = 0; u < 32; ++u)
-        v[e][u] = prow[(size_t)min(c + u, nchunks - 1) * stride + min(tid + 256 * e, K - 1)];
+        v[e][u] = *reinterpret_cast<const float*>(reinterpret_cast<const char*>(part) + o[e][u]);
+    __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
     for (int e = 0; e < EPT; ++e)
 #pragma unroll
@@ -450,19 +464,27 @@ __global__ __launch_bounds__(256) void m1_logits2_kernel(const float* __restrict
 //               dropped at the store; blocks gx == 0 store z for the backward pass.
 //   B fragment, MFMA sequence per output, the (w0 + w1) + (w2 + w3) sum through LDS and part[cx][n][k]: as L1v2, so
 //               the partial logits are bit-identical too.
+// ROWS = 16, the full-tile geometry: grid (C/64, ceil(ceil(K/16)/7), ceil(N/16)), block = 64 channels x 7 k-tiles x 16
+//   images.  Lane (r, kq) loads image n0 + r, no tile row is a repeat: 28 MFMAs and 28 Wt dwords per lane where the
+//   8-image form at KG = 13 issues 52 of each for the same outputs, 64 + 28 KB per block against 32 + 52 KB, the same
+//   256 blocks at the benchmark shape.  Only who loads and stores what differs: every z and every partial logit is the
+//   same chain.  launch_logits2_fold states when it is taken.  Headline step, six alternated runs each: 46.05 ->
+//   45.14 us (20 steps), 44.94 -> 43.87 us (200 steps); profiles/chain_bodies_summary.md.
 // --------------------------------------------------------------------------------------------
-template <int KG>
+template <int KG, int ROWS>   // ROWS: images per block, 8 (half tiles) or 16 (full tiles)
 __global__ __launch_bounds__(256) void m1_logits2_fold_kernel(const float* __restrict__ pacc,
                                                               const float* __restrict__ Wt,
                                                               float* __restrict__ zsave,
                                                               float* __restrict__ part, int N, int C, int K,
                                                               int S, int P) {
-  extern __shared__ __attribute__((aligned(16))) float red[];   // [4 waves][KG tiles][8 rows][16]
+  static_assert(ROWS == 8 || ROWS == 16, "half or full MFMA tiles");
+  constexpr int RT = ROWS * 16;   // outputs per k-tile
+  extern __shared__ __attribute__((aligned(16))) float red[];   // [4 waves][KG tiles][ROWS rows][16]
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const int r = lane & 15, kq = lane >> 4;
-  const int cx = blockIdx.x, gx = blockIdx.y, n0 = blockIdx.z * 8;
+  const int cx = blockIdx.x, gx = blockIdx.y, n0 = blockIdx.z * ROWS;
   const int ktiles = (K + 15) >> 4;
-  const int n = min(n0 + (r & 7), N - 1);                              // rows >= N: discarded at the stores
+  const int n = min(n0 + (r & (ROWS - 1)), N - 1);                     // rows >= N: discarded at the stores
   const int cw = cx * 64 + wave * 16;
   const float invP = 1.0f / (float)P;
   int colj[KG];
@@ -490,7 +512,7 @@ __global__ __launch_bounds__(256) void m1_logits2_fold_kernel(const float* __res
       z.z = fmaf(first[u].z, invP, z.z); z.w = fmaf(first[u].w, invP, z.w);
     }
   }
-  if (gx == 0 && r < 8 && n0 + r < N) *reinterpret_cast<float4*>(zsave + (size_t)(n0 + r) * C + cw + 4 * kq) = z;
+  if (gx == 0 && r < ROWS && n0 + r < N) *reinterpret_cast<float4*>(zsave + (size_t)(n0 + r) * C + cw + 4 * kq) = z;
   f32x4 acc[KG];
 #pragma unroll
   for (int j = 0; j < KG; ++j) acc[j] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -500,21 +522,22 @@ __global__ __launch_bounds__(256) void m1_logits2_fold_kernel(const float* __res
 #pragma unroll
     for (int j = 0; j < KG; ++j) acc[j] = mfma16(av[e], bw[j][e], acc[j]);
   }
-  // ---- fixed-order sum of the 4 waves' 16-channel shares (tile rows 0..7: lanes kq < 2), one store per element ----
-  if (kq < 2) {
+  // ---- fixed-order sum of the 4 waves' 16-channel shares (tile rows 0..ROWS-1: lanes kq < ROWS / 4), one store per
+  // element ----
+  if (kq < ROWS / 4) {
 #pragma unroll
     for (int j = 0; j < KG; ++j)
 #pragma unroll
-      for (int reg = 0; reg < 4; ++reg) red[(wave * KG + j) * 128 + (kq * 4 + reg) * 16 + r] = acc[j][reg];
+      for (int reg = 0; reg < 4; ++reg) red[(wave * KG + j) * RT + (kq * 4 + reg) * 16 + r] = acc[j][reg];
   }
   __syncthreads();
   float* out = part + (size_t)cx * N * K;
 #pragma unroll
-  for (int m = 0; m < (KG + 1) / 2; ++m) {
-    const int i = m * 256 + tid;                 // (tile j, row, column) of the block's KG x 8 x 16 outputs
-    if (i < KG * 128) {
-      const float sm = (red[i] + red[KG * 128 + i]) + (red[2 * KG * 128 + i] + red[3 * KG * 128 + i]);
-      const int j = i >> 7, row = (i >> 4) & 7, colr = i & 15;
+  for (int m = 0; m < (KG * RT + 255) / 256; ++m) {
+    const int i = m * 256 + tid;                 // (tile j, row, column) of the block's KG x ROWS x 16 outputs
+    if (i < KG * RT) {
+      const float sm = (red[i] + red[KG * RT + i]) + (red[2 * KG * RT + i] + red[3 * KG * RT + i]);
+      const int j = i / RT, row = (i >> 4) & (ROWS - 1), colr = i & 15;
       const int nn = n0 + row, kt = gx * KG + j, k = kt * 16 + colr;
       if (nn < N && kt < ktiles && k < K) out[(size_t)nn * K + k] = sm;
     }
@@ -914,6 +937,10 @@ __global__ __launch_bounds__(256) void m1_bwd_head_tiles_kernel(
 // B4: dwa[c] = sum_b pdwa[b][c] (fixed order), dba = sum_b pdba[b].
 // grid = ceil(C/32) blocks of 1024 threads: 32 row groups x 32 columns, 128-byte row segments.
 // The last kernel of the backward call: optionally advances the HBM dropout counter.
+// (Narrower blocks on more CUs -- 16 or 8 columns x 32 row groups, the same sums -- were measured at nblk = 512,
+// C = 2048 and made the step slower, + 0.4 and + 1.8 us: a 64- or 32-byte row segment per block has two or four CUs
+// fetch every 128-byte line.  Non-temporal dWt stores in m1_bwd_head_kernel, in front of the streaming pass: - 0.2 to
+// - 0.35 us, inside the run-to-run spread, not kept.  profiles/chain_bodies_summary.md.)
 // --------------------------------------------------------------------------------------------
 // What is summed and where the sums go: ColsumArgs (apa_colsum.h).  A struct passed by value is not preloaded, so the
 // fields the first batch of loads is addressed with travel in front of it as scalars (and the grid size, a hidden
@@ -954,8 +981,8 @@ static int launch_logits2(const float* z, const float* Wt, float* part_ws, int N
   return APA_OK;
 }
 
-// L1v2f: two k-tile groups per 64-channel chunk and 8-image group while an instance covers half the k-tiles
-// (K <= 416), more groups of 13 beyond
+// L1v2f, the 8-image form: two k-tile groups per 64-channel chunk and 8-image group while an instance covers half the
+// k-tiles (K <= 416), more groups of 13 beyond; the 16-image form: groups of 7 k-tiles
 bool m1_logits2_fold_supported(int N, int C, int S) {
   return C % 64 == 0 && S >= 1 && S <= 16 && N >= 1 && N < 128;   // N >= 128: the nsub = 4 form keeps its finalize
 }
@@ -965,10 +992,25 @@ static int launch_logits2_fold(const M1Fold& f, const float* Wt, float* zsave, f
   const int ktiles = (K + 15) / 16, half = (ktiles + 1) / 2;
   const int kg = half <= 1 ? 1 : (half <= 2 ? 2 : (half <= 4 ? 4 : (half <= 7 ? 7 : 13)));
   if (M1Trace* t = m1_trace()) t->logits_nsub = 1;
+  // The geometry: full tiles (16 images x 7 k-tiles) where they put at least as many blocks on the chip as the
+  // 8-image form or fill its 256 CUs anyway, and the second half of a tile is not all repeats (N > 8); else the
+  // 8-image form, which covers the chip better at small N and small K.  APA_IFLAG_FOLD_TILE16 (the probe library's
+  // g_m1_iflags only) takes the full tiles at any shape.
+  const int blocks8 = (C / 64) * ((ktiles + kg - 1) / kg) * ((N + 7) / 8);
+  const int blocks16 = (C / 64) * ((ktiles + 6) / 7) * ((N + 15) / 16);
+  const bool tile16 = (g_m1_iflags & APA_IFLAG_FOLD_TILE16) || (N > 8 && (blocks16 >= blocks8 || blocks16 >= 256));
+  if (tile16) {
+    dim3 grid(C / 64, (ktiles + 6) / 7, (N + 15) / 16);
+    const size_t shm = (size_t)4 * 7 * 256 * sizeof(float);   // 28 KB
+    hipLaunchKernelGGL((m1_logits2_fold_kernel<7, 16>), grid, dim3(256), shm, st, f.pacc, Wt, zsave, part_ws, N, C, K,
+                       f.S, f.P);
+    APA_LAUNCH_CHECK("m1_logits2_fold_kernel");
+    return APA_OK;
+  }
   dim3 grid(C / 64, (ktiles + kg - 1) / kg, (N + 7) / 8);
   const size_t shm = (size_t)4 * kg * 128 * sizeof(float);   // 26 KB at KG = 13
-#define APA_LF(KG)                                                                                          \
-  hipLaunchKernelGGL((m1_logits2_fold_kernel<KG>), grid, dim3(256), shm, st, f.pacc, Wt, zsave, part_ws, N, \
+#define APA_LF(KG)                                                                                             \
+  hipLaunchKernelGGL((m1_logits2_fold_kernel<KG, 8>), grid, dim3(256), shm, st, f.pacc, Wt, zsave, part_ws, N, \
                      C, K, f.S, f.P)
   if (kg == 1) APA_LF(1);
   else if (kg == 2) APA_LF(2);
@@ -1003,7 +1045,9 @@ int m1_logits2_partials(float* z, const float* Wt, float* part_ws, int N, int C,
 bool m1_bwd_head_supported(int N, int C, int K);
 // L1v2 + L2x (fused train step): partial logits, then reduce + softmax cross-entropy per image
 bool m1_logits_xent_supported(int N, int C, int K, bool eval) {
+  // the reducer addresses the partial copies with 32-bit byte offsets
   return m1_logits2_supported(C, K) && N >= 1 && K >= 4 && K <= 512 &&
+         m1_logits2_ws_bytes(N, C, K) / logits2_nsub(N, C) < ((size_t)1 << 32) &&
          (eval || m1_bwd_head_supported(N, C, K));   // training: the head kernel finishes loss[0]
 }
 
