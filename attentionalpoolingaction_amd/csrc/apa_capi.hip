@@ -3,6 +3,7 @@
 #include <stdarg.h>
 #include <stdio.h>
 
+#include "../../include/apa_pose_cache.h"
 #include "apa_internal.h"
 #include "../../include/apa_clip_epoch.h"
 
@@ -750,7 +751,11 @@ extern "C" int apa_attn_head_train_step_multilabel(const apa_multilabel* ml, con
 // backward rows pass, the pooling pass's dX share in the dX product's epilogue) sum in other orders than the per-op
 // kernels -- att moves by 2.5e-7, logits 4.4e-7, dWa 9.4e-7, dX by a bf16 ulp; the bf16 operand copies in io (W1_bf16,
 // W2T_bf16) are not read there.  A sigmoid loss still rides in the logits reducer inside head_step.
-static int pose_attn_step(const char* fn, const apa_pose_attn_step_io* io, PoolCall d, StepLoss L, int J) {
+// fc (apa_pose_cache.h: the cached step, pose_cache_check passed): io->X is a T-image cache.  The launches that read X
+// -- the Ppre product, both pooling passes, the dW1 product -- follow the index; everything else has the batch shape
+static const int64_t* cached_labels(PoolCall* d, const apa_feature_cache* fc, const int64_t* labels);
+static int pose_attn_step(const char* fn, const apa_pose_attn_step_io* io, PoolCall d, StepLoss L, int J,
+                          const apa_feature_cache* fc = nullptr) {
   if (!io) {
     set_error("%s: null io", fn);
     return APA_ERR_INVALID_ARG;
@@ -779,6 +784,10 @@ static int pose_attn_step(const char* fn, const apa_pose_attn_step_io* io, PoolC
   const int N = d.N, P = d.P, C = d.C, Cp = d.Ca, K = d.K, dtype = d.dtype;
   d.ws = s.ws_pool; d.ws_bytes = s.ws_pool_bytes;
   L.labels = s.labels; L.wt = s.action_wt; L.grad_scale = s.grad_scale; L.loss = s.loss_action; L.G = s.G;
+  if (fc) {   // (labels_cached: the [N] copy lives where the class-agnostic cached step keeps it)
+    d.fc = fc; d.fc_pose = true;
+    L.labels = cached_labels(&d, fc, s.labels);
+  }
   size_t pool_bytes = 0;   // everything the loss would refuse, the clip's defects among it, before the first launch
   if ((rc = head_step_check(fn, d, L, s.logits, &pool_bytes)) != APA_OK) return rc;
   const M1Fwd f{s.X, s.Ppre, s.Wa, s.ba, s.Wt, s.bt, s.logits, s.att, s.zsave, s.abar};
@@ -791,14 +800,17 @@ static int pose_attn_step(const char* fn, const apa_pose_attn_step_io* io, PoolC
   // rank-1, dZ (x) Wa, added to the dX the pooling pass wrote, on the workspace the forward half prepared
   PoseCall pc = pose_call(fn, N, P, C, Cp, J, dtype, s.ws_pose, s.ws_pose_bytes, d.st);
   pc.ws_name = "pose workspace";
+  if (fc) pc.rmap = GemmRowMap{fc->index, fc->cache_images, P};
   const PoseFwd pf = {s.X, s.W1, s.b1, s.W2, s.b2, s.Ppre, s.Pl};
   const PoseBwd pb = {s.X, s.W1, s.W2, s.Ppre, s.dPl, nullptr, s.dZ, s.Wa, s.dX, s.dW1, s.db1, s.dW2, s.db2, true, true,
                       frozen};
   const bool fast = !L.clips && !L.ml && pose_step_fast_ok(pc, pf, pb) && m1_supported(C, Cp, dtype, false) &&
                     m1_small_route_ok(C, K, s.G, s.Wt, s.zsave);
   if (!fast) {
-    rc = apa_pose_head_fwd(s.X, s.W1, s.b1, s.W2, s.b2, s.Ppre, s.Pl, s.ws_pose, s.ws_pose_bytes, N, P, C, Cp, J,
-                           dtype, d.st);
+    // (apa_pose_head_fwd and, below, apa_pose_head_bwd_rank1ext, as calls that carry the step's row map)
+    PoseCall pcf = pose_call("apa_pose_head_fwd", N, P, C, Cp, J, dtype, s.ws_pose, s.ws_pose_bytes, d.st);
+    pcf.rmap = pc.rmap;
+    rc = pose_head_fwd_run(pcf, pf);
     if (rc != APA_OK) return rc;
     rc = apa_pose_l2_loss_fwd_bwd(s.Pl, s.pose_labels, s.pose_valid, s.loss_pose, s.dPl, pose_ws_loss_scratch(pc),
                                   apa_pose_l2_workspace_bytes(N, P, J), N, P, J, s.pose_wt, s.grad_scale, d.st);
@@ -806,10 +818,9 @@ static int pose_attn_step(const char* fn, const apa_pose_attn_step_io* io, PoolC
     d.flags |= APA_FLAG_DXATT_RANK1;   // s.dZ receives dZ itself; apa_pose_head_bwd_rank1ext re-forms dXatt from it
     rc = head_step_run(d, L, f, b, pool_bytes);
     if (rc != APA_OK) return rc;
-    return apa_pose_head_bwd_rank1ext(s.X, s.W1, s.W2, s.Ppre, s.dPl, s.dZ, s.Wa, s.dX,
-                                      1 | APA_POSE_WS_FROM_FWD | (frozen ? APA_POSE_NO_DX : 0),
-                                      s.dW1, s.db1, s.dW2, s.db2, s.ws_pose, s.ws_pose_bytes, N, P, C, Cp, J, dtype,
-                                      d.st);
+    PoseCall pcb = pose_call("apa_pose_head_bwd", N, P, C, Cp, J, dtype, s.ws_pose, s.ws_pose_bytes, d.st);
+    pcb.rmap = pc.rmap;
+    return pose_head_bwd_run(pcb, pb);   // accumulate, workspace from the forward call, no dX on frozen features
   }
   PoseStepArgs a;
   // a caller-kept bf16 copy of W1 is an OPTIMISATION: apa_momentum_sgd_step_shadow accepts any 4-byte aligned
@@ -1556,9 +1567,11 @@ extern "C" size_t apa_pose_attn_eval_workspace_bytes(int N, int P, int C, int Cp
 }
 
 // clips_fn == nullptr: apa_pose_attn_eval_step; else the _clips entry point of that name with its clip and scores kind
+// fc (apa_pose_cache.h: the cached step, flat batches; cached_fn its name): as in pose_attn_step
 static int pose_attn_eval(const char* clips_fn, const apa_clip_pool* clip, int kind, const apa_pose_attn_eval_io* io,
-                          int N, int P, int C, int Cp, int J, int K, unsigned flags, int dtype, void* stream) {
-  const char* fn = clips_fn ? clips_fn : "apa_pose_attn_eval_step";
+                          int N, int P, int C, int Cp, int J, int K, unsigned flags, int dtype, void* stream,
+                          const apa_feature_cache* fc = nullptr, const char* cached_fn = nullptr) {
+  const char* fn = cached_fn ? cached_fn : clips_fn ? clips_fn : "apa_pose_attn_eval_step";
   if (!io) {
     set_error("%s: null io", fn);
     return APA_ERR_INVALID_ARG;
@@ -1603,6 +1616,7 @@ static int pose_attn_eval(const char* clips_fn, const apa_clip_pool* clip, int k
   const bool relu_att = (flags & APA_FLAG_RELU_ATT) && !(flags & APA_FLAG_SOFTMAX_ATT);
   PoseCall pc = pose_call(fn, N, P, C, Cp, J, dtype, w, cv.pose, stream);
   pc.ws_name = "pose workspace";
+  if (fc) pc.rmap = GemmRowMap{fc->index, fc->cache_images, P};
   PoseStepArgs a;
   a.W1_bf16 = s.W1_bf16; a.wa = s.Wa; a.ba = s.ba; a.att = s.att; a.relu_att = relu_att;
   PoseEvalOut o = {0, nullptr, false};
@@ -1613,9 +1627,14 @@ static int pose_attn_eval(const char* clips_fn, const apa_clip_pool* clip, int k
   const void* xatt = o.ppre ? o.ppre : static_cast<const void*>(zpart);
   PoolCall d = pool_call({N, P, C, Cp, K, 1, dtype}, flags, 1.0f, 0, 0, w + cv.pose, cv.pool, stream);
   if (o.att_ready) d.flags |= APA_IFLAG_ATT_READY;
+  const int64_t* labels = s.labels;
+  if (fc) {
+    d.fc = fc; d.fc_pose = true;
+    labels = cached_labels(&d, fc, s.labels);
+  }
   const M1Fwd f{s.X, xatt, s.Wa, s.ba, s.Wt, s.bt, s.logits, s.att, s.zsave, s.abar};
-  return clips_fn ? attn_head_eval_clips(fn, clip, kind, d, f, s.labels, s.loss, s.probs, s.pred)
-                  : attn_head_eval(d, f, s.labels, s.loss, s.probs, s.pred);
+  return clips_fn ? attn_head_eval_clips(fn, clip, kind, d, f, labels, s.loss, s.probs, s.pred)
+                  : attn_head_eval(d, f, labels, s.loss, s.probs, s.pred);
 }
 
 extern "C" int apa_pose_attn_eval_step(const apa_pose_attn_eval_io* io, int N, int P, int C, int Cp, int J, int K,
@@ -1628,4 +1647,84 @@ extern "C" int apa_pose_attn_eval_step_clips(const apa_clip_pool* clip, int scor
                                              unsigned flags, int dtype, void* stream) {
   return pose_attn_eval("apa_pose_attn_eval_step_clips", clip, scores_kind, io, N, P, C, Cp, J, K, flags, dtype,
                         stream);
+}
+
+// ---- the cfg 003 steps from a resident feature cache (apa_pose_cache.h) ------------------------------------------------
+// What the two cached steps refuse about their descriptor, the cache and the forms it cannot have, each by name and
+// before anything is queued, in the order the header promises; what remains is the plain step's.  The admission of the
+// two products that read X through the row map is gemm_rowmap_check's (pose_rowmap_check describes them).
+static int pose_cache_check(const char* fn, const apa_feature_cache* fc, const void* X, const void* dX, bool train,
+                            unsigned flags, int N, int P, int C, int Cp, int J, int dtype, const float* W1,
+                            const void* W1_bf16, void* ws_pose, size_t ws_pose_bytes, void* stream) {
+  if (!fc || !fc->index) {
+    set_error("%s: null apa_feature_cache / index pointer", fn);
+    return APA_ERR_INVALID_ARG;
+  }
+  if (reinterpret_cast<uintptr_t>(fc->index) & 3) {
+    set_error("%s: apa_feature_cache.index must be 4-byte aligned", fn);
+    return APA_ERR_INVALID_ARG;
+  }
+  if (fc->cache_images < 1) {
+    set_error("%s: apa_feature_cache.cache_images=%d: a cache holds at least one image", fn, fc->cache_images);
+    return APA_ERR_INVALID_ARG;
+  }
+  if (dX) {
+    set_error("%s: a feature cache has no gradient: io->dX must be NULL", fn);
+    return APA_ERR_INVALID_ARG;
+  }
+  if (train && !(flags & APA_FLAG_FROZEN_INPUT)) {
+    set_error("%s: a feature cache is frozen: a training step needs APA_FLAG_FROZEN_INPUT", fn);
+    return APA_ERR_INVALID_ARG;
+  }
+  if (dtype != APA_DTYPE_BF16) {
+    set_error("%s: dtype %d: the pose-regularised head is served from a bf16 cache (fp32 and FP8 caches: gather a "
+              "batch and run the plain step)", fn, dtype);
+    return APA_ERR_UNSUPPORTED;
+  }
+  if ((reinterpret_cast<uintptr_t>(X) & 15) || C % 8 != 0) {
+    set_error("%s: the cache must be 16-byte aligned with C a multiple of 8 (C=%d): its rows are fetched by 16-byte "
+              "vectors and LDS-DMA", fn, C);
+    return APA_ERR_UNSUPPORTED;
+  }
+  if (N > 0 && P > 0 && C > 0 && Cp > 0 && J > 0) {
+    PoseCall pc = pose_call(fn, N, P, C, Cp, J, dtype, ws_pose, ws_pose_bytes, stream);
+    pc.rmap = GemmRowMap{fc->index, fc->cache_images, P};
+    const int rc = pose_rowmap_check(pc, X, W1, W1_bf16, train);
+    if (rc != APA_OK) return rc;
+  }
+  if (flags & APA_FLAG_SOFTMAX_ATT) {
+    set_error("%s: a feature cache does not serve APA_FLAG_SOFTMAX_ATT: the gathered pooling passes have no softmax "
+              "instance (the backward pass forms dZ under the softmax)", fn);
+    return APA_ERR_UNSUPPORTED;
+  }
+  return APA_OK;
+}
+
+extern "C" int apa_pose_attn_train_step_cached(const apa_feature_cache* cache, const apa_pose_attn_step_io* io, int N,
+                                               int P, int C, int Cp, int J, int K, unsigned flags, float keep_prob,
+                                               uint64_t seed, uint64_t offset, int dtype, void* stream) {
+  const char* fn = "apa_pose_attn_train_step_cached";
+  if (!io) {
+    set_error("%s: null io", fn);
+    return APA_ERR_INVALID_ARG;
+  }
+  const int rc = pose_cache_check(fn, cache, io->X, io->dX, true, flags, N, P, C, Cp, J, dtype, io->W1, io->W1_bf16,
+                                  io->ws_pose, io->ws_pose_bytes, stream);
+  if (rc != APA_OK) return rc;
+  return pose_attn_step(fn, io, pool_call({N, P, C, Cp, K, 1, dtype}, flags, keep_prob, seed, offset, nullptr, 0, stream),
+                        StepLoss{}, J, cache);
+}
+
+extern "C" int apa_pose_attn_eval_step_cached(const apa_feature_cache* cache, const apa_pose_attn_eval_io* io, int N,
+                                              int P, int C, int Cp, int J, int K, unsigned flags, int dtype,
+                                              void* stream) {
+  const char* fn = "apa_pose_attn_eval_step_cached";
+  if (!io) {
+    set_error("%s: null io", fn);
+    return APA_ERR_INVALID_ARG;
+  }
+  const int rc = pose_cache_check(fn, cache, io->X, nullptr, false, flags, N, P, C, Cp, J, dtype, io->W1, io->W1_bf16,
+                                  io->ws, io->ws_bytes, stream);
+  if (rc != APA_OK) return rc;
+  return pose_attn_eval(nullptr, nullptr, APA_SCORES_SOFTMAX, io, N, P, C, Cp, J, K, flags, dtype, stream, cache, fn);
 }

@@ -242,8 +242,9 @@ __host__ __device__ __forceinline__ void m1_pix_range(int s, int P, int S, int& 
 // as their last argument, the plain instances an empty M1NoGather in its place, and fetch the feature rows -- on the
 // FP8 arm also the scale -- of image m1_src_image(n, g); every other address, and the dropout hash's element index,
 // keep the batch position n.  The price is one dependent scalar read in front of the first feature load, paid by the
-// gathered instances alone.  Which instances exist is m1_pool_form's to say (apa_internal.h): a gathered call is fused
-// and stores no dX, so GATHER meets neither FUSED = false, RIN nor NODX = false.
+// gathered instances alone.  Which instances exist is m1_pool_form's to say (apa_internal.h): a gathered call stores no
+// dX and applies neither relu to its input nor a softmax, so GATHER meets neither RIN, SM nor NODX = false; it is fused,
+// or (the cfg 003 cached steps) carries a batch-shaped attention map, FUSED = false.
 __device__ __forceinline__ int m1_src_image(int n, const M1NoGather&) { return n; }
 __device__ __forceinline__ int m1_src_image(int n, const M1Gather& g) { return min(max(g.index[n], 0), g.T - 1); }
 // forward pass, `one`: true in exactly one thread per image

@@ -28,4 +28,14 @@ struct PcGather {
 };
 template <bool GATHER> using PcGatherArg = std::conditional_t<GATHER, PcGather, M1NoGather>;
 
+// ... and of operand A of a dense product (GemmDesc::rmap, the MAP instances of apa_gemm_bf16.hip): the same row rule,
+// row r of A is fetched from row clamp(index[r / P], 0, T - 1) * P + r % P of the buffer behind A.  Clamped silently:
+// the status word and the labels are the forward pooling pass's (m1_gather_note), once per step.  index == nullptr: A
+// is a plain batch
+struct GemmRowMap {
+  const int32_t* index = nullptr;   // [rows of A / P]
+  int T = 0;                        // images behind A
+  int P = 0;                        // rows per image
+};
+
 }  // namespace apa

@@ -24,7 +24,7 @@ namespace apa {
 
 typedef short bf16x8 __attribute__((ext_vector_type(8)));
 
-constexpr int GM = 128, GN = 128, GK = 32;
+constexpr int GM = 128, GN = 128, GK = GEMM_GK;
 constexpr int LDS_BF16 = 40;  // elements per LDS row (bf16)
 constexpr int LDS_F32 = 33;   // elements per LDS row (fp32)
 
@@ -415,10 +415,8 @@ static int gemm_launch_t(const GemmDesc& d, hipStream_t st) {
   constexpr int VLA = Elem<TA>::VL, VLB = Elem<TB>::VL;
   p.a_vec = aligned16(d.A) && (d.lda % VLA == 0);
   p.b_vec = aligned16(d.B) && (d.ldb % VLB == 0);
-  int splits = d.splits < 1 ? 1 : d.splits;
-  int kps = (d.K + splits - 1) / splits;
-  kps = (kps + GK - 1) / GK * GK;
-  splits = (d.K + kps - 1) / kps;
+  int splits, kps;
+  gemm_split(d.K, d.splits, GK, &splits, &kps);
   p.k_per_split = kps;
   p.partial = splits > 1 ? d.ws : nullptr;
   if (splits > 1 && !d.ws) {
@@ -436,9 +434,8 @@ static int gemm_launch_t(const GemmDesc& d, hipStream_t st) {
   bool twin = false;
   if (gemm_bf16_eligible(d)) {
     // 64-deep K tiles: re-derive the split so every chunk is a multiple of 64
-    int kps64 = (d.K + splits - 1) / splits;
-    kps64 = (kps64 + 63) / 64 * 64;
-    splits = (d.K + kps64 - 1) / kps64;
+    int kps64;
+    gemm_split(d.K, splits, 64, &splits, &kps64);
     if (d.twin && !gemm_bf16_twin_ok(d, splits, kps64)) {   // one after the other
       GemmDesc a = d; a.twin = nullptr;
       int rc = gemm_launch_t<TA, TB, TC, A_KC, B_KC>(a, st);
@@ -523,6 +520,10 @@ static int gemm_launch_layout(const GemmDesc& d, hipStream_t st) {
 
 int gemm_launch(const GemmDesc& d, hipStream_t st) {
   if (d.M <= 0 || d.N <= 0 || d.K <= 0) return APA_OK;
+  if (d.rmap.index) {   // a mapped A is served by the MAP instances of the bf16 path alone; nothing is queued otherwise
+    const int rc = gemm_rowmap_check(d, "gemm");
+    if (rc != APA_OK) return rc;
+  }
   const int key = d.ta * 4 + d.tb * 2 + d.tc;  // dtype codes: 0 f32, 1 bf16
   switch (key) {
     case 0: return gemm_launch_layout<float, float, float>(d, st);

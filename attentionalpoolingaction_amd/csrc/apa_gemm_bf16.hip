@@ -31,6 +31,8 @@ typedef short bf16x8 __attribute__((ext_vector_type(8)));
 typedef short bf16x4 __attribute__((ext_vector_type(4)));
 
 constexpr int TM = 128, TN = 128, TK = 64;
+// which kernel gemm_bf16_launch picks for an eligible product (bf16_kind)
+enum { KIND_GENERIC_ID = 0, KIND_WIDE_ID, KIND_RING_ID, KIND_GLDS64_ID, KIND_GLDS128_ID };
 constexpr int LD_KC = TK + 8;    // [row][k] image, 144-byte rows
 constexpr int LD_KM = TM + 8;    // [k][row] image, 272-byte rows
 constexpr int OP_ELEMS = TM * LD_KC;   // 9216 >= TK * LD_KM = 8704
@@ -66,6 +68,25 @@ struct Stage {
       } else {
         const int k = k0 + (vi >> 4), row = min(r0 + (vi & 15) * 8, rlim - 8);
         const uint4 x = load8(base + (long)min(k, klim - 1) * ld + row);
+        v[i] = k < klim ? x : make_uint4(0u, 0u, 0u, 0u);
+      }
+    }
+  }
+  // the mapped form (GemmDesc::rmap): srow[i] is the row of `base` behind this thread's i-th vector -- !KM: the source
+  // of row min(r0 + (vi >> 3), rlim - 1), fixed over the k tiles; KM: the source of k row k0 + (vi >> 4), which the
+  // caller has clamped to the split's last row where it lies past klim (zeroed here as in load)
+  __device__ __forceinline__ void load_rows(const T* __restrict__ base, long ld, const long (&srow)[4], int r0, int rlim,
+                                            int k0, int klim, int tid) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int vi = tid + i * 256;
+      if (!KM) {
+        const int k = k0 + (vi & 7) * 8;
+        const uint4 x = load8(base + srow[i] * ld + min(k, klim - 8));
+        v[i] = k < klim ? x : make_uint4(0u, 0u, 0u, 0u);
+      } else {
+        const int k = k0 + (vi >> 4), row = min(r0 + (vi & 15) * 8, rlim - 8);
+        const uint4 x = load8(base + srow[i] * ld + row);
         v[i] = k < klim ? x : make_uint4(0u, 0u, 0u, 0u);
       }
     }
@@ -125,6 +146,42 @@ struct FastParams {
   int nt_out;    // GemmDesc::stream_out: non-temporal bf16 vector stores of C
   // GemmDesc::zp_*: the contracted epilogue of gemm_bf16_ring_kernel<.., ZP> (C is not stored)
   const float* zp_w; float* zp_out;
+  // GemmDesc::rmap (the MAP instances alone read these; behind everything else, so that no plain instance's argument
+  // offsets move): index [rm_N], images behind A, rows per image
+  const int32_t* rm_index; int rm_T, rm_P, rm_N;
+};
+// The row of the buffer behind A that holds batch row r (already clamped to the batch by the caller): one division,
+// one index read -- the prologue's, never the loop's
+__device__ __forceinline__ long rm_src_row(const FastParams& p, int r) {
+  const int n = r / p.rm_P, pix = r - n * p.rm_P;
+  return (long)min(max(p.rm_index[n], 0), p.rm_T - 1) * p.rm_P + pix;
+}
+// k-major mapped A: the contraction walks the batch rows, so a lane's S source rows change with every k tile.  It
+// carries (image, pixel) of each, advanced by TK per tile with a carry loop (TK may exceed P; the only divisions are
+// init's), and holds the index entry of the NEXT tile's rows, requested one tile ahead -- no feature load waits for an
+// index entry requested in its own iteration.  The DMA-staged kernels request it right BEHIND tile t's DMAs and drain
+// them (vmcnt(0)) before the barrier that hands tile t over, so the entry is home when tile t + 1's addresses are
+// formed.  The register-staged kernel requests tile t + 1's entries in FRONT of tile t's feature loads (walk_rows
+// resolves tile t's rows and moves on in one go) and consumes them an iteration later, behind the store of tile t's
+// registers to LDS, which has waited for everything issued before it
+template <int S> struct RowWalk {
+  int n[S], pix[S];
+  int32_t id[S];
+  __device__ __forceinline__ void init(const FastParams& p, int s, int r) { n[s] = r / p.rm_P; pix[s] = r - n[s] * p.rm_P; }
+  __device__ __forceinline__ void request(const FastParams& p) {   // (past the batch: the last image's entry, never used)
+#pragma unroll
+    for (int s = 0; s < S; ++s) id[s] = p.rm_index[min(n[s], p.rm_N - 1)];
+  }
+  __device__ __forceinline__ long src(const FastParams& p, int s) const {
+    return (long)min(max(id[s], 0), p.rm_T - 1) * p.rm_P + pix[s];
+  }
+  __device__ __forceinline__ void advance(const FastParams& p) {
+#pragma unroll
+    for (int s = 0; s < S; ++s) {
+      pix[s] += 64;
+      while (pix[s] >= p.rm_P) { pix[s] -= p.rm_P; ++n[s]; }
+    }
+  }
 };
 __device__ __forceinline__ void twin_select(FastParams& p) {
   if (blockIdx.y) {
@@ -321,7 +378,9 @@ __device__ __forceinline__ void epilogue(f32x4 (&acc)[4][4], const FastParams& p
   }
 }
 
-template <typename TA, typename TB, typename TC, bool A_KM, bool B_KM>
+// MAP (here and in the three DMA-staged kernels below): operand A is read through GemmDesc::rmap.  Only A's source
+// addresses differ from the plain instance; the clamp to the batch (min(r0 + row, rlim - 1)) is applied before the map
+template <typename TA, typename TB, typename TC, bool A_KM, bool B_KM, bool MAP = false>
 __global__ __launch_bounds__(256, 2) void gemm_bf16_kernel(FastParams p) {
   extern __shared__ __attribute__((aligned(16))) short smem[];   // [2 buffers][A image | B image]
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
@@ -343,8 +402,34 @@ __global__ __launch_bounds__(256, 2) void gemm_bf16_kernel(FastParams p) {
 #pragma unroll
     for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
 
+  // MAP: the source rows of this thread's four A vectors -- row-major A: resolved once, here; k-major A: walked
+  // (all of it dead in the plain instances)
+  long srow[4];
+  long slast = 0;            // k-major: the source of the split's last row (what rows past the split read)
+  RowWalk<4> wk;
+  auto walk_rows = [&](int k0) {   // srow of the k tile at k0 from the walk's state, then on to the next tile
+#pragma unroll
+    for (int i = 0; i < 4; ++i) srow[i] = k0 + (tid >> 4) + 16 * i < kend ? wk.src(p, i) : slast;
+    wk.advance(p);
+    wk.request(p);
+  };
+  if constexpr (MAP) {
+    if (nk > 0) {
+      if constexpr (!A_KM) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) srow[i] = rm_src_row(p, min(m0 + (tid >> 3) + 32 * i, p.M - 1));
+      } else {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) wk.init(p, i, kbeg + (tid >> 4) + 16 * i);
+        wk.request(p);
+        slast = rm_src_row(p, kend - 1);
+        walk_rows(kbeg);
+      }
+    }
+  }
   if (nk > 0) {
-    sa.load(A, p.lda, m0, p.M, kbeg, kend, tid);
+    if constexpr (MAP) sa.load_rows(A, p.lda, srow, m0, p.M, kbeg, kend, tid);
+    else sa.load(A, p.lda, m0, p.M, kbeg, kend, tid);
     sb.load(B, p.ldb, n0, p.N, kbeg, kend, tid);
     sa.store(smem, tid);
     sb.store(smem + OP_ELEMS, tid);
@@ -355,7 +440,12 @@ __global__ __launch_bounds__(256, 2) void gemm_bf16_kernel(FastParams p) {
     const short* b_img = a_img + OP_ELEMS;
     const bool more = t + 1 < nk;
     if (more) {   // next tile's global loads fly underneath this tile's MFMAs
-      sa.load(A, p.lda, m0, p.M, kbeg + (t + 1) * TK, kend, tid);
+      if constexpr (MAP) {
+        if constexpr (A_KM) walk_rows(kbeg + (t + 1) * TK);   // (its entries were requested an iteration ago: home)
+        sa.load_rows(A, p.lda, srow, m0, p.M, kbeg + (t + 1) * TK, kend, tid);
+      } else {
+        sa.load(A, p.lda, m0, p.M, kbeg + (t + 1) * TK, kend, tid);
+      }
       sb.load(B, p.ldb, n0, p.N, kbeg + (t + 1) * TK, kend, tid);
     }
 #pragma unroll
@@ -428,6 +518,13 @@ __device__ __forceinline__ long glds_src_offset(int g, int lane, long ld, int r0
   }
 }
 
+// ... of row-major A on a MAP instance: the lane's one source row, resolved here (the prologue) behind the same clamp
+__device__ __forceinline__ long glds_src_offset_map(const FastParams& p, int g, int lane, int r0) {
+  const int row = 8 * g + (lane >> 3);
+  const int chunk = (lane & 7) ^ ((row >> 1) & 7);
+  return rm_src_row(p, min(r0 + row, p.M - 1)) * p.lda + chunk * 8;
+}
+
 template <bool KM>
 __device__ __forceinline__ bf16x8 fragment_sw(const short* img, int rbase, int ks, int lane) {
   const int l16 = lane & 15, kb = lane >> 4;
@@ -448,7 +545,7 @@ __device__ __forceinline__ bf16x8 fragment_sw(const short* img, int rbase, int k
   }
 }
 
-template <typename TC, bool A_KM, bool B_KM, bool MID = false>
+template <typename TC, bool A_KM, bool B_KM, bool MID = false, bool MAP = false>
 __global__ __launch_bounds__(256, 2) void gemm_bf16_glds_kernel(FastParams p) {
   extern __shared__ __attribute__((aligned(16))) short smem[];   // [2 buffers][A image | B image], + epilogue
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
@@ -462,14 +559,26 @@ __global__ __launch_bounds__(256, 2) void gemm_bf16_glds_kernel(FastParams p) {
   // per-lane DMA source pointers: wave w issues LDS KiB-blocks g = 4w .. 4w+3 of both images
   const bf16_t* asrc[4];
   const bf16_t* bsrc[4];
+  // MAP, k-major A: the lane's column offset inside a k row (fixed: the swizzle repeats every tile) and the walk over
+  // the four k rows it fetches per tile (RowWalk); dead elsewhere
+  long acol[4];
+  RowWalk<4> wk;
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
     const int g = wave * 4 + j;
-    asrc[j] = static_cast<const bf16_t*>(p.A) + glds_src_offset<A_KM>(g, lane, p.lda, m0, p.M) +
-              (A_KM ? (long)kbeg * p.lda : (long)kbeg);
+    if constexpr (MAP && A_KM) {
+      acol[j] = glds_src_offset<true>(g, lane, 0, m0, p.M);
+      wk.init(p, j, kbeg + 4 * g + (lane >> 4));
+    } else if constexpr (MAP) {
+      asrc[j] = static_cast<const bf16_t*>(p.A) + glds_src_offset_map(p, g, lane, m0) + (long)kbeg;
+    } else {
+      asrc[j] = static_cast<const bf16_t*>(p.A) + glds_src_offset<A_KM>(g, lane, p.lda, m0, p.M) +
+                (A_KM ? (long)kbeg * p.lda : (long)kbeg);
+    }
     bsrc[j] = static_cast<const bf16_t*>(p.B) + glds_src_offset<B_KM>(g, lane, p.ldb, n0, p.N) +
               (B_KM ? (long)kbeg * p.ldb : (long)kbeg);
   }
+  if constexpr (MAP && A_KM) wk.request(p);   // tile 0's entries: the one dependent read, in front of the first DMA
   const long a_step = A_KM ? (long)TK * p.lda : (long)TK;
   const long b_step = B_KM ? (long)TK * p.ldb : (long)TK;
   typedef __attribute__((address_space(1))) const void* gptr;
@@ -477,12 +586,20 @@ __global__ __launch_bounds__(256, 2) void gemm_bf16_glds_kernel(FastParams p) {
   auto issue = [&](int buf) {
     short* a_img = smem + buf * 2 * IMG;
     short* b_img = a_img + IMG;
+    if constexpr (MAP && A_KM) {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) asrc[j] = static_cast<const bf16_t*>(p.A) + wk.src(p, j) * p.lda + acol[j];
+    }
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       __builtin_amdgcn_global_load_lds((gptr)asrc[j], (lptr)(a_img + (wave * 4 + j) * 512), 16, 0, 0);
       __builtin_amdgcn_global_load_lds((gptr)bsrc[j], (lptr)(b_img + (wave * 4 + j) * 512), 16, 0, 0);
       asrc[j] += a_step;
       bsrc[j] += b_step;
+    }
+    if constexpr (MAP && A_KM) {   // the next tile's rows; their entries are requested behind this tile's DMAs
+      wk.advance(p);
+      wk.request(p);
     }
   };
 
@@ -574,7 +691,7 @@ __device__ __forceinline__ bf16x8 fragment_b64(const short* img, int rbase, int 
   return bf16x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
 }
 
-template <typename TC, bool A_KM, bool B_KM>
+template <typename TC, bool A_KM, bool B_KM, bool MAP = false>
 __global__ __launch_bounds__(256, 3) void gemm_bf16_glds64_kernel(FastParams p) {
   extern __shared__ __attribute__((aligned(16))) short smem[];   // [2 stages][A 16 KiB | B 8 KiB]
   twin_select(p);
@@ -589,10 +706,21 @@ __global__ __launch_bounds__(256, 3) void gemm_bf16_glds64_kernel(FastParams p) 
 
   const bf16_t* asrc[4];
   const bf16_t* bsrc[2];
+  long acol[4];      // MAP, k-major A: as in gemm_bf16_glds_kernel
+  RowWalk<4> wk;
 #pragma unroll
-  for (int j = 0; j < 4; ++j)
-    asrc[j] = static_cast<const bf16_t*>(p.A) + glds_src_offset<A_KM>(wave * 4 + j, lane, p.lda, m0, p.M) +
-              (A_KM ? (long)kbeg * p.lda : (long)kbeg);
+  for (int j = 0; j < 4; ++j) {
+    if constexpr (MAP && A_KM) {
+      acol[j] = glds_src_offset<true>(wave * 4 + j, lane, 0, m0, p.M);
+      wk.init(p, j, kbeg + 4 * (wave * 4 + j) + (lane >> 4));
+    } else if constexpr (MAP) {
+      asrc[j] = static_cast<const bf16_t*>(p.A) + glds_src_offset_map(p, wave * 4 + j, lane, m0) + (long)kbeg;
+    } else {
+      asrc[j] = static_cast<const bf16_t*>(p.A) + glds_src_offset<A_KM>(wave * 4 + j, lane, p.lda, m0, p.M) +
+                (A_KM ? (long)kbeg * p.lda : (long)kbeg);
+    }
+  }
+  if constexpr (MAP && A_KM) wk.request(p);
 #pragma unroll
   for (int j = 0; j < 2; ++j)
     bsrc[j] = static_cast<const bf16_t*>(p.B) + glds_src_offset_b64<B_KM>(wave * 2 + j, lane, p.ldb, n0, p.N) +
@@ -604,6 +732,10 @@ __global__ __launch_bounds__(256, 3) void gemm_bf16_glds64_kernel(FastParams p) 
   auto issue = [&](int buf) {
     short* a_img = smem + buf * STAGE;
     short* b_img = a_img + IMG;
+    if constexpr (MAP && A_KM) {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) asrc[j] = static_cast<const bf16_t*>(p.A) + wk.src(p, j) * p.lda + acol[j];
+    }
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       __builtin_amdgcn_global_load_lds((gptr)asrc[j], (lptr)(a_img + (wave * 4 + j) * 512), 16, 0, 0);
@@ -613,6 +745,10 @@ __global__ __launch_bounds__(256, 3) void gemm_bf16_glds64_kernel(FastParams p) 
     for (int j = 0; j < 2; ++j) {
       __builtin_amdgcn_global_load_lds((gptr)bsrc[j], (lptr)(b_img + (wave * 2 + j) * 512), 16, 0, 0);
       bsrc[j] += b_step;
+    }
+    if constexpr (MAP && A_KM) {
+      wk.advance(p);
+      wk.request(p);
     }
   };
 
@@ -741,7 +877,7 @@ __device__ __forceinline__ void ring_wait_barrier() {
   asm volatile("s_barrier" ::: "memory");
 }
 
-template <typename TC, bool B_KM, int MT, bool ZP = false>
+template <typename TC, bool B_KM, int MT, bool ZP = false, bool MAP = false>
 __global__ __launch_bounds__(512, 1) void gemm_bf16_ring_kernel(FastParams p) {
   typedef RingCfg<MT> R;
   twin_select(p);
@@ -764,7 +900,10 @@ __global__ __launch_bounds__(512, 1) void gemm_bf16_ring_kernel(FastParams p) {
   for (int j = 0; j < NMINE; ++j) {
     const int b = wave + 8 * j;
     if (b < R::TMR / 8) {
-      src[j] = static_cast<const bf16_t*>(p.A) + glds_src_offset<false>(b, lane, p.lda, m0, p.M);
+      // (MAP: the lane's source row is resolved here, once; the stage's DMA instructions are the plain instance's, so
+      // the counted vmcnt waits below count what they counted)
+      if constexpr (MAP) src[j] = static_cast<const bf16_t*>(p.A) + glds_src_offset_map(p, b, lane, m0);
+      else src[j] = static_cast<const bf16_t*>(p.A) + glds_src_offset<false>(b, lane, p.lda, m0, p.M);
       dst[j] = (uint32_t)b * 1024u;
       step[j] = TK;
     } else {
@@ -938,17 +1077,17 @@ __global__ __launch_bounds__(512, 1) void gemm_bf16_ring_kernel(FastParams p) {
   }
 }
 
-template <typename TC, bool B_KM, int MT, bool ZP = false>
+template <typename TC, bool B_KM, int MT, bool ZP = false, bool MAP = false>
 int launch_ring(const FastParams& p, hipStream_t st) {
   typedef RingCfg<MT> R;
   static thread_local PerDevice<bool> attr_dev; bool& attr_set = attr_dev.here();
   if (!attr_set) {
-    APA_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_bf16_ring_kernel<TC, B_KM, MT, ZP>),
+    APA_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_bf16_ring_kernel<TC, B_KM, MT, ZP, MAP>),
                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)R::LDS_BYTES));
     attr_set = true;
   }
   const int tiles = ((p.M + R::TMR - 1) / R::TMR) * ((p.N + TN - 1) / TN);
-  hipLaunchKernelGGL((gemm_bf16_ring_kernel<TC, B_KM, MT, ZP>), dim3(tiles, p.A2 ? 2 : 1), dim3(512), R::LDS_BYTES, st, p);
+  hipLaunchKernelGGL((gemm_bf16_ring_kernel<TC, B_KM, MT, ZP, MAP>), dim3(tiles, p.A2 ? 2 : 1), dim3(512), R::LDS_BYTES, st, p);
   APA_LAUNCH_CHECK("gemm_bf16_ring_kernel");
   return APA_OK;
 }
@@ -1297,22 +1436,22 @@ static int ring_pick_mt(int M, int N, int cus) {
   return 0;
 }
 
-template <typename TC, bool B_KM, bool ZP = false>
+template <typename TC, bool B_KM, bool ZP = false, bool MAP = false>
 int launch_ring_mt(const FastParams& p, int mt, hipStream_t st) {
   switch (mt) {
-    case 4: return launch_ring<TC, B_KM, 4, ZP>(p, st);
-    case 5: return launch_ring<TC, B_KM, 5, ZP>(p, st);
-    case 6: return launch_ring<TC, B_KM, 6, ZP>(p, st);
-    case 7: return launch_ring<TC, B_KM, 7, ZP>(p, st);
-    default: return launch_ring<TC, B_KM, 8, ZP>(p, st);
+    case 4: return launch_ring<TC, B_KM, 4, ZP, MAP>(p, st);
+    case 5: return launch_ring<TC, B_KM, 5, ZP, MAP>(p, st);
+    case 6: return launch_ring<TC, B_KM, 6, ZP, MAP>(p, st);
+    case 7: return launch_ring<TC, B_KM, 7, ZP, MAP>(p, st);
+    default: return launch_ring<TC, B_KM, 8, ZP, MAP>(p, st);
   }
 }
 
-template <typename TC, bool A_KM, bool B_KM>
+template <typename TC, bool A_KM, bool B_KM, bool MAP = false>
 int launch_glds64(const FastParams& p, int splits, hipStream_t st) {
   const size_t shm = (size_t)2 * (IMG + IMGB64) * sizeof(short);   // 49 152 B
   const int tiles = ((p.M + TM - 1) / TM) * ((p.N + 63) / 64);
-  hipLaunchKernelGGL((gemm_bf16_glds64_kernel<TC, A_KM, B_KM>), dim3(tiles, p.A2 ? 2 : 1, splits), dim3(256), shm, st, p);
+  hipLaunchKernelGGL((gemm_bf16_glds64_kernel<TC, A_KM, B_KM, MAP>), dim3(tiles, p.A2 ? 2 : 1, splits), dim3(256), shm, st, p);
   APA_LAUNCH_CHECK("gemm_bf16_glds64_kernel");
   return APA_OK;
 }
@@ -1327,17 +1466,17 @@ int launch_glds64_layout(const FastParams& p, bool a_km, bool b_km, int splits, 
   return launch_glds64<TC, false, false>(p, splits, st);
 }
 
-template <typename TC, bool A_KM, bool B_KM>
+template <typename TC, bool A_KM, bool B_KM, bool MAP = false>
 int launch_glds(const FastParams& p, int splits, hipStream_t st) {
   const size_t shm = (size_t)2 * 2 * OP_ELEMS * sizeof(short);   // epilogue stage needs 67 584 B
   static thread_local PerDevice<bool> attr_dev; bool& attr_set = attr_dev.here();
   if (!attr_set) {
-    APA_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_bf16_glds_kernel<TC, A_KM, B_KM>),
+    APA_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_bf16_glds_kernel<TC, A_KM, B_KM, false, MAP>),
                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
     attr_set = true;
   }
   const int tiles = ((p.M + TM - 1) / TM) * ((p.N + TN - 1) / TN);
-  hipLaunchKernelGGL((gemm_bf16_glds_kernel<TC, A_KM, B_KM>), dim3(tiles, 1, splits), dim3(256), shm, st, p);
+  hipLaunchKernelGGL((gemm_bf16_glds_kernel<TC, A_KM, B_KM, false, MAP>), dim3(tiles, 1, splits), dim3(256), shm, st, p);
   APA_LAUNCH_CHECK("gemm_bf16_glds_kernel");
   return APA_OK;
 }
@@ -1352,18 +1491,18 @@ int launch_glds_layout(const FastParams& p, bool a_km, bool b_km, int splits, hi
   return launch_glds<TC, false, false>(p, splits, st);
 }
 
-template <typename TA, typename TB, typename TC, bool A_KM, bool B_KM>
+template <typename TA, typename TB, typename TC, bool A_KM, bool B_KM, bool MAP = false>
 int launch(const FastParams& p, int splits, hipStream_t st) {
   const size_t shm = (size_t)2 * 2 * OP_ELEMS * sizeof(short);   // 73 728 B
   static thread_local PerDevice<bool> attr_dev; bool& attr_set = attr_dev.here();
   if (!attr_set) {
     APA_HIP_CHECK(hipFuncSetAttribute(
-        reinterpret_cast<const void*>(gemm_bf16_kernel<TA, TB, TC, A_KM, B_KM>),
+        reinterpret_cast<const void*>(gemm_bf16_kernel<TA, TB, TC, A_KM, B_KM, MAP>),
         hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
     attr_set = true;
   }
   const int tiles = ((p.M + TM - 1) / TM) * ((p.N + TN - 1) / TN);
-  hipLaunchKernelGGL((gemm_bf16_kernel<TA, TB, TC, A_KM, B_KM>), dim3(tiles, 1, splits), dim3(256), shm,
+  hipLaunchKernelGGL((gemm_bf16_kernel<TA, TB, TC, A_KM, B_KM, MAP>), dim3(tiles, 1, splits), dim3(256), shm,
                      st, p);
   APA_LAUNCH_CHECK("gemm_bf16_kernel");
   return APA_OK;
@@ -1377,6 +1516,34 @@ int launch_layout(const FastParams& p, bool a_km, bool b_km, int splits, hipStre
   }
   if (b_km) return launch<bf16_t, TB, TC, false, true>(p, splits, st);
   return launch<bf16_t, TB, TC, false, false>(p, splits, st);
+}
+
+// The MAP instances (GemmDesc::rmap), in the forms the two products that read a feature cache use -- B k-major (a
+// weight or a gradient map, [K][N]) everywhere, and k-contiguous as well in the ring kernel; C bf16 or fp32; the
+// register-staged kernel with a bf16 or an fp32 B.  gemm_rowmap_check admits nothing else.
+template <typename TC>
+int launch_mapped(const FastParams& p, const GemmDesc& d, int kind, int mt, int splits, hipStream_t st) {
+  const bool a_km = !d.a_kc;
+  switch (kind) {
+    case KIND_RING_ID:
+      if (d.zp_out) {
+        if constexpr (sizeof(TC) == 2) return launch_ring_mt<bf16_t, true, true, true>(p, mt, st);
+        break;
+      }
+      return d.b_kc ? launch_ring_mt<TC, false, false, true>(p, mt, st) : launch_ring_mt<TC, true, false, true>(p, mt, st);
+    case KIND_GLDS64_ID:
+      return a_km ? launch_glds64<TC, true, true, true>(p, splits, st) : launch_glds64<TC, false, true, true>(p, splits, st);
+    case KIND_GLDS128_ID:
+      return a_km ? launch_glds<TC, true, true, true>(p, splits, st) : launch_glds<TC, false, true, true>(p, splits, st);
+    case KIND_GENERIC_ID:
+      if (d.tb == 1)
+        return a_km ? launch<bf16_t, bf16_t, TC, true, true, true>(p, splits, st)
+                    : launch<bf16_t, bf16_t, TC, false, true, true>(p, splits, st);
+      return a_km ? launch<bf16_t, float, TC, true, true, true>(p, splits, st)
+                  : launch<bf16_t, float, TC, false, true, true>(p, splits, st);
+  }
+  set_error("gemm_bf16: a mapped product reached a kernel without a MAP instance (internal)");
+  return APA_ERR_UNSUPPORTED;
 }
 }  // namespace
 
@@ -1394,6 +1561,7 @@ int gemm_bf16_mid_dropout(const void* A, long lda, const void* B, long ldb, void
   p.k_per_split = K; p.partial = nullptr; p.Nout = N;
   p.A2 = nullptr; p.B2 = nullptr; p.C2 = nullptr; p.ldc2 = 0; p.bias2 = nullptr; p.partial2 = nullptr;
   p.Nout2 = 0; p.vec_epi2 = 0; p.nt_out = 0; p.zp_w = nullptr; p.zp_out = nullptr;
+  p.rm_index = nullptr; p.rm_T = 0; p.rm_P = 1; p.rm_N = 0;
   p.drop_c = 0; p.inv_keep = inv_keep; p.thresh = 0; p.seed = 0; p.offset = 0;
   p.offset_dev = nullptr;
   p.vec_epi = N % 8 == 0 && (reinterpret_cast<uintptr_t>(C) & 15) == 0 && (ldc * 2) % 16 == 0;
@@ -1451,7 +1619,8 @@ bool gemm_bf16_zp_serves(const GemmDesc& d) {
 }
 
 // which kernel gemm_bf16_launch picks for an eligible product
-enum { KIND_GENERIC = 0, KIND_WIDE, KIND_RING, KIND_GLDS64, KIND_GLDS128 };
+enum { KIND_GENERIC = KIND_GENERIC_ID, KIND_WIDE = KIND_WIDE_ID, KIND_RING = KIND_RING_ID, KIND_GLDS64 = KIND_GLDS64_ID,
+       KIND_GLDS128 = KIND_GLDS128_ID };
 static int bf16_kind(const GemmDesc& d, int splits, int k_per_split) {
   if (!(d.tb == 1 && k_per_split % TK == 0 && d.K % TK == 0)) return KIND_GENERIC;
   if (d.zp_out) return gemm_bf16_zp_serves(d) && splits == 1 ? KIND_RING : KIND_GENERIC;   // (refused below unless RING)
@@ -1471,6 +1640,29 @@ bool gemm_bf16_twin_ok(const GemmDesc& d, int splits, int k_per_split) {
   if (splits > 1 && (!d.ws || !t.ws || d.ws == t.ws)) return false;
   const int kind = bf16_kind(d, splits, k_per_split);
   return kind == KIND_RING || kind == KIND_GLDS64;
+}
+
+// GemmDesc::rmap: what the MAP instances serve (apa_internal.h).  The split is gemm_launch's own
+int gemm_rowmap_check(const GemmDesc& d, const char* what) {
+  const GemmRowMap& m = d.rmap;
+  const int rows = d.a_kc ? d.M : d.K;
+  const char* why = nullptr;
+  if (!m.index || m.T < 1 || m.P < 1 || rows < 1 || rows % m.P != 0) why = "a batch of whole images with an index and a cache of at least one image";
+  else if (d.ta != 1) why = "bf16 features (fp32 features take the fp32-unpacking kernels, which read a dense batch)";
+  else if (!gemm_bf16_eligible(d)) why = "a product of the bf16 MFMA path (16-byte addressable operand rows, whole 8-element vectors, no dropout on A)";
+  else if (d.twin || d.r1_row || d.mid_bits || d.drop_c) why = "a plain product (no twin, rank-1 term, mid-contraction mask or output dropout)";
+  else {
+    int splits, kps, kps64;
+    gemm_split(d.K, d.splits, GEMM_GK, &splits, &kps);
+    gemm_split(d.K, splits, 64, &splits, &kps64);
+    const int kind = bf16_kind(d, splits, kps64);
+    if (kind == KIND_WIDE) why = "a product the wide kernel does not take (it has no mapped instance)";
+    else if (d.b_kc && kind != KIND_RING) why = "B stored [K][N] wherever the ring kernel does not take the product";
+    else if (d.zp_out && (kind != KIND_RING || d.tc != 1)) why = "the ring kernel and a bf16 C for the contracted epilogue";
+  }
+  if (!why) return APA_OK;
+  set_error("%s: a feature cache behind operand A needs %s (M=%d N=%d K=%d P=%d)", what, why, d.M, d.N, d.K, m.P);
+  return APA_ERR_UNSUPPORTED;
 }
 
 static bool vec_epilogue_ok(const GemmDesc& d, int nout, const float* partial) {
@@ -1500,7 +1692,26 @@ int gemm_bf16_launch(const GemmDesc& d, int splits, int k_per_split, hipStream_t
   p.maskbits = nullptr;
   p.r1_row = nullptr; p.r1_col = nullptr; p.r1_bits = nullptr; p.r1_P = 1; p.r1_invP = 0.f; p.r1_inv_keep = 1.f;
   p.vec_epi = vec_epilogue_ok(d, p.Nout, p.partial);
+  p.rm_index = d.rmap.index; p.rm_T = d.rmap.T; p.rm_P = d.rmap.P > 0 ? d.rmap.P : 1;
+  p.rm_N = (d.a_kc ? d.M : d.K) / p.rm_P;
   const int kind = bf16_kind(d, splits, k_per_split);
+  if (d.rmap.index) {   // (gemm_launch asked gemm_rowmap_check first: a form with a MAP instance)
+    const int mt = kind == KIND_RING ? ring_pick_mt(d.M, d.N, gemm_cu_count()) : 0;
+    if (d.trace) {
+      d.trace->kind = kind == KIND_RING ? GEMM_KIND_RING : kind == KIND_GLDS64 ? GEMM_KIND_GLDS64
+                      : kind == KIND_GLDS128 ? GEMM_KIND_GLDS128 : GEMM_KIND_BF16;
+      d.trace->mt = mt;
+    }
+    if (d.zp_out) {
+      if (kind != KIND_RING) {
+        set_error("gemm_bf16: contracted epilogue requested for a product the ring kernel does not serve (internal)");
+        return APA_ERR_UNSUPPORTED;
+      }
+      p.zp_w = d.zp_w; p.zp_out = d.zp_out; p.vec_epi = 1; p.C = nullptr;
+    }
+    if (d.tc == 1) return launch_mapped<bf16_t>(p, d, kind, mt, splits, st);
+    return launch_mapped<float>(p, d, kind, mt, splits, st);
+  }
   if (d.twin) {
     if (!gemm_bf16_twin_ok(d, splits, k_per_split)) {
       set_error("gemm_bf16: twin products reached a kernel that serves one problem per launch (internal)");

@@ -95,6 +95,28 @@ int apa_probe_gemm_launch(const ProbeGemm* p, const ProbeGemm* twin, const Probe
   return rc;
 }
 
+// ... with operand A read through a row map (GemmDesc::rmap): A addresses a [T * P] row buffer, row r of the product's A
+// is its row clamp(index[r / P], 0, T - 1) * P + r % P
+int apa_probe_gemm_launch_rowmap(const ProbeGemm* p, const int32_t* index, int T, int P, ProbeTrace* trace) {
+  if (!p || p->version != PROBE_VERSION) {
+    apa::set_error("apa_probe_gemm_launch_rowmap: null descriptor or version mismatch");
+    return APA_ERR_INVALID_ARG;
+  }
+  apa::GemmTrace tr;
+  apa::GemmDesc d = to_desc(*p);
+  d.rmap.index = index; d.rmap.T = T; d.rmap.P = P;
+  d.trace = &tr;
+  int rc = APA_OK;
+  if (!index) {
+    apa::set_error("apa_probe_gemm_launch_rowmap: null index");
+    rc = APA_ERR_INVALID_ARG;
+  } else {
+    rc = apa::gemm_launch(d, nullptr);
+  }
+  to_trace(tr, trace);
+  return rc;
+}
+
 int apa_probe_m1_colsum(const ProbeColsum* c, void* stream) {
   if (!c) { apa::set_error("apa_probe_m1_colsum: null"); return APA_ERR_INVALID_ARG; }
   return apa::m1_colsum(to_colsum(*c), static_cast<hipStream_t>(stream));

@@ -191,10 +191,30 @@ struct GemmDesc {
   ColsumJob* tail = nullptr;
   // optional: where to record the kernel kind / split / reduce that served this product (null at product call sites)
   GemmTrace* trace = nullptr;
+  // A is a T-image feature cache read by image index (apa_gather.h: GemmRowMap): with a_kc the map applies to the M rows
+  // (Ppre = X . W1), else to the contraction rows (dW1 = X^T . dPpre).  B, C, bias, the partials, the dropout element
+  // index and every epilogue keep the batch position.  Served by the MAP instances of the bf16 kernels only
+  // (gemm_rowmap_check); the plain instances never see it
+  GemmRowMap rmap;
 };
 size_t gemm_ws_bytes(int M, int N, int splits);
 int gemm_pick_splits(int M, int N, int K);
+// the split gemm_launch runs for a requested one: whole GEMM_GK-deep k chunks (the k tile of apa_gemm.hip's kernels),
+// then -- on the bf16 path -- whole 64-deep ones
+constexpr int GEMM_GK = 32;
+inline void gemm_split(int K, int want, int unit, int* splits, int* k_per_split) {
+  int s = want < 1 ? 1 : want;
+  int kps = (K + s - 1) / s;
+  kps = (kps + unit - 1) / unit * unit;
+  *splits = (K + kps - 1) / kps;
+  *k_per_split = kps;
+}
 int gemm_launch(const GemmDesc& d, hipStream_t st);
+// The admission rule of a mapped product (d.rmap.index != nullptr), asked by gemm_launch first and by the entry points
+// before anything is queued: APA_OK, or APA_ERR_UNSUPPORTED with its sentence -- a product gemm_launch would send to
+// the fp32-unpacking kernels (fp32 features, anything gemm_bf16_eligible refuses), a form without a MAP instance, or a
+// batch that is not whole images.  `what`: the product's name in the sentence
+int gemm_rowmap_check(const GemmDesc& d, const char* what);
 // apa_gemm_bf16.hip: the fast bf16 path (128x128x64, transposing LDS reads for k-major operands)
 bool gemm_bf16_eligible(const GemmDesc& d);
 int gemm_bf16_launch(const GemmDesc& d, int splits, int k_per_split, hipStream_t st);
@@ -272,6 +292,9 @@ struct PoolCall : PoolDims {
   // index (labels_cached), which the forward pooling pass drops into the workspace (m1_gathered_labels)
   const apa_feature_cache* fc = nullptr;
   const int64_t* fc_labels = nullptr;
+  // set by the cfg 003 cached steps alone (apa_pose_cache.h): the gathered call may carry a separate attention input --
+  // batch-shaped, never read through the index (m1_call_fill: the pose form)
+  bool fc_pose = false;
 };
 
 struct M1Plan {
@@ -363,12 +386,12 @@ template <typename F> inline int m1_fused_train(bool fused, bool train, F&& go) 
   return train ? go(std::false_type{}, std::true_type{}) : go(std::false_type{}, std::false_type{});
 }
 // the FUSED x TRAIN x GATHER instances of a streaming kernel: go(F, TR, G), std::bool_constant tags.  A gathered call
-// is fused (m1_call_fill: the cache form), so it has the two instances over TRAIN; a plain call the four of
-// m1_fused_train.  The arms that exist for plain calls only (relu on the input, the dX stores) are the launcher's,
-// chosen under `if constexpr (!G)`: no gathered instance of them is ever named.
+// is fused (m1_call_fill: the cache form) or carries the cfg 003 steps' batch-shaped attention map (the pose form), so
+// it has the four instances of m1_fused_train as a plain call has.  The arms that exist for plain calls only (relu on
+// the input, softmax, the dX stores) are the launcher's, chosen under `if constexpr (!G)`: no gathered instance of them
+// is ever named.
 template <typename Fn> inline int m1_pool_form(const M1Call& c, Fn&& go) {
-  if (c.gather) return c.train ? go(std::true_type{}, std::true_type{}, std::true_type{})
-                               : go(std::true_type{}, std::false_type{}, std::true_type{});
+  if (c.gather) return m1_fused_train(c.fused, c.train, [&](auto F, auto TR) { return go(F, TR, std::true_type{}); });
   return m1_fused_train(c.fused, c.train, [&](auto F, auto TR) { return go(F, TR, std::false_type{}); });
 }
 // ... of an FP8 kernel, which has no FUSED parameter (m1_call_fill: an FP8 call is fused): go(TR, G)
@@ -486,6 +509,9 @@ struct PoseCall {
   const char* fn; const char* ws_name;
   int N, P, C, Cp, J, dtype; hipStream_t st;
   void* ws; size_t ws_bytes; PosePlan pl;   // pl: all zero while a dimension is non-positive (pose_check refuses those)
+  // the cfg 003 cached steps (apa_pose_cache.h): X is a T-image cache, the two products that read it (Ppre, dW1) take
+  // the row map.  index == nullptr on every other call
+  GemmRowMap rmap = {};
   char* at(size_t off) const { return static_cast<char*>(ws) + off; }
 };
 PoseCall pose_call(const char* fn, int N, int P, int C, int Cp, int J, int dtype, void* ws, size_t ws_bytes,
@@ -520,6 +546,13 @@ struct PoseStepArgs {
   float pool_inv_keep = 1.f;
 };
 bool pose_step_fast_ok(const PoseCall& c, const PoseFwd& f, const PoseBwd& b);
+// apa_pose_head_fwd / apa_pose_head_bwd[_rank1ext] on a call the caller built (the composed route of the cfg 003 steps:
+// c.rmap travels with it)
+int pose_head_fwd_run(const PoseCall& c, const PoseFwd& f);
+int pose_head_bwd_run(const PoseCall& c, const PoseBwd& b);
+// c.rmap set: would gemm_rowmap_check admit the two products that read X?  Launches nothing.  w1_shadow: the caller's
+// bf16 copy of W1, or null
+int pose_rowmap_check(const PoseCall& c, const void* X, const float* W1, const void* w1_shadow, bool backward);
 // What the pose head ran (filled on the host only, as M1Trace: the product never sets the pointer; the test-only
 // probe library does, around one call, and tests/test_pose_paths_gpu.py reads it back).  0 = not decided by this call.
 enum PoseW1 { POSE_W1_NONE = 0, POSE_W1_BF16_COPY, POSE_W1_F32, POSE_W1_REUSED, POSE_W1_SHADOW };

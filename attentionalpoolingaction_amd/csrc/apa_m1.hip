@@ -439,7 +439,13 @@ int m1_call_fill(M1Call& c, const PoolCall& d, const M1Fwd* f, const M1Bwd* b, c
     set_error("attn_pool M=1: APA_DTYPE_FP8_E4M3 serves the fused identity / relu head on frozen features only");
     return APA_ERR_UNSUPPORTED;
   }
-  if (c.gather && !cache_form) {
+  // ... and, from the cfg 003 cached steps alone (PoolCall::fc_pose, apa_pose_cache.h), the same head with a separate
+  // attention input: that input (pose_pre_logits, or the map already in `att`) has the batch shape and is never read
+  // through the index; the pooling passes run their (FUSED = false, GATHER) instances.  No softmax (the backward pass has
+  // no gathered softmax instance), no FP8
+  const bool pose_form = d.fc_pose && !c.fused && c.pool != M1_POOL_FP8 && c.act != M1_ACT_SOFTMAX && !c.relu_input &&
+                         !c.ext && !cat && !(b && !c.no_dx) && !(flags & APA_IFLAG_NO_DX);
+  if (c.gather && !cache_form && !pose_form) {
     set_error("attn_pool M=1: a feature cache serves the fused identity / relu head on frozen features only");
     return APA_ERR_UNSUPPORTED;
   }

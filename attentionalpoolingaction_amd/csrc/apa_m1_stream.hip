@@ -295,8 +295,8 @@ __device__ __forceinline__ void fwd_chunk(FwdState<T, VW, PIX, FUSED, TRAIN>& st
 // use, behind an HBM wait that is longer.
 // GATHER: the gathered instances (apa_device.h: M1Gather; the plain ones take an empty M1NoGather).  The window is full,
 // so the descriptor lies behind it: the index read is one scalar load in front of the first chunk's address, which the
-// plain instances do not have.  FUSED only, without RIN and (backward) NODX only: the launchers below name every
-// instance from m1_pool_form's tags.
+// plain instances do not have.  FUSED or not (the cfg 003 cached steps: att / dZ keep the batch position, only xim
+// moves), without RIN or SM and (backward) NODX only: the launchers below name every instance from m1_pool_form's tags.
 // SM: the softmax instances (fwd_chunk); forward: of the fused forms only, a map that is already final is pooled as it is.
 template <typename T, int VW, int PIX, bool FUSED, bool TRAIN, bool SM, bool RIN = false, bool GATHER = false>
 __global__ __launch_bounds__(256, 2) void m1s_pool_fwd_kernel(
@@ -684,8 +684,8 @@ static int launch_fwd_t(const M1Call& c, const M1Fwd& io) {
       return k;
     };
     auto kernel = arm(std::false_type{});
-    // softmax: plain fused maps only (m1_call_fill: pool_act is the identity on a map that is already final, and the
-    // cache form a gathered call has to be excludes softmax)
+    // softmax: plain fused maps only (m1_call_fill: pool_act is the identity on a map that is already final, and both
+    // forms a gathered call can have -- the cache form and the cfg 003 steps' pose form -- exclude softmax)
     if constexpr (f && !g) {
       if (c.pool_act == M1_ACT_SOFTMAX) kernel = arm(std::true_type{});
     }
@@ -723,7 +723,7 @@ static int launch_bwd_t(const M1Call& c, const M1Bwd& io) {
         return k;
       };
       // softmax: every plain form has its instance (dZ is formed in this pass, fused or not); a gathered call has none
-      // (m1_call_fill: the cache form excludes softmax)
+      // (m1_call_fill: the cache form and the pose form exclude softmax)
       if constexpr (!g) {
         if (c.act == M1_ACT_SOFTMAX) return act_arm(std::true_type{});
       }

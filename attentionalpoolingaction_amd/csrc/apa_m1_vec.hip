@@ -23,8 +23,9 @@ namespace apa {
 // Outputs: att (FUSED: id/relu -> final A, softmax -> raw Z, normalised in F2),
 //          pacc[blk][C] partial sum_p A*Xt, pstat[blk][4] = {m, l, asum, -}.
 // --------------------------------------------------------------------------------------------
-// GATHER: the gathered instances (apa_device.h: M1Gather; the plain ones take an empty M1NoGather), FUSED only -- the
-// launchers below name every instance from m1_pool_form's tags
+// GATHER: the gathered instances (apa_device.h: M1Gather; the plain ones take an empty M1NoGather), FUSED or -- the cfg
+// 003 cached steps, whose attention map has the batch shape -- not; the launchers below name every instance from
+// m1_pool_form's tags
 template <typename T, int VEC, bool FUSED, bool TRAIN, bool GATHER = false>
 __global__ __launch_bounds__(256) void m1_pool_fwd_kernel(
     const T* __restrict__ X, const float* __restrict__ Wa, const float* __restrict__ ba,
@@ -401,7 +402,7 @@ static int launch_bwd_t(const M1Call& c, const M1Bwd& io) {
   if (M1Trace* t = m1_trace()) { t->pool_bwd = M1_POOL_VEC; t->bwd_w = VEC; t->bwd_pix = 0; }
   m1_pool_form(c, [&](auto F, auto TR, auto G) {
     constexpr bool f = decltype(F)::value, t = decltype(TR)::value, g = decltype(G)::value;
-    // the arm without the dX stores (c.no_dx) is a gathered call's only one; a plain call has both
+    // the arm without the dX stores (c.no_dx) is a gathered call's only one, fused or not; a plain call has both
     auto kernel = m1_bwd_main_kernel<T, VEC, f, t, true, g>;
     if constexpr (!g) {
       if (!c.no_dx) kernel = m1_bwd_main_kernel<T, VEC, f, t, false>;

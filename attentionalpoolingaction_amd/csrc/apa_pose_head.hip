@@ -919,6 +919,7 @@ static GemmDesc pose_ppre_product(const PoseCall& c, const PoseFwd& f, const Pos
   g.B = w1.B; g.ldb = c.Cp; g.tb = w1.tb; g.b_kc = false;
   g.C = f.Ppre; g.ldc = c.Cp; g.tc = dt_code(c.dtype);
   g.M = (int)c.pl.R; g.N = c.Cp; g.K = c.C; g.bias = f.b1; g.act = 1;
+  g.rmap = c.rmap;   // (a cached step: X is the cache, the M rows go through the index)
   return g;
 }
 
@@ -946,16 +947,19 @@ extern "C" size_t apa_pose_head_workspace_bytes(int N, int P, int C, int Cp, int
   return pose_plan(N, P, C, Cp, J, dtype).total;
 }
 
+int apa::pose_head_fwd_run(const PoseCall& c, const PoseFwd& f) {
+  int rc = pose_check(c, f.X && f.W1 && f.b1 && f.W2 && f.b2 && f.Ppre && f.Pl);
+  if (rc != APA_OK) return rc;
+  rc = gemm_launch(pose_ppre_product(c, f, pose_w1_operand(c, f.W1, nullptr, false, &PoseTrace::w1_fwd)), c.st);
+  if (rc != APA_OK) return rc;
+  return pose_pl_product(c, f, nullptr);
+}
+
 extern "C" int apa_pose_head_fwd(const void* X, const float* W1, const float* b1, const float* W2,
                                  const float* b2, void* Ppre, float* Pl, void* ws, size_t ws_bytes,
                                  int N, int P, int C, int Cp, int J, int dtype, void* stream) {
-  const PoseCall c = pose_call("apa_pose_head_fwd", N, P, C, Cp, J, dtype, ws, ws_bytes, stream);
-  const PoseFwd f = {X, W1, b1, W2, b2, Ppre, Pl};
-  int rc = pose_check(c, X && W1 && b1 && W2 && b2 && Ppre && Pl);
-  if (rc != APA_OK) return rc;
-  rc = gemm_launch(pose_ppre_product(c, f, pose_w1_operand(c, W1, nullptr, false, &PoseTrace::w1_fwd)), c.st);
-  if (rc != APA_OK) return rc;
-  return pose_pl_product(c, f, nullptr);
+  return pose_head_fwd_run(pose_call("apa_pose_head_fwd", N, P, C, Cp, J, dtype, ws, ws_bytes, stream),
+                           PoseFwd{X, W1, b1, W2, b2, Ppre, Pl});
 }
 
 // split-K factor of dW1 = X^T . dPpre.  bf16 features take the 128 x 64 tile kernel, three blocks per CU: the
@@ -975,6 +979,21 @@ static int pose_dw1_splits(int C, int Cp, int R, int dtype) {
   return s;
 }
 
+// dW1[c,j] = sum_r X[r,c] dPpre[r,j]: the one description of the product, launched by pose_head_bwd_big and put to the
+// row map's admission rule by pose_rowmap_check before anything is queued (dW1: the caller's, or a stand-in there)
+static GemmDesc pose_dw1_product(const PoseCall& c, const void* X, float* dW1, ColsumJob* job) {
+  const int tdt = dt_code(c.dtype);
+  GemmDesc g;
+  g.A = X; g.lda = c.C; g.ta = tdt; g.a_kc = false;
+  g.B = c.at(c.pl.off_dppre); g.ldb = c.Cp; g.tb = tdt; g.b_kc = false;
+  g.C = dW1; g.ldc = c.Cp; g.tc = 0;
+  g.M = c.C; g.N = c.Cp; g.K = (int)c.pl.R;
+  g.splits = pose_dw1_splits(c.C, c.Cp, (int)c.pl.R, c.dtype); g.ws = reinterpret_cast<float*>(c.at(c.pl.off_gemm));
+  g.tail = job;
+  g.rmap = c.rmap;   // (a cached step: the contraction rows go through the index)
+  return g;
+}
+
 // The tail of every backward route, the two dense products: dW1 = X^T . dPpre and dX (+)= dPpre . W1^T (b.no_dx: the
 // first alone -- the second's only output is dX, and the pooling share its epilogue may carry goes with it).
 // job: a column sum nothing behind it reads (the MFMA rows pass's) -- it rides on the tail blocks of dW1's split-K
@@ -986,13 +1005,7 @@ static int pose_head_bwd_big(const PoseCall& c, const PoseBwd& b, const PoseStep
   PoseTrace* tr = pose_trace();
   int rc;
   {  // dW1[c,j] = sum_r X[r,c] dPpre[r,j]
-    GemmDesc g;
-    g.A = b.X; g.lda = C; g.ta = tdt; g.a_kc = false;
-    g.B = dPpre; g.ldb = Cp; g.tb = tdt; g.b_kc = false;
-    g.C = b.dW1; g.ldc = Cp; g.tc = 0;
-    g.M = C; g.N = Cp; g.K = R;
-    g.splits = pose_dw1_splits(C, Cp, R, c.dtype); g.ws = reinterpret_cast<float*>(c.at(c.pl.off_gemm));
-    g.tail = job;
+    GemmDesc g = pose_dw1_product(c, b.X, b.dW1, job);
     GemmTrace gt;
     if (tr) g.trace = &gt;
     rc = gemm_launch(g, c.st);
@@ -1307,6 +1320,23 @@ int pose_eval_fwd(const PoseCall& c, const PoseFwd& f, const PoseStepArgs& a, fl
 // dPpre (+ the rank-1 attention-branch gradient dZ (x) wa), dW2, db1, db2, dWa, dba in one pass + one column
 // sum that also finishes the pose loss and advances the dropout counter; then dW1 and dX (+)= dPpre.W1^T
 int pose_bwd_fused(const PoseCall& c, const PoseBwd& b, const PoseStepArgs& a) { return pose_head_bwd_impl(c, b, &a); }
+int pose_head_bwd_run(const PoseCall& c, const PoseBwd& b) { return pose_head_bwd_impl(c, b); }
+
+// The two products of a cached step that read X, as the routes above will describe them, put to gemm_rowmap_check:
+// nothing is launched (pose_w1_operand's decision is repeated without its conversion launch).  The operands that live
+// in the workspace are 256-byte aligned by the carve
+int pose_rowmap_check(const PoseCall& c, const void* X, const float* W1, const void* w1_shadow, bool backward) {
+  if (!c.rmap.index) return APA_OK;
+  const bool shadow = w1_shadow && c.dtype == APA_DTYPE_BF16 && (reinterpret_cast<uintptr_t>(w1_shadow) & 15) == 0;
+  const bool copy = c.dtype == APA_DTYPE_BF16 && ((size_t)c.C * c.Cp) % 8 == 0 && (reinterpret_cast<uintptr_t>(W1) & 15) == 0;
+  const PoseFwd f = {X, W1, nullptr, nullptr, nullptr, c.at(c.pl.off_dppre), nullptr};
+  GemmDesc g1 = pose_ppre_product(c, f, PoseW1Op{shadow ? w1_shadow : copy ? c.at(c.pl.off_w1b) : static_cast<const void*>(W1),
+                                                 shadow || copy ? 1 : 0});
+  int rc = gemm_rowmap_check(g1, c.fn);
+  if (rc != APA_OK || !backward) return rc;
+  // dW1 = X^T . dPpre as pose_head_bwd_big launches it (the workspace stands in for the caller's dW1; no tail job)
+  return gemm_rowmap_check(pose_dw1_product(c, X, reinterpret_cast<float*>(c.at(c.pl.off_gemm)), nullptr), c.fn);
+}
 
 }  // namespace apa
 

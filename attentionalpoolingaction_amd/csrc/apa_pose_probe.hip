@@ -4,6 +4,7 @@
 // libapa_hip.so).  Each wrapper runs one of the product's own extern "C" entry points with the same arguments while
 // the calling thread's PoseTrace pointer (apa_internal.h) is set, so the tests read back which kernel family, template
 // instance, block shape and reduce form served the call.  The trace is zeroed first; the pointer is cleared afterwards.
+#include "../../include/apa_pose_cache.h"
 #include "apa_internal.h"
 
 namespace {
@@ -15,6 +16,14 @@ struct TraceScope {
     apa::g_pose_trace = t;
   }
   ~TraceScope() { apa::g_pose_trace = nullptr; }
+};
+// the pooling half's trace beside it (the cached cfg 003 steps: both are compared with the plain step's)
+struct M1TraceScope {
+  explicit M1TraceScope(apa::M1Trace* t) {
+    if (t) *t = apa::M1Trace{};
+    apa::g_m1_trace = t;
+  }
+  ~M1TraceScope() { apa::g_m1_trace = nullptr; }
 };
 }  // namespace
 
@@ -68,6 +77,27 @@ int apa_probe_pose_attn_train_step(apa::PoseTrace* t, const apa_pose_attn_step_i
                                    int dtype, void* stream) {
   TraceScope s(t);
   return apa_pose_attn_train_step(io, N, P, C, Cp, J, K, flags, keep_prob, seed, offset, dtype, stream);
+}
+
+// The cfg 003 steps from a feature cache (apa_pose_cache.h) with both traces; cache == NULL: the plain step on io->X,
+// traced the same way -- what the cached call is compared with
+int apa_probe_pose_attn_train_step_cached(apa::PoseTrace* t, apa::M1Trace* m, const apa_feature_cache* cache,
+                                          const apa_pose_attn_step_io* io, int N, int P, int C, int Cp, int J, int K,
+                                          unsigned flags, float keep_prob, uint64_t seed, uint64_t offset, int dtype,
+                                          void* stream) {
+  TraceScope s(t);
+  M1TraceScope sm(m);
+  if (!cache) return apa_pose_attn_train_step(io, N, P, C, Cp, J, K, flags, keep_prob, seed, offset, dtype, stream);
+  return apa_pose_attn_train_step_cached(cache, io, N, P, C, Cp, J, K, flags, keep_prob, seed, offset, dtype, stream);
+}
+
+int apa_probe_pose_attn_eval_step_cached(apa::PoseTrace* t, apa::M1Trace* m, const apa_feature_cache* cache,
+                                         const apa_pose_attn_eval_io* io, int N, int P, int C, int Cp, int J, int K,
+                                         unsigned flags, int dtype, void* stream) {
+  TraceScope s(t);
+  M1TraceScope sm(m);
+  if (!cache) return apa_pose_attn_eval_step(io, N, P, C, Cp, J, K, flags, dtype, stream);
+  return apa_pose_attn_eval_step_cached(cache, io, N, P, C, Cp, J, K, flags, dtype, stream);
 }
 
 }  // extern "C"

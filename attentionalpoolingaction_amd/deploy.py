@@ -1054,6 +1054,7 @@ class FusedHeadStep:
         self._frozen_copies = []         # [(name, refresh)]: operand copies of frozen variables, built once
         self._frozen_seen = {}
         self._steps = {}                 # key (shape, dtype, preact) -> bound one-call step, most recent last
+        self._pose_rows = {}             # (PoseLabelTable id, N) -> (the table, pose labels [N,P*J], valid [N,J]): the buffers a cached cfg 003 step reads
         self._step_obj = None
         self._key = None
         self.w1_shadow = None
@@ -1122,13 +1123,27 @@ class FusedHeadStep:
         return ''
 
     @staticmethod
-    def cache_unsupported_reason(head, network_fn, batch) -> str:
+    def cache_unsupported_reason(head, network_fn, batch, multi_label: bool = False) -> str:
         """why `batch` -- an Fp8Features batch, a CachedBatch or a CachedClips -- cannot feed this head; '' when it can.
         An Fp8Features batch, and every head but the single-layer per-class one: `fp8_unsupported_reason`.  The per-class
         head (with identity, ReLU or spatial-softmax attention) is served from a bf16 cache on the fused per-class
-        route (K <= 64, C % 256 == 0, C <= 8192: cof.cached_per_class_served), flat or on clips."""
+        route (K <= 64, C % 256 == 0, C <= 8192: cof.cached_per_class_served), flat or on clips.  The cfg 003 form
+        (attention from pose_pre_logits, identity or ReLU) is served from a flat CachedBatch on a bf16 cache where
+        pose_cache.cached_pose_served holds (a training head also needs N * P to be a multiple of 8) -- under the softmax
+        cross-entropy only: `multi_label` (TRAIN.LOSS_FN_ACTION 'multi-label*', which the two callers pass) is refused by
+        name, the cached cfg 003 steps have no sigmoid form."""
         from .custom_ops import custom_ops_factory as cof
         why = FusedHeadStep.fp8_unsupported_reason(head, network_fn)
+        if why == 'attention from pose_pre_logits (the cfg 003 form)' and isinstance(batch, cof.CachedBatch) and \
+                not isinstance(batch, cof.CachedClips) and not batch.cache.fp8 and batch.dtype == torch.bfloat16:
+            from .custom_ops import pose_cache
+            plain = not (head.per_class or head.rank != 1 or head.with_pose_feat or head.softmax_att)
+            if plain and pose_cache.cached_pose_served(batch, head.pose_w1.shape[1], head.pose_w2.shape[1],
+                                                       head.num_classes, train=bool(head.is_training)):
+                if multi_label:
+                    return ('attention from pose_pre_logits (the cfg 003 form) under a sigmoid action loss (a cache '
+                            'feeds this head under the softmax cross-entropy only)')
+                return ''
         if why != 'per-class attention maps' or not isinstance(batch, cof.CachedBatch):
             return why
         if head.rank != 1:
@@ -1277,7 +1292,14 @@ class FusedHeadStep:
                 grad_scale=self.loss_scale)
         elif self.pose_form:
             shadow = self.w1_shadow if X.dtype == torch.bfloat16 else None
-            st = cof.PoseAttnTrainStep(
+            step_cls = cof.PoseAttnTrainStep
+            if self._cb:    # a bf16 feature cache read by index (custom_ops/pose_cache.py): flat softmax batches
+                from .custom_ops import pose_cache
+                if clip:
+                    raise ValueError('FusedHeadStep: a CachedBatch feeds the cfg 003 form under the softmax '
+                                     'cross-entropy on flat batches only')
+                step_cls = pose_cache.PoseAttnTrainStepCached
+            st = step_cls(
                 X, (p['pose_w1'], p['pose_b1'], p['pose_w2'], p['pose_b2'], p['att_weights'], p['att_biases'],
                     p['td_weights'], p['td_biases']), labels_action, labels_pose, pose_valid,
                 (dX, v['pose_w1'], v['pose_b1'], v['pose_w2'], v['pose_b2'], v['att_weights'], v['att_biases'],
@@ -1322,7 +1344,20 @@ class FusedHeadStep:
         head = self.head
         n, c = last_conv.shape[0], last_conv.shape[-1]
         X = last_conv.flat() if (self._fp8 or self._cb) else last_conv.detach().contiguous().view(n, -1, c)
-        if self.pose_form:
+        if self.pose_form and self._cb and hasattr(labels_pose, 'gather') and hasattr(labels_pose, 'new_batch'):
+            # a PoseLabelTable (custom_ops/pose_cache.py): the batch's rows land in buffers the bound step keeps reading
+            # (the entry holds the table itself: its id cannot be taken by another object while the entry lives)
+            table, tkey = labels_pose, (id(labels_pose), n)
+            held = self._pose_rows.pop(tkey, None)
+            if held is None or held[0] is not table:
+                held = (table,) + tuple(table.new_batch(n))
+            self._pose_rows[tkey] = held                     # most recent last
+            while len(self._pose_rows) > self.max_bound_steps:
+                self._pose_rows.pop(next(iter(self._pose_rows)))
+            labels_pose, pose_valid = held[1], held[2]
+            table.gather(X.index, labels_pose, pose_valid)   # (ids clamped as the kernels clamp them: three launches)
+            labels_pose = labels_pose.view(n, -1, table.J)
+        elif self.pose_form:
             J = self.params['pose_w2'].shape[1]
             labels_pose = labels_pose.contiguous().float().view(n, -1, J)
             if pose_valid.dtype == torch.bool:
@@ -1346,7 +1381,10 @@ class FusedHeadStep:
                tuple(p.data_ptr() for p in self.params.values())) + \
               ((id(X.cache), labels_action is None) if self._cb else ())
         st, cached = self._select(key, X, labels_action, labels_pose, pose_valid, frames)
-        if cached and self._cb:
+        if cached and self._cb and self.pose_form:
+            st.rebind(index=X.index, labels=labels_action, pose_labels=labels_pose, pose_valid=pose_valid,
+                      offset=head._step)
+        elif cached and self._cb:
             st.rebind(index=X.index, labels=labels_action, offset=head._step)
         elif cached and self.pose_form:
             st.rebind(X=X, labels=labels_action, pose_labels=labels_pose, pose_valid=pose_valid, offset=head._step)
@@ -1383,7 +1421,8 @@ class FusedHeadStep:
         self._fp8 = isinstance(images, Fp8Features)
         if self._fp8 or self._cb:   # a cached conv5 map: frozen by construction, no backbone in front of it
             what = 'an Fp8Features batch' if self._fp8 else 'a CachedBatch'
-            why = self.cache_unsupported_reason(self.head, self.network_fn, images)
+            why = self.cache_unsupported_reason(self.head, self.network_fn, images,
+                                                multi_label=self.cfg.TRAIN.LOSS_FN_ACTION != 'softmax-xentropy')
             if not why and not self.frozen_features:
                 why = 'frozen_features=False (a cache has no gradient: build the step with frozen_features=True)'
             if why:
@@ -1411,7 +1450,7 @@ class FusedHeadStep:
                              'step (frame pooling at rank > 1 runs through the per-op module)')
         if self._preact and not self.head.can_fuse_input_relu(last_conv.dtype):
             last_conv, self._preact = torch.relu(last_conv), False
-        if self.pose_form and (labels_pose is None or pose_valid is None):
+        if self.pose_form and (labels_pose is None or (pose_valid is None and not hasattr(labels_pose, 'new_batch'))):
             raise ValueError('FusedHeadStep: the cfg 003 form needs labels_pose [N,H,W,J] and pose_valid [N,J]')
         if self.cfg.TRAIN.LOSS_FN_ACTION != 'softmax-xentropy':     # multi-hot labels of any dtype -> float32, once
             labels_action = labels_action.to(torch.float32).contiguous()
@@ -1672,6 +1711,12 @@ class FusedHeadEval:
         # flat softmax batches: the defaults, i.e. the steps as they always were; clips and / or sigmoid scores: the
         # *_eval_step_clips entry points (frame pooling, scores and predictions inside the call)
         clips = dict(frames=frames, temporal=temporal, scores='sigmoid' if self.multi_label else 'softmax')
+        if self.pose_form and isinstance(X, cof.CachedBatch):   # a bf16 feature cache read by index: flat batches
+            from .custom_ops import pose_cache
+            return pose_cache.PoseAttnEvalStepCached(
+                X, (h.pose_w1.data, h.pose_b1.data, h.pose_w2.data, h.pose_b2.data, h.att_weights.data,
+                    h.att_biases.data, h.td_weights.data, h.td_biases.data), flags=flags,
+                want_pose_logits=want_pose_logits)
         if self.pose_form:
             return cof.PoseAttnEvalStep(
                 X, (h.pose_w1.data, h.pose_b1.data, h.pose_w2.data, h.pose_b2.data, h.att_weights.data,
@@ -1693,7 +1738,8 @@ class FusedHeadEval:
         cb = isinstance(images, CachedBatch)
         fp8 = isinstance(images, Fp8Features) or cb
         if fp8:             # a cached conv5 map: FP8, or a FeatureCache read by index (see FusedHeadStep.cache_unsupported_reason)
-            why = FusedHeadStep.cache_unsupported_reason(self.head, self.network_fn, images)
+            why = FusedHeadStep.cache_unsupported_reason(self.head, self.network_fn, images,
+                                                         multi_label=self.multi_label)
             if why:
                 raise ValueError('FusedHeadEval: %s is not served with %s' % (
                     'a CachedBatch' if cb else 'an Fp8Features batch', why))

@@ -40,6 +40,10 @@ headline stays the cfg 002 training workload); run this file directly for one wo
   cached_perclass_bf16
             the same three variants for the HMDB-51 per-class head (M = K = 51, bf16, weight images kept by the caller)
             from a resident bf16 cache of --cache-images (2048) maps 14x14x2048, --batch 32.
+  cached003_bf16 / eval003_cached_bf16
+            the same three variants for the cfg 003 head (pose head 2048 -> 768 -> 16, attention from pose_pre_logits,
+            K = 393, caller-held W1 shadow and W2^T image; custom_ops/pose_cache.py) from a resident bf16 cache:
+            (a) includes the PoseLabelTable.gather of the step's pose labels, (b) the same label gather.  --steps 100.
   cached_hmdb_perclass_clips_bf16
             cached_hmdb_clips_bf16 with the per-class head (M = K = 51): 81 videos x 25 frames, 8 clips x 4 frames,
             temporal attention; evaluation at 4 x 25.
@@ -1294,6 +1298,119 @@ def run_cached(cof, dev, args, which):
             'clamped_ids': int(info['steps'][0]._cached.cache.status)}
 
 
+def build_cached003(cof, dev, N=32, H=14, T=2048, train=True):
+    """cfg 003 (pose head 2048 -> 768 -> 16, attention from pose_pre_logits, K = 393) from a RESIDENT bf16 cache of T
+    14x14x2048 maps, three ways: (a) the cached step (custom_ops/pose_cache.py) on a fresh shuffled index per step,
+    PoseLabelTable.gather included when training; (b) cache.gather(index) + rebind + the plain frozen step, plus the
+    same label gather; (c) the plain step on one fixed batch.  Training: dropout keep 0.2, a caller-held W1 shadow and
+    W2^T image.  -> ({name: step}, info)"""
+    from attentionalpoolingaction_amd.custom_ops import pose_cache
+    C, P, Cp, J, K = 2048, H * H, 768, 16, 393
+    T = max(int(T), 4 * N)
+    g = torch.Generator().manual_seed(42)
+    labels = torch.randint(0, K, (T,), generator=g).to(dev)
+    cache = cof.FeatureCache.empty((T, H, H, C), torch.bfloat16, dev, labels=labels)
+    for first in range(0, T, 256):
+        n = min(256, T - first)
+        cache.write(first, _features(n, P, C, torch.bfloat16, dev, seed=42 + first).view(n, H, H, C))
+    rn = lambda *s: torch.randn(*s, generator=g)
+    params = tuple(t.to(dev) for t in (rn(C, Cp) / C ** 0.5, torch.zeros(Cp), rn(Cp, J) / Cp ** 0.5, torch.zeros(J),
+                                       rn(Cp, 1) / Cp ** 0.5, torch.zeros(1), rn(C, K) / C ** 0.5, torch.zeros(K)))
+    table = pose_cache.PoseLabelTable(rn(T, H, H, J).to(dev), (torch.rand(T, J, generator=g) < 0.8).to(dev))
+    batches = [b for e in range(4) for b in cache.epoch(N, seed=e)]
+    w1b = params[0].to(torch.bfloat16)
+    f = cache.features
+    state = {'a': 0, 'b': 0}
+    if train:
+        w2t = cof.pose_w2t_image(params[2])
+        ctr = torch.zeros(1, dtype=torch.int64, device=dev)
+        kw = dict(flags=cof.attn_flags(False, False, True), keep_prob=0.2, seed=42, offset=ctr, w1_bf16=w1b, w2t_bf16=w2t)
+        grads = lambda: [None] + [torch.empty_like(t) for t in params]
+        rows = [table.new_batch(N) for _ in range(3)]
+        for lab, val in rows:
+            table.gather(batches[0], lab, val, clamp=False)
+        st_a = pose_cache.PoseAttnTrainStepCached(cache.select(batches[0]), params, None, rows[0][0].view(N, P, J),
+                                                  rows[0][1], grads(), **kw)
+        st_b = cof.PoseAttnTrainStep(cache.gather(batches[0]).view(N, P, C), params, labels[:N].clone(),
+                                     rows[1][0].view(N, P, J), rows[1][1], grads(), **kw)
+        st_c = cof.PoseAttnTrainStep(f[:N].view(N, P, C), params, labels[:N].contiguous(), rows[2][0].view(N, P, J),
+                                     rows[2][1], grads(), **kw)
+    else:
+        st_a = pose_cache.PoseAttnEvalStepCached(cache.select(batches[0]), params, None, w1_bf16=w1b)
+        st_b = cof.PoseAttnEvalStep(cache.gather(batches[0]).view(N, P, C), params, None, w1_bf16=w1b)
+        st_c = cof.PoseAttnEvalStep(f[:N].view(N, P, C), params, None, w1_bf16=w1b)
+
+    def step_a():
+        idx = batches[state['a'] % len(batches)]
+        state['a'] += 1
+        if train:
+            table.gather(idx, rows[0][0], rows[0][1], clamp=False)
+        st_a.rebind(index=idx)
+        st_a.run()
+
+    def step_b():
+        idx = batches[state['b'] % len(batches)]
+        state['b'] += 1
+        if train:
+            table.gather(idx, rows[1][0], rows[1][1], clamp=False)
+            st_b.rebind(X=cache.gather(idx).view(N, P, C), labels=labels[idx.long()])
+        else:
+            st_b.rebind(X=cache.gather(idx).view(N, P, C))
+        st_b.run()
+
+    def step_a_clamped():   # (a) with the table's default: the ids clamped first, a third launch (what deploy pays)
+        idx = batches[state['a'] % len(batches)]
+        state['a'] += 1
+        table.gather(idx, rows[0][0], rows[0][1])
+        st_a.rebind(index=idx)
+        st_a.run()
+
+    def step_a_bare():      # (a) without the PoseLabelTable.gather: what its launches cost
+        idx = batches[state['a'] % len(batches)]
+        state['a'] += 1
+        st_a.rebind(index=idx)
+        st_a.run()
+
+    info = {'N': N, 'T': T, 'shape': '{} of {} x {}x{}x{}, Cp={}, J={}, K={}{}'.format(
+        N, T, H, H, C, Cp, J, K, ', dropout keep=0.2' if train else ''),
+            'gather_bytes_per_step': 2 * N * P * C * 2, 'pose_label_bytes_per_step': N * P * J * 4 + N * J,
+            'cache_bytes': T * P * C * 2, 'cache': cache, 'steps': (st_a, st_b, st_c)}
+    forms = {'a_cached': step_a, 'b_gather_rebind_plain': step_b, 'c_plain_fixed': st_c.run}
+    if train:
+        forms['a_without_label_gather'] = step_a_bare
+        forms['a_label_gather_clamped'] = step_a_clamped
+    return forms, info
+
+
+def run_cached003(cof, dev, args, which):
+    """cached003_bf16 / eval003_cached_bf16: the three variants ALTERNATING in one process, five timed loops of each,
+    interleaved; medians and the loops' spread (as run_cached)."""
+    train = which == 'cached003_bf16'
+    forms, info = build_cached003(cof, dev, args.batch, args.hw, args.cache_images, train)
+    if args.only in forms:      # one variant alone (a kernel trace of it)
+        forms = {args.only: forms[args.only]}
+    for _ in range(args.warmup):
+        for step in forms.values():
+            step()
+    torch.cuda.synchronize()
+    runs = {k: [] for k in forms}
+    for _ in range(5):
+        for name, step in forms.items():
+            sec, _ = timed(step, args.steps, 0, min_ms=0.0, repeats=1)
+            runs[name].append(sec * 1e6)
+    med = {k: sorted(v)[len(v) // 2] for k, v in runs.items()}
+    return {'workload': '{}: cfg 003 one-call {} step from a resident bf16 feature cache, three variants alternating '
+                        'in one process; {}'.format(which, 'frozen training' if train else 'evaluation', info['shape']),
+            'us_per_step': {k: round(v, 2) for k, v in med.items()},
+            'us_per_step_runs': {k: [round(x, 2) for x in v] for k, v in runs.items()},
+            'us_per_step_spread': {k: round(max(v) - min(v), 2) for k, v in runs.items()},
+            'a_minus_c_us': round(med['a_cached'] - med['c_plain_fixed'], 2) if len(med) > 1 else None,
+            'a_over_b': round(med['a_cached'] / med['b_gather_rebind_plain'], 4) if len(med) > 1 else None,
+            'gather_bytes_per_step': info['gather_bytes_per_step'],
+            'pose_label_bytes_per_step': info['pose_label_bytes_per_step'], 'cache_bytes': info['cache_bytes'],
+            'clamped_ids': int(info['cache'].status)}
+
+
 def _measure_routes(forms, steps):
     """{name: callable that enqueues one pass of `steps` steps} ALTERNATING, five timed passes each after one untimed:
     per pass the wall clock around it with ONE synchronise at its end and a pair of device events around it; medians per
@@ -1921,6 +2038,7 @@ def main():
                                                          'hico002', 'charades_clips', 'frozen002', 'frozen003',
                                                          'frozen_perclass', 'frozen002_fp8', 'eval002_fp8',
                                                          'cached002_fp8', 'cached002_bf16', 'cached_perclass_bf16',
+                                                         'cached003_bf16', 'eval003_cached_bf16',
                                                          'epoch002_fp8',
                                                          'epoch002_bf16', 'explain002', 'map393'] +
                     sorted(EVAL_CLIPS) + sorted(RANK_WORKLOADS) + sorted(CACHED_CLIPS) + sorted(CLIP_EPOCHS))
@@ -1928,8 +2046,10 @@ def main():
     ap.add_argument('--frames', type=int, default=4, help='video_*: frames per clip')
     ap.add_argument('--only', default=None, choices=['clip_one_call', 'module_path', 'flat_one_call',
                                                      'multilabel_one_call', 'softmax_one_call', 'one_call',
-                                                     'sequence', 'rank_one_call', 'rank1_one_call'],
-                    help='video_* / hico002 / charades_clips / eval_* / rank*: run one variant alone (kernel traces)')
+                                                     'sequence', 'rank_one_call', 'rank1_one_call', 'a_cached',
+                                                     'b_gather_rebind_plain', 'c_plain_fixed'],
+                    help='video_* / hico002 / charades_clips / eval_* / rank* / cached003_bf16 / eval003_cached_bf16: run '
+                         'one variant alone (kernel traces)')
     ap.add_argument('--batch', type=int, default=32)
     ap.add_argument('--cache-images', type=int, default=2048, help='cached002_*: images in the resident cache')
     ap.add_argument('--hw', type=int, default=14)
@@ -1975,6 +2095,9 @@ def main():
         return
     if args.workload in ('cached002_fp8', 'cached002_bf16', 'cached_perclass_bf16'):
         print(json.dumps(run_cached(cof, dev, args, args.workload)))
+        return
+    if args.workload in ('cached003_bf16', 'eval003_cached_bf16'):
+        print(json.dumps(run_cached003(cof, dev, args, args.workload)))
         return
     if args.workload in ('epoch002_fp8', 'epoch002_bf16'):
         print(json.dumps(run_epoch(cof, dev, args, args.workload)))
