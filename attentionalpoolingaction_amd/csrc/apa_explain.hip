@@ -33,11 +33,9 @@ constexpr int EXP_THREADS = 256;
 constexpr size_t EXP_LDS_MAX = 64 * 1024;       // T * C * 4 bytes of weights per block
 constexpr size_t EXP_LDS_SMALL = 16 * 1024;     // up to here the block count is the evaluation step's
 
-struct ExplainPlan {
-  int S, nblk;
-  size_t off_w, off_k, off_b, total;
-};
+}  // namespace
 
+// (ExplainPlan and ExplainGeom: apa_internal.h)
 // S: the pixel splits of the evaluation step's own pooling pass (m1_plan), so that block (n, s) meets the lines the
 // same XCD read last; halved while a block's weight image is large -- the image is staged once per block, and at
 // T * C * 4 = 64 KiB two blocks fill a CU's LDS anyway
@@ -54,6 +52,8 @@ ExplainPlan explain_plan(int N, int P, int C, int K, int T) {
   pl.total = off;
   return pl;
 }
+
+namespace {
 
 __global__ __launch_bounds__(EXP_THREADS) void explain_gather_kernel(
     const float* __restrict__ Wt, const float* __restrict__ bt, const int32_t* __restrict__ classes,
@@ -90,12 +90,6 @@ template <> struct XVec<bf16_t, 4> {
   static __device__ __forceinline__ void unpack(const R& r, float* o) {
     o[0] = bf16_lo(r.x); o[1] = bf16_hi(r.x); o[2] = bf16_lo(r.y); o[3] = bf16_hi(r.y);
   }
-};
-
-// pixels a wave takes at a time: PIX * T dot products fit the 16 slots of one DPP row
-template <int TT> struct ExplainGeom {
-  static constexpr int PIX = TT <= 4 ? 4 : (TT == 5 ? 3 : 2);
-  static constexpr int U = PIX == 2 ? 4 : 2;   // channel vectors per round: U * PIX (6 or 8) loads in flight per lane
 };
 
 template <typename T, int EPV, int TT>

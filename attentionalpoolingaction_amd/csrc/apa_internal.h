@@ -676,4 +676,16 @@ int pc_weight_images(const PoolCall& d, const float* Wa, const float* ba, const 
 int pc_forward(const PoolCall& d, const M1Fwd& io, M1Xent* xf = nullptr);
 int pc_backward(const PoolCall& d, const M1Bwd& io, const M1Xent* xf = nullptr);
 
+// apa_explain.hip: what apa_attn_explain decides before its launches (read by the test-only probe, apa_explain_probe.hip)
+struct ExplainPlan {
+  int S, nblk;                          // pixel splits per image, N * S blocks
+  size_t off_w, off_k, off_b, total;    // workspace carve (byte offsets)
+};
+ExplainPlan explain_plan(int N, int P, int C, int K, int T);
+// pixels a wave of explain_main_kernel<.., TT> takes at a time: PIX * TT dot products fit the 16 slots of one DPP row
+template <int TT> struct ExplainGeom {
+  static constexpr int PIX = TT <= 4 ? 4 : (TT == 5 ? 3 : 2);
+  static constexpr int U = PIX == 2 ? 4 : 2;   // channel vectors per round: U * PIX (6 or 8) loads in flight per lane
+};
+
 }  // namespace apa

@@ -176,17 +176,58 @@ OVERLAY_CASES = [
 ]
 
 
+# The edges of apa_attention_overlay that no fixture holds (tests/test_explain_gpu.py; their conditions are checked on
+# the CPU from the float64 reference alone, tests/test_explain_paths_cpu.py).  Further kinds:
+#   'mixed'   N = 2, T = 3: image 0 in [0, 255] under a map >= 0 (t = 0, lo >= 0), a map <= -1 (t = 1, lo < 0 and
+#             |lo| > hi) and a map == 0 (t = 2, lo >= 0); image 1 mean-subtracted under signed maps -- the (n,t) images of
+#             one call take different branches of the uint8 rule, with different extremes;
+#   'allneg'  a negative image under a map <= 0: hi < 0, so max(|lo|,|hi|) is |lo|;
+#   'lozero'  'nonneg' with a black pixel under a zero map corner: lo == 0 exactly, in float32 and in float64.
+# The seeds are chosen so that at most BAND_SHARE of every (n,t) image lies in the uint8 band (the extreme value always
+# lands on an integer, which is why the thin images are 301 long).
+OVERLAY_EDGE_CASES = [
+    dict(name='down_15x20_7x9', N=1, T=2, h=15, w=20, H=7, W=9, kind='meansub', seed=601),
+    dict(name='identity_9x11', N=1, T=2, h=9, w=11, H=9, W=11, kind='nonneg', seed=602),
+    dict(name='m1x1_13x17', N=2, T=1, h=1, w=1, H=13, W=17, kind='meansub', seed=503),
+    dict(name='m1x7_5x40', N=1, T=2, h=1, w=7, H=5, W=40, kind='nonneg', seed=504),
+    dict(name='m7x1_40x5', N=1, T=2, h=7, w=1, H=40, W=5, kind='meansub', seed=505),
+    dict(name='row_image_1x301', N=1, T=2, h=3, w=5, H=1, W=301, kind='meansub', seed=506),
+    dict(name='column_image_301x1', N=1, T=2, h=5, w=3, H=301, W=1, kind='nonneg', seed=507),
+    dict(name='mixed_4x6_20x24', N=2, T=3, h=4, w=6, H=20, W=24, kind='mixed', seed=508),
+    dict(name='allneg_4x6_20x24', N=1, T=2, h=4, w=6, H=20, W=24, kind='allneg', seed=509),
+    dict(name='lozero_4x6_20x24', N=1, T=2, h=4, w=6, H=20, W=24, kind='lozero', seed=510),
+    dict(name='m5x5_130x131', N=1, T=1, h=5, w=5, H=130, W=131, kind='meansub', seed=511),   # 17030 pixels
+]
+
+
 def overlay_inputs(case):
     """(maps [N,T,h,w] float32, images [N,H,W,3] float32) of a case, from its seed"""
     rs = np.random.RandomState(case['seed'])
     shape_m = (case['N'], case['T'], case['h'], case['w'])
     shape_i = (case['N'], case['H'], case['W'], 3)
-    if case['kind'] == 'nonneg':
+    kind = case['kind']
+    if kind in ('nonneg', 'lozero'):
         maps = rs.rand(*shape_m)
         images = np.floor(rs.rand(*shape_i) * 256.0)
-    else:
+        if kind == 'lozero':
+            maps[:, :, 0, 0] = 0.0
+            images[:, 0, 0, :] = 0.0
+    elif kind == 'meansub':
         maps = rs.randn(*shape_m) * 0.5
         images = np.floor(rs.rand(*shape_i) * 256.0) - 128.0
+    elif kind == 'mixed':
+        assert case['N'] == 2 and case['T'] == 3
+        maps = rs.randn(*shape_m) * 0.5
+        images = np.floor(rs.rand(*shape_i) * 256.0) - 128.0
+        images[0] += 128.0
+        maps[0, 0] = rs.rand(case['h'], case['w'])
+        maps[0, 1] = -1.0 - rs.rand(case['h'], case['w'])
+        maps[0, 2] = 0.0
+    elif kind == 'allneg':
+        maps = -rs.rand(*shape_m)
+        images = -1.0 - np.floor(rs.rand(*shape_i) * 127.0)
+    else:
+        raise ValueError('overlay_inputs: unknown kind %r' % (kind,))
     return maps.astype(np.float32), images.astype(np.float32)
 
 
