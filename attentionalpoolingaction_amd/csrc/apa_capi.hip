@@ -466,11 +466,13 @@ extern "C" size_t apa_attn_pool_rank_workspace_bytes(int N, int P, int C, int Ca
 static int rank_fwd_run(const PoolCall& d, const RankCall& rk, const M1Fwd& f) {
   M1Call c;
   const int rc = m1_call_fill(c, d, &f, nullptr);
+  m1_call_full_rows(c, false);   // m1r_pool_fwd_kernel: its own rows, never the paired form
   return rc != APA_OK ? rc : m1r_forward(c, rk, f);
 }
 static int rank_bwd_run(const PoolCall& d, const RankCall& rk, const M1Bwd& b) {
   M1Call c;
   const int rc = m1_call_fill(c, d, nullptr, &b);
+  m1_call_full_rows(c, true);
   return rc != APA_OK ? rc : m1r_backward(c, rk, b);
 }
 

@@ -241,6 +241,8 @@ constexpr unsigned APA_IFLAG_FINALIZE_LAUNCH = 1u << 27;   // M == 1 forward: m1
                                                            // own where the logits kernel could merge the partials itself
 constexpr unsigned APA_IFLAG_FOLD_TILE16 = 1u << 28;   // M == 1 folded forward: the 16-image geometry at any shape (read from
                                                        // g_m1_iflags only: the probe library's tests)
+constexpr unsigned APA_IFLAG_UNPAIRED = 1u << 29;      // M == 1 forward streaming pass: one 256-thread block and one partial row per
+                                                       // logical block at any S (read from g_m1_iflags only, by m1_call_fill)
 
 struct M1Xent {
   const int64_t* labels = nullptr;
@@ -337,6 +339,9 @@ struct M1FwdRoute {
 };
 extern thread_local unsigned g_m1_iflags;
 extern thread_local M1FwdRoute g_m1_fwd_route;
+// ... and the partial rows (M1Call::nrows) of the last traced forward / backward m1_call_fill
+struct M1Rows { int fwd, bwd; };
+extern thread_local M1Rows g_m1_rows;
 
 enum M1Act { M1_ACT_ID = 0, M1_ACT_RELU = 1, M1_ACT_SOFTMAX = 2 };   // passed to the kernels as int
 // A forward / backward call: the caller's tensors (M1Fwd / M1Bwd) and, in M1Call, everything the call resolves before
@@ -358,6 +363,14 @@ struct M1Call {
   // small-K route (m1_small_route_ok); gemv2: Ca is served by the register-resident attention GEMV backward
   bool fused, train, rank1, ext, relu_input, no_dx, small, gemv2;
   M1Pool pool; M1Plan pl;  // the pooling family of both streaming passes; the plan and what is carved from it:
+  // partial rows of pacc the forward streaming pass of this call writes: pl.nblk, or pl.nblk / 2 where two logical
+  // blocks share one 512-thread block and add their rows before they leave the CU (apa_m1_stream.hip: the paired
+  // form -- fp32, stream family, even S, no softmax).  A backward call always has pl.nblk (pdwa / pdba: one row per
+  // logical block).  pstat keeps one entry per logical block
+  // (the rank-R route fills the same descriptor but runs its own m1r_* kernels, one row per logical block: its two
+  // entry points reset the count with m1_call_full_rows)
+  int nrows;
+  bool paired() const { return nrows != pl.nblk; }
   float *pacc, *pstat, *pdwa, *pdba, *dz, *dzatt, *gemm_ws, *cat_e;   // (dzatt: the caller's dXatt under rank1)
   float* sn;               // [N] G . bt behind pdba (the region is sized nblk + N): null off the small-K route
   uint8_t* maskbits;       // forward (training): where the keep-bits go
@@ -368,6 +381,12 @@ struct M1Call {
   // a gathered call (PoolCall::fc): both streaming passes run their gathered instances on `ga`; T: the images behind X
   bool gather; int T; M1Gather ga;
 };
+// A call whose streaming kernels are not apa_m1_stream.hip's whatever c.pool says (apa_capi.hip: rank_fwd_run /
+// rank_bwd_run): one partial row per logical block
+inline void m1_call_full_rows(M1Call& c, bool bwd) {
+  c.nrows = c.pl.nblk;
+  if (m1_trace()) (bwd ? g_m1_rows.bwd : g_m1_rows.fwd) = c.nrows;
+}
 // where a gathered forward pass leaves labels[index[n]] for the loss reducers behind it: the head of the pdwa region,
 // which nothing writes before the backward pass (nblk * C * 4 >= N * 8 bytes for every served C)
 inline int64_t* m1_gathered_labels(void* ws, const M1Plan& pl) {
@@ -459,8 +478,9 @@ size_t m1_logits2_ws_bytes(int N, int C, int K);
 // The folded forward: the partial logits kernel merges the pooling pass's S per-block partials in its prologue
 // (z, stored too) and the reduce kernel forms abar from the per-block statistics, both with m1_finalize_fwd_kernel's
 // own summation chains -- z and abar are outputs then.  null: z and abar are in memory already.
-struct M1Fold { const float* pacc; const float* pstat; int S, P; };
-bool m1_logits2_fold_supported(int N, int C, int S);
+// rows: partial rows per image in pacc (S, or S / 2 behind a paired pooling pass); pstat has S entries per image
+struct M1Fold { const float* pacc; const float* pstat; int S, P, rows; };
+bool m1_logits2_fold_supported(int N, int C, int rows);
 int m1_logits2(float* z, const float* Wt, float* abar, const float* bt, float* logits,
                float* part_ws, int N, int C, int K, hipStream_t st, const M1Fold* fold = nullptr);
 int m1_logits2_partials(float* z, const float* Wt, float* part_ws, int N, int C, int K, hipStream_t st,

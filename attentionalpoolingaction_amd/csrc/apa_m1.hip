@@ -29,10 +29,12 @@ namespace apa {
 // (one float4 each).
 //   z[n,c] = (1/P) sum_s pacc[n,s,c] * w_s     w_s = exp(m_s - M)/L (on-line softmax) or 1
 //   abar[n] = (1/P) sum_p A[n,p];  softmax: att[n,p] <- exp(Z - M)/L
+// R: partial rows per image in pacc -- S, or S / 2 behind a paired pooling pass (apa_m1_stream.hip; never the on-line
+// softmax, whose rows carry their own weights); pstat always has S entries per image.
 // --------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void m1_finalize_fwd_kernel(
-    const float* __restrict__ pacc, const float* __restrict__ pstat, int P, int S, int C, int online_softmax, int cw,
-    float* __restrict__ z, float* __restrict__ abar, float* __restrict__ att) {   // inputs and sizes first: preload
+    const float* __restrict__ pacc, const float* __restrict__ pstat, int P, int S, int R, int C, int online_softmax,
+    int cw, float* __restrict__ z, float* __restrict__ abar, float* __restrict__ att) {   // inputs and sizes first: preload
   // cw = threads of the block that carry channels (one float4 each): the grid is (N, ceil(C / 4cw)).  A CU
   // sustains only ~25-30 GB/s of vector loads, so the 4 MB of partials want to be spread over all 256
   // CUs (cw = 64 at N = 32: 256 blocks x 16 KB) rather than 64 blocks x 64 KB (cw = 256).
@@ -47,12 +49,12 @@ __global__ __launch_bounds__(256) void m1_finalize_fwd_kernel(
   constexpr int FB = 16;
   const bool chan = (int)threadIdx.x < cw;
   const int v = chan ? blockIdx.y * cw + threadIdx.x : 0;
-  const float* pa = pacc + (size_t)n * S * C + (v * 4 < C ? v * 4 : 0);
+  const float* pa = pacc + (size_t)n * R * C + (v * 4 < C ? v * 4 : 0);
   float4 first[FB];
   if (chan) {   // wave-uniform: cw is a multiple of 64
 #pragma unroll
     for (int u = 0; u < FB; ++u)
-      first[u] = *reinterpret_cast<const float4*>(pa + (size_t)min(u, S - 1) * C);
+      first[u] = *reinterpret_cast<const float4*>(pa + (size_t)min(u, R - 1) * C);
   }
   // one split per thread: no serial dependent-load chain
   float m_s = -INFINITY, l_s = 0.f, a_s = 0.f;
@@ -85,20 +87,20 @@ __global__ __launch_bounds__(256) void m1_finalize_fwd_kernel(
     float4 r = make_float4(0.f, 0.f, 0.f, 0.f);
 #pragma unroll
     for (int u = 0; u < FB; ++u) {
-      if (u < S) {
+      if (u < R) {
         const float w = s_w[u];
         r.x = fmaf(first[u].x, w, r.x); r.y = fmaf(first[u].y, w, r.y);
         r.z = fmaf(first[u].z, w, r.z); r.w = fmaf(first[u].w, w, r.w);
       }
     }
-    for (int s0 = FB; s0 < S; s0 += FB) {   // S > 16 (small batches): further rounds of 16
+    for (int s0 = FB; s0 < R; s0 += FB) {   // more than 16 rows (small batches): further rounds of 16
       float4 a[FB];
 #pragma unroll
       for (int u = 0; u < FB; ++u)
-        a[u] = *reinterpret_cast<const float4*>(pa + (size_t)min(s0 + u, S - 1) * C);
+        a[u] = *reinterpret_cast<const float4*>(pa + (size_t)min(s0 + u, R - 1) * C);
 #pragma unroll
       for (int u = 0; u < FB; ++u) {
-        const float w = s0 + u < S ? s_w[s0 + u] : 0.f;
+        const float w = s0 + u < R ? s_w[s0 + u] : 0.f;
         r.x = fmaf(a[u].x, w, r.x); r.y = fmaf(a[u].y, w, r.y);
         r.z = fmaf(a[u].z, w, r.z); r.w = fmaf(a[u].w, w, r.w);
       }
@@ -311,6 +313,7 @@ __global__ __launch_bounds__(256) void m1_att_gemv_bwd2_kernel(
 thread_local M1Trace* g_m1_trace = nullptr;
 thread_local unsigned g_m1_iflags = 0;
 thread_local M1FwdRoute g_m1_fwd_route = {0, 0};
+thread_local M1Rows g_m1_rows = {0, 0};
 
 // Any channel count that is a whole number of 16-byte vectors is served: the channel-split streaming
 // kernels (apa_m1_stream.hip) for the wide benchmark shapes, the per-pixel kernels (apa_m1_vec.hip) for the
@@ -392,6 +395,13 @@ int m1_call_fill(M1Call& c, const PoolCall& d, const M1Fwd* f, const M1Bwd* b, c
            : !c.ext && m1s_supported(C, dtype) ? M1_POOL_STREAM
            : !c.ext && m1v_supported(C, dtype) ? M1_POOL_VEC : M1_POOL_GENERIC;
   c.pl = m1_plan(N, P, C, Ca, K);
+  // The paired form of the forward streaming pass (apa_m1_stream.hip): the plan is the logical one, the rows are what
+  // is written.  fp32 features on the stream family with an even S and no softmax in the pooling kernel; bf16 features,
+  // softmax instances, odd S and every backward pass keep one row per logical block (measured:
+  // profiles/paired_rows_summary.md)
+  const bool paired = f && c.pool == M1_POOL_STREAM && dtype == APA_DTYPE_F32 && c.pl.S % 2 == 0 &&
+                      c.pool_act != M1_ACT_SOFTMAX && !(g_m1_iflags & APA_IFLAG_UNPAIRED);
+  c.nrows = paired ? c.pl.nblk / 2 : c.pl.nblk;
   char* w = static_cast<char*>(ws);
   c.pacc = reinterpret_cast<float*>(w + c.pl.off_pacc);
   c.pstat = reinterpret_cast<float*>(w + c.pl.off_pstat);
@@ -426,6 +436,7 @@ int m1_call_fill(M1Call& c, const PoolCall& d, const M1Fwd* f, const M1Bwd* b, c
   c.td_ready = hk.td_ready; c.grad_ready = hk.grad_ready;
   if (M1Trace* tr = m1_trace()) {
     tr->S = c.pl.S; tr->ppb = c.pl.ppb; tr->nblk = c.pl.nblk; tr->fused = c.fused; tr->relu_input = c.relu_input;
+    (b ? g_m1_rows.bwd : g_m1_rows.fwd) = c.nrows;
   }
 
   // ---- every refusal of the path: nothing has been launched yet ----
@@ -537,9 +548,10 @@ int m1_forward(const M1Call& c, const M1Fwd& io, M1Xent* xf) {
   // budget of 16 loads per lane (identity / relu attention -- the on-line softmax merge and the normalisation of att
   // stay with the finalize kernel --, S <= 16, N < 128, no concatenated channels, 16-byte rows), else a launch of its own
   const bool fold = (xroute || l2route) && !((c.flags | g_m1_iflags) & APA_IFLAG_FINALIZE_LAUNCH) &&
-                    c.act != M1_ACT_SOFTMAX && !c.cat && m1_logits2_fold_supported(N, C, c.pl.S) &&
+                    c.act != M1_ACT_SOFTMAX && !c.cat && m1_logits2_fold_supported(N, C, c.nrows / N) &&
+                    c.pl.S <= 16 &&   // (the reducers' abar: one pstat entry per logical block, 16 at the most)
                     ((reinterpret_cast<uintptr_t>(io.zsave) | reinterpret_cast<uintptr_t>(c.pacc)) & 15) == 0;
-  const M1Fold mf{c.pacc, c.pstat, c.pl.S, c.P};
+  const M1Fold mf{c.pacc, c.pstat, c.pl.S, c.P, c.nrows / N};
   // enough blocks to put every CU to work (the kernel is bound by the bytes each CU loads)
   int cw = 256;
   while (cw > 64 && (long)N * ((C + 4 * cw - 1) / (4 * cw)) < 256) cw >>= 1;
@@ -550,7 +562,7 @@ int m1_forward(const M1Call& c, const M1Fwd& io, M1Xent* xf) {
   }
   if (!fold) {
     hipLaunchKernelGGL(m1_finalize_fwd_kernel, dim3(N, (C + 4 * cw - 1) / (4 * cw)), dim3(256), 0, c.st, c.pacc,
-                       c.pstat, c.P, c.pl.S, C, online, cw, io.zsave, io.abar, io.att);
+                       c.pstat, c.P, c.pl.S, c.nrows / N, C, online, cw, io.zsave, io.abar, io.att);
     APA_LAUNCH_CHECK("m1_finalize_fwd_kernel");
   }
   // logits = z . Wt + abar (x) bt -- the first reader of Wt / bt (apa_hooks.td_weights_ready_event)

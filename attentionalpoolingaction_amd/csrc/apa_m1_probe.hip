@@ -75,6 +75,64 @@ int apa_probe_m1_call_fill(int bwd, int loss_done, int xatt_is_x, int N, int P, 
   return rc;
 }
 
+// The paired form of the streaming passes (apa_m1_stream.hip; tests/test_m1_paired_rows_*.py).
+// out[0..1] = partial rows (M1Call::nrows) of the last traced forward / backward call
+void apa_probe_m1_rows(int64_t* out) { out[0] = apa::g_m1_rows.fwd; out[1] = apa::g_m1_rows.bwd; }
+
+// m1_call_fill alone, as apa_probe_m1_call_fill, for the row-count rule: out[0..3] = nrows, nblk, S, plan total.
+// unpaired != 0: with APA_IFLAG_UNPAIRED set for the call; unpaired == 2: as the rank-R entry points fill it
+// (apa_capi.hip rank_fwd_run / rank_bwd_run: m1_call_full_rows behind m1_call_fill).
+int apa_probe_m1_call_rows(int bwd, int xatt_is_x, int unpaired, int N, int P, int C, int Ca, int K, unsigned flags,
+                           float keep_prob, int dtype, int64_t* out) {
+  alignas(16) static char base[64];
+  apa::M1Call c;
+  apa::M1Bwd b{};
+  b.X = base; b.Xatt = xatt_is_x ? base : base + 16;
+  b.Wt = reinterpret_cast<const float*>(base); b.zsave = b.Wt; b.G = b.Wt; b.att = b.Wt;
+  b.dXatt = base;
+  apa::PoolCall d{{N, P, C, Ca, K, 1, dtype}};
+  d.flags = flags; d.keep_prob = keep_prob; d.seed = 1; d.offset = 2; d.ws = base;
+  const apa::M1Fwd f{b.X, b.Xatt};
+  const unsigned saved = apa::g_m1_iflags;
+  if (unpaired == 1) apa::g_m1_iflags |= apa::APA_IFLAG_UNPAIRED;
+  const int rc = apa::m1_call_fill(c, d, bwd ? nullptr : &f, bwd ? &b : nullptr, nullptr);
+  if (unpaired == 2) apa::m1_call_full_rows(c, bwd != 0);
+  apa::g_m1_iflags = saved;
+  out[0] = c.nrows; out[1] = c.pl.nblk; out[2] = c.pl.S; out[3] = (int64_t)c.pl.total;
+  return rc;
+}
+
+// apa_probe_m1_fwd_ex / apa_probe_m1_bwd_ex with pairing forced off: the streaming pass runs one 256-thread block and
+// writes one partial row per logical block, at any S.  The workspace then holds the unpaired rows for a test to add up.
+namespace {
+struct UnpairedScope {
+  unsigned saved;
+  UnpairedScope() : saved(apa::g_m1_iflags) { apa::g_m1_iflags |= apa::APA_IFLAG_UNPAIRED; }
+  ~UnpairedScope() { apa::g_m1_iflags = saved; }
+};
+}  // namespace
+int apa_probe_m1_fwd_unpaired(apa::M1Trace* t, const apa_hooks* hooks, const void* X, const void* Xatt, const float* Wa,
+                              const float* ba, const float* Wt, const float* bt, float* logits, float* att,
+                              float* zsave, float* abar, void* topdown, void* ws, size_t ws_bytes, int N, int P, int C,
+                              int Ca, int K, int M, unsigned flags, float keep_prob, uint64_t seed, uint64_t offset,
+                              int dtype, void* stream) {
+  TraceScope s(t);
+  UnpairedScope u;
+  return apa_attn_pool_fwd_ex(hooks, X, Xatt, Wa, ba, Wt, bt, logits, att, zsave, abar, topdown, ws, ws_bytes, N, P,
+                              C, Ca, K, M, flags, keep_prob, seed, offset, dtype, stream);
+}
+int apa_probe_m1_bwd_unpaired(apa::M1Trace* t, const apa_hooks* hooks, const void* X, const void* Xatt, const float* Wa,
+                              const float* ba, const float* Wt, const float* bt, const float* att, const float* zsave,
+                              const float* abar, const float* G, void* dX, void* dXatt, float* dWa, float* dba,
+                              float* dWt, float* dbt, void* ws, size_t ws_bytes, int N, int P, int C, int Ca, int K,
+                              int M, unsigned flags, float keep_prob, uint64_t seed, uint64_t offset, int dtype,
+                              void* stream) {
+  TraceScope s(t);
+  UnpairedScope u;
+  return apa_attn_pool_bwd_ex(hooks, X, Xatt, Wa, ba, Wt, bt, att, zsave, abar, G, dX, dXatt, dWa, dba, dWt, dbt,
+                              ws, ws_bytes, N, P, C, Ca, K, M, flags, keep_prob, seed, offset, dtype, stream);
+}
+
 int apa_probe_m1_fwd_ex(apa::M1Trace* t, const apa_hooks* hooks, const void* X, const void* Xatt, const float* Wa,
                         const float* ba, const float* Wt, const float* bt, float* logits, float* att, float* zsave,
                         float* abar, void* topdown, void* ws, size_t ws_bytes, int N, int P, int C, int Ca, int K,

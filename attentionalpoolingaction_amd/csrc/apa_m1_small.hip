@@ -470,13 +470,15 @@ __global__ __launch_bounds__(256) void m1_logits2_kernel(const float* __restrict
 //   256 blocks at the benchmark shape.  Only who loads and stores what differs: every z and every partial logit is the
 //   same chain.  launch_logits2_fold states when it is taken.  Headline step, six alternated runs each: 46.05 ->
 //   45.14 us (20 steps), 44.94 -> 43.87 us (200 steps); profiles/chain_bodies_summary.md.
+// R: partial rows per image (M1Fold::rows: S, or S / 2 behind a paired pooling pass, whose rows are already the sum of
+//   two logical blocks'); FB: rows requested per lane, 16, or 8 where R <= 8 -- half the prologue's loads.
 // --------------------------------------------------------------------------------------------
-template <int KG, int ROWS>   // ROWS: images per block, 8 (half tiles) or 16 (full tiles)
+template <int KG, int ROWS, int FB = 16>   // ROWS: images per block, 8 (half tiles) or 16 (full tiles)
 __global__ __launch_bounds__(256) void m1_logits2_fold_kernel(const float* __restrict__ pacc,
                                                               const float* __restrict__ Wt,
                                                               float* __restrict__ zsave,
                                                               float* __restrict__ part, int N, int C, int K,
-                                                              int S, int P) {
+                                                              int R, int P) {
   static_assert(ROWS == 8 || ROWS == 16, "half or full MFMA tiles");
   constexpr int RT = ROWS * 16;   // outputs per k-tile
   extern __shared__ __attribute__((aligned(16))) float red[];   // [4 waves][KG tiles][ROWS rows][16]
@@ -492,11 +494,10 @@ __global__ __launch_bounds__(256) void m1_logits2_fold_kernel(const float* __res
   for (int j = 0; j < KG; ++j)                                          // surplus tiles / columns:
     colj[j] = min(min(gx * KG + j, ktiles - 1) * 16 + r, K - 1);       // recomputed, discarded
   // every load of the block in one batch, the partials first: the merge runs while Wt is still arriving
-  constexpr int FB = 16;
-  const float* pa = pacc + (size_t)n * S * C + cw + 4 * kq;
+  const float* pa = pacc + (size_t)n * R * C + cw + 4 * kq;
   float4 first[FB];
 #pragma unroll
-  for (int u = 0; u < FB; ++u) first[u] = *reinterpret_cast<const float4*>(pa + (size_t)min(u, S - 1) * C);
+  for (int u = 0; u < FB; ++u) first[u] = *reinterpret_cast<const float4*>(pa + (size_t)min(u, R - 1) * C);
   __builtin_amdgcn_sched_barrier(0);   // (left to itself the compiler requests Wt first: + 0.7 us on the step)
   float bw[KG][4];
 #pragma unroll
@@ -507,7 +508,7 @@ __global__ __launch_bounds__(256) void m1_logits2_fold_kernel(const float* __res
   float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
 #pragma unroll
   for (int u = 0; u < FB; ++u) {
-    if (u < S) {
+    if (u < R) {
       z.x = fmaf(first[u].x, invP, z.x); z.y = fmaf(first[u].y, invP, z.y);
       z.z = fmaf(first[u].z, invP, z.z); z.w = fmaf(first[u].w, invP, z.w);
     }
@@ -983,8 +984,8 @@ static int launch_logits2(const float* z, const float* Wt, float* part_ws, int N
 
 // L1v2f, the 8-image form: two k-tile groups per 64-channel chunk and 8-image group while an instance covers half the
 // k-tiles (K <= 416), more groups of 13 beyond; the 16-image form: groups of 7 k-tiles
-bool m1_logits2_fold_supported(int N, int C, int S) {
-  return C % 64 == 0 && S >= 1 && S <= 16 && N >= 1 && N < 128;   // N >= 128: the nsub = 4 form keeps its finalize
+bool m1_logits2_fold_supported(int N, int C, int rows) {
+  return C % 64 == 0 && rows >= 1 && rows <= 16 && N >= 1 && N < 128;   // N >= 128: the nsub = 4 form keeps its finalize
 }
 
 static int launch_logits2_fold(const M1Fold& f, const float* Wt, float* zsave, float* part_ws, int N, int C, int K,
@@ -1002,8 +1003,12 @@ static int launch_logits2_fold(const M1Fold& f, const float* Wt, float* zsave, f
   if (tile16) {
     dim3 grid(C / 64, (ktiles + 6) / 7, (N + 15) / 16);
     const size_t shm = (size_t)4 * 7 * 256 * sizeof(float);   // 28 KB
-    hipLaunchKernelGGL((m1_logits2_fold_kernel<7, 16>), grid, dim3(256), shm, st, f.pacc, Wt, zsave, part_ws, N, C, K,
-                       f.S, f.P);
+    if (f.rows <= 8)
+      hipLaunchKernelGGL((m1_logits2_fold_kernel<7, 16, 8>), grid, dim3(256), shm, st, f.pacc, Wt, zsave, part_ws, N, C,
+                         K, f.rows, f.P);
+    else
+      hipLaunchKernelGGL((m1_logits2_fold_kernel<7, 16>), grid, dim3(256), shm, st, f.pacc, Wt, zsave, part_ws, N, C, K,
+                         f.rows, f.P);
     APA_LAUNCH_CHECK("m1_logits2_fold_kernel");
     return APA_OK;
   }
@@ -1011,7 +1016,7 @@ static int launch_logits2_fold(const M1Fold& f, const float* Wt, float* zsave, f
   const size_t shm = (size_t)4 * kg * 128 * sizeof(float);   // 26 KB at KG = 13
 #define APA_LF(KG)                                                                                             \
   hipLaunchKernelGGL((m1_logits2_fold_kernel<KG, 8>), grid, dim3(256), shm, st, f.pacc, Wt, zsave, part_ws, N, \
-                     C, K, f.S, f.P)
+                     C, K, f.rows, f.P)
   if (kg == 1) APA_LF(1);
   else if (kg == 2) APA_LF(2);
   else if (kg == 4) APA_LF(4);

@@ -144,6 +144,74 @@ __device__ __forceinline__ void load_chunk(uint4 (&xr)[PIX][VW], const T* xim, i
 // compiler keeps exact s_waitcnt counts and the next chunk's loads stay in flight -- and the
 // surplus slots repeat the block's last pixel: their weights are zero in every accumulation and
 // their dX stores rewrite the identical bytes.
+// --------------------------------------------------------------------------------------------
+// The paired form (PAIR) of the FORWARD pass, fp32 features.  The plan puts two logical blocks on every CU; as two
+// 256-thread blocks they cannot see each other, and each leaves a partial row of its own for the fold / finalize kernel
+// to read.  PAIR runs the two logical blocks
+// (n, 2s') and (n, 2s' + 1) of an even S as ONE 512-thread block: waves 0-3 ("quad 0") are the first, waves 4-7 the
+// second.  Each quad is a logical block exactly as before -- its pixels, its walk, its chunk order, its own ring,
+// its own exchange buffers, block_dots over its own four waves -- so att, the keep bits and pstat keep their
+// bits; only at the end quad 1 hands its channel accumulators to quad 0 through LDS and ONE row, acc0 + acc1,
+// leaves the CU (row n S/2 + s').  Same waves per CU, half the partial rows for the fold / finalize kernel to merge.
+// Measured (profiles/paired_rows_summary.md): the forward pass paired alone is 1.1 - 1.2 us of the fp32 headline step
+// and passes the project's rule; the backward pass paired alone does not (43.45 -> 43.22 us, rule 43.19) and adds
+// 0.24 us on top of the forward pairing, inside the spread: it keeps its 256-thread form.  bf16 features: the forward
+// pass is VALU-bound on the dropout hash and the keep bits, and a barrier shared by eight waves costs it about 1 us
+// (N = 32, K = 51): unpaired.
+// s_barrier counts the block's eight waves, so both quads have to execute the same number of barriers: a quad whose
+// run has fewer chunks than its partner's executes the missing ones behind its loop and nothing else.
+// Physical block b of nblk / 2 is pair xcd_remap(b, nblk / 2): with nblk a multiple of 16 (the benchmark batch) every
+// logical block stays on the XCD it had.
+// --------------------------------------------------------------------------------------------
+struct PairId { int blk, quad, wave, tid; };   // logical block, quad (0 / 1), wave and thread within the quad
+template <bool PAIR>
+__device__ __forceinline__ PairId pair_id(int nblk) {
+  PairId r;
+  if (PAIR) {
+    r.quad = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 8));   // wave-uniform: keep n, s and the ranges scalar
+    r.blk = 2 * xcd_remap(blockIdx.x, nblk >> 1) + r.quad;
+  } else {
+    r.quad = 0;
+    r.blk = xcd_remap(blockIdx.x, nblk);
+  }
+  r.tid = threadIdx.x & 255;
+  r.wave = r.tid >> 6;
+  return r;
+}
+// chunks of the partner quad's run (split s ^ 1 of the same image)
+template <int PIX>
+__device__ __forceinline__ int partner_chunks(int s, int P, int S) {
+  int b, e;
+  m1_pix_range(s ^ 1, P, S, b, e);
+  return (e - b + PIX - 1) / PIX;
+}
+// quad 1's EPL accumulators join quad 0's: row[c] = acc0[c] + acc1[c], one add per element, in quad 0's registers.
+// sm: C floats.  One barrier, executed by all eight waves.
+template <int EPL, int EPV>
+__device__ __forceinline__ void pair_merge(float (&acc)[EPL], float* sm, int quad, int cbase) {
+#pragma unroll
+  for (int j = 0; j < EPL / EPV; ++j) {
+#pragma unroll
+    for (int e = 0; e < EPV; e += 4) {
+      const int i = j * EPV + e;
+      if (quad == 1)
+        *reinterpret_cast<float4*>(sm + cbase + j * 64 * EPV + e) = make_float4(acc[i], acc[i + 1], acc[i + 2], acc[i + 3]);
+    }
+  }
+  __syncthreads();
+  if (quad == 0) {
+#pragma unroll
+    for (int j = 0; j < EPL / EPV; ++j) {
+#pragma unroll
+      for (int e = 0; e < EPV; e += 4) {
+        const int i = j * EPV + e;
+        const float4 o = *reinterpret_cast<const float4*>(sm + cbase + j * 64 * EPV + e);
+        acc[i] = acc[i] + o.x; acc[i + 1] = acc[i + 1] + o.y; acc[i + 2] = acc[i + 2] + o.z; acc[i + 3] = acc[i + 3] + o.w;
+      }
+    }
+  }
+}
+
 struct ChunkRange { int q0, np; };
 template <int PIX>
 __device__ __forceinline__ ChunkRange chunk_range(int p_begin, int p_end, int ch) {
@@ -298,8 +366,11 @@ __device__ __forceinline__ void fwd_chunk(FwdState<T, VW, PIX, FUSED, TRAIN>& st
 // plain instances do not have.  FUSED or not (the cfg 003 cached steps: att / dZ keep the batch position, only xim
 // moves), without RIN or SM and (backward) NODX only: the launchers below name every instance from m1_pool_form's tags.
 // SM: the softmax instances (fwd_chunk); forward: of the fused forms only, a map that is already final is pooled as it is.
-template <typename T, int VW, int PIX, bool FUSED, bool TRAIN, bool SM, bool RIN = false, bool GATHER = false>
-__global__ __launch_bounds__(256, 2) void m1s_pool_fwd_kernel(
+// PAIR: the 512-thread paired form above (fp32 only; never SM: the (m, l, acc) merge of two softmax blocks stays the finalize
+// kernel's); nblk is always the LOGICAL block count.
+template <typename T, int VW, int PIX, bool FUSED, bool TRAIN, bool SM, bool RIN = false, bool GATHER = false,
+          bool PAIR = false>
+__global__ __launch_bounds__(PAIR ? 512 : 256, PAIR ? 1 : 2) void m1s_pool_fwd_kernel(
     const T* __restrict__ X, int P, int S, int nblk, int act, const float* __restrict__ Wa,
     const float* __restrict__ ba, float* __restrict__ att, float* __restrict__ pacc,
     // ---- beyond the preload window ----
@@ -309,11 +380,15 @@ __global__ __launch_bounds__(256, 2) void m1s_pool_fwd_kernel(
   constexpr int EPL = VW * EPV;   // channels per lane
   constexpr int CW = EPL * 64;    // channels per wave
   constexpr int C = CW * 4;
-  __shared__ __attribute__((aligned(16))) float sm_x[APA_M1S_NB][256];   // one exchange buffer per ring slot
+  static_assert(!(PAIR && SM), "softmax instances keep one block per logical block");
+  __shared__ __attribute__((aligned(16))) float sm_xq[PAIR ? 2 : 1][APA_M1S_NB][256];   // per quad: one exchange buffer per ring slot
+  __shared__ __attribute__((aligned(16))) float sm_row[PAIR ? C : 4];
 
-  const unsigned blk = (unsigned)xcd_remap(blockIdx.x, nblk);
+  const PairId id = pair_id<PAIR>(nblk);
+  const unsigned blk = (unsigned)id.blk;
   const int n = (int)(blk / (unsigned)S), s = (int)(blk % (unsigned)S);
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int wave = id.wave, lane = threadIdx.x & 63;
+  float (*sm_x)[256] = sm_xq[id.quad];
   int p_begin, p_end;
   m1_pix_range(s, P, S, p_begin, p_end);
   const int npt = p_end - p_begin;
@@ -372,18 +447,26 @@ __global__ __launch_bounds__(256, 2) void m1s_pool_fwd_kernel(
     }
   }
 
-  float* pa = pacc + (size_t)blk * C + cbase;
+  if constexpr (PAIR) {
+    // the barriers of the partner's surplus chunks (FUSED: one per chunk, block_dots), then the hand-over
+    if (FUSED)
+      for (int ch = nchunk, nc = partner_chunks<PIX>(s, P, S); ch < nc; ++ch) __syncthreads();
+    pair_merge<EPL, EPV>(st.acc, sm_row, id.quad, cbase);
+  }
+  if (!PAIR || id.quad == 0) {
+    float* pa = pacc + (size_t)(PAIR ? blk >> 1 : blk) * C + cbase;
 #pragma unroll
-  for (int j = 0; j < VW; ++j) {
+    for (int j = 0; j < VW; ++j) {
 #pragma unroll
-    for (int e = 0; e < EPV; e += 4) {
-      const int i = j * EPV + e;
-      *reinterpret_cast<float4*>(pa + j * 64 * EPV + e) =
-          make_float4(st.acc[i], st.acc[i + 1], st.acc[i + 2], st.acc[i + 3]);
+      for (int e = 0; e < EPV; e += 4) {
+        const int i = j * EPV + e;
+        *reinterpret_cast<float4*>(pa + j * 64 * EPV + e) =
+            make_float4(st.acc[i], st.acc[i + 1], st.acc[i + 2], st.acc[i + 3]);
+      }
     }
   }
-  m1_gather_note(n, s == 0 && threadIdx.x == 0, g);
-  if (threadIdx.x == 0) {
+  m1_gather_note(n, s == 0 && id.tid == 0, g);
+  if (id.tid == 0) {
     pstat[blk * 4 + 0] = (FUSED && SM) ? st.m_run : 0.f;
     pstat[blk * 4 + 1] = st.l_run;
     pstat[blk * 4 + 2] = st.a_sum;
@@ -674,22 +757,28 @@ static int launch_fwd_t(const M1Call& c, const M1Fwd& io) {
   if (M1Trace* t = m1_trace()) { t->pool_fwd = M1_POOL_STREAM; t->fwd_w = VW; t->fwd_pix = PIX; }
   m1_pool_form(c, [&](auto F, auto TR, auto G) {
     constexpr bool f = decltype(F)::value, t = decltype(TR)::value, g = decltype(G)::value;
-    auto arm = [&](auto SM) {
-      constexpr bool sm = decltype(SM)::value;
-      auto k = m1s_pool_fwd_kernel<T, VW, PIX, f, t, sm, false, g>;
+    auto arm = [&](auto SM, auto PR) {
+      constexpr bool sm = decltype(SM)::value, pr = decltype(PR)::value;
+      auto k = m1s_pool_fwd_kernel<T, VW, PIX, f, t, sm, false, g, pr>;
       // relu on the input: instantiated for the plain fused map only (m1_call_fill: relu_input is fused, never gathered)
       if constexpr (f && !g) {
-        if (c.relu_input) k = m1s_pool_fwd_kernel<T, VW, PIX, true, t, sm, true>;
+        if (c.relu_input) k = m1s_pool_fwd_kernel<T, VW, PIX, true, t, sm, true, false, pr>;
       }
       return k;
     };
-    auto kernel = arm(std::false_type{});
+    const std::true_type yes; const std::false_type no;
+    auto kernel = arm(no, no);
+    // the paired form (m1_call_fill: c.nrows): fp32 features, every instance but the softmax ones
+    const bool pair = c.paired();
+    if constexpr (sizeof(T) == 4) {
+      if (pair) kernel = arm(no, yes);
+    }
     // softmax: plain fused maps only (m1_call_fill: pool_act is the identity on a map that is already final, and both
     // forms a gathered call can have -- the cache form and the cfg 003 steps' pose form -- exclude softmax)
     if constexpr (f && !g) {
-      if (c.pool_act == M1_ACT_SOFTMAX) kernel = arm(std::true_type{});
+      if (c.pool_act == M1_ACT_SOFTMAX) kernel = arm(yes, no);
     }
-    launch_ev(kernel, dim3(c.pl.nblk), dim3(256), 0, c.st, c.ev0, c.ev1, static_cast<const T*>(io.X), c.P, c.pl.S,
+    launch_ev(kernel, dim3(c.nrows), dim3(pair ? 512 : 256), 0, c.st, c.ev0, c.ev1, static_cast<const T*>(io.X), c.P, c.pl.S,
               c.pl.nblk, c.pool_act, io.Wa, io.ba, io.att, c.pacc, c.pstat, c.inv_keep, c.key.thresh, c.key.seed,
               c.key.offset, c.key.offset_dev, c.maskbits, m1_gather_arg<g>(c));
     return APA_OK;
