@@ -4,8 +4,7 @@
 #include <stdio.h>
 
 #include "../../include/apa_pose_cache.h"
-#include "apa_internal.h"
-#include "../../include/apa_clip_epoch.h"
+#include "apa_capi.h"
 
 namespace apa {
 
@@ -528,6 +527,69 @@ extern "C" int apa_attn_head_train_step_rank(const apa_rank_maps* rank, const vo
   return rc != APA_OK ? rc : rank_bwd_run(d, rkb, b);
 }
 
+// ---- a resident feature cache read by image index (apa.h: apa_feature_cache) -----------------------------------------
+// What a *_cached call refuses about its descriptor and about the forms a cache cannot have, each reason by name and
+// before anything is queued; what remains (pointers, workspace, the FP8 arm's own limits) is pool_check's as ever.
+// backward: a backward call or a training step.  per_class: false for the epoch calls, which keep refusing M != 1 (their
+// update rewrites no weight images, which the per-class deploy path relies on) while the step they loop over serves it.
+static int cache_check(const char* fn, const apa_feature_cache* fc, const PoolCall& d, const void* X, const void* Xatt,
+                       bool topdown, bool backward, const void* dX, bool per_class = true) {
+  if (!fc || !fc->index) {
+    set_error("%s: null apa_feature_cache / index pointer", fn);
+    return APA_ERR_INVALID_ARG;
+  }
+  if (reinterpret_cast<uintptr_t>(fc->index) & 3) {
+    set_error("%s: apa_feature_cache.index must be 4-byte aligned", fn);
+    return APA_ERR_INVALID_ARG;
+  }
+  if (fc->cache_images < 1) {
+    set_error("%s: apa_feature_cache.cache_images=%d: a cache holds at least one image", fn, fc->cache_images);
+    return APA_ERR_INVALID_ARG;
+  }
+  const int rc = check_common(fn, d, true);
+  if (rc != APA_OK) return rc;
+  if (dX) {
+    set_error("%s: a feature cache has no gradient: dX must be NULL", fn);
+    return APA_ERR_INVALID_ARG;
+  }
+  if (backward && !(d.flags & APA_FLAG_FROZEN_INPUT)) {
+    set_error("%s: a feature cache is frozen: a backward call or a training step needs APA_FLAG_FROZEN_INPUT", fn);
+    return APA_ERR_INVALID_ARG;
+  }
+  if (const char* why = cache_form_why(d, X, Xatt, topdown, false, per_class)) {   // (FP8's own limits: pool_check)
+    if (per_class && cache_per_class(d))
+      set_error("%s: a feature cache does not serve %s: with per-class maps the gathered kernels feed the fused bf16 "
+                "route (K <= 64) with attention from the map itself", fn, why);
+    else
+      set_error("%s: a feature cache does not serve %s: the gathered kernels feed the fused class-agnostic head with "
+                "identity or relu attention", fn, why);
+    return APA_ERR_UNSUPPORTED;
+  }
+  if (d.M != 1 && (reinterpret_cast<uintptr_t>(X) & 15)) {
+    set_error("%s: a feature cache of per-class maps must be 16-byte aligned (the fused route fetches its rows by "
+              "LDS-DMA)", fn);
+    return APA_ERR_INVALID_ARG;
+  }
+  return APA_OK;
+}
+
+// labels_cached: `labels` is [T]; the loss reads the [N] copy the forward pooling pass leaves in the workspace
+static const int64_t* cached_labels(PoolCall* d, const apa_feature_cache* fc, const int64_t* labels) {
+  if (!fc->labels_cached || !labels || !d->ws) return labels;
+  d->fc_labels = labels;
+  if (d->M != 1) return pc_gathered_labels(d->ws, d->N, d->P, d->C, d->Ca, d->K, d->dtype);
+  return m1_gathered_labels(d->ws, m1_plan(d->N, d->P, d->C, d->Ca, d->K));
+}
+
+// labels_cached reads a per-FRAME table through the index; a clip's or a sigmoid row's labels are per clip / per row
+static int cached_clip_labels_check(const char* fn, const apa_feature_cache* fc, bool ml, bool clip) {
+  if (!fc->labels_cached || (!ml && !clip)) return APA_OK;
+  set_error("%s: apa_feature_cache.labels_cached = 1 is not served together with %s: such labels are per clip or per "
+            "row and come from the sampler (apa_sample_clip_frames), not through the frame index", fn,
+            ml ? "an apa_multilabel" : "an apa_clip_pool");
+  return APA_ERR_INVALID_ARG;
+}
+
 // ---- the one-call training steps ------------------------------------------------------------------------------------
 // The loss of a step.  ml: a sigmoid action loss on ml->labels (checked by check_multilabel; `labels` unused), null:
 // the softmax cross-entropy on the integer `labels`.  clips: the loss is taken on the rows pooled over each clip's frames
@@ -674,13 +736,60 @@ static int head_step_run(PoolCall d, const StepLoss& L, const M1Fwd& f, const M1
   return attn_pool_bwd(d, b, xf.done && !xf.finished ? &xf : nullptr);
 }
 
-// fn: the entry point's name for the refusals
-static int head_step(const char* fn, const PoolCall& d, const StepLoss& L, const M1Fwd& f, const M1Bwd& b) {
-  size_t pool_bytes = 0;
-  const int rc = head_step_check(fn, d, L, f.logits, &pool_bytes);
-  return rc != APA_OK ? rc : head_step_run(d, L, f, b, pool_bytes);
+// The request (apa_capi.h: HeadTrainStep) as the calls the step is made of
+struct HeadTrainCall { PoolCall d; StepLoss L; M1Fwd f; M1Bwd b; size_t pool_bytes = 0; };
+
+// Everything a step refuses above the two pooling halves' own checks, in ONE order for every entry point, in fn's name
+// and with nothing launched:
+//   1. the cache: its descriptor and the forms it cannot have (cache_check; per_class: its argument);
+//   2. the sigmoid loss (check_multilabel);
+//   3. a cache's labels_cached beside labels that are per clip or per row (cached_clip_labels_check);
+//   4. the loss's pointers -- on clips with the clip itself, the shape and the workspace (head_step_check).
+// A part the request does not take is skipped.  (cached_labels: the identity unless labels_cached, which 3. leaves to
+// the flat softmax step alone.)
+static int head_train_call(const char* fn, const HeadTrainStep& r, bool per_class, HeadTrainCall* c) {
+  c->d = fp8_served(pool_call(r.dims, r.flags, r.keep_prob, r.seed, r.offset, r.ws, r.ws_bytes, r.stream, r.hooks));
+  c->f = M1Fwd{r.X, r.Xatt, r.Wa, r.ba, r.Wt, r.bt, r.logits, r.att, r.zsave, r.abar};
+  c->b = M1Bwd{r.X, r.Xatt, r.Wa, r.Wt, r.bt, r.att, r.zsave, r.abar, r.G, r.dX, r.dXatt, r.dWa, r.dba, r.dWt, r.dbt};
+  int rc = APA_OK;
+  if (r.cached && (rc = cache_check(fn, r.cache, c->d, r.X, r.Xatt, false, true, r.dX, per_class)) != APA_OK) return rc;
+  if (r.sigmoid && (rc = check_multilabel(fn, r.ml)) != APA_OK) return rc;
+  const int64_t* labels = r.sigmoid ? nullptr : r.labels;
+  if (r.cached) {
+    if ((rc = cached_clip_labels_check(fn, r.cache, r.sigmoid, r.clips)) != APA_OK) return rc;
+    c->d.fc = r.cache;
+    labels = cached_labels(&c->d, r.cache, labels);
+  }
+  c->L = StepLoss{r.sigmoid ? r.ml : nullptr, labels, r.clips, r.clip, r.loss_wt, r.grad_scale, r.loss, r.G};
+  return head_step_check(fn, c->d, c->L, r.logits, &c->pool_bytes);
 }
 
+int apa::head_train_step(const char* fn, const HeadTrainStep& r) {
+  HeadTrainCall c;
+  const int rc = head_train_call(fn, r, true, &c);
+  return rc != APA_OK ? rc : head_step_run(c.d, c.L, c.f, c.b, c.pool_bytes);
+}
+
+// the pooling call's refusals and the M == 1 paths' own (m1_call_fill) for one half; nothing is launched
+static int pool_half_check(const PoolCall& d, const M1Fwd* f, const M1Bwd* b) {
+  const int rc = pool_check(d, f, b);
+  if (rc != APA_OK) return rc;
+  M1Call c;
+  return m1_call_fill(c, d, f, b);
+}
+
+// (per-class maps on a cache: refused here although the step serves them -- an epoch's update rewrites no weight images)
+int apa::head_train_check(const char* fn, const HeadTrainStep& r) {
+  HeadTrainCall c;
+  int rc = head_train_call(fn, r, false, &c);
+  if (rc != APA_OK) return rc;
+  c.d.ws_bytes = c.pool_bytes;
+  if ((rc = pool_half_check(c.d, &c.f, nullptr)) != APA_OK) return rc;
+  c.d.flags |= APA_FLAG_WS_FROM_FWD;
+  return pool_half_check(c.d, nullptr, &c.b);
+}
+
+// The six entry points: pack the request (the flat list in its order, then the parts the entry point takes), one call.
 extern "C" int apa_attn_head_train_step_ex(const apa_hooks* hooks, const void* X, const void* Xatt, const float* Wa,
                                            const float* ba, const float* Wt, const float* bt, const int64_t* labels,
                                            float loss_wt, float grad_scale, float* logits, float* att, float* zsave,
@@ -688,12 +797,10 @@ extern "C" int apa_attn_head_train_step_ex(const apa_hooks* hooks, const void* X
                                            float* dba, float* dWt, float* dbt, void* ws, size_t ws_bytes, int N, int P,
                                            int C, int Ca, int K, int M, unsigned flags, float keep_prob, uint64_t seed,
                                            uint64_t offset, int dtype, void* stream) {
-  return head_step("apa_attn_head_train_step",
-                   fp8_served(pool_call({N, P, C, Ca, K, M, dtype}, flags, keep_prob, seed, offset, ws, ws_bytes, stream,
-                                        hooks)),
-                   StepLoss{nullptr, labels, false, nullptr, loss_wt, grad_scale, loss, G},
-                   M1Fwd{X, Xatt, Wa, ba, Wt, bt, logits, att, zsave, abar},
-                   M1Bwd{X, Xatt, Wa, Wt, bt, att, zsave, abar, G, dX, dXatt, dWa, dba, dWt, dbt});
+  return head_train_step("apa_attn_head_train_step",
+                         {X, Xatt, Wa, ba, Wt, bt, labels, loss_wt, grad_scale, logits, att, zsave, abar, loss, G, dX,
+                          dXatt, dWa, dba, dWt, dbt, ws, ws_bytes, {N, P, C, Ca, K, M, dtype}, flags, keep_prob, seed,
+                          offset, stream, hooks});
 }
 
 extern "C" int apa_attn_head_train_step(const void* X, const void* Xatt, const float* Wa, const float* ba,
@@ -716,12 +823,10 @@ extern "C" int apa_attn_head_train_step_clips(const apa_clip_pool* clip, const a
                                               float* dbt, void* ws, size_t ws_bytes, int N, int P, int C, int Ca, int K,
                                               int M, unsigned flags, float keep_prob, uint64_t seed, uint64_t offset,
                                               int dtype, void* stream) {
-  return head_step("apa_attn_head_train_step_clips",
-                   fp8_served(pool_call({N, P, C, Ca, K, M, dtype}, flags, keep_prob, seed, offset, ws, ws_bytes, stream,
-                                        hooks)),
-                   StepLoss{nullptr, labels, true, clip, loss_wt, grad_scale, loss, G},
-                   M1Fwd{X, Xatt, Wa, ba, Wt, bt, logits, att, zsave, abar},
-                   M1Bwd{X, Xatt, Wa, Wt, bt, att, zsave, abar, G, dX, dXatt, dWa, dba, dWt, dbt});
+  HeadTrainStep r{X, Xatt, Wa, ba, Wt, bt, labels, loss_wt, grad_scale, logits, att, zsave, abar, loss, G, dX, dXatt, dWa,
+                  dba, dWt, dbt, ws, ws_bytes, {N, P, C, Ca, K, M, dtype}, flags, keep_prob, seed, offset, stream, hooks};
+  r.clip = clip; r.clips = true;   // (a null clip is clip_step_check's to report)
+  return head_train_step("apa_attn_head_train_step_clips", r);
 }
 
 // clip == NULL: the flat step, apa_attn_head_train_step_ex with the loss exchanged
@@ -734,14 +839,45 @@ extern "C" int apa_attn_head_train_step_multilabel(const apa_multilabel* ml, con
                                                    void* ws, size_t ws_bytes, int N, int P, int C, int Ca, int K, int M,
                                                    unsigned flags, float keep_prob, uint64_t seed, uint64_t offset,
                                                    int dtype, void* stream) {
-  const int rc = check_multilabel("apa_attn_head_train_step_multilabel", ml);
-  if (rc != APA_OK) return rc;
-  return head_step("apa_attn_head_train_step_multilabel",
-                   fp8_served(pool_call({N, P, C, Ca, K, M, dtype}, flags, keep_prob, seed, offset, ws, ws_bytes, stream,
-                                        hooks)),
-                   StepLoss{ml, nullptr, clip != nullptr, clip, loss_wt, grad_scale, loss, G},
-                   M1Fwd{X, Xatt, Wa, ba, Wt, bt, logits, att, zsave, abar},
-                   M1Bwd{X, Xatt, Wa, Wt, bt, att, zsave, abar, G, dX, dXatt, dWa, dba, dWt, dbt});
+  HeadTrainStep r{X, Xatt, Wa, ba, Wt, bt, nullptr, loss_wt, grad_scale, logits, att, zsave, abar, loss, G, dX, dXatt, dWa,
+                  dba, dWt, dbt, ws, ws_bytes, {N, P, C, Ca, K, M, dtype}, flags, keep_prob, seed, offset, stream, hooks};
+  r.ml = ml; r.sigmoid = true;   // (a null ml is check_multilabel's to report)
+  r.clip = clip; r.clips = clip != nullptr;
+  return head_train_step("apa_attn_head_train_step_multilabel", r);
+}
+
+extern "C" int apa_attn_head_train_step_cached(const apa_feature_cache* cache, const apa_hooks* hooks, const void* X,
+                                               const void* Xatt, const float* Wa, const float* ba, const float* Wt,
+                                               const float* bt, const int64_t* labels, float loss_wt, float grad_scale,
+                                               float* logits, float* att, float* zsave, float* abar, float* loss,
+                                               float* G, void* dX, void* dXatt, float* dWa, float* dba, float* dWt,
+                                               float* dbt, void* ws, size_t ws_bytes, int N, int P, int C, int Ca, int K,
+                                               int M, unsigned flags, float keep_prob, uint64_t seed, uint64_t offset,
+                                               int dtype, void* stream) {
+  HeadTrainStep r{X, Xatt, Wa, ba, Wt, bt, labels, loss_wt, grad_scale, logits, att, zsave, abar, loss, G, dX, dXatt, dWa,
+                  dba, dWt, dbt, ws, ws_bytes, {N, P, C, Ca, K, M, dtype}, flags, keep_prob, seed, offset, stream, hooks};
+  r.cache = cache; r.cached = true;
+  return head_train_step("apa_attn_head_train_step_cached", r);
+}
+
+// clips and the sigmoid losses from a frame cache; ml == NULL && clip == NULL: apa_attn_head_train_step_cached itself,
+// by name too
+extern "C" int apa_attn_head_train_step_cached_clips(const apa_feature_cache* cache, const apa_multilabel* ml,
+                                                     const apa_clip_pool* clip, const apa_hooks* hooks, const void* X,
+                                                     const void* Xatt, const float* Wa, const float* ba,
+                                                     const float* Wt, const float* bt, const int64_t* labels,
+                                                     float loss_wt, float grad_scale, float* logits, float* att,
+                                                     float* zsave, float* abar, float* loss, float* G, void* dX,
+                                                     void* dXatt, float* dWa, float* dba, float* dWt, float* dbt,
+                                                     void* ws, size_t ws_bytes, int N, int P, int C, int Ca, int K,
+                                                     int M, unsigned flags, float keep_prob, uint64_t seed,
+                                                     uint64_t offset, int dtype, void* stream) {
+  HeadTrainStep r{X, Xatt, Wa, ba, Wt, bt, labels, loss_wt, grad_scale, logits, att, zsave, abar, loss, G, dX, dXatt, dWa,
+                  dba, dWt, dbt, ws, ws_bytes, {N, P, C, Ca, K, M, dtype}, flags, keep_prob, seed, offset, stream, hooks};
+  r.cache = cache; r.cached = true;
+  r.ml = ml; r.sigmoid = ml != nullptr;
+  r.clip = clip; r.clips = clip != nullptr;
+  return head_train_step(ml || clip ? "apa_attn_head_train_step_cached_clips" : "apa_attn_head_train_step_cached", r);
 }
 
 // ---- the one-call steps of the pose-regularised head (cfg 003) ------------------------------------------------------
@@ -755,7 +891,6 @@ extern "C" int apa_attn_head_train_step_multilabel(const apa_multilabel* ml, con
 // W2T_bf16) are not read there.  A sigmoid loss still rides in the logits reducer inside head_step.
 // fc (apa_pose_cache.h: the cached step, pose_cache_check passed): io->X is a T-image cache.  The launches that read X
 // -- the Ppre product, both pooling passes, the dW1 product -- follow the index; everything else has the batch shape
-static const int64_t* cached_labels(PoolCall* d, const apa_feature_cache* fc, const int64_t* labels);
 static int pose_attn_step(const char* fn, const apa_pose_attn_step_io* io, PoolCall d, StepLoss L, int J,
                           const apa_feature_cache* fc = nullptr) {
   if (!io) {
@@ -997,18 +1132,63 @@ static int attn_head_eval_clips(const char* fn, const apa_clip_pool* clip, int k
                             d.K, d.st);
 }
 
+// The request (apa_capi.h: HeadEvalStep) as the call the step is made of
+struct HeadEvalCall { PoolCall d; M1Fwd f; const int64_t* labels = nullptr; };
+
+// Everything an evaluation step refuses above the pooling call's own checks, in ONE order, in fn's name, nothing
+// launched:
+//   1. the cache (cache_check; per_class: its argument), a clip handed to a cached step that takes none, labels_cached
+//      beside a clip (cached_clip_labels_check);
+//   2. the scores, and the clip with them (eval_scores_check).
+// The plain step (no cache, no clip pool taken) has none of these: attn_head_eval words its own refusals.
+static int head_eval_call(const char* fn, const HeadEvalStep& r, bool per_class, HeadEvalCall* c) {
+  c->d = fp8_served(pool_call(r.dims, r.flags, 1.0f, 0, 0, r.ws, r.ws_bytes, r.stream));
+  c->f = M1Fwd{r.X, r.Xatt, r.Wa, r.ba, r.Wt, r.bt, r.logits, r.att, r.zsave, r.abar};
+  c->labels = r.labels;
+  if (!r.cached && !r.clips) return APA_OK;
+  int rc = APA_OK;
+  if (r.cached) {
+    if ((rc = cache_check(fn, r.cache, c->d, r.X, r.Xatt, false, false, nullptr, per_class)) != APA_OK) return rc;
+    if (r.clip && !r.clips) {
+      set_error("%s: a feature cache does not serve clips: flat batches only (clip must be NULL)", fn);
+      return APA_ERR_UNSUPPORTED;
+    }
+    if ((rc = cached_clip_labels_check(fn, r.cache, false, r.clips)) != APA_OK) return rc;
+  }
+  rc = eval_scores_check(fn, r.clip, r.scores_kind, r.dims.N, r.dims.K, r.logits, r.labels, r.loss, r.probs, r.pred);
+  if (rc != APA_OK || !r.cached) return rc;
+  c->d.fc = r.cache;
+  c->labels = cached_labels(&c->d, r.cache, r.labels);
+  return APA_OK;
+}
+
+// (the plain step: scores_kind is the softmax and there is no clip, so attn_head_eval_clips IS attn_head_eval)
+int apa::head_eval_step(const char* fn, const HeadEvalStep& r) {
+  HeadEvalCall c;
+  const int rc = head_eval_call(fn, r, true, &c);
+  return rc != APA_OK ? rc
+                      : attn_head_eval_clips(fn, r.clip, r.scores_kind, c.d, c.f, c.labels, r.loss, r.probs, r.pred);
+}
+
+// (per-class maps on a cache: refused with the training epoch's, so that the pair stays one interface)
+int apa::head_eval_check(const char* fn, const HeadEvalStep& r) {
+  HeadEvalCall c;
+  const int rc = head_eval_call(fn, r, false, &c);
+  if (rc != APA_OK) return rc;
+  c.d.flags &= ~(unsigned)APA_FLAG_TRAIN;
+  return pool_half_check(c.d, &c.f, nullptr);
+}
+
 extern "C" int apa_attn_head_eval_step_clips(const apa_clip_pool* clip, int scores_kind, const void* X,
                                              const void* Xatt, const float* Wa, const float* ba, const float* Wt,
                                              const float* bt, const int64_t* labels, float* logits, float* att,
                                              float* zsave, float* abar, float* loss, float* probs, int64_t* pred,
                                              void* ws, size_t ws_bytes, int N, int P, int C, int Ca, int K, int M,
                                              unsigned flags, int dtype, void* stream) {
-  const char* fn = "apa_attn_head_eval_step_clips";
-  const int rc = eval_scores_check(fn, clip, scores_kind, N, K, logits, labels, loss, probs, pred);
-  if (rc != APA_OK) return rc;
-  return attn_head_eval_clips(fn, clip, scores_kind,
-                              fp8_served(pool_call({N, P, C, Ca, K, M, dtype}, flags, 1.0f, 0, 0, ws, ws_bytes, stream)),
-                              M1Fwd{X, Xatt, Wa, ba, Wt, bt, logits, att, zsave, abar}, labels, loss, probs, pred);
+  HeadEvalStep r{X, Xatt, Wa, ba, Wt, bt, labels, logits, att, zsave, abar, loss, probs, pred, ws, ws_bytes,
+                 {N, P, C, Ca, K, M, dtype}, flags, stream, scores_kind};
+  r.clip = clip; r.clips = true;
+  return head_eval_step("apa_attn_head_eval_step_clips", r);
 }
 
 extern "C" int apa_attn_head_eval_step(const void* X, const void* Xatt, const float* Wa, const float* ba,
@@ -1016,64 +1196,42 @@ extern "C" int apa_attn_head_eval_step(const void* X, const void* Xatt, const fl
                                        float* att, float* zsave, float* abar, float* loss, float* probs, int64_t* pred,
                                        void* ws, size_t ws_bytes, int N, int P, int C, int Ca, int K, int M,
                                        unsigned flags, int dtype, void* stream) {
-  return attn_head_eval(fp8_served(pool_call({N, P, C, Ca, K, M, dtype}, flags, 1.0f, 0, 0, ws, ws_bytes, stream)),
-                        M1Fwd{X, Xatt, Wa, ba, Wt, bt, logits, att, zsave, abar}, labels, loss, probs, pred);
+  return head_eval_step("apa_attn_head_eval_step",
+                        {X, Xatt, Wa, ba, Wt, bt, labels, logits, att, zsave, abar, loss, probs, pred, ws, ws_bytes,
+                         {N, P, C, Ca, K, M, dtype}, flags, stream});
 }
 
-// ---- a resident feature cache read by image index (apa.h: apa_feature_cache) -----------------------------------------
-// What a *_cached call refuses about its descriptor and about the forms a cache cannot have, each reason by name and
-// before anything is queued; what remains (pointers, workspace, the FP8 arm's own limits) is pool_check's as ever.
-// backward: a backward call or a training step.  per_class: false for the epoch calls, which keep refusing M != 1 (their
-// update rewrites no weight images, which the per-class deploy path relies on) while the step they loop over serves it.
-static int cache_check(const char* fn, const apa_feature_cache* fc, const PoolCall& d, const void* X, const void* Xatt,
-                       bool topdown, bool backward, const void* dX, bool per_class = true) {
-  if (!fc || !fc->index) {
-    set_error("%s: null apa_feature_cache / index pointer", fn);
-    return APA_ERR_INVALID_ARG;
-  }
-  if (reinterpret_cast<uintptr_t>(fc->index) & 3) {
-    set_error("%s: apa_feature_cache.index must be 4-byte aligned", fn);
-    return APA_ERR_INVALID_ARG;
-  }
-  if (fc->cache_images < 1) {
-    set_error("%s: apa_feature_cache.cache_images=%d: a cache holds at least one image", fn, fc->cache_images);
-    return APA_ERR_INVALID_ARG;
-  }
-  const int rc = check_common(fn, d, true);
-  if (rc != APA_OK) return rc;
-  if (dX) {
-    set_error("%s: a feature cache has no gradient: dX must be NULL", fn);
-    return APA_ERR_INVALID_ARG;
-  }
-  if (backward && !(d.flags & APA_FLAG_FROZEN_INPUT)) {
-    set_error("%s: a feature cache is frozen: a backward call or a training step needs APA_FLAG_FROZEN_INPUT", fn);
-    return APA_ERR_INVALID_ARG;
-  }
-  if (const char* why = cache_form_why(d, X, Xatt, topdown, false, per_class)) {   // (FP8's own limits: pool_check)
-    if (per_class && cache_per_class(d))
-      set_error("%s: a feature cache does not serve %s: with per-class maps the gathered kernels feed the fused bf16 "
-                "route (K <= 64) with attention from the map itself", fn, why);
-    else
-      set_error("%s: a feature cache does not serve %s: the gathered kernels feed the fused class-agnostic head with "
-                "identity or relu attention", fn, why);
-    return APA_ERR_UNSUPPORTED;
-  }
-  if (d.M != 1 && (reinterpret_cast<uintptr_t>(X) & 15)) {
-    set_error("%s: a feature cache of per-class maps must be 16-byte aligned (the fused route fetches its rows by "
-              "LDS-DMA)", fn);
-    return APA_ERR_INVALID_ARG;
-  }
-  return APA_OK;
+// flat batches, softmax or sigmoid scores: everything behind the pooling pass never sees X.  `clip` is there to be
+// refused by name.
+extern "C" int apa_attn_head_eval_step_cached(const apa_feature_cache* cache, const apa_clip_pool* clip,
+                                              int scores_kind, const void* X, const void* Xatt, const float* Wa,
+                                              const float* ba, const float* Wt, const float* bt, const int64_t* labels,
+                                              float* logits, float* att, float* zsave, float* abar, float* loss,
+                                              float* probs, int64_t* pred, void* ws, size_t ws_bytes, int N, int P,
+                                              int C, int Ca, int K, int M, unsigned flags, int dtype, void* stream) {
+  HeadEvalStep r{X, Xatt, Wa, ba, Wt, bt, labels, logits, att, zsave, abar, loss, probs, pred, ws, ws_bytes,
+                 {N, P, C, Ca, K, M, dtype}, flags, stream, scores_kind};
+  r.cache = cache; r.cached = true;
+  r.clip = clip;
+  return head_eval_step("apa_attn_head_eval_step_cached", r);
 }
 
-// labels_cached: `labels` is [T]; the loss reads the [N] copy the forward pooling pass leaves in the workspace
-static const int64_t* cached_labels(PoolCall* d, const apa_feature_cache* fc, const int64_t* labels) {
-  if (!fc->labels_cached || !labels || !d->ws) return labels;
-  d->fc_labels = labels;
-  if (d->M != 1) return pc_gathered_labels(d->ws, d->N, d->P, d->C, d->Ca, d->K, d->dtype);
-  return m1_gathered_labels(d->ws, m1_plan(d->N, d->P, d->C, d->Ca, d->K));
+// clips from a frame cache; clip == NULL: apa_attn_head_eval_step_cached itself, by name too
+extern "C" int apa_attn_head_eval_step_cached_clips(const apa_feature_cache* cache, const apa_clip_pool* clip,
+                                                    int scores_kind, const void* X, const void* Xatt, const float* Wa,
+                                                    const float* ba, const float* Wt, const float* bt,
+                                                    const int64_t* labels, float* logits, float* att, float* zsave,
+                                                    float* abar, float* loss, float* probs, int64_t* pred, void* ws,
+                                                    size_t ws_bytes, int N, int P, int C, int Ca, int K, int M,
+                                                    unsigned flags, int dtype, void* stream) {
+  HeadEvalStep r{X, Xatt, Wa, ba, Wt, bt, labels, logits, att, zsave, abar, loss, probs, pred, ws, ws_bytes,
+                 {N, P, C, Ca, K, M, dtype}, flags, stream, scores_kind};
+  r.cache = cache; r.cached = true;
+  r.clip = clip; r.clips = clip != nullptr;
+  return head_eval_step(clip ? "apa_attn_head_eval_step_cached_clips" : "apa_attn_head_eval_step_cached", r);
 }
 
+// ---- the pooling calls on a resident feature cache (apa.h: apa_feature_cache; cache_check above) ---------------------
 extern "C" int apa_attn_pool_fwd_cached(const apa_feature_cache* cache, const apa_hooks* hooks, const void* X,
                                         const void* Xatt, const float* Wa, const float* ba, const float* Wt,
                                         const float* bt, float* logits, float* att, float* zsave, float* abar,
@@ -1102,450 +1260,6 @@ extern "C" int apa_attn_pool_bwd_cached(const apa_feature_cache* cache, const ap
   if (rc != APA_OK) return rc;
   d.fc = cache;
   return attn_pool_bwd(d, M1Bwd{X, Xatt, Wa, Wt, bt, att, zsave, abar, G, dX, dXatt, dWa, dba, dWt, dbt}, nullptr);
-}
-
-extern "C" int apa_attn_head_train_step_cached(const apa_feature_cache* cache, const apa_hooks* hooks, const void* X,
-                                               const void* Xatt, const float* Wa, const float* ba, const float* Wt,
-                                               const float* bt, const int64_t* labels, float loss_wt, float grad_scale,
-                                               float* logits, float* att, float* zsave, float* abar, float* loss,
-                                               float* G, void* dX, void* dXatt, float* dWa, float* dba, float* dWt,
-                                               float* dbt, void* ws, size_t ws_bytes, int N, int P, int C, int Ca, int K,
-                                               int M, unsigned flags, float keep_prob, uint64_t seed, uint64_t offset,
-                                               int dtype, void* stream) {
-  const char* fn = "apa_attn_head_train_step_cached";
-  PoolCall d = fp8_served(pool_call({N, P, C, Ca, K, M, dtype}, flags, keep_prob, seed, offset, ws, ws_bytes, stream,
-                                    hooks));
-  const int rc = cache_check(fn, cache, d, X, Xatt, false, true, dX);
-  if (rc != APA_OK) return rc;
-  d.fc = cache;
-  const int64_t* lab = cached_labels(&d, cache, labels);
-  return head_step(fn, d, StepLoss{nullptr, lab, false, nullptr, loss_wt, grad_scale, loss, G},
-                   M1Fwd{X, Xatt, Wa, ba, Wt, bt, logits, att, zsave, abar},
-                   M1Bwd{X, Xatt, Wa, Wt, bt, att, zsave, abar, G, dX, dXatt, dWa, dba, dWt, dbt});
-}
-
-// flat batches, softmax or sigmoid scores: everything behind the pooling pass never sees X
-extern "C" int apa_attn_head_eval_step_cached(const apa_feature_cache* cache, const apa_clip_pool* clip,
-                                              int scores_kind, const void* X, const void* Xatt, const float* Wa,
-                                              const float* ba, const float* Wt, const float* bt, const int64_t* labels,
-                                              float* logits, float* att, float* zsave, float* abar, float* loss,
-                                              float* probs, int64_t* pred, void* ws, size_t ws_bytes, int N, int P,
-                                              int C, int Ca, int K, int M, unsigned flags, int dtype, void* stream) {
-  const char* fn = "apa_attn_head_eval_step_cached";
-  PoolCall d = fp8_served(pool_call({N, P, C, Ca, K, M, dtype}, flags, 1.0f, 0, 0, ws, ws_bytes, stream));
-  int rc = cache_check(fn, cache, d, X, Xatt, false, false, nullptr);
-  if (rc != APA_OK) return rc;
-  if (clip) {
-    set_error("%s: a feature cache does not serve clips: flat batches only (clip must be NULL)", fn);
-    return APA_ERR_UNSUPPORTED;
-  }
-  if ((rc = eval_scores_check(fn, nullptr, scores_kind, N, K, logits, labels, loss, probs, pred)) != APA_OK) return rc;
-  d.fc = cache;
-  const int64_t* lab = cached_labels(&d, cache, labels);
-  return attn_head_eval_clips(fn, nullptr, scores_kind, d, M1Fwd{X, Xatt, Wa, ba, Wt, bt, logits, att, zsave, abar}, lab,
-                              loss, probs, pred);
-}
-
-// ---- clips and the sigmoid losses from a frame cache (apa.h: the *_cached_clips steps) --------------------------------
-// labels_cached reads a per-FRAME table through the index; a clip's or a sigmoid row's labels are per clip / per row
-static int cached_clip_labels_check(const char* fn, const apa_feature_cache* fc, bool ml, bool clip) {
-  if (!fc->labels_cached || (!ml && !clip)) return APA_OK;
-  set_error("%s: apa_feature_cache.labels_cached = 1 is not served together with %s: such labels are per clip or per "
-            "row and come from the sampler (apa_sample_clip_frames), not through the frame index", fn,
-            ml ? "an apa_multilabel" : "an apa_clip_pool");
-  return APA_ERR_INVALID_ARG;
-}
-
-// ml == NULL && clip == NULL: apa_attn_head_train_step_cached itself
-extern "C" int apa_attn_head_train_step_cached_clips(const apa_feature_cache* cache, const apa_multilabel* ml,
-                                                     const apa_clip_pool* clip, const apa_hooks* hooks, const void* X,
-                                                     const void* Xatt, const float* Wa, const float* ba,
-                                                     const float* Wt, const float* bt, const int64_t* labels,
-                                                     float loss_wt, float grad_scale, float* logits, float* att,
-                                                     float* zsave, float* abar, float* loss, float* G, void* dX,
-                                                     void* dXatt, float* dWa, float* dba, float* dWt, float* dbt,
-                                                     void* ws, size_t ws_bytes, int N, int P, int C, int Ca, int K,
-                                                     int M, unsigned flags, float keep_prob, uint64_t seed,
-                                                     uint64_t offset, int dtype, void* stream) {
-  if (!ml && !clip)
-    return apa_attn_head_train_step_cached(cache, hooks, X, Xatt, Wa, ba, Wt, bt, labels, loss_wt, grad_scale, logits,
-                                           att, zsave, abar, loss, G, dX, dXatt, dWa, dba, dWt, dbt, ws, ws_bytes, N, P,
-                                           C, Ca, K, M, flags, keep_prob, seed, offset, dtype, stream);
-  const char* fn = "apa_attn_head_train_step_cached_clips";
-  PoolCall d = fp8_served(pool_call({N, P, C, Ca, K, M, dtype}, flags, keep_prob, seed, offset, ws, ws_bytes, stream,
-                                    hooks));
-  int rc = cache_check(fn, cache, d, X, Xatt, false, true, dX);
-  if (rc != APA_OK) return rc;
-  if (ml && (rc = check_multilabel(fn, ml)) != APA_OK) return rc;
-  if ((rc = cached_clip_labels_check(fn, cache, ml != nullptr, clip != nullptr)) != APA_OK) return rc;
-  d.fc = cache;
-  return head_step(fn, d, StepLoss{ml, ml ? nullptr : labels, clip != nullptr, clip, loss_wt, grad_scale, loss, G},
-                   M1Fwd{X, Xatt, Wa, ba, Wt, bt, logits, att, zsave, abar},
-                   M1Bwd{X, Xatt, Wa, Wt, bt, att, zsave, abar, G, dX, dXatt, dWa, dba, dWt, dbt});
-}
-
-// clip == NULL: apa_attn_head_eval_step_cached itself
-extern "C" int apa_attn_head_eval_step_cached_clips(const apa_feature_cache* cache, const apa_clip_pool* clip,
-                                                    int scores_kind, const void* X, const void* Xatt, const float* Wa,
-                                                    const float* ba, const float* Wt, const float* bt,
-                                                    const int64_t* labels, float* logits, float* att, float* zsave,
-                                                    float* abar, float* loss, float* probs, int64_t* pred, void* ws,
-                                                    size_t ws_bytes, int N, int P, int C, int Ca, int K, int M,
-                                                    unsigned flags, int dtype, void* stream) {
-  if (!clip)
-    return apa_attn_head_eval_step_cached(cache, nullptr, scores_kind, X, Xatt, Wa, ba, Wt, bt, labels, logits, att,
-                                          zsave, abar, loss, probs, pred, ws, ws_bytes, N, P, C, Ca, K, M, flags, dtype,
-                                          stream);
-  const char* fn = "apa_attn_head_eval_step_cached_clips";
-  PoolCall d = fp8_served(pool_call({N, P, C, Ca, K, M, dtype}, flags, 1.0f, 0, 0, ws, ws_bytes, stream));
-  int rc = cache_check(fn, cache, d, X, Xatt, false, false, nullptr);
-  if (rc != APA_OK) return rc;
-  if ((rc = cached_clip_labels_check(fn, cache, false, true)) != APA_OK) return rc;
-  if ((rc = eval_scores_check(fn, clip, scores_kind, N, K, logits, labels, loss, probs, pred)) != APA_OK) return rc;
-  d.fc = cache;
-  return attn_head_eval_clips(fn, clip, scores_kind, d, M1Fwd{X, Xatt, Wa, ba, Wt, bt, logits, att, zsave, abar},
-                              labels, loss, probs, pred);
-}
-
-// ---- a whole epoch over the cache behind one host call (apa.h: apa_epoch) --------------------------------------------
-// Both calls ARE the loop over the *_cached step they name (and, training, apa_momentum_sgd_step behind each step):
-// the same entry points with the same arguments, so the same launches and the same bits.  What is added is the order of
-// things: every refusal -- the epoch's, the optimiser's, the descriptor's, the step's for the shape (both halves, and
-// the evaluation pass's shorter last batch) -- is made here, before the first launch.
-
-// the epoch's own refusals; *steps: the number of steps it runs
-static int epoch_check(const char* fn, const apa_epoch* ep, const apa_feature_cache* cache, int N, bool train,
-                       int* steps) {
-  if (!ep || !ep->order) {
-    set_error("%s: null apa_epoch / order pointer", fn);
-    return APA_ERR_INVALID_ARG;
-  }
-  if (!cache) {
-    set_error("%s: null apa_feature_cache", fn);
-    return APA_ERR_INVALID_ARG;
-  }
-  if (N <= 0) {
-    set_error("%s: non-positive batch size N=%d", fn, N);
-    return APA_ERR_INVALID_ARG;
-  }
-  if (train ? (ep->count < N || ep->count % N != 0) : ep->count < 1) {
-    set_error(train ? "%s: apa_epoch.count=%d is not a whole, positive number of batches of N=%d images"
-                    : "%s: apa_epoch.count=%d: an evaluation pass visits at least one image (N=%d)", fn, ep->count, N);
-    return APA_ERR_INVALID_ARG;
-  }
-  const long long s = ((long long)ep->count + N - 1) / N;
-  if (s * N > 0x7fffffffLL) {
-    set_error("%s: steps * N = %lld is past 2^31 - 1 (count=%d, N=%d)", fn, s * N, ep->count, N);
-    return APA_ERR_INVALID_ARG;
-  }
-  *steps = (int)s;
-  return APA_OK;
-}
-
-// what sgd_launch (apa_optim.hip) refuses about apa_momentum_sgd_step's arguments, before the first step
-static int epoch_sgd_check(const char* fn, const apa_epoch_sgd* o) {
-  if (o->nseg <= 0 || o->nseg > APA_SGD_MAX_SEGMENTS || !o->weights || !o->sizes || !o->weight_decay ||
-      !o->grad_flat || !o->acc_flat) {
-    set_error("%s: apa_epoch_sgd: bad arguments (nseg=%d, max %d; weights, sizes, weight_decay, grad_flat and acc_flat "
-              "must be given)", fn, o->nseg, APA_SGD_MAX_SEGMENTS);
-    return APA_ERR_INVALID_ARG;
-  }
-  for (int i = 0; i < o->nseg; ++i)
-    if (!o->weights[i]) {
-      set_error("%s: apa_epoch_sgd.weights[%d] is NULL", fn, i);
-      return APA_ERR_INVALID_ARG;
-    }
-  return APA_OK;
-}
-
-// the pooling call's refusals and the M == 1 paths' own (m1_call_fill) for one half; nothing is launched
-static int epoch_half_check(const PoolCall& d, const M1Fwd* f, const M1Bwd* b) {
-  const int rc = pool_check(d, f, b);
-  if (rc != APA_OK) return rc;
-  M1Call c;
-  return m1_call_fill(c, d, f, b);
-}
-
-extern "C" int apa_attn_head_train_epoch_cached(const apa_epoch* ep, const apa_epoch_sgd* opt,
-                                                const apa_feature_cache* cache, const apa_hooks* hooks, const void* X,
-                                                const void* Xatt, const float* Wa, const float* ba, const float* Wt,
-                                                const float* bt, const int64_t* labels, float loss_wt, float grad_scale,
-                                                float* logits, float* att, float* zsave, float* abar, float* loss,
-                                                float* G, void* dX, void* dXatt, float* dWa, float* dba, float* dWt,
-                                                float* dbt, void* ws, size_t ws_bytes, int N, int P, int C, int Ca, int K,
-                                                int M, unsigned flags, float keep_prob, uint64_t seed, uint64_t offset,
-                                                int dtype, void* stream) {
-  const char* fn = "apa_attn_head_train_epoch_cached";
-  if (!opt || !opt->lr) {
-    set_error("%s: null apa_epoch_sgd / lr pointer", fn);
-    return APA_ERR_INVALID_ARG;
-  }
-  int steps = 0;
-  int rc = epoch_check(fn, ep, cache, N, true, &steps);
-  if (rc != APA_OK) return rc;
-  if ((rc = epoch_sgd_check(fn, opt)) != APA_OK) return rc;
-  apa_feature_cache fc = *cache;
-  fc.index = ep->order;
-  {  // the step's checks, once for the shape
-    PoolCall d = fp8_served(pool_call({N, P, C, Ca, K, M, dtype}, flags, keep_prob, seed, offset, ws, ws_bytes, stream,
-                                      hooks));
-    // (per-class maps: refused here although the step serves them -- this call's update rewrites no weight images)
-    if ((rc = cache_check(fn, &fc, d, X, Xatt, false, true, dX, false)) != APA_OK) return rc;
-    d.fc = &fc;
-    const StepLoss L{nullptr, labels, false, nullptr, loss_wt, grad_scale, loss, G};
-    const M1Fwd f{X, Xatt, Wa, ba, Wt, bt, logits, att, zsave, abar};
-    const M1Bwd b{X, Xatt, Wa, Wt, bt, att, zsave, abar, G, dX, dXatt, dWa, dba, dWt, dbt};
-    size_t pool_bytes = 0;
-    if ((rc = head_step_check(fn, d, L, logits, &pool_bytes)) != APA_OK) return rc;
-    d.ws_bytes = pool_bytes;
-    if ((rc = epoch_half_check(d, &f, nullptr)) != APA_OK) return rc;
-    d.flags |= APA_FLAG_WS_FROM_FWD;
-    if ((rc = epoch_half_check(d, nullptr, &b)) != APA_OK) return rc;
-  }
-  const bool rng_dev = (flags & APA_FLAG_RNG_DEVICE) != 0;   // the counter in HBM advances by itself
-  for (int s = 0; s < steps; ++s) {
-    fc.index = ep->order + (size_t)s * N;
-    rc = apa_attn_head_train_step_cached(&fc, hooks, X, Xatt, Wa, ba, Wt, bt,
-                                         (fc.labels_cached || !labels) ? labels : labels + (size_t)s * N, loss_wt,
-                                         grad_scale, logits, att, zsave, abar, loss + (size_t)s * (1 + N), G, dX, dXatt,
-                                         dWa, dba, dWt, dbt, ws, ws_bytes, N, P, C, Ca, K, M, flags, keep_prob, seed,
-                                         rng_dev ? offset : offset + (uint64_t)s, dtype, stream);
-    if (rc != APA_OK) return rc;
-    rc = apa_momentum_sgd_step(opt->nseg, opt->weights, opt->sizes, opt->weight_decay, opt->grad_flat, opt->acc_flat,
-                               opt->lr[s], opt->momentum, opt->grad_scale, stream);
-    if (rc != APA_OK) return rc;
-  }
-  return APA_OK;
-}
-
-extern "C" int apa_attn_head_eval_epoch_cached(const apa_epoch* ep, const apa_feature_cache* cache, int scores_kind,
-                                               const void* X, const void* Xatt, const float* Wa, const float* ba,
-                                               const float* Wt, const float* bt, const int64_t* labels, float* logits,
-                                               float* att, float* zsave, float* abar, float* loss, float* probs,
-                                               int64_t* pred, void* ws, size_t ws_bytes, int N, int P, int C, int Ca,
-                                               int K, int M, unsigned flags, int dtype, void* stream) {
-  const char* fn = "apa_attn_head_eval_epoch_cached";
-  int steps = 0;
-  int rc = epoch_check(fn, ep, cache, N, false, &steps);
-  if (rc != APA_OK) return rc;
-  apa_feature_cache fc = *cache;
-  fc.index = ep->order;
-  const int last = ep->count - (steps - 1) * N;   // rows of the last step, 1..N
-  {  // the step's checks, once for the full batch and once for the last step's shape
-    const M1Fwd f{X, Xatt, Wa, ba, Wt, bt, logits, att, zsave, abar};
-    for (int n : {N, last}) {
-      PoolCall d = fp8_served(pool_call({n, P, C, Ca, K, M, dtype}, flags, 1.0f, 0, 0, ws, ws_bytes, stream));
-      // (per-class maps: refused with the training epoch's, so that the pair stays one interface)
-      if ((rc = cache_check(fn, &fc, d, X, Xatt, false, false, nullptr, false)) != APA_OK) return rc;
-      if ((rc = eval_scores_check(fn, nullptr, scores_kind, n, K, logits, labels, loss, probs, pred)) != APA_OK)
-        return rc;
-      d.fc = &fc;
-      d.flags &= ~(unsigned)APA_FLAG_TRAIN;
-      if ((rc = epoch_half_check(d, &f, nullptr)) != APA_OK) return rc;
-    }
-  }
-  for (int s = 0; s < steps; ++s) {
-    const size_t row = (size_t)s * N;
-    fc.index = ep->order + row;
-    rc = apa_attn_head_eval_step_cached(&fc, nullptr, scores_kind, X, Xatt, Wa, ba, Wt, bt,
-                                        (fc.labels_cached || !labels) ? labels : labels + row, logits + row * K, att,
-                                        zsave, abar, loss ? loss + (size_t)s * (1 + N) : nullptr, probs + row * K,
-                                        pred + row, ws, ws_bytes, s == steps - 1 ? last : N, P, C, Ca, K, M, flags,
-                                        dtype, stream);
-    if (rc != APA_OK) return rc;
-  }
-  return APA_OK;
-}
-
-// ---- a whole epoch of CLIPS / sigmoid losses behind one host call (apa_clip_epoch.h) --------------------------------
-// The same construction as the flat epoch calls above, with the keyed sampler in front of every step: the loop over
-// apa_sample_clip_frames_keyed, the *_cached_clips step and (training) apa_momentum_sgd_step, every refusal made first.
-
-// the epoch's own refusals; F: frames per video (1 without a clip); *B, *steps: videos per step, steps
-static int clip_epoch_check(const char* fn, const apa_epoch* ep, const apa_clip_epoch* ce,
-                            const apa_feature_cache* cache, const apa_clip_pool* clip, int N, bool train, int* B,
-                            int* steps) {
-  if (!ep || !ep->order) {
-    set_error("%s: null apa_epoch / order pointer", fn);
-    return APA_ERR_INVALID_ARG;
-  }
-  if (!cache) {
-    set_error("%s: null apa_feature_cache", fn);
-    return APA_ERR_INVALID_ARG;
-  }
-  if (!ce) {
-    set_error("%s: null apa_clip_epoch", fn);
-    return APA_ERR_INVALID_ARG;
-  }
-  const int F = clip ? clip->frames : 1;
-  if (N <= 0 || F <= 0 || N % F != 0) {
-    set_error("%s: N=%d is not a whole, positive number of clips of %d frames", fn, N, F);
-    return APA_ERR_INVALID_ARG;
-  }
-  const int b = N / F;
-  if (train ? (ep->count < b || ep->count % b != 0) : ep->count < 1) {
-    set_error(train ? "%s: apa_epoch.count=%d is not a whole, positive number of batches of B=%d videos"
-                    : "%s: apa_epoch.count=%d: an evaluation pass visits at least one video (B=%d)", fn, ep->count, b);
-    return APA_ERR_INVALID_ARG;
-  }
-  const long long s = ((long long)ep->count + b - 1) / b;
-  if (s * b > 0x7fffffffLL) {
-    set_error("%s: steps * B = %lld is past 2^31 - 1 (count=%d, B=%d)", fn, s * b, ep->count, b);
-    return APA_ERR_INVALID_ARG;
-  }
-  *B = b;
-  *steps = (int)s;
-  return APA_OK;
-}
-
-// the sampler's call of one step: labels / targets are sampled where both the table and the destination are given
-static int clip_epoch_sample(const apa_clip_epoch* ce, const int32_t* videos, int64_t* labels, float* targets,
-                             int32_t* status, int B, int F, int K, int mode, int step, void* stream) {
-  const bool lab = ce->video_labels && labels, tgt = ce->video_targets && targets;
-  return apa_sample_clip_frames_keyed(ce->video_first, ce->video_frames, lab ? ce->video_labels : nullptr,
-                                      tgt ? ce->video_targets : nullptr, videos, ce->index, lab ? labels : nullptr,
-                                      tgt ? targets : nullptr, status, ce->V, B, F, K, mode, ce->seed, ce->epoch,
-                                      (uint64_t)step, stream);
-}
-
-// what the step will read from the sampler must be sampled; then the sampler's own refusals for the shape
-static int clip_epoch_sampler_check(const char* fn, const apa_clip_epoch* ce, const int32_t* videos, bool need_labels,
-                                    bool need_targets, int B, int F, int K, int mode) {
-  if (!ce->index || (reinterpret_cast<uintptr_t>(ce->index) & 3)) {
-    set_error("%s: apa_clip_epoch.index must be a 4-byte aligned device pointer (int32 [B*frames] scratch)", fn);
-    return APA_ERR_INVALID_ARG;
-  }
-  if (need_targets && (!ce->video_targets || !ce->targets)) {
-    set_error("%s: a sigmoid loss reads the sampled targets: apa_clip_epoch.video_targets and .targets are required", fn);
-    return APA_ERR_INVALID_ARG;
-  }
-  if (need_labels && (!ce->video_labels || !ce->labels)) {
-    set_error("%s: the softmax cross-entropy reads the sampled labels: apa_clip_epoch.video_labels and .labels are "
-              "required", fn);
-    return APA_ERR_INVALID_ARG;
-  }
-  const bool lab = ce->video_labels && ce->labels, tgt = ce->video_targets && ce->targets;
-  return sample_clip_check(fn, ce->video_first, ce->video_frames, lab ? ce->video_labels : nullptr,
-                           tgt ? ce->video_targets : nullptr, videos, ce->index, ce->labels, ce->targets, ce->V, B, F, K,
-                           mode, false);
-}
-
-extern "C" int apa_attn_head_train_epoch_cached_clips(
-    const apa_epoch* ep, const apa_epoch_sgd* opt, const apa_clip_epoch* ce, const apa_feature_cache* cache,
-    const apa_multilabel* ml, const apa_clip_pool* clip, const apa_hooks* hooks, const void* X, const void* Xatt,
-    const float* Wa, const float* ba, const float* Wt, const float* bt, const int64_t* labels, float loss_wt,
-    float grad_scale, float* logits, float* att, float* zsave, float* abar, float* loss, float* G, void* dX, void* dXatt,
-    float* dWa, float* dba, float* dWt, float* dbt, void* ws, size_t ws_bytes, int N, int P, int C, int Ca, int K, int M,
-    unsigned flags, float keep_prob, uint64_t seed, uint64_t offset, int dtype, void* stream) {
-  const char* fn = "apa_attn_head_train_epoch_cached_clips";
-  (void)labels;   // the sampler's take their place
-  if (!opt || !opt->lr) {
-    set_error("%s: null apa_epoch_sgd / lr pointer", fn);
-    return APA_ERR_INVALID_ARG;
-  }
-  int B = 0, steps = 0;
-  int rc = clip_epoch_check(fn, ep, ce, cache, clip, N, true, &B, &steps);
-  if (rc != APA_OK) return rc;
-  if ((rc = epoch_sgd_check(fn, opt)) != APA_OK) return rc;
-  const int F = N / B;
-  if ((rc = clip_epoch_sampler_check(fn, ce, ep->order, ml == nullptr, ml != nullptr, B, F, K, ce->mode)) != APA_OK)
-    return rc;
-  apa_multilabel mls{};
-  if (ml) {
-    mls = *ml;
-    mls.labels = ce->targets;
-    if ((rc = check_multilabel(fn, &mls)) != APA_OK) return rc;
-  }
-  const apa_multilabel* const m = ml ? &mls : nullptr;
-  apa_feature_cache fc = *cache;
-  fc.index = ce->index;
-  fc.labels_cached = 0;
-  {  // the step's checks, once for the shape
-    PoolCall d = fp8_served(pool_call({N, P, C, Ca, K, M, dtype}, flags, keep_prob, seed, offset, ws, ws_bytes, stream,
-                                      hooks));
-    // (per-class maps: refused here although the step serves them -- this call's update rewrites no weight images)
-    if ((rc = cache_check(fn, &fc, d, X, Xatt, false, true, dX, false)) != APA_OK) return rc;
-    d.fc = &fc;
-    const StepLoss L{m, m ? nullptr : ce->labels, clip != nullptr, clip, loss_wt, grad_scale, loss, G};
-    const M1Fwd f{X, Xatt, Wa, ba, Wt, bt, logits, att, zsave, abar};
-    const M1Bwd b{X, Xatt, Wa, Wt, bt, att, zsave, abar, G, dX, dXatt, dWa, dba, dWt, dbt};
-    size_t pool_bytes = 0;
-    if ((rc = head_step_check(fn, d, L, logits, &pool_bytes)) != APA_OK) return rc;
-    d.ws_bytes = pool_bytes;
-    if ((rc = epoch_half_check(d, &f, nullptr)) != APA_OK) return rc;
-    d.flags |= APA_FLAG_WS_FROM_FWD;
-    if ((rc = epoch_half_check(d, nullptr, &b)) != APA_OK) return rc;
-  }
-  const bool rng_dev = (flags & APA_FLAG_RNG_DEVICE) != 0;   // the counter in HBM advances by itself
-  for (int s = 0; s < steps; ++s) {
-    rc = clip_epoch_sample(ce, ep->order + (size_t)s * B, ce->labels, ce->targets, fc.status, B, F, K, ce->mode, s,
-                           stream);
-    if (rc != APA_OK) return rc;
-    rc = apa_attn_head_train_step_cached_clips(&fc, m, clip, hooks, X, Xatt, Wa, ba, Wt, bt, ce->labels, loss_wt,
-                                               grad_scale, logits, att, zsave, abar, loss + (size_t)s * (1 + B), G, dX,
-                                               dXatt, dWa, dba, dWt, dbt, ws, ws_bytes, N, P, C, Ca, K, M, flags,
-                                               keep_prob, seed, rng_dev ? offset : offset + (uint64_t)s, dtype, stream);
-    if (rc != APA_OK) return rc;
-    rc = apa_momentum_sgd_step(opt->nseg, opt->weights, opt->sizes, opt->weight_decay, opt->grad_flat, opt->acc_flat,
-                               opt->lr[s], opt->momentum, opt->grad_scale, stream);
-    if (rc != APA_OK) return rc;
-  }
-  return APA_OK;
-}
-
-extern "C" int apa_attn_head_eval_epoch_cached_clips(
-    const apa_epoch* ep, const apa_clip_epoch* ce, const apa_feature_cache* cache, const apa_clip_pool* clip,
-    int scores_kind, const void* X, const void* Xatt, const float* Wa, const float* ba, const float* Wt, const float* bt,
-    const int64_t* labels, float* logits, float* att, float* zsave, float* abar, float* loss, float* probs, int64_t* pred,
-    void* ws, size_t ws_bytes, int N, int P, int C, int Ca, int K, int M, unsigned flags, int dtype, void* stream) {
-  const char* fn = "apa_attn_head_eval_epoch_cached_clips";
-  (void)labels;   // the sampler's take their place
-  int B = 0, steps = 0;
-  int rc = clip_epoch_check(fn, ep, ce, cache, clip, N, false, &B, &steps);
-  if (rc != APA_OK) return rc;
-  const int F = N / B;
-  const int last = ep->count - (steps - 1) * B;   // videos of the last step, 1..B
-  if ((rc = clip_epoch_sampler_check(fn, ce, ep->order, loss != nullptr, false, B, F, K, APA_CLIP_FRAMES_UNIFORM)) !=
-      APA_OK)
-    return rc;
-  apa_feature_cache fc = *cache;
-  fc.index = ce->index;
-  fc.labels_cached = 0;
-  {  // the step's checks, once for the full batch and once for the last step's shape
-    const M1Fwd f{X, Xatt, Wa, ba, Wt, bt, logits, att, zsave, abar};
-    for (int b : {B, last}) {
-      const int n = b * F;
-      PoolCall d = fp8_served(pool_call({n, P, C, Ca, K, M, dtype}, flags, 1.0f, 0, 0, ws, ws_bytes, stream));
-      // (per-class maps: refused with the training epoch's, so that the pair stays one interface)
-      if ((rc = cache_check(fn, &fc, d, X, Xatt, false, false, nullptr, false)) != APA_OK) return rc;
-      if ((rc = eval_scores_check(fn, clip, scores_kind, n, K, logits, loss ? ce->labels : nullptr, loss, probs, pred)) !=
-          APA_OK)
-        return rc;
-      d.fc = &fc;
-      d.flags &= ~(unsigned)APA_FLAG_TRAIN;
-      if ((rc = epoch_half_check(d, &f, nullptr)) != APA_OK) return rc;
-    }
-  }
-  for (int s = 0; s < steps; ++s) {
-    const size_t row = (size_t)s * B;
-    const int b = s == steps - 1 ? last : B;
-    rc = clip_epoch_sample(ce, ep->order + row, ce->labels ? ce->labels + row : nullptr,
-                           ce->targets ? ce->targets + row * K : nullptr, fc.status, b, F, K, APA_CLIP_FRAMES_UNIFORM, s,
-                           stream);
-    if (rc != APA_OK) return rc;
-    apa_clip_pool cp{};
-    if (clip) {
-      cp = *clip;
-      cp.pooled = clip->pooled + row * K;
-    }
-    // (clip == NULL: one-frame videos -- the logits rows are the per-video rows and advance with the others)
-    rc = apa_attn_head_eval_step_cached_clips(&fc, clip ? &cp : nullptr, scores_kind, X, Xatt, Wa, ba, Wt, bt,
-                                              loss ? ce->labels + row : nullptr, clip ? logits : logits + row * K, att,
-                                              zsave, abar, loss ? loss + (size_t)s * (1 + B) : nullptr, probs + row * K,
-                                              pred + row, ws, ws_bytes, b * F, P, C, Ca, K, M, flags, dtype, stream);
-    if (rc != APA_OK) return rc;
-  }
-  return APA_OK;
 }
 
 // workspace of apa_pose_attn_eval_step: [pose head | pooling (+ the label-free loss scratch) | column-tile partials]

@@ -8,7 +8,7 @@
 //       fp32 and below 1 (rng_hash: the dropout mask's two-round 24-bit multiply-xorshift mix, apa_device.h)
 // Counter-based: every frame computes its own draw, and only where its segment has a choice.  No workspace, no LDS, no
 // atomics but the integer status count: identical calls give identical bits.  The epoch calls that loop over this
-// launch, the *_cached_clips step and the update are apa_capi.hip's (they share the step's refusals).
+// launch, the *_cached_clips step and the update are apa_epoch.hip's (one driver with the flat epoch calls).
 #include "../../include/apa_clip_epoch.h"
 #include "apa_clip_sample.h"
 #include "apa_internal.h"

@@ -5,6 +5,7 @@ The oracle of every new entry point is the sequence it is defined as, run with t
 * the training epoch == `sample_clips_keyed(step=s, out=clips)` + `HeadTrainStep.rebind(offset=) + run()` +
   `BoundMomentumSGD.run(lr[s])` per step -- every weight, accumulator, output, the whole loss log and `status`;
 * the evaluation epoch == `FeatureCache.sample_clips(..., 'uniform')` + `HeadEvalStep` per batch, the last batch shorter;
+* on a cache whose videos are its images, both epochs == the flat epoch calls (HeadTrainEpoch / HeadEvalEpoch);
 * deploy.FusedHeadStep.train_video_epoch / FusedHeadEval.evaluate_videos == the per-batch deploy loops;
 * a captured hipGraph of each entry point replays its eager calls (tests/_graph_replay.py), and freezes the key.
 Every comparison is torch.equal: the library has no floating-point atomics.
@@ -353,8 +354,70 @@ def test_validation_epoch_is_the_loop(gpu, dtype, form):
     cache.status.zero_()
 
 
+# ------------------------------------------------------------------------------------------ the two epoch interfaces
+def test_one_frame_videos_are_the_flat_epoch(gpu):
+    """The clip epoch calls and the flat epoch calls of apa.h run one driver; on a cache whose videos are its images
+    (one frame each, video labels = image labels) they are the same epoch.  T = 10 maps of 3x3x32 in bf16, K = 5,
+    N = B = 4: training visits 8 ids in 2 steps under dropout, evaluation 10 rows in steps of 4, 4 and 2."""
+    T1, C1, K1, N1 = 10, 32, 5, 4
+    g = torch.Generator().manual_seed(91)
+    img = torch.relu(torch.randn(T1, 3, 3, C1, generator=g)) * (0.25 + 4.0 * torch.rand((T1, 1, 1, 1), generator=g))
+    labels = torch.randint(0, K1, (T1,), generator=g).to(gpu)
+    cache = cof.FeatureCache.empty((T1, 3, 3, C1), torch.bfloat16, gpu, labels=labels)
+    assert cache.write(0, img.to(gpu)).tolist() == [0] * T1
+    cache.set_videos(torch.arange(T1), torch.ones(T1, dtype=torch.int64), labels=labels)
+    w0 = [(torch.rand(C1, 1, generator=g) * (4.0 / C1)), torch.rand(1, generator=g) * 0.1 - 0.3,
+          (torch.rand(C1, K1, generator=g) - 0.25) / C1 ** 0.5, torch.rand(K1, generator=g) * 0.1]
+    n = sum(t.numel() for t in w0)
+    acc0 = torch.rand((n,), generator=g) * 1e-3
+
+    def state():
+        w, grad, o, views = [t.clone().to(gpu) for t in w0], torch.zeros((n,), device=gpu), 0, []
+        for t in w:
+            views.append(grad[o:o + t.numel()].view(t.shape))
+            o += t.numel()
+        return w, views, grad, acc0.clone().to(gpu)
+    # ---- training: 2 steps, ids may repeat
+    order = torch.tensor([7, 2, 9, 0, 3, 3, 5, 8], dtype=torch.int32, device=gpu)
+    lr = [LR0, LR0 * 0.5]
+    kw = dict(steps=2, momentum=MOMENTUM, flags=cof.APA_FLAG_TRAIN | cof.APA_FLAG_RELU_ATT, keep_prob=KEEP, seed=SEED,
+              offset=OFFSET, loss_wt=1.3, grad_scale=0.5)
+    wf, vf, gf, af = state()
+    flat = cof.HeadTrainEpoch(cache, N1, *wf, tuple(vf), wf, [4e-3, 0.0, 2e-3, 0.0], gf, af, labels_cached=True, **kw)
+    assert flat.run(order, lr) == 2
+    wc, vc, gc, ac = state()
+    clip = ce.ClipTrainEpoch(cache, N1, 1, *wc, tuple(vc), wc, [4e-3, 0.0, 2e-3, 0.0], gc, ac, **kw)
+    log = clip.run(order, lr, **KEY)
+    torch.cuda.synchronize()
+    assert clip._clip is None and tuple(log.shape) == (2, 1 + N1)
+    assert torch.equal(log, flat.loss) and bool(torch.isfinite(log).all()) and not torch.equal(log[0], log[1])
+    for k, (a, b) in enumerate(zip(wc, wf)):
+        assert torch.equal(a, b) and not torch.equal(a, w0[k].to(gpu)), k
+    assert torch.equal(gc, gf) and torch.equal(ac, af)
+    for k in ('logits', 'G', 'att', 'zsave', 'abar'):                       # the last step's
+        assert torch.equal(getattr(clip, k), getattr(flat, k)), k
+    assert float(clip.G.abs().max()) > 0
+    assert torch.equal(clip.index, order[N1:]) and torch.equal(clip.labels, labels[order[N1:].long()])
+    # ---- evaluation: all 10 rows, the last step holds 2
+    order = cof.epoch_order(T1, 3, 1, gpu)
+    ekw = dict(capacity=T1, flags=cof.APA_FLAG_RELU_ATT, scores='softmax', want_loss=True)
+    ef = cof.HeadEvalEpoch(cache, N1, *wf, **ekw)
+    ec = ce.ClipEvalEpoch(cache, N1, 1, *wf, **ekw)
+    ef.loss.fill_(NAN), ec.loss.fill_(NAN)
+    assert ef.run(order, T1) == ec.run(order, T1) == 3
+    torch.cuda.synchronize()
+    assert ec._clip is None and ec.pooled is ec.logits
+    for k in ('probs', 'pred', 'logits'):
+        assert torch.equal(getattr(ec, k), getattr(ef, k)), k
+    assert torch.equal(ec.loss[:2], ef.loss[:2]) and torch.equal(ec.loss[2, :3], ef.loss[2, :3])
+    assert bool(torch.isfinite(ec.loss[2, :3]).all()) and bool(torch.isnan(ec.loss[2, 3:]).all())
+    for k in ('att', 'zsave', 'abar'):                                      # the last step's two rows
+        assert torch.equal(getattr(ec, k)[:2], getattr(ef, k)[:2]), k
+    assert torch.equal(ec.labels, labels[order.long()]) and int(cache.status) == 0
+
+
 # ------------------------------------------------------------------------------------------ deploy
-DEPLOY = [('vstep_temporal_att_train', False), ('vstep_framepool_train', False), ('mlstep_clip_temporal_ml', True),
+DEPLOY =[('vstep_temporal_att_train', False), ('vstep_framepool_train', False), ('mlstep_clip_temporal_ml', True),
           ('mlstep_flat002_ml2_c32', True)]
 D_COUNTS = [1, 2, 3, 5, 4]
 
