@@ -1978,3 +1978,152 @@ class FusedHeadEval:
             out['overlay_bottom_up'] = cof.attention_overlay(bottom_maps.contiguous(), src)
             out['overlay_combined'] = cof.attention_overlay(out['combined'], src)
         return out
+
+
+class HeadSweep:
+    """H class-agnostic heads (cfg 002) trained and evaluated from ONE pass over a resident `FeatureCache` per direction
+    (custom_ops/multihead.py, include/apa_multihead.h): a learning-rate / weight-decay sweep, several initialisations or
+    a seed ensemble whose scores are averaged at test time ("late fusion", the reference's eval.py).
+
+        sweep = deploy.HeadSweep([get_network_fn(..., backbone=None) for _ in range(4)], cfg, lrs=[.1, .03, .01, .003])
+        log = sweep.train_epoch(cache, 32, cache.order(seed, epoch))          # loss log [steps, H, 1 + 32]
+        meters = sweep.evaluate_cache(val_cache, 64)                          # H per-head meters + the fused one
+        h = sweep.best('mAP')
+
+    The heads must have identical shapes and flags (a ValueError names the first difference).  Their parameters move
+    into stacked storages -- Wa [H,C], ba [H], Wt [H,C,K], bt [H,K] -- and each head's `Parameter.data` becomes a view of
+    row h, so every head stays usable on its own and its `state_dict()` still works.  All heads share the batch, the
+    labels and ONE dropout mask per step: the mask's step counter advances once per step for the whole sweep (heads that
+    need different keep probabilities or mask streams train as separate FusedHeadStep runs).  FP8 caches are refused by
+    the library by name.  Momentum SGD (TRAIN.MOMENTUM) with per-head learning rate and weight decay (biases carry
+    none); `FusedHeadStep` / `FusedHeadEval` and their reasons are unchanged."""
+
+    NAMES = ('att_weights', 'att_biases', 'td_weights', 'td_biases')
+
+    def __init__(self, network_fns, cfg, lrs, weight_decays=None):
+        from . import nets_factory
+        from .custom_ops import multihead as mh
+        fns = list(network_fns)
+        H = len(fns)
+        if not 1 <= H <= mh.APA_HEADS_MAX:
+            raise ValueError('HeadSweep: 1 .. %d heads expected (got %d)' % (mh.APA_HEADS_MAX, H))
+        for i, fn in enumerate(fns):
+            why = '' if isinstance(fn.head, nets_factory.AttentionalPoolingHead) else 'a head without the attention op'
+            why = why or FusedHeadStep.fp8_unsupported_reason(fn.head, fn)
+            if not why and cfg.TRAIN.LOSS_FN_ACTION != 'softmax-xentropy':
+                why = 'LOSS_FN_ACTION %r (the multi-head step takes the softmax cross-entropy)' % cfg.TRAIN.LOSS_FN_ACTION
+            if why:
+                raise ValueError('HeadSweep: head %d is not served with %s' % (i, why))
+        h0 = fns[0].head
+        for i, fn in enumerate(fns[1:], 1):
+            h = fn.head
+            for n in self.NAMES:
+                a, b = getattr(h0, n), getattr(h, n)
+                if a.shape != b.shape or a.dtype != b.dtype or a.device != b.device:
+                    raise ValueError('HeadSweep: head %d differs from head 0 in %s (%s %s on %s against %s %s on %s)' % (
+                        i, n, tuple(b.shape), b.dtype, b.device, tuple(a.shape), a.dtype, a.device))
+            for n in ('relu_att', 'softmax_att', 'keep_prob', 'is_training', 'seed'):
+                if getattr(h0, n) != getattr(h, n):
+                    raise ValueError('HeadSweep: head %d differs from head 0 in %s (%r against %r)' % (
+                        i, n, getattr(h, n), getattr(h0, n)))
+        self.network_fns, self.heads, self.cfg, self.H = fns, [fn.head for fn in fns], cfg, H
+        self.lrs = [float(v) for v in lrs]
+        if len(self.lrs) != H:
+            raise ValueError('HeadSweep: one learning rate per head expected (%d for %d heads)' % (len(self.lrs), H))
+        wds = [float(getattr(fn, 'weight_decay', 0.0)) for fn in fns] if weight_decays is None else \
+            [float(v) for v in weight_decays]
+        if len(wds) != H:
+            raise ValueError('HeadSweep: one weight decay per head expected (%d for %d heads)' % (len(wds), H))
+        self.weight_decays = wds
+        # the stacked storages; each head's parameters become views of its rows
+        self.stacked = []
+        with torch.no_grad():
+            for n in self.NAMES:
+                rows = [getattr(h, n).data.reshape(-1) for h in self.heads]
+                st = torch.stack(rows).contiguous()
+                for i, h in enumerate(self.heads):
+                    p = getattr(h, n)
+                    p.data = st[i].view(p.shape)
+                self.stacked.append(st)
+        C, K = (int(d) for d in h0.td_weights.shape)
+        self.C, self.K = C, K
+        self.Wa, self.ba = self.stacked[0], self.stacked[1].view(H)
+        self.Wt, self.bt = self.stacked[2].view(H, C, K), self.stacked[3]
+        self._step = int(h0._step)
+        self._train = self._train_key = self._eval = self._eval_key = None
+        self.acc = None
+        self.meters = None
+
+    def _params(self):
+        return self.Wa, self.ba, self.Wt, self.bt
+
+    def train_epoch(self, cache, batch_size: int, order, lr=None):
+        """steps = order.numel() / batch_size training steps of all heads and their updates as ONE host call
+        (apa_multihead_train_epoch_cached), on the cache's own labels.  `lr`: None (the sweep's `lrs` in every step), H
+        values, or one row of H values per step.  Returns the loss log [steps, H, 1 + batch_size] on the device."""
+        from .custom_ops import multihead as mh
+        if cache.labels is None:
+            raise ValueError('HeadSweep.train_epoch: a FeatureCache without labels')
+        h0 = self.heads[0]
+        if not h0.is_training:
+            raise ValueError('HeadSweep.train_epoch: evaluation-mode heads (build network_fn with is_training=True)')
+        N, count = int(batch_size), int(order.numel())
+        if N < 1 or count < N or count % N:
+            raise ValueError('HeadSweep.train_epoch: order holds %d ids, not a whole number of batches of %d' % (count, N))
+        steps = count // N
+        key = (cache, N, steps)                  # (the cache itself: an id could be reused by another cache)
+        if self._train is None or self._train_key != key:
+            step = mh.MultiHeadTrainStep(
+                cache.select(torch.zeros((N,), dtype=torch.int32, device=cache.device)), *self._params(), 'cache',
+                relu_att=h0.relu_att, keep_prob=h0.keep_prob, seed=h0.seed, offset=self._step,
+                loss_wt=float(self.cfg.TRAIN.LOSS_FN_ACTION_WT))
+            if self.acc is None:
+                self.acc = torch.zeros_like(step.grad_flat)
+            momentum = float(self.cfg.TRAIN.MOMENTUM) if self.cfg.TRAIN.OPTIMIZER == 'momentum' else 0.0
+            sgd = mh.MultiHeadSGD(self._params(), [self.weight_decays, 0.0, self.weight_decays, 0.0], step.grad_flat,
+                                  self.acc, self.lrs, momentum)
+            self._train, self._train_key = mh.MultiHeadTrainEpoch(step, sgd, steps), key
+        log = self._train.run(order, self.lrs if lr is None else lr, offset=self._step)
+        self._step += steps                      # ONE dropout stream for the whole sweep: once per step
+        for h in self.heads:
+            h._step = self._step
+        return log
+
+    def evaluate_cache(self, cache, batch_size: int, meters=None, order=None):
+        """A validation pass of all heads over the cache as ONE host call (apa_multihead_eval_epoch_cached).  Fills and
+        returns H + 1 `eval_utils.DeviceEvaluation` meters: one per head and, last, one for the fused scores (the mean
+        of the heads' softmax scores).  The truth is `cache.labels[order]`."""
+        from . import eval_utils
+        from .custom_ops import multihead as mh
+        if cache.labels is None:
+            raise ValueError('HeadSweep.evaluate_cache: a FeatureCache without labels (the truth is cache.labels[order])')
+        N = int(batch_size)
+        if N < 1:
+            raise ValueError('HeadSweep.evaluate_cache: batch_size >= 1 expected')
+        if order is None:
+            order = torch.arange(cache.T, dtype=torch.int32, device=cache.device)
+        count = int(order.numel())
+        key = (cache, N)
+        if self._eval is None or self._eval_key != key or self._eval.capacity < count:
+            self._eval = mh.MultiHeadEvalEpoch(cache, N, *self._params(), capacity=count,
+                                               relu_att=self.heads[0].relu_att, fused=True)
+            self._eval_key = key
+        probs, pred, fused_probs, fused_pred = self._eval.run(order)
+        if meters is None:
+            meters = [eval_utils.DeviceEvaluation(count, self.K, cache.device) for _ in range(self.H + 1)]
+        if len(meters) != self.H + 1:
+            raise ValueError('HeadSweep.evaluate_cache: %d meters expected (one per head and the fused one)' % (self.H + 1))
+        truth = cache.labels[order.long().clamp(0, cache.T - 1)]
+        for i, m in enumerate(meters):
+            scores, t = m.reserve(count)
+            scores.copy_(probs[i] if i < self.H else fused_probs)
+            t.copy_(truth)
+        self.meters = meters
+        return meters
+
+    def best(self, metric: str = 'mAP') -> int:
+        """the head with the largest `metric` ('mAP' / 'accuracy') of the last `evaluate_cache` (the first of equals)"""
+        if self.meters is None:
+            raise ValueError('HeadSweep.best: evaluate_cache() first')
+        vals = [m.result()[metric] for m in self.meters[:self.H]]
+        return max(range(self.H), key=lambda i: (vals[i], -i))

@@ -1,0 +1,564 @@
+"""The multi-head cached step (include/apa_multihead.h) on the GPU.
+
+* every case of tests/_multihead_reference.py CASES, training and evaluation: outputs and workspace inside NaN-guarded
+  allocations, two runs that repeat bit for bit, every per-head output against float64 in the error model of
+  tests/_m1_probe.py (forward outputs from the inputs; logits, loss, G and the backward from the step's own forward
+  outputs), cache.status == 1 whatever H is;
+* head h of a multi-head step against apa_attn_head_train_step_cached on head h's weights, within the sum of the two
+  routes' bounds, on inputs none of whose relu gates lies within its bound of zero (asserted);
+* heads with identical weights give identical bits; the heads update == H calls of apa_momentum_sgd_step, bit for bit;
+* the two epoch calls == their per-step loops, bit for bit; nothing is written past row `count`;
+* the late-fusion scores against float64; one hipGraph row per stream-taking entry point (tests/_graph_replay.py).
+"""
+import ctypes
+
+import pytest
+import torch
+
+from attentionalpoolingaction_amd.custom_ops import custom_ops_factory as cof
+from attentionalpoolingaction_amd.custom_ops import multihead as mh
+from tests import _gemm_probe as gp
+from tests import _graph_replay as gr
+from tests import _m1_probe as mp
+from tests import _multihead_reference as mr
+from tests._m1_probe import Bnd
+
+pytestmark = pytest.mark.gpu
+
+T = mr.T_CACHE
+IDS = [c['name'] for c in mr.CASES]
+
+
+def _dev(inp, dev):
+    return {k: v.to(dev) for k, v in inp.items()}
+
+
+class _Run(object):
+    """The NaN-guarded buffers of one case and the two steps on them (the C entry points, directly)."""
+
+    def __init__(self, c, inp, dev, train=True, scores=cof.APA_SCORES_SOFTMAX, keep=mr.KEEP):
+        self.c, self.inp, self.train, self.scores, self.keep = c, inp, train, scores, keep
+        self.lib = mh.load_library()
+        H, N, P, C, K = c['H'], c['N'], c['P'], c['C'], c['K']
+        f32, Gd = torch.float32, gp.Guarded
+        o = {'logits': Gd(H * N, K, K, f32, dev), 'att': Gd(H * N, P, P, f32, dev), 'zsave': Gd(H * N, C, C, f32, dev),
+             'abar': Gd(1, H * N, H * N, f32, dev), 'loss': Gd(H, 1 + N, 1 + N, f32, dev)}
+        if train:
+            o.update({'G': Gd(H * N, K, K, f32, dev), 'dWa': Gd(H, C, C, f32, dev), 'dba': Gd(1, H, H, f32, dev),
+                      'dWt': Gd(H * C, K, K, f32, dev), 'dbt': Gd(H, K, K, f32, dev)})
+        else:
+            o.update({'probs': Gd(H * N, K, K, f32, dev), 'fused_probs': Gd(N, K, K, f32, dev)})
+            self.pred = torch.full((H * N + 64,), -7, dtype=torch.int64, device=dev)
+            self.fused_pred = torch.full((N + 64,), -7, dtype=torch.int64, device=dev)
+        self.out = o
+        self.ws_bytes = mh.workspace_bytes(H, N, P, C, K)
+        assert self.ws_bytes > 0
+        self.ws = Gd(1, (self.ws_bytes + 3) // 4, (self.ws_bytes + 3) // 4, f32, dev)
+        self.status = torch.zeros((1,), dtype=torch.int32, device=dev)
+        self.fc = cof.ApaFeatureCache(inp['index'].data_ptr(), T, 1 if c['labels_cached'] else 0, self.status.data_ptr())
+        self.heads = mh.ApaMultihead(H, inp['Wa'].data_ptr(), inp['ba'].data_ptr(), inp['Wt'].data_ptr(),
+                                     inp['bt'].data_ptr())
+        self.labels = inp['cache_labels'] if c['labels_cached'] else inp['labels']
+        self.mask = cof.dropout_mask((N * P * C,), keep, mr.SEED, mr.OFFSET) if train and keep < 1.0 else None
+        self.flags = (cof.APA_FLAG_RELU_ATT if c['relu'] else 0)
+        if train:
+            self.flags |= cof.APA_FLAG_FROZEN_INPUT | (cof.APA_FLAG_TRAIN if keep < 1.0 else 0)
+        self.dtype = cof.APA_DTYPE_BF16 if c['bf16'] else cof.APA_DTYPE_F32
+        for b in list(o.values()) + [self.ws]:
+            b.snapshot()
+
+    def p(self, k):
+        return self.out[k].ptr
+
+    def run(self):
+        c = self.c
+        dims = (c['N'], c['P'], c['C'], c['K'])
+        A = ctypes.addressof
+        if self.train:
+            rc = self.lib.apa_multihead_train_step_cached(
+                A(self.fc), None, A(self.heads), self.inp['X'].data_ptr(), self.labels.data_ptr(), 1.0, 1.0,
+                self.p('logits'), self.p('att'), self.p('zsave'), self.p('abar'), self.p('loss'), self.p('G'),
+                self.p('dWa'), self.p('dba'), self.p('dWt'), self.p('dbt'), self.ws.ptr, self.ws_bytes, *dims, self.flags,
+                self.keep, mr.SEED, mr.OFFSET, self.dtype, gp.stream_ptr())
+        else:
+            soft = self.scores == cof.APA_SCORES_SOFTMAX
+            rc = self.lib.apa_multihead_eval_step_cached(
+                A(self.fc), A(self.heads), self.scores, self.inp['X'].data_ptr(),
+                self.labels.data_ptr() if soft else None, self.p('logits'), self.p('att'), self.p('zsave'),
+                self.p('abar'), self.p('loss') if soft else None, self.p('probs'), self.pred.data_ptr(),
+                self.p('fused_probs'), self.fused_pred.data_ptr(), self.ws.ptr, self.ws_bytes, *dims, self.flags,
+                self.dtype, gp.stream_ptr())
+        assert rc == 0, self.lib.apa_last_error()
+
+    def restore(self):
+        for b in list(self.out.values()) + [self.ws]:
+            b.restore()
+
+    def check_guards(self):
+        for k, b in self.out.items():
+            b.check_guards(k)
+        self.ws.check_guards('workspace')
+        if not self.train:
+            H, N = self.c['H'], self.c['N']
+            assert bool((self.pred[H * N:] == -7).all()) and bool((self.fused_pred[N:] == -7).all())
+
+    def bits(self):
+        d = {k: b.bits() for k, b in self.out.items()}
+        if not self.train:
+            d['pred'], d['fused_pred'] = self.pred.clone(), self.fused_pred.clone()
+            if self.scores != cof.APA_SCORES_SOFTMAX:
+                del d['loss']
+        return d
+
+    def got(self):
+        return {k: b.view.clone() for k, b in self.out.items()}
+
+
+def _first_max(x):
+    """the first maximal index along the last axis (torch.argmax does not promise the first one on a GPU)"""
+    K = x.shape[-1]
+    ar = torch.arange(K, device=x.device).expand_as(x)
+    return torch.where(x == x.amax(dim=-1, keepdim=True), ar, torch.full_like(ar, K)).amin(dim=-1)
+
+
+def _same_bits(a, b, what):
+    assert a.keys() == b.keys()
+    for k in a:
+        assert torch.equal(a[k], b[k]), '{}: {} differs'.format(what, k)
+
+
+def _twice(r):
+    """two runs from the same initial state: guards untouched, bits repeated; -> the outputs"""
+    r.run()
+    torch.cuda.synchronize()
+    r.check_guards()
+    first, got = r.bits(), r.got()
+    status = int(r.status)
+    r.restore()
+    r.status.zero_()
+    r.run()
+    torch.cuda.synchronize()
+    r.check_guards()
+    _same_bits(first, r.bits(), 'second run')
+    assert status == int(r.status) == 1, 'one id of the index lies outside the cache: status {}'.format(status)
+    return got
+
+
+@pytest.mark.parametrize('c', mr.CASES, ids=IDS)
+def test_train_case(gpu, c):
+    inp = _dev(mr.inputs(c), gpu)
+    r = _Run(c, inp, gpu, train=True)
+    got = _twice(r)
+    with torch.no_grad():
+        mr.check_all(c, inp, got, r.mask)
+
+
+def test_train_case_without_dropout(gpu):
+    c = mr.case_by_name('f32_c2048_h4')
+    inp = _dev(mr.inputs(c), gpu)
+    r = _Run(c, inp, gpu, train=True, keep=1.0)
+    got = _twice(r)
+    with torch.no_grad():
+        mr.check_all(c, inp, got, None)
+
+
+@pytest.mark.parametrize('c', mr.CASES, ids=IDS)
+def test_eval_case(gpu, c):
+    inp = _dev(mr.inputs(c), gpu)
+    r = _Run(c, inp, gpu, train=False)
+    got = _twice(r)
+    H, N, K = c['H'], c['N'], c['K']
+    with torch.no_grad():
+        mr.check_all(c, inp, {k: got[k] for k in ('att', 'zsave', 'abar', 'logits')}, None)
+        lg = got['logits'].double().reshape(H, N, K)
+        p = torch.softmax(lg, dim=-1)
+        tol = mp.C_ACC * (K + 16) * mp.EPS32
+        mp.check(got['probs'], Bnd(p, tol * p), 'probs')
+        _, per_b, mean_b = mr.xent_bnd(c, got['logits'].reshape(H, N, K), inp['labels'])
+        loss = got['loss'].double().reshape(H, 1 + N)
+        mp.check(loss[:, 1:], per_b, 'loss per example', zero_ref=True)
+        mp.check(loss[:, 0], mean_b, 'loss', zero_ref=True)
+        mp.check(got['fused_probs'], mr.fused_bnd(got['probs'].reshape(H, N, K)), 'fused_probs')
+        pred = r.pred[:H * N].reshape(H, N)
+        # the first maximal index of the kernel's own logits; on tie-free rows it is float64's argmax
+        assert torch.equal(pred, _first_max(got['logits'].reshape(H, N, K)))
+        top2 = lg.topk(min(2, K), dim=-1).values
+        clear = (top2[..., 0] - top2[..., -1] > 1e-4) if K > 1 else torch.ones_like(pred, dtype=torch.bool)
+        assert torch.equal(pred[clear], lg.argmax(dim=-1)[clear])
+        fp = got['fused_probs'].reshape(N, K)
+        assert torch.equal(r.fused_pred[:N], _first_max(fp))
+        f64 = got['probs'].double().reshape(H, N, K).mean(dim=0)
+        t2 = f64.topk(min(2, K), dim=-1).values
+        clear = (t2[..., 0] - t2[..., -1] > 1e-5) if K > 1 else torch.ones((N,), dtype=torch.bool, device=gpu)
+        assert torch.equal(r.fused_pred[:N][clear], f64.argmax(dim=-1)[clear])
+
+
+def test_eval_sigmoid_scores(gpu):
+    c = mr.case_by_name('bf16_c520_h2_k393')
+    inp = _dev(mr.inputs(c), gpu)
+    r = _Run(c, inp, gpu, train=False, scores=cof.APA_SCORES_SIGMOID)
+    got = _twice(r)
+    H, N, K = c['H'], c['N'], c['K']
+    lg = got['logits'].double().reshape(H, N, K)
+    s = torch.sigmoid(lg)
+    # the bound of tests/test_eval_clips_gpu.py for the same expression: 4 * 2^-24 absolute (scores <= 1)
+    mp.check(got['probs'], Bnd(s, torch.full_like(s, 4 * mp.EPS32)), 'sigmoid scores')
+    mp.check(got['fused_probs'], mr.fused_bnd(got['probs'].reshape(H, N, K)), 'fused_probs')
+    assert torch.equal(r.pred[:H * N].reshape(H, N), _first_max(got['logits'].reshape(H, N, K)))
+
+
+def _single_head(c, inp, h, dev):
+    """apa_attn_head_train_step_cached on head h's weights, same (seed, offset, keep_prob) -> dict of its outputs"""
+    lib = cof.load_library()
+    N, P, C, K = c['N'], c['P'], c['C'], c['K']
+    f32 = dict(dtype=torch.float32, device=dev)
+    o = dict(logits=torch.empty((N, K), **f32), att=torch.empty((N, P), **f32), zsave=torch.empty((N, C), **f32),
+             abar=torch.empty((N,), **f32), loss=torch.empty((1 + N,), **f32), G=torch.empty((N, K), **f32),
+             dWa=torch.empty((C,), **f32), dba=torch.empty((1,), **f32), dWt=torch.empty((C, K), **f32),
+             dbt=torch.empty((K,), **f32))
+    flags = (cof.APA_FLAG_RELU_ATT if c['relu'] else 0) | cof.APA_FLAG_FROZEN_INPUT | cof.APA_FLAG_TRAIN
+    nb = int(cof.attn_pool_workspace_bytes(N, P, C, C, K, 1, flags))
+    ws = torch.empty((nb,), dtype=torch.uint8, device=dev)
+    status = torch.zeros((1,), dtype=torch.int32, device=dev)
+    fc = cof.ApaFeatureCache(inp['index'].data_ptr(), T, 1 if c['labels_cached'] else 0, status.data_ptr())
+    labels = inp['cache_labels'] if c['labels_cached'] else inp['labels']
+    Wa, ba, Wt, bt = (inp[k][h].contiguous() for k in ('Wa', 'ba', 'Wt', 'bt'))
+    X = inp['X'].data_ptr()
+    rc = lib.apa_attn_head_train_step_cached(
+        ctypes.addressof(fc), None, X, X, Wa.data_ptr(), ba.data_ptr(), Wt.data_ptr(), bt.data_ptr(), labels.data_ptr(),
+        1.0, 1.0, o['logits'].data_ptr(), o['att'].data_ptr(), o['zsave'].data_ptr(), o['abar'].data_ptr(),
+        o['loss'].data_ptr(), o['G'].data_ptr(), None, None, o['dWa'].data_ptr(), o['dba'].data_ptr(),
+        o['dWt'].data_ptr(), o['dbt'].data_ptr(), ws.data_ptr(), nb, N, P, C, C, K, 1, flags, mr.KEEP, mr.SEED, mr.OFFSET,
+        cof.APA_DTYPE_BF16 if c['bf16'] else cof.APA_DTYPE_F32, gp.stream_ptr())
+    assert rc == 0, lib.apa_last_error()
+    torch.cuda.synchronize()
+    assert int(status) == 1
+    return o
+
+
+@pytest.mark.parametrize('c', mr.CASES, ids=IDS)
+def test_each_head_agrees_with_the_single_head_step(gpu, c):
+    """|multi - single| <= the sum of the two routes' bounds: both lie inside the bound the error model gives each output
+    FROM THE INPUTS ALONE (errors carried through every stage), with no relu gate within its bound of zero, so both
+    routes take the same gates.  H = 1 is one of the cases."""
+    inp = _dev(mr.inputs(c), gpu)
+    r = _Run(c, inp, gpu, train=True)
+    r.run()
+    torch.cuda.synchronize()
+    got = r.got()
+    H, N, P, C, K = c['H'], c['N'], c['P'], c['C'], c['K']
+    with torch.no_grad():
+        Xb = mr.batch_of(inp)
+        fref, amb = mr.forward_bnd(c, Xb, inp['Wa'], inp['ba'], r.mask)
+        assert amb is None or int(amb.sum()) == 0
+        lg = mr.logits_bnd(c, fref['zsave'], fref['abar'], inp['Wt'], inp['bt'])
+        G_b, per_b, mean_b = mr.xent_bnd(c, lg, inp['labels'])
+        bref = mr.backward_bnd(c, Xb, fref['att'], fref['zsave'], fref['abar'], G_b, inp['Wt'], inp['bt'], r.mask)
+        bounds = dict(att=fref['att'], zsave=fref['zsave'], abar=fref['abar'], logits=lg, G=G_b, dWa=bref['dWa'],
+                      dba=bref['dba'], dWt=bref['dWt'], dbt=bref['dbt'])
+        shapes = dict(att=(H, N, P), zsave=(H, N, C), abar=(H, N), logits=(H, N, K), G=(H, N, K), dWa=(H, C), dba=(H,),
+                      dWt=(H, C, K), dbt=(H, K))
+        for h in range(H):
+            one = _single_head(c, inp, h, gpu)
+            for k, b in bounds.items():
+                m = got[k].double().reshape(shapes[k])[h]
+                s = one[k].double().reshape(m.shape)
+                mp.check(m, Bnd(b.ref[h], b.err[h]), 'multi ' + k, zero_ref=True)
+                mp.check(s, Bnd(b.ref[h], b.err[h]), 'single ' + k, zero_ref=True)
+                assert bool(((m - s).abs() <= 2 * b.err[h]).all()), (k, h)
+            ml, sl = got['loss'].double().reshape(H, 1 + N)[h], one['loss'].double()
+            assert bool(((ml[1:] - sl[1:]).abs() <= 2 * per_b.err[h]).all())
+            assert abs(float(ml[0] - sl[0])) <= 2 * float(mean_b.err[h])
+
+
+def test_identical_heads_give_identical_bits(gpu):
+    c = mr.case_by_name('f32_c2048_h4')
+    inp = _dev(mr.inputs(c, identical_heads=True), gpu)
+    for train in (True, False):
+        r = _Run(c, inp, gpu, train=train)
+        r.run()
+        torch.cuda.synchronize()
+        H = c['H']
+        for k, v in r.got().items():
+            if k == 'fused_probs':
+                continue
+            rows = v.reshape(H, -1).view(torch.int32)
+            for h in range(1, H):
+                assert torch.equal(rows[0], rows[h]), (train, k, h)
+        if not train:
+            pred = r.pred[:H * c['N']].reshape(H, -1)
+            assert all(torch.equal(pred[0], pred[h]) for h in range(1, H))
+
+
+# ------------------------------------------------------------------------------------------ the heads update
+def _sgd_problem(dev, H=3, sizes=(10, 7, 1, 1031)):
+    g = torch.Generator().manual_seed(11)
+    ws = [torch.randn((H, n), generator=g).to(dev) for n in sizes]
+    total = H * sum(sizes)
+    grad = torch.randn((total,), generator=g).to(dev)
+    acc = torch.randn((total,), generator=g).to(dev)
+    wd = [[0.01 * (i + 1) * (h + 1) if n > 1 else 0.0 for h in range(H)] for i, n in enumerate(sizes)]
+    lr = [0.1, 0.03, 0.5][:H]
+    mom = [0.9, 0.0, 0.5][:H]
+    return ws, grad, acc, wd, lr, mom
+
+
+def test_heads_update_equals_H_single_updates(gpu):
+    """different lr / momentum / decay per head, segment sizes that are no multiple of the vector width"""
+    H, sizes = 3, (10, 7, 1, 1031)
+    ws, grad, acc, wd, lr, mom = _sgd_problem(gpu, H, sizes)
+    ref_w = [w.clone() for w in ws]
+    ref_acc = acc.clone()
+    sgd = mh.MultiHeadSGD(ws, wd, grad, acc, lr, mom, grad_scale=0.5)
+    sgd.run()
+    torch.cuda.synchronize()
+    lib = cof.load_library()
+    offs, o = [], 0
+    for n in sizes:
+        offs.append(o)
+        o += H * n
+    for h in range(H):
+        wh = [w[h].clone() for w in ref_w]
+        gh = torch.cat([grad[offs[i] + h * n: offs[i] + (h + 1) * n] for i, n in enumerate(sizes)]).contiguous()
+        ah = torch.cat([ref_acc[offs[i] + h * n: offs[i] + (h + 1) * n] for i, n in enumerate(sizes)]).contiguous()
+        wp = (ctypes.c_void_p * len(sizes))(*[w.data_ptr() for w in wh])
+        sz = (ctypes.c_size_t * len(sizes))(*sizes)
+        wdh = (ctypes.c_float * len(sizes))(*[wd[i][h] for i in range(len(sizes))])
+        rc = lib.apa_momentum_sgd_step(len(sizes), wp, sz, wdh, gh.data_ptr(), ah.data_ptr(), lr[h], mom[h], 0.5,
+                                       gp.stream_ptr())
+        assert rc == 0, lib.apa_last_error()
+        torch.cuda.synchronize()
+        o = 0
+        for i, n in enumerate(sizes):
+            assert torch.equal(ws[i][h].view(torch.int32), wh[i].view(torch.int32)), ('weights', h, i)
+            assert torch.equal(acc[offs[i] + h * n: offs[i] + (h + 1) * n].view(torch.int32),
+                               ah[o:o + n].view(torch.int32)), ('accumulator', h, i)
+            o += n
+
+
+# ------------------------------------------------------------------------------------------ the classes and the epochs
+EC = mr.case('epoch_f32_c64', 3, 3, 5, 64, 6)
+STEPS = 3
+
+
+def _epoch_problem(dev, bf16=False):
+    g = torch.Generator().manual_seed(77)
+    H, N, P, C, K = EC['H'], EC['N'], EC['P'], EC['C'], EC['K']
+    X = torch.randn((T, P, 1, C), generator=g).clamp_min(0).to(torch.bfloat16 if bf16 else torch.float32).to(dev)
+    labels = torch.randint(0, K, (T,), generator=g).to(dev)
+    cache = cof.FeatureCache(X, labels)
+    Wa = (torch.randn((H, C), generator=g) / C ** 0.5).to(dev)
+    ba = torch.full((H,), 0.1).to(dev)
+    Wt = (torch.randn((H, C, K), generator=g) / C ** 0.5).to(dev)
+    bt = (torch.randn((H, K), generator=g) * 0.1).to(dev)
+    return cache, [Wa, ba, Wt, bt]
+
+
+def _orders(dev, count, rounds=3):
+    g = torch.Generator().manual_seed(3)
+    out = []
+    for r in range(rounds):
+        o = torch.randint(0, T, (count,), generator=g).to(torch.int32)
+        o[(2 * r + 1) % count] = T + 1          # one id outside the cache
+        out.append(o.to(dev))
+    return out
+
+
+def _trainer(dev):
+    cache, params = _epoch_problem(dev)
+    H, N, C, K = EC['H'], EC['N'], EC['C'], EC['K']
+    step = mh.MultiHeadTrainStep(cache.select(torch.zeros((N,), dtype=torch.int32, device=dev)), *params, 'cache',
+                                 relu_att=True, keep_prob=mr.KEEP, seed=mr.SEED, offset=mr.OFFSET)
+    _, total = mh.grad_layout(H, C, K)
+    acc = torch.zeros((total,), dtype=torch.float32, device=dev)
+    sgd = mh.MultiHeadSGD(params, [[1e-3, 2e-3, 0.0], 0.0, [1e-3, 0.0, 5e-3], 0.0], step.grad_flat, acc,
+                          [0.1, 0.2, 0.3], [0.9, 0.5, 0.0])
+    return cache, params, step, sgd, acc
+
+
+LRS = [[0.1, 0.2, 0.3], [0.05, 0.2, 0.0], [0.1, 0.1, 0.1]]
+STEP_OUT = ('logits', 'att', 'zsave', 'abar', 'G', 'grad_flat')
+
+
+def test_train_epoch_equals_the_loop_of_steps(gpu):
+    order = _orders(gpu, STEPS * EC['N'], 1)[0]
+    N = EC['N']
+    cache_a, params_a, step_a, sgd_a, acc_a = _trainer(gpu)
+    log = []
+    for s in range(STEPS):
+        step_a.rebind(index=order[s * N:(s + 1) * N], offset=mr.OFFSET + s)
+        step_a.run()
+        sgd_a.run(lr=LRS[s])
+        log.append(step_a.loss.clone())
+    torch.cuda.synchronize()
+    cache_b, params_b, step_b, sgd_b, acc_b = _trainer(gpu)
+    ep = mh.MultiHeadTrainEpoch(step_b, sgd_b, STEPS)
+    loss = ep.run(order, LRS)
+    torch.cuda.synchronize()
+    assert torch.equal(loss, torch.stack(log))
+    for a, b in zip(params_a, params_b):
+        assert torch.equal(a, b)
+    assert torch.equal(acc_a, acc_b) and float(acc_a.abs().max()) > 0
+    for k in STEP_OUT:
+        assert torch.equal(getattr(step_a, k), getattr(step_b, k)), k
+    assert int(cache_a.status) == int(cache_b.status) == 1
+    assert step_b.offset == mr.OFFSET + STEPS      # the dropout counter advanced once per step for all heads
+
+
+def test_eval_epoch_equals_the_loop_of_steps_and_stops_at_count(gpu):
+    """count = 7 rows, N = 3: two full steps and a last batch of one, in guarded outputs"""
+    H, N, P, C, K = EC['H'], EC['N'], EC['P'], EC['C'], EC['K']
+    count = 7
+    order = _orders(gpu, count, 1)[0]
+    cache, params = _epoch_problem(gpu)
+    lab = cache.labels[order.long().clamp(0, T - 1)].contiguous()
+    want = dict(logits=torch.empty((H, count, K), device=gpu), probs=torch.empty((H, count, K), device=gpu),
+                pred=torch.empty((H, count), dtype=torch.int64, device=gpu), fused_probs=torch.empty((count, K), device=gpu),
+                fused_pred=torch.empty((count,), dtype=torch.int64, device=gpu))
+    losses = []
+    for s in range(3):
+        n = min(N, count - s * N)
+        st = mh.MultiHeadEvalStep(cache.select(order[s * N:s * N + n]), *params, lab[s * N:s * N + n].contiguous(),
+                                  relu_att=True)
+        st.run()
+        torch.cuda.synchronize()
+        for k in ('logits', 'probs', 'pred'):
+            want[k][:, s * N:s * N + n] = getattr(st, k)
+        want['fused_probs'][s * N:s * N + n] = st.fused_probs
+        want['fused_pred'][s * N:s * N + n] = st.fused_pred
+        losses.append(st.loss.clone())
+        last = st
+    assert int(cache.status) == 1
+    cache.status.zero_()
+    f32, Gd = torch.float32, gp.Guarded
+    o = {'logits': Gd(H * count, K, K, f32, gpu), 'probs': Gd(H * count, K, K, f32, gpu),
+         'fused_probs': Gd(count, K, K, f32, gpu), 'att': Gd(H * N, P, P, f32, gpu), 'zsave': Gd(H * N, C, C, f32, gpu),
+         'abar': Gd(1, H * N, H * N, f32, gpu), 'loss': Gd(3 * H, 1 + N, 1 + N, f32, gpu)}
+    pred = torch.full((H * count + 32,), -7, dtype=torch.int64, device=gpu)
+    fpred = torch.full((count + 32,), -7, dtype=torch.int64, device=gpu)
+    nb = max(mh.workspace_bytes(H, n, P, C, K) for n in (1, N))
+    ws = Gd(1, nb // 4, nb // 4, f32, gpu)
+    for b in list(o.values()) + [ws]:
+        b.snapshot()
+    lib = mh.load_library()
+    ep = cof.ApaEpoch(order.data_ptr(), count)
+    fc = cof.ApaFeatureCache(None, T, 0, cache.status.data_ptr())
+    heads = mh.ApaMultihead(H, *[p.data_ptr() for p in params])
+    A = ctypes.addressof
+    rc = lib.apa_multihead_eval_epoch_cached(
+        A(ep), A(fc), A(heads), cof.APA_SCORES_SOFTMAX, cache.features.data_ptr(), lab.data_ptr(), o['logits'].ptr,
+        o['att'].ptr, o['zsave'].ptr, o['abar'].ptr, o['loss'].ptr, o['probs'].ptr, pred.data_ptr(), o['fused_probs'].ptr,
+        fpred.data_ptr(), ws.ptr, nb, N, P, C, K, cof.APA_FLAG_RELU_ATT, cof.APA_DTYPE_F32, gp.stream_ptr())
+    assert rc == 0, lib.apa_last_error()
+    torch.cuda.synchronize()
+    for k, b in o.items():
+        b.check_guards(k)
+    ws.check_guards('workspace')
+    assert bool((pred[H * count:] == -7).all()) and bool((fpred[count:] == -7).all())
+    assert torch.equal(o['logits'].view.reshape(H, count, K), want['logits'])
+    assert torch.equal(o['probs'].view.reshape(H, count, K), want['probs'])
+    assert torch.equal(o['fused_probs'].view, want['fused_probs'])
+    assert torch.equal(pred[:H * count].reshape(H, count), want['pred'])
+    assert torch.equal(fpred[:count], want['fused_pred'])
+    lg = o['loss'].view.reshape(3, H * (1 + N))
+    for s in range(2):
+        assert torch.equal(lg[s].reshape(H, 1 + N), losses[s]), s
+    assert torch.equal(lg[2][:H * 2].reshape(H, 2), losses[2])       # the last step's slot holds [H][1 + 1]
+    # att / zsave / abar: the last step's, stacked for its batch of one
+    assert torch.equal(o['att'].view.reshape(-1)[:H * P], last.att.reshape(-1))
+    assert torch.equal(o['zsave'].view.reshape(-1)[:H * C], last.zsave.reshape(-1))
+    assert int(cache.status) == 1
+    # the class gives the same rows
+    epc = mh.MultiHeadEvalEpoch(cache, N, *params, capacity=16, relu_att=True)
+    probs, cpred, fprobs, fcpred = epc.run(order)
+    torch.cuda.synchronize()
+    assert torch.equal(probs, want['probs']) and torch.equal(cpred, want['pred'])
+    assert torch.equal(fprobs, want['fused_probs']) and torch.equal(fcpred, want['fused_pred'])
+
+
+# ------------------------------------------------------------------------------------------ hipGraph rows
+def _row_train_step(dev):
+    rounds = [{'index': o} for o in _orders(dev, EC['N'])]
+
+    def make():
+        cache, params, step, sgd, acc = _trainer(dev)
+        state = {k: getattr(step, k) for k in STEP_OUT + ('loss',)}
+        state['status'] = cache.status
+        return gr.Case(step.run, {'index': step._index}, state, STEP_OUT + ('loss',), 'logits')
+    return make, rounds
+
+
+def _row_eval_step(dev):
+    rounds = [{'index': o} for o in _orders(dev, EC['N'])]
+
+    def make():
+        cache, params = _epoch_problem(dev)
+        st = mh.MultiHeadEvalStep(cache.select(torch.zeros((EC['N'],), dtype=torch.int32, device=dev)), *params, 'cache',
+                                  relu_att=True)
+        names = ('logits', 'att', 'zsave', 'abar', 'loss', 'probs', 'pred', 'fused_probs', 'fused_pred')
+        state = {k: getattr(st, k) for k in names}
+        state['status'] = cache.status
+        return gr.Case(st.run, {'index': st._index}, state, names, 'probs')
+    return make, rounds
+
+
+def _row_sgd(dev):
+    g = torch.Generator().manual_seed(5)
+    ws0, grad0, acc0, wd, lr, mom = _sgd_problem(dev)
+    rounds = [{'grad': torch.randn(grad0.shape, generator=g).to(dev)} for _ in range(3)]
+
+    def make():
+        ws, grad, acc, wd, lr, mom = _sgd_problem(dev)
+        sgd = mh.MultiHeadSGD(ws, wd, grad, acc, lr, mom)
+        state = {'w%d' % i: w for i, w in enumerate(ws)}
+        state['acc'] = acc
+        return gr.Case(sgd.run, {'grad': grad}, state, (), 'w3')
+    return make, rounds
+
+
+def _row_train_epoch(dev):
+    rounds = [{'order': o} for o in _orders(dev, STEPS * EC['N'])]
+
+    def make():
+        cache, params, step, sgd, acc = _trainer(dev)
+        ep = mh.MultiHeadTrainEpoch(step, sgd, STEPS)
+        order = torch.zeros((STEPS * EC['N'],), dtype=torch.int32, device=dev)
+        state = {k: getattr(step, k) for k in STEP_OUT}
+        state.update(loss=ep.loss, acc=acc, status=cache.status, Wa=params[0], ba=params[1], Wt=params[2], bt=params[3])
+
+        def call():
+            ep.run(order, LRS, offset=mr.OFFSET)     # (a capture freezes the key: the same key in every eager call)
+        return gr.Case(call, {'order': order}, state, STEP_OUT + ('loss',), 'loss')
+    return make, rounds
+
+
+def _row_eval_epoch(dev):
+    count = 7
+    rounds = [{'order': o} for o in _orders(dev, count)]
+
+    def make():
+        cache, params = _epoch_problem(dev)
+        epc = mh.MultiHeadEvalEpoch(cache, EC['N'], *params, capacity=count, relu_att=True, labels='cache')
+        order = torch.zeros((count,), dtype=torch.int32, device=dev)
+
+        def call():
+            epc.run(order)
+            return dict(logits=epc.logits, probs=epc.probs, pred=epc.pred, fused_probs=epc.fused_probs,
+                        fused_pred=epc.fused_pred, loss=epc.loss)
+        return gr.Case(call, {'order': order}, {'status': cache.status}, (), 'probs')
+    return make, rounds
+
+
+ROWS = [('apa_multihead_train_step_cached', _row_train_step), ('apa_multihead_eval_step_cached', _row_eval_step),
+        ('apa_momentum_sgd_step_heads', _row_sgd), ('apa_multihead_train_epoch_cached', _row_train_epoch),
+        ('apa_multihead_eval_epoch_cached', _row_eval_epoch)]
+
+
+def test_every_stream_taking_entry_point_has_a_row():
+    assert sorted(r[0] for r in ROWS) == [s for s in mh.exported_symbols() if s != 'apa_multihead_workspace_bytes']
+
+
+@pytest.mark.parametrize('r', ROWS, ids=[r[0] for r in ROWS])
+def test_replay_equals_eager(gpu, r):
+    make, rounds = r[1](gpu)
+    gr.replay_equals_eager(r[0], make, rounds, R=3)

@@ -1992,6 +1992,119 @@ def run_map393(cof, dev, args):
             'classes_with_positives': len(got['aps'])}
 
 
+SWEEPS = {'sweep002_bf16': torch.bfloat16, 'sweep002_fp32': torch.float32}
+
+
+def run_sweep(cof, dev, args, which):
+    """sweep002_bf16 / sweep002_fp32: H = 4 cfg 002 heads on a RESIDENT cache of T 14x14x2048 maps (K = 393, dropout
+    keep 0.2, a fresh shuffled index per step), three training routes ALTERNATING in one process, medians of five
+    loops of `--steps` steps and the loops' spread:
+      a_multihead     one apa_multihead_train_step_cached + one apa_momentum_sgd_step_heads
+      b_four_single   four HeadTrainStep cached steps + four BoundMomentumSGD updates on the same batches
+      c_one_single    one single-head step + update, for scale
+    and the evaluation step against four HeadEvalStep calls the same way."""
+    from attentionalpoolingaction_amd.custom_ops import multihead as mh
+    Hh, C, K, hw, N = 4, 2048, args.classes or 393, args.hw, args.batch
+    P = hw * hw
+    T = max(int(args.cache_images), 4 * N)
+    g = torch.Generator().manual_seed(42)
+    labels = torch.randint(0, K, (T,), generator=g).to(dev)
+    cache = cof.FeatureCache.empty((T, hw, hw, C), SWEEPS[which], dev, labels=labels)
+    for first in range(0, T, 256):
+        n = min(256, T - first)
+        cache.write(first, _features(n, P, C, torch.bfloat16, dev, seed=42 + first).view(n, hw, hw, C))
+    Wa = (torch.randn(Hh, C, generator=g) / C ** 0.5).to(dev); ba = torch.zeros(Hh, device=dev)
+    Wt = (torch.randn(Hh, C, K, generator=g) / C ** 0.5).to(dev); bt = torch.zeros(Hh, K, device=dev)
+    batches = [b for e in range(4) for b in cache.epoch(N, seed=e)]
+    batch0 = cache.select(batches[0])
+    lrs, moms = [1e-3, 3e-4, 1e-4, 3e-5], [0.9] * Hh
+    # (a)
+    st_a = mh.MultiHeadTrainStep(batch0, Wa, ba, Wt, bt, 'cache', keep_prob=0.2, seed=42)
+    acc_a = torch.zeros_like(st_a.grad_flat)
+    sgd_a = mh.MultiHeadSGD([Wa, ba, Wt, bt], [1e-4, 0.0, 1e-4, 0.0], st_a.grad_flat, acc_a, lrs, moms)
+    # (b), (c): single heads on copies of the rows
+    singles, wsets = [], []
+    for h in range(Hh):
+        w = [Wa[h].clone().view(C, 1), ba[h:h + 1].clone(), Wt[h].clone(), bt[h].clone()]
+        flat = torch.zeros(sum(t.numel() for t in w), device=dev)
+        views, o = [], 0
+        for t in w:
+            views.append(flat[o:o + t.numel()].view(t.shape))
+            o += t.numel()
+        st = cof.HeadTrainStep(batch0, batch0, *w, None, (None, None) + tuple(views),
+                               flags=cof.attn_flags(False, False, True), keep_prob=0.2, seed=42, offset=0)
+        opt = cof.BoundMomentumSGD(w, [1e-4, 0.0, 1e-4, 0.0], flat, torch.zeros_like(flat))
+        singles.append((st, opt))
+        wsets.append(w)
+    state = {'a': 0, 'b': 0, 'c': 0, 'ea': 0, 'eb': 0}
+
+    def nxt(k):
+        idx = batches[state[k] % len(batches)]
+        state[k] += 1
+        return idx, state[k]
+
+    def step_a():
+        idx, s = nxt('a')
+        st_a.rebind(index=idx, offset=s)
+        st_a.run()
+        sgd_a.run()
+
+    def step_b():
+        idx, s = nxt('b')
+        for h, (st, opt) in enumerate(singles):
+            st.rebind(index=idx, offset=s)
+            st.run()
+            opt.run(lrs[h], moms[h])
+
+    def step_c():
+        idx, s = nxt('c')
+        st, opt = singles[0]
+        st.rebind(index=idx, offset=s)
+        st.run()
+        opt.run(lrs[0], moms[0])
+
+    # both evaluation routes read the cache's labels and log the loss; route (a) also writes the fused scores
+    ev_a = mh.MultiHeadEvalStep(batch0, Wa, ba, Wt, bt, 'cache')
+    ev_b = [cof.HeadEvalStep(batch0, batch0, *w) for w in wsets]
+
+    def eval_a():
+        idx, _ = nxt('ea')
+        ev_a.rebind(index=idx)
+        ev_a.run()
+
+    def eval_b():
+        idx, _ = nxt('eb')
+        for ev in ev_b:
+            ev.rebind(index=idx)
+            ev.run()
+
+    forms = {'a_multihead': step_a, 'b_four_single': step_b, 'c_one_single': step_c, 'eval_a_multihead': eval_a,
+             'eval_b_four_single': eval_b}
+    if args.only:
+        forms = {k: v for k, v in forms.items() if k == args.only}
+    for _ in range(args.warmup):
+        for step in forms.values():
+            step()
+    torch.cuda.synchronize()
+    runs = {k: [] for k in forms}
+    for _ in range(5):
+        for name, step in forms.items():
+            sec, _ = timed(step, args.steps, 0, min_ms=0.0, repeats=1)
+            runs[name].append(sec * 1e6)
+    med = {k: sorted(v)[len(v) // 2] for k, v in runs.items()}
+    out = {'workload': '{}: H = 4 cfg 002 heads from a resident {} cache, {} of {} x {}x{}x{}, K={}, dropout keep=0.2, '
+                       'routes alternating in one process'.format(which, 'bf16' if which.endswith('bf16') else 'fp32', N, T,
+                                                                  hw, hw, C, K),
+           'us_per_step': {k: round(v, 2) for k, v in med.items()},
+           'us_per_step_runs': {k: [round(x, 2) for x in v] for k, v in runs.items()},
+           'us_per_step_spread': {k: round(max(v) - min(v), 2) for k, v in runs.items()}}
+    if 'a_multihead' in med and 'b_four_single' in med:
+        out['a_over_b'] = round(med['a_multihead'] / med['b_four_single'], 4)
+    if 'eval_a_multihead' in med and 'eval_b_four_single' in med:
+        out['eval_a_over_b'] = round(med['eval_a_multihead'] / med['eval_b_four_single'], 4)
+    return out
+
+
 def timed(fn, steps, warmup, min_ms=50.0, repeats=5):
     """median over >= `repeats` timed loops of `steps` steps each (>= min_ms of device time in total)."""
     for _ in range(warmup):
@@ -2040,14 +2153,16 @@ def main():
                                                          'cached002_fp8', 'cached002_bf16', 'cached_perclass_bf16',
                                                          'cached003_bf16', 'eval003_cached_bf16',
                                                          'epoch002_fp8',
-                                                         'epoch002_bf16', 'explain002', 'map393'] +
+                                                         'epoch002_bf16', 'explain002', 'map393'] + sorted(SWEEPS) +
                     sorted(EVAL_CLIPS) + sorted(RANK_WORKLOADS) + sorted(CACHED_CLIPS) + sorted(CLIP_EPOCHS))
     ap.add_argument('--clips', type=int, default=8, help='video_*: clips per batch')
     ap.add_argument('--frames', type=int, default=4, help='video_*: frames per clip')
     ap.add_argument('--only', default=None, choices=['clip_one_call', 'module_path', 'flat_one_call',
                                                      'multilabel_one_call', 'softmax_one_call', 'one_call',
                                                      'sequence', 'rank_one_call', 'rank1_one_call', 'a_cached',
-                                                     'b_gather_rebind_plain', 'c_plain_fixed'],
+                                                     'b_gather_rebind_plain', 'c_plain_fixed', 'a_multihead',
+                                                     'b_four_single', 'c_one_single', 'eval_a_multihead',
+                                                     'eval_b_four_single'],
                     help='video_* / hico002 / charades_clips / eval_* / rank* / cached003_bf16 / eval003_cached_bf16: run '
                          'one variant alone (kernel traces)')
     ap.add_argument('--batch', type=int, default=32)
@@ -2101,6 +2216,9 @@ def main():
         return
     if args.workload in ('epoch002_fp8', 'epoch002_bf16'):
         print(json.dumps(run_epoch(cof, dev, args, args.workload)))
+        return
+    if args.workload in SWEEPS:
+        print(json.dumps(run_sweep(cof, dev, args, args.workload)))
         return
     if args.workload in CACHED_CLIPS:
         print(json.dumps(run_cached_clips(cof, dev, args, args.workload)))
