@@ -59,8 +59,6 @@ struct ClipLayout {
   }
 };
 
-typedef float f4u __attribute__((ext_vector_type(4), aligned(4)));
-
 __device__ __forceinline__ float clip_t(const ClipSeg& s, float g, float w) { return fmaf(s.wd, w, g); }
 
 // block-wide sum of one double per thread: xor-shuffle tree inside each wave, then the waves in index order

@@ -14,6 +14,13 @@ struct bf16_t { uint16_t v; };
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
+typedef float f4u __attribute__((ext_vector_type(4), aligned(4)));   // 16 bytes at any 4-byte aligned address
+
+// D = A B + C on v_mfma_f32_16x16x4_f32 (exact fp32): lane (r, kq) = (lane & 15, lane >> 4) supplies A[row r][k = kq]
+// and B[k = kq][column r] and holds D[row 4 kq + reg][column r]
+__device__ __forceinline__ f32x4 mfma16(float a, float b, f32x4 c) {
+  return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
+}
 
 // ---------------------------------------------------------------------------------------------
 // Cross-lane reductions.  In-row (16 lanes) butterflies run on DPP (no LDS traffic); the four
@@ -81,6 +88,37 @@ __device__ __forceinline__ int wave_min_i(int v) {
   const int r0 = __builtin_amdgcn_readlane(v, 0), r1 = __builtin_amdgcn_readlane(v, 16);
   const int r2 = __builtin_amdgcn_readlane(v, 32), r3 = __builtin_amdgcn_readlane(v, 48);
   return min(min(r0, r1), min(r2, r3));
+}
+
+// First maximal index of row[0 .. K) on one wave, lanes striding by 64 (wave-uniform result); SIG: the row's sigmoids
+// go to sig
+template <bool SIG>
+__device__ __forceinline__ int wave_first_max(const float* __restrict__ row, int K, int lane, float* __restrict__ sig) {
+  float m = -INFINITY;
+  int arg = 0x7fffffff;
+  for (int k = lane; k < K; k += 64) {
+    const float x = row[k];
+    if (x > m) { m = x; arg = k; }
+    if (SIG) sig[k] = 1.0f / (1.0f + expf(-x));
+  }
+  const float mw = wave_max(m);
+  return wave_min_i((m == mw) ? arg : 0x7fffffff);
+}
+
+// tf.train.MomentumOptimizer's element update with the slim L2 term: a <- momentum a + (gscale g + wd w),
+// w <- w - lr a; and four elements of it
+__device__ __forceinline__ void momentum_sgd_update(float& a, float& w, float g, float wd, float lr, float momentum,
+                                                    float gscale) {
+  a = fmaf(momentum, a, fmaf(wd, w, g * gscale));
+  w = fmaf(-lr, a, w);
+}
+__device__ __forceinline__ void momentum_sgd_update4(f4u& a, f4u& w, const f4u& g, float wd, float lr, float momentum,
+                                                     float gscale) {
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    a[e] = fmaf(momentum, a[e], fmaf(wd, w[e], g[e] * gscale));
+    w[e] = fmaf(-lr, a[e], w[e]);
+  }
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -48,10 +48,10 @@ __global__ __launch_bounds__(256) void sgemm16_kernel(const float* __restrict__ 
       a[t] = (ok && i_ok) ? ap[(size_t)kk * a_sk] : 0.f;
       b[t] = (ok && j_ok) ? bp[(size_t)kk * b_sk] : 0.f;
     }
-    acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a[0], b[0], acc0, 0, 0, 0);
-    acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a[1], b[1], acc1, 0, 0, 0);
-    acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a[2], b[2], acc0, 0, 0, 0);
-    acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a[3], b[3], acc1, 0, 0, 0);
+    acc0 = mfma16(a[0], b[0], acc0);
+    acc1 = mfma16(a[1], b[1], acc1);
+    acc0 = mfma16(a[2], b[2], acc0);
+    acc1 = mfma16(a[3], b[3], acc1);
   }
   // C/D layout: col = lane & 15, row = (lane >> 4) * 4 + reg
   const int col = tj * 16 + (lane & 15);

@@ -17,7 +17,7 @@
 // kernels; nothing is accumulated with atomics, every run repeats bit for bit.  The chain gradients dw_r / db_r are
 // summed directly (the kernel has Z_{r-1} and dZ~_r of its pixel at hand): 2 (R - 1) partials per block.
 //
-// One wave owns a pixel; a lane owns NVL 16-byte vectors of its row (vector j * 64 + lane), all in registers:
+// One wave owns a pixel and keeps its row in registers (apa_rowpass.h: ownership, loader, dot, keep bits, merges):
 // NVL * EPV = 8 elements per lane serve C <= 512, 32 elements C <= 2048 (the ResNet conv5 map: every lane busy).
 // The forward pass keeps its R accumulator sets in registers and the attention weights in LDS; the backward pass keeps
 // the image's R rows of dz and the attention weights in LDS, its dwa accumulators in registers: two blocks per CU.
@@ -27,6 +27,7 @@
 
 #include "apa_device.h"
 #include "apa_internal.h"
+#include "apa_rowpass.h"
 
 namespace apa {
 
@@ -50,59 +51,6 @@ __device__ __forceinline__ void rank_chain(float z0, const float* cw, const floa
   for (int r = 0; r < RMAX; ++r) A[r] = r < R ? (act == M1_ACT_RELU ? fmaxf(Z[r], 0.f) : Z[r]) : 0.f;
 }
 
-// keep decisions of the lane's NVL * EPV elements of pixel row `ebase`, one bit each (library stream, device counter
-// or the caller's bit image: apa_device.h)
-template <int NVL, int EPV>
-__device__ __forceinline__ uint32_t rank_keep_bits(uint64_t ebase, int lane, int nvec, uint32_t k0, uint32_t k1,
-                                                   uint32_t thresh) {
-  uint32_t bits = 0;
-#pragma unroll
-  for (int j = 0; j < NVL; ++j) {
-    const int v = j * 64 + lane;
-    if (v < nvec) {
-#pragma unroll
-      for (int e = 0; e < EPV; e += 2) {
-        float m0, m1;
-        rng_keep2_x(ebase + (uint64_t)v * EPV + e, k0, k1, thresh, m0, m1);
-        bits |= (m0 != 0.f ? 1u : 0u) << (j * EPV + e);
-        bits |= (m1 != 0.f ? 1u : 0u) << (j * EPV + e + 1);
-      }
-    }
-  }
-  return bits;
-}
-
-// The 4 waves' register rows of EL floats per lane, summed in a fixed order into dst[c]: waves 1..3 pass theirs
-// through LDS, wave 0 adds (w0 + w1) + (w2 + w3) and stores.  Every thread of the block calls it.
-template <int NVL, int EPV>
-__device__ __forceinline__ void rank_merge_rows(const float* row, float* sm, float* dst, int wave, int lane,
-                                                int nvec) {
-  constexpr int EL = NVL * EPV;
-  __syncthreads();   // sm may still be read from the previous round
-  if (wave > 0) {
-#pragma unroll
-    for (int i = 0; i < EL; ++i) sm[((wave - 1) * EL + i) * 64 + lane] = row[i];
-  }
-  __syncthreads();
-  if (wave == 0) {
-#pragma unroll
-    for (int j = 0; j < NVL; ++j) {
-      const int v = j * 64 + lane;
-      if (v < nvec) {
-        float o[EPV];
-#pragma unroll
-        for (int e = 0; e < EPV; ++e) {
-          const int i = j * EPV + e;
-          o[e] = (row[i] + sm[(0 * EL + i) * 64 + lane]) + (sm[(1 * EL + i) * 64 + lane] + sm[(2 * EL + i) * 64 + lane]);
-        }
-#pragma unroll
-        for (int e = 0; e < EPV; e += 4)
-          *reinterpret_cast<float4*>(dst + (size_t)v * EPV + e) = make_float4(o[e], o[e + 1], o[e + 2], o[e + 3]);
-      }
-    }
-  }
-}
-
 // --------------------------------------------------------------------------------------------
 // Forward pass.  grid N * S blocks of 256 threads (m1_plan); block (n, s) owns pixels [p_begin, p_end) of image n,
 // wave w the pixels p_begin + w, + 4, ...  Outputs: z0 [N,P] (FUSED; else it is an input), att [N,P,R], and per block
@@ -122,6 +70,7 @@ __global__ __launch_bounds__(256, 2) void m1r_pool_fwd_kernel(
   if (TRAIN) rng_key_dev_x(seed, offset_dev ? *offset_dev : offset, thresh, k0, k1);
   const int blk = blockIdx.x, n = blk / S, s = blk % S;
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  // 64-bit quotients: nothing on this path checks m1_pix_range_ok, which m1_pix_range's 32-bit form needs
   const int p_begin = (int)(((long)s * P) / S), p_end = (int)(((long)(s + 1) * P) / S);
   const int nvec = C / EPV;
   float cw[RMAX - 1], cb[RMAX - 1];
@@ -138,14 +87,9 @@ __global__ __launch_bounds__(256, 2) void m1r_pool_fwd_kernel(
     for (int i = 0; i < EL; ++i) acc[r][i] = 0.f;
   float asum[RMAX] = {0.f, 0.f, 0.f, 0.f};
   const T* xim = X + (size_t)n * P * C;
-  const uint4 zero4 = make_uint4(0u, 0u, 0u, 0u);
   uint4 nxt[NVL];
   if (p_begin + wave < p_end) {
-#pragma unroll
-    for (int j = 0; j < NVL; ++j) {
-      const int v = j * 64 + lane;
-      nxt[j] = v < nvec ? ld16(xim + (size_t)(p_begin + wave) * C + (size_t)v * EPV) : zero4;
-    }
+    row_load<T, NVL>(nxt, xim + (size_t)(p_begin + wave) * C, lane, nvec);
   }
   // the attention weights wait in LDS (zero beyond C): the registers belong to the R accumulator sets.  Staged behind
   // the first row's loads, which travel meanwhile
@@ -158,26 +102,12 @@ __global__ __launch_bounds__(256, 2) void m1r_pool_fwd_kernel(
 #pragma unroll
     for (int j = 0; j < NVL; ++j) Vec<T>::unpack(nxt[j], x + j * EPV);
     if (p + 4 < p_end) {   // the next row travels while this one is consumed
-#pragma unroll
-      for (int j = 0; j < NVL; ++j) {
-        const int v = j * 64 + lane;
-        nxt[j] = v < nvec ? ld16(xim + (size_t)(p + 4) * C + (size_t)v * EPV) : zero4;
-      }
+      row_load<T, NVL>(nxt, xim + (size_t)(p + 4) * C, lane, nvec);
     }
     const size_t px = (size_t)n * P + p;
     float zl;
     if (FUSED) {
-      float d = 0.f;
-#pragma unroll
-      for (int j = 0; j < NVL; ++j) {
-#pragma unroll
-        for (int e = 0; e < EPV; e += 4) {
-          const float4 w4 = *reinterpret_cast<const float4*>(sm_wa + (j * 64 + lane) * EPV + e);
-          const int i = j * EPV + e;
-          d = fmaf(x[i], w4.x, d); d = fmaf(x[i + 1], w4.y, d);
-          d = fmaf(x[i + 2], w4.z, d); d = fmaf(x[i + 3], w4.w, d);
-        }
-      }
+      const float d = row_dot<NVL, EPV>(x, sm_wa, lane);
       zl = wave_sum(d) + bias;
       if (lane == 0) z0[px] = zl;
     } else {
@@ -187,7 +117,7 @@ __global__ __launch_bounds__(256, 2) void m1r_pool_fwd_kernel(
     rank_chain(zl, cw, cb, R, act, Z, A);
     if (lane < R) att[px * R + lane] = lane == 0 ? A[0] : (lane == 1 ? A[1] : (lane == 2 ? A[2] : A[3]));
     if (TRAIN) {
-      const uint32_t bits = rank_keep_bits<NVL, EPV>((uint64_t)px * C, lane, nvec, k0, k1, thresh);
+      const uint32_t bits = row_keep_bits<RngAny, NVL, EPV>((uint64_t)px * C, lane, nvec, k0, k1, thresh);
 #pragma unroll
       for (int i = 0; i < EL; ++i) x[i] = (bits >> i) & 1u ? x[i] : 0.f;
     }
@@ -205,7 +135,7 @@ __global__ __launch_bounds__(256, 2) void m1r_pool_fwd_kernel(
   float* pa = pacc + (size_t)blk * R * C;
 #pragma unroll
   for (int r = 0; r < RMAX; ++r)
-    if (r < R) rank_merge_rows<NVL, EPV>(acc[r], sm, pa + (size_t)r * C, wave, lane, nvec);
+    if (r < R) row_merge4<NVL, EPV>(acc[r], sm, pa + (size_t)r * C, wave, lane, nvec);
   if (lane == 0) {
 #pragma unroll
     for (int r = 0; r < RMAX; ++r) sm_stat[wave][r] = asum[r];
@@ -213,7 +143,7 @@ __global__ __launch_bounds__(256, 2) void m1r_pool_fwd_kernel(
   __syncthreads();
   if (threadIdx.x < RMAX) {
     const int r = threadIdx.x;
-    pstat[blk * 4 + r] = (sm_stat[0][r] + sm_stat[1][r]) + (sm_stat[2][r] + sm_stat[3][r]);
+    pstat[blk * 4 + r] = row_stat_merge4(sm_stat, r);
   }
 }
 
@@ -269,15 +199,10 @@ __global__ __launch_bounds__(256) void m1r_bwd_main_kernel(
   float cdw[RMAX - 1] = {0.f, 0.f, 0.f}, cdb[RMAX - 1] = {0.f, 0.f, 0.f}, dba = 0.f;
   const T* xim = X + (size_t)n * P * C;
   T* dxim = dX + (size_t)n * P * C;
-  const uint4 zero4 = make_uint4(0u, 0u, 0u, 0u);
   uint4 nxt[NVL];
   float z0n = 0.f;
   if (p_begin + wave < p_end) {
-#pragma unroll
-    for (int j = 0; j < NVL; ++j) {
-      const int v = j * 64 + lane;
-      nxt[j] = v < nvec ? ld16(xim + (size_t)(p_begin + wave) * C + (size_t)v * EPV) : zero4;
-    }
+    row_load<T, NVL>(nxt, xim + (size_t)(p_begin + wave) * C, lane, nvec);
     z0n = z0[(size_t)n * P + p_begin + wave];
   }
   // staged behind the first row's loads, which travel meanwhile
@@ -294,24 +219,20 @@ __global__ __launch_bounds__(256) void m1r_bwd_main_kernel(
     for (int j = 0; j < NVL; ++j) Vec<T>::unpack(nxt[j], x + j * EPV);
     const float z0p = z0n;
     if (p + 4 < p_end) {   // the next row travels while this one is consumed
-#pragma unroll
-      for (int j = 0; j < NVL; ++j) {
-        const int v = j * 64 + lane;
-        nxt[j] = v < nvec ? ld16(xim + (size_t)(p + 4) * C + (size_t)v * EPV) : zero4;
-      }
+      row_load<T, NVL>(nxt, xim + (size_t)(p + 4) * C, lane, nvec);
       z0n = z0[(size_t)n * P + p + 4];
     }
     const size_t px = (size_t)n * P + p;
     float Z[RMAX], A[RMAX];
     rank_chain(z0p, cw, cb, R, act, Z, A);
     uint32_t bits = 0xFFFFFFFFu;
-    if (TRAIN) bits = rank_keep_bits<NVL, EPV>((uint64_t)px * C, lane, nvec, k0, k1, thresh);
+    if (TRAIN) bits = row_keep_bits<RngAny, NVL, EPV>((uint64_t)px * C, lane, nvec, k0, k1, thresh);
     float dZ[RMAX];
 #pragma unroll
     for (int r = 0; r < RMAX; ++r) {
       dZ[r] = 0.f;
       if (r < R) {
-        float d = 0.f;
+        float d = 0.f;   // row_dot over the kept elements, inline: as a routine it spills (profiles/rowpass_summary.md)
 #pragma unroll
         for (int j = 0; j < NVL; ++j) {
 #pragma unroll
@@ -378,7 +299,7 @@ __global__ __launch_bounds__(256) void m1r_bwd_main_kernel(
     if (FUSED) dba += g0;
     else if (lane == 0) dzatt[px] = g0;
   }
-  if (FUSED) rank_merge_rows<NVL, EPV>(dwa, sm, pdwa + (size_t)blk * C, wave, lane, nvec);
+  if (FUSED) row_merge4<NVL, EPV>(dwa, sm, pdwa + (size_t)blk * C, wave, lane, nvec);
   if (lane == 0) {
 #pragma unroll
     for (int r = 0; r < RMAX - 1; ++r) {
@@ -391,7 +312,7 @@ __global__ __launch_bounds__(256) void m1r_bwd_main_kernel(
   __syncthreads();
   if (threadIdx.x < 8) {
     const int j = threadIdx.x;
-    const float t = (sm_stat[0][j] + sm_stat[1][j]) + (sm_stat[2][j] + sm_stat[3][j]);
+    const float t = row_stat_merge4(sm_stat, j);
     if (j < 6) pchain[(size_t)blk * 8 + j] = t;
     else if (j == 6) { if (FUSED) pdba[blk] = t; pchain[(size_t)blk * 8 + 6] = 0.f; }
     else pchain[(size_t)blk * 8 + 7] = 0.f;
@@ -586,11 +507,9 @@ int m1r_forward(const M1Call& c, const RankCall& rk, const M1Fwd& io) {
     f0.att = rk.z0;
     if ((rc = m1_att_gemv_forward(c0, f0)) != APA_OK) return rc;
   }
-  const int nvl = m1r_vectors_per_lane(C, c.dtype);
-  if (c.dtype == APA_DTYPE_F32)
-    rc = nvl == 2 ? launch_fwd<float, 2>(c, rk, rp, io, ch) : launch_fwd<float, 8>(c, rk, rp, io, ch);
-  else
-    rc = nvl == 1 ? launch_fwd<bf16_t, 1>(c, rk, rp, io, ch) : launch_fwd<bf16_t, 4>(c, rk, rp, io, ch);
+  rc = row_instance(C, c.dtype, [&](auto t, auto nvl) {
+    return launch_fwd<decltype(t), decltype(nvl)::value>(c, rk, rp, io, ch);
+  });
   if (rc != APA_OK) return rc;
   APA_LAUNCH_CHECK("m1r_pool_fwd_kernel");
   hipLaunchKernelGGL(m1r_finalize_fwd_kernel, dim3(N, (R * C / 4 + 255) / 256), dim3(256), 0, c.st,
@@ -652,12 +571,9 @@ int m1r_backward(const M1Call& c, const RankCall& rk, const M1Bwd& io) {
       if (rc != APA_OK) return rc;
     }
   }
-  const int nvl = m1r_vectors_per_lane(C, c.dtype);
-  const float* snp = small ? sn : nullptr;
-  if (c.dtype == APA_DTYPE_F32)
-    rc = nvl == 2 ? launch_bwd<float, 2>(c, rk, rp, io, ch, snp) : launch_bwd<float, 8>(c, rk, rp, io, ch, snp);
-  else
-    rc = nvl == 1 ? launch_bwd<bf16_t, 1>(c, rk, rp, io, ch, snp) : launch_bwd<bf16_t, 4>(c, rk, rp, io, ch, snp);
+  rc = row_instance(C, c.dtype, [&](auto t, auto nvl) {
+    return launch_bwd<decltype(t), decltype(nvl)::value>(c, rk, rp, io, ch, small ? sn : nullptr);
+  });
   if (rc != APA_OK) return rc;
   APA_LAUNCH_CHECK("m1r_bwd_main_kernel");
   FinishArgs fa;

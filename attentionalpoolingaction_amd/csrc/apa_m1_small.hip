@@ -21,10 +21,6 @@
 
 namespace apa {
 
-__device__ __forceinline__ f32x4 mfma16(float a, float b, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
-}
-
 // L2: logits[n,k] = sum_cc part[cc][n][k] + abar[n] * bt[k]   (fixed order over cc)
 // pstat (the folded route): abar is formed here from the pooling pass's statistics and stored for the backward pass
 __global__ __launch_bounds__(256) void m1_logits_reduce_kernel(const float* __restrict__ part,
@@ -564,7 +560,6 @@ __global__ __launch_bounds__(256) void m1_logits2_fold_kernel(const float* __res
 // G (50 KB) is re-read by every block from L2; Wt / dWt slabs are touched exactly once.
 // Everything is exact fp32 (v_mfma_f32_16x16x4_f32) with fixed summation order.
 // --------------------------------------------------------------------------------------------
-typedef float f4u __attribute__((ext_vector_type(4), aligned(4)));
 
 template <int UG>   // 16-wide k groups (role 0) / k tiles (role 1) per wave: ceil(ceil(K/16)/4)
 __global__ __launch_bounds__(256) void m1_bwd_head_kernel(

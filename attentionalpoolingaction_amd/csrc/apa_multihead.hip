@@ -1,75 +1,24 @@
 // apa_multihead.hip -- H independent class-agnostic heads (M == 1, Xatt == X) fed from ONE streaming pass over the
 // cached features per direction (include/apa_multihead.h).
 //
-// The shape of apa_m1_rank.hip, in its independent form: one wave owns a pixel, the pixel's row stays in registers, a
-// lane owns NVL 16-byte vectors of it (vector j * 64 + lane).  The forward pass keeps the H rows of Wa in LDS and H
-// accumulator sets in registers; the backward pass keeps the image's H rows of dz in LDS and H sets of dWa accumulators
-// in registers, and walks each block's pixels in the direction opposite to the forward pass (the rows the forward pass
-// of the same block read last are the likeliest to still sit in that XCD's L2).  The keep bits of a row are drawn once
-// and serve all heads.  Per-block partials are merged in a fixed order; nothing is accumulated with floating-point
-// atomics, every run repeats bit for bit.  The small products and the loss carry the head as a grid dimension, so a step
-// has the same number of launches whatever H is.  The three products are exact fp32 on v_mfma_f32_16x16x4_f32 with
-// operands straight from global memory, as in apa_m1_small.hip.
+// The shape of apa_m1_rank.hip, in its independent form, built from the same row routines (apa_rowpass.h: ownership,
+// loader, dot, keep bits, merges).  The forward pass keeps the H rows of Wa in LDS and H accumulator sets in registers;
+// the backward pass keeps the image's H rows of dz in LDS and H sets of dWa accumulators in registers, and walks each
+// block's pixels in the direction opposite to the forward pass (the rows the forward pass of the same block read last
+// are the likeliest to still sit in that XCD's L2).  The keep bits of a row are drawn once and serve all heads.  The
+// small products and the loss carry the head as a grid dimension, so a step has the same number of launches whatever H
+// is.  The three products are exact fp32 on v_mfma_f32_16x16x4_f32 (mfma16) with operands straight from global memory,
+// as in apa_m1_small.hip.  Nothing is accumulated with floating-point atomics, every run repeats bit for bit.
 #include <math.h>
 
 #include "../../include/apa_multihead.h"
 #include "apa_device.h"
 #include "apa_internal.h"
+#include "apa_rowpass.h"
 
 namespace apa {
 namespace {
 constexpr int HMAX = APA_HEADS_MAX;
-
-// keep decisions of the lane's NVL * EPV elements of the pixel row starting at flat element `ebase`, one bit each
-template <int NVL, int EPV>
-__device__ __forceinline__ uint32_t mh_keep_bits(uint64_t ebase, int lane, int nvec, uint32_t k0, uint32_t k1,
-                                                 uint32_t thresh) {
-  uint32_t bits = 0;
-#pragma unroll
-  for (int j = 0; j < NVL; ++j) {
-    const int v = j * 64 + lane;
-    if (v < nvec) {
-#pragma unroll
-      for (int e = 0; e < EPV; e += 2) {
-        float m0, m1;
-        rng_keep2(ebase + (uint64_t)v * EPV + e, k0, k1, thresh, m0, m1);
-        bits |= (m0 != 0.f ? 1u : 0u) << (j * EPV + e);
-        bits |= (m1 != 0.f ? 1u : 0u) << (j * EPV + e + 1);
-      }
-    }
-  }
-  return bits;
-}
-
-// The 4 waves' register rows of EL floats per lane, summed in a fixed order into dst[c]: waves 1..3 pass theirs through
-// LDS (3 * EL * 64 floats at sm), wave 0 adds (w0 + w1) + (w2 + w3) and stores.  Every thread of the block calls it.
-template <int NVL, int EPV>
-__device__ __forceinline__ void mh_merge_rows(const float* row, float* sm, float* dst, int wave, int lane, int nvec) {
-  constexpr int EL = NVL * EPV;
-  __syncthreads();   // sm may still be read from the previous round
-  if (wave > 0) {
-#pragma unroll
-    for (int i = 0; i < EL; ++i) sm[((wave - 1) * EL + i) * 64 + lane] = row[i];
-  }
-  __syncthreads();
-  if (wave == 0) {
-#pragma unroll
-    for (int j = 0; j < NVL; ++j) {
-      const int v = j * 64 + lane;
-      if (v < nvec) {
-        float o[EPV];
-#pragma unroll
-        for (int e = 0; e < EPV; ++e) {
-          const int i = j * EPV + e;
-          o[e] = (row[i] + sm[(0 * EL + i) * 64 + lane]) + (sm[(1 * EL + i) * 64 + lane] + sm[(2 * EL + i) * 64 + lane]);
-        }
-#pragma unroll
-        for (int e = 0; e < EPV; e += 4)
-          *reinterpret_cast<float4*>(dst + (size_t)v * EPV + e) = make_float4(o[e], o[e + 1], o[e + 2], o[e + 3]);
-      }
-    }
-  }
-}
 
 // --------------------------------------------------------------------------------------------
 // Forward pass.  grid N * S blocks of 256 threads; block (n, s) owns pixels [p_begin, p_end) of batch image n = cache
@@ -104,8 +53,8 @@ __global__ __launch_bounds__(256, 2) void mh_pool_fwd_kernel(const T* __restrict
     for (int i = 0; i < EL; ++i) acc[h][i] = 0.f;
   float asum[HMAX] = {0.f, 0.f, 0.f, 0.f};
   const T* xim = X + (size_t)m1_src_image(n, g) * P * C;
-  const uint4 zero4 = make_uint4(0u, 0u, 0u, 0u);
-  uint4 nxt[NVL];
+  const uint4 zero4 = make_uint4(0u, 0u, 0u, 0u);   // the loader and the dot, inline:
+  uint4 nxt[NVL];                                  // profiles/rowpass_summary.md (timing)
   if (p_begin + wave < p_end) {
 #pragma unroll
     for (int j = 0; j < NVL; ++j) {
@@ -154,7 +103,7 @@ __global__ __launch_bounds__(256, 2) void mh_pool_fwd_kernel(const T* __restrict
     if (lane < H)
       att[((size_t)lane * N + n) * P + p] = lane == 0 ? A[0] : (lane == 1 ? A[1] : (lane == 2 ? A[2] : A[3]));
     if (TRAIN) {
-      const uint32_t bits = mh_keep_bits<NVL, EPV>(((uint64_t)n * P + p) * C, lane, nvec, k0, k1, thresh);
+      const uint32_t bits = row_keep_bits<RngLib, NVL, EPV>(((uint64_t)n * P + p) * C, lane, nvec, k0, k1, thresh);
 #pragma unroll
       for (int i = 0; i < EL; ++i) x[i] = (bits >> i) & 1u ? x[i] : 0.f;
     }
@@ -172,7 +121,7 @@ __global__ __launch_bounds__(256, 2) void mh_pool_fwd_kernel(const T* __restrict
   float* pa = pacc + (size_t)blk * H * C;
 #pragma unroll
   for (int h = 0; h < HMAX; ++h)
-    if (h < H) mh_merge_rows<NVL, EPV>(acc[h], sm, pa + (size_t)h * C, wave, lane, nvec);
+    if (h < H) row_merge4<NVL, EPV>(acc[h], sm, pa + (size_t)h * C, wave, lane, nvec);
   if (lane == 0) {
 #pragma unroll
     for (int h = 0; h < HMAX; ++h) sm_stat[wave][h] = asum[h];
@@ -180,7 +129,7 @@ __global__ __launch_bounds__(256, 2) void mh_pool_fwd_kernel(const T* __restrict
   __syncthreads();
   if (threadIdx.x < HMAX) {
     const int h = threadIdx.x;
-    pstat[(size_t)blk * 4 + h] = (sm_stat[0][h] + sm_stat[1][h]) + (sm_stat[2][h] + sm_stat[3][h]);
+    pstat[(size_t)blk * 4 + h] = row_stat_merge4(sm_stat, h);
   }
 }
 
@@ -211,10 +160,7 @@ __global__ __launch_bounds__(256) void mh_finalize_fwd_kernel(const float* __res
 // grid.z (the forms of apa_m1_small.hip: lane (r, kq) = (lane & 15, lane >> 4) supplies A[row r][k = kq] and
 // B[k = kq][column r] of a 16 x 4 by 4 x 16 step and holds D[row 4 kq + reg][column r]; fixed summation order).  A wave
 // owns MT 16-row tiles that share its B operand.
-__device__ __forceinline__ f32x4 mh_mfma(float a, float b, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
-}
-
+//
 // logits[h,n,k] = sum_c z[h,n,c] Wt[h,c,k] + abar[h,n] bt[h,k].  grid (ceil(K / 16), ceil(N / (16 MT)), H), LW waves per
 // block: wave w multiplies the 4-channel groups [w (C/4) / LW, (w + 1) (C/4) / LW) of MT image tiles by one 16-column
 // tile of Wt, wave 0 adds the LW partial tiles in wave order and the bias term.  hs: rows between two heads of `logits`
@@ -248,12 +194,12 @@ __global__ __launch_bounds__(64 * LW) void mh_logits_kernel(const float* __restr
 #pragma unroll
     for (int u = 0; u < 4; ++u)
 #pragma unroll
-      for (int t = 0; t < MT; ++t) acc[t] = mh_mfma(a[u][t], b[u], acc[t]);
+      for (int t = 0; t < MT; ++t) acc[t] = mfma16(a[u][t], b[u], acc[t]);
   }
   for (; g < g1; ++g) {
     const float b = w[(size_t)g * 4 * K];
 #pragma unroll
-    for (int t = 0; t < MT; ++t) acc[t] = mh_mfma(zr[t][g * 4], b, acc[t]);
+    for (int t = 0; t < MT; ++t) acc[t] = mfma16(zr[t][g * 4], b, acc[t]);
   }
   if (wave > 0) {
 #pragma unroll
@@ -349,7 +295,7 @@ __global__ __launch_bounds__(256) void mh_dz_kernel(const float* __restrict__ G,
 #pragma unroll
     for (int e = 0; e < 4; ++e)
 #pragma unroll
-      for (int t = 0; t < MT; ++t) acc[t] = mh_mfma(a[t][e], b[e], acc[t]);
+      for (int t = 0; t < MT; ++t) acc[t] = mfma16(a[t][e], b[e], acc[t]);
   }
   if (kb < K) {
 #pragma unroll
@@ -357,7 +303,7 @@ __global__ __launch_bounds__(256) void mh_dz_kernel(const float* __restrict__ G,
       const bool in = kb + 4 * kq + e < K;
       const float b = in ? w[kb + e] : 0.f;
 #pragma unroll
-      for (int t = 0; t < MT; ++t) acc[t] = mh_mfma(in ? gr[t][kb + e] : 0.f, b, acc[t]);
+      for (int t = 0; t < MT; ++t) acc[t] = mfma16(in ? gr[t][kb + e] : 0.f, b, acc[t]);
     }
   }
   const int c = c0 + r;
@@ -402,7 +348,7 @@ __global__ __launch_bounds__(256) void mh_dwt_kernel(const float* __restrict__ z
       a[t] = in ? v : 0.f;
     }
 #pragma unroll
-    for (int t = 0; t < WT; ++t) acc[t] = mh_mfma(a[t], b, acc[t]);
+    for (int t = 0; t < WT; ++t) acc[t] = mfma16(a[t], b, acc[t]);
   };
   int nb = 0;
   for (; nb + 16 <= N; nb += 16) {
@@ -448,15 +394,10 @@ __global__ __launch_bounds__(256, 2) void mh_bwd_main_kernel(const T* __restrict
   // this wave's pixels p_begin + wave + 4 i, i = cnt - 1 .. 0
   const int cnt = p_begin + wave < p_end ? (p_end - p_begin - wave + 3) / 4 : 0;
   const T* xim = X + (size_t)m1_src_image(n, g) * P * C;
-  const uint4 zero4 = make_uint4(0u, 0u, 0u, 0u);
   uint4 nxt[NVL];
   if (cnt > 0) {
     const int p = p_begin + wave + 4 * (cnt - 1);
-#pragma unroll
-    for (int j = 0; j < NVL; ++j) {
-      const int v = j * 64 + lane;
-      nxt[j] = v < nvec ? ld16(xim + (size_t)p * C + (size_t)v * EPV) : zero4;
-    }
+    row_load<T, NVL>(nxt, xim + (size_t)p * C, lane, nvec);
   }
   float sn[HMAX];   // G[h,n,:] . bt[h,:], the bias' share of dA (mh_dz_kernel)
 #pragma unroll
@@ -478,18 +419,14 @@ __global__ __launch_bounds__(256, 2) void mh_bwd_main_kernel(const T* __restrict
 #pragma unroll
     for (int j = 0; j < NVL; ++j) Vec<T>::unpack(nxt[j], x + j * EPV);
     if (it > 0) {   // the next row travels while this one is consumed
-#pragma unroll
-      for (int j = 0; j < NVL; ++j) {
-        const int v = j * 64 + lane;
-        nxt[j] = v < nvec ? ld16(xim + (size_t)(p - 4) * C + (size_t)v * EPV) : zero4;
-      }
+      row_load<T, NVL>(nxt, xim + (size_t)(p - 4) * C, lane, nvec);
     }
     uint32_t bits = 0xFFFFFFFFu;
-    if (TRAIN) bits = mh_keep_bits<NVL, EPV>(((uint64_t)n * P + p) * C, lane, nvec, k0, k1, thresh);
+    if (TRAIN) bits = row_keep_bits<RngLib, NVL, EPV>(((uint64_t)n * P + p) * C, lane, nvec, k0, k1, thresh);
 #pragma unroll
     for (int h = 0; h < HMAX; ++h) {
       if (h < H) {
-        float d = 0.f;
+        float d = 0.f;   // row_dot over the kept elements, inline: as a routine it spills (profiles/rowpass_summary.md)
 #pragma unroll
         for (int j = 0; j < NVL; ++j) {
 #pragma unroll
@@ -517,7 +454,7 @@ __global__ __launch_bounds__(256, 2) void mh_bwd_main_kernel(const T* __restrict
   float* pg = pgrad + (size_t)blk * ld;
 #pragma unroll
   for (int h = 0; h < HMAX; ++h)
-    if (h < H) mh_merge_rows<NVL, EPV>(dwa[h], sm_dz, pg + (size_t)h * C, wave, lane, nvec);
+    if (h < H) row_merge4<NVL, EPV>(dwa[h], sm_dz, pg + (size_t)h * C, wave, lane, nvec);
   if (lane == 0) {
 #pragma unroll
     for (int h = 0; h < HMAX; ++h) sm_stat[wave][h] = dba[h];
@@ -525,7 +462,7 @@ __global__ __launch_bounds__(256, 2) void mh_bwd_main_kernel(const T* __restrict
   __syncthreads();
   if ((int)threadIdx.x < HMAX) {
     const int h = threadIdx.x;
-    pg[(size_t)H * C + h] = (sm_stat[0][h] + sm_stat[1][h]) + (sm_stat[2][h] + sm_stat[3][h]);   // (h >= H: zeros)
+    pg[(size_t)H * C + h] = row_stat_merge4(sm_stat, h);   // (h >= H: zeros)
   }
 }
 
@@ -550,15 +487,7 @@ __global__ __launch_bounds__(256) void mh_scores_kernel(const float* __restrict_
       const float lv = mh_softmax_row(row, K, labels ? (int)labels[n] : -1, prow, nullptr, 0.f, &cand);
       if (lane == 0 && loss) loss[(size_t)h * (1 + N) + 1 + n] = lv;
     } else {
-      float m = -INFINITY;
-      int arg = 0x7fffffff;
-      for (int k = lane; k < K; k += 64) {
-        const float x = row[k];
-        if (x > m) { m = x; arg = k; }
-        prow[k] = 1.0f / (1.0f + expf(-x));
-      }
-      const float mw = wave_max(m);
-      cand = wave_min_i((m == mw) ? arg : 0x7fffffff);
+      cand = wave_first_max<true>(row, K, lane, prow);
     }
     if (lane == 0) pred[(size_t)h * hs + n] = cand;
   }
@@ -573,14 +502,7 @@ __global__ __launch_bounds__(256) void mh_scores_kernel(const float* __restrict_
   if (!fused_pred) return;
   __syncthreads();
   if (wave == 0) {
-    float m = -INFINITY;
-    int arg = 0x7fffffff;
-    for (int k = lane; k < K; k += 64) {
-      const float x = fused_probs[(size_t)n * K + k];
-      if (x > m) { m = x; arg = k; }
-    }
-    const float mw = wave_max(m);
-    const int cand = wave_min_i((m == mw) ? arg : 0x7fffffff);
+    const int cand = wave_first_max<false>(fused_probs + (size_t)n * K, K, lane, nullptr);
     if (lane == 0) fused_pred[n] = cand;
   }
 }
@@ -595,7 +517,6 @@ struct HeadSegs {
 };
 __global__ __launch_bounds__(256) void mh_momentum_sgd_kernel(HeadSegs s, const float* __restrict__ grad,
                                                               float* __restrict__ acc, int H, float gscale) {
-  typedef float f4v __attribute__((ext_vector_type(4), aligned(4)));
   const int sg = blockIdx.y, h = blockIdx.z;
   const size_t n = (s.off[sg + 1] - s.off[sg]) / (size_t)H, o = s.off[sg] + (size_t)h * n;
   float* __restrict__ w = s.w[sg] + (size_t)h * n;
@@ -604,22 +525,16 @@ __global__ __launch_bounds__(256) void mh_momentum_sgd_kernel(HeadSegs s, const 
   const float wd = s.wd[sg][h], lr = s.lr[h], momentum = s.momentum[h];
   const size_t nv = n / 4;
   for (size_t v = (size_t)blockIdx.x * 256 + threadIdx.x; v < nv; v += (size_t)gridDim.x * 256) {
-    f4v wv = *reinterpret_cast<const f4v*>(w + v * 4);
-    const f4v gv = *reinterpret_cast<const f4v*>(g + v * 4);
-    f4v av = *reinterpret_cast<const f4v*>(a + v * 4);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      av[e] = fmaf(momentum, av[e], fmaf(wd, wv[e], gv[e] * gscale));
-      wv[e] = fmaf(-lr, av[e], wv[e]);
-    }
-    *reinterpret_cast<f4v*>(a + v * 4) = av;
-    *reinterpret_cast<f4v*>(w + v * 4) = wv;
+    f4u wv = *reinterpret_cast<const f4u*>(w + v * 4);
+    const f4u gv = *reinterpret_cast<const f4u*>(g + v * 4);
+    f4u av = *reinterpret_cast<const f4u*>(a + v * 4);
+    momentum_sgd_update4(av, wv, gv, wd, lr, momentum, gscale);
+    *reinterpret_cast<f4u*>(a + v * 4) = av;
+    *reinterpret_cast<f4u*>(w + v * 4) = wv;
   }
   if (blockIdx.x == 0) {
     for (size_t i = nv * 4 + threadIdx.x; i < n; i += 256) {
-      const float av = fmaf(momentum, a[i], fmaf(wd, w[i], g[i] * gscale));
-      a[i] = av;
-      w[i] = fmaf(-lr, av, w[i]);
+      momentum_sgd_update(a[i], w[i], g[i], wd, lr, momentum, gscale);
     }
   }
 }
@@ -667,13 +582,24 @@ struct MhStep {
 
 #define MH_REFUSE(code, ...) do { set_error(__VA_ARGS__); return code; } while (0)
 
-// rules 1 .. 8 of the header, in its order; `index`: the index (a step) or the order (an epoch)
-int mh_check(const MhStep& a, const int32_t* index, const char* index_name, size_t ws_need_extra) {
+int mh_check_heads(const char* who, int H) {
+  if (H < 1 || H > APA_HEADS_MAX)
+    MH_REFUSE(APA_ERR_INVALID_ARG, "%s: H = %d outside 1 .. APA_HEADS_MAX (%d)", who, H, APA_HEADS_MAX);
+  return APA_OK;
+}
+
+// rules 1 .. 8 of the header, in its order; `index`: the index (a step) or the order (an epoch).  epoch_rule(need): what
+// an epoch checks behind rules 1 and 2 and in front of the rest (H, its count rule, the optimiser's checks), with cache,
+// heads and index at hand; need: workspace bytes it asks for beyond the step's own plan.  A step has none.
+template <typename Rule>
+int mh_check(const MhStep& a, const int32_t* index, const char* index_name, Rule&& epoch_rule) {
   const char* who = a.who;
   if (!a.cache) MH_REFUSE(APA_ERR_INVALID_ARG, "%s: cache is NULL", who);
   if (!a.heads) MH_REFUSE(APA_ERR_INVALID_ARG, "%s: heads is NULL", who);
   if (!index) MH_REFUSE(APA_ERR_INVALID_ARG, "%s: %s is NULL", who, index_name);
   const apa_multihead& hd = *a.heads;
+  size_t ws_need_extra = 0;
+  if (const int rc = epoch_rule(ws_need_extra)) return rc;
   const struct { const void* p; const char* name; bool need; } ptrs[] = {
       {hd.Wa, "heads->Wa", true}, {hd.ba, "heads->ba", true}, {hd.Wt, "heads->Wt", true}, {hd.bt, "heads->bt", true},
       {a.X, "X", true}, {a.labels, "labels", a.train || a.loss != nullptr}, {a.logits, "logits", true},
@@ -683,8 +609,7 @@ int mh_check(const MhStep& a, const int32_t* index, const char* index_name, size
       {a.fused_probs, "fused_probs", !a.train && a.fused_pred != nullptr}, {a.ws, "ws", true}};
   for (const auto& q : ptrs)
     if (q.need && !q.p) MH_REFUSE(APA_ERR_INVALID_ARG, "%s: %s is NULL", who, q.name);
-  if (hd.H < 1 || hd.H > APA_HEADS_MAX)
-    MH_REFUSE(APA_ERR_INVALID_ARG, "%s: H = %d outside 1 .. APA_HEADS_MAX (%d)", who, hd.H, APA_HEADS_MAX);
+  if (const int rc = mh_check_heads(who, hd.H)) return rc;
   if (a.N < 1 || a.P < 1 || a.C < 1 || a.K < 1 || a.cache->cache_images < 1)
     MH_REFUSE(APA_ERR_INVALID_ARG, "%s: non-positive size (N=%d P=%d C=%d K=%d cache_images=%d)", who, a.N, a.P, a.C, a.K,
               a.cache->cache_images);
@@ -721,32 +646,32 @@ int mh_check(const MhStep& a, const int32_t* index, const char* index_name, size
   return APA_OK;
 }
 
+// what both streaming passes of a step are launched with
+struct MhPass { bool drop; int act; float inv_keep; uint32_t thresh; M1Gather g; };
+
 template <typename T, int NVL>
-void mh_launch_fwd(const MhStep& a, const MhPlan& pl, const M1Gather& g, bool drop, uint32_t thresh, hipStream_t st) {
+void mh_launch_fwd(const MhStep& a, const MhPlan& pl, const MhPass& ps, hipStream_t st) {
   char* w = static_cast<char*>(a.ws);
   float* pacc = reinterpret_cast<float*>(w + pl.off_pacc);
   float* pstat = reinterpret_cast<float*>(w + pl.off_pstat);
-  const int act = (a.flags & APA_FLAG_RELU_ATT) ? M1_ACT_RELU : M1_ACT_ID;
-  const float inv_keep = drop ? 1.0f / a.keep_prob : 1.0f;
   auto go = [&](auto kernel) {
     launch_ev(kernel, dim3(pl.nblk), dim3(256), 0, st, a.hk.fwd0, a.hk.fwd1, static_cast<const T*>(a.X), a.heads->Wa,
-              a.heads->ba, a.att, pacc, pstat, a.N, a.P, pl.S, a.C, a.heads->H, act, inv_keep, thresh, a.seed, a.offset, g);
+              a.heads->ba, a.att, pacc, pstat, a.N, a.P, pl.S, a.C, a.heads->H, ps.act, ps.inv_keep, ps.thresh, a.seed,
+              a.offset, ps.g);
   };
-  if (drop) go(mh_pool_fwd_kernel<T, NVL, true>); else go(mh_pool_fwd_kernel<T, NVL, false>);
+  if (ps.drop) go(mh_pool_fwd_kernel<T, NVL, true>); else go(mh_pool_fwd_kernel<T, NVL, false>);
 }
 
 template <typename T, int NVL>
-void mh_launch_bwd(const MhStep& a, const MhPlan& pl, const M1Gather& g, bool drop, uint32_t thresh, hipStream_t st) {
+void mh_launch_bwd(const MhStep& a, const MhPlan& pl, const MhPass& ps, hipStream_t st) {
   char* w = static_cast<char*>(a.ws);
-  const int act = (a.flags & APA_FLAG_RELU_ATT) ? M1_ACT_RELU : M1_ACT_ID;
-  const float inv_keep = drop ? 1.0f / a.keep_prob : 1.0f;
   auto go = [&](auto kernel) {
     launch_ev(kernel, dim3(pl.nblk), dim3(256), 0, st, a.hk.bwd0, a.hk.bwd1, static_cast<const T*>(a.X),
               static_cast<const float*>(a.att), reinterpret_cast<const float*>(w + pl.off_dz),
               reinterpret_cast<const float*>(w + pl.off_sn), reinterpret_cast<float*>(w + pl.off_pgrad), a.N, a.P, pl.S, a.C,
-              a.heads->H, act, inv_keep, thresh, a.seed, a.offset, g);
+              a.heads->H, ps.act, ps.inv_keep, ps.thresh, a.seed, a.offset, ps.g);
   };
-  if (drop) go(mh_bwd_main_kernel<T, NVL, true>); else go(mh_bwd_main_kernel<T, NVL, false>);
+  if (ps.drop) go(mh_bwd_main_kernel<T, NVL, true>); else go(mh_bwd_main_kernel<T, NVL, false>);
 }
 
 // the launches of one step; everything was checked
@@ -755,23 +680,20 @@ int mh_run(const MhStep& a, const int32_t* index, hipStream_t st) {
   const int H = hd.H, N = a.N, P = a.P, C = a.C, K = a.K;
   const MhPlan pl = mh_plan(H, N, P, C);
   char* w = static_cast<char*>(a.ws);
-  const bool drop = a.train && (a.flags & APA_FLAG_TRAIN);
-  const uint32_t thresh = drop ? keep_thresh(a.keep_prob) : 0u;
-  M1Gather g;
-  g.index = index; g.T = a.cache->cache_images; g.status = a.cache->status;
+  MhPass ps;
+  ps.drop = a.train && (a.flags & APA_FLAG_TRAIN);
+  ps.act = (a.flags & APA_FLAG_RELU_ATT) ? M1_ACT_RELU : M1_ACT_ID;
+  ps.inv_keep = ps.drop ? 1.0f / a.keep_prob : 1.0f;
+  ps.thresh = ps.drop ? keep_thresh(a.keep_prob) : 0u;
+  ps.g.index = index; ps.g.T = a.cache->cache_images; ps.g.status = a.cache->status;
   const int64_t* labels = a.labels;
-  g.labels = nullptr; g.labels_out = nullptr;
+  ps.g.labels = nullptr; ps.g.labels_out = nullptr;
   if (a.cache->labels_cached && a.labels) {
-    g.labels = a.labels;
-    g.labels_out = reinterpret_cast<int64_t*>(w + pl.off_labels);
-    labels = g.labels_out;
+    ps.g.labels = a.labels;
+    ps.g.labels_out = reinterpret_cast<int64_t*>(w + pl.off_labels);
+    labels = ps.g.labels_out;
   }
-  const int nvl = m1r_vectors_per_lane(C, a.dtype);
-  if (a.dtype == APA_DTYPE_F32) {
-    if (nvl == 2) mh_launch_fwd<float, 2>(a, pl, g, drop, thresh, st); else mh_launch_fwd<float, 8>(a, pl, g, drop, thresh, st);
-  } else {
-    if (nvl == 1) mh_launch_fwd<bf16_t, 1>(a, pl, g, drop, thresh, st); else mh_launch_fwd<bf16_t, 4>(a, pl, g, drop, thresh, st);
-  }
+  row_instance(C, a.dtype, [&](auto t, auto nvl) { mh_launch_fwd<decltype(t), decltype(nvl)::value>(a, pl, ps, st); });
   APA_LAUNCH_CHECK("mh_pool_fwd_kernel");
   hipLaunchKernelGGL(mh_finalize_fwd_kernel, dim3(N, (C / 4 + 255) / 256, H), dim3(256), 0, st,
                      reinterpret_cast<const float*>(w + pl.off_pacc), reinterpret_cast<const float*>(w + pl.off_pstat), N, P,
@@ -819,11 +741,7 @@ int mh_run(const MhStep& a, const int32_t* index, hipStream_t st) {
                      static_cast<const float*>(a.zsave), static_cast<const float*>(a.abar), static_cast<const float*>(a.G),
                      a.dWt, a.dbt, N, C, K);
   APA_LAUNCH_CHECK("mh_dwt_kernel");
-  if (a.dtype == APA_DTYPE_F32) {
-    if (nvl == 2) mh_launch_bwd<float, 2>(a, pl, g, drop, thresh, st); else mh_launch_bwd<float, 8>(a, pl, g, drop, thresh, st);
-  } else {
-    if (nvl == 1) mh_launch_bwd<bf16_t, 1>(a, pl, g, drop, thresh, st); else mh_launch_bwd<bf16_t, 4>(a, pl, g, drop, thresh, st);
-  }
+  row_instance(C, a.dtype, [&](auto t, auto nvl) { mh_launch_bwd<decltype(t), decltype(nvl)::value>(a, pl, ps, st); });
   APA_LAUNCH_CHECK("mh_bwd_main_kernel");
   ColsumArgs cs;   // [nblk][H C + 4]: the H dWa rows, then the H dba partials as a second section
   cs.pdwa = reinterpret_cast<const float*>(w + pl.off_pgrad);
@@ -834,7 +752,7 @@ int mh_run(const MhStep& a, const int32_t* index, hipStream_t st) {
 
 int sgd_heads_check(const char* who, int H, int nseg, float* const* weights, const size_t* sizes, const float* weight_decay,
                     const float* grad_flat, float* acc_flat, const float* lr, const float* momentum) {
-  if (H < 1 || H > APA_HEADS_MAX) MH_REFUSE(APA_ERR_INVALID_ARG, "%s: H = %d outside 1 .. APA_HEADS_MAX (%d)", who, H, APA_HEADS_MAX);
+  if (const int rc = mh_check_heads(who, H)) return rc;
   if (nseg <= 0 || nseg > APA_SGD_MAX_SEGMENTS || !weights || !sizes || !weight_decay || !grad_flat || !acc_flat || !lr ||
       !momentum)
     MH_REFUSE(APA_ERR_INVALID_ARG, "%s: bad arguments (nseg=%d, max %d)", who, nseg, APA_SGD_MAX_SEGMENTS);
@@ -884,41 +802,65 @@ extern "C" size_t apa_multihead_workspace_bytes(int H, int N, int P, int C, int 
   return mh_plan(H, N, P, C).total;
 }
 
-extern "C" int apa_multihead_train_step_cached(const apa_feature_cache* cache, const apa_hooks* hooks,
-                                               const apa_multihead* heads, const void* X, const int64_t* labels,
-                                               float loss_wt, float grad_scale, float* logits, float* att, float* zsave,
-                                               float* abar, float* loss, float* G, float* dWa, float* dba, float* dWt,
-                                               float* dbt, void* ws, size_t ws_bytes, int N, int P, int C, int K,
-                                               unsigned flags, float keep_prob, uint64_t seed, uint64_t offset, int dtype,
-                                               void* stream) {
+namespace {
+// A direction's flat argument list as the step it describes (hs = N: an evaluation epoch spaces its heads wider)
+MhStep mh_train_args(const char* who, const apa_feature_cache* cache, const apa_hooks* hooks, const apa_multihead*
+                     heads, const void* X, const int64_t* labels, float loss_wt, float grad_scale, float* logits, float*
+                     att, float* zsave, float* abar, float* loss, float* G, float* dWa, float* dba, float* dWt, float*
+                     dbt, void* ws, size_t ws_bytes, int N, int P, int C, int K, unsigned flags, float keep_prob,
+                     uint64_t seed, uint64_t offset, int dtype) {
   MhStep a = {};
-  a.who = "apa_multihead_train_step_cached";
+  a.who = who;
   a.cache = cache; a.heads = heads; a.X = X; a.labels = labels;
   a.logits = logits; a.att = att; a.zsave = zsave; a.abar = abar; a.loss = loss; a.G = G;
   a.dWa = dWa; a.dba = dba; a.dWt = dWt; a.dbt = dbt; a.ws = ws; a.ws_bytes = ws_bytes;
   a.N = N; a.P = P; a.C = C; a.K = K; a.flags = flags; a.keep_prob = keep_prob; a.seed = seed; a.offset = offset;
   a.dtype = dtype; a.train = true; a.loss_wt = loss_wt; a.grad_scale = grad_scale; a.hs = (size_t)(N > 0 ? N : 0);
   a.hk = Hooks(hooks);
-  const int rc = mh_check(a, cache ? cache->index : nullptr, "cache->index", 0);
-  if (rc != APA_OK) return rc;
-  return mh_run(a, cache->index, static_cast<hipStream_t>(stream));
+  return a;
 }
 
-extern "C" int apa_multihead_eval_step_cached(const apa_feature_cache* cache, const apa_multihead* heads, int scores_kind,
-                                              const void* X, const int64_t* labels, float* logits, float* att,
-                                              float* zsave, float* abar, float* loss, float* probs, int64_t* pred,
-                                              float* fused_probs, int64_t* fused_pred, void* ws, size_t ws_bytes, int N,
-                                              int P, int C, int K, unsigned flags, int dtype, void* stream) {
+MhStep mh_eval_args(const char* who, const apa_feature_cache* cache, const apa_multihead* heads, int scores_kind, const
+                    void* X, const int64_t* labels, float* logits, float* att, float* zsave, float* abar, float* loss,
+                    float* probs, int64_t* pred, float* fused_probs, int64_t* fused_pred, void* ws, size_t ws_bytes, int
+                    N, int P, int C, int K, unsigned flags, int dtype) {
   MhStep a = {};
-  a.who = "apa_multihead_eval_step_cached";
+  a.who = who;
   a.cache = cache; a.heads = heads; a.X = X; a.labels = labels;
   a.logits = logits; a.att = att; a.zsave = zsave; a.abar = abar; a.loss = loss;
-  a.probs = probs; a.pred = pred; a.fused_probs = fused_probs; a.fused_pred = fused_pred; a.ws = ws; a.ws_bytes = ws_bytes;
-  a.N = N; a.P = P; a.C = C; a.K = K; a.flags = flags & ~APA_FLAG_TRAIN; a.keep_prob = 1.f; a.dtype = dtype;
-  a.train = false; a.scores_kind = scores_kind; a.hs = (size_t)(N > 0 ? N : 0);
-  const int rc = mh_check(a, cache ? cache->index : nullptr, "cache->index", 0);
-  if (rc != APA_OK) return rc;
-  return mh_run(a, cache->index, static_cast<hipStream_t>(stream));
+  a.probs = probs; a.pred = pred; a.fused_probs = fused_probs; a.fused_pred = fused_pred;
+  a.ws = ws; a.ws_bytes = ws_bytes; a.N = N; a.P = P; a.C = C; a.K = K; a.flags = flags & ~APA_FLAG_TRAIN;
+  a.keep_prob = 1.f; a.dtype = dtype; a.train = false; a.scores_kind = scores_kind; a.hs = (size_t)(N > 0 ? N : 0);
+  return a;
+}
+
+int mh_step(const MhStep& a, void* stream) {
+  const int32_t* index = a.cache ? a.cache->index : nullptr;
+  const int rc = mh_check(a, index, "cache->index", [](size_t&) { return APA_OK; });
+  return rc != APA_OK ? rc : mh_run(a, index, static_cast<hipStream_t>(stream));
+}
+}  // namespace
+
+extern "C" int apa_multihead_train_step_cached(const apa_feature_cache* cache, const apa_hooks* hooks, const
+                                               apa_multihead* heads, const void* X, const int64_t* labels, float
+                                               loss_wt, float grad_scale, float* logits, float* att, float* zsave,
+                                               float* abar, float* loss, float* G, float* dWa, float* dba, float* dWt,
+                                               float* dbt, void* ws, size_t ws_bytes, int N, int P, int C, int K,
+                                               unsigned flags, float keep_prob, uint64_t seed, uint64_t offset, int
+                                               dtype, void* stream) {
+  return mh_step(mh_train_args("apa_multihead_train_step_cached", cache, hooks, heads, X, labels, loss_wt, grad_scale,
+                               logits, att, zsave, abar, loss, G, dWa, dba, dWt, dbt, ws, ws_bytes, N, P, C, K, flags,
+                               keep_prob, seed, offset, dtype), stream);
+}
+
+extern "C" int apa_multihead_eval_step_cached(const apa_feature_cache* cache, const apa_multihead* heads, int
+                                              scores_kind, const void* X, const int64_t* labels, float* logits, float*
+                                              att, float* zsave, float* abar, float* loss, float* probs, int64_t* pred,
+                                              float* fused_probs, int64_t* fused_pred, void* ws, size_t ws_bytes, int N,
+                                              int P, int C, int K, unsigned flags, int dtype, void* stream) {
+  return mh_step(mh_eval_args("apa_multihead_eval_step_cached", cache, heads, scores_kind, X, labels, logits, att,
+                              zsave, abar, loss, probs, pred, fused_probs, fused_pred, ws, ws_bytes, N, P, C, K, flags,
+                              dtype), stream);
 }
 
 extern "C" int apa_momentum_sgd_step_heads(int H, int nseg, float* const* weights, const size_t* sizes,
@@ -931,38 +873,29 @@ extern "C" int apa_momentum_sgd_step_heads(int H, int nseg, float* const* weight
                        static_cast<hipStream_t>(stream));
 }
 
-extern "C" int apa_multihead_train_epoch_cached(const apa_epoch* ep, const apa_multihead_sgd* opt,
-                                                const apa_feature_cache* cache, const apa_hooks* hooks,
-                                                const apa_multihead* heads, const void* X, const int64_t* labels,
-                                                float loss_wt, float grad_scale, float* logits, float* att, float* zsave,
-                                                float* abar, float* loss, float* G, float* dWa, float* dba, float* dWt,
-                                                float* dbt, void* ws, size_t ws_bytes, int N, int P, int C, int K,
-                                                unsigned flags, float keep_prob, uint64_t seed, uint64_t offset, int dtype,
-                                                void* stream) {
+extern "C" int apa_multihead_train_epoch_cached(const apa_epoch* ep, const apa_multihead_sgd* opt, const
+                                                apa_feature_cache* cache, const apa_hooks* hooks, const apa_multihead*
+                                                heads, const void* X, const int64_t* labels, float loss_wt, float
+                                                grad_scale, float* logits, float* att, float* zsave, float* abar, float*
+                                                loss, float* G, float* dWa, float* dba, float* dWt, float* dbt, void*
+                                                ws, size_t ws_bytes, int N, int P, int C, int K, unsigned flags, float
+                                                keep_prob, uint64_t seed, uint64_t offset, int dtype, void* stream) {
   const char* who = "apa_multihead_train_epoch_cached";
   if (!ep) MH_REFUSE(APA_ERR_INVALID_ARG, "%s: ep is NULL", who);
   if (!opt) MH_REFUSE(APA_ERR_INVALID_ARG, "%s: opt is NULL", who);
   if (!opt->lr) MH_REFUSE(APA_ERR_INVALID_ARG, "%s: opt->lr is NULL", who);
-  MhStep a = {};
-  a.who = who;
-  a.cache = cache; a.heads = heads; a.X = X; a.labels = labels;
-  a.logits = logits; a.att = att; a.zsave = zsave; a.abar = abar; a.loss = loss; a.G = G;
-  a.dWa = dWa; a.dba = dba; a.dWt = dWt; a.dbt = dbt; a.ws = ws; a.ws_bytes = ws_bytes;
-  a.N = N; a.P = P; a.C = C; a.K = K; a.flags = flags; a.keep_prob = keep_prob; a.seed = seed; a.offset = offset;
-  a.dtype = dtype; a.train = true; a.loss_wt = loss_wt; a.grad_scale = grad_scale; a.hs = (size_t)(N > 0 ? N : 0);
-  a.hk = Hooks(hooks);
-  // rules 1 and 2, then the count rules in the place of rule 3's sizes, then the rest
-  if (!cache) MH_REFUSE(APA_ERR_INVALID_ARG, "%s: cache is NULL", who);
-  if (!heads) MH_REFUSE(APA_ERR_INVALID_ARG, "%s: heads is NULL", who);
-  if (!ep->order) MH_REFUSE(APA_ERR_INVALID_ARG, "%s: ep->order is NULL", who);
-  if (heads->H < 1 || heads->H > APA_HEADS_MAX)
-    MH_REFUSE(APA_ERR_INVALID_ARG, "%s: H = %d outside 1 .. APA_HEADS_MAX (%d)", who, heads->H, APA_HEADS_MAX);
-  if (N < 1 || ep->count < N || ep->count % N != 0)
-    MH_REFUSE(APA_ERR_INVALID_ARG, "%s: count = %d is not a positive multiple of N = %d", who, ep->count, N);
-  int rc = sgd_heads_check(who, heads->H, opt->nseg, opt->weights, opt->sizes, opt->weight_decay, opt->grad_flat,
+  const MhStep a = mh_train_args(who, cache, hooks, heads, X, labels, loss_wt, grad_scale, logits, att, zsave, abar,
+                                 loss, G, dWa, dba, dWt, dbt, ws, ws_bytes, N, P, C, K, flags, keep_prob, seed, offset,
+                                 dtype);
+  // rules 1 and 2, then the count rule in the place of rule 3's sizes and the optimiser's checks, then the rest
+  int rc = mh_check(a, ep->order, "ep->order", [&](size_t&) -> int {
+    if (const int r = mh_check_heads(who, heads->H)) return r;
+    if (N < 1 || ep->count < N || ep->count % N != 0)
+      MH_REFUSE(APA_ERR_INVALID_ARG, "%s: count = %d is not a positive multiple of N = %d", who, ep->count, N);
+    return sgd_heads_check(who, heads->H, opt->nseg, opt->weights, opt->sizes, opt->weight_decay, opt->grad_flat,
                            opt->acc_flat, opt->lr, opt->momentum);
+  });
   if (rc != APA_OK) return rc;
-  if ((rc = mh_check(a, ep->order, "ep->order", 0)) != APA_OK) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
   const int steps = ep->count / N, H = heads->H;
   for (int s = 0; s < steps; ++s) {
@@ -978,33 +911,31 @@ extern "C" int apa_multihead_train_epoch_cached(const apa_epoch* ep, const apa_m
   return APA_OK;
 }
 
-extern "C" int apa_multihead_eval_epoch_cached(const apa_epoch* ep, const apa_feature_cache* cache,
-                                               const apa_multihead* heads, int scores_kind, const void* X,
-                                               const int64_t* labels, float* logits, float* att, float* zsave, float* abar,
-                                               float* loss, float* probs, int64_t* pred, float* fused_probs,
-                                               int64_t* fused_pred, void* ws, size_t ws_bytes, int N, int P, int C, int K,
-                                               unsigned flags, int dtype, void* stream) {
+extern "C" int apa_multihead_eval_epoch_cached(const apa_epoch* ep, const apa_feature_cache* cache, const apa_multihead*
+                                               heads, int scores_kind, const void* X, const int64_t* labels, float*
+                                               logits, float* att, float* zsave, float* abar, float* loss, float* probs,
+                                               int64_t* pred, float* fused_probs, int64_t* fused_pred, void* ws, size_t
+                                               ws_bytes, int N, int P, int C, int K, unsigned flags, int dtype, void*
+                                               stream) {
   const char* who = "apa_multihead_eval_epoch_cached";
   if (!ep) MH_REFUSE(APA_ERR_INVALID_ARG, "%s: ep is NULL", who);
-  if (!cache) MH_REFUSE(APA_ERR_INVALID_ARG, "%s: cache is NULL", who);
-  if (!heads) MH_REFUSE(APA_ERR_INVALID_ARG, "%s: heads is NULL", who);
-  if (!ep->order) MH_REFUSE(APA_ERR_INVALID_ARG, "%s: ep->order is NULL", who);
-  if (heads->H < 1 || heads->H > APA_HEADS_MAX)
-    MH_REFUSE(APA_ERR_INVALID_ARG, "%s: H = %d outside 1 .. APA_HEADS_MAX (%d)", who, heads->H, APA_HEADS_MAX);
-  if (N < 1 || ep->count < 1) MH_REFUSE(APA_ERR_INVALID_ARG, "%s: count = %d, N = %d: both must be positive", who, ep->count, N);
-  MhStep a = {};
-  a.who = who;
-  a.cache = cache; a.heads = heads; a.X = X; a.labels = labels;
-  a.logits = logits; a.att = att; a.zsave = zsave; a.abar = abar; a.loss = loss;
-  a.probs = probs; a.pred = pred; a.fused_probs = fused_probs; a.fused_pred = fused_pred; a.ws = ws; a.ws_bytes = ws_bytes;
-  a.N = N; a.P = P; a.C = C; a.K = K; a.flags = flags & ~APA_FLAG_TRAIN; a.keep_prob = 1.f; a.dtype = dtype;
-  a.train = false; a.scores_kind = scores_kind; a.hs = (size_t)ep->count;
-  const int steps = (ep->count + N - 1) / N, last = ep->count - (steps - 1) * N, H = heads->H;
-  // the smaller last batch runs in the same workspace: its plan is checked with the full batch's
-  const size_t need_last = (P >= 1 && C >= 1) ? mh_plan(H, last, P, C).total : 0;
-  int rc = mh_check(a, ep->order, "ep->order", need_last);
+  MhStep a = mh_eval_args(who, cache, heads, scores_kind, X, labels, logits, att, zsave, abar, loss, probs, pred,
+                          fused_probs, fused_pred, ws, ws_bytes, N, P, C, K, flags, dtype);
+  int steps = 0, last = 0;
+  int rc = mh_check(a, ep->order, "ep->order", [&](size_t& need) -> int {
+    if (const int r = mh_check_heads(who, heads->H)) return r;
+    if (N < 1 || ep->count < 1)
+      MH_REFUSE(APA_ERR_INVALID_ARG, "%s: count = %d, N = %d: both must be positive", who, ep->count, N);
+    steps = (ep->count + N - 1) / N;
+    last = ep->count - (steps - 1) * N;
+    // the smaller last batch runs in the same workspace: its plan is checked with the full batch's
+    need = (P >= 1 && C >= 1) ? mh_plan(heads->H, last, P, C).total : 0;
+    return APA_OK;
+  });
   if (rc != APA_OK) return rc;
+  a.hs = (size_t)ep->count;
   hipStream_t st = static_cast<hipStream_t>(stream);
+  const int H = heads->H;
   for (int s = 0; s < steps; ++s) {
     MhStep b = a;
     const size_t r0 = (size_t)s * N;

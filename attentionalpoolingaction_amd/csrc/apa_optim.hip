@@ -40,7 +40,6 @@ template <bool IMG>
 __global__ __launch_bounds__(256) void momentum_sgd_kernel(SgdSegs s, const float* __restrict__ grad,
                                                            float* __restrict__ acc, float lr,
                                                            float momentum, float gscale, SgdImgs im) {
-  typedef float f4u __attribute__((ext_vector_type(4), aligned(4)));
   const int sg = blockIdx.y;
   const size_t o = s.off[sg], n = s.off[sg + 1] - o;
   float* __restrict__ w = s.w[sg];
@@ -53,11 +52,7 @@ __global__ __launch_bounds__(256) void momentum_sgd_kernel(SgdSegs s, const floa
     f4u wv = *reinterpret_cast<const f4u*>(w + v * 4);
     const f4u gv = *reinterpret_cast<const f4u*>(g + v * 4);
     f4u av = *reinterpret_cast<const f4u*>(a + v * 4);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      av[e] = fmaf(momentum, av[e], fmaf(wd, wv[e], gv[e] * gscale));
-      wv[e] = fmaf(-lr, av[e], wv[e]);
-    }
+    momentum_sgd_update4(av, wv, gv, wd, lr, momentum, gscale);
     *reinterpret_cast<f4u*>(a + v * 4) = av;
     *reinterpret_cast<f4u*>(w + v * 4) = wv;
     if (sh) {   // the bf16 operand copy the MFMA products read (pose-head W1): kept current by the update itself
@@ -73,10 +68,8 @@ __global__ __launch_bounds__(256) void momentum_sgd_kernel(SgdSegs s, const floa
   }
   if (blockIdx.x == 0) {
     for (size_t i = nv * 4 + threadIdx.x; i < n; i += 256) {
-      const float av = fmaf(momentum, a[i], fmaf(wd, w[i], g[i] * gscale));
-      a[i] = av;
-      const float wn = fmaf(-lr, av, w[i]);
-      w[i] = wn;
+      momentum_sgd_update(a[i], w[i], g[i], wd, lr, momentum, gscale);
+      const float wn = w[i];
       if (sh) sh[i].v = (uint16_t)f32_to_bf16_bits(wn);
       if constexpr (IMG) {
         const int ni = im.n[sg];
@@ -135,7 +128,6 @@ template <bool DIV>
 // (`out` is NOT __restrict__: with more than APA_ACC_MAX_PARTS parts the running sum in `out` leads the next launch
 // as parts.p[0]; every thread reads its elements of all parts before it writes the same elements of `out`.)
 __global__ __launch_bounds__(256) void accumulate_kernel(AccParts parts, float* out, size_t n, float scale) {
-  typedef float f4u __attribute__((ext_vector_type(4), aligned(4)));
   const size_t nv = n / 4;
   for (size_t v = (size_t)blockIdx.x * 256 + threadIdx.x; v < nv; v += (size_t)gridDim.x * 256) {
     f4u acc = *reinterpret_cast<const f4u*>(parts.p[0] + v * 4);

@@ -710,7 +710,6 @@ __global__ __launch_bounds__(512) void pc_bwd_dw_kernel(
 //     dT / dZ (dbt | dba), and, in the one-call step after a folded forward product, finishes logits and
 //     cross-entropy of the images that START in its rows (pc_row_xent: G never comes from memory).
 // ---------------------------------------------------------------------------------------------
-typedef float f4u __attribute__((ext_vector_type(4), aligned(4)));
 constexpr int DX_ROWS = 128, DX_MAXU = 16, DX_MAXIMG = 5, DX_MLD = 17, DX_WAVES = 8;
 constexpr size_t DX_LDS_REST = DX_ROWS * DX_MLD * 4 + DX_MAXIMG * 64 * 4 + DX_WAVES * 2 * 64 * 4;
 constexpr size_t DX_LDS_BYTES = (size_t)DX_MAXU * 8192 + DX_LDS_REST;   // the most a launch asks for

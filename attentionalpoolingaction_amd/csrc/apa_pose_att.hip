@@ -311,8 +311,8 @@ __global__ __launch_bounds__(64 * CLS_WAVES) void pal_cls_fwd_kernel(const float
           if (kt < KT) {                                   // wave-uniform
             const int k = kt * 16 + (lane & 15);
             const float b = k < K ? wrow[k] : 0.f;
-            acc[t][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0, b, acc[t][0], 0, 0, 0);
-            acc[t][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1, b, acc[t][1], 0, 0, 0);
+            acc[t][0] = mfma16(a0, b, acc[t][0]);
+            acc[t][1] = mfma16(a1, b, acc[t][1]);
           }
         }
       }
@@ -390,8 +390,8 @@ __global__ __launch_bounds__(64 * CB_WAVES) void pal_cls_bwd_kernel(const float*
         const float a0 = s_g[(lane & 15) * ldg + k];
         const float a1 = s_g[(16 + (lane & 15)) * ldg + k];
         const float b = (r < R && k < K) ? wrow[k] : 0.f;
-        d0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a0, b, d0, 0, 0, 0);
-        d1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a1, b, d1, 0, 0, 0);
+        d0 = mfma16(a0, b, d0);
+        d1 = mfma16(a1, b, d1);
       }
       if (r < R) {
 #pragma unroll
@@ -416,7 +416,7 @@ __global__ __launch_bounds__(64 * CB_WAVES) void pal_cls_bwd_kernel(const float*
 #pragma unroll
         for (int s = 0; s < 8; ++s) {
           const float b = s_g[(4 * s + (lane >> 4)) * ldg + kt * 16 + (lane & 15)];
-          acc = __builtin_amdgcn_mfma_f32_16x16x4f32(fa[s], b, acc, 0, 0, 0);
+          acc = mfma16(fa[s], b, acc);
         }
         const int k = kt * 16 + (lane & 15);
         if (k < K) {

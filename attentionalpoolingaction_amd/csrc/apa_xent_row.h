@@ -14,8 +14,6 @@
 
 namespace apa {
 
-typedef float f4u __attribute__((ext_vector_type(4), aligned(4)));   // 16 bytes at any 4-byte aligned address
-
 constexpr int XENT_ROW_MIN_K = 4, XENT_ROW_MAX_K = 1024;   // the half-wave forms; any other K: the stream form
 __host__ __device__ inline bool xent_row_half_wave(int K) { return K >= XENT_ROW_MIN_K && K <= XENT_ROW_MAX_K; }
 // 16-byte vectors per lane of the half wave: ceil(ceil(K / 4) / 32), rounded up to the instantiated 1 / 2 / 4 / 8

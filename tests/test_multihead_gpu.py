@@ -36,7 +36,8 @@ def _dev(inp, dev):
 class _Run(object):
     """The NaN-guarded buffers of one case and the two steps on them (the C entry points, directly)."""
 
-    def __init__(self, c, inp, dev, train=True, scores=cof.APA_SCORES_SOFTMAX, keep=mr.KEEP):
+    def __init__(self, c, inp, dev, train=True, scores=cof.APA_SCORES_SOFTMAX, keep=None):
+        keep = c['keep'] if keep is None else keep
         self.c, self.inp, self.train, self.scores, self.keep = c, inp, train, scores, keep
         self.lib = mh.load_library()
         H, N, P, C, K = c['H'], c['N'], c['P'], c['C'], c['K']
@@ -150,7 +151,7 @@ def test_train_case(gpu, c):
     r = _Run(c, inp, gpu, train=True)
     got = _twice(r)
     with torch.no_grad():
-        mr.check_all(c, inp, got, r.mask)
+        mr.check_all(c, inp, got, r.mask, r.keep)
 
 
 def test_train_case_without_dropout(gpu):
@@ -216,7 +217,8 @@ def _single_head(c, inp, h, dev):
              abar=torch.empty((N,), **f32), loss=torch.empty((1 + N,), **f32), G=torch.empty((N, K), **f32),
              dWa=torch.empty((C,), **f32), dba=torch.empty((1,), **f32), dWt=torch.empty((C, K), **f32),
              dbt=torch.empty((K,), **f32))
-    flags = (cof.APA_FLAG_RELU_ATT if c['relu'] else 0) | cof.APA_FLAG_FROZEN_INPUT | cof.APA_FLAG_TRAIN
+    flags = (cof.APA_FLAG_RELU_ATT if c['relu'] else 0) | cof.APA_FLAG_FROZEN_INPUT
+    flags |= cof.APA_FLAG_TRAIN if c['keep'] < 1.0 else 0
     nb = int(cof.attn_pool_workspace_bytes(N, P, C, C, K, 1, flags))
     ws = torch.empty((nb,), dtype=torch.uint8, device=dev)
     status = torch.zeros((1,), dtype=torch.int32, device=dev)
@@ -228,7 +230,7 @@ def _single_head(c, inp, h, dev):
         ctypes.addressof(fc), None, X, X, Wa.data_ptr(), ba.data_ptr(), Wt.data_ptr(), bt.data_ptr(), labels.data_ptr(),
         1.0, 1.0, o['logits'].data_ptr(), o['att'].data_ptr(), o['zsave'].data_ptr(), o['abar'].data_ptr(),
         o['loss'].data_ptr(), o['G'].data_ptr(), None, None, o['dWa'].data_ptr(), o['dba'].data_ptr(),
-        o['dWt'].data_ptr(), o['dbt'].data_ptr(), ws.data_ptr(), nb, N, P, C, C, K, 1, flags, mr.KEEP, mr.SEED, mr.OFFSET,
+        o['dWt'].data_ptr(), o['dbt'].data_ptr(), ws.data_ptr(), nb, N, P, C, C, K, 1, flags, c['keep'], mr.SEED, mr.OFFSET,
         cof.APA_DTYPE_BF16 if c['bf16'] else cof.APA_DTYPE_F32, gp.stream_ptr())
     assert rc == 0, lib.apa_last_error()
     torch.cuda.synchronize()
